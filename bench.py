@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- JPEG decode Mpixels/sec on a 4:2:0 1080p batch (BASELINE.json's metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A *step* is one pass of the GPU hot path -- de-quantise + 8x8 integer IDCT + h2v2 upsample +
@@ -22,6 +22,11 @@ staging (mjh_decode_memory_fmt) -> H2D.  No environment knob is involved.  Every
 distinct sources by hash against the int16 pipeline (and, on rank 0 at N = 1, byte for byte against the
 reference itself in the cpu_baseline leg), every further image by a device-side comparison with its source.
 
+A plain run (no --full) does only what the headline needs: set up, warm up, time exactly --steps launches, write the outputs
+of the last one if --dump-outputs is given, print the line.  The verification of every image just described, the figure at
+exactly --warmup launches (roofline.*_at_requested_warmup), the IDCT wavefront classes, the host stage, the legs, end to end
+and the CPU baseline run with --full only; the rest of `roofline` comes from the timed steps and is in every line.
+
 `roofline.achieved` keeps the ALGORITHMIC bytes of SURVEY.md 8(d) in the numerator (int16 coefficients,
 12 487 680 B per image); `roofline.traffic` / `hbm_counter_frac` are what the HBM counters saw (fewer bytes:
 compact planes), from the rocprofv3 --pmc passes committed under profiles/ (tools/profile.sh).
@@ -29,10 +34,10 @@ compact planes), from the rocprofv3 --pmc passes committed under profiles/ (tool
 `roofline.idct_wavefront_classes` (and the same per decode leg): fraction of the launch's IDCT wavefronts that took the DC-only /
 2x2 / 4x4 / full transform, counted by one extra untimed launch (mij_batch_count_idct_classes).
 
-N > 1 additionally: every rank runs the end-to-end GPU-walk ring on its slice at the same time with its share of the host
+N > 1 with --full additionally: every rank runs the end-to-end GPU-walk ring on its slice at the same time with its share of the host
 cores (`end_to_end.per_rank` + aggregate), rank 0 times the CPU baseline; control plane on gloo (--control-plane nccl for RCCL).
 
-The one JSON line (rank 0) also carries, all OUTSIDE the timed region and only at N = 1:
+With --full the one JSON line (rank 0) also carries, all OUTSIDE the timed region and only at N = 1:
   legs.prepass          what stands between the host walk and the fused kernel over 1024 DISTINCT slots: nothing for compact
                         staging; H2D into a scratch + k_pack_c8 (timed alone) for int16 staging; frac_including_pack
   legs.int16_planes     the same kernel family on int16 tile-layout planes
@@ -229,6 +234,31 @@ def timed_launches(bt, steps):
     bt.timer_end()
     bt.wait()
     return bt.timer_ms() / steps
+
+
+DUMP_SAMPLE_SLOTS = 16        # images of the batch sampled for --dump-outputs (besides its last one, dumped whole)
+DUMP_SAMPLE_VALUES = 1 << 18  # values per sampled image, the same positions in every one
+
+
+def dump_outputs(bt, count, d):
+    """--dump-outputs: the RGB8 pixels the last launch left in the batch as float32 .npy files under d -- the last image whole
+    (rgb_last_image), and for a fixed seeded choice of images the same fixed seeded positions of each (rgb_sample, with the image and
+    flat byte indices in rgb_sample_slots / rgb_sample_positions).  43 MB at 1080p; -> {name: shape}"""
+    os.makedirs(d, exist_ok=True)
+    rng = np.random.default_rng(20261015)
+    slots = np.sort(rng.choice(count, size=min(DUMP_SAMPLE_SLOTS, count), replace=False))
+    last = bt.fetch(count - 1)
+    pos = np.sort(rng.choice(last.size, size=min(DUMP_SAMPLE_VALUES, last.size), replace=False))
+    arrays = {
+        "rgb_last_image": last.astype(np.float32),
+        "rgb_sample": np.stack([bt.fetch(int(s)).reshape(-1)[pos] for s in slots]).astype(np.float32),
+        "rgb_sample_slots": slots.astype(np.float64),
+        "rgb_sample_positions": pos.astype(np.float64),
+    }
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20, "outputs to dump exceed 64 MB"
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def frac_of(algo_bytes, ms):
@@ -874,12 +904,19 @@ def main():
     ap.add_argument("--settle-ms", type=float, default=25.0,
                     help="the settled figure's warm-up lasts at least this long (more launches than --warmup if need be; the number "
                          "issued is reported as config.warmup_launches_issued): after an idle gap launch durations take "
-                         "~25 ms to settle (power management), whatever W says.  The figure with exactly --warmup launches is "
+                         "~25 ms to settle (power management), whatever W says.  With --full the figure with exactly --warmup launches is "
                          "reported beside it (roofline.frac_at_requested_warmup)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the (untimed-region) end-to-end measurement")
-    ap.add_argument("--no-legs", action="store_true", help="skip the secondary legs (int16 planes, harsh batch, configs 4 and 5, 4:2:2)")
-    ap.add_argument("--legs", default="", help="comma-separated subset of the secondary legs to run (default: all)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: verification of every image against the int16 pipeline, the figure at exactly "
+                         "--warmup launches, IDCT wavefront classes, host stage, the secondary legs, end to end and the CPU baseline "
+                         "(the --no-* / --legs options below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0's RGB8 pixels as float32: its last image whole, "
+                         "a fixed seeded sample of the others) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the (untimed-region) end-to-end measurement")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the secondary legs (int16 planes, harsh batch, configs 4 and 5, 4:2:2)")
+    ap.add_argument("--legs", default="", help="with --full: comma-separated subset of the secondary legs to run (default: all)")
     ap.add_argument("--control-plane", default=os.environ.get("MIJ_CONTROL_PLANE", "gloo"), choices=["gloo", "nccl"],
                     help="N > 1: backend of the barrier / MAX / SUM / all-gather of a few scalars.  gloo by default: the data path has no collective "
                          "(independent images), so nothing is gained by taking RCCL's bring-up into the run; nccl (= RCCL) by flag")
@@ -917,29 +954,33 @@ def main():
     d0 = ica.HostDecoder.probe(datas[0], 3)
     cbytes, obytes = ica.Batch.coef_bytes(d0), ica.Batch.out_bytes(d0)
 
-    # ---- reference pixels of the distinct images: host walk -> int16 planes -> fused kernel
-    ref_batch, _, host_stage_s = resident_batch(ica, ctx, datas, 0, distinct, "int16", cbytes, obytes)
-    ref_batch.launch()
-    ref_batch.wait()
-    assert {ref_batch.slot_path(s) for s in range(distinct)} == {1}, "the fused kernel did not take the batch"
-    src_hash = [ref_batch.hash_out(s) for s in range(distinct)]
-    ref_batch.close()
+    # ---- --full: reference pixels of the distinct images: host walk -> int16 planes -> fused kernel
+    src_hash, host_stage_s = None, None
+    if args.full:
+        ref_batch, _, host_stage_s = resident_batch(ica, ctx, datas, 0, distinct, "int16", cbytes, obytes)
+        ref_batch.launch()
+        ref_batch.wait()
+        assert {ref_batch.slot_path(s) for s in range(distinct)} == {1}, "the fused kernel did not take the batch"
+        src_hash = [ref_batch.hash_out(s) for s in range(distinct)]
+        ref_batch.close()
 
-    # ---- the timed batch: this rank's slice, default plane format, every image verified
+    # ---- the timed batch: this rank's slice, default plane format (with --full: every image verified)
     batch, owners, _ = resident_batch(ica, ctx, datas, lo, n_img, "compact", cbytes, obytes)
     batch.launch()
     batch.wait()
     paths = {batch.slot_path(s) for s in range(n_img)}
     assert paths == {1}, "the fused kernel did not take the batch: %r" % paths
     assert all(batch.slot_coef_bytes(s) == 1 for s in range(min(n_img, 32))), "the batch is not in the default (compact) plane format"
-    n_verified = verify_batch(batch, owners, src_hash)
+    n_verified = verify_batch(batch, owners, src_hash) if args.full else -1
 
-    # ---- (a) exactly --warmup untimed launches, then exactly --steps timed ones: the figure at the requested warm-up
-    cp.barrier()
-    for _ in range(max(0, args.warmup)):
-        batch.launch()
-    batch.wait()
-    ms_requested = timed_launches(batch, args.steps)
+    # ---- (a) --full: exactly --warmup untimed launches, then exactly --steps timed ones: the figure at the requested warm-up
+    ms_requested = -1.0
+    if args.full:
+        cp.barrier()
+        for _ in range(max(0, args.warmup)):
+            batch.launch()
+        batch.wait()
+        ms_requested = timed_launches(batch, args.steps)
 
     # ---- (b) the settled figure: a warm-up of at least --settle-ms directly in front of the timed region;
     # timed region: exactly K steps, barrier + device sync on both sides
@@ -962,11 +1003,12 @@ def main():
     kernel_ms_max = cp.max(kernel_ms)
     ms_requested_max = cp.max(ms_requested)
     per_rank = cp.gather_floats([float(cp.rank), float(lo), float(hi), kernel_ms, ms_requested, float(n_verified)])
+    dumped = dump_outputs(batch, n_img, args.dump_outputs) if (args.dump_outputs and cp.rank == 0) else None
 
-    main_classes = idct_classes(batch) if cp.rank == 0 else None
-    solo = cp.rank == 0 and cp.world == 1
+    main_classes = idct_classes(batch) if (args.full and cp.rank == 0) else None
+    solo = args.full and cp.rank == 0 and cp.world == 1
     gpu_px = [batch.fetch(next(s for s, (kk, src) in enumerate(owners) if kk == k and src is None)) for k in range(distinct)] \
-        if (cp.rank == 0 and not args.no_cpu_baseline) else None
+        if (args.full and cp.rank == 0 and not args.no_cpu_baseline) else None
     # release the timed batch before the legs: 12.8 GB and, more to the point, its stream (a process gets 4 hardware
     # queues; a fifth stream would share one with a batch of the end-to-end ring below and serialise the two)
     batch.close()
@@ -1030,7 +1072,7 @@ def main():
     # runs the GPU-walk ring on its own slice with its share of the host cores, all ranks at the same time (barrier in front); the line
     # carries per-rank and aggregate end-to-end rates, pixels left in HBM and copied to pinned host memory.
     e2e_ranks = None
-    if cp.world > 1 and not args.no_e2e:
+    if args.full and cp.world > 1 and not args.no_e2e:
         local_world = max(1, int(os.environ.get("LOCAL_WORLD_SIZE", str(cp.world))))
         threads = max(1, usable_cores() // local_world)
         n_ring = max(1024, 2 * n_img)
@@ -1051,7 +1093,8 @@ def main():
         ranks = [{"rank": int(r[0]), "images": [int(r[1]), int(r[2])], "kernel_ms_per_launch": round(r[3], 4),
                   "frac": round(frac_of(ALGO_BYTES_PER_IMAGE * (int(r[2]) - int(r[1])), r[3]), 4) if r[3] > 0 else None,
                   "kernel_mpix_s": round((int(r[2]) - int(r[1])) * W * H / r[3] / 1e3, 1) if r[3] > 0 else None,
-                  "kernel_ms_at_requested_warmup": round(r[4], 4), "images_verified": int(r[5])} for r in per_rank]
+                  "kernel_ms_at_requested_warmup": round(r[4], 4) if r[4] >= 0 else None,
+                  "images_verified": int(r[5]) if r[5] >= 0 else None} for r in per_rank]
         roof = {
             "bound": "hbm",
             "achieved": round(achieved, 1),
@@ -1061,8 +1104,8 @@ def main():
             "kernel": "mij::k_fused420<3,false,true>",
             "kernel_ms_per_launch": round(kernel_ms_max, 4),
             "algorithmic_bytes_per_launch": algo_launch,
-            "frac_at_requested_warmup": round(frac_of(algo_launch, ms_requested_max), 4),
-            "kernel_ms_at_requested_warmup": round(ms_requested_max, 4),
+            "frac_at_requested_warmup": round(frac_of(algo_launch, ms_requested_max), 4) if args.full else None,
+            "kernel_ms_at_requested_warmup": round(ms_requested_max, 4) if args.full else None,
             "note": "frac = algorithmic bytes (int16 coefficients + RGB8, SURVEY 8d) / time / 8 TB/s; hbm_counter_frac = bytes the TCC counters saw / "
                     "time / 8 TB/s (fewer: compact planes); at this point the kernel is bound by VALU issue, not by HBM (DESIGN.md 3.1)",
         }
@@ -1101,11 +1144,15 @@ def main():
             },
             "roofline": roof,
             "per_rank": ranks,
-            "host_stage": {
+        }
+        out["config"]["full"] = args.full
+        if dumped is not None:
+            out["config"]["dumped_outputs"] = dumped
+        if host_stage_s is not None:
+            out["host_stage"] = {
                 "huffman_walk_mpix_s_single_thread": round(distinct * W * H / host_stage_s / 1e6, 1),
                 "note": "host entropy stage, 1 thread, writing pinned staging; outside the timed region",
-            },
-        }
+            }
         if legs:
             out["legs"] = legs
         if e2e is not None:
@@ -1123,7 +1170,7 @@ def main():
                 "value_gpu_entropy_with_d2h": round(sum(r[1] for r in good) * W * H / max(r[4] for r in good) / 1e6, 1) if good else None,
                 "ranks_ok": len(good), "per_rank": rows,
             }
-        if cp.rank == 0 and not args.no_cpu_baseline:
+        if args.full and cp.rank == 0 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(datas, gpu_pixels=lambda i: gpu_px[i])
             except Exception as exc:  # noqa: BLE001

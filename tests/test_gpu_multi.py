@@ -91,7 +91,7 @@ def test_bench_two_ranks_share_one_gpu(tmp_path):
         e = dict(env)
         e.update({"RANK": str(r), "LOCAL_RANK": str(r)})
         procs.append(subprocess.Popen([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--total-images", "96",
-                                       "--distinct", "4", "--no-cpu-baseline"], env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+                                       "--distinct", "4", "--no-cpu-baseline", "--full"], env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []
     for p in procs:
         so, se = p.communicate(timeout=900)
@@ -105,6 +105,33 @@ def test_bench_two_ranks_share_one_gpu(tmp_path):
     e2e = line["end_to_end"]
     assert e2e["ranks_ok"] == 2 and e2e["value_gpu_entropy"] > 0 and e2e["value_gpu_entropy_with_d2h"] > 0, e2e
     assert [r["rank"] for r in e2e["per_rank"]] == [0, 1] and all(r["mpix_s"] > 0 and r["host_threads"] >= 1 for r in e2e["per_rank"])
+
+
+@pytest.mark.spawns_gpu_children
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """bench.py without --full: the headline alone (exactly --steps timed launches, no legs, no end to end, no CPU baseline) and, with
+    --dump-outputs, the pixels of the last timed launch as float32 .npy files that equal the oracle's decode of the same images."""
+    import image_codecs_amd as ica
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--images", "40",
+                        "--distinct", "4", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 4 and line["warmup"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "Mpix/s"
+    assert line["higher_is_better"] is True and line["config"]["full"] is False
+    assert "legs" not in line and "end_to_end" not in line and "cpu_baseline" not in line and "host_stage" not in line
+    files = {p.name: np.load(p) for p in out.iterdir()}
+    assert set(files) == {"rgb_last_image.npy", "rgb_sample.npy", "rgb_sample_slots.npy", "rgb_sample_positions.npy"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+    oracle = helpers.Oracle()
+    want = [oracle.load(ica.synth_jpeg(1920, 1080, seed=s, quality=90), 3)[1] for s in range(4)]
+    assert np.array_equal(files["rgb_last_image.npy"], want[39 % 4].astype(np.float32))
+    slots, pos = files["rgb_sample_slots.npy"].astype(np.int64), files["rgb_sample_positions.npy"].astype(np.int64)
+    assert len(slots) == 16 and len(pos) == 1 << 18
+    for row, s in zip(files["rgb_sample.npy"], slots):
+        assert np.array_equal(row, want[s % 4].reshape(-1)[pos].astype(np.float32)), s
 
 
 def test_decode_batch_multi_two_contexts(ica, oracle, gpu_ctx, golden):

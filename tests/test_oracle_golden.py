@@ -79,34 +79,44 @@ def test_oracle_encoder(golden, oracle):
         assert got == bytes(golden[nm + "/jpg"]), nm
 
 
-@pytest.mark.skipif(not helpers.Reference.available(), reason="oracle/_ref not built (reference absent on this box)")
 def test_oracle_vs_live_reference_seeded(oracle):
-    """Beyond the committed vectors: seeded inputs through the reference library itself."""
-    ref = helpers.Reference()
+    """Beyond the committed vectors: seeded inputs through the reference library itself where it is built, and always against what it
+    returned for them (helpers.StoredReference)."""
+    ref = helpers.Reference() if helpers.Reference.available() else None
+    stored = helpers.StoredReference()
     rng = np.random.default_rng(2024)
     for i in range(40):
         w, h = int(rng.integers(1, 90)), int(rng.integers(1, 70))
         q = int(rng.choice([5, 30, 50, 75, 90, 91, 100]))
         img = rng.integers(0, 256, (h, w, 3)).astype(np.uint8) if i % 2 else np.tile(np.arange(w, dtype=np.uint8)[None, :, None] * 3, (h, 1, 3))
-        jr, jo = ref.encode(img, q), oracle.encode(img, q)
-        assert jr == jo, (w, h, q)
+        jo = oracle.encode(img, q)
+        assert helpers.digest_bytes(jo) == stored.encode(img, q), (w, h, q)
+        if ref is not None:
+            assert ref.encode(img, q) == jo, (w, h, q)
         for req in (0, 1, 2, 3, 4):
-            a, b = ref.load(jr, req), oracle.load(jr, req)
-            assert a[0] == b[0] == "ok"
-            assert np.array_equal(a[1], b[1]), (w, h, q, req)
+            b = oracle.load(jo, req)
+            assert b[0] == "ok" and helpers.digest_load(b) == stored.load(jo, req), (w, h, q, req)
+            if ref is not None:
+                a = ref.load(jo, req)
+                assert a[0] == b[0] == "ok"
+                assert np.array_equal(a[1], b[1]), (w, h, q, req)
     # IDCT on adversarial blocks
     for amp in (100, 2000, 32767):
         for _ in range(200):
             blk = rng.integers(-amp, amp + 1, 64).astype(np.int16)
-            assert np.array_equal(ref.idct(blk), oracle.idct(blk))
+            o = oracle.idct(blk)
+            assert helpers.digest_bytes(o.tobytes()) == stored.idct(blk)
+            if ref is not None:
+                assert np.array_equal(ref.idct(blk), o)
 
 
-@pytest.mark.skipif(not helpers.Reference.available(), reason="oracle/_ref not built (reference absent on this box)")
 def test_oracle_vs_live_reference_fuzz(golden, oracle):
-    """Mutated streams: same accept/reject decision and reason; same pixels whenever both decode.
+    """Mutated streams: same accept/reject decision and reason; same pixels whenever both decode -- against the reference library
+    where it is built, and always against what it returned for them (helpers.StoredReference).
     (Streams on which the reference consumes uninitialised memory are skipped: those are the ones
     that bail out of a scan early, which only happens with a restart interval defined.)"""
-    ref = helpers.Reference()
+    ref = helpers.Reference() if helpers.Reference.available() else None
+    stored = helpers.StoredReference()
     agree = 0
     for name in ("b420_64x64_q90", "b444_40x24_q95", "prog_420_64x64", "prog_444_64x64", "rst_blocks_64x48", "grey_33x20", "b422_37x21"):
         base = golden.jpg(name)
@@ -115,12 +125,16 @@ def test_oracle_vs_live_reference_fuzz(golden, oracle):
             # restart-interval scan makes the reference read never-written planes)
             markers = (seed % 3 == 0) and name.startswith(("b4", "grey"))
             data = helpers.mutate(base, seed * 7919 + len(name), allow_markers=markers)
-            a, b = ref.load(data, 3), oracle.load(data, 3)
-            assert a[0] == b[0], (name, seed, a[1] if a[0] == "fail" else "ok", b[1] if b[0] == "fail" else "ok")
-            if a[0] == "fail":
-                assert a[1] == b[1], (name, seed)
-            elif not name.startswith("rst"):
-                assert np.array_equal(a[1], b[1]), (name, seed)
+            b = oracle.load(data, 3)
+            pixels = not name.startswith("rst")
+            assert helpers.digest_load(b, pixels) == stored.load(data, 3, pixels), (name, seed, b[1] if b[0] == "fail" else "ok")
+            if ref is not None:
+                a = ref.load(data, 3)
+                assert a[0] == b[0], (name, seed, a[1] if a[0] == "fail" else "ok", b[1] if b[0] == "fail" else "ok")
+                if a[0] == "fail":
+                    assert a[1] == b[1], (name, seed)
+                elif pixels:
+                    assert np.array_equal(a[1], b[1]), (name, seed)
             agree += 1
     assert agree == 420
 
@@ -134,21 +148,25 @@ LAYOUTS_R2 = [  # (factors per component, Adobe transform or -1): the layouts of
 ]
 
 
-@pytest.mark.skipif(not helpers.Reference.available(), reason="oracle/_ref not built (reference absent on this box)")
 def test_oracle_vs_live_reference_sampling_layouts(oracle):
     """Streams of the test-side writer with unusual sampling factors, Adobe-tagged RGB / CMYK / YCCK and a fourth
     component: the oracle decodes them exactly as the reference does (resample_row_v_2 / _generic, codec/jpeg.c:1774-1782,
-    :1962-1971; colour branches :2320-2431), for every req_comp.  These are the inputs of the GPU layout tests."""
+    :1962-1971; colour branches :2320-2431), for every req_comp -- the reference library where it is built, and always what it
+    returned for them (helpers.StoredReference).  These are the inputs of the GPU layout tests."""
     import image_codecs_amd as ica
-    ref = helpers.Reference()
+    ref = helpers.Reference() if helpers.Reference.available() else None
+    stored = helpers.StoredReference()
     n = 0
     for li, (hv, app14) in enumerate(LAYOUTS_R2):
         for si, (w, h) in enumerate(((64, 48), (36, 20), (4, 4), (30, 17), (200, 97))):
             plan, du = ica.host_transform(ica.synth_rgb(w, h, 300 + 7 * li + si), 92)
             data = helpers.baseline_layout_from_444(plan, du, hv, app14, restart_mcus=(3 if si == 1 else 0))
             for req in (0, 1, 2, 3, 4):
-                a, b = ref.load(data, req), oracle.load(data, req)
-                assert a[0] == b[0] == "ok", (hv, app14, w, h, req)
-                assert np.array_equal(a[1], b[1]), (hv, app14, w, h, req)
+                b = oracle.load(data, req)
+                assert b[0] == "ok" and helpers.digest_load(b) == stored.load(data, req), (hv, app14, w, h, req)
+                if ref is not None:
+                    a = ref.load(data, req)
+                    assert a[0] == b[0] == "ok", (hv, app14, w, h, req)
+                    assert np.array_equal(a[1], b[1]), (hv, app14, w, h, req)
                 n += 1
     assert n == len(LAYOUTS_R2) * 5 * 5

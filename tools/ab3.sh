@@ -7,7 +7,7 @@ LEGS=${LEGS:-int16_planes,harsh_batch}
 for r in $(seq 1 $ROUNDS); do
 	for lib in "$@"; do
 		echo -n "round $r $(basename $(dirname $lib)): "
-		MIJ_LIB=$(realpath $lib) python bench.py --no-cpu-baseline --no-e2e --legs $LEGS 2>/dev/null |
+		MIJ_LIB=$(realpath $lib) python bench.py --full --no-cpu-baseline --no-e2e --legs $LEGS 2>/dev/null |
 			python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); L=d.get('legs',{})

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 for r in 1 2 3; do
 	for lib in "$@"; do
 		echo -n "round $r $(basename $(dirname $lib)): "
-		MIJ_LIB=$(realpath $lib) python bench.py --no-cpu-baseline --no-e2e --legs config4 2>/dev/null | python -c "
+		MIJ_LIB=$(realpath $lib) python bench.py --full --no-cpu-baseline --no-e2e --legs config4 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); c=d['legs']['config4']; e=c.get('end_to_end',{})
 print('e2e', e.get('mpix_s'), 'host stage', e.get('host_stage_only_mpix_s'), 'single thread', c.get('host_progressive_stage_mpix_s_single_thread'))"

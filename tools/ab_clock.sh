@@ -6,7 +6,7 @@ for lib in "$@"; do
 	tag=$(basename $(dirname $lib))
 	OUT=gpurun_out/abclk_$tag
 	rm -rf $OUT; mkdir -p $OUT
-	MIJ_LIB=$(realpath $lib) timeout -k 10 200 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d $OUT -- python3 bench.py --images 1024 --steps 10 --warmup 3 --no-cpu-baseline --no-e2e >$OUT/stdout 2>$OUT/stderr
+	MIJ_LIB=$(realpath $lib) timeout -k 10 200 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d $OUT -- python3 bench.py --full --images 1024 --steps 10 --warmup 3 --no-cpu-baseline --no-e2e >$OUT/stdout 2>$OUT/stderr
 	python3 - $OUT $tag <<'PY'
 import csv, glob, sys
 out, tag = sys.argv[1], sys.argv[2]

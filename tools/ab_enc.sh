@@ -5,7 +5,7 @@ ROUNDS=${ROUNDS:-3}
 for r in $(seq 1 $ROUNDS); do
 	for lib in "$@"; do
 		echo -n "round $r $(basename $(dirname $lib)): "
-		MIJ_LIB=$(realpath $lib) python bench.py --legs config5,config5_q95_444 2>/dev/null |
+		MIJ_LIB=$(realpath $lib) python bench.py --full --legs config5,config5_q95_444 2>/dev/null |
 			python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); L=d['legs']

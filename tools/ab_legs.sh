@@ -6,7 +6,7 @@ ROUNDS=${ROUNDS:-2}
 for r in $(seq 1 $ROUNDS); do
 	for lib in "$@"; do
 		echo -n "round $r $(basename $(dirname $lib)): "
-		MIJ_LIB=$(realpath $lib) python bench.py --no-cpu-baseline --no-e2e 2>/dev/null |
+		MIJ_LIB=$(realpath $lib) python bench.py --full --no-cpu-baseline --no-e2e 2>/dev/null |
 			python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); L=d['legs']

@@ -6,7 +6,7 @@ OUT=$REPO/gpurun_out/prof_clock
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd "$REPO"
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d "$OUT/grbm" -- python3 bench.py --images 1024 --steps 10 --warmup 3 --no-cpu-baseline --no-e2e >"$OUT/grbm.stdout" 2>"$OUT/grbm.stderr"
+timeout -k 10 300 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d "$OUT/grbm" -- python3 bench.py --full --images 1024 --steps 10 --warmup 3 --no-cpu-baseline --no-e2e >"$OUT/grbm.stdout" 2>"$OUT/grbm.stderr"
 echo "rc=$?"
 python3 - "$OUT" <<'PY'
 import csv, glob, sys

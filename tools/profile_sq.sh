@@ -13,7 +13,7 @@ echo "$RUN" > "$REPO/gpurun_out/prof_$TAG.latest"
 FAILED=0
 export TMPDIR=/tmp
 cd "$REPO"
-ARGS="--no-cpu-baseline --no-e2e"
+ARGS="--full --no-cpu-baseline --no-e2e"
 run() {
 	name=$1
 	shift

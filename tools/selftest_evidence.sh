@@ -3,10 +3,12 @@
 # stream is flipped on purpose (MIJ_BENCH_SELFTEST_MISMATCH=1), the leg must fail, name the file it kept, and the file must load.
 set -u
 cd "$(dirname "$0")/.."
-MIJ_BENCH_SELFTEST_MISMATCH=1 python3 bench.py --no-cpu-baseline --no-e2e --legs config5 --steps 3 --warmup 2 > gpurun_out/selftest_evidence.json 2> gpurun_out/selftest_evidence.err
-python3 - <<'PY'
-import glob, json, numpy as np
-line = json.loads([l for l in open("gpurun_out/selftest_evidence.json") if l.startswith("{")][-1])
+OUT=${OUT:-out}
+mkdir -p "$OUT"
+MIJ_BENCH_SELFTEST_MISMATCH=1 python3 bench.py --full --no-cpu-baseline --no-e2e --legs config5 --steps 3 --warmup 2 > "$OUT/selftest_evidence.json" 2> "$OUT/selftest_evidence.err"
+python3 - "$OUT/selftest_evidence.json" <<'PY'
+import glob, json, sys, numpy as np
+line = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 err = line["legs"]["config5"]["error"]
 print(err[:900])
 assert "evidence kept in" in err and "first fetch == second fetch: True" in err and "reference-made golden: checker True, ours False" in err

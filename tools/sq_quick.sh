@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/sq_quick.sh <tag> [bench args] -- issue counters of the headline kernel only: two small --pmc passes over
-# `python3 bench.py --no-legs --no-e2e --no-cpu-baseline --steps 10 --warmup 5`, summarised by tools/sq_quick.py.
+# `python3 bench.py --full --no-legs --no-e2e --no-cpu-baseline --steps 10 --warmup 5`, summarised by tools/sq_quick.py.
 # Every run gets its own directory (never overwritten); counter passes carry --kernel-trace only.
 set -u
 TAG=${1:-sq}
@@ -11,7 +11,7 @@ OUT=$REPO/gpurun_out/$RUN
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd "$REPO"
-ARGS="--no-legs --no-e2e --no-cpu-baseline --steps 10 --warmup 5 $*"
+ARGS="--full --no-legs --no-e2e --no-cpu-baseline --steps 10 --warmup 5 $*"
 FAILED=0
 run() {
 	name=$1

@@ -57,7 +57,7 @@ def pick(rows, which):
     return rows[-K:]
 
 
-lines = ["# rocprofv3 summary %s" % tag, "", "command profiled: `python3 bench.py --no-cpu-baseline --no-e2e` (the driver's default N=1 command without the two host-side legs)", ""]
+lines = ["# rocprofv3 summary %s" % tag, "", "command profiled: `python3 bench.py --full --no-cpu-baseline --no-e2e` (the full N=1 run without the two host-side legs)", ""]
 # ---- pass 1: kernel trace
 kt = one("trace/**/*kernel_trace.csv")
 trace = []
