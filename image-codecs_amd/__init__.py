@@ -2,7 +2,7 @@
 
 The product is the shared library ``lib/libimagecodecs_mi355x.so`` built from ``csrc/``:
   * ``stbi_*``  the reference's public surface (include/image_api.h; reference definitions in
-                convert.c:188-266, image_api.c:74-145, codec/jpeg_write.c:368-388),
+                convert.c:188-266,286-336,402-411, image_api.c:74-145, codec/jpeg_write.c:368-388),
   * ``mij_*``   the GPU back end's C-ABI (include/mij.h; replaces the kernel seam
                 codec/jpeg.c:83-85),
   * ``mjh_*``   the host entropy decoder (csrc/jpeg_entropy.h; codec/jpeg.c:88-558,1119-1756).
@@ -40,6 +40,15 @@ from .binding import (  # noqa: F401
     stbi_info_from_callbacks,
     stbi_write_jpg,
     stbi_load_16_from_memory,
+    stbi_loadf,
+    stbi_loadf_from_memory,
+    stbi_loadf_from_file,
+    stbi_loadf_from_callbacks,
+    stbi_ldr_to_hdr_gamma,
+    stbi_ldr_to_hdr_scale,
+    stbi_hdr_to_ldr_gamma,
+    stbi_hdr_to_ldr_scale,
+    ldr_to_hdr_lut,
     stbi_set_flip_vertically_on_load,
     stbi_write_jpg_to_memory,
     detile_coefficients,

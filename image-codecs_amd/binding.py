@@ -203,6 +203,73 @@ def stbi_load_16_from_memory(data, req_comp=0):
     return arr, x.value, y.value, c.value
 
 
+# ---- float loaders (convert.c:286-336) and their gamma / scale (convert.c:402-411)
+
+# What stbi_ldr_to_hdr_gamma / _scale last set THROUGH THIS MODULE (the C globals are float): the defaults of ldr_to_hdr_lut() and
+# Batch.set_out_f32(lut=None).  The library has no getter, so a value set by C code in the same process is not seen here; pass
+# gamma / scale or a table explicitly in that case.  The stbi_loadf* loaders themselves always read the C globals.
+_l2h = [np.float32(2.2), np.float32(1.0)]
+
+
+def stbi_ldr_to_hdr_gamma(gamma):
+    lib().stbi_ldr_to_hdr_gamma.argtypes = [C.c_float]
+    lib().stbi_ldr_to_hdr_gamma(float(gamma))
+    _l2h[0] = np.float32(gamma)
+
+
+def stbi_ldr_to_hdr_scale(scale):
+    lib().stbi_ldr_to_hdr_scale.argtypes = [C.c_float]
+    lib().stbi_ldr_to_hdr_scale(float(scale))
+    _l2h[1] = np.float32(scale)
+
+
+def stbi_hdr_to_ldr_gamma(gamma):
+    lib().stbi_hdr_to_ldr_gamma.argtypes = [C.c_float]
+    lib().stbi_hdr_to_ldr_gamma(float(gamma))
+
+
+def stbi_hdr_to_ldr_scale(scale):
+    lib().stbi_hdr_to_ldr_scale.argtypes = [C.c_float]
+    lib().stbi_hdr_to_ldr_scale(float(scale))
+
+
+def ldr_to_hdr_lut(n_out, gamma=None, scale=None):
+    """mjh_ldr_to_hdr_lut: float32 [n_out, 256], the tables of stbi__ldr_to_hdr (gamma / scale None: the values last set through
+    this module's stbi_ldr_to_hdr_gamma / _scale -- not ones C code set directly, see _l2h)."""
+    L = lib()
+    L.mjh_ldr_to_hdr_lut.argtypes = [C.c_int, C.c_float, C.c_float, C.c_void_p]
+    out = np.empty((int(n_out), 256), dtype=np.float32)
+    L.mjh_ldr_to_hdr_lut(int(n_out), float(_l2h[0] if gamma is None else gamma), float(_l2h[1] if scale is None else scale),
+                         out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def _loadf_result(p, x, y, c, req_comp):
+    if not p:
+        return None
+    n = req_comp if req_comp else c.value
+    return _take(p, (y.value, x.value, n), np.float32), x.value, y.value, c.value
+
+
+def stbi_loadf_from_memory(data, req_comp=0):
+    """-> (pixels[h, w, n] float32, w, h, comp_in_file) or None (see stbi_failure_reason())."""
+    L = lib()
+    L.stbi_loadf_from_memory.restype = C.POINTER(C.c_float)
+    L.stbi_loadf_from_memory.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+    x, y, c = C.c_int(), C.c_int(), C.c_int()
+    p = L.stbi_loadf_from_memory(bytes(data), len(data), C.byref(x), C.byref(y), C.byref(c), int(req_comp))
+    return _loadf_result(p, x, y, c, req_comp)
+
+
+def stbi_loadf(filename, req_comp=0):
+    L = lib()
+    L.stbi_loadf.restype = C.POINTER(C.c_float)
+    L.stbi_loadf.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+    x, y, c = C.c_int(), C.c_int(), C.c_int()
+    p = L.stbi_loadf(os.fsencode(filename), C.byref(x), C.byref(y), C.byref(c), int(req_comp))
+    return _loadf_result(p, x, y, c, req_comp)
+
+
 def stbi_info_from_memory(data):
     """-> (ok, w, h, comp)"""
     x, y, c = C.c_int(), C.c_int(), C.c_int()
@@ -262,6 +329,17 @@ def stbi_load_from_callbacks(data, req_comp=0, chunk=None):
     return _take(p, (y.value, x.value, n), np.uint8), x.value, y.value, c.value
 
 
+def stbi_loadf_from_callbacks(data, req_comp=0, chunk=None):
+    """stbi_loadf_from_callbacks over an in-memory source; result as stbi_loadf_from_memory."""
+    L = lib()
+    L.stbi_loadf_from_callbacks.restype = C.POINTER(C.c_float)
+    L.stbi_loadf_from_callbacks.argtypes = [C.POINTER(IoCallbacks), C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+    src = _CallbackSource(data, chunk)
+    x, y, c = C.c_int(), C.c_int(), C.c_int()
+    p = L.stbi_loadf_from_callbacks(C.byref(src.cb), None, C.byref(x), C.byref(y), C.byref(c), int(req_comp))
+    return _loadf_result(p, x, y, c, req_comp)
+
+
 def stbi_info_from_callbacks(data, chunk=None):
     L = lib()
     L.stbi_info_from_callbacks.argtypes = [C.POINTER(IoCallbacks), C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -305,6 +383,24 @@ def stbi_load_from_file(filename, req_comp=0, offset=0):
             return None, pos
         n = req_comp if req_comp else c.value
         return (_take(p, (y.value, x.value, n), np.uint8), x.value, y.value, c.value), pos
+    finally:
+        libc.fclose(f)
+
+
+def stbi_loadf_from_file(filename, req_comp=0, offset=0):
+    """fopen + fseek(offset) + stbi_loadf_from_file + ftell: -> (result as stbi_loadf_from_memory or None, position the FILE*
+    was left at -- wherever reading stopped: the float loader does not seek back, convert.c:331-336)."""
+    L, libc = lib(), _c_stdio()
+    L.stbi_loadf_from_file.restype = C.POINTER(C.c_float)
+    L.stbi_loadf_from_file.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+    f = libc.fopen(os.fsencode(filename), b"rb")
+    if not f:
+        raise OSError("fopen failed: %s" % filename)
+    try:
+        libc.fseek(f, offset, 0)
+        x, y, c = C.c_int(), C.c_int(), C.c_int()
+        p = L.stbi_loadf_from_file(f, C.byref(x), C.byref(y), C.byref(c), int(req_comp))
+        return _loadf_result(p, x, y, c, req_comp), libc.ftell(f)
     finally:
         libc.fclose(f)
 
@@ -753,6 +849,43 @@ class Batch:
         out = np.empty((d.height, d.width, d.n_out), dtype=np.uint8)
         _check(lib().mij_batch_fetch(self._h, int(slot), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.size)), "mij_batch_fetch")
         return out
+
+    # ---- float output (mij_batch_set_out_f32): k_out_f32 behind the decode kernels, into a float arena of its own
+    @staticmethod
+    def out_f32_bytes(desc):
+        L = lib()
+        L.mij_image_out_f32_bytes.restype = C.c_size_t
+        L.mij_image_out_f32_bytes.argtypes = [C.POINTER(ImageDesc)]
+        return L.mij_image_out_f32_bytes(C.byref(desc))
+
+    def reserve_out_f32(self, nbytes):
+        L = lib()
+        L.mij_batch_out_f32_reserve.argtypes = [C.c_void_p, C.c_size_t]
+        _check(L.mij_batch_out_f32_reserve(self._h, C.c_size_t(nbytes)), "mij_batch_out_f32_reserve")
+
+    def set_out_f32(self, slot, lut=None):
+        """Ask for the slot's pixels as float32 through lut [n_out, 256] (None: the stb table at the gamma and scale last set through
+        this module, see ldr_to_hdr_lut)."""
+        n = self._desc(slot).n_out
+        t = ldr_to_hdr_lut(n) if lut is None else np.ascontiguousarray(lut, dtype=np.float32).reshape(n, 256)
+        L = lib()
+        L.mij_batch_set_out_f32.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _check(L.mij_batch_set_out_f32(self._h, int(slot), t.ctypes.data_as(C.c_void_p)), "mij_batch_set_out_f32")
+
+    def fetch_f32(self, slot):
+        d = self._desc(slot)
+        out = np.empty((d.height, d.width, d.n_out), dtype=np.float32)
+        L = lib()
+        L.mij_batch_fetch_f32.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        _check(L.mij_batch_fetch_f32(self._h, int(slot), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.size)), "mij_batch_fetch_f32")
+        return out
+
+    def device_out_f32(self, slot):
+        """Device address of the slot's floats (None without float output)."""
+        L = lib()
+        L.mij_batch_device_out_f32.restype = C.c_void_p
+        L.mij_batch_device_out_f32.argtypes = [C.c_void_p, C.c_int]
+        return L.mij_batch_device_out_f32(self._h, int(slot))
 
     def fetch_all_async(self, dst_ptr, dst_bytes):
         """mij_batch_fetch_all_async into a (pinned) host buffer; wait() completes it."""

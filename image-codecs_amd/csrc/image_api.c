@@ -5,10 +5,12 @@
  * Mirrors, for JPEG only, the reference's dispatch and post-processing:
  *   stbi__load_main                     image_api.c:3-56    (type test, then load)
  *   stbi__load_and_postprocess_8bit/16  convert.c:78-133    (8<->16 conversion, vertical flip)
+ *   stbi__loadf_main + stbi__ldr_to_hdr  convert.c:286-336, common.c:391-424 (float output: tables built here, applied on the GPU)
  *   stbi_load* / stbi_info* / is_16_bit / is_hdr            convert.c:188-266,345-398 image_api.c:74-145
  *   load_jpeg_image's argument checks and outputs           codec/jpeg.c:2224-2249,2293,2433-2438
  * The pixel work itself (IDCT, upsample, colour) runs on the GPU; there is no CPU fallback.
  */
+#include <math.h>
 #include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
@@ -62,6 +64,7 @@ typedef struct {
 	mij_batch *b;
 	size_t coef_cap, out_cap, stream_cap;
 	uint8_t *bounce; /* pinned host buffer of out_cap bytes, allocated on first need (fetch_pixels) */
+	size_t f32_cap;  /* bytes of the batch's float arena (mij_batch_out_f32_reserve), reserved on the first stbi_loadf* call */
 } tl_batch;
 
 /* The calling thread's one-picture batch lives in thread-local storage while the thread lives.  When the thread ends, the batch
@@ -71,7 +74,7 @@ typedef struct {
  * made stbi_load calls).  A new thread takes a pooled batch before it creates one -- which also spares thread-pool style callers
  * the 70 MB of allocations per new thread. */
 #define MIJ_POOL_MAX 64
-static __thread tl_batch t_batch = {NULL, 0, 0, 0, NULL};
+static __thread tl_batch t_batch = {NULL, 0, 0, 0, NULL, 0};
 static pthread_key_t g_batch_key;
 static pthread_once_t g_batch_key_once = PTHREAD_ONCE_INIT;
 static pthread_mutex_t g_pool_lock = PTHREAD_MUTEX_INITIALIZER;
@@ -108,7 +111,7 @@ static void remember_thread_batch(void)
 
 /* a one-image batch big enough for `d` (and, stream_bytes > 0, with an entropy arena for a file of that many bytes: the GPU
  * Huffman walk), grown geometrically and reused across calls */
-static mij_batch *thread_batch(mij_ctx *ctx, const mij_image_desc *d, size_t stream_bytes)
+static mij_batch *thread_batch_u8(mij_ctx *ctx, const mij_image_desc *d, size_t stream_bytes)
 {
 	size_t cb = mij_image_coef_bytes(d), ob = mij_image_out_bytes(d);
 	if (!t_batch.b) { /* a batch a finished thread left behind, the roomiest one */
@@ -138,7 +141,7 @@ static mij_batch *thread_batch(mij_ctx *ctx, const mij_image_desc *d, size_t str
 			mij_host_free(t_batch.bounce);
 		t_batch.b = NULL;
 		t_batch.bounce = NULL;
-		t_batch.coef_cap = t_batch.out_cap = t_batch.stream_cap = 0;
+		t_batch.coef_cap = t_batch.out_cap = t_batch.stream_cap = t_batch.f32_cap = 0;
 		remember_thread_batch();
 	}
 	{
@@ -165,11 +168,35 @@ static mij_batch *thread_batch(mij_ctx *ctx, const mij_image_desc *d, size_t str
 	return t_batch.b;
 }
 
+/* the same with, f32_bytes > 0, a float arena of at least that many bytes (stbi_loadf*), grown with slack, or exactly as big before
+ * giving up.  A failed reserve may leave the batch with no float arena at all (mij_batch_out_f32_reserve), so f32_cap is then 0: the
+ * next call reserves again instead of trusting a capacity the batch no longer has. */
+static mij_batch *thread_batch(mij_ctx *ctx, const mij_image_desc *d, size_t stream_bytes, size_t f32_bytes)
+{
+	mij_batch *b = thread_batch_u8(ctx, d, stream_bytes);
+	if (b && f32_bytes > t_batch.f32_cap) { /* the batch was just reset: it holds no float request */
+		size_t cap = f32_bytes + f32_bytes / 4 + 4096;
+		if (mij_batch_out_f32_reserve(b, cap) != MIJ_OK) {
+			cap = f32_bytes;
+			if (mij_batch_out_f32_reserve(b, cap) != MIJ_OK)
+				cap = 0;
+		}
+		t_batch.f32_cap = cap;
+		remember_thread_batch();
+		if (!cap)
+			return NULL;
+	}
+	return b;
+}
+
 /* Pixels of the thread batch's one picture into the caller's malloc block.  A device-to-host copy into pageable memory goes
  * through one staging path inside the HIP runtime: calls from several threads queue up behind each other (eight threads decoding
  * 1080p pictures: 4 Gpix/s in all, tools/bench_threads.py).  With more than one stbi_load call in flight the pixels therefore
  * cross PCIe into the batch's own pinned buffer and the calling thread copies them out itself. */
 static int g_calls_in_flight = 0;
+
+/* what a load hands back: the decoded bytes, or the floats of stbi__ldr_to_hdr made from them on the device (k_out_f32) */
+enum { OUT_U8 = 0, OUT_F32 = 1 };
 
 static int fetch_pixels(mij_batch *b, int slot, unsigned char *pixels, size_t nbytes)
 {
@@ -191,6 +218,47 @@ static int fetch_pixels(mij_batch *b, int slot, unsigned char *pixels, size_t nb
 	}
 	return mij_batch_fetch(b, slot, pixels, nbytes);
 }
+
+/* nvals bytes (OUT_U8, fetch_pixels) or floats (OUT_F32) of the thread batch's picture.  Floats cross PCIe in place of the bytes -- no
+ * uint8 copy comes back -- through the context's one pinned bounce buffer (mij_batch_fetch_f32, d2h_bounced): concurrent stbi_loadf*
+ * calls take turns on it (DESIGN.md 4c gives the cost; the per-thread pinned buffer of fetch_pixels is not used for floats). */
+static int fetch_out(mij_batch *b, int slot, void *dst, size_t nvals, int kind)
+{
+	if (kind == OUT_F32)
+		return mij_batch_fetch_f32(b, slot, (float *)dst, nvals);
+	return fetch_pixels(b, slot, (unsigned char *)dst, nvals);
+}
+
+static float g_l2h_gamma = 2.2f, g_l2h_scale = 1.0f;         /* convert.c:402, process-global as there */
+static float g_h2l_gamma_i = 1.0f / 2.2f, g_h2l_scale_i = 1.0f; /* convert.c:407: only HDR input reads them, never JPEG */
+
+void stbi_ldr_to_hdr_gamma(float gamma) { g_l2h_gamma = gamma; }
+void stbi_ldr_to_hdr_scale(float scale) { g_l2h_scale = scale; }
+void stbi_hdr_to_ldr_gamma(float gamma) { g_h2l_gamma_i = 1 / gamma; }
+void stbi_hdr_to_ldr_scale(float scale) { g_h2l_scale_i = 1 / scale; }
+
+/* common.c:391-424, per value instead of per pixel: the same float quotient, double pow and multiply, cast to float */
+void mjh_ldr_to_hdr_lut(int n_out, float gamma, float scale, float *lut)
+{
+	const int n = (n_out & 1) ? n_out : n_out - 1; /* colour channels; an even count ends with alpha */
+	int k, v;
+	for (k = 0; k < n_out; ++k)
+		for (v = 0; v < 256; ++v)
+			lut[256 * k + v] = k < n ? (float)(pow(v / 255.0f, gamma) * scale) : v / 255.0f;
+}
+
+/* float output asked of a slot: the reference's tables at the current gamma and scale */
+static int ask_f32(mij_batch *b, int slot, int n_out)
+{
+	float lut[4 * 256];
+	mjh_ldr_to_hdr_lut(n_out, g_l2h_gamma, g_l2h_scale, lut);
+	return mij_batch_set_out_f32(b, slot, lut);
+}
+
+/* stbi__malloc_mad4(x, y, comp, sizeof(float), 0) (common.c:397): the float block must stay within INT_MAX bytes.  Its own string
+ * object, so that loadf_main can tell this "outofmem" -- which the reference reports as it is -- from the 8-bit load's. */
+static const char k_f32_outofmem[] = "outofmem";
+static int f32_too_big(size_t nvals) { return nvals > 0x7fffffffu / sizeof(float); }
 
 /* ------------------------------------------------------------------ load */
 
@@ -227,7 +295,7 @@ static size_t gpu_walk_min_pixels(void)
 
 /* One image through the GPU Huffman walk: NULL when the file is not a layout the walk takes, when the walk reports the
  * stream back, or on any resource problem -- the caller then takes the host walk. */
-static unsigned char *load_gpu_walk(mij_ctx *ctx, const uint8_t *buf, int len, int req_comp, const mij_image_desc *desc)
+static void *load_gpu_walk(mij_ctx *ctx, const uint8_t *buf, int len, int req_comp, const mij_image_desc *desc, int kind)
 {
 	mjg_scan *scan;
 	mij_batch *b;
@@ -238,7 +306,10 @@ static unsigned char *load_gpu_walk(mij_ctx *ctx, const uint8_t *buf, int len, i
 	int slot, nfb = 0, fb[1];
 	if (len <= 0)
 		return NULL;
-	b = thread_batch(ctx, desc, (size_t)len + (size_t)len / 8 + 8192);
+	/* a float block beyond INT_MAX bytes gets no float arena: the host walk below reports it after its own checks */
+	if (kind == OUT_F32 && f32_too_big((size_t)desc->n_out * (size_t)desc->width * (size_t)desc->height))
+		return NULL;
+	b = thread_batch(ctx, desc, (size_t)len + (size_t)len / 8 + 8192, kind == OUT_F32 ? mij_image_out_f32_bytes(desc) : 0);
 	if (!b || !(stage = mij_batch_entropy_stage(b, &cap)))
 		return NULL;
 	scan = (mjg_scan *)malloc(sizeof(*scan));
@@ -252,22 +323,28 @@ static unsigned char *load_gpu_walk(mij_ctx *ctx, const uint8_t *buf, int len, i
 	nbytes = (size_t)scan->desc.n_out * (size_t)scan->desc.width * (size_t)scan->desc.height;
 	if (nbytes > 0x7fffffffu - 1)
 		goto out;
+	if (kind == OUT_F32 && (f32_too_big(nbytes) || ask_f32(b, slot, scan->desc.n_out) != MIJ_OK))
+		goto out; /* the host walk below reports it */
 	if (mij_batch_entropy_launch(b) != MIJ_OK)
 		goto out;
 	/* while the GPU walks: the caller's pixel block, and its pages touched once -- a fresh 50 MB block costs 12 000 page faults, which
 	 * otherwise land in the copy-out at the end of the call (round 3: the pixels are copied out of a pinned buffer, not DMA'd in) */
-	pixels = (unsigned char *)malloc(nbytes + 1); /* codec/jpeg.c:2293: n * x * y + 1 bytes */
-	if (pixels && nbytes >= ((size_t)1 << 20)) {
-		size_t i;
-		for (i = 0; i < nbytes; i += 4096)
-			pixels[i] = 0;
+	{
+		/* codec/jpeg.c:2293: n * x * y + 1 bytes; floats: stbi__malloc_mad4, n * x * y * 4 (common.c:397) */
+		const size_t block = kind == OUT_F32 ? nbytes * sizeof(float) : nbytes + 1;
+		pixels = (unsigned char *)malloc(block);
+		if (pixels && block >= ((size_t)1 << 20)) {
+			size_t i;
+			for (i = 0; i < block; i += 4096)
+				pixels[i] = 0;
+		}
 	}
 	if (mij_batch_entropy_finish(b, fb, 1, &nfb) != MIJ_OK || nfb != 0 || !pixels) {
 		free(pixels);
 		pixels = NULL;
 		goto out;
 	}
-	if (mij_batch_submit(b) != MIJ_OK || fetch_pixels(b, slot, pixels, nbytes) != MIJ_OK) {
+	if (mij_batch_submit(b) != MIJ_OK || fetch_out(b, slot, pixels, nbytes, kind) != MIJ_OK) {
 		free(pixels);
 		pixels = NULL;
 	}
@@ -277,7 +354,7 @@ out:
 }
 
 /* stbi__load_main (image_api.c:3-56) + stbi__jpeg_load / load_jpeg_image (codec/jpeg.c:2224-2452) */
-static unsigned char *load_main_counted(mjh_reader *r, int *x, int *y, int *comp, int req_comp)
+static void *load_main_counted(mjh_reader *r, int *x, int *y, int *comp, int req_comp, int kind)
 {
 	mjh_decoder *d;
 	mij_image_desc desc;
@@ -323,7 +400,7 @@ static unsigned char *load_main_counted(mjh_reader *r, int *x, int *y, int *comp
 	 * the treatment of damaged streams stay the reference's.  Small pictures are quicker on the host (the GPU walk is some
 	 * thirty launches and two waits); callback and FILE sources are walked as they arrive. */
 	if (r->io.read == NULL && mjh_gpu_walk_default() && (size_t)desc.width * (size_t)desc.height >= gpu_walk_min_pixels()) {
-		unsigned char *px = load_gpu_walk(ctx, r->orig, (int)(r->orig_end - r->orig), req_comp, &desc);
+		void *px = load_gpu_walk(ctx, r->orig, (int)(r->orig_end - r->orig), req_comp, &desc, kind);
 		if (px) {
 			*x = desc.width;
 			*y = desc.height;
@@ -333,7 +410,10 @@ static unsigned char *load_main_counted(mjh_reader *r, int *x, int *y, int *comp
 			return px;
 		}
 	}
-	b = thread_batch(ctx, &desc, 0);
+	/* no float arena for a float block beyond INT_MAX bytes (stbi__malloc_mad4): the 8-bit load still runs, so that its own failures read as
+	 * the reference's, and the size check below then fails the call before anything is allocated for the floats */
+	nbytes = (size_t)desc.n_out * (size_t)desc.width * (size_t)desc.height;
+	b = thread_batch(ctx, &desc, 0, kind == OUT_F32 && !f32_too_big(nbytes) ? mij_image_out_f32_bytes(&desc) : 0);
 	if (!b) {
 		free(d);
 		return fail_ptr("outofmem");
@@ -376,12 +456,22 @@ static unsigned char *load_main_counted(mjh_reader *r, int *x, int *y, int *comp
 		free(d);
 		return fail_ptr("outofmem");
 	}
-	pixels = (unsigned char *)malloc(nbytes + 1);
+	if (kind == OUT_F32) {
+		if (f32_too_big(nbytes)) {
+			free(d);
+			return fail_ptr(k_f32_outofmem);
+		}
+		if (ask_f32(b, slot, desc.n_out) != MIJ_OK) {
+			free(d);
+			return fail_ptr("outofmem");
+		}
+	}
+	pixels = (unsigned char *)malloc(kind == OUT_F32 ? nbytes * sizeof(float) : nbytes + 1);
 	if (!pixels) {
 		free(d);
-		return fail_ptr("outofmem");
+		return fail_ptr(kind == OUT_F32 ? k_f32_outofmem : "outofmem");
 	}
-	if (mij_batch_submit(b) != MIJ_OK || fetch_pixels(b, slot, pixels, nbytes) != MIJ_OK) {
+	if (mij_batch_submit(b) != MIJ_OK || fetch_out(b, slot, pixels, nbytes, kind) != MIJ_OK) {
 		free(pixels);
 		free(d);
 		return fail_ptr("gpu decode failed");
@@ -394,11 +484,11 @@ static unsigned char *load_main_counted(mjh_reader *r, int *x, int *y, int *comp
 	return pixels;
 }
 
-static unsigned char *load_main(mjh_reader *r, int *x, int *y, int *comp, int req_comp)
+static void *load_main(mjh_reader *r, int *x, int *y, int *comp, int req_comp, int kind)
 {
-	unsigned char *p;
+	void *p;
 	__atomic_add_fetch(&g_calls_in_flight, 1, __ATOMIC_RELAXED);
-	p = load_main_counted(r, x, y, comp, req_comp);
+	p = load_main_counted(r, x, y, comp, req_comp, kind);
 	__atomic_sub_fetch(&g_calls_in_flight, 1, __ATOMIC_RELAXED);
 	return p;
 }
@@ -407,7 +497,7 @@ static unsigned char *load_main(mjh_reader *r, int *x, int *y, int *comp, int re
 static unsigned char *load_and_postprocess_8bit(mjh_reader *r, int *x, int *y, int *comp, int req_comp)
 {
 	int file_comp = 0;
-	unsigned char *result = load_main(r, x, y, &file_comp, req_comp);
+	unsigned char *result = (unsigned char *)load_main(r, x, y, &file_comp, req_comp, OUT_U8);
 	if (!result)
 		return NULL;
 	if (comp)
@@ -424,7 +514,7 @@ static stbi_us *load_and_postprocess_16bit(mjh_reader *r, int *x, int *y, int *c
 {
 	int file_comp = 0, channels, n, i;
 	stbi_us *wide;
-	unsigned char *result = load_main(r, x, y, &file_comp, req_comp);
+	unsigned char *result = (unsigned char *)load_main(r, x, y, &file_comp, req_comp, OUT_U8);
 	if (!result)
 		return NULL;
 	if (comp)
@@ -442,6 +532,26 @@ static stbi_us *load_and_postprocess_16bit(mjh_reader *r, int *x, int *y, int *c
 	if (g_flip_on_load)
 		vertical_flip(wide, *x, *y, channels * (int)sizeof(stbi_us));
 	return wide;
+}
+
+/* stbi__loadf_main (convert.c:286-303): the 8-bit load, flip included, then stbi__ldr_to_hdr with comp = req_comp ? req_comp : file
+ * comp -- here one load that leaves floats (k_out_f32, tables of mjh_ldr_to_hdr_lut) instead of bytes.  Any failure of the 8-bit
+ * load becomes "unknown image type" as there, except this library's own "no gpu device"; a float block beyond INT_MAX bytes
+ * is "outofmem". */
+static float *loadf_main(mjh_reader *r, int *x, int *y, int *comp, int req_comp)
+{
+	int file_comp = 0;
+	float *result = (float *)load_main(r, x, y, &file_comp, req_comp, OUT_F32);
+	if (!result) {
+		if (t_reason != k_f32_outofmem && !(t_reason && !strcmp(t_reason, "no gpu device")))
+			t_reason = "unknown image type";
+		return NULL;
+	}
+	if (comp)
+		*comp = file_comp;
+	if (g_flip_on_load)
+		vertical_flip(result, *x, *y, (req_comp ? req_comp : file_comp) * (int)sizeof(float));
+	return result;
 }
 
 stbi_uc *stbi_load_from_memory(stbi_uc const *buffer, int len, int *x, int *y, int *comp, int req_comp)
@@ -512,6 +622,39 @@ stbi_us *stbi_load_16(char const *filename, int *x, int *y, int *comp, int req_c
 	if (!f)
 		return (stbi_us *)fail_ptr("can't fopen");
 	result = stbi_load_from_file_16(f, x, y, comp, req_comp);
+	fclose(f);
+	return result;
+}
+
+float *stbi_loadf_from_memory(stbi_uc const *buffer, int len, int *x, int *y, int *comp, int req_comp)
+{
+	mjh_reader r;
+	mjh_reader_mem(&r, buffer, len);
+	return loadf_main(&r, x, y, comp, req_comp);
+}
+
+float *stbi_loadf_from_callbacks(stbi_io_callbacks const *clbk, void *user, int *x, int *y, int *comp, int req_comp)
+{
+	mjh_reader r;
+	mjh_reader_callbacks(&r, clbk, user);
+	return loadf_main(&r, x, y, comp, req_comp);
+}
+
+/* convert.c:331-336: unlike stbi_load_from_file, no seek back over what was read ahead */
+float *stbi_loadf_from_file(FILE *f, int *x, int *y, int *comp, int req_comp)
+{
+	mjh_reader r;
+	mjh_reader_file(&r, f);
+	return loadf_main(&r, x, y, comp, req_comp);
+}
+
+float *stbi_loadf(char const *filename, int *x, int *y, int *comp, int req_comp)
+{
+	FILE *f = fopen(filename, "rb");
+	float *result;
+	if (!f)
+		return (float *)fail_ptr("can't fopen");
+	result = stbi_loadf_from_file(f, x, y, comp, req_comp);
 	fclose(f);
 	return result;
 }

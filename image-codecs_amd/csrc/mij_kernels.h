@@ -2835,6 +2835,93 @@ __global__ __launch_bounds__(192) void k_encode444(const EncImage *__restrict__ 
 	}
 }
 
+/* ------------------------------------------------------------------ float output (mij_batch_set_out_f32, stbi_loadf*)
+ *
+ * k_out_f32 turns a slot's decoded bytes into floats through one 256-entry table per channel: byte i of the slot uses the
+ * table of channel i % n_out.  The tables are built on the host with the reference's own expression (stbi__ldr_to_hdr,
+ * common.c:391-424: a double pow per value), so the device only indexes them and the result is bit-exact by construction.
+ * One workgroup takes MIJ_F32_CHUNK bytes of one slot: it loads that slot's tables into LDS once, then every lane reads one
+ * 4-byte word and stores its four floats as one 16-byte store, so each wave store instruction writes 1 KiB of whole lines. */
+#define MIJ_F32_CHUNK 32768u     /* input bytes per workgroup (a multiple of 4: words never straddle chunks) */
+#define MIJ_F32_LUT_FLOATS 1024u /* floats per slot in the table arena: four 256-entry tables, the unused ones zero */
+#define MIJ_F32_LDS_STRIDE 264u  /* floats between the channel tables in LDS: channel k starts 8k banks further on, so the
+                                    R, G and B lookups of one grey value (ds_read_b32, 32 banks per half-wave) do not collide */
+
+struct DevF32 { /* one slot that asked for float output */
+	uint64_t src_off; /* byte offset of its n_out*W*H bytes in the output arena */
+	uint64_t dst_off; /* byte offset of its floats in the float arena (256-aligned) */
+	uint64_t nbytes;  /* n_out * width * height */
+	uint32_t n_out, pad;
+};
+struct WorkF32 { /* bytes [chunk * MIJ_F32_CHUNK, + MIJ_F32_CHUNK) of float slot f */
+	uint32_t f, chunk;
+};
+
+/* channel of byte j of a word whose first byte has channel c0 */
+template <int N>
+__device__ __forceinline__ uint32_t f32_chan(uint32_t c0, uint32_t j)
+{
+	if (N == 1)
+		return 0u;
+	if (N == 2)
+		return j & 1u;
+	if (N == 4)
+		return j;
+	const uint32_t k = c0 + j; /* N == 3: c0 < 3, j < 4 */
+	return k >= 3u ? k - 3u : k;
+}
+
+typedef float f4v __attribute__((ext_vector_type(4)));
+
+template <int N>
+__device__ __forceinline__ void f32_chunk(const float *lut, const uint32_t *__restrict__ src, f4v *__restrict__ dst, uint32_t nw, uint32_t ph0)
+{
+#pragma unroll 4
+	for (uint32_t i = threadIdx.x; i < nw; i += 256u) {
+		const uint32_t v = __builtin_nontemporal_load(src + i);
+		/* words start at multiples of 4 bytes: only three channels have a phase that moves from word to word */
+		const uint32_t c0 = N == 3 ? (ph0 + i) % 3u : 0u;
+		f4v o;
+		o.x = lut[f32_chan<N>(c0, 0) * MIJ_F32_LDS_STRIDE + (v & 255u)];
+		o.y = lut[f32_chan<N>(c0, 1) * MIJ_F32_LDS_STRIDE + ((v >> 8) & 255u)];
+		o.z = lut[f32_chan<N>(c0, 2) * MIJ_F32_LDS_STRIDE + ((v >> 16) & 255u)];
+		o.w = lut[f32_chan<N>(c0, 3) * MIJ_F32_LDS_STRIDE + (v >> 24)];
+		__builtin_nontemporal_store(o, dst + i);
+	}
+}
+
+__global__ __launch_bounds__(256) void k_out_f32(const DevF32 *__restrict__ fs, const WorkF32 *__restrict__ work, const float *__restrict__ luts,
+																  const uint8_t *__restrict__ out, uint8_t *__restrict__ f32)
+{
+	__shared__ float lut[4 * MIJ_F32_LDS_STRIDE];
+	const WorkF32 w = work[blockIdx.x];
+	const DevF32 s = fs[w.f];
+	const uint32_t n = s.n_out;
+	const float *g = luts + (size_t)w.f * MIJ_F32_LUT_FLOATS;
+	for (uint32_t t = threadIdx.x; t < n * 256u; t += 256u)
+		lut[(t >> 8) * MIJ_F32_LDS_STRIDE + (t & 255u)] = g[t];
+	__syncthreads();
+
+	const uint64_t b0 = (uint64_t)w.chunk * MIJ_F32_CHUNK;
+	const uint64_t left = s.nbytes - b0;
+	const uint32_t len = left < MIJ_F32_CHUNK ? (uint32_t)left : MIJ_F32_CHUNK, nw = len >> 2;
+	const uint8_t *src = out + s.src_off + b0; /* 4-aligned: slots start on 256 bytes, chunks on MIJ_F32_CHUNK */
+	uint8_t *dst = f32 + s.dst_off + 4u * b0;  /* 16-aligned */
+	const uint32_t ph0 = (uint32_t)(b0 % 3u);
+	switch (n) {
+	case 1: f32_chunk<1>(lut, reinterpret_cast<const uint32_t *>(src), reinterpret_cast<f4v *>(dst), nw, 0u); break;
+	case 2: f32_chunk<2>(lut, reinterpret_cast<const uint32_t *>(src), reinterpret_cast<f4v *>(dst), nw, 0u); break;
+	case 3: f32_chunk<3>(lut, reinterpret_cast<const uint32_t *>(src), reinterpret_cast<f4v *>(dst), nw, ph0); break;
+	default: f32_chunk<4>(lut, reinterpret_cast<const uint32_t *>(src), reinterpret_cast<f4v *>(dst), nw, 0u); break;
+	}
+	/* the slot's last 1-3 bytes when n_out * W * H is not a multiple of 4 (e.g. 33 x 17 x 3): one float each */
+	const uint32_t tail = len & 3u;
+	if (threadIdx.x < tail) {
+		const uint64_t i = b0 + 4u * nw + threadIdx.x;
+		reinterpret_cast<float *>(dst)[4u * nw + threadIdx.x] = lut[(uint32_t)(i % n) * MIJ_F32_LDS_STRIDE + src[4u * nw + threadIdx.x]];
+	}
+}
+
 } /* namespace mij */
 
 #endif

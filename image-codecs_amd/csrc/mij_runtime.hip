@@ -206,6 +206,7 @@ struct Slot {
 	int es_index;      /* index into the entropy arena's scan list, or -1 */
 	int coef_bytes_fmt; /* 1: compact planes in HBM (low bytes + escapes + DC array), 0: int16 tile layout */
 	int path;          /* 0 none, 1 fused 4:2:0, 2 two-pass, 3 fused 4:4:4, 4 fused 4:2:2, 5 fused grey, 6 fused 4:4:0 */
+	int f32;           /* float output: index of the slot's request (mij_batch::f32_req), -1 none */
 };
 
 /* kernel families of a launch plan, in launch order */
@@ -249,6 +250,19 @@ struct mij_batch {
 	int coef_fmt;  /* format new coefficient planes get in HBM: 1 compact (default), 0 int16 (MIJ_COEF_FORMAT=int16, mij_batch_set_coef_format) */
 	int band_rows; /* MCU rows per fused workgroup; 0 = automatic */
 	struct EsArena *es; /* GPU entropy stage, allocated by mij_batch_entropy_reserve */
+	/* float output (mij_batch_set_out_f32): the arena, one request per slot that asked (its place in the arena and its tables), and what
+	 * upload made of them for k_out_f32 -- descriptors, tables and (slot, chunk) work list in one pinned / device buffer pair */
+	uint8_t *d_f32;
+	size_t f32_cap, f32_used;
+	struct F32Req {
+		int slot;
+		size_t off;
+		float lut[MIJ_F32_LUT_FLOATS];
+	};
+	std::vector<F32Req> f32_req;
+	uint8_t *h_f32plan, *d_f32plan;
+	size_t f32plan_cap;
+	size_t f32_items, f32_lut_at, f32_work_at; /* work items of the last upload; byte offsets of the tables and the work list in the plan */
 };
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -300,6 +314,9 @@ extern "C" int mij_batch_create(mij_ctx *ctx, int max_images, size_t stage_bytes
 		b->coef_fmt = (fmt && (!strcmp(fmt, "int16") || !strcmp(fmt, "0"))) ? 0 : 1;
 	}
 	b->es = nullptr;
+	b->d_f32 = b->h_f32plan = b->d_f32plan = nullptr;
+	b->f32_cap = b->f32_used = b->f32plan_cap = 0;
+	b->f32_items = b->f32_lut_at = b->f32_work_at = 0;
 	b->stream = nullptr;
 	b->ev_begin = b->ev_end = nullptr;
 	b->ev_pack0 = b->ev_pack1 = nullptr;
@@ -365,6 +382,12 @@ extern "C" void mij_batch_destroy(mij_batch *b)
 		(void)hipHostFree(b->h_l1max);
 	if (b->es)
 		es_free_fwd(b->es);
+	if (b->d_f32)
+		(void)hipFree(b->d_f32);
+	if (b->h_f32plan)
+		(void)hipHostFree(b->h_f32plan);
+	if (b->d_f32plan)
+		(void)hipFree(b->d_f32plan);
 	if (b->ev_begin)
 		(void)hipEventDestroy(b->ev_begin);
 	if (b->ev_end)
@@ -388,6 +411,9 @@ extern "C" int mij_batch_reset(mij_batch *b)
 	b->stage_used = b->coef_used = b->out_used = 0;
 	b->uploaded = b->launched = false;
 	b->launches.clear();
+	b->f32_req.clear();
+	b->f32_used = 0;
+	b->f32_items = 0;
 	es_reset_fwd(b->es);
 	return MIJ_OK;
 }
@@ -512,6 +538,7 @@ static int add_common(mij_batch *b, const mij_image_desc *d, int clone_of, bool 
 	s.coef_bytes_fmt = clone_of >= 0 ? b->slots[(size_t)clone_of].coef_bytes_fmt : 0;
 	s.coef_bytes = cbytes;
 	s.path = 0;
+	s.f32 = -1;
 	if (clone_of < 0) {
 		if (b->stage_used + cbytes > b->stage_cap) {
 			if (!lazy_stage)
@@ -911,6 +938,51 @@ static size_t band_segment_lds(int mcu_x, int nseg, size_t bytes_per_col)
 	return (size_t)(widest + 2) * bytes_per_col;
 }
 
+/* Float output: k_out_f32's descriptors, tables and work list -- (float slot, chunk) items, MIJ_F32_CHUNK input bytes each -- built
+ * next to the decode plan and copied up on the batch stream.  A batch without float requests does nothing here. */
+static int f32_plan(mij_batch *b)
+{
+	b->f32_items = 0;
+	const size_t nreq = b->f32_req.size();
+	if (!nreq)
+		return MIJ_OK;
+	std::vector<WorkF32> work;
+	for (size_t f = 0; f < nreq; ++f) {
+		const Slot &s = b->slots[(size_t)b->f32_req[f].slot];
+		if (s.desc.flags & MIJ_FLAG_SKIP)
+			continue;
+		const uint64_t nbytes = (uint64_t)s.desc.n_out * (uint64_t)s.desc.width * (uint64_t)s.desc.height;
+		for (uint64_t c = 0; c * MIJ_F32_CHUNK < nbytes; ++c)
+			work.push_back(WorkF32{(uint32_t)f, (uint32_t)c});
+	}
+	if (work.empty())
+		return MIJ_OK;
+	const size_t lut_at = align_up(sizeof(DevF32) * nreq, 256), work_at = lut_at + sizeof(float) * MIJ_F32_LUT_FLOATS * nreq;
+	const size_t need = work_at + sizeof(WorkF32) * work.size();
+	if (need > b->f32plan_cap)
+		HIP_TRY(hipStreamSynchronize(b->stream));
+	int rc = grow_pair(b->h_f32plan, b->d_f32plan, b->f32plan_cap, align_up(need, 4));
+	if (rc != MIJ_OK)
+		return rc;
+	DevF32 *fd = reinterpret_cast<DevF32 *>(b->h_f32plan);
+	for (size_t f = 0; f < nreq; ++f) {
+		const mij_batch::F32Req &q = b->f32_req[f];
+		const Slot &s = b->slots[(size_t)q.slot];
+		fd[f].src_off = s.dev.out_off;
+		fd[f].dst_off = q.off;
+		fd[f].nbytes = (uint64_t)s.desc.n_out * (uint64_t)s.desc.width * (uint64_t)s.desc.height;
+		fd[f].n_out = (uint32_t)s.desc.n_out;
+		fd[f].pad = 0;
+		memcpy(b->h_f32plan + lut_at + sizeof(float) * MIJ_F32_LUT_FLOATS * f, q.lut, sizeof(q.lut));
+	}
+	memcpy(b->h_f32plan + work_at, work.data(), sizeof(WorkF32) * work.size());
+	HIP_TRY(copy_table(b->d_f32plan, b->h_f32plan, align_up(need, 4), b->stream));
+	b->f32_items = work.size();
+	b->f32_lut_at = lut_at;
+	b->f32_work_at = work_at;
+	return MIJ_OK;
+}
+
 extern "C" int mij_batch_upload(mij_batch *b)
 {
 	if (!b)
@@ -1275,6 +1347,8 @@ extern "C" int mij_batch_upload(mij_batch *b)
 		const Slot &src = b->slots[(size_t)s.clone_of];
 		HIP_TRY(hipMemcpyAsync(b->d_coef + s.coef_base, b->d_coef + src.coef_base, s.coef_bytes, hipMemcpyDeviceToDevice, b->stream));
 	}
+	if ((rc = f32_plan(b)) != MIJ_OK)
+		return rc;
 	b->uploaded = true;
 	b->launched = false;
 	return MIJ_OK;
@@ -1403,6 +1477,13 @@ extern "C" int mij_batch_launch(mij_batch *b)
 		}
 		HIP_TRY(hipGetLastError());
 	}
+	/* float output, behind every decode family (both front ends end here) */
+	if (b->f32_items) {
+		hipLaunchKernelGGL(k_out_f32, dim3((unsigned)b->f32_items), dim3(256), 0, b->stream, reinterpret_cast<const DevF32 *>(b->d_f32plan),
+								 reinterpret_cast<const WorkF32 *>(b->d_f32plan + b->f32_work_at), reinterpret_cast<const float *>(b->d_f32plan + b->f32_lut_at),
+								 b->d_out, b->d_f32);
+		HIP_TRY(hipGetLastError());
+	}
 	b->launched = true;
 	return MIJ_OK;
 }
@@ -1485,6 +1566,93 @@ extern "C" void *mij_batch_device_out(mij_batch *b, int slot)
 	if (!b || slot < 0 || slot >= (int)b->slots.size())
 		return nullptr;
 	return b->d_out + b->slots[(size_t)slot].dev.out_off;
+}
+
+/* ------------------------------------------------------------------ float output */
+
+extern "C" size_t mij_image_out_f32_bytes(const mij_image_desc *d) { return align_up(4 * (size_t)d->n_out * d->width * d->height, 256); }
+
+extern "C" int mij_batch_out_f32_reserve(mij_batch *b, size_t bytes)
+{
+	if (!b || !bytes)
+		return set_err(MIJ_E_ARG, "mij_batch_out_f32_reserve: bad argument");
+	if (bytes <= b->f32_cap)
+		return MIJ_OK;
+	if (!b->f32_req.empty())
+		return set_err(MIJ_E_STATE, "mij_batch_out_f32_reserve: slots hold float requests (reset the batch first)");
+	HIP_TRY(hipSetDevice(b->ctx->device));
+	HIP_TRY(hipStreamSynchronize(b->stream));
+	/* the new arena first, so that a failure leaves the old one in place; only when memory is short does the old one go first */
+	const size_t cap = align_up(bytes, 256);
+	uint8_t *p = nullptr;
+	hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), cap);
+	if (e == hipErrorOutOfMemory && b->d_f32) {
+		(void)hipGetLastError();
+		(void)hipFree(b->d_f32);
+		b->d_f32 = nullptr;
+		b->f32_cap = 0;
+		e = hipMalloc(reinterpret_cast<void **>(&p), cap);
+	}
+	if (e != hipSuccess) {
+		(void)hipGetLastError();
+		return set_err(e == hipErrorOutOfMemory ? MIJ_E_NOMEM : MIJ_E_HIP, "mij_batch_out_f32_reserve: %s", hipGetErrorString(e));
+	}
+	if (b->d_f32)
+		(void)hipFree(b->d_f32);
+	b->d_f32 = p;
+	b->f32_cap = cap;
+	return MIJ_OK;
+}
+
+extern "C" int mij_batch_set_out_f32(mij_batch *b, int slot, const float *lut)
+{
+	if (!b || slot < 0 || slot >= (int)b->slots.size() || !lut)
+		return set_err(MIJ_E_ARG, "mij_batch_set_out_f32: bad slot or table");
+	if (b->uploaded)
+		return set_err(MIJ_E_STATE, "mij_batch_set_out_f32 after mij_batch_upload");
+	Slot &s = b->slots[(size_t)slot];
+	if (s.desc.flags & MIJ_FLAG_SKIP)
+		return set_err(MIJ_E_STATE, "slot %d was rejected by the host stage", slot);
+	if (s.f32 < 0) {
+		const size_t need = mij_image_out_f32_bytes(&s.desc);
+		if (!b->d_f32 || b->f32_used + need > b->f32_cap)
+			return set_err(MIJ_E_ARG, "float arena too small (%zu of %zu bytes used, %zu needed; mij_batch_out_f32_reserve)", b->f32_used, b->f32_cap, need);
+		mij_batch::F32Req q;
+		q.slot = slot;
+		q.off = b->f32_used;
+		b->f32_req.push_back(q);
+		b->f32_used += need;
+		s.f32 = (int)b->f32_req.size() - 1;
+	}
+	float *t = b->f32_req[(size_t)s.f32].lut;
+	memset(t, 0, sizeof(float) * MIJ_F32_LUT_FLOATS);
+	memcpy(t, lut, sizeof(float) * 256 * (size_t)s.desc.n_out);
+	return MIJ_OK;
+}
+
+extern "C" int mij_batch_fetch_f32(mij_batch *b, int slot, float *dst, size_t dst_elems)
+{
+	if (!b || slot < 0 || slot >= (int)b->slots.size() || !dst)
+		return set_err(MIJ_E_ARG, "bad slot or destination");
+	const Slot &s = b->slots[(size_t)slot];
+	if (s.f32 < 0)
+		return set_err(MIJ_E_STATE, "slot %d has no float output (mij_batch_set_out_f32)", slot);
+	if (!b->launched)
+		return set_err(MIJ_E_STATE, "mij_batch_fetch_f32 before launch");
+	if (s.desc.flags & MIJ_FLAG_SKIP)
+		return set_err(MIJ_E_STATE, "slot %d was rejected by the host stage", slot);
+	const size_t elems = (size_t)s.desc.n_out * s.desc.width * s.desc.height;
+	if (dst_elems < elems)
+		return set_err(MIJ_E_ARG, "destination too small (%zu < %zu floats)", dst_elems, elems);
+	HIP_TRY(hipSetDevice(b->ctx->device));
+	return d2h_bounced(b->ctx, b->stream, dst, b->d_f32 + b->f32_req[(size_t)s.f32].off, elems * sizeof(float));
+}
+
+extern "C" void *mij_batch_device_out_f32(mij_batch *b, int slot)
+{
+	if (!b || slot < 0 || slot >= (int)b->slots.size() || b->slots[(size_t)slot].f32 < 0)
+		return nullptr;
+	return b->d_f32 + b->f32_req[(size_t)b->slots[(size_t)slot].f32].off;
 }
 
 extern "C" int mij_batch_timer_begin(mij_batch *b)

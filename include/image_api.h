@@ -12,7 +12,8 @@
  * IDCT, chroma up-sampling and YCbCr->RGB run in hand-written HIP kernels.  There is no CPU
  * fallback for those stages: without a GPU the loaders fail with reason "no gpu device".
  *
- * Only JPEG is handled (every other codec of the reference is out of scope).
+ * Only JPEG is handled (every other codec of the reference is out of scope); the float loaders
+ * (stbi_loadf*) take JPEG too, and the HDR format itself stays out of scope.
  */
 #ifndef IMAGE_API_H
 #define IMAGE_API_H
@@ -54,6 +55,25 @@ stbi_us *stbi_load_16(char const *filename, int *x, int *y, int *comp, int req_c
 stbi_us *stbi_load_from_file_16(FILE *f, int *x, int *y, int *comp, int req_comp);                                  /* convert.c:213 */
 stbi_us *stbi_load_16_from_memory(stbi_uc const *buffer, int len, int *x, int *y, int *comp, int req_comp);         /* convert.c:240 */
 stbi_us *stbi_load_16_from_callbacks(stbi_io_callbacks const *clbk, void *user, int *x, int *y, int *comp, int req_comp); /* convert.c:247 */
+
+/*
+ * Float loaders (stbi__loadf_main, convert.c:286-303): the 8-bit load above, vertical flip included, then per channel
+ * (float)(pow(v / 255.0f, gamma) * scale) for colour channels and v / 255.0f for alpha (comp 2 and 4), comp = req_comp ? req_comp
+ * : file comp (stbi__ldr_to_hdr, common.c:391-424).  gamma 2.2 and scale 1.0 unless set with stbi_ldr_to_hdr_gamma / _scale
+ * (process-global).  The conversion runs on the GPU through per-channel tables built on the host with libm's pow, so the floats are
+ * the reference's bit for bit.  Returns a malloc block of comp*x*y floats, free with stbi_image_free.  Every failure of the 8-bit
+ * load reads "unknown image type" (convert.c:302) except "no gpu device"; a block beyond INT_MAX bytes fails with "outofmem".
+ * stbi_loadf_from_file leaves the FILE* wherever reading stopped: unlike stbi_load_from_file it does not seek back over bytes it
+ * read ahead but did not use (convert.c:331-336 against :199-211).
+ */
+float *stbi_loadf(char const *filename, int *x, int *y, int *comp, int req_comp);                                    /* convert.c:320 */
+float *stbi_loadf_from_file(FILE *f, int *x, int *y, int *comp, int req_comp);                                      /* convert.c:331 */
+float *stbi_loadf_from_memory(stbi_uc const *buffer, int len, int *x, int *y, int *comp, int req_comp);             /* convert.c:305 */
+float *stbi_loadf_from_callbacks(stbi_io_callbacks const *clbk, void *user, int *x, int *y, int *comp, int req_comp); /* convert.c:312 */
+void stbi_ldr_to_hdr_gamma(float gamma);                                                                             /* convert.c:404 */
+void stbi_ldr_to_hdr_scale(float scale);                                                                             /* convert.c:405 */
+void stbi_hdr_to_ldr_gamma(float gamma); /* convert.c:410: stores 1/gamma, which only HDR input reads (never JPEG) */
+void stbi_hdr_to_ldr_scale(float scale); /* convert.c:411: stores 1/scale, likewise */
 
 /* header-only queries (host only; no GPU needed) */
 int stbi_info(char const *filename, int *x, int *y, int *comp);                                                     /* image_api.c:74 */

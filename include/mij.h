@@ -338,6 +338,25 @@ int mij_batch_idct_class_counts(mij_batch *b, uint64_t out[4]);
 int mij_batch_entropy_rounds(const mij_batch *b);
 
 /*
+ * Float output (stbi_loadf*, codec-free consumers that want float pixels in HBM).  A slot may ask, before upload, for its
+ * n_out*W*H bytes to be turned into as many floats by one 256-entry table per channel (byte i uses table i % n_out): a pass of
+ * its own (k_out_f32) behind every decode kernel of the launch writes them into a separate device arena.  mjh_ldr_to_hdr_lut
+ * (mij_host.h) builds the reference's stbi__ldr_to_hdr tables.  The slot's uint8 output stays valid and fetchable; a batch
+ * without float requests launches exactly what it launches without this section.  mij_batch_reset forgets every request.
+ */
+size_t mij_image_out_f32_bytes(const mij_image_desc *d); /* 4*n_out*width*height, rounded up to 256 */
+/* The float arena: bytes of device memory (grows only; MIJ_E_STATE while slots hold requests).  On MIJ_E_NOMEM the old arena is kept
+ * when there was room to try beside it, else the batch is left with none (set_out_f32 then gives MIJ_E_ARG until a reserve succeeds). */
+int mij_batch_out_f32_reserve(mij_batch *b, size_t bytes);
+/* lut = n_out*256 floats, table of channel k at lut[256*k], copied.  Before mij_batch_upload (else MIJ_E_STATE); MIJ_E_STATE for a
+ * skipped slot, MIJ_E_ARG when the arena has no room for mij_image_out_f32_bytes more.  Asking again replaces the tables. */
+int mij_batch_set_out_f32(mij_batch *b, int slot, const float *lut);
+/* D2H of a float slot's n_out*W*H floats (MIJ_E_STATE for a slot without float output or before launch); waits for the batch. */
+int mij_batch_fetch_f32(mij_batch *b, int slot, float *dst, size_t dst_elems);
+/* Device address of a float slot's floats (NULL for a slot without float output); valid until reset/destroy. */
+void *mij_batch_device_out_f32(mij_batch *b, int slot);
+
+/*
  * Encoder half (BASELINE config 5): the JPEG writer's colour transform, edge replication, 2x2
  * chroma mean, float AAN forward DCT and quantiser (codec/jpeg_write.c:24-74, :96-118, :283-352)
  * for a batch of images on the GPU.  Input: interleaved 8-bit pixels, comp 1..4 as passed to

@@ -145,6 +145,11 @@ int mij_write_jpg_batch(const void *const *pixels, const int *x, const int *y, c
 /* mjw_emit into memory: bytes written, 0 when `cap` is too small or an argument is bad (cap >= 1024 + 2 bytes per coefficient always fits) */
 size_t mjw_emit_to_memory(const mjw_plan *p, const int16_t *du, unsigned char *out, size_t cap);
 
+/* The tables of stbi__ldr_to_hdr (common.c:391-424) for mij_batch_set_out_f32: lut[256*k + v] for channel k < n_out.  Colour
+ * channels (all of them for odd n_out, all but the last for even n_out) get (float)(pow(v / 255.0f, gamma) * scale), the
+ * alpha channel of n_out 2 and 4 gets v / 255.0f -- the reference's expressions, evaluated with libm's pow. */
+void mjh_ldr_to_hdr_lut(int n_out, float gamma, float scale, float *lut);
+
 #ifdef __cplusplus
 }
 #endif
