@@ -19,6 +19,13 @@ from .binding import (  # noqa: F401
     MijError,
     ImageDesc,
     Batch,
+    OutTensor,
+    MIJ_DT_U8,
+    MIJ_DT_F16,
+    MIJ_DT_BF16,
+    MIJ_DT_F32,
+    MIJ_LAYOUT_HWC,
+    MIJ_LAYOUT_CHW,
     Context,
     Encoder,
     PinnedBuffer,
@@ -59,3 +66,14 @@ from .binding import (  # noqa: F401
     gpu_available,
 )
 from .synth import synth_rgb, synth_jpeg, synth_rgb_edges  # noqa: F401
+
+_TENSOR_OUT = ("TensorDecoder", "tensor_tables")
+
+
+def __getattr__(name):
+    """TensorDecoder and tensor_tables live in tensor_out, which imports torch: loaded on first use, so that importing the package
+    does not import torch."""
+    if name in _TENSOR_OUT:
+        from . import tensor_out
+        return getattr(tensor_out, name)
+    raise AttributeError("module 'image_codecs_amd' has no attribute %r" % name)

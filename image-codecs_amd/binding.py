@@ -565,6 +565,18 @@ def _check(rc, what):
     return rc
 
 
+MIJ_DT_U8, MIJ_DT_F16, MIJ_DT_BF16, MIJ_DT_F32 = 0, 1, 2, 3
+MIJ_LAYOUT_HWC, MIJ_LAYOUT_CHW = 0, 1
+_DTYPES = {"u8": MIJ_DT_U8, "f16": MIJ_DT_F16, "bf16": MIJ_DT_BF16, "f32": MIJ_DT_F32}
+_LAYOUTS = {"HWC": MIJ_LAYOUT_HWC, "CHW": MIJ_LAYOUT_CHW}
+
+
+class OutTensor(C.Structure):
+    """mij_out_tensor (include/mij.h)."""
+    _fields_ = [("dst", C.c_void_p), ("dtype", C.c_int32), ("layout", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32),
+                ("h", C.c_int32), ("flip_x", C.c_int32), ("flip_y", C.c_int32), ("row_pitch", C.c_int64), ("plane_pitch", C.c_int64)]
+
+
 class Context:
     """mij_ctx: one per (process, device)."""
 
@@ -886,6 +898,23 @@ class Batch:
         L.mij_batch_device_out_f32.restype = C.c_void_p
         L.mij_batch_device_out_f32.argtypes = [C.c_void_p, C.c_int]
         return L.mij_batch_device_out_f32(self._h, int(slot))
+
+    # ---- tensor output (mij_batch_set_out_tensor): k_out_tensor writes a crop window into device memory the caller owns
+    def set_out_tensor(self, slot, dst, dtype, layout, x0, y0, w, h, row_pitch, plane_pitch=0, flip_x=False, flip_y=False, table=None):
+        """dst: raw device address; dtype MIJ_DT_* (or "u8", "f16", "bf16", "f32"), layout MIJ_LAYOUT_* (or "HWC", "CHW"); pitches in
+        elements; table: n_out*256 elements of dtype as any buffer (e.g. numpy uint16 for f16 / bf16), None only for u8 (identity)."""
+        t = OutTensor(C.c_void_p(int(dst)), _DTYPES.get(dtype, dtype), _LAYOUTS.get(layout, layout), int(x0), int(y0), int(w), int(h),
+                      int(bool(flip_x)), int(bool(flip_y)), int(row_pitch), int(plane_pitch))
+        tp = None
+        if table is not None:
+            tb = np.ascontiguousarray(table)
+            need = 256 * self._desc(slot).n_out * (1, 2, 2, 4)[t.dtype] if 0 <= t.dtype <= 3 else 0
+            if tb.nbytes < need:
+                raise ValueError("table has %d bytes, %d needed" % (tb.nbytes, need))
+            tp = tb.ctypes.data_as(C.c_void_p)
+        L = lib()
+        L.mij_batch_set_out_tensor.argtypes = [C.c_void_p, C.c_int, C.POINTER(OutTensor), C.c_void_p]
+        _check(L.mij_batch_set_out_tensor(self._h, int(slot), C.byref(t), tp), "mij_batch_set_out_tensor")
 
     def fetch_all_async(self, dst_ptr, dst_bytes):
         """mij_batch_fetch_all_async into a (pinned) host buffer; wait() completes it."""

@@ -2922,6 +2922,128 @@ __global__ __launch_bounds__(256) void k_out_f32(const DevF32 *__restrict__ fs, 
 	}
 }
 
+/* ------------------------------------------------------------------ tensor output (mij_batch_set_out_tensor)
+ *
+ * k_out_tensor copies a crop window of a slot's decoded bytes into memory the caller owns, optionally flipped, as HWC or CHW, each
+ * value through one 256-entry table per channel of the output element type (u8, f16, bf16 or f32; a u8 request without tables is
+ * the identity).  The tables are built on the host, so the device only indexes them, as in k_out_f32.
+ * A work item is (request, band of window rows, segment of window columns) of at most MIJ_TEN_ITEM_BYTES source bytes.  Phase 1
+ * stages the band's source bytes in LDS as aligned dwords (the first one may start before the window); phase 2 walks each output
+ * line -- a window row for HWC, one channel of a window row for CHW -- in units: a head up to the first 16-byte boundary of the
+ * destination, then 16-byte aligned stores, then a tail.  The head and the tail are stored element by element, so nothing outside
+ * the destination elements is written whatever the alignment and pitches.  CHW de-interleaves by reading the staged bytes from LDS. */
+#define MIJ_TEN_ITEM_BYTES 24576u /* source bytes per work item */
+#define MIJ_TEN_MAX_ROWS 128u     /* window rows per work item (bounds the dword slack of phase 1) */
+#define MIJ_TEN_STAGE_WORDS ((MIJ_TEN_ITEM_BYTES + 8u * MIJ_TEN_MAX_ROWS) / 4u)
+#define MIJ_TEN_LUT_BYTES 4096u   /* bytes per request in the table area: four 256-entry tables of up to 4-byte elements */
+#define MIJ_TEN_LDS_PAD 32u       /* bytes between the channel tables in LDS: each channel starts 8 banks further on */
+
+struct DevTensor { /* one slot that asked for tensor output */
+	uint64_t src_off;               /* byte offset of its n_out*W*H bytes in the output arena */
+	uint64_t dst;                   /* caller's device address (validated on the host) */
+	int64_t row_pitch, plane_pitch; /* elements */
+	uint32_t src_w, n_out;
+	uint32_t x0, y0, w, h;
+	uint32_t flip_x, flip_y;
+	uint32_t esize, chw; /* bytes per output element (1, 2, 4); 1 for CHW */
+	uint32_t lut, pad;   /* lut 0: identity (u8 without tables) */
+};
+struct WorkTensor { /* window rows [row0, row0 + nrows) x window columns [p0, p0 + np) of request t */
+	uint32_t t, row0, p0;
+	uint16_t nrows, np;
+};
+
+typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+
+template <typename T, bool CHW, int N>
+__device__ __forceinline__ void tensor_item(const DevTensor &s, const WorkTensor &wk, const uint8_t *__restrict__ out, const uint8_t *lut, uint32_t *stage)
+{
+	constexpr uint32_t ES = sizeof(T), V = 16u / ES, LS = 256u * ES + MIJ_TEN_LDS_PAD, PW = 4u / ES;
+	const uint32_t np = wk.np, nr = wk.nrows, nb = np * N;
+	const uint32_t lsd = (nb + 6u) >> 2; /* dwords per staged row: room for a start up to 3 bytes before the window */
+	const uint32_t sxa = s.flip_x ? s.x0 + s.w - wk.p0 - np : s.x0 + wk.p0; /* first source column of the segment */
+	const uint64_t rowb = (uint64_t)s.src_w * N;
+	for (uint32_t i = threadIdx.x; i < nr * lsd; i += 256u) {
+		const uint32_t r = i / lsd, k = i - r * lsd, oy = wk.row0 + r;
+		const uint32_t sy = s.flip_y ? s.y0 + s.h - 1u - oy : s.y0 + oy;
+		const uint64_t a = s.src_off + sy * rowb + (uint64_t)sxa * N;
+		/* the dwords that hold the segment's bytes; the last ends inside the slot's 256-aligned region of the arena */
+		if (k < (((uint32_t)(a & 3u) + nb + 3u) >> 2))
+			stage[i] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(out + (a & ~(uint64_t)3)) + k);
+	}
+	__syncthreads();
+	const uint8_t *sb = reinterpret_cast<const uint8_t *>(stage);
+	const uint32_t E = CHW ? np : nb, nl = CHW ? nr * N : nr, um = E / V + 2u;
+	for (uint32_t i = threadIdx.x; i < nl * um; i += 256u) {
+		const uint32_t line = i / um, u = i - line * um;
+		const uint32_t r = CHW ? line / N : line, pc = CHW ? line - r * N : 0u, oy = wk.row0 + r;
+		const uint32_t sy = s.flip_y ? s.y0 + s.h - 1u - oy : s.y0 + oy;
+		const uint8_t *srow = sb + r * lsd * 4u + (uint32_t)((s.src_off + sy * rowb + (uint64_t)sxa * N) & 3u);
+		T *d = reinterpret_cast<T *>(s.dst) + (int64_t)oy * s.row_pitch + (CHW ? (int64_t)pc * s.plane_pitch + wk.p0 : (int64_t)wk.p0 * N);
+		const uint32_t head = (uint32_t)(((16u - ((uintptr_t)d & 15u)) & 15u) / ES);
+		const uint32_t e0 = u ? head + (u - 1u) * V : 0u;
+		const uint32_t e1 = u ? min(E, e0 + V) : min(E, head);
+		if (e0 >= e1)
+			continue;
+		auto value = [&](uint32_t e) -> T {
+			const uint32_t q = CHW ? e : e / N, c = CHW ? pc : e - q * N;
+			const uint32_t v = srow[(s.flip_x ? np - 1u - q : q) * N + c];
+			return s.lut ? reinterpret_cast<const T *>(lut + c * LS)[v] : (T)v;
+		};
+		if (u && e1 - e0 == V) { /* 16-byte aligned: one store */
+			u4v o;
+#pragma unroll
+			for (uint32_t k = 0; k < 4u; ++k) {
+				uint32_t wd = 0;
+#pragma unroll
+				for (uint32_t j = 0; j < PW; ++j)
+					wd |= (uint32_t)value(e0 + k * PW + j) << (8u * ES * j);
+				o[k] = wd;
+			}
+			__builtin_nontemporal_store(o, reinterpret_cast<u4v *>(d + e0));
+		} else {
+			for (uint32_t e = e0; e < e1; ++e)
+				d[e] = value(e);
+		}
+	}
+}
+
+template <typename T, bool CHW>
+__device__ __forceinline__ void tensor_item_n(const DevTensor &s, const WorkTensor &wk, const uint8_t *__restrict__ out, const uint8_t *lut, uint32_t *stage)
+{
+	switch (s.n_out) {
+	case 1: tensor_item<T, CHW, 1>(s, wk, out, lut, stage); break;
+	case 2: tensor_item<T, CHW, 2>(s, wk, out, lut, stage); break;
+	case 3: tensor_item<T, CHW, 3>(s, wk, out, lut, stage); break;
+	default: tensor_item<T, CHW, 4>(s, wk, out, lut, stage); break;
+	}
+}
+
+__global__ __launch_bounds__(256) void k_out_tensor(const DevTensor *__restrict__ ts, const WorkTensor *__restrict__ work, const uint8_t *__restrict__ luts,
+																	 const uint8_t *__restrict__ out)
+{
+	__shared__ uint32_t stage[MIJ_TEN_STAGE_WORDS];
+	__shared__ uint32_t lutw[4u * (1024u + MIJ_TEN_LDS_PAD) / 4u];
+	const WorkTensor wk = work[blockIdx.x];
+	const DevTensor s = ts[wk.t];
+	if (s.lut) {
+		const uint32_t tw = 64u * s.esize, lsw = tw + MIJ_TEN_LDS_PAD / 4u; /* dwords per table in the plan, per table in LDS */
+		const uint32_t *g = reinterpret_cast<const uint32_t *>(luts + (size_t)wk.t * MIJ_TEN_LUT_BYTES);
+		for (uint32_t t = threadIdx.x; t < s.n_out * tw; t += 256u)
+			lutw[(t / tw) * lsw + t % tw] = g[t];
+	}
+	const uint8_t *lut = reinterpret_cast<const uint8_t *>(lutw);
+	/* tensor_item's __syncthreads orders the table writes before the lookups */
+	switch (s.esize * 2u + s.chw) {
+	case 2: tensor_item_n<uint8_t, false>(s, wk, out, lut, stage); break;
+	case 3: tensor_item_n<uint8_t, true>(s, wk, out, lut, stage); break;
+	case 4: tensor_item_n<uint16_t, false>(s, wk, out, lut, stage); break;
+	case 5: tensor_item_n<uint16_t, true>(s, wk, out, lut, stage); break;
+	case 8: tensor_item_n<uint32_t, false>(s, wk, out, lut, stage); break;
+	default: tensor_item_n<uint32_t, true>(s, wk, out, lut, stage); break;
+	}
+}
+
 } /* namespace mij */
 
 #endif

@@ -207,6 +207,7 @@ struct Slot {
 	int coef_bytes_fmt; /* 1: compact planes in HBM (low bytes + escapes + DC array), 0: int16 tile layout */
 	int path;          /* 0 none, 1 fused 4:2:0, 2 two-pass, 3 fused 4:4:4, 4 fused 4:2:2, 5 fused grey, 6 fused 4:4:0 */
 	int f32;           /* float output: index of the slot's request (mij_batch::f32_req), -1 none */
+	int ten;           /* tensor output: index of the slot's request (mij_batch::ten_req), -1 none */
 };
 
 /* kernel families of a launch plan, in launch order */
@@ -263,6 +264,19 @@ struct mij_batch {
 	uint8_t *h_f32plan, *d_f32plan;
 	size_t f32plan_cap;
 	size_t f32_items, f32_lut_at, f32_work_at; /* work items of the last upload; byte offsets of the tables and the work list in the plan */
+	/* tensor output (mij_batch_set_out_tensor): one validated request per slot that asked, and what upload made of them for
+	 * k_out_tensor -- descriptors, tables and (request, rows, columns) work list in one pinned / device buffer pair */
+	struct TenReq {
+		int slot;
+		mij_out_tensor t;
+		uint32_t esize;
+		bool lut;
+		uint8_t table[MIJ_TEN_LUT_BYTES];
+	};
+	std::vector<TenReq> ten_req;
+	uint8_t *h_tenplan, *d_tenplan;
+	size_t tenplan_cap;
+	size_t ten_items, ten_lut_at, ten_work_at;
 };
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -317,6 +331,9 @@ extern "C" int mij_batch_create(mij_ctx *ctx, int max_images, size_t stage_bytes
 	b->d_f32 = b->h_f32plan = b->d_f32plan = nullptr;
 	b->f32_cap = b->f32_used = b->f32plan_cap = 0;
 	b->f32_items = b->f32_lut_at = b->f32_work_at = 0;
+	b->h_tenplan = b->d_tenplan = nullptr;
+	b->tenplan_cap = 0;
+	b->ten_items = b->ten_lut_at = b->ten_work_at = 0;
 	b->stream = nullptr;
 	b->ev_begin = b->ev_end = nullptr;
 	b->ev_pack0 = b->ev_pack1 = nullptr;
@@ -388,6 +405,10 @@ extern "C" void mij_batch_destroy(mij_batch *b)
 		(void)hipHostFree(b->h_f32plan);
 	if (b->d_f32plan)
 		(void)hipFree(b->d_f32plan);
+	if (b->h_tenplan)
+		(void)hipHostFree(b->h_tenplan);
+	if (b->d_tenplan)
+		(void)hipFree(b->d_tenplan);
 	if (b->ev_begin)
 		(void)hipEventDestroy(b->ev_begin);
 	if (b->ev_end)
@@ -414,6 +435,8 @@ extern "C" int mij_batch_reset(mij_batch *b)
 	b->f32_req.clear();
 	b->f32_used = 0;
 	b->f32_items = 0;
+	b->ten_req.clear();
+	b->ten_items = 0;
 	es_reset_fwd(b->es);
 	return MIJ_OK;
 }
@@ -539,6 +562,7 @@ static int add_common(mij_batch *b, const mij_image_desc *d, int clone_of, bool 
 	s.coef_bytes = cbytes;
 	s.path = 0;
 	s.f32 = -1;
+	s.ten = -1;
 	if (clone_of < 0) {
 		if (b->stage_used + cbytes > b->stage_cap) {
 			if (!lazy_stage)
@@ -983,6 +1007,71 @@ static int f32_plan(mij_batch *b)
 	return MIJ_OK;
 }
 
+/* Tensor output: k_out_tensor's descriptors, tables and work list -- (request, band of window rows, segment of window columns) items of
+ * at most MIJ_TEN_ITEM_BYTES source bytes and MIJ_TEN_MAX_ROWS rows -- built next to the decode plan and copied up on the batch stream.
+ * A batch without tensor requests does nothing here. */
+static int ten_plan(mij_batch *b)
+{
+	b->ten_items = 0;
+	const size_t nreq = b->ten_req.size();
+	if (!nreq)
+		return MIJ_OK;
+	std::vector<WorkTensor> work;
+	for (size_t t = 0; t < nreq; ++t) {
+		const mij_batch::TenReq &q = b->ten_req[t];
+		if (b->slots[(size_t)q.slot].desc.flags & MIJ_FLAG_SKIP)
+			continue;
+		const uint32_t c = (uint32_t)b->slots[(size_t)q.slot].desc.n_out, w = (uint32_t)q.t.w, h = (uint32_t)q.t.h;
+		const uint32_t segw = std::min(w, MIJ_TEN_ITEM_BYTES / c);
+		for (uint32_t p0 = 0; p0 < w; p0 += segw) {
+			const uint32_t np = std::min(segw, w - p0);
+			const uint32_t rows = std::max(1u, std::min(std::min(h, MIJ_TEN_MAX_ROWS), MIJ_TEN_ITEM_BYTES / (np * c)));
+			for (uint32_t r0 = 0; r0 < h; r0 += rows)
+				work.push_back(WorkTensor{(uint32_t)t, r0, p0, (uint16_t)std::min(rows, h - r0), (uint16_t)np});
+		}
+	}
+	if (work.empty())
+		return MIJ_OK;
+	if (work.size() > 0x7fffffffu)
+		return set_err(MIJ_E_ARG, "tensor output: %zu work items", work.size());
+	const size_t lut_at = align_up(sizeof(DevTensor) * nreq, 256), work_at = lut_at + MIJ_TEN_LUT_BYTES * nreq;
+	const size_t need = work_at + sizeof(WorkTensor) * work.size();
+	if (need > b->tenplan_cap)
+		HIP_TRY(hipStreamSynchronize(b->stream));
+	int rc = grow_pair(b->h_tenplan, b->d_tenplan, b->tenplan_cap, align_up(need, 4));
+	if (rc != MIJ_OK)
+		return rc;
+	DevTensor *td = reinterpret_cast<DevTensor *>(b->h_tenplan);
+	for (size_t t = 0; t < nreq; ++t) {
+		const mij_batch::TenReq &q = b->ten_req[t];
+		const Slot &s = b->slots[(size_t)q.slot];
+		DevTensor &d = td[t];
+		d.src_off = s.dev.out_off;
+		d.dst = (uint64_t)(uintptr_t)q.t.dst;
+		d.row_pitch = q.t.row_pitch;
+		d.plane_pitch = q.t.layout == MIJ_LAYOUT_CHW ? q.t.plane_pitch : 0;
+		d.src_w = (uint32_t)s.desc.width;
+		d.n_out = (uint32_t)s.desc.n_out;
+		d.x0 = (uint32_t)q.t.x0;
+		d.y0 = (uint32_t)q.t.y0;
+		d.w = (uint32_t)q.t.w;
+		d.h = (uint32_t)q.t.h;
+		d.flip_x = q.t.flip_x ? 1u : 0u;
+		d.flip_y = q.t.flip_y ? 1u : 0u;
+		d.esize = q.esize;
+		d.chw = q.t.layout == MIJ_LAYOUT_CHW ? 1u : 0u;
+		d.lut = q.lut ? 1u : 0u;
+		d.pad = 0;
+		memcpy(b->h_tenplan + lut_at + MIJ_TEN_LUT_BYTES * t, q.table, MIJ_TEN_LUT_BYTES);
+	}
+	memcpy(b->h_tenplan + work_at, work.data(), sizeof(WorkTensor) * work.size());
+	HIP_TRY(copy_table(b->d_tenplan, b->h_tenplan, align_up(need, 4), b->stream));
+	b->ten_items = work.size();
+	b->ten_lut_at = lut_at;
+	b->ten_work_at = work_at;
+	return MIJ_OK;
+}
+
 extern "C" int mij_batch_upload(mij_batch *b)
 {
 	if (!b)
@@ -1349,6 +1438,8 @@ extern "C" int mij_batch_upload(mij_batch *b)
 	}
 	if ((rc = f32_plan(b)) != MIJ_OK)
 		return rc;
+	if ((rc = ten_plan(b)) != MIJ_OK)
+		return rc;
 	b->uploaded = true;
 	b->launched = false;
 	return MIJ_OK;
@@ -1482,6 +1573,12 @@ extern "C" int mij_batch_launch(mij_batch *b)
 		hipLaunchKernelGGL(k_out_f32, dim3((unsigned)b->f32_items), dim3(256), 0, b->stream, reinterpret_cast<const DevF32 *>(b->d_f32plan),
 								 reinterpret_cast<const WorkF32 *>(b->d_f32plan + b->f32_work_at), reinterpret_cast<const float *>(b->d_f32plan + b->f32_lut_at),
 								 b->d_out, b->d_f32);
+		HIP_TRY(hipGetLastError());
+	}
+	/* tensor output into the callers' memory, behind the float pass */
+	if (b->ten_items) {
+		hipLaunchKernelGGL(k_out_tensor, dim3((unsigned)b->ten_items), dim3(256), 0, b->stream, reinterpret_cast<const DevTensor *>(b->d_tenplan),
+								 reinterpret_cast<const WorkTensor *>(b->d_tenplan + b->ten_work_at), b->d_tenplan + b->ten_lut_at, b->d_out);
 		HIP_TRY(hipGetLastError());
 	}
 	b->launched = true;
@@ -1653,6 +1750,69 @@ extern "C" void *mij_batch_device_out_f32(mij_batch *b, int slot)
 	if (!b || slot < 0 || slot >= (int)b->slots.size() || b->slots[(size_t)slot].f32 < 0)
 		return nullptr;
 	return b->d_f32 + b->f32_req[(size_t)b->slots[(size_t)slot].f32].off;
+}
+
+/* ------------------------------------------------------------------ tensor output */
+
+extern "C" int mij_batch_set_out_tensor(mij_batch *b, int slot, const mij_out_tensor *t, const void *table)
+{
+	if (!b || slot < 0 || slot >= (int)b->slots.size() || !t)
+		return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor: bad slot or request");
+	if (b->uploaded)
+		return set_err(MIJ_E_STATE, "mij_batch_set_out_tensor after mij_batch_upload");
+	Slot &s = b->slots[(size_t)slot];
+	if (s.desc.flags & MIJ_FLAG_SKIP)
+		return set_err(MIJ_E_STATE, "slot %d was rejected by the host stage", slot);
+	if (t->dtype < MIJ_DT_U8 || t->dtype > MIJ_DT_F32 || (t->layout != MIJ_LAYOUT_HWC && t->layout != MIJ_LAYOUT_CHW))
+		return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor: dtype %d / layout %d unknown", t->dtype, t->layout);
+	if (!table && t->dtype != MIJ_DT_U8)
+		return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor: a table is required for dtype %d", t->dtype);
+	const int64_t W = s.desc.width, H = s.desc.height, C = s.desc.n_out;
+	if (t->w < 1 || t->h < 1 || t->x0 < 0 || t->y0 < 0 || (int64_t)t->x0 + t->w > W || (int64_t)t->y0 + t->h > H)
+		return set_err(MIJ_E_ARG, "window %d,%d %dx%d outside the %lldx%lld picture of slot %d", t->x0, t->y0, t->w, t->h, (long long)W, (long long)H, slot);
+	const bool chw = t->layout == MIJ_LAYOUT_CHW;
+	const int64_t w = t->w, h = t->h, rp = t->row_pitch, pp = chw ? t->plane_pitch : 0;
+	const int64_t lim = (int64_t)1 << 40; /* keeps the extent below in range */
+	if (rp < 0 || rp > lim || pp < 0 || pp > lim)
+		return set_err(MIJ_E_ARG, "pitch out of range (row %lld, plane %lld)", (long long)rp, (long long)pp);
+	const int64_t line = chw ? w : w * C;
+	if ((h > 1 && rp < line) || (chw && C > 1 && pp < (h - 1) * rp + w))
+		return set_err(MIJ_E_ARG, "pitches let rows or planes overlap (row %lld, plane %lld; %lldx%lldx%lld %s)", (long long)rp, (long long)pp, (long long)w,
+							(long long)h, (long long)C, chw ? "CHW" : "HWC");
+	const uint32_t es = t->dtype == MIJ_DT_U8 ? 1u : (t->dtype == MIJ_DT_F32 ? 4u : 2u);
+	const uintptr_t dst = (uintptr_t)t->dst;
+	if (!dst || (dst & (es - 1u)))
+		return set_err(MIJ_E_ARG, "dst %p is not aligned to its %u-byte elements", t->dst, es);
+	const uint64_t last = (uint64_t)((h - 1) * rp + (chw ? (C - 1) * pp + w - 1 : w * C - 1)); /* element offset of the last element */
+	const uint64_t extent = (last + 1) * es;
+	HIP_TRY(hipSetDevice(b->ctx->device));
+	hipPointerAttribute_t pa;
+	memset(&pa, 0, sizeof(pa));
+	hipError_t e = hipPointerGetAttributes(&pa, t->dst);
+	if (e != hipSuccess || pa.type != hipMemoryTypeDevice || pa.isManaged || pa.device != b->ctx->device) {
+		(void)hipGetLastError();
+		return set_err(MIJ_E_ARG, "dst %p is not device memory of device %d", t->dst, b->ctx->device);
+	}
+	hipDeviceptr_t base = nullptr;
+	size_t size = 0;
+	e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)t->dst);
+	if (e != hipSuccess || !base || dst < (uintptr_t)base || dst - (uintptr_t)base > size || extent > size - (dst - (uintptr_t)base)) {
+		(void)hipGetLastError();
+		return set_err(MIJ_E_ARG, "the %llu bytes from dst %p are not inside one allocation (%p, %zu bytes)", (unsigned long long)extent, t->dst, (void *)base, size);
+	}
+	if (s.ten < 0) {
+		b->ten_req.emplace_back();
+		b->ten_req.back().slot = slot;
+		s.ten = (int)b->ten_req.size() - 1;
+	}
+	mij_batch::TenReq &q = b->ten_req[(size_t)s.ten];
+	q.t = *t;
+	q.esize = es;
+	q.lut = table != nullptr;
+	memset(q.table, 0, sizeof(q.table));
+	if (table)
+		memcpy(q.table, table, (size_t)es * 256 * (size_t)C);
+	return MIJ_OK;
 }
 
 extern "C" int mij_batch_timer_begin(mij_batch *b)

@@ -1,0 +1,210 @@
+"""Batch decode straight into device tensors: crop window, flips, layout and per-channel normalisation done by k_out_tensor
+(mij_batch_set_out_tensor) behind the decode kernels, written into memory the caller's torch tensor owns.
+
+Importing this module imports torch; ``import image_codecs_amd`` alone does not (TensorDecoder and tensor_tables are loaded
+from here on first use)."""
+import torch
+
+from .binding import Batch, Context, HostDecoder, MijError, MIJ_DT_U8, MIJ_DT_F16, MIJ_DT_BF16, MIJ_DT_F32, MIJ_LAYOUT_HWC, MIJ_LAYOUT_CHW
+
+_DT = {torch.uint8: MIJ_DT_U8, torch.float16: MIJ_DT_F16, torch.bfloat16: MIJ_DT_BF16, torch.float32: MIJ_DT_F32}
+_BITS = {torch.uint8: torch.uint8, torch.float16: torch.int16, torch.bfloat16: torch.int16, torch.float32: torch.int32}
+
+
+def tensor_tables(n_out, dtype, mean=None, std=None):
+    """[n_out, 256] tables of dtype on the CPU: the value table[c][v] that channel c's byte v becomes.  The contract:
+    ((torch.arange(256, dtype=torch.float32) / 255 - mean[c]) / std[c]).to(dtype), with mean / std omitted meaning v / 255, and the
+    identity for torch.uint8 (which takes no mean / std)."""
+    n_out = int(n_out)
+    if dtype not in _DT:
+        raise ValueError("dtype must be one of uint8, float16, bfloat16, float32 (got %s)" % (dtype,))
+    if dtype == torch.uint8:
+        if mean is not None or std is not None:
+            raise ValueError("uint8 output takes no mean / std")
+        return torch.arange(256, dtype=torch.uint8).repeat(n_out, 1)
+    v = torch.arange(256, dtype=torch.float32) / 255
+    if mean is None and std is None:
+        return v.to(dtype).repeat(n_out, 1)
+    mean = _per_channel(mean, n_out, "mean", 0.0)
+    std = _per_channel(std, n_out, "std", 1.0)
+    return torch.stack([((v - mean[c]) / std[c]).to(dtype) for c in range(n_out)])
+
+
+def _per_channel(vals, n_out, what, default):
+    if vals is None:
+        return [default] * n_out
+    vals = [float(x) for x in vals]
+    if len(vals) != n_out:
+        raise ValueError("%s has %d values for %d channels" % (what, len(vals), n_out))
+    return vals
+
+
+def _flags(v, n, what):
+    if v is None:
+        return [False] * n
+    if isinstance(v, bool):
+        return [v] * n
+    v = [bool(x) for x in v]
+    if len(v) != n:
+        raise ValueError("%s has %d entries for %d pictures" % (what, len(v), n))
+    return v
+
+
+def _one_hip_runtime():
+    """torch and the library must share one HIP runtime, or torch's allocations are unknown to the library (which then refuses them).
+    They do when torch is imported before the library is first loaded; loaded the other way round, torch brings its own copy."""
+    with open("/proc/self/maps") as f:
+        paths = {ln.split()[-1] for ln in f if "libamdhip64" in ln}
+    if len(paths) > 1:
+        raise RuntimeError("two HIP runtimes in this process (%s): import torch before the first call into image_codecs_amd" % ", ".join(sorted(paths)))
+
+
+class TensorDecoder:
+    """Decodes batches of JPEGs into one [N, C, h, w] (layout "CHW") or [N, h, w, C] ("HWC") tensor on a GPU.  Owns a Context and a
+    Batch, grown as needed and reused across calls.  decode() is synchronous: it synchronises the device's current torch stream
+    before the batch writes the tensor and waits for the batch before it returns."""
+
+    def __init__(self, device=None):
+        dev = torch.device("cuda") if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("TensorDecoder needs a GPU device, got %s" % dev)
+        self._dev = dev  # without an index: the current device, looked up at first use (argument checks need no device)
+        self._ctx = None
+        self._batch = None
+        self._cap = (0, 0, 0)
+
+    @property
+    def device(self):
+        if self._dev.index is None:
+            self._dev = torch.device("cuda", torch.cuda.current_device())
+        return self._dev
+
+    def close(self):
+        if self._batch is not None:
+            self._batch.close()
+            self._batch = None
+        if self._ctx is not None:
+            self._ctx.close()
+            self._ctx = None
+        self._cap = (0, 0, 0)
+
+    def _batch_for(self, n, coef, out):
+        need = (max(1, n), max(coef, 256), max(out, 256))
+        if self._batch is None or any(a > b for a, b in zip(need, self._cap)):
+            if self._batch is not None:
+                self._batch.close()
+                self._batch = None
+            if self._ctx is None:
+                self._ctx = Context(self.device.index)
+            cap = tuple(max(a, b) for a, b in zip(need, self._cap))
+            self._batch = Batch(self._ctx, cap[0], cap[1], cap[1], cap[2])
+            self._cap = cap
+        else:
+            self._batch.reset()
+        return self._batch
+
+    def decode(self, datas, *, req_comp=3, crops=None, flip_x=None, flip_y=None, layout="CHW", dtype=torch.float16, mean=None, std=None,
+               out=None, threads=16):
+        """-> (tensor, reasons).  crops: None (the whole picture; every picture the same size) or one (x0, y0, w, h) per picture, all of
+        the same w and h.  flip_x / flip_y: None, one bool for all, or one per picture.  The value of channel c's byte v is
+        tensor_tables(C, dtype, mean, std)[c][v].  out: a tensor of the right shape and dtype on this device, with any row / plane
+        padding (e.g. a slice of a larger tensor); None allocates one.  A rejected picture leaves its [i] slice untouched (zero in a
+        tensor allocated here) and gets its reason in reasons[i]; reasons[i] is None for a decoded one."""
+        datas = list(datas)
+        n = len(datas)
+        if layout not in ("CHW", "HWC"):
+            raise ValueError("layout must be 'CHW' or 'HWC'")
+        if dtype not in _DT:
+            raise ValueError("dtype must be one of uint8, float16, bfloat16, float32 (got %s)" % (dtype,))
+        if not 0 <= int(req_comp) <= 4:
+            raise ValueError("req_comp must be 0..4")
+        fx, fy = _flags(flip_x, n, "flip_x"), _flags(flip_y, n, "flip_y")
+        if dtype == torch.uint8 and (mean is not None or std is not None):
+            raise ValueError("uint8 output takes no mean / std")
+        if crops is not None and len(crops) != n:
+            raise ValueError("crops has %d windows for %d pictures" % (len(crops), n))
+        # headers only: sizes, channels and arena needs, before any device call
+        descs, reasons = [], [None] * n
+        for i, d in enumerate(datas):
+            try:
+                descs.append(HostDecoder.probe(d, req_comp))
+            except MijError as e:
+                descs.append(None)
+                reasons[i] = str(e)
+        ok = [d for d in descs if d is not None]
+        chans = {d.n_out for d in ok}
+        if len(chans) > 1:
+            raise ValueError("pictures decode to different channel counts %s (pass req_comp)" % sorted(chans))
+        if crops is None:
+            sizes = {(d.width, d.height) for d in ok}
+            if len(sizes) > 1:
+                raise ValueError("pictures of different sizes %s need crops" % sorted(sizes))
+            wins = [None if d is None else (0, 0, d.width, d.height) for d in descs]
+        else:
+            wins = [tuple(int(v) for v in c) for c in crops]
+            if any(len(c) != 4 for c in wins):
+                raise ValueError("a crop is (x0, y0, w, h)")
+            if len({c[2:] for c in wins}) > 1:
+                raise ValueError("crop windows of different sizes %s" % sorted({c[2:] for c in wins}))
+            for i, (c, d) in enumerate(zip(wins, descs)):
+                if c[2] < 1 or c[3] < 1 or c[0] < 0 or c[1] < 0 or (d is not None and (c[0] + c[2] > d.width or c[1] + c[3] > d.height)):
+                    raise ValueError("crop %s of picture %d outside its %dx%d picture" % (c, i, d.width if d else 0, d.height if d else 0))
+        whs = {c[2:] for c in wins if c is not None}
+        C = req_comp if req_comp else (chans.pop() if chans else None)
+        if out is not None:
+            if out.dim() != 4:
+                raise ValueError("out must have 4 dimensions")
+            C = C or (out.shape[1] if layout == "CHW" else out.shape[3])
+            oh, ow = (out.shape[2], out.shape[3]) if layout == "CHW" else (out.shape[1], out.shape[2])
+            whs.add((ow, oh))
+        if not whs or C is None:
+            raise ValueError("no decodable picture to size the tensor (pass out)")
+        if len(whs) > 1:
+            raise ValueError("window sizes %s differ from out" % sorted(whs))
+        w, h = whs.pop()
+        tables = None if dtype == torch.uint8 else tensor_tables(C, dtype, mean, std)
+        shape = (n, C, h, w) if layout == "CHW" else (n, h, w, C)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=self.device)
+            fresh = True
+        else:
+            fresh = False
+            if out.device != self.device:
+                raise ValueError("out is on %s, the decoder on %s" % (out.device, self.device))
+            if tuple(out.shape) != shape or out.dtype != dtype:
+                raise ValueError("out is %s %s, %s %s expected" % (tuple(out.shape), out.dtype, shape, dtype))
+        st = out.stride()
+        if layout == "CHW":
+            ok_strides = (n < 2 or st[0] >= 0) and (w < 2 or st[3] == 1) and st[2] >= 0 and st[1] >= 0
+            row_pitch, plane_pitch = st[2], st[1]
+        else:
+            ok_strides = (n < 2 or st[0] >= 0) and (C < 2 or st[3] == 1) and (w < 2 or st[2] == C) and st[1] >= 0
+            row_pitch, plane_pitch = st[1], 0
+        if not ok_strides:
+            raise ValueError("out strides %s: %s needs unit-stride channels / pixels" % (st, layout))
+        if n == 0:
+            return out, reasons
+        _one_hip_runtime()
+        cb = sum(Batch.coef_bytes(d) for d in ok)
+        ob = sum(Batch.out_bytes(d) for d in ok)
+        b = self._batch_for(n, cb, ob)
+        _, slots, why = b.decode_jpegs(datas, req_comp, threads=int(threads))
+        es = out.element_size()
+        tb = None if tables is None else tables.contiguous().view(_BITS[dtype]).numpy()
+        for i, sl in enumerate(slots):
+            if sl < 0:
+                reasons[i] = why[i] or reasons[i] or "rejected"
+                continue
+            if descs[i] is not None:
+                b.descs[sl] = descs[i]  # already probed: spares set_out_tensor a second header parse
+            x0, y0 = wins[i][0], wins[i][1]
+            b.set_out_tensor(sl, out.data_ptr() + i * st[0] * es, _DT[dtype], MIJ_LAYOUT_CHW if layout == "CHW" else MIJ_LAYOUT_HWC,
+                             x0, y0, w, h, row_pitch, plane_pitch, fx[i], fy[i], tb)
+        torch.cuda.current_stream(self.device).synchronize()
+        b.submit()
+        b.wait()
+        if fresh:
+            for i, r in enumerate(reasons):
+                if r is not None:
+                    out[i].zero_()
+        return out, reasons

@@ -357,6 +357,39 @@ int mij_batch_fetch_f32(mij_batch *b, int slot, float *dst, size_t dst_elems);
 void *mij_batch_device_out_f32(mij_batch *b, int slot);
 
 /*
+ * Tensor output (a PyTorch input pipeline, any consumer that wants the pixels in device memory it owns).  A slot may ask, before
+ * upload, for a crop window [x0, x0+w) x [y0, y0+h) of its decoded picture to be written to `dst`, optionally flipped (flip_x
+ * reverses columns, flip_y rows, inside the window; channel order is kept), each value v of channel c as table[c][v] in the output
+ * element type.  C = n_out of the slot; pitches are in elements:
+ *     MIJ_LAYOUT_HWC  element (y, x, c) at dst + y*row_pitch + x*C + c        (plane_pitch ignored)
+ *     MIJ_LAYOUT_CHW  element (c, y, x) at dst + c*plane_pitch + y*row_pitch + x
+ * A pass of its own (k_out_tensor) behind every decode kernel of the launch -- and behind the float pass -- writes exactly those
+ * elements: row padding and whatever lies around them stay untouched.  The slot's uint8 output (and a float request of the same
+ * slot) stays valid and fetchable; a batch without tensor requests launches exactly what it launches without this section.
+ *
+ * ORDERING: dst is written on the batch's stream during mij_batch_launch (mij_batch_submit).  Nothing orders that write against the
+ * caller's other streams: make dst idle before the submit (e.g. synchronise the stream that last used it) and mij_batch_wait before
+ * reading it.
+ */
+enum { MIJ_DT_U8 = 0, MIJ_DT_F16 = 1, MIJ_DT_BF16 = 2, MIJ_DT_F32 = 3 };
+enum { MIJ_LAYOUT_HWC = 0, MIJ_LAYOUT_CHW = 1 };
+typedef struct {
+	void *dst;                      /* device memory on the batch's device, owned by the caller (e.g. a torch tensor's data_ptr()) */
+	int32_t dtype, layout;          /* MIJ_DT_*, MIJ_LAYOUT_* */
+	int32_t x0, y0, w, h;           /* crop window in the decoded picture */
+	int32_t flip_x, flip_y;
+	int64_t row_pitch, plane_pitch; /* elements; plane_pitch ignored for HWC */
+} mij_out_tensor;
+/* table = n_out*256 elements of dtype (the table of channel k at element 256*k), copied; NULL only for MIJ_DT_U8 (identity).
+ * Before mij_batch_upload (else MIJ_E_STATE); MIJ_E_STATE for a skipped slot; asking again replaces the request; mij_batch_reset
+ * forgets every request.  MIJ_E_ARG, checked on the host, when the window leaves the picture or w or h < 1, when a pitch lets rows
+ * or planes overlap (HWC: row_pitch < w*C; CHW: row_pitch < w or plane_pitch < (h-1)*row_pitch + w; a pitch only counts where there
+ * is more than one row or plane), when dst is not aligned to the element size, when dst is not device memory of the batch's device,
+ * or when the written extent [dst, last element] is not inside the one allocation hipMemGetAddressRange reports for dst (a range that
+ * cannot be determined is refused too).  A refused request leaves any earlier request of the slot in place. */
+int mij_batch_set_out_tensor(mij_batch *b, int slot, const mij_out_tensor *t, const void *table);
+
+/*
  * Encoder half (BASELINE config 5): the JPEG writer's colour transform, edge replication, 2x2
  * chroma mean, float AAN forward DCT and quantiser (codec/jpeg_write.c:24-74, :96-118, :283-352)
  * for a batch of images on the GPU.  Input: interleaved 8-bit pixels, comp 1..4 as passed to
