@@ -20,6 +20,14 @@ from .binding import (  # noqa: F401
     ImageDesc,
     Batch,
     OutTensor,
+    OutResize,
+    FILTERS,
+    MIJ_FILTER_BOX,
+    MIJ_FILTER_BILINEAR,
+    MIJ_FILTER_HAMMING,
+    MIJ_FILTER_BICUBIC,
+    MIJ_FILTER_LANCZOS,
+    resize_coeffs,
     MIJ_DT_U8,
     MIJ_DT_F16,
     MIJ_DT_BF16,

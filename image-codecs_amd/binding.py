@@ -577,6 +577,32 @@ class OutTensor(C.Structure):
                 ("h", C.c_int32), ("flip_x", C.c_int32), ("flip_y", C.c_int32), ("row_pitch", C.c_int64), ("plane_pitch", C.c_int64)]
 
 
+MIJ_FILTER_BOX, MIJ_FILTER_BILINEAR, MIJ_FILTER_HAMMING, MIJ_FILTER_BICUBIC, MIJ_FILTER_LANCZOS = 0, 1, 2, 3, 4
+FILTERS = {"box": MIJ_FILTER_BOX, "bilinear": MIJ_FILTER_BILINEAR, "hamming": MIJ_FILTER_HAMMING, "bicubic": MIJ_FILTER_BICUBIC,
+           "lanczos": MIJ_FILTER_LANCZOS}
+
+
+class OutResize(C.Structure):
+    """mij_out_resize (include/mij.h)."""
+    _fields_ = [("out_w", C.c_int32), ("out_h", C.c_int32), ("filter", C.c_int32), ("reserved", C.c_int32)]
+
+
+def resize_coeffs(n_in, n_out, filter="bilinear"):
+    """mjh_resize_coeffs: one axis of the resized tensor output's contract -> (lo, n, k): int32 [n_out], int32 [n_out] and the
+    fixed-point taps int32 [n_out, ksize] (k[o, t] for t >= n[o] is zero).  filter: a name of FILTERS or MIJ_FILTER_*."""
+    f = FILTERS.get(filter, filter)
+    L = lib()
+    L.mjh_resize_coeffs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+    ks = L.mjh_resize_coeffs(int(n_in), int(n_out), int(f), None, None, 0)
+    if ks < 1:
+        raise ValueError("mjh_resize_coeffs(%r, %r, %r) refused" % (n_in, n_out, filter))
+    lo_n = np.zeros((int(n_out), 2), np.int32)
+    k = np.zeros((int(n_out), ks), np.int32)
+    got = L.mjh_resize_coeffs(int(n_in), int(n_out), int(f), lo_n.ctypes.data_as(C.c_void_p), k.ctypes.data_as(C.c_void_p), k.size)
+    assert got == ks
+    return lo_n[:, 0].copy(), lo_n[:, 1].copy(), k
+
+
 class Context:
     """mij_ctx: one per (process, device)."""
 
@@ -915,6 +941,24 @@ class Batch:
         L = lib()
         L.mij_batch_set_out_tensor.argtypes = [C.c_void_p, C.c_int, C.POINTER(OutTensor), C.c_void_p]
         _check(L.mij_batch_set_out_tensor(self._h, int(slot), C.byref(t), tp), "mij_batch_set_out_tensor")
+
+    def set_out_tensor_resized(self, slot, dst, dtype, layout, x0, y0, w, h, out_w, out_h, row_pitch, plane_pitch=0, flip_x=False, flip_y=False,
+                               table=None, filter="bilinear"):
+        """mij_batch_set_out_tensor_resized: the window (x0, y0, w, h) resized to out_w x out_h with filter (a name of FILTERS or
+        MIJ_FILTER_*), then as set_out_tensor; pitches describe the out_w x out_h extent."""
+        t = OutTensor(C.c_void_p(int(dst)), _DTYPES.get(dtype, dtype), _LAYOUTS.get(layout, layout), int(x0), int(y0), int(w), int(h),
+                      int(bool(flip_x)), int(bool(flip_y)), int(row_pitch), int(plane_pitch))
+        r = OutResize(int(out_w), int(out_h), int(FILTERS.get(filter, filter)), 0)
+        tp = None
+        if table is not None:
+            tb = np.ascontiguousarray(table)
+            need = 256 * self._desc(slot).n_out * (1, 2, 2, 4)[t.dtype] if 0 <= t.dtype <= 3 else 0
+            if tb.nbytes < need:
+                raise ValueError("table has %d bytes, %d needed" % (tb.nbytes, need))
+            tp = tb.ctypes.data_as(C.c_void_p)
+        L = lib()
+        L.mij_batch_set_out_tensor_resized.argtypes = [C.c_void_p, C.c_int, C.POINTER(OutTensor), C.POINTER(OutResize), C.c_void_p]
+        _check(L.mij_batch_set_out_tensor_resized(self._h, int(slot), C.byref(t), C.byref(r), tp), "mij_batch_set_out_tensor_resized")
 
     def fetch_all_async(self, dst_ptr, dst_bytes):
         """mij_batch_fetch_all_async into a (pinned) host buffer; wait() completes it."""

@@ -2955,31 +2955,20 @@ struct WorkTensor { /* window rows [row0, row0 + nrows) x window columns [p0, p0
 
 typedef uint32_t u4v __attribute__((ext_vector_type(4)));
 
-template <typename T, bool CHW, int N>
-__device__ __forceinline__ void tensor_item(const DevTensor &s, const WorkTensor &wk, const uint8_t *__restrict__ out, const uint8_t *lut, uint32_t *stage)
+/* Phase 2 of a tensor work item, shared by k_out_tensor and k_out_resize: store nr rows x np columns of staged bytes (row r's
+ * n_out-interleaved bytes at srow_of(r), in the order of the window, unflipped in x) to destination rows [row0, row0 + nr) and columns
+ * [p0, p0 + np) of request s, flipping columns when s.flip_x and looking each value up in its channel's table. */
+template <typename T, bool CHW, int N, typename RowOf>
+__device__ __forceinline__ void tensor_store(const DevTensor &s, uint32_t row0, uint32_t p0, uint32_t nr, uint32_t np, const uint8_t *lut, RowOf srow_of)
 {
 	constexpr uint32_t ES = sizeof(T), V = 16u / ES, LS = 256u * ES + MIJ_TEN_LDS_PAD, PW = 4u / ES;
-	const uint32_t np = wk.np, nr = wk.nrows, nb = np * N;
-	const uint32_t lsd = (nb + 6u) >> 2; /* dwords per staged row: room for a start up to 3 bytes before the window */
-	const uint32_t sxa = s.flip_x ? s.x0 + s.w - wk.p0 - np : s.x0 + wk.p0; /* first source column of the segment */
-	const uint64_t rowb = (uint64_t)s.src_w * N;
-	for (uint32_t i = threadIdx.x; i < nr * lsd; i += 256u) {
-		const uint32_t r = i / lsd, k = i - r * lsd, oy = wk.row0 + r;
-		const uint32_t sy = s.flip_y ? s.y0 + s.h - 1u - oy : s.y0 + oy;
-		const uint64_t a = s.src_off + sy * rowb + (uint64_t)sxa * N;
-		/* the dwords that hold the segment's bytes; the last ends inside the slot's 256-aligned region of the arena */
-		if (k < (((uint32_t)(a & 3u) + nb + 3u) >> 2))
-			stage[i] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(out + (a & ~(uint64_t)3)) + k);
-	}
-	__syncthreads();
-	const uint8_t *sb = reinterpret_cast<const uint8_t *>(stage);
+	const uint32_t nb = np * N;
 	const uint32_t E = CHW ? np : nb, nl = CHW ? nr * N : nr, um = E / V + 2u;
 	for (uint32_t i = threadIdx.x; i < nl * um; i += 256u) {
 		const uint32_t line = i / um, u = i - line * um;
-		const uint32_t r = CHW ? line / N : line, pc = CHW ? line - r * N : 0u, oy = wk.row0 + r;
-		const uint32_t sy = s.flip_y ? s.y0 + s.h - 1u - oy : s.y0 + oy;
-		const uint8_t *srow = sb + r * lsd * 4u + (uint32_t)((s.src_off + sy * rowb + (uint64_t)sxa * N) & 3u);
-		T *d = reinterpret_cast<T *>(s.dst) + (int64_t)oy * s.row_pitch + (CHW ? (int64_t)pc * s.plane_pitch + wk.p0 : (int64_t)wk.p0 * N);
+		const uint32_t r = CHW ? line / N : line, pc = CHW ? line - r * N : 0u, oy = row0 + r;
+		const uint8_t *srow = srow_of(r);
+		T *d = reinterpret_cast<T *>(s.dst) + (int64_t)oy * s.row_pitch + (CHW ? (int64_t)pc * s.plane_pitch + p0 : (int64_t)p0 * N);
 		const uint32_t head = (uint32_t)(((16u - ((uintptr_t)d & 15u)) & 15u) / ES);
 		const uint32_t e0 = u ? head + (u - 1u) * V : 0u;
 		const uint32_t e1 = u ? min(E, e0 + V) : min(E, head);
@@ -3006,6 +2995,29 @@ __device__ __forceinline__ void tensor_item(const DevTensor &s, const WorkTensor
 				d[e] = value(e);
 		}
 	}
+}
+
+template <typename T, bool CHW, int N>
+__device__ __forceinline__ void tensor_item(const DevTensor &s, const WorkTensor &wk, const uint8_t *__restrict__ out, const uint8_t *lut, uint32_t *stage)
+{
+	const uint32_t np = wk.np, nr = wk.nrows, nb = np * N;
+	const uint32_t lsd = (nb + 6u) >> 2; /* dwords per staged row: room for a start up to 3 bytes before the window */
+	const uint32_t sxa = s.flip_x ? s.x0 + s.w - wk.p0 - np : s.x0 + wk.p0; /* first source column of the segment */
+	const uint64_t rowb = (uint64_t)s.src_w * N;
+	for (uint32_t i = threadIdx.x; i < nr * lsd; i += 256u) {
+		const uint32_t r = i / lsd, k = i - r * lsd, oy = wk.row0 + r;
+		const uint32_t sy = s.flip_y ? s.y0 + s.h - 1u - oy : s.y0 + oy;
+		const uint64_t a = s.src_off + sy * rowb + (uint64_t)sxa * N;
+		/* the dwords that hold the segment's bytes; the last ends inside the slot's 256-aligned region of the arena */
+		if (k < (((uint32_t)(a & 3u) + nb + 3u) >> 2))
+			stage[i] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(out + (a & ~(uint64_t)3)) + k);
+	}
+	__syncthreads();
+	const uint8_t *sb = reinterpret_cast<const uint8_t *>(stage);
+	tensor_store<T, CHW, N>(s, wk.row0, wk.p0, nr, np, lut, [&](uint32_t r) {
+		const uint32_t oy = wk.row0 + r, sy = s.flip_y ? s.y0 + s.h - 1u - oy : s.y0 + oy;
+		return sb + r * lsd * 4u + (uint32_t)((s.src_off + sy * rowb + (uint64_t)sxa * N) & 3u);
+	});
 }
 
 template <typename T, bool CHW>
@@ -3041,6 +3053,184 @@ __global__ __launch_bounds__(256) void k_out_tensor(const DevTensor *__restrict_
 	case 5: tensor_item_n<uint16_t, true>(s, wk, out, lut, stage); break;
 	case 8: tensor_item_n<uint32_t, false>(s, wk, out, lut, stage); break;
 	default: tensor_item_n<uint32_t, true>(s, wk, out, lut, stage); break;
+	}
+}
+
+/* ------------------------------------------------------------------ resized tensor output (mij_batch_set_out_tensor_resized)
+ *
+ * k_out_resize resizes a request's crop window to out_w x out_h with the integer separable filter of include/mij.h (horizontal pass,
+ * then vertical), then stores it through tensor_store as k_out_tensor does.  The coefficients are built on the host (one lo / n pair
+ * and one row of ks taps per output column or row; an axis whose size does not change gets the identity, one tap of 2^22, which
+ * reproduces the skipped pass exactly).  A work item is (request, band of at most MIJ_RSZ_ROWS output rows, segment of output
+ * columns), one (column, channel) per lane.  The item walks the source rows its band's vertical taps need, a round of rows at a
+ * time: the rows' span of source columns is staged in LDS as dwords; each lane sums its horizontal taps from LDS, clamps, and adds
+ * the value into the accumulators (registers) of the band rows whose taps cover that source row.  A span wider than the stage is
+ * walked in chunks of columns, one row per round, the partial sums kept in a register -- the sums are integers, so their order does
+ * not matter.  The segment's horizontal taps sit in LDS when they fit (MIJ_RSZ_KCAP) and are read from the plan otherwise, so LDS
+ * and registers stay bounded for any ratio; so do the band's vertical taps (MIJ_RSZ_VCAP).  All arithmetic is 32-bit integer: 24-bit multiplies when every |k| < 2^23 (the host
+ * checks), full 32-bit ones otherwise. */
+#define MIJ_RSZ_STAGE_WORDS 4096u /* 16 KiB of staged source bytes */
+#define MIJ_RSZ_KCAP 3072u        /* horizontal taps of a segment held in LDS */
+#define MIJ_RSZ_VCAP 1024u        /* vertical taps of a band held in LDS */
+#define MIJ_RSZ_ROWS 16u          /* output rows per work item: vertical accumulators per lane */
+
+struct DevResize {           /* one resized request */
+	DevTensor t;             /* as k_out_tensor's, t.x0, t.y0, t.w, t.h the source window */
+	uint64_t hco, vco;       /* byte offsets in the plan of the horizontal / vertical coefficients: lo, n pairs [out][2], then taps [out][ks] */
+	uint32_t out_w, out_h;
+	uint32_t ksh, ksv;       /* taps per row of the horizontal / vertical coefficients */
+	uint32_t mul32, kglobal; /* 1: some |k| >= 2^23 (32-bit multiplies); 1: the horizontal taps are read from the plan, not LDS */
+	uint32_t vglobal, pad;   /* 1: the vertical taps are read from the plan, not LDS */
+};
+struct WorkResize { /* output rows [q0, q0 + nr) x output columns [u0, u0 + nc) of request t, before flips */
+	uint32_t t, q0, u0;
+	uint16_t nr, nc;
+};
+
+template <bool M32>
+__device__ __forceinline__ int32_t rsz_mac(int32_t acc, uint32_t x, int32_t k)
+{
+	return M32 ? acc + (int32_t)x * k : acc + __mul24((int32_t)x, k);
+}
+
+/* the item's resized bytes: nr rows of nc * n_out bytes (channels interleaved) at `ob`, which aliases the stage */
+template <bool M32, bool KG>
+__device__ __forceinline__ void resize_item(const DevResize &s, const WorkResize &wk, const uint8_t *__restrict__ plan, const uint8_t *__restrict__ out,
+														  uint32_t *stage, int32_t *kl, int32_t *vkl)
+{
+	const uint32_t N = s.t.n_out, nc = wk.nc, nr = wk.nr, q0 = wk.q0, u0 = wk.u0, ksh = s.ksh, ksv = s.ksv;
+	const int32_t *hln = reinterpret_cast<const int32_t *>(plan + s.hco), *hk = hln + 2u * s.out_w;
+	const int32_t *vln = reinterpret_cast<const int32_t *>(plan + s.vco), *vk = vln + 2u * s.out_h;
+	const uint32_t tid = threadIdx.x, o = tid / N, c = tid - o * N;
+	const bool lane = o < nc;
+	const uint32_t uo = u0 + (lane ? o : 0u);
+	const uint32_t sx0 = (uint32_t)hln[2u * u0], sx1 = (uint32_t)(hln[2u * (u0 + nc - 1u)] + hln[2u * (u0 + nc - 1u) + 1u]);
+	const int32_t hlo = hln[2u * uo] - (int32_t)sx0, hn = lane ? hln[2u * uo + 1u] : 0;
+	if (!KG)
+		for (uint32_t i = tid; i < nc * ksh; i += 256u)
+			kl[i] = hk[(size_t)u0 * ksh + i];
+	const int32_t *kp = KG ? hk + (size_t)uo * ksh : kl + (lane ? o : 0u) * ksh;
+	const bool vg = s.vglobal != 0;
+	if (!vg)
+		for (uint32_t i = tid; i < nr * ksv; i += 256u)
+			vkl[i] = vk[(size_t)q0 * ksv + i];
+	/* the band's vertical taps: output row q0 + j reads source rows [vlo[j], vlo[j] + vn[j]) */
+	uint32_t vlo[MIJ_RSZ_ROWS], vn[MIJ_RSZ_ROWS];
+	int32_t acc[MIJ_RSZ_ROWS];
+#pragma unroll
+	for (uint32_t j = 0; j < MIJ_RSZ_ROWS; ++j) {
+		vlo[j] = j < nr ? (uint32_t)vln[2u * (q0 + j)] : 0u;
+		vn[j] = j < nr ? (uint32_t)vln[2u * (q0 + j) + 1u] : 0u;
+		acc[j] = 1 << 21;
+	}
+	const uint32_t sy0 = vlo[0], sy1 = (uint32_t)(vln[2u * (q0 + nr - 1u)] + vln[2u * (q0 + nr - 1u) + 1u]);
+	const uint32_t span = sx1 - sx0, ccmax = (MIJ_RSZ_STAGE_WORDS * 4u - 8u) / N;
+	const bool one = span <= ccmax; /* the whole span in one chunk: several rows per round */
+	const uint32_t cc = one ? span : ccmax, ld = (cc * N + 6u) >> 2; /* dwords per staged row: room for a start up to 3 bytes early */
+	const uint32_t R = one ? MIJ_RSZ_STAGE_WORDS / ld : 1u;
+	const uint64_t rowb = (uint64_t)s.t.src_w * N, col0 = s.t.src_off + (uint64_t)(s.t.x0 + sx0) * N;
+	const uint8_t *sb = reinterpret_cast<const uint8_t *>(stage);
+	auto vertical = [&](uint32_t sy, int32_t hs) {
+		const uint32_t hv = (uint32_t)min(max(hs >> 22, 0), 255);
+#pragma unroll
+		for (uint32_t j = 0; j < MIJ_RSZ_ROWS; ++j) {
+			const uint32_t d = sy - vlo[j];
+			if (d < vn[j])
+				acc[j] = rsz_mac<M32>(acc[j], hv, vg ? vk[(size_t)(q0 + j) * ksv + d] : vkl[j * ksv + d]);
+		}
+	};
+	__syncthreads(); /* kl, vkl, and the tables k_out_resize put in LDS */
+	for (uint32_t y = sy0; y < sy1; y += R) {
+		const uint32_t nrw = min(R, sy1 - y);
+		int32_t hsum = 1 << 21;
+		for (uint32_t cx = 0; cx < span; cx += cc) {
+			const uint32_t ncc = min(cc, span - cx), nb = ncc * N;
+			for (uint32_t i = tid; i < nrw * ld; i += 256u) {
+				const uint32_t r = i / ld, k = i - r * ld;
+				const uint64_t a = col0 + (uint64_t)(s.t.y0 + y + r) * rowb + (uint64_t)cx * N;
+				/* the dwords that hold the chunk's bytes; the last ends inside the slot's 256-aligned region of the arena */
+				if (k < (((uint32_t)(a & 3u) + nb + 3u) >> 2))
+					stage[i] = reinterpret_cast<const uint32_t *>(out + (a & ~(uint64_t)3))[k];
+			}
+			__syncthreads();
+			const int32_t tb = max((int32_t)cx - hlo, 0), te = min(hn, (int32_t)(cx + ncc) - hlo);
+			for (uint32_t r = 0; r < nrw; ++r) {
+				const uint64_t a = col0 + (uint64_t)(s.t.y0 + y + r) * rowb + (uint64_t)cx * N;
+				const uint8_t *row = sb + r * ld * 4u + (uint32_t)(a & 3u) + (int32_t)(hlo - (int32_t)cx) * (int32_t)N + c;
+				/* four taps at a time: their LDS reads are issued together, so that their latency overlaps */
+				int32_t p = 0, p1 = 0, t = tb;
+				for (; t + 4 <= te; t += 4) {
+					const uint32_t x0 = row[t * (int32_t)N], x1 = row[(t + 1) * (int32_t)N], x2 = row[(t + 2) * (int32_t)N], x3 = row[(t + 3) * (int32_t)N];
+					const int32_t k0 = kp[t], k1 = kp[t + 1], k2 = kp[t + 2], k3 = kp[t + 3];
+					p = rsz_mac<M32>(rsz_mac<M32>(p, x0, k0), x2, k2);
+					p1 = rsz_mac<M32>(rsz_mac<M32>(p1, x1, k1), x3, k3);
+				}
+				for (; t < te; ++t)
+					p = rsz_mac<M32>(p, row[t * (int32_t)N], kp[t]);
+				p += p1;
+				if (one)
+					vertical(y + r, p + (1 << 21));
+				else
+					hsum += p;
+			}
+			__syncthreads();
+		}
+		if (!one)
+			vertical(y, hsum);
+	}
+	uint8_t *ob = reinterpret_cast<uint8_t *>(stage);
+	if (lane) {
+#pragma unroll
+		for (uint32_t j = 0; j < MIJ_RSZ_ROWS; ++j)
+			if (j < nr)
+				ob[j * nc * N + o * N + c] = (uint8_t)min(max(acc[j] >> 22, 0), 255);
+	}
+	__syncthreads();
+}
+
+template <typename T, bool CHW>
+__device__ __forceinline__ void resize_store(const DevResize &s, const WorkResize &wk, const uint8_t *lut, const uint8_t *ob)
+{
+	const uint32_t nr = wk.nr, nc = wk.nc, rb = nc * s.t.n_out;
+	const uint32_t row0 = s.t.flip_y ? s.out_h - wk.q0 - nr : wk.q0, p0 = s.t.flip_x ? s.out_w - wk.u0 - nc : wk.u0;
+	auto row_of = [&](uint32_t r) { return ob + (s.t.flip_y ? nr - 1u - r : r) * rb; };
+	switch (s.t.n_out) {
+	case 1: tensor_store<T, CHW, 1>(s.t, row0, p0, nr, nc, lut, row_of); break;
+	case 2: tensor_store<T, CHW, 2>(s.t, row0, p0, nr, nc, lut, row_of); break;
+	case 3: tensor_store<T, CHW, 3>(s.t, row0, p0, nr, nc, lut, row_of); break;
+	default: tensor_store<T, CHW, 4>(s.t, row0, p0, nr, nc, lut, row_of); break;
+	}
+}
+
+__global__ __launch_bounds__(256) void k_out_resize(const DevResize *__restrict__ rs, const WorkResize *__restrict__ work, const uint8_t *__restrict__ luts,
+																	 const uint8_t *__restrict__ plan, const uint8_t *__restrict__ out)
+{
+	__shared__ uint32_t stage[MIJ_RSZ_STAGE_WORDS];
+	__shared__ int32_t kl[MIJ_RSZ_KCAP];
+	__shared__ int32_t vkl[MIJ_RSZ_VCAP];
+	__shared__ uint32_t lutw[4u * (1024u + MIJ_TEN_LDS_PAD) / 4u];
+	const WorkResize wk = work[blockIdx.x];
+	const DevResize s = rs[wk.t];
+	if (s.t.lut) {
+		const uint32_t tw = 64u * s.t.esize, lsw = tw + MIJ_TEN_LDS_PAD / 4u;
+		const uint32_t *g = reinterpret_cast<const uint32_t *>(luts + (size_t)wk.t * MIJ_TEN_LUT_BYTES);
+		for (uint32_t t = threadIdx.x; t < s.t.n_out * tw; t += 256u)
+			lutw[(t / tw) * lsw + t % tw] = g[t];
+	}
+	switch (s.mul32 * 2u + s.kglobal) {
+	case 0: resize_item<false, false>(s, wk, plan, out, stage, kl, vkl); break;
+	case 1: resize_item<false, true>(s, wk, plan, out, stage, kl, vkl); break;
+	case 2: resize_item<true, false>(s, wk, plan, out, stage, kl, vkl); break;
+	default: resize_item<true, true>(s, wk, plan, out, stage, kl, vkl); break;
+	}
+	const uint8_t *lut = reinterpret_cast<const uint8_t *>(lutw), *ob = reinterpret_cast<const uint8_t *>(stage);
+	switch (s.t.esize * 2u + s.t.chw) {
+	case 2: resize_store<uint8_t, false>(s, wk, lut, ob); break;
+	case 3: resize_store<uint8_t, true>(s, wk, lut, ob); break;
+	case 4: resize_store<uint16_t, false>(s, wk, lut, ob); break;
+	case 5: resize_store<uint16_t, true>(s, wk, lut, ob); break;
+	case 8: resize_store<uint32_t, false>(s, wk, lut, ob); break;
+	default: resize_store<uint32_t, true>(s, wk, lut, ob); break;
 	}
 }
 

@@ -9,11 +9,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <new>
 #include <vector>
 
 #include "mij.h"
+#include "mij_host.h"
 #include "mij_kernels.h"
 
 using namespace mij;
@@ -266,9 +268,17 @@ struct mij_batch {
 	size_t f32_items, f32_lut_at, f32_work_at; /* work items of the last upload; byte offsets of the tables and the work list in the plan */
 	/* tensor output (mij_batch_set_out_tensor): one validated request per slot that asked, and what upload made of them for
 	 * k_out_tensor -- descriptors, tables and (request, rows, columns) work list in one pinned / device buffer pair */
+	struct RszCoef {
+		std::vector<int32_t> v; /* lo, n pairs [out][2], then taps [out][ks] */
+		int ks;
+		bool big, fits; /* some |k| >= 2^23; 255 * sum |k| + 2^21 < 2^31 for every output */
+	};
 	struct TenReq {
 		int slot;
 		mij_out_tensor t;
+		bool rsz; /* a resized request: r, and the coefficients of its axes */
+		mij_out_resize r;
+		const RszCoef *ch, *cv;
 		uint32_t esize;
 		bool lut;
 		uint8_t table[MIJ_TEN_LUT_BYTES];
@@ -277,6 +287,12 @@ struct mij_batch {
 	uint8_t *h_tenplan, *d_tenplan;
 	size_t tenplan_cap;
 	size_t ten_items, ten_lut_at, ten_work_at;
+	/* resized tensor output (mij_batch_set_out_tensor_resized): coefficients per (in, out, filter), kept until reset (std::map: the
+	 * requests point at them), and k_out_resize's plan -- descriptors, tables, coefficients and work list -- in a buffer pair of its own */
+	std::map<uint64_t, RszCoef> rsz_coef;
+	uint8_t *h_rszplan, *d_rszplan;
+	size_t rszplan_cap;
+	size_t rsz_items, rsz_lut_at, rsz_work_at;
 };
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -334,6 +350,9 @@ extern "C" int mij_batch_create(mij_ctx *ctx, int max_images, size_t stage_bytes
 	b->h_tenplan = b->d_tenplan = nullptr;
 	b->tenplan_cap = 0;
 	b->ten_items = b->ten_lut_at = b->ten_work_at = 0;
+	b->h_rszplan = b->d_rszplan = nullptr;
+	b->rszplan_cap = 0;
+	b->rsz_items = b->rsz_lut_at = b->rsz_work_at = 0;
 	b->stream = nullptr;
 	b->ev_begin = b->ev_end = nullptr;
 	b->ev_pack0 = b->ev_pack1 = nullptr;
@@ -409,6 +428,10 @@ extern "C" void mij_batch_destroy(mij_batch *b)
 		(void)hipHostFree(b->h_tenplan);
 	if (b->d_tenplan)
 		(void)hipFree(b->d_tenplan);
+	if (b->h_rszplan)
+		(void)hipHostFree(b->h_rszplan);
+	if (b->d_rszplan)
+		(void)hipFree(b->d_rszplan);
 	if (b->ev_begin)
 		(void)hipEventDestroy(b->ev_begin);
 	if (b->ev_end)
@@ -437,6 +460,8 @@ extern "C" int mij_batch_reset(mij_batch *b)
 	b->f32_items = 0;
 	b->ten_req.clear();
 	b->ten_items = 0;
+	b->rsz_coef.clear();
+	b->rsz_items = 0;
 	es_reset_fwd(b->es);
 	return MIJ_OK;
 }
@@ -1007,6 +1032,27 @@ static int f32_plan(mij_batch *b)
 	return MIJ_OK;
 }
 
+/* k_out_tensor's / k_out_resize's descriptor of a request */
+static void dev_tensor(DevTensor &d, const mij_batch::TenReq &q, const Slot &s)
+{
+	d.src_off = s.dev.out_off;
+	d.dst = (uint64_t)(uintptr_t)q.t.dst;
+	d.row_pitch = q.t.row_pitch;
+	d.plane_pitch = q.t.layout == MIJ_LAYOUT_CHW ? q.t.plane_pitch : 0;
+	d.src_w = (uint32_t)s.desc.width;
+	d.n_out = (uint32_t)s.desc.n_out;
+	d.x0 = (uint32_t)q.t.x0;
+	d.y0 = (uint32_t)q.t.y0;
+	d.w = (uint32_t)q.t.w;
+	d.h = (uint32_t)q.t.h;
+	d.flip_x = q.t.flip_x ? 1u : 0u;
+	d.flip_y = q.t.flip_y ? 1u : 0u;
+	d.esize = q.esize;
+	d.chw = q.t.layout == MIJ_LAYOUT_CHW ? 1u : 0u;
+	d.lut = q.lut ? 1u : 0u;
+	d.pad = 0;
+}
+
 /* Tensor output: k_out_tensor's descriptors, tables and work list -- (request, band of window rows, segment of window columns) items of
  * at most MIJ_TEN_ITEM_BYTES source bytes and MIJ_TEN_MAX_ROWS rows -- built next to the decode plan and copied up on the batch stream.
  * A batch without tensor requests does nothing here. */
@@ -1019,7 +1065,7 @@ static int ten_plan(mij_batch *b)
 	std::vector<WorkTensor> work;
 	for (size_t t = 0; t < nreq; ++t) {
 		const mij_batch::TenReq &q = b->ten_req[t];
-		if (b->slots[(size_t)q.slot].desc.flags & MIJ_FLAG_SKIP)
+		if ((b->slots[(size_t)q.slot].desc.flags & MIJ_FLAG_SKIP) || q.rsz) /* resized requests: rsz_plan */
 			continue;
 		const uint32_t c = (uint32_t)b->slots[(size_t)q.slot].desc.n_out, w = (uint32_t)q.t.w, h = (uint32_t)q.t.h;
 		const uint32_t segw = std::min(w, MIJ_TEN_ITEM_BYTES / c);
@@ -1045,23 +1091,7 @@ static int ten_plan(mij_batch *b)
 	for (size_t t = 0; t < nreq; ++t) {
 		const mij_batch::TenReq &q = b->ten_req[t];
 		const Slot &s = b->slots[(size_t)q.slot];
-		DevTensor &d = td[t];
-		d.src_off = s.dev.out_off;
-		d.dst = (uint64_t)(uintptr_t)q.t.dst;
-		d.row_pitch = q.t.row_pitch;
-		d.plane_pitch = q.t.layout == MIJ_LAYOUT_CHW ? q.t.plane_pitch : 0;
-		d.src_w = (uint32_t)s.desc.width;
-		d.n_out = (uint32_t)s.desc.n_out;
-		d.x0 = (uint32_t)q.t.x0;
-		d.y0 = (uint32_t)q.t.y0;
-		d.w = (uint32_t)q.t.w;
-		d.h = (uint32_t)q.t.h;
-		d.flip_x = q.t.flip_x ? 1u : 0u;
-		d.flip_y = q.t.flip_y ? 1u : 0u;
-		d.esize = q.esize;
-		d.chw = q.t.layout == MIJ_LAYOUT_CHW ? 1u : 0u;
-		d.lut = q.lut ? 1u : 0u;
-		d.pad = 0;
+		dev_tensor(td[t], q, s);
 		memcpy(b->h_tenplan + lut_at + MIJ_TEN_LUT_BYTES * t, q.table, MIJ_TEN_LUT_BYTES);
 	}
 	memcpy(b->h_tenplan + work_at, work.data(), sizeof(WorkTensor) * work.size());
@@ -1069,6 +1099,88 @@ static int ten_plan(mij_batch *b)
 	b->ten_items = work.size();
 	b->ten_lut_at = lut_at;
 	b->ten_work_at = work_at;
+	return MIJ_OK;
+}
+
+/* Resized tensor output: k_out_resize's descriptors, tables, coefficients (each (in, out, filter) once) and work list -- (request, band of
+ * at most MIJ_RSZ_ROWS output rows, segment of output columns) -- in one buffer pair.  A segment has at most one column per lane
+ * (256 / n_out), few enough that its horizontal taps fit MIJ_RSZ_KCAP (else they stay in the plan) and, where it can, that its span of
+ * source bytes fills at most half the stage, so that a round stages two rows or more.  A band has as many rows as keep its vertical taps
+ * within MIJ_RSZ_VCAP (else they stay in the plan).  A batch without resized requests does nothing. */
+static int rsz_plan(mij_batch *b)
+{
+	b->rsz_items = 0;
+	const size_t nreq = b->ten_req.size();
+	size_t nrsz = 0;
+	for (const mij_batch::TenReq &q : b->ten_req)
+		nrsz += q.rsz && !(b->slots[(size_t)q.slot].desc.flags & MIJ_FLAG_SKIP);
+	if (!nrsz)
+		return MIJ_OK;
+	/* byte offsets of the coefficient blocks, each (in, out, filter) once */
+	std::map<const mij_batch::RszCoef *, uint64_t> at;
+	const size_t lut_at = align_up(sizeof(DevResize) * nreq, 256), coef_at = lut_at + MIJ_TEN_LUT_BYTES * nreq;
+	size_t off = coef_at;
+	std::vector<WorkResize> work;
+	std::vector<uint32_t> kglobal(nreq, 0), vglobal(nreq, 0);
+	for (size_t t = 0; t < nreq; ++t) {
+		const mij_batch::TenReq &q = b->ten_req[t];
+		if (!q.rsz || (b->slots[(size_t)q.slot].desc.flags & MIJ_FLAG_SKIP))
+			continue;
+		for (const mij_batch::RszCoef *c : {q.ch, q.cv})
+			if (at.emplace(c, off).second)
+				off += c->v.size() * sizeof(int32_t);
+		const uint32_t n = (uint32_t)b->slots[(size_t)q.slot].desc.n_out, ow = (uint32_t)q.r.out_w, oh = (uint32_t)q.r.out_h;
+		const uint32_t ksh = (uint32_t)q.ch->ks;
+		uint32_t nc = 256u / n;
+		if (ksh > MIJ_RSZ_KCAP)
+			kglobal[t] = 1;
+		else
+			nc = std::min(nc, MIJ_RSZ_KCAP / ksh);
+		const double scale = (double)q.t.w / ow, half = MIJ_RSZ_STAGE_WORDS * 2.0 / n; /* source columns in half the stage */
+		if ((nc * scale + ksh) > half)
+			nc = (uint32_t)std::max(1.0, std::min((double)nc, (half - ksh) / scale));
+		const uint32_t nseg = (ow + nc - 1) / nc, segw = (ow + nseg - 1) / nseg;
+		const uint32_t ksv = (uint32_t)q.cv->ks, rows = ksv > MIJ_RSZ_VCAP ? MIJ_RSZ_ROWS : std::min(MIJ_RSZ_ROWS, MIJ_RSZ_VCAP / ksv);
+		vglobal[t] = ksv > MIJ_RSZ_VCAP ? 1u : 0u;
+		const uint32_t nband = (oh + rows - 1) / rows, bandh = (oh + nband - 1) / nband;
+		for (uint32_t q0 = 0; q0 < oh; q0 += bandh)
+			for (uint32_t u0 = 0; u0 < ow; u0 += segw)
+				work.push_back(WorkResize{(uint32_t)t, q0, u0, (uint16_t)std::min(bandh, oh - q0), (uint16_t)std::min(segw, ow - u0)});
+	}
+	if (work.size() > 0x7fffffffu)
+		return set_err(MIJ_E_ARG, "resized tensor output: %zu work items", work.size());
+	const size_t work_at = align_up(off, 16), need = work_at + sizeof(WorkResize) * work.size();
+	if (need > b->rszplan_cap)
+		HIP_TRY(hipStreamSynchronize(b->stream));
+	int rc = grow_pair(b->h_rszplan, b->d_rszplan, b->rszplan_cap, align_up(need, 4));
+	if (rc != MIJ_OK)
+		return rc;
+	DevResize *rd = reinterpret_cast<DevResize *>(b->h_rszplan);
+	memset(rd, 0, sizeof(DevResize) * nreq);
+	for (size_t t = 0; t < nreq; ++t) {
+		const mij_batch::TenReq &q = b->ten_req[t];
+		if (!q.rsz || (b->slots[(size_t)q.slot].desc.flags & MIJ_FLAG_SKIP))
+			continue;
+		DevResize &d = rd[t];
+		dev_tensor(d.t, q, b->slots[(size_t)q.slot]);
+		d.hco = at[q.ch];
+		d.vco = at[q.cv];
+		d.out_w = (uint32_t)q.r.out_w;
+		d.out_h = (uint32_t)q.r.out_h;
+		d.ksh = (uint32_t)q.ch->ks;
+		d.ksv = (uint32_t)q.cv->ks;
+		d.mul32 = (q.ch->big || q.cv->big) ? 1u : 0u;
+		d.kglobal = kglobal[t];
+		d.vglobal = vglobal[t];
+		memcpy(b->h_rszplan + lut_at + MIJ_TEN_LUT_BYTES * t, q.table, MIJ_TEN_LUT_BYTES);
+	}
+	for (const auto &e : at)
+		memcpy(b->h_rszplan + e.second, e.first->v.data(), e.first->v.size() * sizeof(int32_t));
+	memcpy(b->h_rszplan + work_at, work.data(), sizeof(WorkResize) * work.size());
+	HIP_TRY(copy_table(b->d_rszplan, b->h_rszplan, align_up(need, 4), b->stream));
+	b->rsz_items = work.size();
+	b->rsz_lut_at = lut_at;
+	b->rsz_work_at = work_at;
 	return MIJ_OK;
 }
 
@@ -1440,6 +1552,8 @@ extern "C" int mij_batch_upload(mij_batch *b)
 		return rc;
 	if ((rc = ten_plan(b)) != MIJ_OK)
 		return rc;
+	if ((rc = rsz_plan(b)) != MIJ_OK)
+		return rc;
 	b->uploaded = true;
 	b->launched = false;
 	return MIJ_OK;
@@ -1579,6 +1693,12 @@ extern "C" int mij_batch_launch(mij_batch *b)
 	if (b->ten_items) {
 		hipLaunchKernelGGL(k_out_tensor, dim3((unsigned)b->ten_items), dim3(256), 0, b->stream, reinterpret_cast<const DevTensor *>(b->d_tenplan),
 								 reinterpret_cast<const WorkTensor *>(b->d_tenplan + b->ten_work_at), b->d_tenplan + b->ten_lut_at, b->d_out);
+		HIP_TRY(hipGetLastError());
+	}
+	/* resized tensor output, behind the plain one */
+	if (b->rsz_items) {
+		hipLaunchKernelGGL(k_out_resize, dim3((unsigned)b->rsz_items), dim3(256), 0, b->stream, reinterpret_cast<const DevResize *>(b->d_rszplan),
+								 reinterpret_cast<const WorkResize *>(b->d_rszplan + b->rsz_work_at), b->d_rszplan + b->rsz_lut_at, b->d_rszplan, b->d_out);
 		HIP_TRY(hipGetLastError());
 	}
 	b->launched = true;
@@ -1754,7 +1874,49 @@ extern "C" void *mij_batch_device_out_f32(mij_batch *b, int slot)
 
 /* ------------------------------------------------------------------ tensor output */
 
-extern "C" int mij_batch_set_out_tensor(mij_batch *b, int slot, const mij_out_tensor *t, const void *table)
+/* One axis of a resized request: the coefficients of mjh_resize_coeffs, cached per (in, out, filter) until reset, and checked against
+ * the kernel's arithmetic.  An axis whose size does not change gets the identity (one tap of 2^22 per output), which gives back the
+ * input bytes exactly: the contract skips that pass. */
+static const mij_batch::RszCoef *rsz_coef(mij_batch *b, int in, int out, int filter)
+{
+	const uint64_t key = ((uint64_t)(uint32_t)in << 32) | ((uint64_t)(uint32_t)out << 3) | (uint64_t)(uint32_t)(in == out ? 7 : filter);
+	auto it = b->rsz_coef.find(key);
+	if (it != b->rsz_coef.end())
+		return &it->second;
+	mij_batch::RszCoef c;
+	if (in == out) {
+		c.ks = 1;
+		c.v.resize((size_t)out * 3);
+		for (int o = 0; o < out; ++o) {
+			c.v[2 * (size_t)o] = o;
+			c.v[2 * (size_t)o + 1] = 1;
+			c.v[2 * (size_t)out + o] = 1 << 22;
+		}
+	} else {
+		c.ks = mjh_resize_coeffs(in, out, filter, nullptr, nullptr, 0);
+		if (c.ks < 1)
+			return nullptr;
+		c.v.resize((size_t)out * (2 + (size_t)c.ks));
+		if (mjh_resize_coeffs(in, out, filter, c.v.data(), c.v.data() + 2 * (size_t)out, (size_t)out * c.ks) != c.ks)
+			return nullptr;
+	}
+	/* 24-bit multiplies take |k| < 2^23; a 32-bit sum of 2^21 and n products of a byte cannot overflow while 255 * sum |k| < 2^31 - 2^21 */
+	c.big = false;
+	c.fits = true;
+	for (int o = 0; o < out; ++o) {
+		int64_t sum = 0;
+		const int32_t *k = c.v.data() + 2 * (size_t)out + (size_t)o * c.ks;
+		for (int t = 0; t < c.ks; ++t) {
+			const int64_t a = k[t] < 0 ? -(int64_t)k[t] : k[t];
+			sum += a;
+			c.big |= a >= ((int64_t)1 << 23);
+		}
+		c.fits &= 255 * sum < ((int64_t)1 << 31) - ((int64_t)1 << 21);
+	}
+	return &b->rsz_coef.emplace(key, std::move(c)).first->second;
+}
+
+static int set_out_tensor(mij_batch *b, int slot, const mij_out_tensor *t, const mij_out_resize *rz, const void *table)
 {
 	if (!b || slot < 0 || slot >= (int)b->slots.size() || !t)
 		return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor: bad slot or request");
@@ -1770,8 +1932,22 @@ extern "C" int mij_batch_set_out_tensor(mij_batch *b, int slot, const mij_out_te
 	const int64_t W = s.desc.width, H = s.desc.height, C = s.desc.n_out;
 	if (t->w < 1 || t->h < 1 || t->x0 < 0 || t->y0 < 0 || (int64_t)t->x0 + t->w > W || (int64_t)t->y0 + t->h > H)
 		return set_err(MIJ_E_ARG, "window %d,%d %dx%d outside the %lldx%lld picture of slot %d", t->x0, t->y0, t->w, t->h, (long long)W, (long long)H, slot);
+	const mij_batch::RszCoef *ch = nullptr, *cv = nullptr;
+	if (rz) {
+		if (rz->filter < MIJ_FILTER_BOX || rz->filter > MIJ_FILTER_LANCZOS || rz->reserved != 0 || rz->out_w < 1 || rz->out_w > 16384 || rz->out_h < 1 ||
+			 rz->out_h > 16384)
+			return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor_resized: %dx%d filter %d reserved %d refused", rz->out_w, rz->out_h, rz->filter, rz->reserved);
+		ch = rsz_coef(b, t->w, rz->out_w, rz->filter);
+		cv = rsz_coef(b, t->h, rz->out_h, rz->filter);
+		if (!ch || !cv)
+			return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor_resized: no coefficients for %dx%d -> %dx%d", t->w, t->h, rz->out_w, rz->out_h);
+		if (!ch->fits || !cv->fits)
+			return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor_resized: %dx%d -> %dx%d filter %d: coefficients could overflow 32-bit sums", t->w, t->h,
+								rz->out_w, rz->out_h, rz->filter);
+	}
 	const bool chw = t->layout == MIJ_LAYOUT_CHW;
-	const int64_t w = t->w, h = t->h, rp = t->row_pitch, pp = chw ? t->plane_pitch : 0;
+	/* the extent written: the window, or the resized window */
+	const int64_t w = rz ? rz->out_w : t->w, h = rz ? rz->out_h : t->h, rp = t->row_pitch, pp = chw ? t->plane_pitch : 0;
 	const int64_t lim = (int64_t)1 << 40; /* keeps the extent below in range */
 	if (rp < 0 || rp > lim || pp < 0 || pp > lim)
 		return set_err(MIJ_E_ARG, "pitch out of range (row %lld, plane %lld)", (long long)rp, (long long)pp);
@@ -1807,12 +1983,30 @@ extern "C" int mij_batch_set_out_tensor(mij_batch *b, int slot, const mij_out_te
 	}
 	mij_batch::TenReq &q = b->ten_req[(size_t)s.ten];
 	q.t = *t;
+	q.rsz = rz != nullptr;
+	if (rz) {
+		q.r = *rz;
+		q.ch = ch;
+		q.cv = cv;
+	}
 	q.esize = es;
 	q.lut = table != nullptr;
 	memset(q.table, 0, sizeof(q.table));
 	if (table)
 		memcpy(q.table, table, (size_t)es * 256 * (size_t)C);
 	return MIJ_OK;
+}
+
+extern "C" int mij_batch_set_out_tensor(mij_batch *b, int slot, const mij_out_tensor *t, const void *table)
+{
+	return set_out_tensor(b, slot, t, nullptr, table);
+}
+
+extern "C" int mij_batch_set_out_tensor_resized(mij_batch *b, int slot, const mij_out_tensor *t, const mij_out_resize *r, const void *table)
+{
+	if (!r)
+		return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor_resized: no resize");
+	return set_out_tensor(b, slot, t, r, table);
 }
 
 extern "C" int mij_batch_timer_begin(mij_batch *b)

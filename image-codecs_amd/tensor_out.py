@@ -5,7 +5,7 @@ Importing this module imports torch; ``import image_codecs_amd`` alone does not 
 from here on first use)."""
 import torch
 
-from .binding import Batch, Context, HostDecoder, MijError, MIJ_DT_U8, MIJ_DT_F16, MIJ_DT_BF16, MIJ_DT_F32, MIJ_LAYOUT_HWC, MIJ_LAYOUT_CHW
+from .binding import FILTERS, Batch, Context, HostDecoder, MijError, MIJ_DT_U8, MIJ_DT_F16, MIJ_DT_BF16, MIJ_DT_F32, MIJ_LAYOUT_HWC, MIJ_LAYOUT_CHW
 
 _DT = {torch.uint8: MIJ_DT_U8, torch.float16: MIJ_DT_F16, torch.bfloat16: MIJ_DT_BF16, torch.float32: MIJ_DT_F32}
 _BITS = {torch.uint8: torch.uint8, torch.float16: torch.int16, torch.bfloat16: torch.int16, torch.float32: torch.int32}
@@ -104,11 +104,13 @@ class TensorDecoder:
         return self._batch
 
     def decode(self, datas, *, req_comp=3, crops=None, flip_x=None, flip_y=None, layout="CHW", dtype=torch.float16, mean=None, std=None,
-               out=None, threads=16):
+               out=None, threads=16, size=None, filter="bilinear"):
         """-> (tensor, reasons).  crops: None (the whole picture; every picture the same size) or one (x0, y0, w, h) per picture, all of
-        the same w and h.  flip_x / flip_y: None, one bool for all, or one per picture.  The value of channel c's byte v is
-        tensor_tables(C, dtype, mean, std)[c][v].  out: a tensor of the right shape and dtype on this device, with any row / plane
-        padding (e.g. a slice of a larger tensor); None allocates one.  A rejected picture leaves its [i] slice untouched (zero in a
+        the same w and h.  size: None, or (out_h, out_w): each window is resized to it with filter (box, bilinear, hamming, bicubic or
+        lanczos; the exact integer contract of mij_batch_set_out_tensor_resized, Pillow's for one channel, crop first), and windows and
+        pictures may then differ in size.  flip_x / flip_y: None, one bool for all, or one per picture (after a resize they reverse the
+        resized columns / rows).  The value of channel c's byte v is tensor_tables(C, dtype, mean, std)[c][v].  out: a tensor of the
+        right shape and dtype on this device, with any row / plane padding (e.g. a slice of a larger tensor); None allocates one.  A rejected picture leaves its [i] slice untouched (zero in a
         tensor allocated here) and gets its reason in reasons[i]; reasons[i] is None for a decoded one."""
         datas = list(datas)
         n = len(datas)
@@ -123,6 +125,15 @@ class TensorDecoder:
             raise ValueError("uint8 output takes no mean / std")
         if crops is not None and len(crops) != n:
             raise ValueError("crops has %d windows for %d pictures" % (len(crops), n))
+        if filter not in FILTERS:
+            raise ValueError("filter must be one of %s (got %r)" % (", ".join(FILTERS), filter))
+        if size is not None:
+            try:
+                size = tuple(int(v) for v in size)
+            except TypeError:
+                raise ValueError("size is (out_h, out_w), got %r" % (size,)) from None
+            if len(size) != 2 or not all(1 <= v <= 16384 for v in size):
+                raise ValueError("size is (out_h, out_w), each 1..16384, got %r" % (size,))
         # headers only: sizes, channels and arena needs, before any device call
         descs, reasons = [], [None] * n
         for i, d in enumerate(datas):
@@ -137,19 +148,19 @@ class TensorDecoder:
             raise ValueError("pictures decode to different channel counts %s (pass req_comp)" % sorted(chans))
         if crops is None:
             sizes = {(d.width, d.height) for d in ok}
-            if len(sizes) > 1:
+            if len(sizes) > 1 and size is None:
                 raise ValueError("pictures of different sizes %s need crops" % sorted(sizes))
             wins = [None if d is None else (0, 0, d.width, d.height) for d in descs]
         else:
             wins = [tuple(int(v) for v in c) for c in crops]
             if any(len(c) != 4 for c in wins):
                 raise ValueError("a crop is (x0, y0, w, h)")
-            if len({c[2:] for c in wins}) > 1:
+            if len({c[2:] for c in wins}) > 1 and size is None:
                 raise ValueError("crop windows of different sizes %s" % sorted({c[2:] for c in wins}))
             for i, (c, d) in enumerate(zip(wins, descs)):
                 if c[2] < 1 or c[3] < 1 or c[0] < 0 or c[1] < 0 or (d is not None and (c[0] + c[2] > d.width or c[1] + c[3] > d.height)):
                     raise ValueError("crop %s of picture %d outside its %dx%d picture" % (c, i, d.width if d else 0, d.height if d else 0))
-        whs = {c[2:] for c in wins if c is not None}
+        whs = {c[2:] for c in wins if c is not None} if size is None else {(size[1], size[0])}
         C = req_comp if req_comp else (chans.pop() if chans else None)
         if out is not None:
             if out.dim() != 4:
@@ -198,8 +209,12 @@ class TensorDecoder:
             if descs[i] is not None:
                 b.descs[sl] = descs[i]  # already probed: spares set_out_tensor a second header parse
             x0, y0 = wins[i][0], wins[i][1]
-            b.set_out_tensor(sl, out.data_ptr() + i * st[0] * es, _DT[dtype], MIJ_LAYOUT_CHW if layout == "CHW" else MIJ_LAYOUT_HWC,
-                             x0, y0, w, h, row_pitch, plane_pitch, fx[i], fy[i], tb)
+            lay = MIJ_LAYOUT_CHW if layout == "CHW" else MIJ_LAYOUT_HWC
+            if size is None:
+                b.set_out_tensor(sl, out.data_ptr() + i * st[0] * es, _DT[dtype], lay, x0, y0, w, h, row_pitch, plane_pitch, fx[i], fy[i], tb)
+            else:
+                b.set_out_tensor_resized(sl, out.data_ptr() + i * st[0] * es, _DT[dtype], lay, x0, y0, wins[i][2], wins[i][3], w, h, row_pitch,
+                                         plane_pitch, fx[i], fy[i], tb, filter)
         torch.cuda.current_stream(self.device).synchronize()
         b.submit()
         b.wait()

@@ -390,6 +390,36 @@ typedef struct {
 int mij_batch_set_out_tensor(mij_batch *b, int slot, const mij_out_tensor *t, const void *table);
 
 /*
+ * Resized tensor output: the crop window (t->x0, t->y0, t->w, t->h) resized to out_w x out_h, then flipped, looked up in the tables and
+ * stored as mij_batch_set_out_tensor does.  The contract, exact and integer (Pillow's resampling of one 8-bit channel, crop first):
+ * every channel is resized on its own with filter F -- box, bilinear, hamming, bicubic (a = -0.5) or lanczos (a = 3), supports
+ * 0.5 / 1 / 1 / 2 / 3.  One axis with `in` samples and `out` outputs:
+ *     scale = in / out (double);  fs = max(scale, 1);  support = F.support * fs;  ksize = 2 * ceil(support) + 1
+ *     for o in 0..out-1:
+ *         center = (o + 0.5) * scale
+ *         lo = max((int)(center - support + 0.5), 0);  n = min((int)(center + support + 0.5), in) - lo
+ *         w[t] = F((t + lo - center + 0.5) / fs) for t < n;  ww = sum of w[t] in order;  w[t] /= ww when ww != 0
+ *         k[t] = (int)(w[t] * 2^22 + (w[t] < 0 ? -0.5 : 0.5))
+ *         y[o] = clamp((2^21 + sum_t x[lo + t] * k[t]) >> 22, 0, 255)
+ * The horizontal pass runs first over every row of the window (skipped when out_w == w) and gives a uint8 h x out_w image; the
+ * vertical pass runs on that (skipped when out_h == h).  Taps never read outside the window.  flip_x / flip_y then reverse the
+ * output's columns / rows.  Unlike Pillow, RGBA and grey+alpha pictures are not premultiplied: alpha is one more channel.
+ * A resized request with out_w == w and out_h == h gives the plain request's bytes.
+ */
+enum { MIJ_FILTER_BOX = 0, MIJ_FILTER_BILINEAR = 1, MIJ_FILTER_HAMMING = 2, MIJ_FILTER_BICUBIC = 3, MIJ_FILTER_LANCZOS = 4 };
+typedef struct {
+	int32_t out_w, out_h; /* 1..16384 */
+	int32_t filter;       /* MIJ_FILTER_* */
+	int32_t reserved;     /* 0 */
+} mij_out_resize;
+/* t->w, t->h: the source window (inside the picture); pitches, alignment and the one-allocation check apply to the out_w x out_h
+ * extent.  Otherwise the rules of mij_batch_set_out_tensor: before upload, not for a skipped slot, forgotten by reset, a refused
+ * request keeps the earlier one.  A slot holds one tensor request: a plain and a resized request replace each other.  MIJ_E_ARG also
+ * for an unknown filter, out_w or out_h outside 1..16384, a non-zero reserved, and for coefficients whose 32-bit sums could
+ * overflow (255 * sum |k| + 2^21 >= 2^31; no such case is known). */
+int mij_batch_set_out_tensor_resized(mij_batch *b, int slot, const mij_out_tensor *t, const mij_out_resize *r, const void *table);
+
+/*
  * Encoder half (BASELINE config 5): the JPEG writer's colour transform, edge replication, 2x2
  * chroma mean, float AAN forward DCT and quantiser (codec/jpeg_write.c:24-74, :96-118, :283-352)
  * for a batch of images on the GPU.  Input: interleaved 8-bit pixels, comp 1..4 as passed to

@@ -150,6 +150,12 @@ size_t mjw_emit_to_memory(const mjw_plan *p, const int16_t *du, unsigned char *o
  * alpha channel of n_out 2 and 4 gets v / 255.0f -- the reference's expressions, evaluated with libm's pow. */
 void mjh_ldr_to_hdr_lut(int n_out, float gamma, float scale, float *lut);
 
+/* One axis of the resized tensor output's contract (include/mij.h, mij_batch_set_out_tensor_resized): `in` samples to `out` with
+ * filter MIJ_FILTER_*.  Returns ksize, the taps per output row of k, or MIJ_E_ARG (in or out outside 1..2^24, unknown filter).
+ * When lo_n and k are non-NULL and cap >= out * ksize, also writes lo_n[2*o] = lo and lo_n[2*o+1] = n of output o and its fixed-point
+ * taps at k[o*ksize .. o*ksize + n) (the rest of the row is zero); with a smaller cap nothing is written. */
+int mjh_resize_coeffs(int in, int out, int filter, int32_t *lo_n, int32_t *k, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif
