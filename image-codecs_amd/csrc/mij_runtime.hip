@@ -51,6 +51,62 @@ extern "C" int mij_device_count(void)
 	return n;
 }
 
+/* ------------------------------------------------------------------ decode kernel families */
+
+/* kernel families of a launch plan, in launch order.  MK_RS_FAST + RS_*: pass 2 compiled per resampler (k_resample_fast) */
+enum { MK_PLANES = 0, MK_RESAMPLE, MK_RS_FAST, MK_420 = MK_RS_FAST + RS_KINDS, MK_422, MK_444, MK_GREY, MK_440, MK_420W, MK_440W /* k_fused420w / k_fused440w: 512 threads, wide pictures */, MK_420X /* 1024 threads: one workgroup per CU */, MK_420S, MK_420T /* 128 / 64 threads: narrow pictures */, MK_422W, MK_422X, MK_422S, MK_422T /* k_fused422 with 512 / 1024 / 128 / 64 threads */, MK_1X1C /* k_fused1x1c: RGB-tagged / CMYK / YCCK at 1x1 */, MK_420C, MK_440C /* column segments: a row of MCUs beyond a CU's LDS */, MK_KINDS };
+
+/* A family's kernels per variant = 4 * (n_out == 4) + 2 * wide IDCT + compact planes (k_resample_fast: 4 * (n_out == 4) + 2 * YCbCr
+ * colour).  Every decode kernel takes (const DevImage *, const Work *, const uint8_t *in, uint8_t *out); io says which arenas in and
+ * out are. */
+enum { MK_VARIANTS = 8 };
+enum Arena { COEF_OUT, COEF_PLANES, PLANES_OUT };
+struct Family {
+	unsigned threads; /* workgroup size */
+	Arena io;
+	bool band; /* a band kernel: dynamic LDS up to the whole CU's */
+	const void *k[MK_VARIANTS];
+};
+#define MIJ_K(...) reinterpret_cast<const void *>(&__VA_ARGS__)
+#define MIJ_NWB(K)                                                                                                                  \
+	{ MIJ_K(K<3, false, false>), MIJ_K(K<3, false, true>), MIJ_K(K<3, true, false>), MIJ_K(K<3, true, true>),                      \
+	  MIJ_K(K<4, false, false>), MIJ_K(K<4, false, true>), MIJ_K(K<4, true, false>), MIJ_K(K<4, true, true>) }
+#define MIJ_WB(K) { MIJ_K(K<false, false>), MIJ_K(K<false, true>), MIJ_K(K<true, false>), MIJ_K(K<true, true>) }
+#define MIJ_RSF(R)                                                                                                                  \
+	{ MIJ_K(k_resample_fast<R, false, 3>), nullptr, MIJ_K(k_resample_fast<R, true, 3>), nullptr,                                   \
+	  MIJ_K(k_resample_fast<R, false, 4>), nullptr, MIJ_K(k_resample_fast<R, true, 4>), nullptr }
+static const Family families[MK_KINDS] = {
+	/* MK_PLANES */ {256, COEF_PLANES, false, MIJ_WB(k_idct_planes)},
+	/* MK_RESAMPLE */ {256, PLANES_OUT, false, {MIJ_K(k_resample_color)}},
+	{256, PLANES_OUT, false, MIJ_RSF(RS_ROW1)},
+	{256, PLANES_OUT, false, MIJ_RSF(RS_V2)},
+	{256, PLANES_OUT, false, MIJ_RSF(RS_H2)},
+	{256, PLANES_OUT, false, MIJ_RSF(RS_HV2)},
+	{256, PLANES_OUT, false, MIJ_RSF(RS_GEN2)},
+	{256, PLANES_OUT, false, MIJ_RSF(RS_GEN4)},
+	/* MK_420 */ {MIJ_F420_NT, COEF_OUT, true, MIJ_NWB(k_fused420)},
+	/* MK_422 */ {MIJ_F420_NT, COEF_OUT, true, MIJ_NWB(k_fused422)},
+	/* MK_444 */ {256, COEF_OUT, false, MIJ_NWB(k_fused444)},
+	/* MK_GREY */ {256, COEF_OUT, false, MIJ_WB(k_fused_grey)},
+	/* MK_440 */ {MIJ_F420_NT, COEF_OUT, true, MIJ_NWB(k_fused440)},
+	/* MK_420W */ {MIJ_F420W_NT, COEF_OUT, true, MIJ_NWB(k_fused420w)},
+	/* MK_440W */ {MIJ_F420W_NT, COEF_OUT, true, MIJ_NWB(k_fused440w)},
+	/* MK_420X */ {MIJ_F420X_NT, COEF_OUT, true, MIJ_NWB(k_fused420x)},
+	/* MK_420S */ {MIJ_F420S_NT, COEF_OUT, true, MIJ_NWB(k_fused420s)},
+	/* MK_420T */ {MIJ_F420T_NT, COEF_OUT, true, MIJ_NWB(k_fused420t)},
+	/* MK_422W */ {MIJ_F420W_NT, COEF_OUT, true, MIJ_NWB(k_fused422w)},
+	/* MK_422X */ {MIJ_F420X_NT, COEF_OUT, true, MIJ_NWB(k_fused422x)},
+	/* MK_422S */ {MIJ_F420S_NT, COEF_OUT, true, MIJ_NWB(k_fused422s)},
+	/* MK_422T */ {MIJ_F420T_NT, COEF_OUT, true, MIJ_NWB(k_fused422t)},
+	/* MK_1X1C */ {256, COEF_OUT, false, MIJ_NWB(k_fused1x1c)},
+	/* MK_420C */ {MIJ_F420C_NT, COEF_OUT, true, MIJ_NWB(k_fused420c)},
+	/* MK_440C */ {MIJ_F420C_NT, COEF_OUT, true, MIJ_NWB(k_fused440c)},
+};
+#undef MIJ_RSF
+#undef MIJ_WB
+#undef MIJ_NWB
+#undef MIJ_K
+
 /* ------------------------------------------------------------------ context */
 
 struct mij_ctx {
@@ -104,26 +160,10 @@ extern "C" int mij_ctx_create(int device, mij_ctx **out)
 	}
 	c->max_dyn_lds = 160 * 1024;
 	/* allow the fused band kernels to use the whole 160 KiB of LDS for wide images */
-#define MIJ_LDS_ATTR(K) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds)
-#define MIJ_LDS_ATTR8(K)                                                                                                           \
-	MIJ_LDS_ATTR((K<3, false, false>)); MIJ_LDS_ATTR((K<3, true, false>)); MIJ_LDS_ATTR((K<4, false, false>)); MIJ_LDS_ATTR((K<4, true, false>)); \
-	MIJ_LDS_ATTR((K<3, false, true>)); MIJ_LDS_ATTR((K<3, true, true>)); MIJ_LDS_ATTR((K<4, false, true>)); MIJ_LDS_ATTR((K<4, true, true>))
-	MIJ_LDS_ATTR8(k_fused420);
-	MIJ_LDS_ATTR8(k_fused420w);
-	MIJ_LDS_ATTR8(k_fused420x);
-	MIJ_LDS_ATTR8(k_fused420s);
-	MIJ_LDS_ATTR8(k_fused420t);
-	MIJ_LDS_ATTR8(k_fused440);
-	MIJ_LDS_ATTR8(k_fused440w);
-	MIJ_LDS_ATTR8(k_fused420c);
-	MIJ_LDS_ATTR8(k_fused440c);
-	MIJ_LDS_ATTR8(k_fused422);
-	MIJ_LDS_ATTR8(k_fused422w);
-	MIJ_LDS_ATTR8(k_fused422x);
-	MIJ_LDS_ATTR8(k_fused422s);
-	MIJ_LDS_ATTR8(k_fused422t);
-#undef MIJ_LDS_ATTR8
-#undef MIJ_LDS_ATTR
+	for (const Family &f : families)
+		if (f.band)
+			for (const void *k : f.k)
+				(void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
 	(void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_encode420), hipFuncAttributeMaxDynamicSharedMemorySize, MIJ_ENC_LDS);
 	(void)hipGetLastError();
 	*out = c;
@@ -197,6 +237,16 @@ extern "C" int mij_ctx_info(const mij_ctx *ctx, char *arch, size_t arch_len, int
 
 /* ------------------------------------------------------------------ batch */
 
+/* the kernel family the last upload chose for a slot (mij_batch_slot_path) */
+enum SlotPath { PATH_NONE = 0, PATH_420, PATH_TWO_PASS, PATH_444, PATH_422, PATH_GREY, PATH_440, PATH_1X1C };
+
+/* what classify chose for a slot: the path, the family (MK_*) and variant whose work list takes its items (two-pass: pass 2's),
+ * column segments per band, and the LDS of a whole row of MCUs (the band kernels) */
+struct Choice {
+	int path = PATH_NONE, kind = -1, var = 0, nseg = 1;
+	size_t lds = 0;
+};
+
 struct Slot {
 	mij_image_desc desc;
 	DevImage dev;
@@ -207,67 +257,69 @@ struct Slot {
 	int dev_coef;      /* 1: the GPU entropy stage wrote the coefficient planes in HBM; nothing to upload */
 	int es_index;      /* index into the entropy arena's scan list, or -1 */
 	int coef_bytes_fmt; /* 1: compact planes in HBM (low bytes + escapes + DC array), 0: int16 tile layout */
-	int path;          /* 0 none, 1 fused 4:2:0, 2 two-pass, 3 fused 4:4:4, 4 fused 4:2:2, 5 fused grey, 6 fused 4:4:0 */
+	Choice choice;     /* of the last upload; path 0 none, 1 fused 4:2:0, 2 two-pass, 3 fused 4:4:4, 4 fused 4:2:2, 5 fused grey, 6 fused 4:4:0, 7 fused 1x1 colour */
 	int f32;           /* float output: index of the slot's request (mij_batch::f32_req), -1 none */
 	int ten;           /* tensor output: index of the slot's request (mij_batch::ten_req), -1 none */
 };
 
-/* kernel families of a launch plan, in launch order */
-/* MK_RS_FAST + RS_*: pass 2 compiled per resampler (k_resample_fast); list index [n_out == 4][YCbCr colour][0] */
-enum { MK_PLANES = 0, MK_RESAMPLE, MK_RS_FAST, MK_420 = MK_RS_FAST + RS_KINDS, MK_422, MK_444, MK_GREY, MK_440, MK_420W, MK_440W /* k_fused420w / k_fused440w: 512 threads, wide pictures */, MK_420X /* 1024 threads: one workgroup per CU */, MK_420S, MK_420T /* 128 / 64 threads: narrow pictures */, MK_422W, MK_422X, MK_422S, MK_422T /* k_fused422 with 512 / 1024 / 128 / 64 threads */, MK_1X1C /* k_fused1x1c: RGB-tagged / CMYK / YCCK at 1x1 */, MK_420C, MK_440C /* column segments: a row of MCUs beyond a CU's LDS */, MK_KINDS };
 struct Work4 { /* WorkBand and WorkIdct are both four u32 */
 	uint32_t a, b, c, d;
 };
 
+/* an output pass's plan -- descriptors, tables and work list -- in one pinned buffer and its device copy */
+struct PlanBuf {
+	uint8_t *h = nullptr, *d = nullptr;
+	size_t cap = 0;
+	size_t items = 0, lut_at = 0, work_at = 0; /* work items of the last upload; byte offsets of the tables and the work list */
+};
+
 struct mij_batch {
-	mij_ctx *ctx;
-	hipStream_t stream;
-	hipEvent_t ev_begin, ev_end;
-	hipEvent_t ev_pack0, ev_pack1; /* around k_pack_c8 in the last upload (mij_batch_pack_ms); created on first use */
-	bool pack_timed;
-	int max_images;
+	mij_ctx *ctx = nullptr;
+	hipStream_t stream = nullptr;
+	hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+	hipEvent_t ev_pack0 = nullptr, ev_pack1 = nullptr; /* around k_pack_c8 in the last upload (mij_batch_pack_ms); created on first use */
+	bool pack_timed = false;
+	int max_images = 0;
 	/* arenas */
-	uint8_t *stage;
-	size_t stage_cap, stage_used;
-	uint8_t *d_coef;
-	size_t coef_cap, coef_used;
-	uint8_t *d_out;
-	size_t out_cap, out_used;
-	uint8_t *d_planes;
-	size_t planes_cap;
-	uint8_t *d_up16; /* upload scratch: int16 planes on their way into compact planes (k_pack_c8), stage_cap bytes */
-	uint32_t *d_l1max, *h_l1max; /* per slot: largest per-block L1 the pack kernel saw (MIJ_FLAG_L1_ON_DEVICE); max_images entries, created on first use */
+	uint8_t *stage = nullptr;
+	size_t stage_cap = 0, stage_used = 0;
+	uint8_t *d_coef = nullptr;
+	size_t coef_cap = 0, coef_used = 0;
+	uint8_t *d_out = nullptr;
+	size_t out_cap = 0, out_used = 0;
+	uint8_t *d_planes = nullptr;
+	size_t planes_cap = 0;
+	uint8_t *d_up16 = nullptr; /* upload scratch: int16 planes on their way into compact planes (k_pack_c8), stage_cap bytes */
+	uint32_t *d_l1max = nullptr, *h_l1max = nullptr; /* per slot: largest per-block L1 the pack kernel saw (MIJ_FLAG_L1_ON_DEVICE); max_images entries, created on first use */
 	/* descriptors + work lists (pinned host mirror + device copy) */
-	DevImage *h_imgs, *d_imgs;
-	Work4 *h_work, *d_work;
-	size_t work_cap;
+	DevImage *h_imgs = nullptr, *d_imgs = nullptr;
+	Work4 *h_work = nullptr, *d_work = nullptr;
+	size_t work_cap = 0;
 	std::vector<Slot> slots;
-	/* launch plan built by upload */
+	/* launch plan built by upload: one per non-empty (family, variant) work list */
 	struct Launch {
-		int kind, nout, wide, b8;
+		int kind, var;
 		size_t first, count, lds;
 	};
 	std::vector<Launch> launches;
-	bool uploaded, launched;
-	int force_generic; /* 0: fused kernels where they apply; 1: two-pass path for every image; 2: and its run-time-general pass 2 */
-	int coef_fmt;  /* format new coefficient planes get in HBM: 1 compact (default), 0 int16 (MIJ_COEF_FORMAT=int16, mij_batch_set_coef_format) */
-	int band_rows; /* MCU rows per fused workgroup; 0 = automatic */
-	struct EsArena *es; /* GPU entropy stage, allocated by mij_batch_entropy_reserve */
+	bool uploaded = false, launched = false;
+	int force_generic = 0; /* 0: fused kernels where they apply; 1: two-pass path for every image; 2: and its run-time-general pass 2 */
+	int coef_fmt = 1;  /* format new coefficient planes get in HBM: 1 compact (default), 0 int16 (MIJ_COEF_FORMAT=int16, mij_batch_set_coef_format) */
+	int band_rows = 0; /* MCU rows per fused workgroup; 0 = automatic */
+	struct EsArena *es = nullptr; /* GPU entropy stage, allocated by mij_batch_entropy_reserve */
 	/* float output (mij_batch_set_out_f32): the arena, one request per slot that asked (its place in the arena and its tables), and what
-	 * upload made of them for k_out_f32 -- descriptors, tables and (slot, chunk) work list in one pinned / device buffer pair */
-	uint8_t *d_f32;
-	size_t f32_cap, f32_used;
+	 * upload made of them for k_out_f32 -- descriptors, tables and (slot, chunk) work list */
+	uint8_t *d_f32 = nullptr;
+	size_t f32_cap = 0, f32_used = 0;
 	struct F32Req {
 		int slot;
 		size_t off;
 		float lut[MIJ_F32_LUT_FLOATS];
 	};
 	std::vector<F32Req> f32_req;
-	uint8_t *h_f32plan, *d_f32plan;
-	size_t f32plan_cap;
-	size_t f32_items, f32_lut_at, f32_work_at; /* work items of the last upload; byte offsets of the tables and the work list in the plan */
+	PlanBuf f32plan;
 	/* tensor output (mij_batch_set_out_tensor): one validated request per slot that asked, and what upload made of them for
-	 * k_out_tensor -- descriptors, tables and (request, rows, columns) work list in one pinned / device buffer pair */
+	 * k_out_tensor -- descriptors, tables and (request, rows, columns) work list */
 	struct RszCoef {
 		std::vector<int32_t> v; /* lo, n pairs [out][2], then taps [out][ks] */
 		int ks;
@@ -284,20 +336,20 @@ struct mij_batch {
 		uint8_t table[MIJ_TEN_LUT_BYTES];
 	};
 	std::vector<TenReq> ten_req;
-	uint8_t *h_tenplan, *d_tenplan;
-	size_t tenplan_cap;
-	size_t ten_items, ten_lut_at, ten_work_at;
+	PlanBuf tenplan;
 	/* resized tensor output (mij_batch_set_out_tensor_resized): coefficients per (in, out, filter), kept until reset (std::map: the
 	 * requests point at them), and k_out_resize's plan -- descriptors, tables, coefficients and work list -- in a buffer pair of its own */
 	std::map<uint64_t, RszCoef> rsz_coef;
-	uint8_t *h_rszplan, *d_rszplan;
-	size_t rszplan_cap;
-	size_t rsz_items, rsz_lut_at, rsz_work_at;
+	PlanBuf rszplan;
 };
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static void es_free_fwd(struct EsArena *e);
 static void es_reset_fwd(struct EsArena *e);
+
+/* one free per device / pinned pointer, which is left null */
+template <typename T> static void free_dev(T *&p) { if (p) (void)hipFree(p); p = nullptr; }
+template <typename T> static void free_host(T *&p) { if (p) (void)hipHostFree(p); p = nullptr; }
 
 static inline size_t comp_tiles(const mij_comp_desc &cp) { return ((size_t)(cp.bw * cp.bh) + 63) >> 6; }
 
@@ -324,39 +376,11 @@ extern "C" int mij_batch_create(mij_ctx *ctx, int max_images, size_t stage_bytes
 		return set_err(MIJ_E_NOMEM, "out of host memory");
 	b->ctx = ctx;
 	b->max_images = max_images;
-	b->stage = nullptr;
-	b->d_coef = b->d_out = b->d_planes = nullptr;
-	b->h_imgs = b->d_imgs = nullptr;
-	b->h_work = b->d_work = nullptr;
-	b->d_up16 = nullptr;
-	b->d_l1max = b->h_l1max = nullptr;
 	b->stage_cap = stage_bytes;
 	b->coef_cap = coef_bytes;
 	b->out_cap = out_bytes;
-	b->stage_used = b->coef_used = b->out_used = 0;
-	b->planes_cap = 0;
-	b->work_cap = 0;
-	b->uploaded = b->launched = false;
-	b->force_generic = 0;
-	b->band_rows = 0;
-	{
-		const char *fmt = getenv("MIJ_COEF_FORMAT");
-		b->coef_fmt = (fmt && (!strcmp(fmt, "int16") || !strcmp(fmt, "0"))) ? 0 : 1;
-	}
-	b->es = nullptr;
-	b->d_f32 = b->h_f32plan = b->d_f32plan = nullptr;
-	b->f32_cap = b->f32_used = b->f32plan_cap = 0;
-	b->f32_items = b->f32_lut_at = b->f32_work_at = 0;
-	b->h_tenplan = b->d_tenplan = nullptr;
-	b->tenplan_cap = 0;
-	b->ten_items = b->ten_lut_at = b->ten_work_at = 0;
-	b->h_rszplan = b->d_rszplan = nullptr;
-	b->rszplan_cap = 0;
-	b->rsz_items = b->rsz_lut_at = b->rsz_work_at = 0;
-	b->stream = nullptr;
-	b->ev_begin = b->ev_end = nullptr;
-	b->ev_pack0 = b->ev_pack1 = nullptr;
-	b->pack_timed = false;
+	const char *fmt = getenv("MIJ_COEF_FORMAT");
+	b->coef_fmt = (fmt && (!strcmp(fmt, "int16") || !strcmp(fmt, "0"))) ? 0 : 1;
 	const char *env = getenv("MIJ_BAND_ROWS");
 	if (env)
 		b->band_rows = atoi(env);
@@ -394,52 +418,27 @@ extern "C" void mij_batch_destroy(mij_batch *b)
 	(void)hipSetDevice(b->ctx->device);
 	if (b->stream)
 		(void)hipStreamSynchronize(b->stream);
-	if (b->stage)
-		(void)hipHostFree(b->stage);
-	if (b->d_coef)
-		(void)hipFree(b->d_coef);
-	if (b->d_out)
-		(void)hipFree(b->d_out);
-	if (b->d_planes)
-		(void)hipFree(b->d_planes);
-	if (b->h_imgs)
-		(void)hipHostFree(b->h_imgs);
-	if (b->d_imgs)
-		(void)hipFree(b->d_imgs);
-	if (b->h_work)
-		(void)hipHostFree(b->h_work);
-	if (b->d_work)
-		(void)hipFree(b->d_work);
-	if (b->d_up16)
-		(void)hipFree(b->d_up16);
-	if (b->d_l1max)
-		(void)hipFree(b->d_l1max);
-	if (b->h_l1max)
-		(void)hipHostFree(b->h_l1max);
+	free_host(b->stage);
+	free_dev(b->d_coef);
+	free_dev(b->d_out);
+	free_dev(b->d_planes);
+	free_host(b->h_imgs);
+	free_dev(b->d_imgs);
+	free_host(b->h_work);
+	free_dev(b->d_work);
+	free_dev(b->d_up16);
+	free_dev(b->d_l1max);
+	free_host(b->h_l1max);
 	if (b->es)
 		es_free_fwd(b->es);
-	if (b->d_f32)
-		(void)hipFree(b->d_f32);
-	if (b->h_f32plan)
-		(void)hipHostFree(b->h_f32plan);
-	if (b->d_f32plan)
-		(void)hipFree(b->d_f32plan);
-	if (b->h_tenplan)
-		(void)hipHostFree(b->h_tenplan);
-	if (b->d_tenplan)
-		(void)hipFree(b->d_tenplan);
-	if (b->h_rszplan)
-		(void)hipHostFree(b->h_rszplan);
-	if (b->d_rszplan)
-		(void)hipFree(b->d_rszplan);
-	if (b->ev_begin)
-		(void)hipEventDestroy(b->ev_begin);
-	if (b->ev_end)
-		(void)hipEventDestroy(b->ev_end);
-	if (b->ev_pack0)
-		(void)hipEventDestroy(b->ev_pack0);
-	if (b->ev_pack1)
-		(void)hipEventDestroy(b->ev_pack1);
+	free_dev(b->d_f32);
+	for (PlanBuf *p : {&b->f32plan, &b->tenplan, &b->rszplan}) {
+		free_host(p->h);
+		free_dev(p->d);
+	}
+	for (hipEvent_t ev : {b->ev_begin, b->ev_end, b->ev_pack0, b->ev_pack1})
+		if (ev)
+			(void)hipEventDestroy(ev);
 	if (b->stream)
 		(void)hipStreamDestroy(b->stream);
 	delete b;
@@ -457,11 +456,9 @@ extern "C" int mij_batch_reset(mij_batch *b)
 	b->launches.clear();
 	b->f32_req.clear();
 	b->f32_used = 0;
-	b->f32_items = 0;
 	b->ten_req.clear();
-	b->ten_items = 0;
 	b->rsz_coef.clear();
-	b->rsz_items = 0;
+	b->f32plan.items = b->tenplan.items = b->rszplan.items = 0;
 	es_reset_fwd(b->es);
 	return MIJ_OK;
 }
@@ -585,7 +582,7 @@ static int add_common(mij_batch *b, const mij_image_desc *d, int clone_of, bool 
 	s.es_index = -1;
 	s.coef_bytes_fmt = clone_of >= 0 ? b->slots[(size_t)clone_of].coef_bytes_fmt : 0;
 	s.coef_bytes = cbytes;
-	s.path = 0;
+	s.choice = Choice();
 	s.f32 = -1;
 	s.ten = -1;
 	if (clone_of < 0) {
@@ -713,7 +710,7 @@ extern "C" int mij_batch_slot_path(const mij_batch *b, int slot)
 {
 	if (!b || slot < 0 || slot >= (int)b->slots.size())
 		return 0;
-	return b->slots[(size_t)slot].path;
+	return b->slots[(size_t)slot].choice.path;
 }
 extern "C" int mij_batch_force_generic(mij_batch *b, int on)
 {
@@ -724,65 +721,6 @@ extern "C" int mij_batch_force_generic(mij_batch *b, int on)
 	return MIJ_OK;
 }
 
-/* can the fused h2v2 kernel take this image? */
-static bool fused420_ok(const mij_batch *b, const mij_image_desc &d)
-{
-	if (b->force_generic || (d.flags & MIJ_FLAG_SKIP))
-		return false;
-	if (d.ncomp != 3 || d.color != MIJ_COLOR_YCBCR || (d.n_out != 3 && d.n_out != 4))
-		return false;
-	if (d.comp[0].h != 2 || d.comp[0].v != 2)
-		return false;
-	for (int c = 1; c < 3; ++c)
-		if (d.comp[c].h != 1 || d.comp[c].v != 1)
-			return false;
-	return true; /* any width: a row of MCUs beyond the LDS of a CU goes in column segments (fused420_kind) */
-}
-
-/* single-component images: IDCT straight into the pixel buffer */
-/* h1v2 (4:4:0): luma 1x2, chroma 1x1 -- the band kernel with H2 = false, 304 * mcu_x bytes of LDS */
-static size_t fused440_lds(const mij_image_desc &d) { return (size_t)d.mcu_x * (16 * 8 + 2 * 8 * 8 + 2 * 8 + 4 * 8); }
-static bool fused440_ok(const mij_batch *b, const mij_image_desc &d)
-{
-	if (b->force_generic || (d.flags & MIJ_FLAG_SKIP))
-		return false;
-	if (d.ncomp != 3 || d.color != MIJ_COLOR_YCBCR || (d.n_out != 3 && d.n_out != 4))
-		return false;
-	if (d.comp[0].h != 1 || d.comp[0].v != 2)
-		return false;
-	for (int c = 1; c < 3; ++c)
-		if (d.comp[c].h != 1 || d.comp[c].v != 1)
-			return false;
-	return true; /* any width, see fused420_ok */
-}
-
-static bool fused_grey_ok(const mij_batch *b, const mij_image_desc &d)
-{
-	if (b->force_generic || (d.flags & MIJ_FLAG_SKIP))
-		return false;
-	/* one component -- or the luma of a YCbCr file asked for as grey (req_comp 1 / 2: the reference resamples only component 0
-	 * then, codec/jpeg.c:2246,:2380-2430), when the luma plane has the picture's own resolution: the chroma planes are not even
-	 * transformed */
-	const bool luma_only = d.ncomp == 3 && d.comp[0].h == d.h_max && d.comp[0].v == d.v_max && d.n_out < 3;
-	return (d.ncomp == 1 || luma_only) && d.color == MIJ_COLOR_GREY && d.n_out >= 1 && d.n_out <= 4 && (uint64_t)d.width * d.height * d.n_out < 0xfffffff0ull;
-}
-
-/* can the fused h2v1 kernel take this image? */
-static bool fused422_ok(const mij_batch *b, const mij_image_desc &d)
-{
-	if (b->force_generic || (d.flags & MIJ_FLAG_SKIP))
-		return false;
-	if (d.ncomp != 3 || d.color != MIJ_COLOR_YCBCR || (d.n_out != 3 && d.n_out != 4))
-		return false;
-	if (d.comp[0].h != 2 || d.comp[0].v != 1)
-		return false;
-	for (int c = 1; c < 3; ++c)
-		if (d.comp[c].h != 1 || d.comp[c].v != 1)
-			return false;
-	return (size_t)d.mcu_x * 256 + 16 <= (size_t)b->ctx->max_dyn_lds;
-}
-
-/* can the register-resident 4:4:4 kernel take this image? */
 /* Which specialised pass 2 (RS_*, mij_kernels.h) serves an image of the two-pass path, or -1 for the run-time-general
  * k_resample_color: component 0 (and 3) at full resolution, components 1 and 2 sharing factors that divide, W % 4 == 0,
  * three or four output channels.  *ycc: YCbCr colour (stbi__YCbCr_to_RGB_row) as opposed to RGB-tagged / CMYK / YCCK. */
@@ -815,23 +753,85 @@ static bool all_1x1(const mij_image_desc &d)
 			return false;
 	return (uint64_t)d.width * d.height * d.n_out < 0xfffffff0ull;
 }
-static bool fused444_ok(const mij_batch *b, const mij_image_desc &d)
+
+/* LDS per MCU column of the band kernels: 4:2:0, and 4:4:0 (H2 = false) */
+static const size_t LDS_COL_420 = 16 * 16 + 2 * 8 * 8 + 2 * 16 + 4 * 8, LDS_COL_440 = 16 * 8 + 2 * 8 * 8 + 2 * 8 + 4 * 8;
+/* MCU columns up to which the 4:2:0 and 4:2:2 band kernels run with one / two waves (mij_kernels.h, k_fused420s / t) */
+static const int ONE_WAVE_COLS = 24, TWO_WAVE_COLS = 56;
+
+/* Which form of a band kernel a picture takes: by the workgroups of its width that fit a CU's LDS, and for narrow pictures by how many
+ * waves a row of MCUs keeps busy (mij_kernels.h, k_fused420w / x / s / t) */
+static int band_form(size_t lds, size_t cap, int mcu_x, int mk, int mk_w, int mk_x, int mk_s, int mk_t)
 {
-	if (b->force_generic || (d.flags & MIJ_FLAG_SKIP) || (d.n_out != 3 && d.n_out != 4))
-		return false;
-	/* three-component YCbCr, or four components whose transform is YCbCr with the fourth ignored (codec/jpeg.c:2367-2370): the kernel only touches components 0-2 */
-	if (!((d.ncomp == 3 && d.color == MIJ_COLOR_YCBCR) || (d.ncomp == 4 && d.color == MIJ_COLOR_YCBCRA)))
-		return false;
-	return all_1x1(d);
+	if (2 * lds > cap)
+		return mk_x;
+	if (3 * lds > cap)
+		return mk_w;
+	return mcu_x <= ONE_WAVE_COLS ? mk_t : (mcu_x <= TWO_WAVE_COLS ? mk_s : mk);
 }
-/* k_fused1x1c: RGB-tagged (codec/jpeg.c:2325-2335), Adobe CMYK (:2343-2354), YCCK (:2355-2366) with every component at 1x1 */
-static bool fused1x1c_ok(const mij_batch *b, const mij_image_desc &d)
+
+/* Column segments of a picture too wide for one workgroup's LDS (bytes_per_col per MCU column): the fewest segments, of equal width, of
+ * which two fit a CU with their two halo columns each.  Returns the segment count; segment k spans MCU columns [mcu_x * k / n, mcu_x * (k + 1) / n). */
+static int band_segments(size_t cap, int mcu_x, size_t bytes_per_col)
 {
-	if (b->force_generic || (d.flags & MIJ_FLAG_SKIP) || (d.n_out != 3 && d.n_out != 4))
-		return false;
-	if (!((d.ncomp == 3 && d.color == MIJ_COLOR_RGB) || (d.ncomp == 4 && (d.color == MIJ_COLOR_CMYK || d.color == MIJ_COLOR_YCCK))))
-		return false;
-	return all_1x1(d);
+	const int fit = (int)(cap / (2 * bytes_per_col)) - 2; /* two workgroups per CU (mij_kernels.h, k_fused420c) */
+	if (fit < 1)
+		return mcu_x; /* cannot happen with 160 KiB of LDS: one column per segment */
+	return (mcu_x + fit - 1) / fit;
+}
+static size_t band_segment_lds(int mcu_x, int nseg, size_t bytes_per_col)
+{
+	int widest = 0;
+	for (int k = 0; k < nseg; ++k) {
+		const int w = (int)((long)mcu_x * (k + 1) / nseg - (long)mcu_x * k / nseg);
+		widest = w > widest ? w : widest;
+	}
+	return (size_t)(widest + 2) * bytes_per_col;
+}
+
+/* The kernel family of a slot, in order of precedence: fused 4:2:0, grey, 4:2:2, 4:4:0, 4:4:4, 1x1 colour, else the two-pass path.
+ * The YCbCr band kernels take any width (a row of MCUs beyond the LDS of a CU goes in column segments) but 4:2:2, whose row has to fit. */
+static Choice classify(const mij_batch *b, const Slot &s)
+{
+	const mij_image_desc &d = s.desc;
+	const size_t cap = (size_t)b->ctx->max_dyn_lds;
+	const int o4 = d.n_out == 4 ? 4 : 0, var = o4 | ((d.flags & MIJ_FLAG_WIDE_IDCT) ? 2 : 0) | (s.coef_bytes_fmt ? 1 : 0);
+	if (d.flags & MIJ_FLAG_SKIP) /* rejected by the host stage after it got a slot */
+		return Choice();
+	if (!b->force_generic) {
+		const bool rgb_out = d.n_out == 3 || d.n_out == 4;
+		const bool ycc = d.ncomp == 3 && d.color == MIJ_COLOR_YCBCR && rgb_out && d.comp[1].h == 1 && d.comp[1].v == 1 && d.comp[2].h == 1 && d.comp[2].v == 1;
+		const int lh = d.comp[0].h, lv = d.comp[0].v;
+		/* one component -- or the luma of a YCbCr file asked for as grey (req_comp 1 / 2: the reference resamples only component 0
+		 * then, codec/jpeg.c:2246,:2380-2430), when the luma plane has the picture's own resolution: the chroma planes are not even
+		 * transformed */
+		const bool luma_only = d.ncomp == 3 && lh == d.h_max && lv == d.v_max && d.n_out < 3;
+		if (ycc && lh == 2 && lv == 2) {
+			const size_t lds = (size_t)d.mcu_x * LDS_COL_420;
+			const int mk = lds > cap ? MK_420C : band_form(lds, cap, d.mcu_x, MK_420, MK_420W, MK_420X, MK_420S, MK_420T);
+			return Choice{PATH_420, mk, var, mk == MK_420C ? band_segments(cap, d.mcu_x, LDS_COL_420) : 1, lds};
+		}
+		if ((d.ncomp == 1 || luma_only) && d.color == MIJ_COLOR_GREY && d.n_out >= 1 && d.n_out <= 4 && (uint64_t)d.width * d.height * d.n_out < 0xfffffff0ull)
+			return Choice{PATH_GREY, MK_GREY, var & 3};
+		if (ycc && lh == 2 && lv == 1 && (size_t)d.mcu_x * 256 + 16 <= cap) {
+			const size_t lds = (size_t)d.mcu_x * 256 + 16;
+			return Choice{PATH_422, band_form(lds, cap, d.mcu_x, MK_422, MK_422W, MK_422X, MK_422S, MK_422T), var, 1, lds};
+		}
+		if (ycc && lh == 1 && lv == 2) {
+			const size_t lds = (size_t)d.mcu_x * LDS_COL_440;
+			const int mk = lds > cap ? MK_440C : (3 * lds > cap ? MK_440W : MK_440);
+			return Choice{PATH_440, mk, var, mk == MK_440C ? band_segments(cap, d.mcu_x, LDS_COL_440) : 1, lds};
+		}
+		/* 4:4:4: three-component YCbCr, or four components whose transform is YCbCr with the fourth ignored (codec/jpeg.c:2367-2370): the
+		 * kernel only touches components 0-2.  k_fused1x1c: RGB-tagged (codec/jpeg.c:2325-2335), Adobe CMYK (:2343-2354), YCCK (:2355-2366) */
+		if (rgb_out && ((d.ncomp == 3 && d.color == MIJ_COLOR_YCBCR) || (d.ncomp == 4 && d.color == MIJ_COLOR_YCBCRA)) && all_1x1(d))
+			return Choice{PATH_444, MK_444, var};
+		if (rgb_out && ((d.ncomp == 3 && d.color == MIJ_COLOR_RGB) || (d.ncomp == 4 && (d.color == MIJ_COLOR_CMYK || d.color == MIJ_COLOR_YCCK))) && all_1x1(d))
+			return Choice{PATH_1X1C, MK_1X1C, var};
+	}
+	int ycc = 0;
+	const int rk = resample_fast_kind(b, d, &ycc);
+	return rk < 0 ? Choice{PATH_TWO_PASS, MK_RESAMPLE, 0} : Choice{PATH_TWO_PASS, MK_RS_FAST + rk, o4 | ycc << 1};
 }
 
 /* Small tables (image descriptors, work lists, Huffman tables) go to the device by a copy KERNEL reading the
@@ -893,12 +893,8 @@ static int grow_pair(T *&h, T *&d, size_t &cap, size_t need)
 	if (need <= cap)
 		return MIJ_OK;
 	size_t ncap = need + need / 2 + 64;
-	if (h)
-		(void)hipHostFree(h);
-	if (d)
-		(void)hipFree(d);
-	h = nullptr;
-	d = nullptr;
+	free_host(h);
+	free_dev(d);
 	cap = 0;
 	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h), sizeof(T) * ncap, hipHostMallocDefault));
 	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof(T) * ncap));
@@ -906,92 +902,29 @@ static int grow_pair(T *&h, T *&d, size_t &cap, size_t need)
 	return MIJ_OK;
 }
 
-/* experiment knobs (environment, read once): MIJ_SEG_MIN = MCU columns beyond which a picture goes in column segments although its row
- * fits the LDS; MIJ_SEG_COLS = widest segment in MCU columns (0: whatever fills the LDS) */
-static int seg_min_cols()
+/* Puts an output pass's plan of `need` bytes on the device: grows the buffer pair (waiting for the stream first, whose launches may
+ * still read the old one), lets fill write the pinned side, copies it up on the batch stream, and records the items and offsets. */
+template <typename Fill>
+static int plan_put(mij_batch *b, PlanBuf &p, size_t need, size_t items, size_t lut_at, size_t work_at, Fill fill)
 {
-	static int v = -1;
-	if (v < 0) {
-		const char *e = getenv("MIJ_SEG_MIN");
-		v = e ? atoi(e) : 1 << 30;
-	}
-	return v;
-}
-static int seg_max_cols()
-{
-	static int v = -1;
-	if (v < 0) {
-		const char *e = getenv("MIJ_SEG_COLS");
-		v = e ? atoi(e) : 0;
-	}
-	return v;
-}
-static size_t fused420_lds(const mij_image_desc &d) { return (size_t)d.mcu_x * (16 * 16 + 2 * 8 * 8 + 2 * 16 + 4 * 8); }
-/* fewer than three workgroups of the band kernel fit a CU's LDS: the eight-wave form (k_fused420w) */
-/* which form of the band kernel a 4:2:0 picture takes (-1: none): by the workgroups of its width that fit a CU's LDS, and for narrow
- * pictures by how many waves a row of MCUs keeps busy (mij_kernels.h, k_fused420w / x / s / t) */
-static int fused420_kind(const mij_batch *b, const mij_image_desc &d)
-{
-	if (!fused420_ok(b, d))
-		return -1;
-	const size_t lds = fused420_lds(d), cap = (size_t)b->ctx->max_dyn_lds;
-	if (lds > cap || d.mcu_x > seg_min_cols())
-		return MK_420C;
-	if (2 * lds > cap)
-		return MK_420X;
-	if (3 * lds > cap)
-		return MK_420W;
-	return d.mcu_x <= 24 ? MK_420T : (d.mcu_x <= 56 ? MK_420S : MK_420);
-}
-#ifndef MIJ_422T_MAX /* MCU columns up to which k_fused422 runs with one / two waves (A/B: 0 switches a form off) */
-#define MIJ_422T_MAX 24
-#endif
-#ifndef MIJ_422S_MAX
-#define MIJ_422S_MAX 56
-#endif
-static int band_threads(int kind)
-{
-	switch (kind) {
-	case MK_420X: case MK_422X: return MIJ_F420X_NT;
-	case MK_420C: case MK_440C: return MIJ_F420C_NT;
-	case MK_420W: case MK_440W: case MK_422W: return MIJ_F420W_NT;
-	case MK_420S: case MK_422S: return MIJ_F420S_NT;
-	case MK_420T: case MK_422T: return MIJ_F420T_NT;
-	default: return MIJ_F420_NT;
-	}
-}
-static bool fused440_wide(const mij_batch *b, const mij_image_desc &d) { return fused440_ok(b, d) && 3 * fused440_lds(d) > (size_t)b->ctx->max_dyn_lds; }
-static int fused440_kind(const mij_batch *b, const mij_image_desc &d)
-{
-	return !fused440_ok(b, d) ? -1 : (fused440_lds(d) > (size_t)b->ctx->max_dyn_lds ? MK_440C : (fused440_wide(b, d) ? MK_440W : MK_440));
-}
-/* Column segments of a picture too wide for one workgroup's LDS (bytes_per_col per MCU column): the fewest segments, of equal width, of
- * which two fit a CU with their two halo columns each.  Returns the segment count; segment k spans MCU columns [mcu_x * k / n, mcu_x * (k + 1) / n). */
-static int band_segments(const mij_batch *b, int mcu_x, size_t bytes_per_col)
-{
-	const int most = (int)((size_t)b->ctx->max_dyn_lds / bytes_per_col) - 2; /* what fits at all */
-	int fit = (int)((size_t)b->ctx->max_dyn_lds / (2 * bytes_per_col)) - 2;   /* two workgroups per CU (mij_kernels.h, k_fused420c) */
-	if (seg_max_cols() > 0)
-		fit = seg_max_cols() < most ? seg_max_cols() : most;
-	if (fit < 1)
-		return mcu_x; /* cannot happen with 160 KiB of LDS: one column per segment */
-	return (mcu_x + fit - 1) / fit;
-}
-static size_t band_segment_lds(int mcu_x, int nseg, size_t bytes_per_col)
-{
-	int widest = 0;
-	for (int k = 0; k < nseg; ++k) {
-		const int w = (int)((long)mcu_x * (k + 1) / nseg - (long)mcu_x * k / nseg);
-		widest = w > widest ? w : widest;
-	}
-	return (size_t)(widest + 2) * bytes_per_col;
+	if (need > p.cap)
+		HIP_TRY(hipStreamSynchronize(b->stream));
+	int rc = grow_pair(p.h, p.d, p.cap, align_up(need, 4));
+	if (rc != MIJ_OK)
+		return rc;
+	fill(p.h);
+	HIP_TRY(copy_table(p.d, p.h, align_up(need, 4), b->stream));
+	p.items = items;
+	p.lut_at = lut_at;
+	p.work_at = work_at;
+	return MIJ_OK;
 }
 
 /* Float output: k_out_f32's descriptors, tables and work list -- (float slot, chunk) items, MIJ_F32_CHUNK input bytes each -- built
  * next to the decode plan and copied up on the batch stream.  A batch without float requests does nothing here. */
 static int f32_plan(mij_batch *b)
 {
-	b->f32_items = 0;
+	b->f32plan.items = 0;
 	const size_t nreq = b->f32_req.size();
 	if (!nreq)
 		return MIJ_OK;
@@ -1008,28 +941,20 @@ static int f32_plan(mij_batch *b)
 		return MIJ_OK;
 	const size_t lut_at = align_up(sizeof(DevF32) * nreq, 256), work_at = lut_at + sizeof(float) * MIJ_F32_LUT_FLOATS * nreq;
 	const size_t need = work_at + sizeof(WorkF32) * work.size();
-	if (need > b->f32plan_cap)
-		HIP_TRY(hipStreamSynchronize(b->stream));
-	int rc = grow_pair(b->h_f32plan, b->d_f32plan, b->f32plan_cap, align_up(need, 4));
-	if (rc != MIJ_OK)
-		return rc;
-	DevF32 *fd = reinterpret_cast<DevF32 *>(b->h_f32plan);
-	for (size_t f = 0; f < nreq; ++f) {
-		const mij_batch::F32Req &q = b->f32_req[f];
-		const Slot &s = b->slots[(size_t)q.slot];
-		fd[f].src_off = s.dev.out_off;
-		fd[f].dst_off = q.off;
-		fd[f].nbytes = (uint64_t)s.desc.n_out * (uint64_t)s.desc.width * (uint64_t)s.desc.height;
-		fd[f].n_out = (uint32_t)s.desc.n_out;
-		fd[f].pad = 0;
-		memcpy(b->h_f32plan + lut_at + sizeof(float) * MIJ_F32_LUT_FLOATS * f, q.lut, sizeof(q.lut));
-	}
-	memcpy(b->h_f32plan + work_at, work.data(), sizeof(WorkF32) * work.size());
-	HIP_TRY(copy_table(b->d_f32plan, b->h_f32plan, align_up(need, 4), b->stream));
-	b->f32_items = work.size();
-	b->f32_lut_at = lut_at;
-	b->f32_work_at = work_at;
-	return MIJ_OK;
+	return plan_put(b, b->f32plan, need, work.size(), lut_at, work_at, [&](uint8_t *h) {
+		DevF32 *fd = reinterpret_cast<DevF32 *>(h);
+		for (size_t f = 0; f < nreq; ++f) {
+			const mij_batch::F32Req &q = b->f32_req[f];
+			const Slot &s = b->slots[(size_t)q.slot];
+			fd[f].src_off = s.dev.out_off;
+			fd[f].dst_off = q.off;
+			fd[f].nbytes = (uint64_t)s.desc.n_out * (uint64_t)s.desc.width * (uint64_t)s.desc.height;
+			fd[f].n_out = (uint32_t)s.desc.n_out;
+			fd[f].pad = 0;
+			memcpy(h + lut_at + sizeof(float) * MIJ_F32_LUT_FLOATS * f, q.lut, sizeof(q.lut));
+		}
+		memcpy(h + work_at, work.data(), sizeof(WorkF32) * work.size());
+	});
 }
 
 /* k_out_tensor's / k_out_resize's descriptor of a request */
@@ -1058,7 +983,7 @@ static void dev_tensor(DevTensor &d, const mij_batch::TenReq &q, const Slot &s)
  * A batch without tensor requests does nothing here. */
 static int ten_plan(mij_batch *b)
 {
-	b->ten_items = 0;
+	b->tenplan.items = 0;
 	const size_t nreq = b->ten_req.size();
 	if (!nreq)
 		return MIJ_OK;
@@ -1082,24 +1007,15 @@ static int ten_plan(mij_batch *b)
 		return set_err(MIJ_E_ARG, "tensor output: %zu work items", work.size());
 	const size_t lut_at = align_up(sizeof(DevTensor) * nreq, 256), work_at = lut_at + MIJ_TEN_LUT_BYTES * nreq;
 	const size_t need = work_at + sizeof(WorkTensor) * work.size();
-	if (need > b->tenplan_cap)
-		HIP_TRY(hipStreamSynchronize(b->stream));
-	int rc = grow_pair(b->h_tenplan, b->d_tenplan, b->tenplan_cap, align_up(need, 4));
-	if (rc != MIJ_OK)
-		return rc;
-	DevTensor *td = reinterpret_cast<DevTensor *>(b->h_tenplan);
-	for (size_t t = 0; t < nreq; ++t) {
-		const mij_batch::TenReq &q = b->ten_req[t];
-		const Slot &s = b->slots[(size_t)q.slot];
-		dev_tensor(td[t], q, s);
-		memcpy(b->h_tenplan + lut_at + MIJ_TEN_LUT_BYTES * t, q.table, MIJ_TEN_LUT_BYTES);
-	}
-	memcpy(b->h_tenplan + work_at, work.data(), sizeof(WorkTensor) * work.size());
-	HIP_TRY(copy_table(b->d_tenplan, b->h_tenplan, align_up(need, 4), b->stream));
-	b->ten_items = work.size();
-	b->ten_lut_at = lut_at;
-	b->ten_work_at = work_at;
-	return MIJ_OK;
+	return plan_put(b, b->tenplan, need, work.size(), lut_at, work_at, [&](uint8_t *h) {
+		DevTensor *td = reinterpret_cast<DevTensor *>(h);
+		for (size_t t = 0; t < nreq; ++t) {
+			const mij_batch::TenReq &q = b->ten_req[t];
+			dev_tensor(td[t], q, b->slots[(size_t)q.slot]);
+			memcpy(h + lut_at + MIJ_TEN_LUT_BYTES * t, q.table, MIJ_TEN_LUT_BYTES);
+		}
+		memcpy(h + work_at, work.data(), sizeof(WorkTensor) * work.size());
+	});
 }
 
 /* Resized tensor output: k_out_resize's descriptors, tables, coefficients (each (in, out, filter) once) and work list -- (request, band of
@@ -1109,7 +1025,7 @@ static int ten_plan(mij_batch *b)
  * within MIJ_RSZ_VCAP (else they stay in the plan).  A batch without resized requests does nothing. */
 static int rsz_plan(mij_batch *b)
 {
-	b->rsz_items = 0;
+	b->rszplan.items = 0;
 	const size_t nreq = b->ten_req.size();
 	size_t nrsz = 0;
 	for (const mij_batch::TenReq &q : b->ten_req)
@@ -1150,61 +1066,57 @@ static int rsz_plan(mij_batch *b)
 	if (work.size() > 0x7fffffffu)
 		return set_err(MIJ_E_ARG, "resized tensor output: %zu work items", work.size());
 	const size_t work_at = align_up(off, 16), need = work_at + sizeof(WorkResize) * work.size();
-	if (need > b->rszplan_cap)
-		HIP_TRY(hipStreamSynchronize(b->stream));
-	int rc = grow_pair(b->h_rszplan, b->d_rszplan, b->rszplan_cap, align_up(need, 4));
-	if (rc != MIJ_OK)
-		return rc;
-	DevResize *rd = reinterpret_cast<DevResize *>(b->h_rszplan);
-	memset(rd, 0, sizeof(DevResize) * nreq);
-	for (size_t t = 0; t < nreq; ++t) {
-		const mij_batch::TenReq &q = b->ten_req[t];
-		if (!q.rsz || (b->slots[(size_t)q.slot].desc.flags & MIJ_FLAG_SKIP))
-			continue;
-		DevResize &d = rd[t];
-		dev_tensor(d.t, q, b->slots[(size_t)q.slot]);
-		d.hco = at[q.ch];
-		d.vco = at[q.cv];
-		d.out_w = (uint32_t)q.r.out_w;
-		d.out_h = (uint32_t)q.r.out_h;
-		d.ksh = (uint32_t)q.ch->ks;
-		d.ksv = (uint32_t)q.cv->ks;
-		d.mul32 = (q.ch->big || q.cv->big) ? 1u : 0u;
-		d.kglobal = kglobal[t];
-		d.vglobal = vglobal[t];
-		memcpy(b->h_rszplan + lut_at + MIJ_TEN_LUT_BYTES * t, q.table, MIJ_TEN_LUT_BYTES);
-	}
-	for (const auto &e : at)
-		memcpy(b->h_rszplan + e.second, e.first->v.data(), e.first->v.size() * sizeof(int32_t));
-	memcpy(b->h_rszplan + work_at, work.data(), sizeof(WorkResize) * work.size());
-	HIP_TRY(copy_table(b->d_rszplan, b->h_rszplan, align_up(need, 4), b->stream));
-	b->rsz_items = work.size();
-	b->rsz_lut_at = lut_at;
-	b->rsz_work_at = work_at;
-	return MIJ_OK;
+	return plan_put(b, b->rszplan, need, work.size(), lut_at, work_at, [&](uint8_t *h) {
+		DevResize *rd = reinterpret_cast<DevResize *>(h);
+		memset(rd, 0, sizeof(DevResize) * nreq);
+		for (size_t t = 0; t < nreq; ++t) {
+			const mij_batch::TenReq &q = b->ten_req[t];
+			if (!q.rsz || (b->slots[(size_t)q.slot].desc.flags & MIJ_FLAG_SKIP))
+				continue;
+			DevResize &d = rd[t];
+			dev_tensor(d.t, q, b->slots[(size_t)q.slot]);
+			d.hco = at[q.ch];
+			d.vco = at[q.cv];
+			d.out_w = (uint32_t)q.r.out_w;
+			d.out_h = (uint32_t)q.r.out_h;
+			d.ksh = (uint32_t)q.ch->ks;
+			d.ksv = (uint32_t)q.cv->ks;
+			d.mul32 = (q.ch->big || q.cv->big) ? 1u : 0u;
+			d.kglobal = kglobal[t];
+			d.vglobal = vglobal[t];
+			memcpy(h + lut_at + MIJ_TEN_LUT_BYTES * t, q.table, MIJ_TEN_LUT_BYTES);
+		}
+		for (const auto &e : at)
+			memcpy(h + e.second, e.first->v.data(), e.first->v.size() * sizeof(int32_t));
+		memcpy(h + work_at, work.data(), sizeof(WorkResize) * work.size());
+	});
 }
 
-extern "C" int mij_batch_upload(mij_batch *b)
-{
-	if (!b)
-		return set_err(MIJ_E_ARG, "batch is NULL");
-	HIP_TRY(hipSetDevice(b->ctx->device));
-	const size_t n = b->slots.size();
-	if (n == 0)
-		return set_err(MIJ_E_STATE, "batch is empty");
+/* ---- mij_batch_upload, step by step.  Each step keeps its copies and launches on the batch stream in the order given here. */
 
-	/* ---- format of the planes in HBM.  Slots the GPU entropy stage wrote keep theirs; host-staged slots get the
-	 * batch's format (compact by default: uploaded as int16 into the scratch, packed by k_pack_c8); clones follow
-	 * their source (which precedes them). */
+static bool host_staged(const Slot &s) { return s.clone_of < 0 && !s.dev_coef; }
+static bool l1_on_device(const Slot &s) { return host_staged(s) && (s.desc.flags & MIJ_FLAG_L1_ON_DEVICE) && !(s.desc.flags & MIJ_FLAG_SKIP); }
+
+/* (slot, component, first block) per 256 blocks of a component's tiles: the pack kernel's work items */
+static void push_tiles(std::vector<Work4> &L, uint32_t i, const mij_image_desc &d)
+{
+	for (int c = 0; c < d.ncomp; ++c)
+		for (uint32_t f = 0, nb = (uint32_t)comp_tiles(d.comp[c]) * 64u; f < nb; f += 256)
+			L.push_back(Work4{i, (uint32_t)c, f, 0u});
+}
+
+/* Format of the planes in HBM.  Slots the GPU entropy stage wrote keep theirs; host-staged slots get the batch's format (compact by
+ * default: uploaded as int16 into the scratch, packed by k_pack_c8); clones follow their source (which precedes them). */
+static int plane_formats(mij_batch *b)
+{
 	bool need_pack = false;
-	for (size_t i = 0; i < n; ++i) {
-		Slot &s = b->slots[i];
+	for (Slot &s : b->slots) {
 		if (s.clone_of >= 0)
 			s.coef_bytes_fmt = b->slots[(size_t)s.clone_of].coef_bytes_fmt;
 		else if (!s.dev_coef) /* planes the host staged compact keep that format whatever the batch's default */
 			s.coef_bytes_fmt = ((b->coef_fmt || (s.desc.flags & (MIJ_FLAG_STAGED_COMPACT | MIJ_FLAG_L1_ON_DEVICE))) && !(s.desc.flags & MIJ_FLAG_SKIP)) ? 1 : 0;
 		layout_coef(s);
-		if (s.clone_of < 0 && !s.dev_coef && s.coef_bytes_fmt && !(s.desc.flags & MIJ_FLAG_STAGED_COMPACT))
+		if (host_staged(s) && s.coef_bytes_fmt && !(s.desc.flags & MIJ_FLAG_STAGED_COMPACT))
 			need_pack = true;
 	}
 	if (need_pack && !b->d_up16) {
@@ -1212,288 +1124,257 @@ extern "C" int mij_batch_upload(mij_batch *b)
 		if (e != hipSuccess)
 			return set_err(e == hipErrorOutOfMemory ? MIJ_E_NOMEM : MIJ_E_HIP, "upload scratch: %s", hipGetErrorString(e));
 	}
+	return MIJ_OK;
+}
 
-	/* ---- progressive files whose L1 bound the host left to the device (MIJ_FLAG_L1_ON_DEVICE): their planes go up and are packed NOW, the
-	 * pack kernel takes every block's L1 on the way, the maxima come back, and MIJ_FLAG_WIDE_IDCT is set before the launch plan below sorts
-	 * the images by it.  Afterwards these slots hold finished compact planes in HBM (dev_coef: later uploads leave them alone). */
-	{
-		std::vector<Work4> pre;
-		for (size_t i = 0; i < n; ++i) {
-			const Slot &s = b->slots[i];
-			if (s.clone_of < 0 && !s.dev_coef && (s.desc.flags & MIJ_FLAG_L1_ON_DEVICE) && !(s.desc.flags & MIJ_FLAG_SKIP))
-				for (int c = 0; c < s.desc.ncomp; ++c)
-					for (uint32_t f = 0, nb = (uint32_t)comp_tiles(s.desc.comp[c]) * 64u; f < nb; f += 256)
-						pre.push_back(Work4{(uint32_t)i, (uint32_t)c, f, 0u});
+/* Progressive files whose L1 bound the host left to the device (MIJ_FLAG_L1_ON_DEVICE): their planes go up and are packed NOW, the
+ * pack kernel takes every block's L1 on the way, the maxima come back, and MIJ_FLAG_WIDE_IDCT is set before the decode plan sorts the
+ * images by it.  Afterwards these slots hold finished compact planes in HBM (dev_coef: later uploads leave them alone). */
+static int l1_prepack(mij_batch *b)
+{
+	const size_t n = b->slots.size();
+	std::vector<Work4> pre;
+	for (size_t i = 0; i < n; ++i)
+		if (l1_on_device(b->slots[i]))
+			push_tiles(pre, (uint32_t)i, b->slots[i].desc);
+	if (pre.empty())
+		return MIJ_OK;
+	if (!b->d_l1max) {
+		HIP_TRY(hipMalloc(reinterpret_cast<void **>(&b->d_l1max), sizeof(uint32_t) * (size_t)b->max_images));
+		HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&b->h_l1max), sizeof(uint32_t) * (size_t)b->max_images, hipHostMallocDefault));
+	}
+	if (pre.size() > b->work_cap)
+		HIP_TRY(hipStreamSynchronize(b->stream));
+	int rc = grow_pair(b->h_work, b->d_work, b->work_cap, pre.size());
+	if (rc != MIJ_OK)
+		return rc;
+	memcpy(b->h_work, pre.data(), pre.size() * sizeof(Work4));
+	for (size_t i = 0; i < n; ++i) {
+		Slot &s = b->slots[i];
+		s.dev.src16_off = s.stage_off == MIJ_NO_STAGE ? 0 : s.stage_off;
+		b->h_imgs[i] = s.dev;
+		if (host_staged(s) && (s.desc.flags & MIJ_FLAG_L1_ON_DEVICE))
+			b->h_imgs[i].flags |= MIJ_DEV_L1_MAX;
+	}
+	HIP_TRY(copy_table(b->d_imgs, b->h_imgs, sizeof(DevImage) * n, b->stream));
+	HIP_TRY(copy_table(b->d_work, b->h_work, sizeof(Work4) * pre.size(), b->stream));
+	HIP_TRY(hipMemsetAsync(b->d_l1max, 0, sizeof(uint32_t) * n, b->stream));
+	for (const Slot &s : b->slots)
+		if (l1_on_device(s)) {
+			size_t bytes16 = 0;
+			for (int c = 0; c < s.desc.ncomp; ++c)
+				bytes16 += comp_tiles(s.desc.comp[c]) << 13;
+			HIP_TRY(hipMemcpyAsync(b->d_up16 + s.stage_off, b->stage + s.stage_off, bytes16, hipMemcpyHostToDevice, b->stream));
 		}
-		if (!pre.empty()) {
-			if (!b->d_l1max) {
-				HIP_TRY(hipMalloc(reinterpret_cast<void **>(&b->d_l1max), sizeof(uint32_t) * (size_t)b->max_images));
-				HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&b->h_l1max), sizeof(uint32_t) * (size_t)b->max_images, hipHostMallocDefault));
-			}
-			if (pre.size() > b->work_cap)
-				HIP_TRY(hipStreamSynchronize(b->stream));
-			int rc0;
-			if ((rc0 = grow_pair(b->h_work, b->d_work, b->work_cap, pre.size())) != MIJ_OK)
-				return rc0;
-			memcpy(b->h_work, pre.data(), pre.size() * sizeof(Work4));
-			for (size_t i = 0; i < n; ++i) {
-				Slot &s = b->slots[i];
-				s.dev.src16_off = s.stage_off == MIJ_NO_STAGE ? 0 : s.stage_off;
-				b->h_imgs[i] = s.dev;
-				if (s.clone_of < 0 && !s.dev_coef && (s.desc.flags & MIJ_FLAG_L1_ON_DEVICE))
-					b->h_imgs[i].flags |= MIJ_DEV_L1_MAX;
-			}
-			HIP_TRY(copy_table(b->d_imgs, b->h_imgs, sizeof(DevImage) * n, b->stream));
-			HIP_TRY(copy_table(b->d_work, b->h_work, sizeof(Work4) * pre.size(), b->stream));
-			HIP_TRY(hipMemsetAsync(b->d_l1max, 0, sizeof(uint32_t) * n, b->stream));
-			for (size_t i = 0; i < n; ++i) {
-				const Slot &s = b->slots[i];
-				if (s.clone_of < 0 && !s.dev_coef && (s.desc.flags & MIJ_FLAG_L1_ON_DEVICE) && !(s.desc.flags & MIJ_FLAG_SKIP)) {
-					size_t bytes16 = 0;
-					for (int c = 0; c < s.desc.ncomp; ++c)
-						bytes16 += comp_tiles(s.desc.comp[c]) << 13;
-					HIP_TRY(hipMemcpyAsync(b->d_up16 + s.stage_off, b->stage + s.stage_off, bytes16, hipMemcpyHostToDevice, b->stream));
-				}
-			}
-			hipLaunchKernelGGL(k_pack_c8, dim3((unsigned)pre.size()), dim3(256), 0, b->stream, b->d_imgs, reinterpret_cast<const WorkIdct *>(b->d_work), b->d_up16, b->d_coef, b->d_l1max);
-			HIP_TRY(hipGetLastError());
-			HIP_TRY(copy_table_to_host(b->h_l1max, b->d_l1max, sizeof(uint32_t) * n, b->stream));
-			HIP_TRY(hipStreamSynchronize(b->stream));
-			for (size_t i = 0; i < n; ++i) {
-				Slot &s = b->slots[i];
-				if (s.clone_of < 0 && !s.dev_coef && (s.desc.flags & MIJ_FLAG_L1_ON_DEVICE) && !(s.desc.flags & MIJ_FLAG_SKIP)) {
-					s.desc.flags &= ~(uint32_t)MIJ_FLAG_L1_ON_DEVICE;
-					if (b->h_l1max[i] > (uint32_t)MIJ_BLOCK_L1_LIMIT)
-						s.desc.flags |= MIJ_FLAG_WIDE_IDCT;
-					s.dev.flags = (int32_t)s.desc.flags | MIJ_DEV_COEF_BYTES;
-					s.dev_coef = 1;
-				}
-			}
-			for (size_t i = 0; i < n; ++i) { /* clones take their source's verdict */
-				Slot &s = b->slots[i];
-				if (s.clone_of >= 0 && (s.desc.flags & MIJ_FLAG_L1_ON_DEVICE)) {
-					s.desc.flags = b->slots[(size_t)s.clone_of].desc.flags;
-					s.dev.flags = (int32_t)s.desc.flags | MIJ_DEV_COEF_BYTES;
-				}
+	hipLaunchKernelGGL(k_pack_c8, dim3((unsigned)pre.size()), dim3(256), 0, b->stream, b->d_imgs, reinterpret_cast<const WorkIdct *>(b->d_work), b->d_up16, b->d_coef, b->d_l1max);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(copy_table_to_host(b->h_l1max, b->d_l1max, sizeof(uint32_t) * n, b->stream));
+	HIP_TRY(hipStreamSynchronize(b->stream));
+	for (size_t i = 0; i < n; ++i) {
+		Slot &s = b->slots[i];
+		if (l1_on_device(s)) {
+			s.desc.flags &= ~(uint32_t)MIJ_FLAG_L1_ON_DEVICE;
+			if (b->h_l1max[i] > (uint32_t)MIJ_BLOCK_L1_LIMIT)
+				s.desc.flags |= MIJ_FLAG_WIDE_IDCT;
+			s.dev.flags = (int32_t)s.desc.flags | MIJ_DEV_COEF_BYTES;
+			s.dev_coef = 1;
+		}
+	}
+	for (Slot &s : b->slots) /* clones take their source's verdict */
+		if (s.clone_of >= 0 && (s.desc.flags & MIJ_FLAG_L1_ON_DEVICE)) {
+			s.desc.flags = b->slots[(size_t)s.clone_of].desc.flags;
+			s.dev.flags = (int32_t)s.desc.flags | MIJ_DEV_COEF_BYTES;
+		}
+	return MIJ_OK;
+}
+
+/* The decode plan: one work list per (kernel family, variant) with the LDS its launch needs, the pack list, and the bytes of scratch
+ * sample planes the two-pass path needs */
+namespace {
+struct Plan {
+	std::vector<Work4> pack, lists[MK_KINDS][MK_VARIANTS];
+	size_t lds[MK_KINDS][MK_VARIANTS] = {};
+	size_t planes_need = 0;
+};
+} // namespace
+
+/* Automatic band count per family of the 4:2:0 / 4:4:0 band kernels.  The grid runs in "rounds" of (CUs x workgroups per CU by LDS)
+ * co-resident workgroups; the last round of a launch is only as full as the remainder, and every band re-does two chroma block rows
+ * of IDCT as halo.  Pick the bands-per-image (1..16) that minimises  rounds x (1 + halo share)  per unit of work; measured on MI355X:
+ * 1024 x 1080p -> 6 bands (6144 workgroups = 8.0 rounds of 768) beats 4 (5.33 rounds) by ~1.5 %. */
+static const int BAND_CAP = 64; /* most bands per picture of a small 4:2:0 batch, below */
+static void auto_bands(const mij_batch *b, int nb[MK_KINDS])
+{
+	size_t n_fused[MK_KINDS] = {}, mcu_rows_sum[MK_KINDS] = {}, lds_max[MK_KINDS] = {};
+	for (const Slot &s : b->slots)
+		if (s.choice.path == PATH_420 || s.choice.path == PATH_440) {
+			const int k = s.choice.kind;
+			++n_fused[k];
+			mcu_rows_sum[k] += (size_t)s.desc.mcu_y;
+			lds_max[k] = s.choice.lds > lds_max[k] ? s.choice.lds : lds_max[k];
+		}
+	const int cu = b->ctx->prop.multiProcessorCount > 0 ? b->ctx->prop.multiProcessorCount : 256;
+	for (int kind = 0; kind < MK_KINDS; ++kind) {
+		nb[kind] = 1;
+		if (!n_fused[kind])
+			continue;
+		size_t per_cu = lds_max[kind] ? (size_t)b->ctx->max_dyn_lds / lds_max[kind] : 1;
+		const size_t by_waves = 4 * MIJ_F420_WAVES / ((size_t)families[kind].threads / 64); /* waves per SIMD by registers x four SIMDs */
+		per_cu = per_cu < 1 ? 1 : (per_cu > by_waves ? by_waves : per_cu);
+		const size_t slots = (size_t)cu * per_cu;
+		const double avg_rows = (double)mcu_rows_sum[kind] / (double)n_fused[kind];
+		double best = 1e30;
+		/* up to 16 bands per picture; up to BAND_CAP for 4:2:0 batches so small that sixteen bands each leave workgroup slots
+		 * empty (a lone picture from stbi_load, a handful): 16 x 1080p 0.078 -> 0.058 ms.  Not for 4:4:0, whose halo is a larger share
+		 * of a band (0.069 -> 0.093 ms), and not once the slots are full (36 x 5120 x 2880: 0.70 -> 0.73 ms with the higher cap). */
+		const int cap = (kind != MK_440 && kind != MK_440W && kind != MK_440C && n_fused[kind] * 16 <= slots) ? BAND_CAP : 16;
+		for (int k = 1; k <= cap && k <= (int)avg_rows; ++k) {
+			const size_t wgs = n_fused[kind] * (size_t)k;
+			const size_t rounds = (wgs + slots - 1) / slots;
+			/* every inner band edge re-transforms two chroma block rows (4 of an MCU row's 6 blocks' worth), the IDCT being ~45 %
+			 * of the work; a launch also pays about 0.3 band lengths of ramp-up and tail whatever its shape -- without that term
+			 * the model took 3 bands for 1024 x 1080p where 6 measure 1.5 % faster, and 3 for 256 images where 12 measure 4 % faster
+			 * (interleaved runs, profiles/r02z_band_count.txt) */
+			const double halo = 1.0 + 0.45 * 4.0 * (k - 1) / (6.0 * avg_rows);
+			const double cost = ((double)rounds + 0.3) * (avg_rows / k) * halo; /* time ~ (rounds + ramp) x band length */
+			if (cost < best * 0.999) {
+				best = cost;
+				nb[kind] = k;
 			}
 		}
 	}
+}
 
-	/* ---- plan: one work list per (kernel family, n_out, wide IDCT, plane format) */
-	std::vector<Work4> lists[MK_KINDS][2][2][2];
-	size_t lds_need[MK_KINDS][2][2][2];
-	memset(lds_need, 0, sizeof(lds_need));
-	std::vector<Work4> pack;
-	size_t planes_need = 0, planes_off = 0;
-	const int cu = b->ctx->prop.multiProcessorCount > 0 ? b->ctx->prop.multiProcessorCount : 256;
-	/* Automatic band count per image.  The grid runs in "rounds" of (CUs x workgroups per CU by LDS)
-	 * co-resident workgroups; the last round of a launch is only as full as the remainder, and every
-	 * band re-does two chroma block rows of IDCT as halo.  Pick the bands-per-image (1..16) that
-	 * minimises  rounds x (1 + halo share)  per unit of work; measured on MI355X: 1024 x 1080p ->
-	 * 6 bands (6144 workgroups = 8.0 rounds of 768) beats 4 (5.33 rounds) by ~1.5 %. */
-#ifndef MIJ_BAND_CAP
-#define MIJ_BAND_CAP 64
-#endif
-	auto auto_bands = [&](int (*kind_of)(const mij_batch *, const mij_image_desc &), int kind, size_t (*lds_of)(const mij_image_desc &)) -> int {
-		const int nt = band_threads(kind);
-		size_t n_fused = 0, mcu_rows_sum = 0, lds_max = 0;
-		for (size_t i = 0; i < n; ++i)
-			if (kind_of(b, b->slots[i].desc) == kind) {
-				const mij_image_desc &d = b->slots[i].desc;
-				++n_fused;
-				mcu_rows_sum += (size_t)d.mcu_y;
-				if (lds_of(d) > lds_max)
-					lds_max = lds_of(d);
-			}
-		int nb_best = 1;
-		if (n_fused) {
-			size_t per_cu = lds_max ? (size_t)b->ctx->max_dyn_lds / lds_max : 1;
-			const size_t by_waves = 4 * MIJ_F420_WAVES / ((size_t)nt / 64); /* waves per SIMD by registers x four SIMDs */
-			per_cu = per_cu < 1 ? 1 : (per_cu > by_waves ? by_waves : per_cu);
-			const size_t slots = (size_t)cu * per_cu;
-			const double avg_rows = (double)mcu_rows_sum / (double)n_fused;
-			double best = 1e30;
-			/* up to 16 bands per picture; up to MIJ_BAND_CAP for 4:2:0 batches so small that sixteen bands each leave workgroup slots
-			 * empty (a lone picture from stbi_load, a handful): 16 x 1080p 0.078 -> 0.058 ms.  Not for 4:4:0, whose halo is a larger share
-			 * of a band (0.069 -> 0.093 ms), and not once the slots are full (36 x 5120 x 2880: 0.70 -> 0.73 ms with the higher cap). */
-			const int cap = (kind != MK_440 && kind != MK_440W && kind != MK_440C && n_fused * 16 <= slots) ? MIJ_BAND_CAP : 16;
-			for (int nb = 1; nb <= cap && nb <= (int)avg_rows; ++nb) {
-				const size_t wgs = n_fused * (size_t)nb;
-				const size_t rounds = (wgs + slots - 1) / slots;
-				/* every inner band edge re-transforms two chroma block rows (4 of an MCU row's 6 blocks' worth), the IDCT being ~45 %
-				 * of the work; a launch also pays about 0.3 band lengths of ramp-up and tail whatever its shape -- without that term
-				 * the model took 3 bands for 1024 x 1080p where 6 measure 1.5 % faster, and 3 for 256 images where 12 measure 4 % faster
-				 * (interleaved runs, profiles/r02z_band_count.txt) */
-				const double halo = 1.0 + 0.45 * 4.0 * (nb - 1) / (6.0 * avg_rows);
-				const double cost = ((double)rounds + 0.3) * (avg_rows / nb) * halo; /* time ~ (rounds + ramp) x band length */
-				if (cost < best * 0.999) {
-					best = cost;
-					nb_best = nb;
-				}
-			}
-		}
-		return nb_best;
-	};
+/* The work items of a 4:2:0 / 4:4:0 picture: nb bands of about equal MCU rows, each split into the choice's column segments of about equal
+ * MCU columns (only the column-segmented forms read them), and the LDS they need */
+static void push_bands(std::vector<Work4> &L, size_t &lds, uint32_t i, const mij_image_desc &d, const Choice &c, int nb)
+{
+	nb = nb > d.mcu_y ? d.mcu_y : (nb < 1 ? 1 : nb);
+	for (int k = 0; k < nb; ++k)
+		for (int g = 0; g < c.nseg; ++g)
+			L.push_back(Work4{i, (uint32_t)((long)d.mcu_y * k / nb), (uint32_t)((long)d.mcu_y * (k + 1) / nb),
+									(uint32_t)((long)d.mcu_x * g / c.nseg) | (uint32_t)((long)d.mcu_x * (g + 1) / c.nseg) << 16});
+	const size_t need = (c.kind == MK_420C || c.kind == MK_440C) ? band_segment_lds(d.mcu_x, c.nseg, c.lds / (size_t)d.mcu_x) : c.lds;
+	lds = need > lds ? need : lds;
+}
+
+/* (slot, component, first block) per 256 blocks of one component */
+static void push_blocks(std::vector<Work4> &L, uint32_t i, const mij_image_desc &d, int comp)
+{
+	const uint32_t nblk = (uint32_t)(d.comp[comp].bw * d.comp[comp].bh);
+	for (uint32_t f = 0; f < nblk; f += 256)
+		L.push_back(Work4{i, (uint32_t)comp, f, 0u});
+}
+
+static void plan_decode(mij_batch *b, Plan &p)
+{
+	for (Slot &s : b->slots)
+		s.choice = classify(b, s);
 	int auto_nb[MK_KINDS];
-	for (int k = 0; k < MK_KINDS; ++k)
-		auto_nb[k] = 1;
-	for (int k : {MK_420, MK_420W, MK_420X, MK_420S, MK_420T, MK_420C})
-		auto_nb[k] = auto_bands(fused420_kind, k, fused420_lds);
-	for (int k : {MK_440, MK_440W, MK_440C})
-		auto_nb[k] = auto_bands(fused440_kind, k, fused440_lds);
-
-	for (size_t i = 0; i < n; ++i) {
+	auto_bands(b, auto_nb);
+	for (size_t i = 0; i < b->slots.size(); ++i) {
 		Slot &s = b->slots[i];
 		const mij_image_desc &d = s.desc;
-		const int wide = (d.flags & MIJ_FLAG_WIDE_IDCT) ? 1 : 0, b8 = s.coef_bytes_fmt ? 1 : 0, o4 = d.n_out == 4 ? 1 : 0;
-		if (d.flags & MIJ_FLAG_SKIP) { /* rejected by the host stage after it got a slot */
-			s.path = 0;
+		const Choice &c = s.choice;
+		if (c.path == PATH_NONE)
 			continue;
-		}
-		if (s.clone_of < 0 && !s.dev_coef && b8 && !(d.flags & MIJ_FLAG_STAGED_COMPACT)) /* int16 planes in the scratch -> compact planes */
-			for (int c = 0; c < d.ncomp; ++c)
-				for (uint32_t f = 0, nb = (uint32_t)comp_tiles(d.comp[c]) * 64u; f < nb; f += 256)
-					pack.push_back(Work4{(uint32_t)i, (uint32_t)c, f, 0u});
-		auto per_blocks = [&](std::vector<Work4> &L, int comp) {
-			const uint32_t nblk = (uint32_t)(d.comp[comp].bw * d.comp[comp].bh);
-			for (uint32_t f = 0; f < nblk; f += 256)
-				L.push_back(Work4{(uint32_t)i, (uint32_t)comp, f, 0u});
-		};
-		if (fused420_ok(b, d)) {
-			s.path = 1;
-			/* split mcu_y into nb equal-ish bands */
-			const int mk = fused420_kind(b, d);
-			int nb = b->band_rows > 0 ? (d.mcu_y + b->band_rows - 1) / b->band_rows : auto_nb[mk];
-			if (nb > d.mcu_y)
-				nb = d.mcu_y;
-			if (nb < 1)
-				nb = 1;
-			const int nseg = mk == MK_420C ? band_segments(b, d.mcu_x, fused420_lds(d) / (size_t)d.mcu_x) : 1;
-			for (int k = 0; k < nb; ++k)
-				for (int g = 0; g < nseg; ++g) /* cols: only the column-segmented form reads it */
-					lists[mk][o4][wide][b8].push_back(Work4{(uint32_t)i, (uint32_t)((long)d.mcu_y * k / nb), (uint32_t)((long)d.mcu_y * (k + 1) / nb),
-																		 (uint32_t)((long)d.mcu_x * g / nseg) | (uint32_t)((long)d.mcu_x * (g + 1) / nseg) << 16});
-			size_t &l = lds_need[mk][o4][wide][b8];
-			const size_t need = mk == MK_420C ? band_segment_lds(d.mcu_x, nseg, fused420_lds(d) / (size_t)d.mcu_x) : fused420_lds(d);
-			l = need > l ? need : l;
-		} else if (fused_grey_ok(b, d)) {
-			s.path = 5;
-			per_blocks(lists[MK_GREY][0][wide][b8], 0);
-		} else if (fused422_ok(b, d)) {
-			s.path = 4;
-			const size_t lds422 = (size_t)d.mcu_x * 256 + 16, cap422 = (size_t)b->ctx->max_dyn_lds;
-			const int mk422 = 2 * lds422 > cap422 ? MK_422X : (3 * lds422 > cap422 ? MK_422W : (d.mcu_x <= MIJ_422T_MAX ? MK_422T : (d.mcu_x <= MIJ_422S_MAX ? MK_422S : MK_422)));
-			size_t &l = lds_need[mk422][o4][wide][b8];
-			l = lds422 > l ? lds422 : l;
-			/* no halo: bands of about eight MCU rows keep the grid deep without making workgroups short */
+		if (host_staged(s) && s.coef_bytes_fmt && !(d.flags & MIJ_FLAG_STAGED_COMPACT)) /* int16 planes in the scratch -> compact planes */
+			push_tiles(p.pack, (uint32_t)i, d);
+		std::vector<Work4> &L = p.lists[c.kind][c.var];
+		size_t &lds = p.lds[c.kind][c.var];
+		switch (c.path) {
+		case PATH_420:
+		case PATH_440: /* band count by rounds of co-resident workgroups */
+			push_bands(L, lds, (uint32_t)i, d, c, b->band_rows > 0 ? (d.mcu_y + b->band_rows - 1) / b->band_rows : auto_nb[c.kind]);
+			break;
+		case PATH_422: { /* no halo: bands of about eight MCU rows keep the grid deep without making workgroups short */
+			lds = c.lds > lds ? c.lds : lds;
 			const int nb = (d.mcu_y + 7) / 8;
 			for (int k = 0; k < nb; ++k)
-				lists[mk422][o4][wide][b8].push_back(Work4{(uint32_t)i, (uint32_t)((long)d.mcu_y * k / nb), (uint32_t)((long)d.mcu_y * (k + 1) / nb), 0u});
-		} else if (fused440_ok(b, d)) {
-			s.path = 6;
-			const int mk = fused440_kind(b, d);
-			const int nseg = mk == MK_440C ? band_segments(b, d.mcu_x, fused440_lds(d) / (size_t)d.mcu_x) : 1;
-			size_t &l = lds_need[mk][o4][wide][b8];
-			const size_t need = mk == MK_440C ? band_segment_lds(d.mcu_x, nseg, fused440_lds(d) / (size_t)d.mcu_x) : fused440_lds(d);
-			l = need > l ? need : l;
-			/* band count by rounds of co-resident workgroups, as for 4:2:0 */
-			int nb = b->band_rows > 0 ? (d.mcu_y + b->band_rows - 1) / b->band_rows : auto_nb[mk];
-			nb = nb > d.mcu_y ? d.mcu_y : (nb < 1 ? 1 : nb);
-			for (int k = 0; k < nb; ++k)
-				for (int g = 0; g < nseg; ++g)
-					lists[mk][o4][wide][b8].push_back(Work4{(uint32_t)i, (uint32_t)((long)d.mcu_y * k / nb), (uint32_t)((long)d.mcu_y * (k + 1) / nb),
-																		 (uint32_t)((long)d.mcu_x * g / nseg) | (uint32_t)((long)d.mcu_x * (g + 1) / nseg) << 16});
-		} else if (fused444_ok(b, d)) {
-			s.path = 3;
-			per_blocks(lists[MK_444][o4][wide][b8], 0);
-		} else if (fused1x1c_ok(b, d)) {
-			s.path = 7;
-			per_blocks(lists[MK_1X1C][o4][wide][b8], 0);
-		} else {
-			s.path = 2;
-			int ycc = 0;
-			const int rk = resample_fast_kind(b, d, &ycc);
-			std::vector<Work4> &R = rk < 0 ? lists[MK_RESAMPLE][0][0][0] : lists[MK_RS_FAST + rk][o4][ycc][0];
+				L.push_back(Work4{(uint32_t)i, (uint32_t)((long)d.mcu_y * k / nb), (uint32_t)((long)d.mcu_y * (k + 1) / nb), 0u});
+			break;
+		}
+		case PATH_GREY:
+		case PATH_444:
+		case PATH_1X1C:
+			push_blocks(L, (uint32_t)i, d, 0);
+			break;
+		default: { /* PATH_TWO_PASS: pass 2's rows in L, pass 1's blocks in the MK_PLANES list */
 			/* the vs == 2 forms of k_resample_fast take item r as output rows r-1 .. r+2 (row pairs around a chroma row) */
-			const uint32_t r_end = (uint32_t)d.height + ((rk == RS_V2 || rk == RS_HV2) ? 2u : 0u);
+			const uint32_t r_end = (uint32_t)d.height + ((c.kind == MK_RS_FAST + RS_V2 || c.kind == MK_RS_FAST + RS_HV2) ? 2u : 0u);
 			for (uint32_t r = 0; r < r_end; r += MIJ_RESAMPLE_ROWS)
-				R.push_back(Work4{(uint32_t)i, 0u, r, 0u});
-			for (int c = 0; c < d.ncomp; ++c)
-				per_blocks(lists[MK_PLANES][0][wide][b8], c);
+				L.push_back(Work4{(uint32_t)i, 0u, r, 0u});
+			const int wb = ((d.flags & MIJ_FLAG_WIDE_IDCT) ? 2 : 0) | (s.coef_bytes_fmt ? 1 : 0);
+			for (int comp = 0; comp < d.ncomp; ++comp)
+				push_blocks(p.lists[MK_PLANES][wb], (uint32_t)i, d, comp);
 			/* rebase this image's sample planes into the scratch arena */
-			size_t rel0 = 0;
-			for (int c = 0; c < d.ncomp; ++c) {
-				s.dev.comp[c].plane_off = planes_off + rel0;
-				rel0 += align_up((size_t)d.comp[c].bw * 8 * d.comp[c].bh * 8, 256);
+			for (int comp = 0; comp < d.ncomp; ++comp) {
+				s.dev.comp[comp].plane_off = p.planes_need;
+				p.planes_need += align_up((size_t)d.comp[comp].bw * 8 * d.comp[comp].bh * 8, 256);
 			}
-			planes_off += rel0;
-			planes_need = planes_off;
+		}
 		}
 		s.dev.src16_off = s.stage_off == MIJ_NO_STAGE ? 0 : s.stage_off;
 	}
+}
 
-	/* ---- scratch planes for the two-pass path */
-	if (planes_need > b->planes_cap) {
-		HIP_TRY(hipStreamSynchronize(b->stream));
-		if (b->d_planes)
-			(void)hipFree(b->d_planes);
-		b->d_planes = nullptr;
-		b->planes_cap = 0;
-		hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_planes), planes_need);
-		if (e != hipSuccess)
-			return set_err(e == hipErrorOutOfMemory ? MIJ_E_NOMEM : MIJ_E_HIP, "scratch planes: %s", hipGetErrorString(e));
-		b->planes_cap = planes_need;
-	}
+/* scratch planes for the two-pass path */
+static int scratch_planes(mij_batch *b, size_t need)
+{
+	if (need <= b->planes_cap)
+		return MIJ_OK;
+	HIP_TRY(hipStreamSynchronize(b->stream));
+	free_dev(b->d_planes);
+	b->planes_cap = 0;
+	hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_planes), need);
+	if (e != hipSuccess)
+		return set_err(e == hipErrorOutOfMemory ? MIJ_E_NOMEM : MIJ_E_HIP, "scratch planes: %s", hipGetErrorString(e));
+	b->planes_cap = need;
+	return MIJ_OK;
+}
 
-	/* ---- work lists: the pack list first, then one range per launch */
-	size_t total = pack.size();
-	for (int k = 0; k < MK_KINDS; ++k)
-		for (int v = 0; v < 8; ++v)
-			total += lists[k][v >> 2][(v >> 1) & 1][v & 1].size();
+/* work lists: the pack list first, then one range per launch in family and variant order; then the descriptors and the lists go up */
+static int lay_out_work(mij_batch *b, const Plan &p)
+{
+	size_t total = p.pack.size();
+	for (const auto &family : p.lists)
+		for (const std::vector<Work4> &L : family)
+			total += L.size();
 	if (total > b->work_cap)
 		HIP_TRY(hipStreamSynchronize(b->stream));
-	int rc;
-	if ((rc = grow_pair(b->h_work, b->d_work, b->work_cap, total)) != MIJ_OK)
+	int rc = grow_pair(b->h_work, b->d_work, b->work_cap, total);
+	if (rc != MIJ_OK)
 		return rc;
 	b->launches.clear();
-	size_t pos = 0;
-	if (!pack.empty())
-		memcpy(b->h_work, pack.data(), pack.size() * sizeof(Work4));
-	pos = pack.size();
+	if (!p.pack.empty())
+		memcpy(b->h_work, p.pack.data(), p.pack.size() * sizeof(Work4));
+	size_t pos = p.pack.size();
 	for (int k = 0; k < MK_KINDS; ++k)
-		for (int v = 0; v < 8; ++v) {
-			const std::vector<Work4> &L = lists[k][v >> 2][(v >> 1) & 1][v & 1];
+		for (int v = 0; v < MK_VARIANTS; ++v) {
+			const std::vector<Work4> &L = p.lists[k][v];
 			if (L.empty())
 				continue;
 			memcpy(b->h_work + pos, L.data(), L.size() * sizeof(Work4));
-			mij_batch::Launch q;
-			q.kind = k;
-			q.nout = (v >> 2) ? 4 : 3;
-			q.wide = (v >> 1) & 1;
-			q.b8 = v & 1;
-			q.first = pos;
-			q.count = L.size();
-			q.lds = lds_need[k][v >> 2][(v >> 1) & 1][v & 1];
-			if (k == MK_420)
-				if (const char *pad = getenv("MIJ_LDS_PAD")) { /* experiment knob: lower the occupancy on purpose */
-					size_t want = q.lds + (size_t)atol(pad);
-					q.lds = want > (size_t)b->ctx->max_dyn_lds ? (size_t)b->ctx->max_dyn_lds : want;
-				}
-			b->launches.push_back(q);
+			b->launches.push_back(mij_batch::Launch{k, v, pos, L.size(), p.lds[k][v]});
 			pos += L.size();
 		}
+	const size_t n = b->slots.size();
 	for (size_t i = 0; i < n; ++i)
 		b->h_imgs[i] = b->slots[i].dev;
-
-	/* ---- copies, all on the batch stream */
 	HIP_TRY(copy_table(b->d_imgs, b->h_imgs, sizeof(DevImage) * n, b->stream));
 	if (total)
 		HIP_TRY(copy_table(b->d_work, b->h_work, sizeof(Work4) * total, b->stream));
-	/* staged coefficients: own-staging slots are contiguous in the staging arena, the upload scratch and the
-	 * coefficient arena in add order, so runs of them with one destination go up in one copy each */
+	return MIJ_OK;
+}
+
+/* staged coefficients: own-staging slots are contiguous in the staging arena, the upload scratch and the coefficient arena in add
+ * order, so runs of them with one destination go up in one copy each */
+static int copy_coefficients(mij_batch *b)
+{
+	const size_t n = b->slots.size();
 	size_t i = 0;
 	while (i < n) {
-		if (b->slots[i].clone_of >= 0 || b->slots[i].dev_coef || (b->slots[i].desc.flags & MIJ_FLAG_SKIP)) {
+		if (!host_staged(b->slots[i]) || (b->slots[i].desc.flags & MIJ_FLAG_SKIP)) {
 			++i;
 			continue;
 		}
@@ -1504,7 +1385,7 @@ extern "C" int mij_batch_upload(mij_batch *b)
 			const size_t small = (size_t)1 << 20;
 			if (sc.coef_bytes <= small) {
 				size_t j = i, bytes = 0;
-				while (j < n && b->slots[j].clone_of < 0 && !b->slots[j].dev_coef && !(b->slots[j].desc.flags & MIJ_FLAG_SKIP) && (b->slots[j].desc.flags & MIJ_FLAG_STAGED_COMPACT) &&
+				while (j < n && host_staged(b->slots[j]) && !(b->slots[j].desc.flags & MIJ_FLAG_SKIP) && (b->slots[j].desc.flags & MIJ_FLAG_STAGED_COMPACT) &&
 						 b->slots[j].coef_bytes <= small && b->slots[j].stage_off == sc.stage_off + bytes && b->slots[j].coef_base == sc.coef_base + bytes) {
 					bytes += b->slots[j].coef_bytes;
 					++j;
@@ -1521,7 +1402,7 @@ extern "C" int mij_batch_upload(mij_batch *b)
 		size_t j = i, bytes = 0;
 		const int fmt = b->slots[i].coef_bytes_fmt;
 		const size_t s0 = b->slots[i].stage_off, c0 = b->slots[i].coef_base;
-		while (j < n && b->slots[j].clone_of < 0 && !b->slots[j].dev_coef && !(b->slots[j].desc.flags & (MIJ_FLAG_SKIP | MIJ_FLAG_STAGED_COMPACT)) && b->slots[j].coef_bytes_fmt == fmt &&
+		while (j < n && host_staged(b->slots[j]) && !(b->slots[j].desc.flags & (MIJ_FLAG_SKIP | MIJ_FLAG_STAGED_COMPACT)) && b->slots[j].coef_bytes_fmt == fmt &&
 				 b->slots[j].stage_off == s0 + bytes && b->slots[j].coef_base == c0 + bytes) {
 			bytes += b->slots[j].coef_bytes;
 			++j;
@@ -1529,63 +1410,57 @@ extern "C" int mij_batch_upload(mij_batch *b)
 		HIP_TRY(hipMemcpyAsync(fmt ? b->d_up16 + s0 : b->d_coef + c0, b->stage + s0, bytes, hipMemcpyHostToDevice, b->stream));
 		i = j;
 	}
+	return MIJ_OK;
+}
+
+/* k_pack_c8 over the pack list (the head of the work list), between the events mij_batch_pack_ms reads */
+static int launch_pack(mij_batch *b, size_t items)
+{
 	b->pack_timed = false;
-	if (!pack.empty()) {
-		if (!b->ev_pack0) {
-			HIP_TRY(hipEventCreate(&b->ev_pack0));
-			HIP_TRY(hipEventCreate(&b->ev_pack1));
-		}
-		HIP_TRY(hipEventRecord(b->ev_pack0, b->stream));
-		hipLaunchKernelGGL(k_pack_c8, dim3((unsigned)pack.size()), dim3(256), 0, b->stream, b->d_imgs, reinterpret_cast<const WorkIdct *>(b->d_work), b->d_up16, b->d_coef, b->d_l1max);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipEventRecord(b->ev_pack1, b->stream));
-		b->pack_timed = true;
+	if (!items)
+		return MIJ_OK;
+	if (!b->ev_pack0) {
+		HIP_TRY(hipEventCreate(&b->ev_pack0));
+		HIP_TRY(hipEventCreate(&b->ev_pack1));
 	}
-	for (size_t k = 0; k < n; ++k) {
-		const Slot &s = b->slots[k];
-		if (s.clone_of < 0)
-			continue;
-		const Slot &src = b->slots[(size_t)s.clone_of];
-		HIP_TRY(hipMemcpyAsync(b->d_coef + s.coef_base, b->d_coef + src.coef_base, s.coef_bytes, hipMemcpyDeviceToDevice, b->stream));
-	}
-	if ((rc = f32_plan(b)) != MIJ_OK)
+	HIP_TRY(hipEventRecord(b->ev_pack0, b->stream));
+	hipLaunchKernelGGL(k_pack_c8, dim3((unsigned)items), dim3(256), 0, b->stream, b->d_imgs, reinterpret_cast<const WorkIdct *>(b->d_work), b->d_up16, b->d_coef, b->d_l1max);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipEventRecord(b->ev_pack1, b->stream));
+	b->pack_timed = true;
+	return MIJ_OK;
+}
+
+/* clones: their source's planes, device to device */
+static int copy_clones(mij_batch *b)
+{
+	for (const Slot &s : b->slots)
+		if (s.clone_of >= 0)
+			HIP_TRY(hipMemcpyAsync(b->d_coef + s.coef_base, b->d_coef + b->slots[(size_t)s.clone_of].coef_base, s.coef_bytes, hipMemcpyDeviceToDevice, b->stream));
+	return MIJ_OK;
+}
+
+extern "C" int mij_batch_upload(mij_batch *b)
+{
+	if (!b)
+		return set_err(MIJ_E_ARG, "batch is NULL");
+	HIP_TRY(hipSetDevice(b->ctx->device));
+	if (b->slots.empty())
+		return set_err(MIJ_E_STATE, "batch is empty");
+	Plan p;
+	int rc;
+	if ((rc = plane_formats(b)) != MIJ_OK || (rc = l1_prepack(b)) != MIJ_OK)
 		return rc;
-	if ((rc = ten_plan(b)) != MIJ_OK)
+	plan_decode(b, p);
+	if ((rc = scratch_planes(b, p.planes_need)) != MIJ_OK || (rc = lay_out_work(b, p)) != MIJ_OK || (rc = copy_coefficients(b)) != MIJ_OK ||
+		 (rc = launch_pack(b, p.pack.size())) != MIJ_OK || (rc = copy_clones(b)) != MIJ_OK)
 		return rc;
-	if ((rc = rsz_plan(b)) != MIJ_OK)
+	if ((rc = f32_plan(b)) != MIJ_OK || (rc = ten_plan(b)) != MIJ_OK || (rc = rsz_plan(b)) != MIJ_OK)
 		return rc;
 	b->uploaded = true;
 	b->launched = false;
 	return MIJ_OK;
 }
-
-/* one kernel template over (n_out 3/4, wide IDCT, compact planes) */
-#define MIJ_LAUNCH_NWB(K, WT, ARGS)                                                                                                \
-	do {                                                                                                                            \
-		const int v_ = (L.nout == 4 ? 4 : 0) | (L.wide ? 2 : 0) | (L.b8 ? 1 : 0);                                                    \
-		switch (v_) {                                                                                                                \
-		case 0: hipLaunchKernelGGL((K<3, false, false>), grid, block, L.lds, b->stream, b->d_imgs, reinterpret_cast<const WT *>(wk), ARGS); break; \
-		case 1: hipLaunchKernelGGL((K<3, false, true>), grid, block, L.lds, b->stream, b->d_imgs, reinterpret_cast<const WT *>(wk), ARGS); break;  \
-		case 2: hipLaunchKernelGGL((K<3, true, false>), grid, block, L.lds, b->stream, b->d_imgs, reinterpret_cast<const WT *>(wk), ARGS); break;  \
-		case 3: hipLaunchKernelGGL((K<3, true, true>), grid, block, L.lds, b->stream, b->d_imgs, reinterpret_cast<const WT *>(wk), ARGS); break;   \
-		case 4: hipLaunchKernelGGL((K<4, false, false>), grid, block, L.lds, b->stream, b->d_imgs, reinterpret_cast<const WT *>(wk), ARGS); break; \
-		case 5: hipLaunchKernelGGL((K<4, false, true>), grid, block, L.lds, b->stream, b->d_imgs, reinterpret_cast<const WT *>(wk), ARGS); break;  \
-		case 6: hipLaunchKernelGGL((K<4, true, false>), grid, block, L.lds, b->stream, b->d_imgs, reinterpret_cast<const WT *>(wk), ARGS); break;  \
-		default: hipLaunchKernelGGL((K<4, true, true>), grid, block, L.lds, b->stream, b->d_imgs, reinterpret_cast<const WT *>(wk), ARGS); break;  \
-		}                                                                                                                            \
-	} while (0)
-#define MIJ_LAUNCH_WB(K, ARGS)                                                                                                     \
-	do {                                                                                                                            \
-		const int v_ = (L.wide ? 2 : 0) | (L.b8 ? 1 : 0);                                                                            \
-		switch (v_) {                                                                                                                \
-		case 0: hipLaunchKernelGGL((K<false, false>), grid, block, 0, b->stream, b->d_imgs, reinterpret_cast<const WorkIdct *>(wk), ARGS); break; \
-		case 1: hipLaunchKernelGGL((K<false, true>), grid, block, 0, b->stream, b->d_imgs, reinterpret_cast<const WorkIdct *>(wk), ARGS); break;  \
-		case 2: hipLaunchKernelGGL((K<true, false>), grid, block, 0, b->stream, b->d_imgs, reinterpret_cast<const WorkIdct *>(wk), ARGS); break;  \
-		default: hipLaunchKernelGGL((K<true, true>), grid, block, 0, b->stream, b->d_imgs, reinterpret_cast<const WorkIdct *>(wk), ARGS); break;  \
-		}                                                                                                                            \
-	} while (0)
-#define MIJ_COEF_OUT b->d_coef, b->d_out
-#define MIJ_COEF_OUT_PLANES b->d_coef, b->d_planes
 
 extern "C" int mij_batch_launch(mij_batch *b)
 {
@@ -1595,110 +1470,31 @@ extern "C" int mij_batch_launch(mij_batch *b)
 		return set_err(MIJ_E_STATE, "mij_batch_launch before mij_batch_upload");
 	HIP_TRY(hipSetDevice(b->ctx->device));
 	for (const auto &L : b->launches) { /* in family order: pass 2 of the two-pass family runs behind every pass-1 launch */
-		const dim3 grid((unsigned)L.count), block((L.kind >= MK_420 && L.kind != MK_444 && L.kind != MK_GREY && L.kind != MK_1X1C) ? (unsigned)band_threads(L.kind) : 256u);
+		const Family &f = families[L.kind];
 		const Work4 *wk = b->d_work + L.first;
-		switch (L.kind) {
-		case MK_420:
-			MIJ_LAUNCH_NWB(k_fused420, WorkBand, MIJ_COEF_OUT);
-			break;
-		case MK_420W:
-			MIJ_LAUNCH_NWB(k_fused420w, WorkBand, MIJ_COEF_OUT);
-			break;
-		case MK_420X:
-			MIJ_LAUNCH_NWB(k_fused420x, WorkBand, MIJ_COEF_OUT);
-			break;
-		case MK_420S:
-			MIJ_LAUNCH_NWB(k_fused420s, WorkBand, MIJ_COEF_OUT);
-			break;
-		case MK_420T:
-			MIJ_LAUNCH_NWB(k_fused420t, WorkBand, MIJ_COEF_OUT);
-			break;
-		case MK_422:
-			MIJ_LAUNCH_NWB(k_fused422, WorkBand, MIJ_COEF_OUT);
-			break;
-		case MK_422W:
-			MIJ_LAUNCH_NWB(k_fused422w, WorkBand, MIJ_COEF_OUT);
-			break;
-		case MK_422X:
-			MIJ_LAUNCH_NWB(k_fused422x, WorkBand, MIJ_COEF_OUT);
-			break;
-		case MK_422S:
-			MIJ_LAUNCH_NWB(k_fused422s, WorkBand, MIJ_COEF_OUT);
-			break;
-		case MK_422T:
-			MIJ_LAUNCH_NWB(k_fused422t, WorkBand, MIJ_COEF_OUT);
-			break;
-		case MK_440:
-			MIJ_LAUNCH_NWB(k_fused440, WorkBand, MIJ_COEF_OUT);
-			break;
-		case MK_440W:
-			MIJ_LAUNCH_NWB(k_fused440w, WorkBand, MIJ_COEF_OUT);
-			break;
-		case MK_420C:
-			MIJ_LAUNCH_NWB(k_fused420c, WorkBand, MIJ_COEF_OUT);
-			break;
-		case MK_440C:
-			MIJ_LAUNCH_NWB(k_fused440c, WorkBand, MIJ_COEF_OUT);
-			break;
-		case MK_444:
-			MIJ_LAUNCH_NWB(k_fused444, WorkIdct, MIJ_COEF_OUT);
-			break;
-		case MK_1X1C:
-			MIJ_LAUNCH_NWB(k_fused1x1c, WorkIdct, MIJ_COEF_OUT);
-			break;
-		case MK_GREY:
-			MIJ_LAUNCH_WB(k_fused_grey, MIJ_COEF_OUT);
-			break;
-		case MK_PLANES:
-			MIJ_LAUNCH_WB(k_idct_planes, MIJ_COEF_OUT_PLANES);
-			break;
-		case MK_RESAMPLE:
-			hipLaunchKernelGGL(k_resample_color, grid, block, 0, b->stream, b->d_imgs, reinterpret_cast<const WorkIdct *>(wk), b->d_planes, b->d_out);
-			break;
-		default: { /* MK_RS_FAST + RS_*: L.nout, L.wide = YCbCr colour */
-#define MIJ_RS(KIND)                                                                                                                             \
-	case KIND:                                                                                                                                    \
-		if (L.wide) {                                                                                                                              \
-			if (L.nout == 4) hipLaunchKernelGGL((k_resample_fast<KIND, true, 4>), grid, block, 0, b->stream, b->d_imgs, reinterpret_cast<const WorkIdct *>(wk), b->d_planes, b->d_out); \
-			else hipLaunchKernelGGL((k_resample_fast<KIND, true, 3>), grid, block, 0, b->stream, b->d_imgs, reinterpret_cast<const WorkIdct *>(wk), b->d_planes, b->d_out);            \
-		} else {                                                                                                                                   \
-			if (L.nout == 4) hipLaunchKernelGGL((k_resample_fast<KIND, false, 4>), grid, block, 0, b->stream, b->d_imgs, reinterpret_cast<const WorkIdct *>(wk), b->d_planes, b->d_out); \
-			else hipLaunchKernelGGL((k_resample_fast<KIND, false, 3>), grid, block, 0, b->stream, b->d_imgs, reinterpret_cast<const WorkIdct *>(wk), b->d_planes, b->d_out);            \
-		}                                                                                                                                          \
-		break
-			switch (L.kind - MK_RS_FAST) {
-				MIJ_RS(RS_ROW1);
-				MIJ_RS(RS_V2);
-				MIJ_RS(RS_H2);
-				MIJ_RS(RS_HV2);
-				MIJ_RS(RS_GEN2);
-				MIJ_RS(RS_GEN4);
-			default:
-				return set_err(MIJ_E_STATE, "unknown launch kind %d", L.kind);
-			}
-#undef MIJ_RS
-			break;
-		}
-		}
+		const uint8_t *in = f.io == PLANES_OUT ? b->d_planes : b->d_coef;
+		uint8_t *out = f.io == COEF_PLANES ? b->d_planes : b->d_out;
+		void *args[] = {&b->d_imgs, &wk, &in, &out};
+		(void)hipLaunchKernel(f.k[L.var], dim3((unsigned)L.count), dim3(f.threads), args, L.lds, b->stream);
 		HIP_TRY(hipGetLastError());
 	}
 	/* float output, behind every decode family (both front ends end here) */
-	if (b->f32_items) {
-		hipLaunchKernelGGL(k_out_f32, dim3((unsigned)b->f32_items), dim3(256), 0, b->stream, reinterpret_cast<const DevF32 *>(b->d_f32plan),
-								 reinterpret_cast<const WorkF32 *>(b->d_f32plan + b->f32_work_at), reinterpret_cast<const float *>(b->d_f32plan + b->f32_lut_at),
-								 b->d_out, b->d_f32);
+	const PlanBuf &fp = b->f32plan, &tp = b->tenplan, &rp = b->rszplan;
+	if (fp.items) {
+		hipLaunchKernelGGL(k_out_f32, dim3((unsigned)fp.items), dim3(256), 0, b->stream, reinterpret_cast<const DevF32 *>(fp.d),
+								 reinterpret_cast<const WorkF32 *>(fp.d + fp.work_at), reinterpret_cast<const float *>(fp.d + fp.lut_at), b->d_out, b->d_f32);
 		HIP_TRY(hipGetLastError());
 	}
 	/* tensor output into the callers' memory, behind the float pass */
-	if (b->ten_items) {
-		hipLaunchKernelGGL(k_out_tensor, dim3((unsigned)b->ten_items), dim3(256), 0, b->stream, reinterpret_cast<const DevTensor *>(b->d_tenplan),
-								 reinterpret_cast<const WorkTensor *>(b->d_tenplan + b->ten_work_at), b->d_tenplan + b->ten_lut_at, b->d_out);
+	if (tp.items) {
+		hipLaunchKernelGGL(k_out_tensor, dim3((unsigned)tp.items), dim3(256), 0, b->stream, reinterpret_cast<const DevTensor *>(tp.d),
+								 reinterpret_cast<const WorkTensor *>(tp.d + tp.work_at), tp.d + tp.lut_at, b->d_out);
 		HIP_TRY(hipGetLastError());
 	}
 	/* resized tensor output, behind the plain one */
-	if (b->rsz_items) {
-		hipLaunchKernelGGL(k_out_resize, dim3((unsigned)b->rsz_items), dim3(256), 0, b->stream, reinterpret_cast<const DevResize *>(b->d_rszplan),
-								 reinterpret_cast<const WorkResize *>(b->d_rszplan + b->rsz_work_at), b->d_rszplan + b->rsz_lut_at, b->d_rszplan, b->d_out);
+	if (rp.items) {
+		hipLaunchKernelGGL(k_out_resize, dim3((unsigned)rp.items), dim3(256), 0, b->stream, reinterpret_cast<const DevResize *>(rp.d),
+								 reinterpret_cast<const WorkResize *>(rp.d + rp.work_at), rp.d + rp.lut_at, rp.d, b->d_out);
 		HIP_TRY(hipGetLastError());
 	}
 	b->launched = true;
@@ -1805,8 +1601,7 @@ extern "C" int mij_batch_out_f32_reserve(mij_batch *b, size_t bytes)
 	hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), cap);
 	if (e == hipErrorOutOfMemory && b->d_f32) {
 		(void)hipGetLastError();
-		(void)hipFree(b->d_f32);
-		b->d_f32 = nullptr;
+		free_dev(b->d_f32);
 		b->f32_cap = 0;
 		e = hipMalloc(reinterpret_cast<void **>(&p), cap);
 	}
@@ -1814,8 +1609,7 @@ extern "C" int mij_batch_out_f32_reserve(mij_batch *b, size_t bytes)
 		(void)hipGetLastError();
 		return set_err(e == hipErrorOutOfMemory ? MIJ_E_NOMEM : MIJ_E_HIP, "mij_batch_out_f32_reserve: %s", hipGetErrorString(e));
 	}
-	if (b->d_f32)
-		(void)hipFree(b->d_f32);
+	free_dev(b->d_f32);
 	b->d_f32 = p;
 	b->f32_cap = cap;
 	return MIJ_OK;
