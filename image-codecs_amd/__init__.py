@@ -36,6 +36,7 @@ from .binding import (  # noqa: F401
     MIJ_LAYOUT_CHW,
     Context,
     Encoder,
+    InTensor,
     PinnedBuffer,
     host_transform,
     emit_jpeg,
@@ -76,12 +77,16 @@ from .binding import (  # noqa: F401
 from .synth import synth_rgb, synth_jpeg, synth_rgb_edges  # noqa: F401
 
 _TENSOR_OUT = ("TensorDecoder", "tensor_tables")
+_TENSOR_ENCODE = ("TensorEncoder",)
 
 
 def __getattr__(name):
-    """TensorDecoder and tensor_tables live in tensor_out, which imports torch: loaded on first use, so that importing the package
-    does not import torch."""
+    """TensorDecoder and tensor_tables live in tensor_out, TensorEncoder in tensor_encode; both import torch and are loaded on first
+    use, so that importing the package does not import torch."""
     if name in _TENSOR_OUT:
         from . import tensor_out
         return getattr(tensor_out, name)
+    if name in _TENSOR_ENCODE:
+        from . import tensor_encode
+        return getattr(tensor_encode, name)
     raise AttributeError("module 'image_codecs_amd' has no attribute %r" % name)

@@ -1158,12 +1158,22 @@ def mij_write_jpg_batch(images, quality=90, threads=16):
     return res
 
 
-class Encoder:
-    """mij_encoder: batch colour + subsample + fDCT + quantiser on the GPU."""
+class InTensor(C.Structure):
+    """mij_in_tensor (include/mij.h)."""
+    _fields_ = [("src", C.c_void_p), ("layout", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("comp", C.c_int32),
+                ("row_pitch", C.c_int64), ("plane_pitch", C.c_int64)]
 
-    def __init__(self, ctx, max_images, pixel_bytes, du_bytes):
+
+class Encoder:
+    """mij_encoder: batch colour + subsample + fDCT + quantiser on the GPU; with an emission arena (stream_reserve) also the Huffman
+    stage, so that finished streams come back."""
+
+    def __init__(self, ctx, max_images, pixel_bytes, du_bytes, stage_bytes=None):
+        """stage_bytes: pinned staging for host pictures (add); None = pixel_bytes (mij_enc_create), 0 for an encoder fed only by
+        add_device / add_units (mij_enc_create_ex)."""
         L = lib()
         L.mij_enc_create.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]
+        L.mij_enc_create_ex.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]
         L.mij_enc_destroy.argtypes = [C.c_void_p]
         L.mij_enc_add.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         L.mij_enc_add_clone.argtypes = [C.c_void_p, C.c_int]
@@ -1173,7 +1183,14 @@ class Encoder:
         L.mij_enc_plan.argtypes = [C.c_void_p, C.c_int, C.POINTER(WritePlan)]
         L.mij_enc_timer_elapsed_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         self._h = C.c_void_p()
-        _check(L.mij_enc_create(ctx._h, int(max_images), C.c_size_t(pixel_bytes), C.c_size_t(du_bytes), C.byref(self._h)), "mij_enc_create")
+        if stage_bytes is None:
+            _check(L.mij_enc_create(ctx._h, int(max_images), C.c_size_t(pixel_bytes), C.c_size_t(du_bytes), C.byref(self._h)), "mij_enc_create")
+        else:
+            _check(L.mij_enc_create_ex(ctx._h, int(max_images), C.c_size_t(stage_bytes), C.c_size_t(pixel_bytes), C.c_size_t(du_bytes),
+                                       C.byref(self._h)), "mij_enc_create_ex")
+
+    def reset(self):
+        _check(lib().mij_enc_reset(self._h), "mij_enc_reset")
 
     def add(self, pixels, quality=90, flip=False):
         a = np.ascontiguousarray(pixels, dtype=np.uint8)
@@ -1210,6 +1227,44 @@ class Encoder:
         du = np.empty(p.du_elems(), dtype=np.int16)
         _check(lib().mij_enc_fetch(self._h, int(slot), du.ctypes.data_as(C.c_void_p), C.c_size_t(du.size)), "mij_enc_fetch")
         return du.reshape(-1, 64)
+
+    def add_device(self, t, quality=90, flip=False):
+        """mij_enc_add_device: a slot whose uint8 pixels lie in device memory, described by an InTensor."""
+        L = lib()
+        L.mij_enc_add_device.argtypes = [C.c_void_p, C.POINTER(InTensor), C.c_int, C.c_int]
+        return _check(L.mij_enc_add_device(self._h, C.byref(t), int(quality), int(bool(flip))), "mij_enc_add_device")
+
+    def add_units(self, width, height, comp, quality, du):
+        """mij_enc_add_units: a slot whose quantised data units (int16 [n_du, 64], zigzag order) are given."""
+        L = lib()
+        L.mij_enc_add_units.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        d = np.ascontiguousarray(du, dtype=np.int16)
+        plan = WritePlan()
+        L.mjw_plan_init.argtypes = [C.POINTER(WritePlan), C.c_int, C.c_int, C.c_int, C.c_int]
+        if L.mjw_plan_init(C.byref(plan), int(width), int(height), int(comp), int(quality)) and d.size != plan.du_elems():
+            raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, plan.du_elems()))
+        return _check(L.mij_enc_add_units(self._h, int(width), int(height), int(comp), int(quality), d.ctypes.data_as(C.c_void_p)), "mij_enc_add_units")
+
+    def stream_reserve(self, nbytes):
+        """mij_enc_stream_reserve: the GPU emission arena (0 releases it); before upload."""
+        L = lib()
+        L.mij_enc_stream_reserve.argtypes = [C.c_void_p, C.c_size_t]
+        _check(L.mij_enc_stream_reserve(self._h, C.c_size_t(nbytes)), "mij_enc_stream_reserve")
+
+    def fetch_streams(self):
+        """mij_enc_fetch_streams: waits, brings the streams back; -> the number of slots that fit."""
+        L = lib()
+        L.mij_enc_fetch_streams.argtypes = [C.c_void_p]
+        return _check(L.mij_enc_fetch_streams(self._h), "mij_enc_fetch_streams")
+
+    def stream(self, slot):
+        """mij_enc_stream -> (bytes, length), or (None, the length it needs) for a slot that did not fit."""
+        L = lib()
+        L.mij_enc_stream.restype = C.c_void_p
+        L.mij_enc_stream.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]
+        n = C.c_size_t()
+        p = L.mij_enc_stream(self._h, int(slot), C.byref(n))
+        return (C.string_at(p, n.value) if p else None), n.value
 
     def timer_begin(self):
         _check(lib().mij_enc_timer_begin(self._h), "mij_enc_timer_begin")

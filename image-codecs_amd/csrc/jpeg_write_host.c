@@ -437,11 +437,59 @@ void mjw_transform_host(const mjw_plan *p, const void *data, int flip, int16_t *
 		}
 }
 
+/* The headers in front of the entropy-coded segment (codec/jpeg_write.c:245-268): SOI, APP0, DQT, SOF0, DHT, SOS. */
+size_t mjw_header(const mjw_plan *p, unsigned char *out)
+{
+	static const unsigned char soi_app0_dqt[] = {0xFF, 0xD8, 0xFF, 0xE0, 0, 0x10, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0, 0xFF, 0xDB, 0, 0x84, 0};
+	static const unsigned char sos[] = {0xFF, 0xDA, 0, 0xC, 3, 1, 0, 2, 0x11, 3, 0x11, 0, 0x3F, 0};
+	unsigned char sof_dht[24] = {0xFF, 0xC0, 0, 0x11, 8, 0, 0, 0, 0, 3, 1, 0, 0, 2, 0x11, 1, 3, 0x11, 1, 0xFF, 0xC4, 0x01, 0xA2, 0};
+	unsigned char *o = out;
+	sof_dht[5] = (unsigned char)(p->height >> 8);
+	sof_dht[6] = (unsigned char)(p->height & 0xff);
+	sof_dht[7] = (unsigned char)(p->width >> 8);
+	sof_dht[8] = (unsigned char)(p->width & 0xff);
+	sof_dht[11] = (unsigned char)(p->subsample ? 0x22 : 0x11);
+#define PUT(src, n) (memcpy(o, (src), (n)), o += (n))
+	PUT(soi_app0_dqt, sizeof(soi_app0_dqt));
+	PUT(p->ytab, 64);
+	*o++ = 1;
+	PUT(p->ctab, 64);
+	PUT(sof_dht, sizeof(sof_dht));
+	PUT(k_dc_lum_bits + 1, 16);
+	PUT(k_dc_vals, 12);
+	*o++ = 0x10;
+	PUT(k_ac_lum_bits + 1, 16);
+	PUT(k_ac_lum_vals, 162);
+	*o++ = 1;
+	PUT(k_dc_chr_bits + 1, 16);
+	PUT(k_dc_vals, 12);
+	*o++ = 0x11;
+	PUT(k_ac_chr_bits + 1, 16);
+	PUT(k_ac_chr_vals, 162);
+	PUT(sos, sizeof(sos));
+#undef PUT
+	return (size_t)(o - out);
+}
+
+void mjw_huff_tables(uint16_t code[4][256], uint8_t len[4][256])
+{
+	enc_table t[4];
+	int k, i;
+	make_enc_table(&t[0], k_dc_lum_bits, k_dc_vals);
+	make_enc_table(&t[1], k_dc_chr_bits, k_dc_vals);
+	make_enc_table(&t[2], k_ac_lum_bits, k_ac_lum_vals);
+	make_enc_table(&t[3], k_ac_chr_bits, k_ac_chr_vals);
+	for (k = 0; k < 4; ++k)
+		for (i = 0; i < 256; ++i) {
+			code[k][i] = t[k].code[i];
+			len[k][i] = (uint8_t)t[k].len[i];
+		}
+}
+
 int mjw_emit(const mjw_plan *p, const int16_t *du, mjw_write_func *func, void *context)
 {
 	enc_table ydc, yac, cdc, cac;
 	jw_sink *s;
-	const int width = p->width, height = p->height;
 	if (!func || !du)
 		return 0;
 	s = (jw_sink *)calloc(1, sizeof(*s));
@@ -455,31 +503,8 @@ int mjw_emit(const mjw_plan *p, const int16_t *du, mjw_write_func *func, void *c
 	make_enc_table(&cac, k_ac_chr_bits, k_ac_chr_vals);
 	/* headers (codec/jpeg_write.c:245-268) */
 	{
-		static const unsigned char soi_app0_dqt[] = {0xFF, 0xD8, 0xFF, 0xE0, 0, 0x10, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0, 0xFF, 0xDB, 0, 0x84, 0};
-		static const unsigned char sos[] = {0xFF, 0xDA, 0, 0xC, 3, 1, 0, 2, 0x11, 3, 0x11, 0, 0x3F, 0};
-		unsigned char sof_dht[24] = {0xFF, 0xC0, 0, 0x11, 8, 0, 0, 0, 0, 3, 1, 0, 0, 2, 0x11, 1, 3, 0x11, 1, 0xFF, 0xC4, 0x01, 0xA2, 0};
-		sof_dht[5] = (unsigned char)(height >> 8);
-		sof_dht[6] = (unsigned char)(height & 0xff);
-		sof_dht[7] = (unsigned char)(width >> 8);
-		sof_dht[8] = (unsigned char)(width & 0xff);
-		sof_dht[11] = (unsigned char)(p->subsample ? 0x22 : 0x11);
-		sink_bytes(s, soi_app0_dqt, (int)sizeof(soi_app0_dqt));
-		sink_bytes(s, p->ytab, 64);
-		sink_byte(s, 1);
-		sink_bytes(s, p->ctab, 64);
-		sink_bytes(s, sof_dht, (int)sizeof(sof_dht));
-		sink_bytes(s, k_dc_lum_bits + 1, 16);
-		sink_bytes(s, k_dc_vals, 12);
-		sink_byte(s, 0x10);
-		sink_bytes(s, k_ac_lum_bits + 1, 16);
-		sink_bytes(s, k_ac_lum_vals, 162);
-		sink_byte(s, 1);
-		sink_bytes(s, k_dc_chr_bits + 1, 16);
-		sink_bytes(s, k_dc_vals, 12);
-		sink_byte(s, 0x11);
-		sink_bytes(s, k_ac_chr_bits + 1, 16);
-		sink_bytes(s, k_ac_chr_vals, 162);
-		sink_bytes(s, sos, (int)sizeof(sos));
+		unsigned char hdr[MJW_HEADER_BYTES];
+		sink_bytes(s, hdr, (int)mjw_header(p, hdr));
 	}
 	{
 		int dcy = 0, dcu = 0, dcv = 0;

@@ -1710,6 +1710,30 @@ static const mij_batch::RszCoef *rsz_coef(mij_batch *b, int in, int out, int fil
 	return &b->rsz_coef.emplace(key, std::move(c)).first->second;
 }
 
+/* MIJ_OK when the `extent` bytes from p are device memory of `device`, inside the one allocation hipMemGetAddressRange reports for p
+ * (a range that cannot be determined is refused too); else MIJ_E_ARG naming p as `what` */
+static int device_extent(int device, const void *p, uint64_t extent, const char *what)
+{
+	HIP_TRY(hipSetDevice(device));
+	hipPointerAttribute_t pa;
+	memset(&pa, 0, sizeof(pa));
+	hipError_t e = hipPointerGetAttributes(&pa, p);
+	if (e != hipSuccess || pa.type != hipMemoryTypeDevice || pa.isManaged || pa.device != device) {
+		(void)hipGetLastError();
+		return set_err(MIJ_E_ARG, "%s %p is not device memory of device %d", what, p, device);
+	}
+	hipDeviceptr_t base = nullptr;
+	size_t size = 0;
+	const uintptr_t a = (uintptr_t)p;
+	e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p);
+	if (e != hipSuccess || !base || a < (uintptr_t)base || a - (uintptr_t)base > size || extent > size - (a - (uintptr_t)base)) {
+		(void)hipGetLastError();
+		return set_err(MIJ_E_ARG, "the %llu bytes from %s %p are not inside one allocation (%p, %zu bytes)", (unsigned long long)extent, what, p, (void *)base,
+							size);
+	}
+	return MIJ_OK;
+}
+
 static int set_out_tensor(mij_batch *b, int slot, const mij_out_tensor *t, const mij_out_resize *rz, const void *table)
 {
 	if (!b || slot < 0 || slot >= (int)b->slots.size() || !t)
@@ -1755,21 +1779,9 @@ static int set_out_tensor(mij_batch *b, int slot, const mij_out_tensor *t, const
 		return set_err(MIJ_E_ARG, "dst %p is not aligned to its %u-byte elements", t->dst, es);
 	const uint64_t last = (uint64_t)((h - 1) * rp + (chw ? (C - 1) * pp + w - 1 : w * C - 1)); /* element offset of the last element */
 	const uint64_t extent = (last + 1) * es;
-	HIP_TRY(hipSetDevice(b->ctx->device));
-	hipPointerAttribute_t pa;
-	memset(&pa, 0, sizeof(pa));
-	hipError_t e = hipPointerGetAttributes(&pa, t->dst);
-	if (e != hipSuccess || pa.type != hipMemoryTypeDevice || pa.isManaged || pa.device != b->ctx->device) {
-		(void)hipGetLastError();
-		return set_err(MIJ_E_ARG, "dst %p is not device memory of device %d", t->dst, b->ctx->device);
-	}
-	hipDeviceptr_t base = nullptr;
-	size_t size = 0;
-	e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)t->dst);
-	if (e != hipSuccess || !base || dst < (uintptr_t)base || dst - (uintptr_t)base > size || extent > size - (dst - (uintptr_t)base)) {
-		(void)hipGetLastError();
-		return set_err(MIJ_E_ARG, "the %llu bytes from dst %p are not inside one allocation (%p, %zu bytes)", (unsigned long long)extent, t->dst, (void *)base, size);
-	}
+	const int rc = device_extent(b->ctx->device, t->dst, extent, "dst");
+	if (rc != MIJ_OK)
+		return rc;
 	if (s.ten < 0) {
 		b->ten_req.emplace_back();
 		b->ten_req.back().slot = slot;
@@ -2613,9 +2625,14 @@ extern "C" int mij_batch_entropy_rounds(const mij_batch *b) { return b && b->es 
  *
  * GPU half of the JPEG writer: colour transform + 2x2 chroma mean + float AAN fDCT + quantiser
  * (codec/jpeg_write.c:24-118, :283-352) for a batch of images; the host then Huffman-codes the data
- * units (mjw_emit, mij_host.h).  Same arena / stream / work-list design as the decode batch.
+ * units (mjw_emit, mij_host.h), or, with an emission arena, the GPU does (mij_emit_kernels.h).  Same arena / stream /
+ * work-list design as the decode batch.
  */
 #include "mij_host.h"
+#include "mij_emit_kernels.h"
+static_assert(MIJ_EMIT_HDR == MJW_HEADER_BYTES, "header size");
+
+enum { ENC_HOST = 0, ENC_DEVICE = 1, ENC_UNITS = 2 }; /* where a slot's input comes from: pinned staging, a device tensor, given units */
 
 struct EncSlot {
 	mjw_plan plan;
@@ -2623,6 +2640,9 @@ struct EncSlot {
 	size_t stage_off, pix_bytes, du_bytes;
 	int pad_w; /* pixels per staged row: the width rounded up to whole MCU columns (enc_padded_width); staged rows are packed RGB */
 	int clone_of, flip;
+	int kind;                   /* ENC_*; a clone copies its root's pixels whatever the root's kind */
+	mij_in_tensor in;           /* ENC_DEVICE */
+	std::vector<int16_t> units; /* ENC_UNITS */
 };
 
 struct mij_encoder {
@@ -2643,9 +2663,76 @@ struct mij_encoder {
 	size_t n_work[6], first_work[6]; /* [sub*2 + kind]: kind 0 luma units, 1 chroma units; [4]: fused 4:2:0 strips; [5]: fused 4:4:4 strips */
 	std::vector<EncSlot> slots;
 	bool uploaded, launched, force_generic;
+	/* device-pixel slots: the gather kernel's slots and work (rows of MIJ_GATHER_ROWS) */
+	EncGather *h_gath, *d_gath;
+	size_t gath_cap;
+	WorkIdct *h_gwork, *d_gwork;
+	size_t gwork_cap, n_gwork;
+	/* GPU emission (mij_enc_stream_reserve): the stream arena and its pinned mirror, the code tables, per-slot and per-tile lists */
+	uint8_t *d_arena, *h_arena;
+	size_t arena_cap;
+	EmitTables *d_tabs;
+	EmitSlot *h_eslot, *d_eslot;
+	size_t eslot_cap;
+	EmitTile *h_etile, *d_etile;
+	size_t etile_cap, n_etile;
+	uint8_t *h_hdr, *d_hdr;
+	size_t hdr_cap;
+	EmitResult *h_res, *d_res;
+	size_t res_cap;
+	uint32_t *d_tbits, *d_tff, *d_tfrag;
+	uint64_t *d_tboff, *d_tout, *d_sent;
+	size_t tmeta_cap, sent_cap;
+	bool emit_queued, streams_fetched;
 };
 
+template <typename T>
+static int grow_dev(T *&d, size_t &cap, size_t need)
+{
+	if (need <= cap)
+		return MIJ_OK;
+	const size_t ncap = need + need / 2 + 64;
+	free_dev(d);
+	cap = 0;
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof(T) * ncap));
+	cap = ncap;
+	return MIJ_OK;
+}
+
+static void enc_free_emit(mij_encoder *e)
+{
+	free_dev(e->d_arena);
+	free_host(e->h_arena);
+	free_dev(e->d_tabs);
+	e->arena_cap = 0;
+	free_host(e->h_eslot);
+	free_dev(e->d_eslot);
+	e->eslot_cap = 0;
+	free_host(e->h_etile);
+	free_dev(e->d_etile);
+	e->etile_cap = e->n_etile = 0;
+	free_host(e->h_hdr);
+	free_dev(e->d_hdr);
+	e->hdr_cap = 0;
+	free_host(e->h_res);
+	free_dev(e->d_res);
+	e->res_cap = 0;
+	free_dev(e->d_tbits);
+	free_dev(e->d_tff);
+	free_dev(e->d_tfrag);
+	free_dev(e->d_tboff);
+	free_dev(e->d_tout);
+	free_dev(e->d_sent);
+	e->tmeta_cap = e->sent_cap = 0;
+	e->emit_queued = e->streams_fetched = false;
+}
+
 extern "C" int mij_enc_create(mij_ctx *ctx, int max_images, size_t pixel_bytes, size_t du_bytes, mij_encoder **out)
+{
+	return mij_enc_create_ex(ctx, max_images, pixel_bytes, pixel_bytes, du_bytes, out);
+}
+
+extern "C" int mij_enc_create_ex(mij_ctx *ctx, int max_images, size_t stage_bytes, size_t pixel_bytes, size_t du_bytes, mij_encoder **out)
 {
 	if (!ctx || !out || max_images <= 0)
 		return set_err(MIJ_E_ARG, "mij_enc_create: bad argument");
@@ -2663,11 +2750,23 @@ extern "C" int mij_enc_create(mij_ctx *ctx, int max_images, size_t pixel_bytes, 
 	e->h_imgs = e->d_imgs = nullptr;
 	e->h_work = e->d_work = nullptr;
 	e->work_cap = 0;
-	e->stage_cap = pixel_bytes;
+	e->stage_cap = stage_bytes;
 	e->pix_cap = pixel_bytes;
 	e->du_cap = du_bytes;
 	e->stage_used = e->pix_used = e->du_used = 0;
 	e->uploaded = e->launched = false;
+	e->h_gath = e->d_gath = nullptr;
+	e->h_gwork = e->d_gwork = nullptr;
+	e->gath_cap = e->gwork_cap = e->n_gwork = 0;
+	e->d_arena = e->h_arena = nullptr;
+	e->d_tabs = nullptr;
+	e->h_eslot = e->d_eslot = nullptr;
+	e->h_etile = e->d_etile = nullptr;
+	e->h_hdr = e->d_hdr = nullptr;
+	e->h_res = e->d_res = nullptr;
+	e->d_tbits = e->d_tff = e->d_tfrag = nullptr;
+	e->d_tboff = e->d_tout = e->d_sent = nullptr;
+	enc_free_emit(e);
 	e->force_generic = getenv("MIJ_ENC_GENERIC") != nullptr;
 	e->stream = nullptr;
 	e->ev_begin = e->ev_end = nullptr;
@@ -2677,7 +2776,7 @@ extern "C" int mij_enc_create(mij_ctx *ctx, int max_images, size_t pixel_bytes, 
 	if (r == hipSuccess)
 		r = hipEventCreate(&e->ev_end);
 	if (r == hipSuccess)
-		r = hipHostMalloc(reinterpret_cast<void **>(&e->stage), pixel_bytes ? pixel_bytes : 16, hipHostMallocDefault);
+		r = hipHostMalloc(reinterpret_cast<void **>(&e->stage), stage_bytes ? stage_bytes : 16, hipHostMallocDefault);
 	if (r == hipSuccess)
 		r = hipMalloc(reinterpret_cast<void **>(&e->d_pix), pixel_bytes ? pixel_bytes : 16);
 	if (r == hipSuccess)
@@ -2719,6 +2818,11 @@ extern "C" void mij_enc_destroy(mij_encoder *e)
 		(void)hipHostFree(e->h_work);
 	if (e->d_work)
 		(void)hipFree(e->d_work);
+	free_host(e->h_gath);
+	free_dev(e->d_gath);
+	free_host(e->h_gwork);
+	free_dev(e->d_gwork);
+	enc_free_emit(e);
 	if (e->ev_begin)
 		(void)hipEventDestroy(e->ev_begin);
 	if (e->ev_end)
@@ -2737,6 +2841,7 @@ extern "C" int mij_enc_reset(mij_encoder *e)
 	e->slots.clear();
 	e->stage_used = e->pix_used = e->du_used = 0;
 	e->uploaded = e->launched = false;
+	e->emit_queued = e->streams_fetched = false;
 	return MIJ_OK;
 }
 
@@ -2782,7 +2887,7 @@ extern "C" size_t mij_enc_pixel_bytes(int width, int height, int comp, int quali
 	return align_up((size_t)enc_padded_width(width, plan.subsample) * height * 3, 256);
 }
 
-static int enc_add_common(mij_encoder *e, const mjw_plan &plan, const void *pixels, int flip, int clone_of)
+static int enc_add_common(mij_encoder *e, const mjw_plan &plan, const void *pixels, int flip, int clone_of, int kind = ENC_HOST)
 {
 	if ((int)e->slots.size() >= e->max_images)
 		return set_err(MIJ_E_NOMEM, "encoder batch is full (%d images)", e->max_images);
@@ -2790,14 +2895,18 @@ static int enc_add_common(mij_encoder *e, const mjw_plan &plan, const void *pixe
 	s.plan = plan;
 	s.flip = flip;
 	s.clone_of = clone_of;
+	s.kind = kind;
+	memset(&s.in, 0, sizeof(s.in));
 	s.pad_w = enc_padded_width(plan.width, plan.subsample);
-	s.pix_bytes = align_up((size_t)s.pad_w * plan.height * 3, 256); /* staged as packed RGB whatever plan.comp is (enc_stage_rows) */
+	s.pix_bytes = kind == ENC_UNITS ? 0 : align_up((size_t)s.pad_w * plan.height * 3, 256); /* staged as packed RGB whatever plan.comp is (enc_stage_rows) */
 	s.du_bytes = align_up(mjw_plan_du_count(&plan) * 128, 256);
 	if (e->pix_used + s.pix_bytes > e->pix_cap)
 		return set_err(MIJ_E_NOMEM, "pixel arena exhausted");
 	if (e->du_used + s.du_bytes > e->du_cap)
 		return set_err(MIJ_E_NOMEM, "data-unit arena exhausted");
-	if (clone_of < 0) {
+	if (clone_of < 0 && kind != ENC_HOST) {
+		s.stage_off = 0; /* no pinned staging: the gather kernel or the units' own copy fills the device side */
+	} else if (clone_of < 0) {
 		if (e->stage_used + s.pix_bytes > e->stage_cap)
 			return set_err(MIJ_E_NOMEM, "pixel staging exhausted");
 		s.stage_off = e->stage_used;
@@ -2821,8 +2930,9 @@ static int enc_add_common(mij_encoder *e, const mjw_plan &plan, const void *pixe
 	memcpy(s.dev.fc, plan.fdtbl_c, sizeof(s.dev.fc));
 	e->pix_used += s.pix_bytes;
 	e->du_used += s.du_bytes;
-	e->slots.push_back(s);
+	e->slots.push_back(std::move(s));
 	e->uploaded = e->launched = false;
+	e->emit_queued = e->streams_fetched = false;
 	return (int)e->slots.size() - 1;
 }
 
@@ -2848,7 +2958,7 @@ extern "C" int mij_enc_add_uncopied(mij_encoder *e, int width, int height, int c
 
 extern "C" int mij_enc_stage_pixels(mij_encoder *e, int slot, const void *pixels)
 {
-	if (!e || !pixels || slot < 0 || slot >= (int)e->slots.size() || e->slots[(size_t)slot].clone_of >= 0)
+	if (!e || !pixels || slot < 0 || slot >= (int)e->slots.size() || e->slots[(size_t)slot].clone_of >= 0 || e->slots[(size_t)slot].kind != ENC_HOST)
 		return set_err(MIJ_E_ARG, "bad slot or pixels");
 	const EncSlot &s = e->slots[(size_t)slot];
 	enc_stage_rows(e->stage + s.stage_off, static_cast<const uint8_t *>(pixels), s.plan.width, s.plan.height, s.plan.comp, s.pad_w);
@@ -2857,7 +2967,7 @@ extern "C" int mij_enc_stage_pixels(mij_encoder *e, int slot, const void *pixels
 
 extern "C" void *mij_enc_staging(mij_encoder *e, int slot)
 {
-	if (!e || slot < 0 || slot >= (int)e->slots.size() || e->slots[(size_t)slot].clone_of >= 0)
+	if (!e || slot < 0 || slot >= (int)e->slots.size() || e->slots[(size_t)slot].clone_of >= 0 || e->slots[(size_t)slot].kind != ENC_HOST)
 		return nullptr;
 	return e->stage + e->slots[(size_t)slot].stage_off;
 }
@@ -2905,8 +3015,288 @@ extern "C" int mij_enc_add_clone(mij_encoder *e, int src_slot)
 	if (!e || src_slot < 0 || src_slot >= (int)e->slots.size())
 		return set_err(MIJ_E_ARG, "bad source slot");
 	const int root = e->slots[(size_t)src_slot].clone_of >= 0 ? e->slots[(size_t)src_slot].clone_of : src_slot;
-	const EncSlot src = e->slots[(size_t)root];
-	return enc_add_common(e, src.plan, nullptr, src.flip, root);
+	if (e->slots[(size_t)root].kind == ENC_UNITS)
+		return set_err(MIJ_E_ARG, "slot %d holds given data units, which have no pixels to clone", src_slot);
+	const mjw_plan plan = e->slots[(size_t)root].plan;
+	return enc_add_common(e, plan, nullptr, e->slots[(size_t)root].flip, root);
+}
+
+/* The gather kernel of the device-pixel slots (their padded packed-RGB rows from the caller's tensor), queued at upload in place of
+ * the host-to-device copy.  Nothing is queued when there are none. */
+static int enc_gather(mij_encoder *e)
+{
+	size_t ng = 0, nw = 0;
+	for (const EncSlot &s : e->slots)
+		if (s.clone_of < 0 && s.kind == ENC_DEVICE) {
+			++ng;
+			nw += ((size_t)s.plan.height + MIJ_GATHER_ROWS - 1) / MIJ_GATHER_ROWS;
+		}
+	e->n_gwork = nw;
+	if (!ng)
+		return MIJ_OK;
+	if (ng > e->gath_cap || nw > e->gwork_cap)
+		HIP_TRY(hipStreamSynchronize(e->stream)); /* an earlier upload's copies may still read the pinned lists */
+	int rc = grow_pair(e->h_gath, e->d_gath, e->gath_cap, ng);
+	if (rc == MIJ_OK)
+		rc = grow_pair(e->h_gwork, e->d_gwork, e->gwork_cap, nw);
+	if (rc != MIJ_OK)
+		return rc;
+	uint32_t g = 0;
+	size_t w = 0;
+	for (const EncSlot &s : e->slots) {
+		if (s.clone_of >= 0 || s.kind != ENC_DEVICE)
+			continue;
+		EncGather &G = e->h_gath[g];
+		G.src = static_cast<const uint8_t *>(s.in.src);
+		G.row_pitch = s.in.row_pitch;
+		G.plane_pitch = s.in.plane_pitch;
+		G.layout = s.in.layout;
+		G.width = s.plan.width;
+		G.height = s.plan.height;
+		G.comp = s.plan.comp;
+		G.pad_w = s.pad_w;
+		G.pad = 0;
+		G.pix_off = s.dev.pix_off;
+		for (uint32_t y = 0; y < (uint32_t)s.plan.height; y += MIJ_GATHER_ROWS) {
+			const WorkIdct wk = {g, 0u, y, 0u};
+			e->h_gwork[w++] = wk;
+		}
+		++g;
+	}
+	HIP_TRY(hipMemcpyAsync(e->d_gath, e->h_gath, sizeof(EncGather) * ng, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->d_gwork, e->h_gwork, sizeof(WorkIdct) * nw, hipMemcpyHostToDevice, e->stream));
+	hipLaunchKernelGGL(k_enc_gather, dim3((unsigned)nw), dim3(256), 0, e->stream, e->d_gath, e->d_gwork, e->d_pix);
+	HIP_TRY(hipGetLastError());
+	return MIJ_OK;
+}
+
+/* Emission lists at upload: one EmitSlot per slot, its tiles of MIJ_EMIT_TILE units, its headers (a clone shares its root's). */
+static int enc_emit_lists(mij_encoder *e)
+{
+	const size_t n = e->slots.size();
+	size_t nt = 0, nh = 0;
+	for (const EncSlot &s : e->slots) {
+		nt += (mjw_plan_du_count(&s.plan) + MIJ_EMIT_TILE - 1) / MIJ_EMIT_TILE;
+		nh += s.clone_of < 0;
+	}
+	if (nt > UINT32_MAX)
+		return set_err(MIJ_E_ARG, "too many data units to emit in one launch");
+	if (n > e->eslot_cap || nt > e->etile_cap || nh * MIJ_EMIT_HDR > e->hdr_cap || n + 1 > e->res_cap || nt > e->tmeta_cap || n > e->sent_cap)
+		HIP_TRY(hipStreamSynchronize(e->stream)); /* the buffers may still be in use by an earlier launch */
+	int rc = grow_pair(e->h_eslot, e->d_eslot, e->eslot_cap, n);
+	if (rc == MIJ_OK)
+		rc = grow_pair(e->h_etile, e->d_etile, e->etile_cap, nt);
+	if (rc == MIJ_OK)
+		rc = grow_pair(e->h_hdr, e->d_hdr, e->hdr_cap, nh * MIJ_EMIT_HDR);
+	if (rc == MIJ_OK)
+		rc = grow_pair(e->h_res, e->d_res, e->res_cap, n + 1);
+	if (rc == MIJ_OK && nt > e->tmeta_cap) {
+		size_t c = e->tmeta_cap;
+		rc = grow_dev(e->d_tbits, c, nt);
+		c = e->tmeta_cap;
+		if (rc == MIJ_OK)
+			rc = grow_dev(e->d_tff, c, nt);
+		c = e->tmeta_cap;
+		if (rc == MIJ_OK)
+			rc = grow_dev(e->d_tfrag, c, nt);
+		c = e->tmeta_cap;
+		if (rc == MIJ_OK)
+			rc = grow_dev(e->d_tboff, c, nt);
+		c = e->tmeta_cap;
+		if (rc == MIJ_OK)
+			rc = grow_dev(e->d_tout, c, nt);
+		if (rc == MIJ_OK)
+			e->tmeta_cap = c;
+	}
+	if (rc == MIJ_OK)
+		rc = grow_dev(e->d_sent, e->sent_cap, n);
+	if (rc != MIJ_OK)
+		return rc;
+	std::vector<uint32_t> hdr_of(n);
+	uint32_t t = 0, h = 0;
+	for (size_t i = 0; i < n; ++i) {
+		const EncSlot &s = e->slots[i];
+		if (s.clone_of < 0) {
+			mjw_header(&s.plan, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
+			hdr_of[i] = h++;
+		} else {
+			hdr_of[i] = hdr_of[(size_t)s.clone_of];
+		}
+		EmitSlot &es = e->h_eslot[i];
+		es.du_off = s.dev.du_off;
+		es.n_du = (uint32_t)mjw_plan_du_count(&s.plan);
+		es.dpm = (uint32_t)s.plan.du_per_mcu;
+		es.first_tile = t;
+		es.n_tiles = (es.n_du + MIJ_EMIT_TILE - 1) / MIJ_EMIT_TILE;
+		es.hdr = hdr_of[i];
+		es.pad = 0;
+		for (uint32_t u = 0; u < es.n_du; u += MIJ_EMIT_TILE) {
+			const EmitTile tl = {(uint32_t)i, u};
+			e->h_etile[t++] = tl;
+		}
+	}
+	e->n_etile = nt;
+	HIP_TRY(hipMemcpyAsync(e->d_eslot, e->h_eslot, sizeof(EmitSlot) * n, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->d_etile, e->h_etile, sizeof(EmitTile) * nt, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->d_hdr, e->h_hdr, (size_t)nh * MIJ_EMIT_HDR, hipMemcpyHostToDevice, e->stream));
+	return MIJ_OK;
+}
+
+/* The six emission launches behind the transform (mij_emit_kernels.h). */
+static int enc_emit_launch(mij_encoder *e)
+{
+	const uint32_t n = (uint32_t)e->slots.size();
+	const dim3 tiles((unsigned)e->n_etile), per_slot((n + 3) / 4), block(256);
+	const uint8_t *du = reinterpret_cast<const uint8_t *>(e->d_du);
+	hipLaunchKernelGGL(k_emit_len, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_tbits);
+	hipLaunchKernelGGL(k_emit_scan, per_slot, block, 0, e->stream, e->d_eslot, n, e->d_tbits, e->d_tboff);
+	hipLaunchKernelGGL(k_emit_count, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_tbits, e->d_tboff, e->d_tff, e->d_tfrag);
+	hipLaunchKernelGGL(k_emit_stuff, per_slot, block, 0, e->stream, e->d_eslot, n, e->d_tbits, e->d_tboff, e->d_tff, e->d_tfrag, e->d_tout, e->d_sent);
+	hipLaunchKernelGGL(k_emit_place, dim3(1), dim3(1024), 0, e->stream, n, e->d_sent, (uint64_t)e->arena_cap, e->d_res);
+	hipLaunchKernelGGL(k_emit_write, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_hdr, e->d_tbits, e->d_tboff, e->d_tfrag,
+							 e->d_tout, e->d_res, e->d_arena);
+	HIP_TRY(hipGetLastError());
+	e->emit_queued = true;
+	return MIJ_OK;
+}
+
+extern "C" int mij_enc_stream_reserve(mij_encoder *e, size_t bytes)
+{
+	if (!e)
+		return set_err(MIJ_E_ARG, "encoder is NULL");
+	HIP_TRY(hipSetDevice(e->ctx->device));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	enc_free_emit(e);
+	e->uploaded = e->launched = false; /* the emission lists are built at upload */
+	if (!bytes)
+		return MIJ_OK;
+	uint16_t code[4][256];
+	uint8_t len[4][256];
+	mjw_huff_tables(code, len);
+	EmitTables tabs;
+	memcpy(tabs.code, code, sizeof(code));
+	memcpy(tabs.len, len, sizeof(len));
+	hipError_t r = hipMalloc(reinterpret_cast<void **>(&e->d_arena), bytes);
+	if (r == hipSuccess)
+		r = hipHostMalloc(reinterpret_cast<void **>(&e->h_arena), bytes, hipHostMallocDefault);
+	if (r == hipSuccess)
+		r = hipMalloc(reinterpret_cast<void **>(&e->d_tabs), sizeof(EmitTables));
+	if (r == hipSuccess)
+		r = hipMemcpy(e->d_tabs, &tabs, sizeof(tabs), hipMemcpyHostToDevice);
+	if (r != hipSuccess) {
+		enc_free_emit(e);
+		return set_err(r == hipErrorOutOfMemory ? MIJ_E_NOMEM : MIJ_E_HIP, "mij_enc_stream_reserve(%zu): %s", bytes, hipGetErrorString(r));
+	}
+	e->arena_cap = bytes;
+	return MIJ_OK;
+}
+
+extern "C" int mij_enc_fetch_streams(mij_encoder *e)
+{
+	if (!e)
+		return set_err(MIJ_E_ARG, "encoder is NULL");
+	if (!e->d_arena)
+		return set_err(MIJ_E_STATE, "mij_enc_fetch_streams without an emission arena (mij_enc_stream_reserve)");
+	if (!e->launched || !e->emit_queued)
+		return set_err(MIJ_E_STATE, "mij_enc_fetch_streams before mij_enc_launch");
+	HIP_TRY(hipSetDevice(e->ctx->device));
+	const size_t n = e->slots.size();
+	HIP_TRY(hipMemcpyAsync(e->h_res, e->d_res, sizeof(EmitResult) * (n + 1), hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	const size_t used = (size_t)e->h_res[n].off;
+	if (used > e->arena_cap)
+		return set_err(MIJ_E_HIP, "emission reported %zu bytes for a %zu-byte arena", used, e->arena_cap);
+	if (used) {
+		HIP_TRY(hipMemcpyAsync(e->h_arena, e->d_arena, used, hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipStreamSynchronize(e->stream));
+	}
+	e->streams_fetched = true;
+	return (int)e->h_res[n].len;
+}
+
+extern "C" const unsigned char *mij_enc_stream(const mij_encoder *e, int slot, size_t *len)
+{
+	if (len)
+		*len = 0;
+	if (!e || slot < 0 || slot >= (int)e->slots.size()) {
+		set_err(MIJ_E_ARG, "bad slot");
+		return nullptr;
+	}
+	if (!e->streams_fetched) {
+		set_err(MIJ_E_STATE, "mij_enc_stream before mij_enc_fetch_streams");
+		return nullptr;
+	}
+	const EmitResult &r = e->h_res[slot];
+	if (len)
+		*len = (size_t)r.len;
+	if (r.off == ~0ull) {
+		set_err(MIJ_E_NOMEM, "slot %d did not fit in the emission arena (needs %llu bytes)", slot, (unsigned long long)r.len);
+		return nullptr;
+	}
+	return e->h_arena + r.off;
+}
+
+extern "C" int mij_enc_add_device(mij_encoder *e, const mij_in_tensor *t, int quality, int flip_vertically)
+{
+	if (!e || !t)
+		return set_err(MIJ_E_ARG, "bad argument");
+	if (t->layout != MIJ_LAYOUT_HWC && t->layout != MIJ_LAYOUT_CHW)
+		return set_err(MIJ_E_ARG, "mij_enc_add_device: layout %d unknown", t->layout);
+	mjw_plan plan;
+	if (!mjw_plan_init(&plan, t->width, t->height, t->comp, quality))
+		return set_err(MIJ_E_ARG, "bad image arguments (%dx%dx%d)", t->width, t->height, t->comp);
+	const bool chw = t->layout == MIJ_LAYOUT_CHW;
+	const int64_t w = t->width, h = t->height, C = t->comp, rp = t->row_pitch, pp = chw ? t->plane_pitch : 0;
+	const int64_t lim = (int64_t)1 << 40;
+	if (rp < 0 || rp > lim || pp < 0 || pp > lim)
+		return set_err(MIJ_E_ARG, "pitch out of range (row %lld, plane %lld)", (long long)rp, (long long)pp);
+	const int64_t line = chw ? w : w * C;
+	if ((h > 1 && rp < line) || (chw && C > 1 && pp < (h - 1) * rp + w))
+		return set_err(MIJ_E_ARG, "pitches let rows or planes overlap (row %lld, plane %lld; %lldx%lldx%lld %s)", (long long)rp, (long long)pp, (long long)w,
+							(long long)h, (long long)C, chw ? "CHW" : "HWC");
+	if (!t->src)
+		return set_err(MIJ_E_ARG, "src is NULL");
+	const uint64_t last = (uint64_t)((h - 1) * rp + (chw ? (C - 1) * pp + w - 1 : w * C - 1));
+	const int rc = device_extent(e->ctx->device, t->src, last + 1, "src");
+	if (rc != MIJ_OK)
+		return rc;
+	const int slot = enc_add_common(e, plan, nullptr, flip_vertically ? 1 : 0, -1, ENC_DEVICE);
+	if (slot >= 0)
+		e->slots[(size_t)slot].in = *t;
+	return slot;
+}
+
+extern "C" int mij_enc_add_units(mij_encoder *e, int width, int height, int comp, int quality, const int16_t *du)
+{
+	if (!e || !du)
+		return set_err(MIJ_E_ARG, "bad argument");
+	mjw_plan plan;
+	if (!mjw_plan_init(&plan, width, height, comp, quality))
+		return set_err(MIJ_E_ARG, "bad image arguments (%dx%dx%d)", width, height, comp);
+	const size_t nu = mjw_plan_du_count(&plan);
+	const int dpm = plan.du_per_mcu;
+	int pred[3] = {0, 0, 0};
+	for (size_t u = 0; u < nu; ++u) {
+		const int p = (int)(u % (size_t)dpm), c = dpm == 6 ? (p < 4 ? 0 : p - 3) : p;
+		const int16_t *d = du + u * 64;
+		const int diff = d[0] - pred[c];
+		pred[c] = d[0];
+		if (diff < -2047 || diff > 2047)
+			return set_err(MIJ_E_ARG, "unit %zu: DC difference %d outside -2047..2047", u, diff);
+		for (int k = 1; k < 64; ++k)
+			if (d[k] < -1023 || d[k] > 1023)
+				return set_err(MIJ_E_ARG, "unit %zu: AC value %d outside -1023..1023", u, d[k]);
+	}
+	std::vector<int16_t> units;
+	try {
+		units.assign(du, du + nu * 64);
+	} catch (const std::bad_alloc &) {
+		return set_err(MIJ_E_NOMEM, "out of host memory");
+	}
+	const int slot = enc_add_common(e, plan, nullptr, 0, -1, ENC_UNITS);
+	if (slot >= 0)
+		e->slots[(size_t)slot].units.swap(units);
+	return slot;
 }
 
 extern "C" int mij_enc_upload(mij_encoder *e)
@@ -2924,6 +3314,8 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 		const int sub = s.plan.subsample ? 1 : 0;
 		const uint32_t ny = nm * (sub ? 4u : 1u), nc = nm * 2u;
 		e->h_imgs[i] = s.dev;
+		if (s.kind == ENC_UNITS) /* given units: nothing to transform */
+			continue;
 		/* strips of 32 MCUs through the fused kernel: whole 16-pixel columns, packed RGB, 16-byte aligned rows (every width: enc_padded_width) */
 		if (sub && !e->force_generic) { /* every comp: the staging is packed RGB */
 			for (uint32_t f = 0; f < nm; f += MIJ_ENC_STRIP) {
@@ -2967,16 +3359,28 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 	HIP_TRY(hipMemcpyAsync(e->d_work, e->h_work, sizeof(WorkIdct) * total, hipMemcpyHostToDevice, e->stream));
 	for (size_t i = 0; i < n; ++i) {
 		const EncSlot &s = e->slots[i];
-		if (s.clone_of < 0)
+		if (s.clone_of < 0 && s.kind == ENC_HOST)
 			HIP_TRY(hipMemcpyAsync(e->d_pix + s.dev.pix_off, e->stage + s.stage_off, s.pix_bytes, hipMemcpyHostToDevice, e->stream));
+		else if (s.kind == ENC_UNITS)
+			HIP_TRY(hipMemcpyAsync(reinterpret_cast<uint8_t *>(e->d_du) + s.dev.du_off, s.units.data(), s.units.size() * sizeof(int16_t),
+										  hipMemcpyHostToDevice, e->stream));
 	}
+	rc = enc_gather(e); /* device-pixel slots, before the clones copy them */
+	if (rc != MIJ_OK)
+		return rc;
 	for (size_t i = 0; i < n; ++i) {
 		const EncSlot &s = e->slots[i];
 		if (s.clone_of >= 0)
 			HIP_TRY(hipMemcpyAsync(e->d_pix + s.dev.pix_off, e->d_pix + e->slots[(size_t)s.clone_of].dev.pix_off, s.pix_bytes, hipMemcpyDeviceToDevice, e->stream));
 	}
+	if (e->d_arena) {
+		rc = enc_emit_lists(e);
+		if (rc != MIJ_OK)
+			return rc;
+	}
 	e->uploaded = true;
 	e->launched = false;
+	e->emit_queued = e->streams_fetched = false;
 	return MIJ_OK;
 }
 
@@ -3006,7 +3410,13 @@ extern "C" int mij_enc_launch(mij_encoder *e)
 			hipLaunchKernelGGL((k_encode_c<1>), grid, block, 0, e->stream, e->d_imgs, wk, e->d_pix, e->d_du);
 		HIP_TRY(hipGetLastError());
 	}
+	if (e->d_arena) {
+		const int rc = enc_emit_launch(e);
+		if (rc != MIJ_OK)
+			return rc;
+	}
 	e->launched = true;
+	e->streams_fetched = false;
 	return MIJ_OK;
 }
 

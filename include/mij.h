@@ -430,6 +430,9 @@ int mij_batch_set_out_tensor_resized(mij_batch *b, int slot, const mij_out_tenso
 typedef struct mij_encoder mij_encoder;
 
 int mij_enc_create(mij_ctx *ctx, int max_images, size_t pixel_bytes, size_t du_bytes, mij_encoder **out);
+/* the same with pinned staging of its own size (mij_enc_create: stage_bytes = pixel_bytes); an encoder fed only by mij_enc_add_device
+ * and mij_enc_add_units needs none (0) */
+int mij_enc_create_ex(mij_ctx *ctx, int max_images, size_t stage_bytes, size_t pixel_bytes, size_t du_bytes, mij_encoder **out);
 void mij_enc_destroy(mij_encoder *e);
 int mij_enc_reset(mij_encoder *e);
 /* copies the pixels into pinned staging; quality and 4:2:0/4:4:4 choice as stbi_write_jpg; returns the slot */
@@ -461,6 +464,58 @@ int mij_enc_fetch(mij_encoder *e, int slot, int16_t *dst, size_t dst_elems);
 int mij_enc_timer_begin(mij_encoder *e);
 int mij_enc_timer_end(mij_encoder *e);
 int mij_enc_timer_elapsed_ms(mij_encoder *e, float *ms);
+
+/*
+ * Huffman emission on the GPU.  With an emission arena reserved, mij_enc_launch also queues, behind the transform, the kernels
+ * that turn every slot's data units into its complete stream -- exactly the bytes mjw_emit (mij_host.h) writes for those units:
+ * headers, entropy-coded segment with 0xFF 0x00 stuffing, fill bits, EOI.  Only the streams come back to the host.
+ *
+ * The arena holds the streams, placed in slot order: slot i starts where slot i-1 ends.  A slot fits when its stream ends inside
+ * the arena; the first slot that does not fit and every slot after it are not written at all (the kernels write nothing outside
+ * the arena), but their lengths are still computed.  The data-unit arena is only read: mij_enc_fetch / mij_enc_fetch_all still
+ * return every slot's units, so host mjw_emit can always finish a slot that did not fit.
+ *
+ * mij_enc_stream_reserve: before mij_enc_upload; bytes of device arena and of its pinned mirror (0 releases both).  Without an
+ * arena the encoder queues exactly the launches and copies it queues without this section.
+ * mij_enc_fetch_streams: waits for the launch, brings back the lengths and the used part of the arena (two copies) and returns
+ * the number of slots that fit; MIJ_E_STATE without an arena or before mij_enc_launch.
+ * mij_enc_stream: the slot's stream in the pinned mirror, valid until the next mij_enc_fetch_streams, mij_enc_reset or
+ * mij_enc_destroy; *len (when len is not NULL) is the stream's length.  For a slot that did not fit: NULL, *len the length it needs,
+ * and mij_last_error says so.
+ */
+int mij_enc_stream_reserve(mij_encoder *e, size_t bytes);
+int mij_enc_fetch_streams(mij_encoder *e);
+const unsigned char *mij_enc_stream(const mij_encoder *e, int slot, size_t *len);
+
+/*
+ * Encoder slots whose pixels are caller-owned device memory (the mirror image of tensor output).  uint8 elements; C = comp (1..4,
+ * the meaning stbi_write_jpg gives comp); pitches in elements, addressed as mij_out_tensor addresses them:
+ *     MIJ_LAYOUT_HWC  element (y, x, c) at src + y*row_pitch + x*comp + c        (plane_pitch ignored)
+ *     MIJ_LAYOUT_CHW  element (c, y, x) at src + c*plane_pitch + y*row_pitch + x
+ * The slot's stream (GPU emission, or mjw_emit of its units) equals stbi_write_jpg_to_func(width, height, comp, picture, quality)
+ * for the picture those elements describe; with flip_vertically, what that call writes under stbi_flip_vertically_on_write(1).
+ * At mij_enc_upload a gather kernel stages the pixels on the device in place of the host-to-device copy; the slot takes no pinned
+ * staging, and mij_enc_add_clone of it works.  MIJ_E_ARG, checked on the host, for: an unknown layout; width, height, comp or
+ * quality that mjw_plan_init refuses; pitches that let rows or planes overlap (HWC: row_pitch < width*comp; CHW: row_pitch <
+ * width or plane_pitch < (height-1)*row_pitch + width; a pitch only counts where there is more than one row or plane); src not
+ * device memory of the encoder's device; the read extent [src, last element] not inside the one allocation hipMemGetAddressRange
+ * reports for src.
+ *
+ * ORDERING: src is read on the encoder's stream from mij_enc_upload until mij_enc_wait (or a fetch that waits).  Make it idle
+ * before the upload (e.g. synchronise the stream that last wrote it) and leave it unchanged until the wait.
+ */
+typedef struct {
+	const void *src;                /* device memory on the encoder's device, owned by the caller */
+	int32_t layout;                 /* MIJ_LAYOUT_* */
+	int32_t width, height, comp;
+	int64_t row_pitch, plane_pitch; /* elements; plane_pitch ignored for HWC */
+} mij_in_tensor;
+int mij_enc_add_device(mij_encoder *e, const mij_in_tensor *t, int quality, int flip_vertically);
+
+/* A slot whose quantised data units are given: mjw_plan_du_count * 64 int16 in zigzag order, MCU after MCU (copied).  No transform
+ * runs for it; its units are uploaded and emitted.  MIJ_E_ARG when a DC difference (per component, in MCU order, from 0) leaves
+ * -2047..2047 or an AC value leaves -1023..1023: those fall outside the writer's tables.  mij_enc_add_clone refuses such a slot. */
+int mij_enc_add_units(mij_encoder *e, int width, int height, int comp, int quality, const int16_t *du);
 
 #ifdef __cplusplus
 }

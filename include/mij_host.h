@@ -123,6 +123,12 @@ size_t mjw_plan_du_count(const mjw_plan *p);
 void mjw_transform_host(const mjw_plan *p, const void *pixels, int flip_vertically, int16_t *du);
 int mjw_emit(const mjw_plan *p, const int16_t *du, mjw_write_func *func, void *context);
 int mjw_flip_on_write(void); /* the flag set by stbi_flip_vertically_on_write */
+/* The pieces of mjw_emit that GPU emission (mij_enc_stream_reserve, mij.h) reuses: the headers in front of the entropy-coded
+ * segment (always MJW_HEADER_BYTES; returns that count), and the writer's four Huffman code tables indexed by symbol, in the order
+ * luma DC, chroma DC, luma AC, chroma AC (codes right-aligned, len 0 for a symbol the table lacks). */
+#define MJW_HEADER_BYTES 607
+size_t mjw_header(const mjw_plan *p, unsigned char *out);
+void mjw_huff_tables(uint16_t code[4][256], uint8_t len[4][256]);
 
 /* the plan (tables, geometry) the GPU encoder built for a slot, for mjw_emit */
 int mij_enc_plan(const mij_encoder *e, int slot, mjw_plan *out);
