@@ -28,6 +28,7 @@ from .binding import (  # noqa: F401
     MIJ_FILTER_BICUBIC,
     MIJ_FILTER_LANCZOS,
     resize_coeffs,
+    exif_orientation,
     MIJ_DT_U8,
     MIJ_DT_F16,
     MIJ_DT_BF16,

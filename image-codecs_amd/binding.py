@@ -603,6 +603,14 @@ def resize_coeffs(n_in, n_out, filter="bilinear"):
     return lo_n[:, 0].copy(), lo_n[:, 1].copy(), k
 
 
+def exif_orientation(data):
+    """mjh_exif_orientation: the EXIF Orientation tag (1..8) of a JPEG file's bytes; 1 where there is none or it cannot be read."""
+    b = bytes(data)
+    L = lib()
+    L.mjh_exif_orientation.argtypes = [C.c_char_p, C.c_int]
+    return int(L.mjh_exif_orientation(b, len(b)))
+
+
 class Context:
     """mij_ctx: one per (process, device)."""
 
@@ -926,36 +934,48 @@ class Batch:
         return L.mij_batch_device_out_f32(self._h, int(slot))
 
     # ---- tensor output (mij_batch_set_out_tensor): k_out_tensor writes a crop window into device memory the caller owns
-    def set_out_tensor(self, slot, dst, dtype, layout, x0, y0, w, h, row_pitch, plane_pitch=0, flip_x=False, flip_y=False, table=None):
+    def set_out_tensor(self, slot, dst, dtype, layout, x0, y0, w, h, row_pitch, plane_pitch=0, flip_x=False, flip_y=False, table=None,
+                       orientation=1):
         """dst: raw device address; dtype MIJ_DT_* (or "u8", "f16", "bf16", "f32"), layout MIJ_LAYOUT_* (or "HWC", "CHW"); pitches in
-        elements; table: n_out*256 elements of dtype as any buffer (e.g. numpy uint16 for f16 / bf16), None only for u8 (identity)."""
+        elements; table: n_out*256 elements of dtype as any buffer (e.g. numpy uint16 for f16 / bf16), None only for u8 (identity).
+        orientation: 1..8 (EXIF); other than 1, the window is in the displayed picture (mij_batch_set_out_tensor_oriented)."""
         t = OutTensor(C.c_void_p(int(dst)), _DTYPES.get(dtype, dtype), _LAYOUTS.get(layout, layout), int(x0), int(y0), int(w), int(h),
                       int(bool(flip_x)), int(bool(flip_y)), int(row_pitch), int(plane_pitch))
-        tp = None
-        if table is not None:
-            tb = np.ascontiguousarray(table)
-            need = 256 * self._desc(slot).n_out * (1, 2, 2, 4)[t.dtype] if 0 <= t.dtype <= 3 else 0
-            if tb.nbytes < need:
-                raise ValueError("table has %d bytes, %d needed" % (tb.nbytes, need))
-            tp = tb.ctypes.data_as(C.c_void_p)
+        tb, tp = self._table(slot, t, table)
         L = lib()
+        if orientation != 1:
+            self._set_oriented(slot, t, None, orientation, tp)
+            return
         L.mij_batch_set_out_tensor.argtypes = [C.c_void_p, C.c_int, C.POINTER(OutTensor), C.c_void_p]
         _check(L.mij_batch_set_out_tensor(self._h, int(slot), C.byref(t), tp), "mij_batch_set_out_tensor")
 
+    def _table(self, slot, t, table):
+        """-> (buffer, pointer): the caller keeps the buffer alive across the call, which copies the table."""
+        if table is None:
+            return None, None
+        tb = np.ascontiguousarray(table)
+        need = 256 * self._desc(slot).n_out * (1, 2, 2, 4)[t.dtype] if 0 <= t.dtype <= 3 else 0
+        if tb.nbytes < need:
+            raise ValueError("table has %d bytes, %d needed" % (tb.nbytes, need))
+        return tb, tb.ctypes.data_as(C.c_void_p)
+
+    def _set_oriented(self, slot, t, r, orientation, tp):
+        L = lib()
+        L.mij_batch_set_out_tensor_oriented.argtypes = [C.c_void_p, C.c_int, C.POINTER(OutTensor), C.POINTER(OutResize), C.c_int32, C.c_void_p]
+        _check(L.mij_batch_set_out_tensor_oriented(self._h, int(slot), C.byref(t), None if r is None else C.byref(r), int(orientation), tp),
+               "mij_batch_set_out_tensor_oriented")
+
     def set_out_tensor_resized(self, slot, dst, dtype, layout, x0, y0, w, h, out_w, out_h, row_pitch, plane_pitch=0, flip_x=False, flip_y=False,
-                               table=None, filter="bilinear"):
+                               table=None, filter="bilinear", orientation=1):
         """mij_batch_set_out_tensor_resized: the window (x0, y0, w, h) resized to out_w x out_h with filter (a name of FILTERS or
-        MIJ_FILTER_*), then as set_out_tensor; pitches describe the out_w x out_h extent."""
+        MIJ_FILTER_*), then as set_out_tensor; pitches describe the out_w x out_h extent.  orientation: as set_out_tensor's."""
         t = OutTensor(C.c_void_p(int(dst)), _DTYPES.get(dtype, dtype), _LAYOUTS.get(layout, layout), int(x0), int(y0), int(w), int(h),
                       int(bool(flip_x)), int(bool(flip_y)), int(row_pitch), int(plane_pitch))
         r = OutResize(int(out_w), int(out_h), int(FILTERS.get(filter, filter)), 0)
-        tp = None
-        if table is not None:
-            tb = np.ascontiguousarray(table)
-            need = 256 * self._desc(slot).n_out * (1, 2, 2, 4)[t.dtype] if 0 <= t.dtype <= 3 else 0
-            if tb.nbytes < need:
-                raise ValueError("table has %d bytes, %d needed" % (tb.nbytes, need))
-            tp = tb.ctypes.data_as(C.c_void_p)
+        tb, tp = self._table(slot, t, table)
+        if orientation != 1:
+            self._set_oriented(slot, t, r, orientation, tp)
+            return
         L = lib()
         L.mij_batch_set_out_tensor_resized.argtypes = [C.c_void_p, C.c_int, C.POINTER(OutTensor), C.POINTER(OutResize), C.c_void_p]
         _check(L.mij_batch_set_out_tensor_resized(self._h, int(slot), C.byref(t), C.byref(r), tp), "mij_batch_set_out_tensor_resized")

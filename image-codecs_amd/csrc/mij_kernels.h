@@ -3188,7 +3188,8 @@ __device__ __forceinline__ void resize_item(const DevResize &s, const WorkResize
 	__syncthreads();
 }
 
-template <typename T, bool CHW>
+/* TR: k_out_resize_t's instantiation, kept apart from k_out_resize's so that neither kernel's code depends on the other */
+template <typename T, bool CHW, bool TR = false>
 __device__ __forceinline__ void resize_store(const DevResize &s, const WorkResize &wk, const uint8_t *lut, const uint8_t *ob)
 {
 	const uint32_t nr = wk.nr, nc = wk.nc, rb = nc * s.t.n_out;
@@ -3231,6 +3232,250 @@ __global__ __launch_bounds__(256) void k_out_resize(const DevResize *__restrict_
 	case 5: resize_store<uint16_t, true>(s, wk, lut, ob); break;
 	case 8: resize_store<uint32_t, false>(s, wk, lut, ob); break;
 	default: resize_store<uint32_t, true>(s, wk, lut, ob); break;
+	}
+}
+
+/* ------------------------------------------------------------------ oriented tensor output (mij_batch_set_out_tensor_oriented)
+ *
+ * Orientations 2..4 only mirror the stored picture: the host composes the mirror with the request's flips (and, with a resize, mirrors
+ * that axis's coefficients), so k_out_tensor and k_out_resize run them unchanged.  Orientations 5..8 transpose.  The host folds their
+ * mirrors the same way, which leaves one case for the kernels below: the window's output row r (before flips) is stored column
+ * x0 + r and its output column q is stored row y0 + q.  DevTensor keeps its fields with that meaning: x0, y0 the stored column and row
+ * of the window's corner, w the output columns (stored rows), h the output rows (stored columns), the flips those of the output.
+ * Both kernels stage whole stored-row segments, shifted so that each starts on a dword, at a pitch of an odd number of dwords: lanes
+ * that read down a staged column then fall on different LDS banks. */
+
+/* dword k of the bytes [a, a + nb) of `out`, read as the aligned dwords that hold them (none past the one that holds byte nb - 1) */
+__device__ __forceinline__ uint32_t staged_dword(const uint8_t *__restrict__ out, uint64_t a, uint32_t k, uint32_t nb)
+{
+	const uint32_t sh = (uint32_t)(a & 3u), nd = (sh + nb + 3u) >> 2;
+	const uint32_t *p = reinterpret_cast<const uint32_t *>(out + (a & ~(uint64_t)3)) + k;
+	const uint32_t lo = __builtin_nontemporal_load(p), hi = k + 1u < nd ? __builtin_nontemporal_load(p + 1) : 0u;
+	return __builtin_amdgcn_alignbyte(hi, lo, sh);
+}
+
+/* tensor_store with the staged byte of (row r, column q, channel c) given by byte_at(r, q, c); q is the staged column, i.e. the
+ * output column after s.flip_x.  A copy rather than a generalisation, so that k_out_tensor and k_out_resize keep their code. */
+template <typename T, bool CHW, int N, typename ByteAt>
+__device__ __forceinline__ void tensor_store_at(const DevTensor &s, uint32_t row0, uint32_t p0, uint32_t nr, uint32_t np, const uint8_t *lut, ByteAt byte_at)
+{
+	constexpr uint32_t ES = sizeof(T), V = 16u / ES, LS = 256u * ES + MIJ_TEN_LDS_PAD, PW = 4u / ES;
+	const uint32_t nb = np * N;
+	const uint32_t E = CHW ? np : nb, nl = CHW ? nr * N : nr, um = E / V + 2u;
+	for (uint32_t i = threadIdx.x; i < nl * um; i += 256u) {
+		const uint32_t line = i / um, u = i - line * um;
+		const uint32_t r = CHW ? line / N : line, pc = CHW ? line - r * N : 0u, oy = row0 + r;
+		T *d = reinterpret_cast<T *>(s.dst) + (int64_t)oy * s.row_pitch + (CHW ? (int64_t)pc * s.plane_pitch + p0 : (int64_t)p0 * N);
+		const uint32_t head = (uint32_t)(((16u - ((uintptr_t)d & 15u)) & 15u) / ES);
+		const uint32_t e0 = u ? head + (u - 1u) * V : 0u;
+		const uint32_t e1 = u ? min(E, e0 + V) : min(E, head);
+		if (e0 >= e1)
+			continue;
+		auto value = [&](uint32_t e) -> T {
+			const uint32_t q = CHW ? e : e / N, c = CHW ? pc : e - q * N;
+			const uint32_t v = byte_at(r, s.flip_x ? np - 1u - q : q, c);
+			return s.lut ? reinterpret_cast<const T *>(lut + c * LS)[v] : (T)v;
+		};
+		if (u && e1 - e0 == V) { /* 16-byte aligned: one store */
+			u4v o;
+#pragma unroll
+			for (uint32_t k = 0; k < 4u; ++k) {
+				uint32_t wd = 0;
+#pragma unroll
+				for (uint32_t j = 0; j < PW; ++j)
+					wd |= (uint32_t)value(e0 + k * PW + j) << (8u * ES * j);
+				o[k] = wd;
+			}
+			__builtin_nontemporal_store(o, reinterpret_cast<u4v *>(d + e0));
+		} else {
+			for (uint32_t e = e0; e < e1; ++e)
+				d[e] = value(e);
+		}
+	}
+}
+
+/* k_out_tensor_t's work item: output rows [row0, row0 + nrows) x output columns [p0, p0 + np), i.e. np stored-row segments of nrows
+ * stored columns.  Phase 1 stages segment q (ascending stored rows) at q * lsd dwords; phase 2 reads (r, q, c) down staged column r. */
+template <typename T, bool CHW, int N>
+__device__ __forceinline__ void tensor_item_t(const DevTensor &s, const WorkTensor &wk, const uint8_t *__restrict__ out, const uint8_t *lut, uint32_t *stage)
+{
+	const uint32_t np = wk.np, nr = wk.nrows, nb = nr * N, nw = (nb + 3u) >> 2, lsd = nw | 1u;
+	const uint32_t sx = s.flip_y ? s.x0 + s.h - wk.row0 - nr : s.x0 + wk.row0; /* first stored column of the tile */
+	const uint32_t sy = s.flip_x ? s.y0 + s.w - wk.p0 - np : s.y0 + wk.p0;     /* first stored row of the tile */
+	const uint64_t rowb = (uint64_t)s.src_w * N, a0 = s.src_off + (uint64_t)sy * rowb + (uint64_t)sx * N;
+	for (uint32_t i = threadIdx.x; i < np * nw; i += 256u) {
+		const uint32_t q = i / nw, k = i - q * nw;
+		stage[q * lsd + k] = staged_dword(out, a0 + (uint64_t)q * rowb, k, nb);
+	}
+	__syncthreads();
+	const uint8_t *sb = reinterpret_cast<const uint8_t *>(stage);
+	tensor_store_at<T, CHW, N>(s, wk.row0, wk.p0, nr, np, lut, [&](uint32_t r, uint32_t q, uint32_t c) -> uint32_t {
+		return sb[q * lsd * 4u + (s.flip_y ? nr - 1u - r : r) * (uint32_t)N + c];
+	});
+}
+
+template <typename T, bool CHW>
+__device__ __forceinline__ void tensor_item_t_n(const DevTensor &s, const WorkTensor &wk, const uint8_t *__restrict__ out, const uint8_t *lut, uint32_t *stage)
+{
+	switch (s.n_out) {
+	case 1: tensor_item_t<T, CHW, 1>(s, wk, out, lut, stage); break;
+	case 2: tensor_item_t<T, CHW, 2>(s, wk, out, lut, stage); break;
+	case 3: tensor_item_t<T, CHW, 3>(s, wk, out, lut, stage); break;
+	default: tensor_item_t<T, CHW, 4>(s, wk, out, lut, stage); break;
+	}
+}
+
+__global__ __launch_bounds__(256) void k_out_tensor_t(const DevTensor *__restrict__ ts, const WorkTensor *__restrict__ work, const uint8_t *__restrict__ luts,
+																	  const uint8_t *__restrict__ out)
+{
+	__shared__ uint32_t stage[MIJ_TEN_STAGE_WORDS];
+	__shared__ uint32_t lutw[4u * (1024u + MIJ_TEN_LDS_PAD) / 4u];
+	const WorkTensor wk = work[blockIdx.x];
+	const DevTensor s = ts[wk.t];
+	if (s.lut) {
+		const uint32_t tw = 64u * s.esize, lsw = tw + MIJ_TEN_LDS_PAD / 4u;
+		const uint32_t *g = reinterpret_cast<const uint32_t *>(luts + (size_t)wk.t * MIJ_TEN_LUT_BYTES);
+		for (uint32_t t = threadIdx.x; t < s.n_out * tw; t += 256u)
+			lutw[(t / tw) * lsw + t % tw] = g[t];
+	}
+	const uint8_t *lut = reinterpret_cast<const uint8_t *>(lutw);
+	/* tensor_item_t's __syncthreads orders the table writes before the lookups */
+	switch (s.esize * 2u + s.chw) {
+	case 2: tensor_item_t_n<uint8_t, false>(s, wk, out, lut, stage); break;
+	case 3: tensor_item_t_n<uint8_t, true>(s, wk, out, lut, stage); break;
+	case 4: tensor_item_t_n<uint16_t, false>(s, wk, out, lut, stage); break;
+	case 5: tensor_item_t_n<uint16_t, true>(s, wk, out, lut, stage); break;
+	case 8: tensor_item_t_n<uint32_t, false>(s, wk, out, lut, stage); break;
+	default: tensor_item_t_n<uint32_t, true>(s, wk, out, lut, stage); break;
+	}
+}
+
+/* resize_item for a transposed request: the first (horizontal) pass runs down the stored columns.  sx0..sx1 are the stored rows the
+ * segment's horizontal taps read (relative to s.t.y0), sy0..sy1 the stored columns the band's vertical taps read (relative to s.t.x0).
+ * A round stages the span's stored rows x R stored columns, each row's R * N bytes at an odd pitch of ld dwords; each lane sums its
+ * horizontal taps down a staged column and feeds the vertical accumulators as resize_item does.  A span of more rows than the stage
+ * holds is walked in chunks of rows, one column per round, the partial sums kept in a register. */
+template <bool M32, bool KG>
+__device__ __forceinline__ void resize_item_t(const DevResize &s, const WorkResize &wk, const uint8_t *__restrict__ plan, const uint8_t *__restrict__ out,
+																uint32_t *stage, int32_t *kl, int32_t *vkl)
+{
+	const uint32_t N = s.t.n_out, nc = wk.nc, nr = wk.nr, q0 = wk.q0, u0 = wk.u0, ksh = s.ksh, ksv = s.ksv;
+	const int32_t *hln = reinterpret_cast<const int32_t *>(plan + s.hco), *hk = hln + 2u * s.out_w;
+	const int32_t *vln = reinterpret_cast<const int32_t *>(plan + s.vco), *vk = vln + 2u * s.out_h;
+	const uint32_t tid = threadIdx.x, o = tid / N, c = tid - o * N;
+	const bool lane = o < nc;
+	const uint32_t uo = u0 + (lane ? o : 0u);
+	const uint32_t sx0 = (uint32_t)hln[2u * u0], sx1 = (uint32_t)(hln[2u * (u0 + nc - 1u)] + hln[2u * (u0 + nc - 1u) + 1u]);
+	const int32_t hlo = hln[2u * uo] - (int32_t)sx0, hn = lane ? hln[2u * uo + 1u] : 0;
+	if (!KG)
+		for (uint32_t i = tid; i < nc * ksh; i += 256u)
+			kl[i] = hk[(size_t)u0 * ksh + i];
+	const int32_t *kp = KG ? hk + (size_t)uo * ksh : kl + (lane ? o : 0u) * ksh;
+	const bool vg = s.vglobal != 0;
+	if (!vg)
+		for (uint32_t i = tid; i < nr * ksv; i += 256u)
+			vkl[i] = vk[(size_t)q0 * ksv + i];
+	uint32_t vlo[MIJ_RSZ_ROWS], vn[MIJ_RSZ_ROWS];
+	int32_t acc[MIJ_RSZ_ROWS];
+#pragma unroll
+	for (uint32_t j = 0; j < MIJ_RSZ_ROWS; ++j) {
+		vlo[j] = j < nr ? (uint32_t)vln[2u * (q0 + j)] : 0u;
+		vn[j] = j < nr ? (uint32_t)vln[2u * (q0 + j) + 1u] : 0u;
+		acc[j] = 1 << 21;
+	}
+	const uint32_t sy0 = vlo[0], sy1 = (uint32_t)(vln[2u * (q0 + nr - 1u)] + vln[2u * (q0 + nr - 1u) + 1u]);
+	const uint32_t span = sx1 - sx0;
+	const bool one = span <= MIJ_RSZ_STAGE_WORDS; /* every row of the span in one chunk: several columns per round */
+	uint32_t ldm = one ? MIJ_RSZ_STAGE_WORDS / span : 1u;
+	ldm -= (ldm & 1u) ^ 1u; /* odd */
+	const uint32_t R = one ? ldm * 4u / N : 1u, ld = one ? (((R * N + 3u) >> 2) | 1u) : 1u, cc = one ? span : MIJ_RSZ_STAGE_WORDS;
+	const uint64_t rowb = (uint64_t)s.t.src_w * N, base = s.t.src_off + (uint64_t)(s.t.y0 + sx0) * rowb + (uint64_t)s.t.x0 * N;
+	const uint8_t *sb = reinterpret_cast<const uint8_t *>(stage);
+	const int32_t ldb = (int32_t)(ld * 4u);
+	auto vertical = [&](uint32_t sy, int32_t hs) {
+		const uint32_t hv = (uint32_t)min(max(hs >> 22, 0), 255);
+#pragma unroll
+		for (uint32_t j = 0; j < MIJ_RSZ_ROWS; ++j) {
+			const uint32_t d = sy - vlo[j];
+			if (d < vn[j])
+				acc[j] = rsz_mac<M32>(acc[j], hv, vg ? vk[(size_t)(q0 + j) * ksv + d] : vkl[j * ksv + d]);
+		}
+	};
+	__syncthreads(); /* kl, vkl, and the tables k_out_resize_t put in LDS */
+	for (uint32_t y = sy0; y < sy1; y += R) {
+		const uint32_t nrw = min(R, sy1 - y), nb = nrw * N, nw = (nb + 3u) >> 2;
+		int32_t hsum = 1 << 21;
+		for (uint32_t cx = 0; cx < span; cx += cc) {
+			const uint32_t ncc = min(cc, span - cx);
+			for (uint32_t i = tid; i < ncc * nw; i += 256u) {
+				const uint32_t r = i / nw, k = i - r * nw;
+				stage[r * ld + k] = staged_dword(out, base + (uint64_t)(cx + r) * rowb + (uint64_t)y * N, k, nb);
+			}
+			__syncthreads();
+			const int32_t tb = max((int32_t)cx - hlo, 0), te = min(hn, (int32_t)(cx + ncc) - hlo);
+			for (uint32_t r = 0; r < nrw; ++r) {
+				const uint8_t *col = sb + (hlo - (int32_t)cx) * ldb + (int32_t)(r * N + c);
+				/* four taps at a time: their LDS reads are issued together, so that their latency overlaps */
+				int32_t p = 0, p1 = 0, t = tb;
+				for (; t + 4 <= te; t += 4) {
+					const uint32_t x0 = col[t * ldb], x1 = col[(t + 1) * ldb], x2 = col[(t + 2) * ldb], x3 = col[(t + 3) * ldb];
+					const int32_t k0 = kp[t], k1 = kp[t + 1], k2 = kp[t + 2], k3 = kp[t + 3];
+					p = rsz_mac<M32>(rsz_mac<M32>(p, x0, k0), x2, k2);
+					p1 = rsz_mac<M32>(rsz_mac<M32>(p1, x1, k1), x3, k3);
+				}
+				for (; t < te; ++t)
+					p = rsz_mac<M32>(p, col[t * ldb], kp[t]);
+				p += p1;
+				if (one)
+					vertical(y + r, p + (1 << 21));
+				else
+					hsum += p;
+			}
+			__syncthreads();
+		}
+		if (!one)
+			vertical(y, hsum);
+	}
+	uint8_t *ob = reinterpret_cast<uint8_t *>(stage);
+	if (lane) {
+#pragma unroll
+		for (uint32_t j = 0; j < MIJ_RSZ_ROWS; ++j)
+			if (j < nr)
+				ob[j * nc * N + o * N + c] = (uint8_t)min(max(acc[j] >> 22, 0), 255);
+	}
+	__syncthreads();
+}
+
+__global__ __launch_bounds__(256) void k_out_resize_t(const DevResize *__restrict__ rs, const WorkResize *__restrict__ work, const uint8_t *__restrict__ luts,
+																	  const uint8_t *__restrict__ plan, const uint8_t *__restrict__ out)
+{
+	__shared__ uint32_t stage[MIJ_RSZ_STAGE_WORDS];
+	__shared__ int32_t kl[MIJ_RSZ_KCAP];
+	__shared__ int32_t vkl[MIJ_RSZ_VCAP];
+	__shared__ uint32_t lutw[4u * (1024u + MIJ_TEN_LDS_PAD) / 4u];
+	const WorkResize wk = work[blockIdx.x];
+	const DevResize s = rs[wk.t];
+	if (s.t.lut) {
+		const uint32_t tw = 64u * s.t.esize, lsw = tw + MIJ_TEN_LDS_PAD / 4u;
+		const uint32_t *g = reinterpret_cast<const uint32_t *>(luts + (size_t)wk.t * MIJ_TEN_LUT_BYTES);
+		for (uint32_t t = threadIdx.x; t < s.t.n_out * tw; t += 256u)
+			lutw[(t / tw) * lsw + t % tw] = g[t];
+	}
+	switch (s.mul32 * 2u + s.kglobal) {
+	case 0: resize_item_t<false, false>(s, wk, plan, out, stage, kl, vkl); break;
+	case 1: resize_item_t<false, true>(s, wk, plan, out, stage, kl, vkl); break;
+	case 2: resize_item_t<true, false>(s, wk, plan, out, stage, kl, vkl); break;
+	default: resize_item_t<true, true>(s, wk, plan, out, stage, kl, vkl); break;
+	}
+	/* the resized bytes are in the output frame: resize_store writes them as k_out_resize does */
+	const uint8_t *lut = reinterpret_cast<const uint8_t *>(lutw), *ob = reinterpret_cast<const uint8_t *>(stage);
+	switch (s.t.esize * 2u + s.t.chw) {
+	case 2: resize_store<uint8_t, false, true>(s, wk, lut, ob); break;
+	case 3: resize_store<uint8_t, true, true>(s, wk, lut, ob); break;
+	case 4: resize_store<uint16_t, false, true>(s, wk, lut, ob); break;
+	case 5: resize_store<uint16_t, true, true>(s, wk, lut, ob); break;
+	case 8: resize_store<uint32_t, false, true>(s, wk, lut, ob); break;
+	default: resize_store<uint32_t, true, true>(s, wk, lut, ob); break;
 	}
 }
 

@@ -327,8 +327,9 @@ struct mij_batch {
 	};
 	struct TenReq {
 		int slot;
-		mij_out_tensor t;
-		bool rsz; /* a resized request: r, and the coefficients of its axes */
+		mij_out_tensor t; /* in the stored picture's frame: an oriented request's mirrors are folded into the window and flips */
+		bool tr;          /* orientations 5..8: transposed (k_out_tensor_t / k_out_resize_t; DevTensor's transposed meaning) */
+		bool rsz; /* a resized request: r, and the coefficients of its axes (mirrored where the orientation mirrors that axis) */
 		mij_out_resize r;
 		const RszCoef *ch, *cv;
 		uint32_t esize;
@@ -341,6 +342,8 @@ struct mij_batch {
 	 * requests point at them), and k_out_resize's plan -- descriptors, tables, coefficients and work list -- in a buffer pair of its own */
 	std::map<uint64_t, RszCoef> rsz_coef;
 	PlanBuf rszplan;
+	/* oriented tensor output with orientations 5..8 (mij_batch_set_out_tensor_oriented): k_out_tensor_t's and k_out_resize_t's plans */
+	PlanBuf tentplan, rsztplan;
 };
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -432,7 +435,7 @@ extern "C" void mij_batch_destroy(mij_batch *b)
 	if (b->es)
 		es_free_fwd(b->es);
 	free_dev(b->d_f32);
-	for (PlanBuf *p : {&b->f32plan, &b->tenplan, &b->rszplan}) {
+	for (PlanBuf *p : {&b->f32plan, &b->tenplan, &b->rszplan, &b->tentplan, &b->rsztplan}) {
 		free_host(p->h);
 		free_dev(p->d);
 	}
@@ -458,7 +461,7 @@ extern "C" int mij_batch_reset(mij_batch *b)
 	b->f32_used = 0;
 	b->ten_req.clear();
 	b->rsz_coef.clear();
-	b->f32plan.items = b->tenplan.items = b->rszplan.items = 0;
+	b->f32plan.items = b->tenplan.items = b->rszplan.items = b->tentplan.items = b->rsztplan.items = 0;
 	es_reset_fwd(b->es);
 	return MIJ_OK;
 }
@@ -980,19 +983,30 @@ static void dev_tensor(DevTensor &d, const mij_batch::TenReq &q, const Slot &s)
 
 /* Tensor output: k_out_tensor's descriptors, tables and work list -- (request, band of window rows, segment of window columns) items of
  * at most MIJ_TEN_ITEM_BYTES source bytes and MIJ_TEN_MAX_ROWS rows -- built next to the decode plan and copied up on the batch stream.
- * A batch without tensor requests does nothing here. */
-static int ten_plan(mij_batch *b)
+ * With tr, k_out_tensor_t's for the transposed requests instead: tiles of at most MIJ_TEN_TR_BYTES bytes of each of at most
+ * MIJ_TEN_STAGE_WORDS / pitch stored-row segments, near square in pixels.  A batch without such requests does nothing here. */
+#define MIJ_TEN_TR_BYTES 192u
+static int ten_plan(mij_batch *b, bool tr)
 {
-	b->tenplan.items = 0;
+	PlanBuf &pb = tr ? b->tentplan : b->tenplan;
+	pb.items = 0;
 	const size_t nreq = b->ten_req.size();
 	if (!nreq)
 		return MIJ_OK;
 	std::vector<WorkTensor> work;
 	for (size_t t = 0; t < nreq; ++t) {
 		const mij_batch::TenReq &q = b->ten_req[t];
-		if ((b->slots[(size_t)q.slot].desc.flags & MIJ_FLAG_SKIP) || q.rsz) /* resized requests: rsz_plan */
+		if ((b->slots[(size_t)q.slot].desc.flags & MIJ_FLAG_SKIP) || q.rsz || q.tr != tr) /* resized requests: rsz_plan */
 			continue;
 		const uint32_t c = (uint32_t)b->slots[(size_t)q.slot].desc.n_out, w = (uint32_t)q.t.w, h = (uint32_t)q.t.h;
+		if (tr) {
+			const uint32_t rows = std::min(h, std::max(1u, MIJ_TEN_TR_BYTES / c)), lsd = ((rows * c + 3u) >> 2) | 1u;
+			const uint32_t cols = std::min(w, MIJ_TEN_STAGE_WORDS / lsd);
+			for (uint32_t r0 = 0; r0 < h; r0 += rows)
+				for (uint32_t p0 = 0; p0 < w; p0 += cols)
+					work.push_back(WorkTensor{(uint32_t)t, r0, p0, (uint16_t)std::min(rows, h - r0), (uint16_t)std::min(cols, w - p0)});
+			continue;
+		}
 		const uint32_t segw = std::min(w, MIJ_TEN_ITEM_BYTES / c);
 		for (uint32_t p0 = 0; p0 < w; p0 += segw) {
 			const uint32_t np = std::min(segw, w - p0);
@@ -1007,7 +1021,7 @@ static int ten_plan(mij_batch *b)
 		return set_err(MIJ_E_ARG, "tensor output: %zu work items", work.size());
 	const size_t lut_at = align_up(sizeof(DevTensor) * nreq, 256), work_at = lut_at + MIJ_TEN_LUT_BYTES * nreq;
 	const size_t need = work_at + sizeof(WorkTensor) * work.size();
-	return plan_put(b, b->tenplan, need, work.size(), lut_at, work_at, [&](uint8_t *h) {
+	return plan_put(b, pb, need, work.size(), lut_at, work_at, [&](uint8_t *h) {
 		DevTensor *td = reinterpret_cast<DevTensor *>(h);
 		for (size_t t = 0; t < nreq; ++t) {
 			const mij_batch::TenReq &q = b->ten_req[t];
@@ -1022,14 +1036,16 @@ static int ten_plan(mij_batch *b)
  * at most MIJ_RSZ_ROWS output rows, segment of output columns) -- in one buffer pair.  A segment has at most one column per lane
  * (256 / n_out), few enough that its horizontal taps fit MIJ_RSZ_KCAP (else they stay in the plan) and, where it can, that its span of
  * source bytes fills at most half the stage, so that a round stages two rows or more.  A band has as many rows as keep its vertical taps
- * within MIJ_RSZ_VCAP (else they stay in the plan).  A batch without resized requests does nothing. */
-static int rsz_plan(mij_batch *b)
+ * within MIJ_RSZ_VCAP (else they stay in the plan).  With tr, k_out_resize_t's plan for the transposed requests, whose span is one of
+ * stored rows: where it can, few enough that a round stages 8 stored columns or more.  A batch without such requests does nothing. */
+static int rsz_plan(mij_batch *b, bool tr)
 {
-	b->rszplan.items = 0;
+	PlanBuf &pb = tr ? b->rsztplan : b->rszplan;
+	pb.items = 0;
 	const size_t nreq = b->ten_req.size();
 	size_t nrsz = 0;
 	for (const mij_batch::TenReq &q : b->ten_req)
-		nrsz += q.rsz && !(b->slots[(size_t)q.slot].desc.flags & MIJ_FLAG_SKIP);
+		nrsz += q.rsz && q.tr == tr && !(b->slots[(size_t)q.slot].desc.flags & MIJ_FLAG_SKIP);
 	if (!nrsz)
 		return MIJ_OK;
 	/* byte offsets of the coefficient blocks, each (in, out, filter) once */
@@ -1040,7 +1056,7 @@ static int rsz_plan(mij_batch *b)
 	std::vector<uint32_t> kglobal(nreq, 0), vglobal(nreq, 0);
 	for (size_t t = 0; t < nreq; ++t) {
 		const mij_batch::TenReq &q = b->ten_req[t];
-		if (!q.rsz || (b->slots[(size_t)q.slot].desc.flags & MIJ_FLAG_SKIP))
+		if (!q.rsz || q.tr != tr || (b->slots[(size_t)q.slot].desc.flags & MIJ_FLAG_SKIP))
 			continue;
 		for (const mij_batch::RszCoef *c : {q.ch, q.cv})
 			if (at.emplace(c, off).second)
@@ -1052,7 +1068,8 @@ static int rsz_plan(mij_batch *b)
 			kglobal[t] = 1;
 		else
 			nc = std::min(nc, MIJ_RSZ_KCAP / ksh);
-		const double scale = (double)q.t.w / ow, half = MIJ_RSZ_STAGE_WORDS * 2.0 / n; /* source columns in half the stage */
+		/* source columns in half the stage; transposed, stored rows of which the stage holds 8 columns */
+		const double scale = (double)q.t.w / ow, half = tr ? (double)MIJ_RSZ_STAGE_WORDS / (((8u * n + 3u) >> 2) | 1u) : MIJ_RSZ_STAGE_WORDS * 2.0 / n;
 		if ((nc * scale + ksh) > half)
 			nc = (uint32_t)std::max(1.0, std::min((double)nc, (half - ksh) / scale));
 		const uint32_t nseg = (ow + nc - 1) / nc, segw = (ow + nseg - 1) / nseg;
@@ -1066,12 +1083,12 @@ static int rsz_plan(mij_batch *b)
 	if (work.size() > 0x7fffffffu)
 		return set_err(MIJ_E_ARG, "resized tensor output: %zu work items", work.size());
 	const size_t work_at = align_up(off, 16), need = work_at + sizeof(WorkResize) * work.size();
-	return plan_put(b, b->rszplan, need, work.size(), lut_at, work_at, [&](uint8_t *h) {
+	return plan_put(b, pb, need, work.size(), lut_at, work_at, [&](uint8_t *h) {
 		DevResize *rd = reinterpret_cast<DevResize *>(h);
 		memset(rd, 0, sizeof(DevResize) * nreq);
 		for (size_t t = 0; t < nreq; ++t) {
 			const mij_batch::TenReq &q = b->ten_req[t];
-			if (!q.rsz || (b->slots[(size_t)q.slot].desc.flags & MIJ_FLAG_SKIP))
+			if (!q.rsz || q.tr != tr || (b->slots[(size_t)q.slot].desc.flags & MIJ_FLAG_SKIP))
 				continue;
 			DevResize &d = rd[t];
 			dev_tensor(d.t, q, b->slots[(size_t)q.slot]);
@@ -1455,7 +1472,8 @@ extern "C" int mij_batch_upload(mij_batch *b)
 	if ((rc = scratch_planes(b, p.planes_need)) != MIJ_OK || (rc = lay_out_work(b, p)) != MIJ_OK || (rc = copy_coefficients(b)) != MIJ_OK ||
 		 (rc = launch_pack(b, p.pack.size())) != MIJ_OK || (rc = copy_clones(b)) != MIJ_OK)
 		return rc;
-	if ((rc = f32_plan(b)) != MIJ_OK || (rc = ten_plan(b)) != MIJ_OK || (rc = rsz_plan(b)) != MIJ_OK)
+	if ((rc = f32_plan(b)) != MIJ_OK || (rc = ten_plan(b, false)) != MIJ_OK || (rc = rsz_plan(b, false)) != MIJ_OK || (rc = ten_plan(b, true)) != MIJ_OK ||
+		 (rc = rsz_plan(b, true)) != MIJ_OK)
 		return rc;
 	b->uploaded = true;
 	b->launched = false;
@@ -1495,6 +1513,18 @@ extern "C" int mij_batch_launch(mij_batch *b)
 	if (rp.items) {
 		hipLaunchKernelGGL(k_out_resize, dim3((unsigned)rp.items), dim3(256), 0, b->stream, reinterpret_cast<const DevResize *>(rp.d),
 								 reinterpret_cast<const WorkResize *>(rp.d + rp.work_at), rp.d + rp.lut_at, rp.d, b->d_out);
+		HIP_TRY(hipGetLastError());
+	}
+	/* transposed (oriented 5..8) tensor output, plain and resized: only when such a request exists */
+	const PlanBuf &tq = b->tentplan, &rq = b->rsztplan;
+	if (tq.items) {
+		hipLaunchKernelGGL(k_out_tensor_t, dim3((unsigned)tq.items), dim3(256), 0, b->stream, reinterpret_cast<const DevTensor *>(tq.d),
+								 reinterpret_cast<const WorkTensor *>(tq.d + tq.work_at), tq.d + tq.lut_at, b->d_out);
+		HIP_TRY(hipGetLastError());
+	}
+	if (rq.items) {
+		hipLaunchKernelGGL(k_out_resize_t, dim3((unsigned)rq.items), dim3(256), 0, b->stream, reinterpret_cast<const DevResize *>(rq.d),
+								 reinterpret_cast<const WorkResize *>(rq.d + rq.work_at), rq.d + rq.lut_at, rq.d, b->d_out);
 		HIP_TRY(hipGetLastError());
 	}
 	b->launched = true;
@@ -1671,13 +1701,34 @@ extern "C" void *mij_batch_device_out_f32(mij_batch *b, int slot)
 /* One axis of a resized request: the coefficients of mjh_resize_coeffs, cached per (in, out, filter) until reset, and checked against
  * the kernel's arithmetic.  An axis whose size does not change gets the identity (one tap of 2^22 per output), which gives back the
  * input bytes exactly: the contract skips that pass. */
-static const mij_batch::RszCoef *rsz_coef(mij_batch *b, int in, int out, int filter)
+static const mij_batch::RszCoef *rsz_coef(mij_batch *b, int in, int out, int filter, bool mirror = false)
 {
-	const uint64_t key = ((uint64_t)(uint32_t)in << 32) | ((uint64_t)(uint32_t)out << 3) | (uint64_t)(uint32_t)(in == out ? 7 : filter);
+	const uint64_t key = ((uint64_t)(uint32_t)in << 32) | ((uint64_t)(uint32_t)out << 3) | (uint64_t)(uint32_t)(in == out ? 7 : filter) |
+								(mirror && in != out ? (uint64_t)1 << 24 : 0);
 	auto it = b->rsz_coef.find(key);
 	if (it != b->rsz_coef.end())
 		return &it->second;
 	mij_batch::RszCoef c;
+	if (mirror && in != out) {
+		/* the axis read backwards: output o of the mirrored input is output out-1-o of the input, mirrored.  lo* = in - lo - n of
+		 * out-1-o, its taps reversed, stays ascending; the request's flip of the axis is toggled (set_out_tensor). */
+		const mij_batch::RszCoef *f = rsz_coef(b, in, out, filter, false);
+		if (!f)
+			return nullptr;
+		c = *f;
+		const size_t ks = (size_t)c.ks;
+		for (int o = 0; o < out; ++o) {
+			const size_t m = (size_t)(out - 1 - o);
+			const int32_t lo = f->v[2 * m], n = f->v[2 * m + 1];
+			c.v[2 * (size_t)o] = in - lo - n;
+			c.v[2 * (size_t)o + 1] = n;
+			int32_t *k = c.v.data() + 2 * (size_t)out + (size_t)o * ks;
+			const int32_t *fk = f->v.data() + 2 * (size_t)out + m * ks;
+			for (int t = 0; t < n; ++t)
+				k[t] = fk[n - 1 - t];
+		}
+		return &b->rsz_coef.emplace(key, std::move(c)).first->second;
+	}
 	if (in == out) {
 		c.ks = 1;
 		c.v.resize((size_t)out * 3);
@@ -1734,7 +1785,10 @@ static int device_extent(int device, const void *p, uint64_t extent, const char 
 	return MIJ_OK;
 }
 
-static int set_out_tensor(mij_batch *b, int slot, const mij_out_tensor *t, const mij_out_resize *rz, const void *table)
+/* o = 1..8 as (transpose, mirror the stored x axis, mirror the stored y axis): D is (S mirrored)^T when transposed (include/mij.h) */
+static const uint8_t orient_tr[9] = {0, 0, 0, 0, 0, 1, 1, 1, 1}, orient_mx[9] = {0, 0, 1, 1, 0, 0, 0, 1, 1}, orient_my[9] = {0, 0, 0, 1, 1, 0, 1, 1, 0};
+
+static int set_out_tensor(mij_batch *b, int slot, const mij_out_tensor *t, const mij_out_resize *rz, int32_t orient, const void *table)
 {
 	if (!b || slot < 0 || slot >= (int)b->slots.size() || !t)
 		return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor: bad slot or request");
@@ -1747,16 +1801,23 @@ static int set_out_tensor(mij_batch *b, int slot, const mij_out_tensor *t, const
 		return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor: dtype %d / layout %d unknown", t->dtype, t->layout);
 	if (!table && t->dtype != MIJ_DT_U8)
 		return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor: a table is required for dtype %d", t->dtype);
+	if (orient < 1 || orient > 8)
+		return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor_oriented: orientation %d is not 1..8", (int)orient);
+	const bool tr = orient_tr[orient], mx = orient_mx[orient], my = orient_my[orient];
 	const int64_t W = s.desc.width, H = s.desc.height, C = s.desc.n_out;
-	if (t->w < 1 || t->h < 1 || t->x0 < 0 || t->y0 < 0 || (int64_t)t->x0 + t->w > W || (int64_t)t->y0 + t->h > H)
-		return set_err(MIJ_E_ARG, "window %d,%d %dx%d outside the %lldx%lld picture of slot %d", t->x0, t->y0, t->w, t->h, (long long)W, (long long)H, slot);
+	const int64_t DW = tr ? H : W, DH = tr ? W : H; /* the displayed picture */
+	if (t->w < 1 || t->h < 1 || t->x0 < 0 || t->y0 < 0 || (int64_t)t->x0 + t->w > DW || (int64_t)t->y0 + t->h > DH)
+		return set_err(MIJ_E_ARG, "window %d,%d %dx%d outside the %lldx%lld displayed picture of slot %d (orientation %d)", t->x0, t->y0, t->w, t->h,
+							(long long)DW, (long long)DH, slot, (int)orient);
+	/* the axes of the window: D's x axis is S's y axis when transposed; an axis S reads backwards is mirrored */
+	const bool mirror_x = tr ? my : mx, mirror_y = tr ? mx : my;
 	const mij_batch::RszCoef *ch = nullptr, *cv = nullptr;
 	if (rz) {
 		if (rz->filter < MIJ_FILTER_BOX || rz->filter > MIJ_FILTER_LANCZOS || rz->reserved != 0 || rz->out_w < 1 || rz->out_w > 16384 || rz->out_h < 1 ||
 			 rz->out_h > 16384)
 			return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor_resized: %dx%d filter %d reserved %d refused", rz->out_w, rz->out_h, rz->filter, rz->reserved);
-		ch = rsz_coef(b, t->w, rz->out_w, rz->filter);
-		cv = rsz_coef(b, t->h, rz->out_h, rz->filter);
+		ch = rsz_coef(b, t->w, rz->out_w, rz->filter, mirror_x);
+		cv = rsz_coef(b, t->h, rz->out_h, rz->filter, mirror_y);
 		if (!ch || !cv)
 			return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor_resized: no coefficients for %dx%d -> %dx%d", t->w, t->h, rz->out_w, rz->out_h);
 		if (!ch->fits || !cv->fits)
@@ -1789,6 +1850,18 @@ static int set_out_tensor(mij_batch *b, int slot, const mij_out_tensor *t, const
 	}
 	mij_batch::TenReq &q = b->ten_req[(size_t)s.ten];
 	q.t = *t;
+	/* into the stored frame: the window's corner in S, and each mirror composed with the flip of its output axis (for a resize, with
+	 * that axis's coefficients mirrored above: resize(mirror(x)) = mirror(resize*(x)) exactly) */
+	q.tr = tr;
+	if (tr) {
+		q.t.x0 = mx ? (int32_t)(W - t->y0 - t->h) : t->y0; /* output rows are stored columns */
+		q.t.y0 = my ? (int32_t)(H - t->x0 - t->w) : t->x0; /* output columns are stored rows */
+	} else {
+		q.t.x0 = mx ? (int32_t)(W - t->x0 - t->w) : t->x0;
+		q.t.y0 = my ? (int32_t)(H - t->y0 - t->h) : t->y0;
+	}
+	q.t.flip_x = (t->flip_x ? 1 : 0) ^ (mirror_x ? 1 : 0);
+	q.t.flip_y = (t->flip_y ? 1 : 0) ^ (mirror_y ? 1 : 0);
 	q.rsz = rz != nullptr;
 	if (rz) {
 		q.r = *rz;
@@ -1805,14 +1878,20 @@ static int set_out_tensor(mij_batch *b, int slot, const mij_out_tensor *t, const
 
 extern "C" int mij_batch_set_out_tensor(mij_batch *b, int slot, const mij_out_tensor *t, const void *table)
 {
-	return set_out_tensor(b, slot, t, nullptr, table);
+	return set_out_tensor(b, slot, t, nullptr, 1, table);
 }
 
 extern "C" int mij_batch_set_out_tensor_resized(mij_batch *b, int slot, const mij_out_tensor *t, const mij_out_resize *r, const void *table)
 {
 	if (!r)
 		return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor_resized: no resize");
-	return set_out_tensor(b, slot, t, r, table);
+	return set_out_tensor(b, slot, t, r, 1, table);
+}
+
+extern "C" int mij_batch_set_out_tensor_oriented(mij_batch *b, int slot, const mij_out_tensor *t, const mij_out_resize *r, int32_t orientation,
+																 const void *table)
+{
+	return set_out_tensor(b, slot, t, r, orientation, table);
 }
 
 extern "C" int mij_batch_timer_begin(mij_batch *b)

@@ -5,7 +5,7 @@ Importing this module imports torch; ``import image_codecs_amd`` alone does not 
 from here on first use)."""
 import torch
 
-from .binding import FILTERS, Batch, Context, HostDecoder, MijError, MIJ_DT_U8, MIJ_DT_F16, MIJ_DT_BF16, MIJ_DT_F32, MIJ_LAYOUT_HWC, MIJ_LAYOUT_CHW
+from .binding import FILTERS, Batch, Context, HostDecoder, MijError, exif_orientation, MIJ_DT_U8, MIJ_DT_F16, MIJ_DT_BF16, MIJ_DT_F32, MIJ_LAYOUT_HWC, MIJ_LAYOUT_CHW
 
 _DT = {torch.uint8: MIJ_DT_U8, torch.float16: MIJ_DT_F16, torch.bfloat16: MIJ_DT_BF16, torch.float32: MIJ_DT_F32}
 _BITS = {torch.uint8: torch.uint8, torch.float16: torch.int16, torch.bfloat16: torch.int16, torch.float32: torch.int32}
@@ -48,6 +48,27 @@ def _flags(v, n, what):
     if len(v) != n:
         raise ValueError("%s has %d entries for %d pictures" % (what, len(v), n))
     return v
+
+
+def _orientations(v, datas):
+    """decode's orientation= as one value 1..8 per picture"""
+    n = len(datas)
+    if v is None:
+        return [1] * n
+    if isinstance(v, str):
+        if v != "exif":
+            raise ValueError("orientation must be None, 'exif', 1..8 or one value per picture (got %r)" % (v,))
+        return [exif_orientation(d) for d in datas]
+    try:
+        vals = [v] * n if isinstance(v, int) else list(v)
+    except TypeError:
+        raise ValueError("orientation must be None, 'exif', 1..8 or one value per picture (got %r)" % (v,)) from None
+    if len(vals) != n:
+        raise ValueError("orientation has %d values for %d pictures" % (len(vals), n))
+    for o in vals:
+        if isinstance(o, bool) or not isinstance(o, int) or not 1 <= o <= 8:
+            raise ValueError("an orientation is an int 1..8 (got %r)" % (o,))
+    return vals
 
 
 def _one_hip_runtime():
@@ -104,14 +125,17 @@ class TensorDecoder:
         return self._batch
 
     def decode(self, datas, *, req_comp=3, crops=None, flip_x=None, flip_y=None, layout="CHW", dtype=torch.float16, mean=None, std=None,
-               out=None, threads=16, size=None, filter="bilinear"):
+               out=None, threads=16, size=None, filter="bilinear", orientation=None):
         """-> (tensor, reasons).  crops: None (the whole picture; every picture the same size) or one (x0, y0, w, h) per picture, all of
         the same w and h.  size: None, or (out_h, out_w): each window is resized to it with filter (box, bilinear, hamming, bicubic or
         lanczos; the exact integer contract of mij_batch_set_out_tensor_resized, Pillow's for one channel, crop first), and windows and
         pictures may then differ in size.  flip_x / flip_y: None, one bool for all, or one per picture (after a resize they reverse the
         resized columns / rows).  The value of channel c's byte v is tensor_tables(C, dtype, mean, std)[c][v].  out: a tensor of the
         right shape and dtype on this device, with any row / plane padding (e.g. a slice of a larger tensor); None allocates one.  A rejected picture leaves its [i] slice untouched (zero in a
-        tensor allocated here) and gets its reason in reasons[i]; reasons[i] is None for a decoded one."""
+        tensor allocated here) and gets its reason in reasons[i]; reasons[i] is None for a decoded one.  orientation: None (the stored
+        pictures), "exif" (each file's EXIF Orientation tag), one int 1..8 for all or one per picture: each picture is first turned into
+        its displayed picture (include/mij.h, mij_batch_set_out_tensor_oriented), and crops, size and the tensor's shape are in its
+        displayed frame."""
         datas = list(datas)
         n = len(datas)
         if layout not in ("CHW", "HWC"):
@@ -127,6 +151,7 @@ class TensorDecoder:
             raise ValueError("crops has %d windows for %d pictures" % (len(crops), n))
         if filter not in FILTERS:
             raise ValueError("filter must be one of %s (got %r)" % (", ".join(FILTERS), filter))
+        orients = _orientations(orientation, datas)
         if size is not None:
             try:
                 size = tuple(int(v) for v in size)
@@ -143,23 +168,25 @@ class TensorDecoder:
                 descs.append(None)
                 reasons[i] = str(e)
         ok = [d for d in descs if d is not None]
+        # displayed sizes: orientations 5..8 swap the axes
+        dsz = [None if d is None else ((d.height, d.width) if orients[i] >= 5 else (d.width, d.height)) for i, d in enumerate(descs)]
         chans = {d.n_out for d in ok}
         if len(chans) > 1:
             raise ValueError("pictures decode to different channel counts %s (pass req_comp)" % sorted(chans))
         if crops is None:
-            sizes = {(d.width, d.height) for d in ok}
+            sizes = {z for z in dsz if z is not None}
             if len(sizes) > 1 and size is None:
                 raise ValueError("pictures of different sizes %s need crops" % sorted(sizes))
-            wins = [None if d is None else (0, 0, d.width, d.height) for d in descs]
+            wins = [None if z is None else (0, 0, z[0], z[1]) for z in dsz]
         else:
             wins = [tuple(int(v) for v in c) for c in crops]
             if any(len(c) != 4 for c in wins):
                 raise ValueError("a crop is (x0, y0, w, h)")
             if len({c[2:] for c in wins}) > 1 and size is None:
                 raise ValueError("crop windows of different sizes %s" % sorted({c[2:] for c in wins}))
-            for i, (c, d) in enumerate(zip(wins, descs)):
-                if c[2] < 1 or c[3] < 1 or c[0] < 0 or c[1] < 0 or (d is not None and (c[0] + c[2] > d.width or c[1] + c[3] > d.height)):
-                    raise ValueError("crop %s of picture %d outside its %dx%d picture" % (c, i, d.width if d else 0, d.height if d else 0))
+            for i, (c, z) in enumerate(zip(wins, dsz)):
+                if c[2] < 1 or c[3] < 1 or c[0] < 0 or c[1] < 0 or (z is not None and (c[0] + c[2] > z[0] or c[1] + c[3] > z[1])):
+                    raise ValueError("crop %s of picture %d outside its %dx%d picture" % (c, i, z[0] if z else 0, z[1] if z else 0))
         whs = {c[2:] for c in wins if c is not None} if size is None else {(size[1], size[0])}
         C = req_comp if req_comp else (chans.pop() if chans else None)
         if out is not None:
@@ -211,10 +238,11 @@ class TensorDecoder:
             x0, y0 = wins[i][0], wins[i][1]
             lay = MIJ_LAYOUT_CHW if layout == "CHW" else MIJ_LAYOUT_HWC
             if size is None:
-                b.set_out_tensor(sl, out.data_ptr() + i * st[0] * es, _DT[dtype], lay, x0, y0, w, h, row_pitch, plane_pitch, fx[i], fy[i], tb)
+                b.set_out_tensor(sl, out.data_ptr() + i * st[0] * es, _DT[dtype], lay, x0, y0, w, h, row_pitch, plane_pitch, fx[i], fy[i], tb,
+                                 orientation=orients[i])
             else:
                 b.set_out_tensor_resized(sl, out.data_ptr() + i * st[0] * es, _DT[dtype], lay, x0, y0, wins[i][2], wins[i][3], w, h, row_pitch,
-                                         plane_pitch, fx[i], fy[i], tb, filter)
+                                         plane_pitch, fx[i], fy[i], tb, filter, orientation=orients[i])
         torch.cuda.current_stream(self.device).synchronize()
         b.submit()
         b.wait()

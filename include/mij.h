@@ -420,6 +420,33 @@ typedef struct {
 int mij_batch_set_out_tensor_resized(mij_batch *b, int slot, const mij_out_tensor *t, const mij_out_resize *r, const void *table);
 
 /*
+ * Oriented tensor output: the request above applied to the displayed picture D instead of the stored picture S (the decoded
+ * H x W x C pixels of the slot).  Orientation o is 1..8, the EXIF / TIFF Orientation tag (mjh_exif_orientation reads it from a
+ * file); in numpy on S:
+ *     o   D                                   D's size (w x h)
+ *     1   S                                   W x H
+ *     2   S[:, ::-1]                          W x H
+ *     3   S[::-1, ::-1]                       W x H
+ *     4   S[::-1]                             W x H
+ *     5   S.transpose(1, 0, 2)                H x W
+ *     6   S[::-1].transpose(1, 0, 2)          H x W      (the usual portrait shot: rotate 90 degrees clockwise to display)
+ *     7   S[::-1, ::-1].transpose(1, 0, 2)    H x W
+ *     8   S[:, ::-1].transpose(1, 0, 2)       H x W
+ * (PIL.ImageOps.exif_transpose for every o).  The request writes exactly what mij_batch_set_out_tensor (r NULL) or
+ * mij_batch_set_out_tensor_resized (r given) writes when applied to D: the window (t->x0, t->y0, t->w, t->h) is in D's coordinates and
+ * must lie inside D; the resize is the contract above run on D's window, horizontal pass first in D's frame; flip_x / flip_y, the
+ * tables, the layout and the pitches are unchanged, the flips still reversing the final output.  The order is orient, crop, resize,
+ * flip, table, store.  Two consequences: for o = 5..8 the first pass of a resize runs along S's columns, and for a mirroring o the
+ * mirror comes before the resize (the coefficients are not mirror-symmetric, so resize(mirror(x)) may differ from mirror(resize(x))).
+ * o = 1 is byte for byte the request of the existing setters.  Every rule of the two setters above holds (one tensor request per slot,
+ * replaced when asked again, forgotten by reset, a refused request keeps the earlier one; pitches, alignment and the one-allocation
+ * check apply to the output extent); MIJ_E_ARG also for o outside 1..8 and for a window outside D, one that fits S but not D included.
+ * Orientations 2..4 run k_out_tensor / k_out_resize with the mirror folded into the window, the flips and the coefficients;
+ * 5..8 run passes of their own (k_out_tensor_t, k_out_resize_t), launched only when such a request exists.
+ */
+int mij_batch_set_out_tensor_oriented(mij_batch *b, int slot, const mij_out_tensor *t, const mij_out_resize *r, int32_t orientation, const void *table);
+
+/*
  * Encoder half (BASELINE config 5): the JPEG writer's colour transform, edge replication, 2x2
  * chroma mean, float AAN forward DCT and quantiser (codec/jpeg_write.c:24-74, :96-118, :283-352)
  * for a batch of images on the GPU.  Input: interleaved 8-bit pixels, comp 1..4 as passed to

@@ -162,6 +162,14 @@ void mjh_ldr_to_hdr_lut(int n_out, float gamma, float scale, float *lut);
  * taps at k[o*ksize .. o*ksize + n) (the rest of the row is zero); with a smaller cap nothing is written. */
 int mjh_resize_coeffs(int in, int out, int filter, int32_t *lo_n, int32_t *k, size_t cap);
 
+/* The EXIF Orientation (tag 0x0112) of a JPEG file in memory, 1..8 (include/mij.h, mij_batch_set_out_tensor_oriented); never fails:
+ * whatever it cannot read gives 1.  Walks the marker segments from SOI by their lengths (0xFF fill bytes allowed before a marker),
+ * stopping at SOS, EOI, a bad length or the end of the buffer.  Only the first APP1 whose payload starts with "Exif\0\0" counts: its
+ * TIFF header (II*\0 or MM\0*) gives the byte order, and only IFD0 is read (IFD1, the thumbnail's, is not), for an entry of tag
+ * 0x0112, type SHORT and count 1.  Every offset is checked against that segment, and a directory that does not fit it gives 1, as
+ * does a value outside 1..8.  stbi_* and the rest of the library ignore the tag, as the reference does. */
+int mjh_exif_orientation(const uint8_t *buf, int len);
+
 #ifdef __cplusplus
 }
 #endif
