@@ -732,6 +732,12 @@ class Batch:
         _check(L.mij_batch_entropy_run(self._h, fb, n, C.byref(cnt)), "mij_batch_entropy_run")
         return list(fb[:cnt.value])
 
+    def entropy_anomaly(self, slot):
+        """tests: OR of the GPU walk's anomaly words of the slot's scans after entropy_run (0: kept; bits as listed in mij.h)."""
+        L = lib()
+        L.mij_batch_entropy_anomaly.argtypes = [C.c_void_p, C.c_int]
+        return _check(L.mij_batch_entropy_anomaly(self._h, int(slot)), "mij_batch_entropy_anomaly")
+
     def slot_coef_bytes(self, slot):
         """1 when the slot's coefficients sit in HBM as compact planes (the default), 0 for the int16 tile layout."""
         return lib().mij_batch_slot_coef_bytes(self._h, int(slot))
@@ -836,11 +842,18 @@ class Batch:
             raise MijError("mjh_decode_batch: %s" % lib().mij_last_error().decode())
         out_slots = list(slots)
         # mirror the descriptors of the slots the C side added
+        self._mirror_slots(datas, req_comp, out_slots, first)
+        return rc, out_slots, [r.decode() if r else None for r in reasons]
+
+    def _mirror_slots(self, datas, req_comp, out_slots, first):
+        """Mirror the descriptors of the slots the C side added, BY SLOT INDEX: a stream rejected in slot 0 is reported as -1 - 0, which
+        reads like a rejected header (no slot), so counting the reported slots would shift every later descriptor by one."""
         for i, sl in enumerate(out_slots):
             real = sl if sl >= 0 else (-1 - sl if sl < -1 else None)
             if real is not None and real >= first:
-                self.descs.append((datas[i], req_comp))  # header probed when somebody asks (fetch, staging)
-        return rc, out_slots, [r.decode() if r else None for r in reasons]
+                while len(self.descs) <= real:
+                    self.descs.append(None)
+                self.descs[real] = (datas[i], req_comp)  # header probed when somebody asks (fetch, staging)
 
     def decode_jpegs_gpu_begin(self, datas, req_comp=0, threads=1):
         """mjh_decode_batch_gpu_begin: headers + unstuffing on the host threads, GPU walk queued; returns a job
@@ -865,10 +878,7 @@ class Batch:
         if rc < 0:
             raise MijError("mjh_decode_batch_gpu_end: %s" % lib().mij_last_error().decode())
         out_slots = list(job["slots"])
-        for i, sl in enumerate(out_slots):
-            real = sl if sl >= 0 else (-1 - sl if sl < -1 else None)
-            if real is not None and real >= job["first"]:
-                self.descs.append((job["datas"][i], job["req"]))
+        self._mirror_slots(job["datas"], job["req"], out_slots, job["first"])
         return rc, out_slots, [r.decode() if r else None for r in job["reasons"]]
 
     def set_flags(self, slot, flags):

@@ -384,13 +384,13 @@ static inline void reg_grow(mjh_decoder *d, bitreg *b)
 	*b = reg_load(d);
 }
 
-/* codec/jpeg.c:193-243 */
-static inline int huff_decode_r(mjh_decoder *d, const mjh_huff *h, bitreg *b)
+/* codec/jpeg.c:201-243: stbi__jpeg_huff_decode behind its refill, for callers that have already topped the register up where the
+ * reference tops it up.  Refilling a second time is not harmless: a first refill that stopped at a marker leaves few bits, the
+ * reference then fails `size > code_bits`, and a second refill would zero-fill the register and decode on. */
+static inline int huff_decode_norefill(const mjh_huff *h, bitreg *b)
 {
 	unsigned top, temp;
 	int k, c;
-	if (b->bits < 16)
-		reg_grow(d, b);
 	top = b->buf >> (32 - MJH_FAST_BITS);
 	k = h->fast[top];
 	if (k < 255) {
@@ -415,6 +415,14 @@ static inline int huff_decode_r(mjh_decoder *d, const mjh_huff *h, bitreg *b)
 	b->bits -= k;
 	b->buf <<= k;
 	return h->values[c & 255];
+}
+
+/* codec/jpeg.c:193-243 */
+static inline int huff_decode_r(mjh_decoder *d, const mjh_huff *h, bitreg *b)
+{
+	if (b->bits < 16)
+		reg_grow(d, b);
+	return huff_decode_norefill(h, b);
 }
 
 /* codec/jpeg.c:250-265 */
@@ -755,22 +763,42 @@ static inline uint64_t bitrev64(uint64_t x)
 	return x;
 }
 
+/* n single stbi__jpeg_get_bit reads (codec/jpeg.c:280-289) in as few steps as the register allows, the first bit read highest.  The
+ * register is topped up exactly where the single reads top it up -- when it is empty and one more bit is wanted -- so not only the bits
+ * but also the reader's state afterwards (code_bits, nomore, the byte position) are the reference's.  That state is visible: once a
+ * refill has met a marker, it decides whether a later symbol fails the `size > code_bits` test of stbi__jpeg_huff_decode.  (Refilling at
+ * "fewer than n bits" instead returned the same bits, but met the marker at another moment and so accepted or refused other streams.) */
+static inline __attribute__((always_inline)) uint64_t get_single_bits_s(mjh_decoder *d, int n, uint32_t *buf, int *bits)
+{
+	uint64_t v = 0;
+	while (n > 0) {
+		int take;
+		if (*bits < 1) {
+			grow_s(d, buf, bits);
+			if (*bits < 1) { /* the refill met a marker and added nothing: this read takes bit 31 as it stands (:285-287) */
+				v = (v << 1) | (*buf >> 31);
+				*buf <<= 1;
+				--*bits;
+				--n;
+				continue;
+			}
+		}
+		take = n < *bits ? n : *bits; /* 1..32 */
+		v = (v << take) | (((uint64_t)*buf << take) >> 32);
+		*buf = (uint32_t)((uint64_t)*buf << take);
+		*bits -= take;
+		n -= take;
+	}
+	return v;
+}
+
 /* The correction bits of the already non-zero coefficients `where` (a zigzag-order mask, not empty), which the reference reads one
  * get_bit per coefficient in ascending order (codec/jpeg.c:497-505, :536-553): all of them in one or a few reads, the first bit read
- * deposited at the lowest position.  Returns the mask of the coefficients whose bit was set.  The bit register is a first-in-first-out
- * of the stream's bits followed by zeros once the data has run out, so reading n bits at once returns what n single reads return. */
+ * deposited at the lowest position.  Returns the mask of the coefficients whose bit was set. */
 static inline uint64_t read_corrections(mjh_decoder *d, uint64_t where, bitreg *b)
 {
 	const int n = popcnt64(where);
-	uint64_t bits = 0;
-	int left = n;
-	if (n == 1)
-		return get_bit_r(d, b) ? where : 0;
-	while (left > 16) {
-		bits = (bits << 16) | (uint64_t)get_bits_r(d, 16, b);
-		left -= 16;
-	}
-	bits = (bits << left) | (uint64_t)get_bits_r(d, left, b);
+	const uint64_t bits = get_single_bits_s(d, n, &b->buf, &b->bits);
 	return pdep64(bitrev64(bits) >> (64 - n), where);
 }
 
@@ -793,7 +821,7 @@ static inline void apply_corrections(int16_t *blk, uint64_t corr, int bit)
 static __attribute__((noinline)) int refine_symbol_slow(mjh_decoder *d, const mjh_huff *hac)
 {
 	bitreg b = reg_load(d);
-	int rs = huff_decode_r(d, hac, &b), r, s;
+	int rs = huff_decode_norefill(hac, &b), r, s; /* the caller has refilled */
 	if (rs < 0) {
 		reg_store(d, &b);
 		(void)fail(d, "bad huffman code");
@@ -873,22 +901,8 @@ static __attribute__((noinline)) int refine_symbols_wide(mjh_decoder *d, int16_t
 				k = spec_end + 1;
 			if (passed) {
 				/* read_corrections on the locals: the first bit read belongs to the lowest coefficient */
-				int n = popcnt64(passed);
-				uint64_t v = 0;
-				while (n > 16) {
-					if (bits < 16)
-						grow_s(d, &buf, &bits);
-					v = (v << 16) | (buf >> 16);
-					buf <<= 16;
-					bits -= 16;
-					n -= 16;
-				}
-				if (bits < n)
-					grow_s(d, &buf, &bits);
-				v = (v << n) | (uint64_t)(((uint64_t)buf << n) >> 32);
-				buf <<= n;
-				bits -= n;
-				n = popcnt64(passed);
+				const int n = popcnt64(passed);
+				const uint64_t v = get_single_bits_s(d, n, &buf, &bits);
 				corr |= pdep64(bitrev64(v) >> (64 - n), passed);
 			}
 		}
@@ -1009,7 +1023,7 @@ static int decode_block_prog_ac(mjh_decoder *d, int16_t *blk, const mjh_huff *ha
 						r = 64; /* run to the end of the band */
 					}
 				} else {
-					int rs = huff_decode_r(d, hac, &b);
+					int rs = huff_decode_norefill(hac, &b); /* refilled above */
 					if (rs < 0) {
 						reg_store(d, &b);
 						return fail(d, "bad huffman code");

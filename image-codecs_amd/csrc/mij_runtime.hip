@@ -2549,6 +2549,25 @@ extern "C" int mij_batch_entropy_run(mij_batch *b, int *fallback, int cap, int *
 	return mij_batch_entropy_finish(b, fallback, cap, n_fallback);
 }
 
+extern "C" int mij_batch_entropy_anomaly(mij_batch *b, int slot)
+{
+	if (!b || !b->es || slot < 0 || slot >= (int)b->slots.size())
+		return set_err(MIJ_E_ARG, "mij_batch_entropy_anomaly: bad argument");
+	const EsArena *e = b->es;
+	if (e->in_flight)
+		return set_err(MIJ_E_ARG, "mij_batch_entropy_anomaly: the walk has not been finished");
+	uint32_t bad = 0;
+	bool found = false;
+	for (size_t k = 0; k < e->scan_slot.size(); ++k)
+		if (e->scan_slot[k] == slot) {
+			bad |= e->h_verdict[k];
+			found = true;
+		}
+	if (!found)
+		return set_err(MIJ_E_ARG, "slot %d was not walked on the GPU", slot);
+	return (int)(bad & 0x7fffffffu);
+}
+
 extern "C" int mij_batch_fallback_prepare(mij_batch *b, int slot)
 {
 	if (!b || slot < 0 || slot >= (int)b->slots.size())

@@ -8,6 +8,8 @@ call, keyed by the SHA-256 of the call and its input:
   load/<req>/<pixels>   "fail:<reason>", or "ok:<shape>:<comp>:<SHA-256 of the pixels>" ("ok" alone where pixels are not compared)
   encode/<shape>/<q>    "<length>:<SHA-256>" of the writer's stream
   idct                  "<length>:<SHA-256>" of the 8x8 output block
+  verdicts/<req>/<group> one entry per generated list of streams (tests/stream_cases.py), keyed over all of them: one character per
+                        stream ('0' ok, '1'.. a reason) and the reasons behind it -- verdict and reason only, no pixels
 """
 import os
 import subprocess
@@ -23,6 +25,8 @@ TESTS = [
     "tests/test_host_cpu.py::test_host_writer_vs_live_reference_seeded",
     "tests/test_host_cpu.py::test_progressive_host_walk_vs_oracle_fuzz",
     "tests/test_host_cpu.py::test_third_pair_of_huffman_tables_host_walk",
+    "tests/test_stream_ends_host.py::test_progressive_cuts_host_walk_vs_oracle",
+    "tests/test_stream_ends_host.py::test_baseline_stream_ends_host_walk_and_extract_gate",
     "tests/test_progressive_writer.py::test_progressive_stream_carries_the_same_coefficients",
     "tests/test_progressive_writer.py::test_writer_streams_pin_the_oracle_to_the_live_reference",
 ]

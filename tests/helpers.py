@@ -106,7 +106,9 @@ class Oracle:
         return o[: len(y) * step].reshape(-1, step).copy()
 
     def coef(self, data, req=0):
-        cap = np.zeros(1 << 22, dtype=np.int16)
+        if not hasattr(self, "_cap"):
+            self._cap = np.zeros(1 << 22, dtype=np.int16)  # allocated once: only the n elements the call reports are read
+        cap = self._cap
         n = C.c_long()
         x, y, c = C.c_int(), C.c_int(), C.c_int()
         p = self.L.orc_decode_capture(bytes(data), len(data), x, y, c, req, cap.ctypes.data, cap.size, C.byref(n))
@@ -169,6 +171,23 @@ class Reference:
 REF_DIGESTS = os.path.join(ROOT, "tests", "golden", "reference_digests.npz")
 
 
+def primed_load(ref, data, req=0):
+    """Reference.load behind a failing load of garbage: where the reference fails without calling stbi__err its stbi_failure_reason() keeps
+    what an earlier call left -- primed like this, that is "unknown image type", which no stream with whole headers earns itself, and it is
+    reported as a reason of None."""
+    ref.load(b"garbage-not-a-jpeg", 0)
+    r = ref.load(data, req)
+    if r[0] == "fail" and r[1] == "unknown image type":
+        return "fail", None, None
+    return r
+
+
+def verdict_of(res):
+    """a load result as verdict and reason only: "ok" or "fail:<reason>" """
+    return "ok" if res[0] == "ok" else "fail:%s" % res[1]
+
+
+
 def digest_load(res, pixels=True):
     """a load result ('ok', pixels, comp) / ('fail', reason, None) as one string: kind, reason or shape + comp + SHA-256 of the pixels"""
     import hashlib
@@ -224,6 +243,31 @@ class StoredReference:
     def load(self, data, req=0, pixels=True):
         """digest_load of the reference's stbi_load_from_memory(data, req)"""
         return self._answer("load/%d/%d" % (req, int(pixels)), data, lambda r: digest_load(r.load(data, req), pixels))
+
+    def verdicts(self, group, datas, req=0):
+        """What the reference answers for a generated list of streams, verdict and reason only: -> ["ok" | "fail:<reason>", ...].  One stored
+        entry per list (the generators are deterministic), keyed by the SHA-256 over the group name and every stream, so a changed case list
+        fails loudly; the value is one character per stream ('0': ok, '1'...: index into the reasons that follow, each behind a '|')."""
+        import hashlib
+        h = hashlib.sha256()
+        for d in datas:
+            h.update(hashlib.sha256(bytes(d)).digest())
+
+        def compute(ref):
+            reasons, chars = [], []
+            for d in datas:
+                v = verdict_of(primed_load(ref, d, req))
+                if v == "ok":
+                    chars.append("0")
+                    continue
+                if v not in reasons:
+                    reasons.append(v)
+                chars.append(chr(ord("1") + reasons.index(v)))
+            return "".join(chars) + "".join("|" + r for r in reasons)
+
+        parts = self._answer("verdicts/%d/%s" % (req, group), h.digest(), compute).split("|")
+        assert len(parts[0]) == len(datas)
+        return ["ok" if c == "0" else parts[1 + ord(c) - ord("1")] for c in parts[0]]
 
     def encode(self, img, q):
         """digest_bytes of the reference writer's stream"""
