@@ -900,9 +900,25 @@ class Batch:
     def wait(self):
         _check(lib().mij_batch_wait(self._h), "mij_batch_wait")
 
+    def set_scale(self, slot, denom):
+        """mij_batch_set_scale: decode the slot at 1/denom size (1, 2, 4 or 8) straight from its coefficients; before upload and
+        before the slot's tensor request.  Everything that reads the slot's pixels then sees the out_size(slot) picture."""
+        L = lib()
+        L.mij_batch_set_scale.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        _check(L.mij_batch_set_scale(self._h, int(slot), int(denom)), "mij_batch_set_scale")
+
+    def out_size(self, slot):
+        """(width, height) of the slot's stored picture: the file's, or the reduced one (mij_batch_slot_out_size)."""
+        L = lib()
+        L.mij_batch_slot_out_size.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        w, h = C.c_int(), C.c_int()
+        _check(L.mij_batch_slot_out_size(self._h, int(slot), C.byref(w), C.byref(h)), "mij_batch_slot_out_size")
+        return w.value, h.value
+
     def fetch(self, slot):
         d = self._desc(slot)
-        out = np.empty((d.height, d.width, d.n_out), dtype=np.uint8)
+        w, h = self.out_size(slot)
+        out = np.empty((h, w, d.n_out), dtype=np.uint8)
         _check(lib().mij_batch_fetch(self._h, int(slot), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.size)), "mij_batch_fetch")
         return out
 

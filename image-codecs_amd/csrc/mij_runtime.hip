@@ -17,6 +17,7 @@
 #include "mij.h"
 #include "mij_host.h"
 #include "mij_kernels.h"
+#include "mij_scaled_kernels.h"
 
 using namespace mij;
 
@@ -54,10 +55,10 @@ extern "C" int mij_device_count(void)
 /* ------------------------------------------------------------------ decode kernel families */
 
 /* kernel families of a launch plan, in launch order.  MK_RS_FAST + RS_*: pass 2 compiled per resampler (k_resample_fast) */
-enum { MK_PLANES = 0, MK_RESAMPLE, MK_RS_FAST, MK_420 = MK_RS_FAST + RS_KINDS, MK_422, MK_444, MK_GREY, MK_440, MK_420W, MK_440W /* k_fused420w / k_fused440w: 512 threads, wide pictures */, MK_420X /* 1024 threads: one workgroup per CU */, MK_420S, MK_420T /* 128 / 64 threads: narrow pictures */, MK_422W, MK_422X, MK_422S, MK_422T /* k_fused422 with 512 / 1024 / 128 / 64 threads */, MK_1X1C /* k_fused1x1c: RGB-tagged / CMYK / YCCK at 1x1 */, MK_420C, MK_440C /* column segments: a row of MCUs beyond a CU's LDS */, MK_KINDS };
+enum { MK_PLANES = 0, MK_RESAMPLE, MK_RS_FAST, MK_420 = MK_RS_FAST + RS_KINDS, MK_422, MK_444, MK_GREY, MK_440, MK_420W, MK_440W /* k_fused420w / k_fused440w: 512 threads, wide pictures */, MK_420X /* 1024 threads: one workgroup per CU */, MK_420S, MK_420T /* 128 / 64 threads: narrow pictures */, MK_422W, MK_422X, MK_422S, MK_422T /* k_fused422 with 512 / 1024 / 128 / 64 threads */, MK_1X1C /* k_fused1x1c: RGB-tagged / CMYK / YCCK at 1x1 */, MK_420C, MK_440C /* column segments: a row of MCUs beyond a CU's LDS */, MK_SCALED /* + SC_*: reduced-size decode, k_scaled per layout */, MK_KINDS = MK_SCALED + SC_LAYOUTS };
 
 /* A family's kernels per variant = 4 * (n_out == 4) + 2 * wide IDCT + compact planes (k_resample_fast: 4 * (n_out == 4) + 2 * YCbCr
- * colour).  Every decode kernel takes (const DevImage *, const Work *, const uint8_t *in, uint8_t *out); io says which arenas in and
+ * colour; k_scaled: 2 * (log2 of the scale - 1) + compact planes).  Every decode kernel takes (const DevImage *, const Work *, const uint8_t *in, uint8_t *out); io says which arenas in and
  * out are. */
 enum { MK_VARIANTS = 8 };
 enum Arena { COEF_OUT, COEF_PLANES, PLANES_OUT };
@@ -72,6 +73,7 @@ struct Family {
 	{ MIJ_K(K<3, false, false>), MIJ_K(K<3, false, true>), MIJ_K(K<3, true, false>), MIJ_K(K<3, true, true>),                      \
 	  MIJ_K(K<4, false, false>), MIJ_K(K<4, false, true>), MIJ_K(K<4, true, false>), MIJ_K(K<4, true, true>) }
 #define MIJ_WB(K) { MIJ_K(K<false, false>), MIJ_K(K<false, true>), MIJ_K(K<true, false>), MIJ_K(K<true, true>) }
+#define MIJ_SC(Y) { MIJ_K(k_scaled<Y, 2, false>), MIJ_K(k_scaled<Y, 2, true>), MIJ_K(k_scaled<Y, 4, false>), MIJ_K(k_scaled<Y, 4, true>), MIJ_K(k_scaled<Y, 8, false>), MIJ_K(k_scaled<Y, 8, true>) }
 #define MIJ_RSF(R)                                                                                                                  \
 	{ MIJ_K(k_resample_fast<R, false, 3>), nullptr, MIJ_K(k_resample_fast<R, true, 3>), nullptr,                                   \
 	  MIJ_K(k_resample_fast<R, false, 4>), nullptr, MIJ_K(k_resample_fast<R, true, 4>), nullptr }
@@ -101,7 +103,13 @@ static const Family families[MK_KINDS] = {
 	/* MK_1X1C */ {256, COEF_OUT, false, MIJ_NWB(k_fused1x1c)},
 	/* MK_420C */ {MIJ_F420C_NT, COEF_OUT, true, MIJ_NWB(k_fused420c)},
 	/* MK_440C */ {MIJ_F420C_NT, COEF_OUT, true, MIJ_NWB(k_fused440c)},
+	/* MK_SCALED + SC_Y, SC_444, SC_420, SC_422 */
+	{256, COEF_OUT, false, MIJ_SC(SC_Y)},
+	{256, COEF_OUT, false, MIJ_SC(SC_444)},
+	{256, COEF_OUT, false, MIJ_SC(SC_420)},
+	{256, COEF_OUT, false, MIJ_SC(SC_422)},
 };
+#undef MIJ_SC
 #undef MIJ_RSF
 #undef MIJ_WB
 #undef MIJ_NWB
@@ -238,7 +246,7 @@ extern "C" int mij_ctx_info(const mij_ctx *ctx, char *arch, size_t arch_len, int
 /* ------------------------------------------------------------------ batch */
 
 /* the kernel family the last upload chose for a slot (mij_batch_slot_path) */
-enum SlotPath { PATH_NONE = 0, PATH_420, PATH_TWO_PASS, PATH_444, PATH_422, PATH_GREY, PATH_440, PATH_1X1C };
+enum SlotPath { PATH_NONE = 0, PATH_420, PATH_TWO_PASS, PATH_444, PATH_422, PATH_GREY, PATH_440, PATH_1X1C, PATH_SCALED };
 
 /* what classify chose for a slot: the path, the family (MK_*) and variant whose work list takes its items (two-pass: pass 2's),
  * column segments per band, and the LDS of a whole row of MCUs (the band kernels) */
@@ -257,10 +265,16 @@ struct Slot {
 	int dev_coef;      /* 1: the GPU entropy stage wrote the coefficient planes in HBM; nothing to upload */
 	int es_index;      /* index into the entropy arena's scan list, or -1 */
 	int coef_bytes_fmt; /* 1: compact planes in HBM (low bytes + escapes + DC array), 0: int16 tile layout */
-	Choice choice;     /* of the last upload; path 0 none, 1 fused 4:2:0, 2 two-pass, 3 fused 4:4:4, 4 fused 4:2:2, 5 fused grey, 6 fused 4:4:0, 7 fused 1x1 colour */
+	Choice choice;     /* of the last upload; path 0 none, 1 fused 4:2:0, 2 two-pass, 3 fused 4:4:4, 4 fused 4:2:2, 5 fused grey, 6 fused 4:4:0, 7 fused 1x1 colour, 8 reduced-size */
 	int f32;           /* float output: index of the slot's request (mij_batch::f32_req), -1 none */
 	int ten;           /* tensor output: index of the slot's request (mij_batch::ten_req), -1 none */
+	int scale;         /* reduced-size decode (mij_batch_set_scale): 1, 2, 4 or 8; the stored picture is out_w(s) x out_h(s) */
 };
+
+/* the stored picture of a slot: what every consumer of its pixels sees */
+static inline int out_w(const Slot &s) { return mij_scaled_dim(s.desc.width, s.scale); }
+static inline int out_h(const Slot &s) { return mij_scaled_dim(s.desc.height, s.scale); }
+static inline size_t out_px_bytes(const Slot &s) { return (size_t)s.desc.n_out * (size_t)out_w(s) * (size_t)out_h(s); }
 
 struct Work4 { /* WorkBand and WorkIdct are both four u32 */
 	uint32_t a, b, c, d;
@@ -588,6 +602,7 @@ static int add_common(mij_batch *b, const mij_image_desc *d, int clone_of, bool 
 	s.choice = Choice();
 	s.f32 = -1;
 	s.ten = -1;
+	s.scale = 1;
 	if (clone_of < 0) {
 		if (b->stage_used + cbytes > b->stage_cap) {
 			if (!lazy_stage)
@@ -692,6 +707,57 @@ extern "C" int mij_batch_set_flags(mij_batch *b, int slot, uint32_t flags)
 	return MIJ_OK;
 }
 
+/* Which k_scaled layout (SC_*) decodes a picture at reduced size, or -1: one component; or three-component YCbCr (its luma alone when
+ * fewer than three channels are asked for) whose luma has the picture's resolution and whose chroma is 4:4:4, 4:2:0 or 4:2:2 -- the
+ * layouts where every transform length N * h_max / h, N * v_max / v stays within 8 and all components land on one grid. */
+static int scaled_layout(const mij_image_desc &d)
+{
+	if ((uint64_t)d.width * d.height * d.n_out >= 0xfffffff0ull)
+		return -1;
+	if (d.ncomp == 1 && d.color == MIJ_COLOR_GREY)
+		return SC_Y;
+	if (d.ncomp != 3 || (d.color != MIJ_COLOR_YCBCR && d.color != MIJ_COLOR_GREY) || (d.color == MIJ_COLOR_GREY && d.n_out >= 3))
+		return -1;
+	if (d.comp[0].h != d.h_max || d.comp[0].v != d.v_max || d.comp[1].h != 1 || d.comp[1].v != 1 || d.comp[2].h != 1 || d.comp[2].v != 1)
+		return -1;
+	const int lay = (d.h_max == 1 && d.v_max == 1) ? SC_444 : (d.h_max == 2 && d.v_max == 2) ? SC_420 : (d.h_max == 2 && d.v_max == 1) ? SC_422 : -1;
+	return (lay < 0 || d.n_out >= 3) ? lay : SC_Y;
+}
+
+extern "C" int mij_batch_set_scale(mij_batch *b, int slot, int denom)
+{
+	if (!b || slot < 0 || slot >= (int)b->slots.size())
+		return set_err(MIJ_E_ARG, "mij_batch_set_scale: bad slot");
+	if (b->uploaded)
+		return set_err(MIJ_E_STATE, "mij_batch_set_scale after mij_batch_upload");
+	Slot &s = b->slots[(size_t)slot];
+	if (s.desc.flags & MIJ_FLAG_SKIP)
+		return set_err(MIJ_E_STATE, "slot %d was rejected by the host stage", slot);
+	if (denom != 1 && denom != 2 && denom != 4 && denom != 8)
+		return set_err(MIJ_E_ARG, "mij_batch_set_scale: denominator %d is not 1, 2, 4 or 8", denom);
+	if (denom > 1 && scaled_layout(s.desc) < 0)
+		return set_err(MIJ_E_ARG, "mij_batch_set_scale: slot %d cannot be decoded at reduced size (grey, or YCbCr 4:4:4 / 4:2:0 / 4:2:2 only; "
+										  "%d components, colour mode %d, luma %dx%d of %dx%d)", slot, s.desc.ncomp, s.desc.color, s.desc.comp[0].h, s.desc.comp[0].v, s.desc.h_max, s.desc.v_max);
+	if (denom > 1 && s.f32 >= 0)
+		return set_err(MIJ_E_ARG, "mij_batch_set_scale: slot %d has a float output request; float output of reduced pictures is not supported", slot);
+	if (denom != s.scale && s.ten >= 0)
+		return set_err(MIJ_E_STATE, "mij_batch_set_scale: slot %d already has a tensor request for its %dx%d picture; set the scale first", slot, out_w(s), out_h(s));
+	s.scale = denom;
+	return MIJ_OK;
+}
+
+extern "C" int mij_batch_slot_out_size(const mij_batch *b, int slot, int *w, int *h)
+{
+	if (!b || slot < 0 || slot >= (int)b->slots.size())
+		return set_err(MIJ_E_ARG, "mij_batch_slot_out_size: bad slot");
+	const Slot &s = b->slots[(size_t)slot];
+	if (w)
+		*w = out_w(s);
+	if (h)
+		*h = out_h(s);
+	return MIJ_OK;
+}
+
 extern "C" int mij_batch_set_color(mij_batch *b, int slot, int color)
 {
 	if (!b || slot < 0 || slot >= (int)b->slots.size())
@@ -702,6 +768,8 @@ extern "C" int mij_batch_set_color(mij_batch *b, int slot, int color)
 	int rc = check_desc(&d);
 	if (rc != MIJ_OK)
 		return rc;
+	if (s.scale > 1 && scaled_layout(d) < 0)
+		return set_err(MIJ_E_ARG, "mij_batch_set_color: slot %d is decoded at 1/%d size, which colour mode %d does not support", slot, s.scale, color);
 	s.desc.color = color;
 	s.dev.color = color;
 	b->uploaded = b->launched = false;
@@ -801,6 +869,8 @@ static Choice classify(const mij_batch *b, const Slot &s)
 	const int o4 = d.n_out == 4 ? 4 : 0, var = o4 | ((d.flags & MIJ_FLAG_WIDE_IDCT) ? 2 : 0) | (s.coef_bytes_fmt ? 1 : 0);
 	if (d.flags & MIJ_FLAG_SKIP) /* rejected by the host stage after it got a slot */
 		return Choice();
+	if (s.scale > 1) /* reduced-size decode: one family per layout, whatever force_generic says (the two-pass path has no such form) */
+		return Choice{PATH_SCALED, MK_SCALED + scaled_layout(d), (s.scale == 2 ? 0 : (s.scale == 4 ? 2 : 4)) | (s.coef_bytes_fmt ? 1 : 0)};
 	if (!b->force_generic) {
 		const bool rgb_out = d.n_out == 3 || d.n_out == 4;
 		const bool ycc = d.ncomp == 3 && d.color == MIJ_COLOR_YCBCR && rgb_out && d.comp[1].h == 1 && d.comp[1].v == 1 && d.comp[2].h == 1 && d.comp[2].v == 1;
@@ -967,7 +1037,7 @@ static void dev_tensor(DevTensor &d, const mij_batch::TenReq &q, const Slot &s)
 	d.dst = (uint64_t)(uintptr_t)q.t.dst;
 	d.row_pitch = q.t.row_pitch;
 	d.plane_pitch = q.t.layout == MIJ_LAYOUT_CHW ? q.t.plane_pitch : 0;
-	d.src_w = (uint32_t)s.desc.width;
+	d.src_w = (uint32_t)out_w(s);
 	d.n_out = (uint32_t)s.desc.n_out;
 	d.x0 = (uint32_t)q.t.x0;
 	d.y0 = (uint32_t)q.t.y0;
@@ -1316,6 +1386,12 @@ static void plan_decode(mij_batch *b, Plan &p)
 		case PATH_1X1C:
 			push_blocks(L, (uint32_t)i, d, 0);
 			break;
+		case PATH_SCALED: { /* 256 MCUs a workgroup; the luma-only form: 256 luma blocks */
+			const uint32_t nm = c.kind == MK_SCALED + SC_Y ? (uint32_t)(d.comp[0].bw * d.comp[0].bh) : (uint32_t)(d.mcu_x * d.mcu_y);
+			for (uint32_t f = 0; f < nm; f += 256)
+				L.push_back(Work4{(uint32_t)i, 0u, f, 0u});
+			break;
+		}
 		default: { /* PATH_TWO_PASS: pass 2's rows in L, pass 1's blocks in the MK_PLANES list */
 			/* the vs == 2 forms of k_resample_fast take item r as output rows r-1 .. r+2 (row pairs around a chroma row) */
 			const uint32_t r_end = (uint32_t)d.height + ((c.kind == MK_RS_FAST + RS_V2 || c.kind == MK_RS_FAST + RS_HV2) ? 2u : 0u);
@@ -1464,6 +1540,9 @@ extern "C" int mij_batch_upload(mij_batch *b)
 	HIP_TRY(hipSetDevice(b->ctx->device));
 	if (b->slots.empty())
 		return set_err(MIJ_E_STATE, "batch is empty");
+	for (size_t i = 0; i < b->slots.size(); ++i) /* flags and colour may have changed since mij_batch_set_scale */
+		if (b->slots[i].scale > 1 && !(b->slots[i].desc.flags & MIJ_FLAG_SKIP) && scaled_layout(b->slots[i].desc) < 0)
+			return set_err(MIJ_E_ARG, "mij_batch_upload: slot %zu cannot be decoded at 1/%d size", i, b->slots[i].scale);
 	Plan p;
 	int rc;
 	if ((rc = plane_formats(b)) != MIJ_OK || (rc = l1_prepack(b)) != MIJ_OK)
@@ -1557,7 +1636,7 @@ extern "C" int mij_batch_fetch(mij_batch *b, int slot, uint8_t *dst, size_t dst_
 	const Slot &s = b->slots[(size_t)slot];
 	if (s.desc.flags & MIJ_FLAG_SKIP)
 		return set_err(MIJ_E_STATE, "slot %d was rejected by the host stage", slot);
-	const size_t bytes = (size_t)s.desc.n_out * s.desc.width * s.desc.height;
+	const size_t bytes = out_px_bytes(s);
 	if (dst_bytes < bytes)
 		return set_err(MIJ_E_ARG, "destination too small (%zu < %zu)", dst_bytes, bytes);
 	HIP_TRY(hipSetDevice(b->ctx->device));
@@ -1654,6 +1733,8 @@ extern "C" int mij_batch_set_out_f32(mij_batch *b, int slot, const float *lut)
 	Slot &s = b->slots[(size_t)slot];
 	if (s.desc.flags & MIJ_FLAG_SKIP)
 		return set_err(MIJ_E_STATE, "slot %d was rejected by the host stage", slot);
+	if (s.scale > 1)
+		return set_err(MIJ_E_ARG, "mij_batch_set_out_f32: slot %d is decoded at 1/%d size; float output of reduced pictures is not supported", slot, s.scale);
 	if (s.f32 < 0) {
 		const size_t need = mij_image_out_f32_bytes(&s.desc);
 		if (!b->d_f32 || b->f32_used + need > b->f32_cap)
@@ -1804,7 +1885,7 @@ static int set_out_tensor(mij_batch *b, int slot, const mij_out_tensor *t, const
 	if (orient < 1 || orient > 8)
 		return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor_oriented: orientation %d is not 1..8", (int)orient);
 	const bool tr = orient_tr[orient], mx = orient_mx[orient], my = orient_my[orient];
-	const int64_t W = s.desc.width, H = s.desc.height, C = s.desc.n_out;
+	const int64_t W = out_w(s), H = out_h(s), C = s.desc.n_out; /* the stored picture: reduced when the slot has a scale */
 	const int64_t DW = tr ? H : W, DH = tr ? W : H; /* the displayed picture */
 	if (t->w < 1 || t->h < 1 || t->x0 < 0 || t->y0 < 0 || (int64_t)t->x0 + t->w > DW || (int64_t)t->y0 + t->h > DH)
 		return set_err(MIJ_E_ARG, "window %d,%d %dx%d outside the %lldx%lld displayed picture of slot %d (orientation %d)", t->x0, t->y0, t->w, t->h,
@@ -1940,7 +2021,7 @@ extern "C" int mij_batch_hash_out(mij_batch *b, int slot, uint64_t *hash)
 	if (!b || slot < 0 || slot >= (int)b->slots.size() || !hash)
 		return set_err(MIJ_E_ARG, "bad argument");
 	const Slot &s = b->slots[(size_t)slot];
-	const size_t bytes = (size_t)s.desc.n_out * s.desc.width * s.desc.height;
+	const size_t bytes = out_px_bytes(s);
 	std::vector<uint8_t> tmp(bytes);
 	int rc = mij_batch_fetch(b, slot, tmp.data(), bytes);
 	if (rc != MIJ_OK)
@@ -1966,6 +2047,14 @@ __global__ __launch_bounds__(256) void k_count_diff(const uint4 *__restrict__ a,
 		atomicAdd(out, (unsigned long long)bad);
 }
 
+/* the last, partial 16-byte word of two reduced pictures: one more differing word when any of its n bytes differ */
+__global__ __launch_bounds__(64) void k_count_diff_tail(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, uint32_t n, unsigned long long *__restrict__ out)
+{
+	const bool bad = threadIdx.x < n && a[threadIdx.x] != b[threadIdx.x];
+	if (__builtin_amdgcn_ballot_w64(bad) != 0ull && threadIdx.x == 0)
+		atomicAdd(out, 1ull);
+}
+
 extern "C" int mij_batch_diff_slots(mij_batch *b, const int *sa, const int *sb, int n, uint64_t *ndiff)
 {
 	if (!b || !sa || !sb || !ndiff || n < 0)
@@ -1982,11 +2071,15 @@ extern "C" int mij_batch_diff_slots(mij_batch *b, const int *sa, const int *sb, 
 			return set_err(MIJ_E_ARG, "bad slot pair %d", i);
 		}
 		const Slot &x = b->slots[(size_t)sa[i]], &y = b->slots[(size_t)sb[i]];
-		const size_t bytes = align_up((size_t)x.desc.n_out * x.desc.width * x.desc.height, 16);
-		if (bytes != align_up((size_t)y.desc.n_out * y.desc.width * y.desc.height, 16)) {
+		/* a reduced picture leaves the rest of its region unwritten: its last, partial word is compared byte by byte */
+		const bool exact = x.scale > 1 || y.scale > 1;
+		const size_t px = out_px_bytes(x), bytes = exact ? px & ~(size_t)15 : align_up(px, 16);
+		if (exact ? px != out_px_bytes(y) : bytes != align_up(out_px_bytes(y), 16)) {
 			(void)hipFree(d_cnt);
 			return set_err(MIJ_E_ARG, "slot pair %d: different sizes", i);
 		}
+		if (exact && px > bytes)
+			hipLaunchKernelGGL(k_count_diff_tail, dim3(1), dim3(64), 0, b->stream, b->d_out + x.dev.out_off + bytes, b->d_out + y.dev.out_off + bytes, (uint32_t)(px - bytes), d_cnt);
 		/* outputs are 256-byte aligned and padded in the arena, so whole 16-byte words may be compared */
 		hipLaunchKernelGGL(k_count_diff, dim3(1024), dim3(256), 0, b->stream, reinterpret_cast<const uint4 *>(b->d_out + x.dev.out_off),
 								 reinterpret_cast<const uint4 *>(b->d_out + y.dev.out_off), (uint32_t)(bytes / 16), d_cnt);

@@ -71,6 +71,46 @@ def _orientations(v, datas):
     return vals
 
 
+def _reduces(v, n):
+    """decode's reduce= as "auto" or one denominator 1, 2, 4 or 8 per picture"""
+    if v is None:
+        return [1] * n
+    if isinstance(v, str):
+        if v != "auto":
+            raise ValueError("reduce must be None, 1, 2, 4, 8, 'auto' or one value per picture (got %r)" % (v,))
+        return "auto"
+    try:
+        vals = [v] * n if isinstance(v, int) else list(v)
+    except TypeError:
+        raise ValueError("reduce must be None, 1, 2, 4, 8, 'auto' or one value per picture (got %r)" % (v,)) from None
+    if len(vals) != n:
+        raise ValueError("reduce has %d values for %d pictures" % (len(vals), n))
+    for s in vals:
+        if isinstance(s, bool) or not isinstance(s, int) or s not in (1, 2, 4, 8):
+            raise ValueError("a reduce denominator is 1, 2, 4 or 8 (got %r)" % (s,))
+    return vals
+
+
+def reducible(d):
+    """Whether mij_batch_set_scale takes a picture with descriptor d at a denominator above 1 (include/mij.h): one component, or
+    three-component YCbCr whose luma has the picture's resolution with 4:4:4, 4:2:0 or 4:2:2 chroma."""
+    if d.ncomp == 1 and d.color == 0:
+        return True
+    if d.ncomp != 3 or d.color not in (0, 1) or (d.color == 0 and d.n_out >= 3):
+        return False
+    if (d.comp[0].h, d.comp[0].v) != (d.h_max, d.v_max) or any((d.comp[c].h, d.comp[c].v) != (1, 1) for c in (1, 2)):
+        return False
+    return (d.h_max, d.v_max) in ((1, 1), (2, 2), (2, 1))
+
+
+def auto_reduce(w, h, out_w, out_h):
+    """The largest denominator at which a w x h picture, reduced, is still at least out_w x out_h: never upsample from a reduced picture"""
+    for s in (8, 4, 2):
+        if -(-w // s) >= out_w and -(-h // s) >= out_h:
+            return s
+    return 1
+
+
 def _one_hip_runtime():
     """torch and the library must share one HIP runtime, or torch's allocations are unknown to the library (which then refuses them).
     They do when torch is imported before the library is first loaded; loaded the other way round, torch brings its own copy."""
@@ -125,7 +165,7 @@ class TensorDecoder:
         return self._batch
 
     def decode(self, datas, *, req_comp=3, crops=None, flip_x=None, flip_y=None, layout="CHW", dtype=torch.float16, mean=None, std=None,
-               out=None, threads=16, size=None, filter="bilinear", orientation=None):
+               out=None, threads=16, size=None, filter="bilinear", orientation=None, reduce=None):
         """-> (tensor, reasons).  crops: None (the whole picture; every picture the same size) or one (x0, y0, w, h) per picture, all of
         the same w and h.  size: None, or (out_h, out_w): each window is resized to it with filter (box, bilinear, hamming, bicubic or
         lanczos; the exact integer contract of mij_batch_set_out_tensor_resized, Pillow's for one channel, crop first), and windows and
@@ -135,7 +175,12 @@ class TensorDecoder:
         tensor allocated here) and gets its reason in reasons[i]; reasons[i] is None for a decoded one.  orientation: None (the stored
         pictures), "exif" (each file's EXIF Orientation tag), one int 1..8 for all or one per picture: each picture is first turned into
         its displayed picture (include/mij.h, mij_batch_set_out_tensor_oriented), and crops, size and the tensor's shape are in its
-        displayed frame."""
+        displayed frame.  reduce: None or 1 (full-size decode), 2, 4 or 8 for all pictures or one value per picture: the picture is
+        decoded at that fraction of its size straight from its coefficients (mij_batch_set_scale: ceil(W / s) x ceil(H / s)), and crops,
+        size and the tensor's shape are in that reduced (and oriented) frame; a picture whose layout has no reduced decode (4:4:0, 4:1:1,
+        RGB-tagged, CMYK) is rejected with its reason when s > 1.  "auto" (needs size= and crops=None) takes per picture the largest s at
+        which the displayed reduced picture is still at least out_w x out_h -- it never upsamples from a reduced picture -- and 1 for
+        layouts without a reduced decode."""
         datas = list(datas)
         n = len(datas)
         if layout not in ("CHW", "HWC"):
@@ -152,6 +197,9 @@ class TensorDecoder:
         if filter not in FILTERS:
             raise ValueError("filter must be one of %s (got %r)" % (", ".join(FILTERS), filter))
         orients = _orientations(orientation, datas)
+        scales = _reduces(reduce, n)
+        if scales == "auto" and (size is None or crops is not None):
+            raise ValueError("reduce='auto' needs size= and crops=None")
         if size is not None:
             try:
                 size = tuple(int(v) for v in size)
@@ -170,6 +218,14 @@ class TensorDecoder:
         ok = [d for d in descs if d is not None]
         # displayed sizes: orientations 5..8 swap the axes
         dsz = [None if d is None else ((d.height, d.width) if orients[i] >= 5 else (d.width, d.height)) for i, d in enumerate(descs)]
+        if scales == "auto":
+            scales = [1 if z is None or not reducible(descs[i]) else auto_reduce(z[0], z[1], size[1], size[0]) for i, z in enumerate(dsz)]
+        refused = {}  # pictures asked for at a reduced size their layout does not have: decoded, but not written
+        for i, d in enumerate(descs):
+            if d is not None and scales[i] > 1 and not reducible(d):
+                refused[i] = "no reduced-size decode for this layout (%d components, colour mode %d, luma %dx%d of %dx%d)" % (
+                    d.ncomp, d.color, d.comp[0].h, d.comp[0].v, d.h_max, d.v_max)
+        dsz = [None if z is None or i in refused else (-(-z[0] // scales[i]), -(-z[1] // scales[i])) for i, z in enumerate(dsz)]
         chans = {d.n_out for d in ok}
         if len(chans) > 1:
             raise ValueError("pictures decode to different channel counts %s (pass req_comp)" % sorted(chans))
@@ -187,7 +243,7 @@ class TensorDecoder:
             for i, (c, z) in enumerate(zip(wins, dsz)):
                 if c[2] < 1 or c[3] < 1 or c[0] < 0 or c[1] < 0 or (z is not None and (c[0] + c[2] > z[0] or c[1] + c[3] > z[1])):
                     raise ValueError("crop %s of picture %d outside its %dx%d picture" % (c, i, z[0] if z else 0, z[1] if z else 0))
-        whs = {c[2:] for c in wins if c is not None} if size is None else {(size[1], size[0])}
+        whs = {c[2:] for i, c in enumerate(wins) if c is not None and i not in refused} if size is None else {(size[1], size[0])}
         C = req_comp if req_comp else (chans.pop() if chans else None)
         if out is not None:
             if out.dim() != 4:
@@ -233,8 +289,17 @@ class TensorDecoder:
             if sl < 0:
                 reasons[i] = why[i] or reasons[i] or "rejected"
                 continue
+            if i in refused:
+                reasons[i] = refused[i]
+                continue
             if descs[i] is not None:
                 b.descs[sl] = descs[i]  # already probed: spares set_out_tensor a second header parse
+            if scales[i] > 1:
+                try:
+                    b.set_scale(sl, scales[i])
+                except MijError as e:  # a marker behind the header changed the colour branch
+                    reasons[i] = str(e)
+                    continue
             x0, y0 = wins[i][0], wins[i][1]
             lay = MIJ_LAYOUT_CHW if layout == "CHW" else MIJ_LAYOUT_HWC
             if size is None:

@@ -262,12 +262,40 @@ int mij_batch_hash_out(mij_batch *b, int slot, uint64_t *hash);
 int mij_batch_diff_slots(mij_batch *b, const int *sa, const int *sb, int n, uint64_t *ndiff);
 
 /* which kernel family the last upload chose for a slot: 0 none (skipped), 1 fused 4:2:0, 2 generic two-pass,
- * 3 fused 4:4:4, 4 fused 4:2:2, 5 fused grey, 6 fused 4:4:0, 7 fused 1x1 RGB-tagged / CMYK / YCCK */
+ * 3 fused 4:4:4, 4 fused 4:2:2, 5 fused grey, 6 fused 4:4:0, 7 fused 1x1 RGB-tagged / CMYK / YCCK, 8 reduced-size decode */
 int mij_batch_slot_path(const mij_batch *b, int slot);
 /* parity tests compare the kernel families: on = 1 sends every image of the batch down the two-pass path (IDCT to sample
  * planes, then resampling + colour; its pass 2 compiled per resampler where the layout allows), on = 2 also insists on
  * the run-time-general pass 2 (k_resample_color), on = 0 is the default choice */
 int mij_batch_force_generic(mij_batch *b, int on);
+
+/*
+ * Reduced-size decode: a slot may ask, before upload, for its picture at 1/denom size (denom 1, 2, 4 or 8; 1 takes the request
+ * back).  With N = 8 / denom every component is transformed by an N * h_max / h point row and an N * v_max / v point column inverse
+ * DCT on the low coefficients of each block -- libjpeg's scale_denom, Pillow's draft mode -- so all components come out at one
+ * resolution and nothing is upsampled; pixel (X, Y) takes sample (Y mod NV, X mod NH) of block (Y div NV, X div NH) of each
+ * component.  Per block, exactly (32-bit wrapping arithmetic, arithmetic shifts; tests/scaled_model.py restates it in numpy):
+ *     d[u][v] = (short)(coef * q)                                         u < NV, v < NH; nothing outside is read
+ *     t[y][v] = (sum_u K_NV[y][u] * d[u][v] + 512) >> 10
+ *     p[y][x] = clamp255((sum_v K_NH[x][v] * t[y][v] + 65536 + (128 << 17)) >> 17)
+ * K_8 is the reference's STBI__IDCT_1D, K_n[x][u] = rint(4096 * sqrt(2) * a(u) * cos((2x + 1) u pi / 2n)) below it (a(0) = 1 / sqrt(2),
+ * else 1): K_1 = [4096], K_2 = [[4096, 4096], [4096, -4096]], K_4 has rows [4096, 5352, 4096, 2217], [4096, 2217, -4096, -5352],
+ * [4096, -2217, -4096, 5352], [4096, -5352, 4096, -2217].  Colour and channel replication are the full-size path's.
+ *
+ * The stored picture of the slot is then mij_scaled_dim(width, denom) x mij_scaled_dim(height, denom), at the start of the output
+ * region the slot got when it was added, with pitch n_out * that width; mij_batch_fetch, mij_batch_device_out, mij_batch_hash_out,
+ * mij_batch_diff_slots and the three tensor requests (their windows and orientations included) all see that picture.  Set the scale
+ * before the slot's tensor request: changing it under a request is MIJ_E_STATE.  Supported layouts: one component, and three-component
+ * YCbCr whose luma has the picture's resolution with 4:4:4, 4:2:0 or 4:2:2 chroma (n_out 1 / 2: the luma alone).  MIJ_E_ARG for
+ * another denominator, for any other layout with denom > 1 (4:4:0, 4:1:1, RGB-tagged, CMYK / YCCK: refused, not approximated) and for
+ * a slot with a float request (mij_batch_set_out_f32 refuses a reduced slot in turn); MIJ_E_STATE after upload.  Asking again
+ * replaces the request, mij_batch_reset forgets it, clones start at 1.  mij_batch_slot_path reports 8 for such a slot; a batch
+ * without one launches exactly what it launches without this section.
+ */
+static inline int mij_scaled_dim(int v, int denom) { return (v + denom - 1) / denom; }
+int mij_batch_set_scale(mij_batch *b, int slot, int denom);
+/* the stored picture's size: the descriptor's, or the reduced one */
+int mij_batch_slot_out_size(const mij_batch *b, int slot, int *w, int *h);
 
 /* ---- GPU entropy stage (experimental): the baseline Huffman walk itself on the GPU, for single-scan interleaved
  * baseline files, restart intervals included.  The host only parses headers and removes
