@@ -907,6 +907,28 @@ class Batch:
         L.mij_batch_set_scale.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _check(L.mij_batch_set_scale(self._h, int(slot), int(denom)), "mij_batch_set_scale")
 
+    def set_roi(self, slot, x0, y0, w, h):
+        """mij_batch_set_roi: only the MCUs that the rectangle (x0, y0, w, h) of the slot's stored picture needs are decoded; the pixels
+        inside it are what they are without a region, bytes outside roi_rect(slot) are not written.  w == h == 0 takes it back."""
+        L = lib()
+        L.mij_batch_set_roi.argtypes = [C.c_void_p] + [C.c_int] * 5
+        _check(L.mij_batch_set_roi(self._h, int(slot), int(x0), int(y0), int(w), int(h)), "mij_batch_set_roi")
+
+    def set_roi_auto(self, slot, on=True):
+        """mij_batch_set_roi_auto: at upload the slot's region becomes the window its tensor request reads."""
+        L = lib()
+        L.mij_batch_set_roi_auto.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        _check(L.mij_batch_set_roi_auto(self._h, int(slot), int(bool(on))), "mij_batch_set_roi_auto")
+
+    def roi_rect(self, slot):
+        """(x0, y0, w, h): the rectangle of the stored picture that the last upload decodes (mij_batch_slot_roi_rect); the whole picture
+        for a slot without a region."""
+        L = lib()
+        L.mij_batch_slot_roi_rect.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int * 4)]
+        r = (C.c_int * 4)()
+        _check(L.mij_batch_slot_roi_rect(self._h, int(slot), C.byref(r)), "mij_batch_slot_roi_rect")
+        return tuple(r)
+
     def out_size(self, slot):
         """(width, height) of the slot's stored picture: the file's, or the reduced one (mij_batch_slot_out_size)."""
         L = lib()

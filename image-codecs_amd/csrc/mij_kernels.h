@@ -71,6 +71,21 @@ struct WorkBand { /* one workgroup of the band kernels: MCU rows [m0, m1) of an 
 struct WorkIdct { /* one workgroup of k_idct_planes: 256 consecutive blocks of one component */
 	uint32_t img, comp, first, pad;
 };
+/* Region-of-interest decode (mij_batch_set_roi), one per slot, read only by the windowed forms of k_fused_grey, k_fused444,
+ * k_fused1x1c and k_scaled: the rectangle of lane units -- 8 x 8 blocks, or the MCUs / luma blocks of the reduced-size kernels --
+ * that the slot's work items count through in raster order instead of the picture's */
+struct DevRoi {
+	uint32_t x0, y0, w, h;
+};
+/* the windowed forms are the kernels themselves with the table as a trailing argument (a parameter pack: empty for the forms without) */
+__device__ __forceinline__ DevRoi roi_of(uint32_t) { return DevRoi{0u, 0u, 0u, 0u}; }
+__device__ __forceinline__ DevRoi roi_of(uint32_t img, const DevRoi *__restrict__ rois) { return rois[img]; }
+/* unit i of a window in raster order -> its index in a raster of pitch units a row */
+__device__ __forceinline__ uint32_t roi_unit(const DevRoi &r, uint32_t i, uint32_t pitch)
+{
+	const uint32_t wy = i / r.w;
+	return (r.y0 + wy) * pitch + r.x0 + (i - wy * r.w);
+}
 
 /* ------------------------------------------------------------------ small helpers */
 
@@ -925,17 +940,22 @@ __global__ __launch_bounds__(256) void k_pack_c8(const DevImage *__restrict__ im
 /* ------------------------------------------------------------------ fused single-component (grey) kernel
  * One block per lane: IDCT, then the 8x8 samples go straight to the pixel buffer, replicated to n_out
  * channels (codec/jpeg.c:2373-2378, :2380-2430: grey -> y | y,255 | y,y,y | y,y,y,255).  No sample plane. */
-template <bool WIDE, bool B8 = false>
+/* With a table of windows as fifth argument (k_fused_grey<WIDE, B8, const DevRoi *>: slots with a region, mij_batch_set_roi) the work
+ * item's 256 blocks are counted through the slot's window (in blocks) instead of through the picture; everything behind the block index
+ * is the same.  Without, the kernel compiles to the code it was. */
+template <bool WIDE, bool B8 = false, typename... ROI>
 __global__ __launch_bounds__(256) void k_fused_grey(const DevImage *__restrict__ imgs, const WorkIdct *__restrict__ work, const uint8_t *__restrict__ coef,
-																	 uint8_t *__restrict__ outbase)
+																	 uint8_t *__restrict__ outbase, ROI... rois)
 {
 	const WorkIdct wk = work[blockIdx.x];
 	const DevImage &im = imgs[wk.img];
 	const DevComp &cp = im.comp[0];
-	const uint32_t nblk = (uint32_t)(cp.bw * cp.bh);
-	const uint32_t L = wk.first + threadIdx.x;
-	if (L >= nblk)
+	const DevRoi rw = roi_of(wk.img, rois...);
+	const uint32_t nblk = sizeof...(ROI) ? rw.w * rw.h : (uint32_t)(cp.bw * cp.bh);
+	const uint32_t Lr = wk.first + threadIdx.x;
+	if (Lr >= nblk)
 		return;
+	const uint32_t L = sizeof...(ROI) ? roi_unit(rw, Lr, (uint32_t)cp.bw) : Lr;
 	IdctK K;
 	K.init();
 	uint2 rows[8];
@@ -1859,8 +1879,11 @@ struct Block1x1 {
 	bool whole, via_lds;
 	uint8_t *lds_row;
 };
-template <int NOUT>
-__device__ __forceinline__ Block1x1 block_1x1_setup(const DevImage &im, uint32_t L, uint32_t nblk, uint8_t *lds_rows)
+/* WIN (the windowed forms): the one-row test speaks of the window -- W0, roww, nblk are the index of the wave's first lane in the window's
+ * raster (wave-uniform), the window's row width and its size -- whose wave holds neighbours of one block row of the picture when it lies in
+ * one row of the window */
+template <int NOUT, bool WIN>
+__device__ __forceinline__ Block1x1 block_1x1_setup(const DevImage &im, uint32_t L, uint32_t nblk, uint8_t *lds_rows, uint32_t W0, uint32_t roww)
 {
 	Block1x1 g;
 	const uint32_t bw = (uint32_t)im.comp[0].bw;
@@ -1870,25 +1893,30 @@ __device__ __forceinline__ Block1x1 block_1x1_setup(const DevImage &im, uint32_t
 	g.whole = (g.x0 + 8 <= im.width) && ((NOUT == 4) || ((im.width & 3) == 0));
 	/* LDS-transposed stores: every lane of the wave active and whole, all in one block row (lane 0's block row == lane 63's) */
 	const int lane = (int)(threadIdx.x & 63u);
-	const uint32_t L0 = L - (uint32_t)lane;
-	const bool one_row = (L0 / bw) == ((L0 + 63u) / bw) && L0 + 63u < nblk;
+	const uint32_t L0 = WIN ? W0 : L - (uint32_t)lane, rw = WIN ? roww : bw;
+	const bool one_row = (L0 / rw) == ((L0 + 63u) / rw) && L0 + 63u < nblk;
 	g.via_lds = one_row && __builtin_amdgcn_ballot_w64(g.whole) == ~0ull;
 	g.lds_row = lds_rows + (threadIdx.x >> 6) * (64 * 8 * NOUT);
 	return g;
 }
 
-template <int NOUT, bool WIDE, bool B8 = false>
+/* With a table of windows as fifth argument (slots with a region): the work item's 256 blocks are counted through the slot's window, in
+ * blocks.  Without, the kernel compiles to the code it was. */
+template <int NOUT, bool WIDE, bool B8 = false, typename... ROI>
 __global__ __launch_bounds__(256) void k_fused444(const DevImage *__restrict__ imgs, const WorkIdct *__restrict__ work, const uint8_t *__restrict__ coef,
-																  uint8_t *__restrict__ outbase)
+																  uint8_t *__restrict__ outbase, ROI... rois)
 {
 	__shared__ __attribute__((aligned(16))) uint8_t lds_rows[4 * 64 * 8 * NOUT];
 	const WorkIdct wk = work[blockIdx.x];
 	const DevImage &im = imgs[wk.img];
 	const int bw = im.comp[0].bw;
-	const uint32_t nblk = (uint32_t)(bw * im.comp[0].bh);
-	const uint32_t L = wk.first + threadIdx.x;
-	if (L >= nblk)
+	const DevRoi rw = roi_of(wk.img, rois...);
+	const uint32_t nblk = sizeof...(ROI) ? rw.w * rw.h : (uint32_t)(bw * im.comp[0].bh);
+	const uint32_t Lr = wk.first + threadIdx.x;
+	if (Lr >= nblk)
 		return;
+	const uint32_t L = sizeof...(ROI) ? roi_unit(rw, Lr, (uint32_t)bw) : Lr;
+	const uint32_t W0 = sizeof...(ROI) ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(wk.first + (threadIdx.x & ~63u))) : 0u; /* the wave's first index in the window */
 	const int W = im.width, H = im.height;
 	IdctK KI;
 	KI.init();
@@ -1911,7 +1939,7 @@ __global__ __launch_bounds__(256) void k_fused444(const DevImage *__restrict__ i
 		load_block_fmt<B8>(coef_view(coef, im.comp[2]), L, im.dq[2], c);
 		idct_block<WIDE, B8>(KI, c, im.dq[2], rr);
 	}
-	const Block1x1 g = block_1x1_setup<NOUT>(im, L, nblk, lds_rows);
+	const Block1x1 g = block_1x1_setup<NOUT, sizeof...(ROI) != 0>(im, L, nblk, lds_rows, W0, rw.w);
 	const int x0 = g.x0, y0 = g.y0, lane = (int)(threadIdx.x & 63u);
 	uint8_t *const out = outbase + im.out_off;
 	const size_t opitch = (size_t)W * NOUT;
@@ -1954,18 +1982,23 @@ __global__ __launch_bounds__(256) void k_fused444(const DevImage *__restrict__ i
  * have sampling factors 1x1: the same shape as k_fused444 -- a lane owns the 8 x 8 block position, transforms its three or four blocks
  * (with the sparse classes: chroma and K planes of such files are often flat) and converts its 64 pixels in registers -- instead of the
  * two-pass family's round trip of the sample planes through HBM.  The colour mode is wave-uniform (one image per workgroup). */
-template <int NOUT, bool WIDE, bool B8 = false>
+/* With a table of windows as fifth argument (slots with a region): the work item's 256 blocks are counted through the slot's window, in
+ * blocks.  Without, the kernel compiles to the code it was. */
+template <int NOUT, bool WIDE, bool B8 = false, typename... ROI>
 __global__ __launch_bounds__(256) void k_fused1x1c(const DevImage *__restrict__ imgs, const WorkIdct *__restrict__ work, const uint8_t *__restrict__ coef,
-																	uint8_t *__restrict__ outbase)
+																	  uint8_t *__restrict__ outbase, ROI... rois)
 {
 	__shared__ __attribute__((aligned(16))) uint8_t lds_rows[4 * 64 * 8 * NOUT];
 	const WorkIdct wk = work[blockIdx.x];
 	const DevImage &im = imgs[wk.img];
 	const int bw = im.comp[0].bw;
-	const uint32_t nblk = (uint32_t)(bw * im.comp[0].bh);
-	const uint32_t L = wk.first + threadIdx.x;
-	if (L >= nblk)
+	const DevRoi rw = roi_of(wk.img, rois...);
+	const uint32_t nblk = sizeof...(ROI) ? rw.w * rw.h : (uint32_t)(bw * im.comp[0].bh);
+	const uint32_t Lr = wk.first + threadIdx.x;
+	if (Lr >= nblk)
 		return;
+	const uint32_t L = sizeof...(ROI) ? roi_unit(rw, Lr, (uint32_t)bw) : Lr;
+	const uint32_t W0 = sizeof...(ROI) ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(wk.first + (threadIdx.x & ~63u))) : 0u; /* the wave's first index in the window */
 	const int W = im.width, H = im.height, color = im.color;
 	const bool four = color == MIJ_COLOR_CMYK || color == MIJ_COLOR_YCCK;
 	const int count_classes = im.flags & MIJ_DEV_COUNT_CLASSES;
@@ -1982,7 +2015,7 @@ __global__ __launch_bounds__(256) void k_fused1x1c(const DevImage *__restrict__ 
 		for (int r = 0; r < 8; ++r)
 			r3[r] = make_uint2(0xffffffffu, 0xffffffffu);
 	}
-	const Block1x1 g = block_1x1_setup<NOUT>(im, L, nblk, lds_rows);
+	const Block1x1 g = block_1x1_setup<NOUT, sizeof...(ROI) != 0>(im, L, nblk, lds_rows, W0, rw.w);
 	const int lane = (int)(threadIdx.x & 63u);
 	uint8_t *const out = outbase + im.out_off;
 	const size_t opitch = (size_t)W * NOUT;

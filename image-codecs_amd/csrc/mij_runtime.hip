@@ -55,11 +55,11 @@ extern "C" int mij_device_count(void)
 /* ------------------------------------------------------------------ decode kernel families */
 
 /* kernel families of a launch plan, in launch order.  MK_RS_FAST + RS_*: pass 2 compiled per resampler (k_resample_fast) */
-enum { MK_PLANES = 0, MK_RESAMPLE, MK_RS_FAST, MK_420 = MK_RS_FAST + RS_KINDS, MK_422, MK_444, MK_GREY, MK_440, MK_420W, MK_440W /* k_fused420w / k_fused440w: 512 threads, wide pictures */, MK_420X /* 1024 threads: one workgroup per CU */, MK_420S, MK_420T /* 128 / 64 threads: narrow pictures */, MK_422W, MK_422X, MK_422S, MK_422T /* k_fused422 with 512 / 1024 / 128 / 64 threads */, MK_1X1C /* k_fused1x1c: RGB-tagged / CMYK / YCCK at 1x1 */, MK_420C, MK_440C /* column segments: a row of MCUs beyond a CU's LDS */, MK_SCALED /* + SC_*: reduced-size decode, k_scaled per layout */, MK_KINDS = MK_SCALED + SC_LAYOUTS };
+enum { MK_PLANES = 0, MK_RESAMPLE, MK_RS_FAST, MK_420 = MK_RS_FAST + RS_KINDS, MK_422, MK_444, MK_GREY, MK_440, MK_420W, MK_440W /* k_fused420w / k_fused440w: 512 threads, wide pictures */, MK_420X /* 1024 threads: one workgroup per CU */, MK_420S, MK_420T /* 128 / 64 threads: narrow pictures */, MK_422W, MK_422X, MK_422S, MK_422T /* k_fused422 with 512 / 1024 / 128 / 64 threads */, MK_1X1C /* k_fused1x1c: RGB-tagged / CMYK / YCCK at 1x1 */, MK_420C, MK_440C /* column segments: a row of MCUs beyond a CU's LDS */, MK_SCALED /* + SC_*: reduced-size decode, k_scaled per layout */, MK_444R = MK_SCALED + SC_LAYOUTS, MK_GREYR, MK_1X1CR /* windowed forms of k_fused444 / k_fused_grey / k_fused1x1c: slots with a region (mij_batch_set_roi) */, MK_SCALEDR /* + SC_*: k_scaled on a window */, MK_KINDS = MK_SCALEDR + SC_LAYOUTS };
 
 /* A family's kernels per variant = 4 * (n_out == 4) + 2 * wide IDCT + compact planes (k_resample_fast: 4 * (n_out == 4) + 2 * YCbCr
  * colour; k_scaled: 2 * (log2 of the scale - 1) + compact planes).  Every decode kernel takes (const DevImage *, const Work *, const uint8_t *in, uint8_t *out); io says which arenas in and
- * out are. */
+ * out are.  roi: a windowed form, which takes the batch's DevRoi table as a fifth argument. */
 enum { MK_VARIANTS = 8 };
 enum Arena { COEF_OUT, COEF_PLANES, PLANES_OUT };
 struct Family {
@@ -67,13 +67,21 @@ struct Family {
 	Arena io;
 	bool band; /* a band kernel: dynamic LDS up to the whole CU's */
 	const void *k[MK_VARIANTS];
+	bool roi;
 };
 #define MIJ_K(...) reinterpret_cast<const void *>(&__VA_ARGS__)
 #define MIJ_NWB(K)                                                                                                                  \
 	{ MIJ_K(K<3, false, false>), MIJ_K(K<3, false, true>), MIJ_K(K<3, true, false>), MIJ_K(K<3, true, true>),                      \
 	  MIJ_K(K<4, false, false>), MIJ_K(K<4, false, true>), MIJ_K(K<4, true, false>), MIJ_K(K<4, true, true>) }
 #define MIJ_WB(K) { MIJ_K(K<false, false>), MIJ_K(K<false, true>), MIJ_K(K<true, false>), MIJ_K(K<true, true>) }
+/* the windowed forms: the same kernels with the DevRoi table as fifth parameter */
+#define MIJ_R const DevRoi *
+#define MIJ_NWBR(K)                                                                                                                 \
+	{ MIJ_K(K<3, false, false, MIJ_R>), MIJ_K(K<3, false, true, MIJ_R>), MIJ_K(K<3, true, false, MIJ_R>), MIJ_K(K<3, true, true, MIJ_R>),      \
+	  MIJ_K(K<4, false, false, MIJ_R>), MIJ_K(K<4, false, true, MIJ_R>), MIJ_K(K<4, true, false, MIJ_R>), MIJ_K(K<4, true, true, MIJ_R>) }
+#define MIJ_WBR(K) { MIJ_K(K<false, false, MIJ_R>), MIJ_K(K<false, true, MIJ_R>), MIJ_K(K<true, false, MIJ_R>), MIJ_K(K<true, true, MIJ_R>) }
 #define MIJ_SC(Y) { MIJ_K(k_scaled<Y, 2, false>), MIJ_K(k_scaled<Y, 2, true>), MIJ_K(k_scaled<Y, 4, false>), MIJ_K(k_scaled<Y, 4, true>), MIJ_K(k_scaled<Y, 8, false>), MIJ_K(k_scaled<Y, 8, true>) }
+#define MIJ_SCR(Y) { MIJ_K(k_scaled<Y, 2, false, MIJ_R>), MIJ_K(k_scaled<Y, 2, true, MIJ_R>), MIJ_K(k_scaled<Y, 4, false, MIJ_R>), MIJ_K(k_scaled<Y, 4, true, MIJ_R>), MIJ_K(k_scaled<Y, 8, false, MIJ_R>), MIJ_K(k_scaled<Y, 8, true, MIJ_R>) }
 #define MIJ_RSF(R)                                                                                                                  \
 	{ MIJ_K(k_resample_fast<R, false, 3>), nullptr, MIJ_K(k_resample_fast<R, true, 3>), nullptr,                                   \
 	  MIJ_K(k_resample_fast<R, false, 4>), nullptr, MIJ_K(k_resample_fast<R, true, 4>), nullptr }
@@ -108,7 +116,19 @@ static const Family families[MK_KINDS] = {
 	{256, COEF_OUT, false, MIJ_SC(SC_444)},
 	{256, COEF_OUT, false, MIJ_SC(SC_420)},
 	{256, COEF_OUT, false, MIJ_SC(SC_422)},
+	/* MK_444R */ {256, COEF_OUT, false, MIJ_NWBR(k_fused444), true},
+	/* MK_GREYR */ {256, COEF_OUT, false, MIJ_WBR(k_fused_grey), true},
+	/* MK_1X1CR */ {256, COEF_OUT, false, MIJ_NWBR(k_fused1x1c), true},
+	/* MK_SCALEDR + SC_Y, SC_444, SC_420, SC_422 */
+	{256, COEF_OUT, false, MIJ_SCR(SC_Y), true},
+	{256, COEF_OUT, false, MIJ_SCR(SC_444), true},
+	{256, COEF_OUT, false, MIJ_SCR(SC_420), true},
+	{256, COEF_OUT, false, MIJ_SCR(SC_422), true},
 };
+#undef MIJ_SCR
+#undef MIJ_WBR
+#undef MIJ_NWBR
+#undef MIJ_R
 #undef MIJ_SC
 #undef MIJ_RSF
 #undef MIJ_WB
@@ -269,7 +289,14 @@ struct Slot {
 	int f32;           /* float output: index of the slot's request (mij_batch::f32_req), -1 none */
 	int ten;           /* tensor output: index of the slot's request (mij_batch::ten_req), -1 none */
 	int scale;         /* reduced-size decode (mij_batch_set_scale): 1, 2, 4 or 8; the stored picture is out_w(s) x out_h(s) */
+	/* region of interest: what was asked for (mij_batch_set_roi: roi_on and roi[] = x0, y0, w, h in stored pixels; mij_batch_set_roi_auto), and
+	 * what the last upload made of it -- the region in force (reg, reg_px: none for two-pass slots and for windows that need every MCU), the
+	 * decoded rectangle (rect) and the rectangle of lane units the windowed kernels count through (win) */
+	bool roi_on, roi_auto, reg;
+	int roi[4], reg_px[4], rect[4];
+	DevRoi win;
 };
+static inline bool wants_region(const Slot &s) { return s.roi_on || s.roi_auto; }
 
 /* the stored picture of a slot: what every consumer of its pixels sees */
 static inline int out_w(const Slot &s) { return mij_scaled_dim(s.desc.width, s.scale); }
@@ -309,6 +336,8 @@ struct mij_batch {
 	DevImage *h_imgs = nullptr, *d_imgs = nullptr;
 	Work4 *h_work = nullptr, *d_work = nullptr;
 	size_t work_cap = 0;
+	DevRoi *h_roi = nullptr, *d_roi = nullptr; /* per slot, for the windowed kernels: created by the first upload that plans one */
+	size_t roi_cap = 0;
 	std::vector<Slot> slots;
 	/* launch plan built by upload: one per non-empty (family, variant) work list */
 	struct Launch {
@@ -443,6 +472,8 @@ extern "C" void mij_batch_destroy(mij_batch *b)
 	free_dev(b->d_imgs);
 	free_host(b->h_work);
 	free_dev(b->d_work);
+	free_host(b->h_roi);
+	free_dev(b->d_roi);
 	free_dev(b->d_up16);
 	free_dev(b->d_l1max);
 	free_host(b->h_l1max);
@@ -603,6 +634,7 @@ static int add_common(mij_batch *b, const mij_image_desc *d, int clone_of, bool 
 	s.f32 = -1;
 	s.ten = -1;
 	s.scale = 1;
+	s.roi_on = s.roi_auto = s.reg = false;
 	if (clone_of < 0) {
 		if (b->stage_used + cbytes > b->stage_cap) {
 			if (!lazy_stage)
@@ -755,6 +787,65 @@ extern "C" int mij_batch_slot_out_size(const mij_batch *b, int slot, int *w, int
 		*w = out_w(s);
 	if (h)
 		*h = out_h(s);
+	return MIJ_OK;
+}
+
+/* ---- region of interest (include/mij.h) */
+
+static bool rect_inside(const int r[4], int W, int H) { return r[0] >= 0 && r[1] >= 0 && r[2] > 0 && r[3] > 0 && r[2] <= W - r[0] && r[3] <= H - r[1]; }
+
+extern "C" int mij_batch_set_roi(mij_batch *b, int slot, int x0, int y0, int w, int h)
+{
+	if (!b || slot < 0 || slot >= (int)b->slots.size())
+		return set_err(MIJ_E_ARG, "mij_batch_set_roi: bad slot");
+	if (b->uploaded)
+		return set_err(MIJ_E_STATE, "mij_batch_set_roi after mij_batch_upload");
+	Slot &s = b->slots[(size_t)slot];
+	if (s.desc.flags & MIJ_FLAG_SKIP)
+		return set_err(MIJ_E_STATE, "slot %d was rejected by the host stage", slot);
+	if (w == 0 && h == 0) {
+		s.roi_on = false;
+		return MIJ_OK;
+	}
+	const int r[4] = {x0, y0, w, h};
+	if (!rect_inside(r, out_w(s), out_h(s)))
+		return set_err(MIJ_E_ARG, "mij_batch_set_roi: region %d,%d %dx%d is empty or outside the %dx%d stored picture of slot %d", x0, y0, w, h, out_w(s), out_h(s), slot);
+	if (s.f32 >= 0)
+		return set_err(MIJ_E_ARG, "mij_batch_set_roi: slot %d has a float output request; float output of a region is not supported", slot);
+	s.roi_on = true;
+	memcpy(s.roi, r, sizeof(r));
+	return MIJ_OK;
+}
+
+extern "C" int mij_batch_set_roi_auto(mij_batch *b, int slot, int on)
+{
+	if (!b || slot < 0 || slot >= (int)b->slots.size())
+		return set_err(MIJ_E_ARG, "mij_batch_set_roi_auto: bad slot");
+	if (b->uploaded)
+		return set_err(MIJ_E_STATE, "mij_batch_set_roi_auto after mij_batch_upload");
+	Slot &s = b->slots[(size_t)slot];
+	if (s.desc.flags & MIJ_FLAG_SKIP)
+		return set_err(MIJ_E_STATE, "slot %d was rejected by the host stage", slot);
+	if (on && s.f32 >= 0)
+		return set_err(MIJ_E_ARG, "mij_batch_set_roi_auto: slot %d has a float output request; float output of a region is not supported", slot);
+	s.roi_auto = on != 0;
+	return MIJ_OK;
+}
+
+extern "C" int mij_batch_slot_roi_rect(const mij_batch *b, int slot, int rect[4])
+{
+	if (!b || slot < 0 || slot >= (int)b->slots.size() || !rect)
+		return set_err(MIJ_E_ARG, "mij_batch_slot_roi_rect: bad slot or destination");
+	if (!b->uploaded)
+		return set_err(MIJ_E_STATE, "mij_batch_slot_roi_rect before mij_batch_upload");
+	const Slot &s = b->slots[(size_t)slot];
+	if (s.reg) {
+		memcpy(rect, s.rect, sizeof(s.rect));
+	} else {
+		rect[0] = rect[1] = 0;
+		rect[2] = out_w(s);
+		rect[3] = out_h(s);
+	}
 	return MIJ_OK;
 }
 
@@ -1294,7 +1385,7 @@ static void auto_bands(const mij_batch *b, int nb[MK_KINDS])
 {
 	size_t n_fused[MK_KINDS] = {}, mcu_rows_sum[MK_KINDS] = {}, lds_max[MK_KINDS] = {};
 	for (const Slot &s : b->slots)
-		if (s.choice.path == PATH_420 || s.choice.path == PATH_440) {
+		if ((s.choice.path == PATH_420 || s.choice.path == PATH_440) && !s.reg) { /* a slot with a region cuts its own bands (push_region_bands) */
 			const int k = s.choice.kind;
 			++n_fused[k];
 			mcu_rows_sum[k] += (size_t)s.desc.mcu_y;
@@ -1345,6 +1436,111 @@ static void push_bands(std::vector<Work4> &L, size_t &lds, uint32_t i, const mij
 	lds = need > lds ? need : lds;
 }
 
+/* The same for a slot with a region: bands over the MCU rows [r0, r1) only, each cut into the fewest column segments of [c0, c1) that fit the
+ * LDS as band_segments counts it.  Bands of about four MCU rows: a window is narrow, so a band's workgroup is short of lanes whatever its
+ * height, and it is the number of workgroups that fills the machine; the halo a band edge re-transforms is two chroma block rows of the
+ * window's width only. */
+static void push_region_bands(std::vector<Work4> &L, size_t &lds, uint32_t i, size_t cap, size_t bytes_per_col, int r0, int r1, int c0, int c1, int band_rows)
+{
+	const int rows = r1 - r0, cols = c1 - c0, nseg = band_segments(cap, cols, bytes_per_col);
+	const int per = band_rows > 0 ? band_rows : 4, nb = (rows + per - 1) / per;
+	for (int k = 0; k < nb; ++k)
+		for (int g = 0; g < nseg; ++g)
+			L.push_back(Work4{i, (uint32_t)(r0 + (long)rows * k / nb), (uint32_t)(r0 + (long)rows * (k + 1) / nb),
+									(uint32_t)(c0 + (long)cols * g / nseg) | (uint32_t)(c0 + (long)cols * (g + 1) / nseg) << 16});
+	const size_t need = band_segment_lds(cols, nseg, bytes_per_col);
+	lds = need > lds ? need : lds;
+}
+
+/* (slot, first unit) per 256 lane units of a window (the windowed 1 x 1 and reduced-size kernels) */
+static void push_window(std::vector<Work4> &L, uint32_t i, const DevRoi &w)
+{
+	for (uint32_t f = 0, n = w.w * w.h; f < n; f += 256)
+		L.push_back(Work4{i, 0u, f, 0u});
+}
+
+/* The regions of an upload.  Per slot that asked for one: the region in force -- the explicit one, validated against the stored picture as
+ * it is now, or the tensor request's window in the stored frame -- and the checks that tie a request to it. */
+static int resolve_regions(mij_batch *b)
+{
+	for (size_t i = 0; i < b->slots.size(); ++i) {
+		Slot &s = b->slots[i];
+		s.reg = false;
+		if (!wants_region(s) || (s.desc.flags & MIJ_FLAG_SKIP))
+			continue;
+		int win[4] = {0, 0, 0, 0}; /* the request's window in stored pixels: a transposed request's rows are stored columns */
+		if (s.ten >= 0) {
+			const mij_batch::TenReq &q = b->ten_req[(size_t)s.ten];
+			win[0] = q.t.x0, win[1] = q.t.y0, win[2] = q.tr ? q.t.h : q.t.w, win[3] = q.tr ? q.t.w : q.t.h;
+		}
+		if (s.roi_on) { /* an explicit region wins over the automatic one */
+			if (!rect_inside(s.roi, out_w(s), out_h(s)))
+				return set_err(MIJ_E_ARG, "mij_batch_upload: region %d,%d %dx%d of slot %zu is outside its %dx%d stored picture", s.roi[0], s.roi[1], s.roi[2], s.roi[3], i,
+									out_w(s), out_h(s));
+			if (s.ten >= 0 && (win[0] < s.roi[0] || win[1] < s.roi[1] || win[0] + win[2] > s.roi[0] + s.roi[2] || win[1] + win[3] > s.roi[1] + s.roi[3]))
+				return set_err(MIJ_E_ARG, "mij_batch_upload: the tensor request of slot %zu reads %d,%d %dx%d of the stored picture, outside the slot's region %d,%d %dx%d", i,
+									win[0], win[1], win[2], win[3], s.roi[0], s.roi[1], s.roi[2], s.roi[3]);
+			memcpy(s.reg_px, s.roi, sizeof(s.roi));
+		} else {
+			if (s.ten < 0)
+				return set_err(MIJ_E_STATE, "mij_batch_upload: slot %zu asks for an automatic region (mij_batch_set_roi_auto) but has no tensor request", i);
+			memcpy(s.reg_px, win, sizeof(win));
+		}
+		if (s.f32 >= 0)
+			return set_err(MIJ_E_ARG, "mij_batch_upload: slot %zu has a float output request and a region", i);
+		s.reg = true;
+	}
+	return MIJ_OK;
+}
+
+/* What a region makes of a slot's choice: the lane-unit rectangle that covers it (MCUs of the band kernels; 8 x 8 blocks of the 1 x 1
+ * kernels; MCUs, or luma blocks, of the reduced-size kernels), the decoded rectangle, and the windowed family.  The region is dropped
+ * (s.reg = false: the slot is planned as without one) for the two-pass path, which has no windowed form, and when it needs every unit. */
+static void apply_region(Slot &s)
+{
+	const mij_image_desc &d = s.desc;
+	Choice &c = s.choice;
+	int uw, uh; /* unit size in stored pixels */
+	switch (c.path) {
+	case PATH_420: uw = 16, uh = 16; break;
+	case PATH_440: uw = 8, uh = 16; break;
+	case PATH_422: uw = 16, uh = 8; break;
+	case PATH_GREY:
+	case PATH_444:
+	case PATH_1X1C: uw = uh = 8; break;
+	case PATH_SCALED: {
+		const int lay = c.kind - MK_SCALED, n = 8 / s.scale;
+		uw = n * ((lay == SC_420 || lay == SC_422) ? 2 : 1), uh = n * (lay == SC_420 ? 2 : 1);
+		break;
+	}
+	default:
+		s.reg = false;
+		return;
+	}
+	const int W = out_w(s), H = out_h(s);
+	int x0 = s.reg_px[0] / uw, x1 = (s.reg_px[0] + s.reg_px[2] + uw - 1) / uw, y0 = s.reg_px[1] / uh, y1 = (s.reg_px[1] + s.reg_px[3] + uh - 1) / uh;
+	if (c.path == PATH_422) /* rows only: a column form needs the h2v1 filter's halo and edge forms in segments */
+		x0 = 0, x1 = d.mcu_x;
+	/* the grid may reach beyond the picture (padding MCUs, blocks of a luma plane that no pixel row reads): units that hold pixels only */
+	const int ux = (W + uw - 1) / uw, uy = (H + uh - 1) / uh;
+	if (x0 == 0 && y0 == 0 && x1 >= ux && y1 >= uy) {
+		s.reg = false;
+		return;
+	}
+	s.win = DevRoi{(uint32_t)x0, (uint32_t)y0, (uint32_t)(x1 - x0), (uint32_t)(y1 - y0)};
+	s.rect[0] = x0 * uw, s.rect[1] = y0 * uh;
+	s.rect[2] = (x1 * uw < W ? x1 * uw : W) - s.rect[0], s.rect[3] = (y1 * uh < H ? y1 * uh : H) - s.rect[1];
+	switch (c.path) {
+	case PATH_420: c.kind = MK_420C; break;
+	case PATH_440: c.kind = MK_440C; break;
+	case PATH_444: c.kind = MK_444R; break;
+	case PATH_GREY: c.kind = MK_GREYR; break;
+	case PATH_1X1C: c.kind = MK_1X1CR; break;
+	case PATH_SCALED: c.kind = MK_SCALEDR + (c.kind - MK_SCALED); break;
+	default: break; /* PATH_422: the same kernel on fewer bands */
+	}
+}
+
 /* (slot, component, first block) per 256 blocks of one component */
 static void push_blocks(std::vector<Work4> &L, uint32_t i, const mij_image_desc &d, int comp)
 {
@@ -1355,8 +1551,12 @@ static void push_blocks(std::vector<Work4> &L, uint32_t i, const mij_image_desc 
 
 static void plan_decode(mij_batch *b, Plan &p)
 {
-	for (Slot &s : b->slots)
+	const size_t cap = (size_t)b->ctx->max_dyn_lds;
+	for (Slot &s : b->slots) {
 		s.choice = classify(b, s);
+		if (s.reg)
+			apply_region(s);
+	}
 	int auto_nb[MK_KINDS];
 	auto_bands(b, auto_nb);
 	for (size_t i = 0; i < b->slots.size(); ++i) {
@@ -1372,21 +1572,34 @@ static void plan_decode(mij_batch *b, Plan &p)
 		switch (c.path) {
 		case PATH_420:
 		case PATH_440: /* band count by rounds of co-resident workgroups */
+			if (s.reg) {
+				push_region_bands(L, lds, (uint32_t)i, cap, c.path == PATH_420 ? LDS_COL_420 : LDS_COL_440, (int)s.win.y0, (int)(s.win.y0 + s.win.h), (int)s.win.x0,
+										(int)(s.win.x0 + s.win.w), b->band_rows);
+				break;
+			}
 			push_bands(L, lds, (uint32_t)i, d, c, b->band_rows > 0 ? (d.mcu_y + b->band_rows - 1) / b->band_rows : auto_nb[c.kind]);
 			break;
 		case PATH_422: { /* no halo: bands of about eight MCU rows keep the grid deep without making workgroups short */
 			lds = c.lds > lds ? c.lds : lds;
-			const int nb = (d.mcu_y + 7) / 8;
+			const int r0 = s.reg ? (int)s.win.y0 : 0, rows = s.reg ? (int)s.win.h : d.mcu_y; /* a region: its MCU rows, at full width */
+			const int nb = (rows + 7) / 8;
 			for (int k = 0; k < nb; ++k)
-				L.push_back(Work4{(uint32_t)i, (uint32_t)((long)d.mcu_y * k / nb), (uint32_t)((long)d.mcu_y * (k + 1) / nb), 0u});
+				L.push_back(Work4{(uint32_t)i, (uint32_t)(r0 + (long)rows * k / nb), (uint32_t)(r0 + (long)rows * (k + 1) / nb), 0u});
 			break;
 		}
 		case PATH_GREY:
 		case PATH_444:
 		case PATH_1X1C:
-			push_blocks(L, (uint32_t)i, d, 0);
+			if (s.reg)
+				push_window(L, (uint32_t)i, s.win);
+			else
+				push_blocks(L, (uint32_t)i, d, 0);
 			break;
 		case PATH_SCALED: { /* 256 MCUs a workgroup; the luma-only form: 256 luma blocks */
+			if (s.reg) {
+				push_window(L, (uint32_t)i, s.win);
+				break;
+			}
 			const uint32_t nm = c.kind == MK_SCALED + SC_Y ? (uint32_t)(d.comp[0].bw * d.comp[0].bh) : (uint32_t)(d.mcu_x * d.mcu_y);
 			for (uint32_t f = 0; f < nm; f += 256)
 				L.push_back(Work4{(uint32_t)i, 0u, f, 0u});
@@ -1455,6 +1668,16 @@ static int lay_out_work(mij_batch *b, const Plan &p)
 	for (size_t i = 0; i < n; ++i)
 		b->h_imgs[i] = b->slots[i].dev;
 	HIP_TRY(copy_table(b->d_imgs, b->h_imgs, sizeof(DevImage) * n, b->stream));
+	bool windowed = false;
+	for (const mij_batch::Launch &l : b->launches)
+		windowed = windowed || families[l.kind].roi;
+	if (windowed) { /* the windows of the slots the windowed kernels decode; the others' entries are never read */
+		if (!b->h_roi && (rc = grow_pair(b->h_roi, b->d_roi, b->roi_cap, (size_t)b->max_images)) != MIJ_OK)
+			return rc;
+		for (size_t i = 0; i < n; ++i)
+			b->h_roi[i] = b->slots[i].reg ? b->slots[i].win : DevRoi{0u, 0u, 0u, 0u};
+		HIP_TRY(copy_table(b->d_roi, b->h_roi, sizeof(DevRoi) * n, b->stream));
+	}
 	if (total)
 		HIP_TRY(copy_table(b->d_work, b->h_work, sizeof(Work4) * total, b->stream));
 	return MIJ_OK;
@@ -1545,6 +1768,8 @@ extern "C" int mij_batch_upload(mij_batch *b)
 			return set_err(MIJ_E_ARG, "mij_batch_upload: slot %zu cannot be decoded at 1/%d size", i, b->slots[i].scale);
 	Plan p;
 	int rc;
+	if ((rc = resolve_regions(b)) != MIJ_OK)
+		return rc;
 	if ((rc = plane_formats(b)) != MIJ_OK || (rc = l1_prepack(b)) != MIJ_OK)
 		return rc;
 	plan_decode(b, p);
@@ -1571,8 +1796,8 @@ extern "C" int mij_batch_launch(mij_batch *b)
 		const Work4 *wk = b->d_work + L.first;
 		const uint8_t *in = f.io == PLANES_OUT ? b->d_planes : b->d_coef;
 		uint8_t *out = f.io == COEF_PLANES ? b->d_planes : b->d_out;
-		void *args[] = {&b->d_imgs, &wk, &in, &out};
-		(void)hipLaunchKernel(f.k[L.var], dim3((unsigned)L.count), dim3(f.threads), args, L.lds, b->stream);
+		void *args4[] = {&b->d_imgs, &wk, &in, &out}, *args5[] = {&b->d_imgs, &wk, &in, &out, &b->d_roi}; /* the windowed forms take the table of windows */
+		(void)hipLaunchKernel(f.k[L.var], dim3((unsigned)L.count), dim3(f.threads), f.roi ? args5 : args4, L.lds, b->stream);
 		HIP_TRY(hipGetLastError());
 	}
 	/* float output, behind every decode family (both front ends end here) */
@@ -1735,6 +1960,8 @@ extern "C" int mij_batch_set_out_f32(mij_batch *b, int slot, const float *lut)
 		return set_err(MIJ_E_STATE, "slot %d was rejected by the host stage", slot);
 	if (s.scale > 1)
 		return set_err(MIJ_E_ARG, "mij_batch_set_out_f32: slot %d is decoded at 1/%d size; float output of reduced pictures is not supported", slot, s.scale);
+	if (wants_region(s))
+		return set_err(MIJ_E_ARG, "mij_batch_set_out_f32: slot %d decodes a region only; float output of a region is not supported", slot);
 	if (s.f32 < 0) {
 		const size_t need = mij_image_out_f32_bytes(&s.desc);
 		if (!b->d_f32 || b->f32_used + need > b->f32_cap)
@@ -2021,6 +2248,8 @@ extern "C" int mij_batch_hash_out(mij_batch *b, int slot, uint64_t *hash)
 	if (!b || slot < 0 || slot >= (int)b->slots.size() || !hash)
 		return set_err(MIJ_E_ARG, "bad argument");
 	const Slot &s = b->slots[(size_t)slot];
+	if (wants_region(s))
+		return set_err(MIJ_E_STATE, "mij_batch_hash_out: slot %d decodes a region only; the rest of its picture is unspecified", slot);
 	const size_t bytes = out_px_bytes(s);
 	std::vector<uint8_t> tmp(bytes);
 	int rc = mij_batch_fetch(b, slot, tmp.data(), bytes);
@@ -2071,6 +2300,10 @@ extern "C" int mij_batch_diff_slots(mij_batch *b, const int *sa, const int *sb, 
 			return set_err(MIJ_E_ARG, "bad slot pair %d", i);
 		}
 		const Slot &x = b->slots[(size_t)sa[i]], &y = b->slots[(size_t)sb[i]];
+		if (wants_region(x) || wants_region(y)) {
+			(void)hipFree(d_cnt);
+			return set_err(MIJ_E_STATE, "mij_batch_diff_slots: slot pair %d: a slot that decodes a region only cannot be compared", i);
+		}
 		/* a reduced picture leaves the rest of its region unwritten: its last, partial word is compared byte by byte */
 		const bool exact = x.scale > 1 || y.scale > 1;
 		const size_t px = out_px_bytes(x), bytes = exact ? px & ~(size_t)15 : align_up(px, 16);

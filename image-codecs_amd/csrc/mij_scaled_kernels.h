@@ -198,20 +198,25 @@ __device__ __forceinline__ void sc_store_runs(const uint32_t *__restrict__ lds, 
 	}
 }
 
-template <int LAYOUT, int S, bool B8>
+/* With a table of windows as fifth argument (k_scaled<LAYOUT, S, B8, const DevRoi *>: slots with a region, mij_batch_set_roi) the lane grid
+ * is the slot's window -- in MCUs, or luma blocks in the luma-only form -- instead of the picture's grid: the work item's 256 lanes count
+ * through it in raster order, and the strips leave from the window's first column.  Without, the kernel compiles to the code it was. */
+template <int LAYOUT, int S, bool B8, typename... ROI>
 __global__ __launch_bounds__(256) void k_scaled(const DevImage *__restrict__ imgs, const WorkIdct *__restrict__ work, const uint8_t *__restrict__ coef,
-																uint8_t *__restrict__ outbase)
+																uint8_t *__restrict__ outbase, ROI... rois)
 {
 	constexpr int N = 8 / S;
 	constexpr int HM = (LAYOUT == SC_420 || LAYOUT == SC_422) ? 2 : 1, VM = LAYOUT == SC_420 ? 2 : 1;
 	constexpr int TW = N * HM, TH = N * VM; /* the lane's pixel tile; also the chroma transform lengths (NH, NV) */
-	constexpr bool COLOUR = LAYOUT != SC_Y;
+	constexpr bool COLOUR = LAYOUT != SC_Y, WIN = sizeof...(ROI) != 0;
 	__shared__ __attribute__((aligned(16))) uint32_t lds[N * 256 * TW + 4]; /* a strip of N rows, 4 bytes a pixel at the most; + the dword a misaligned read looks into */
 
 	const WorkIdct wk = work[blockIdx.x];
 	const DevImage &im = imgs[wk.img];
 	/* the lane grid: MCUs, or the luma blocks of whatever layout for the luma-only form */
-	const uint32_t gx = (uint32_t)(COLOUR ? im.mcu_x : im.comp[0].bw), gy = (uint32_t)(COLOUR ? im.mcu_y : im.comp[0].bh);
+	const DevRoi rw = roi_of(wk.img, rois...);
+	const uint32_t pgx = (uint32_t)(COLOUR ? im.mcu_x : im.comp[0].bw); /* the picture's grid; the window's first unit in it */
+	const uint32_t gx = WIN ? rw.w : pgx, gy = WIN ? rw.h : (uint32_t)(COLOUR ? im.mcu_y : im.comp[0].bh), ux0 = WIN ? rw.x0 : 0u, uy0 = WIN ? rw.y0 : 0u;
 	const uint32_t nm = gx * gy, m0 = wk.first, cnt = min(256u, nm - m0);
 	const uint32_t m = min(m0 + threadIdx.x, nm - 1u); /* lanes past the end redo the last MCU: they load in bounds and their pixels are never stored */
 	const uint32_t my = m / gx, mx = m - my * gx;
@@ -222,8 +227,9 @@ __global__ __launch_bounds__(256) void k_scaled(const DevImage *__restrict__ img
 
 	uint32_t cb[COLOUR ? TH : 1][(TW + 3) / 4], cr[COLOUR ? TH : 1][(TW + 3) / 4];
 	if constexpr (COLOUR) {
-		sc_block<TH, TW, B8>(coef_view(coef, im.comp[1]), m, im.dq[1], cb);
-		sc_block<TH, TW, B8>(coef_view(coef, im.comp[2]), m, im.dq[2], cr);
+		const uint32_t mc = WIN ? (uy0 + my) * pgx + ux0 + mx : m; /* chroma is 1 x 1: its block index is the MCU's */
+		sc_block<TH, TW, B8>(coef_view(coef, im.comp[1]), mc, im.dq[1], cb);
+		sc_block<TH, TW, B8>(coef_view(coef, im.comp[2]), mc, im.dq[2], cr);
 	}
 	const CoefView yv = coef_view(coef, im.comp[0]);
 	const uint32_t bw0 = (uint32_t)im.comp[0].bw;
@@ -233,7 +239,7 @@ __global__ __launch_bounds__(256) void k_scaled(const DevImage *__restrict__ img
 #pragma unroll
 		for (int dx = 0; dx < HM; ++dx) {
 			uint32_t ys[N][(N + 3) / 4];
-			sc_block<N, N, B8>(yv, (my * VM + dy) * bw0 + mx * HM + dx, im.dq[0], ys);
+			sc_block<N, N, B8>(yv, ((uy0 + my) * VM + dy) * bw0 + (ux0 + mx) * HM + dx, im.dq[0], ys);
 #pragma unroll
 			for (int y = 0; y < N; ++y) {
 				int r[N], g[N], b[N];
@@ -253,7 +259,7 @@ __global__ __launch_bounds__(256) void k_scaled(const DevImage *__restrict__ img
 		__syncthreads();
 		for (uint32_t sy = myA; sy <= myB; ++sy) { /* workgroup-uniform */
 			const uint32_t a = max(m0, sy * gx), e = min(m0 + cnt, (sy + 1u) * gx); /* MCUs [a, e) of MCU row sy */
-			const uint32_t x0 = (a - sy * gx) * TW, x1 = min((e - sy * gx) * TW, OW), Y0 = sy * TH + dy * N;
+			const uint32_t x0 = (ux0 + a - sy * gx) * TW, x1 = min((ux0 + e - sy * gx) * TW, OW), Y0 = (uy0 + sy) * TH + dy * N;
 			if (x1 <= x0 || Y0 >= OH)
 				continue;
 			sc_store_runs(lds, (a - m0) * pxb, rowb, out + ((size_t)Y0 * OW + x0) * n, (size_t)OW * n, (x1 - x0) * n, min((uint32_t)N, OH - Y0));

@@ -165,7 +165,7 @@ class TensorDecoder:
         return self._batch
 
     def decode(self, datas, *, req_comp=3, crops=None, flip_x=None, flip_y=None, layout="CHW", dtype=torch.float16, mean=None, std=None,
-               out=None, threads=16, size=None, filter="bilinear", orientation=None, reduce=None):
+               out=None, threads=16, size=None, filter="bilinear", orientation=None, reduce=None, roi=False):
         """-> (tensor, reasons).  crops: None (the whole picture; every picture the same size) or one (x0, y0, w, h) per picture, all of
         the same w and h.  size: None, or (out_h, out_w): each window is resized to it with filter (box, bilinear, hamming, bicubic or
         lanczos; the exact integer contract of mij_batch_set_out_tensor_resized, Pillow's for one channel, crop first), and windows and
@@ -180,7 +180,10 @@ class TensorDecoder:
         size and the tensor's shape are in that reduced (and oriented) frame; a picture whose layout has no reduced decode (4:4:0, 4:1:1,
         RGB-tagged, CMYK) is rejected with its reason when s > 1.  "auto" (needs size= and crops=None) takes per picture the largest s at
         which the displayed reduced picture is still at least out_w x out_h -- it never upsamples from a reduced picture -- and 1 for
-        layouts without a reduced decode."""
+        layouts without a reduced decode.  roi: False, or True: with crops, every picture decodes only the MCUs its window reads
+        (mij_batch_set_roi_auto; the tensor is the same, bit for bit); with crops=None it changes nothing."""
+        if not isinstance(roi, bool):
+            raise ValueError("roi must be False or True (got %r)" % (roi,))
         datas = list(datas)
         n = len(datas)
         if layout not in ("CHW", "HWC"):
@@ -308,6 +311,8 @@ class TensorDecoder:
             else:
                 b.set_out_tensor_resized(sl, out.data_ptr() + i * st[0] * es, _DT[dtype], lay, x0, y0, wins[i][2], wins[i][3], w, h, row_pitch,
                                          plane_pitch, fx[i], fy[i], tb, filter, orientation=orients[i])
+            if roi and crops is not None:
+                b.set_roi_auto(sl)
         torch.cuda.current_stream(self.device).synchronize()
         b.submit()
         b.wait()

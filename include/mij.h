@@ -297,6 +297,35 @@ int mij_batch_set_scale(mij_batch *b, int slot, int denom);
 /* the stored picture's size: the descriptor's, or the reduced one */
 int mij_batch_slot_out_size(const mij_batch *b, int slot, int *w, int *h);
 
+/*
+ * Region of interest: a slot may carry, before upload, a rectangle (x0, y0, w, h) in pixels of its STORED picture -- the reduced one when
+ * mij_batch_set_scale is in force, and before any orientation -- outside of which nothing needs to be decoded.  The Huffman walk and the
+ * coefficient planes are the whole picture's; the saving is in everything behind them (transform, upsampling, colour, pixel stores).
+ *   - Every pixel inside the rectangle is byte for byte what the slot holds without a region.
+ *   - The decode writes only inside a DECODED RECTANGLE, which mij_batch_slot_roi_rect reports after upload (the whole picture for a slot
+ *     without a region).  It contains the region.  Bytes of the slot's output region outside it are NOT WRITTEN AT ALL: they are
+ *     unspecified -- whatever the arena held -- for mij_batch_fetch, mij_batch_fetch_all_async and mij_batch_device_out, which return
+ *     the slot's region as it is.  mij_batch_hash_out and mij_batch_diff_slots refuse such a slot (MIJ_E_STATE).
+ *   - The slot keeps its full output region and pitch: nothing moves, and tensor requests address pixels as before.
+ *   - By kernel family (mij_batch_slot_path): 4:2:0, 4:4:0, grey, 4:4:4, RGB-tagged / CMYK / YCCK at 1x1 and the reduced-size decode skip
+ *     rows and columns -- the decoded rectangle is the region rounded out to MCU boundaries (8 x 8 blocks for the 1x1 families) and
+ *     clipped to the picture; the contract allows one MCU more on each side.  4:2:2 skips rows only: the decoded rectangle has the
+ *     picture's width.  Two-pass layouts accept the region and decode the picture whole.  A region that needs every MCU is dropped:
+ *     such a slot, and a batch without regions, launch exactly what they launch without this section.
+ * mij_batch_set_roi: w == 0 && h == 0 takes the region back; a later call replaces it; mij_batch_reset forgets it; clones start without.
+ * MIJ_E_ARG for an empty rectangle or one that leaves the stored picture and for a slot with a float request (mij_batch_set_out_f32
+ * refuses a slot with a region in turn); MIJ_E_STATE after upload.
+ * mij_batch_set_roi_auto(on): at upload the region becomes the slot's tensor request window mapped to the stored frame (orientations
+ * folded in; for a resized request the window is its crop, which the filter taps never leave).  An explicit region wins over it.
+ * Upload checks again, since region, scale and request may be set in any order: MIJ_E_ARG for a region outside the stored picture as
+ * the scale in force makes it, and for a tensor request whose stored-frame window leaves an explicit region; MIJ_E_STATE for an
+ * automatic region on a slot without a tensor request.
+ */
+int mij_batch_set_roi(mij_batch *b, int slot, int x0, int y0, int w, int h);
+int mij_batch_set_roi_auto(mij_batch *b, int slot, int on);
+/* the decoded rectangle (x0, y0, w, h in stored pixels) the last upload planned for the slot; MIJ_E_STATE before upload */
+int mij_batch_slot_roi_rect(const mij_batch *b, int slot, int rect[4]);
+
 /* ---- GPU entropy stage (experimental): the baseline Huffman walk itself on the GPU, for single-scan interleaved
  * baseline files, restart intervals included.  The host only parses headers and removes
  * the 0xFF00 byte stuffing (mjh_extract_scan, mij_host.h); coefficients never cross PCIe.  Any stream the GPU

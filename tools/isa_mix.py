@@ -1,8 +1,9 @@
-"""Instruction mix of one kernel in a hipcc -S dump: python3 tools/isa_mix.py dump.s kernel_substring [--blocks]"""
+"""Instruction mix of one kernel in a hipcc -S dump: python3 tools/isa_mix.py dump.s kernel_substring [--blocks]
+Of a kernel and its windowed twin (the same name with a DevRoi table) the first is meant, unless the substring says DevRoi."""
 import collections, re, sys
 s = open(sys.argv[1]).read().split('\n')
 name = sys.argv[2]
-start = next(i for i, l in enumerate(s) if re.match(r'^_ZN3mij\S*' + re.escape(name) + r'\S*:', l))
+start = next(i for i, l in enumerate(s) if re.match(r'^_ZN3mij\S*' + re.escape(name) + r'\S*:', l) and ('DevRoi' in name or 'DevRoi' not in l))
 end = next(i for i in range(start, len(s)) if s[i].strip().startswith('s_endpgm'))
 cnt = collections.Counter()
 blocks = []
