@@ -738,6 +738,12 @@ class Batch:
         L.mij_batch_entropy_anomaly.argtypes = [C.c_void_p, C.c_int]
         return _check(L.mij_batch_entropy_anomaly(self._h, int(slot)), "mij_batch_entropy_anomaly")
 
+    def work_items(self, slot):
+        """tests: work items the last upload put on the slot's own family list (mij_batch_slot_work_items); 0 for a skipped slot."""
+        L = lib()
+        L.mij_batch_slot_work_items.argtypes = [C.c_void_p, C.c_int]
+        return _check(L.mij_batch_slot_work_items(self._h, int(slot)), "mij_batch_slot_work_items")
+
     def slot_coef_bytes(self, slot):
         """1 when the slot's coefficients sit in HBM as compact planes (the default), 0 for the int16 tile layout."""
         return lib().mij_batch_slot_coef_bytes(self._h, int(slot))

@@ -295,6 +295,7 @@ struct Slot {
 	bool roi_on, roi_auto, reg;
 	int roi[4], reg_px[4], rect[4];
 	DevRoi win;
+	int work_items; /* of the last upload, on the slot's own family list (mij_batch_slot_work_items) */
 };
 static inline bool wants_region(const Slot &s) { return s.roi_on || s.roi_auto; }
 
@@ -635,6 +636,7 @@ static int add_common(mij_batch *b, const mij_image_desc *d, int clone_of, bool 
 	s.ten = -1;
 	s.scale = 1;
 	s.roi_on = s.roi_auto = s.reg = false;
+	s.work_items = 0;
 	if (clone_of < 0) {
 		if (b->stage_used + cbytes > b->stage_cap) {
 			if (!lazy_stage)
@@ -847,6 +849,15 @@ extern "C" int mij_batch_slot_roi_rect(const mij_batch *b, int slot, int rect[4]
 		rect[3] = out_h(s);
 	}
 	return MIJ_OK;
+}
+
+extern "C" int mij_batch_slot_work_items(const mij_batch *b, int slot)
+{
+	if (!b || slot < 0 || slot >= (int)b->slots.size())
+		return set_err(MIJ_E_ARG, "mij_batch_slot_work_items: bad slot");
+	if (!b->uploaded)
+		return set_err(MIJ_E_STATE, "mij_batch_slot_work_items before mij_batch_upload");
+	return b->slots[(size_t)slot].work_items;
 }
 
 extern "C" int mij_batch_set_color(mij_batch *b, int slot, int color)
@@ -1563,12 +1574,14 @@ static void plan_decode(mij_batch *b, Plan &p)
 		Slot &s = b->slots[i];
 		const mij_image_desc &d = s.desc;
 		const Choice &c = s.choice;
+		s.work_items = 0;
 		if (c.path == PATH_NONE)
 			continue;
 		if (host_staged(s) && s.coef_bytes_fmt && !(d.flags & MIJ_FLAG_STAGED_COMPACT)) /* int16 planes in the scratch -> compact planes */
 			push_tiles(p.pack, (uint32_t)i, d);
 		std::vector<Work4> &L = p.lists[c.kind][c.var];
 		size_t &lds = p.lds[c.kind][c.var];
+		const size_t before = L.size();
 		switch (c.path) {
 		case PATH_420:
 		case PATH_440: /* band count by rounds of co-resident workgroups */
@@ -1620,6 +1633,7 @@ static void plan_decode(mij_batch *b, Plan &p)
 			}
 		}
 		}
+		s.work_items = (int)(L.size() - before);
 		s.dev.src16_off = s.stage_off == MIJ_NO_STAGE ? 0 : s.stage_off;
 	}
 }

@@ -379,6 +379,10 @@ int mij_batch_fetch_coef(mij_batch *b, int slot, int16_t *dst, size_t dst_elems)
  * block; 8: no convergence; 16: data ran out inside a block; 32: a 0xff data byte behind the final bit position of the last segment;
  * 64: a restart interval ends a byte or more before its marker, or past it (k_es_dc).  Negative code for a slot the walk never had. */
 int mij_batch_entropy_anomaly(mij_batch *b, int slot);
+/* tests: how many work items the last upload put on the slot's own family list -- bands x column segments of the band kernels, one per 256
+ * lane units of a windowed or reduced-size slot, one per 256 blocks of an unwindowed 1x1 slot, pass 2's row groups of a two-pass slot (its
+ * pass-1 blocks and the pack kernel's tiles are not counted).  0 for a skipped slot; MIJ_E_STATE before upload, MIJ_E_ARG for a bad slot. */
+int mij_batch_slot_work_items(const mij_batch *b, int slot);
 /* The format new coefficient planes of this batch get in HBM: MIJ_COEF_COMPACT (default; environment
  * MIJ_COEF_FORMAT=int16 flips the default) or MIJ_COEF_INT16.  Applies to slots added or uploaded afterwards. */
 int mij_batch_set_coef_format(mij_batch *b, int fmt);

@@ -8,36 +8,15 @@ import pytest
 import torch
 
 import coef_cases as CC
-import orient_model as om
-import scaled_model as SM
+from roi_cases import MB, MCU, bound, dense, paint, rounded_out, run_windows, stored_window, want  # noqa: F401  (shared with test_gpu_roi_seams.py)
 
 pytestmark = pytest.mark.gpu
 
-MB = 1 << 20
 MIJ_E_ARG, MIJ_E_STATE = -2, -5
-# full-size MCU in pixels per layout
-MCU = {"420": (16, 16), "422": (16, 8), "440": (8, 16), "444": (8, 8), "grey": (8, 8), "cmyk": (8, 8), "411": (32, 8)}
 REDUCIBLE = ("420", "422", "444", "grey")
 SIZES = ((77, 45), (80, 48))
 
 _cache = {}
-
-
-def dense(layout, size, seed=0):
-    """every position of every block in use: small values, a DC ramp, and every seventh block with values beyond a byte (escaped)"""
-    k = ("dense", layout, size, seed)
-    if k not in _cache:
-        w, h = size
-        r = np.random.default_rng(1000 * seed + w * 7 + h)
-        planes = CC.blank(layout, w, h)
-        for pl in planes:
-            bh, bw, _ = pl.shape
-            pl[:] = r.integers(-9, 10, pl.shape)
-            pl[:, :, 0] = r.integers(-300, 301, (bh, bw))
-            i = np.arange(bh * bw).reshape(bh, bw)
-            pl[:, :, 1:6] += np.where((i % 7 == 3)[:, :, None], r.integers(-700, 701, (bh, bw, 5)), 0).astype(np.int16)
-        _cache[k] = CC.Case("roi_%s_%dx%d_%d" % (layout, w, h, seed), "dense", layout, w, h, planes)
-    return _cache[k]
 
 
 def wide_case(layout):
@@ -48,121 +27,11 @@ def wide_case(layout):
     return _cache[k]
 
 
-def want(oracle, case, req, s=1):
-    """the whole-picture decode: computed once per (case, channels, scale), shared, never changed"""
-    k = ("want", case.name, req, s)
-    if k not in _cache:
-        if s == 1:
-            kind, px, _ = oracle.load(case.stream(), req)
-            assert kind == "ok", case.name
-        else:
-            px = SM.scaled_picture(case.dequantised(), case.layout, (case.w, case.h), s, req)
-        px.setflags(write=False)
-        _cache[k] = px
-    return _cache[k]
-
-
-_hip = []
-
-
-def hip():
-    """the HIP runtime this process has already loaded"""
-    if not _hip:
-        with open("/proc/self/maps") as f:
-            path = next(ln.split()[-1] for ln in f if "libamdhip64" in ln)
-        h = C.CDLL(path)
-        h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        _hip.append(h)
-    return _hip[0]
-
-
-def paint(ica, b, slot, nbytes, seed):
-    """fills the slot's output region on the device with a byte pattern; -> the pattern"""
-    L = ica.lib()
-    L.mij_batch_device_out.restype = C.c_void_p
-    L.mij_batch_device_out.argtypes = [C.c_void_p, C.c_int]
-    pat = np.random.default_rng(seed).integers(0, 256, nbytes, dtype=np.uint8)
-    dst = L.mij_batch_device_out(b._h, int(slot))
-    assert dst
-    assert hip().hipMemcpy(C.c_void_p(dst), pat.ctypes.data_as(C.c_void_p), nbytes, 1) == 0
-    assert hip().hipDeviceSynchronize() == 0
-    return pat
-
-
 def windows(W, H, mw, mh):
     """centre pixel, one interior MCU, a 2 x 2 window across an MCU corner, the four corners, last column, last row, the whole picture"""
     assert W > 2 * mw and H > 2 * mh
     return [(W // 2, H // 2, 1, 1), (mw, mh, mw, mh), (mw - 1, mh - 1, 2, 2), (0, 0, 1, 1), (W - 1, 0, 1, 1), (0, H - 1, 1, 1), (W - 1, H - 1, 1, 1),
             (W - 1, 0, 1, H), (0, H - 1, W, 1), (0, 0, W, H)]
-
-
-def bound(path, win, W, H, mw, mh):
-    """the contract's bound on the decoded rectangle, as (x0, y0, x1, y1), for the kernel family the slot took (mij_batch_slot_path): the
-    region rounded out to MCUs, one MCU more on each side, clipped; 4:2:2 band kernel (4): rows only; two-pass (2): the whole picture"""
-    x0, y0, w, h = win
-    if path == 2:
-        return (0, 0, W, H)
-    bx0, bx1 = max(0, x0 // mw * mw - mw), min(W, -(-(x0 + w) // mw) * mw + mw)
-    by0, by1 = max(0, y0 // mh * mh - mh), min(H, -(-(y0 + h) // mh) * mh + mh)
-    return (0, by0, W, by1) if path == 4 else (bx0, by0, bx1, by1)
-
-
-def run_windows(ica, ctx, oracle, case, req, fmt, s, wins, producer="host", tag=()):
-    """one batch, one slot per window: upload, paint, launch, fetch; -> [(window, rect, picture)]"""
-    b = ica.Batch(ctx, len(wins), 64 * MB, 64 * MB, 128 * MB)
-    try:
-        b.set_coef_format(fmt)
-        if producer == "walk":
-            b.entropy_reserve(16 * MB)
-            slots = []
-            for _ in wins:
-                st, sl = b.add_jpeg_stream(case.stream(), req)
-                assert st == 1, case.name
-                slots.append(sl)
-            for sl in b.entropy_run():  # a stream the walk hands back: the host walk redoes it
-                b.fallback_prepare(sl)
-                d2, _ = ica.HostDecoder.decode(case.stream(), req, out=b.staging(sl))
-                if d2.flags:
-                    b.set_flags(sl, d2.flags)
-        else:
-            slots = [b.add_jpeg(case.stream(), req) for _ in wins]
-        for sl, win in zip(slots, wins):
-            if s > 1:
-                b.set_scale(sl, s)
-            b.set_roi(sl, *win)
-        b.upload()
-        b.wait()
-        px = want(oracle, case, req, s)
-        H, W, n = px.shape
-        pats = [paint(ica, b, sl, px.size, 17 + i).reshape(px.shape) for i, sl in enumerate(slots)]
-        b.launch()
-        b.wait()
-        mw, mh = MCU[case.layout][0] // s, MCU[case.layout][1] // s
-        res = []
-        for sl, win, pat in zip(slots, wins, pats):
-            t = (case.name, "req %d" % req, fmt, "s %d" % s, producer, win) + tuple(tag)
-            assert b.out_size(sl) == (W, H), t
-            got = b.fetch(sl)
-            x0, y0, w, h = win
-            rx, ry, rw, rh = rect = b.roi_rect(sl)
-            assert np.array_equal(got[y0:y0 + h, x0:x0 + w], px[y0:y0 + h, x0:x0 + w]), t + ("inside", rect)
-            outside = np.ones((H, W), bool)
-            outside[ry:ry + rh, rx:rx + rw] = False
-            assert np.array_equal(got[outside], pat[outside]), t + ("outside", rect, int((got[outside] != pat[outside]).sum()))
-            # the decoded rectangle: contains the region, and obeys the bound
-            assert rx <= x0 and ry <= y0 and rx + rw >= x0 + w and ry + rh >= y0 + h, t + (rect,)
-            path = b.slot_path(sl)
-            assert path == (8 if s > 1 else 5 if req < 3 and case.layout != "cmyk" else CC.PATH_OF[case.layout] if req >= 3 else 2), t + (path,)
-            bx0, by0, bx1, by1 = bound(path, win, W, H, mw, mh)
-            assert bx0 <= rx and by0 <= ry and rx + rw <= bx1 and ry + rh <= by1, t + (rect, (bx0, by0, bx1, by1))
-            if path in (2, 4):  # no column form: the picture's width; two-pass: the whole picture
-                assert rx == 0 and rw == W, t + (rect,)
-            if path == 2 or win == (0, 0, W, H):
-                assert rect == (0, 0, W, H) and np.array_equal(got, px), t + (rect,)
-            res.append((win, rect, got))
-        return res
-    finally:
-        b.close()
 
 
 # ------------------------------------------------------------------ 1. exactness inside, silence outside
@@ -268,25 +137,6 @@ def dec(ica, gpu_ctx):
     d = ica.TensorDecoder("cuda:0")
     yield d
     d.close()
-
-
-def stored_window(sw, sh, o, crop):
-    """the rectangle of the sw x sh stored picture that a crop (x0, y0, w, h) of the displayed picture (orientation o) reads, found by
-    orienting a picture of pixel indices: independent of the runtime's mapping"""
-    idx = np.arange(sw * sh, dtype=np.int64).reshape(sh, sw)
-    x0, y0, w, h = crop
-    sub = om.orient(idx, o)[y0:y0 + h, x0:x0 + w]
-    assert sub.shape == (h, w)
-    rows, cols = sub // sw, sub % sw
-    return int(cols.min()), int(rows.min()), int(cols.max() - cols.min() + 1), int(rows.max() - rows.min() + 1)
-
-
-def rounded_out(win, sw, sh, uw, uh, rows_only):
-    """the window rounded out to units of uw x uh stored pixels and clipped; rows_only: at the picture's width (4:2:2 band kernel)"""
-    x0, y0, w, h = win
-    rx0, rx1 = (0, sw) if rows_only else (x0 // uw * uw, min(sw, -(-(x0 + w) // uw) * uw))
-    ry0, ry1 = y0 // uh * uh, min(sh, -(-(y0 + h) // uh) * uh)
-    return rx0, ry0, rx1 - rx0, ry1 - ry0
 
 
 def test_tensor_path(ica, dec):
