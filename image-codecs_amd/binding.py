@@ -678,6 +678,12 @@ class Batch:
             raise MijError("mij_batch_stage_region: %s" % L.mij_last_error().decode())
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(nb.value,))
 
+    def set_dequant(self, slot, desc):
+        """mij_batch_set_dequant: the slot (and its clones) takes comp[].tq and the quantisation tables of desc"""
+        L = lib()
+        L.mij_batch_set_dequant.argtypes = [C.c_void_p, C.c_int, C.POINTER(ImageDesc)]
+        _check(L.mij_batch_set_dequant(self._h, int(slot), C.byref(desc)), "mij_batch_set_dequant")
+
     def set_flags(self, slot, flags):
         _check(lib().mij_batch_set_flags(self._h, int(slot), int(flags)), "mij_batch_set_flags")
         d = self._desc(slot)
@@ -825,6 +831,12 @@ class Batch:
         if d2.flags:
             _check(L.mij_batch_set_flags(self._h, slot, d2.flags), "mij_batch_set_flags")
             d.flags = d2.flags
+        if bytes(d2.dequant) != bytes(d.dequant) or any(d2.comp[c].tq != d.comp[c].tq for c in range(d.ncomp)):
+            # DQT segments behind SOF: the walk ended with other tables than the frame header saw (mjh_final_dequant)
+            self.set_dequant(slot, d2)
+            C.memmove(C.byref(d.dequant), C.byref(d2.dequant), C.sizeof(d.dequant))
+            for c in range(d.ncomp):
+                d.comp[c].tq = d2.comp[c].tq
         if d2.color != d.color:  # a JFIF / Adobe marker behind SOF changed the colour branch (codec/jpeg.c:2244)
             _check(L.mij_batch_set_color(self._h, slot, d2.color), "mij_batch_set_color")
             d.color = d2.color

@@ -35,6 +35,16 @@ typedef struct {
 	const char *todo; /* per image: 1 = the host walk has to do it */
 } pool_t;
 
+/* DQT segments behind the frame header: the slot was added with the tables as they stood there (mjh_final_dequant) */
+static void sync_tables(mij_batch *b, int slot, const mij_image_desc *now, const mij_image_desc *then)
+{
+	int c, differ = memcmp(now->dequant, then->dequant, sizeof(now->dequant)) != 0;
+	for (c = 0; c < now->ncomp; ++c)
+		differ |= now->comp[c].tq != then->comp[c].tq;
+	if (differ)
+		mij_batch_set_dequant(b, slot, now);
+}
+
 static void *worker(void *arg)
 {
 	pool_t *p = (pool_t *)arg;
@@ -62,6 +72,7 @@ static void *worker(void *arg)
 					mij_batch_set_flags(p->b, slot, d.flags);
 				if (d.color != p->descs[i].color) /* a JFIF / Adobe marker behind SOF changed the colour branch */
 					mij_batch_set_color(p->b, slot, d.color);
+				sync_tables(p->b, slot, &d, &p->descs[i]);
 				++good;
 			} else {
 				mij_batch_set_flags(p->b, slot, MIJ_FLAG_SKIP);
@@ -98,7 +109,7 @@ int mjh_decode_batch_host(mij_batch *b, const uint8_t *const *bufs, const int *l
 		reasons[i] = NULL;
 		if (!mjh_probe_memory(bufs[i], lens[i], req_comp, &p.descs[i], &why)) {
 			slots[i] = -1;
-			reasons[i] = why;
+			reasons[i] = why ? why : "decode failed"; /* (the parser sets no reason for a few failures; a rejected image always has one here) */
 			continue;
 		}
 		slots[i] = mij_batch_add_uncleared(b, &p.descs[i]); /* the worker's mjh_decode_memory clears the planes */
@@ -150,7 +161,7 @@ static void *extract_worker(void *arg)
 			p->status[i] = mjh_probe_memory(p->bufs[i], p->lens[i], p->req_comp, &p->scans[i].desc, &why) ? 2 : 0;
 		} else
 			p->status[i] = mjh_extract_scan(p->bufs[i], p->lens[i], p->req_comp, &p->scans[i], p->stage + p->off[i], p->cap[i], &p->slen[i], &why);
-		p->reasons[i] = why;
+		p->reasons[i] = p->status[i] == 0 && !why ? "decode failed" : why;
 	}
 	return NULL;
 }
@@ -559,6 +570,7 @@ static void *multi_worker(void *arg)
 					mij_batch_set_flags(b, slot, d.flags);
 				if (d.color != p->descs[i].color)
 					mij_batch_set_color(b, slot, d.color);
+				sync_tables(b, slot, &d, &p->descs[i]);
 				++good;
 			} else {
 				mij_batch_set_flags(b, slot, MIJ_FLAG_SKIP);
@@ -619,7 +631,7 @@ int mjh_decode_batch_multi(mij_batch *const *batches, int n_batches, const uint8
 		reasons[i] = NULL;
 		if (!mjh_probe_memory(bufs[i], lens[i], req_comp, &p->descs[i], &why)) {
 			slots[i] = -1;
-			reasons[i] = why;
+			reasons[i] = why ? why : "decode failed";
 			continue;
 		}
 		slots[i] = mij_batch_add_uncleared(batches[owner[i]], &p->descs[i]);

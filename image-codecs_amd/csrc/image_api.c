@@ -441,6 +441,11 @@ static void *load_main_counted(mjh_reader *r, int *x, int *y, int *comp, int req
 	}
 	if (mjh_stage_flags(d))
 		mij_batch_set_flags(b, slot, mjh_stage_flags(d));
+	/* DQT segments may follow SOF as well: the slot takes the tables the walk ended with */
+	if (mjh_final_dequant(d, &desc) && mij_batch_set_dequant(b, slot, &desc) != MIJ_OK) {
+		free(d);
+		return fail_ptr("gpu decode failed");
+	}
 	/* is_rgb / CMYK / YCCK are decided once every marker has been seen (codec/jpeg.c:2244): APP0 / APP14 may follow SOF */
 	if (mjh_color_mode(d, desc.n_out) != desc.color) {
 		desc.color = mjh_color_mode(d, desc.n_out);

@@ -1109,9 +1109,14 @@ static int parse_entropy_coded_data(mjh_decoder *d)
 	int ci, k;
 	entropy_reset(d);
 	for (ci = 0; ci < d->scan_n; ++ci) {
-		const uint16_t *q = d->dequant[d->comp[d->order[ci]].tq];
+		mjh_comp *cp = &d->comp[d->order[ci]];
+		const uint16_t *q = d->dequant[cp->tq];
 		for (k = 0; k < 64 + 15; ++k)
 			qz[ci][k] = q[k_dezigzag[k]];
+		if (!d->progressive) {
+			memcpy(cp->dq, q, sizeof(cp->dq));
+			cp->dq_set = 1;
+		}
 	}
 
 	if (!d->progressive) {
@@ -1431,6 +1436,7 @@ static int process_frame_header(mjh_decoder *d, int mode)
 		cp->bh = cp->h2 >> 3;
 		cp->plane = NULL;
 		cp->touched = 0;
+		cp->dq_set = 0;
 		/* the reference mallocs w2*h2+15 bytes here (and 2x that for progressive) */
 		if (!mul_fits_int(cp->w2, cp->h2) || cp->w2 * cp->h2 > INT_MAX - 15)
 			return fail(d, "outofmem");
@@ -1600,6 +1606,39 @@ int mjh_decode_scans(mjh_decoder *d)
 
 int mjh_needs_wide_idct(const mjh_decoder *d) { return d->max_block_l1 > MIJ_BLOCK_L1_LIMIT; }
 
+int mjh_final_dequant(const mjh_decoder *d, mij_image_desc *desc)
+{
+	const uint16_t *eff[4];
+	uint16_t tab[4][64];
+	int tq[4], i, j, n = 0, shared = 1, changed;
+	for (i = 0; i < d->img_n; ++i)
+		eff[i] = (!d->progressive && d->comp[i].dq_set) ? d->comp[i].dq : d->dequant[d->comp[i].tq];
+	for (i = 0; i < d->img_n; ++i)
+		for (j = 0; j < i; ++j)
+			if (d->comp[i].tq == d->comp[j].tq && memcmp(eff[i], eff[j], sizeof(tab[0])) != 0)
+				shared = 0; /* the table was redefined between the scans of two components that name it */
+	memcpy(tab, d->dequant, sizeof(tab));
+	for (i = 0; i < d->img_n; ++i) {
+		if (shared) {
+			tq[i] = d->comp[i].tq;
+		} else {
+			for (j = 0; j < i; ++j)
+				if (memcmp(eff[i], eff[j], sizeof(tab[0])) == 0)
+					break;
+			tq[i] = j < i ? tq[j] : n++;
+		}
+		memcpy(tab[tq[i]], eff[i], sizeof(tab[0]));
+	}
+	changed = memcmp(tab, desc->dequant, sizeof(tab)) != 0;
+	for (i = 0; i < d->img_n; ++i) {
+		if (desc->comp[i].tq != tq[i])
+			changed = 1;
+		desc->comp[i].tq = tq[i];
+	}
+	memcpy(desc->dequant, tab, sizeof(tab));
+	return changed;
+}
+
 /* ------------------------------------------------------------------ one-call memory forms */
 
 static int probe_common(mjh_decoder *d, mjh_reader *r, const uint8_t *buf, int len, int req_comp, mij_image_desc *desc, const char **reason)
@@ -1705,6 +1744,7 @@ int mjh_decode_memory_fmt(const uint8_t *buf, int len, int req_comp, mij_image_d
 		}
 		desc->flags |= mjh_stage_flags(d);
 		desc->color = mjh_color_mode(d, desc->n_out); /* JFIF / Adobe markers behind SOF count too (codec/jpeg.c:2244) */
+		mjh_final_dequant(d, desc);                   /* ... and so do DQT segments */
 		ok = 1;
 	}
 done:
@@ -1744,6 +1784,7 @@ int mjh_decode_memory(const uint8_t *buf, int len, int req_comp, mij_image_desc 
 		if (mjh_needs_wide_idct(d))
 			desc->flags |= MIJ_FLAG_WIDE_IDCT;
 		desc->color = mjh_color_mode(d, desc->n_out); /* JFIF / Adobe markers behind SOF count too (codec/jpeg.c:2244) */
+		mjh_final_dequant(d, desc);                   /* ... and so do DQT segments */
 		ok = 1;
 	}
 done:
@@ -1755,10 +1796,12 @@ done:
 
 /* ------------------------------------------------------------------ scan extraction for the GPU entropy stage
  *
- * Header parsing as above; then, if the file is what the GPU walk takes -- one baseline scan carrying all
- * components interleaved in frame order, the entropy data (cut at RSTn markers if a restart interval is set)
- * followed by EOI -- the
- * segment is copied out with its 0xFF00 stuffing removed (codec/jpeg.c:171-184) together with the tables.
+ * Header parsing as above; then, if the file is what the GPU walk takes -- a baseline frame (SOF0 or SOF1) of one
+ * or three components, at most ten blocks per MCU, a lone component sampled 1x1; every segment between the frame
+ * header and SOS accepted (no DNL, no EOI there); one scan carrying all components interleaved in frame order, the
+ * entropy data (cut at RSTn markers if a restart interval is set) followed by EOI -- the
+ * segment is copied out with its 0xFF00 stuffing removed (codec/jpeg.c:171-184) together with the tables
+ * (Huffman and quantisation) that are current at SOS.
  * Everything else returns 2 ("use the host walk"): that path then reproduces the reference's behaviour,
  * including its failure reasons, so nothing about odd files is decided here.
  */
@@ -1793,6 +1836,7 @@ int mjh_extract_scan(const uint8_t *buf, int len, int req_comp, mjg_scan *scan, 
 	if (!process_scan_header(d))
 		goto done;
 	scan->desc.color = mjh_color_mode(d, scan->desc.n_out); /* markers between SOF and SOS; EOI must follow the data (below) */
+	memcpy(scan->desc.dequant, d->dequant, sizeof(scan->desc.dequant)); /* DQT segments between SOF and SOS: the one scan takes the tables current here */
 	if (d->progressive || d->scan_n != d->img_n || (d->img_n != 1 && d->img_n != 3))
 		goto done;
 	for (ci = 0; ci < d->scan_n; ++ci)

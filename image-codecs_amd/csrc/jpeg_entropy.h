@@ -61,6 +61,10 @@ typedef struct {
 	int bw, bh;       /* blocks per row / rows of the padded grid */
 	int16_t *plane;   /* tile-layout staging plane (mij.h), owned by the caller */
 	int touched;      /* a previous scan already wrote blocks of this component */
+	/* baseline: the quantisation table that was current when the component's (last) scan was walked -- the reference de-quantises
+	 * a baseline block as it decodes it (codec/jpeg.c:325-365), so a DQT segment behind that scan no longer reaches the component */
+	uint16_t dq[64];
+	int dq_set;
 	/* compact staging (mjh_decoder.compact; baseline files only): low-byte tiles, int16 DC array, escape bytes (mij_compact_offsets) */
 	uint8_t *lo8;
 	int16_t *dc16;
@@ -120,6 +124,12 @@ int mjh_color_mode(const mjh_decoder *d, int n_out);
  * d->comp[i].plane (which the caller must have pointed at zero-filled tile-layout planes).
  * For progressive files every block's L1 is computed at the end.  Returns 1 / 0. */
 int mjh_decode_scans(mjh_decoder *d);
+
+/* After mjh_decode_scans: writes the tables the finished image is de-quantised with into desc->dequant (and desc->comp[].tq).
+ * mjh_describe copies the tables as they stand at the frame header, but DQT segments may follow it: a baseline component takes the
+ * table current at its scan, a progressive file the last definition of all (stbi__jpeg_finish, codec/jpeg.c:1319-1324).  Components
+ * that name one table id but were walked under different contents of it get ids of their own.  Returns 1 if desc changed. */
+int mjh_final_dequant(const mjh_decoder *d, mij_image_desc *desc);
 
 /* Non-zero if the finished image needs MIJ_FLAG_WIDE_IDCT. */
 int mjh_needs_wide_idct(const mjh_decoder *d);

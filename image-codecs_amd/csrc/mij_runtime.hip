@@ -572,6 +572,20 @@ static void layout_coef(Slot &s)
 	}
 }
 
+/* quantisation tables, natural order -> in-block position order P = 8*col + rowslot[row] */
+static void fill_dev_dequant(Slot &s)
+{
+	const mij_image_desc &d = s.desc;
+	for (int c = 0; c < d.ncomp; ++c) {
+		uint16_t q[64];
+		for (int row = 0; row < 8; ++row)
+			for (int col = 0; col < 8; ++col)
+				q[8 * col + mij_rowslot[row]] = d.dequant[d.comp[c].tq][8 * row + col];
+		for (int i = 0; i < 32; ++i)
+			s.dev.dq[c][i] = (uint32_t)q[2 * i] | ((uint32_t)q[2 * i + 1] << 16);
+	}
+}
+
 static void fill_dev_image(Slot &s, size_t out_off)
 {
 	const mij_image_desc &d = s.desc;
@@ -600,15 +614,9 @@ static void fill_dev_image(Slot &s, size_t out_off)
 		dc.vs = d.v_max / cp.v;
 		dc.plane_off = plane_off; /* relative; rebased at launch */
 		plane_off += align_up((size_t)cp.bw * 8 * cp.bh * 8, 256);
-		/* quantisation table, natural order -> in-block position order P = 8*col + rowslot[row] */
-		uint16_t q[64];
-		for (int row = 0; row < 8; ++row)
-			for (int col = 0; col < 8; ++col)
-				q[8 * col + mij_rowslot[row]] = d.dequant[cp.tq][8 * row + col];
-		for (int i = 0; i < 32; ++i)
-			v.dq[c][i] = (uint32_t)q[2 * i] | ((uint32_t)q[2 * i + 1] << 16);
 	}
 	v.plane_bytes_total = plane_off;
+	fill_dev_dequant(s);
 }
 
 #define MIJ_NO_STAGE ((size_t)-1)
@@ -874,6 +882,30 @@ extern "C" int mij_batch_set_color(mij_batch *b, int slot, int color)
 		return set_err(MIJ_E_ARG, "mij_batch_set_color: slot %d is decoded at 1/%d size, which colour mode %d does not support", slot, s.scale, color);
 	s.desc.color = color;
 	s.dev.color = color;
+	b->uploaded = b->launched = false;
+	return MIJ_OK;
+}
+
+extern "C" int mij_batch_set_dequant(mij_batch *b, int slot, const mij_image_desc *from)
+{
+	if (!b || !from || slot < 0 || slot >= (int)b->slots.size())
+		return set_err(MIJ_E_ARG, "mij_batch_set_dequant: bad slot or descriptor");
+	Slot &s = b->slots[(size_t)slot];
+	if (from->ncomp != s.desc.ncomp)
+		return set_err(MIJ_E_ARG, "mij_batch_set_dequant: the descriptor has %d components, slot %d has %d", from->ncomp, slot, s.desc.ncomp);
+	for (int c = 0; c < s.desc.ncomp; ++c)
+		if (from->comp[c].tq < 0 || from->comp[c].tq > 3)
+			return set_err(MIJ_E_ARG, "mij_batch_set_dequant: table id %d", from->comp[c].tq);
+	/* the slot and the clones made of it so far: they are the same picture (mij_batch_add_clone always names the root) */
+	for (size_t i = (size_t)slot; i < b->slots.size(); ++i) {
+		Slot &t = b->slots[i];
+		if ((int)i != slot && t.clone_of != slot)
+			continue;
+		for (int c = 0; c < t.desc.ncomp; ++c)
+			t.desc.comp[c].tq = from->comp[c].tq;
+		memcpy(t.desc.dequant, from->dequant, sizeof(t.desc.dequant));
+		fill_dev_dequant(t);
+	}
 	b->uploaded = b->launched = false;
 	return MIJ_OK;
 }

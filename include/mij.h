@@ -227,6 +227,12 @@ int mij_batch_set_flags(mij_batch *b, int slot, uint32_t flags);
  * is_rgb / CMYK / YCCK after the last marker, codec/jpeg.c:2244); the new mode must fit the slot's component count. */
 int mij_batch_set_color(mij_batch *b, int slot, int color);
 
+/* May be called after the entropy stage when DQT segments behind SOF changed the quantisation tables (the reference de-quantises a
+ * baseline block with the table current at its scan and a progressive file with the last definition): takes comp[].tq and dequant
+ * of *from, which must describe the slot's picture otherwise; clones already made of the slot take them too.  A caller that pairs
+ * mij_batch_add with mjh_decode_memory compares the descriptor the walk returns with the one it added, as for flags and colour. */
+int mij_batch_set_dequant(mij_batch *b, int slot, const mij_image_desc *from);
+
 /* submit = upload + launch.  All asynchronous on the batch's stream; wait blocks. */
 int mij_batch_upload(mij_batch *b); /* H2D of staged coefficients (+ D2D for clones) + descriptors */
 int mij_batch_launch(mij_batch *b); /* the decode kernels over every image of the batch */

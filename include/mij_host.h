@@ -54,7 +54,8 @@ int mjh_extract_scan(const uint8_t *buf, int len, int req_comp, mjg_scan *scan, 
  * Batch front end: n JPEGs into a mij batch.  Images are added to the batch in input order
  * (slots[i] = the slot of image i, or -1 with reasons[i] set when its header is rejected);
  * an image whose entropy data is rejected keeps its slot but is flagged MIJ_FLAG_SKIP (reasons[i]
- * set, slot reported as -1 - slot).  Follow with mij_batch_submit().  Returns the number of
+ * set, slot reported as -1 - slot).  reasons[i] is the parser's string, or "decode failed" for the few
+ * failures that set none (a DQT or DHT segment with bytes left over, a scan naming a component the frame lacks).  Follow with mij_batch_submit().  Returns the number of
  * images decoded successfully, or a negative MIJ_E_* code when the batch arenas are too small.
  *
  * mjh_decode_batch       the DEFAULT: the Huffman walk itself runs on the GPU wherever it applies (single-scan baseline

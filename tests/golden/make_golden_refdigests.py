@@ -10,6 +10,11 @@ call, keyed by the SHA-256 of the call and its input:
   idct                  "<length>:<SHA-256>" of the 8x8 output block
   verdicts/<req>/<group> one entry per generated list of streams (tests/stream_cases.py), keyed over all of them: one character per
                         stream ('0' ok, '1'.. a reason) and the reasons behind it -- verdict and reason only, no pixels
+  info                  "1 <x> <y> <comp>" or "0": stbi_info_from_memory
+
+The header families (tests/header_cases.py) are recorded in a child process each: the reference is built with its assertions live and
+ABORTS where a stream strays outside what it defines (a table used before it was defined, ...).  An abort here is an error of the case
+generator: the case belongs into header_cases.product_only, or the generator is wrong.  Nothing is written then.
 """
 import os
 import subprocess
@@ -30,6 +35,7 @@ TESTS = [
     "tests/test_progressive_writer.py::test_progressive_stream_carries_the_same_coefficients",
     "tests/test_progressive_writer.py::test_writer_streams_pin_the_oracle_to_the_live_reference",
 ]
+HEADER_FAMILIES = ["reasons", "segments", "frames", "scans", "tables"]
 
 if __name__ == "__main__":
     if not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libstbref.so")):
@@ -41,5 +47,11 @@ if __name__ == "__main__":
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider"] + TESTS, cwd=ROOT, env=env)
     if r.returncode != 0:
         sys.exit("the tests failed against the reference itself: nothing written")
+    for fam in HEADER_FAMILIES:
+        r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", "tests/test_headers_host.py::test_family_host[%s]" % fam], cwd=ROOT, env=env)
+        if r.returncode < 0 or r.returncode >= 128:
+            sys.exit("the reference aborted on family '%s' (exit status %d): a case outside its contract -- nothing written" % (fam, r.returncode))
+        if r.returncode != 0:
+            sys.exit("family '%s' failed against the reference itself: nothing written" % fam)
     os.replace(tmp, OUT)
     print("wrote", OUT, os.path.getsize(OUT), "bytes")

@@ -142,7 +142,13 @@ class Reference:
         L.ref_encode.restype = C.c_long
         L.ref_encode.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
         L.ref_idct_block.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.stbi_info_from_memory.argtypes = [C.c_char_p, C.c_int, P_INT, P_INT, P_INT]
         self.L = L
+
+    def info(self, data):
+        x, y, c = C.c_int(), C.c_int(), C.c_int()
+        ok = self.L.stbi_info_from_memory(bytes(data), len(data), x, y, c)
+        return ok, x.value, y.value, c.value
 
     def load(self, data, req=0):
         x, y, c = C.c_int(), C.c_int(), C.c_int()
@@ -166,6 +172,93 @@ class Reference:
         o = np.zeros(64, np.uint8)
         self.L.ref_idct_block(o.ctypes.data, 8, b.ctypes.data)
         return o
+
+
+def _dequantised_in_call_order(ica, desc, arena, progressive_order=False):
+    """tile-layout planes -> the reference's IDCT call order (MCU-interleaved for multi-component
+    baseline files; plane order for single-component and progressive files), de-quantised."""
+    planes = ica.detile_coefficients(desc, arena)
+    dq = [np.array(desc.dequant[desc.comp[i].tq][:], dtype=np.int32).reshape(8, 8) for i in range(desc.ncomp)]
+    blocks = []
+    if progressive_order or desc.ncomp == 1:
+        for ci in range(desc.ncomp):
+            cp = desc.comp[ci]
+            for j in range((cp.y + 7) >> 3):
+                for i in range((cp.x + 7) >> 3):
+                    blocks.append((planes[ci][j, i].astype(np.int32) * dq[ci]).astype(np.int16))
+    else:
+        for my in range(desc.mcu_y):
+            for mx in range(desc.mcu_x):
+                for ci in range(desc.ncomp):
+                    cp = desc.comp[ci]
+                    for y in range(cp.v):
+                        for x in range(cp.h):
+                            blocks.append((planes[ci][my * cp.v + y, mx * cp.h + x].astype(np.int32) * dq[ci]).astype(np.int16))
+    return np.stack(blocks).reshape(-1)
+
+
+def _walk_extracted_scan(scan, stream):
+    """Plain sequential Huffman walk over what mjh_extract_scan hands to the GPU stage (tables as copied,
+    unstuffed bytes): -> int16 [nblocks, 64] in zigzag order, DC predicted per component."""
+    bits = int.from_bytes(stream + b"\0" * 16, "big")
+    total = (len(stream) + 16) * 8
+
+    def window(p):
+        return (bits >> (total - p - 64)) & ((1 << 64) - 1)
+
+    tabs = [(bytes(h.fast), bytes(h.size), bytes(h.values), list(h.maxcode), list(h.delta)) for h in scan.huff]
+
+    def symbol(t, win):
+        fast, size, values, maxcode, delta = t
+        top16 = win >> 48
+        k = fast[top16 >> 7]
+        if k < 255:
+            return values[k], size[k]
+        n = 10
+        while top16 >= maxcode[n]:
+            n += 1
+        return values[((top16 >> (16 - n)) & ((1 << n) - 1)) + delta[n]], n
+
+    def extend(win, ln, n):
+        v = (win >> (64 - ln - n)) & ((1 << n) - 1)
+        return v if v >> (n - 1) else v - (1 << n) + 1
+
+    bpm = scan.blocks_per_mcu
+    out = np.zeros((scan.nblocks, 64), np.int64)
+    table = np.frombuffer(stream, np.uint32, count=2 * max(1, scan.n_seg), offset=scan.seg_table_off).reshape(-1, 2)
+    per_seg = scan.restart_mcus * bpm if scan.n_seg else scan.nblocks
+    pred = [0, 0, 0, 0]
+    p = 0
+    slack = []
+    for b in range(scan.nblocks):
+        if b % per_seg == 0:  # a restart interval starts byte aligned with fresh predictors
+            seg = b // per_seg
+            if seg:
+                slack.append(int(table[seg - 1, 0] + table[seg - 1, 1]) * 8 - p)
+            p = int(table[seg, 0]) * 8
+            pred = [0, 0, 0, 0]
+        ci = scan.blk_comp[b % bpm]
+        t, ln = symbol(tabs[scan.dc_tab[ci]], window(p))
+        diff = extend(window(p), ln, t) if t else 0
+        p += ln + t
+        pred[ci] += diff
+        out[b, 0] = pred[ci]
+        k = 1
+        while k < 64:
+            rs, ln = symbol(tabs[scan.ac_tab[ci]], window(p))
+            r, n = rs >> 4, rs & 15
+            if n == 0:
+                p += ln
+                if rs != 0xF0:
+                    break
+                k += 16
+                continue
+            k += r
+            out[b, k] = extend(window(p), ln, n)
+            p += ln + n
+            k += 1
+    slack.append(int(table[-1, 0] + table[-1, 1]) * 8 - p)
+    return out.astype(np.int16), max(slack)
 
 
 REF_DIGESTS = os.path.join(ROOT, "tests", "golden", "reference_digests.npz")
@@ -268,6 +361,13 @@ class StoredReference:
         parts = self._answer("verdicts/%d/%s" % (req, group), h.digest(), compute).split("|")
         assert len(parts[0]) == len(datas)
         return ["ok" if c == "0" else parts[1 + ord(c) - ord("1")] for c in parts[0]]
+
+    def info(self, data):
+        """the reference's stbi_info_from_memory(data) as "ok x y comp" (the numbers only where it answers 1)"""
+        def compute(r):
+            ok, x, y, c = r.info(data)
+            return "%d %d %d %d" % (ok, x, y, c) if ok else "0"
+        return self._answer("info", data, compute)
 
     def encode(self, img, q):
         """digest_bytes of the reference writer's stream"""

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import helpers
+from helpers import _dequantised_in_call_order, _walk_extracted_scan
 
 ROOT = helpers.ROOT
 
@@ -45,29 +46,6 @@ def test_info_matches_reference(golden, ica):
             assert (w, h, c) == tuple(int(v) for v in want[1:]), name
         else:
             assert ica.stbi_failure_reason() == "unknown image type"
-
-
-def _dequantised_in_call_order(ica, desc, arena, progressive_order=False):
-    """tile-layout planes -> the reference's IDCT call order (MCU-interleaved for multi-component
-    baseline files; plane order for single-component and progressive files), de-quantised."""
-    planes = ica.detile_coefficients(desc, arena)
-    dq = [np.array(desc.dequant[desc.comp[i].tq][:], dtype=np.int32).reshape(8, 8) for i in range(desc.ncomp)]
-    blocks = []
-    if progressive_order or desc.ncomp == 1:
-        for ci in range(desc.ncomp):
-            cp = desc.comp[ci]
-            for j in range((cp.y + 7) >> 3):
-                for i in range((cp.x + 7) >> 3):
-                    blocks.append((planes[ci][j, i].astype(np.int32) * dq[ci]).astype(np.int16))
-    else:
-        for my in range(desc.mcu_y):
-            for mx in range(desc.mcu_x):
-                for ci in range(desc.ncomp):
-                    cp = desc.comp[ci]
-                    for y in range(cp.v):
-                        for x in range(cp.h):
-                            blocks.append((planes[ci][my * cp.v + y, mx * cp.h + x].astype(np.int32) * dq[ci]).astype(np.int16))
-    return np.stack(blocks).reshape(-1)
 
 
 def test_host_entropy_stage_matches_reference_coefficients(golden, ica, oracle):
@@ -216,70 +194,6 @@ def test_decode_fails_loudly_without_gpu(golden, ica):
         ica.Context()
 
 
-def _walk_extracted_scan(scan, stream):
-    """Plain sequential Huffman walk over what mjh_extract_scan hands to the GPU stage (tables as copied,
-    unstuffed bytes): -> int16 [nblocks, 64] in zigzag order, DC predicted per component."""
-    bits = int.from_bytes(stream + b"\0" * 16, "big")
-    total = (len(stream) + 16) * 8
-
-    def window(p):
-        return (bits >> (total - p - 64)) & ((1 << 64) - 1)
-
-    tabs = [(bytes(h.fast), bytes(h.size), bytes(h.values), list(h.maxcode), list(h.delta)) for h in scan.huff]
-
-    def symbol(t, win):
-        fast, size, values, maxcode, delta = t
-        top16 = win >> 48
-        k = fast[top16 >> 7]
-        if k < 255:
-            return values[k], size[k]
-        n = 10
-        while top16 >= maxcode[n]:
-            n += 1
-        return values[((top16 >> (16 - n)) & ((1 << n) - 1)) + delta[n]], n
-
-    def extend(win, ln, n):
-        v = (win >> (64 - ln - n)) & ((1 << n) - 1)
-        return v if v >> (n - 1) else v - (1 << n) + 1
-
-    bpm = scan.blocks_per_mcu
-    out = np.zeros((scan.nblocks, 64), np.int64)
-    table = np.frombuffer(stream, np.uint32, count=2 * max(1, scan.n_seg), offset=scan.seg_table_off).reshape(-1, 2)
-    per_seg = scan.restart_mcus * bpm if scan.n_seg else scan.nblocks
-    pred = [0, 0, 0, 0]
-    p = 0
-    slack = []
-    for b in range(scan.nblocks):
-        if b % per_seg == 0:  # a restart interval starts byte aligned with fresh predictors
-            seg = b // per_seg
-            if seg:
-                slack.append(int(table[seg - 1, 0] + table[seg - 1, 1]) * 8 - p)
-            p = int(table[seg, 0]) * 8
-            pred = [0, 0, 0, 0]
-        ci = scan.blk_comp[b % bpm]
-        t, ln = symbol(tabs[scan.dc_tab[ci]], window(p))
-        diff = extend(window(p), ln, t) if t else 0
-        p += ln + t
-        pred[ci] += diff
-        out[b, 0] = pred[ci]
-        k = 1
-        while k < 64:
-            rs, ln = symbol(tabs[scan.ac_tab[ci]], window(p))
-            r, n = rs >> 4, rs & 15
-            if n == 0:
-                p += ln
-                if rs != 0xF0:
-                    break
-                k += 16
-                continue
-            k += r
-            out[b, k] = extend(window(p), ln, n)
-            p += ln + n
-            k += 1
-    slack.append(int(table[-1, 0] + table[-1, 1]) * 8 - p)
-    return out.astype(np.int16), max(slack)
-
-
 def test_extracted_scan_walks_to_the_host_walk_coefficients(golden, ica):
     """What the GPU entropy stage is given (mjh_extract_scan: copied tables, unstuffed segment, block order)
     decodes, with a plain sequential walk, to exactly the host walk's coefficients; layouts outside its scope
@@ -351,6 +265,13 @@ def test_host_stage_is_clean_under_sanitizers(golden, ica, tmp_path):
         f = tmp_path / ("%04d.jpg" % k)
         f.write_bytes(bytes(d))
         files.append(str(f))
+    # the header families (header_cases.py), those outside the reference's contract included: as they are
+    import header_cases
+    for fam in list(header_cases.FAMILIES) + ["product_only"]:
+        for k, c in enumerate(header_cases.family(fam)):
+            f = tmp_path / ("%s_%04d.jpg" % (fam, k))
+            f.write_bytes(c.data)
+            files.append(str(f))
     run = subprocess.run([exe] + files, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     assert run.returncode == 0, run.stderr[-2000:]
     assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr[-2000:]

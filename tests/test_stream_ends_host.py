@@ -20,7 +20,7 @@ import pytest
 
 import helpers
 import stream_cases as sc
-from test_host_cpu import _dequantised_in_call_order
+from helpers import _dequantised_in_call_order
 
 
 def _references():
