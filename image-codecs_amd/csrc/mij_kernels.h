@@ -2964,12 +2964,24 @@ __global__ __launch_bounds__(256) void k_out_f32(const DevF32 *__restrict__ fs, 
  * stages the band's source bytes in LDS as aligned dwords (the first one may start before the window); phase 2 walks each output
  * line -- a window row for HWC, one channel of a window row for CHW -- in units: a head up to the first 16-byte boundary of the
  * destination, then 16-byte aligned stores, then a tail.  The head and the tail are stored element by element, so nothing outside
- * the destination elements is written whatever the alignment and pitches.  CHW de-interleaves by reading the staged bytes from LDS. */
+ * the destination elements is written whatever the alignment and pitches.  CHW de-interleaves by reading the staged bytes from LDS.
+ *
+ * Oriented requests (mij_batch_set_out_tensor_oriented).  Orientations 2..4 only mirror the stored picture: the host composes the
+ * mirror with the request's flips (and, with a resize, mirrors that axis's coefficients), so k_out_tensor and k_out_resize run them
+ * unchanged.  Orientations 5..8 transpose.  The host folds their mirrors the same way, which leaves one case for k_out_tensor_t and
+ * k_out_resize_t: the window's output row r (before flips) is stored column x0 + r and its output column q is stored row y0 + q.
+ * DevTensor keeps its fields with that meaning: x0, y0 the stored column and row of the window's corner, w the output columns (stored
+ * rows), h the output rows (stored columns), the flips those of the output.  Both transposed kernels stage whole stored-row segments,
+ * shifted so that each starts on a dword, at a pitch of an odd number of dwords: lanes that read down a staged column then fall on
+ * different LDS banks.  A transposed kernel is the TR instantiation of the plain one's body: it differs in how phase 1 fills the
+ * stage and in where a staged byte lies, and shares the rest -- the store phase (tensor_store), the resize arithmetic (resize_item),
+ * the table fill and the dispatch on element type, layout and channel count. */
 #define MIJ_TEN_ITEM_BYTES 24576u /* source bytes per work item */
 #define MIJ_TEN_MAX_ROWS 128u     /* window rows per work item (bounds the dword slack of phase 1) */
 #define MIJ_TEN_STAGE_WORDS ((MIJ_TEN_ITEM_BYTES + 8u * MIJ_TEN_MAX_ROWS) / 4u)
 #define MIJ_TEN_LUT_BYTES 4096u   /* bytes per request in the table area: four 256-entry tables of up to 4-byte elements */
 #define MIJ_TEN_LDS_PAD 32u       /* bytes between the channel tables in LDS: each channel starts 8 banks further on */
+#define MIJ_TEN_LUT_WORDS (4u * (1024u + MIJ_TEN_LDS_PAD) / 4u) /* a request's tables in LDS, dwords */
 
 struct DevTensor { /* one slot that asked for tensor output */
 	uint64_t src_off;               /* byte offset of its n_out*W*H bytes in the output arena */
@@ -2988,11 +3000,54 @@ struct WorkTensor { /* window rows [row0, row0 + nrows) x window columns [p0, p0
 
 typedef uint32_t u4v __attribute__((ext_vector_type(4)));
 
-/* Phase 2 of a tensor work item, shared by k_out_tensor and k_out_resize: store nr rows x np columns of staged bytes (row r's
- * n_out-interleaved bytes at srow_of(r), in the order of the window, unflipped in x) to destination rows [row0, row0 + nr) and columns
- * [p0, p0 + np) of request s, flipping columns when s.flip_x and looking each value up in its channel's table. */
-template <typename T, bool CHW, int N, typename RowOf>
-__device__ __forceinline__ void tensor_store(const DevTensor &s, uint32_t row0, uint32_t p0, uint32_t nr, uint32_t np, const uint8_t *lut, RowOf srow_of)
+/* request t's tables from the plan into lutw, MIJ_TEN_LDS_PAD bytes between the channels; the caller's next __syncthreads orders
+ * these writes before the lookups */
+__device__ __forceinline__ void lut_fill(uint32_t *lutw, const DevTensor &s, const uint8_t *__restrict__ luts, uint32_t t)
+{
+	if (!s.lut)
+		return;
+	const uint32_t tw = 64u * s.esize, lsw = tw + MIJ_TEN_LDS_PAD / 4u; /* dwords per table in the plan, per table in LDS */
+	const uint32_t *g = reinterpret_cast<const uint32_t *>(luts + (size_t)t * MIJ_TEN_LUT_BYTES);
+	for (uint32_t i = threadIdx.x; i < s.n_out * tw; i += 256u)
+		lutw[(i / tw) * lsw + i % tw] = g[i];
+}
+
+/* f(Elem<T, CHW, N>{}) with request s's element type, layout and channel count: the one place that turns them into template arguments */
+template <typename T, bool CHW, int N>
+struct Elem {
+	using type = T;
+	static constexpr bool chw = CHW;
+	static constexpr int n = N;
+};
+template <typename T, bool CHW, typename F>
+__device__ __forceinline__ void for_channels(uint32_t n_out, F f)
+{
+	switch (n_out) {
+	case 1: f(Elem<T, CHW, 1>{}); break;
+	case 2: f(Elem<T, CHW, 2>{}); break;
+	case 3: f(Elem<T, CHW, 3>{}); break;
+	default: f(Elem<T, CHW, 4>{}); break;
+	}
+}
+template <typename F>
+__device__ __forceinline__ void for_elem(const DevTensor &s, F f)
+{
+	switch (s.esize * 2u + s.chw) {
+	case 2: for_channels<uint8_t, false>(s.n_out, f); break;
+	case 3: for_channels<uint8_t, true>(s.n_out, f); break;
+	case 4: for_channels<uint16_t, false>(s.n_out, f); break;
+	case 5: for_channels<uint16_t, true>(s.n_out, f); break;
+	case 8: for_channels<uint32_t, false>(s.n_out, f); break;
+	default: for_channels<uint32_t, true>(s.n_out, f); break;
+	}
+}
+
+/* Phase 2 of a tensor work item, shared by the four kernels: store nr rows x np columns of staged bytes to destination rows
+ * [row0, row0 + nr) and columns [p0, p0 + np) of request s, flipping columns when s.flip_x and looking each value up in its channel's
+ * table.  line_at(r) is called once per output line and gives row r's bytes as byte(q, c): the staged byte of column q (the output
+ * column after s.flip_x) and channel c.  What depends on r alone -- a row pointer -- is so computed once per line, not per element. */
+template <typename T, bool CHW, int N, typename LineAt>
+__device__ __forceinline__ void tensor_store(const DevTensor &s, uint32_t row0, uint32_t p0, uint32_t nr, uint32_t np, const uint8_t *lut, LineAt line_at)
 {
 	constexpr uint32_t ES = sizeof(T), V = 16u / ES, LS = 256u * ES + MIJ_TEN_LDS_PAD, PW = 4u / ES;
 	const uint32_t nb = np * N;
@@ -3000,7 +3055,7 @@ __device__ __forceinline__ void tensor_store(const DevTensor &s, uint32_t row0, 
 	for (uint32_t i = threadIdx.x; i < nl * um; i += 256u) {
 		const uint32_t line = i / um, u = i - line * um;
 		const uint32_t r = CHW ? line / N : line, pc = CHW ? line - r * N : 0u, oy = row0 + r;
-		const uint8_t *srow = srow_of(r);
+		const auto byte = line_at(r);
 		T *d = reinterpret_cast<T *>(s.dst) + (int64_t)oy * s.row_pitch + (CHW ? (int64_t)pc * s.plane_pitch + p0 : (int64_t)p0 * N);
 		const uint32_t head = (uint32_t)(((16u - ((uintptr_t)d & 15u)) & 15u) / ES);
 		const uint32_t e0 = u ? head + (u - 1u) * V : 0u;
@@ -3009,7 +3064,7 @@ __device__ __forceinline__ void tensor_store(const DevTensor &s, uint32_t row0, 
 			continue;
 		auto value = [&](uint32_t e) -> T {
 			const uint32_t q = CHW ? e : e / N, c = CHW ? pc : e - q * N;
-			const uint32_t v = srow[(s.flip_x ? np - 1u - q : q) * N + c];
+			const uint32_t v = byte(s.flip_x ? np - 1u - q : q, c);
 			return s.lut ? reinterpret_cast<const T *>(lut + c * LS)[v] : (T)v;
 		};
 		if (u && e1 - e0 == V) { /* 16-byte aligned: one store */
@@ -3030,6 +3085,16 @@ __device__ __forceinline__ void tensor_store(const DevTensor &s, uint32_t row0, 
 	}
 }
 
+/* dword k of the bytes [a, a + nb) of `out`, read as the aligned dwords that hold them (none past the one that holds byte nb - 1) */
+__device__ __forceinline__ uint32_t staged_dword(const uint8_t *__restrict__ out, uint64_t a, uint32_t k, uint32_t nb)
+{
+	const uint32_t sh = (uint32_t)(a & 3u), nd = (sh + nb + 3u) >> 2;
+	const uint32_t *p = reinterpret_cast<const uint32_t *>(out + (a & ~(uint64_t)3)) + k;
+	const uint32_t lo = __builtin_nontemporal_load(p), hi = k + 1u < nd ? __builtin_nontemporal_load(p + 1) : 0u;
+	return __builtin_amdgcn_alignbyte(hi, lo, sh);
+}
+
+/* k_out_tensor's work item: phase 1 stages window row r's bytes as the aligned dwords that hold them, at r * lsd dwords */
 template <typename T, bool CHW, int N>
 __device__ __forceinline__ void tensor_item(const DevTensor &s, const WorkTensor &wk, const uint8_t *__restrict__ out, const uint8_t *lut, uint32_t *stage)
 {
@@ -3049,44 +3114,63 @@ __device__ __forceinline__ void tensor_item(const DevTensor &s, const WorkTensor
 	const uint8_t *sb = reinterpret_cast<const uint8_t *>(stage);
 	tensor_store<T, CHW, N>(s, wk.row0, wk.p0, nr, np, lut, [&](uint32_t r) {
 		const uint32_t oy = wk.row0 + r, sy = s.flip_y ? s.y0 + s.h - 1u - oy : s.y0 + oy;
-		return sb + r * lsd * 4u + (uint32_t)((s.src_off + sy * rowb + (uint64_t)sxa * N) & 3u);
+		const uint8_t *srow = sb + r * lsd * 4u + (uint32_t)((s.src_off + sy * rowb + (uint64_t)sxa * N) & 3u);
+		return [=](uint32_t q, uint32_t c) -> uint32_t { return srow[q * N + c]; };
 	});
 }
 
-template <typename T, bool CHW>
-__device__ __forceinline__ void tensor_item_n(const DevTensor &s, const WorkTensor &wk, const uint8_t *__restrict__ out, const uint8_t *lut, uint32_t *stage)
+/* k_out_tensor_t's work item: output rows [row0, row0 + nrows) x output columns [p0, p0 + np), i.e. np stored-row segments of nrows
+ * stored columns.  Phase 1 stages segment q (ascending stored rows) at q * lsd dwords; phase 2 reads (r, q, c) down staged column r. */
+template <typename T, bool CHW, int N>
+__device__ __forceinline__ void tensor_item_t(const DevTensor &s, const WorkTensor &wk, const uint8_t *__restrict__ out, const uint8_t *lut, uint32_t *stage)
 {
-	switch (s.n_out) {
-	case 1: tensor_item<T, CHW, 1>(s, wk, out, lut, stage); break;
-	case 2: tensor_item<T, CHW, 2>(s, wk, out, lut, stage); break;
-	case 3: tensor_item<T, CHW, 3>(s, wk, out, lut, stage); break;
-	default: tensor_item<T, CHW, 4>(s, wk, out, lut, stage); break;
+	const uint32_t np = wk.np, nr = wk.nrows, nb = nr * N, nw = (nb + 3u) >> 2, lsd = nw | 1u;
+	const uint32_t sx = s.flip_y ? s.x0 + s.h - wk.row0 - nr : s.x0 + wk.row0; /* first stored column of the tile */
+	const uint32_t sy = s.flip_x ? s.y0 + s.w - wk.p0 - np : s.y0 + wk.p0;     /* first stored row of the tile */
+	const uint64_t rowb = (uint64_t)s.src_w * N, a0 = s.src_off + (uint64_t)sy * rowb + (uint64_t)sx * N;
+	for (uint32_t i = threadIdx.x; i < np * nw; i += 256u) {
+		const uint32_t q = i / nw, k = i - q * nw;
+		stage[q * lsd + k] = staged_dword(out, a0 + (uint64_t)q * rowb, k, nb);
 	}
+	__syncthreads();
+	const uint8_t *sb = reinterpret_cast<const uint8_t *>(stage);
+	tensor_store<T, CHW, N>(s, wk.row0, wk.p0, nr, np, lut, [&](uint32_t r) {
+		const uint8_t *scol = sb + (s.flip_y ? nr - 1u - r : r) * (uint32_t)N;
+		return [=](uint32_t q, uint32_t c) -> uint32_t { return scol[q * lsd * 4u + c]; };
+	});
 }
 
+/* the body of k_out_tensor (TR false) and k_out_tensor_t (TR true) */
+template <bool TR>
+__device__ __forceinline__ void out_tensor(const DevTensor *__restrict__ ts, const WorkTensor *__restrict__ work, const uint8_t *__restrict__ luts,
+														 const uint8_t *__restrict__ out)
+{
+	__shared__ uint32_t stage[MIJ_TEN_STAGE_WORDS];
+	__shared__ uint32_t lutw[MIJ_TEN_LUT_WORDS];
+	const WorkTensor wk = work[blockIdx.x];
+	const DevTensor s = ts[wk.t];
+	lut_fill(lutw, s, luts, wk.t);
+	const uint8_t *lut = reinterpret_cast<const uint8_t *>(lutw);
+	/* the item's __syncthreads orders the table writes before the lookups */
+	for_elem(s, [&](auto e) {
+		using E = decltype(e);
+		if constexpr (TR)
+			tensor_item_t<typename E::type, E::chw, E::n>(s, wk, out, lut, stage);
+		else
+			tensor_item<typename E::type, E::chw, E::n>(s, wk, out, lut, stage);
+	});
+}
+
+/* two kernels rather than one template, so that traces and profiles keep the names they know */
 __global__ __launch_bounds__(256) void k_out_tensor(const DevTensor *__restrict__ ts, const WorkTensor *__restrict__ work, const uint8_t *__restrict__ luts,
 																	 const uint8_t *__restrict__ out)
 {
-	__shared__ uint32_t stage[MIJ_TEN_STAGE_WORDS];
-	__shared__ uint32_t lutw[4u * (1024u + MIJ_TEN_LDS_PAD) / 4u];
-	const WorkTensor wk = work[blockIdx.x];
-	const DevTensor s = ts[wk.t];
-	if (s.lut) {
-		const uint32_t tw = 64u * s.esize, lsw = tw + MIJ_TEN_LDS_PAD / 4u; /* dwords per table in the plan, per table in LDS */
-		const uint32_t *g = reinterpret_cast<const uint32_t *>(luts + (size_t)wk.t * MIJ_TEN_LUT_BYTES);
-		for (uint32_t t = threadIdx.x; t < s.n_out * tw; t += 256u)
-			lutw[(t / tw) * lsw + t % tw] = g[t];
-	}
-	const uint8_t *lut = reinterpret_cast<const uint8_t *>(lutw);
-	/* tensor_item's __syncthreads orders the table writes before the lookups */
-	switch (s.esize * 2u + s.chw) {
-	case 2: tensor_item_n<uint8_t, false>(s, wk, out, lut, stage); break;
-	case 3: tensor_item_n<uint8_t, true>(s, wk, out, lut, stage); break;
-	case 4: tensor_item_n<uint16_t, false>(s, wk, out, lut, stage); break;
-	case 5: tensor_item_n<uint16_t, true>(s, wk, out, lut, stage); break;
-	case 8: tensor_item_n<uint32_t, false>(s, wk, out, lut, stage); break;
-	default: tensor_item_n<uint32_t, true>(s, wk, out, lut, stage); break;
-	}
+	out_tensor<false>(ts, work, luts, out);
+}
+__global__ __launch_bounds__(256) void k_out_tensor_t(const DevTensor *__restrict__ ts, const WorkTensor *__restrict__ work, const uint8_t *__restrict__ luts,
+																		const uint8_t *__restrict__ out)
+{
+	out_tensor<true>(ts, work, luts, out);
 }
 
 /* ------------------------------------------------------------------ resized tensor output (mij_batch_set_out_tensor_resized)
@@ -3101,7 +3185,11 @@ __global__ __launch_bounds__(256) void k_out_tensor(const DevTensor *__restrict_
  * walked in chunks of columns, one row per round, the partial sums kept in a register -- the sums are integers, so their order does
  * not matter.  The segment's horizontal taps sit in LDS when they fit (MIJ_RSZ_KCAP) and are read from the plan otherwise, so LDS
  * and registers stay bounded for any ratio; so do the band's vertical taps (MIJ_RSZ_VCAP).  All arithmetic is 32-bit integer: 24-bit multiplies when every |k| < 2^23 (the host
- * checks), full 32-bit ones otherwise. */
+ * checks), full 32-bit ones otherwise.
+ * k_out_resize_t does the same for a transposed request, whose first (horizontal) pass runs down the stored columns: the span is one
+ * of stored rows (relative to t.y0), the band's vertical taps read stored columns (relative to t.x0).  A round stages the span's
+ * stored rows x R stored columns, each row's R * n_out bytes at an odd pitch of dwords, and each lane sums its horizontal taps down a
+ * staged column; a span of more rows than the stage holds is walked in chunks of rows, one column per round. */
 #define MIJ_RSZ_STAGE_WORDS 4096u /* 16 KiB of staged source bytes */
 #define MIJ_RSZ_KCAP 3072u        /* horizontal taps of a segment held in LDS */
 #define MIJ_RSZ_VCAP 1024u        /* vertical taps of a band held in LDS */
@@ -3126,8 +3214,38 @@ __device__ __forceinline__ int32_t rsz_mac(int32_t acc, uint32_t x, int32_t k)
 	return M32 ? acc + (int32_t)x * k : acc + __mul24((int32_t)x, k);
 }
 
-/* the item's resized bytes: nr rows of nc * n_out bytes (channels interleaved) at `ob`, which aliases the stage */
-template <bool M32, bool KG>
+/* How a round fills the stage, for a span of `span` taps positions and n channels.  A round stages R positions of the vertical pass
+ * (plain: source rows; transposed: stored columns) x a chunk of at most cc positions of the span; a staged line (plain: a source row's
+ * chunk of columns; transposed: a stored row's R columns) takes ld dwords.  one: the whole span in one chunk, several R per round. */
+struct RszStage {
+	bool one;
+	uint32_t cc, ld, R;
+};
+template <bool TR>
+__device__ __forceinline__ RszStage rsz_stage(uint32_t span, uint32_t n)
+{
+	RszStage g;
+	if (TR) {
+		g.one = span <= MIJ_RSZ_STAGE_WORDS;
+		uint32_t ldm = g.one ? MIJ_RSZ_STAGE_WORDS / span : 1u;
+		ldm -= (ldm & 1u) ^ 1u; /* odd */
+		g.R = g.one ? ldm * 4u / n : 1u;
+		g.ld = g.one ? (((g.R * n + 3u) >> 2) | 1u) : 1u;
+		g.cc = g.one ? span : MIJ_RSZ_STAGE_WORDS;
+	} else {
+		const uint32_t ccmax = (MIJ_RSZ_STAGE_WORDS * 4u - 8u) / n;
+		g.one = span <= ccmax;
+		g.cc = g.one ? span : ccmax;
+		g.ld = (g.cc * n + 6u) >> 2; /* room for a start up to 3 bytes early */
+		g.R = g.one ? MIJ_RSZ_STAGE_WORDS / g.ld : 1u;
+	}
+	return g;
+}
+
+/* the item's resized bytes: nr rows of nc * n_out bytes (channels interleaved) at `ob`, which aliases the stage.  TR: the request is
+ * transposed.  sx0..sx1 is the span the segment's horizontal taps read and sy0..sy1 what the band's vertical taps read: source columns
+ * and rows of the window when plain, stored rows and columns when transposed. */
+template <bool M32, bool KG, bool TR>
 __device__ __forceinline__ void resize_item(const DevResize &s, const WorkResize &wk, const uint8_t *__restrict__ plan, const uint8_t *__restrict__ out,
 														  uint32_t *stage, int32_t *kl, int32_t *vkl)
 {
@@ -3147,267 +3265,7 @@ __device__ __forceinline__ void resize_item(const DevResize &s, const WorkResize
 	if (!vg)
 		for (uint32_t i = tid; i < nr * ksv; i += 256u)
 			vkl[i] = vk[(size_t)q0 * ksv + i];
-	/* the band's vertical taps: output row q0 + j reads source rows [vlo[j], vlo[j] + vn[j]) */
-	uint32_t vlo[MIJ_RSZ_ROWS], vn[MIJ_RSZ_ROWS];
-	int32_t acc[MIJ_RSZ_ROWS];
-#pragma unroll
-	for (uint32_t j = 0; j < MIJ_RSZ_ROWS; ++j) {
-		vlo[j] = j < nr ? (uint32_t)vln[2u * (q0 + j)] : 0u;
-		vn[j] = j < nr ? (uint32_t)vln[2u * (q0 + j) + 1u] : 0u;
-		acc[j] = 1 << 21;
-	}
-	const uint32_t sy0 = vlo[0], sy1 = (uint32_t)(vln[2u * (q0 + nr - 1u)] + vln[2u * (q0 + nr - 1u) + 1u]);
-	const uint32_t span = sx1 - sx0, ccmax = (MIJ_RSZ_STAGE_WORDS * 4u - 8u) / N;
-	const bool one = span <= ccmax; /* the whole span in one chunk: several rows per round */
-	const uint32_t cc = one ? span : ccmax, ld = (cc * N + 6u) >> 2; /* dwords per staged row: room for a start up to 3 bytes early */
-	const uint32_t R = one ? MIJ_RSZ_STAGE_WORDS / ld : 1u;
-	const uint64_t rowb = (uint64_t)s.t.src_w * N, col0 = s.t.src_off + (uint64_t)(s.t.x0 + sx0) * N;
-	const uint8_t *sb = reinterpret_cast<const uint8_t *>(stage);
-	auto vertical = [&](uint32_t sy, int32_t hs) {
-		const uint32_t hv = (uint32_t)min(max(hs >> 22, 0), 255);
-#pragma unroll
-		for (uint32_t j = 0; j < MIJ_RSZ_ROWS; ++j) {
-			const uint32_t d = sy - vlo[j];
-			if (d < vn[j])
-				acc[j] = rsz_mac<M32>(acc[j], hv, vg ? vk[(size_t)(q0 + j) * ksv + d] : vkl[j * ksv + d]);
-		}
-	};
-	__syncthreads(); /* kl, vkl, and the tables k_out_resize put in LDS */
-	for (uint32_t y = sy0; y < sy1; y += R) {
-		const uint32_t nrw = min(R, sy1 - y);
-		int32_t hsum = 1 << 21;
-		for (uint32_t cx = 0; cx < span; cx += cc) {
-			const uint32_t ncc = min(cc, span - cx), nb = ncc * N;
-			for (uint32_t i = tid; i < nrw * ld; i += 256u) {
-				const uint32_t r = i / ld, k = i - r * ld;
-				const uint64_t a = col0 + (uint64_t)(s.t.y0 + y + r) * rowb + (uint64_t)cx * N;
-				/* the dwords that hold the chunk's bytes; the last ends inside the slot's 256-aligned region of the arena */
-				if (k < (((uint32_t)(a & 3u) + nb + 3u) >> 2))
-					stage[i] = reinterpret_cast<const uint32_t *>(out + (a & ~(uint64_t)3))[k];
-			}
-			__syncthreads();
-			const int32_t tb = max((int32_t)cx - hlo, 0), te = min(hn, (int32_t)(cx + ncc) - hlo);
-			for (uint32_t r = 0; r < nrw; ++r) {
-				const uint64_t a = col0 + (uint64_t)(s.t.y0 + y + r) * rowb + (uint64_t)cx * N;
-				const uint8_t *row = sb + r * ld * 4u + (uint32_t)(a & 3u) + (int32_t)(hlo - (int32_t)cx) * (int32_t)N + c;
-				/* four taps at a time: their LDS reads are issued together, so that their latency overlaps */
-				int32_t p = 0, p1 = 0, t = tb;
-				for (; t + 4 <= te; t += 4) {
-					const uint32_t x0 = row[t * (int32_t)N], x1 = row[(t + 1) * (int32_t)N], x2 = row[(t + 2) * (int32_t)N], x3 = row[(t + 3) * (int32_t)N];
-					const int32_t k0 = kp[t], k1 = kp[t + 1], k2 = kp[t + 2], k3 = kp[t + 3];
-					p = rsz_mac<M32>(rsz_mac<M32>(p, x0, k0), x2, k2);
-					p1 = rsz_mac<M32>(rsz_mac<M32>(p1, x1, k1), x3, k3);
-				}
-				for (; t < te; ++t)
-					p = rsz_mac<M32>(p, row[t * (int32_t)N], kp[t]);
-				p += p1;
-				if (one)
-					vertical(y + r, p + (1 << 21));
-				else
-					hsum += p;
-			}
-			__syncthreads();
-		}
-		if (!one)
-			vertical(y, hsum);
-	}
-	uint8_t *ob = reinterpret_cast<uint8_t *>(stage);
-	if (lane) {
-#pragma unroll
-		for (uint32_t j = 0; j < MIJ_RSZ_ROWS; ++j)
-			if (j < nr)
-				ob[j * nc * N + o * N + c] = (uint8_t)min(max(acc[j] >> 22, 0), 255);
-	}
-	__syncthreads();
-}
-
-/* TR: k_out_resize_t's instantiation, kept apart from k_out_resize's so that neither kernel's code depends on the other */
-template <typename T, bool CHW, bool TR = false>
-__device__ __forceinline__ void resize_store(const DevResize &s, const WorkResize &wk, const uint8_t *lut, const uint8_t *ob)
-{
-	const uint32_t nr = wk.nr, nc = wk.nc, rb = nc * s.t.n_out;
-	const uint32_t row0 = s.t.flip_y ? s.out_h - wk.q0 - nr : wk.q0, p0 = s.t.flip_x ? s.out_w - wk.u0 - nc : wk.u0;
-	auto row_of = [&](uint32_t r) { return ob + (s.t.flip_y ? nr - 1u - r : r) * rb; };
-	switch (s.t.n_out) {
-	case 1: tensor_store<T, CHW, 1>(s.t, row0, p0, nr, nc, lut, row_of); break;
-	case 2: tensor_store<T, CHW, 2>(s.t, row0, p0, nr, nc, lut, row_of); break;
-	case 3: tensor_store<T, CHW, 3>(s.t, row0, p0, nr, nc, lut, row_of); break;
-	default: tensor_store<T, CHW, 4>(s.t, row0, p0, nr, nc, lut, row_of); break;
-	}
-}
-
-__global__ __launch_bounds__(256) void k_out_resize(const DevResize *__restrict__ rs, const WorkResize *__restrict__ work, const uint8_t *__restrict__ luts,
-																	 const uint8_t *__restrict__ plan, const uint8_t *__restrict__ out)
-{
-	__shared__ uint32_t stage[MIJ_RSZ_STAGE_WORDS];
-	__shared__ int32_t kl[MIJ_RSZ_KCAP];
-	__shared__ int32_t vkl[MIJ_RSZ_VCAP];
-	__shared__ uint32_t lutw[4u * (1024u + MIJ_TEN_LDS_PAD) / 4u];
-	const WorkResize wk = work[blockIdx.x];
-	const DevResize s = rs[wk.t];
-	if (s.t.lut) {
-		const uint32_t tw = 64u * s.t.esize, lsw = tw + MIJ_TEN_LDS_PAD / 4u;
-		const uint32_t *g = reinterpret_cast<const uint32_t *>(luts + (size_t)wk.t * MIJ_TEN_LUT_BYTES);
-		for (uint32_t t = threadIdx.x; t < s.t.n_out * tw; t += 256u)
-			lutw[(t / tw) * lsw + t % tw] = g[t];
-	}
-	switch (s.mul32 * 2u + s.kglobal) {
-	case 0: resize_item<false, false>(s, wk, plan, out, stage, kl, vkl); break;
-	case 1: resize_item<false, true>(s, wk, plan, out, stage, kl, vkl); break;
-	case 2: resize_item<true, false>(s, wk, plan, out, stage, kl, vkl); break;
-	default: resize_item<true, true>(s, wk, plan, out, stage, kl, vkl); break;
-	}
-	const uint8_t *lut = reinterpret_cast<const uint8_t *>(lutw), *ob = reinterpret_cast<const uint8_t *>(stage);
-	switch (s.t.esize * 2u + s.t.chw) {
-	case 2: resize_store<uint8_t, false>(s, wk, lut, ob); break;
-	case 3: resize_store<uint8_t, true>(s, wk, lut, ob); break;
-	case 4: resize_store<uint16_t, false>(s, wk, lut, ob); break;
-	case 5: resize_store<uint16_t, true>(s, wk, lut, ob); break;
-	case 8: resize_store<uint32_t, false>(s, wk, lut, ob); break;
-	default: resize_store<uint32_t, true>(s, wk, lut, ob); break;
-	}
-}
-
-/* ------------------------------------------------------------------ oriented tensor output (mij_batch_set_out_tensor_oriented)
- *
- * Orientations 2..4 only mirror the stored picture: the host composes the mirror with the request's flips (and, with a resize, mirrors
- * that axis's coefficients), so k_out_tensor and k_out_resize run them unchanged.  Orientations 5..8 transpose.  The host folds their
- * mirrors the same way, which leaves one case for the kernels below: the window's output row r (before flips) is stored column
- * x0 + r and its output column q is stored row y0 + q.  DevTensor keeps its fields with that meaning: x0, y0 the stored column and row
- * of the window's corner, w the output columns (stored rows), h the output rows (stored columns), the flips those of the output.
- * Both kernels stage whole stored-row segments, shifted so that each starts on a dword, at a pitch of an odd number of dwords: lanes
- * that read down a staged column then fall on different LDS banks. */
-
-/* dword k of the bytes [a, a + nb) of `out`, read as the aligned dwords that hold them (none past the one that holds byte nb - 1) */
-__device__ __forceinline__ uint32_t staged_dword(const uint8_t *__restrict__ out, uint64_t a, uint32_t k, uint32_t nb)
-{
-	const uint32_t sh = (uint32_t)(a & 3u), nd = (sh + nb + 3u) >> 2;
-	const uint32_t *p = reinterpret_cast<const uint32_t *>(out + (a & ~(uint64_t)3)) + k;
-	const uint32_t lo = __builtin_nontemporal_load(p), hi = k + 1u < nd ? __builtin_nontemporal_load(p + 1) : 0u;
-	return __builtin_amdgcn_alignbyte(hi, lo, sh);
-}
-
-/* tensor_store with the staged byte of (row r, column q, channel c) given by byte_at(r, q, c); q is the staged column, i.e. the
- * output column after s.flip_x.  A copy rather than a generalisation, so that k_out_tensor and k_out_resize keep their code. */
-template <typename T, bool CHW, int N, typename ByteAt>
-__device__ __forceinline__ void tensor_store_at(const DevTensor &s, uint32_t row0, uint32_t p0, uint32_t nr, uint32_t np, const uint8_t *lut, ByteAt byte_at)
-{
-	constexpr uint32_t ES = sizeof(T), V = 16u / ES, LS = 256u * ES + MIJ_TEN_LDS_PAD, PW = 4u / ES;
-	const uint32_t nb = np * N;
-	const uint32_t E = CHW ? np : nb, nl = CHW ? nr * N : nr, um = E / V + 2u;
-	for (uint32_t i = threadIdx.x; i < nl * um; i += 256u) {
-		const uint32_t line = i / um, u = i - line * um;
-		const uint32_t r = CHW ? line / N : line, pc = CHW ? line - r * N : 0u, oy = row0 + r;
-		T *d = reinterpret_cast<T *>(s.dst) + (int64_t)oy * s.row_pitch + (CHW ? (int64_t)pc * s.plane_pitch + p0 : (int64_t)p0 * N);
-		const uint32_t head = (uint32_t)(((16u - ((uintptr_t)d & 15u)) & 15u) / ES);
-		const uint32_t e0 = u ? head + (u - 1u) * V : 0u;
-		const uint32_t e1 = u ? min(E, e0 + V) : min(E, head);
-		if (e0 >= e1)
-			continue;
-		auto value = [&](uint32_t e) -> T {
-			const uint32_t q = CHW ? e : e / N, c = CHW ? pc : e - q * N;
-			const uint32_t v = byte_at(r, s.flip_x ? np - 1u - q : q, c);
-			return s.lut ? reinterpret_cast<const T *>(lut + c * LS)[v] : (T)v;
-		};
-		if (u && e1 - e0 == V) { /* 16-byte aligned: one store */
-			u4v o;
-#pragma unroll
-			for (uint32_t k = 0; k < 4u; ++k) {
-				uint32_t wd = 0;
-#pragma unroll
-				for (uint32_t j = 0; j < PW; ++j)
-					wd |= (uint32_t)value(e0 + k * PW + j) << (8u * ES * j);
-				o[k] = wd;
-			}
-			__builtin_nontemporal_store(o, reinterpret_cast<u4v *>(d + e0));
-		} else {
-			for (uint32_t e = e0; e < e1; ++e)
-				d[e] = value(e);
-		}
-	}
-}
-
-/* k_out_tensor_t's work item: output rows [row0, row0 + nrows) x output columns [p0, p0 + np), i.e. np stored-row segments of nrows
- * stored columns.  Phase 1 stages segment q (ascending stored rows) at q * lsd dwords; phase 2 reads (r, q, c) down staged column r. */
-template <typename T, bool CHW, int N>
-__device__ __forceinline__ void tensor_item_t(const DevTensor &s, const WorkTensor &wk, const uint8_t *__restrict__ out, const uint8_t *lut, uint32_t *stage)
-{
-	const uint32_t np = wk.np, nr = wk.nrows, nb = nr * N, nw = (nb + 3u) >> 2, lsd = nw | 1u;
-	const uint32_t sx = s.flip_y ? s.x0 + s.h - wk.row0 - nr : s.x0 + wk.row0; /* first stored column of the tile */
-	const uint32_t sy = s.flip_x ? s.y0 + s.w - wk.p0 - np : s.y0 + wk.p0;     /* first stored row of the tile */
-	const uint64_t rowb = (uint64_t)s.src_w * N, a0 = s.src_off + (uint64_t)sy * rowb + (uint64_t)sx * N;
-	for (uint32_t i = threadIdx.x; i < np * nw; i += 256u) {
-		const uint32_t q = i / nw, k = i - q * nw;
-		stage[q * lsd + k] = staged_dword(out, a0 + (uint64_t)q * rowb, k, nb);
-	}
-	__syncthreads();
-	const uint8_t *sb = reinterpret_cast<const uint8_t *>(stage);
-	tensor_store_at<T, CHW, N>(s, wk.row0, wk.p0, nr, np, lut, [&](uint32_t r, uint32_t q, uint32_t c) -> uint32_t {
-		return sb[q * lsd * 4u + (s.flip_y ? nr - 1u - r : r) * (uint32_t)N + c];
-	});
-}
-
-template <typename T, bool CHW>
-__device__ __forceinline__ void tensor_item_t_n(const DevTensor &s, const WorkTensor &wk, const uint8_t *__restrict__ out, const uint8_t *lut, uint32_t *stage)
-{
-	switch (s.n_out) {
-	case 1: tensor_item_t<T, CHW, 1>(s, wk, out, lut, stage); break;
-	case 2: tensor_item_t<T, CHW, 2>(s, wk, out, lut, stage); break;
-	case 3: tensor_item_t<T, CHW, 3>(s, wk, out, lut, stage); break;
-	default: tensor_item_t<T, CHW, 4>(s, wk, out, lut, stage); break;
-	}
-}
-
-__global__ __launch_bounds__(256) void k_out_tensor_t(const DevTensor *__restrict__ ts, const WorkTensor *__restrict__ work, const uint8_t *__restrict__ luts,
-																	  const uint8_t *__restrict__ out)
-{
-	__shared__ uint32_t stage[MIJ_TEN_STAGE_WORDS];
-	__shared__ uint32_t lutw[4u * (1024u + MIJ_TEN_LDS_PAD) / 4u];
-	const WorkTensor wk = work[blockIdx.x];
-	const DevTensor s = ts[wk.t];
-	if (s.lut) {
-		const uint32_t tw = 64u * s.esize, lsw = tw + MIJ_TEN_LDS_PAD / 4u;
-		const uint32_t *g = reinterpret_cast<const uint32_t *>(luts + (size_t)wk.t * MIJ_TEN_LUT_BYTES);
-		for (uint32_t t = threadIdx.x; t < s.n_out * tw; t += 256u)
-			lutw[(t / tw) * lsw + t % tw] = g[t];
-	}
-	const uint8_t *lut = reinterpret_cast<const uint8_t *>(lutw);
-	/* tensor_item_t's __syncthreads orders the table writes before the lookups */
-	switch (s.esize * 2u + s.chw) {
-	case 2: tensor_item_t_n<uint8_t, false>(s, wk, out, lut, stage); break;
-	case 3: tensor_item_t_n<uint8_t, true>(s, wk, out, lut, stage); break;
-	case 4: tensor_item_t_n<uint16_t, false>(s, wk, out, lut, stage); break;
-	case 5: tensor_item_t_n<uint16_t, true>(s, wk, out, lut, stage); break;
-	case 8: tensor_item_t_n<uint32_t, false>(s, wk, out, lut, stage); break;
-	default: tensor_item_t_n<uint32_t, true>(s, wk, out, lut, stage); break;
-	}
-}
-
-/* resize_item for a transposed request: the first (horizontal) pass runs down the stored columns.  sx0..sx1 are the stored rows the
- * segment's horizontal taps read (relative to s.t.y0), sy0..sy1 the stored columns the band's vertical taps read (relative to s.t.x0).
- * A round stages the span's stored rows x R stored columns, each row's R * N bytes at an odd pitch of ld dwords; each lane sums its
- * horizontal taps down a staged column and feeds the vertical accumulators as resize_item does.  A span of more rows than the stage
- * holds is walked in chunks of rows, one column per round, the partial sums kept in a register. */
-template <bool M32, bool KG>
-__device__ __forceinline__ void resize_item_t(const DevResize &s, const WorkResize &wk, const uint8_t *__restrict__ plan, const uint8_t *__restrict__ out,
-																uint32_t *stage, int32_t *kl, int32_t *vkl)
-{
-	const uint32_t N = s.t.n_out, nc = wk.nc, nr = wk.nr, q0 = wk.q0, u0 = wk.u0, ksh = s.ksh, ksv = s.ksv;
-	const int32_t *hln = reinterpret_cast<const int32_t *>(plan + s.hco), *hk = hln + 2u * s.out_w;
-	const int32_t *vln = reinterpret_cast<const int32_t *>(plan + s.vco), *vk = vln + 2u * s.out_h;
-	const uint32_t tid = threadIdx.x, o = tid / N, c = tid - o * N;
-	const bool lane = o < nc;
-	const uint32_t uo = u0 + (lane ? o : 0u);
-	const uint32_t sx0 = (uint32_t)hln[2u * u0], sx1 = (uint32_t)(hln[2u * (u0 + nc - 1u)] + hln[2u * (u0 + nc - 1u) + 1u]);
-	const int32_t hlo = hln[2u * uo] - (int32_t)sx0, hn = lane ? hln[2u * uo + 1u] : 0;
-	if (!KG)
-		for (uint32_t i = tid; i < nc * ksh; i += 256u)
-			kl[i] = hk[(size_t)u0 * ksh + i];
-	const int32_t *kp = KG ? hk + (size_t)uo * ksh : kl + (lane ? o : 0u) * ksh;
-	const bool vg = s.vglobal != 0;
-	if (!vg)
-		for (uint32_t i = tid; i < nr * ksv; i += 256u)
-			vkl[i] = vk[(size_t)q0 * ksv + i];
+	/* the band's vertical taps: output row q0 + j reads positions [vlo[j], vlo[j] + vn[j]) */
 	uint32_t vlo[MIJ_RSZ_ROWS], vn[MIJ_RSZ_ROWS];
 	int32_t acc[MIJ_RSZ_ROWS];
 #pragma unroll
@@ -3418,13 +3276,14 @@ __device__ __forceinline__ void resize_item_t(const DevResize &s, const WorkResi
 	}
 	const uint32_t sy0 = vlo[0], sy1 = (uint32_t)(vln[2u * (q0 + nr - 1u)] + vln[2u * (q0 + nr - 1u) + 1u]);
 	const uint32_t span = sx1 - sx0;
-	const bool one = span <= MIJ_RSZ_STAGE_WORDS; /* every row of the span in one chunk: several columns per round */
-	uint32_t ldm = one ? MIJ_RSZ_STAGE_WORDS / span : 1u;
-	ldm -= (ldm & 1u) ^ 1u; /* odd */
-	const uint32_t R = one ? ldm * 4u / N : 1u, ld = one ? (((R * N + 3u) >> 2) | 1u) : 1u, cc = one ? span : MIJ_RSZ_STAGE_WORDS;
-	const uint64_t rowb = (uint64_t)s.t.src_w * N, base = s.t.src_off + (uint64_t)(s.t.y0 + sx0) * rowb + (uint64_t)s.t.x0 * N;
+	const RszStage g = rsz_stage<TR>(span, N);
+	const bool one = g.one;
+	const uint32_t cc = g.cc, ld = g.ld, R = g.R;
+	const uint64_t rowb = (uint64_t)s.t.src_w * N;
+	/* the first byte the span reads: of the window's row 0 when plain, of its stored column 0 when transposed */
+	const uint64_t base = TR ? s.t.src_off + (uint64_t)(s.t.y0 + sx0) * rowb + (uint64_t)s.t.x0 * N : s.t.src_off + (uint64_t)(s.t.x0 + sx0) * N;
+	const int32_t ts = TR ? (int32_t)(ld * 4u) : (int32_t)N; /* bytes between a lane's taps in the stage */
 	const uint8_t *sb = reinterpret_cast<const uint8_t *>(stage);
-	const int32_t ldb = (int32_t)(ld * 4u);
 	auto vertical = [&](uint32_t sy, int32_t hs) {
 		const uint32_t hv = (uint32_t)min(max(hs >> 22, 0), 255);
 #pragma unroll
@@ -3434,30 +3293,47 @@ __device__ __forceinline__ void resize_item_t(const DevResize &s, const WorkResi
 				acc[j] = rsz_mac<M32>(acc[j], hv, vg ? vk[(size_t)(q0 + j) * ksv + d] : vkl[j * ksv + d]);
 		}
 	};
-	__syncthreads(); /* kl, vkl, and the tables k_out_resize_t put in LDS */
+	__syncthreads(); /* kl, vkl, and the tables the kernel put in LDS */
 	for (uint32_t y = sy0; y < sy1; y += R) {
-		const uint32_t nrw = min(R, sy1 - y), nb = nrw * N, nw = (nb + 3u) >> 2;
+		const uint32_t nrw = min(R, sy1 - y);
 		int32_t hsum = 1 << 21;
 		for (uint32_t cx = 0; cx < span; cx += cc) {
 			const uint32_t ncc = min(cc, span - cx);
-			for (uint32_t i = tid; i < ncc * nw; i += 256u) {
-				const uint32_t r = i / nw, k = i - r * nw;
-				stage[r * ld + k] = staged_dword(out, base + (uint64_t)(cx + r) * rowb + (uint64_t)y * N, k, nb);
+			/* the round's staged lines: nrw source rows of ncc columns when plain, ncc stored rows of nrw columns when transposed */
+			const uint32_t nb = (TR ? nrw : ncc) * N;
+			auto line = [&](uint32_t l) -> uint64_t {
+				return TR ? base + (uint64_t)(cx + l) * rowb + (uint64_t)y * N : base + (uint64_t)(s.t.y0 + y + l) * rowb + (uint64_t)cx * N;
+			};
+			if (TR) { /* each line shifted to start on a dword */
+				const uint32_t nw = (nb + 3u) >> 2;
+				for (uint32_t i = tid; i < ncc * nw; i += 256u) {
+					const uint32_t l = i / nw, k = i - l * nw;
+					stage[l * ld + k] = staged_dword(out, line(l), k, nb);
+				}
+			} else { /* each line as the aligned dwords that hold it */
+				for (uint32_t i = tid; i < nrw * ld; i += 256u) {
+					const uint32_t l = i / ld, k = i - l * ld;
+					const uint64_t a = line(l);
+					/* the last dword ends inside the slot's 256-aligned region of the arena */
+					if (k < (((uint32_t)(a & 3u) + nb + 3u) >> 2))
+						stage[i] = reinterpret_cast<const uint32_t *>(out + (a & ~(uint64_t)3))[k];
+				}
 			}
 			__syncthreads();
 			const int32_t tb = max((int32_t)cx - hlo, 0), te = min(hn, (int32_t)(cx + ncc) - hlo);
 			for (uint32_t r = 0; r < nrw; ++r) {
-				const uint8_t *col = sb + (hlo - (int32_t)cx) * ldb + (int32_t)(r * N + c);
+				/* the lane's byte at tap 0 of position y + r */
+				const uint8_t *px = sb + (hlo - (int32_t)cx) * ts + (TR ? r * N + c : r * ld * 4u + (uint32_t)(line(r) & 3u) + c);
 				/* four taps at a time: their LDS reads are issued together, so that their latency overlaps */
 				int32_t p = 0, p1 = 0, t = tb;
 				for (; t + 4 <= te; t += 4) {
-					const uint32_t x0 = col[t * ldb], x1 = col[(t + 1) * ldb], x2 = col[(t + 2) * ldb], x3 = col[(t + 3) * ldb];
+					const uint32_t x0 = px[t * ts], x1 = px[(t + 1) * ts], x2 = px[(t + 2) * ts], x3 = px[(t + 3) * ts];
 					const int32_t k0 = kp[t], k1 = kp[t + 1], k2 = kp[t + 2], k3 = kp[t + 3];
 					p = rsz_mac<M32>(rsz_mac<M32>(p, x0, k0), x2, k2);
 					p1 = rsz_mac<M32>(rsz_mac<M32>(p1, x1, k1), x3, k3);
 				}
 				for (; t < te; ++t)
-					p = rsz_mac<M32>(p, col[t * ldb], kp[t]);
+					p = rsz_mac<M32>(p, px[t * ts], kp[t]);
 				p += p1;
 				if (one)
 					vertical(y + r, p + (1 << 21));
@@ -3479,37 +3355,52 @@ __device__ __forceinline__ void resize_item_t(const DevResize &s, const WorkResi
 	__syncthreads();
 }
 
-__global__ __launch_bounds__(256) void k_out_resize_t(const DevResize *__restrict__ rs, const WorkResize *__restrict__ work, const uint8_t *__restrict__ luts,
-																	  const uint8_t *__restrict__ plan, const uint8_t *__restrict__ out)
+/* the resized bytes at `ob` are in the output frame for plain and transposed requests alike: one store for both */
+template <typename T, bool CHW, int N>
+__device__ __forceinline__ void resize_store(const DevResize &s, const WorkResize &wk, const uint8_t *lut, const uint8_t *ob)
+{
+	const uint32_t nr = wk.nr, nc = wk.nc;
+	const uint32_t row0 = s.t.flip_y ? s.out_h - wk.q0 - nr : wk.q0, p0 = s.t.flip_x ? s.out_w - wk.u0 - nc : wk.u0;
+	tensor_store<T, CHW, N>(s.t, row0, p0, nr, nc, lut, [&](uint32_t r) {
+		const uint8_t *srow = ob + (s.t.flip_y ? nr - 1u - r : r) * nc * N;
+		return [=](uint32_t q, uint32_t c) -> uint32_t { return srow[q * N + c]; };
+	});
+}
+
+/* the body of k_out_resize (TR false) and k_out_resize_t (TR true) */
+template <bool TR>
+__device__ __forceinline__ void out_resize(const DevResize *__restrict__ rs, const WorkResize *__restrict__ work, const uint8_t *__restrict__ luts,
+														 const uint8_t *__restrict__ plan, const uint8_t *__restrict__ out)
 {
 	__shared__ uint32_t stage[MIJ_RSZ_STAGE_WORDS];
 	__shared__ int32_t kl[MIJ_RSZ_KCAP];
 	__shared__ int32_t vkl[MIJ_RSZ_VCAP];
-	__shared__ uint32_t lutw[4u * (1024u + MIJ_TEN_LDS_PAD) / 4u];
+	__shared__ uint32_t lutw[MIJ_TEN_LUT_WORDS];
 	const WorkResize wk = work[blockIdx.x];
 	const DevResize s = rs[wk.t];
-	if (s.t.lut) {
-		const uint32_t tw = 64u * s.t.esize, lsw = tw + MIJ_TEN_LDS_PAD / 4u;
-		const uint32_t *g = reinterpret_cast<const uint32_t *>(luts + (size_t)wk.t * MIJ_TEN_LUT_BYTES);
-		for (uint32_t t = threadIdx.x; t < s.t.n_out * tw; t += 256u)
-			lutw[(t / tw) * lsw + t % tw] = g[t];
-	}
+	lut_fill(lutw, s.t, luts, wk.t);
 	switch (s.mul32 * 2u + s.kglobal) {
-	case 0: resize_item_t<false, false>(s, wk, plan, out, stage, kl, vkl); break;
-	case 1: resize_item_t<false, true>(s, wk, plan, out, stage, kl, vkl); break;
-	case 2: resize_item_t<true, false>(s, wk, plan, out, stage, kl, vkl); break;
-	default: resize_item_t<true, true>(s, wk, plan, out, stage, kl, vkl); break;
+	case 0: resize_item<false, false, TR>(s, wk, plan, out, stage, kl, vkl); break;
+	case 1: resize_item<false, true, TR>(s, wk, plan, out, stage, kl, vkl); break;
+	case 2: resize_item<true, false, TR>(s, wk, plan, out, stage, kl, vkl); break;
+	default: resize_item<true, true, TR>(s, wk, plan, out, stage, kl, vkl); break;
 	}
-	/* the resized bytes are in the output frame: resize_store writes them as k_out_resize does */
 	const uint8_t *lut = reinterpret_cast<const uint8_t *>(lutw), *ob = reinterpret_cast<const uint8_t *>(stage);
-	switch (s.t.esize * 2u + s.t.chw) {
-	case 2: resize_store<uint8_t, false, true>(s, wk, lut, ob); break;
-	case 3: resize_store<uint8_t, true, true>(s, wk, lut, ob); break;
-	case 4: resize_store<uint16_t, false, true>(s, wk, lut, ob); break;
-	case 5: resize_store<uint16_t, true, true>(s, wk, lut, ob); break;
-	case 8: resize_store<uint32_t, false, true>(s, wk, lut, ob); break;
-	default: resize_store<uint32_t, true, true>(s, wk, lut, ob); break;
-	}
+	for_elem(s.t, [&](auto e) {
+		using E = decltype(e);
+		resize_store<typename E::type, E::chw, E::n>(s, wk, lut, ob);
+	});
+}
+
+__global__ __launch_bounds__(256) void k_out_resize(const DevResize *__restrict__ rs, const WorkResize *__restrict__ work, const uint8_t *__restrict__ luts,
+																	 const uint8_t *__restrict__ plan, const uint8_t *__restrict__ out)
+{
+	out_resize<false>(rs, work, luts, plan, out);
+}
+__global__ __launch_bounds__(256) void k_out_resize_t(const DevResize *__restrict__ rs, const WorkResize *__restrict__ work, const uint8_t *__restrict__ luts,
+																		const uint8_t *__restrict__ plan, const uint8_t *__restrict__ out)
+{
+	out_resize<true>(rs, work, luts, plan, out);
 }
 
 } /* namespace mij */

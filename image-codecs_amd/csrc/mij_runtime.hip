@@ -1830,6 +1830,19 @@ extern "C" int mij_batch_upload(mij_batch *b)
 	return MIJ_OK;
 }
 
+/* One output pass on the batch stream, if its plan has work items: a kernel that takes the plan's descriptors, work list and tables, then
+ * `tail`.  A batch without such requests launches nothing. */
+template <typename Dev, typename Work, typename Lut, typename... Params, typename... Args>
+static int launch_out_pass(mij_batch *b, const PlanBuf &p, void (*kernel)(const Dev *, const Work *, const Lut *, Params...), Args... tail)
+{
+	if (!p.items)
+		return MIJ_OK;
+	hipLaunchKernelGGL(kernel, dim3((unsigned)p.items), dim3(256), 0, b->stream, reinterpret_cast<const Dev *>(p.d), reinterpret_cast<const Work *>(p.d + p.work_at),
+							 reinterpret_cast<const Lut *>(p.d + p.lut_at), tail...);
+	HIP_TRY(hipGetLastError());
+	return MIJ_OK;
+}
+
 extern "C" int mij_batch_launch(mij_batch *b)
 {
 	if (!b)
@@ -1846,37 +1859,14 @@ extern "C" int mij_batch_launch(mij_batch *b)
 		(void)hipLaunchKernel(f.k[L.var], dim3((unsigned)L.count), dim3(f.threads), f.roi ? args5 : args4, L.lds, b->stream);
 		HIP_TRY(hipGetLastError());
 	}
-	/* float output, behind every decode family (both front ends end here) */
-	const PlanBuf &fp = b->f32plan, &tp = b->tenplan, &rp = b->rszplan;
-	if (fp.items) {
-		hipLaunchKernelGGL(k_out_f32, dim3((unsigned)fp.items), dim3(256), 0, b->stream, reinterpret_cast<const DevF32 *>(fp.d),
-								 reinterpret_cast<const WorkF32 *>(fp.d + fp.work_at), reinterpret_cast<const float *>(fp.d + fp.lut_at), b->d_out, b->d_f32);
-		HIP_TRY(hipGetLastError());
-	}
-	/* tensor output into the callers' memory, behind the float pass */
-	if (tp.items) {
-		hipLaunchKernelGGL(k_out_tensor, dim3((unsigned)tp.items), dim3(256), 0, b->stream, reinterpret_cast<const DevTensor *>(tp.d),
-								 reinterpret_cast<const WorkTensor *>(tp.d + tp.work_at), tp.d + tp.lut_at, b->d_out);
-		HIP_TRY(hipGetLastError());
-	}
-	/* resized tensor output, behind the plain one */
-	if (rp.items) {
-		hipLaunchKernelGGL(k_out_resize, dim3((unsigned)rp.items), dim3(256), 0, b->stream, reinterpret_cast<const DevResize *>(rp.d),
-								 reinterpret_cast<const WorkResize *>(rp.d + rp.work_at), rp.d + rp.lut_at, rp.d, b->d_out);
-		HIP_TRY(hipGetLastError());
-	}
-	/* transposed (oriented 5..8) tensor output, plain and resized: only when such a request exists */
-	const PlanBuf &tq = b->tentplan, &rq = b->rsztplan;
-	if (tq.items) {
-		hipLaunchKernelGGL(k_out_tensor_t, dim3((unsigned)tq.items), dim3(256), 0, b->stream, reinterpret_cast<const DevTensor *>(tq.d),
-								 reinterpret_cast<const WorkTensor *>(tq.d + tq.work_at), tq.d + tq.lut_at, b->d_out);
-		HIP_TRY(hipGetLastError());
-	}
-	if (rq.items) {
-		hipLaunchKernelGGL(k_out_resize_t, dim3((unsigned)rq.items), dim3(256), 0, b->stream, reinterpret_cast<const DevResize *>(rq.d),
-								 reinterpret_cast<const WorkResize *>(rq.d + rq.work_at), rq.d + rq.lut_at, rq.d, b->d_out);
-		HIP_TRY(hipGetLastError());
-	}
+	/* the output passes, behind every decode family (both front ends end here): float output, tensor output into the callers' memory,
+	 * resized tensor output, then the transposed (oriented 5..8) forms of the last two */
+	int rc;
+	if ((rc = launch_out_pass(b, b->f32plan, k_out_f32, b->d_out, b->d_f32)) != MIJ_OK || (rc = launch_out_pass(b, b->tenplan, k_out_tensor, b->d_out)) != MIJ_OK ||
+		 (rc = launch_out_pass(b, b->rszplan, k_out_resize, b->rszplan.d, b->d_out)) != MIJ_OK ||
+		 (rc = launch_out_pass(b, b->tentplan, k_out_tensor_t, b->d_out)) != MIJ_OK ||
+		 (rc = launch_out_pass(b, b->rsztplan, k_out_resize_t, b->rsztplan.d, b->d_out)) != MIJ_OK)
+		return rc;
 	b->launched = true;
 	return MIJ_OK;
 }

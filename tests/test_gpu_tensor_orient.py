@@ -153,6 +153,19 @@ def test_tiles_both_ways_and_big_pictures(ica, oracle, dec):
     assert tm.same_bits(got[0], _want(px, 6, (0, 0, 3000, 4000), (224, 224), "bilinear", False, False, "CHW", torch.float16, MEAN[:3], STD[:3]))
 
 
+def test_long_spans_transposed(ica, oracle, dec):
+    """the transposed resize where its taps outgrow LDS: a 180 x 4200 stored picture is 4200 x 180 displayed.  Lanczos to 1 x 2 reads
+    4200 stored rows per output column (more than the stage's 4096: the span is walked in chunks) with 12601 horizontal taps (read from
+    the plan) and 1081 vertical ones (read from the plan); a 700-wide window to 1 x 1 has the same taps with the span in one chunk"""
+    data = ica.synth_jpeg(180, 4200, seed=18, quality=90)
+    px = oracle.load(data, 3)[1]
+    for o in (5, 6, 7, 8):
+        for win, size in (((0, 0, 4200, 180), (1, 2)), ((100, 0, 700, 180), (1, 1))):
+            got, reasons = dec.decode([data], crops=[win], orientation=o, size=size, filter="lanczos", dtype=torch.uint8, layout="HWC")
+            assert reasons == [None]
+            assert tm.same_bits(got[0], _want(px, o, win, size, "lanczos", False, False, "HWC", torch.uint8)), (o, win, size)
+
+
 def test_random_resized_crops_in_displayed_frame(ica, oracle, dec):
     data = ica.synth_jpeg(640, 360, seed=31, quality=90)
     px = oracle.load(data, 3)[1]
