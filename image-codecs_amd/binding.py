@@ -631,6 +631,15 @@ class Context:
             self._h = C.c_void_p()
 
 
+# the kernel families of a launch plan by index: the MK_* enumeration of mij_runtime.hip, in its order (mij_batch_slot_kernel)
+KERNEL_KINDS = (
+    "MK_PLANES", "MK_RESAMPLE", "MK_RS_FAST+RS_ROW1", "MK_RS_FAST+RS_V2", "MK_RS_FAST+RS_H2", "MK_RS_FAST+RS_HV2", "MK_RS_FAST+RS_GEN2",
+    "MK_RS_FAST+RS_GEN4", "MK_420", "MK_422", "MK_444", "MK_GREY", "MK_440", "MK_420W", "MK_440W", "MK_420X", "MK_420S", "MK_420T", "MK_422W",
+    "MK_422X", "MK_422S", "MK_422T", "MK_1X1C", "MK_420C", "MK_440C", "MK_SCALED+SC_Y", "MK_SCALED+SC_444", "MK_SCALED+SC_420",
+    "MK_SCALED+SC_422", "MK_444R", "MK_GREYR", "MK_1X1CR", "MK_SCALEDR+SC_Y", "MK_SCALEDR+SC_444", "MK_SCALEDR+SC_420", "MK_SCALEDR+SC_422",
+)
+
+
 class Batch:
     """mij_batch: staging + device arenas + stream.  Thin, order-preserving wrapper."""
 
@@ -749,6 +758,15 @@ class Batch:
         L = lib()
         L.mij_batch_slot_work_items.argtypes = [C.c_void_p, C.c_int]
         return _check(L.mij_batch_slot_work_items(self._h, int(slot)), "mij_batch_slot_work_items")
+
+    def slot_kernel(self, slot):
+        """tests: what the last upload chose for the slot (mij_batch_slot_kernel): -> (family name from KERNEL_KINDS, variant bits, column
+        segments per band); (None, 0, 1) for a skipped slot."""
+        L = lib()
+        L.mij_batch_slot_kernel.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        kind, var, nseg = C.c_int(), C.c_int(), C.c_int()
+        _check(L.mij_batch_slot_kernel(self._h, int(slot), C.byref(kind), C.byref(var), C.byref(nseg)), "mij_batch_slot_kernel")
+        return (KERNEL_KINDS[kind.value] if kind.value >= 0 else None), var.value, nseg.value
 
     def slot_coef_bytes(self, slot):
         """1 when the slot's coefficients sit in HBM as compact planes (the default), 0 for the int16 tile layout."""

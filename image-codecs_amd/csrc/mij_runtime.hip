@@ -868,6 +868,22 @@ extern "C" int mij_batch_slot_work_items(const mij_batch *b, int slot)
 	return b->slots[(size_t)slot].work_items;
 }
 
+extern "C" int mij_batch_slot_kernel(const mij_batch *b, int slot, int *kind, int *variant, int *segments)
+{
+	if (!b || slot < 0 || slot >= (int)b->slots.size())
+		return set_err(MIJ_E_ARG, "mij_batch_slot_kernel: bad slot");
+	if (!b->uploaded)
+		return set_err(MIJ_E_STATE, "mij_batch_slot_kernel before mij_batch_upload");
+	const Choice &c = b->slots[(size_t)slot].choice;
+	if (kind)
+		*kind = c.kind;
+	if (variant)
+		*variant = c.var;
+	if (segments)
+		*segments = c.nseg;
+	return MIJ_OK;
+}
+
 extern "C" int mij_batch_set_color(mij_batch *b, int slot, int color)
 {
 	if (!b || slot < 0 || slot >= (int)b->slots.size())

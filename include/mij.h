@@ -389,6 +389,11 @@ int mij_batch_entropy_anomaly(mij_batch *b, int slot);
  * lane units of a windowed or reduced-size slot, one per 256 blocks of an unwindowed 1x1 slot, pass 2's row groups of a two-pass slot (its
  * pass-1 blocks and the pack kernel's tiles are not counted).  0 for a skipped slot; MIJ_E_STATE before upload, MIJ_E_ARG for a bad slot. */
 int mij_batch_slot_work_items(const mij_batch *b, int slot);
+/* tests: the kernel the last upload chose for a slot -- *kind the index of its family in the launch plan (the MK_* order of mij_runtime.hip:
+ * which form of a band kernel, which pass 2 of the two-pass path), *variant the family's variant bits (4: four channels, 2: wide IDCT --
+ * pass 2: YCbCr colour --, 1: compact planes), *segments the column segments per band (1 unless the row of MCUs is cut).  Any pointer may
+ * be NULL.  *kind is -1 for a skipped slot; MIJ_E_STATE before upload, MIJ_E_ARG for a bad slot. */
+int mij_batch_slot_kernel(const mij_batch *b, int slot, int *kind, int *variant, int *segments);
 /* The format new coefficient planes of this batch get in HBM: MIJ_COEF_COMPACT (default; environment
  * MIJ_COEF_FORMAT=int16 flips the default) or MIJ_COEF_INT16.  Applies to slots added or uploaded afterwards. */
 int mij_batch_set_coef_format(mij_batch *b, int fmt);

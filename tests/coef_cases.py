@@ -26,6 +26,19 @@ PATH_OF = {"420": 1, "440": 6, "422": 4, "444": 3, "grey": 5, "411": 2, "rgb": 7
 # four-component files it declines with status 2, like progressive ones)
 GPU_WALK_LAYOUTS = ("420", "440", "422", "444", "grey", "411", "rgb")
 
+# layouts other test modules add for their own pictures (sample_cases.py): known to the writer and the geometry below, and to none of this
+# module's families, tables or everything()
+EXTRA_LAYOUTS = {}
+
+
+def all_layouts():
+    return {**LAYOUTS, **EXTRA_LAYOUTS}
+
+
+def _layout(name):
+    return LAYOUTS[name] if name in LAYOUTS else EXTRA_LAYOUTS[name]
+
+
 ONES = np.ones(128, np.int64)
 
 
@@ -39,7 +52,7 @@ class Case:
         if progressive is not None and len(self.planes) > 1:
             # the AC scans of a progressive file carry one component each and, like every non-interleaved scan, only the blocks that hold
             # picture (T.81 A.2.2): the AC terms of the MCU padding are not in the stream, only its DC terms (interleaved scan) are
-            hv, _ = LAYOUTS[layout]
+            hv, _ = _layout(layout)
             hmax, vmax = max(a for a, _ in hv), max(b for _, b in hv)
             for p, (hh, vv) in zip(self.planes, hv):
                 cw, ch = ((w * hh + hmax - 1) // hmax + 7) // 8, ((h * vv + vmax - 1) // vmax + 7) // 8
@@ -89,7 +102,7 @@ class Case:
 
 def geometry(layout, w, h):
     """-> (mcu_x, mcu_y, [(bh, bw) per component])"""
-    hv, _ = LAYOUTS[layout]
+    hv, _ = _layout(layout)
     hmax, vmax = max(a for a, _ in hv), max(b for _, b in hv)
     mcu_x, mcu_y = (w + 8 * hmax - 1) // (8 * hmax), (h + 8 * vmax - 1) // (8 * vmax)
     return mcu_x, mcu_y, [(mcu_y * v, mcu_x * hh) for hh, v in hv]
@@ -97,7 +110,7 @@ def geometry(layout, w, h):
 
 def scan_order(layout, w, h, comp):
     """-> (MCU index, block row, block column) of component `comp`'s blocks in the order an interleaved scan codes them"""
-    hv, _ = LAYOUTS[layout]
+    hv, _ = _layout(layout)
     mcu_x, mcu_y, _ = geometry(layout, w, h)
     hh, vv = hv[comp]
     m = np.repeat(np.arange(mcu_x * mcu_y), hh * vv)
@@ -128,7 +141,7 @@ def sixteen_bit_tables(data, qt):
 
 def _write(case):
     L = C.CDLL(helpers.build_prog_writer())
-    hv, app14 = LAYOUTS[case.layout]
+    hv, app14 = _layout(case.layout)
     n_c = len(hv)
     for p, (bh, bw) in zip(case.planes, geometry(case.layout, case.w, case.h)[2]):
         assert p.shape == (bh, bw, 64), (case.name, p.shape, bh, bw)

@@ -10,6 +10,7 @@ in wrapping 32-bit arithmetic.  Pixel (X, Y) of the ceil(W / s) x ceil(H / s) pi
 import numpy as np
 
 import idct_model as M
+from upsample_model import ycbcr_to_rgb  # the colour row: stated once, with the rest of the output stage
 
 # K_n[x][u] = rint(4096 * sqrt(2) * a(u) * cos((2x + 1) u pi / 2n)), a(0) = 1 / sqrt(2): the reference's scale, DC weight 4096
 K = {
@@ -40,17 +41,6 @@ def block_transform(d, nv, nh):
     t = np.stack([v >> 10 for v in idct_1d([d[..., u, :] for u in range(nv)], nv, 512)], axis=-2)          # [..., nv, nh]
     o = idct_1d([t[..., :, v] for v in range(nh)], nh, 65536 + (128 << 17))
     return np.clip(np.stack([x >> 17 for x in o], axis=-1), 0, 255).astype(np.uint8)
-
-
-def ycbcr_to_rgb(y, cb, cr):
-    """the reference's stbi__YCbCr_to_RGB_row per pixel (codec/jpeg.c:1976-2018): uint8 arrays -> [..., 3]"""
-    f = lambda x: int(np.float32(x) * np.float32(4096.0) + np.float32(0.5)) << 8  # stbi__float2fixed
-    yf = (y.astype(np.int64) << 20) + (1 << 19)
-    cr, cb = cr.astype(np.int64) - 128, cb.astype(np.int64) - 128
-    r = yf + cr * f(1.40200)
-    g = yf + cr * -f(0.71414) + ((cb * -f(0.34414)) & -65536)  # "& 0xffff0000" on a 32-bit int keeps the sign bits
-    b = yf + cb * f(1.77200)
-    return np.stack([np.clip(v >> 20, 0, 255) for v in (r, g, b)], axis=-1).astype(np.uint8)
 
 
 def component_plane(d, nv, nh):

@@ -200,7 +200,7 @@ def test_full_size_1080p_batch_properties(ica, oracle, gpu_ctx):
 
 
 def test_wide_images_take_the_band_kernel_in_column_segments(ica, oracle, gpu_ctx, monkeypatch):
-    """A row of 4:2:0 MCUs beyond 5840 pixels (4:4:0: 4300) does not fit the LDS of a CU: since round 3 such pictures are cut into column
+    """A row of 4:2:0 MCUs beyond 163840 // LDS_COL_420 = 365 columns (5840 pixels; 4:4:0: 163840 // LDS_COL_440 = 538 columns, 4304 pixels) does not fit the LDS of a CU: since round 3 such pictures are cut into column
     segments, each transformed with one MCU column of halo on either side (k_fused420c / k_fused440c, fused_band SEG), instead of falling to
     the two-pass kernels.  Widths on both sides of the switch and of the segment counts, odd and unaligned widths (the careful strips of the
     last segment), pictures a few rows high and several bands high, both output widths, both plane formats, both producers: all equal to
@@ -235,11 +235,14 @@ def test_wide_images_take_the_band_kernel_in_column_segments(ica, oracle, gpu_ct
 
 def test_band_kernels_by_workgroups_per_cu(ica, oracle, gpu_ctx, monkeypatch):
     """The band kernels come with one, two, four, eight or sixteen waves per workgroup, chosen by the picture's width (narrow rows do
-    not fill four waves; of wide ones only two or one workgroups fit a CU's LDS: k_fused420t / s / - / w / x, k_fused440 / w): widths on both sides of each switch,
+    not fill four waves; of wide ones only two or one workgroups fit a CU's LDS: k_fused420t / s / - / w / x, k_fused440 / w): widths in every form's range,
     odd sizes, both output widths, one band and many, mixed in one batch -- all equal to the CPU checker."""
     import helpers
     datas = []
-    for w in (1904, 1920, 2288, 2304, 2320, 2848, 2864, 3840, 4097):  # 4:2:0: 448 B per 16 pixels; 3 x fit up to 1904, 2 x up to 2848
+    # 4:2:0: LDS_COL_420 = 448 B per MCU column of 16 pixels against 160 KiB: three workgroups fit up to 163840 // (3 * 448) = 121 columns (1936
+    # pixels), two up to 163840 // (2 * 448) = 182 (2912).  So 1904 and 1920 both take the base form and 2848 and 2864 both w: every form is
+    # reached here, the switches themselves are straddled in test_gpu_upsample.py (test_band_forms)
+    for w in (1904, 1920, 2288, 2304, 2320, 2848, 2864, 3840, 4097):
         datas.append(ica.synth_jpeg(w, 70, w & 7, 90))
     for w, h in ((1, 1), (17, 9), (383, 40), (384, 33), (385, 50), (400, 16), (895, 30), (896, 47), (897, 20), (912, 64)):  # one wave up to 24 MCU columns, two up to 56
         datas.append(ica.synth_jpeg(w, h, (w + h) & 7, 85))
