@@ -768,6 +768,12 @@ class Batch:
         _check(L.mij_batch_slot_kernel(self._h, int(slot), C.byref(kind), C.byref(var), C.byref(nseg)), "mij_batch_slot_kernel")
         return (KERNEL_KINDS[kind.value] if kind.value >= 0 else None), var.value, nseg.value
 
+    def slot_pipelined(self, slot):
+        """tests: True when the slot's launch runs the pipelined twin of its band kernel (mij_batch_slot_pipelined)"""
+        L = lib()
+        L.mij_batch_slot_pipelined.argtypes = [C.c_void_p, C.c_int]
+        return bool(_check(L.mij_batch_slot_pipelined(self._h, int(slot)), "mij_batch_slot_pipelined"))
+
     def slot_coef_bytes(self, slot):
         """1 when the slot's coefficients sit in HBM as compact planes (the default), 0 for the int16 tile layout."""
         return lib().mij_batch_slot_coef_bytes(self._h, int(slot))

@@ -614,7 +614,7 @@ __device__ __forceinline__ void idct_block_dc(const IdctK &K, int dcq, uint2 (&r
 /* a block's loaded low bytes and DC term (compact planes): the loads of several blocks can be in flight before the first is transformed */
 struct RawB8 {
 	uint2 h[8];
-	uint32_t dc;
+	uint16_t dc; /* 16 bits as loaded: widened where it is read, not where a loop carries it */
 };
 __device__ __forceinline__ void load_raw_b8(const CoefView &cv, uint32_t L, RawB8 &r)
 {
@@ -1307,6 +1307,25 @@ __device__ __forceinline__ void strip_row_packed(const ColorK &K, uint32_t cb4, 
 	store_px4<NOUT>(dst, p[0], p[1], p[2], p[3]);
 }
 
+/* Wave task ww of MCU row m of a band kernel's phase A (fused_band): the component (wave-uniform), the lane's block i of the row's nblk and its
+ * index L in the component's plane.  lane0 is the lane, or 0 for a load nobody uses.  A lane beyond the row's blocks gets the row's last block. */
+struct BandTask {
+	int comp, i, nblk;
+	uint32_t L;
+};
+template <bool SEG>
+__device__ __forceinline__ BandTask band_task(int m, int ww, int lane0, int nYw, int nCw, int bwY, int bwC, int gbwY, int gbwC, int bx0Y, int bx0C)
+{
+	BandTask t;
+	t.comp = ww < nYw ? 0 : ((ww - nYw) < nCw ? 1 : 2);
+	t.i = (ww - (t.comp == 0 ? 0 : (t.comp == 1 ? nYw : nYw + nCw))) * 64 + lane0; /* luma: block of the two block rows 2m, 2m+1 (contiguous in L) */
+	t.nblk = t.comp == 0 ? 2 * bwY : bwC;
+	const int ic = min(t.i, t.nblk - 1);
+	const int by = (t.comp == 0 && ic >= bwY) ? 1 : 0, bx = ic - by * bwY;
+	t.L = SEG ? (uint32_t)(t.comp == 0 ? (2 * m + by) * gbwY + bx0Y + bx : m * gbwC + bx0C + bx) : (uint32_t)((t.comp == 0 ? 2 * m * bwY : m * bwC) + ic);
+	return t;
+}
+
 /* threads per workgroup of k_fused420 (A/B knob: 256 = three workgroups of four waves per CU at 1080p, 512 = two of eight) */
 #ifndef MIJ_F420_NT
 #define MIJ_F420_NT 256
@@ -1325,7 +1344,7 @@ __device__ __forceinline__ void strip_row_packed(const ColorK &K, uint32_t cb4, 
  * 5840 pixels, 4:4:0 beyond 4300) are cut into column segments.  A segment transforms one MCU column more on either side (the horizontal
  * chroma filter reads c[i-1] and c[i+1], codec/jpeg.c:1784-1835); everything inside the kernel is in LOCAL columns (the segment plus its
  * halo), and only the plane addresses, the output columns and the picture-edge tests are global.  SEG = false compiles to the code it was. */
-template <int NOUT, bool WIDE, bool B8, bool H2, int NT, bool SEG = false>
+template <int NOUT, bool WIDE, bool B8, bool H2, int NT, bool SEG = false, bool PF = false>
 __device__ __forceinline__ void fused_band(const DevImage *__restrict__ imgs, const WorkBand *__restrict__ work, const uint8_t *__restrict__ coef,
 														 uint8_t *__restrict__ outbase)
 {
@@ -1499,10 +1518,65 @@ __device__ __forceinline__ void fused_band(const DevImage *__restrict__ imgs, co
 		chroma_halo(m0 - 1, 1, saveCb + sv * CP, saveCr + sv * CP);
 	}
 
+	/* ---- phase A as a software pipeline (PIPE: compact planes, not WIDE).  nxt holds the loaded blocks of the wave's
+	 * NEXT task.  A task begins with the one wait for them and their copy into cur, issues the loads of the task behind it into nxt, and only
+	 * then classifies and transforms cur: nine loads are in flight under every transform.  The task behind a row's last task is the wave's
+	 * first task of the next MCU row, whose loads so have the barrier and the whole of phase B to arrive; behind the band's last task every
+	 * lane re-reads that task's first block (one cache line per load), which nobody uses.  So every task issues exactly nine loads -- none is
+	 * predicated, per lane or per wave, and no path reaches a wait with another number in flight.  A lane beyond the row's blocks reads the
+	 * row's last block and only its LDS writes are dropped; the copies vote in the class ballot like the block they copy, so classes and
+	 * class counts are those of the plain loop.  (Two register sets taken in turn would save the copy, sixteen v_mov per task, but want a
+	 * second instance of the transforms: the compiler folds a set picked by a wave-uniform flag back into one set and a swap.) */
+	constexpr bool PIPE = PF && B8 && !WIDE;
+	const int ntask = nYw + 2 * nCw;
+	RawB8 nxt; /* the loaded blocks of the wave's next task */
+	auto task_of = [&](int m, int ww, int lane0) { return band_task<SEG>(m, ww, lane0, nYw, nCw, bwY, bwC, gbwY, gbwC, bx0Y, bx0C); };
+	auto task_view = [&](int comp) { /* by value: a view picked by reference at run time would put the three on the stack */
+		CoefView cv;
+		cv.plane = comp == 0 ? cvY.plane : (comp == 1 ? cvCb.plane : cvCr.plane);
+		cv.dc = comp == 0 ? cvY.dc : (comp == 1 ? cvCb.dc : cvCr.dc);
+		cv.hi = comp == 0 ? cvY.hi : (comp == 1 ? cvCb.hi : cvCr.hi);
+		return cv;
+	};
+	if constexpr (PIPE) {
+		if (wave < ntask && m0 < m1) {
+			const BandTask t = task_of(m0, wave, lane);
+			load_raw_b8(task_view(t.comp), t.L, nxt);
+		}
+	}
+
 	for (int m = m0; m < m1; ++m) {
 		__syncthreads(); /* previous phase B (and the prologue) done with the planes / save buffers */
 		/* ---- phase A: IDCT of MCU row m, one block per lane, component uniform per wave; one call site for the three components
 		 * (the sparse-class transforms of load_idct_block are instantiated once per kernel) */
+		if constexpr (PIPE) {
+			for (int ww = wave; ww < ntask; ww += NT / 64) {
+				const bool row_end = ww + NT / 64 >= ntask, band_end = row_end && m + 1 >= m1;
+				const int nm = row_end ? (band_end ? m : m + 1) : m, nw = row_end ? (band_end ? ww : wave) : ww + NT / 64;
+				const BandTask t = task_of(m, ww, lane), nt = task_of(nm, nw, band_end ? 0 : lane);
+				const int comp = t.comp, i = t.i, nblk = t.nblk;
+				const CoefView cv = task_view(comp), ncv = task_view(nt.comp);
+				/* the one wait for this task's loads, and the copy that frees nxt for the loads behind it.  The empty asm pins both HERE:
+				 * left alone, the compiler sinks them to the loop's end, where the wait stands in front of the barrier and phase B */
+				asm volatile("" : "+v"(nxt.h[0].x), "+v"(nxt.h[0].y), "+v"(nxt.h[1].x), "+v"(nxt.h[1].y), "+v"(nxt.h[2].x), "+v"(nxt.h[2].y), "+v"(nxt.h[3].x), "+v"(nxt.h[3].y),
+									 "+v"(nxt.h[4].x), "+v"(nxt.h[4].y), "+v"(nxt.h[5].x), "+v"(nxt.h[5].y), "+v"(nxt.h[6].x), "+v"(nxt.h[6].y), "+v"(nxt.h[7].x), "+v"(nxt.h[7].y),
+									 "+v"(nxt.dc));
+				const RawB8 cur = nxt;
+				load_raw_b8(ncv, nt.L, nxt);
+				uint2 rows[8];
+				const int cls = idct_raw_b8(KI, cv, t.L, im.dq[comp], cur, rows);
+				if (count_classes && lane == 0)
+					atomicAdd(&g_idct_class[cls], 1ull);
+				if (i < nblk) {
+					const int by = (comp == 0 && i >= bwY) ? 1 : 0, bx = i - by * bwY;
+					const int pitch = comp == 0 ? YP : CP;
+					uint8_t *dst = (comp == 0 ? sY : (comp == 1 ? sCb : sCr)) + (8 * by) * pitch + 8 * bx;
+#pragma unroll
+					for (int r = 0; r < 8; ++r)
+						*reinterpret_cast<uint2 *>(dst + r * pitch) = rows[r];
+				}
+			}
+		} else
 		for (int ww = wave; ww < nYw + 2 * nCw; ww += NT / 64) {
 			uint2 rows[8];
 			const int comp = ww < nYw ? 0 : ((ww - nYw) < nCw ? 1 : 2); /* wave-uniform */
@@ -1580,6 +1654,21 @@ __global__ __launch_bounds__(MIJ_F420_NT) MIJ_F420_ATTR void k_fused420(const De
 																  uint8_t *__restrict__ outbase)
 {
 	fused_band<NOUT, WIDE, B8, true, MIJ_F420_NT>(imgs, work, coef, outbase);
+}
+
+/* The same kernel with phase A as a software pipeline (fused_band, PF; compact planes that are not WIDE).  It holds a second block's loaded
+ * registers (133 / 135 VGPRs against 117: three waves per SIMD), so the launch takes it only where the LDS of the list already keeps a CU
+ * to MIJ_F420P_WAVES waves per SIMD -- a row of more than 1456 pixels at 256 threads -- and the kind, variant and work list stay those of
+ * k_fused420.  A/B knob: -DMIJ_F420_PF=0 never takes it. */
+#ifndef MIJ_F420_PF
+#define MIJ_F420_PF 1
+#endif
+#define MIJ_F420P_WAVES 3
+template <int NOUT>
+__global__ __launch_bounds__(MIJ_F420_NT) void k_fused420p(const DevImage *__restrict__ imgs, const WorkBand *__restrict__ work, const uint8_t *__restrict__ coef,
+																			  uint8_t *__restrict__ outbase)
+{
+	fused_band<NOUT, false, true, true, MIJ_F420_NT, false, true>(imgs, work, coef, outbase);
 }
 
 /* The same kernel with eight waves per workgroup, for pictures whose row of MCUs leaves room for only one or two workgroups in a CU's

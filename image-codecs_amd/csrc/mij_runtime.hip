@@ -125,6 +125,16 @@ static const Family families[MK_KINDS] = {
 	{256, COEF_OUT, false, MIJ_SCR(SC_420), true},
 	{256, COEF_OUT, false, MIJ_SCR(SC_422), true},
 };
+/* MK_420's pipelined twins (k_fused420p), by variant: compact planes without the wide IDCT only.  Not a family: a launch of MK_420 takes the twin of
+ * its variant where band_prefetch says so, and everything that names a picture's kernel (kind, variant, segments) stays what it was. */
+static const void *const k420_prefetch[MK_VARIANTS] = {nullptr, MIJ_K(k_fused420p<3>), nullptr, nullptr, nullptr, MIJ_K(k_fused420p<4>), nullptr, nullptr};
+/* The twin needs more registers (MIJ_F420P_WAVES waves per SIMD), so it runs only where the launch's LDS allows no more workgroups per CU than that anyway */
+static bool band_prefetch(int kind, int var, size_t lds, size_t cap)
+{
+	if (!MIJ_F420_PF || kind != MK_420 || !k420_prefetch[var] || !lds)
+		return false;
+	return (cap / lds) * (families[MK_420].threads / 64) <= 4 * MIJ_F420P_WAVES;
+}
 #undef MIJ_SCR
 #undef MIJ_WBR
 #undef MIJ_NWBR
@@ -192,6 +202,9 @@ extern "C" int mij_ctx_create(int device, mij_ctx **out)
 		if (f.band)
 			for (const void *k : f.k)
 				(void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
+	for (const void *k : k420_prefetch)
+		if (k)
+			(void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
 	(void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_encode420), hipFuncAttributeMaxDynamicSharedMemorySize, MIJ_ENC_LDS);
 	(void)hipGetLastError();
 	*out = c;
@@ -884,6 +897,20 @@ extern "C" int mij_batch_slot_kernel(const mij_batch *b, int slot, int *kind, in
 	return MIJ_OK;
 }
 
+/* tests: 1 when the launch that decodes the slot runs the pipelined twin of its kernel (band_prefetch on its list's LDS), 0 when the plain one */
+extern "C" int mij_batch_slot_pipelined(const mij_batch *b, int slot)
+{
+	if (!b || slot < 0 || slot >= (int)b->slots.size())
+		return set_err(MIJ_E_ARG, "mij_batch_slot_pipelined: bad slot");
+	if (!b->uploaded)
+		return set_err(MIJ_E_STATE, "mij_batch_slot_pipelined before mij_batch_upload");
+	const Choice &c = b->slots[(size_t)slot].choice;
+	for (const mij_batch::Launch &l : b->launches)
+		if (l.kind == c.kind && l.var == c.var)
+			return band_prefetch(l.kind, l.var, l.lds, (size_t)b->ctx->max_dyn_lds) ? 1 : 0;
+	return 0;
+}
+
 extern "C" int mij_batch_set_color(mij_batch *b, int slot, int color)
 {
 	if (!b || slot < 0 || slot >= (int)b->slots.size())
@@ -1456,7 +1483,9 @@ static void auto_bands(const mij_batch *b, int nb[MK_KINDS])
 		if (!n_fused[kind])
 			continue;
 		size_t per_cu = lds_max[kind] ? (size_t)b->ctx->max_dyn_lds / lds_max[kind] : 1;
-		const size_t by_waves = 4 * MIJ_F420_WAVES / ((size_t)families[kind].threads / 64); /* waves per SIMD by registers x four SIMDs */
+		/* waves per SIMD by registers x four SIMDs.  The pipelined twin of MK_420 allows MIJ_F420P_WAVES only, but it is taken just where the LDS
+		 * bound above is at most that many workgroups of four waves already (band_prefetch), so the count below is right for it as well */
+		const size_t by_waves = 4 * MIJ_F420_WAVES / ((size_t)families[kind].threads / 64);
 		per_cu = per_cu < 1 ? 1 : (per_cu > by_waves ? by_waves : per_cu);
 		const size_t slots = (size_t)cu * per_cu;
 		const double avg_rows = (double)mcu_rows_sum[kind] / (double)n_fused[kind];
@@ -1872,7 +1901,8 @@ extern "C" int mij_batch_launch(mij_batch *b)
 		const uint8_t *in = f.io == PLANES_OUT ? b->d_planes : b->d_coef;
 		uint8_t *out = f.io == COEF_PLANES ? b->d_planes : b->d_out;
 		void *args4[] = {&b->d_imgs, &wk, &in, &out}, *args5[] = {&b->d_imgs, &wk, &in, &out, &b->d_roi}; /* the windowed forms take the table of windows */
-		(void)hipLaunchKernel(f.k[L.var], dim3((unsigned)L.count), dim3(f.threads), f.roi ? args5 : args4, L.lds, b->stream);
+		const void *k = band_prefetch(L.kind, L.var, L.lds, (size_t)b->ctx->max_dyn_lds) ? k420_prefetch[L.var] : f.k[L.var];
+		(void)hipLaunchKernel(k, dim3((unsigned)L.count), dim3(f.threads), f.roi ? args5 : args4, L.lds, b->stream);
 		HIP_TRY(hipGetLastError());
 	}
 	/* the output passes, behind every decode family (both front ends end here): float output, tensor output into the callers' memory,

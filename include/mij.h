@@ -394,6 +394,9 @@ int mij_batch_slot_work_items(const mij_batch *b, int slot);
  * pass 2: YCbCr colour --, 1: compact planes), *segments the column segments per band (1 unless the row of MCUs is cut).  Any pointer may
  * be NULL.  *kind is -1 for a skipped slot; MIJ_E_STATE before upload, MIJ_E_ARG for a bad slot. */
 int mij_batch_slot_kernel(const mij_batch *b, int slot, int *kind, int *variant, int *segments);
+/* tests: 1 when the launch that decodes the slot runs the pipelined twin of its kernel (k_fused420p: compact planes without the wide IDCT, in a
+ * list whose LDS leaves a CU three workgroups at most), 0 when the plain kernel; kind, variant and segments do not tell the two apart */
+int mij_batch_slot_pipelined(const mij_batch *b, int slot);
 /* The format new coefficient planes of this batch get in HBM: MIJ_COEF_COMPACT (default; environment
  * MIJ_COEF_FORMAT=int16 flips the default) or MIJ_COEF_INT16.  Applies to slots added or uploaded afterwards. */
 int mij_batch_set_coef_format(mij_batch *b, int fmt);
