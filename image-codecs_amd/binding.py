@@ -774,6 +774,12 @@ class Batch:
         L.mij_batch_slot_pipelined.argtypes = [C.c_void_p, C.c_int]
         return bool(_check(L.mij_batch_slot_pipelined(self._h, int(slot)), "mij_batch_slot_pipelined"))
 
+    def slot_marched(self, slot):
+        """tests: True when the slot's launch runs the pipelined twin with the marching phase B, k_fused420m (mij_batch_slot_marched)"""
+        L = lib()
+        L.mij_batch_slot_marched.argtypes = [C.c_void_p, C.c_int]
+        return bool(_check(L.mij_batch_slot_marched(self._h, int(slot)), "mij_batch_slot_marched"))
+
     def slot_coef_bytes(self, slot):
         """1 when the slot's coefficients sit in HBM as compact planes (the default), 0 for the int16 tile layout."""
         return lib().mij_batch_slot_coef_bytes(self._h, int(slot))

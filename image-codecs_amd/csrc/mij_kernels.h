@@ -1286,6 +1286,21 @@ __device__ __forceinline__ void strip_row(const ColorK &K, uint32_t wk, uint32_t
 	store_px4<NOUT>(dst, p0, p1, p2, p3);
 }
 
+/* the first n < 4 pixels of such a strip, RGBA: the rest of a row behind its whole strips (fused_band, MARCH) */
+__device__ __forceinline__ void strip_row_part(const ColorK &K, uint32_t wk, uint32_t wk1, uint32_t vb0, uint32_t vb1, uint32_t vb2, uint32_t vr0, uint32_t vr1,
+															  uint32_t vr2, uint32_t yv, uint8_t *__restrict__ dst, int n)
+{
+	const uint32_t cb[4] = {dot4(vb0, wk1, K.w128), dot4(vb1, wk, K.w128), dot4(vb1, wk1, K.w128), dot4(vb2, wk, K.w128)};
+	const uint32_t cr[4] = {dot4(vr0, wk1, K.w128), dot4(vr1, wk, K.w128), dot4(vr1, wk1, K.w128), dot4(vr2, wk, K.w128)};
+	const uint32_t sel[4] = {K.p0, K.p1, K.p2, K.p3};
+#pragma unroll
+	for (int j = 0; j < 3; ++j)
+		if (j < n) {
+			const Rgb12 p = color_px(K, __builtin_amdgcn_perm(cr[j], yv, sel[j]), __builtin_amdgcn_perm(cb[j], yv, sel[j]));
+			reinterpret_cast<uint32_t *>(dst)[j] = sat4<12>(p.r, p.g, p.b, 0x7fffffff); /* alpha saturates to 255 */
+		}
+}
+
 /* (3 n + f + 2) >> 2 on the four bytes of n and f (even and odd bytes in 16-bit lanes: 3*255 + 255 + 2 < 2^16) */
 __device__ __forceinline__ uint32_t rs_v2(uint32_t n, uint32_t f)
 {
@@ -1344,7 +1359,13 @@ __device__ __forceinline__ BandTask band_task(int m, int ww, int lane0, int nYw,
  * 5840 pixels, 4:4:0 beyond 4300) are cut into column segments.  A segment transforms one MCU column more on either side (the horizontal
  * chroma filter reads c[i-1] and c[i+1], codec/jpeg.c:1784-1835); everything inside the kernel is in LOCAL columns (the segment plus its
  * halo), and only the plane addresses, the output columns and the picture-edge tests are global.  SEG = false compiles to the code it was. */
-template <int NOUT, bool WIDE, bool B8, bool H2, int NT, bool SEG = false, bool PF = false>
+/* MARCH = true (k_fused420m: 256 threads, 4:2:0, no segments, rows of at most 2048 pixels that the fast strips cover): another phase B.
+ * A lane owns strips tid and tid + 256 of EVERY row pair of the band, so what the strip loop works out per row pair -- which strips, their
+ * LDS offsets, the byte shift, the edge selector, the bounds tests, the store offset -- is computed once per workgroup, and the second
+ * strip sits at compile-time constants from the first (+512 bytes in a chroma row, +1024 in a luma row).  The aligned and edge-fixed
+ * vector of the upper chroma row and the luma dword of the row above an MCU row are carried in registers from the row pair before: a row
+ * pair loads the lower chroma row only, and the save buffers and their copy loop are not used (but for the halo row of the prologue). */
+template <int NOUT, bool WIDE, bool B8, bool H2, int NT, bool SEG = false, bool PF = false, bool MARCH = false>
 __device__ __forceinline__ void fused_band(const DevImage *__restrict__ imgs, const WorkBand *__restrict__ work, const uint8_t *__restrict__ coef,
 														 uint8_t *__restrict__ outbase)
 {
@@ -1513,6 +1534,103 @@ __device__ __forceinline__ void fused_band(const DevImage *__restrict__ imgs, co
 		}
 	};
 
+	/* ---- MARCH: the lane's strips a = tid and b = tid + NT, fixed for the band.  A strip that does not exist is loaded all the same (but
+	 * from the save buffers) and never emitted: the reads stay inside the workgroup's LDS.  The farthest is strip b of lane 255 in row 7 of
+	 * Cr, bytes [7 CP + 1020, 7 CP + 1028) behind sCr, and sCr has 8 CP + 64 mcu_x = 72 mcu_x bytes to the end of the save area: inside from
+	 * 15 MCU columns on, and the host sends nothing narrower than 16 here (mij_runtime.hip, band_march).  Luma ends 2048 bytes into row 15 at the
+	 * most, in front of the 144 mcu_x bytes of chroma planes and save area. */
+	static_assert(!MARCH || (NT == 256 && H2 && !SEG), "MARCH: 4:2:0 rows at 256 threads without column segments only");
+	struct MarchRows { /* bytes (c[i0-1], c[i0], c[i0+1], c[i0+2]) of a chroma row, columns clamped to the picture: Cb and Cr of strips a and b */
+		uint32_t ba, ra, bb, rb;
+	};
+	constexpr int M_CB = 2 * NT, M_YB = 4 * NT, M_XB = 4 * NT * NOUT; /* strip b behind strip a: bytes of a chroma row, a luma row, an output row */
+	[[maybe_unused]] MarchRows mA = {0u, 0u, 0u, 0u}; /* carried: chroma row C-1 */
+	[[maybe_unused]] uint32_t mYa = 0u, mYb = 0u;      /* carried: luma row 15 of the MCU row above (the band's first row pair emits no upper row) */
+	[[maybe_unused]] const int m_nld = aligned ? nstrip : 0, m_nfast = aligned ? (W >> 2) : 0; /* strips with samples; whole strips */
+	[[maybe_unused]] const int m_co = ((2 * tid - 1) >> 2) * 4, m_yo = 4 * tid; /* strip 0 reads the dword in front of the row (inside LDS); the edge fix discards it */
+	[[maybe_unused]] const uint32_t m_sh = (uint32_t)(2 * tid - 1) & 3u, m_xo0 = (uint32_t)(4 * tid) * NOUT;
+	/* picture edges: column -1 -> 0 and every column beyond wc-1 -> wc-1, as a byte selector (identity inside the picture).  For a whole
+	 * strip that is fused420's "byte 0 := byte 1" and "byte 3 := byte 2"; the partial strip of an RGBA row may end one column sooner */
+	auto m_edge_sel = [&](int s) {
+		const int i0 = 2 * s;
+		uint32_t sel = i0 == 0 ? 1u : 0u;
+		for (int k = 1; k < 4; ++k)
+			sel |= (uint32_t)max(min(k, wc - i0), 0) << (8 * k);
+		return sel;
+	};
+	[[maybe_unused]] const uint32_t m_sela = m_edge_sel(tid), m_selb = m_edge_sel(tid + NT);
+	[[maybe_unused]] const bool m_eda = __builtin_amdgcn_ballot_w64(tid < m_nld && m_sela != 0x03020100u) != 0; /* wave-uniform: a lane of the wave has an edge strip */
+	[[maybe_unused]] const bool m_edb = __builtin_amdgcn_ballot_w64(tid + NT < m_nld && m_selb != 0x03020100u) != 0;
+	[[maybe_unused]] const bool m_ema = tid < m_nfast, m_emb = tid + NT < m_nfast, m_lda = tid < m_nld, m_ldb = tid + NT < m_nld;
+	[[maybe_unused]] const bool m_tla = tid == m_nfast && tid < m_nld, m_tlb = tid + NT == m_nfast && tid + NT < m_nld; /* the partial last strip of an RGBA row */
+	[[maybe_unused]] const bool m_wave_tail = __builtin_amdgcn_ballot_w64(m_tla || m_tlb) != 0;
+	/* chroma rows cb / cr -> R: two dwords and a byte funnel shift per strip and component, all reads issued before the first use */
+	auto m_load = [&](const uint8_t *cb, const uint8_t *cr, bool planes, MarchRows &R) {
+		const uint32_t *pb = reinterpret_cast<const uint32_t *>(cb + m_co), *pr = reinterpret_cast<const uint32_t *>(cr + m_co);
+		uint32_t b0 = 0, b1 = 0, r0 = 0, r1 = 0, c0 = 0, c1 = 0, s0 = 0, s1 = 0;
+		if (planes || m_lda) { /* the planes have the save area behind them (above); the save buffers have nothing */
+			b0 = pb[0];
+			b1 = pb[1];
+			r0 = pr[0];
+			r1 = pr[1];
+		}
+		if (planes || m_ldb) {
+			c0 = pb[M_CB / 4];
+			c1 = pb[M_CB / 4 + 1];
+			s0 = pr[M_CB / 4];
+			s1 = pr[M_CB / 4 + 1];
+		}
+		R.ba = __builtin_amdgcn_alignbyte(b1, b0, m_sh);
+		R.ra = __builtin_amdgcn_alignbyte(r1, r0, m_sh);
+		R.bb = __builtin_amdgcn_alignbyte(c1, c0, m_sh);
+		R.rb = __builtin_amdgcn_alignbyte(s1, s0, m_sh);
+		if (m_eda) { /* the empty asm keeps these two a branch that the other waves skip: left alone they become four selects in every wave */
+			asm volatile("");
+			R.ba = __builtin_amdgcn_perm(0, R.ba, m_sela);
+			R.ra = __builtin_amdgcn_perm(0, R.ra, m_sela);
+		}
+		if (m_edb) {
+			asm volatile("");
+			R.bb = __builtin_amdgcn_perm(0, R.bb, m_selb);
+			R.rb = __builtin_amdgcn_perm(0, R.rb, m_selb);
+		}
+	};
+	/* output rows ra (upper chroma row A near, luma yA*) and ra + 1 (lower row B near, luma yB*) of the lane's strips */
+	auto m_emit = [&](const MarchRows &A, const MarchRows &B, uint32_t yAa, uint32_t yAb, uint32_t yBa, uint32_t yBb, int ra, bool doA, bool doB) {
+		uint8_t *const rowB = out + (size_t)(ra + 1) * opitch, *const rowA = rowB - opitch; /* wave-uniform; ra = -1 is never emitted */
+		/* the store takes the row in scalar registers and the lane's 32-bit offset; widened outside the loop it would be a 64-bit add per store */
+		uint32_t m_xo = m_xo0;
+		asm volatile("" : "+v"(m_xo));
+		if (m_ema) {
+			const uint32_t vb0 = __builtin_amdgcn_perm(A.ba, B.ba, KC.v0), vb1 = __builtin_amdgcn_perm(A.ba, B.ba, KC.v1), vb2 = __builtin_amdgcn_perm(A.ba, B.ba, KC.v2);
+			const uint32_t vr0 = __builtin_amdgcn_perm(A.ra, B.ra, KC.v0), vr1 = __builtin_amdgcn_perm(A.ra, B.ra, KC.v1), vr2 = __builtin_amdgcn_perm(A.ra, B.ra, KC.v2);
+			if (doB)
+				strip_row<NOUT>(KC, KC.wBk, KC.wBk1, vb0, vb1, vb2, vr0, vr1, vr2, yBa, rowB + m_xo);
+			if (doA)
+				strip_row<NOUT>(KC, KC.wAk, KC.wAk1, vb0, vb1, vb2, vr0, vr1, vr2, yAa, rowA + m_xo);
+		}
+		if (m_emb) {
+			const uint32_t vb0 = __builtin_amdgcn_perm(A.bb, B.bb, KC.v0), vb1 = __builtin_amdgcn_perm(A.bb, B.bb, KC.v1), vb2 = __builtin_amdgcn_perm(A.bb, B.bb, KC.v2);
+			const uint32_t vr0 = __builtin_amdgcn_perm(A.rb, B.rb, KC.v0), vr1 = __builtin_amdgcn_perm(A.rb, B.rb, KC.v1), vr2 = __builtin_amdgcn_perm(A.rb, B.rb, KC.v2);
+			if (doB)
+				strip_row<NOUT>(KC, KC.wBk, KC.wBk1, vb0, vb1, vb2, vr0, vr1, vr2, yBb, (rowB + M_XB) + m_xo);
+			if (doA)
+				strip_row<NOUT>(KC, KC.wAk, KC.wAk1, vb0, vb1, vb2, vr0, vr1, vr2, yAb, (rowA + M_XB) + m_xo);
+		}
+		if constexpr (NOUT == 4) { /* W % 4 pixels behind the whole strips (an RGB row with such a rest is not aligned): one lane of the workgroup */
+			if (m_wave_tail && (m_tla || m_tlb)) {
+				const uint32_t ab = m_tlb ? A.bb : A.ba, bb = m_tlb ? B.bb : B.ba, ar = m_tlb ? A.rb : A.ra, br = m_tlb ? B.rb : B.ra;
+				const uint32_t vb0 = __builtin_amdgcn_perm(ab, bb, KC.v0), vb1 = __builtin_amdgcn_perm(ab, bb, KC.v1), vb2 = __builtin_amdgcn_perm(ab, bb, KC.v2);
+				const uint32_t vr0 = __builtin_amdgcn_perm(ar, br, KC.v0), vr1 = __builtin_amdgcn_perm(ar, br, KC.v1), vr2 = __builtin_amdgcn_perm(ar, br, KC.v2);
+				const uint32_t xo = m_xo + (m_tlb ? (uint32_t)M_XB : 0u);
+				if (doB)
+					strip_row_part(KC, KC.wBk, KC.wBk1, vb0, vb1, vb2, vr0, vr1, vr2, m_tlb ? yBb : yBa, rowB + xo, W & 3);
+				if (doA)
+					strip_row_part(KC, KC.wAk, KC.wAk1, vb0, vb1, vb2, vr0, vr1, vr2, m_tlb ? yAb : yAa, rowA + xo, W & 3);
+			}
+		}
+	};
+
 	/* ---- prologue: chroma row 8*m0-1 from the block row above the band */
 	if (m0 > 0) {
 		chroma_halo(m0 - 1, 1, saveCb + sv * CP, saveCr + sv * CP);
@@ -1596,6 +1714,35 @@ __device__ __forceinline__ void fused_band(const DevImage *__restrict__ imgs, co
 		__syncthreads();
 
 		/* ---- phase B: chroma rows C = 8m .. 8m+7 -> output rows 2C-1, 2C */
+		if constexpr (MARCH) {
+			if (m == m0 && m0 > 0)
+				m_load(saveCb, saveCr, false, mA); /* the prologue's halo row; the barriers above order it */
+#pragma unroll 1
+			for (int cc = 0; cc < 8; ++cc) {
+				const int C = 8 * m + cc, ra = 2 * C - 1;
+				const bool doA = ra >= row_lo && ra < row_hi, doB = ra + 1 >= row_lo && ra + 1 < row_hi;
+				/* row offsets stay scalar: one add of the lane's offset per row read (as induction variables they are a vector add more each) */
+				int oc = cc * CP, oy = (2 * cc) * YP;
+				asm volatile("" : "+s"(oc), "+s"(oy));
+				/* row C, or beyond the last effective chroma row the row above once more */
+				MarchRows B = mA; /* rows below the picture emit nothing, the carry moves on */
+				if (C <= hc - 1)
+					m_load(sCb + oc, sCr + oc, true, B);
+				if (C == 0) /* the picture's top: row -1 is row 0 */
+					mA = B;
+				const uint8_t *py = sY + oy + m_yo;
+				const uint32_t yBa = *reinterpret_cast<const uint32_t *>(py), yBb = *reinterpret_cast<const uint32_t *>(py + M_YB);
+				uint32_t yAa = mYa, yAb = mYb;
+				if (cc > 0) {
+					yAa = *reinterpret_cast<const uint32_t *>(py - YP);
+					yAb = *reinterpret_cast<const uint32_t *>(py - YP + M_YB);
+				}
+				m_emit(mA, B, yAa, yAb, yBa, yBb, ra, doA, doB);
+				mA = B;
+			}
+			mYa = *reinterpret_cast<const uint32_t *>(sY + 15 * YP + m_yo);
+			mYb = *reinterpret_cast<const uint32_t *>(sY + 15 * YP + m_yo + M_YB);
+		} else {
 		for (int cc = 0; cc < 8; ++cc) {
 			const int C = 8 * m + cc;
 			/* row C-1: previous plane row, or the saved row, or (image top) row 0 itself */
@@ -1629,10 +1776,23 @@ __device__ __forceinline__ void fused_band(const DevImage *__restrict__ imgs, co
 			}
 			sv = nv;
 		}
+		}
 	}
 
-	/* ---- epilogue: the band's last row 16*m1-1 pairs chroma row 8*m1-1 (saved) with row 8*m1 */
-	{
+	/* ---- epilogue: the band's last row 16*m1-1 pairs chroma row 8*m1-1 (saved, or carried) with row 8*m1 */
+	if constexpr (MARCH) {
+		const int C = 8 * m1, ra = 2 * C - 1;
+		if (ra >= row_lo && ra < row_hi) {
+			MarchRows B = mA;
+			if (C <= hc - 1) { /* there is a block row below: its first sample row */
+				__syncthreads(); /* planes free */
+				chroma_halo(m1, 0, sCb, sCr);
+				__syncthreads();
+				m_load(sCb, sCr, true, B);
+			}
+			m_emit(mA, B, mYa, mYb, mYa, mYb, ra, true, false);
+		}
+	} else {
 		const int C = 8 * m1, ra = 2 * C - 1;
 		if (ra >= row_lo && ra < row_hi) {
 			__syncthreads(); /* planes free, save buffers written */
@@ -1669,6 +1829,19 @@ __global__ __launch_bounds__(MIJ_F420_NT) void k_fused420p(const DevImage *__res
 																			  uint8_t *__restrict__ outbase)
 {
 	fused_band<NOUT, false, true, true, MIJ_F420_NT, false, true>(imgs, work, coef, outbase);
+}
+
+/* ... and with phase B marching down its lanes' own strips (fused_band, MARCH): taken in k_fused420p's place where every picture of the
+ * list has rows of whole dwords, at most 2048 pixels wide, inside 32-bit offsets (mij_runtime.hip, band_march).  Three waves per SIMD as
+ * well.  A/B knob: -DMIJ_F420_MARCH=0 never takes it. */
+#ifndef MIJ_F420_MARCH
+#define MIJ_F420_MARCH 1
+#endif
+template <int NOUT>
+__global__ __launch_bounds__(MIJ_F420_NT) void k_fused420m(const DevImage *__restrict__ imgs, const WorkBand *__restrict__ work, const uint8_t *__restrict__ coef,
+																			  uint8_t *__restrict__ outbase)
+{
+	fused_band<NOUT, false, true, true, MIJ_F420_NT, false, true, true>(imgs, work, coef, outbase);
 }
 
 /* The same kernel with eight waves per workgroup, for pictures whose row of MCUs leaves room for only one or two workgroups in a CU's

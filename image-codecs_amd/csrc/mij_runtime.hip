@@ -135,6 +135,8 @@ static bool band_prefetch(int kind, int var, size_t lds, size_t cap)
 		return false;
 	return (cap / lds) * (families[MK_420].threads / 64) <= 4 * MIJ_F420P_WAVES;
 }
+/* ... and the twins whose phase B marches down its lanes' own strips (k_fused420m), taken in their place where band_march says so */
+static const void *const k420_march[MK_VARIANTS] = {nullptr, MIJ_K(k_fused420m<3>), nullptr, nullptr, nullptr, MIJ_K(k_fused420m<4>), nullptr, nullptr};
 #undef MIJ_SCR
 #undef MIJ_WBR
 #undef MIJ_NWBR
@@ -203,6 +205,9 @@ extern "C" int mij_ctx_create(int device, mij_ctx **out)
 			for (const void *k : f.k)
 				(void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
 	for (const void *k : k420_prefetch)
+		if (k)
+			(void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
+	for (const void *k : k420_march)
 		if (k)
 			(void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, c->max_dyn_lds);
 	(void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_encode420), hipFuncAttributeMaxDynamicSharedMemorySize, MIJ_ENC_LDS);
@@ -357,6 +362,7 @@ struct mij_batch {
 	struct Launch {
 		int kind, var;
 		size_t first, count, lds;
+		bool marched; /* a pipelined launch of MK_420 that takes k_fused420m (band_march) */
 	};
 	std::vector<Launch> launches;
 	bool uploaded = false, launched = false;
@@ -908,6 +914,20 @@ extern "C" int mij_batch_slot_pipelined(const mij_batch *b, int slot)
 	for (const mij_batch::Launch &l : b->launches)
 		if (l.kind == c.kind && l.var == c.var)
 			return band_prefetch(l.kind, l.var, l.lds, (size_t)b->ctx->max_dyn_lds) ? 1 : 0;
+	return 0;
+}
+
+/* tests: 1 when that launch runs the twin whose phase B marches down its lanes' own strips (band_march), 0 otherwise */
+extern "C" int mij_batch_slot_marched(const mij_batch *b, int slot)
+{
+	if (!b || slot < 0 || slot >= (int)b->slots.size())
+		return set_err(MIJ_E_ARG, "mij_batch_slot_marched: bad slot");
+	if (!b->uploaded)
+		return set_err(MIJ_E_STATE, "mij_batch_slot_marched before mij_batch_upload");
+	const Choice &c = b->slots[(size_t)slot].choice;
+	for (const mij_batch::Launch &l : b->launches)
+		if (l.kind == c.kind && l.var == c.var)
+			return l.marched ? 1 : 0;
 	return 0;
 }
 
@@ -1483,7 +1503,7 @@ static void auto_bands(const mij_batch *b, int nb[MK_KINDS])
 		if (!n_fused[kind])
 			continue;
 		size_t per_cu = lds_max[kind] ? (size_t)b->ctx->max_dyn_lds / lds_max[kind] : 1;
-		/* waves per SIMD by registers x four SIMDs.  The pipelined twin of MK_420 allows MIJ_F420P_WAVES only, but it is taken just where the LDS
+		/* waves per SIMD by registers x four SIMDs.  The pipelined twins of MK_420 (k_fused420p, k_fused420m) allow MIJ_F420P_WAVES only, but are taken just where the LDS
 		 * bound above is at most that many workgroups of four waves already (band_prefetch), so the count below is right for it as well */
 		const size_t by_waves = 4 * MIJ_F420_WAVES / ((size_t)families[kind].threads / 64);
 		per_cu = per_cu < 1 ? 1 : (per_cu > by_waves ? by_waves : per_cu);
@@ -1730,6 +1750,25 @@ static int scratch_planes(mij_batch *b, size_t need)
 	return MIJ_OK;
 }
 
+/* Whether a launch takes k_fused420m where it would take k_fused420p: every picture of its list has rows of whole dwords (RGBA, or a width
+ * that is a multiple of four), an output inside the 32-bit offsets of fused_band's fast strips (its `aligned`), and at most 2048 pixels a row,
+ * two strips per lane -- and at least 16 MCU columns, below which a lane's second strip would be read from behind the workgroup's LDS
+ * (mij_kernels.h, fused_band; MK_420 holds no picture that narrow as the forms are chosen now).  One picture that does not: the whole list stays. */
+static bool band_march(const mij_batch *b, int kind, int var, size_t lds, const std::vector<Work4> &L)
+{
+	if (!MIJ_F420_MARCH || !band_prefetch(kind, var, lds, (size_t)b->ctx->max_dyn_lds) || !k420_march[var])
+		return false;
+	const uint32_t n_out = (var & 4) ? 4u : 3u;
+	for (const Work4 &w : L) {
+		const DevImage &d = b->slots[(size_t)w.a].dev;
+		const bool dwords = n_out == 4 || (d.width & 3) == 0;
+		const bool fits = (uint64_t)((uint32_t)d.width * n_out) * (uint32_t)d.height < 0xfffffff0ull;
+		if (!dwords || !fits || d.width > 2048 || d.mcu_x < 16)
+			return false;
+	}
+	return true;
+}
+
 /* work lists: the pack list first, then one range per launch in family and variant order; then the descriptors and the lists go up */
 static int lay_out_work(mij_batch *b, const Plan &p)
 {
@@ -1752,7 +1791,7 @@ static int lay_out_work(mij_batch *b, const Plan &p)
 			if (L.empty())
 				continue;
 			memcpy(b->h_work + pos, L.data(), L.size() * sizeof(Work4));
-			b->launches.push_back(mij_batch::Launch{k, v, pos, L.size(), p.lds[k][v]});
+			b->launches.push_back(mij_batch::Launch{k, v, pos, L.size(), p.lds[k][v], band_march(b, k, v, p.lds[k][v], L)});
 			pos += L.size();
 		}
 	const size_t n = b->slots.size();
@@ -1901,7 +1940,7 @@ extern "C" int mij_batch_launch(mij_batch *b)
 		const uint8_t *in = f.io == PLANES_OUT ? b->d_planes : b->d_coef;
 		uint8_t *out = f.io == COEF_PLANES ? b->d_planes : b->d_out;
 		void *args4[] = {&b->d_imgs, &wk, &in, &out}, *args5[] = {&b->d_imgs, &wk, &in, &out, &b->d_roi}; /* the windowed forms take the table of windows */
-		const void *k = band_prefetch(L.kind, L.var, L.lds, (size_t)b->ctx->max_dyn_lds) ? k420_prefetch[L.var] : f.k[L.var];
+		const void *k = L.marched ? k420_march[L.var] : (band_prefetch(L.kind, L.var, L.lds, (size_t)b->ctx->max_dyn_lds) ? k420_prefetch[L.var] : f.k[L.var]);
 		(void)hipLaunchKernel(k, dim3((unsigned)L.count), dim3(f.threads), f.roi ? args5 : args4, L.lds, b->stream);
 		HIP_TRY(hipGetLastError());
 	}

@@ -397,6 +397,9 @@ int mij_batch_slot_kernel(const mij_batch *b, int slot, int *kind, int *variant,
 /* tests: 1 when the launch that decodes the slot runs the pipelined twin of its kernel (k_fused420p: compact planes without the wide IDCT, in a
  * list whose LDS leaves a CU three workgroups at most), 0 when the plain kernel; kind, variant and segments do not tell the two apart */
 int mij_batch_slot_pipelined(const mij_batch *b, int slot);
+/* tests: 1 when that launch runs k_fused420m, the pipelined twin whose phase B marches down its lanes' own strips: a pipelined list of which every
+ * picture has rows of whole dwords (four channels, or a width that is a multiple of four) of at most 2048 pixels; 0 otherwise */
+int mij_batch_slot_marched(const mij_batch *b, int slot);
 /* The format new coefficient planes of this batch get in HBM: MIJ_COEF_COMPACT (default; environment
  * MIJ_COEF_FORMAT=int16 flips the default) or MIJ_COEF_INT16.  Applies to slots added or uploaded afterwards. */
 int mij_batch_set_coef_format(mij_batch *b, int fmt);
