@@ -41,6 +41,9 @@ from .binding import (  # noqa: F401
     PinnedBuffer,
     host_transform,
     emit_jpeg,
+    write_histogram,
+    optimal_huffman_table,
+    MJW_OPTIMIZE_HUFFMAN,
     mij_write_jpg_to_memory,
     mij_write_jpg_batch,
     HostDecoder,

@@ -1183,6 +1183,9 @@ class PinnedBuffer:
 
 # ---------------------------------------------------------------- encoder (config 5)
 
+MJW_OPTIMIZE_HUFFMAN = 1
+
+
 class WritePlan(C.Structure):
     """mjw_plan (include/mij_host.h)."""
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("comp", C.c_int), ("subsample", C.c_int), ("mcu_x", C.c_int),
@@ -1211,34 +1214,65 @@ def host_transform(pixels, quality=90, flip=False):
     return plan, du.reshape(-1, 64)
 
 
-def emit_jpeg(plan, du):
-    """mjw_emit: headers + Huffman stage over given data units -> bytes."""
+def emit_jpeg(plan, du, optimize=False):
+    """mjw_emit: headers + Huffman stage over given data units -> bytes.  optimize: mjw_emit_optimized, the same stream with Huffman
+    tables built from the units' own symbol statistics."""
     L = lib()
-    L.mjw_emit.argtypes = [C.POINTER(WritePlan), C.c_void_p, _WRITE_CB, C.c_void_p]
+    fn = L.mjw_emit_optimized if optimize else L.mjw_emit
+    fn.argtypes = [C.POINTER(WritePlan), C.c_void_p, _WRITE_CB, C.c_void_p]
     chunks = []
     cb = _WRITE_CB(lambda _c, data, size: chunks.append(C.string_at(data, size)))
     d = np.ascontiguousarray(du, dtype=np.int16)
-    ok = L.mjw_emit(C.byref(plan), d.ctypes.data_as(C.c_void_p), cb, None)
+    ok = fn(C.byref(plan), d.ctypes.data_as(C.c_void_p), cb, None)
     return b"".join(chunks) if ok else None
 
 
-def mij_write_jpg_to_memory(pixels, quality=90):
-    """mij_write_jpg_to_func: the writer with its transform stage on the GPU -> bytes (None on failure)."""
+def write_histogram(plan, du):
+    """mjw_histogram: the symbols mjw_emit emits for these units, counted -> uint32 [4, 256] (luma DC, chroma DC, luma AC, chroma AC),
+    None when it is refused."""
+    L = lib()
+    L.mjw_histogram.argtypes = [C.POINTER(WritePlan), C.c_void_p, C.c_void_p]
+    d = np.ascontiguousarray(du, dtype=np.int16)
+    freq = np.zeros((4, 256), np.uint32)
+    return freq if L.mjw_histogram(C.byref(plan), d.ctypes.data_as(C.c_void_p), freq.ctypes.data_as(C.c_void_p)) else None
+
+
+def optimal_huffman_table(freq):
+    """mjw_optimal_table: 256 counts -> (BITS[16], HUFFVAL) as lists, None when a code would exceed 32 bits before shortening."""
+    L = lib()
+    L.mjw_optimal_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    f = np.ascontiguousarray(freq, dtype=np.uint32)
+    if f.shape != (256,):
+        raise ValueError("freq must hold 256 counts")
+    bits, vals, n = np.zeros(16, np.uint8), np.zeros(256, np.uint8), C.c_int()
+    if not L.mjw_optimal_table(f.ctypes.data_as(C.c_void_p), bits.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p), C.byref(n)):
+        return None
+    return bits.tolist(), vals[:n.value].tolist()
+
+
+def mij_write_jpg_to_memory(pixels, quality=90, optimize=False):
+    """mij_write_jpg_to_func: the writer with its transform stage on the GPU -> bytes (None on failure).  optimize:
+    mij_write_jpg_to_func_ex with MJW_OPTIMIZE_HUFFMAN."""
     a = np.ascontiguousarray(pixels, dtype=np.uint8)
     if a.ndim == 2:
         a = a[:, :, None]
     h, w, comp = a.shape
     L = lib()
+    L.mij_write_jpg_to_func_ex.argtypes = [_WRITE_CB, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_uint]
     L.mij_write_jpg_to_func.argtypes = [_WRITE_CB, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     chunks = []
     cb = _WRITE_CB(lambda _c, data, size: chunks.append(C.string_at(data, size)))
-    ok = L.mij_write_jpg_to_func(cb, None, w, h, comp, a.ctypes.data_as(C.c_void_p), int(quality))
+    if optimize:
+        ok = L.mij_write_jpg_to_func_ex(cb, None, w, h, comp, a.ctypes.data_as(C.c_void_p), int(quality), MJW_OPTIMIZE_HUFFMAN)
+    else:
+        ok = L.mij_write_jpg_to_func(cb, None, w, h, comp, a.ctypes.data_as(C.c_void_p), int(quality))
     return b"".join(chunks) if ok else None
 
 
-def mij_write_jpg_batch(images, quality=90, threads=16):
+def mij_write_jpg_batch(images, quality=90, threads=16, optimize=False):
     """mij_write_jpg_batch: a list of uint8 pictures [h, w, comp] (or [h, w]; None = a NULL pixel pointer) -> list of byte streams
-    (None where the picture was refused).  A negative return raises; the C side has released every stream by then."""
+    (None where the picture was refused).  A negative return raises; the C side has released every stream by then.  optimize:
+    mij_write_jpg_batch_ex with MJW_OPTIMIZE_HUFFMAN."""
     L = lib()
     arrs = []
     for im in images:
@@ -1257,7 +1291,12 @@ def mij_write_jpg_batch(images, quality=90, threads=16):
     cs = (C.c_int * n)(*[(a.shape[2] if a is not None else 3) for a in arrs])
     out = (C.c_void_p * n)()
     lens = (C.c_size_t * n)()
-    rc = L.mij_write_jpg_batch(px, xs, ys, cs, n, int(quality), int(threads), out, lens)
+    if optimize:
+        L.mij_write_jpg_batch_ex.restype = C.c_int
+        L.mij_write_jpg_batch_ex.argtypes = L.mij_write_jpg_batch.argtypes + [C.c_uint]
+        rc = L.mij_write_jpg_batch_ex(px, xs, ys, cs, n, int(quality), int(threads), out, lens, MJW_OPTIMIZE_HUFFMAN)
+    else:
+        rc = L.mij_write_jpg_batch(px, xs, ys, cs, n, int(quality), int(threads), out, lens)
     if rc < 0:
         assert not any(out[i] for i in range(n)), "mij_write_jpg_batch returned an error and left streams allocated"
         raise MijError("mij_write_jpg_batch: error %d" % rc)
@@ -1360,6 +1399,19 @@ class Encoder:
         if L.mjw_plan_init(C.byref(plan), int(width), int(height), int(comp), int(quality)) and d.size != plan.du_elems():
             raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, plan.du_elems()))
         return _check(L.mij_enc_add_units(self._h, int(width), int(height), int(comp), int(quality), d.ctypes.data_as(C.c_void_p)), "mij_enc_add_units")
+
+    def set_optimize(self, slot, on=True):
+        """mij_enc_set_optimize: the slot's stream gets Huffman tables built from its own symbol statistics; before upload."""
+        L = lib()
+        L.mij_enc_set_optimize.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        _check(L.mij_enc_set_optimize(self._h, int(slot), int(bool(on))), "mij_enc_set_optimize")
+
+    def slot_optimized(self, slot):
+        """mij_enc_slot_optimized, after fetch_streams: True when the slot's stream carries its own tables, False when optimisation
+        was not asked for it or it fell back to the plain tables."""
+        L = lib()
+        L.mij_enc_slot_optimized.argtypes = [C.c_void_p, C.c_int]
+        return bool(_check(L.mij_enc_slot_optimized(self._h, int(slot)), "mij_enc_slot_optimized"))
 
     def stream_reserve(self, nbytes):
         """mij_enc_stream_reserve: the GPU emission arena (0 releases it); before upload."""

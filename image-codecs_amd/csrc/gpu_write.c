@@ -96,13 +96,18 @@ static void pool_give(pooled_enc *e)
 
 int mij_write_jpg_to_func(mjw_write_func *func, void *context, int x, int y, int comp, const void *data, int quality)
 {
+	return mij_write_jpg_to_func_ex(func, context, x, y, comp, data, quality, 0);
+}
+
+int mij_write_jpg_to_func_ex(mjw_write_func *func, void *context, int x, int y, int comp, const void *data, int quality, unsigned flags)
+{
 	mjw_plan plan;
 	mij_ctx *ctx;
 	pooled_enc pe;
 	int16_t *du = NULL;
 	size_t elems, pix;
 	int slot, ok = 0;
-	if (!func || !data || !mjw_plan_init(&plan, x, y, comp, quality))
+	if (!func || !data || (flags & ~MJW_OPTIMIZE_HUFFMAN) || !mjw_plan_init(&plan, x, y, comp, quality))
 		return 0;
 	ctx = writer_ctx();
 	if (!ctx)
@@ -114,7 +119,7 @@ int mij_write_jpg_to_func(mjw_write_func *func, void *context, int x, int y, int
 	du = (int16_t *)malloc(elems * sizeof(int16_t));
 	slot = du ? mij_enc_add(pe.enc, data, x, y, comp, quality, mjw_flip_on_write()) : -1;
 	if (slot >= 0 && mij_enc_upload(pe.enc) == MIJ_OK && mij_enc_launch(pe.enc) == MIJ_OK && mij_enc_fetch(pe.enc, slot, du, elems) == MIJ_OK)
-		ok = mjw_emit(&plan, du, func, context);
+		ok = (flags & MJW_OPTIMIZE_HUFFMAN ? mjw_emit_optimized : mjw_emit)(&plan, du, func, context);
 	free(du);
 	pool_give(&pe);
 	return ok;
@@ -132,6 +137,7 @@ typedef struct {
 	unsigned char **out;
 	size_t *out_len;
 	int lo, hi, next, phase, ok, stage_failed;
+	unsigned flags;
 	pthread_mutex_t lock;
 } wb_job;
 
@@ -158,7 +164,7 @@ static void *wb_worker(void *arg)
 				/* a coefficient takes at most 27 bits and every output byte may be a stuffed 0xFF: under 7 bytes each (untouched pages cost nothing) */
 				const size_t cap = 2048 + mjw_plan_du_count(&plan) * 64 * 7;
 				unsigned char *buf = (unsigned char *)malloc(cap);
-				const size_t len = buf ? mjw_emit_to_memory(&plan, du, buf, cap) : 0;
+				const size_t len = buf ? (j->flags & MJW_OPTIMIZE_HUFFMAN ? mjw_emit_optimized_to_memory : mjw_emit_to_memory)(&plan, du, buf, cap) : 0;
 				if (len) {
 					unsigned char *fit = (unsigned char *)realloc(buf, len);
 					j->out[i] = fit ? fit : buf;
@@ -204,12 +210,18 @@ static void wb_run(wb_job *j, mij_encoder *enc, int phase, int lo, int hi, int t
 int mij_write_jpg_batch(const void *const *pixels, const int *x, const int *y, const int *comp, int n, int quality, int threads,
 								unsigned char **out, size_t *out_len)
 {
+	return mij_write_jpg_batch_ex(pixels, x, y, comp, n, quality, threads, out, out_len, 0);
+}
+
+int mij_write_jpg_batch_ex(const void *const *pixels, const int *x, const int *y, const int *comp, int n, int quality, int threads,
+									unsigned char **out, size_t *out_len, unsigned flags)
+{
 	mij_ctx *ctx;
 	pooled_enc pe[2];
 	wb_job j;
 	size_t pix_max = 0, dub_max = 0;
 	int i, *slot, *cend, nchunk = 0, rc = MIJ_OK, have[2] = {0, 0}, queued[2] = {0, 0}, img_max = 0, c;
-	if (!pixels || !x || !y || !comp || !out || !out_len || n < 0)
+	if (!pixels || !x || !y || !comp || !out || !out_len || n < 0 || (flags & ~MJW_OPTIMIZE_HUFFMAN))
 		return MIJ_E_ARG;
 	for (i = 0; i < n; ++i) {
 		out[i] = NULL;
@@ -264,6 +276,7 @@ int mij_write_jpg_batch(const void *const *pixels, const int *x, const int *y, c
 	j.slot = slot;
 	j.out = out;
 	j.out_len = out_len;
+	j.flags = flags;
 	pthread_mutex_init(&j.lock, NULL);
 	if (threads < 1)
 		threads = 1;

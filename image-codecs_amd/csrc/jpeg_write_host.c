@@ -486,26 +486,16 @@ void mjw_huff_tables(uint16_t code[4][256], uint8_t len[4][256])
 		}
 }
 
-int mjw_emit(const mjw_plan *p, const int16_t *du, mjw_write_func *func, void *context)
+/* headers (hdr_len bytes), the entropy-coded segment under the four tables, fill and EOI */
+static int emit_with(const mjw_plan *p, const int16_t *du, mjw_write_func *func, void *context, const enc_table *ydc, const enc_table *yac,
+							const enc_table *cdc, const enc_table *cac, const unsigned char *hdr, size_t hdr_len)
 {
-	enc_table ydc, yac, cdc, cac;
-	jw_sink *s;
-	if (!func || !du)
-		return 0;
-	s = (jw_sink *)calloc(1, sizeof(*s));
+	jw_sink *s = (jw_sink *)calloc(1, sizeof(*s));
 	if (!s)
 		return 0;
 	s->func = func;
 	s->context = context;
-	make_enc_table(&ydc, k_dc_lum_bits, k_dc_vals);
-	make_enc_table(&cdc, k_dc_chr_bits, k_dc_vals);
-	make_enc_table(&yac, k_ac_lum_bits, k_ac_lum_vals);
-	make_enc_table(&cac, k_ac_chr_bits, k_ac_chr_vals);
-	/* headers (codec/jpeg_write.c:245-268) */
-	{
-		unsigned char hdr[MJW_HEADER_BYTES];
-		sink_bytes(s, hdr, (int)mjw_header(p, hdr));
-	}
+	sink_bytes(s, hdr, (int)hdr_len); /* headers (codec/jpeg_write.c:245-268) */
 	{
 		int dcy = 0, dcu = 0, dcv = 0;
 		size_t m, nm = (size_t)p->mcu_x * (size_t)p->mcu_y;
@@ -513,17 +503,17 @@ int mjw_emit(const mjw_plan *p, const int16_t *du, mjw_write_func *func, void *c
 		s->nacc = 0;
 		for (m = 0; m < nm; ++m) {
 			if (p->subsample) {
-				dcy = emit_du(s, du, dcy, &ydc, &yac);
-				dcy = emit_du(s, du + 64, dcy, &ydc, &yac);
-				dcy = emit_du(s, du + 128, dcy, &ydc, &yac);
-				dcy = emit_du(s, du + 192, dcy, &ydc, &yac);
-				dcu = emit_du(s, du + 256, dcu, &cdc, &cac);
-				dcv = emit_du(s, du + 320, dcv, &cdc, &cac);
+				dcy = emit_du(s, du, dcy, ydc, yac);
+				dcy = emit_du(s, du + 64, dcy, ydc, yac);
+				dcy = emit_du(s, du + 128, dcy, ydc, yac);
+				dcy = emit_du(s, du + 192, dcy, ydc, yac);
+				dcu = emit_du(s, du + 256, dcu, cdc, cac);
+				dcv = emit_du(s, du + 320, dcv, cdc, cac);
 				du += 384;
 			} else {
-				dcy = emit_du(s, du, dcy, &ydc, &yac);
-				dcu = emit_du(s, du + 64, dcu, &cdc, &cac);
-				dcv = emit_du(s, du + 128, dcv, &cdc, &cac);
+				dcy = emit_du(s, du, dcy, ydc, yac);
+				dcu = emit_du(s, du + 64, dcu, cdc, cac);
+				dcv = emit_du(s, du + 128, dcv, cdc, cac);
 				du += 192;
 			}
 		}
@@ -535,6 +525,186 @@ int mjw_emit(const mjw_plan *p, const int16_t *du, mjw_write_func *func, void *c
 	sink_flush(s);
 	free(s);
 	return 1;
+}
+
+int mjw_emit(const mjw_plan *p, const int16_t *du, mjw_write_func *func, void *context)
+{
+	enc_table ydc, yac, cdc, cac;
+	unsigned char hdr[MJW_HEADER_BYTES];
+	if (!func || !du)
+		return 0;
+	make_enc_table(&ydc, k_dc_lum_bits, k_dc_vals);
+	make_enc_table(&cdc, k_dc_chr_bits, k_dc_vals);
+	make_enc_table(&yac, k_ac_lum_bits, k_ac_lum_vals);
+	make_enc_table(&cac, k_ac_chr_bits, k_ac_chr_vals);
+	return emit_with(p, du, func, context, &ydc, &yac, &cdc, &cac, hdr, mjw_header(p, hdr));
+}
+
+/* ---- optimised Huffman tables (include/mij_host.h): the symbols mjw_emit emits, counted; ITU-T T.81 K.2 on the counts */
+
+/* one unit's symbols into its DC and AC histograms: emit_du's walk with counts in place of codes */
+static int count_du(const int16_t *du, int dc_pred, uint32_t *fdc, uint32_t *fac)
+{
+	const int diff = du[0] - dc_pred;
+	unsigned bits;
+	int nbits = 0, prev = 0, i;
+	if (diff)
+		magnitude_bits(diff, &bits, &nbits);
+	++fdc[nbits];
+	for (i = 1; i < 64; ++i)
+		if (du[i]) {
+			const int run = i - prev - 1;
+			prev = i;
+			fac[0xF0] += (uint32_t)(run >> 4);
+			magnitude_bits(du[i], &bits, &nbits);
+			++fac[(((run & 15) << 4) + nbits) & 255];
+		}
+	if (prev != 63)
+		++fac[0x00];
+	return du[0];
+}
+
+int mjw_histogram(const mjw_plan *p, const int16_t *du, uint32_t freq[4][256])
+{
+	int dcy = 0, dcu = 0, dcv = 0;
+	size_t m, nm;
+	if (!p || !du || !freq || mjw_plan_du_count(p) > (size_t)(UINT32_MAX / 64))
+		return 0;
+	memset(freq, 0, sizeof(uint32_t) * 4 * 256);
+	nm = (size_t)p->mcu_x * (size_t)p->mcu_y;
+	for (m = 0; m < nm; ++m) {
+		int k;
+		for (k = 0; k < (p->subsample ? 4 : 1); ++k, du += 64)
+			dcy = count_du(du, dcy, freq[0], freq[2]);
+		dcu = count_du(du, dcu, freq[1], freq[3]);
+		dcv = count_du(du + 64, dcv, freq[1], freq[3]);
+		du += 128;
+	}
+	return 1;
+}
+
+int mjw_optimal_table(const uint32_t freq_in[256], uint8_t bits_out[16], uint8_t vals[256], int *nvals)
+{
+	uint64_t freq[257];
+	int codesize[257], others[257], bits[33], i, j, n = 0;
+	if (!freq_in || !bits_out || !vals || !nvals)
+		return 0;
+	for (i = 0; i < 256; ++i)
+		freq[i] = freq_in[i];
+	freq[256] = 1; /* the pseudo-symbol that keeps the all-ones code free */
+	for (i = 0; i < 257; ++i) {
+		codesize[i] = 0;
+		others[i] = -1;
+	}
+	for (;;) {
+		int c1 = -1, c2 = -1;
+		uint64_t v = UINT64_MAX;
+		for (i = 0; i <= 256; ++i)
+			if (freq[i] && freq[i] <= v) {
+				v = freq[i];
+				c1 = i;
+			}
+		v = UINT64_MAX;
+		for (i = 0; i <= 256; ++i)
+			if (freq[i] && freq[i] <= v && i != c1) {
+				v = freq[i];
+				c2 = i;
+			}
+		if (c2 < 0)
+			break;
+		freq[c1] += freq[c2];
+		freq[c2] = 0;
+		for (++codesize[c1]; others[c1] >= 0; ++codesize[c1])
+			c1 = others[c1];
+		others[c1] = c2;
+		for (++codesize[c2]; others[c2] >= 0; ++codesize[c2])
+			c2 = others[c2];
+	}
+	memset(bits, 0, sizeof(bits));
+	for (i = 0; i <= 256; ++i)
+		if (codesize[i]) {
+			if (codesize[i] > 32)
+				return 0;
+			++bits[codesize[i]];
+		}
+	for (i = 32; i > 16; --i)
+		while (bits[i] > 0) {
+			for (j = i - 2; bits[j] == 0; --j)
+				;
+			bits[i] -= 2;
+			++bits[i - 1];
+			bits[j + 1] += 2;
+			--bits[j];
+		}
+	for (i = 16; i > 0 && bits[i] == 0; --i)
+		;
+	if (i > 0)
+		--bits[i]; /* the pseudo-symbol's code */
+	for (i = 1; i <= 16; ++i)
+		bits_out[i - 1] = (uint8_t)bits[i];
+	for (i = 1; i <= 32; ++i)
+		for (j = 0; j < 256; ++j)
+			if (codesize[j] == i)
+				vals[n++] = (uint8_t)j;
+	*nvals = n;
+	return 1;
+}
+
+size_t mjw_header_optimized(const mjw_plan *p, const uint8_t bits[4][16], const uint8_t vals[4][256], unsigned char *out)
+{
+	static const unsigned char sos[] = {0xFF, 0xDA, 0, 0xC, 3, 1, 0, 2, 0x11, 3, 0x11, 0, 0x3F, 0};
+	static const unsigned char ids[4] = {0x00, 0x10, 0x01, 0x11};
+	static const int order[4] = {0, 2, 1, 3}; /* mjw_header's: luma DC, luma AC, chroma DC, chroma AC */
+	unsigned char plain[MJW_HEADER_BYTES], *o = out + 177;
+	int k, i, n;
+	mjw_header(p, plain);
+	memcpy(out, plain, 177); /* up to and including the DHT length */
+	for (k = 0; k < 4; ++k) {
+		const int t = order[k];
+		for (i = 0, n = 0; i < 16; ++i)
+			n += bits[t][i];
+		*o++ = ids[k];
+		memcpy(o, bits[t], 16);
+		memcpy(o + 16, vals[t], (size_t)n);
+		o += 16 + n;
+	}
+	n = (int)(o - (out + 175));
+	out[175] = (unsigned char)(n >> 8);
+	out[176] = (unsigned char)(n & 0xff);
+	memcpy(o, sos, sizeof(sos));
+	return (size_t)(o - out) + sizeof(sos);
+}
+
+int mjw_optimized_tables(const mjw_plan *p, const int16_t *du, uint8_t bits[4][16], uint8_t vals[4][256])
+{
+	uint32_t freq[4][256];
+	int t, n;
+	if (!mjw_histogram(p, du, freq))
+		return 0;
+	for (t = 0; t < 4; ++t) {
+		memset(vals[t], 0, 256);
+		if (!mjw_optimal_table(freq[t], bits[t], vals[t], &n))
+			return 0;
+	}
+	return 1;
+}
+
+int mjw_emit_optimized(const mjw_plan *p, const int16_t *du, mjw_write_func *func, void *context)
+{
+	uint8_t bits[4][16], vals[4][256];
+	unsigned char b17[17], hdr[MJW_HEADER_BYTES];
+	enc_table t[4];
+	int k;
+	if (!func || !du || !p)
+		return 0;
+	if (!mjw_optimized_tables(p, du, bits, vals))
+		return mjw_emit(p, du, func, context); /* a code longer than 32 bits before limiting: the plain tables */
+	for (k = 0; k < 4; ++k) {
+		b17[0] = 0;
+		memcpy(b17 + 1, bits[k], 16);
+		make_enc_table(&t[k], b17, vals[k]);
+	}
+	return emit_with(p, du, func, context, &t[0], &t[2], &t[1], &t[3], hdr, mjw_header_optimized(p, bits, vals, hdr));
 }
 
 typedef struct {
@@ -552,7 +722,7 @@ static void mem_sink_write(void *context, void *data, int size)
 	memcpy(m->out + m->len, data, (size_t)size);
 	m->len += (size_t)size;
 }
-size_t mjw_emit_to_memory(const mjw_plan *p, const int16_t *du, unsigned char *out, size_t cap)
+static size_t emit_to_memory(const mjw_plan *p, const int16_t *du, unsigned char *out, size_t cap, int optimize)
 {
 	mem_sink m;
 	if (!p || !du || !out)
@@ -561,10 +731,12 @@ size_t mjw_emit_to_memory(const mjw_plan *p, const int16_t *du, unsigned char *o
 	m.cap = cap;
 	m.len = 0;
 	m.overflow = 0;
-	if (!mjw_emit(p, du, mem_sink_write, &m) || m.overflow)
+	if (!(optimize ? mjw_emit_optimized : mjw_emit)(p, du, mem_sink_write, &m) || m.overflow)
 		return 0;
 	return m.len;
 }
+size_t mjw_emit_to_memory(const mjw_plan *p, const int16_t *du, unsigned char *out, size_t cap) { return emit_to_memory(p, du, out, cap, 0); }
+size_t mjw_emit_optimized_to_memory(const mjw_plan *p, const int16_t *du, unsigned char *out, size_t cap) { return emit_to_memory(p, du, out, cap, 1); }
 
 int stbi_write_jpg_to_func(stbi_write_func *func, void *context, int x, int y, int comp, const void *data, int quality)
 {

@@ -19,6 +19,16 @@
  *                  first tile stores the headers, its last tile the EOI
  * Bits left below a byte after the fill are dropped (they are the last tile's tail).  Nothing but the streams of fitting slots is
  * written to the arena, and the data units are only read.
+ *
+ * Optimised Huffman tables (mij_enc_set_optimize; the contract is mjw_emit_optimized's, include/mij_host.h): two more launches in
+ * front of the six, over the optimised slots only, and none when there is no such slot:
+ *   k_emit_hist    per tile of an optimised slot: the symbols its lanes own, counted in an LDS histogram and added to the slot's
+ *                  uint32 [4][256] counts
+ *   k_emit_build   one workgroup per optimised slot, one wavefront per table: ITU-T T.81 K.2 on the counts (libjpeg's tie-breaking),
+ *                  the slot's EmitTables entry, its DHT segment and header length; a slot with a code above 32 bits before the
+ *                  shortening keeps table 0 (the plain tables) and the plain header
+ * The tile kernels read the tables their EmitTile.tab names -- in the tile's own entry, so that the copy of the tables into LDS waits
+ * for that entry alone and not for the slot's as well -- and the header length EmitSlot.hlen.
  */
 #pragma once
 
@@ -37,11 +47,13 @@ struct EmitSlot {
 	uint64_t du_off; /* bytes into the data-unit arena */
 	uint32_t n_du, dpm; /* units; units per MCU: 6 (4:2:0) or 3 (4:4:4) */
 	uint32_t first_tile, n_tiles;
-	uint32_t hdr, pad; /* header of the slot: hdrs + hdr * MIJ_EMIT_HDR */
+	uint32_t hdr, tab; /* header of the slot: hdrs + hdr * MIJ_EMIT_HDR; tab > 0: optimised, its tables are entry tab, its counts tab - 1 */
+	uint32_t hlen, pad; /* the header's length: MIJ_EMIT_HDR, or what k_emit_build wrote */
 };
 
 struct EmitTile {
 	uint32_t slot, first; /* the tile's first unit in its slot */
+	uint32_t tab, pad;    /* the tables the tile kernels use: entry 0 (plain), or what k_emit_build wrote */
 };
 
 struct EmitResult {
@@ -57,8 +69,7 @@ __device__ __forceinline__ int emit_mag(int v, uint32_t &bits)
 	return n;
 }
 
-/* What lane `lane` emits for unit u of a slot: zrl ZRL codes, then sym, then extra (EOB and / or fill).  Every lane of the wave
- * must call it for the same unit (ballot). */
+/* What lane `lane` emits for unit u of a slot: zrl ZRL codes, then sym, then extra (EOB and / or fill). */
 struct LaneBits {
 	uint32_t sym, extra, zrl_code;
 	int sym_len, extra_len, zrl_len, zrl;
@@ -81,25 +92,26 @@ __device__ __forceinline__ UnitIn emit_load(const EmitSlot &s, const int16_t *__
 	in.pred = lane == 0 && prev >= 0 ? (int)du[(size_t)prev * 64] : 0;
 	return in;
 }
-__device__ __forceinline__ void emit_lane(const EmitTables *__restrict__ T, const EmitSlot &s, UnitIn in, uint32_t u, int lane, LaneBits &L)
+/* Which lane owns which symbol of unit u, said once for the emission kernels and for the histogram: own.dc(category, bits) in lane
+ * 0, own.ac(ZRLs, run/size symbol, size, bits) in a lane k > 0 whose coefficient is non-zero (the ZRLs, 0xF0 per 16 zeros of its run,
+ * come before the symbol), own.eob() in lane 63 when coefficient 63 is zero; own.begin(luma) first.  Every lane of the wave must call
+ * it for the same unit (ballot). */
+template <typename Own>
+__device__ __forceinline__ void emit_owner(const EmitSlot &s, UnitIn in, uint32_t u, int lane, Own &own)
 {
 	const uint32_t m = u / s.dpm, p = u - m * s.dpm;
 	const bool luma = p < (s.dpm == 6u ? 4u : 1u);
 	const int v = in.v;
 	const uint64_t nz = __ballot(v != 0) & ~1ull;
-	const int dc = luma ? 0 : 1, ac = luma ? 2 : 3;
-	L.sym = L.extra = L.zrl_code = 0;
-	L.sym_len = L.extra_len = L.zrl_len = L.zrl = 0;
+	own.begin(luma);
 	if (lane == 0) {
 		const int diff = v - in.pred;
 		if (diff == 0) {
-			L.sym = T->code[dc][0];
-			L.sym_len = T->len[dc][0];
+			own.dc(0, 0u);
 		} else {
 			uint32_t bits;
 			const int n = emit_mag(diff, bits);
-			L.sym = ((uint32_t)T->code[dc][n] << n) | bits;
-			L.sym_len = T->len[dc][n] + n;
+			own.dc(n, bits);
 		}
 	} else if (v != 0) {
 		const uint64_t below = nz & ((1ull << lane) - 1ull);
@@ -107,28 +119,57 @@ __device__ __forceinline__ void emit_lane(const EmitTables *__restrict__ T, cons
 		const int run = lane - last - 1;
 		uint32_t bits;
 		const int n = emit_mag(v, bits), sym = ((run & 15) << 4) + n;
-		L.zrl = run >> 4;
-		L.zrl_code = T->code[ac][0xF0];
-		L.zrl_len = T->len[ac][0xF0];
-		L.sym = ((uint32_t)T->code[ac][sym & 255] << n) | bits;
-		L.sym_len = T->len[ac][sym & 255] + n;
+		own.ac(run >> 4, sym & 255, n, bits);
 	}
-	if (lane == 63) {
-		if (v == 0) {
-			L.extra = T->code[ac][0];
-			L.extra_len = T->len[ac][0];
-		}
-		if (u + 1 == s.n_du) { /* the slot's last unit: fill to a byte boundary with ones */
-			L.extra = (L.extra << 7) | 0x7Fu;
-			L.extra_len += 7;
-		}
+	if (lane == 63 && v == 0)
+		own.eob();
+}
+
+/* the owner that looks the symbols up in T */
+struct LaneCoder {
+	const EmitTables *__restrict__ T;
+	LaneBits &L;
+	int dcT, acT;
+	__device__ __forceinline__ void begin(bool luma)
+	{
+		dcT = luma ? 0 : 1;
+		acT = luma ? 2 : 3;
+		L.sym = L.extra = L.zrl_code = 0;
+		L.sym_len = L.extra_len = L.zrl_len = L.zrl = 0;
+	}
+	__device__ __forceinline__ void dc(int n, uint32_t bits)
+	{
+		L.sym = ((uint32_t)T->code[dcT][n] << n) | bits;
+		L.sym_len = T->len[dcT][n] + n;
+	}
+	__device__ __forceinline__ void ac(int zrl, int sym, int n, uint32_t bits)
+	{
+		L.zrl = zrl;
+		L.zrl_code = T->code[acT][0xF0];
+		L.zrl_len = T->len[acT][0xF0];
+		L.sym = ((uint32_t)T->code[acT][sym] << n) | bits;
+		L.sym_len = T->len[acT][sym] + n;
+	}
+	__device__ __forceinline__ void eob()
+	{
+		L.extra = T->code[acT][0];
+		L.extra_len = T->len[acT][0];
+	}
+};
+__device__ __forceinline__ void emit_lane(const EmitTables *__restrict__ T, const EmitSlot &s, UnitIn in, uint32_t u, int lane, LaneBits &L)
+{
+	LaneCoder c = {T, L, 0, 0};
+	emit_owner(s, in, u, lane, c);
+	if (lane == 63 && u + 1 == s.n_du) { /* the slot's last unit: fill to a byte boundary with ones */
+		L.extra = (L.extra << 7) | 0x7Fu;
+		L.extra_len += 7;
 	}
 }
 
-/* f(j, LaneBits) for the units j = wave, wave + 4, ... < n of a tile (first unit `first`), the next unit's loads in flight */
+/* f(j, u, UnitIn) for the units j = wave, wave + 4, ... < n of a tile (first unit `first`, u = first + j), the next unit's loads in
+ * flight */
 template <typename F>
-__device__ __forceinline__ void emit_units(const EmitTables *__restrict__ T, const EmitSlot &s, const int16_t *__restrict__ du, uint32_t first, uint32_t n,
-														 F f)
+__device__ __forceinline__ void emit_unit_loop(const EmitSlot &s, const int16_t *__restrict__ du, uint32_t first, uint32_t n, F f)
 {
 	const int lane = threadIdx.x & 63;
 	uint32_t j = threadIdx.x >> 6;
@@ -139,11 +180,21 @@ __device__ __forceinline__ void emit_units(const EmitTables *__restrict__ T, con
 		UnitIn next = in;
 		if (j + 4 < n)
 			next = emit_load(s, du, first + j + 4, lane);
-		LaneBits L;
-		emit_lane(T, s, in, first + j, lane, L);
-		f(j, L);
+		f(j, first + j, in);
 		in = next;
 	}
+}
+/* f(j, LaneBits) for those units, their symbols looked up in T */
+template <typename F>
+__device__ __forceinline__ void emit_units(const EmitTables *__restrict__ T, const EmitSlot &s, const int16_t *__restrict__ du, uint32_t first, uint32_t n,
+														 F f)
+{
+	const int lane = threadIdx.x & 63;
+	emit_unit_loop(s, du, first, n, [&](uint32_t j, uint32_t u, UnitIn in) {
+		LaneBits L;
+		emit_lane(T, s, in, u, lane, L);
+		f(j, L);
+	});
 }
 
 /* the code tables into LDS (every workgroup of the tile kernels; blockDim.x = 256) */
@@ -229,7 +280,7 @@ __global__ __launch_bounds__(256) void k_emit_len(const EmitSlot *__restrict__ s
 	const int16_t *du = reinterpret_cast<const int16_t *>(du_base + s.du_off);
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const uint32_t n = min((uint32_t)MIJ_EMIT_TILE, s.n_du - tl.first);
-	emit_tables_to_lds(T, &tab);
+	emit_tables_to_lds(T + tl.tab, &tab);
 	uint32_t acc = 0;
 	emit_units(&tab, s, du, tl.first, n, [&](uint32_t, const LaneBits &L) { acc += wave_sum((uint32_t)L.total()); });
 	if (lane == 0)
@@ -280,7 +331,7 @@ __global__ __launch_bounds__(256) void k_emit_count(const EmitSlot *__restrict__
 		}
 		return;
 	}
-	emit_tables_to_lds(T, &tab);
+	emit_tables_to_lds(T + tl.tab, &tab);
 	emit_pack_tile(&tab, s, tl, reinterpret_cast<const int16_t *>(du_base + s.du_off), h, nwords, buf, uoff);
 	uint32_t c = 0;
 	for (uint32_t j = (h ? 1u : 0u) + threadIdx.x; j < n_own; j += blockDim.x)
@@ -337,7 +388,8 @@ __global__ __launch_bounds__(256) void k_emit_stuff(const EmitSlot *__restrict__
 }
 
 /* one workgroup of 1024: every slot's length and offset in slot order; res[n_slots] = {bytes used, slots that fit} */
-__global__ __launch_bounds__(1024) void k_emit_place(uint32_t n_slots, const uint64_t *__restrict__ s_ent, uint64_t cap, EmitResult *__restrict__ res)
+__global__ __launch_bounds__(1024) void k_emit_place(const EmitSlot *__restrict__ slots, uint32_t n_slots, const uint64_t *__restrict__ s_ent, uint64_t cap,
+																		  EmitResult *__restrict__ res)
 {
 	__shared__ uint64_t wsum[16];
 	__shared__ unsigned long long used, nfit;
@@ -349,7 +401,7 @@ __global__ __launch_bounds__(1024) void k_emit_place(uint32_t n_slots, const uin
 		const uint32_t i = i0 + threadIdx.x;
 		const uint64_t ent = i < n_slots ? s_ent[i] : 0;
 		const bool bad = ent == ~0ull;
-		const uint64_t len = i < n_slots && !bad ? MIJ_EMIT_HDR + ent + 2 : 0;
+		const uint64_t len = i < n_slots && !bad ? slots[i].hlen + ent + 2 : 0;
 		uint64_t incl = len;
 		for (int o = 1; o < 64; o <<= 1) {
 			const uint64_t t = __shfl_up(incl, o, 64);
@@ -403,7 +455,7 @@ __global__ __launch_bounds__(256) void k_emit_write(const EmitSlot *__restrict__
 	const EmitSlot s = slots[tl.slot];
 	uint8_t *out = arena + r.off;
 	if (tl.first == 0)
-		for (uint32_t i = threadIdx.x; i < MIJ_EMIT_HDR; i += blockDim.x)
+		for (uint32_t i = threadIdx.x; i < s.hlen; i += blockDim.x)
 			out[i] = hdrs[(size_t)s.hdr * MIJ_EMIT_HDR + i];
 	if (tl.first + MIJ_EMIT_TILE >= s.n_du && threadIdx.x == 0) {
 		out[r.len - 2] = 0xFF;
@@ -412,7 +464,7 @@ __global__ __launch_bounds__(256) void k_emit_write(const EmitSlot *__restrict__
 	const uint64_t b0 = t_boff[blockIdx.x], b1 = b0 + t_bits[blockIdx.x];
 	const uint32_t h = (uint32_t)(b0 & 7u), n_own = (uint32_t)((b1 >> 3) - (b0 >> 3));
 	const uint32_t nwords = (uint32_t)((h + (b1 - b0) + 31) / 32);
-	emit_tables_to_lds(T, &tab);
+	emit_tables_to_lds(T + tl.tab, &tab);
 	emit_pack_tile(&tab, s, tl, reinterpret_cast<const int16_t *>(du_base + s.du_off), h, nwords, buf, uoff);
 	if (h && threadIdx.x == 0) /* the previous tile's tail completes the first byte */
 		buf[0] |= (t_frag[blockIdx.x - 1] >> 8) << (32 - h);
@@ -431,12 +483,221 @@ __global__ __launch_bounds__(256) void k_emit_write(const EmitSlot *__restrict__
 	uint32_t pos = incl - c;
 	for (int w = 0; w < wave; ++w)
 		pos += part[w];
-	uint8_t *o = out + MIJ_EMIT_HDR + t_out[blockIdx.x] + pos;
+	uint8_t *o = out + s.hlen + t_out[blockIdx.x] + pos;
 	for (uint32_t j = j0; j < j1; ++j) {
 		const uint32_t b = lds_byte(buf, j);
 		*o++ = (uint8_t)b;
 		if (b == 0xFFu)
 			*o++ = 0;
+	}
+}
+
+/* ---- optimised Huffman tables */
+
+/* the owner that counts the symbols: hist[4][256] in LDS */
+struct LaneCounter {
+	uint32_t *hist, *dcH, *acH;
+	__device__ __forceinline__ void begin(bool luma)
+	{
+		dcH = hist + (luma ? 0 : 1) * 256;
+		acH = hist + (luma ? 2 : 3) * 256;
+	}
+	__device__ __forceinline__ void dc(int n, uint32_t) { atomicAdd(&dcH[n & 255], 1u); }
+	__device__ __forceinline__ void ac(int zrl, int sym, int, uint32_t)
+	{
+		if (zrl)
+			atomicAdd(&acH[0xF0], (uint32_t)zrl);
+		atomicAdd(&acH[sym & 255], 1u);
+	}
+	__device__ __forceinline__ void eob() { atomicAdd(&acH[0], 1u); }
+};
+
+/* per tile of an optimised slot: its symbols counted, freq[(s.tab - 1)][4][256] += (luma DC, chroma DC, luma AC, chroma AC) */
+__global__ __launch_bounds__(256) void k_emit_hist(const EmitSlot *__restrict__ slots, const EmitTile *__restrict__ tiles, const uint8_t *__restrict__ du_base,
+																	uint32_t *__restrict__ freq)
+{
+	__shared__ uint32_t hist[4 * 256];
+	const EmitTile tl = tiles[blockIdx.x];
+	const EmitSlot s = slots[tl.slot];
+	const int16_t *du = reinterpret_cast<const int16_t *>(du_base + s.du_off);
+	const int lane = threadIdx.x & 63;
+	const uint32_t n = min((uint32_t)MIJ_EMIT_TILE, s.n_du - tl.first);
+	for (uint32_t i = threadIdx.x; i < 4 * 256; i += blockDim.x)
+		hist[i] = 0;
+	__syncthreads();
+	emit_unit_loop(s, du, tl.first, n, [&](uint32_t, uint32_t u, UnitIn in) {
+		LaneCounter c = {hist, nullptr, nullptr};
+		emit_owner(s, in, u, lane, c);
+	});
+	__syncthreads();
+	uint32_t *g = freq + (size_t)(s.tab - 1u) * (4 * 256);
+	for (uint32_t i = threadIdx.x; i < 4 * 256; i += blockDim.x)
+		if (hist[i])
+			atomicAdd(&g[i], hist[i]);
+}
+
+/* the SOS segment behind the DHT segment (mjw_header) */
+__device__ const uint8_t k_emit_sos[14] = {0xFF, 0xDA, 0, 0xC, 3, 1, 0, 2, 0x11, 3, 0x11, 0, 0x3F, 0};
+
+__device__ __forceinline__ uint64_t wave_min64(uint64_t v)
+{
+	for (int o = 32; o > 0; o >>= 1) {
+		const uint64_t t = __shfl_xor(v, o, 64);
+		v = t < v ? t : v;
+	}
+	return v;
+}
+
+/* One workgroup per optimised slot k (slot opt_slots[k], counts freq[k], tables tabs[k + 1]), wave t builds table t by ITU-T T.81 K.2 as
+ * libjpeg's jpeg_gen_optimal_table does (mjw_optimal_table, csrc/jpeg_write_host.c, is the same procedure on the host).  Lane l holds
+ * the entries l, l + 64, l + 128, l + 192 and, lane 0, the pseudo-symbol 256 in registers.  A merge is two wave-wide argmins over
+ * (count, largest index first) and one pass that gives every leaf of the two trees one more bit and the first tree's name -- the
+ * leaves libjpeg reaches through its `others` chains.  Counts are uint32: a table holds at most 64 symbols per unit and
+ * mij_enc_set_optimize refuses slots of more than 2^32 / 64 units, so no sum wraps.  Integer arithmetic only. */
+__global__ __launch_bounds__(256) void k_emit_build(EmitSlot *__restrict__ slots, EmitTile *__restrict__ tiles, const uint32_t *__restrict__ opt_slots,
+																	 const uint32_t *__restrict__ freq, EmitTables *__restrict__ tabs, uint8_t *__restrict__ hdrs,
+																	 uint32_t *__restrict__ opt_ok)
+{
+	__shared__ uint32_t bits[4][34], first_code[4][17], first_pos[4][17], nvals[4];
+	__shared__ uint32_t fail;
+	const int lane = threadIdx.x & 63, t = threadIdx.x >> 6;
+	const uint32_t k = blockIdx.x, slot = opt_slots[k];
+	if (threadIdx.x == 0)
+		fail = 0;
+	if (lane < 34)
+		bits[t][lane] = 0;
+	__syncthreads();
+	const uint32_t *f = freq + (size_t)k * (4 * 256) + t * 256;
+	uint32_t fr[5];
+	int cs[5], grp[5];
+#pragma unroll
+	for (int q = 0; q < 5; ++q) {
+		fr[q] = q < 4 ? f[lane + 64 * q] : (lane == 0 ? 1u : 0u);
+		cs[q] = 0;
+		grp[q] = lane + 64 * q;
+	}
+	for (;;) {
+		uint64_t k1 = ~0ull, k2 = ~0ull;
+#pragma unroll
+		for (int q = 0; q < 5; ++q)
+			if (fr[q]) {
+				const uint64_t key = (uint64_t)fr[q] << 32 | (uint32_t)(511 - (lane + 64 * q)); /* smallest count, then largest index */
+				k1 = key < k1 ? key : k1;
+			}
+		k1 = wave_min64(k1);
+		const int c1 = 511 - (int)(uint32_t)k1;
+#pragma unroll
+		for (int q = 0; q < 5; ++q)
+			if (fr[q] && lane + 64 * q != c1) {
+				const uint64_t key = (uint64_t)fr[q] << 32 | (uint32_t)(511 - (lane + 64 * q));
+				k2 = key < k2 ? key : k2;
+			}
+		k2 = wave_min64(k2);
+		if (k2 == ~0ull)
+			break;
+		const int c2 = 511 - (int)(uint32_t)k2;
+		const uint32_t sum = (uint32_t)(k1 >> 32) + (uint32_t)(k2 >> 32);
+#pragma unroll
+		for (int q = 0; q < 5; ++q) {
+			const int i = lane + 64 * q;
+			if (i == c1)
+				fr[q] = sum;
+			if (i == c2)
+				fr[q] = 0;
+			if (grp[q] == c1 || grp[q] == c2) {
+				++cs[q];
+				grp[q] = c1;
+			}
+		}
+	}
+	/* the lengths' counts (pseudo-symbol included); HUFFVAL position of each symbol: by unlimited length, then by value */
+	bool deep = false;
+#pragma unroll
+	for (int q = 0; q < 5; ++q) {
+		deep = deep || cs[q] > 32;
+		if (cs[q] >= 1 && cs[q] <= 32)
+			atomicAdd(&bits[t][cs[q]], 1u);
+	}
+	if (__ballot(deep) != 0 && lane == 0)
+		atomicOr(&fail, 1u);
+	int pos[4] = {-1, -1, -1, -1};
+	uint32_t nv = 0;
+	for (int l = 1; l <= 32; ++l)
+#pragma unroll
+		for (int q = 0; q < 4; ++q) {
+			const uint64_t m = __ballot(cs[q] == l);
+			if (cs[q] == l)
+				pos[q] = (int)(nv + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)));
+			nv += (uint32_t)__popcll(m);
+		}
+	__syncthreads();
+	if (lane == 0 && !fail) { /* K.3: lengths above 16 shortened pairwise; the pseudo-symbol's code removed; Annex C's first codes */
+		uint32_t *b = bits[t];
+		for (int i = 32; i > 16; --i)
+			while (b[i] > 0) {
+				int j = i - 2;
+				while (j > 0 && b[j] == 0)
+					--j;
+				b[i] -= 2;
+				++b[i - 1];
+				b[j + 1] += 2;
+				--b[j];
+			}
+		int i = 16;
+		while (i > 0 && b[i] == 0)
+			--i;
+		if (i > 0)
+			--b[i];
+		uint32_t code = 0, p = 0;
+		for (int l = 1; l <= 16; ++l) {
+			first_code[t][l] = code;
+			first_pos[t][l] = p;
+			code = (code + b[l]) << 1;
+			p += b[l];
+		}
+		nvals[t] = p;
+	}
+	__syncthreads();
+	const uint32_t hlen = 177u + 4u * 17u + nvals[0] + nvals[1] + nvals[2] + nvals[3] + 14u;
+	const bool ok = !fail && hlen <= MIJ_EMIT_HDR && nvals[t] == nv;
+	const bool all_ok = __syncthreads_and(ok) != 0;
+	const uint32_t tile0 = slots[slot].first_tile, ntile = slots[slot].n_tiles;
+	for (uint32_t i = threadIdx.x; i < ntile; i += blockDim.x)
+		tiles[tile0 + i].tab = all_ok ? k + 1 : 0u;
+	if (all_ok) {
+		/* the DHT segment holds the tables in mjw_header's order: luma DC, luma AC, chroma DC, chroma AC */
+		const uint32_t before = t == 0 ? 0u : (t == 2 ? 17u + nvals[0] : (t == 1 ? 34u + nvals[0] + nvals[2] : 51u + nvals[0] + nvals[2] + nvals[1]));
+		uint8_t *h = hdrs + (size_t)slots[slot].hdr * MIJ_EMIT_HDR, *seg = h + 177 + before;
+		EmitTables *T = tabs + k + 1;
+		if (lane == 0)
+			seg[0] = (uint8_t)(t == 0 ? 0x00 : (t == 2 ? 0x10 : (t == 1 ? 0x01 : 0x11)));
+		if (lane < 16)
+			seg[1 + lane] = (uint8_t)bits[t][lane + 1];
+#pragma unroll
+		for (int q = 0; q < 4; ++q) {
+			uint32_t code = 0, len = 0;
+			if (pos[q] >= 0) {
+				for (int l = 1; l <= 16; ++l)
+					if ((uint32_t)pos[q] >= first_pos[t][l] && (uint32_t)pos[q] < first_pos[t][l] + bits[t][l]) {
+						len = (uint32_t)l;
+						code = first_code[t][l] + (uint32_t)pos[q] - first_pos[t][l];
+					}
+				seg[17 + pos[q]] = (uint8_t)(lane + 64 * q);
+			}
+			T->code[t][lane + 64 * q] = (uint16_t)code;
+			T->len[t][lane + 64 * q] = (uint8_t)len;
+		}
+		if (t == 3 && lane < 14)
+			h[hlen - 14 + lane] = k_emit_sos[lane];
+		if (threadIdx.x == 0) {
+			h[175] = (uint8_t)((hlen - 14 - 175) >> 8);
+			h[176] = (uint8_t)((hlen - 14 - 175) & 0xFFu);
+			slots[slot].hlen = hlen;
+			opt_ok[k] = 1;
+		}
+	} else if (threadIdx.x == 0) { /* the plain tables and the plain header, which the upload left in place */
+		slots[slot].hlen = MIJ_EMIT_HDR;
+		opt_ok[k] = 0;
 	}
 }
 

@@ -3186,6 +3186,7 @@ struct EncSlot {
 	int pad_w; /* pixels per staged row: the width rounded up to whole MCU columns (enc_padded_width); staged rows are packed RGB */
 	int clone_of, flip;
 	int kind;                   /* ENC_*; a clone copies its root's pixels whatever the root's kind */
+	bool optimize;              /* mij_enc_set_optimize */
 	mij_in_tensor in;           /* ENC_DEVICE */
 	std::vector<int16_t> units; /* ENC_UNITS */
 };
@@ -3229,6 +3230,18 @@ struct mij_encoder {
 	uint64_t *d_tboff, *d_tout, *d_sent;
 	size_t tmeta_cap, sent_cap;
 	bool emit_queued, streams_fetched;
+	/* optimised Huffman tables (mij_enc_set_optimize): d_tabs holds tabs_cap entries, entry 0 the plain tables (h_tabs0) and entry k + 1 those of
+	 * the k-th optimised slot; its tiles, its slot number, its counts and whether it kept its own tables */
+	EmitTables h_tabs0;
+	size_t tabs_cap;
+	EmitTile *h_otile, *d_otile;
+	size_t otile_cap, n_otile;
+	uint32_t *h_optslot, *d_optslot;
+	size_t optslot_cap, n_opt;
+	uint32_t *d_freq, *d_optok;
+	size_t freq_cap, optok_cap;
+	std::vector<int> opt_of;      /* slot -> k, or -1 */
+	std::vector<uint32_t> opt_ok; /* after mij_enc_fetch_streams */
 };
 
 template <typename T>
@@ -3249,7 +3262,16 @@ static void enc_free_emit(mij_encoder *e)
 	free_dev(e->d_arena);
 	free_host(e->h_arena);
 	free_dev(e->d_tabs);
-	e->arena_cap = 0;
+	e->arena_cap = e->tabs_cap = 0;
+	free_host(e->h_otile);
+	free_dev(e->d_otile);
+	e->otile_cap = e->n_otile = 0;
+	free_host(e->h_optslot);
+	free_dev(e->d_optslot);
+	e->optslot_cap = e->n_opt = 0;
+	free_dev(e->d_freq);
+	free_dev(e->d_optok);
+	e->freq_cap = e->optok_cap = 0;
 	free_host(e->h_eslot);
 	free_dev(e->d_eslot);
 	e->eslot_cap = 0;
@@ -3311,6 +3333,9 @@ extern "C" int mij_enc_create_ex(mij_ctx *ctx, int max_images, size_t stage_byte
 	e->h_res = e->d_res = nullptr;
 	e->d_tbits = e->d_tff = e->d_tfrag = nullptr;
 	e->d_tboff = e->d_tout = e->d_sent = nullptr;
+	e->h_otile = e->d_otile = nullptr;
+	e->h_optslot = e->d_optslot = nullptr;
+	e->d_freq = e->d_optok = nullptr;
 	enc_free_emit(e);
 	e->force_generic = getenv("MIJ_ENC_GENERIC") != nullptr;
 	e->stream = nullptr;
@@ -3441,6 +3466,7 @@ static int enc_add_common(mij_encoder *e, const mjw_plan &plan, const void *pixe
 	s.flip = flip;
 	s.clone_of = clone_of;
 	s.kind = kind;
+	s.optimize = false;
 	memset(&s.in, 0, sizeof(s.in));
 	s.pad_w = enc_padded_width(plan.width, plan.subsample);
 	s.pix_bytes = kind == ENC_UNITS ? 0 : align_up((size_t)s.pad_w * plan.height * 3, 256); /* staged as packed RGB whatever plan.comp is (enc_stage_rows) */
@@ -3563,7 +3589,32 @@ extern "C" int mij_enc_add_clone(mij_encoder *e, int src_slot)
 	if (e->slots[(size_t)root].kind == ENC_UNITS)
 		return set_err(MIJ_E_ARG, "slot %d holds given data units, which have no pixels to clone", src_slot);
 	const mjw_plan plan = e->slots[(size_t)root].plan;
-	return enc_add_common(e, plan, nullptr, e->slots[(size_t)root].flip, root);
+	const int slot = enc_add_common(e, plan, nullptr, e->slots[(size_t)root].flip, root);
+	if (slot >= 0)
+		e->slots[(size_t)slot].optimize = e->slots[(size_t)src_slot].optimize;
+	return slot;
+}
+
+extern "C" int mij_enc_set_optimize(mij_encoder *e, int slot, int on)
+{
+	if (!e || slot < 0 || slot >= (int)e->slots.size())
+		return set_err(MIJ_E_ARG, "bad slot");
+	if (e->uploaded)
+		return set_err(MIJ_E_STATE, "mij_enc_set_optimize after mij_enc_upload");
+	if (on && mjw_plan_du_count(&e->slots[(size_t)slot].plan) > (size_t)(UINT32_MAX / 64))
+		return set_err(MIJ_E_ARG, "slot %d: the symbol counts of %zu data units do not fit 32 bits", slot, mjw_plan_du_count(&e->slots[(size_t)slot].plan));
+	e->slots[(size_t)slot].optimize = on != 0;
+	return MIJ_OK;
+}
+
+extern "C" int mij_enc_slot_optimized(const mij_encoder *e, int slot)
+{
+	if (!e || slot < 0 || slot >= (int)e->slots.size())
+		return set_err(MIJ_E_ARG, "bad slot");
+	if (!e->streams_fetched)
+		return set_err(MIJ_E_STATE, "mij_enc_slot_optimized before mij_enc_fetch_streams");
+	const int k = e->opt_of[(size_t)slot];
+	return k >= 0 && e->opt_ok[(size_t)k] ? 1 : 0;
 }
 
 /* The gather kernel of the device-pixel slots (their padded packed-RGB rows from the caller's tensor), queued at upload in place of
@@ -3615,20 +3666,43 @@ static int enc_gather(mij_encoder *e)
 	return MIJ_OK;
 }
 
-/* Emission lists at upload: one EmitSlot per slot, its tiles of MIJ_EMIT_TILE units, its headers (a clone shares its root's). */
+/* A slot has a header of its own unless it is a plain clone of a plain root, which shares the root's: k_emit_build writes an optimised
+ * slot's DHT segment into its header. */
+static bool enc_own_header(const mij_encoder *e, const EncSlot &s) { return s.clone_of < 0 || s.optimize || e->slots[(size_t)s.clone_of].optimize; }
+
+/* Emission lists at upload: one EmitSlot per slot, its tiles of MIJ_EMIT_TILE units, its headers (enc_own_header).  Optimised slots also get their tiles in a list of their
+ * own, a table entry and counts. */
 static int enc_emit_lists(mij_encoder *e)
 {
 	const size_t n = e->slots.size();
-	size_t nt = 0, nh = 0;
+	size_t nt = 0, nh = 0, no = 0, not_ = 0;
 	for (const EncSlot &s : e->slots) {
-		nt += (mjw_plan_du_count(&s.plan) + MIJ_EMIT_TILE - 1) / MIJ_EMIT_TILE;
-		nh += s.clone_of < 0;
+		const size_t tiles = (mjw_plan_du_count(&s.plan) + MIJ_EMIT_TILE - 1) / MIJ_EMIT_TILE;
+		nt += tiles;
+		nh += enc_own_header(e, s);
+		no += s.optimize;
+		not_ += s.optimize ? tiles : 0;
 	}
 	if (nt > UINT32_MAX)
 		return set_err(MIJ_E_ARG, "too many data units to emit in one launch");
-	if (n > e->eslot_cap || nt > e->etile_cap || nh * MIJ_EMIT_HDR > e->hdr_cap || n + 1 > e->res_cap || nt > e->tmeta_cap || n > e->sent_cap)
+	if (n > e->eslot_cap || nt > e->etile_cap || nh * MIJ_EMIT_HDR > e->hdr_cap || n + 1 > e->res_cap || nt > e->tmeta_cap || n > e->sent_cap ||
+		 not_ > e->otile_cap || no > e->optslot_cap || no * 1024 > e->freq_cap || no > e->optok_cap || no + 1 > e->tabs_cap)
 		HIP_TRY(hipStreamSynchronize(e->stream)); /* the buffers may still be in use by an earlier launch */
 	int rc = grow_pair(e->h_eslot, e->d_eslot, e->eslot_cap, n);
+	if (rc == MIJ_OK && no) {
+		rc = grow_pair(e->h_otile, e->d_otile, e->otile_cap, not_);
+		if (rc == MIJ_OK)
+			rc = grow_pair(e->h_optslot, e->d_optslot, e->optslot_cap, no);
+		if (rc == MIJ_OK)
+			rc = grow_dev(e->d_freq, e->freq_cap, no * 1024);
+		if (rc == MIJ_OK)
+			rc = grow_dev(e->d_optok, e->optok_cap, no);
+		if (rc == MIJ_OK && no + 1 > e->tabs_cap) {
+			rc = grow_dev(e->d_tabs, e->tabs_cap, no + 1);
+			if (rc == MIJ_OK)
+				HIP_TRY(hipMemcpy(e->d_tabs, &e->h_tabs0, sizeof(EmitTables), hipMemcpyHostToDevice));
+		}
+	}
 	if (rc == MIJ_OK)
 		rc = grow_pair(e->h_etile, e->d_etile, e->etile_cap, nt);
 	if (rc == MIJ_OK)
@@ -3658,10 +3732,11 @@ static int enc_emit_lists(mij_encoder *e)
 	if (rc != MIJ_OK)
 		return rc;
 	std::vector<uint32_t> hdr_of(n);
-	uint32_t t = 0, h = 0;
+	uint32_t t = 0, h = 0, k = 0, ot = 0;
+	e->opt_of.assign(n, -1);
 	for (size_t i = 0; i < n; ++i) {
 		const EncSlot &s = e->slots[i];
-		if (s.clone_of < 0) {
+		if (enc_own_header(e, s)) {
 			mjw_header(&s.plan, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
 			hdr_of[i] = h++;
 		} else {
@@ -3674,30 +3749,50 @@ static int enc_emit_lists(mij_encoder *e)
 		es.first_tile = t;
 		es.n_tiles = (es.n_du + MIJ_EMIT_TILE - 1) / MIJ_EMIT_TILE;
 		es.hdr = hdr_of[i];
-		es.pad = 0;
+		es.tab = es.pad = 0;
+		es.hlen = MIJ_EMIT_HDR;
+		if (s.optimize) {
+			e->opt_of[i] = (int)k;
+			e->h_optslot[k] = (uint32_t)i;
+			es.tab = ++k;
+		}
 		for (uint32_t u = 0; u < es.n_du; u += MIJ_EMIT_TILE) {
-			const EmitTile tl = {(uint32_t)i, u};
+			const EmitTile tl = {(uint32_t)i, u, 0u, 0u};
 			e->h_etile[t++] = tl;
+			if (s.optimize)
+				e->h_otile[ot++] = tl;
 		}
 	}
 	e->n_etile = nt;
+	e->n_opt = no;
+	e->n_otile = not_;
+	if (no) {
+		HIP_TRY(hipMemcpyAsync(e->d_otile, e->h_otile, sizeof(EmitTile) * not_, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_optslot, e->h_optslot, sizeof(uint32_t) * no, hipMemcpyHostToDevice, e->stream));
+	}
 	HIP_TRY(hipMemcpyAsync(e->d_eslot, e->h_eslot, sizeof(EmitSlot) * n, hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipMemcpyAsync(e->d_etile, e->h_etile, sizeof(EmitTile) * nt, hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipMemcpyAsync(e->d_hdr, e->h_hdr, (size_t)nh * MIJ_EMIT_HDR, hipMemcpyHostToDevice, e->stream));
 	return MIJ_OK;
 }
 
-/* The six emission launches behind the transform (mij_emit_kernels.h). */
+/* The six emission launches behind the transform (mij_emit_kernels.h); with optimised slots, their counts and tables first. */
 static int enc_emit_launch(mij_encoder *e)
 {
 	const uint32_t n = (uint32_t)e->slots.size();
 	const dim3 tiles((unsigned)e->n_etile), per_slot((n + 3) / 4), block(256);
 	const uint8_t *du = reinterpret_cast<const uint8_t *>(e->d_du);
+	if (e->n_opt) {
+		HIP_TRY(hipMemsetAsync(e->d_freq, 0, sizeof(uint32_t) * 1024 * e->n_opt, e->stream));
+		hipLaunchKernelGGL(k_emit_hist, dim3((unsigned)e->n_otile), block, 0, e->stream, e->d_eslot, e->d_otile, du, e->d_freq);
+		hipLaunchKernelGGL(k_emit_build, dim3((unsigned)e->n_opt), block, 0, e->stream, e->d_eslot, e->d_etile, e->d_optslot, e->d_freq, e->d_tabs, e->d_hdr,
+								 e->d_optok);
+	}
 	hipLaunchKernelGGL(k_emit_len, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_tbits);
 	hipLaunchKernelGGL(k_emit_scan, per_slot, block, 0, e->stream, e->d_eslot, n, e->d_tbits, e->d_tboff);
 	hipLaunchKernelGGL(k_emit_count, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_tbits, e->d_tboff, e->d_tff, e->d_tfrag);
 	hipLaunchKernelGGL(k_emit_stuff, per_slot, block, 0, e->stream, e->d_eslot, n, e->d_tbits, e->d_tboff, e->d_tff, e->d_tfrag, e->d_tout, e->d_sent);
-	hipLaunchKernelGGL(k_emit_place, dim3(1), dim3(1024), 0, e->stream, n, e->d_sent, (uint64_t)e->arena_cap, e->d_res);
+	hipLaunchKernelGGL(k_emit_place, dim3(1), dim3(1024), 0, e->stream, e->d_eslot, n, e->d_sent, (uint64_t)e->arena_cap, e->d_res);
 	hipLaunchKernelGGL(k_emit_write, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_hdr, e->d_tbits, e->d_tboff, e->d_tfrag,
 							 e->d_tout, e->d_res, e->d_arena);
 	HIP_TRY(hipGetLastError());
@@ -3718,7 +3813,7 @@ extern "C" int mij_enc_stream_reserve(mij_encoder *e, size_t bytes)
 	uint16_t code[4][256];
 	uint8_t len[4][256];
 	mjw_huff_tables(code, len);
-	EmitTables tabs;
+	EmitTables &tabs = e->h_tabs0;
 	memcpy(tabs.code, code, sizeof(code));
 	memcpy(tabs.len, len, sizeof(len));
 	hipError_t r = hipMalloc(reinterpret_cast<void **>(&e->d_arena), bytes);
@@ -3733,6 +3828,7 @@ extern "C" int mij_enc_stream_reserve(mij_encoder *e, size_t bytes)
 		return set_err(r == hipErrorOutOfMemory ? MIJ_E_NOMEM : MIJ_E_HIP, "mij_enc_stream_reserve(%zu): %s", bytes, hipGetErrorString(r));
 	}
 	e->arena_cap = bytes;
+	e->tabs_cap = 1;
 	return MIJ_OK;
 }
 
@@ -3755,6 +3851,9 @@ extern "C" int mij_enc_fetch_streams(mij_encoder *e)
 		HIP_TRY(hipMemcpyAsync(e->h_arena, e->d_arena, used, hipMemcpyDeviceToHost, e->stream));
 		HIP_TRY(hipStreamSynchronize(e->stream));
 	}
+	e->opt_ok.assign(e->n_opt, 0u);
+	if (e->n_opt)
+		HIP_TRY(hipMemcpy(e->opt_ok.data(), e->d_optok, sizeof(uint32_t) * e->n_opt, hipMemcpyDeviceToHost));
 	e->streams_fetched = true;
 	return (int)e->h_res[n].len;
 }

@@ -136,11 +136,15 @@ class TensorEncoder:
             self._enc.reset()
         return self._enc
 
-    def encode(self, images, *, quality=90, layout="CHW", flip_vertically=False):
+    def encode(self, images, *, quality=90, layout="CHW", flip_vertically=False, optimize=False):
         """quality: 1..100, or 0 for the default 90, as stbi_write_jpg takes it.  images: a 4-D uint8 tensor on the GPU ([N, C, H, W] for layout "CHW", [N, H, W, C] for "HWC") or a sequence of 3-D
         (2-D: grey) uint8 tensors, whose sizes may differ; C is 1..4 (stbi_write_jpg's comp).  Strided views are accepted (unit
         stride along W for CHW; strides C and 1 along W and C for HWC).  -> one bytes object per picture: what
-        stbi_write_jpg_to_func(W, H, C, picture, quality) writes (under stbi_flip_vertically_on_write(1) with flip_vertically)."""
+        stbi_write_jpg_to_func(W, H, C, picture, quality) writes (under stbi_flip_vertically_on_write(1) with flip_vertically).
+        optimize (a bool): every stream gets Huffman tables built on the GPU from its own symbol statistics -- the same coefficients in
+        fewer bytes, what mjw_emit_optimized writes for the picture's data units, whatever the arena's size."""
+        if not isinstance(optimize, bool):
+            raise ValueError("optimize must be a bool, got %r" % (optimize,))
         if isinstance(quality, bool) or not isinstance(quality, int) or not 0 <= quality <= 100:
             raise ValueError("quality must be an int in 0..100 (0: stbi_write_jpg's default, 90), got %r" % (quality,))
         views = self._views(images, layout)
@@ -161,19 +165,21 @@ class TensorEncoder:
             while j < len(views) and j - i < MAX_SLOTS and (j == i or pix + sizes[j][0] <= MAX_PIXEL_BYTES):
                 pix += sizes[j][0]
                 j += 1
-            streams, h = self._encode_chunk(views[i:j], sizes[i:j], quality, lay, flip)
+            streams, h = self._encode_chunk(views[i:j], sizes[i:j], quality, lay, flip, optimize)
             out.extend(streams)
             host += h
             i = j
         self.last_host_emitted = host
         return out
 
-    def _encode_chunk(self, views, sizes, quality, lay, flip):
+    def _encode_chunk(self, views, sizes, quality, lay, flip, optimize):
         if not self._arena:  # a first guess, about 0.75 bytes per pixel; misses grow it
             self._arena = _align(sum(1024 + (px * 3) // 4 for (_, _, px) in sizes), 1 << 20)
         enc = self._encoder_for(len(views), sum(s[0] for s in sizes), sum(s[1] for s in sizes))
         for (t, w, h, c, rp, pp) in views:
-            enc.add_device(InTensor(t.data_ptr(), lay, w, h, c, rp, pp), quality, flip)
+            slot = enc.add_device(InTensor(t.data_ptr(), lay, w, h, c, rp, pp), quality, flip)
+            if optimize:
+                enc.set_optimize(slot)
         enc.upload()
         enc.launch()
         enc.fetch_streams()
@@ -182,7 +188,7 @@ class TensorEncoder:
             data, n = enc.stream(slot)
             need += n
             if data is None:  # did not fit: its units are still on the device, the host Huffman stage finishes it
-                data = emit_jpeg(enc.plan(slot), enc.fetch(slot))
+                data = emit_jpeg(enc.plan(slot), enc.fetch(slot), optimize)
                 host += 1
             streams.append(data)
         if host:

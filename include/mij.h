@@ -627,6 +627,24 @@ int mij_enc_add_device(mij_encoder *e, const mij_in_tensor *t, int quality, int 
  * -2047..2047 or an AC value leaves -1023..1023: those fall outside the writer's tables.  mij_enc_add_clone refuses such a slot. */
 int mij_enc_add_units(mij_encoder *e, int width, int height, int comp, int quality, const int16_t *du);
 
+/*
+ * Optimised Huffman tables: a slot's stream with tables built from its own symbol statistics in place of the four Annex-K tables --
+ * the bytes mjw_emit_optimized (mij_host.h) writes for the slot's units.  Only the DHT segment and the codes of the entropy-coded
+ * segment differ from the plain stream; coefficients, MCU order, stuffing, fill bits and every other segment are the same.  With an
+ * emission arena the counts (k_emit_hist) and the tables (k_emit_build, ITU-T T.81 K.2) are made on the GPU in front of the emission
+ * kernels, for the optimised slots only; a launch without such a slot queues what it queued before.  Without an arena nothing new is
+ * queued: finish such a slot with mjw_emit_optimized on its fetched units.
+ *
+ * mij_enc_set_optimize: for a slot of any kind (host pixels, device pixels, given units, clone), after it is added and before
+ * mij_enc_upload; MIJ_E_STATE after the upload, MIJ_E_ARG for a bad slot or one whose unit count times 64 does not fit 32 bits (the
+ * counts are uint32).  A clone inherits the request of the slot it is made from; mij_enc_reset forgets all requests.
+ * mij_enc_slot_optimized: after mij_enc_fetch_streams (MIJ_E_STATE before): 1 when the slot's stream carries its own tables, 0 when
+ * optimisation was not asked for it or the slot fell back to the plain tables (a code of more than 32 bits before K.2's shortening;
+ * its stream is then mjw_emit's).  A slot that does not fit the arena still reports its exact length under its tables.
+ */
+int mij_enc_set_optimize(mij_encoder *e, int slot, int on);
+int mij_enc_slot_optimized(const mij_encoder *e, int slot);
+
 #ifdef __cplusplus
 }
 #endif

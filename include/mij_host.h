@@ -152,6 +152,35 @@ int mij_write_jpg_batch(const void *const *pixels, const int *x, const int *y, c
 /* mjw_emit into memory: bytes written, 0 when `cap` is too small or an argument is bad (cap >= 1024 + 2 bytes per coefficient always fits) */
 size_t mjw_emit_to_memory(const mjw_plan *p, const int16_t *du, unsigned char *out, size_t cap);
 
+/*
+ * Optimised Huffman tables: the same stream as mjw_emit but for the DHT segment and the codes, which come from the picture's own
+ * symbol statistics (what libjpeg calls `optimize`).  Tables are indexed luma DC, chroma DC, luma AC, chroma AC throughout.
+ *   mjw_histogram        the symbols mjw_emit emits for these units, counted per table: one DC category per unit, one 0xF0 per 16 zeros
+ *                        of a run, one run/size symbol per non-zero AC, one 0x00 per unit whose coefficient 63 is zero.  0 when the
+ *                        unit count times 64 does not fit 32 bits.
+ *   mjw_optimal_table    ITU-T T.81 K.2 as libjpeg's jpeg_gen_optimal_table runs it: a pseudo-symbol 256 of count 1, the two smallest
+ *                        non-zero counts merged until one is left (among equal counts the largest index is taken), lengths above 16
+ *                        shortened pairwise (K.3), the pseudo-symbol's code removed, HUFFVAL by unlimited length then value.  bits[l-1]
+ *                        is the number of codes of length l.  Returns 0, with nothing usable written, when a length before the
+ *                        shortening exceeds 32.
+ *   mjw_header_optimized mjw_header with these four tables in its one DHT segment (same order and identifiers); returns the length,
+ *                        at most MJW_HEADER_BYTES.
+ *   mjw_emit_optimized   histogram + four tables + emission; when a table cannot be built (the over-32 case, or a histogram that is
+ *                        refused) the stream is mjw_emit's.  mjw_optimized_tables is its table step alone: 0 in those cases.
+ */
+int mjw_histogram(const mjw_plan *p, const int16_t *du, uint32_t freq[4][256]);
+int mjw_optimal_table(const uint32_t freq[256], uint8_t bits[16], uint8_t vals[256], int *nvals);
+size_t mjw_header_optimized(const mjw_plan *p, const uint8_t bits[4][16], const uint8_t vals[4][256], unsigned char *out);
+int mjw_optimized_tables(const mjw_plan *p, const int16_t *du, uint8_t bits[4][16], uint8_t vals[4][256]);
+int mjw_emit_optimized(const mjw_plan *p, const int16_t *du, mjw_write_func *func, void *context);
+size_t mjw_emit_optimized_to_memory(const mjw_plan *p, const int16_t *du, unsigned char *out, size_t cap);
+/* mij_write_jpg_to_func / mij_write_jpg_batch with flags: MJW_OPTIMIZE_HUFFMAN finishes every stream with mjw_emit_optimized; flags 0 is
+ * the plain call. */
+#define MJW_OPTIMIZE_HUFFMAN 1u
+int mij_write_jpg_to_func_ex(mjw_write_func *func, void *context, int x, int y, int comp, const void *data, int quality, unsigned flags);
+int mij_write_jpg_batch_ex(const void *const *pixels, const int *x, const int *y, const int *comp, int n, int quality, int threads,
+                           unsigned char **out, size_t *out_len, unsigned flags);
+
 /* The tables of stbi__ldr_to_hdr (common.c:391-424) for mij_batch_set_out_f32: lut[256*k + v] for channel k < n_out.  Colour
  * channels (all of them for odd n_out, all but the last for even n_out) get (float)(pow(v / 255.0f, gamma) * scale), the
  * alpha channel of n_out 2 and 4 gets v / 255.0f -- the reference's expressions, evaluated with libm's pow. */

@@ -7,7 +7,13 @@
        (mij_enc_fetch_all), bytes and wall ms.
   E2E  TensorEncoder.encode of a [N2, 3, 1080, 1920] uint8 CUDA tensor against mij_write_jpg_batch of the same pictures from host
        memory (16 host threads), alternated ROUNDS times; Gpix/s of wall clock.
-  --kernel  only the q=90 encoder with emission, LAUNCHES launches (run it under `rocprofv3 --kernel-trace --stats`, a run of its own).
+  --kernel  only the q=90 encoder with emission, LAUNCHES launches (run it under `rocprofv3 --kernel-trace --stats`, a run of its own);
+            with --optimize every slot asks for optimised Huffman tables.
+  --opt     optimised Huffman tables: T/E's slots in three encoders -- no arena, arena with plain slots, arena
+            with every slot optimised -- launched alternately STEPS times; emission ms of plain and of optimised slots, stream bytes
+            of both.  One JSON line on stdout, no file.  A library without mij_enc_set_optimize gives the plain figures alone.
+  --opt-ab PARENT_LIB  --opt in fresh child processes, alternating PARENT_LIB (the parent commit's library, through MIJ_LIB) and
+            this tree's library AB_ROUNDS times; writes profiles/tensor_encode_opt.json.
 Streams are checked against the reference's stored lengths and SHA-256 (tests/golden/writer_golden_r3.npz) first."""
 import argparse
 import ctypes as C
@@ -28,7 +34,7 @@ W, H = 1920, 1080
 WG = os.path.join(ROOT, "tests", "golden", "writer_golden_r3.npz")
 
 
-def encoder(ctx, imgs, count, q, arena):
+def encoder(ctx, imgs, count, q, arena, optimize=False):
     pix = ica.binding.lib().mij_enc_pixel_bytes
     pix.restype = C.c_size_t
     pix.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
@@ -41,6 +47,9 @@ def encoder(ctx, imgs, count, q, arena):
     src = [enc.add(a, q) for a in imgs]
     while len(src) < count:
         src.append(enc.add_clone(src[len(src) % len(imgs)]))
+    if optimize:
+        for s in src:
+            enc.set_optimize(s)
     enc.upload()
     return enc, dub * count
 
@@ -94,6 +103,69 @@ def leg(ctx, imgs, count, q, steps, wg):
                     "units_ms": d2h_units_ms}}
 
 
+def opt_leg(ctx, imgs, count, q, steps, wg):
+    """emission ms of plain slots and of optimised slots over the same pictures; their stream bytes"""
+    lens = wg["bench/q%d/len" % q]
+    arena = int(max(int(v) for v in lens) * 1.1) * count
+    has_opt = hasattr(ica.lib(), "mij_enc_set_optimize")
+    encs = [encoder(ctx, imgs, count, q, 0)[0], encoder(ctx, imgs, count, q, arena)[0]]
+    if has_opt:
+        encs.append(encoder(ctx, imgs, count, q, arena, optimize=True)[0])
+    for e in encs:
+        launch_ms(e)  # warm
+    t = [[] for _ in encs]
+    for _ in range(steps):
+        for k, e in enumerate(encs):
+            t[k].append(launch_ms(e))
+    out = {"quality": q, "pictures": count, "steps": steps}
+    med = [float(np.median(x)) for x in t]
+    out["transform_ms"] = round(med[0], 3)
+    out["plain_emission_ms"] = {"median": round(med[1] - med[0], 3), "per_step": [round(b - a, 3) for a, b in zip(t[0], t[1])]}
+    assert encs[1].fetch_streams() == count
+    out["plain_bytes"] = sum(encs[1].stream(s)[1] for s in range(count))
+    if has_opt:
+        out["optimised_emission_ms"] = {"median": round(med[2] - med[0], 3), "per_step": [round(b - a, 3) for a, b in zip(t[0], t[2])]}
+        assert encs[2].fetch_streams() == count
+        out["optimised_bytes"] = sum(encs[2].stream(s)[1] for s in range(count))
+        out["optimised_slots"] = sum(encs[2].slot_optimized(s) for s in range(count))
+        out["bytes_ratio"] = round(out["optimised_bytes"] / out["plain_bytes"], 4)
+        for s in range(min(4, len(imgs))):  # the streams themselves: the host's optimised emission of the same units
+            assert encs[2].stream(s)[0] == ica.emit_jpeg(encs[2].plan(s), encs[2].fetch(s), True), (q, s)
+    for e in encs:
+        e.close()
+    return out
+
+
+def opt_ab(parent_lib, a):
+    """--opt in child processes, parent library and this one in turn"""
+    import subprocess
+    runs = {"parent": [], "change": []}
+    for r in range(a.ab_rounds):
+        for name in ("parent", "change"):
+            env = dict(os.environ)
+            env.pop("MIJ_LIB", None)
+            if name == "parent":
+                env["MIJ_LIB"] = os.path.abspath(parent_lib)
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--opt", "--count", str(a.count), "--steps", str(a.steps)], env=env,
+                               stdout=subprocess.PIPE, check=True, timeout=900)
+            runs[name].append(json.loads(p.stdout.decode().strip().splitlines()[-1]))
+            print(name, r, json.dumps(runs[name][-1]["legs"]), flush=True)
+    res = {"tool": "bench_tensor_encode --opt-ab", "device": runs["change"][0]["device"], "pictures": a.count, "steps": a.steps, "rounds": a.ab_rounds,
+           "legs": []}
+    for k, q in enumerate((90, 95)):
+        par = [x["legs"][k]["plain_emission_ms"]["median"] for x in runs["parent"]]
+        chg = [x["legs"][k]["plain_emission_ms"]["median"] for x in runs["change"]]
+        opt = [x["legs"][k]["optimised_emission_ms"]["median"] for x in runs["change"]]
+        last = runs["change"][-1]["legs"][k]
+        res["legs"].append({"quality": q, "plain_emission_ms_parent": par, "plain_emission_ms_change": chg, "optimised_emission_ms": opt,
+                            "plain_bytes": last["plain_bytes"], "optimised_bytes": last["optimised_bytes"], "bytes_ratio": last["bytes_ratio"],
+                            "optimised_slots": last["optimised_slots"]})
+    line = json.dumps(res)
+    print(line)
+    with open(os.path.join(ROOT, "profiles", "tensor_encode_opt.json"), "w") as f:
+        f.write(line + "\n")
+
+
 def e2e(imgs, n, rounds, q):
     batch = torch.from_numpy(np.stack([imgs[i % len(imgs)] for i in range(n)])).cuda().permute(0, 3, 1, 2).contiguous()
     host = [imgs[i % len(imgs)] for i in range(n)]
@@ -127,7 +199,13 @@ def main():
     ap.add_argument("--kernel", action="store_true")
     ap.add_argument("--launches", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tensor_encode.json"))
+    ap.add_argument("--optimize", action="store_true")
+    ap.add_argument("--opt", action="store_true")
+    ap.add_argument("--opt-ab", metavar="PARENT_LIB")
+    ap.add_argument("--ab-rounds", type=int, default=2)
     a = ap.parse_args()
+    if a.opt_ab:  # before any GPU use in this process: the children own the device
+        return opt_ab(a.opt_ab, a)
     if not torch.cuda.is_available() or not ica.gpu_available():
         raise SystemExit("bench_tensor_encode: no GPU")
     wg = np.load(WG, allow_pickle=False)
@@ -135,7 +213,7 @@ def main():
     ctx = ica.Context()
     if a.kernel:
         lens = wg["bench/q90/len"]
-        enc, _ = encoder(ctx, imgs, a.count, 90, int(max(int(v) for v in lens) * 1.1) * a.count)
+        enc, _ = encoder(ctx, imgs, a.count, 90, int(max(int(v) for v in lens) * 1.1) * a.count, a.optimize)
         for _ in range(a.launches):
             enc.launch()
             enc.wait()
@@ -144,6 +222,10 @@ def main():
         ctx.close()
         return
     arch, cus, mem = ctx.info()
+    if a.opt:
+        print(json.dumps({"tool": "bench_tensor_encode --opt", "device": arch, "legs": [opt_leg(ctx, imgs, a.count, q, a.steps, wg) for q in (90, 95)]}))
+        ctx.close()
+        return
     res = {"tool": "bench_tensor_encode", "device": arch, "cus": cus, "legs": [leg(ctx, imgs, a.count, 90, a.steps, wg),
                                                                                leg(ctx, imgs, a.count, 95, a.steps, wg)]}
     ctx.close()
