@@ -38,6 +38,7 @@ from .binding import (  # noqa: F401
     Context,
     Encoder,
     InTensor,
+    InConvert,
     PinnedBuffer,
     host_transform,
     emit_jpeg,

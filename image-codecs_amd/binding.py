@@ -1319,6 +1319,20 @@ class InTensor(C.Structure):
                 ("row_pitch", C.c_int64), ("plane_pitch", C.c_int64)]
 
 
+class InConvert(C.Structure):
+    """mij_in_convert (include/mij.h): the element type of a float device-pixel slot and its per-channel float32 scale and bias."""
+    _fields_ = [("dtype", C.c_int32), ("scale", C.c_float * 4), ("bias", C.c_float * 4)]
+
+    def __init__(self, dtype=MIJ_DT_F32, scale=(), bias=()):
+        """dtype: MIJ_DT_* or "f16" / "bf16" / "f32"; scale, bias: up to 4 values, the rest stay 0"""
+        super().__init__()
+        self.dtype = _DTYPES.get(dtype, dtype)
+        for k, v in enumerate(scale):
+            self.scale[k] = v
+        for k, v in enumerate(bias):
+            self.bias[k] = v
+
+
 class Encoder:
     """mij_encoder: batch colour + subsample + fDCT + quantiser on the GPU; with an emission arena (stream_reserve) also the Huffman
     stage, so that finished streams come back."""
@@ -1388,6 +1402,13 @@ class Encoder:
         L = lib()
         L.mij_enc_add_device.argtypes = [C.c_void_p, C.POINTER(InTensor), C.c_int, C.c_int]
         return _check(L.mij_enc_add_device(self._h, C.byref(t), int(quality), int(bool(flip))), "mij_enc_add_device")
+
+    def add_device_float(self, t, convert, quality=90, flip=False):
+        """mij_enc_add_device_float: a slot whose float16 / bfloat16 / float32 elements lie in device memory, described by an InTensor
+        (pitches in elements), de-normalised on the GPU by the contract of include/mij.h with the InConvert's scale and bias."""
+        L = lib()
+        L.mij_enc_add_device_float.argtypes = [C.c_void_p, C.POINTER(InTensor), C.POINTER(InConvert), C.c_int, C.c_int]
+        return _check(L.mij_enc_add_device_float(self._h, C.byref(t), C.byref(convert), int(quality), int(bool(flip))), "mij_enc_add_device_float")
 
     def add_units(self, width, height, comp, quality, du):
         """mij_enc_add_units: a slot whose quantised data units (int16 [n_du, 64], zigzag order) are given."""

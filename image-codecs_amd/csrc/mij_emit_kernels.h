@@ -735,3 +735,144 @@ __global__ __launch_bounds__(256) void k_enc_gather(const EncGather *__restrict_
 		d[2] = px[2] >> 16 | px[3] << 8;
 	}
 }
+
+/* ---- device pixels held as float16 / bfloat16 / float32 (mij_enc_add_device_float): the same padded packed-RGB rows, every element
+ * de-normalised by the contract of include/mij.h on the way.  The same work list and the same output as k_enc_gather: one workgroup
+ * per MIJ_GATHER_ROWS rows, a thread makes 4 pixels = 3 aligned words.  A thread's 4 pixels are 4 consecutive elements of each plane
+ * (planar: CHW, and grey in either layout) or 4*comp consecutive elements (interleaved): each run of 4 elements is one 8-byte
+ * (16-bit types) or 16-byte (float32) load where its address is so aligned and the group lies inside the picture, and 4 element
+ * loads otherwise -- the right-edge group, whose x clamps to width-1, and rows that base pointer, row pitch or plane pitch leave
+ * misaligned.  x0 is a multiple of 4, so a row (of one plane) is aligned or not as a whole and a wavefront diverges at the edge
+ * group only.  Both paths fetch the same elements. */
+struct EncGatherF {
+	EncGather g; /* src and the pitches count elements of the slot's dtype */
+	float scale[4], bias[4];
+};
+
+struct GatherF16 {
+	typedef uint16_t raw;
+	static __device__ __forceinline__ float widen(uint16_t v) { return (float)__builtin_bit_cast(_Float16, v); }
+};
+struct GatherBF16 {
+	typedef uint16_t raw;
+	static __device__ __forceinline__ float widen(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
+};
+struct GatherF32 {
+	typedef uint32_t raw;
+	static __device__ __forceinline__ float widen(uint32_t v) { return __uint_as_float(v); }
+};
+
+/* 4 elements with one load.  Native vector types: as a struct of four words the load falls apart into element loads, which the
+ * compiler then merges with the element path's */
+typedef uint32_t gather_u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t gather_u32x4 __attribute__((ext_vector_type(4)));
+static __device__ __forceinline__ void gather_load4(const uint16_t *p, uint16_t *r)
+{
+	const gather_u32x2 v = *reinterpret_cast<const gather_u32x2 *>(p);
+	r[0] = (uint16_t)v.x, r[1] = (uint16_t)(v.x >> 16), r[2] = (uint16_t)v.y, r[3] = (uint16_t)(v.y >> 16);
+}
+static __device__ __forceinline__ void gather_load4(const uint32_t *p, uint32_t *r)
+{
+	const gather_u32x4 v = *reinterpret_cast<const gather_u32x4 *>(p);
+	r[0] = v.x, r[1] = v.y, r[2] = v.z, r[3] = v.w;
+}
+
+/* the contract's u for the widened element x: two roundings, never a fused multiply-add */
+static __device__ __forceinline__ uint32_t gather_denorm(float x, float scale, float bias)
+{
+#pragma clang fp contract(off)
+	float t = __fadd_rn(__fmul_rn(x, scale), bias);
+	t = t > 0.0f ? t : 0.0f;     /* fmaxf(t, 0.0f), spelled out: NaN fails the comparison and becomes 0 */
+	t = t < 255.0f ? t : 255.0f; /* fminf(t, 255.0f) */
+	return (uint32_t)rintf(t);   /* round half to even */
+}
+
+/* SX: elements from one pixel to the next (1: planar, channel c lies c * plane_pitch further; else interleaved, channel c is element c
+ * of the pixel); NCH: channels read (1: grey, the picture's first channel in r, g and b; 3) */
+template <typename D, int SX, int NCH>
+static __device__ __forceinline__ void gather_float_rows(const EncGatherF &G, uint32_t y0, uint32_t rows, uint8_t *__restrict__ pix)
+{
+	typedef typename D::raw R;
+	const EncGather &g = G.g;
+	const R *src = reinterpret_cast<const R *>(g.src);
+	const uint32_t groups = (uint32_t)g.pad_w / 4;
+	const uintptr_t vmask = 4 * sizeof(R) - 1;
+	for (uint32_t idx = threadIdx.x; idx < rows * groups; idx += blockDim.x) {
+		const uint32_t y = y0 + idx / groups, x0 = (idx % groups) * 4;
+		const R *row = src + (int64_t)y * g.row_pitch;
+		const bool inside = x0 + 4 <= (uint32_t)g.width;
+		R e[4][NCH];
+		if (SX == 1) {
+#pragma unroll
+			for (int c = 0; c < NCH; ++c) {
+				const R *plane = row + (int64_t)c * g.plane_pitch;
+				if (inside && ((uintptr_t)(plane + x0) & vmask) == 0) {
+					R r[4];
+					gather_load4(plane + x0, r);
+#pragma unroll
+					for (int j = 0; j < 4; ++j)
+						e[j][c] = r[j];
+				} else {
+#pragma unroll
+					for (int j = 0; j < 4; ++j)
+						e[j][c] = plane[min((int)x0 + j, g.width - 1)];
+				}
+			}
+		} else {
+			const R *p = row + (int64_t)x0 * SX;
+			if (inside && ((uintptr_t)p & vmask) == 0) {
+				R r[4 * SX];
+#pragma unroll
+				for (int k = 0; k < SX; ++k)
+					gather_load4(p + 4 * k, r + 4 * k);
+#pragma unroll
+				for (int j = 0; j < 4; ++j)
+#pragma unroll
+					for (int c = 0; c < NCH; ++c)
+						e[j][c] = r[j * SX + c];
+			} else {
+#pragma unroll
+				for (int j = 0; j < 4; ++j) {
+					const R *q = row + (int64_t)min((int)x0 + j, g.width - 1) * SX;
+#pragma unroll
+					for (int c = 0; c < NCH; ++c)
+						e[j][c] = q[c];
+				}
+			}
+		}
+		uint32_t px[4];
+#pragma unroll
+		for (int j = 0; j < 4; ++j) {
+			const uint32_t r = gather_denorm(D::widen(e[j][0]), G.scale[0], G.bias[0]);
+			if constexpr (NCH == 3)
+				px[j] = r | gather_denorm(D::widen(e[j][1]), G.scale[1], G.bias[1]) << 8 | gather_denorm(D::widen(e[j][2]), G.scale[2], G.bias[2]) << 16;
+			else
+				px[j] = r * 0x010101u;
+		}
+		uint32_t *d = reinterpret_cast<uint32_t *>(pix + g.pix_off + (size_t)y * (size_t)g.pad_w * 3 + (size_t)x0 * 3);
+		d[0] = px[0] | px[1] << 24;
+		d[1] = px[1] >> 8 | px[2] << 16;
+		d[2] = px[2] >> 16 | px[3] << 8;
+	}
+}
+
+template <typename D>
+__global__ __launch_bounds__(256) void k_enc_gather_float(const EncGatherF *__restrict__ gs, const WorkIdct *__restrict__ work, uint8_t *__restrict__ pix)
+{
+	const WorkIdct wk = work[blockIdx.x];
+	const EncGatherF G = gs[wk.img];
+	const uint32_t y0 = wk.first, rows = min((uint32_t)MIJ_GATHER_ROWS, (uint32_t)G.g.height - y0);
+	const int comp = G.g.comp;
+	if (G.g.layout == 1 || comp == 1) { /* planar; the alpha plane of comp 2 and 4 is never read */
+		if (comp > 2)
+			gather_float_rows<D, 1, 3>(G, y0, rows, pix);
+		else
+			gather_float_rows<D, 1, 1>(G, y0, rows, pix);
+	} else if (comp == 2) {
+		gather_float_rows<D, 2, 1>(G, y0, rows, pix);
+	} else if (comp == 3) {
+		gather_float_rows<D, 3, 3>(G, y0, rows, pix);
+	} else {
+		gather_float_rows<D, 4, 3>(G, y0, rows, pix);
+	}
+}

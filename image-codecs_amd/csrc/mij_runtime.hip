@@ -5,6 +5,7 @@
  */
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -3188,6 +3189,7 @@ struct EncSlot {
 	int kind;                   /* ENC_*; a clone copies its root's pixels whatever the root's kind */
 	bool optimize;              /* mij_enc_set_optimize */
 	mij_in_tensor in;           /* ENC_DEVICE */
+	mij_in_convert cv;          /* ENC_DEVICE with float elements (mij_enc_add_device_float); cv.dtype is MIJ_DT_U8 for every other slot */
 	std::vector<int16_t> units; /* ENC_UNITS */
 };
 
@@ -3214,6 +3216,11 @@ struct mij_encoder {
 	size_t gath_cap;
 	WorkIdct *h_gwork, *d_gwork;
 	size_t gwork_cap, n_gwork;
+	/* the same for the float device-pixel slots, grouped by dtype: one launch of k_enc_gather_float each */
+	EncGatherF *h_fgath, *d_fgath;
+	size_t fgath_cap;
+	WorkIdct *h_fgwork, *d_fgwork;
+	size_t fgwork_cap;
 	/* GPU emission (mij_enc_stream_reserve): the stream arena and its pinned mirror, the code tables, per-slot and per-tile lists */
 	uint8_t *d_arena, *h_arena;
 	size_t arena_cap;
@@ -3325,6 +3332,9 @@ extern "C" int mij_enc_create_ex(mij_ctx *ctx, int max_images, size_t stage_byte
 	e->h_gath = e->d_gath = nullptr;
 	e->h_gwork = e->d_gwork = nullptr;
 	e->gath_cap = e->gwork_cap = e->n_gwork = 0;
+	e->h_fgath = e->d_fgath = nullptr;
+	e->h_fgwork = e->d_fgwork = nullptr;
+	e->fgath_cap = e->fgwork_cap = 0;
 	e->d_arena = e->h_arena = nullptr;
 	e->d_tabs = nullptr;
 	e->h_eslot = e->d_eslot = nullptr;
@@ -3392,6 +3402,10 @@ extern "C" void mij_enc_destroy(mij_encoder *e)
 	free_dev(e->d_gath);
 	free_host(e->h_gwork);
 	free_dev(e->d_gwork);
+	free_host(e->h_fgath);
+	free_dev(e->d_fgath);
+	free_host(e->h_fgwork);
+	free_dev(e->d_fgwork);
 	enc_free_emit(e);
 	if (e->ev_begin)
 		(void)hipEventDestroy(e->ev_begin);
@@ -3468,6 +3482,8 @@ static int enc_add_common(mij_encoder *e, const mjw_plan &plan, const void *pixe
 	s.kind = kind;
 	s.optimize = false;
 	memset(&s.in, 0, sizeof(s.in));
+	memset(&s.cv, 0, sizeof(s.cv));
+	s.cv.dtype = MIJ_DT_U8;
 	s.pad_w = enc_padded_width(plan.width, plan.subsample);
 	s.pix_bytes = kind == ENC_UNITS ? 0 : align_up((size_t)s.pad_w * plan.height * 3, 256); /* staged as packed RGB whatever plan.comp is (enc_stage_rows) */
 	s.du_bytes = align_up(mjw_plan_du_count(&plan) * 128, 256);
@@ -3623,7 +3639,7 @@ static int enc_gather(mij_encoder *e)
 {
 	size_t ng = 0, nw = 0;
 	for (const EncSlot &s : e->slots)
-		if (s.clone_of < 0 && s.kind == ENC_DEVICE) {
+		if (s.clone_of < 0 && s.kind == ENC_DEVICE && s.cv.dtype == MIJ_DT_U8) {
 			++ng;
 			nw += ((size_t)s.plan.height + MIJ_GATHER_ROWS - 1) / MIJ_GATHER_ROWS;
 		}
@@ -3640,7 +3656,7 @@ static int enc_gather(mij_encoder *e)
 	uint32_t g = 0;
 	size_t w = 0;
 	for (const EncSlot &s : e->slots) {
-		if (s.clone_of >= 0 || s.kind != ENC_DEVICE)
+		if (s.clone_of >= 0 || s.kind != ENC_DEVICE || s.cv.dtype != MIJ_DT_U8)
 			continue;
 		EncGather &G = e->h_gath[g];
 		G.src = static_cast<const uint8_t *>(s.in.src);
@@ -3663,6 +3679,73 @@ static int enc_gather(mij_encoder *e)
 	HIP_TRY(hipMemcpyAsync(e->d_gwork, e->h_gwork, sizeof(WorkIdct) * nw, hipMemcpyHostToDevice, e->stream));
 	hipLaunchKernelGGL(k_enc_gather, dim3((unsigned)nw), dim3(256), 0, e->stream, e->d_gath, e->d_gwork, e->d_pix);
 	HIP_TRY(hipGetLastError());
+	return MIJ_OK;
+}
+
+/* The float device-pixel slots (mij_enc_add_device_float): their gather lists, grouped by dtype, and one launch of k_enc_gather_float
+ * per dtype that has slots.  Nothing is queued when there are none. */
+static int enc_gather_float(mij_encoder *e)
+{
+	size_t ng = 0, nw = 0;
+	for (const EncSlot &s : e->slots)
+		if (s.clone_of < 0 && s.kind == ENC_DEVICE && s.cv.dtype != MIJ_DT_U8) {
+			++ng;
+			nw += ((size_t)s.plan.height + MIJ_GATHER_ROWS - 1) / MIJ_GATHER_ROWS;
+		}
+	if (!ng)
+		return MIJ_OK;
+	if (ng > e->fgath_cap || nw > e->fgwork_cap)
+		HIP_TRY(hipStreamSynchronize(e->stream)); /* an earlier upload's copies may still read the pinned lists */
+	int rc = grow_pair(e->h_fgath, e->d_fgath, e->fgath_cap, ng);
+	if (rc == MIJ_OK)
+		rc = grow_pair(e->h_fgwork, e->d_fgwork, e->fgwork_cap, nw);
+	if (rc != MIJ_OK)
+		return rc;
+	static const int32_t dts[3] = {MIJ_DT_F16, MIJ_DT_BF16, MIJ_DT_F32};
+	size_t first[4] = {0, 0, 0, 0};
+	uint32_t g = 0;
+	size_t w = 0;
+	for (int k = 0; k < 3; ++k) {
+		for (const EncSlot &s : e->slots) {
+			if (s.clone_of >= 0 || s.kind != ENC_DEVICE || s.cv.dtype != dts[k])
+				continue;
+			EncGatherF &G = e->h_fgath[g];
+			G.g.src = static_cast<const uint8_t *>(s.in.src);
+			G.g.row_pitch = s.in.row_pitch;
+			G.g.plane_pitch = s.in.plane_pitch;
+			G.g.layout = s.in.layout;
+			G.g.width = s.plan.width;
+			G.g.height = s.plan.height;
+			G.g.comp = s.plan.comp;
+			G.g.pad_w = s.pad_w;
+			G.g.pad = 0;
+			G.g.pix_off = s.dev.pix_off;
+			memcpy(G.scale, s.cv.scale, sizeof(G.scale));
+			memcpy(G.bias, s.cv.bias, sizeof(G.bias));
+			for (uint32_t y = 0; y < (uint32_t)s.plan.height; y += MIJ_GATHER_ROWS) {
+				const WorkIdct wk = {g, 0u, y, 0u};
+				e->h_fgwork[w++] = wk;
+			}
+			++g;
+		}
+		first[k + 1] = w;
+	}
+	HIP_TRY(hipMemcpyAsync(e->d_fgath, e->h_fgath, sizeof(EncGatherF) * ng, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->d_fgwork, e->h_fgwork, sizeof(WorkIdct) * nw, hipMemcpyHostToDevice, e->stream));
+	for (int k = 0; k < 3; ++k) {
+		const size_t n = first[k + 1] - first[k];
+		if (!n)
+			continue;
+		const dim3 grid((unsigned)n), block(256);
+		const WorkIdct *wk = e->d_fgwork + first[k];
+		if (dts[k] == MIJ_DT_F16)
+			hipLaunchKernelGGL(k_enc_gather_float<GatherF16>, grid, block, 0, e->stream, e->d_fgath, wk, e->d_pix);
+		else if (dts[k] == MIJ_DT_BF16)
+			hipLaunchKernelGGL(k_enc_gather_float<GatherBF16>, grid, block, 0, e->stream, e->d_fgath, wk, e->d_pix);
+		else
+			hipLaunchKernelGGL(k_enc_gather_float<GatherF32>, grid, block, 0, e->stream, e->d_fgath, wk, e->d_pix);
+		HIP_TRY(hipGetLastError());
+	}
 	return MIJ_OK;
 }
 
@@ -3880,10 +3963,12 @@ extern "C" const unsigned char *mij_enc_stream(const mij_encoder *e, int slot, s
 	return e->h_arena + r.off;
 }
 
-extern "C" int mij_enc_add_device(mij_encoder *e, const mij_in_tensor *t, int quality, int flip_vertically)
+/* mij_enc_add_device (cv NULL: uint8 elements) and mij_enc_add_device_float: the checks they share, extents in bytes of the element */
+static int enc_add_device(mij_encoder *e, const mij_in_tensor *t, const mij_in_convert *cv, int quality, int flip_vertically)
 {
 	if (!e || !t)
 		return set_err(MIJ_E_ARG, "bad argument");
+	const uint64_t es = !cv ? 1u : cv->dtype == MIJ_DT_F32 ? 4u : 2u;
 	if (t->layout != MIJ_LAYOUT_HWC && t->layout != MIJ_LAYOUT_CHW)
 		return set_err(MIJ_E_ARG, "mij_enc_add_device: layout %d unknown", t->layout);
 	mjw_plan plan;
@@ -3900,14 +3985,37 @@ extern "C" int mij_enc_add_device(mij_encoder *e, const mij_in_tensor *t, int qu
 							(long long)h, (long long)C, chw ? "CHW" : "HWC");
 	if (!t->src)
 		return set_err(MIJ_E_ARG, "src is NULL");
+	if ((uintptr_t)t->src % es)
+		return set_err(MIJ_E_ARG, "src %p is not aligned to its %llu-byte elements", t->src, (unsigned long long)es);
 	const uint64_t last = (uint64_t)((h - 1) * rp + (chw ? (C - 1) * pp + w - 1 : w * C - 1));
-	const int rc = device_extent(e->ctx->device, t->src, last + 1, "src");
+	const int rc = device_extent(e->ctx->device, t->src, (last + 1) * es, "src");
 	if (rc != MIJ_OK)
 		return rc;
 	const int slot = enc_add_common(e, plan, nullptr, flip_vertically ? 1 : 0, -1, ENC_DEVICE);
-	if (slot >= 0)
+	if (slot >= 0) {
 		e->slots[(size_t)slot].in = *t;
+		if (cv)
+			e->slots[(size_t)slot].cv = *cv;
+	}
 	return slot;
+}
+
+extern "C" int mij_enc_add_device(mij_encoder *e, const mij_in_tensor *t, int quality, int flip_vertically)
+{
+	return enc_add_device(e, t, nullptr, quality, flip_vertically);
+}
+
+extern "C" int mij_enc_add_device_float(mij_encoder *e, const mij_in_tensor *t, const mij_in_convert *cv, int quality, int flip_vertically)
+{
+	if (!e || !t || !cv)
+		return set_err(MIJ_E_ARG, "bad argument");
+	if (cv->dtype != MIJ_DT_F16 && cv->dtype != MIJ_DT_BF16 && cv->dtype != MIJ_DT_F32)
+		return set_err(MIJ_E_ARG, "mij_enc_add_device_float: dtype %d is not a float type%s", cv->dtype,
+							cv->dtype == MIJ_DT_U8 ? " (uint8 pictures go through mij_enc_add_device)" : "");
+	for (int c = 0; c < t->comp && c < 4; ++c)
+		if (!std::isfinite(cv->scale[c]) || !std::isfinite(cv->bias[c]))
+			return set_err(MIJ_E_ARG, "mij_enc_add_device_float: scale / bias of channel %d is not finite", c);
+	return enc_add_device(e, t, cv, quality, flip_vertically);
 }
 
 extern "C" int mij_enc_add_units(mij_encoder *e, int width, int height, int comp, int quality, const int16_t *du)
@@ -4010,6 +4118,8 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 										  hipMemcpyHostToDevice, e->stream));
 	}
 	rc = enc_gather(e); /* device-pixel slots, before the clones copy them */
+	if (rc == MIJ_OK)
+		rc = enc_gather_float(e);
 	if (rc != MIJ_OK)
 		return rc;
 	for (size_t i = 0; i < n; ++i) {

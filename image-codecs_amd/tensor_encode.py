@@ -1,13 +1,16 @@
 """JPEG streams straight from device tensors: the encoder's slots read caller-owned device memory (mij_enc_add_device, a gather
 kernel in place of the host copy), and the Huffman stage runs on the GPU too (mij_enc_stream_reserve), so only finished streams
-cross PCIe.  The counterpart of TensorDecoder.
+cross PCIe.  The counterpart of TensorDecoder: encode() takes uint8 pictures, encode_normalized() the float16 / bfloat16 / float32
+tensors a model works on, de-normalised inside the gather kernel (mij_enc_add_device_float).
 
 Importing this module imports torch; ``import image_codecs_amd`` alone does not (TensorEncoder is loaded from here on first use)."""
 import ctypes as C
+import math
 
 import torch
 
-from .binding import Context, Encoder, InTensor, WritePlan, emit_jpeg, lib, MIJ_LAYOUT_HWC, MIJ_LAYOUT_CHW
+from .binding import (Context, Encoder, InConvert, InTensor, WritePlan, emit_jpeg, lib, MIJ_LAYOUT_HWC, MIJ_LAYOUT_CHW, MIJ_DT_F16, MIJ_DT_BF16,
+                      MIJ_DT_F32)
 from .tensor_out import _one_hip_runtime
 
 # one launch takes at most this many pictures / bytes of pixel arena; larger calls are cut into chunks
@@ -28,11 +31,43 @@ def _align(v, a):
     return (v + a - 1) // a * a
 
 
+_FLOAT_DT = {torch.float16: MIJ_DT_F16, torch.bfloat16: MIJ_DT_BF16, torch.float32: MIJ_DT_F32}
+
+
+def _numbers(vals, what):
+    if vals is None:
+        return None
+    try:
+        return [float(x) for x in vals]
+    except TypeError:
+        raise ValueError("%s must be None or a sequence of numbers, one per channel" % what) from None
+
+
+def denorm_scale_bias(n, mean=None, std=None):
+    """-> (scale, bias), n float32 values each (as Python floats): scale[c] = float32(255.0 * std[c]), bias[c] = float32(255.0 *
+    mean[c]), the products taken in Python doubles; mean / std omitted mean 0 / 1, tensor_tables' convention.  ValueError for a wrong
+    number of values, a std of 0 and anything that is not finite as a float32."""
+    out = []
+    for vals, what, default in ((_numbers(std, "std"), "std", 1.0), (_numbers(mean, "mean"), "mean", 0.0)):
+        if vals is None:
+            vals = [default] * n
+        if len(vals) != n:
+            raise ValueError("%s has %d values for %d channels" % (what, len(vals), n))
+        f = [C.c_float(255.0 * v).value for v in vals]
+        if not all(math.isfinite(v) for v in f):
+            raise ValueError("%s %r: a value is not finite as a float32 once multiplied by 255" % (what, vals))
+        if what == "std" and 0.0 in f:
+            raise ValueError("std %r holds a 0 (as a float32 once multiplied by 255)" % (vals,))
+        out.append(f)
+    return out[0], out[1]
+
+
 class TensorEncoder:
     """Encodes uint8 pictures that live on a GPU into JPEG byte streams, each exactly what stbi_write_jpg_to_func writes for that
-    picture.  Owns a Context, an Encoder and its emission arena, grown as needed and reused across calls.  encode() is synchronous:
-    it synchronises the device's current torch stream before the encoder reads the tensors and waits for the streams before it
-    returns.  Slots whose streams do not fit the arena are finished on the host from their data units (last_host_emitted counts
+    picture (encode), and float16 / bfloat16 / float32 pictures as the uint8 pictures they de-normalise to (encode_normalized).
+    Owns a Context, an Encoder and its emission arena, grown as needed and reused across calls.  Both calls are synchronous: they
+    synchronise the device's current torch stream before the encoder reads the tensors and wait for the streams before they
+    return.  Slots whose streams do not fit the arena are finished on the host from their data units (last_host_emitted counts
     them) and the arena grows for the next call."""
 
     def __init__(self, device=None):
@@ -73,8 +108,9 @@ class TensorEncoder:
             self._enc.stream_reserve(self._arena)
 
     @staticmethod
-    def _views(images, layout):
-        """-> [(tensor, width, height, comp, row_pitch, plane_pitch)], every check that needs no device"""
+    def _views(images, layout, floats=False):
+        """-> [(tensor, width, height, comp, row_pitch, plane_pitch)], the checks of dtype, shape and strides.  floats: the pictures are
+        float16, bfloat16 or float32, all of one dtype (encode_normalized); else uint8."""
         if layout not in ("CHW", "HWC"):
             raise ValueError("layout must be 'CHW' or 'HWC'")
         if isinstance(images, torch.Tensor):
@@ -87,8 +123,13 @@ class TensorEncoder:
         for i, t in enumerate(images):
             if not isinstance(t, torch.Tensor):
                 raise ValueError("picture %d is not a tensor" % i)
-            if t.dtype != torch.uint8:
-                raise ValueError("picture %d is %s; only uint8 pictures are encoded" % (i, t.dtype))
+            if floats:
+                if t.dtype not in _FLOAT_DT:
+                    raise ValueError("picture %d is %s; encode_normalized takes float16, bfloat16 or float32 pictures (uint8: encode)" % (i, t.dtype))
+                if t.dtype != images[0].dtype:
+                    raise ValueError("picture %d is %s, picture 0 is %s; one call takes one dtype" % (i, t.dtype, images[0].dtype))
+            elif t.dtype != torch.uint8:
+                raise ValueError("picture %d is %s; only uint8 pictures are encoded (float pictures: encode_normalized)" % (i, t.dtype))
             if t.dim() == 2:
                 h, w = t.shape
                 c, rp, pp = 1, t.stride(0), 0
@@ -111,13 +152,17 @@ class TensorEncoder:
             if not 1 <= c <= 4:
                 raise ValueError("picture %d has %d channels; 1..4 are encoded" % (i, c))
             out.append((t, w, h, c, rp, pp))
-        for i, (t, w, h, _, _, _) in enumerate(out):
+        return out
+
+    @staticmethod
+    def _placed(views):
+        """the checks of where the pictures are and how large, after those of what they are"""
+        for i, (t, w, h, _, _, _) in enumerate(views):
             if t.device.type != "cuda":
                 raise ValueError("picture %d is on %s, not on a GPU" % (i, t.device))
-        for (_, w, h, _, _, _) in out:
+        for (_, w, h, _, _, _) in views:
             if not (1 <= w <= 65535 and 1 <= h <= 65535):
                 raise ValueError("picture size %dx%d outside 1..65535" % (w, h))
-        return out
 
     def _encoder_for(self, n, pix, du):
         need = (max(1, n), max(pix, 256), max(du, 256))
@@ -143,11 +188,39 @@ class TensorEncoder:
         stbi_write_jpg_to_func(W, H, C, picture, quality) writes (under stbi_flip_vertically_on_write(1) with flip_vertically).
         optimize (a bool): every stream gets Huffman tables built on the GPU from its own symbol statistics -- the same coefficients in
         fewer bytes, what mjw_emit_optimized writes for the picture's data units, whatever the arena's size."""
+        return self._encode(images, None, None, quality, layout, flip_vertically, optimize, False)
+
+    def encode_normalized(self, images, *, mean=None, std=None, quality=90, layout="CHW", flip_vertically=False, optimize=False):
+        """encode() for the tensors a model works on: images as for encode() -- the same shapes, stride rules and layouts -- but float16,
+        bfloat16 or float32, one dtype per call.  The pictures are de-normalised on the GPU, inside the kernel that gathers them
+        (mij_enc_add_device_float), by the contract of include/mij.h: for element x of channel c
+            t = float32(x) * scale[c];  t = t + bias[c]   (float32, two roundings, no fused multiply-add)
+            u = uint8(rint(min(max(t, 0), 255)))          (round half to even; NaN -> 0, -Inf -> 0, +Inf -> 255)
+        with scale[c] = float32(255.0 * std[c]) and bias[c] = float32(255.0 * mean[c]).  -> one bytes object per picture: what encode()
+        gives for the uint8 pictures of those u.
+        mean / std: None, or one value per channel of the pictures (C values; the alpha of C = 2 or 4 takes a value that is never used).
+        Both None: the pictures hold v / 255, tensor_tables' convention; with the mean / std a TensorDecoder.decode was given, its
+        tensors come back as the bytes they were made from, for all three dtypes.  A tensor holding 0..255 values is std=[1/255]*C.
+        ValueError, before any device is touched, for uint8 or any other non-float dtype, mixed dtypes, a wrong number of mean / std
+        values, a std of 0, a value that is not finite, and everything encode() refuses."""
+        return self._encode(images, mean, std, quality, layout, flip_vertically, optimize, True)
+
+    def _encode(self, images, mean, std, quality, layout, flip_vertically, optimize, floats):
         if not isinstance(optimize, bool):
             raise ValueError("optimize must be a bool, got %r" % (optimize,))
         if isinstance(quality, bool) or not isinstance(quality, int) or not 0 <= quality <= 100:
             raise ValueError("quality must be an int in 0..100 (0: stbi_write_jpg's default, 90), got %r" % (quality,))
-        views = self._views(images, layout)
+        views = self._views(images, layout, floats)
+        convs = None
+        if floats:  # one InConvert per channel count among the pictures; mean / std are checked even for an empty call
+            mean, std = _numbers(mean, "mean"), _numbers(std, "std")
+            given = mean if mean is not None else std
+            by_c = {c: None for c in ([v[3] for v in views] or [len(given) if given is not None else 1])}
+            for c in by_c:
+                scale, bias = denorm_scale_bias(c, mean, std)
+                by_c[c] = InConvert(_FLOAT_DT[views[0][0].dtype] if views else MIJ_DT_F32, scale, bias)
+            convs = [by_c[v[3]] for v in views]
+        self._placed(views)
         if not views:
             return []
         flip = bool(flip_vertically)
@@ -165,19 +238,20 @@ class TensorEncoder:
             while j < len(views) and j - i < MAX_SLOTS and (j == i or pix + sizes[j][0] <= MAX_PIXEL_BYTES):
                 pix += sizes[j][0]
                 j += 1
-            streams, h = self._encode_chunk(views[i:j], sizes[i:j], quality, lay, flip, optimize)
+            streams, h = self._encode_chunk(views[i:j], sizes[i:j], quality, lay, flip, optimize, convs[i:j] if floats else None)
             out.extend(streams)
             host += h
             i = j
         self.last_host_emitted = host
         return out
 
-    def _encode_chunk(self, views, sizes, quality, lay, flip, optimize):
+    def _encode_chunk(self, views, sizes, quality, lay, flip, optimize, convs=None):
         if not self._arena:  # a first guess, about 0.75 bytes per pixel; misses grow it
             self._arena = _align(sum(1024 + (px * 3) // 4 for (_, _, px) in sizes), 1 << 20)
         enc = self._encoder_for(len(views), sum(s[0] for s in sizes), sum(s[1] for s in sizes))
-        for (t, w, h, c, rp, pp) in views:
-            slot = enc.add_device(InTensor(t.data_ptr(), lay, w, h, c, rp, pp), quality, flip)
+        for k, (t, w, h, c, rp, pp) in enumerate(views):
+            it = InTensor(t.data_ptr(), lay, w, h, c, rp, pp)
+            slot = enc.add_device(it, quality, flip) if convs is None else enc.add_device_float(it, convs[k], quality, flip)
             if optimize:
                 enc.set_optimize(slot)
         enc.upload()

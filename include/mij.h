@@ -622,6 +622,35 @@ typedef struct {
 } mij_in_tensor;
 int mij_enc_add_device(mij_encoder *e, const mij_in_tensor *t, int quality, int flip_vertically);
 
+/*
+ * Device-pixel slots whose elements are float16, bfloat16 or float32: the backward direction of tensor output.  The gather kernel
+ * de-normalises every element on its way into the pixel arena.  THE CONTRACT, for element x of channel c, with the caller's
+ * float32 scale[c] and bias[c]:
+ *
+ *     t = fl32( fl32(x) * scale[c] )      // x widened exactly: f16 and bf16 -> f32 lose nothing
+ *     t = fl32( t + bias[c] )             // two roundings: NO fused multiply-add
+ *     u = (uint8) rintf( fminf( fmaxf(t, 0.0f), 255.0f ) )   // round half to even; NaN -> 0, -Inf -> 0, +Inf -> 255
+ *
+ * The picture that is encoded is the uint8 picture of those u.  From there on the slot is an ordinary device-pixel slot: the comp
+ * channel rule (grey and grey + alpha take channel 0 for r, g and b; alpha is never read as a colour), edge replication, flip,
+ * mij_enc_add_clone, mij_enc_set_optimize, mij_enc_stream_reserve and mij_enc_fetch work on it unchanged, and its stream equals
+ * stbi_write_jpg_to_func(width, height, comp, the picture of u, quality).  The kernels (k_enc_gather_float, one per dtype)
+ * multiply and add with __fmul_rn and __fadd_rn, which the compiler cannot contract.  Subnormal float32 inputs and products may or
+ * may not be flushed to zero; with |scale| < 2^100 that never changes u (such a product stays below 2^-26).  For tensors made by mij_batch_set_out_tensor's tables ((v/255 - mean)/std):
+ * scale = 255*std and bias = 255*mean invert them exactly, for all three dtypes (tests/test_tensor_encode_float_host.py).
+ *
+ * t's pitches count elements of cv->dtype.  Every check of mij_enc_add_device applies, the read extent taken in bytes of the
+ * element size.  MIJ_E_ARG also for: MIJ_DT_U8 (mij_enc_add_device's job) or an unknown dtype; src not aligned to its element
+ * size; a scale or bias among the first comp entries that is not finite.  uint8 slots and float slots of one upload each get
+ * their own gather launch (float slots one per dtype); an upload without a float slot queues exactly what it queued before.
+ * ORDERING as for mij_enc_add_device.
+ */
+typedef struct {
+	int32_t dtype; /* MIJ_DT_F16 | MIJ_DT_BF16 | MIJ_DT_F32 */
+	float scale[4], bias[4];
+} mij_in_convert;
+int mij_enc_add_device_float(mij_encoder *e, const mij_in_tensor *t, const mij_in_convert *cv, int quality, int flip_vertically);
+
 /* A slot whose quantised data units are given: mjw_plan_du_count * 64 int16 in zigzag order, MCU after MCU (copied).  No transform
  * runs for it; its units are uploaded and emitted.  MIJ_E_ARG when a DC difference (per component, in MCU order, from 0) leaves
  * -2047..2047 or an AC value leaves -1023..1023: those fall outside the writer's tables.  mij_enc_add_clone refuses such a slot. */
