@@ -42,6 +42,15 @@ from .binding import (  # noqa: F401
     PinnedBuffer,
     host_transform,
     emit_jpeg,
+    TranscodePlan,
+    MJW_COPY_MARKERS,
+    transcode_plan,
+    transcode_header,
+    units_from_region,
+    units_codable,
+    emit_transcoded,
+    copy_markers,
+    transcode_memory,
     write_histogram,
     optimal_huffman_table,
     MJW_OPTIMIZE_HUFFMAN,
@@ -83,6 +92,7 @@ from .synth import synth_rgb, synth_jpeg, synth_rgb_edges  # noqa: F401
 
 _TENSOR_OUT = ("TensorDecoder", "tensor_tables")
 _TENSOR_ENCODE = ("TensorEncoder",)
+_TRANSCODE = ("Transcoder",)
 
 
 def __getattr__(name):
@@ -94,4 +104,7 @@ def __getattr__(name):
     if name in _TENSOR_ENCODE:
         from . import tensor_encode
         return getattr(tensor_encode, name)
+    if name in _TRANSCODE:  # no torch behind this one; loaded on first use like the other front ends
+        from . import transcode
+        return getattr(transcode, name)
     raise AttributeError("module 'image_codecs_amd' has no attribute %r" % name)

@@ -1227,6 +1227,117 @@ def emit_jpeg(plan, du, optimize=False):
     return b"".join(chunks) if ok else None
 
 
+class TranscodePlan(C.Structure):
+    """mjw_tplan (include/mij_host.h): the plan of a lossless transcode -- the source's geometry and tables."""
+    _fields_ = [("plan", WritePlan), ("ncomp", C.c_int), ("lh", C.c_int), ("lv", C.c_int)]
+
+    def du_elems(self):
+        return self.plan.du_elems()
+
+
+MJW_COPY_MARKERS = 2
+_libc_free = None
+
+
+def _take_malloced(ptr, n):
+    global _libc_free
+    if _libc_free is None:
+        _libc_free = C.CDLL(None).free
+        _libc_free.argtypes = [C.c_void_p]
+    data = C.string_at(ptr, n)
+    _libc_free(ptr)
+    return data
+
+
+def transcode_plan(desc):
+    """mjw_tplan_from_desc -> (TranscodePlan, None), or (None, reason) for a source that is not transcodable."""
+    L = lib()
+    L.mjw_tplan_from_desc.argtypes = [C.POINTER(TranscodePlan), C.POINTER(ImageDesc), C.POINTER(C.c_char_p)]
+    t, why = TranscodePlan(), C.c_char_p()
+    if not L.mjw_tplan_from_desc(C.byref(t), C.byref(desc), C.byref(why)):
+        return None, (why.value.decode() if why.value else "refused")
+    return t, None
+
+
+def transcode_header(tplan, tables=None):
+    """mjw_theader, or mjw_theader_optimized with tables = (bits uint8 [4, 16], vals uint8 [4, 256]) -> bytes"""
+    L = lib()
+    out = C.create_string_buffer(1024)
+    if tables is None:
+        L.mjw_theader.restype = C.c_size_t
+        L.mjw_theader.argtypes = [C.POINTER(TranscodePlan), C.c_char_p]
+        n = L.mjw_theader(C.byref(tplan), out)
+    else:
+        bits, vals = (np.ascontiguousarray(a, np.uint8) for a in tables)
+        assert bits.shape == (4, 16) and vals.shape == (4, 256)
+        L.mjw_theader_optimized.restype = C.c_size_t
+        L.mjw_theader_optimized.argtypes = [C.POINTER(TranscodePlan), C.c_void_p, C.c_void_p, C.c_char_p]
+        n = L.mjw_theader_optimized(C.byref(tplan), bits.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p), out)
+    return out.raw[:n]
+
+
+def units_from_region(desc, region, compact):
+    """mjw_units_from_region: an image's coefficient region (host_decode_staged) -> int16 [n_du, 64], None when not transcodable."""
+    t, _ = transcode_plan(desc)
+    if t is None:
+        return None
+    L = lib()
+    L.mjw_units_from_region.argtypes = [C.POINTER(ImageDesc), C.c_void_p, C.c_int, C.c_void_p]
+    r = np.ascontiguousarray(region, np.uint8)
+    du = np.empty(t.du_elems(), np.int16)
+    if not L.mjw_units_from_region(C.byref(desc), r.ctypes.data_as(C.c_void_p), int(bool(compact)), du.ctypes.data_as(C.c_void_p)):
+        return None
+    return du.reshape(-1, 64)
+
+
+def units_codable(tplan, du):
+    """mjw_tunits_codable -> (True, None) or (False, reason)"""
+    L = lib()
+    L.mjw_tunits_codable.argtypes = [C.POINTER(TranscodePlan), C.c_void_p, C.POINTER(C.c_char_p)]
+    d = np.ascontiguousarray(du, np.int16)
+    if d.size != tplan.du_elems():
+        raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, tplan.du_elems()))
+    why = C.c_char_p()
+    ok = L.mjw_tunits_codable(C.byref(tplan), d.ctypes.data_as(C.c_void_p), C.byref(why))
+    return bool(ok), (None if ok else why.value.decode())
+
+
+def emit_transcoded(tplan, du, optimize=False):
+    """mjw_temit / mjw_temit_optimized over given units -> bytes, None when the units are not codable."""
+    L = lib()
+    fn = L.mjw_temit_optimized if optimize else L.mjw_temit
+    fn.argtypes = [C.POINTER(TranscodePlan), C.c_void_p, _WRITE_CB, C.c_void_p]
+    d = np.ascontiguousarray(du, np.int16)
+    if d.size != tplan.du_elems():
+        raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, tplan.du_elems()))
+    chunks = []
+    cb = _WRITE_CB(lambda _c, data, size: chunks.append(C.string_at(data, size)))
+    return b"".join(chunks) if fn(C.byref(tplan), d.ctypes.data_as(C.c_void_p), cb, None) else None
+
+
+def copy_markers(src, stream):
+    """mjw_copy_markers: `stream` with the source's APPn and COM segments behind SOI -> (bytes, None) or (None, reason)"""
+    L = lib()
+    L.mjw_copy_markers.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_char_p)]
+    src, stream = bytes(src), bytes(stream)
+    out, n, why = C.c_void_p(), C.c_size_t(), C.c_char_p()
+    if not L.mjw_copy_markers(src, len(src), stream, len(stream), C.byref(out), C.byref(n), C.byref(why)):
+        return None, (why.value.decode() if why.value else "refused")
+    return _take_malloced(out, n.value), None
+
+
+def transcode_memory(data, optimize=False, copy_markers=False):
+    """mjh_transcode_memory, the lossless transcode on the host alone -> (bytes, None) or (None, reason)"""
+    L = lib()
+    L.mjh_transcode_memory.argtypes = [C.c_char_p, C.c_int, C.c_uint, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_char_p)]
+    data = bytes(data)
+    out, n, why = C.c_void_p(), C.c_size_t(), C.c_char_p()
+    flags = (MJW_OPTIMIZE_HUFFMAN if optimize else 0) | (MJW_COPY_MARKERS if copy_markers else 0)
+    if not L.mjh_transcode_memory(data, len(data), flags, C.byref(out), C.byref(n), C.byref(why)):
+        return None, (why.value.decode() if why.value else "decode failed")
+    return _take_malloced(out, n.value), None
+
+
 def write_histogram(plan, du):
     """mjw_histogram: the symbols mjw_emit emits for these units, counted -> uint32 [4, 256] (luma DC, chroma DC, luma AC, chroma AC),
     None when it is refused."""
@@ -1420,6 +1531,35 @@ class Encoder:
         if L.mjw_plan_init(C.byref(plan), int(width), int(height), int(comp), int(quality)) and d.size != plan.du_elems():
             raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, plan.du_elems()))
         return _check(L.mij_enc_add_units(self._h, int(width), int(height), int(comp), int(quality), d.ctypes.data_as(C.c_void_p)), "mij_enc_add_units")
+
+    def add_coef(self, batch, slot):
+        """mij_enc_add_coef: a slot whose units are the quantised coefficients of an uploaded Batch's slot (lossless transcode).
+        MijError with the reason for a picture that is not transcodable.  The batch must stay as it is until wait() or a fetch."""
+        L = lib()
+        L.mij_enc_add_coef.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        return _check(L.mij_enc_add_coef(self._h, batch._h, int(slot)), "mij_enc_add_coef")
+
+    def tplan(self, slot):
+        """mij_enc_tplan: the TranscodePlan of a slot made by add_coef"""
+        L = lib()
+        L.mij_enc_tplan.argtypes = [C.c_void_p, C.c_int, C.POINTER(TranscodePlan)]
+        t = TranscodePlan()
+        _check(L.mij_enc_tplan(self._h, int(slot), C.byref(t)), "mij_enc_tplan")
+        return t
+
+    def slot_status(self, slot):
+        """mij_enc_slot_status, after fetch_streams -> "ok", "no room" (finish it on the host from its units) or "uncodable" """
+        L = lib()
+        L.mij_enc_slot_status.argtypes = [C.c_void_p, C.c_int]
+        return ("ok", "no room", "uncodable")[_check(L.mij_enc_slot_status(self._h, int(slot)), "mij_enc_slot_status")]
+
+    def coef_ms(self):
+        """ms the conversion kernels (planes -> units) of the last upload took, None when there were none"""
+        L = lib()
+        L.mij_enc_coef_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        ms = C.c_float()
+        _check(L.mij_enc_coef_ms(self._h, C.byref(ms)), "mij_enc_coef_ms")
+        return None if ms.value < 0 else ms.value
 
     def set_optimize(self, slot, on=True):
         """mij_enc_set_optimize: the slot's stream gets Huffman tables built from its own symbol statistics; before upload."""

@@ -487,8 +487,8 @@ void mjw_huff_tables(uint16_t code[4][256], uint8_t len[4][256])
 }
 
 /* headers (hdr_len bytes), the entropy-coded segment under the four tables, fill and EOI */
-static int emit_with(const mjw_plan *p, const int16_t *du, mjw_write_func *func, void *context, const enc_table *ydc, const enc_table *yac,
-							const enc_table *cdc, const enc_table *cac, const unsigned char *hdr, size_t hdr_len)
+static int emit_units_with(size_t nm, int ny, int ncomp, const int16_t *du, mjw_write_func *func, void *context, const enc_table *ydc, const enc_table *yac,
+									const enc_table *cdc, const enc_table *cac, const unsigned char *hdr, size_t hdr_len)
 {
 	jw_sink *s = (jw_sink *)calloc(1, sizeof(*s));
 	if (!s)
@@ -498,23 +498,17 @@ static int emit_with(const mjw_plan *p, const int16_t *du, mjw_write_func *func,
 	sink_bytes(s, hdr, (int)hdr_len); /* headers (codec/jpeg_write.c:245-268) */
 	{
 		int dcy = 0, dcu = 0, dcv = 0;
-		size_t m, nm = (size_t)p->mcu_x * (size_t)p->mcu_y;
+		size_t m;
+		int k;
 		s->acc = 0;
 		s->nacc = 0;
-		for (m = 0; m < nm; ++m) {
-			if (p->subsample) {
+		for (m = 0; m < nm; ++m) { /* an MCU: its ny luma units, then Cb and Cr where the picture has them */
+			for (k = 0; k < ny; ++k, du += 64)
 				dcy = emit_du(s, du, dcy, ydc, yac);
-				dcy = emit_du(s, du + 64, dcy, ydc, yac);
-				dcy = emit_du(s, du + 128, dcy, ydc, yac);
-				dcy = emit_du(s, du + 192, dcy, ydc, yac);
-				dcu = emit_du(s, du + 256, dcu, cdc, cac);
-				dcv = emit_du(s, du + 320, dcv, cdc, cac);
-				du += 384;
-			} else {
-				dcy = emit_du(s, du, dcy, ydc, yac);
-				dcu = emit_du(s, du + 64, dcu, cdc, cac);
-				dcv = emit_du(s, du + 128, dcv, cdc, cac);
-				du += 192;
+			if (ncomp == 3) {
+				dcu = emit_du(s, du, dcu, cdc, cac);
+				dcv = emit_du(s, du + 64, dcv, cdc, cac);
+				du += 128;
 			}
 		}
 		put_bits(s, 0x7F, 7); /* pad to a byte boundary with ones */
@@ -525,6 +519,11 @@ static int emit_with(const mjw_plan *p, const int16_t *du, mjw_write_func *func,
 	sink_flush(s);
 	free(s);
 	return 1;
+}
+static int emit_with(const mjw_plan *p, const int16_t *du, mjw_write_func *func, void *context, const enc_table *ydc, const enc_table *yac,
+							const enc_table *cdc, const enc_table *cac, const unsigned char *hdr, size_t hdr_len)
+{
+	return emit_units_with((size_t)p->mcu_x * (size_t)p->mcu_y, p->subsample ? 4 : 1, 3, du, func, context, ydc, yac, cdc, cac, hdr, hdr_len);
 }
 
 int mjw_emit(const mjw_plan *p, const int16_t *du, mjw_write_func *func, void *context)
@@ -564,22 +563,28 @@ static int count_du(const int16_t *du, int dc_pred, uint32_t *fdc, uint32_t *fac
 	return du[0];
 }
 
-int mjw_histogram(const mjw_plan *p, const int16_t *du, uint32_t freq[4][256])
+static void histogram_units(size_t nm, int ny, int ncomp, const int16_t *du, uint32_t freq[4][256])
 {
 	int dcy = 0, dcu = 0, dcv = 0;
-	size_t m, nm;
-	if (!p || !du || !freq || mjw_plan_du_count(p) > (size_t)(UINT32_MAX / 64))
-		return 0;
+	size_t m;
 	memset(freq, 0, sizeof(uint32_t) * 4 * 256);
-	nm = (size_t)p->mcu_x * (size_t)p->mcu_y;
 	for (m = 0; m < nm; ++m) {
 		int k;
-		for (k = 0; k < (p->subsample ? 4 : 1); ++k, du += 64)
+		for (k = 0; k < ny; ++k, du += 64)
 			dcy = count_du(du, dcy, freq[0], freq[2]);
-		dcu = count_du(du, dcu, freq[1], freq[3]);
-		dcv = count_du(du + 64, dcv, freq[1], freq[3]);
-		du += 128;
+		if (ncomp == 3) {
+			dcu = count_du(du, dcu, freq[1], freq[3]);
+			dcv = count_du(du + 64, dcv, freq[1], freq[3]);
+			du += 128;
+		}
 	}
+}
+
+int mjw_histogram(const mjw_plan *p, const int16_t *du, uint32_t freq[4][256])
+{
+	if (!p || !du || !freq || mjw_plan_du_count(p) > (size_t)(UINT32_MAX / 64))
+		return 0;
+	histogram_units((size_t)p->mcu_x * (size_t)p->mcu_y, p->subsample ? 4 : 1, 3, du, freq);
 	return 1;
 }
 
@@ -707,6 +712,141 @@ int mjw_emit_optimized(const mjw_plan *p, const int16_t *du, mjw_write_func *fun
 	return emit_with(p, du, func, context, &t[0], &t[2], &t[1], &t[3], hdr, mjw_header_optimized(p, bits, vals, hdr));
 }
 
+/* ---- lossless transcode (include/mij_host.h, mjw_tplan): the same emission over the five MCU shapes a transcodable source has, with the
+ * source's own quantisation tables in the header */
+
+static int tplan_ny(const mjw_tplan *t) { return t->ncomp == 1 ? 1 : t->lh * t->lv; }
+size_t mjw_tplan_du_count(const mjw_tplan *t) { return t ? mjw_plan_du_count(&t->plan) : 0; }
+
+/* SOI .. SOS with the four tables given as BITS (16 counts) and HUFFVAL, indexed luma DC, chroma DC, luma AC, chroma AC; a grey picture
+ * carries one quantisation table, one component and the two luma tables */
+static size_t theader_tables(const mjw_tplan *t, const unsigned char *const bits[4], const unsigned char *const vals[4], unsigned char *out)
+{
+	static const unsigned char soi_app0[] = {0xFF, 0xD8, 0xFF, 0xE0, 0, 0x10, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+	static const unsigned char ids[4] = {0x00, 0x10, 0x01, 0x11};
+	static const int order[4] = {0, 2, 1, 3};
+	const int grey = t->ncomp == 1, ntab = grey ? 2 : 4;
+	const mjw_plan *p = &t->plan;
+	unsigned char *o = out, *dht_len;
+	int k, i, n;
+#define PUT(src, n) (memcpy(o, (src), (n)), o += (n))
+	PUT(soi_app0, sizeof(soi_app0));
+	*o++ = 0xFF, *o++ = 0xDB, *o++ = 0, *o++ = (unsigned char)(grey ? 0x43 : 0x84), *o++ = 0;
+	PUT(p->ytab, 64);
+	if (!grey) {
+		*o++ = 1;
+		PUT(p->ctab, 64);
+	}
+	*o++ = 0xFF, *o++ = 0xC0, *o++ = 0, *o++ = (unsigned char)(grey ? 0x0B : 0x11), *o++ = 8;
+	*o++ = (unsigned char)(p->height >> 8), *o++ = (unsigned char)(p->height & 0xff);
+	*o++ = (unsigned char)(p->width >> 8), *o++ = (unsigned char)(p->width & 0xff);
+	*o++ = (unsigned char)t->ncomp;
+	*o++ = 1, *o++ = (unsigned char)(grey ? 0x11 : (t->lh << 4 | t->lv)), *o++ = 0;
+	if (!grey) {
+		*o++ = 2, *o++ = 0x11, *o++ = 1;
+		*o++ = 3, *o++ = 0x11, *o++ = 1;
+	}
+	*o++ = 0xFF, *o++ = 0xC4;
+	dht_len = o;
+	o += 2;
+	for (k = 0; k < ntab; ++k) {
+		const int tb = order[k];
+		for (i = 0, n = 0; i < 16; ++i)
+			n += bits[tb][i];
+		*o++ = ids[k];
+		PUT(bits[tb], 16);
+		PUT(vals[tb], (size_t)n);
+	}
+	n = (int)(o - dht_len);
+	dht_len[0] = (unsigned char)(n >> 8);
+	dht_len[1] = (unsigned char)(n & 0xff);
+	if (grey) {
+		static const unsigned char sos1[] = {0xFF, 0xDA, 0, 8, 1, 1, 0, 0, 0x3F, 0};
+		PUT(sos1, sizeof(sos1));
+	} else {
+		static const unsigned char sos3[] = {0xFF, 0xDA, 0, 0xC, 3, 1, 0, 2, 0x11, 3, 0x11, 0, 0x3F, 0};
+		PUT(sos3, sizeof(sos3));
+	}
+#undef PUT
+	return (size_t)(o - out);
+}
+
+size_t mjw_theader(const mjw_tplan *t, unsigned char *out)
+{
+	const unsigned char *const bits[4] = {k_dc_lum_bits + 1, k_dc_chr_bits + 1, k_ac_lum_bits + 1, k_ac_chr_bits + 1};
+	const unsigned char *const vals[4] = {k_dc_vals, k_dc_vals, k_ac_lum_vals, k_ac_chr_vals};
+	return theader_tables(t, bits, vals, out);
+}
+
+size_t mjw_theader_optimized(const mjw_tplan *t, const uint8_t bits[4][16], const uint8_t vals[4][256], unsigned char *out)
+{
+	const unsigned char *const b[4] = {bits[0], bits[1], bits[2], bits[3]};
+	const unsigned char *const v[4] = {vals[0], vals[1], vals[2], vals[3]};
+	return theader_tables(t, b, v, out);
+}
+
+int mjw_tunits_codable(const mjw_tplan *t, const int16_t *du, const char **reason)
+{
+	const size_t nu = mjw_tplan_du_count(t);
+	const int ny = tplan_ny(t), dpm = t->plan.du_per_mcu;
+	int pred[3] = {0, 0, 0}, k;
+	size_t u;
+	for (u = 0; u < nu; ++u, du += 64) {
+		const int p = (int)(u % (size_t)dpm), c = p < ny ? 0 : p - ny + 1, diff = du[0] - pred[c];
+		pred[c] = du[0];
+		if (diff < -2047 || diff > 2047) {
+			if (reason)
+				*reason = "a DC difference outside -2047..2047";
+			return 0;
+		}
+		for (k = 1; k < 64; ++k)
+			if (du[k] < -1023 || du[k] > 1023) {
+				if (reason)
+					*reason = "an AC coefficient outside -1023..1023";
+				return 0;
+			}
+	}
+	return 1;
+}
+
+int mjw_temit(const mjw_tplan *t, const int16_t *du, mjw_write_func *func, void *context)
+{
+	enc_table ydc, yac, cdc, cac;
+	unsigned char hdr[MJW_HEADER_BYTES];
+	if (!t || !func || !du || !mjw_tunits_codable(t, du, NULL))
+		return 0;
+	make_enc_table(&ydc, k_dc_lum_bits, k_dc_vals);
+	make_enc_table(&cdc, k_dc_chr_bits, k_dc_vals);
+	make_enc_table(&yac, k_ac_lum_bits, k_ac_lum_vals);
+	make_enc_table(&cac, k_ac_chr_bits, k_ac_chr_vals);
+	return emit_units_with((size_t)t->plan.mcu_x * (size_t)t->plan.mcu_y, tplan_ny(t), t->ncomp, du, func, context, &ydc, &yac, &cdc, &cac, hdr,
+								  mjw_theader(t, hdr));
+}
+
+int mjw_temit_optimized(const mjw_tplan *t, const int16_t *du, mjw_write_func *func, void *context)
+{
+	uint32_t freq[4][256];
+	uint8_t bits[4][16], vals[4][256];
+	unsigned char b17[17], hdr[MJW_HEADER_BYTES];
+	enc_table tb[4];
+	int k, n;
+	if (!t || !func || !du || !mjw_tunits_codable(t, du, NULL))
+		return 0;
+	if (mjw_tplan_du_count(t) > (size_t)(UINT32_MAX / 64))
+		return mjw_temit(t, du, func, context);
+	histogram_units((size_t)t->plan.mcu_x * (size_t)t->plan.mcu_y, tplan_ny(t), t->ncomp, du, freq);
+	for (k = 0; k < 4; ++k) {
+		memset(vals[k], 0, 256);
+		if (!mjw_optimal_table(freq[k], bits[k], vals[k], &n))
+			return mjw_temit(t, du, func, context); /* a code longer than 32 bits before limiting: the plain tables */
+		b17[0] = 0;
+		memcpy(b17 + 1, bits[k], 16);
+		make_enc_table(&tb[k], b17, vals[k]);
+	}
+	return emit_units_with((size_t)t->plan.mcu_x * (size_t)t->plan.mcu_y, tplan_ny(t), t->ncomp, du, func, context, &tb[0], &tb[2], &tb[1], &tb[3], hdr,
+								  mjw_theader_optimized(t, bits, vals, hdr));
+}
+
 typedef struct {
 	unsigned char *out;
 	size_t cap, len;
@@ -737,6 +877,19 @@ static size_t emit_to_memory(const mjw_plan *p, const int16_t *du, unsigned char
 }
 size_t mjw_emit_to_memory(const mjw_plan *p, const int16_t *du, unsigned char *out, size_t cap) { return emit_to_memory(p, du, out, cap, 0); }
 size_t mjw_emit_optimized_to_memory(const mjw_plan *p, const int16_t *du, unsigned char *out, size_t cap) { return emit_to_memory(p, du, out, cap, 1); }
+size_t mjw_temit_to_memory(const mjw_tplan *t, const int16_t *du, unsigned flags, unsigned char *out, size_t cap)
+{
+	mem_sink m;
+	if (!t || !du || !out)
+		return 0;
+	m.out = out;
+	m.cap = cap;
+	m.len = 0;
+	m.overflow = 0;
+	if (!((flags & MJW_OPTIMIZE_HUFFMAN) ? mjw_temit_optimized : mjw_temit)(t, du, mem_sink_write, &m) || m.overflow)
+		return 0;
+	return m.len;
+}
 
 int stbi_write_jpg_to_func(stbi_write_func *func, void *context, int x, int y, int comp, const void *data, int quality)
 {

@@ -45,10 +45,10 @@ struct EmitTables {
 
 struct EmitSlot {
 	uint64_t du_off; /* bytes into the data-unit arena */
-	uint32_t n_du, dpm; /* units; units per MCU: 6 (4:2:0) or 3 (4:4:4) */
+	uint32_t n_du, dpm; /* units; units per MCU: 6 (4:2:0), 3 (4:4:4) and, for coefficient slots (mij_enc_add_coef), 4 (4:2:2, 4:4:0) or 1 (grey) */
 	uint32_t first_tile, n_tiles;
 	uint32_t hdr, tab; /* header of the slot: hdrs + hdr * MIJ_EMIT_HDR; tab > 0: optimised, its tables are entry tab, its counts tab - 1 */
-	uint32_t hlen, pad; /* the header's length: MIJ_EMIT_HDR, or what k_emit_build wrote */
+	uint32_t hlen, ny; /* the header's length: what the upload wrote, or what k_emit_build wrote; luma units per MCU (1, 2 or 4): unit p of an MCU is luma when p < ny */
 };
 
 struct EmitTile {
@@ -82,11 +82,10 @@ struct UnitIn {
 __device__ __forceinline__ UnitIn emit_load(const EmitSlot &s, const int16_t *__restrict__ du, uint32_t u, int lane)
 {
 	const uint32_t m = u / s.dpm, p = u - m * s.dpm;
-	long prev = -1; /* the unit whose DC predicts this one's: the previous unit of the component in MCU order */
-	if (s.dpm == 6u)
-		prev = (p > 0 && p < 4) ? (long)u - 1 : (m > 0 ? (long)u - (p < 4 ? 3 : 6) : -1);
-	else
-		prev = m > 0 ? (long)u - 3 : -1;
+	/* the unit whose DC predicts this one's, the previous unit of the component in MCU order: u - 1 inside an MCU's luma run, the last luma unit
+	 * of the MCU before for its first, the same unit of the MCU before for chroma */
+	const long back = p < s.ny ? (long)(s.dpm - s.ny + 1u) : (long)s.dpm;
+	const long prev = p > 0 && p < s.ny ? (long)u - 1 : (m > 0 ? (long)u - back : -1);
 	UnitIn in;
 	in.v = du[(size_t)u * 64 + lane];
 	in.pred = lane == 0 && prev >= 0 ? (int)du[(size_t)prev * 64] : 0;
@@ -100,7 +99,7 @@ template <typename Own>
 __device__ __forceinline__ void emit_owner(const EmitSlot &s, UnitIn in, uint32_t u, int lane, Own &own)
 {
 	const uint32_t m = u / s.dpm, p = u - m * s.dpm;
-	const bool luma = p < (s.dpm == 6u ? 4u : 1u);
+	const bool luma = p < s.ny;
 	const int v = in.v;
 	const uint64_t nz = __ballot(v != 0) & ~1ull;
 	own.begin(luma);
@@ -313,7 +312,8 @@ __global__ __launch_bounds__(256) void k_emit_scan(const EmitSlot *__restrict__ 
 /* per tile: the 0xFF bytes among those whose 8 bits all lie in the tile, and the head / tail fragments (t_frag = head | tail << 8) */
 __global__ __launch_bounds__(256) void k_emit_count(const EmitSlot *__restrict__ slots, const EmitTile *__restrict__ tiles,
 																	 const EmitTables *__restrict__ T, const uint8_t *__restrict__ du_base, const uint32_t *__restrict__ t_bits,
-																	 const uint64_t *__restrict__ t_boff, uint32_t *__restrict__ t_ff, uint32_t *__restrict__ t_frag)
+																	 const uint64_t *__restrict__ t_boff, uint32_t *__restrict__ t_ff, uint32_t *__restrict__ t_frag,
+																	 const uint32_t *__restrict__ s_flag)
 {
 	__shared__ uint32_t buf[MIJ_EMIT_LDS_WORDS];
 	__shared__ uint32_t uoff[MIJ_EMIT_TILE + 1];
@@ -324,7 +324,9 @@ __global__ __launch_bounds__(256) void k_emit_count(const EmitSlot *__restrict__
 	const uint64_t b0 = t_boff[blockIdx.x], b1 = b0 + t_bits[blockIdx.x];
 	const uint32_t h = (uint32_t)(b0 & 7u), n_own = (uint32_t)((b1 >> 3) - (b0 >> 3));
 	const uint32_t nwords = (uint32_t)((h + (b1 - b0) + 31) / 32);
-	if (nwords > MIJ_EMIT_LDS_WORDS - 1) { /* only units outside the writer's ranges get here: the slot is refused (k_emit_stuff) */
+	/* units outside the writer's ranges: the slot is refused (k_emit_stuff) before anything is packed -- a coefficient slot the conversion
+	 * kernel flagged (s_flag, NULL when the launch has no such slot), or a tile longer than the ranges allow */
+	if ((s_flag && s_flag[tl.slot]) || nwords > MIJ_EMIT_LDS_WORDS - 1) {
 		if (threadIdx.x == 0) {
 			t_ff[blockIdx.x] = ~0u;
 			t_frag[blockIdx.x] = 0;
@@ -536,8 +538,11 @@ __global__ __launch_bounds__(256) void k_emit_hist(const EmitSlot *__restrict__ 
 			atomicAdd(&g[i], hist[i]);
 }
 
-/* the SOS segment behind the DHT segment (mjw_header) */
+/* the SOS segment behind the DHT segment (mjw_header), and a grey slot's (mjw_theader) */
 __device__ const uint8_t k_emit_sos[14] = {0xFF, 0xDA, 0, 0xC, 3, 1, 0, 2, 0x11, 3, 0x11, 0, 0x3F, 0};
+__device__ const uint8_t k_emit_sos1[10] = {0xFF, 0xDA, 0, 8, 1, 1, 0, 0, 0x3F, 0};
+#define MIJ_EMIT_DHT_AT 177 /* the first byte behind the DHT segment's length in a three-component header */
+#define MIJ_EMIT_DHT_AT1 106 /* ... in a grey header: one quantisation table, one component in SOF0 */
 
 __device__ __forceinline__ uint64_t wave_min64(uint64_t v)
 {
@@ -658,7 +663,10 @@ __global__ __launch_bounds__(256) void k_emit_build(EmitSlot *__restrict__ slots
 		nvals[t] = p;
 	}
 	__syncthreads();
-	const uint32_t hlen = 177u + 4u * 17u + nvals[0] + nvals[1] + nvals[2] + nvals[3] + 14u;
+	/* a slot without chroma (dpm == ny) carries the two luma tables only, in the shorter header */
+	const bool grey = slots[slot].dpm == slots[slot].ny;
+	const uint32_t dht_at = grey ? MIJ_EMIT_DHT_AT1 : MIJ_EMIT_DHT_AT, sos_len = grey ? 10u : 14u;
+	const uint32_t hlen = grey ? dht_at + 2u * 17u + nvals[0] + nvals[2] + sos_len : dht_at + 4u * 17u + nvals[0] + nvals[1] + nvals[2] + nvals[3] + sos_len;
 	const bool ok = !fail && hlen <= MIJ_EMIT_HDR && nvals[t] == nv;
 	const bool all_ok = __syncthreads_and(ok) != 0;
 	const uint32_t tile0 = slots[slot].first_tile, ntile = slots[slot].n_tiles;
@@ -667,11 +675,12 @@ __global__ __launch_bounds__(256) void k_emit_build(EmitSlot *__restrict__ slots
 	if (all_ok) {
 		/* the DHT segment holds the tables in mjw_header's order: luma DC, luma AC, chroma DC, chroma AC */
 		const uint32_t before = t == 0 ? 0u : (t == 2 ? 17u + nvals[0] : (t == 1 ? 34u + nvals[0] + nvals[2] : 51u + nvals[0] + nvals[2] + nvals[1]));
-		uint8_t *h = hdrs + (size_t)slots[slot].hdr * MIJ_EMIT_HDR, *seg = h + 177 + before;
+		uint8_t *h = hdrs + (size_t)slots[slot].hdr * MIJ_EMIT_HDR, *seg = h + dht_at + before;
 		EmitTables *T = tabs + k + 1;
-		if (lane == 0)
+		const bool in_dht = !grey || t == 0 || t == 2; /* the code tables are written for all four: a grey slot never looks its chroma tables up */
+		if (lane == 0 && in_dht)
 			seg[0] = (uint8_t)(t == 0 ? 0x00 : (t == 2 ? 0x10 : (t == 1 ? 0x01 : 0x11)));
-		if (lane < 16)
+		if (lane < 16 && in_dht)
 			seg[1 + lane] = (uint8_t)bits[t][lane + 1];
 #pragma unroll
 		for (int q = 0; q < 4; ++q) {
@@ -682,22 +691,22 @@ __global__ __launch_bounds__(256) void k_emit_build(EmitSlot *__restrict__ slots
 						len = (uint32_t)l;
 						code = first_code[t][l] + (uint32_t)pos[q] - first_pos[t][l];
 					}
-				seg[17 + pos[q]] = (uint8_t)(lane + 64 * q);
+				if (in_dht)
+					seg[17 + pos[q]] = (uint8_t)(lane + 64 * q);
 			}
 			T->code[t][lane + 64 * q] = (uint16_t)code;
 			T->len[t][lane + 64 * q] = (uint8_t)len;
 		}
-		if (t == 3 && lane < 14)
-			h[hlen - 14 + lane] = k_emit_sos[lane];
+		if (t == 3 && (uint32_t)lane < sos_len)
+			h[hlen - sos_len + lane] = grey ? k_emit_sos1[lane] : k_emit_sos[lane];
 		if (threadIdx.x == 0) {
-			h[175] = (uint8_t)((hlen - 14 - 175) >> 8);
-			h[176] = (uint8_t)((hlen - 14 - 175) & 0xFFu);
+			h[dht_at - 2] = (uint8_t)((hlen - sos_len - (dht_at - 2)) >> 8);
+			h[dht_at - 1] = (uint8_t)((hlen - sos_len - (dht_at - 2)) & 0xFFu);
 			slots[slot].hlen = hlen;
 			opt_ok[k] = 1;
 		}
 	} else if (threadIdx.x == 0) { /* the plain tables and the plain header, which the upload left in place */
-		slots[slot].hlen = MIJ_EMIT_HDR;
-		opt_ok[k] = 0;
+		opt_ok[k] = 0; /* hlen is still the plain header's, as the upload wrote it */
 	}
 }
 

@@ -5,6 +5,7 @@
  */
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -3176,9 +3177,12 @@ extern "C" int mij_batch_entropy_rounds(const mij_batch *b) { return b && b->es 
  */
 #include "mij_host.h"
 #include "mij_emit_kernels.h"
+#include "mij_transcode_kernels.h"
 static_assert(MIJ_EMIT_HDR == MJW_HEADER_BYTES, "header size");
 
-enum { ENC_HOST = 0, ENC_DEVICE = 1, ENC_UNITS = 2 }; /* where a slot's input comes from: pinned staging, a device tensor, given units */
+/* where a slot's input comes from: pinned staging, a device tensor, given units, a decode batch's coefficient planes */
+enum { ENC_HOST = 0, ENC_DEVICE = 1, ENC_UNITS = 2, ENC_COEF = 3 };
+static inline bool enc_has_pixels(int kind) { return kind == ENC_HOST || kind == ENC_DEVICE; }
 
 struct EncSlot {
 	mjw_plan plan;
@@ -3191,6 +3195,11 @@ struct EncSlot {
 	mij_in_tensor in;           /* ENC_DEVICE */
 	mij_in_convert cv;          /* ENC_DEVICE with float elements (mij_enc_add_device_float); cv.dtype is MIJ_DT_U8 for every other slot */
 	std::vector<int16_t> units; /* ENC_UNITS */
+	/* ENC_COEF (mij_enc_add_coef): the transcode plan (tp.plan == plan), the batch, and where the slot's planes lay when it was added */
+	mjw_tplan tp;
+	mij_batch *src;
+	CoefSlot coef;
+	int coef_fmt;
 };
 
 struct mij_encoder {
@@ -3247,6 +3256,19 @@ struct mij_encoder {
 	size_t optslot_cap, n_opt;
 	uint32_t *d_freq, *d_optok;
 	size_t freq_cap, optok_cap;
+	/* coefficient slots (mij_enc_add_coef): the conversion kernel's slots and work (plane tiles), the event that orders it behind the
+	 * batch's stream, and the per-slot flags it raises for uncodable values (d_sflag: one per slot, read by k_emit_count) */
+	CoefSlot *h_cslot, *d_cslot;
+	size_t cslot_cap;
+	WorkIdct *h_cwork, *d_cwork;
+	size_t cwork_cap;
+	uint32_t *d_sflag;
+	size_t sflag_cap;
+	hipEvent_t ev_coef;
+	bool has_coef; /* the last upload had a coefficient slot */
+	std::vector<uint32_t> sflag; /* after mij_enc_fetch_streams */
+	hipEvent_t ev_conv0, ev_conv1; /* around the conversion kernels of the last upload (mij_enc_coef_ms) */
+	bool conv_timed;
 	std::vector<int> opt_of;      /* slot -> k, or -1 */
 	std::vector<uint32_t> opt_ok; /* after mij_enc_fetch_streams */
 };
@@ -3346,6 +3368,12 @@ extern "C" int mij_enc_create_ex(mij_ctx *ctx, int max_images, size_t stage_byte
 	e->h_otile = e->d_otile = nullptr;
 	e->h_optslot = e->d_optslot = nullptr;
 	e->d_freq = e->d_optok = nullptr;
+	e->h_cslot = e->d_cslot = nullptr;
+	e->h_cwork = e->d_cwork = nullptr;
+	e->d_sflag = nullptr;
+	e->cslot_cap = e->cwork_cap = e->sflag_cap = 0;
+	e->ev_coef = e->ev_conv0 = e->ev_conv1 = nullptr;
+	e->has_coef = e->conv_timed = false;
 	enc_free_emit(e);
 	e->force_generic = getenv("MIJ_ENC_GENERIC") != nullptr;
 	e->stream = nullptr;
@@ -3406,6 +3434,17 @@ extern "C" void mij_enc_destroy(mij_encoder *e)
 	free_dev(e->d_fgath);
 	free_host(e->h_fgwork);
 	free_dev(e->d_fgwork);
+	free_host(e->h_cslot);
+	free_dev(e->d_cslot);
+	free_host(e->h_cwork);
+	free_dev(e->d_cwork);
+	free_dev(e->d_sflag);
+	if (e->ev_coef)
+		(void)hipEventDestroy(e->ev_coef);
+	if (e->ev_conv0)
+		(void)hipEventDestroy(e->ev_conv0);
+	if (e->ev_conv1)
+		(void)hipEventDestroy(e->ev_conv1);
 	enc_free_emit(e);
 	if (e->ev_begin)
 		(void)hipEventDestroy(e->ev_begin);
@@ -3485,7 +3524,11 @@ static int enc_add_common(mij_encoder *e, const mjw_plan &plan, const void *pixe
 	memset(&s.cv, 0, sizeof(s.cv));
 	s.cv.dtype = MIJ_DT_U8;
 	s.pad_w = enc_padded_width(plan.width, plan.subsample);
-	s.pix_bytes = kind == ENC_UNITS ? 0 : align_up((size_t)s.pad_w * plan.height * 3, 256); /* staged as packed RGB whatever plan.comp is (enc_stage_rows) */
+	s.src = nullptr;
+	s.coef_fmt = 0;
+	memset(&s.tp, 0, sizeof(s.tp));
+	memset(&s.coef, 0, sizeof(s.coef));
+	s.pix_bytes = !enc_has_pixels(kind) ? 0 : align_up((size_t)s.pad_w * plan.height * 3, 256); /* staged as packed RGB whatever plan.comp is (enc_stage_rows) */
 	s.du_bytes = align_up(mjw_plan_du_count(&plan) * 128, 256);
 	if (e->pix_used + s.pix_bytes > e->pix_cap)
 		return set_err(MIJ_E_NOMEM, "pixel arena exhausted");
@@ -3602,8 +3645,8 @@ extern "C" int mij_enc_add_clone(mij_encoder *e, int src_slot)
 	if (!e || src_slot < 0 || src_slot >= (int)e->slots.size())
 		return set_err(MIJ_E_ARG, "bad source slot");
 	const int root = e->slots[(size_t)src_slot].clone_of >= 0 ? e->slots[(size_t)src_slot].clone_of : src_slot;
-	if (e->slots[(size_t)root].kind == ENC_UNITS)
-		return set_err(MIJ_E_ARG, "slot %d holds given data units, which have no pixels to clone", src_slot);
+	if (!enc_has_pixels(e->slots[(size_t)root].kind))
+		return set_err(MIJ_E_ARG, "slot %d holds given data units or coefficient planes, which have no pixels to clone", src_slot);
 	const mjw_plan plan = e->slots[(size_t)root].plan;
 	const int slot = enc_add_common(e, plan, nullptr, e->slots[(size_t)root].flip, root);
 	if (slot >= 0)
@@ -3814,13 +3857,16 @@ static int enc_emit_lists(mij_encoder *e)
 		rc = grow_dev(e->d_sent, e->sent_cap, n);
 	if (rc != MIJ_OK)
 		return rc;
-	std::vector<uint32_t> hdr_of(n);
+	std::vector<uint32_t> hdr_of(n), hlen_of(n, (uint32_t)MIJ_EMIT_HDR);
 	uint32_t t = 0, h = 0, k = 0, ot = 0;
 	e->opt_of.assign(n, -1);
 	for (size_t i = 0; i < n; ++i) {
 		const EncSlot &s = e->slots[i];
 		if (enc_own_header(e, s)) {
-			mjw_header(&s.plan, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
+			if (s.kind == ENC_COEF) /* shorter for a grey slot */
+				hlen_of[i] = (uint32_t)mjw_theader(&s.tp, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
+			else
+				mjw_header(&s.plan, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
 			hdr_of[i] = h++;
 		} else {
 			hdr_of[i] = hdr_of[(size_t)s.clone_of];
@@ -3832,8 +3878,9 @@ static int enc_emit_lists(mij_encoder *e)
 		es.first_tile = t;
 		es.n_tiles = (es.n_du + MIJ_EMIT_TILE - 1) / MIJ_EMIT_TILE;
 		es.hdr = hdr_of[i];
-		es.tab = es.pad = 0;
-		es.hlen = MIJ_EMIT_HDR;
+		es.tab = 0;
+		es.ny = s.kind == ENC_COEF ? (s.tp.ncomp == 1 ? 1u : (uint32_t)(s.tp.lh * s.tp.lv)) : (s.plan.subsample ? 4u : 1u);
+		es.hlen = hlen_of[i];
 		if (s.optimize) {
 			e->opt_of[i] = (int)k;
 			e->h_optslot[k] = (uint32_t)i;
@@ -3873,7 +3920,8 @@ static int enc_emit_launch(mij_encoder *e)
 	}
 	hipLaunchKernelGGL(k_emit_len, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_tbits);
 	hipLaunchKernelGGL(k_emit_scan, per_slot, block, 0, e->stream, e->d_eslot, n, e->d_tbits, e->d_tboff);
-	hipLaunchKernelGGL(k_emit_count, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_tbits, e->d_tboff, e->d_tff, e->d_tfrag);
+	hipLaunchKernelGGL(k_emit_count, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_tbits, e->d_tboff, e->d_tff, e->d_tfrag,
+							 e->has_coef ? e->d_sflag : nullptr);
 	hipLaunchKernelGGL(k_emit_stuff, per_slot, block, 0, e->stream, e->d_eslot, n, e->d_tbits, e->d_tboff, e->d_tff, e->d_tfrag, e->d_tout, e->d_sent);
 	hipLaunchKernelGGL(k_emit_place, dim3(1), dim3(1024), 0, e->stream, e->d_eslot, n, e->d_sent, (uint64_t)e->arena_cap, e->d_res);
 	hipLaunchKernelGGL(k_emit_write, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_hdr, e->d_tbits, e->d_tboff, e->d_tfrag,
@@ -3934,6 +3982,9 @@ extern "C" int mij_enc_fetch_streams(mij_encoder *e)
 		HIP_TRY(hipMemcpyAsync(e->h_arena, e->d_arena, used, hipMemcpyDeviceToHost, e->stream));
 		HIP_TRY(hipStreamSynchronize(e->stream));
 	}
+	e->sflag.assign(n, 0u);
+	if (e->has_coef)
+		HIP_TRY(hipMemcpy(e->sflag.data(), e->d_sflag, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
 	e->opt_ok.assign(e->n_opt, 0u);
 	if (e->n_opt)
 		HIP_TRY(hipMemcpy(e->opt_ok.data(), e->d_optok, sizeof(uint32_t) * e->n_opt, hipMemcpyDeviceToHost));
@@ -4051,6 +4102,179 @@ extern "C" int mij_enc_add_units(mij_encoder *e, int width, int height, int comp
 	return slot;
 }
 
+/* ---- coefficient slots (lossless transcode): a decode batch's planes become the slot's data units on the device */
+
+extern "C" int mij_enc_add_coef(mij_encoder *e, mij_batch *b, int slot)
+{
+	if (!e || !b)
+		return set_err(MIJ_E_ARG, "bad argument");
+	if (b->ctx != e->ctx)
+		return set_err(MIJ_E_ARG, "mij_enc_add_coef: the batch belongs to another context");
+	if (slot < 0 || slot >= (int)b->slots.size())
+		return set_err(MIJ_E_ARG, "mij_enc_add_coef: bad batch slot %d", slot);
+	const Slot &bs = b->slots[(size_t)slot];
+	if (bs.desc.flags & MIJ_FLAG_SKIP)
+		return set_err(MIJ_E_ARG, "mij_enc_add_coef: batch slot %d was rejected by the entropy stage", slot);
+	if (!b->uploaded)
+		return set_err(MIJ_E_ARG, "mij_enc_add_coef: the planes of batch slot %d are not in device memory yet (mij_batch_upload first)", slot);
+	mjw_tplan tp;
+	const char *why = nullptr;
+	if (!mjw_tplan_from_desc(&tp, &bs.desc, &why))
+		return set_err(MIJ_E_ARG, "not transcodable: %s", why ? why : "refused");
+	const size_t nu = mjw_tplan_du_count(&tp);
+	if (nu > UINT32_MAX / 64)
+		return set_err(MIJ_E_ARG, "not transcodable: too many data units");
+	const int es = enc_add_common(e, tp.plan, nullptr, 0, -1, ENC_COEF);
+	if (es < 0)
+		return es;
+	EncSlot &s = e->slots[(size_t)es];
+	s.tp = tp;
+	s.src = b;
+	s.coef_fmt = bs.coef_bytes_fmt ? 1 : 0;
+	for (int c = 0; c < tp.ncomp; ++c) {
+		s.coef.coef_off[c] = bs.dev.comp[c].coef_off;
+		s.coef.dc_off[c] = bs.dev.comp[c].dc_off;
+		s.coef.hi_off[c] = bs.dev.comp[c].hi_off;
+	}
+	s.coef.du_off = s.dev.du_off;
+	s.coef.mcu_x = (uint32_t)tp.plan.mcu_x;
+	s.coef.mcu_y = (uint32_t)tp.plan.mcu_y;
+	s.coef.lh = (uint32_t)tp.lh;
+	s.coef.lv = (uint32_t)tp.lv;
+	s.coef.ncomp = (uint32_t)tp.ncomp;
+	s.coef.dpm = (uint32_t)tp.plan.du_per_mcu;
+	s.coef.n_du = (uint32_t)nu;
+	s.coef.slot = (uint32_t)es;
+	return es;
+}
+
+extern "C" int mij_enc_tplan(const mij_encoder *e, int slot, mjw_tplan *out)
+{
+	if (!e || slot < 0 || slot >= (int)e->slots.size() || !out || e->slots[(size_t)slot].kind != ENC_COEF)
+		return set_err(MIJ_E_ARG, "bad slot, or not a coefficient slot");
+	*out = e->slots[(size_t)slot].tp;
+	return MIJ_OK;
+}
+
+extern "C" int mij_enc_slot_status(const mij_encoder *e, int slot)
+{
+	if (!e || slot < 0 || slot >= (int)e->slots.size())
+		return set_err(MIJ_E_ARG, "bad slot");
+	if (!e->streams_fetched)
+		return set_err(MIJ_E_STATE, "mij_enc_slot_status before mij_enc_fetch_streams");
+	if ((size_t)slot < e->sflag.size() && e->sflag[(size_t)slot]) {
+		set_err(MIJ_E_ARG, "slot %d: not codable: an AC coefficient outside -1023..1023 or a DC difference outside -2047..2047", slot);
+		return MIJ_ENC_SLOT_UNCODABLE;
+	}
+	if (e->h_res[slot].off == ~0ull) {
+		set_err(MIJ_E_NOMEM, "slot %d did not fit in the emission arena (needs %llu bytes)", slot, (unsigned long long)e->h_res[slot].len);
+		return MIJ_ENC_SLOT_NO_ROOM;
+	}
+	return MIJ_ENC_SLOT_OK;
+}
+
+extern "C" int mij_enc_coef_ms(mij_encoder *e, float *ms)
+{
+	if (!e || !ms)
+		return set_err(MIJ_E_ARG, "bad argument");
+	*ms = -1.0f;
+	if (!e->conv_timed)
+		return MIJ_OK;
+	HIP_TRY(hipEventSynchronize(e->ev_conv1));
+	HIP_TRY(hipEventElapsedTime(ms, e->ev_conv0, e->ev_conv1));
+	return MIJ_OK;
+}
+
+/* The conversion kernel of the coefficient slots, queued at upload in place of a copy of units: behind an event on every source
+ * batch's stream, one launch per (batch, plane format) over a list of plane tiles.  The flags are cleared whenever the emission may
+ * read them. */
+static int enc_coef_convert(mij_encoder *e)
+{
+	const size_t n = e->slots.size();
+	size_t nc = 0, nw = 0;
+	for (const EncSlot &s : e->slots)
+		if (s.kind == ENC_COEF) {
+			++nc;
+			nw += ((size_t)s.coef.mcu_x * s.coef.mcu_y * s.coef.lh * s.coef.lv + 63) / 64 + (s.coef.ncomp == 3 ? 2 * (((size_t)s.coef.mcu_x * s.coef.mcu_y + 63) / 64) : 0);
+		}
+	e->has_coef = nc != 0;
+	e->conv_timed = false;
+	if (!nc)
+		return MIJ_OK;
+	if (nw > UINT32_MAX)
+		return set_err(MIJ_E_ARG, "too many plane tiles to convert in one launch");
+	if (nc > e->cslot_cap || nw > e->cwork_cap || n > e->sflag_cap)
+		HIP_TRY(hipStreamSynchronize(e->stream));
+	int rc = grow_pair(e->h_cslot, e->d_cslot, e->cslot_cap, nc);
+	if (rc == MIJ_OK)
+		rc = grow_pair(e->h_cwork, e->d_cwork, e->cwork_cap, nw);
+	if (rc == MIJ_OK)
+		rc = grow_dev(e->d_sflag, e->sflag_cap, n);
+	if (rc != MIJ_OK)
+		return rc;
+	if (!e->ev_coef) {
+		HIP_TRY(hipEventCreateWithFlags(&e->ev_coef, hipEventDisableTiming));
+		HIP_TRY(hipEventCreate(&e->ev_conv0));
+		HIP_TRY(hipEventCreate(&e->ev_conv1));
+	}
+	/* groups: slots of one batch and one plane format are contiguous in the lists */
+	struct Group {
+		mij_batch *b;
+		int fmt;
+		size_t first, count;
+	};
+	std::vector<Group> groups;
+	std::vector<mij_batch *> batches;
+	for (const EncSlot &s : e->slots)
+		if (s.kind == ENC_COEF) {
+			bool seen = false;
+			for (const Group &g : groups)
+				seen = seen || (g.b == s.src && g.fmt == s.coef_fmt);
+			if (!seen)
+				groups.push_back(Group{s.src, s.coef_fmt, 0, 0});
+			if (std::find(batches.begin(), batches.end(), s.src) == batches.end())
+				batches.push_back(s.src);
+		}
+	size_t k = 0, w = 0;
+	for (Group &g : groups) {
+		g.first = w;
+		for (const EncSlot &s : e->slots) {
+			if (s.kind != ENC_COEF || s.src != g.b || s.coef_fmt != g.fmt)
+				continue;
+			e->h_cslot[k] = s.coef;
+			for (uint32_t c = 0; c < s.coef.ncomp; ++c) {
+				const size_t nblk = (size_t)s.coef.mcu_x * s.coef.mcu_y * (c ? 1u : s.coef.lh * s.coef.lv);
+				for (size_t t = 0; t < (nblk + 63) / 64; ++t)
+					e->h_cwork[w++] = WorkIdct{(uint32_t)k, c, (uint32_t)t, 0u};
+			}
+			++k;
+		}
+		g.count = w - g.first;
+	}
+	HIP_TRY(hipMemcpyAsync(e->d_cslot, e->h_cslot, sizeof(CoefSlot) * nc, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->d_cwork, e->h_cwork, sizeof(WorkIdct) * nw, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemsetAsync(e->d_sflag, 0, sizeof(uint32_t) * n, e->stream));
+	for (mij_batch *b : batches) { /* whatever the batch's stream still does to the planes comes first */
+		HIP_TRY(hipEventRecord(e->ev_coef, b->stream));
+		HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_coef, 0));
+	}
+	HIP_TRY(hipEventRecord(e->ev_conv0, e->stream));
+	for (const Group &g : groups) {
+		if (!g.count)
+			continue;
+		const dim3 grid((unsigned)g.count), block(64);
+		uint8_t *du = reinterpret_cast<uint8_t *>(e->d_du);
+		if (g.fmt)
+			hipLaunchKernelGGL(k_coef_units<1>, grid, block, 0, e->stream, e->d_cslot, e->d_cwork + g.first, g.b->d_coef, du, e->d_sflag);
+		else
+			hipLaunchKernelGGL(k_coef_units<0>, grid, block, 0, e->stream, e->d_cslot, e->d_cwork + g.first, g.b->d_coef, du, e->d_sflag);
+		HIP_TRY(hipGetLastError());
+	}
+	HIP_TRY(hipEventRecord(e->ev_conv1, e->stream));
+	e->conv_timed = true;
+	return MIJ_OK;
+}
+
 extern "C" int mij_enc_upload(mij_encoder *e)
 {
 	if (!e)
@@ -4066,7 +4290,7 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 		const int sub = s.plan.subsample ? 1 : 0;
 		const uint32_t ny = nm * (sub ? 4u : 1u), nc = nm * 2u;
 		e->h_imgs[i] = s.dev;
-		if (s.kind == ENC_UNITS) /* given units: nothing to transform */
+		if (!enc_has_pixels(s.kind)) /* given units, or units made from coefficient planes: nothing to transform */
 			continue;
 		/* strips of 32 MCUs through the fused kernel: whole 16-pixel columns, packed RGB, 16-byte aligned rows (every width: enc_padded_width) */
 		if (sub && !e->force_generic) { /* every comp: the staging is packed RGB */
@@ -4120,6 +4344,8 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 	rc = enc_gather(e); /* device-pixel slots, before the clones copy them */
 	if (rc == MIJ_OK)
 		rc = enc_gather_float(e);
+	if (rc == MIJ_OK)
+		rc = enc_coef_convert(e);
 	if (rc != MIJ_OK)
 		return rc;
 	for (size_t i = 0; i < n; ++i) {

@@ -1,0 +1,272 @@
+/*
+ * transcode_host.c -- the host half of the lossless transcode (include/mij_host.h, mjw_tplan): which sources are transcodable, the
+ * coefficient planes read as the writer's data units, the marker copy, and the whole path on the host (mjh_transcode_memory).  The
+ * emission itself is the writer's (jpeg_write_host.c: mjw_temit).
+ */
+#include <stdlib.h>
+#include <string.h>
+
+#include "mij_host.h"
+
+/* natural index -> zigzag position (codec/jpeg_write.c:1-2) */
+static const unsigned char k_zigzag_of[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30,
+															 41, 43, 9,  11, 18, 24, 31, 40, 44, 53, 10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38,
+															 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
+
+static int refuse(const char **reason, const char *why)
+{
+	if (reason)
+		*reason = why;
+	return 0;
+}
+
+int mjw_tplan_from_desc(mjw_tplan *t, const mij_image_desc *d, const char **reason)
+{
+	int c, i;
+	if (!t || !d)
+		return refuse(reason, "bad argument");
+	if (d->width <= 0 || d->height <= 0 || d->width > 65535 || d->height > 65535 || d->mcu_x <= 0 || d->mcu_y <= 0)
+		return refuse(reason, "bad picture size");
+	if (d->ncomp == 4)
+		return refuse(reason, "four-component (CMYK / YCCK) source");
+	if (d->ncomp != 1 && d->ncomp != 3)
+		return refuse(reason, "component count not 1 or 3");
+	if (d->ncomp == 3 && d->color == MIJ_COLOR_RGB)
+		return refuse(reason, "RGB-tagged source");
+	if (d->ncomp == 3 && d->color != MIJ_COLOR_YCBCR)
+		return refuse(reason, "colour mode is not YCbCr");
+	for (c = 1; c < d->ncomp; ++c)
+		if (d->comp[c].h != 1 || d->comp[c].v != 1)
+			return refuse(reason, "chroma sampling factors other than 1x1");
+	if (d->ncomp == 1 && (d->comp[0].h != 1 || d->comp[0].v != 1))
+		return refuse(reason, "grey sampling factors other than 1x1");
+	if (d->comp[0].h < 1 || d->comp[0].h > 2 || d->comp[0].v < 1 || d->comp[0].v > 2)
+		return refuse(reason, "luma sampling factors beyond 2x2 (4:1:1 and the like)");
+	for (c = 0; c < d->ncomp; ++c) {
+		if (d->comp[c].tq < 0 || d->comp[c].tq > 3)
+			return refuse(reason, "bad quantisation table index");
+		if (d->comp[c].bw != d->mcu_x * d->comp[c].h || d->comp[c].bh != d->mcu_y * d->comp[c].v)
+			return refuse(reason, "block grid does not match the MCU grid");
+		for (i = 0; i < 64; ++i)
+			if (d->dequant[d->comp[c].tq][i] > 255 || d->dequant[d->comp[c].tq][i] < 1)
+				return refuse(reason, "a quantisation table entry outside 1..255 (16-bit tables are not written)");
+	}
+	if (d->ncomp == 3 && memcmp(d->dequant[d->comp[1].tq], d->dequant[d->comp[2].tq], sizeof(d->dequant[0])))
+		return refuse(reason, "Cb and Cr use different quantisation tables");
+	memset(t, 0, sizeof(*t));
+	t->ncomp = d->ncomp;
+	t->lh = d->comp[0].h;
+	t->lv = d->comp[0].v;
+	t->plan.width = d->width;
+	t->plan.height = d->height;
+	t->plan.comp = d->ncomp;
+	t->plan.subsample = t->lh == 2 && t->lv == 2;
+	t->plan.mcu_x = d->mcu_x;
+	t->plan.mcu_y = d->mcu_y;
+	t->plan.du_per_mcu = d->ncomp == 1 ? 1 : t->lh * t->lv + 2;
+	for (i = 0; i < 64; ++i) {
+		t->plan.ytab[k_zigzag_of[i]] = (unsigned char)d->dequant[d->comp[0].tq][i];
+		t->plan.ctab[k_zigzag_of[i]] = (unsigned char)d->dequant[d->comp[d->ncomp == 3 ? 1 : 0].tq][i];
+	}
+	if ((size_t)d->mcu_x * (size_t)d->mcu_y > ((size_t)1 << 26))
+		return refuse(reason, "too many MCUs");
+	return 1;
+}
+
+/* coefficient at in-block position P of block L of a component, in either plane format */
+typedef struct {
+	const int16_t *plane;               /* int16 tile layout */
+	const uint8_t *lo, *hi, *dc;        /* compact planes */
+} comp_src;
+
+static void read_block(const comp_src *s, int compact, size_t L, int16_t *du)
+{
+	int k;
+	if (!compact) {
+		for (k = 0; k < 64; ++k)
+			du[k] = s->plane[mij_coef_index((uint32_t)L, mij_zigzag_pos[k])];
+		return;
+	}
+	{
+		const uint8_t *blo = s->lo + ((L >> 6) << 12) + ((L & 63) << 3);
+		const int esc = blo[0] & 1;
+		uint16_t dcv;
+		for (k = 1; k < 64; ++k) {
+			const int P = mij_zigzag_pos[k];
+			int v = (int8_t)blo[((size_t)(P >> 3) << 9) + (P & 7)];
+			if (esc)
+				v += 256 * (int)(int8_t)s->hi[(L << 6) + (size_t)P];
+			du[k] = (int16_t)v;
+		}
+		memcpy(&dcv, s->dc + 2 * L, 2);
+		du[0] = (int16_t)dcv;
+	}
+}
+
+int mjw_units_from_region(const mij_image_desc *d, const uint8_t *region, int format, int16_t *du)
+{
+	mjw_tplan t;
+	comp_src src[3];
+	size_t off = 0;
+	int c, mx, my, sx, sy;
+	if (!region || !du || (format != MIJ_COEF_INT16 && format != MIJ_COEF_COMPACT) || !mjw_tplan_from_desc(&t, d, NULL))
+		return 0;
+	for (c = 0; c < d->ncomp; ++c) {
+		memset(&src[c], 0, sizeof(src[c]));
+		if (format == MIJ_COEF_COMPACT) {
+			size_t lo, dc, hi;
+			mij_compact_offsets(d, c, &lo, &dc, &hi);
+			src[c].lo = region + lo;
+			src[c].dc = region + dc;
+			src[c].hi = region + hi;
+		} else {
+			src[c].plane = (const int16_t *)(const void *)(region + off);
+			off += mij_plane_elems((uint32_t)(d->comp[c].bw * d->comp[c].bh)) * sizeof(int16_t);
+		}
+	}
+	for (my = 0; my < d->mcu_y; ++my)
+		for (mx = 0; mx < d->mcu_x; ++mx)
+			for (c = 0; c < d->ncomp; ++c) {
+				const mij_comp_desc *cp = &d->comp[c];
+				for (sy = 0; sy < cp->v; ++sy)
+					for (sx = 0; sx < cp->h; ++sx, du += 64)
+						read_block(&src[c], format == MIJ_COEF_COMPACT, (size_t)(mx * cp->h + sx) + (size_t)(my * cp->v + sy) * (size_t)cp->bw, du);
+			}
+	return 1;
+}
+
+int mjw_copy_markers(const uint8_t *src, int src_len, const unsigned char *stream, size_t stream_len, unsigned char **out, size_t *out_len,
+                     const char **reason)
+{
+	static const size_t own = 18; /* the writer's APP0 behind SOI */
+	size_t copy = 0, o;
+	int i, pass, has_own = 0;
+	unsigned char *dst = NULL;
+	if (!out || !out_len)
+		return refuse(reason, "bad argument");
+	*out = NULL;
+	*out_len = 0;
+	if (!src || src_len < 4 || src[0] != 0xFF || src[1] != 0xD8)
+		return refuse(reason, "source has no SOI");
+	if (!stream || stream_len < 2 + own || stream[2] != 0xFF || stream[3] != 0xE0)
+		return refuse(reason, "stream does not start with SOI and APP0");
+	for (pass = 0; pass < 2; ++pass) { /* measure, then copy */
+		o = 2;
+		if (pass) {
+			dst = (unsigned char *)malloc(stream_len + copy);
+			if (!dst)
+				return refuse(reason, "out of memory");
+			dst[0] = 0xFF;
+			dst[1] = 0xD8;
+			if (!has_own) {
+				memcpy(dst + o, stream + 2, own);
+				o += own;
+			}
+		}
+		for (i = 2;;) {
+			int m, n;
+			if (i + 2 > src_len)
+				return free(dst), refuse(reason, "source ends before its first SOS");
+			if (src[i] != 0xFF)
+				return free(dst), refuse(reason, "source has bytes that are no marker in front of its first SOS");
+			m = src[i + 1];
+			if (m == 0xFF) { /* fill byte */
+				++i;
+				continue;
+			}
+			if (m == 0xDA)
+				break;
+			if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) {
+				i += 2;
+				continue;
+			}
+			if (m == 0xD9 || m == 0x00)
+				return free(dst), refuse(reason, "source ends before its first SOS");
+			if (i + 4 > src_len)
+				return free(dst), refuse(reason, "a segment length is cut off");
+			n = (src[i + 2] << 8) | src[i + 3];
+			if (n < 2 || i + 2 + n > src_len)
+				return free(dst), refuse(reason, "a segment length runs past the end of the source");
+			if ((m >= 0xE0 && m <= 0xEF) || m == 0xFE) {
+				if (!pass) {
+					copy += (size_t)n + 2;
+					if ((m == 0xE0 && n >= 7 && !memcmp(src + i + 4, "JFIF", 5)) || (m == 0xEE && n >= 7 && !memcmp(src + i + 4, "Adobe", 5)))
+						has_own = 1;
+				} else {
+					memcpy(dst + o, src + i, (size_t)n + 2);
+					o += (size_t)n + 2;
+				}
+			}
+			i += 2 + n;
+		}
+	}
+	memcpy(dst + o, stream + 2 + own, stream_len - 2 - own);
+	o += stream_len - 2 - own;
+	*out = dst;
+	*out_len = o;
+	return 1;
+}
+
+int mjh_transcode_memory(const uint8_t *src, int len, unsigned flags, unsigned char **out, size_t *out_len, const char **reason)
+{
+	mij_image_desc d;
+	mjw_tplan t;
+	const char *why = NULL;
+	uint8_t *region = NULL;
+	int16_t *du = NULL;
+	unsigned char *buf = NULL;
+	size_t rbytes, nu, cap, n = 0;
+	int ok = 0;
+	if (!out || !out_len)
+		return refuse(reason, "bad argument");
+	*out = NULL;
+	*out_len = 0;
+	if (!src || len <= 0)
+		return refuse(reason, "bad argument");
+	if (flags & ~(MJW_OPTIMIZE_HUFFMAN | MJW_COPY_MARKERS))
+		return refuse(reason, "unknown flag");
+	if (!mjh_probe_memory(src, len, 0, &d, &why))
+		return refuse(reason, why ? why : "decode failed");
+	rbytes = mij_image_region_bytes(&d);
+	region = (uint8_t *)malloc(rbytes ? rbytes : 1);
+	if (!region)
+		return refuse(reason, "out of memory");
+	if (!mjh_decode_memory_fmt(src, len, 0, &d, region, rbytes, 0, &why)) {
+		refuse(reason, why ? why : "decode failed");
+		goto done;
+	}
+	if (!mjw_tplan_from_desc(&t, &d, reason))
+		goto done;
+	nu = mjw_tplan_du_count(&t);
+	du = (int16_t *)malloc(nu * 64 * sizeof(int16_t));
+	cap = 1024 + nu * 128;
+	buf = (unsigned char *)malloc(cap);
+	if (!du || !buf) {
+		refuse(reason, "out of memory");
+		goto done;
+	}
+	if (!mjw_units_from_region(&d, region, (d.flags & MIJ_FLAG_STAGED_COMPACT) ? MIJ_COEF_COMPACT : MIJ_COEF_INT16, du)) {
+		refuse(reason, "units could not be read");
+		goto done;
+	}
+	if (!mjw_tunits_codable(&t, du, reason))
+		goto done;
+	n = mjw_temit_to_memory(&t, du, flags & MJW_OPTIMIZE_HUFFMAN, buf, cap);
+	if (!n) {
+		refuse(reason, "emission failed");
+		goto done;
+	}
+	if (flags & MJW_COPY_MARKERS) {
+		ok = mjw_copy_markers(src, len, buf, n, out, out_len, reason);
+	} else {
+		*out = buf;
+		*out_len = n;
+		buf = NULL;
+		ok = 1;
+	}
+done:
+	free(region);
+	free(du);
+	free(buf);
+	return ok;
+}

@@ -1,0 +1,221 @@
+"""Lossless JPEG transcode on the GPU: jpegtran -optimize for a batch.  The decode front end (Huffman walk on the GPU where it applies,
+host walk otherwise) leaves every picture's quantised coefficients in device memory; a conversion kernel re-orders them into the writer's
+data units (mij_enc_add_coef) and the emission kernels write the new streams, with Huffman tables built on the GPU from each picture's own
+statistics.  The same coefficients, to the bit, in a smaller file: no IDCT, no pixels, no generation loss, and only finished streams
+cross PCIe on the way back.  No pixel kernel is launched.
+
+This module needs no torch."""
+from .binding import Batch, Context, Encoder, HostDecoder, MijError, copy_markers as _copy_markers, emit_transcoded, transcode_plan
+
+# one launch takes at most this many pictures / bytes of coefficient arena; larger calls are cut into chunks
+MAX_SLOTS = 4096
+MAX_COEF_BYTES = 2 << 30
+
+
+def _align(v, a):
+    return (v + a - 1) // a * a
+
+
+class Transcoder:
+    """transcode(datas) -> one new JPEG stream per source, or None where the source cannot be transcoded (last_reasons says why).
+
+    Owns a Context, a Batch and an Encoder with its emission arena, grown as needed and reused across calls.  Synchronous.  Sources that
+    are transcodable: grey, and YCbCr (JFIF or Adobe transform 1) as 4:4:4, 4:2:2, 4:4:0 or 4:2:0, baseline or progressive, with or without
+    restart intervals, whose quantisation tables hold 8-bit entries and are the same for Cb and Cr.  The output is always a baseline stream
+    without restart intervals (include/mij_host.h, mjw_tplan, has the whole contract).  Slots whose streams do not fit the arena are
+    finished on the host from their units (last_host_emitted counts them) and the arena grows for the next call."""
+
+    def __init__(self, device=None):
+        if device is not None and (isinstance(device, bool) or not isinstance(device, int) or device < 0):
+            raise ValueError("device must be None (the current device) or a device index, got %r" % (device,))
+        self._device = -1 if device is None else device
+        self._ctx = None
+        self._batch = None
+        self._enc = None
+        self._bcap = (0, 0, 0, 0)
+        self._ecap = (0, 0)
+        self._arena = 0
+        self._fmt = "compact"
+        self.last_reasons = []
+        self.last_host_emitted = 0
+        self.last_timing = {}
+
+    @property
+    def arena_bytes(self):
+        return self._arena
+
+    def close(self):
+        for name in ("_enc", "_batch", "_ctx"):
+            h = getattr(self, name)
+            if h is not None:
+                h.close()
+                setattr(self, name, None)
+        self._bcap, self._ecap, self._arena = (0, 0, 0, 0), (0, 0), 0
+
+    def reserve_arena(self, nbytes):
+        """Sets the emission arena's size for the next call (tests and measurements; transcode() sizes it by itself)."""
+        self._arena = max(0, int(nbytes))
+        if self._enc is not None:
+            self._enc.stream_reserve(self._arena)
+
+    def set_coef_format(self, fmt):
+        """'compact' (default) or 'int16': the format the coefficient planes get in device memory (tests)."""
+        if fmt not in ("compact", "int16"):
+            raise ValueError("coefficient format must be 'compact' or 'int16'")
+        self._fmt = fmt
+        if self._batch is not None:
+            self._batch.set_coef_format(fmt)
+
+    def _batch_for(self, n, coef, out, stream):
+        need = (max(1, n), max(coef, 256), max(out, 256), stream)
+        if self._batch is None or any(a > b for a, b in zip(need, self._bcap)):
+            if self._batch is not None:
+                self._batch.close()
+                self._batch = None
+            if self._ctx is None:
+                self._ctx = Context(self._device)
+            cap = tuple(max(a, b) for a, b in zip(need, self._bcap))
+            self._batch = Batch(self._ctx, cap[0], cap[1], cap[1], cap[2])
+            self._batch.set_coef_format(self._fmt)
+            if cap[3]:
+                self._batch.entropy_reserve(cap[3])
+            self._bcap = cap
+        else:
+            self._batch.reset()
+        return self._batch
+
+    def _encoder_for(self, n, du):
+        need = (max(1, n), max(du, 256))
+        if self._enc is None or any(a > b for a, b in zip(need, self._ecap)):
+            if self._enc is not None:
+                self._enc.close()
+                self._enc = None
+            cap = tuple(max(a, b) for a, b in zip(need, self._ecap))
+            self._enc = Encoder(self._ctx, cap[0], 0, cap[1], stage_bytes=0)
+            self._ecap = cap
+            if self._arena:
+                self._enc.stream_reserve(self._arena)
+        else:
+            self._enc.reset()
+        return self._enc
+
+    def transcode(self, datas, *, optimize=True, copy_markers="all", only_if_smaller=False, gpu_entropy=None, threads=16):
+        """datas: a sequence of JPEG files as bytes.  -> a list with, per source, the new stream (bytes) or None; last_reasons[i] is None
+        or the reason source i was refused or could not be decoded.
+        optimize: Huffman tables built from each picture's own statistics (mjw_temit_optimized's stream); False: the Annex-K tables.
+        copy_markers: "all" puts the source's APPn and COM segments (those before its first SOS, in source order) directly behind SOI,
+        the writer's own JFIF APP0 being dropped when the source carries a JFIF APP0 or an Adobe APP14; "none" leaves the stream as
+        emitted.  Offsets inside copied segments (MPF and the like) are not fixed up.
+        only_if_smaller: the source's own bytes are returned where the result is not shorter.
+        gpu_entropy: the front end, as Batch.decode_jpegs takes it (None: the default; True / False: GPU walk where it applies / host).
+        ValueError, before a device is touched, for arguments that are not of these kinds."""
+        if not isinstance(optimize, bool) or not isinstance(only_if_smaller, bool):
+            raise ValueError("optimize and only_if_smaller must be bools")
+        if copy_markers not in ("all", "none"):
+            raise ValueError("copy_markers must be 'all' or 'none', got %r" % (copy_markers,))
+        if gpu_entropy not in (None, True, False):
+            raise ValueError("gpu_entropy must be None, True or False")
+        if isinstance(threads, bool) or not isinstance(threads, int) or threads < 1:
+            raise ValueError("threads must be a positive int")
+        if isinstance(datas, (bytes, bytearray, memoryview, str)):
+            raise ValueError("datas is a sequence of JPEG files, not one file")
+        datas = list(datas)
+        for i, d in enumerate(datas):
+            if not isinstance(d, (bytes, bytearray, memoryview)):
+                raise ValueError("source %d is not bytes" % i)
+        datas = [bytes(d) for d in datas]
+        out = [None] * len(datas)
+        reasons = [None] * len(datas)
+        self.last_host_emitted = 0
+        self.last_timing = {"convert_ms": 0.0, "emit_ms": 0.0}
+        # headers first: sizes for the arenas, and the pictures no front end would take
+        todo = []
+        for i, d in enumerate(datas):
+            try:
+                desc = HostDecoder.probe(d, 0)
+            except MijError as e:
+                reasons[i] = str(e)
+                continue
+            # what the frame header settles -- component count and sampling -- is refused here; colour and tables may still change behind
+            # it, so those are judged on the walked picture's descriptor (mij_enc_add_coef)
+            c0 = desc.comp[0]
+            if desc.ncomp not in (1, 3) or not (1 <= c0.h <= 2 and 1 <= c0.v <= 2) or (desc.ncomp == 1 and (c0.h, c0.v) != (1, 1)) or \
+                    any((desc.comp[c].h, desc.comp[c].v) != (1, 1) for c in range(1, desc.ncomp)):
+                reasons[i] = "not transcodable: " + (transcode_plan(desc)[1] or "refused")
+                continue
+            du = sum(desc.comp[c].bw * desc.comp[c].bh for c in range(desc.ncomp)) * 128
+            todo.append((i, Batch.coef_bytes(desc), Batch.out_bytes(desc), _align(du, 256), desc.width * desc.height))
+        k = 0
+        while k < len(todo):
+            j, coef = k, 0
+            while j < len(todo) and j - k < MAX_SLOTS and (j == k or coef + todo[j][1] <= MAX_COEF_BYTES):
+                coef += todo[j][1]
+                j += 1
+            self._chunk(datas, todo[k:j], out, reasons, optimize, gpu_entropy, threads)
+            k = j
+        for i, d in enumerate(datas):
+            if out[i] is None:
+                continue
+            if copy_markers == "all":
+                out[i], why = _copy_markers(d, out[i])
+                if out[i] is None:
+                    reasons[i] = "markers: " + why
+                    continue
+            if only_if_smaller and len(out[i]) >= len(d):
+                out[i] = d
+        self.last_reasons = reasons
+        return out
+
+    def _chunk(self, datas, items, out, reasons, optimize, gpu_entropy, threads):
+        n = len(items)
+        srcs = [datas[it[0]] for it in items]
+        stream = 0
+        if gpu_entropy:  # mjh_decode_batch_gpu wants its arena reserved; the default front end makes its own
+            stream = _align(sum(len(s) + 4096 for s in srcs), 1 << 20)
+        b = self._batch_for(n, sum(it[1] for it in items), sum(it[2] for it in items), stream)
+        _, slots, why = b.decode_jpegs(srcs, 0, threads=threads, gpu_entropy=gpu_entropy)
+        if not any(sl >= 0 for sl in slots):
+            for it, r in zip(items, why):
+                reasons[it[0]] = r or "decode failed"
+            return
+        b.upload()  # the coefficient planes into device memory (pack where needed); no pixel kernel runs
+        if not self._arena:  # a first guess, about half a byte per pixel; misses grow it
+            self._arena = _align(sum(1024 + it[4] // 2 for it in items), 1 << 20)
+        enc = self._encoder_for(n, sum(it[3] for it in items))
+        es = {}
+        for it, sl, r in zip(items, slots, why):
+            if sl < 0:
+                reasons[it[0]] = r or "decode failed"
+                continue
+            try:
+                es[it[0]] = enc.add_coef(b, sl)
+            except MijError as e:
+                reasons[it[0]] = str(e).split(": ", 1)[-1]
+                continue
+            if optimize:
+                enc.set_optimize(es[it[0]])
+        if not es:
+            b.wait()
+            return
+        enc.upload()
+        enc.timer_begin()
+        enc.launch()
+        enc.timer_end()
+        enc.fetch_streams()
+        self.last_timing["convert_ms"] += enc.coef_ms() or 0.0
+        self.last_timing["emit_ms"] += enc.timer_ms()
+        need, host = 0, 0
+        for i, slot in es.items():
+            data, ln = enc.stream(slot)
+            if data is None:
+                if enc.slot_status(slot) == "uncodable":
+                    reasons[i] = "not codable: an AC coefficient outside -1023..1023 or a DC difference outside -2047..2047"
+                    continue
+                data = emit_transcoded(enc.tplan(slot), enc.fetch(slot), optimize)  # its units are on the device: the host finishes it
+                host += 1
+            need += ln
+            out[i] = data
+        self.last_host_emitted += host
+        if host:
+            self._arena = _align(need + need // 8, 1 << 20)
+            enc.stream_reserve(self._arena)

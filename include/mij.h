@@ -674,6 +674,35 @@ int mij_enc_add_units(mij_encoder *e, int width, int height, int comp, int quali
 int mij_enc_set_optimize(mij_encoder *e, int slot, int on);
 int mij_enc_slot_optimized(const mij_encoder *e, int slot);
 
+/*
+ * Lossless transcode: an encoder slot whose data units are the QUANTISED coefficients of a decode batch's slot, taken from the batch's
+ * coefficient planes in device memory -- a new slot kind beside given units.  The contract (which sources are transcodable, the unit
+ * order, the stream) is written in mij_host.h (mjw_tplan); the slot's stream is what mjw_temit / mjw_temit_optimized write for
+ * mjw_units_from_region of the slot's planes.
+ *
+ * mij_enc_add_coef: takes the batch slot's descriptor as it stands and makes the transcode plan.  MIJ_E_ARG, with the reason in
+ * mij_last_error ("not transcodable: ..."), for a picture that is not transcodable, a slot flagged MIJ_FLAG_SKIP, a batch of another
+ * context, and a batch that has not been uploaded since the slot was added (its planes are not in HBM yet: mij_batch_upload, which
+ * launches no pixel kernel).  Reserves room in the unit arena (MIJ_E_NOMEM).  At mij_enc_upload a conversion kernel (k_coef_units: planes
+ * to units, either plane format) is queued on the encoder's stream in place of a copy of units, behind an event recorded on the batch's
+ * stream; the same pass decides whether the units are codable (AC in -1023..1023, DC differences in -2047..2047).  A slot that is not
+ * is reported like one that does not fit the arena (mij_enc_stream: NULL, length 0) and is never packed by the emission kernels.
+ * mij_enc_set_optimize, mij_enc_stream_reserve, mij_enc_fetch_streams, mij_enc_stream and mij_enc_fetch work on such a slot unchanged;
+ * mij_enc_add_clone refuses it; mij_enc_plan gives its geometry only (use mij_enc_tplan, mij_host.h, and mjw_temit for its units).
+ *
+ * ORDERING: the batch's planes are read on the encoder's stream from mij_enc_upload until mij_enc_wait (or a fetch that waits).  The batch
+ * must not be reset, uploaded again, walked again or destroyed until then.
+ *
+ * mij_enc_slot_status: after mij_enc_fetch_streams (MIJ_E_STATE before), for a slot of any kind: MIJ_ENC_SLOT_OK, MIJ_ENC_SLOT_NO_ROOM
+ * (it did not fit the arena: finish it on the host from its units) or MIJ_ENC_SLOT_UNCODABLE (never for slots that are not coefficient
+ * slots); mij_last_error says the same in words.
+ * mij_enc_coef_ms: measurement: milliseconds the conversion kernels of the last mij_enc_upload took, -1 when there were none.
+ */
+enum { MIJ_ENC_SLOT_OK = 0, MIJ_ENC_SLOT_NO_ROOM = 1, MIJ_ENC_SLOT_UNCODABLE = 2 };
+int mij_enc_add_coef(mij_encoder *e, mij_batch *b, int slot);
+int mij_enc_slot_status(const mij_encoder *e, int slot);
+int mij_enc_coef_ms(mij_encoder *e, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -181,6 +181,63 @@ int mij_write_jpg_to_func_ex(mjw_write_func *func, void *context, int x, int y, 
 int mij_write_jpg_batch_ex(const void *const *pixels, const int *x, const int *y, const int *comp, int n, int quality, int threads,
                            unsigned char **out, size_t *out_len, unsigned flags);
 
+/*
+ * Lossless transcode: a decoded picture's QUANTISED coefficients written out again as a new baseline stream -- the same coefficients to
+ * the bit, no IDCT, no pixels, no generation loss (jpegtran -optimize).  On the GPU: mij_enc_add_coef (mij.h); these calls are the written
+ * contract, the fallback for slots that do not fit the emission arena, and what the CPU tests pin.
+ *
+ * A source is TRANSCODABLE when its descriptor says: one component at 1x1, or three-component YCbCr (MIJ_COLOR_YCBCR: JFIF, or Adobe
+ * transform 1) with chroma at 1x1 and luma (h, v) one of (1,1) (2,1) (1,2) (2,2); every dequant entry of the tables in use <= 255; Cb and
+ * Cr tables of equal contents.  Its units are CODABLE when every AC value lies in -1023..1023 and every DC difference (against the previous
+ * unit of the same component in MCU order, from 0) in -2047..2047: mij_enc_add_units' ranges.
+ *
+ * Units: int16[64] each in zigzag order, MCU after MCU in raster MCU order; inside an MCU the luma blocks in raster order (h across, v down),
+ * then Cb, then Cr -- 4:2:2 is Y0 Y1 Cb Cr, 4:4:0 is Ytop Ybottom Cb Cr, grey is one unit per MCU.  The block of component c at MCU (mx, my),
+ * sub-block (sx, sy) is plane block L = (mx*h_c + sx) + (my*v_c + sy)*bw_c, and unit coefficient k is plane position mij_zigzag_pos[k].
+ * Blocks a non-interleaved scan never coded are what the planes hold (zeros) and are emitted like any other.
+ *
+ * Stream: SOI, the writer's JFIF APP0, DQT with the SOURCE's tables in zigzag order (luma as id 0, chroma as id 1), SOF0 with the source's
+ * size and sampling, DHT, SOS and the entropy-coded segment exactly as mjw_emit / mjw_emit_optimized code units; no DRI.  For 4:4:4 and 4:2:0
+ * the header is mjw_header's (mjw_header_optimized's) byte for byte given those tables, for 4:2:2 and 4:4:0 only the luma sampling byte
+ * differs; a grey stream has a one-component SOF0 and SOS, one DQT table and only the luma DC and AC tables in its DHT.  At most
+ * MJW_HEADER_BYTES.
+ *
+ *   mjw_tplan_from_desc    the plan of a descriptor, or 0 with *reason (a static string) when the source is not transcodable.  plan.ytab /
+ *                          plan.ctab are the source's tables, plan.du_per_mcu the units per MCU (1, 3, 4 or 6), plan.comp = ncomp,
+ *                          plan.subsample 1 for 4:2:0 only; the reciprocal tables are zero (nothing is transformed).
+ *   mjw_units_from_region  the units of an image's coefficient region (mjh_decode_memory_fmt, mij_batch_stage_region) in format
+ *                          MIJ_COEF_INT16 or MIJ_COEF_COMPACT; 0 when the descriptor is not transcodable.
+ *   mjw_tunits_codable     1, or 0 with *reason (may be NULL)
+ *   mjw_temit[_optimized]  the stream of the units; 0 also for units that are not codable
+ *   mjw_temit_to_memory    flags 0 or MJW_OPTIMIZE_HUFFMAN; bytes written, 0 when cap is too small (1024 + 2 bytes per coefficient fits)
+ *   mjw_copy_markers       `stream` (as emitted) with the APPn and COM segments the source carries before its first SOS, in source order,
+ *                          directly behind SOI; the writer's own APP0 is dropped when the source carries a JFIF APP0 or an Adobe APP14 and
+ *                          kept first otherwise.  *out is malloc'ed (the caller frees it).  0 with *reason for a truncated or malformed
+ *                          segment length or a source without SOS.  Offsets inside copied segments (MPF and the like) are NOT fixed up.
+ *   mjh_transcode_memory   the whole thing on the host: host walk, units, emit; flags MJW_OPTIMIZE_HUFFMAN and / or MJW_COPY_MARKERS.
+ *                          *out is malloc'ed (the caller frees it); 0 with *reason for a picture that is undecodable, not transcodable
+ *                          or not codable.
+ *   mij_enc_tplan          the plan the GPU encoder holds for a slot made by mij_enc_add_coef (MIJ_E_ARG for any other slot)
+ */
+typedef struct {
+	mjw_plan plan;
+	int ncomp, lh, lv; /* 1 or 3 components; luma sampling factors */
+} mjw_tplan;
+#define MJW_COPY_MARKERS 2u
+int mjw_tplan_from_desc(mjw_tplan *t, const mij_image_desc *d, const char **reason);
+size_t mjw_tplan_du_count(const mjw_tplan *t);
+size_t mjw_theader(const mjw_tplan *t, unsigned char *out);
+size_t mjw_theader_optimized(const mjw_tplan *t, const uint8_t bits[4][16], const uint8_t vals[4][256], unsigned char *out);
+int mjw_units_from_region(const mij_image_desc *d, const uint8_t *region, int format, int16_t *du);
+int mjw_tunits_codable(const mjw_tplan *t, const int16_t *du, const char **reason);
+int mjw_temit(const mjw_tplan *t, const int16_t *du, mjw_write_func *func, void *context);
+int mjw_temit_optimized(const mjw_tplan *t, const int16_t *du, mjw_write_func *func, void *context);
+size_t mjw_temit_to_memory(const mjw_tplan *t, const int16_t *du, unsigned flags, unsigned char *out, size_t cap);
+int mjw_copy_markers(const uint8_t *src, int src_len, const unsigned char *stream, size_t stream_len, unsigned char **out, size_t *out_len,
+                     const char **reason);
+int mjh_transcode_memory(const uint8_t *src, int len, unsigned flags, unsigned char **out, size_t *out_len, const char **reason);
+int mij_enc_tplan(const mij_encoder *e, int slot, mjw_tplan *out);
+
 /* The tables of stbi__ldr_to_hdr (common.c:391-424) for mij_batch_set_out_f32: lut[256*k + v] for channel k < n_out.  Colour
  * channels (all of them for odd n_out, all but the last for even n_out) get (float)(pow(v / 255.0f, gamma) * scale), the
  * alpha channel of n_out 2 and 4 gets v / 255.0f -- the reference's expressions, evaluated with libm's pow. */
