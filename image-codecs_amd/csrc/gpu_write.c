@@ -161,8 +161,7 @@ static void *wb_worker(void *arg)
 			mjw_plan plan;
 			const int16_t *du = mij_enc_units(j->enc, j->slot[i]);
 			if (du && mij_enc_plan(j->enc, j->slot[i], &plan) == MIJ_OK) {
-				/* a coefficient takes at most 27 bits and every output byte may be a stuffed 0xFF: under 7 bytes each (untouched pages cost nothing) */
-				const size_t cap = 2048 + mjw_plan_du_count(&plan) * 64 * 7;
+				const size_t cap = MJW_STREAM_CAP(mjw_plan_du_count(&plan)); /* fits whatever the units hold (untouched pages cost nothing) */
 				unsigned char *buf = (unsigned char *)malloc(cap);
 				const size_t len = buf ? (j->flags & MJW_OPTIMIZE_HUFFMAN ? mjw_emit_optimized_to_memory : mjw_emit_to_memory)(&plan, du, buf, cap) : 0;
 				if (len) {

@@ -239,7 +239,7 @@ int mjh_transcode_memory(const uint8_t *src, int len, unsigned flags, unsigned c
 		goto done;
 	nu = mjw_tplan_du_count(&t);
 	du = (int16_t *)malloc(nu * 64 * sizeof(int16_t));
-	cap = 1024 + nu * 128;
+	cap = MJW_STREAM_CAP(nu);
 	buf = (unsigned char *)malloc(cap);
 	if (!du || !buf) {
 		refuse(reason, "out of memory");

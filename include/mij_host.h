@@ -149,7 +149,11 @@ int mij_write_jpg_to_func(mjw_write_func *func, void *context, int x, int y, int
  * return every out[i] is NULL again and nothing is left for the caller to free. */
 int mij_write_jpg_batch(const void *const *pixels, const int *x, const int *y, const int *comp, int n, int quality, int threads,
                         unsigned char **out, size_t *out_len);
-/* mjw_emit into memory: bytes written, 0 when `cap` is too small or an argument is bad (cap >= 1024 + 2 bytes per coefficient always fits) */
+/* A capacity that holds the stream of `units` data units whatever they contain: a coefficient takes at most 27 bits (a 16-bit code and
+ * 11 value bits) and every output byte may be a 0xFF that is stuffed, so under 7 bytes each; headers and EOI fit the 2048.  (Two bytes
+ * per coefficient are NOT enough: a codable unit can take 1667 bits before stuffing.) */
+#define MJW_STREAM_CAP(units) ((size_t)2048 + (size_t)(units) * 64 * 7)
+/* mjw_emit into memory: bytes written, 0 when `cap` is too small or an argument is bad (MJW_STREAM_CAP(mjw_plan_du_count(p)) always fits) */
 size_t mjw_emit_to_memory(const mjw_plan *p, const int16_t *du, unsigned char *out, size_t cap);
 
 /*
@@ -209,7 +213,7 @@ int mij_write_jpg_batch_ex(const void *const *pixels, const int *x, const int *y
  *                          MIJ_COEF_INT16 or MIJ_COEF_COMPACT; 0 when the descriptor is not transcodable.
  *   mjw_tunits_codable     1, or 0 with *reason (may be NULL)
  *   mjw_temit[_optimized]  the stream of the units; 0 also for units that are not codable
- *   mjw_temit_to_memory    flags 0 or MJW_OPTIMIZE_HUFFMAN; bytes written, 0 when cap is too small (1024 + 2 bytes per coefficient fits)
+ *   mjw_temit_to_memory    flags 0 or MJW_OPTIMIZE_HUFFMAN; bytes written, 0 when cap is too small (MJW_STREAM_CAP(mjw_tplan_du_count(t)) always fits)
  *   mjw_copy_markers       `stream` (as emitted) with the APPn and COM segments the source carries before its first SOS, in source order,
  *                          directly behind SOI; the writer's own APP0 is dropped when the source carries a JFIF APP0 or an Adobe APP14 and
  *                          kept first otherwise.  *out is malloc'ed (the caller frees it).  0 with *reason for a truncated or malformed

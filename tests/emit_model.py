@@ -35,19 +35,54 @@ def tables_from_header(hdr):
     return out
 
 
+def tables_from_stream(data):
+    """(the four tables in the order luma DC, chroma DC, luma AC, chroma AC, the length of the headers) of any baseline stream with one
+    scan, read from its own DHT segments; a table the stream lacks (a grey stream has no chroma tables) is empty"""
+    dht, i = {}, 2
+    while True:
+        assert data[i] == 0xFF, i
+        m, n = data[i + 1], (data[i + 2] << 8) | data[i + 3]
+        if m == 0xC4:
+            j = i + 4
+            while j < i + 2 + n:
+                ident, bits = data[j], data[j + 1:j + 17]
+                cnt = sum(bits)
+                vals = data[j + 17:j + 17 + cnt]
+                t, code, k = {}, 0, 0
+                for ln in range(1, 17):
+                    for _ in range(bits[ln - 1]):
+                        t[vals[k]] = (code, ln)
+                        code += 1
+                        k += 1
+                    code <<= 1
+                dht[ident] = t
+                j += 17 + cnt
+            assert j == i + 2 + n
+        i += 2 + n
+        if m == 0xDA:
+            return [dht.get(ident, {}) for ident in (0x00, 0x01, 0x10, 0x11)], i
+
+
 def _mag(v):
     n = abs(int(v)).bit_length()
     return n, (v - 1 if v < 0 else v) & ((1 << n) - 1)
 
 
-def unit_pieces(T, du, u, dpm, n_du):
-    """[(lane, [(code, len), ...])] for unit u of a slot (du: [n_du, 64] int16)"""
+def luma_units(dpm, ny=None):
+    """the luma units per MCU: given, or what the writer's own two layouts have (6 -> 4, 3 -> 1)"""
+    return (4 if dpm == 6 else 1) if ny is None else ny
+
+
+def unit_pieces(T, du, u, dpm, n_du, ny=None):
+    """[(lane, [(code, len), ...])] for unit u of a slot (du: [n_du, 64] int16); ny: the luma units per MCU (luma_units), the other
+    dpm - ny units being Cb and Cr -- a grey slot has dpm = ny = 1"""
+    ny = luma_units(dpm, ny)
     m, p = divmod(u, dpm)
-    luma = p < (4 if dpm == 6 else 1)
-    if dpm == 6:
-        prev = u - 1 if 0 < p < 4 else (u - (3 if p < 4 else 6) if m > 0 else -1)
+    luma = p < ny
+    if luma:  # the luma unit before it; for an MCU's first one, the last luma unit of the MCU before
+        prev = u - 1 if p > 0 else (u - (dpm - ny + 1) if m > 0 else -1)
     else:
-        prev = u - 3 if m > 0 else -1
+        prev = u - dpm if m > 0 else -1
     dc, ac = (T[0], T[2]) if luma else (T[1], T[3])
     v = [int(x) for x in du[u]]
     lanes = []
@@ -78,15 +113,15 @@ def unit_pieces(T, du, u, dpm, n_du):
     return lanes
 
 
-def unit_bits(T, du, u, dpm, n_du):
-    return sum(ln for _, ps in unit_pieces(T, du, u, dpm, n_du) for _, ln in ps)
+def unit_bits(T, du, u, dpm, n_du, ny=None):
+    return sum(ln for _, ps in unit_pieces(T, du, u, dpm, n_du, ny) for _, ln in ps)
 
 
-def _pack(T, du, first, n, dpm, n_du, h):
+def _pack(T, du, first, n, dpm, n_du, h, ny=None):
     """the tile's bits as a Python int of h + bits bits (the first h zero), MSB first; and that bit count"""
     acc, nb = 0, h
     for u in range(first, first + n):
-        for _, ps in unit_pieces(T, du, u, dpm, n_du):
+        for _, ps in unit_pieces(T, du, u, dpm, n_du, ny):
             for c, ln in ps:
                 acc = (acc << ln) | c
                 nb += ln
@@ -98,20 +133,22 @@ def _bytes_of(acc, nb, nbytes):
     return [(acc >> (nb - 8 * (j + 1))) & 0xFF for j in range(nbytes)]
 
 
-def emit_entropy(T, du, dpm, tile=128, stats=None):
-    """The stuffed entropy-coded segment the kernels write for one slot (fill included, the bits below the last byte dropped)."""
+def emit_entropy(T, du, dpm, tile=128, stats=None, ny=None):
+    """The stuffed entropy-coded segment the kernels write for one slot (fill included, the bits below the last byte dropped).
+    stats, when given, receives the bits, the tiles, and of the seams between tiles those that fall on a byte boundary (aligned) and those
+    whose shared byte is 0xFF (shared_ff)."""
     du = np.asarray(du, dtype=np.int16).reshape(-1, 64)
     n_du = du.shape[0]
     tiles = [(f, min(tile, n_du - f)) for f in range(0, n_du, tile)]
     # k_emit_len, k_emit_scan
-    t_bits = [sum(unit_bits(T, du, u, dpm, n_du) for u in range(f, f + n)) for (f, n) in tiles]
+    t_bits = [sum(unit_bits(T, du, u, dpm, n_du, ny) for u in range(f, f + n)) for (f, n) in tiles]
     t_boff = np.concatenate([[0], np.cumsum(t_bits, dtype=np.int64)[:-1]]).tolist()
     # k_emit_count
     t_ff, t_head, t_tail = [], [], []
     for (f, n), b0, nbit in zip(tiles, t_boff, t_bits):
         b1, h = b0 + nbit, b0 % 8
         n_own = (b1 >> 3) - (b0 >> 3)
-        acc, nb = _pack(T, du, f, n, dpm, n_du, h)
+        acc, nb = _pack(T, du, f, n, dpm, n_du, h, ny)
         by = _bytes_of(acc, nb, n_own)
         t_ff.append(sum(1 for j in range(1 if h else 0, n_own) if by[j] == 0xFF))
         t_head.append(by[0] & ((1 << (8 - h)) - 1) if h and n_own else 0)
@@ -122,6 +159,8 @@ def emit_entropy(T, du, dpm, tile=128, stats=None):
     for t, ((f, n), b0, nbit) in enumerate(zip(tiles, t_boff, t_bits)):
         b1, h = b0 + nbit, b0 % 8
         v = (b1 >> 3) - (b0 >> 3) + t_ff[t]
+        if stats is not None and t > 0 and not h:
+            stats["aligned"] = stats.get("aligned", 0) + 1
         if h and t > 0:
             shared = (t_tail[t - 1] << (8 - h)) | t_head[t]
             v += shared == 0xFF
@@ -135,7 +174,7 @@ def emit_entropy(T, du, dpm, tile=128, stats=None):
     for t, ((f, n), b0, nbit) in enumerate(zip(tiles, t_boff, t_bits)):
         b1, h = b0 + nbit, b0 % 8
         n_own = (b1 >> 3) - (b0 >> 3)
-        acc, nb = _pack(T, du, f, n, dpm, n_du, h)
+        acc, nb = _pack(T, du, f, n, dpm, n_du, h, ny)
         if h:
             acc |= t_tail[t - 1] << (nb - h)
         o = t_out[t]
@@ -180,13 +219,19 @@ def _unit(rng, kind):
 KINDS = ["zero", 15, 16, 17, 31, 32, 48, "last", "ff", "max", "rand"]
 
 
-def adversarial_units(rng, n_mcu, dpm, dc_extremes=True):
+def _components(dpm, ny=None):
+    """the component of each of an MCU's units"""
+    ny = luma_units(dpm, ny)
+    return [0 if p < ny else p - ny + 1 for p in range(dpm)]
+
+
+def adversarial_units(rng, n_mcu, dpm, dc_extremes=True, ny=None):
     """[n_mcu * dpm, 64] int16 units covering every case of KINDS, DC differences of +-2047 per component when dc_extremes,
-    and every AC value inside -1023..1023"""
+    and every AC value inside -1023..1023; ny as in unit_pieces"""
     n = n_mcu * dpm
     du = np.stack([_unit(rng, KINDS[(i * 7 + int(rng.integers(0, 3))) % len(KINDS)]) for i in range(n)])
     # DC: per component, differences walk the full range; +-2047 appear when asked
-    comp = np.array([(p if dpm == 3 else (0 if p < 4 else p - 3)) for p in range(dpm)] * n_mcu)
+    comp = np.array(_components(dpm, ny) * n_mcu)
     for c in range(3):
         idx = np.nonzero(comp == c)[0]
         vals = np.zeros(len(idx), np.int64)
@@ -201,9 +246,9 @@ def adversarial_units(rng, n_mcu, dpm, dc_extremes=True):
     return du
 
 
-def dc_diffs(du, dpm):
+def dc_diffs(du, dpm, ny=None):
     du = np.asarray(du).reshape(-1, 64)
-    comp = np.array([(p if dpm == 3 else (0 if p < 4 else p - 3)) for p in range(dpm)] * (du.shape[0] // dpm))
+    comp = np.array(_components(dpm, ny) * (du.shape[0] // dpm))
     out = []
     for c in range(3):
         v = du[comp == c, 0].astype(np.int64)

@@ -302,19 +302,17 @@ class Writer:
                 pred[ci] = int(blk[0])
                 n = _size(diff)
                 cur.append((0, ci, n, diff if diff >= 0 else diff - 1, n))
-                r = 0
-                for k in range(1, 64):
-                    v = int(blk[k])
-                    if v == 0:
-                        r += 1
-                        continue
+                last = 0
+                for k in np.flatnonzero(blk[1:]) + 1:  # the non-zero coefficients: a block of zeros costs one call
+                    k, v = int(k), int(blk[k])
+                    r = k - last - 1
+                    last = k
                     while r > 15:
                         cur.append((1, ci, 0xF0, 0, 0))
                         r -= 16
                     n = _size(v)
                     cur.append((1, ci, (r << 4) | n, v if v >= 0 else v - 1, n))
-                    r = 0
-                if r:
+                if last < 63:
                     cur.append((1, ci, self.eob, 0, 0))
         intervals.append(cur)
         return intervals
@@ -338,14 +336,19 @@ class Writer:
         for j, iv in enumerate(self._tokens([s[0] for s in sel])):
             if j:
                 out += bytes([0xFF, 0xD0 + (j - 1) % 8])
-            acc, n = 0, 0
+            acc, n, done = 0, 0, bytearray()
             for cls, ci, sym, extra, nx in iv:
                 code, ln = enc[(cls, ci)][sym]
                 acc = (acc << (ln + nx)) | (code << nx) | (extra & ((1 << nx) - 1))
                 n += ln + nx
+                if n >= 2048:  # whole bytes leave the accumulator, so that it stays short
+                    keep = n & 7
+                    done += (acc >> keep).to_bytes((n - keep) // 8, "big")
+                    acc, n = acc & ((1 << keep) - 1), keep
             pad = -n % 8
             acc = (acc << pad) | ((1 << pad) - 1)
-            out += acc.to_bytes((n + pad) // 8, "big").replace(b"\xff", b"\xff\x00")
+            done += acc.to_bytes((n + pad) // 8, "big")
+            out += bytes(done).replace(b"\xff", b"\xff\x00")
         return bytes(out)
 
     def scan(self, sel, data=None, length=None, **kw):

@@ -110,13 +110,15 @@ def _cat(v):
     return np.where(a > 0, np.floor(np.log2(np.maximum(a, 1))).astype(np.int64) + 1, 0)
 
 
-def histogram(du, dpm):
-    """[4][256] counts of the symbols of units du ([n, 64] int16, MCU order, dpm units per MCU: 6 or 3)"""
+def histogram(du, dpm, ny=None):
+    """[4][256] counts of the symbols of units du ([n, 64] int16, MCU order, dpm units per MCU of which ny are luma: emit_model.luma_units;
+    a grey slot, dpm = ny = 1, counts nothing in the chroma tables)"""
     du = np.asarray(du, np.int16).reshape(-1, 64).astype(np.int64)
     n = du.shape[0]
+    ny = em.luma_units(dpm, ny)
     p = np.arange(n) % dpm
-    luma = p < (4 if dpm == 6 else 1)
-    comp = np.where(luma, 0, p - (3 if dpm == 6 else 0))
+    luma = p < ny
+    comp = np.where(luma, 0, p - ny + 1)
     freq = np.zeros((4, 256), np.int64)
     for c in range(3):
         dc = du[comp == c, 0]
@@ -141,14 +143,28 @@ def tables(freq4):
     return None if any(x is None for x in t) else t
 
 
+def _dht_span(hdr):
+    """(start, end) of the one DHT segment of a writer's header: DHT_AT for three components, further in front for a grey stream"""
+    i = 2
+    while hdr[i + 1] != 0xC4:
+        assert hdr[i] == 0xFF and hdr[i + 1] != 0xDA, i
+        i += 2 + ((hdr[i + 2] << 8) | hdr[i + 3])
+    return i, i + 2 + ((hdr[i + 2] << 8) | hdr[i + 3])
+
+
 def header(plain, tabs):
-    """the plain header's bytes with `tabs` in the DHT segment"""
+    """the plain header's bytes with `tabs` in the DHT segment, for the tables that segment holds: four, or the two luma tables of a
+    grey stream"""
+    a, b = _dht_span(plain)
+    have = dht_tables(plain[a + 4:b])
     seg = bytearray()
     for ident, k in zip(_IDS, _ORDER):
+        if ident not in have:
+            continue
         bits, vals = tabs[k]
         seg += bytes([ident]) + bytes(bits) + bytes(vals)
     n = len(seg) + 2
-    return bytes(plain[:DHT_AT]) + bytes([0xFF, 0xC4, n >> 8, n & 255]) + bytes(seg) + _SOS
+    return bytes(plain[:a]) + bytes([0xFF, 0xC4, n >> 8, n & 255]) + bytes(seg) + bytes(plain[b:])
 
 
 class _Codes(dict):
@@ -181,22 +197,25 @@ def dht_tables(seg):
 
 
 def tables_from_header(hdr):
-    """-> [ {symbol: (code, len)} ] x 4 from the one DHT segment of a writer's header, plain or optimised"""
-    assert hdr[DHT_AT] == 0xFF and hdr[DHT_AT + 1] == 0xC4
-    n = (hdr[DHT_AT + 2] << 8) | hdr[DHT_AT + 3]
-    d = dht_tables(hdr[DHT_AT + 4:DHT_AT + 2 + n])
-    assert list(d) == [0x00, 0x10, 0x01, 0x11]
-    assert bytes(hdr[DHT_AT + 2 + n:]) == _SOS
-    return [_canonical(*d[i]) for i in (0x00, 0x01, 0x10, 0x11)]
+    """-> [ {symbol: (code, len)} ] x 4 from the one DHT segment of a writer's header, plain or optimised (a grey header's chroma tables
+    are empty)"""
+    a, b = _dht_span(hdr)
+    d = dht_tables(hdr[a + 4:b])
+    if a == DHT_AT:
+        assert list(d) == [0x00, 0x10, 0x01, 0x11]
+        assert bytes(hdr[b:]) == _SOS
+    else:
+        assert list(d) == [0x00, 0x10] and hdr[b + 1] == 0xDA and hdr[b + 4] == 1
+    return [_canonical(*d[i]) if i in d else _Codes() for i in (0x00, 0x01, 0x10, 0x11)]
 
 
-def emit_optimized(plain_hdr, du, dpm):
+def emit_optimized(plain_hdr, du, dpm, ny=None):
     """the optimised stream of units du whose plain header is plain_hdr, or None for the over-32 fallback"""
-    t = tables(histogram(du, dpm))
+    t = tables(histogram(du, dpm, ny))
     if t is None:
         return None
     h = header(plain_hdr, t)
-    return h + em.emit_entropy(tables_from_header(h), du, dpm) + b"\xff\xd9"
+    return h + em.emit_entropy(tables_from_header(h), du, dpm, ny=ny) + b"\xff\xd9"
 
 
 def deep_counts(depth):

@@ -134,11 +134,11 @@ int main(void)
 				bad++;
 			}
 			if (!mjw_tunits_codable(&t, du, &why)) { fprintf(stderr, "shape %d size %d: %s\n", si, zi, why); bad++; }
-			mem = malloc(1024 + nu * 128);
+			mem = malloc(MJW_STREAM_CAP(nu));
 			if (!mjw_temit(&t, du, sink_write, &a) || !mjw_temit_optimized(&t, du, sink_write, &b)) bad++;
-			n1 = mjw_temit_to_memory(&t, du, 0, mem, 1024 + nu * 128);
+			n1 = mjw_temit_to_memory(&t, du, 0, mem, MJW_STREAM_CAP(nu));
 			if (n1 != a.n || memcmp(mem, a.p, n1)) bad++;
-			n2 = mjw_temit_to_memory(&t, du, MJW_OPTIMIZE_HUFFMAN, mem, 1024 + nu * 128);
+			n2 = mjw_temit_to_memory(&t, du, MJW_OPTIMIZE_HUFFMAN, mem, MJW_STREAM_CAP(nu));
 			if (n2 != b.n || memcmp(mem, b.p, n2)) bad++;
 			if (mjw_temit_to_memory(&t, du, 0, mem, a.n - 1)) bad++; /* one byte short: refused, nothing written past it */
 			if (!mjh_transcode_memory(a.p, (int)a.n, 0, &out, &n1, &why) || n1 != a.n || memcmp(out, a.p, n1)) {
@@ -152,7 +152,7 @@ int main(void)
 				bad += check_prefixes(b.p, b.n);
 			du[64 * (nu - 1) + 63] = 1024; /* one value over: every emitter refuses */
 			if (mjw_tunits_codable(&t, du, &why) || mjw_temit(&t, du, sink_write, &a) || mjw_temit_optimized(&t, du, sink_write, &a) ||
-				 mjw_temit_to_memory(&t, du, 0, mem, 1024 + nu * 128)) bad++;
+				 mjw_temit_to_memory(&t, du, 0, mem, MJW_STREAM_CAP(nu))) bad++;
 			free(mem), free(du), free(du2), free(r16), free(rc), free(a.p), free(b.p);
 			++cases;
 		}

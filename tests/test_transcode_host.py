@@ -4,10 +4,13 @@ their reasons, and the marker copy equals the model.  No GPU."""
 import numpy as np
 import pytest
 
+import emit_model as em
 import helpers
 import header_cases as hc
+import hufopt_model as hm
 import transcode_cases as tc
 import transcode_model as model
+import transcode_planes as tp
 
 
 def _c_table(path, name):
@@ -243,3 +246,147 @@ def test_host_transcode_under_sanitizers(tmp_path):
     assert run.returncode == 0, run.stdout[-1000:] + run.stderr[-2000:]
     assert "runtime error" not in run.stderr and "Sanitizer" not in run.stderr, run.stderr[-2000:]
     assert "transcode harness: 20 cases, 0 failures" in run.stdout
+
+
+# ---------------------------------------------------------------- sources made from chosen coefficient planes (transcode_planes.py)
+
+def test_units_to_planes_inverts_the_model():
+    rng = np.random.default_rng(7)
+    for layout, hv in tp.LAYOUTS.items():
+        w, h = tp.size(layout, (5, 3), True)
+        g = tp.Geom(w, h, hv)
+        du = rng.integers(-1023, 1024, size=(g.n_du, 64)).astype(np.int16)
+        planes = tp.units_to_planes(du, w, h, hv)
+        assert [p.shape for p in planes] == [(c.bh, c.bw, 64) for c in g.comp]
+        assert np.array_equal(model.units_from_planes(g, tp.natural(planes)), du), layout
+
+
+def test_chosen_planes_are_what_they_claim():
+    """the properties the sources are built for, in numpy, before anything decodes them"""
+    for layout, hv in tp.LAYOUTS.items():
+        for s in tp.address(layout):
+            g = tp.Geom(s.w, s.h, s.hv)
+            assert (g.mcu_x, g.mcu_y) in tp.GRIDS
+            for c, p in enumerate(s.planes):
+                assert np.abs(p.astype(np.int64)).max() <= 1023
+                plain = (np.arange(p.shape[0] * p.shape[1]) % 3 == 0).reshape(p.shape[:2])
+                assert p[plain].min() >= -128 and p[plain].max() <= 127
+                if (~plain).any():
+                    assert ((p[~plain][:, 1:] > 127) | (p[~plain][:, 1:] < -128)).any(axis=1).all()
+        assert len(tp.address(layout)) == 20 and max(s.w for s in tp.address(layout)) <= 1040
+        e = tp.edge_values(layout)
+        for p in e.planes:
+            flat = p.reshape(-1, 64)
+            for v in tp.EDGE_VALUES:
+                assert (flat[:, 1:] == v).any(axis=0).all(), (layout, v)
+        d = tp.dense(layout)
+        assert tp.escaped_blocks(d.planes) == sum(p.shape[0] * p.shape[1] for p in d.planes)
+        # the triangle: no MCU-order difference is large, the first blocks of consecutive MCU rows differ by 2200, and the block above
+        # (which is block L - bw) is 2047 away and more somewhere
+        t = tp.triangle(layout)
+        g = tp.Geom(t.w, t.h, t.hv)
+        for c, p in enumerate(t.planes):
+            dc = p[:, :, 0].astype(np.int64)
+            seq = tp.mcu_order(g, c)
+            order = np.array([dc[by, bx] for by, bx in seq])
+            assert np.abs(np.diff(np.concatenate([[0], order]))).max() <= 1100
+            v = g.comp[c].v
+            assert abs(int(dc[v, 0]) - int(dc[0, 0])) == 2200
+            assert np.abs(np.diff(dc, axis=0)).max() > 2047
+        assert not any(p[:, :, 1:].any() for p in t.planes)
+    # the pairs: every branch a layout has, in every component; the predecessor in an earlier tile wherever a block index can cross one
+    for layout, hv in tp.LAYOUTS.items():
+        for comp, (a, v) in enumerate(hv):
+            for branch in tp.BRANCHES:
+                exists = {"a": a > 1, "b": v > 1}.get(branch, True)
+                same, cross = tp.pair_site(layout, comp, branch, True), tp.pair_site(layout, comp, branch, False)
+                assert (same is not None) == exists, (layout, comp, branch)
+                assert (cross is not None) == (exists and branch in "bcd"), (layout, comp, branch)
+                for site in (same, cross):
+                    if site is not None:
+                        assert site[0][0] * site[0][1] <= 70
+    assert len(tp.dc_pairs("420")) == 4 * (8 + 5 + 5)  # luma: a, b twice, c twice, d twice, e; chroma: c twice, d twice, e
+    assert len(tp.ac_limits("420")) == 2 + 2 * 4 * 3 * 2 and len(tp.ac_limits("grey")) == 2 + 4 * 3 * 2  # components, blocks, positions, signs
+    for layout in tp.LAYOUTS:  # two DCs and nothing else: whatever other block a rule takes for the predecessor, it sees 1024 at the most
+        for src, ok in tp.dc_pairs(layout):
+            assert sum(int(np.count_nonzero(p)) for p in src.planes) == (1 if "branch e" in src.name else 2), src.name
+            assert max(int(np.abs(p[:, :, 0].astype(np.int64)).max()) for p in src.planes) <= (2048 if "branch e" in src.name else 1024)
+    pair = tp.dc_pair("420", 0, "d", False, -2048)
+    dcs = pair.planes[0][:, :, 0]
+    assert sorted(dcs[dcs != 0].tolist()) == [-1024, 1024] and not any(p[:, :, 0].any() for p in pair.planes[1:])
+
+
+@pytest.mark.parametrize("layout", list(tp.LAYOUTS))
+def test_chosen_planes_units_and_verdicts(ica, layout):
+    """every source made from chosen planes, on both plane formats: the units the host reads equal the model's of the decoded planes and
+    of the planes handed to the writer, and the model's verdict is the host's, at the unit check and through the whole path"""
+    cases = tp.all_sources(layout)
+    refused = 0
+    for src, ok in cases:
+        want = tp.expected_units(src)
+        verdict = model.codable(tp.Geom(src.w, src.h, src.hv), want)
+        assert verdict == ok, src.name
+        refused += not verdict
+        for compact in (False, True):
+            desc, region = ica.host_decode_staged(src.data, 0, want_compact=compact)
+            is_compact = bool(desc.flags & 4)
+            assert is_compact == compact, src.name
+            arena = ica.expand_compact_region(desc, region) if is_compact else region.view(np.int16)[:desc.coef_elems()]
+            assert np.array_equal(model.units_from_planes(desc, ica.detile_coefficients(desc, arena)), want), (src.name, compact)
+            got = ica.units_from_region(desc, region, is_compact)
+            assert got is not None and np.array_equal(got, want), (src.name, compact)
+            if is_compact:
+                offs, _ = ica.compact_offsets(desc)
+                flagged = 0
+                for c, (lo, _, _) in enumerate(offs):
+                    L = np.arange(desc.comp[c].bw * desc.comp[c].bh)
+                    flagged += int((region[lo + ((L >> 6) << 12) + ((L & 63) << 3)] & 1).sum())
+                assert flagged == tp.escaped_blocks(src.planes), src.name
+        t, _ = ica.transcode_plan(desc)
+        assert ica.units_codable(t, want)[0] == verdict, src.name
+        for optimize in (False, True):
+            out, why = ica.transcode_memory(src.data, optimize=optimize)
+            assert (out is not None) == verdict, (src.name, optimize, why)
+            if not verdict:
+                assert ("DC" in why) if src.name.startswith("dc pair") else ("AC" in why), (src.name, why)
+    assert refused == sum(1 for _, ok in cases if not ok) >= 10 + 24
+
+
+def test_longest_units_fit_the_hosts_buffer(ica):
+    """dense noise in every layout and the longest codable units under the Annex-K tables: some 200 to 250 bytes per unit, which
+    mjh_transcode_memory's buffer has to hold (it was sized at 128 per unit and answered "emission failed")"""
+    srcs = [tp.dense(layout) for layout in tp.LAYOUTS] + [tp.longest()]
+    for src in srcs:
+        want = tp.expected_units(src)
+        assert model.codable(tp.Geom(src.w, src.h, src.hv), want)
+        out, why = ica.transcode_memory(src.data, optimize=False)
+        assert out is not None, (src.name, why)
+        assert len(out) > 607 + 128 * len(want), src.name  # the case the old bound missed
+        d2, r2 = ica.host_decode_staged(out, 0, want_compact=False)
+        assert np.array_equal(ica.units_from_region(d2, r2, False), want), src.name
+    assert len(ica.transcode_memory(tp.longest().data)[0]) > 240 * 387
+
+
+@pytest.mark.parametrize("layout", list(tp.LAYOUTS))
+def test_emission_model_equals_the_host_for_every_layout(ica, layout):
+    """the emission model generalised to (dpm, ny) against mjw_temit / mjw_temit_optimized byte for byte, at eleven tiles and more, with
+    a seam that shares a 0xFF byte and a seam on a byte boundary under the plain tables"""
+    src = tp.emission(layout)
+    du, want, stats, _ = tp.emission_model(layout)
+    g = tp.Geom(src.w, src.h, src.hv)
+    assert len(du) >= 1300 and stats["tiles"] == (len(du) + 127) // 128 >= 11
+    assert stats.get("shared_ff", 0) >= 1 and stats.get("aligned", 0) >= 1, stats
+    assert np.array_equal(du, em.adversarial_units(np.random.default_rng(tp.EMISSION[layout][1]), g.mcu_x * g.mcu_y, g.dpm, ny=g.ny))
+    assert np.abs(em.dc_diffs(du, g.dpm, g.ny)).max() == 2047
+    desc, region = ica.host_decode_staged(src.data, 0, want_compact=True)
+    assert np.array_equal(ica.units_from_region(desc, region, bool(desc.flags & 4)), du)
+    t, _ = ica.transcode_plan(desc)
+    assert (t.plan.du_per_mcu, t.lh * t.lv if t.ncomp == 3 else 1) == (g.dpm, g.ny)
+    for optimize in (False, True):
+        got = ica.emit_transcoded(t, du, optimize)
+        assert got == want[optimize], (layout, optimize)
+        assert ica.transcode_memory(src.data, optimize=optimize)[0] == got, (layout, optimize)
+    assert len(want[True]) < len(want[False])
+    # the histogram the optimised tables come from, against the library's for the two layouts the writer's own plans have
+    if layout in ("444", "420"):
+        assert np.array_equal(hm.histogram(du, g.dpm, g.ny), ica.write_histogram(t.plan, du))
