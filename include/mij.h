@@ -381,7 +381,7 @@ int mij_batch_fallback_prepare(mij_batch *b, int slot);
  * int16 tile layout (compact planes are expanded on the host); dst_elems >= sum of mij_plane_elems */
 int mij_batch_fetch_coef(mij_batch *b, int slot, int16_t *dst, size_t dst_elems);
 /* tests: why the GPU walk handed a slot back -- the OR of the anomaly words of the slot's scans (one per restart interval) after
- * mij_batch_entropy_run / _finish.  0: kept.  1: a run past coefficient 63 or a bad code; 2: arena; 4: the stream ends before the last
+ * mij_batch_entropy_run / _finish.  0: kept.  1: a run past coefficient 63 or a bad code; 2: inconsistent chain (with 8); 4: the stream ends before the last
  * block; 8: no convergence; 16: data ran out inside a block; 32: a 0xff data byte behind the final bit position of the last segment;
  * 64: a restart interval ends a byte or more before its marker, or past it (k_es_dc).  Negative code for a slot the walk never had. */
 int mij_batch_entropy_anomaly(mij_batch *b, int slot);

@@ -1,13 +1,13 @@
 """The GPU Huffman walk where the entropy data ENDS.  It hands an image back to the host walk through an anomaly word whose bits are separate
-hand-written rules (es_decode, k_es_dc): 1 a run past coefficient 63 or a bad code, 2 arena, 4 the stream ends before the last block,
+hand-written rules (es_decode, k_es_dc): 1 a run past coefficient 63 or a bad code, 2 an inconsistent chain, 4 the stream ends before the last block,
 8 no convergence, 16 the data ran out inside a block, 32 a 0xff data byte behind the final bit position of the last interval, 64 a restart
 interval that ends a byte or more before its marker, or past it.  A rule that is off by a bit or a byte would make the walk ACCEPT a stream
 and deliver pixels the reference does not.  The cases are the ones test_stream_ends_host.py runs on the CPU (stream_cases.py): bytes behind
 the last block, cuts, edits around restart markers, streams that end on and around subsequence boundaries.
 
 Everything is compared bit for bit with the oracle (and the host walk's planes); which bits a case raises is predicted from the rules'
-own comments by stream_cases.predict_anomaly, a plain sequential walk on the test side.  Bits 2 (an exhausted arena) and 8 (a chain that does not
-settle in 96 rounds) are not covered: no small construction raises them.
+own comments by stream_cases.predict_anomaly, a plain sequential walk on the test side.  Bits 8 (a chain that does not settle in 96 rounds)
+and 2 (its hand-over states do not chain up; only ever with 8) are not raised here: test_gpu_walk_seams.py holds them.
 
 Nothing here provokes a fault: every stream sits in the entropy arena with the zero padding the kernels rely on."""
 import numpy as np
