@@ -29,6 +29,7 @@ from .binding import (  # noqa: F401
     MIJ_FILTER_LANCZOS,
     resize_coeffs,
     exif_orientation,
+    exif_set_orientation,
     MIJ_DT_U8,
     MIJ_DT_F16,
     MIJ_DT_BF16,
@@ -51,6 +52,8 @@ from .binding import (  # noqa: F401
     emit_transcoded,
     copy_markers,
     transcode_memory,
+    transcode_plan_oriented,
+    units_orient,
     write_histogram,
     optimal_huffman_table,
     MJW_OPTIMIZE_HUFFMAN,

@@ -611,6 +611,16 @@ def exif_orientation(data):
     return int(L.mjh_exif_orientation(b, len(b)))
 
 
+def exif_set_orientation(data, value):
+    """mjh_exif_set_orientation on a copy of a JPEG file's bytes -> (bytes, patched): the entry exif_orientation reads set to value
+    (1..8); the same bytes and False where there is no such entry."""
+    buf = C.create_string_buffer(bytes(data), len(data))
+    L = lib()
+    L.mjh_exif_set_orientation.argtypes = [C.c_char_p, C.c_int, C.c_int]
+    ok = L.mjh_exif_set_orientation(buf, len(data), int(value))
+    return buf.raw, bool(ok)
+
+
 class Context:
     """mij_ctx: one per (process, device)."""
 
@@ -1326,16 +1336,50 @@ def copy_markers(src, stream):
     return _take_malloced(out, n.value), None
 
 
-def transcode_memory(data, optimize=False, copy_markers=False):
-    """mjh_transcode_memory, the lossless transcode on the host alone -> (bytes, None) or (None, reason)"""
+def transcode_memory(data, optimize=False, copy_markers=False, orientation=None, trim=False):
+    """mjh_transcode_memory, the lossless transcode on the host alone -> (bytes, None) or (None, reason).  With an orientation
+    (1..8, or "exif" for the file's own tag) it is mjh_transcode_memory_oriented; trim chooses its edge mode."""
     L = lib()
-    L.mjh_transcode_memory.argtypes = [C.c_char_p, C.c_int, C.c_uint, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_char_p)]
     data = bytes(data)
     out, n, why = C.c_void_p(), C.c_size_t(), C.c_char_p()
     flags = (MJW_OPTIMIZE_HUFFMAN if optimize else 0) | (MJW_COPY_MARKERS if copy_markers else 0)
-    if not L.mjh_transcode_memory(data, len(data), flags, C.byref(out), C.byref(n), C.byref(why)):
+    if orientation is None:
+        L.mjh_transcode_memory.argtypes = [C.c_char_p, C.c_int, C.c_uint, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_char_p)]
+        ok = L.mjh_transcode_memory(data, len(data), flags, C.byref(out), C.byref(n), C.byref(why))
+    else:
+        L.mjh_transcode_memory_oriented.argtypes = [C.c_char_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                    C.POINTER(C.c_char_p)]
+        ok = L.mjh_transcode_memory_oriented(data, len(data), flags, 0 if orientation == "exif" else int(orientation), int(bool(trim)), C.byref(out),
+                                             C.byref(n), C.byref(why))
+    if not ok:
         return None, (why.value.decode() if why.value else "decode failed")
     return _take_malloced(out, n.value), None
+
+
+def transcode_plan_oriented(tplan, orientation, trim=False):
+    """mjw_tplan_oriented: the destination's plan of a source's -> (TranscodePlan, None), or (None, reason) where it is refused"""
+    L = lib()
+    L.mjw_tplan_oriented.argtypes = [C.POINTER(TranscodePlan), C.POINTER(TranscodePlan), C.c_int, C.c_int, C.POINTER(C.c_char_p)]
+    t, why = TranscodePlan(), C.c_char_p()
+    if not L.mjw_tplan_oriented(C.byref(t), C.byref(tplan), int(orientation), int(bool(trim)), C.byref(why)):
+        return None, (why.value.decode() if why.value else "refused")
+    return t, None
+
+
+def units_orient(tplan, du, orientation, trim=False):
+    """mjw_units_orient: a source's units (in its plan's order) -> the destination's, int16 [n_du, 64]; None where the picture is refused"""
+    dst, _ = transcode_plan_oriented(tplan, orientation, trim)
+    if dst is None:
+        return None
+    L = lib()
+    L.mjw_units_orient.argtypes = [C.POINTER(TranscodePlan), C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    d = np.ascontiguousarray(du, np.int16)
+    if d.size != tplan.du_elems():
+        raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, tplan.du_elems()))
+    out = np.empty(dst.du_elems(), np.int16)
+    if not L.mjw_units_orient(C.byref(tplan), d.ctypes.data_as(C.c_void_p), int(orientation), int(bool(trim)), out.ctypes.data_as(C.c_void_p)):
+        return None
+    return out.reshape(-1, 64)
 
 
 def write_histogram(plan, du):
@@ -1532,12 +1576,17 @@ class Encoder:
             raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, plan.du_elems()))
         return _check(L.mij_enc_add_units(self._h, int(width), int(height), int(comp), int(quality), d.ctypes.data_as(C.c_void_p)), "mij_enc_add_units")
 
-    def add_coef(self, batch, slot):
+    def add_coef(self, batch, slot, orientation=1, trim=False):
         """mij_enc_add_coef: a slot whose units are the quantised coefficients of an uploaded Batch's slot (lossless transcode).
-        MijError with the reason for a picture that is not transcodable.  The batch must stay as it is until wait() or a fetch."""
+        MijError with the reason for a picture that is not transcodable.  The batch must stay as it is until wait() or a fetch.
+        orientation 1..8 and trim: mij_enc_add_coef_oriented, the coefficients reoriented on the way (the slot's plan, units and stream
+        are the destination's); MijError with the reason for a picture the edge mode refuses."""
         L = lib()
-        L.mij_enc_add_coef.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        return _check(L.mij_enc_add_coef(self._h, batch._h, int(slot)), "mij_enc_add_coef")
+        if orientation == 1 and not trim:
+            L.mij_enc_add_coef.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+            return _check(L.mij_enc_add_coef(self._h, batch._h, int(slot)), "mij_enc_add_coef")
+        L.mij_enc_add_coef_oriented.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        return _check(L.mij_enc_add_coef_oriented(self._h, batch._h, int(slot), int(orientation), int(bool(trim))), "mij_enc_add_coef_oriented")
 
     def tplan(self, slot):
         """mij_enc_tplan: the TranscodePlan of a slot made by add_coef"""

@@ -4104,7 +4104,7 @@ extern "C" int mij_enc_add_units(mij_encoder *e, int width, int height, int comp
 
 /* ---- coefficient slots (lossless transcode): a decode batch's planes become the slot's data units on the device */
 
-extern "C" int mij_enc_add_coef(mij_encoder *e, mij_batch *b, int slot)
+extern "C" int mij_enc_add_coef_oriented(mij_encoder *e, mij_batch *b, int slot, int orientation, int trim)
 {
 	if (!e || !b)
 		return set_err(MIJ_E_ARG, "bad argument");
@@ -4117,12 +4117,14 @@ extern "C" int mij_enc_add_coef(mij_encoder *e, mij_batch *b, int slot)
 		return set_err(MIJ_E_ARG, "mij_enc_add_coef: batch slot %d was rejected by the entropy stage", slot);
 	if (!b->uploaded)
 		return set_err(MIJ_E_ARG, "mij_enc_add_coef: the planes of batch slot %d are not in device memory yet (mij_batch_upload first)", slot);
-	mjw_tplan tp;
+	mjw_tplan sp, tp; /* the source's plan (the planes' geometry) and the destination's (the stream's) */
 	const char *why = nullptr;
-	if (!mjw_tplan_from_desc(&tp, &bs.desc, &why))
+	if (!mjw_tplan_from_desc(&sp, &bs.desc, &why))
 		return set_err(MIJ_E_ARG, "not transcodable: %s", why ? why : "refused");
+	if (!mjw_tplan_oriented(&tp, &sp, orientation, trim, &why))
+		return set_err(MIJ_E_ARG, "not transformable: %s", why ? why : "refused");
 	const size_t nu = mjw_tplan_du_count(&tp);
-	if (nu > UINT32_MAX / 64)
+	if (mjw_tplan_du_count(&sp) > UINT32_MAX / 64)
 		return set_err(MIJ_E_ARG, "not transcodable: too many data units");
 	const int es = enc_add_common(e, tp.plan, nullptr, 0, -1, ENC_COEF);
 	if (es < 0)
@@ -4136,17 +4138,27 @@ extern "C" int mij_enc_add_coef(mij_encoder *e, mij_batch *b, int slot)
 		s.coef.dc_off[c] = bs.dev.comp[c].dc_off;
 		s.coef.hi_off[c] = bs.dev.comp[c].hi_off;
 	}
+	const bool tr = orient_tr[orientation];
 	s.coef.du_off = s.dev.du_off;
-	s.coef.mcu_x = (uint32_t)tp.plan.mcu_x;
-	s.coef.mcu_y = (uint32_t)tp.plan.mcu_y;
-	s.coef.lh = (uint32_t)tp.lh;
-	s.coef.lv = (uint32_t)tp.lv;
+	s.coef.mcu_x = (uint32_t)sp.plan.mcu_x;
+	s.coef.mcu_y = (uint32_t)sp.plan.mcu_y;
+	s.coef.lh = (uint32_t)sp.lh;
+	s.coef.lv = (uint32_t)sp.lv;
 	s.coef.ncomp = (uint32_t)tp.ncomp;
 	s.coef.dpm = (uint32_t)tp.plan.du_per_mcu;
 	s.coef.n_du = (uint32_t)nu;
 	s.coef.slot = (uint32_t)es;
+	s.coef.d_mcu_x = (uint32_t)tp.plan.mcu_x;
+	s.coef.d_mcu_y = (uint32_t)tp.plan.mcu_y;
+	s.coef.d_lh = (uint32_t)tp.lh;
+	s.coef.d_lv = (uint32_t)tp.lv;
+	s.coef.ext_x = (uint32_t)(tr ? tp.plan.mcu_y : tp.plan.mcu_x);
+	s.coef.ext_y = (uint32_t)(tr ? tp.plan.mcu_x : tp.plan.mcu_y);
+	s.coef.orient = (orient_mx[orientation] ? MIJ_CONV_NX : 0u) | (orient_my[orientation] ? MIJ_CONV_NY : 0u) | (tr ? MIJ_CONV_TR : 0u);
 	return es;
 }
+
+extern "C" int mij_enc_add_coef(mij_encoder *e, mij_batch *b, int slot) { return mij_enc_add_coef_oriented(e, b, slot, 1, 0); }
 
 extern "C" int mij_enc_tplan(const mij_encoder *e, int slot, mjw_tplan *out)
 {
@@ -4185,8 +4197,16 @@ extern "C" int mij_enc_coef_ms(mij_encoder *e, float *ms)
 	return MIJ_OK;
 }
 
+/* k_coef_units' instances by [compact][MIJ_CONV_NX | MIJ_CONV_NY | MIJ_CONV_TR] */
+typedef void (*coef_units_fn)(const CoefSlot *, const WorkIdct *, const uint8_t *, uint8_t *, uint32_t *);
+#define MIJ_CONV_ROW_OF(C) \
+	{k_coef_units<C, 0, 0, 0>, k_coef_units<C, 0, 1, 0>, k_coef_units<C, 0, 0, 1>, k_coef_units<C, 0, 1, 1>, \
+	 k_coef_units<C, 1, 0, 0>, k_coef_units<C, 1, 1, 0>, k_coef_units<C, 1, 0, 1>, k_coef_units<C, 1, 1, 1>}
+static const coef_units_fn k_coef_units_of[2][8] = {MIJ_CONV_ROW_OF(0), MIJ_CONV_ROW_OF(1)};
+#undef MIJ_CONV_ROW_OF
+
 /* The conversion kernel of the coefficient slots, queued at upload in place of a copy of units: behind an event on every source
- * batch's stream, one launch per (batch, plane format) over a list of plane tiles.  The flags are cleared whenever the emission may
+ * batch's stream, one launch per (batch, plane format, orientation's template instance) over a list of plane tiles.  The flags are cleared whenever the emission may
  * read them. */
 static int enc_coef_convert(mij_encoder *e)
 {
@@ -4217,10 +4237,11 @@ static int enc_coef_convert(mij_encoder *e)
 		HIP_TRY(hipEventCreate(&e->ev_conv0));
 		HIP_TRY(hipEventCreate(&e->ev_conv1));
 	}
-	/* groups: slots of one batch and one plane format are contiguous in the lists */
+	/* groups: slots of one batch, one plane format and one template instance (orientation) are contiguous in the lists */
 	struct Group {
 		mij_batch *b;
 		int fmt;
+		uint32_t orient;
 		size_t first, count;
 	};
 	std::vector<Group> groups;
@@ -4229,9 +4250,9 @@ static int enc_coef_convert(mij_encoder *e)
 		if (s.kind == ENC_COEF) {
 			bool seen = false;
 			for (const Group &g : groups)
-				seen = seen || (g.b == s.src && g.fmt == s.coef_fmt);
+				seen = seen || (g.b == s.src && g.fmt == s.coef_fmt && g.orient == s.coef.orient);
 			if (!seen)
-				groups.push_back(Group{s.src, s.coef_fmt, 0, 0});
+				groups.push_back(Group{s.src, s.coef_fmt, s.coef.orient, 0, 0});
 			if (std::find(batches.begin(), batches.end(), s.src) == batches.end())
 				batches.push_back(s.src);
 		}
@@ -4239,7 +4260,7 @@ static int enc_coef_convert(mij_encoder *e)
 	for (Group &g : groups) {
 		g.first = w;
 		for (const EncSlot &s : e->slots) {
-			if (s.kind != ENC_COEF || s.src != g.b || s.coef_fmt != g.fmt)
+			if (s.kind != ENC_COEF || s.src != g.b || s.coef_fmt != g.fmt || s.coef.orient != g.orient)
 				continue;
 			e->h_cslot[k] = s.coef;
 			for (uint32_t c = 0; c < s.coef.ncomp; ++c) {
@@ -4264,10 +4285,8 @@ static int enc_coef_convert(mij_encoder *e)
 			continue;
 		const dim3 grid((unsigned)g.count), block(64);
 		uint8_t *du = reinterpret_cast<uint8_t *>(e->d_du);
-		if (g.fmt)
-			hipLaunchKernelGGL(k_coef_units<1>, grid, block, 0, e->stream, e->d_cslot, e->d_cwork + g.first, g.b->d_coef, du, e->d_sflag);
-		else
-			hipLaunchKernelGGL(k_coef_units<0>, grid, block, 0, e->stream, e->d_cslot, e->d_cwork + g.first, g.b->d_coef, du, e->d_sflag);
+		hipLaunchKernelGGL(k_coef_units_of[g.fmt ? 1 : 0][g.orient & 7u], grid, block, 0, e->stream, e->d_cslot, e->d_cwork + g.first, g.b->d_coef, du,
+								 e->d_sflag);
 		HIP_TRY(hipGetLastError());
 	}
 	HIP_TRY(hipEventRecord(e->ev_conv1, e->stream));

@@ -17,6 +17,15 @@
  *            place, eight units per pass.
  * Unit index of block (bx, by) of a component with factors h x v: MCU (bx / h, by / v), sub-block (bx % h, by % v):
  *   u = (my * mcu_x + mx) * dpm + first + sy * h + sx,  first = 0 for luma, ny for Cb, ny + 1 for Cr.
+ *
+ * Orientations (mij_enc_add_coef_oriented; the rules are mjw_tplan_oriented's, mij_host.h).  The load phase is the source's whatever the
+ * orientation: tiles of the SOURCE plane.  What is known at compile time is templated -- TR (transpose), NX and NY (the source's x / y axis
+ * is mirrored, so odd u / odd v change sign): the position -> zigzag table becomes the transposed one and the signs a constant mask, so
+ * every LDS store keeps its constant offset and <0, 0, 0> is the plain kernel.  Only the block geometry is run-time: source block (bx, by)
+ * inside the kept extent goes to (ew - 1 - bx | bx, eh - 1 - by | by), swapped when TR, and gets its unit index from the DESTINATION's
+ * geometry; a block the trim drops gets u = ~0 and is neither checked nor stored.  The DC predecessor is the previous unit of the component
+ * in destination order, mapped back through the same mirrors and swap to a source block index and loaded as before.  The store phase is
+ * unchanged: whole 128-byte units are scattered, not pieces.
  */
 #pragma once
 
@@ -25,9 +34,13 @@
 struct CoefSlot {
 	uint64_t coef_off[3], dc_off[3], hi_off[3]; /* bytes into the batch's coefficient arena, per component (DevComp) */
 	uint64_t du_off;                            /* bytes into the encoder's unit arena */
-	uint32_t mcu_x, mcu_y, lh, lv;
-	uint32_t ncomp, dpm, n_du, slot;            /* slot: the encoder slot, whose flag an uncodable value raises */
+	uint32_t mcu_x, mcu_y, lh, lv;              /* the SOURCE's: the planes' geometry */
+	uint32_t ncomp, dpm, n_du, slot;            /* n_du: the destination's units; slot: the encoder slot, whose flag an uncodable value raises */
+	uint32_t d_mcu_x, d_mcu_y, d_lh, d_lv;      /* the destination's (the source's again for orientation 1) */
+	uint32_t ext_x, ext_y;                      /* the source's MCU columns and rows that the trim keeps */
+	uint32_t orient, pad;                       /* MIJ_CONV_NX | MIJ_CONV_NY | MIJ_CONV_TR: which template instance converts the slot */
 };
+enum { MIJ_CONV_NX = 1, MIJ_CONV_NY = 2, MIJ_CONV_TR = 4 };
 
 /* in-block position P -> zigzag index k: the inverse of mij_zigzag_pos (tests/test_transcode_host.py holds the two against each other) */
 static constexpr uint8_t k_zigzag_of_pos[64] = {
@@ -36,14 +49,35 @@ static constexpr uint8_t k_zigzag_of_pos[64] = {
 	14, 39, 25, 50, 16, 31, 46, 57, 15, 45, 30, 56, 26, 40, 51, 58,
 	27, 52, 41, 59, 29, 44, 55, 62, 28, 54, 43, 61, 42, 53, 60, 63};
 
-template <int COMPACT>
+/* per source position P = 8 * u + mij_rowslot[v]: the destination's zigzag index ((u, v) -> (v, u) when transposed) and whether the
+ * coefficient changes sign (odd u under a mirrored x, odd v under a mirrored y) */
+struct ConvTable {
+	uint8_t zz[64];
+	bool neg[64];
+};
+template <int TR, int NX, int NY>
+static constexpr ConvTable make_conv_table()
+{
+	constexpr uint8_t rowslot[8] = {0, 4, 2, 5, 1, 6, 3, 7}, row_of_slot[8] = {0, 4, 2, 6, 1, 3, 5, 7};
+	ConvTable t{};
+	for (int P = 0; P < 64; ++P) {
+		const int u = P >> 3, v = row_of_slot[P & 7];
+		t.zz[P] = k_zigzag_of_pos[TR ? 8 * v + rowslot[u] : P];
+		t.neg[P] = (NX && (u & 1)) != (NY && (v & 1));
+	}
+	return t;
+}
+template <int TR, int NX, int NY>
+static constexpr ConvTable k_conv_table = make_conv_table<TR, NX, NY>();
+
+template <int COMPACT, int TR = 0, int NX = 0, int NY = 0>
 __global__ __launch_bounds__(64) void k_coef_units(const CoefSlot *__restrict__ slots, const WorkIdct *__restrict__ work, const uint8_t *__restrict__ coef,
 																	uint8_t *__restrict__ du_base, uint32_t *__restrict__ s_flag)
 {
 	__shared__ int16_t rows[64 * MIJ_CONV_ROW];
 	__shared__ uint32_t unit_of[64];
 	const WorkIdct wk = work[blockIdx.x];
-	const CoefSlot s = slots[wk.img];
+	const CoefSlot &s = slots[wk.img]; /* read in place (scalar loads): a copy indexed by c would live in scratch, 152 bytes per lane */
 	const uint32_t c = wk.comp, tile = wk.first, lane = threadIdx.x;
 	const uint32_t h = c ? 1u : s.lh, v = c ? 1u : s.lv, bw = s.mcu_x * h, nblk = bw * s.mcu_y * v;
 	const uint32_t L = tile * 64u + lane;
@@ -87,25 +121,38 @@ __global__ __launch_bounds__(64) void k_coef_units(const CoefSlot *__restrict__ 
 				val[8 * q + j] = (int)(int16_t)(w[j >> 1] >> (16 * (j & 1)));
 		}
 	}
+	constexpr bool PLAIN = !TR && !NX && !NY; /* orientation 1: the destination is the source */
+	/* the kept extent of the source plane in blocks, and the destination's geometry for this component */
+	const uint32_t ew = PLAIN ? bw : s.ext_x * h, eh = PLAIN ? s.mcu_y * v : s.ext_y * v;
+	const uint32_t dh = PLAIN ? h : (c ? 1u : s.d_lh), dv = PLAIN ? v : (c ? 1u : s.d_lv), dmcu_x = PLAIN ? s.mcu_x : s.d_mcu_x;
+	const uint32_t sbx = L % bw, sby = L / bw;
 	uint32_t u = ~0u;
-	if (live) {
-		const uint32_t bx = L % bw, by = L / bw, mx = bx / h, my = by / v, sx = bx - mx * h, sy = by - my * v;
+	if (live && sbx < ew && sby < eh) {
+		const uint32_t x1 = NX ? ew - 1u - sbx : sbx, y1 = NY ? eh - 1u - sby : sby;
+		const uint32_t bx = TR ? y1 : x1, by = TR ? x1 : y1; /* the block's place in the destination */
+		const uint32_t mx = bx / dh, my = by / dv, sx = bx - mx * dh, sy = by - my * dv;
 		const uint32_t ny = s.ncomp == 1u ? 1u : s.lh * s.lv;
-		u = (my * s.mcu_x + mx) * s.dpm + (c ? ny + c - 1u : sy * h + sx);
+		u = (my * dmcu_x + mx) * s.dpm + (c ? ny + c - 1u : sy * dh + sx);
 		if (u >= s.n_du)
 			u = ~0u;
-		/* the block whose DC predicts this one's */
-		long pb = -1;
+		/* the block whose DC predicts this one's: the destination's previous unit of the component, (px, py) there */
+		uint32_t px = 0, py = 0;
+		bool has = true;
 		if (sx > 0)
-			pb = (long)L - 1;
+			px = bx - 1u, py = by;
 		else if (sy > 0)
-			pb = (long)(by - 1u) * bw + (mx * h + h - 1u);
+			px = mx * dh + dh - 1u, py = by - 1u;
 		else if (mx > 0)
-			pb = (long)(my * v + v - 1u) * bw + (mx * h - 1u);
+			px = mx * dh - 1u, py = my * dv + dv - 1u;
 		else if (my > 0)
-			pb = (long)(my * v - 1u) * bw + (bw - 1u);
+			px = dmcu_x * dh - 1u, py = my * dv - 1u;
+		else
+			has = false;
 		int pred = 0;
-		if (pb >= 0) {
+		if (has) {
+			/* back through the swap and the mirrors to the source plane's block index */
+			const uint32_t qx = TR ? py : px, qy = TR ? px : py;
+			const size_t pb = (size_t)(NY ? eh - 1u - qy : qy) * bw + (NX ? ew - 1u - qx : qx);
 			if (COMPACT)
 				pred = reinterpret_cast<const int16_t *>(coef + s.dc_off[c])[pb];
 			else
@@ -121,7 +168,7 @@ __global__ __launch_bounds__(64) void k_coef_units(const CoefSlot *__restrict__ 
 	unit_of[lane] = u;
 #pragma unroll
 	for (int P = 0; P < 64; ++P)
-		rows[lane * MIJ_CONV_ROW + k_zigzag_of_pos[P]] = (int16_t)val[P];
+		rows[lane * MIJ_CONV_ROW + k_conv_table<TR, NX, NY>.zz[P]] = (int16_t)(k_conv_table<TR, NX, NY>.neg[P] ? -val[P] : val[P]);
 	__syncthreads();
 #pragma unroll
 	for (int i = 0; i < 8; ++i) {

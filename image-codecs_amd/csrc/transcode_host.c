@@ -3,6 +3,7 @@
  * coefficient planes read as the writer's data units, the marker copy, and the whole path on the host (mjh_transcode_memory).  The
  * emission itself is the writer's (jpeg_write_host.c: mjw_temit).
  */
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -135,6 +136,103 @@ int mjw_units_from_region(const mij_image_desc *d, const uint8_t *region, int fo
 	return 1;
 }
 
+/* ---- orientation (mjw_tplan_oriented, include/mij_host.h): mirrors of the source's axes first, then an optional transpose */
+static const unsigned char k_orient_tr[9] = {0, 0, 0, 0, 0, 1, 1, 1, 1}, k_orient_mx[9] = {0, 0, 1, 1, 0, 0, 0, 1, 1},
+									k_orient_my[9] = {0, 0, 0, 1, 1, 0, 1, 1, 0};
+
+/* one mirrored axis: its size in pixels and MCUs after the edge mode; 0 with *reason where the picture is refused */
+static int mirror_axis(const char *axis, const char *name, int *size, int *mcus, int mcu_px, int trim, const char **reason)
+{
+	static _Thread_local char why[2][160]; /* one per axis; static strings as every other reason is */
+	char *w = why[axis[0] == 'y'];
+	if (*size % mcu_px == 0)
+		return 1;
+	if (!trim) {
+		snprintf(w, sizeof(why[0]), "not perfect: the mirrored %s axis (%s %d) is no multiple of the MCU size %d; edge mode trim drops the partial MCU", axis,
+					name, *size, mcu_px);
+		return refuse(reason, w);
+	}
+	if (*size < mcu_px) {
+		snprintf(w, sizeof(why[0]), "nothing left after the trim: the mirrored %s axis (%s %d) is smaller than the MCU size %d", axis, name, *size, mcu_px);
+		return refuse(reason, w);
+	}
+	*mcus = *size / mcu_px;
+	*size = *mcus * mcu_px;
+	return 1;
+}
+
+int mjw_tplan_oriented(mjw_tplan *dst, const mjw_tplan *src, int o, int trim, const char **reason)
+{
+	mjw_tplan t;
+	int w, h, ex, ey, r, c;
+	if (!dst || !src)
+		return refuse(reason, "bad argument");
+	if (o < 1 || o > 8)
+		return refuse(reason, "orientation is not 1..8");
+	if (src->lh < 1 || src->lh > 2 || src->lv < 1 || src->lv > 2 || src->plan.mcu_x < 1 || src->plan.mcu_y < 1)
+		return refuse(reason, "bad source plan");
+	t = *src;
+	w = src->plan.width, h = src->plan.height, ex = src->plan.mcu_x, ey = src->plan.mcu_y;
+	if (k_orient_mx[o] && !mirror_axis("x", "width", &w, &ex, 8 * src->lh, trim, reason))
+		return 0;
+	if (k_orient_my[o] && !mirror_axis("y", "height", &h, &ey, 8 * src->lv, trim, reason))
+		return 0;
+	if (!k_orient_tr[o]) {
+		t.plan.width = w, t.plan.height = h, t.plan.mcu_x = ex, t.plan.mcu_y = ey;
+	} else {
+		t.plan.width = h, t.plan.height = w, t.plan.mcu_x = ey, t.plan.mcu_y = ex;
+		t.lh = src->lv, t.lv = src->lh;
+		for (r = 0; r < 8; ++r)
+			for (c = 0; c < 8; ++c) {
+				t.plan.ytab[k_zigzag_of[8 * r + c]] = src->plan.ytab[k_zigzag_of[8 * c + r]];
+				t.plan.ctab[k_zigzag_of[8 * r + c]] = src->plan.ctab[k_zigzag_of[8 * c + r]];
+			}
+	}
+	*dst = t;
+	return 1;
+}
+
+int mjw_units_orient(const mjw_tplan *src, const int16_t *du_src, int o, int trim, int16_t *du_dst)
+{
+	mjw_tplan t;
+	unsigned char from[64], neg[64];
+	int r, c, k, comp, mx, my, sx, sy;
+	if (!du_src || !du_dst || !mjw_tplan_oriented(&t, src, o, trim, NULL))
+		return 0;
+	{
+		const int tr = k_orient_tr[o], fx = k_orient_mx[o], fy = k_orient_my[o];
+		const int ny = src->ncomp == 1 ? 1 : src->lh * src->lv, dpm = src->plan.du_per_mcu;
+		/* the source's MCUs that stay: the destination's, swapped back */
+		const int ex = tr ? t.plan.mcu_y : t.plan.mcu_x, ey = tr ? t.plan.mcu_x : t.plan.mcu_y;
+		for (r = 0; r < 8; ++r) /* destination (v = r, u = c) takes source (v, u) = (c, r) when transposed; odd source u / v change sign */
+			for (c = 0; c < 8; ++c) {
+				const int sr = tr ? c : r, sc = tr ? r : c;
+				from[k_zigzag_of[8 * r + c]] = k_zigzag_of[8 * sr + sc];
+				neg[k_zigzag_of[8 * r + c]] = (unsigned char)(((fx && (sc & 1)) ? 1 : 0) ^ ((fy && (sr & 1)) ? 1 : 0));
+			}
+		for (my = 0; my < t.plan.mcu_y; ++my)
+			for (mx = 0; mx < t.plan.mcu_x; ++mx)
+				for (comp = 0; comp < t.ncomp; ++comp) {
+					const int dh = comp ? 1 : t.lh, dv = comp ? 1 : t.lv, sh = comp ? 1 : src->lh, sv = comp ? 1 : src->lv;
+					for (sy = 0; sy < dv; ++sy)
+						for (sx = 0; sx < dh; ++sx, du_dst += 64) {
+							const int dbx = mx * dh + sx, dby = my * dv + sy;
+							int bx = tr ? dby : dbx, by = tr ? dbx : dby;
+							const int16_t *s;
+							if (fx)
+								bx = ex * sh - 1 - bx;
+							if (fy)
+								by = ey * sv - 1 - by;
+							s = du_src + 64 * (((size_t)(by / sv) * (size_t)src->plan.mcu_x + (size_t)(bx / sh)) * (size_t)dpm +
+													 (size_t)(comp ? ny + comp - 1 : (by % sv) * sh + bx % sh));
+							for (k = 0; k < 64; ++k)
+								du_dst[k] = neg[k] ? (int16_t)-s[from[k]] : s[from[k]];
+						}
+				}
+	}
+	return 1;
+}
+
 int mjw_copy_markers(const uint8_t *src, int src_len, const unsigned char *stream, size_t stream_len, unsigned char **out, size_t *out_len,
                      const char **reason)
 {
@@ -207,13 +305,13 @@ int mjw_copy_markers(const uint8_t *src, int src_len, const unsigned char *strea
 	return 1;
 }
 
-int mjh_transcode_memory(const uint8_t *src, int len, unsigned flags, unsigned char **out, size_t *out_len, const char **reason)
+int mjw_transcode_memory_at(const uint8_t *src, int len, unsigned flags, int o, int trim, unsigned char **out, size_t *out_len, const char **reason)
 {
 	mij_image_desc d;
-	mjw_tplan t;
+	mjw_tplan t, ts;
 	const char *why = NULL;
 	uint8_t *region = NULL;
-	int16_t *du = NULL;
+	int16_t *du = NULL, *du_src = NULL;
 	unsigned char *buf = NULL;
 	size_t rbytes, nu, cap, n = 0;
 	int ok = 0;
@@ -235,17 +333,20 @@ int mjh_transcode_memory(const uint8_t *src, int len, unsigned flags, unsigned c
 		refuse(reason, why ? why : "decode failed");
 		goto done;
 	}
-	if (!mjw_tplan_from_desc(&t, &d, reason))
+	if (!mjw_tplan_from_desc(&ts, &d, reason) || !mjw_tplan_oriented(&t, &ts, o, trim, reason))
 		goto done;
 	nu = mjw_tplan_du_count(&t);
 	du = (int16_t *)malloc(nu * 64 * sizeof(int16_t));
+	if (o != 1)
+		du_src = (int16_t *)malloc(mjw_tplan_du_count(&ts) * 64 * sizeof(int16_t));
 	cap = MJW_STREAM_CAP(nu);
 	buf = (unsigned char *)malloc(cap);
-	if (!du || !buf) {
+	if (!du || !buf || (o != 1 && !du_src)) {
 		refuse(reason, "out of memory");
 		goto done;
 	}
-	if (!mjw_units_from_region(&d, region, (d.flags & MIJ_FLAG_STAGED_COMPACT) ? MIJ_COEF_COMPACT : MIJ_COEF_INT16, du)) {
+	if (!mjw_units_from_region(&d, region, (d.flags & MIJ_FLAG_STAGED_COMPACT) ? MIJ_COEF_COMPACT : MIJ_COEF_INT16, o != 1 ? du_src : du) ||
+		 (o != 1 && !mjw_units_orient(&ts, du_src, o, trim, du))) {
 		refuse(reason, "units could not be read");
 		goto done;
 	}
@@ -267,6 +368,12 @@ int mjh_transcode_memory(const uint8_t *src, int len, unsigned flags, unsigned c
 done:
 	free(region);
 	free(du);
+	free(du_src);
 	free(buf);
 	return ok;
+}
+
+int mjh_transcode_memory(const uint8_t *src, int len, unsigned flags, unsigned char **out, size_t *out_len, const char **reason)
+{
+	return mjw_transcode_memory_at(src, len, flags, 1, 0, out, out_len, reason);
 }

@@ -1,0 +1,30 @@
+/*
+ * transcode_orient.c -- mjh_transcode_memory_oriented (include/mij_host.h): the lossless transcode on the host with an orientation
+ * applied, the file's own EXIF tag included.  The transform itself is transcode_host.c's (mjw_tplan_oriented, mjw_units_orient,
+ * mjw_transcode_memory_at); this file adds what needs the EXIF walk (exif.c), so that transcode_host.c links without it.
+ */
+#include <limits.h>
+
+#include "mij_host.h"
+
+int mjh_transcode_memory_oriented(const uint8_t *src, int len, unsigned flags, int o, int trim, unsigned char **out, size_t *out_len,
+                                  const char **reason)
+{
+	if (o < 0 || o > 8) {
+		if (out)
+			*out = NULL;
+		if (out_len)
+			*out_len = 0;
+		if (reason)
+			*reason = "orientation is not 0 (the file's tag) or 1..8";
+		return 0;
+	}
+	if (o == 0)
+		o = mjh_exif_orientation(src, len);
+	if (!mjw_transcode_memory_at(src, len, flags, o, trim, out, out_len, reason))
+		return 0;
+	/* the picture is upright now: a copied tag that still said otherwise would turn it a second time */
+	if ((flags & MJW_COPY_MARKERS) && o != 1)
+		(void)mjh_exif_set_orientation(*out, *out_len > (size_t)INT_MAX ? INT_MAX : (int)*out_len, 1);
+	return 1;
+}

@@ -5,7 +5,8 @@ statistics.  The same coefficients, to the bit, in a smaller file: no IDCT, no p
 cross PCIe on the way back.  No pixel kernel is launched.
 
 This module needs no torch."""
-from .binding import Batch, Context, Encoder, HostDecoder, MijError, copy_markers as _copy_markers, emit_transcoded, transcode_plan
+from .binding import Batch, Context, Encoder, HostDecoder, MijError, copy_markers as _copy_markers, emit_transcoded, exif_orientation, \
+    exif_set_orientation, transcode_plan
 
 # one launch takes at most this many pictures / bytes of coefficient arena; larger calls are cut into chunks
 MAX_SLOTS = 4096
@@ -14,6 +15,25 @@ MAX_COEF_BYTES = 2 << 30
 
 def _align(v, a):
     return (v + a - 1) // a * a
+
+
+def _orientations(v, datas):
+    """transcode's orientation= as one value 1..8 per source, the files' own tags read where "exif" is asked"""
+    n = len(datas)
+    what = "orientation must be None, 'exif', 1..8 or one of those per source (got %r)"
+    if v is None or isinstance(v, str) or (isinstance(v, int) and not isinstance(v, bool)):
+        vals = [v] * n
+    else:
+        try:
+            vals = list(v)
+        except TypeError:
+            raise ValueError(what % (v,)) from None
+        if len(vals) != n:
+            raise ValueError("orientation has %d values for %d sources" % (len(vals), n))
+    for o in vals:
+        if not (o is None or o == "exif" or (isinstance(o, int) and not isinstance(o, bool) and 1 <= o <= 8)):
+            raise ValueError(what % (o,))
+    return [1 if o is None else exif_orientation(d) if o == "exif" else o for o, d in zip(vals, datas)]
 
 
 class Transcoder:
@@ -99,7 +119,8 @@ class Transcoder:
             self._enc.reset()
         return self._enc
 
-    def transcode(self, datas, *, optimize=True, copy_markers="all", only_if_smaller=False, gpu_entropy=None, threads=16):
+    def transcode(self, datas, *, optimize=True, copy_markers="all", only_if_smaller=False, gpu_entropy=None, threads=16, orientation=None,
+                  edge="perfect"):
         """datas: a sequence of JPEG files as bytes.  -> a list with, per source, the new stream (bytes) or None; last_reasons[i] is None
         or the reason source i was refused or could not be decoded.
         optimize: Huffman tables built from each picture's own statistics (mjw_temit_optimized's stream); False: the Annex-K tables.
@@ -108,6 +129,13 @@ class Transcoder:
         emitted.  Offsets inside copied segments (MPF and the like) are not fixed up.
         only_if_smaller: the source's own bytes are returned where the result is not shorter.
         gpu_entropy: the front end, as Batch.decode_jpegs takes it (None: the default; True / False: GPU walk where it applies / host).
+        orientation: None (the coefficients as stored), "exif" (each file's own Orientation tag), an int 1..8, or a sequence of those per
+        source, as TensorDecoder.decode takes it: the picture is rotated / flipped / transposed in the coefficients, exactly (jpegtran's
+        set; include/mij_host.h, mjw_tplan_oriented).  Where that changed the picture the transformed stream is returned whatever
+        only_if_smaller says, and copy_markers="all" resets the copied EXIF Orientation tag to 1 (other EXIF fields -- pixel dimensions,
+        the thumbnail -- are left as they are).
+        edge: a mirrored axis that is no multiple of the MCU size cannot be mirrored exactly: "perfect" refuses that picture (its reason
+        names the axis), "trim" drops the partial MCU column / row of the mirrored axes (jpegtran -trim).
         ValueError, before a device is touched, for arguments that are not of these kinds."""
         if not isinstance(optimize, bool) or not isinstance(only_if_smaller, bool):
             raise ValueError("optimize and only_if_smaller must be bools")
@@ -117,6 +145,8 @@ class Transcoder:
             raise ValueError("gpu_entropy must be None, True or False")
         if isinstance(threads, bool) or not isinstance(threads, int) or threads < 1:
             raise ValueError("threads must be a positive int")
+        if edge not in ("perfect", "trim"):
+            raise ValueError("edge must be 'perfect' or 'trim', got %r" % (edge,))
         if isinstance(datas, (bytes, bytearray, memoryview, str)):
             raise ValueError("datas is a sequence of JPEG files, not one file")
         datas = list(datas)
@@ -124,6 +154,7 @@ class Transcoder:
             if not isinstance(d, (bytes, bytearray, memoryview)):
                 raise ValueError("source %d is not bytes" % i)
         datas = [bytes(d) for d in datas]
+        orients = _orientations(orientation, datas)
         out = [None] * len(datas)
         reasons = [None] * len(datas)
         self.last_host_emitted = 0
@@ -151,7 +182,7 @@ class Transcoder:
             while j < len(todo) and j - k < MAX_SLOTS and (j == k or coef + todo[j][1] <= MAX_COEF_BYTES):
                 coef += todo[j][1]
                 j += 1
-            self._chunk(datas, todo[k:j], out, reasons, optimize, gpu_entropy, threads)
+            self._chunk(datas, todo[k:j], out, reasons, optimize, gpu_entropy, threads, orients, edge == "trim")
             k = j
         for i, d in enumerate(datas):
             if out[i] is None:
@@ -161,12 +192,14 @@ class Transcoder:
                 if out[i] is None:
                     reasons[i] = "markers: " + why
                     continue
-            if only_if_smaller and len(out[i]) >= len(d):
+                if orients[i] != 1:  # the picture is upright now: the copied tag must not turn it again
+                    out[i], _ = exif_set_orientation(out[i], 1)
+            if only_if_smaller and orients[i] == 1 and len(out[i]) >= len(d):
                 out[i] = d
         self.last_reasons = reasons
         return out
 
-    def _chunk(self, datas, items, out, reasons, optimize, gpu_entropy, threads):
+    def _chunk(self, datas, items, out, reasons, optimize, gpu_entropy, threads, orients, trim):
         n = len(items)
         srcs = [datas[it[0]] for it in items]
         stream = 0
@@ -188,7 +221,7 @@ class Transcoder:
                 reasons[it[0]] = r or "decode failed"
                 continue
             try:
-                es[it[0]] = enc.add_coef(b, sl)
+                es[it[0]] = enc.add_coef(b, sl, orients[it[0]], trim)
             except MijError as e:
                 reasons[it[0]] = str(e).split(": ", 1)[-1]
                 continue

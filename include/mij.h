@@ -697,9 +697,17 @@ int mij_enc_slot_optimized(const mij_encoder *e, int slot);
  * (it did not fit the arena: finish it on the host from its units) or MIJ_ENC_SLOT_UNCODABLE (never for slots that are not coefficient
  * slots); mij_last_error says the same in words.
  * mij_enc_coef_ms: measurement: milliseconds the conversion kernels of the last mij_enc_upload took, -1 when there were none.
+ *
+ * mij_enc_add_coef_oriented: the same slot with one of the eight EXIF orientations applied to the coefficients on the way (lossless
+ * rotate / flip / transpose; the numbering is mij_batch_set_out_tensor_oriented's, the rules and the two edge modes are written in
+ * mij_host.h, mjw_tplan_oriented).  The conversion kernel permutes the blocks, transposes them and changes the signs; the slot's plan
+ * (mij_enc_tplan), units (mij_enc_fetch) and stream are the DESTINATION picture's, and codability is judged in its unit order.  MIJ_E_ARG
+ * with the host's reason ("not transformable: ...") for an orientation outside 1..8, for a picture with a partial MCU on a mirrored axis
+ * when trim is 0, and for one with nothing left after the trim.  mij_enc_add_coef is this with (1, 0).
  */
 enum { MIJ_ENC_SLOT_OK = 0, MIJ_ENC_SLOT_NO_ROOM = 1, MIJ_ENC_SLOT_UNCODABLE = 2 };
 int mij_enc_add_coef(mij_encoder *e, mij_batch *b, int slot);
+int mij_enc_add_coef_oriented(mij_encoder *e, mij_batch *b, int slot, int orientation, int trim);
 int mij_enc_slot_status(const mij_encoder *e, int slot);
 int mij_enc_coef_ms(mij_encoder *e, float *ms);
 

@@ -242,6 +242,51 @@ int mjw_copy_markers(const uint8_t *src, int src_len, const unsigned char *strea
 int mjh_transcode_memory(const uint8_t *src, int len, unsigned flags, unsigned char **out, size_t *out_len, const char **reason);
 int mij_enc_tplan(const mij_encoder *e, int slot, mjw_tplan *out);
 
+/*
+ * Lossless reorientation in the transcode (jpegtran -rotate / -flip / -transpose, exiftran -a): the eight EXIF orientations applied to the
+ * coefficients, exactly, without decoding.  On the GPU: mij_enc_add_coef_oriented (mij.h); these calls are the written contract.
+ *
+ * NUMBERING.  Orientation o is 1..8 with the meaning mij.h gives it for mij_batch_set_out_tensor_oriented: the displayed picture D, in
+ * numpy on the stored picture S, is  1: S   2: S[:, ::-1]   3: S[::-1, ::-1]   4: S[::-1]   5: S.T   6: S[::-1].T   7: S[::-1, ::-1].T
+ * 8: S[:, ::-1].T -- mirrors of SOURCE axes first (x for o = 2, 3, 7, 8; y for o = 3, 4, 6, 7), then a transpose for o >= 5.
+ *
+ * BLOCK RULES, per component, u the horizontal and v the vertical frequency (in the planes' position order P = 8 * u + mij_rowslot[v],
+ * i.e. unit coefficient k sits at u = mij_zigzag_pos[k] >> 3, mij_rowslot[v] = mij_zigzag_pos[k] & 7):
+ *   mirror of source x   block column bx -> BW - 1 - bx, BW the component's block columns after the trim; the coefficient at (u, v) is
+ *                        negated where u is odd
+ *   mirror of source y   the same with rows, BH and v
+ *   transpose            block (bx, by) -> (by, bx); coefficient (u, v) -> (v, u); luma factors (h, v) -> (v, h), so 4:2:2 and 4:4:0 swap
+ *                        while 4:4:4, 4:2:0 and grey keep their kind; mcu_x and mcu_y swap; width and height swap; both quantisation
+ *                        tables are transposed (Cb and Cr keep sharing theirs)
+ * The destination's units are in the writer's unit order OF THE DESTINATION picture (above, with the destination's geometry); DC
+ * differences, and so codability, are judged in that order.  AC codability does not depend on o.
+ *
+ * PARTIAL MCUS.  A mirrored source axis whose size is no multiple of the source's MCU size on that axis (8 * lh wide, 8 * lv high; 8 for
+ * grey) cannot be mirrored exactly: its partial MCU would have to become the first.  trim = 0 (perfect) refuses such a picture with a
+ * reason that names the axis, its size and the MCU size; trim = 1 drops the partial MCU column / row of the MIRRORED axes only
+ * (jpegtran -trim): the size on that axis becomes the largest multiple of the MCU size, and a picture with nothing left is refused.  Axes
+ * that are not mirrored keep their partial MCU, padding blocks included, exactly as the planes hold them.
+ *
+ *   mjw_tplan_oriented        the destination's plan from a source's; 0 with *reason (a static or per-thread string, valid until the
+ *                             thread's next call) for o outside 1..8 and the refusals above.  o = 1 copies the plan.
+ *   mjw_units_orient          the destination's units from the source's (mjw_units_from_region's order, of the src plan); du_dst holds
+ *                             mjw_tplan_du_count(destination) units.  0 where mjw_tplan_oriented refuses.  mjw_temit* run unchanged on
+ *                             the destination plan and units.
+ *   mjw_transcode_memory_at   mjh_transcode_memory with o in 1..8 and an edge mode, the part that needs no EXIF code; copied markers are
+ *                             the source's, untouched.  mjh_transcode_memory is this with (1, 0).
+ *   mjh_transcode_memory_oriented   the whole thing: o = 0 means the file's own tag (mjh_exif_orientation).  When markers are copied and
+ *                             o != 1, the Orientation entry mjh_exif_orientation reads is rewritten to 1 in the copied APP1
+ *                             (mjh_exif_set_orientation): the coefficients are upright now, and a viewer would turn them again.  NOT fixed:
+ *                             every other EXIF field (PixelXDimension / PixelYDimension, the thumbnail of IFD1 and its own tag) and offsets
+ *                             inside other segments stay as the source has them.
+ */
+int mjw_tplan_oriented(mjw_tplan *dst, const mjw_tplan *src, int o, int trim, const char **reason);
+int mjw_units_orient(const mjw_tplan *src, const int16_t *du_src, int o, int trim, int16_t *du_dst);
+int mjw_transcode_memory_at(const uint8_t *src, int len, unsigned flags, int o, int trim, unsigned char **out, size_t *out_len,
+                            const char **reason);
+int mjh_transcode_memory_oriented(const uint8_t *src, int len, unsigned flags, int o, int trim, unsigned char **out, size_t *out_len,
+                                  const char **reason);
+
 /* The tables of stbi__ldr_to_hdr (common.c:391-424) for mij_batch_set_out_f32: lut[256*k + v] for channel k < n_out.  Colour
  * channels (all of them for odd n_out, all but the last for even n_out) get (float)(pow(v / 255.0f, gamma) * scale), the
  * alpha channel of n_out 2 and 4 gets v / 255.0f -- the reference's expressions, evaluated with libm's pow. */
@@ -260,6 +305,10 @@ int mjh_resize_coeffs(int in, int out, int filter, int32_t *lo_n, int32_t *k, si
  * 0x0112, type SHORT and count 1.  Every offset is checked against that segment, and a directory that does not fit it gives 1, as
  * does a value outside 1..8.  stbi_* and the rest of the library ignore the tag, as the reference does. */
 int mjh_exif_orientation(const uint8_t *buf, int len);
+/* Sets that entry: the same walk with the same bounds checks, then the entry's two value bytes are overwritten in place with `value`
+ * (1..8) in the TIFF block's byte order.  1 when an entry was patched; 0, and the buffer untouched, where the walk finds no Orientation
+ * entry of one SHORT (mjh_exif_orientation's "cannot read" cases) or value is outside 1..8.  Nothing else of the file changes. */
+int mjh_exif_set_orientation(uint8_t *buf, int len, int value);
 
 #ifdef __cplusplus
 }
