@@ -54,6 +54,10 @@ from .binding import (  # noqa: F401
     transcode_memory,
     transcode_plan_oriented,
     units_orient,
+    quality_tables,
+    requant_magic,
+    transcode_plan_requant,
+    units_requant,
     write_histogram,
     optimal_huffman_table,
     MJW_OPTIMIZE_HUFFMAN,

@@ -1336,14 +1336,86 @@ def copy_markers(src, stream):
     return _take_malloced(out, n.value), None
 
 
-def transcode_memory(data, optimize=False, copy_markers=False, orientation=None, trim=False):
+def _qtable_pair(tables):
+    """(luma, chroma), 64 ints 1..255 each in zigzag order -> two 64-byte strings; ValueError for anything else"""
+    what = "qtables must be a (luma, chroma) pair of 64 ints 1..255 each, in zigzag order"
+    try:
+        pair = [list(t) for t in tables]
+    except TypeError:
+        raise ValueError(what) from None
+    if len(pair) != 2 or any(len(t) != 64 for t in pair):
+        raise ValueError(what)
+    for t in pair:
+        for v in t:
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 1 <= v <= 255:
+                raise ValueError(what + " (got %r)" % (v,))
+    return bytes(int(v) for v in pair[0]), bytes(int(v) for v in pair[1])
+
+
+def quality_tables(quality):
+    """mjw_quality_tables: the (luma, chroma) tables the writer uses at quality 1..100, uint8 [64] each in zigzag order; None outside"""
+    L = lib()
+    L.mjw_quality_tables.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+    luma, chroma = np.zeros(64, np.uint8), np.zeros(64, np.uint8)
+    if not L.mjw_quality_tables(int(quality), luma.ctypes.data_as(C.c_void_p), chroma.ctypes.data_as(C.c_void_p)):
+        return None
+    return luma, chroma
+
+
+def requant_magic(b):
+    """mjw_requant_magic -> (m, inc): n // b == ((n + inc) * m) >> 32 for every n < 2^24, the division of the conversion kernel"""
+    L = lib()
+    L.mjw_requant_magic.argtypes = [C.c_int, C.POINTER(C.c_uint32)]
+    L.mjw_requant_magic.restype = C.c_uint32
+    inc = C.c_uint32()
+    m = L.mjw_requant_magic(int(b), C.byref(inc))
+    return int(m), int(inc.value)
+
+
+def transcode_plan_requant(tplan, tables, coarsen_only=True):
+    """mjw_tplan_requant: the plan with its tables replaced -> (TranscodePlan, changed), or (None, reason) where it is refused.  tables
+    are passed as they are (uint8 [64] each), so that a zero entry reaches the library."""
+    L = lib()
+    L.mjw_tplan_requant.argtypes = [C.POINTER(TranscodePlan), C.POINTER(TranscodePlan), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_char_p)]
+    luma, chroma = (np.ascontiguousarray(t, np.uint8) for t in tables)
+    assert luma.shape == (64,) and chroma.shape == (64,)
+    t, why = TranscodePlan(), C.c_char_p()
+    r = L.mjw_tplan_requant(C.byref(t), C.byref(tplan), luma.ctypes.data_as(C.c_void_p), chroma.ctypes.data_as(C.c_void_p), int(bool(coarsen_only)),
+                            C.byref(why))
+    if not r:
+        return None, (why.value.decode() if why.value else "refused")
+    return t, r == 2
+
+
+def units_requant(src, dst, du):
+    """mjw_units_requant: the units of plan src (tables s) requantised for plan dst (tables d) -> int16 [n_du, 64]; None on bad arguments"""
+    L = lib()
+    L.mjw_units_requant.argtypes = [C.POINTER(TranscodePlan), C.POINTER(TranscodePlan), C.c_void_p, C.c_void_p]
+    d = np.ascontiguousarray(du, np.int16)
+    if d.size != src.du_elems():
+        raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, src.du_elems()))
+    out = np.empty(dst.du_elems(), np.int16)
+    if not L.mjw_units_requant(C.byref(src), C.byref(dst), d.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)):
+        return None
+    return out.reshape(-1, 64)
+
+
+def transcode_memory(data, optimize=False, copy_markers=False, orientation=None, trim=False, tables=None, coarsen_only=True):
     """mjh_transcode_memory, the lossless transcode on the host alone -> (bytes, None) or (None, reason).  With an orientation
-    (1..8, or "exif" for the file's own tag) it is mjh_transcode_memory_oriented; trim chooses its edge mode."""
+    (1..8, or "exif" for the file's own tag) it is mjh_transcode_memory_oriented; trim chooses its edge mode.  With tables = (luma,
+    chroma) it is mjh_transcode_memory_requant: the coefficients requantised after the orientation."""
     L = lib()
     data = bytes(data)
     out, n, why = C.c_void_p(), C.c_size_t(), C.c_char_p()
     flags = (MJW_OPTIMIZE_HUFFMAN if optimize else 0) | (MJW_COPY_MARKERS if copy_markers else 0)
-    if orientation is None:
+    if tables is not None:
+        luma, chroma = _qtable_pair(tables)
+        L.mjh_transcode_memory_requant.argtypes = [C.c_char_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_int,
+                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_char_p)]
+        o = 1 if orientation is None else 0 if orientation == "exif" else int(orientation)
+        ok = L.mjh_transcode_memory_requant(data, len(data), flags, o, int(bool(trim)), luma, chroma, int(bool(coarsen_only)), C.byref(out),
+                                            C.byref(n), C.byref(why))
+    elif orientation is None:
         L.mjh_transcode_memory.argtypes = [C.c_char_p, C.c_int, C.c_uint, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_char_p)]
         ok = L.mjh_transcode_memory(data, len(data), flags, C.byref(out), C.byref(n), C.byref(why))
     else:
@@ -1576,17 +1648,30 @@ class Encoder:
             raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, plan.du_elems()))
         return _check(L.mij_enc_add_units(self._h, int(width), int(height), int(comp), int(quality), d.ctypes.data_as(C.c_void_p)), "mij_enc_add_units")
 
-    def add_coef(self, batch, slot, orientation=1, trim=False):
+    def add_coef(self, batch, slot, orientation=1, trim=False, tables=None, coarsen_only=True):
         """mij_enc_add_coef: a slot whose units are the quantised coefficients of an uploaded Batch's slot (lossless transcode).
         MijError with the reason for a picture that is not transcodable.  The batch must stay as it is until wait() or a fetch.
         orientation 1..8 and trim: mij_enc_add_coef_oriented, the coefficients reoriented on the way (the slot's plan, units and stream
-        are the destination's); MijError with the reason for a picture the edge mode refuses."""
+        are the destination's); MijError with the reason for a picture the edge mode refuses.
+        tables = (luma, chroma), 64 entries 1..255 each in zigzag order: mij_enc_add_coef_requant, the coefficients requantised to those
+        tables (their entry-wise maximum with the source's when coarsen_only) after the orientation."""
         L = lib()
+        if tables is not None:
+            luma, chroma = _qtable_pair(tables)
+            L.mij_enc_add_coef_requant.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_int]
+            return _check(L.mij_enc_add_coef_requant(self._h, batch._h, int(slot), int(orientation), int(bool(trim)), luma, chroma,
+                                                     int(bool(coarsen_only))), "mij_enc_add_coef_requant")
         if orientation == 1 and not trim:
             L.mij_enc_add_coef.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
             return _check(L.mij_enc_add_coef(self._h, batch._h, int(slot)), "mij_enc_add_coef")
         L.mij_enc_add_coef_oriented.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
         return _check(L.mij_enc_add_coef_oriented(self._h, batch._h, int(slot), int(orientation), int(bool(trim))), "mij_enc_add_coef_oriented")
+
+    def slot_requantized(self, slot):
+        """mij_enc_slot_requantized: whether add_coef's tables changed an entry of the slot's plan (false: a plain lossless slot)"""
+        L = lib()
+        L.mij_enc_slot_requantized.argtypes = [C.c_void_p, C.c_int]
+        return bool(_check(L.mij_enc_slot_requantized(self._h, int(slot)), "mij_enc_slot_requantized"))
 
     def tplan(self, slot):
         """mij_enc_tplan: the TranscodePlan of a slot made by add_coef"""

@@ -348,23 +348,38 @@ static int emit_du(jw_sink *s, const int16_t *du, int dc_pred, const enc_table *
  *                         data unit (:283-352 minus the Huffman calls): DU blocks, MCU order, zigzag order
  *   3. mjw_emit           headers (:245-268), Huffman emission (:120-169), padding and EOI (:358-363)
  */
-int mjw_plan_init(mjw_plan *p, int width, int height, int comp, int quality)
+
+/* the two tables at a quality in 1..100, zigzag order: mjw_plan_init's, and mjw_quality_tables' for the requantising transcode */
+static void quality_tables(int quality, unsigned char *ytab, unsigned char *ctab)
 {
-	static const float aasf[8] = {1.0f * 2.828427125f,         1.387039845f * 2.828427125f, 1.306562965f * 2.828427125f, 1.175875602f * 2.828427125f,
-											1.0f * 2.828427125f,         0.785694958f * 2.828427125f, 0.541196100f * 2.828427125f, 0.275899379f * 2.828427125f};
-	int i, row, col, k, mcu;
-	if (!p || !width || !height || comp > 4 || comp < 1 || width < 0 || height < 0)
-		return 0;
-	quality = quality ? quality : 90;
-	p->subsample = quality <= 90 ? 1 : 0;
-	quality = quality < 1 ? 1 : (quality > 100 ? 100 : quality);
+	int i;
 	quality = quality < 50 ? 5000 / quality : 200 - quality * 2;
 	for (i = 0; i < 64; ++i) {
 		int yq = (k_qt_lum[i] * quality + 50) / 100;
 		int cq = (k_qt_chr[i] * quality + 50) / 100;
-		p->ytab[k_zigzag_of[i]] = (unsigned char)(yq < 1 ? 1 : (yq > 255 ? 255 : yq));
-		p->ctab[k_zigzag_of[i]] = (unsigned char)(cq < 1 ? 1 : (cq > 255 ? 255 : cq));
+		ytab[k_zigzag_of[i]] = (unsigned char)(yq < 1 ? 1 : (yq > 255 ? 255 : yq));
+		ctab[k_zigzag_of[i]] = (unsigned char)(cq < 1 ? 1 : (cq > 255 ? 255 : cq));
 	}
+}
+
+int mjw_quality_tables(int quality, unsigned char luma[64], unsigned char chroma[64])
+{
+	if (!luma || !chroma || quality < 1 || quality > 100)
+		return 0;
+	quality_tables(quality, luma, chroma);
+	return 1;
+}
+
+int mjw_plan_init(mjw_plan *p, int width, int height, int comp, int quality)
+{
+	static const float aasf[8] = {1.0f * 2.828427125f,         1.387039845f * 2.828427125f, 1.306562965f * 2.828427125f, 1.175875602f * 2.828427125f,
+											1.0f * 2.828427125f,         0.785694958f * 2.828427125f, 0.541196100f * 2.828427125f, 0.275899379f * 2.828427125f};
+	int row, col, k, mcu;
+	if (!p || !width || !height || comp > 4 || comp < 1 || width < 0 || height < 0)
+		return 0;
+	quality = quality ? quality : 90;
+	p->subsample = quality <= 90 ? 1 : 0;
+	quality_tables(quality < 1 ? 1 : (quality > 100 ? 100 : quality), p->ytab, p->ctab);
 	for (row = 0, k = 0; row < 8; ++row)
 		for (col = 0; col < 8; ++col, ++k) {
 			p->fdtbl_y[k] = 1 / (p->ytab[k_zigzag_of[k]] * aasf[row] * aasf[col]);

@@ -3200,6 +3200,7 @@ struct EncSlot {
 	mij_batch *src;
 	CoefSlot coef;
 	int coef_fmt;
+	unsigned char rq_from[2][64]; /* a requantising slot (coef.rq != 0): the tables tp's replaced, luma and chroma, zigzag order */
 };
 
 struct mij_encoder {
@@ -3262,6 +3263,8 @@ struct mij_encoder {
 	size_t cslot_cap;
 	WorkIdct *h_cwork, *d_cwork;
 	size_t cwork_cap;
+	RqTable *h_rqt, *d_rqt; /* one per requantising slot of the upload (CoefSlot::rq - 1) */
+	size_t rqt_cap;
 	uint32_t *d_sflag;
 	size_t sflag_cap;
 	hipEvent_t ev_coef;
@@ -3370,6 +3373,8 @@ extern "C" int mij_enc_create_ex(mij_ctx *ctx, int max_images, size_t stage_byte
 	e->d_freq = e->d_optok = nullptr;
 	e->h_cslot = e->d_cslot = nullptr;
 	e->h_cwork = e->d_cwork = nullptr;
+	e->h_rqt = e->d_rqt = nullptr;
+	e->rqt_cap = 0;
 	e->d_sflag = nullptr;
 	e->cslot_cap = e->cwork_cap = e->sflag_cap = 0;
 	e->ev_coef = e->ev_conv0 = e->ev_conv1 = nullptr;
@@ -3438,6 +3443,8 @@ extern "C" void mij_enc_destroy(mij_encoder *e)
 	free_dev(e->d_cslot);
 	free_host(e->h_cwork);
 	free_dev(e->d_cwork);
+	free_host(e->h_rqt);
+	free_dev(e->d_rqt);
 	free_dev(e->d_sflag);
 	if (e->ev_coef)
 		(void)hipEventDestroy(e->ev_coef);
@@ -3528,6 +3535,7 @@ static int enc_add_common(mij_encoder *e, const mjw_plan &plan, const void *pixe
 	s.coef_fmt = 0;
 	memset(&s.tp, 0, sizeof(s.tp));
 	memset(&s.coef, 0, sizeof(s.coef));
+	memset(s.rq_from, 0, sizeof(s.rq_from));
 	s.pix_bytes = !enc_has_pixels(kind) ? 0 : align_up((size_t)s.pad_w * plan.height * 3, 256); /* staged as packed RGB whatever plan.comp is (enc_stage_rows) */
 	s.du_bytes = align_up(mjw_plan_du_count(&plan) * 128, 256);
 	if (e->pix_used + s.pix_bytes > e->pix_cap)
@@ -4104,7 +4112,8 @@ extern "C" int mij_enc_add_units(mij_encoder *e, int width, int height, int comp
 
 /* ---- coefficient slots (lossless transcode): a decode batch's planes become the slot's data units on the device */
 
-extern "C" int mij_enc_add_coef_oriented(mij_encoder *e, mij_batch *b, int slot, int orientation, int trim)
+extern "C" int mij_enc_add_coef_requant(mij_encoder *e, mij_batch *b, int slot, int orientation, int trim, const unsigned char *luma,
+                                        const unsigned char *chroma, int coarsen_only)
 {
 	if (!e || !b)
 		return set_err(MIJ_E_ARG, "bad argument");
@@ -4117,12 +4126,18 @@ extern "C" int mij_enc_add_coef_oriented(mij_encoder *e, mij_batch *b, int slot,
 		return set_err(MIJ_E_ARG, "mij_enc_add_coef: batch slot %d was rejected by the entropy stage", slot);
 	if (!b->uploaded)
 		return set_err(MIJ_E_ARG, "mij_enc_add_coef: the planes of batch slot %d are not in device memory yet (mij_batch_upload first)", slot);
-	mjw_tplan sp, tp; /* the source's plan (the planes' geometry) and the destination's (the stream's) */
+	if (!luma != !chroma)
+		return set_err(MIJ_E_ARG, "mij_enc_add_coef_requant: one table without the other");
+	mjw_tplan sp, op, tp; /* the source's plan (the planes' geometry), the oriented one, and the destination's (the stream's) */
 	const char *why = nullptr;
 	if (!mjw_tplan_from_desc(&sp, &bs.desc, &why))
 		return set_err(MIJ_E_ARG, "not transcodable: %s", why ? why : "refused");
-	if (!mjw_tplan_oriented(&tp, &sp, orientation, trim, &why))
+	if (!mjw_tplan_oriented(&op, &sp, orientation, trim, &why))
 		return set_err(MIJ_E_ARG, "not transformable: %s", why ? why : "refused");
+	tp = op;
+	int rq = 1; /* mjw_tplan_requant's answer: 2 where a table entry changes */
+	if (luma && !(rq = mjw_tplan_requant(&tp, &op, luma, chroma, coarsen_only, &why)))
+		return set_err(MIJ_E_ARG, "not requantisable: %s", why ? why : "refused");
 	const size_t nu = mjw_tplan_du_count(&tp);
 	if (mjw_tplan_du_count(&sp) > UINT32_MAX / 64)
 		return set_err(MIJ_E_ARG, "not transcodable: too many data units");
@@ -4155,7 +4170,15 @@ extern "C" int mij_enc_add_coef_oriented(mij_encoder *e, mij_batch *b, int slot,
 	s.coef.ext_x = (uint32_t)(tr ? tp.plan.mcu_y : tp.plan.mcu_x);
 	s.coef.ext_y = (uint32_t)(tr ? tp.plan.mcu_x : tp.plan.mcu_y);
 	s.coef.orient = (orient_mx[orientation] ? MIJ_CONV_NX : 0u) | (orient_my[orientation] ? MIJ_CONV_NY : 0u) | (tr ? MIJ_CONV_TR : 0u);
+	s.coef.rq = rq == 2 ? 1u : 0u; /* enc_coef_convert numbers the tables */
+	memcpy(s.rq_from[0], op.plan.ytab, 64);
+	memcpy(s.rq_from[1], op.plan.ctab, 64);
 	return es;
+}
+
+extern "C" int mij_enc_add_coef_oriented(mij_encoder *e, mij_batch *b, int slot, int orientation, int trim)
+{
+	return mij_enc_add_coef_requant(e, b, slot, orientation, trim, nullptr, nullptr, 0);
 }
 
 extern "C" int mij_enc_add_coef(mij_encoder *e, mij_batch *b, int slot) { return mij_enc_add_coef_oriented(e, b, slot, 1, 0); }
@@ -4166,6 +4189,13 @@ extern "C" int mij_enc_tplan(const mij_encoder *e, int slot, mjw_tplan *out)
 		return set_err(MIJ_E_ARG, "bad slot, or not a coefficient slot");
 	*out = e->slots[(size_t)slot].tp;
 	return MIJ_OK;
+}
+
+extern "C" int mij_enc_slot_requantized(const mij_encoder *e, int slot)
+{
+	if (!e || slot < 0 || slot >= (int)e->slots.size() || e->slots[(size_t)slot].kind != ENC_COEF)
+		return set_err(MIJ_E_ARG, "bad slot, or not a coefficient slot");
+	return e->slots[(size_t)slot].coef.rq ? 1 : 0;
 }
 
 extern "C" int mij_enc_slot_status(const mij_encoder *e, int slot)
@@ -4197,24 +4227,25 @@ extern "C" int mij_enc_coef_ms(mij_encoder *e, float *ms)
 	return MIJ_OK;
 }
 
-/* k_coef_units' instances by [compact][MIJ_CONV_NX | MIJ_CONV_NY | MIJ_CONV_TR] */
-typedef void (*coef_units_fn)(const CoefSlot *, const WorkIdct *, const uint8_t *, uint8_t *, uint32_t *);
-#define MIJ_CONV_ROW_OF(C) \
-	{k_coef_units<C, 0, 0, 0>, k_coef_units<C, 0, 1, 0>, k_coef_units<C, 0, 0, 1>, k_coef_units<C, 0, 1, 1>, \
-	 k_coef_units<C, 1, 0, 0>, k_coef_units<C, 1, 1, 0>, k_coef_units<C, 1, 0, 1>, k_coef_units<C, 1, 1, 1>}
-static const coef_units_fn k_coef_units_of[2][8] = {MIJ_CONV_ROW_OF(0), MIJ_CONV_ROW_OF(1)};
+/* k_coef_units' instances by [requantising][compact][MIJ_CONV_NX | MIJ_CONV_NY | MIJ_CONV_TR] */
+typedef void (*coef_units_fn)(const CoefSlot *, const WorkIdct *, const uint8_t *, uint8_t *, uint32_t *, const RqTable *);
+#define MIJ_CONV_ROW_OF(C, R) \
+	{k_coef_units<C, 0, 0, 0, R>, k_coef_units<C, 0, 1, 0, R>, k_coef_units<C, 0, 0, 1, R>, k_coef_units<C, 0, 1, 1, R>, \
+	 k_coef_units<C, 1, 0, 0, R>, k_coef_units<C, 1, 1, 0, R>, k_coef_units<C, 1, 0, 1, R>, k_coef_units<C, 1, 1, 1, R>}
+static const coef_units_fn k_coef_units_of[2][2][8] = {{MIJ_CONV_ROW_OF(0, 0), MIJ_CONV_ROW_OF(1, 0)}, {MIJ_CONV_ROW_OF(0, 1), MIJ_CONV_ROW_OF(1, 1)}};
 #undef MIJ_CONV_ROW_OF
 
 /* The conversion kernel of the coefficient slots, queued at upload in place of a copy of units: behind an event on every source
- * batch's stream, one launch per (batch, plane format, orientation's template instance) over a list of plane tiles.  The flags are cleared whenever the emission may
+ * batch's stream, one launch per (batch, plane format, orientation's template instance, plain or requantising) over a list of plane tiles.  The flags are cleared whenever the emission may
  * read them. */
 static int enc_coef_convert(mij_encoder *e)
 {
 	const size_t n = e->slots.size();
-	size_t nc = 0, nw = 0;
+	size_t nc = 0, nw = 0, nq = 0;
 	for (const EncSlot &s : e->slots)
 		if (s.kind == ENC_COEF) {
 			++nc;
+			nq += s.coef.rq ? 1 : 0;
 			nw += ((size_t)s.coef.mcu_x * s.coef.mcu_y * s.coef.lh * s.coef.lv + 63) / 64 + (s.coef.ncomp == 3 ? 2 * (((size_t)s.coef.mcu_x * s.coef.mcu_y + 63) / 64) : 0);
 		}
 	e->has_coef = nc != 0;
@@ -4223,9 +4254,11 @@ static int enc_coef_convert(mij_encoder *e)
 		return MIJ_OK;
 	if (nw > UINT32_MAX)
 		return set_err(MIJ_E_ARG, "too many plane tiles to convert in one launch");
-	if (nc > e->cslot_cap || nw > e->cwork_cap || n > e->sflag_cap)
+	if (nc > e->cslot_cap || nw > e->cwork_cap || n > e->sflag_cap || nq > e->rqt_cap)
 		HIP_TRY(hipStreamSynchronize(e->stream));
 	int rc = grow_pair(e->h_cslot, e->d_cslot, e->cslot_cap, nc);
+	if (rc == MIJ_OK)
+		rc = grow_pair(e->h_rqt, e->d_rqt, e->rqt_cap, nq);
 	if (rc == MIJ_OK)
 		rc = grow_pair(e->h_cwork, e->d_cwork, e->cwork_cap, nw);
 	if (rc == MIJ_OK)
@@ -4237,11 +4270,12 @@ static int enc_coef_convert(mij_encoder *e)
 		HIP_TRY(hipEventCreate(&e->ev_conv0));
 		HIP_TRY(hipEventCreate(&e->ev_conv1));
 	}
-	/* groups: slots of one batch, one plane format and one template instance (orientation) are contiguous in the lists */
+	/* groups: slots of one batch, one plane format and one template instance (orientation; plain or requantising) are contiguous in the lists */
 	struct Group {
 		mij_batch *b;
 		int fmt;
 		uint32_t orient;
+		bool rq;
 		size_t first, count;
 	};
 	std::vector<Group> groups;
@@ -4250,19 +4284,23 @@ static int enc_coef_convert(mij_encoder *e)
 		if (s.kind == ENC_COEF) {
 			bool seen = false;
 			for (const Group &g : groups)
-				seen = seen || (g.b == s.src && g.fmt == s.coef_fmt && g.orient == s.coef.orient);
+				seen = seen || (g.b == s.src && g.fmt == s.coef_fmt && g.orient == s.coef.orient && g.rq == (s.coef.rq != 0));
 			if (!seen)
-				groups.push_back(Group{s.src, s.coef_fmt, s.coef.orient, 0, 0});
+				groups.push_back(Group{s.src, s.coef_fmt, s.coef.orient, s.coef.rq != 0, 0, 0});
 			if (std::find(batches.begin(), batches.end(), s.src) == batches.end())
 				batches.push_back(s.src);
 		}
-	size_t k = 0, w = 0;
+	size_t k = 0, w = 0, q = 0;
 	for (Group &g : groups) {
 		g.first = w;
 		for (const EncSlot &s : e->slots) {
-			if (s.kind != ENC_COEF || s.src != g.b || s.coef_fmt != g.fmt || s.coef.orient != g.orient)
+			if (s.kind != ENC_COEF || s.src != g.b || s.coef_fmt != g.fmt || s.coef.orient != g.orient || g.rq != (s.coef.rq != 0))
 				continue;
 			e->h_cslot[k] = s.coef;
+			if (g.rq) {
+				rq_fill(e->h_rqt[q], (s.coef.orient & MIJ_CONV_TR) != 0, s.rq_from[0], s.tp.plan.ytab, s.rq_from[1], s.tp.plan.ctab);
+				e->h_cslot[k].rq = (uint32_t)++q;
+			}
 			for (uint32_t c = 0; c < s.coef.ncomp; ++c) {
 				const size_t nblk = (size_t)s.coef.mcu_x * s.coef.mcu_y * (c ? 1u : s.coef.lh * s.coef.lv);
 				for (size_t t = 0; t < (nblk + 63) / 64; ++t)
@@ -4274,6 +4312,8 @@ static int enc_coef_convert(mij_encoder *e)
 	}
 	HIP_TRY(hipMemcpyAsync(e->d_cslot, e->h_cslot, sizeof(CoefSlot) * nc, hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipMemcpyAsync(e->d_cwork, e->h_cwork, sizeof(WorkIdct) * nw, hipMemcpyHostToDevice, e->stream));
+	if (nq)
+		HIP_TRY(hipMemcpyAsync(e->d_rqt, e->h_rqt, sizeof(RqTable) * nq, hipMemcpyHostToDevice, e->stream));
 	HIP_TRY(hipMemsetAsync(e->d_sflag, 0, sizeof(uint32_t) * n, e->stream));
 	for (mij_batch *b : batches) { /* whatever the batch's stream still does to the planes comes first */
 		HIP_TRY(hipEventRecord(e->ev_coef, b->stream));
@@ -4285,8 +4325,8 @@ static int enc_coef_convert(mij_encoder *e)
 			continue;
 		const dim3 grid((unsigned)g.count), block(64);
 		uint8_t *du = reinterpret_cast<uint8_t *>(e->d_du);
-		hipLaunchKernelGGL(k_coef_units_of[g.fmt ? 1 : 0][g.orient & 7u], grid, block, 0, e->stream, e->d_cslot, e->d_cwork + g.first, g.b->d_coef, du,
-								 e->d_sflag);
+		hipLaunchKernelGGL(k_coef_units_of[g.rq ? 1 : 0][g.fmt ? 1 : 0][g.orient & 7u], grid, block, 0, e->stream, e->d_cslot, e->d_cwork + g.first, g.b->d_coef, du,
+								 e->d_sflag, static_cast<const RqTable *>(e->d_rqt));
 		HIP_TRY(hipGetLastError());
 	}
 	HIP_TRY(hipEventRecord(e->ev_conv1, e->stream));

@@ -26,6 +26,14 @@
  * geometry; a block the trim drops gets u = ~0 and is neither checked nor stored.  The DC predecessor is the previous unit of the component
  * in destination order, mapped back through the same mirrors and swap to a source block index and loaded as before.  The store phase is
  * unchanged: whole 128-byte units are scattered, not pieces.
+ *
+ * Requantisation (mij_enc_add_coef_requant; the rule is mjw_units_requant's, mij_host.h).  RQ = 1 instances take every coefficient, after the
+ * load and the orientation's sign and before the codability check, through y = sgn(x) * ((|x| + (b >> 1)) / b), x = c * a, clamped to
+ * +-32767: so codability is judged on the result.  a, b and the constants of the exact division (mjw_requant_magic: one v_mul_hi_u32, no
+ * divide and no branch) come from the slot's RqTable, indexed by component class and by the SOURCE position P -- the host has put the destination
+ * coefficient's entries there (rq_fill, through the transposition of make_conv_table) -- so every read has a wave-uniform address and a
+ * constant offset: scalar loads, no per-lane copy.  The DC predecessor goes through the DC entry before the difference is taken.
+ * RQ = 0 instances contain none of this.
  */
 #pragma once
 
@@ -38,9 +46,21 @@ struct CoefSlot {
 	uint32_t ncomp, dpm, n_du, slot;            /* n_du: the destination's units; slot: the encoder slot, whose flag an uncodable value raises */
 	uint32_t d_mcu_x, d_mcu_y, d_lh, d_lv;      /* the destination's (the source's again for orientation 1) */
 	uint32_t ext_x, ext_y;                      /* the source's MCU columns and rows that the trim keeps */
-	uint32_t orient, pad;                       /* MIJ_CONV_NX | MIJ_CONV_NY | MIJ_CONV_TR: which template instance converts the slot */
+	uint32_t orient, rq;                        /* MIJ_CONV_NX | MIJ_CONV_NY | MIJ_CONV_TR: which template instance converts the slot; rq: 1 + the
+	                                               index of the slot's RqTable for a requantising slot (the RQ = 1 instances), 0 for a plain one */
 };
 enum { MIJ_CONV_NX = 1, MIJ_CONV_NY = 2, MIJ_CONV_TR = 4 };
+
+/* One requantising slot's constants per component class (0 luma, 1 chroma) and source position P: the source step a, the destination
+ * step b, and the exact division by b (mjw_requant_magic): m, and h = (b >> 1) + inc, what the magnitude takes before the multiply-high
+ * -- the rounding's half and the constant's own increment in one, so that b = 1 needs no case of its own in the kernel. */
+struct RqEntry {
+	uint32_t m;
+	uint8_t a, b, h, pad;
+};
+struct RqTable {
+	RqEntry e[2][64];
+};
 
 /* in-block position P -> zigzag index k: the inverse of mij_zigzag_pos (tests/test_transcode_host.py holds the two against each other) */
 static constexpr uint8_t k_zigzag_of_pos[64] = {
@@ -55,14 +75,20 @@ struct ConvTable {
 	uint8_t zz[64];
 	bool neg[64];
 };
+/* position P = 8 * u + rowslot[v] -> the position of (v, u): where the transposed block holds the coefficient */
+static constexpr int conv_transposed_pos(int P)
+{
+	constexpr uint8_t rowslot[8] = {0, 4, 2, 5, 1, 6, 3, 7}, row_of_slot[8] = {0, 4, 2, 6, 1, 3, 5, 7};
+	return 8 * row_of_slot[P & 7] + rowslot[P >> 3];
+}
 template <int TR, int NX, int NY>
 static constexpr ConvTable make_conv_table()
 {
-	constexpr uint8_t rowslot[8] = {0, 4, 2, 5, 1, 6, 3, 7}, row_of_slot[8] = {0, 4, 2, 6, 1, 3, 5, 7};
+	constexpr uint8_t row_of_slot[8] = {0, 4, 2, 6, 1, 3, 5, 7};
 	ConvTable t{};
 	for (int P = 0; P < 64; ++P) {
 		const int u = P >> 3, v = row_of_slot[P & 7];
-		t.zz[P] = k_zigzag_of_pos[TR ? 8 * v + rowslot[u] : P];
+		t.zz[P] = k_zigzag_of_pos[TR ? conv_transposed_pos(P) : P];
 		t.neg[P] = (NX && (u & 1)) != (NY && (v & 1));
 	}
 	return t;
@@ -70,9 +96,30 @@ static constexpr ConvTable make_conv_table()
 template <int TR, int NX, int NY>
 static constexpr ConvTable k_conv_table = make_conv_table<TR, NX, NY>();
 
-template <int COMPACT, int TR = 0, int NX = 0, int NY = 0>
+/* The table of a requantising slot for a plan whose tables (zigzag order) go from ya / ca to yb / cb: destination coefficient k sits at
+ * source position mij_zigzag_pos[k], or at its transposed position when the slot's instance transposes. */
+static inline void rq_fill(RqTable &t, bool tr, const unsigned char *ya, const unsigned char *yb, const unsigned char *ca, const unsigned char *cb)
+{
+	for (int k = 0; k < 64; ++k) {
+		const int P = tr ? conv_transposed_pos(mij_zigzag_pos[k]) : mij_zigzag_pos[k];
+		uint32_t yi, ci;
+		const uint32_t ym = mjw_requant_magic(yb[k], &yi), cm = mjw_requant_magic(cb[k], &ci);
+		t.e[0][P] = RqEntry{ym, ya[k], yb[k], (uint8_t)((yb[k] >> 1) + yi), 0};
+		t.e[1][P] = RqEntry{cm, ca[k], cb[k], (uint8_t)((cb[k] >> 1) + ci), 0};
+	}
+}
+
+/* mjw_units_requant's rule for one value: n = |c * a| + (b >> 1) < 2^24, so the multiply-high of n + inc by m is the exact quotient */
+__device__ __forceinline__ int rq_value(int c, const RqEntry &q)
+{
+	const int x = c * (int)q.a;
+	const int y = (int)min(__umulhi((uint32_t)(x < 0 ? -x : x) + q.h, q.m), 32767u);
+	return x < 0 ? -y : y;
+}
+
+template <int COMPACT, int TR = 0, int NX = 0, int NY = 0, int RQ = 0>
 __global__ __launch_bounds__(64) void k_coef_units(const CoefSlot *__restrict__ slots, const WorkIdct *__restrict__ work, const uint8_t *__restrict__ coef,
-																	uint8_t *__restrict__ du_base, uint32_t *__restrict__ s_flag)
+																	uint8_t *__restrict__ du_base, uint32_t *__restrict__ s_flag, const RqTable *__restrict__ rqt)
 {
 	__shared__ int16_t rows[64 * MIJ_CONV_ROW];
 	__shared__ uint32_t unit_of[64];
@@ -121,6 +168,12 @@ __global__ __launch_bounds__(64) void k_coef_units(const CoefSlot *__restrict__ 
 				val[8 * q + j] = (int)(int16_t)(w[j >> 1] >> (16 * (j & 1)));
 		}
 	}
+	if constexpr (RQ) { /* sign (with the int16 wrap the plain path's cast has), then the new step: the check below sees the result */
+		const RqEntry *q = rqt[s.rq - 1u].e[c ? 1 : 0]; /* wave-uniform: scalar loads */
+#pragma unroll
+		for (int P = 0; P < 64; ++P)
+			val[P] = rq_value(k_conv_table<TR, NX, NY>.neg[P] ? (int)(int16_t)-val[P] : val[P], q[P]);
+	}
 	constexpr bool PLAIN = !TR && !NX && !NY; /* orientation 1: the destination is the source */
 	/* the kept extent of the source plane in blocks, and the destination's geometry for this component */
 	const uint32_t ew = PLAIN ? bw : s.ext_x * h, eh = PLAIN ? s.mcu_y * v : s.ext_y * v;
@@ -158,6 +211,8 @@ __global__ __launch_bounds__(64) void k_coef_units(const CoefSlot *__restrict__ 
 			else
 				pred = reinterpret_cast<const int16_t *>(coef + s.coef_off[c])[((size_t)(pb >> 6) << 12) + ((size_t)(pb & 63) << 3)];
 		}
+		if constexpr (RQ)
+			pred = rq_value(pred, rqt[s.rq - 1u].e[c ? 1 : 0][0]);
 		bool bad = (uint32_t)(val[0] - pred + 2047) > 4094u;
 #pragma unroll
 		for (int P = 1; P < 64; ++P)
@@ -168,7 +223,7 @@ __global__ __launch_bounds__(64) void k_coef_units(const CoefSlot *__restrict__ 
 	unit_of[lane] = u;
 #pragma unroll
 	for (int P = 0; P < 64; ++P)
-		rows[lane * MIJ_CONV_ROW + k_conv_table<TR, NX, NY>.zz[P]] = (int16_t)(k_conv_table<TR, NX, NY>.neg[P] ? -val[P] : val[P]);
+		rows[lane * MIJ_CONV_ROW + k_conv_table<TR, NX, NY>.zz[P]] = (int16_t)(!RQ && k_conv_table<TR, NX, NY>.neg[P] ? -val[P] : val[P]);
 	__syncthreads();
 #pragma unroll
 	for (int i = 0; i < 8; ++i) {

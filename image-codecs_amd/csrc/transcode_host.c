@@ -233,6 +233,62 @@ int mjw_units_orient(const mjw_tplan *src, const int16_t *du_src, int o, int tri
 	return 1;
 }
 
+/* ---- requantisation (mjw_tplan_requant, include/mij_host.h): new tables in the coefficient domain, after the orientation */
+int mjw_tplan_requant(mjw_tplan *dst, const mjw_tplan *src, const unsigned char luma[64], const unsigned char chroma[64], int coarsen_only,
+                      const char **reason)
+{
+	mjw_tplan t;
+	int k, changed = 0;
+	if (!dst || !src || !luma || !chroma)
+		return refuse(reason, "bad argument");
+	t = *src;
+	for (k = 0; k < 64; ++k) {
+		if (!luma[k] || !chroma[k] || !src->plan.ytab[k] || !src->plan.ctab[k])
+			return refuse(reason, "a quantisation table entry of zero");
+		t.plan.ytab[k] = coarsen_only && src->plan.ytab[k] > luma[k] ? src->plan.ytab[k] : luma[k];
+		if (src->ncomp == 3)
+			t.plan.ctab[k] = coarsen_only && src->plan.ctab[k] > chroma[k] ? src->plan.ctab[k] : chroma[k];
+		else /* grey: one table, kept in both places as mjw_tplan_from_desc leaves it */
+			t.plan.ctab[k] = t.plan.ytab[k];
+		changed |= t.plan.ytab[k] != src->plan.ytab[k] || t.plan.ctab[k] != src->plan.ctab[k];
+	}
+	*dst = t;
+	return changed ? 2 : 1;
+}
+
+uint32_t mjw_requant_magic(int b, uint32_t *inc)
+{
+	if (inc)
+		*inc = b == 1;
+	if (b < 1 || b > 255)
+		return 0u;
+	return b == 1 ? 0xFFFFFFFFu : (uint32_t)(((uint64_t)1 << 32) / (uint32_t)b) + 1u;
+}
+
+int mjw_units_requant(const mjw_tplan *src, const mjw_tplan *dst, const int16_t *du_src, int16_t *du_dst)
+{
+	size_t u, nu;
+	int k, ny, dpm;
+	if (!src || !dst || !du_src || !du_dst || src->ncomp != dst->ncomp || src->plan.du_per_mcu != dst->plan.du_per_mcu || src->plan.du_per_mcu < 1 ||
+		 mjw_tplan_du_count(src) != mjw_tplan_du_count(dst))
+		return 0;
+	for (k = 0; k < 64; ++k)
+		if (!dst->plan.ytab[k] || (dst->ncomp == 3 && !dst->plan.ctab[k]))
+			return 0;
+	nu = mjw_tplan_du_count(src);
+	dpm = src->plan.du_per_mcu;
+	ny = src->ncomp == 1 ? 1 : dpm - 2;
+	for (u = 0; u < nu; ++u, du_src += 64, du_dst += 64) {
+		const int chroma = (int)(u % (size_t)dpm) >= ny;
+		const unsigned char *a = chroma ? src->plan.ctab : src->plan.ytab, *b = chroma ? dst->plan.ctab : dst->plan.ytab;
+		for (k = 0; k < 64; ++k) {
+			const int x = du_src[k] * a[k], m = ((x < 0 ? -x : x) + (b[k] >> 1)) / b[k];
+			du_dst[k] = (int16_t)(m > 32767 ? (x < 0 ? -32767 : 32767) : (x < 0 ? -m : m));
+		}
+	}
+	return 1;
+}
+
 int mjw_copy_markers(const uint8_t *src, int src_len, const unsigned char *stream, size_t stream_len, unsigned char **out, size_t *out_len,
                      const char **reason)
 {
@@ -305,10 +361,12 @@ int mjw_copy_markers(const uint8_t *src, int src_len, const unsigned char *strea
 	return 1;
 }
 
-int mjw_transcode_memory_at(const uint8_t *src, int len, unsigned flags, int o, int trim, unsigned char **out, size_t *out_len, const char **reason)
+int mjw_transcode_memory_requant_at(const uint8_t *src, int len, unsigned flags, int o, int trim, const unsigned char *luma,
+                                    const unsigned char *chroma, int coarsen_only, unsigned char **out, size_t *out_len, const char **reason)
 {
 	mij_image_desc d;
-	mjw_tplan t, ts;
+	mjw_tplan t, ts, tq;
+	int rq = 0;
 	const char *why = NULL;
 	uint8_t *region = NULL;
 	int16_t *du = NULL, *du_src = NULL;
@@ -319,7 +377,7 @@ int mjw_transcode_memory_at(const uint8_t *src, int len, unsigned flags, int o, 
 		return refuse(reason, "bad argument");
 	*out = NULL;
 	*out_len = 0;
-	if (!src || len <= 0)
+	if (!src || len <= 0 || !luma != !chroma)
 		return refuse(reason, "bad argument");
 	if (flags & ~(MJW_OPTIMIZE_HUFFMAN | MJW_COPY_MARKERS))
 		return refuse(reason, "unknown flag");
@@ -350,6 +408,21 @@ int mjw_transcode_memory_at(const uint8_t *src, int len, unsigned flags, int o, 
 		refuse(reason, "units could not be read");
 		goto done;
 	}
+	if (luma) { /* requant(orient(source)): a plan whose tables did not change keeps its units */
+		if (!(rq = mjw_tplan_requant(&tq, &t, luma, chroma, coarsen_only, reason)))
+			goto done;
+		if (rq == 2) {
+			int16_t *dq = (int16_t *)malloc(nu * 64 * sizeof(int16_t));
+			if (!dq || !mjw_units_requant(&t, &tq, du, dq)) {
+				free(dq);
+				refuse(reason, dq ? "units could not be requantised" : "out of memory");
+				goto done;
+			}
+			free(du);
+			du = dq;
+			t = tq;
+		}
+	}
 	if (!mjw_tunits_codable(&t, du, reason))
 		goto done;
 	n = mjw_temit_to_memory(&t, du, flags & MJW_OPTIMIZE_HUFFMAN, buf, cap);
@@ -371,6 +444,11 @@ done:
 	free(du_src);
 	free(buf);
 	return ok;
+}
+
+int mjw_transcode_memory_at(const uint8_t *src, int len, unsigned flags, int o, int trim, unsigned char **out, size_t *out_len, const char **reason)
+{
+	return mjw_transcode_memory_requant_at(src, len, flags, o, trim, NULL, NULL, 0, out, out_len, reason);
 }
 
 int mjh_transcode_memory(const uint8_t *src, int len, unsigned flags, unsigned char **out, size_t *out_len, const char **reason)

@@ -1,14 +1,14 @@
 /*
- * transcode_orient.c -- mjh_transcode_memory_oriented (include/mij_host.h): the lossless transcode on the host with an orientation
- * applied, the file's own EXIF tag included.  The transform itself is transcode_host.c's (mjw_tplan_oriented, mjw_units_orient,
- * mjw_transcode_memory_at); this file adds what needs the EXIF walk (exif.c), so that transcode_host.c links without it.
+ * transcode_orient.c -- mjh_transcode_memory_oriented and mjh_transcode_memory_requant (include/mij_host.h): the transcode on the host
+ * with an orientation applied, the file's own EXIF tag included, and optionally new quantisation tables.  The transform itself is transcode_host.c's (mjw_tplan_oriented, mjw_units_orient,
+ * mjw_transcode_memory_requant_at); this file adds what needs the EXIF walk (exif.c), so that transcode_host.c links without it.
  */
 #include <limits.h>
 
 #include "mij_host.h"
 
-int mjh_transcode_memory_oriented(const uint8_t *src, int len, unsigned flags, int o, int trim, unsigned char **out, size_t *out_len,
-                                  const char **reason)
+int mjh_transcode_memory_requant(const uint8_t *src, int len, unsigned flags, int o, int trim, const unsigned char *luma,
+                                 const unsigned char *chroma, int coarsen_only, unsigned char **out, size_t *out_len, const char **reason)
 {
 	if (o < 0 || o > 8) {
 		if (out)
@@ -21,10 +21,16 @@ int mjh_transcode_memory_oriented(const uint8_t *src, int len, unsigned flags, i
 	}
 	if (o == 0)
 		o = mjh_exif_orientation(src, len);
-	if (!mjw_transcode_memory_at(src, len, flags, o, trim, out, out_len, reason))
+	if (!mjw_transcode_memory_requant_at(src, len, flags, o, trim, luma, chroma, coarsen_only, out, out_len, reason))
 		return 0;
 	/* the picture is upright now: a copied tag that still said otherwise would turn it a second time */
 	if ((flags & MJW_COPY_MARKERS) && o != 1)
 		(void)mjh_exif_set_orientation(*out, *out_len > (size_t)INT_MAX ? INT_MAX : (int)*out_len, 1);
 	return 1;
+}
+
+int mjh_transcode_memory_oriented(const uint8_t *src, int len, unsigned flags, int o, int trim, unsigned char **out, size_t *out_len,
+                                  const char **reason)
+{
+	return mjh_transcode_memory_requant(src, len, flags, o, trim, NULL, NULL, 0, out, out_len, reason);
 }

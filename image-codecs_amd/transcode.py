@@ -5,8 +5,8 @@ statistics.  The same coefficients, to the bit, in a smaller file: no IDCT, no p
 cross PCIe on the way back.  No pixel kernel is launched.
 
 This module needs no torch."""
-from .binding import Batch, Context, Encoder, HostDecoder, MijError, copy_markers as _copy_markers, emit_transcoded, exif_orientation, \
-    exif_set_orientation, transcode_plan
+from .binding import Batch, Context, Encoder, HostDecoder, MijError, _qtable_pair, copy_markers as _copy_markers, emit_transcoded, \
+    exif_orientation, exif_set_orientation, quality_tables, transcode_plan
 
 # one launch takes at most this many pictures / bytes of coefficient arena; larger calls are cut into chunks
 MAX_SLOTS = 4096
@@ -36,6 +36,34 @@ def _orientations(v, datas):
     return [1 if o is None else exif_orientation(d) if o == "exif" else o for o, d in zip(vals, datas)]
 
 
+def _targets(quality, qtables, n):
+    """transcode's quality= / qtables= as one (luma, chroma) pair of 64-byte tables, or None, per source"""
+    if quality is not None and qtables is not None:
+        raise ValueError("quality and qtables are two ways to say the same thing: give one")
+    if qtables is not None:
+        return [_qtable_pair(qtables)] * n
+    what = "quality must be None, an int 1..100 or one of those per source (got %r)"
+    if quality is None or (isinstance(quality, int) and not isinstance(quality, bool)):
+        vals = [quality] * n
+    else:
+        if isinstance(quality, (str, bytes)):
+            raise ValueError(what % (quality,))
+        try:
+            vals = list(quality)
+        except TypeError:
+            raise ValueError(what % (quality,)) from None
+        if len(vals) != n:
+            raise ValueError("quality has %d values for %d sources" % (len(vals), n))
+    for q in vals:
+        if not (q is None or (isinstance(q, int) and not isinstance(q, bool) and 1 <= q <= 100)):
+            raise ValueError(what % (q,))
+    made = {}
+    for q in vals:
+        if q is not None and q not in made:
+            made[q] = tuple(t.tobytes() for t in quality_tables(q))
+    return [None if q is None else made[q] for q in vals]
+
+
 class Transcoder:
     """transcode(datas) -> one new JPEG stream per source, or None where the source cannot be transcoded (last_reasons says why).
 
@@ -58,6 +86,7 @@ class Transcoder:
         self._fmt = "compact"
         self.last_reasons = []
         self.last_host_emitted = 0
+        self.last_requantized = []
         self.last_timing = {}
 
     @property
@@ -120,7 +149,7 @@ class Transcoder:
         return self._enc
 
     def transcode(self, datas, *, optimize=True, copy_markers="all", only_if_smaller=False, gpu_entropy=None, threads=16, orientation=None,
-                  edge="perfect"):
+                  edge="perfect", quality=None, qtables=None, coarsen_only=True):
         """datas: a sequence of JPEG files as bytes.  -> a list with, per source, the new stream (bytes) or None; last_reasons[i] is None
         or the reason source i was refused or could not be decoded.
         optimize: Huffman tables built from each picture's own statistics (mjw_temit_optimized's stream); False: the Annex-K tables.
@@ -136,6 +165,12 @@ class Transcoder:
         the thumbnail -- are left as they are).
         edge: a mirrored axis that is no multiple of the MCU size cannot be mirrored exactly: "perfect" refuses that picture (its reason
         names the axis), "trim" drops the partial MCU column / row of the mirrored axes (jpegtran -trim).
+        quality: None, an int 1..100 or one of those per source: the coefficients are requantised, on the GPU and without pixels, to the
+        tables this writer uses at that quality (one rounding each: include/mij_host.h, mjw_tplan_requant), after the orientation.  The
+        sampling, the geometry and the markers stay the source's.  qtables: instead, one (luma, chroma) pair of 64 ints 1..255 in zigzag
+        order for all sources.  coarsen_only (default): each entry becomes the larger of the source's and the target's, since a finer
+        step restores nothing and only grows the file; False takes the target as it is.  last_requantized[i] says whether source i's
+        tables changed; where they did not, the stream is the lossless one.  only_if_smaller keeps its meaning.
         ValueError, before a device is touched, for arguments that are not of these kinds."""
         if not isinstance(optimize, bool) or not isinstance(only_if_smaller, bool):
             raise ValueError("optimize and only_if_smaller must be bools")
@@ -147,6 +182,8 @@ class Transcoder:
             raise ValueError("threads must be a positive int")
         if edge not in ("perfect", "trim"):
             raise ValueError("edge must be 'perfect' or 'trim', got %r" % (edge,))
+        if not isinstance(coarsen_only, bool):
+            raise ValueError("coarsen_only must be a bool")
         if isinstance(datas, (bytes, bytearray, memoryview, str)):
             raise ValueError("datas is a sequence of JPEG files, not one file")
         datas = list(datas)
@@ -155,6 +192,8 @@ class Transcoder:
                 raise ValueError("source %d is not bytes" % i)
         datas = [bytes(d) for d in datas]
         orients = _orientations(orientation, datas)
+        targets = _targets(quality, qtables, len(datas))
+        self.last_requantized = requantized = [False] * len(datas)
         out = [None] * len(datas)
         reasons = [None] * len(datas)
         self.last_host_emitted = 0
@@ -182,7 +221,8 @@ class Transcoder:
             while j < len(todo) and j - k < MAX_SLOTS and (j == k or coef + todo[j][1] <= MAX_COEF_BYTES):
                 coef += todo[j][1]
                 j += 1
-            self._chunk(datas, todo[k:j], out, reasons, optimize, gpu_entropy, threads, orients, edge == "trim")
+            self._chunk(datas, todo[k:j], out, reasons, optimize, gpu_entropy, threads, orients, edge == "trim", targets, coarsen_only,
+                        requantized)
             k = j
         for i, d in enumerate(datas):
             if out[i] is None:
@@ -199,7 +239,7 @@ class Transcoder:
         self.last_reasons = reasons
         return out
 
-    def _chunk(self, datas, items, out, reasons, optimize, gpu_entropy, threads, orients, trim):
+    def _chunk(self, datas, items, out, reasons, optimize, gpu_entropy, threads, orients, trim, targets, coarsen_only, requantized):
         n = len(items)
         srcs = [datas[it[0]] for it in items]
         stream = 0
@@ -221,10 +261,11 @@ class Transcoder:
                 reasons[it[0]] = r or "decode failed"
                 continue
             try:
-                es[it[0]] = enc.add_coef(b, sl, orients[it[0]], trim)
+                es[it[0]] = enc.add_coef(b, sl, orients[it[0]], trim, targets[it[0]], coarsen_only)
             except MijError as e:
                 reasons[it[0]] = str(e).split(": ", 1)[-1]
                 continue
+            requantized[it[0]] = enc.slot_requantized(es[it[0]])
             if optimize:
                 enc.set_optimize(es[it[0]])
         if not es:

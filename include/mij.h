@@ -704,10 +704,23 @@ int mij_enc_slot_optimized(const mij_encoder *e, int slot);
  * (mij_enc_tplan), units (mij_enc_fetch) and stream are the DESTINATION picture's, and codability is judged in its unit order.  MIJ_E_ARG
  * with the host's reason ("not transformable: ...") for an orientation outside 1..8, for a picture with a partial MCU on a mirrored axis
  * when trim is 0, and for one with nothing left after the trim.  mij_enc_add_coef is this with (1, 0).
+ *
+ * mij_enc_add_coef_requant: the same slot with new quantisation tables as well: luma and chroma are the 64-entry target tables in zigzag
+ * order, entries 1..255 (both NULL: none, which is mij_enc_add_coef_oriented exactly); coarsen_only takes the entry-wise maximum with the
+ * source's.  The rule, the rounding and the order -- requant(orient(source)) -- are written in mij_host.h (mjw_tplan_requant,
+ * mjw_units_requant).  The conversion kernel's requantising instances divide exactly by multiply-high constants from a per-slot table
+ * (mjw_requant_magic) and judge codability on the RESULT; a slot whose tables do not change is a plain slot and takes the plain
+ * instance.  mij_enc_tplan reports the destination plan, tables included, and mij_enc_fetch the requantised units, so a slot that
+ * misses the arena is finished on the host as before.  MIJ_E_ARG ("not requantisable: ...") for a zero table entry.  One upload may
+ * hold plain, oriented and requantising slots.  mij_enc_slot_requantized: 1 for a coefficient slot whose tables changed, 0 for a plain
+ * one, MIJ_E_ARG for any other slot.
  */
 enum { MIJ_ENC_SLOT_OK = 0, MIJ_ENC_SLOT_NO_ROOM = 1, MIJ_ENC_SLOT_UNCODABLE = 2 };
 int mij_enc_add_coef(mij_encoder *e, mij_batch *b, int slot);
 int mij_enc_add_coef_oriented(mij_encoder *e, mij_batch *b, int slot, int orientation, int trim);
+int mij_enc_add_coef_requant(mij_encoder *e, mij_batch *b, int slot, int orientation, int trim, const unsigned char *luma,
+                             const unsigned char *chroma, int coarsen_only);
+int mij_enc_slot_requantized(const mij_encoder *e, int slot);
 int mij_enc_slot_status(const mij_encoder *e, int slot);
 int mij_enc_coef_ms(mij_encoder *e, float *ms);
 

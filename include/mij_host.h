@@ -287,7 +287,51 @@ int mjw_transcode_memory_at(const uint8_t *src, int len, unsigned flags, int o, 
 int mjh_transcode_memory_oriented(const uint8_t *src, int len, unsigned flags, int o, int trim, unsigned char **out, size_t *out_len,
                                   const char **reason);
 
-/* The tables of stbi__ldr_to_hdr (common.c:391-424) for mij_batch_set_out_f32: lut[256*k + v] for channel k < n_out.  Colour
+/*
+ * Requantisation in the transcode: new quantisation tables applied to the coefficients, without pixels -- one rounding per coefficient,
+ * the sampling, geometry and markers untouched.  On the GPU: mij_enc_add_coef_requant (mij.h); these calls are the written contract.
+ *
+ * TABLES, all in zigzag order as mjw_plan.ytab / ctab are.  s_l, s_c: the tables of the plan that is requantised -- the ORIENTED plan
+ * (mjw_tplan_oriented) when an orientation is applied too: the result is requant(orient(source)).  t_l, t_c: the target, every entry
+ * 1..255.  The destination's tables are d = max(s, t) entry by entry when coarsen_only is set (a finer step restores nothing and only
+ * grows the file), d = t otherwise.  Cb and Cr share d_c; grey uses d_l only (its plan keeps ctab = ytab).  A plan whose d equals s
+ * everywhere is a plain lossless transcode: same units, same bytes.  What makes a source transcodable is judged on the source, as before.
+ *
+ * COEFFICIENTS.  Unit coefficient k of a component with source entry a = s[k] and destination entry b = d[k], source value c (int16, the
+ * DC included, taken after the orientation's sign):
+ *   x = c * a                               |x| <= 32768 * 255 < 2^23
+ *   y = sgn(x) * ((|x| + (b >> 1)) / b)     integer division: round to nearest, halves away from zero
+ *   y = clamp(y, -32767, 32767)             only so that a unit is an int16; such a unit is uncodable anyway
+ * Codability (mjw_tunits_codable) is judged on y in the destination's unit order: an AC of 1500 at a = 1 is codable at b = 2, and with
+ * coarsen_only off and b < a a codable source can become uncodable.
+ *
+ * STREAM: mjw_temit / mjw_temit_optimized of the destination plan -- the (oriented) plan with ytab / ctab replaced by d -- and units.
+ *
+ *   mjw_quality_tables      the pair mjw_plan_init makes at quality 1..100 (stbi_write_jpg's tables); 0 outside that range
+ *   mjw_tplan_requant       dst = src with its tables replaced by d.  0 with *reason for a zero entry in any of the four tables; 1 when d
+ *                           equals s everywhere; 2 when an entry changed
+ *   mjw_units_requant       the rule above over every unit of src (the plan whose tables are s) into du_dst (the plan whose tables are d;
+ *                           the two plans differ in their tables only), with plain `/`: the reference for the kernel.  0 on bad arguments
+ *   mjw_requant_magic       the constants of the exact division the conversion kernel runs in place of `/`: returns m and sets *inc so
+ *                           that n / b == (uint32_t)(((uint64_t)(n + inc) * m) >> 32) for every n < 2^24.  For b in 2..255
+ *                           m = floor(2^32 / b) + 1 and inc = 0: the error n * (m * b - 2^32) <= 2^24 * 255 stays below 2^32.  For b = 1,
+ *                           where that m would not fit 32 bits, m = 2^32 - 1 and inc = 1: (n + 1) * (2^32 - 1) >> 32 is n.  0 for b
+ *                           outside 1..255.  The kernel's tables are filled by this function (inc is added with the rounding's b >> 1).
+ *   mjw_transcode_memory_requant_at   mjw_transcode_memory_at, then the tables (luma and chroma both NULL: none), then the emission
+ *   mjh_transcode_memory_requant      the whole thing on the host: orient (o = 0: the file's tag, as mjh_transcode_memory_oriented), then
+ *                           requantise, then emit.  mjh_transcode_memory_oriented is this with no tables.
+ */
+int mjw_quality_tables(int quality, unsigned char luma[64], unsigned char chroma[64]);
+int mjw_tplan_requant(mjw_tplan *dst, const mjw_tplan *src, const unsigned char luma[64], const unsigned char chroma[64], int coarsen_only,
+                      const char **reason);
+int mjw_units_requant(const mjw_tplan *src, const mjw_tplan *dst, const int16_t *du_src, int16_t *du_dst);
+uint32_t mjw_requant_magic(int b, uint32_t *inc);
+int mjw_transcode_memory_requant_at(const uint8_t *src, int len, unsigned flags, int o, int trim, const unsigned char *luma,
+                                    const unsigned char *chroma, int coarsen_only, unsigned char **out, size_t *out_len, const char **reason);
+int mjh_transcode_memory_requant(const uint8_t *src, int len, unsigned flags, int o, int trim, const unsigned char *luma,
+                                 const unsigned char *chroma, int coarsen_only, unsigned char **out, size_t *out_len, const char **reason);
+
+/* The tables of stbi__ldr_to_hdr(common.c:391-424) for mij_batch_set_out_f32: lut[256*k + v] for channel k < n_out.  Colour
  * channels (all of them for odd n_out, all but the last for even n_out) get (float)(pow(v / 255.0f, gamma) * scale), the
  * alpha channel of n_out 2 and 4 gets v / 255.0f -- the reference's expressions, evaluated with libm's pow. */
 void mjh_ldr_to_hdr_lut(int n_out, float gamma, float scale, float *lut);
