@@ -54,6 +54,10 @@ from .binding import (  # noqa: F401
     transcode_memory,
     transcode_plan_oriented,
     units_orient,
+    transcode_plan_grey,
+    units_grey,
+    transcode_plan_cropped,
+    units_crop,
     quality_tables,
     requant_magic,
     transcode_plan_requant,

@@ -1400,15 +1400,26 @@ def units_requant(src, dst, du):
     return out.reshape(-1, 64)
 
 
-def transcode_memory(data, optimize=False, copy_markers=False, orientation=None, trim=False, tables=None, coarsen_only=True):
+def transcode_memory(data, optimize=False, copy_markers=False, orientation=None, trim=False, tables=None, coarsen_only=True, crop=None,
+                     grey=False):
     """mjh_transcode_memory, the lossless transcode on the host alone -> (bytes, None) or (None, reason).  With an orientation
     (1..8, or "exif" for the file's own tag) it is mjh_transcode_memory_oriented; trim chooses its edge mode.  With tables = (luma,
-    chroma) it is mjh_transcode_memory_requant: the coefficients requantised after the orientation."""
+    chroma) it is mjh_transcode_memory_requant: the coefficients requantised after the orientation.  With crop = (x0, y0, w, h) in the
+    displayed frame and / or grey=True it is mjh_transcode_memory_window: grey -> orient -> crop -> requantise."""
     L = lib()
     data = bytes(data)
     out, n, why = C.c_void_p(), C.c_size_t(), C.c_char_p()
     flags = (MJW_OPTIMIZE_HUFFMAN if optimize else 0) | (MJW_COPY_MARKERS if copy_markers else 0)
-    if tables is not None:
+    if crop is not None or grey:
+        luma, chroma = (None, None) if tables is None else _qtable_pair(tables)
+        win = None if crop is None else (C.c_int * 4)(*[int(v) for v in crop])
+        L.mjh_transcode_memory_window.argtypes = [C.c_char_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_char_p,
+                                                  C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int),
+                                                  C.POINTER(C.c_char_p)]
+        o = 1 if orientation is None else 0 if orientation == "exif" else int(orientation)
+        ok = L.mjh_transcode_memory_window(data, len(data), flags, o, int(bool(trim)), win, int(bool(grey)), luma, chroma,
+                                           int(bool(coarsen_only)), C.byref(out), C.byref(n), None, C.byref(why))
+    elif tables is not None:
         luma, chroma = _qtable_pair(tables)
         L.mjh_transcode_memory_requant.argtypes = [C.c_char_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_int,
                                                    C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_char_p)]
@@ -1436,6 +1447,60 @@ def transcode_plan_oriented(tplan, orientation, trim=False):
     if not L.mjw_tplan_oriented(C.byref(t), C.byref(tplan), int(orientation), int(bool(trim)), C.byref(why)):
         return None, (why.value.decode() if why.value else "refused")
     return t, None
+
+
+def transcode_plan_grey(tplan):
+    """mjw_tplan_grey: the one-component plan of a plan (a grey plan is copied) -> TranscodePlan, None for a bad plan"""
+    L = lib()
+    L.mjw_tplan_grey.argtypes = [C.POINTER(TranscodePlan), C.POINTER(TranscodePlan)]
+    t = TranscodePlan()
+    return t if L.mjw_tplan_grey(C.byref(t), C.byref(tplan)) else None
+
+
+def units_grey(tplan, du):
+    """mjw_units_grey: a source's units -> the grey plan's (the luma blocks inside ceil(W / 8) x ceil(H / 8)), int16 [n_du, 64]"""
+    dst = transcode_plan_grey(tplan)
+    if dst is None:
+        return None
+    L = lib()
+    L.mjw_units_grey.argtypes = [C.POINTER(TranscodePlan), C.c_void_p, C.c_void_p]
+    d = np.ascontiguousarray(du, np.int16)
+    if d.size != tplan.du_elems():
+        raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, tplan.du_elems()))
+    out = np.empty(dst.du_elems(), np.int16)
+    if not L.mjw_units_grey(C.byref(tplan), d.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)):
+        return None
+    return out.reshape(-1, 64)
+
+
+def transcode_plan_cropped(tplan, crop):
+    """mjw_tplan_cropped: the plan of the window crop = (x0, y0, w, h) of a plan's picture -> (TranscodePlan, (x0', y0', W', H')), the kept
+    rectangle with its origin on the MCU grid, or (None, reason) for a window that does not lie inside the picture"""
+    L = lib()
+    L.mjw_tplan_cropped.argtypes = [C.POINTER(TranscodePlan), C.POINTER(TranscodePlan), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                    C.POINTER(C.c_char_p)]
+    t, why, rect = TranscodePlan(), C.c_char_p(), (C.c_int * 4)()
+    x0, y0, w, h = (int(v) for v in crop)
+    if not L.mjw_tplan_cropped(C.byref(t), C.byref(tplan), x0, y0, w, h, rect, C.byref(why)):
+        return None, (why.value.decode() if why.value else "refused")
+    return t, tuple(rect)
+
+
+def units_crop(tplan, du, rect):
+    """mjw_units_crop: the units of the kept rectangle `rect` (as transcode_plan_cropped returned it) from the plan's, int16 [n_du, 64];
+    None for a rectangle that is none"""
+    dst, kept = transcode_plan_cropped(tplan, rect)
+    if dst is None or kept != tuple(int(v) for v in rect):
+        return None
+    L = lib()
+    L.mjw_units_crop.argtypes = [C.POINTER(TranscodePlan), C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
+    d = np.ascontiguousarray(du, np.int16)
+    if d.size != tplan.du_elems():
+        raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, tplan.du_elems()))
+    out = np.empty(dst.du_elems(), np.int16)
+    if not L.mjw_units_crop(C.byref(tplan), d.ctypes.data_as(C.c_void_p), (C.c_int * 4)(*kept), out.ctypes.data_as(C.c_void_p)):
+        return None
+    return out.reshape(-1, 64)
 
 
 def units_orient(tplan, du, orientation, trim=False):
@@ -1648,14 +1713,23 @@ class Encoder:
             raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, plan.du_elems()))
         return _check(L.mij_enc_add_units(self._h, int(width), int(height), int(comp), int(quality), d.ctypes.data_as(C.c_void_p)), "mij_enc_add_units")
 
-    def add_coef(self, batch, slot, orientation=1, trim=False, tables=None, coarsen_only=True):
+    def add_coef(self, batch, slot, orientation=1, trim=False, tables=None, coarsen_only=True, crop=None, grey=False):
         """mij_enc_add_coef: a slot whose units are the quantised coefficients of an uploaded Batch's slot (lossless transcode).
         MijError with the reason for a picture that is not transcodable.  The batch must stay as it is until wait() or a fetch.
         orientation 1..8 and trim: mij_enc_add_coef_oriented, the coefficients reoriented on the way (the slot's plan, units and stream
         are the destination's); MijError with the reason for a picture the edge mode refuses.
         tables = (luma, chroma), 64 entries 1..255 each in zigzag order: mij_enc_add_coef_requant, the coefficients requantised to those
-        tables (their entry-wise maximum with the source's when coarsen_only) after the orientation."""
+        tables (their entry-wise maximum with the source's when coarsen_only) after the orientation.
+        crop = (x0, y0, w, h) in the displayed frame and / or grey=True: mij_enc_add_coef_window, in the order grey -> orient -> crop ->
+        requantise; slot_rect(slot) is the kept rectangle.  MijError with the reason for a window outside the picture."""
         L = lib()
+        if crop is not None or grey:
+            luma, chroma = (None, None) if tables is None else _qtable_pair(tables)
+            win = None if crop is None else (C.c_int * 4)(*[int(v) for v in crop])
+            L.mij_enc_add_coef_window.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_char_p,
+                                                  C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+            return _check(L.mij_enc_add_coef_window(self._h, batch._h, int(slot), int(orientation), int(bool(trim)), win, int(bool(grey)), luma,
+                                                    chroma, int(bool(coarsen_only)), None), "mij_enc_add_coef_window")
         if tables is not None:
             luma, chroma = _qtable_pair(tables)
             L.mij_enc_add_coef_requant.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_int]
@@ -1666,6 +1740,35 @@ class Encoder:
             return _check(L.mij_enc_add_coef(self._h, batch._h, int(slot)), "mij_enc_add_coef")
         L.mij_enc_add_coef_oriented.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
         return _check(L.mij_enc_add_coef_oriented(self._h, batch._h, int(slot), int(orientation), int(bool(trim))), "mij_enc_add_coef_oriented")
+
+    def slot_rect(self, slot):
+        """mij_enc_slot_rect: the rectangle (x0', y0', W', H') of the displayed picture a coefficient slot keeps: the crop with its origin
+        moved down to the MCU grid, the whole picture where none was asked"""
+        L = lib()
+        L.mij_enc_slot_rect.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        r = (C.c_int * 4)()
+        _check(L.mij_enc_slot_rect(self._h, int(slot), r), "mij_enc_slot_rect")
+        return tuple(r)
+
+    def slot_greyed(self, slot):
+        """mij_enc_slot_greyed: whether add_coef's grey dropped the chroma of a colour source"""
+        L = lib()
+        L.mij_enc_slot_greyed.argtypes = [C.c_void_p, C.c_int]
+        return bool(_check(L.mij_enc_slot_greyed(self._h, int(slot)), "mij_enc_slot_greyed"))
+
+    def slot_windowed(self, slot):
+        """mij_enc_slot_windowed: whether add_coef's crop or grey changed the picture (false: the slot is converted as it was without them)"""
+        L = lib()
+        L.mij_enc_slot_windowed.argtypes = [C.c_void_p, C.c_int]
+        return bool(_check(L.mij_enc_slot_windowed(self._h, int(slot)), "mij_enc_slot_windowed"))
+
+    def coef_tiles(self):
+        """mij_enc_coef_tiles: the 64-block plane tiles the last upload queued for conversion, over all its coefficient slots"""
+        L = lib()
+        L.mij_enc_coef_tiles.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        n = C.c_uint32()
+        _check(L.mij_enc_coef_tiles(self._h, C.byref(n)), "mij_enc_coef_tiles")
+        return int(n.value)
 
     def slot_requantized(self, slot):
         """mij_enc_slot_requantized: whether add_coef's tables changed an entry of the slot's plan (false: a plain lossless slot)"""

@@ -3200,6 +3200,8 @@ struct EncSlot {
 	mij_batch *src;
 	CoefSlot coef;
 	int coef_fmt;
+	int rect[4];                  /* the kept rectangle in the displayed frame (mij_enc_slot_rect) */
+	bool greyed;                  /* Cb and Cr of a colour source were dropped */
 	unsigned char rq_from[2][64]; /* a requantising slot (coef.rq != 0): the tables tp's replaced, luma and chroma, zigzag order */
 };
 
@@ -3269,6 +3271,7 @@ struct mij_encoder {
 	size_t sflag_cap;
 	hipEvent_t ev_coef;
 	bool has_coef; /* the last upload had a coefficient slot */
+	uint32_t coef_tiles; /* plane tiles its conversion queued (mij_enc_coef_tiles) */
 	std::vector<uint32_t> sflag; /* after mij_enc_fetch_streams */
 	hipEvent_t ev_conv0, ev_conv1; /* around the conversion kernels of the last upload (mij_enc_coef_ms) */
 	bool conv_timed;
@@ -3379,6 +3382,7 @@ extern "C" int mij_enc_create_ex(mij_ctx *ctx, int max_images, size_t stage_byte
 	e->cslot_cap = e->cwork_cap = e->sflag_cap = 0;
 	e->ev_coef = e->ev_conv0 = e->ev_conv1 = nullptr;
 	e->has_coef = e->conv_timed = false;
+	e->coef_tiles = 0;
 	enc_free_emit(e);
 	e->force_generic = getenv("MIJ_ENC_GENERIC") != nullptr;
 	e->stream = nullptr;
@@ -3536,6 +3540,8 @@ static int enc_add_common(mij_encoder *e, const mjw_plan &plan, const void *pixe
 	memset(&s.tp, 0, sizeof(s.tp));
 	memset(&s.coef, 0, sizeof(s.coef));
 	memset(s.rq_from, 0, sizeof(s.rq_from));
+	memset(s.rect, 0, sizeof(s.rect));
+	s.greyed = false;
 	s.pix_bytes = !enc_has_pixels(kind) ? 0 : align_up((size_t)s.pad_w * plan.height * 3, 256); /* staged as packed RGB whatever plan.comp is (enc_stage_rows) */
 	s.du_bytes = align_up(mjw_plan_du_count(&plan) * 128, 256);
 	if (e->pix_used + s.pix_bytes > e->pix_cap)
@@ -4112,8 +4118,8 @@ extern "C" int mij_enc_add_units(mij_encoder *e, int width, int height, int comp
 
 /* ---- coefficient slots (lossless transcode): a decode batch's planes become the slot's data units on the device */
 
-extern "C" int mij_enc_add_coef_requant(mij_encoder *e, mij_batch *b, int slot, int orientation, int trim, const unsigned char *luma,
-                                        const unsigned char *chroma, int coarsen_only)
+extern "C" int mij_enc_add_coef_window(mij_encoder *e, mij_batch *b, int slot, int orientation, int trim, const int *crop, int grey,
+                                       const unsigned char *luma, const unsigned char *chroma, int coarsen_only, int *rect_out)
 {
 	if (!e || !b)
 		return set_err(MIJ_E_ARG, "bad argument");
@@ -4128,15 +4134,25 @@ extern "C" int mij_enc_add_coef_requant(mij_encoder *e, mij_batch *b, int slot, 
 		return set_err(MIJ_E_ARG, "mij_enc_add_coef: the planes of batch slot %d are not in device memory yet (mij_batch_upload first)", slot);
 	if (!luma != !chroma)
 		return set_err(MIJ_E_ARG, "mij_enc_add_coef_requant: one table without the other");
-	mjw_tplan sp, op, tp; /* the source's plan (the planes' geometry), the oriented one, and the destination's (the stream's) */
+	/* the source's plan (the planes' geometry), the grey one, the oriented one, the cropped one, and the destination's (the stream's) */
+	mjw_tplan sp, gp, op, cp, tp;
 	const char *why = nullptr;
 	if (!mjw_tplan_from_desc(&sp, &bs.desc, &why))
 		return set_err(MIJ_E_ARG, "not transcodable: %s", why ? why : "refused");
-	if (!mjw_tplan_oriented(&op, &sp, orientation, trim, &why))
+	const bool greyed = grey && sp.ncomp == 3;
+	gp = sp;
+	if (greyed && !mjw_tplan_grey(&gp, &sp))
+		return set_err(MIJ_E_ARG, "not transcodable: bad source plan");
+	if (!mjw_tplan_oriented(&op, &gp, orientation, trim, &why))
 		return set_err(MIJ_E_ARG, "not transformable: %s", why ? why : "refused");
-	tp = op;
+	cp = op;
+	int rect[4] = {0, 0, op.plan.width, op.plan.height};
+	if (crop && !mjw_tplan_cropped(&cp, &op, crop[0], crop[1], crop[2], crop[3], rect, &why))
+		return set_err(MIJ_E_ARG, "not croppable: %s", why ? why : "refused");
+	const bool cropped = rect[0] || rect[1] || rect[2] != op.plan.width || rect[3] != op.plan.height;
+	tp = cp;
 	int rq = 1; /* mjw_tplan_requant's answer: 2 where a table entry changes */
-	if (luma && !(rq = mjw_tplan_requant(&tp, &op, luma, chroma, coarsen_only, &why)))
+	if (luma && !(rq = mjw_tplan_requant(&tp, &cp, luma, chroma, coarsen_only, &why)))
 		return set_err(MIJ_E_ARG, "not requantisable: %s", why ? why : "refused");
 	const size_t nu = mjw_tplan_du_count(&tp);
 	if (mjw_tplan_du_count(&sp) > UINT32_MAX / 64)
@@ -4148,6 +4164,8 @@ extern "C" int mij_enc_add_coef_requant(mij_encoder *e, mij_batch *b, int slot, 
 	s.tp = tp;
 	s.src = b;
 	s.coef_fmt = bs.coef_bytes_fmt ? 1 : 0;
+	memcpy(s.rect, rect, sizeof(rect));
+	s.greyed = greyed;
 	for (int c = 0; c < tp.ncomp; ++c) {
 		s.coef.coef_off[c] = bs.dev.comp[c].coef_off;
 		s.coef.dc_off[c] = bs.dev.comp[c].dc_off;
@@ -4171,9 +4189,66 @@ extern "C" int mij_enc_add_coef_requant(mij_encoder *e, mij_batch *b, int slot, 
 	s.coef.ext_y = (uint32_t)(tr ? tp.plan.mcu_x : tp.plan.mcu_y);
 	s.coef.orient = (orient_mx[orientation] ? MIJ_CONV_NX : 0u) | (orient_my[orientation] ? MIJ_CONV_NY : 0u) | (tr ? MIJ_CONV_TR : 0u);
 	s.coef.rq = rq == 2 ? 1u : 0u; /* enc_coef_convert numbers the tables */
-	memcpy(s.rq_from[0], op.plan.ytab, 64);
-	memcpy(s.rq_from[1], op.plan.ctab, 64);
+	memcpy(s.rq_from[0], cp.plan.ytab, 64);
+	memcpy(s.rq_from[1], cp.plan.ctab, 64);
+	s.coef.win = greyed || cropped ? 1u : 0u;
+	if (s.coef.win) {
+		/* the kept rectangle in MCUs of the oriented frame, taken back through the transpose and the mirrors into the (grey) source's
+		 * stored frame, whose MCUs the trim kept are ext_x x ext_y; then in blocks of each component's plane */
+		const uint32_t ex = (uint32_t)(tr ? op.plan.mcu_y : op.plan.mcu_x), ey = (uint32_t)(tr ? op.plan.mcu_x : op.plan.mcu_y);
+		const uint32_t cx = (uint32_t)(rect[0] / (8 * op.lh)), cy = (uint32_t)(rect[1] / (8 * op.lv)), cw = (uint32_t)cp.plan.mcu_x, ch = (uint32_t)cp.plan.mcu_y;
+		uint32_t gx = tr ? cy : cx, gy = tr ? cx : cy;
+		const uint32_t gw = tr ? ch : cw, gh = tr ? cw : ch;
+		if (orient_mx[orientation])
+			gx = ex - gx - gw;
+		if (orient_my[orientation])
+			gy = ey - gy - gh;
+		for (int k = 0; k < 2; ++k) {
+			const uint32_t fh = k ? 1u : (uint32_t)gp.lh, fv = k ? 1u : (uint32_t)gp.lv;
+			const bool none = k && tp.ncomp == 1; /* a grey destination keeps no chroma block */
+			s.coef.w_ox[k] = gx * fh, s.coef.w_oy[k] = gy * fv;
+			s.coef.w_ew[k] = none ? 0u : gw * fh, s.coef.w_eh[k] = none ? 0u : gh * fv;
+		}
+	}
+	if (rect_out)
+		memcpy(rect_out, rect, sizeof(rect));
 	return es;
+}
+
+extern "C" int mij_enc_add_coef_requant(mij_encoder *e, mij_batch *b, int slot, int orientation, int trim, const unsigned char *luma,
+                                        const unsigned char *chroma, int coarsen_only)
+{
+	return mij_enc_add_coef_window(e, b, slot, orientation, trim, nullptr, 0, luma, chroma, coarsen_only, nullptr);
+}
+
+extern "C" int mij_enc_slot_rect(const mij_encoder *e, int slot, int rect[4])
+{
+	if (!e || slot < 0 || slot >= (int)e->slots.size() || !rect || e->slots[(size_t)slot].kind != ENC_COEF)
+		return set_err(MIJ_E_ARG, "bad slot, or not a coefficient slot");
+	memcpy(rect, e->slots[(size_t)slot].rect, sizeof(e->slots[(size_t)slot].rect));
+	return MIJ_OK;
+}
+
+extern "C" int mij_enc_slot_greyed(const mij_encoder *e, int slot)
+{
+	if (!e || slot < 0 || slot >= (int)e->slots.size() || e->slots[(size_t)slot].kind != ENC_COEF)
+		return set_err(MIJ_E_ARG, "bad slot, or not a coefficient slot");
+	return e->slots[(size_t)slot].greyed ? 1 : 0;
+}
+
+extern "C" int mij_enc_slot_windowed(const mij_encoder *e, int slot)
+{
+	if (!e || slot < 0 || slot >= (int)e->slots.size() || e->slots[(size_t)slot].kind != ENC_COEF)
+		return set_err(MIJ_E_ARG, "bad slot, or not a coefficient slot");
+	return e->slots[(size_t)slot].coef.win ? 1 : 0;
+}
+
+extern "C" int mij_enc_coef_tiles(const mij_encoder *e, uint32_t *tiles)
+{
+	if (!e || !tiles)
+		return set_err(MIJ_E_ARG, "bad argument");
+	*tiles = e->coef_tiles;
+	return MIJ_OK;
 }
 
 extern "C" int mij_enc_add_coef_oriented(mij_encoder *e, mij_batch *b, int slot, int orientation, int trim)
@@ -4227,17 +4302,44 @@ extern "C" int mij_enc_coef_ms(mij_encoder *e, float *ms)
 	return MIJ_OK;
 }
 
-/* k_coef_units' instances by [requantising][compact][MIJ_CONV_NX | MIJ_CONV_NY | MIJ_CONV_TR] */
+/* k_coef_units' instances by [requantising][compact][MIJ_CONV_NX | MIJ_CONV_NY | MIJ_CONV_TR]; the windowed ones in a table of their own */
 typedef void (*coef_units_fn)(const CoefSlot *, const WorkIdct *, const uint8_t *, uint8_t *, uint32_t *, const RqTable *);
 #define MIJ_CONV_ROW_OF(C, R) \
 	{k_coef_units<C, 0, 0, 0, R>, k_coef_units<C, 0, 1, 0, R>, k_coef_units<C, 0, 0, 1, R>, k_coef_units<C, 0, 1, 1, R>, \
 	 k_coef_units<C, 1, 0, 0, R>, k_coef_units<C, 1, 1, 0, R>, k_coef_units<C, 1, 0, 1, R>, k_coef_units<C, 1, 1, 1, R>}
 static const coef_units_fn k_coef_units_of[2][2][8] = {{MIJ_CONV_ROW_OF(0, 0), MIJ_CONV_ROW_OF(1, 0)}, {MIJ_CONV_ROW_OF(0, 1), MIJ_CONV_ROW_OF(1, 1)}};
 #undef MIJ_CONV_ROW_OF
+#define MIJ_CONV_ROW_OF(C, R) \
+	{k_coef_units<C, 0, 0, 0, R, 1>, k_coef_units<C, 0, 1, 0, R, 1>, k_coef_units<C, 0, 0, 1, R, 1>, k_coef_units<C, 0, 1, 1, R, 1>, \
+	 k_coef_units<C, 1, 0, 0, R, 1>, k_coef_units<C, 1, 1, 0, R, 1>, k_coef_units<C, 1, 0, 1, R, 1>, k_coef_units<C, 1, 1, 1, R, 1>}
+static const coef_units_fn k_coef_units_win_of[2][2][8] = {{MIJ_CONV_ROW_OF(0, 0), MIJ_CONV_ROW_OF(1, 0)}, {MIJ_CONV_ROW_OF(0, 1), MIJ_CONV_ROW_OF(1, 1)}};
+#undef MIJ_CONV_ROW_OF
+
+/* The plane tiles of component c a slot's conversion reads: every tile of the plane for a plain slot; for a windowed one those that hold
+ * a block of the kept rectangle (a tile is 64 consecutive blocks of the plane in raster order), in rising order.  Calls f(tile). */
+template <typename F>
+static void coef_slot_tiles(const CoefSlot &cs, uint32_t c, F f)
+{
+	const size_t bw = (size_t)cs.mcu_x * (c ? 1u : cs.lh), bh = (size_t)cs.mcu_y * (c ? 1u : cs.lv);
+	if (!cs.win) {
+		for (size_t t = 0; t < (bw * bh + 63) / 64; ++t)
+			f((uint32_t)t);
+		return;
+	}
+	const int k = c ? 1 : 0;
+	size_t next = 0; /* the first tile not yet named */
+	for (size_t by = cs.w_oy[k]; cs.w_ew[k] && by < (size_t)cs.w_oy[k] + cs.w_eh[k]; ++by) {
+		const size_t lo = (by * bw + cs.w_ox[k]) >> 6, hi = (by * bw + cs.w_ox[k] + cs.w_ew[k] - 1) >> 6;
+		for (size_t t = lo > next ? lo : next; t <= hi; ++t)
+			f((uint32_t)t);
+		next = hi + 1 > next ? hi + 1 : next;
+	}
+}
 
 /* The conversion kernel of the coefficient slots, queued at upload in place of a copy of units: behind an event on every source
- * batch's stream, one launch per (batch, plane format, orientation's template instance, plain or requantising) over a list of plane tiles.  The flags are cleared whenever the emission may
- * read them. */
+ * batch's stream, one launch per (batch, plane format, orientation's template instance, plain or requantising, whole or windowed) over a
+ * list of plane tiles -- every tile of a plain slot's planes, those its kept rectangle touches for a windowed one (coef_slot_tiles).  The
+ * flags are cleared whenever the emission may read them. */
 static int enc_coef_convert(mij_encoder *e)
 {
 	const size_t n = e->slots.size();
@@ -4246,10 +4348,12 @@ static int enc_coef_convert(mij_encoder *e)
 		if (s.kind == ENC_COEF) {
 			++nc;
 			nq += s.coef.rq ? 1 : 0;
-			nw += ((size_t)s.coef.mcu_x * s.coef.mcu_y * s.coef.lh * s.coef.lv + 63) / 64 + (s.coef.ncomp == 3 ? 2 * (((size_t)s.coef.mcu_x * s.coef.mcu_y + 63) / 64) : 0);
+			for (uint32_t c = 0; c < s.coef.ncomp; ++c) /* what is queued below: a windowed slot names only the tiles its rectangle touches */
+				coef_slot_tiles(s.coef, c, [&](uint32_t) { ++nw; });
 		}
 	e->has_coef = nc != 0;
 	e->conv_timed = false;
+	e->coef_tiles = 0;
 	if (!nc)
 		return MIJ_OK;
 	if (nw > UINT32_MAX)
@@ -4270,12 +4374,13 @@ static int enc_coef_convert(mij_encoder *e)
 		HIP_TRY(hipEventCreate(&e->ev_conv0));
 		HIP_TRY(hipEventCreate(&e->ev_conv1));
 	}
-	/* groups: slots of one batch, one plane format and one template instance (orientation; plain or requantising) are contiguous in the lists */
+	/* groups: slots of one batch, one plane format and one template instance (orientation; plain or requantising; whole or windowed) are
+	 * contiguous in the lists */
 	struct Group {
 		mij_batch *b;
 		int fmt;
 		uint32_t orient;
-		bool rq;
+		bool rq, win;
 		size_t first, count;
 	};
 	std::vector<Group> groups;
@@ -4284,9 +4389,9 @@ static int enc_coef_convert(mij_encoder *e)
 		if (s.kind == ENC_COEF) {
 			bool seen = false;
 			for (const Group &g : groups)
-				seen = seen || (g.b == s.src && g.fmt == s.coef_fmt && g.orient == s.coef.orient && g.rq == (s.coef.rq != 0));
+				seen = seen || (g.b == s.src && g.fmt == s.coef_fmt && g.orient == s.coef.orient && g.rq == (s.coef.rq != 0) && g.win == (s.coef.win != 0));
 			if (!seen)
-				groups.push_back(Group{s.src, s.coef_fmt, s.coef.orient, s.coef.rq != 0, 0, 0});
+				groups.push_back(Group{s.src, s.coef_fmt, s.coef.orient, s.coef.rq != 0, s.coef.win != 0, 0, 0});
 			if (std::find(batches.begin(), batches.end(), s.src) == batches.end())
 				batches.push_back(s.src);
 		}
@@ -4294,18 +4399,15 @@ static int enc_coef_convert(mij_encoder *e)
 	for (Group &g : groups) {
 		g.first = w;
 		for (const EncSlot &s : e->slots) {
-			if (s.kind != ENC_COEF || s.src != g.b || s.coef_fmt != g.fmt || s.coef.orient != g.orient || g.rq != (s.coef.rq != 0))
+			if (s.kind != ENC_COEF || s.src != g.b || s.coef_fmt != g.fmt || s.coef.orient != g.orient || g.rq != (s.coef.rq != 0) || g.win != (s.coef.win != 0))
 				continue;
 			e->h_cslot[k] = s.coef;
 			if (g.rq) {
 				rq_fill(e->h_rqt[q], (s.coef.orient & MIJ_CONV_TR) != 0, s.rq_from[0], s.tp.plan.ytab, s.rq_from[1], s.tp.plan.ctab);
 				e->h_cslot[k].rq = (uint32_t)++q;
 			}
-			for (uint32_t c = 0; c < s.coef.ncomp; ++c) {
-				const size_t nblk = (size_t)s.coef.mcu_x * s.coef.mcu_y * (c ? 1u : s.coef.lh * s.coef.lv);
-				for (size_t t = 0; t < (nblk + 63) / 64; ++t)
-					e->h_cwork[w++] = WorkIdct{(uint32_t)k, c, (uint32_t)t, 0u};
-			}
+			for (uint32_t c = 0; c < s.coef.ncomp; ++c)
+				coef_slot_tiles(s.coef, c, [&](uint32_t t) { e->h_cwork[w++] = WorkIdct{(uint32_t)k, c, t, 0u}; });
 			++k;
 		}
 		g.count = w - g.first;
@@ -4325,11 +4427,12 @@ static int enc_coef_convert(mij_encoder *e)
 			continue;
 		const dim3 grid((unsigned)g.count), block(64);
 		uint8_t *du = reinterpret_cast<uint8_t *>(e->d_du);
-		hipLaunchKernelGGL(k_coef_units_of[g.rq ? 1 : 0][g.fmt ? 1 : 0][g.orient & 7u], grid, block, 0, e->stream, e->d_cslot, e->d_cwork + g.first, g.b->d_coef, du,
+		hipLaunchKernelGGL((g.win ? k_coef_units_win_of : k_coef_units_of)[g.rq ? 1 : 0][g.fmt ? 1 : 0][g.orient & 7u], grid, block, 0, e->stream, e->d_cslot, e->d_cwork + g.first, g.b->d_coef, du,
 								 e->d_sflag, static_cast<const RqTable *>(e->d_rqt));
 		HIP_TRY(hipGetLastError());
 	}
 	HIP_TRY(hipEventRecord(e->ev_conv1, e->stream));
+	e->coef_tiles = (uint32_t)nw;
 	e->conv_timed = true;
 	return MIJ_OK;
 }

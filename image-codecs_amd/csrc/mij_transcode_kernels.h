@@ -34,6 +34,17 @@
  * coefficient's entries there (rq_fill, through the transposition of make_conv_table) -- so every read has a wave-uniform address and a
  * constant offset: scalar loads, no per-lane copy.  The DC predecessor goes through the DC entry before the difference is taken.
  * RQ = 0 instances contain none of this.
+ *
+ * Windows (mij_enc_add_coef_window; the rules are mjw_tplan_grey's and mjw_tplan_cropped's, mij_host.h).  WIN = 1 instances convert the slots
+ * whose destination is a crop of the (oriented) picture, or the grey picture of a colour source.  Both are "which blocks go where", so
+ * the tables and signs stay compile-time; what changes is geometry, all run-time: per component class the slot names the kept rectangle
+ * of the SOURCE plane in blocks, origin (w_ox, w_oy) and extent (w_ew, w_eh) -- the host has taken the crop back through the transpose,
+ * the mirrors and the trim.  A lane whose block lies outside it is dead (u = ~0); one inside mirrors within the rectangle, swaps when TR
+ * and takes its unit index from the destination's geometry, which for a grey destination of a colour source is dpm = 1, dh = dv = 1,
+ * ny = 1 while the plane keeps the colour source's stride.  The DC predecessor is the destination's previous unit mapped back through
+ * swap, mirrors and origin: the first unit of the window predicts from 0 whatever lies left of the cut.  The work list of such a slot
+ * names only the tiles that hold a block of the rectangle (enc_coef_convert), and no chroma tile for a grey destination.
+ * WIN = 0 instances contain none of this.
  */
 #pragma once
 
@@ -46,6 +57,8 @@ struct CoefSlot {
 	uint32_t ncomp, dpm, n_du, slot;            /* n_du: the destination's units; slot: the encoder slot, whose flag an uncodable value raises */
 	uint32_t d_mcu_x, d_mcu_y, d_lh, d_lv;      /* the destination's (the source's again for orientation 1) */
 	uint32_t ext_x, ext_y;                      /* the source's MCU columns and rows that the trim keeps */
+	uint32_t w_ox[2], w_oy[2], w_ew[2], w_eh[2]; /* a windowed slot (win != 0): the kept rectangle of the source plane in blocks, luma and chroma */
+	uint32_t win, pad;                          /* win: 1 for a slot the WIN = 1 instances convert */
 	uint32_t orient, rq;                        /* MIJ_CONV_NX | MIJ_CONV_NY | MIJ_CONV_TR: which template instance converts the slot; rq: 1 + the
 	                                               index of the slot's RqTable for a requantising slot (the RQ = 1 instances), 0 for a plain one */
 };
@@ -117,14 +130,14 @@ __device__ __forceinline__ int rq_value(int c, const RqEntry &q)
 	return x < 0 ? -y : y;
 }
 
-template <int COMPACT, int TR = 0, int NX = 0, int NY = 0, int RQ = 0>
+template <int COMPACT, int TR = 0, int NX = 0, int NY = 0, int RQ = 0, int WIN = 0>
 __global__ __launch_bounds__(64) void k_coef_units(const CoefSlot *__restrict__ slots, const WorkIdct *__restrict__ work, const uint8_t *__restrict__ coef,
 																	uint8_t *__restrict__ du_base, uint32_t *__restrict__ s_flag, const RqTable *__restrict__ rqt)
 {
 	__shared__ int16_t rows[64 * MIJ_CONV_ROW];
 	__shared__ uint32_t unit_of[64];
 	const WorkIdct wk = work[blockIdx.x];
-	const CoefSlot &s = slots[wk.img]; /* read in place (scalar loads): a copy indexed by c would live in scratch, 152 bytes per lane */
+	const CoefSlot &s = slots[wk.img]; /* read in place (scalar loads): a copy indexed by c would live in scratch, 184 bytes per lane */
 	const uint32_t c = wk.comp, tile = wk.first, lane = threadIdx.x;
 	const uint32_t h = c ? 1u : s.lh, v = c ? 1u : s.lv, bw = s.mcu_x * h, nblk = bw * s.mcu_y * v;
 	const uint32_t L = tile * 64u + lane;
@@ -174,17 +187,18 @@ __global__ __launch_bounds__(64) void k_coef_units(const CoefSlot *__restrict__ 
 		for (int P = 0; P < 64; ++P)
 			val[P] = rq_value(k_conv_table<TR, NX, NY>.neg[P] ? (int)(int16_t)-val[P] : val[P], q[P]);
 	}
-	constexpr bool PLAIN = !TR && !NX && !NY; /* orientation 1: the destination is the source */
-	/* the kept extent of the source plane in blocks, and the destination's geometry for this component */
-	const uint32_t ew = PLAIN ? bw : s.ext_x * h, eh = PLAIN ? s.mcu_y * v : s.ext_y * v;
+	constexpr bool PLAIN = !TR && !NX && !NY && !WIN; /* orientation 1 and no window: the destination is the source */
+	/* the kept extent of the source plane in blocks (a window: a rectangle with an origin), and the destination's geometry for this component */
+	const uint32_t ox = WIN ? s.w_ox[c ? 1 : 0] : 0u, oy = WIN ? s.w_oy[c ? 1 : 0] : 0u;
+	const uint32_t ew = WIN ? s.w_ew[c ? 1 : 0] : PLAIN ? bw : s.ext_x * h, eh = WIN ? s.w_eh[c ? 1 : 0] : PLAIN ? s.mcu_y * v : s.ext_y * v;
 	const uint32_t dh = PLAIN ? h : (c ? 1u : s.d_lh), dv = PLAIN ? v : (c ? 1u : s.d_lv), dmcu_x = PLAIN ? s.mcu_x : s.d_mcu_x;
 	const uint32_t sbx = L % bw, sby = L / bw;
 	uint32_t u = ~0u;
-	if (live && sbx < ew && sby < eh) {
-		const uint32_t x1 = NX ? ew - 1u - sbx : sbx, y1 = NY ? eh - 1u - sby : sby;
+	if (live && sbx - ox < ew && sby - oy < eh) { /* unsigned: a block left of or above the origin wraps and is out */
+		const uint32_t x1 = NX ? ew - 1u - (sbx - ox) : sbx - ox, y1 = NY ? eh - 1u - (sby - oy) : sby - oy;
 		const uint32_t bx = TR ? y1 : x1, by = TR ? x1 : y1; /* the block's place in the destination */
 		const uint32_t mx = bx / dh, my = by / dv, sx = bx - mx * dh, sy = by - my * dv;
-		const uint32_t ny = s.ncomp == 1u ? 1u : s.lh * s.lv;
+		const uint32_t ny = s.ncomp == 1u ? 1u : s.lh * s.lv; /* ncomp is the destination's: 1 for a grey destination of a colour source */
 		u = (my * dmcu_x + mx) * s.dpm + (c ? ny + c - 1u : sy * dh + sx);
 		if (u >= s.n_du)
 			u = ~0u;
@@ -205,7 +219,7 @@ __global__ __launch_bounds__(64) void k_coef_units(const CoefSlot *__restrict__ 
 		if (has) {
 			/* back through the swap and the mirrors to the source plane's block index */
 			const uint32_t qx = TR ? py : px, qy = TR ? px : py;
-			const size_t pb = (size_t)(NY ? eh - 1u - qy : qy) * bw + (NX ? ew - 1u - qx : qx);
+			const size_t pb = (size_t)(oy + (NY ? eh - 1u - qy : qy)) * bw + (ox + (NX ? ew - 1u - qx : qx));
 			if (COMPACT)
 				pred = reinterpret_cast<const int16_t *>(coef + s.dc_off[c])[pb];
 			else

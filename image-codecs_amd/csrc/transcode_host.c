@@ -1,6 +1,7 @@
 /*
  * transcode_host.c -- the host half of the lossless transcode (include/mij_host.h, mjw_tplan): which sources are transcodable, the
- * coefficient planes read as the writer's data units, the marker copy, and the whole path on the host (mjh_transcode_memory).  The
+ * coefficient planes read as the writer's data units, the orientation, requantisation, greyscale and crop steps, the marker copy, and
+ * the whole path on the host (mjh_transcode_memory, mjw_transcode_memory_window_at).  The
  * emission itself is the writer's (jpeg_write_host.c: mjw_temit).
  */
 #include <stdio.h>
@@ -361,18 +362,109 @@ int mjw_copy_markers(const uint8_t *src, int src_len, const unsigned char *strea
 	return 1;
 }
 
-int mjw_transcode_memory_requant_at(const uint8_t *src, int len, unsigned flags, int o, int trim, const unsigned char *luma,
-                                    const unsigned char *chroma, int coarsen_only, unsigned char **out, size_t *out_len, const char **reason)
+/* ---- greyscale and crop (mjw_tplan_grey, mjw_tplan_cropped, include/mij_host.h): which blocks go where, no coefficient value changes;
+ * and the whole chain grey -> orient -> crop -> requantise -> emit, which needs no EXIF code (mjh_transcode_memory_window,
+ * transcode_orient.c, adds the file's tag) */
+static int plan_ok(const mjw_tplan *t)
+{
+	return t && (t->ncomp == 1 || t->ncomp == 3) && t->lh >= 1 && t->lh <= 2 && t->lv >= 1 && t->lv <= 2 && t->plan.mcu_x >= 1 && t->plan.mcu_y >= 1 &&
+			 t->plan.width >= 1 && t->plan.height >= 1 && t->plan.du_per_mcu == (t->ncomp == 1 ? 1 : t->lh * t->lv + 2) && (t->ncomp == 3 || (t->lh == 1 && t->lv == 1));
+}
+
+int mjw_tplan_grey(mjw_tplan *dst, const mjw_tplan *src)
+{
+	mjw_tplan t;
+	if (!dst || !plan_ok(src))
+		return 0;
+	t = *src;
+	if (src->ncomp == 3) {
+		t.ncomp = 1;
+		t.lh = t.lv = 1;
+		t.plan.comp = 1;
+		t.plan.subsample = 0;
+		t.plan.mcu_x = (src->plan.width + 7) / 8;
+		t.plan.mcu_y = (src->plan.height + 7) / 8;
+		t.plan.du_per_mcu = 1;
+		memcpy(t.plan.ctab, t.plan.ytab, sizeof(t.plan.ctab));
+	}
+	*dst = t;
+	return 1;
+}
+
+int mjw_units_grey(const mjw_tplan *src, const int16_t *du_src, int16_t *du_dst)
+{
+	mjw_tplan t;
+	int bx, by;
+	if (!du_src || !du_dst || !mjw_tplan_grey(&t, src))
+		return 0;
+	if (src->ncomp == 1) {
+		memcpy(du_dst, du_src, mjw_tplan_du_count(src) * 64 * sizeof(int16_t));
+		return 1;
+	}
+	for (by = 0; by < t.plan.mcu_y; ++by)
+		for (bx = 0; bx < t.plan.mcu_x; ++bx, du_dst += 64)
+			memcpy(du_dst,
+					 du_src + 64 * (((size_t)(by / src->lv) * (size_t)src->plan.mcu_x + (size_t)(bx / src->lh)) * (size_t)src->plan.du_per_mcu +
+										 (size_t)((by % src->lv) * src->lh + bx % src->lh)),
+					 64 * sizeof(int16_t));
+	return 1;
+}
+
+int mjw_tplan_cropped(mjw_tplan *dst, const mjw_tplan *src, int x0, int y0, int w, int h, int rect[4], const char **reason)
+{
+	static _Thread_local char why[200];
+	mjw_tplan t;
+	int mw, mh, dx, dy;
+	if (!dst || !plan_ok(src))
+		return refuse(reason, "bad argument");
+	if (w < 1 || h < 1 || x0 < 0 || y0 < 0 || x0 > src->plan.width - w || y0 > src->plan.height - h) {
+		snprintf(why, sizeof(why), "the window %dx%d+%d+%d does not lie inside the picture (%d x %d)", w, h, x0, y0, src->plan.width, src->plan.height);
+		return refuse(reason, why);
+	}
+	mw = 8 * src->lh, mh = 8 * src->lv;
+	dx = x0 % mw, dy = y0 % mh;
+	t = *src;
+	t.plan.width = w + dx;
+	t.plan.height = h + dy;
+	t.plan.mcu_x = (t.plan.width + mw - 1) / mw;
+	t.plan.mcu_y = (t.plan.height + mh - 1) / mh;
+	if (rect)
+		rect[0] = x0 - dx, rect[1] = y0 - dy, rect[2] = t.plan.width, rect[3] = t.plan.height;
+	*dst = t;
+	return 1;
+}
+
+int mjw_units_crop(const mjw_tplan *src, const int16_t *du_src, const int rect[4], int16_t *du_dst)
+{
+	mjw_tplan t;
+	int my, kept[4];
+	if (!du_src || !du_dst || !rect || !mjw_tplan_cropped(&t, src, rect[0], rect[1], rect[2], rect[3], kept, NULL) || kept[0] != rect[0] || kept[1] != rect[1])
+		return 0; /* rect is a kept rectangle: its origin lies on the MCU grid */
+	{
+		const size_t row = (size_t)t.plan.mcu_x * (size_t)src->plan.du_per_mcu * 64;
+		const int mx0 = rect[0] / (8 * src->lh), my0 = rect[1] / (8 * src->lv);
+		for (my = 0; my < t.plan.mcu_y; ++my)
+			memcpy(du_dst + (size_t)my * row,
+					 du_src + ((size_t)(my + my0) * (size_t)src->plan.mcu_x + (size_t)mx0) * (size_t)src->plan.du_per_mcu * 64, row * sizeof(int16_t));
+	}
+	return 1;
+}
+
+/* one step's units replace the previous step's */
+static int16_t *units_for(const mjw_tplan *t) { return (int16_t *)malloc(mjw_tplan_du_count(t) * 64 * sizeof(int16_t)); }
+
+int mjw_transcode_memory_window_at(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
+                                   const unsigned char *chroma, int coarsen_only, unsigned char **out, size_t *out_len, int *rect_out,
+                                   const char **reason)
 {
 	mij_image_desc d;
-	mjw_tplan t, ts, tq;
-	int rq = 0;
+	mjw_tplan t, next;
 	const char *why = NULL;
 	uint8_t *region = NULL;
-	int16_t *du = NULL, *du_src = NULL;
+	int16_t *du = NULL, *dn = NULL;
 	unsigned char *buf = NULL;
-	size_t rbytes, nu, cap, n = 0;
-	int ok = 0;
+	size_t rbytes, cap, n = 0;
+	int ok = 0, rect[4];
 	if (!out || !out_len)
 		return refuse(reason, "bad argument");
 	*out = NULL;
@@ -391,40 +483,54 @@ int mjw_transcode_memory_requant_at(const uint8_t *src, int len, unsigned flags,
 		refuse(reason, why ? why : "decode failed");
 		goto done;
 	}
-	if (!mjw_tplan_from_desc(&ts, &d, reason) || !mjw_tplan_oriented(&t, &ts, o, trim, reason))
+	if (!mjw_tplan_from_desc(&t, &d, reason))
 		goto done;
-	nu = mjw_tplan_du_count(&t);
-	du = (int16_t *)malloc(nu * 64 * sizeof(int16_t));
-	if (o != 1)
-		du_src = (int16_t *)malloc(mjw_tplan_du_count(&ts) * 64 * sizeof(int16_t));
-	cap = MJW_STREAM_CAP(nu);
-	buf = (unsigned char *)malloc(cap);
-	if (!du || !buf || (o != 1 && !du_src)) {
+	du = units_for(&t);
+	if (!du) {
 		refuse(reason, "out of memory");
 		goto done;
 	}
-	if (!mjw_units_from_region(&d, region, (d.flags & MIJ_FLAG_STAGED_COMPACT) ? MIJ_COEF_COMPACT : MIJ_COEF_INT16, o != 1 ? du_src : du) ||
-		 (o != 1 && !mjw_units_orient(&ts, du_src, o, trim, du))) {
+	if (!mjw_units_from_region(&d, region, (d.flags & MIJ_FLAG_STAGED_COMPACT) ? MIJ_COEF_COMPACT : MIJ_COEF_INT16, du)) {
 		refuse(reason, "units could not be read");
 		goto done;
 	}
-	if (luma) { /* requant(orient(source)): a plan whose tables did not change keeps its units */
-		if (!(rq = mjw_tplan_requant(&tq, &t, luma, chroma, coarsen_only, reason)))
+#define STEP(plan_call, units_call)            \
+	do {                                        \
+		if (!(plan_call))                        \
+			goto done;                            \
+		dn = units_for(&next);                   \
+		if (!dn || !(units_call)) {              \
+			refuse(reason, dn ? "units could not be read" : "out of memory"); \
+			goto done;                            \
+		}                                        \
+		free(du);                                \
+		du = dn, dn = NULL, t = next;            \
+	} while (0)
+	if (grey && t.ncomp == 3)
+		STEP(mjw_tplan_grey(&next, &t) || refuse(reason, "bad source plan"), mjw_units_grey(&t, du, dn));
+	if (o != 1)
+		STEP(mjw_tplan_oriented(&next, &t, o, trim, reason), mjw_units_orient(&t, du, o, trim, dn));
+	else if (!mjw_tplan_oriented(&next, &t, o, trim, reason))
+		goto done;
+	rect[0] = rect[1] = 0, rect[2] = t.plan.width, rect[3] = t.plan.height;
+	if (crop)
+		STEP(mjw_tplan_cropped(&next, &t, crop[0], crop[1], crop[2], crop[3], rect, reason), mjw_units_crop(&t, du, rect, dn));
+	if (luma) { /* a plan whose tables did not change keeps its units */
+		const int rq = mjw_tplan_requant(&next, &t, luma, chroma, coarsen_only, reason);
+		if (!rq)
 			goto done;
-		if (rq == 2) {
-			int16_t *dq = (int16_t *)malloc(nu * 64 * sizeof(int16_t));
-			if (!dq || !mjw_units_requant(&t, &tq, du, dq)) {
-				free(dq);
-				refuse(reason, dq ? "units could not be requantised" : "out of memory");
-				goto done;
-			}
-			free(du);
-			du = dq;
-			t = tq;
-		}
+		if (rq == 2)
+			STEP(1, mjw_units_requant(&t, &next, du, dn));
 	}
+#undef STEP
 	if (!mjw_tunits_codable(&t, du, reason))
 		goto done;
+	cap = MJW_STREAM_CAP(mjw_tplan_du_count(&t));
+	buf = (unsigned char *)malloc(cap);
+	if (!buf) {
+		refuse(reason, "out of memory");
+		goto done;
+	}
 	n = mjw_temit_to_memory(&t, du, flags & MJW_OPTIMIZE_HUFFMAN, buf, cap);
 	if (!n) {
 		refuse(reason, "emission failed");
@@ -438,12 +544,20 @@ int mjw_transcode_memory_requant_at(const uint8_t *src, int len, unsigned flags,
 		buf = NULL;
 		ok = 1;
 	}
+	if (ok && rect_out)
+		memcpy(rect_out, rect, sizeof(rect));
 done:
 	free(region);
 	free(du);
-	free(du_src);
+	free(dn);
 	free(buf);
 	return ok;
+}
+
+int mjw_transcode_memory_requant_at(const uint8_t *src, int len, unsigned flags, int o, int trim, const unsigned char *luma,
+                                    const unsigned char *chroma, int coarsen_only, unsigned char **out, size_t *out_len, const char **reason)
+{
+	return mjw_transcode_memory_window_at(src, len, flags, o, trim, NULL, 0, luma, chroma, coarsen_only, out, out_len, NULL, reason);
 }
 
 int mjw_transcode_memory_at(const uint8_t *src, int len, unsigned flags, int o, int trim, unsigned char **out, size_t *out_len, const char **reason)

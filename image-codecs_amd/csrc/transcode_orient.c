@@ -1,14 +1,16 @@
 /*
- * transcode_orient.c -- mjh_transcode_memory_oriented and mjh_transcode_memory_requant (include/mij_host.h): the transcode on the host
- * with an orientation applied, the file's own EXIF tag included, and optionally new quantisation tables.  The transform itself is transcode_host.c's (mjw_tplan_oriented, mjw_units_orient,
- * mjw_transcode_memory_requant_at); this file adds what needs the EXIF walk (exif.c), so that transcode_host.c links without it.
+ * transcode_orient.c -- mjh_transcode_memory_oriented, mjh_transcode_memory_requant and mjh_transcode_memory_window (include/mij_host.h):
+ * the transcode on the host with an orientation applied, the file's own EXIF tag included, and optionally a crop, greyscale and new
+ * quantisation tables.  The transforms themselves are transcode_host.c's (mjw_tplan_oriented, mjw_units_orient, mjw_tplan_cropped,
+ * mjw_transcode_memory_window_at); this file adds what needs the EXIF walk (exif.c), so that transcode_host.c links without it.
  */
 #include <limits.h>
 
 #include "mij_host.h"
 
-int mjh_transcode_memory_requant(const uint8_t *src, int len, unsigned flags, int o, int trim, const unsigned char *luma,
-                                 const unsigned char *chroma, int coarsen_only, unsigned char **out, size_t *out_len, const char **reason)
+int mjh_transcode_memory_window(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
+                                const unsigned char *chroma, int coarsen_only, unsigned char **out, size_t *out_len, int *rect_out,
+                                const char **reason)
 {
 	if (o < 0 || o > 8) {
 		if (out)
@@ -21,12 +23,18 @@ int mjh_transcode_memory_requant(const uint8_t *src, int len, unsigned flags, in
 	}
 	if (o == 0)
 		o = mjh_exif_orientation(src, len);
-	if (!mjw_transcode_memory_requant_at(src, len, flags, o, trim, luma, chroma, coarsen_only, out, out_len, reason))
+	if (!mjw_transcode_memory_window_at(src, len, flags, o, trim, crop, grey, luma, chroma, coarsen_only, out, out_len, rect_out, reason))
 		return 0;
 	/* the picture is upright now: a copied tag that still said otherwise would turn it a second time */
 	if ((flags & MJW_COPY_MARKERS) && o != 1)
 		(void)mjh_exif_set_orientation(*out, *out_len > (size_t)INT_MAX ? INT_MAX : (int)*out_len, 1);
 	return 1;
+}
+
+int mjh_transcode_memory_requant(const uint8_t *src, int len, unsigned flags, int o, int trim, const unsigned char *luma,
+                                 const unsigned char *chroma, int coarsen_only, unsigned char **out, size_t *out_len, const char **reason)
+{
+	return mjh_transcode_memory_window(src, len, flags, o, trim, NULL, 0, luma, chroma, coarsen_only, out, out_len, NULL, reason);
 }
 
 int mjh_transcode_memory_oriented(const uint8_t *src, int len, unsigned flags, int o, int trim, unsigned char **out, size_t *out_len,

@@ -6,7 +6,8 @@ cross PCIe on the way back.  No pixel kernel is launched.
 
 This module needs no torch."""
 from .binding import Batch, Context, Encoder, HostDecoder, MijError, _qtable_pair, copy_markers as _copy_markers, emit_transcoded, \
-    exif_orientation, exif_set_orientation, quality_tables, transcode_plan
+    exif_orientation, exif_set_orientation, quality_tables, transcode_plan, transcode_plan_cropped, transcode_plan_grey, \
+    transcode_plan_oriented
 
 # one launch takes at most this many pictures / bytes of coefficient arena; larger calls are cut into chunks
 MAX_SLOTS = 4096
@@ -64,6 +65,71 @@ def _targets(quality, qtables, n):
     return [None if q is None else made[q] for q in vals]
 
 
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def _window(v):
+    """one crop window as a tuple of four ints, ValueError for anything else or a size below 1"""
+    what = "a crop window is (x0, y0, w, h), four ints with w >= 1 and h >= 1 (got %r)"
+    if isinstance(v, (str, bytes)):
+        raise ValueError(what % (v,))
+    try:
+        win = tuple(v)
+    except TypeError:
+        raise ValueError(what % (v,)) from None
+    if len(win) != 4 or not all(_is_int(x) for x in win) or win[2] < 1 or win[3] < 1:
+        raise ValueError(what % (v,))
+    return win
+
+
+def _crops(v, n):
+    """transcode's crop= as one window or None per source"""
+    if v is None:
+        return [None] * n
+    if isinstance(v, (str, bytes)):
+        raise ValueError("crop must be None, one (x0, y0, w, h) or one of those per source (got %r)" % (v,))
+    try:
+        vals = list(v)
+    except TypeError:
+        raise ValueError("crop must be None, one (x0, y0, w, h) or one of those per source (got %r)" % (v,)) from None
+    if vals and all(_is_int(x) or isinstance(x, (bool, float)) for x in vals):  # numbers: one window for all
+        return [_window(vals)] * n
+    if len(vals) != n:
+        raise ValueError("crop has %d windows for %d sources" % (len(vals), n))
+    return [None if w is None else _window(w) for w in vals]
+
+
+def _greys(v, n):
+    """transcode's grey= as one bool per source"""
+    if isinstance(v, bool):
+        return [v] * n
+    if isinstance(v, (str, bytes)):
+        raise ValueError("grey must be a bool or one per source (got %r)" % (v,))
+    try:
+        vals = list(v)
+    except TypeError:
+        raise ValueError("grey must be a bool or one per source (got %r)" % (v,)) from None
+    if len(vals) != n:
+        raise ValueError("grey has %d values for %d sources" % (len(vals), n))
+    if not all(isinstance(g, bool) for g in vals):
+        raise ValueError("grey must be a bool or one per source (got %r)" % (v,))
+    return vals
+
+
+def _destination(desc, o, trim, crop, grey):
+    """-> (data-unit elements, pixels) of the picture a source becomes, from its header alone; None where a step refuses (mij_enc_add_coef
+    says why later) and the source's own size has to do"""
+    t = transcode_plan(desc)[0]
+    if t is not None and grey:
+        t = transcode_plan_grey(t)
+    if t is not None:
+        t = transcode_plan_oriented(t, o, trim)[0]
+    if t is not None and crop is not None:
+        t = transcode_plan_cropped(t, crop)[0]
+    return None if t is None else (t.du_elems(), t.plan.width * t.plan.height)
+
+
 class Transcoder:
     """transcode(datas) -> one new JPEG stream per source, or None where the source cannot be transcoded (last_reasons says why).
 
@@ -87,6 +153,8 @@ class Transcoder:
         self.last_reasons = []
         self.last_host_emitted = 0
         self.last_requantized = []
+        self.last_crops = []
+        self.last_greyed = []
         self.last_timing = {}
 
     @property
@@ -149,7 +217,7 @@ class Transcoder:
         return self._enc
 
     def transcode(self, datas, *, optimize=True, copy_markers="all", only_if_smaller=False, gpu_entropy=None, threads=16, orientation=None,
-                  edge="perfect", quality=None, qtables=None, coarsen_only=True):
+                  edge="perfect", quality=None, qtables=None, coarsen_only=True, crop=None, grey=False):
         """datas: a sequence of JPEG files as bytes.  -> a list with, per source, the new stream (bytes) or None; last_reasons[i] is None
         or the reason source i was refused or could not be decoded.
         optimize: Huffman tables built from each picture's own statistics (mjw_temit_optimized's stream); False: the Annex-K tables.
@@ -171,6 +239,16 @@ class Transcoder:
         order for all sources.  coarsen_only (default): each entry becomes the larger of the source's and the target's, since a finer
         step restores nothing and only grows the file; False takes the target as it is.  last_requantized[i] says whether source i's
         tables changed; where they did not, the stream is the lossless one.  only_if_smaller keeps its meaning.
+        grey: a bool, or one per source: Cb and Cr are dropped and the luma coefficients kept to the bit (jpegtran -grayscale), before the
+        orientation -- a grey picture's MCU is 8 x 8, so edge="perfect" mirrors a 4:2:0 picture whose size is a multiple of 8 but not
+        of 16 once it is grey.  last_greyed[i] says whether chroma was dropped (not for a grey source).
+        crop: None, one window (x0, y0, w, h) for all sources, or a sequence with one window or None per source, in the displayed frame
+        (after the orientation), as TensorDecoder's crops are: the window is cut out of the coefficients (jpegtran -crop).  Its origin
+        moves down to the MCU grid (8 * h_luma x 8 * v_luma, 8 x 8 once grey) and the size grows by what it moved; last_crops[i] is the
+        kept (x0', y0', W', H'), None where no crop was asked.  A window that does not lie inside its picture is refused for that picture
+        alone, with its reason in last_reasons[i].  The steps run as grey -> orient -> crop -> requantise (include/mij_host.h,
+        mjw_tplan_cropped); where crop or grey changed the picture the result is returned whatever only_if_smaller says.  EXIF pixel
+        dimensions and thumbnails of copied markers are not fixed up.
         ValueError, before a device is touched, for arguments that are not of these kinds."""
         if not isinstance(optimize, bool) or not isinstance(only_if_smaller, bool):
             raise ValueError("optimize and only_if_smaller must be bools")
@@ -193,7 +271,12 @@ class Transcoder:
         datas = [bytes(d) for d in datas]
         orients = _orientations(orientation, datas)
         targets = _targets(quality, qtables, len(datas))
+        crops = _crops(crop, len(datas))
+        greys = _greys(grey, len(datas))
         self.last_requantized = requantized = [False] * len(datas)
+        self.last_crops = kept = [None] * len(datas)
+        self.last_greyed = greyed = [False] * len(datas)
+        windowed = [False] * len(datas)
         out = [None] * len(datas)
         reasons = [None] * len(datas)
         self.last_host_emitted = 0
@@ -213,8 +296,12 @@ class Transcoder:
                     any((desc.comp[c].h, desc.comp[c].v) != (1, 1) for c in range(1, desc.ncomp)):
                 reasons[i] = "not transcodable: " + (transcode_plan(desc)[1] or "refused")
                 continue
-            du = sum(desc.comp[c].bw * desc.comp[c].bh for c in range(desc.ncomp)) * 128
-            todo.append((i, Batch.coef_bytes(desc), Batch.out_bytes(desc), _align(du, 256), desc.width * desc.height))
+            du, px = sum(desc.comp[c].bw * desc.comp[c].bh for c in range(desc.ncomp)) * 128, desc.width * desc.height
+            if crops[i] is not None or greys[i]:  # the arenas hold the destination: a window of a large picture needs little
+                dst = _destination(desc, orients[i], edge == "trim", crops[i], greys[i])
+                if dst is not None:
+                    du, px = dst[0] * 2, dst[1]
+            todo.append((i, Batch.coef_bytes(desc), Batch.out_bytes(desc), _align(du, 256), px))
         k = 0
         while k < len(todo):
             j, coef = k, 0
@@ -222,7 +309,7 @@ class Transcoder:
                 coef += todo[j][1]
                 j += 1
             self._chunk(datas, todo[k:j], out, reasons, optimize, gpu_entropy, threads, orients, edge == "trim", targets, coarsen_only,
-                        requantized)
+                        requantized, crops, greys, kept, greyed, windowed)
             k = j
         for i, d in enumerate(datas):
             if out[i] is None:
@@ -234,12 +321,13 @@ class Transcoder:
                     continue
                 if orients[i] != 1:  # the picture is upright now: the copied tag must not turn it again
                     out[i], _ = exif_set_orientation(out[i], 1)
-            if only_if_smaller and orients[i] == 1 and len(out[i]) >= len(d):
+            if only_if_smaller and orients[i] == 1 and not windowed[i] and len(out[i]) >= len(d):
                 out[i] = d
         self.last_reasons = reasons
         return out
 
-    def _chunk(self, datas, items, out, reasons, optimize, gpu_entropy, threads, orients, trim, targets, coarsen_only, requantized):
+    def _chunk(self, datas, items, out, reasons, optimize, gpu_entropy, threads, orients, trim, targets, coarsen_only, requantized, crops,
+               greys, kept, greyed, windowed):
         n = len(items)
         srcs = [datas[it[0]] for it in items]
         stream = 0
@@ -261,10 +349,14 @@ class Transcoder:
                 reasons[it[0]] = r or "decode failed"
                 continue
             try:
-                es[it[0]] = enc.add_coef(b, sl, orients[it[0]], trim, targets[it[0]], coarsen_only)
+                es[it[0]] = enc.add_coef(b, sl, orients[it[0]], trim, targets[it[0]], coarsen_only, crops[it[0]], greys[it[0]])
             except MijError as e:
                 reasons[it[0]] = str(e).split(": ", 1)[-1]
                 continue
+            if crops[it[0]] is not None:
+                kept[it[0]] = enc.slot_rect(es[it[0]])
+            greyed[it[0]] = enc.slot_greyed(es[it[0]])
+            windowed[it[0]] = enc.slot_windowed(es[it[0]])
             requantized[it[0]] = enc.slot_requantized(es[it[0]])
             if optimize:
                 enc.set_optimize(es[it[0]])

@@ -714,12 +714,31 @@ int mij_enc_slot_optimized(const mij_encoder *e, int slot);
  * misses the arena is finished on the host as before.  MIJ_E_ARG ("not requantisable: ...") for a zero table entry.  One upload may
  * hold plain, oriented and requantising slots.  mij_enc_slot_requantized: 1 for a coefficient slot whose tables changed, 0 for a plain
  * one, MIJ_E_ARG for any other slot.
+ *
+ * mij_enc_add_coef_window: the same slot with jpegtran's -grayscale and -crop as well, in the order grey -> orient -> crop -> requantise
+ * (the contract is mij_host.h's, mjw_tplan_grey and mjw_tplan_cropped).  grey != 0 drops Cb and Cr of a colour source: the destination
+ * is a one-component picture whose MCU is 8 x 8, which the edge mode and the crop then see.  crop = (x0, y0, w, h) in the displayed
+ * frame (after the orientation), or NULL; the kept rectangle -- the origin moved down to the MCU grid -- is written to rect_out (may be
+ * NULL; (0, 0, W, H) of the destination without a crop) and mij_enc_slot_rect returns it later.  MIJ_E_ARG ("not croppable: ...") for a
+ * window that does not lie inside the picture.  A slot with no crop (or the whole picture) and no grey (or a grey source) is a plain slot
+ * and is converted by the instance that converted it before; every other one is a windowed slot: the conversion kernel's WIN instances
+ * read, per component, only the 64-block plane tiles that hold a block of the kept rectangle, and no chroma tile for a grey
+ * destination.  mij_enc_add_coef_requant is this with no crop and grey = 0.
+ * mij_enc_slot_greyed: 1 for a coefficient slot whose chroma was dropped; mij_enc_slot_windowed: 1 for a windowed slot (crop or grey
+ * changed the picture), 0 for a plain one; MIJ_E_ARG for any other slot.
+ * mij_enc_coef_tiles: the number of plane tiles the last mij_enc_upload queued for conversion, over all its coefficient slots.
  */
 enum { MIJ_ENC_SLOT_OK = 0, MIJ_ENC_SLOT_NO_ROOM = 1, MIJ_ENC_SLOT_UNCODABLE = 2 };
 int mij_enc_add_coef(mij_encoder *e, mij_batch *b, int slot);
 int mij_enc_add_coef_oriented(mij_encoder *e, mij_batch *b, int slot, int orientation, int trim);
 int mij_enc_add_coef_requant(mij_encoder *e, mij_batch *b, int slot, int orientation, int trim, const unsigned char *luma,
                              const unsigned char *chroma, int coarsen_only);
+int mij_enc_add_coef_window(mij_encoder *e, mij_batch *b, int slot, int orientation, int trim, const int *crop, int grey, const unsigned char *luma,
+                            const unsigned char *chroma, int coarsen_only, int *rect_out);
+int mij_enc_slot_rect(const mij_encoder *e, int slot, int rect[4]);
+int mij_enc_slot_greyed(const mij_encoder *e, int slot);
+int mij_enc_slot_windowed(const mij_encoder *e, int slot);
+int mij_enc_coef_tiles(const mij_encoder *e, uint32_t *tiles);
 int mij_enc_slot_requantized(const mij_encoder *e, int slot);
 int mij_enc_slot_status(const mij_encoder *e, int slot);
 int mij_enc_coef_ms(mij_encoder *e, float *ms);

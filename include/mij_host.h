@@ -331,6 +331,54 @@ int mjw_transcode_memory_requant_at(const uint8_t *src, int len, unsigned flags,
 int mjh_transcode_memory_requant(const uint8_t *src, int len, unsigned flags, int o, int trim, const unsigned char *luma,
                                  const unsigned char *chroma, int coarsen_only, unsigned char **out, size_t *out_len, const char **reason);
 
+/*
+ * Greyscale and crop in the transcode (jpegtran -grayscale, jpegtran -crop WxH+X+Y): which blocks go where; no coefficient value changes
+ * and no pixel is made.  On the GPU: mij_enc_add_coef_window (mij.h); these calls are the written contract.  The steps run in a fixed
+ * order, each plan-to-plan and units-to-units:   grey -> orient (edge mode) -> crop -> requantise -> emit
+ *
+ * GREY.  A three-component plan becomes a one-component plan of the same width and height: lh = lv = 1, mcu_x = ceil(W / 8),
+ * mcu_y = ceil(H / 8), du_per_mcu = 1, ytab kept and ctab = ytab (the grey plan's convention).  Unit (bx, by) of the destination is luma
+ * plane block (bx, by) of the source; the luma blocks beyond ceil(W / 8) x ceil(H / 8) -- the source's MCU padding -- are dropped.  A grey
+ * source is copied.  Every later step sees a grey picture: the edge mode's MCU size and the crop's grid are 8 x 8, so a 4:2:0 picture
+ * whose height is a multiple of 8 but not of 16 is mirrored exactly once it is grey.
+ *
+ * CROP.  In the frame of the plan it is given -- the displayed frame, after the orientation -- of size W x H and MCU size mw = 8 * lh,
+ * mh = 8 * lv.  A window (x0, y0, w, h) is refused, with a reason that names the window and the picture's size, unless w >= 1, h >= 1,
+ * x0 >= 0, y0 >= 0, x0 + w <= W and y0 + h <= H.  The kept rectangle is jpegtran's: the origin moves down to the MCU grid and the size
+ * grows by what the origin moved, so the right and bottom edges stay where they were asked:  x0' = x0 - x0 % mw, W' = w + x0 % mw, the
+ * same for y.  The destination has size W' x H', the same sampling and tables, mcu_x = ceil(W' / mw), mcu_y = ceil(H' / mh); its block
+ * (bx, by) of component c is the source's block (bx + (x0' / mw) * h_c, by + (y0' / mh) * v_c): the window is shifted by whole MCUs, each
+ * component by that many MCUs times its own factor.  A partial last MCU column or row takes the blocks the source planes hold there, as
+ * jpegtran does.  A window that is the whole picture copies the plan and the units.
+ *
+ * Codability (mjw_tunits_codable) is judged on the final units in the destination's unit order: a DC's predecessor is the previous unit
+ * of its component INSIDE the window, the first one's is 0 -- so a cut can make a codable source uncodable and the reverse.
+ *
+ * MARKERS with MJW_COPY_MARKERS are copied as before and the Orientation tag is reset when o != 1.  An Adobe APP14 on a now one-component
+ * frame is left alone (a one-component frame takes no colour transform).  NOT fixed, as before: EXIF pixel dimensions and thumbnails.
+ *
+ *   mjw_tplan_grey      dst = the grey plan of src; 0 for a bad plan
+ *   mjw_units_grey      the grey plan's units from src's; 0 on bad arguments
+ *   mjw_tplan_cropped   dst = the plan of the kept rectangle, rect (may be NULL) = (x0', y0', W', H'); 0 with *reason (a per-thread string,
+ *                       valid until the thread's next call) for a refused window
+ *   mjw_units_crop      the units of the kept rectangle `rect` (as mjw_tplan_cropped returned it: origin on the MCU grid) from src's
+ *   mjw_transcode_memory_window_at   the whole chain with o in 1..8; crop = (x0, y0, w, h) or NULL, grey 0 or 1; rect_out (may be NULL)
+ *                       gets the kept rectangle, (0, 0, W, H) of the oriented picture without a crop.  mjw_transcode_memory_requant_at is
+ *                       this with no crop and grey = 0.
+ *   mjh_transcode_memory_window      the same with o = 0 meaning the file's own tag; mjh_transcode_memory_requant is this with no crop and
+ *                       grey = 0, byte for byte what it was.
+ */
+int mjw_tplan_grey(mjw_tplan *dst, const mjw_tplan *src);
+int mjw_units_grey(const mjw_tplan *src, const int16_t *du_src, int16_t *du_dst);
+int mjw_tplan_cropped(mjw_tplan *dst, const mjw_tplan *src, int x0, int y0, int w, int h, int rect[4], const char **reason);
+int mjw_units_crop(const mjw_tplan *src, const int16_t *du_src, const int rect[4], int16_t *du_dst);
+int mjw_transcode_memory_window_at(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
+                                   const unsigned char *chroma, int coarsen_only, unsigned char **out, size_t *out_len, int *rect_out,
+                                   const char **reason);
+int mjh_transcode_memory_window(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
+                                const unsigned char *chroma, int coarsen_only, unsigned char **out, size_t *out_len, int *rect_out,
+                                const char **reason);
+
 /* The tables of stbi__ldr_to_hdr(common.c:391-424) for mij_batch_set_out_f32: lut[256*k + v] for channel k < n_out.  Colour
  * channels (all of them for odd n_out, all but the last for even n_out) get (float)(pow(v / 255.0f, gamma) * scale), the
  * alpha channel of n_out 2 and 4 gets v / 255.0f -- the reference's expressions, evaluated with libm's pow. */
