@@ -1224,15 +1224,30 @@ def host_transform(pixels, quality=90, flip=False):
     return plan, du.reshape(-1, 64)
 
 
-def emit_jpeg(plan, du, optimize=False):
+def _restart_mcus(v):
+    """a restart interval in MCUs as an int; None means 0 (none)"""
+    if v is None:
+        return 0
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        raise ValueError("a restart interval is None or an int (got %r)" % (v,))
+    return int(v)
+
+
+def emit_jpeg(plan, du, optimize=False, restart_mcus=None):
     """mjw_emit: headers + Huffman stage over given data units -> bytes.  optimize: mjw_emit_optimized, the same stream with Huffman
-    tables built from the units' own symbol statistics."""
+    tables built from the units' own symbol statistics.  restart_mcus: mjw_emit_restart, a restart interval of that many MCUs (None or
+    0: none, the calls above); None for an interval outside 0..65535."""
     L = lib()
-    fn = L.mjw_emit_optimized if optimize else L.mjw_emit
-    fn.argtypes = [C.POINTER(WritePlan), C.c_void_p, _WRITE_CB, C.c_void_p]
+    ri = _restart_mcus(restart_mcus)
     chunks = []
     cb = _WRITE_CB(lambda _c, data, size: chunks.append(C.string_at(data, size)))
     d = np.ascontiguousarray(du, dtype=np.int16)
+    if ri:
+        L.mjw_emit_restart.argtypes = [C.POINTER(WritePlan), C.c_void_p, C.c_uint, C.c_int, _WRITE_CB, C.c_void_p]
+        ok = L.mjw_emit_restart(C.byref(plan), d.ctypes.data_as(C.c_void_p), MJW_OPTIMIZE_HUFFMAN if optimize else 0, ri, cb, None)
+        return b"".join(chunks) if ok else None
+    fn = L.mjw_emit_optimized if optimize else L.mjw_emit
+    fn.argtypes = [C.POINTER(WritePlan), C.c_void_p, _WRITE_CB, C.c_void_p]
     ok = fn(C.byref(plan), d.ctypes.data_as(C.c_void_p), cb, None)
     return b"".join(chunks) if ok else None
 
@@ -1300,29 +1315,67 @@ def units_from_region(desc, region, compact):
     return du.reshape(-1, 64)
 
 
-def units_codable(tplan, du):
-    """mjw_tunits_codable -> (True, None) or (False, reason)"""
+def units_codable(tplan, du, restart_mcus=None):
+    """mjw_tunits_codable -> (True, None) or (False, reason); restart_mcus: mjw_tunits_codable_restart, the DC differences taken against
+    predictors that restart every that many MCUs"""
     L = lib()
-    L.mjw_tunits_codable.argtypes = [C.POINTER(TranscodePlan), C.c_void_p, C.POINTER(C.c_char_p)]
+    ri = _restart_mcus(restart_mcus)
     d = np.ascontiguousarray(du, np.int16)
     if d.size != tplan.du_elems():
         raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, tplan.du_elems()))
     why = C.c_char_p()
-    ok = L.mjw_tunits_codable(C.byref(tplan), d.ctypes.data_as(C.c_void_p), C.byref(why))
+    if ri:
+        L.mjw_tunits_codable_restart.argtypes = [C.POINTER(TranscodePlan), C.c_void_p, C.c_int, C.POINTER(C.c_char_p)]
+        ok = L.mjw_tunits_codable_restart(C.byref(tplan), d.ctypes.data_as(C.c_void_p), ri, C.byref(why))
+    else:
+        L.mjw_tunits_codable.argtypes = [C.POINTER(TranscodePlan), C.c_void_p, C.POINTER(C.c_char_p)]
+        ok = L.mjw_tunits_codable(C.byref(tplan), d.ctypes.data_as(C.c_void_p), C.byref(why))
     return bool(ok), (None if ok else why.value.decode())
 
 
-def emit_transcoded(tplan, du, optimize=False):
-    """mjw_temit / mjw_temit_optimized over given units -> bytes, None when the units are not codable."""
+def emit_transcoded(tplan, du, optimize=False, restart_mcus=None):
+    """mjw_temit / mjw_temit_optimized over given units -> bytes, None when the units are not codable.  restart_mcus: mjw_temit_restart."""
     L = lib()
-    fn = L.mjw_temit_optimized if optimize else L.mjw_temit
-    fn.argtypes = [C.POINTER(TranscodePlan), C.c_void_p, _WRITE_CB, C.c_void_p]
+    ri = _restart_mcus(restart_mcus)
     d = np.ascontiguousarray(du, np.int16)
     if d.size != tplan.du_elems():
         raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, tplan.du_elems()))
     chunks = []
     cb = _WRITE_CB(lambda _c, data, size: chunks.append(C.string_at(data, size)))
+    if ri:
+        L.mjw_temit_restart.argtypes = [C.POINTER(TranscodePlan), C.c_void_p, C.c_uint, C.c_int, _WRITE_CB, C.c_void_p]
+        ok = L.mjw_temit_restart(C.byref(tplan), d.ctypes.data_as(C.c_void_p), MJW_OPTIMIZE_HUFFMAN if optimize else 0, ri, cb, None)
+        return b"".join(chunks) if ok else None
+    fn = L.mjw_temit_optimized if optimize else L.mjw_temit
+    fn.argtypes = [C.POINTER(TranscodePlan), C.c_void_p, _WRITE_CB, C.c_void_p]
     return b"".join(chunks) if fn(C.byref(tplan), d.ctypes.data_as(C.c_void_p), cb, None) else None
+
+
+def restart_interval(tplan, restart_rows=None, restart_mcus=None):
+    """mjw_restart_interval: the interval in MCUs of a plan from one given in MCU rows or in MCUs -> (Ri, None), or (None, reason) for both
+    given, a negative value or a result above 65535"""
+    L = lib()
+    L.mjw_restart_interval.argtypes = [C.POINTER(TranscodePlan), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_char_p)]
+    ri, why = C.c_int(), C.c_char_p()
+    rows, mcus = (min(max(_restart_mcus(v), -1), 1 << 30) for v in (restart_rows, restart_mcus))
+    if not L.mjw_restart_interval(C.byref(tplan), rows, mcus, C.byref(ri), C.byref(why)):
+        return None, (why.value.decode() if why.value else "refused")
+    return ri.value, None
+
+
+def restart_histogram(plan, du, restart_mcus):
+    """mjw_histogram_restart (a WritePlan) or mjw_thistogram_restart (a TranscodePlan) -> uint32 [4, 256], None when refused"""
+    L = lib()
+    t = isinstance(plan, TranscodePlan)
+    fn = L.mjw_thistogram_restart if t else L.mjw_histogram_restart
+    fn.argtypes = [C.POINTER(TranscodePlan if t else WritePlan), C.c_void_p, C.c_int, C.c_void_p]
+    d = np.ascontiguousarray(du, np.int16)
+    if d.size != plan.du_elems():
+        raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, plan.du_elems()))
+    freq = np.zeros((4, 256), np.uint32)
+    if not fn(C.byref(plan), d.ctypes.data_as(C.c_void_p), _restart_mcus(restart_mcus), freq.ctypes.data_as(C.c_void_p)):
+        return None
+    return freq
 
 
 def copy_markers(src, stream):
@@ -1401,16 +1454,28 @@ def units_requant(src, dst, du):
 
 
 def transcode_memory(data, optimize=False, copy_markers=False, orientation=None, trim=False, tables=None, coarsen_only=True, crop=None,
-                     grey=False):
+                     grey=False, restart_rows=None, restart_mcus=None):
     """mjh_transcode_memory, the lossless transcode on the host alone -> (bytes, None) or (None, reason).  With an orientation
     (1..8, or "exif" for the file's own tag) it is mjh_transcode_memory_oriented; trim chooses its edge mode.  With tables = (luma,
     chroma) it is mjh_transcode_memory_requant: the coefficients requantised after the orientation.  With crop = (x0, y0, w, h) in the
-    displayed frame and / or grey=True it is mjh_transcode_memory_window: grey -> orient -> crop -> requantise."""
+    displayed frame and / or grey=True it is mjh_transcode_memory_window: grey -> orient -> crop -> requantise.  With restart_rows or
+    restart_mcus (an interval in MCU rows or MCUs of the destination; both given, negative or above 65535 MCUs: refused with a reason) it
+    is mjh_transcode_memory_restart_by."""
     L = lib()
     data = bytes(data)
     out, n, why = C.c_void_p(), C.c_size_t(), C.c_char_p()
     flags = (MJW_OPTIMIZE_HUFFMAN if optimize else 0) | (MJW_COPY_MARKERS if copy_markers else 0)
-    if crop is not None or grey:
+    rows, mcus = (min(max(_restart_mcus(v), -1), 1 << 30) for v in (restart_rows, restart_mcus))
+    if rows or mcus:
+        luma, chroma = (None, None) if tables is None else _qtable_pair(tables)
+        win = None if crop is None else (C.c_int * 4)(*[int(v) for v in crop])
+        L.mjh_transcode_memory_restart_by.argtypes = [C.c_char_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_char_p,
+                                                      C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                      C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_char_p)]
+        o = 1 if orientation is None else 0 if orientation == "exif" else int(orientation)
+        ok = L.mjh_transcode_memory_restart_by(data, len(data), flags, o, int(bool(trim)), win, int(bool(grey)), luma, chroma,
+                                               int(bool(coarsen_only)), rows, mcus, C.byref(out), C.byref(n), None, None, C.byref(why))
+    elif crop is not None or grey:
         luma, chroma = (None, None) if tables is None else _qtable_pair(tables)
         win = None if crop is None else (C.c_int * 4)(*[int(v) for v in crop])
         L.mjh_transcode_memory_window.argtypes = [C.c_char_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_char_p,
@@ -1803,6 +1868,18 @@ class Encoder:
         L = lib()
         L.mij_enc_set_optimize.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _check(L.mij_enc_set_optimize(self._h, int(slot), int(bool(on))), "mij_enc_set_optimize")
+
+    def set_restart(self, slot, restart_mcus):
+        """mij_enc_set_restart: the slot's stream gets a restart interval of that many MCUs (0 or None: none); before upload."""
+        L = lib()
+        L.mij_enc_set_restart.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        _check(L.mij_enc_set_restart(self._h, int(slot), _restart_mcus(restart_mcus)), "mij_enc_set_restart")
+
+    def slot_restart(self, slot):
+        """mij_enc_slot_restart: the slot's restart interval in MCUs, 0 when it has none"""
+        L = lib()
+        L.mij_enc_slot_restart.argtypes = [C.c_void_p, C.c_int]
+        return _check(L.mij_enc_slot_restart(self._h, int(slot)), "mij_enc_slot_restart")
 
     def slot_optimized(self, slot):
         """mij_enc_slot_optimized, after fetch_streams: True when the slot's stream carries its own tables, False when optimisation

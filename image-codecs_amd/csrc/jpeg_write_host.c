@@ -502,8 +502,10 @@ void mjw_huff_tables(uint16_t code[4][256], uint8_t len[4][256])
 }
 
 /* headers (hdr_len bytes), the entropy-coded segment under the four tables, fill and EOI */
-static int emit_units_with(size_t nm, int ny, int ncomp, const int16_t *du, mjw_write_func *func, void *context, const enc_table *ydc, const enc_table *yac,
-									const enc_table *cdc, const enc_table *cac, const unsigned char *hdr, size_t hdr_len)
+/* ri > 0: a restart interval of ri MCUs (include/mij_host.h, RESTART INTERVALS): the fill of the scan's end after every ri MCUs that are not the
+ * scan's last, the marker RSTk behind it, the DC predictors back at 0 */
+static int emit_units_with(size_t nm, int ny, int ncomp, size_t ri, const int16_t *du, mjw_write_func *func, void *context, const enc_table *ydc,
+									const enc_table *yac, const enc_table *cdc, const enc_table *cac, const unsigned char *hdr, size_t hdr_len)
 {
 	jw_sink *s = (jw_sink *)calloc(1, sizeof(*s));
 	if (!s)
@@ -513,7 +515,8 @@ static int emit_units_with(size_t nm, int ny, int ncomp, const int16_t *du, mjw_
 	sink_bytes(s, hdr, (int)hdr_len); /* headers (codec/jpeg_write.c:245-268) */
 	{
 		int dcy = 0, dcu = 0, dcv = 0;
-		size_t m;
+		size_t m, left = ri;
+		unsigned rst = 0;
 		int k;
 		s->acc = 0;
 		s->nacc = 0;
@@ -524,6 +527,16 @@ static int emit_units_with(size_t nm, int ny, int ncomp, const int16_t *du, mjw_
 				dcu = emit_du(s, du, dcu, cdc, cac);
 				dcv = emit_du(s, du + 64, dcv, cdc, cac);
 				du += 128;
+			}
+			if (ri && --left == 0 && m + 1 < nm) { /* an interval ends as the scan does; what is left below a byte is dropped */
+				put_bits(s, 0x7F, 7);
+				put_bits_finish(s);
+				s->acc = 0;
+				s->nacc = 0;
+				sink_byte(s, 0xFF);
+				sink_byte(s, (unsigned char)(0xD0 + (rst++ & 7u)));
+				dcy = dcu = dcv = 0;
+				left = ri;
 			}
 		}
 		put_bits(s, 0x7F, 7); /* pad to a byte boundary with ones */
@@ -538,7 +551,7 @@ static int emit_units_with(size_t nm, int ny, int ncomp, const int16_t *du, mjw_
 static int emit_with(const mjw_plan *p, const int16_t *du, mjw_write_func *func, void *context, const enc_table *ydc, const enc_table *yac,
 							const enc_table *cdc, const enc_table *cac, const unsigned char *hdr, size_t hdr_len)
 {
-	return emit_units_with((size_t)p->mcu_x * (size_t)p->mcu_y, p->subsample ? 4 : 1, 3, du, func, context, ydc, yac, cdc, cac, hdr, hdr_len);
+	return emit_units_with((size_t)p->mcu_x * (size_t)p->mcu_y, p->subsample ? 4 : 1, 3, 0, du, func, context, ydc, yac, cdc, cac, hdr, hdr_len);
 }
 
 int mjw_emit(const mjw_plan *p, const int16_t *du, mjw_write_func *func, void *context)
@@ -578,10 +591,10 @@ static int count_du(const int16_t *du, int dc_pred, uint32_t *fdc, uint32_t *fac
 	return du[0];
 }
 
-static void histogram_units(size_t nm, int ny, int ncomp, const int16_t *du, uint32_t freq[4][256])
+static void histogram_units(size_t nm, int ny, int ncomp, size_t ri, const int16_t *du, uint32_t freq[4][256])
 {
 	int dcy = 0, dcu = 0, dcv = 0;
-	size_t m;
+	size_t m, left = ri;
 	memset(freq, 0, sizeof(uint32_t) * 4 * 256);
 	for (m = 0; m < nm; ++m) {
 		int k;
@@ -592,6 +605,10 @@ static void histogram_units(size_t nm, int ny, int ncomp, const int16_t *du, uin
 			dcv = count_du(du + 64, dcv, freq[1], freq[3]);
 			du += 128;
 		}
+		if (ri && --left == 0) { /* the next MCU starts an interval: its DC categories are those of differences against 0 */
+			dcy = dcu = dcv = 0;
+			left = ri;
+		}
 	}
 }
 
@@ -599,7 +616,7 @@ int mjw_histogram(const mjw_plan *p, const int16_t *du, uint32_t freq[4][256])
 {
 	if (!p || !du || !freq || mjw_plan_du_count(p) > (size_t)(UINT32_MAX / 64))
 		return 0;
-	histogram_units((size_t)p->mcu_x * (size_t)p->mcu_y, p->subsample ? 4 : 1, 3, du, freq);
+	histogram_units((size_t)p->mcu_x * (size_t)p->mcu_y, p->subsample ? 4 : 1, 3, 0, du, freq);
 	return 1;
 }
 
@@ -834,7 +851,7 @@ int mjw_temit(const mjw_tplan *t, const int16_t *du, mjw_write_func *func, void 
 	make_enc_table(&cdc, k_dc_chr_bits, k_dc_vals);
 	make_enc_table(&yac, k_ac_lum_bits, k_ac_lum_vals);
 	make_enc_table(&cac, k_ac_chr_bits, k_ac_chr_vals);
-	return emit_units_with((size_t)t->plan.mcu_x * (size_t)t->plan.mcu_y, tplan_ny(t), t->ncomp, du, func, context, &ydc, &yac, &cdc, &cac, hdr,
+	return emit_units_with((size_t)t->plan.mcu_x * (size_t)t->plan.mcu_y, tplan_ny(t), t->ncomp, 0, du, func, context, &ydc, &yac, &cdc, &cac, hdr,
 								  mjw_theader(t, hdr));
 }
 
@@ -849,7 +866,7 @@ int mjw_temit_optimized(const mjw_tplan *t, const int16_t *du, mjw_write_func *f
 		return 0;
 	if (mjw_tplan_du_count(t) > (size_t)(UINT32_MAX / 64))
 		return mjw_temit(t, du, func, context);
-	histogram_units((size_t)t->plan.mcu_x * (size_t)t->plan.mcu_y, tplan_ny(t), t->ncomp, du, freq);
+	histogram_units((size_t)t->plan.mcu_x * (size_t)t->plan.mcu_y, tplan_ny(t), t->ncomp, 0, du, freq);
 	for (k = 0; k < 4; ++k) {
 		memset(vals[k], 0, 256);
 		if (!mjw_optimal_table(freq[k], bits[k], vals[k], &n))
@@ -858,7 +875,7 @@ int mjw_temit_optimized(const mjw_tplan *t, const int16_t *du, mjw_write_func *f
 		memcpy(b17 + 1, bits[k], 16);
 		make_enc_table(&tb[k], b17, vals[k]);
 	}
-	return emit_units_with((size_t)t->plan.mcu_x * (size_t)t->plan.mcu_y, tplan_ny(t), t->ncomp, du, func, context, &tb[0], &tb[2], &tb[1], &tb[3], hdr,
+	return emit_units_with((size_t)t->plan.mcu_x * (size_t)t->plan.mcu_y, tplan_ny(t), t->ncomp, 0, du, func, context, &tb[0], &tb[2], &tb[1], &tb[3], hdr,
 								  mjw_theader_optimized(t, bits, vals, hdr));
 }
 
@@ -902,6 +919,187 @@ size_t mjw_temit_to_memory(const mjw_tplan *t, const int16_t *du, unsigned flags
 	m.len = 0;
 	m.overflow = 0;
 	if (!((flags & MJW_OPTIMIZE_HUFFMAN) ? mjw_temit_optimized : mjw_temit)(t, du, mem_sink_write, &m) || m.overflow)
+		return 0;
+	return m.len;
+}
+
+/* ---- restart intervals (include/mij_host.h, RESTART INTERVALS): the same emission with a DRI segment in front of SOS, the scan's fill and
+ * a marker at every interval end, and every quantity that follows the DC predictors taken against the restarted ones.  ri == 0 is the
+ * calls above, byte for byte. */
+
+int mjw_restart_interval(const mjw_tplan *t, int rows, int mcus, int *ri, const char **reason)
+{
+	const char *why = NULL;
+	long long v = 0;
+	if (!t || !ri || t->plan.mcu_x < 1 || t->plan.mcu_y < 1)
+		why = "bad argument";
+	else if (rows < 0 || mcus < 0)
+		why = "a restart interval cannot be negative";
+	else if (rows && mcus)
+		why = "a restart interval is given in MCU rows or in MCUs, not both";
+	else if ((v = rows ? (long long)rows * t->plan.mcu_x : mcus) > 65535)
+		why = "a restart interval above 65535 MCUs does not fit the DRI segment";
+	if (why) {
+		if (reason)
+			*reason = why;
+		return 0;
+	}
+	*ri = (int)v;
+	return 1;
+}
+
+/* the DRI segment pushed in between DHT and SOS of a finished header whose SOS segment takes sos_len bytes */
+static size_t header_add_dri(unsigned char *hdr, size_t len, size_t sos_len, int ri)
+{
+	unsigned char *sos = hdr + len - sos_len;
+	if (ri <= 0)
+		return len;
+	memmove(sos + 6, sos, sos_len);
+	sos[0] = 0xFF, sos[1] = 0xDD, sos[2] = 0, sos[3] = 4;
+	sos[4] = (unsigned char)(ri >> 8), sos[5] = (unsigned char)(ri & 0xff);
+	return len + 6;
+}
+static int ri_ok(int ri) { return ri >= 0 && ri <= 65535; }
+static size_t tplan_sos_len(const mjw_tplan *t) { return t->ncomp == 1 ? 10 : 14; }
+
+size_t mjw_header_restart(const mjw_plan *p, int ri, unsigned char *out) { return ri_ok(ri) ? header_add_dri(out, mjw_header(p, out), 14, ri) : 0; }
+size_t mjw_header_optimized_restart(const mjw_plan *p, const uint8_t bits[4][16], const uint8_t vals[4][256], int ri, unsigned char *out)
+{
+	return ri_ok(ri) ? header_add_dri(out, mjw_header_optimized(p, bits, vals, out), 14, ri) : 0;
+}
+size_t mjw_theader_restart(const mjw_tplan *t, int ri, unsigned char *out)
+{
+	return ri_ok(ri) ? header_add_dri(out, mjw_theader(t, out), tplan_sos_len(t), ri) : 0;
+}
+size_t mjw_theader_optimized_restart(const mjw_tplan *t, const uint8_t bits[4][16], const uint8_t vals[4][256], int ri, unsigned char *out)
+{
+	return ri_ok(ri) ? header_add_dri(out, mjw_theader_optimized(t, bits, vals, out), tplan_sos_len(t), ri) : 0;
+}
+
+int mjw_histogram_restart(const mjw_plan *p, const int16_t *du, int ri, uint32_t freq[4][256])
+{
+	if (!p || !du || !freq || !ri_ok(ri) || mjw_plan_du_count(p) > (size_t)(UINT32_MAX / 64))
+		return 0;
+	histogram_units((size_t)p->mcu_x * (size_t)p->mcu_y, p->subsample ? 4 : 1, 3, (size_t)ri, du, freq);
+	return 1;
+}
+int mjw_thistogram_restart(const mjw_tplan *t, const int16_t *du, int ri, uint32_t freq[4][256])
+{
+	if (!t || !du || !freq || !ri_ok(ri) || mjw_tplan_du_count(t) > (size_t)(UINT32_MAX / 64))
+		return 0;
+	histogram_units((size_t)t->plan.mcu_x * (size_t)t->plan.mcu_y, tplan_ny(t), t->ncomp, (size_t)ri, du, freq);
+	return 1;
+}
+
+/* mjw_tunits_codable's ranges over nm MCUs of ny luma units and, with three components, Cb and Cr; the predictors restart every ri MCUs */
+static int units_codable(size_t nm, int ny, int ncomp, size_t ri, const int16_t *du, const char **reason)
+{
+	const int dpm = ny + (ncomp == 3 ? 2 : 0);
+	int pred[3] = {0, 0, 0}, k, p;
+	size_t m, left = ri;
+	for (m = 0; m < nm; ++m) {
+		for (p = 0; p < dpm; ++p, du += 64) {
+			const int c = p < ny ? 0 : p - ny + 1, diff = du[0] - pred[c];
+			pred[c] = du[0];
+			if (diff < -2047 || diff > 2047) {
+				if (reason)
+					*reason = "a DC difference outside -2047..2047";
+				return 0;
+			}
+			for (k = 1; k < 64; ++k)
+				if (du[k] < -1023 || du[k] > 1023) {
+					if (reason)
+						*reason = "an AC coefficient outside -1023..1023";
+					return 0;
+				}
+		}
+		if (ri && --left == 0) {
+			pred[0] = pred[1] = pred[2] = 0;
+			left = ri;
+		}
+	}
+	return 1;
+}
+int mjw_units_codable_restart(const mjw_plan *p, const int16_t *du, int ri, const char **reason)
+{
+	if (!p || !du || !ri_ok(ri)) {
+		if (reason)
+			*reason = "bad argument";
+		return 0;
+	}
+	return units_codable((size_t)p->mcu_x * (size_t)p->mcu_y, p->subsample ? 4 : 1, 3, (size_t)ri, du, reason);
+}
+int mjw_tunits_codable_restart(const mjw_tplan *t, const int16_t *du, int ri, const char **reason)
+{
+	if (!t || !du || !ri_ok(ri)) {
+		if (reason)
+			*reason = "bad argument";
+		return 0;
+	}
+	return units_codable((size_t)t->plan.mcu_x * (size_t)t->plan.mcu_y, tplan_ny(t), t->ncomp, (size_t)ri, du, reason);
+}
+
+/* the emission of a plan (t == NULL) or a transcode plan with an interval: plain tables, or the optimised ones of the restarted histogram (the
+ * plain ones where a table cannot be built, as mjw_emit_optimized falls back) */
+static int emit_restart(const mjw_plan *p, const mjw_tplan *t, const int16_t *du, unsigned flags, int ri, mjw_write_func *func, void *context)
+{
+	const size_t nm = (size_t)p->mcu_x * (size_t)p->mcu_y, nu = mjw_plan_du_count(p);
+	const int ny = t ? tplan_ny(t) : (p->subsample ? 4 : 1), ncomp = t ? t->ncomp : 3;
+	uint32_t freq[4][256];
+	uint8_t bits[4][16], vals[4][256];
+	unsigned char b17[17], hdr[MJW_HEADER_RESTART_BYTES];
+	enc_table tb[4];
+	size_t hlen;
+	int k, n, opt = (flags & MJW_OPTIMIZE_HUFFMAN) && nu <= (size_t)(UINT32_MAX / 64);
+	if (opt) {
+		histogram_units(nm, ny, ncomp, (size_t)ri, du, freq);
+		for (k = 0; k < 4 && opt; ++k) {
+			memset(vals[k], 0, 256);
+			if (!mjw_optimal_table(freq[k], bits[k], vals[k], &n)) {
+				opt = 0;
+				break;
+			}
+			b17[0] = 0;
+			memcpy(b17 + 1, bits[k], 16);
+			make_enc_table(&tb[k], b17, vals[k]);
+		}
+	}
+	if (!opt) {
+		make_enc_table(&tb[0], k_dc_lum_bits, k_dc_vals);
+		make_enc_table(&tb[1], k_dc_chr_bits, k_dc_vals);
+		make_enc_table(&tb[2], k_ac_lum_bits, k_ac_lum_vals);
+		make_enc_table(&tb[3], k_ac_chr_bits, k_ac_chr_vals);
+	}
+	if (t)
+		hlen = opt ? mjw_theader_optimized_restart(t, bits, vals, ri, hdr) : mjw_theader_restart(t, ri, hdr);
+	else
+		hlen = opt ? mjw_header_optimized_restart(p, bits, vals, ri, hdr) : mjw_header_restart(p, ri, hdr);
+	return emit_units_with(nm, ny, ncomp, (size_t)ri, du, func, context, &tb[0], &tb[2], &tb[1], &tb[3], hdr, hlen);
+}
+
+int mjw_emit_restart(const mjw_plan *p, const int16_t *du, unsigned flags, int ri, mjw_write_func *func, void *context)
+{
+	if (!p || !du || !func || !ri_ok(ri) || (flags & ~MJW_OPTIMIZE_HUFFMAN))
+		return 0;
+	return emit_restart(p, NULL, du, flags, ri, func, context);
+}
+int mjw_temit_restart(const mjw_tplan *t, const int16_t *du, unsigned flags, int ri, mjw_write_func *func, void *context)
+{
+	if (!t || !du || !func || !ri_ok(ri) || (flags & ~MJW_OPTIMIZE_HUFFMAN) || !mjw_tunits_codable_restart(t, du, ri, NULL))
+		return 0;
+	return emit_restart(&t->plan, t, du, flags, ri, func, context);
+}
+size_t mjw_emit_restart_to_memory(const mjw_plan *p, const int16_t *du, unsigned flags, int ri, unsigned char *out, size_t cap)
+{
+	mem_sink m = {out, cap, 0, 0};
+	if (!out || !mjw_emit_restart(p, du, flags, ri, mem_sink_write, &m) || m.overflow)
+		return 0;
+	return m.len;
+}
+size_t mjw_temit_restart_to_memory(const mjw_tplan *t, const int16_t *du, unsigned flags, int ri, unsigned char *out, size_t cap)
+{
+	mem_sink m = {out, cap, 0, 0};
+	if (!out || !mjw_temit_restart(t, du, flags, ri, mem_sink_write, &m) || m.overflow)
 		return 0;
 	return m.len;
 }

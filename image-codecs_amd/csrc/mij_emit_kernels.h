@@ -20,6 +20,14 @@
  * Bits left below a byte after the fill are dropped (they are the last tile's tail).  Nothing but the streams of fitting slots is
  * written to the arena, and the data units are only read.
  *
+ * Restart intervals (mij_enc_set_restart; the contract is include/mij_host.h, RESTART INTERVALS): the same launches.  The tile list of a slot
+ * with an interval is cut so that no tile straddles an interval end (EmitTile.pad: unit count, "ends interval k"); a tile is then either
+ * MIJ_EMIT_TILE units long or ends an interval with the 7 fill bits, so it never holds less than a byte.  emit_load predicts an interval's
+ * first units from 0 and the fill's owner is every interval's last unit (both read from the tile's flags, no division by the interval); k_emit_scan's offsets restart at each interval (a segmented scan),
+ * which makes an interval's first tile start at a byte boundary and its last tile's tail the dropped remainder; k_emit_stuff adds the two
+ * marker bytes behind an interval's last tile and k_emit_write stores them there.  k_emit_build puts the DRI segment in front of SOS.
+ * A slot without an interval has one tile per MIJ_EMIT_TILE units and no flag, and every kernel computes for it what it computed before.
+ *
  * Optimised Huffman tables (mij_enc_set_optimize; the contract is mjw_emit_optimized's, include/mij_host.h): two more launches in
  * front of the six, over the optimised slots only, and none when there is no such slot:
  *   k_emit_hist    per tile of an optimised slot: the symbols its lanes own, counted in an LDS histogram and added to the slot's
@@ -33,7 +41,7 @@
 #pragma once
 
 #define MIJ_EMIT_TILE 128
-#define MIJ_EMIT_HDR 607 /* MJW_HEADER_BYTES */
+#define MIJ_EMIT_HDR 613 /* MJW_HEADER_RESTART_BYTES: the stride of the header list, and the longest header */
 /* most bits a unit within the writer's ranges takes: chroma DC 11 + 11, 63 AC symbols of 16 + 10, the 7 fill bits */
 #define MIJ_EMIT_MAX_DU_BITS (22 + 63 * 26 + 7)
 #define MIJ_EMIT_LDS_WORDS ((MIJ_EMIT_TILE * MIJ_EMIT_MAX_DU_BITS + 7 + 31) / 32 + 1)
@@ -49,12 +57,26 @@ struct EmitSlot {
 	uint32_t first_tile, n_tiles;
 	uint32_t hdr, tab; /* header of the slot: hdrs + hdr * MIJ_EMIT_HDR; tab > 0: optimised, its tables are entry tab, its counts tab - 1 */
 	uint32_t hlen, ny; /* the header's length: what the upload wrote, or what k_emit_build wrote; luma units per MCU (1, 2 or 4): unit p of an MCU is luma when p < ny */
+	uint32_t ri, pad;  /* the restart interval in MCUs (mij_enc_set_restart), 0: none */
 };
 
 struct EmitTile {
 	uint32_t slot, first; /* the tile's first unit in its slot */
-	uint32_t tab, pad;    /* the tables the tile kernels use: entry 0 (plain), or what k_emit_build wrote */
+	uint32_t tab, pad;    /* the tables the tile kernels use: entry 0 (plain), or what k_emit_build wrote; pad: emit_tile_pad */
 };
+/* EmitTile.pad: the tile's unit count (1..MIJ_EMIT_TILE; no tile straddles an interval end) in bits 0-8; MIJ_TILE_ENDS when the tile's last
+ * unit ends a restart interval that a marker follows (not the slot's last), with that interval's number mod 8 in bits 10-12;
+ * MIJ_TILE_STARTS when the tile's first MCU is the first of an interval or of the slot (its units predict from 0); MIJ_TILE_FILLS when its last
+ * unit is the last of an interval or of the slot (the 7 fill bits follow it).  A slot without an interval has STARTS on its first tile, FILLS on
+ * its last and never ENDS.  The kernels take what depends on the interval from these flags: no division by it anywhere. */
+#define MIJ_TILE_ENDS 0x200u
+#define MIJ_TILE_STARTS 0x2000u
+#define MIJ_TILE_FILLS 0x4000u
+__host__ __device__ __forceinline__ uint32_t emit_tile_pad(uint32_t n, bool starts, bool fills, bool ends, uint32_t k)
+{
+	return n | (starts ? MIJ_TILE_STARTS : 0u) | (fills ? MIJ_TILE_FILLS : 0u) | (ends ? MIJ_TILE_ENDS | (k & 7u) << 10 : 0u);
+}
+__device__ __forceinline__ uint32_t emit_tile_units(const EmitTile &tl) { return tl.pad & 0x1FFu; }
 
 struct EmitResult {
 	uint64_t off, len; /* off = ~0 for a slot that does not fit; entry n: {bytes used, slots that fit} */
@@ -78,14 +100,16 @@ struct LaneBits {
 struct UnitIn {
 	int v, pred; /* this lane's coefficient; the DC predictor (lane 0) */
 };
-/* the loads of unit u (issued a unit ahead of its use: emit_units) */
-__device__ __forceinline__ UnitIn emit_load(const EmitSlot &s, const int16_t *__restrict__ du, uint32_t u, int lane)
+/* the loads of unit u of tile tl (issued a unit ahead of its use: emit_units) */
+__device__ __forceinline__ UnitIn emit_load(const EmitSlot &s, const EmitTile &tl, const int16_t *__restrict__ du, uint32_t u, int lane)
 {
 	const uint32_t m = u / s.dpm, p = u - m * s.dpm;
 	/* the unit whose DC predicts this one's, the previous unit of the component in MCU order: u - 1 inside an MCU's luma run, the last luma unit
 	 * of the MCU before for its first, the same unit of the MCU before for chroma */
 	const long back = p < s.ny ? (long)(s.dpm - s.ny + 1u) : (long)s.dpm;
-	const long prev = p > 0 && p < s.ny ? (long)u - 1 : (m > 0 ? (long)u - back : -1);
+	/* an interval's first MCU (the slot's first without an interval) has no MCU before it: the first MCU of a tile that starts one */
+	const bool first_mcu = (tl.pad & MIJ_TILE_STARTS) && u - tl.first < s.dpm;
+	const long prev = p > 0 && p < s.ny ? (long)u - 1 : (!first_mcu ? (long)u - back : -1);
 	UnitIn in;
 	in.v = du[(size_t)u * 64 + lane];
 	in.pred = lane == 0 && prev >= 0 ? (int)du[(size_t)prev * 64] : 0;
@@ -155,43 +179,43 @@ struct LaneCoder {
 		L.extra_len = T->len[acT][0];
 	}
 };
-__device__ __forceinline__ void emit_lane(const EmitTables *__restrict__ T, const EmitSlot &s, UnitIn in, uint32_t u, int lane, LaneBits &L)
+__device__ __forceinline__ void emit_lane(const EmitTables *__restrict__ T, const EmitSlot &s, const EmitTile &tl, UnitIn in, uint32_t u, int lane, LaneBits &L)
 {
 	LaneCoder c = {T, L, 0, 0};
 	emit_owner(s, in, u, lane, c);
-	if (lane == 63 && u + 1 == s.n_du) { /* the slot's last unit: fill to a byte boundary with ones */
+	/* the slot's last unit, and the last unit of a restart interval: fill to a byte boundary with ones */
+	if (lane == 63 && (tl.pad & MIJ_TILE_FILLS) && u + 1 == tl.first + emit_tile_units(tl)) {
 		L.extra = (L.extra << 7) | 0x7Fu;
 		L.extra_len += 7;
 	}
 }
 
-/* f(j, u, UnitIn) for the units j = wave, wave + 4, ... < n of a tile (first unit `first`, u = first + j), the next unit's loads in
- * flight */
+/* f(j, u, UnitIn) for the units j = wave, wave + 4, ... < n of tile tl (u = tl.first + j), the next unit's loads in flight */
 template <typename F>
-__device__ __forceinline__ void emit_unit_loop(const EmitSlot &s, const int16_t *__restrict__ du, uint32_t first, uint32_t n, F f)
+__device__ __forceinline__ void emit_unit_loop(const EmitSlot &s, const EmitTile &tl, const int16_t *__restrict__ du, F f)
 {
 	const int lane = threadIdx.x & 63;
+	const uint32_t first = tl.first, n = emit_tile_units(tl);
 	uint32_t j = threadIdx.x >> 6;
 	if (j >= n)
 		return;
-	UnitIn in = emit_load(s, du, first + j, lane);
+	UnitIn in = emit_load(s, tl, du, first + j, lane);
 	for (; j < n; j += 4) {
 		UnitIn next = in;
 		if (j + 4 < n)
-			next = emit_load(s, du, first + j + 4, lane);
+			next = emit_load(s, tl, du, first + j + 4, lane);
 		f(j, first + j, in);
 		in = next;
 	}
 }
 /* f(j, LaneBits) for those units, their symbols looked up in T */
 template <typename F>
-__device__ __forceinline__ void emit_units(const EmitTables *__restrict__ T, const EmitSlot &s, const int16_t *__restrict__ du, uint32_t first, uint32_t n,
-														 F f)
+__device__ __forceinline__ void emit_units(const EmitTables *__restrict__ T, const EmitSlot &s, const EmitTile &tl, const int16_t *__restrict__ du, F f)
 {
 	const int lane = threadIdx.x & 63;
-	emit_unit_loop(s, du, first, n, [&](uint32_t j, uint32_t u, UnitIn in) {
+	emit_unit_loop(s, tl, du, [&](uint32_t j, uint32_t u, UnitIn in) {
 		LaneBits L;
-		emit_lane(T, s, in, u, lane, L);
+		emit_lane(T, s, tl, in, u, lane, L);
 		f(j, L);
 	});
 }
@@ -240,10 +264,10 @@ __device__ void emit_pack_tile(const EmitTables *__restrict__ T, const EmitSlot 
 										 uint32_t nwords, uint32_t *buf, uint32_t *uoff)
 {
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const uint32_t n = min((uint32_t)MIJ_EMIT_TILE, s.n_du - tl.first);
+	const uint32_t n = emit_tile_units(tl);
 	for (uint32_t i = threadIdx.x; i < nwords; i += blockDim.x)
 		buf[i] = 0;
-	emit_units(T, s, du, tl.first, n, [&](uint32_t j, const LaneBits &L) {
+	emit_units(T, s, tl, du, [&](uint32_t j, const LaneBits &L) {
 		const uint32_t t = wave_sum((uint32_t)L.total());
 		if (lane == 0)
 			uoff[j] = t;
@@ -258,7 +282,7 @@ __device__ void emit_pack_tile(const EmitTables *__restrict__ T, const EmitSlot 
 			uoff[2 * lane + 1] = incl - b;
 	}
 	__syncthreads();
-	emit_units(T, s, du, tl.first, n, [&](uint32_t j, const LaneBits &L) {
+	emit_units(T, s, tl, du, [&](uint32_t j, const LaneBits &L) {
 		const uint32_t len = (uint32_t)L.total();
 		uint32_t pos = h + uoff[j] + wave_incl_scan(len, lane) - len;
 		for (int z = 0; z < L.zrl; ++z, pos += (uint32_t)L.zrl_len)
@@ -278,10 +302,9 @@ __global__ __launch_bounds__(256) void k_emit_len(const EmitSlot *__restrict__ s
 	const EmitSlot s = slots[tl.slot];
 	const int16_t *du = reinterpret_cast<const int16_t *>(du_base + s.du_off);
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const uint32_t n = min((uint32_t)MIJ_EMIT_TILE, s.n_du - tl.first);
 	emit_tables_to_lds(T + tl.tab, &tab);
 	uint32_t acc = 0;
-	emit_units(&tab, s, du, tl.first, n, [&](uint32_t, const LaneBits &L) { acc += wave_sum((uint32_t)L.total()); });
+	emit_units(&tab, s, tl, du, [&](uint32_t, const LaneBits &L) { acc += wave_sum((uint32_t)L.total()); });
 	if (lane == 0)
 		part[wave] = acc;
 	__syncthreads();
@@ -289,22 +312,42 @@ __global__ __launch_bounds__(256) void k_emit_len(const EmitSlot *__restrict__ s
 		t_bits[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
 }
 
-/* one wave per slot: each tile's bit offset in its slot */
-__global__ __launch_bounds__(256) void k_emit_scan(const EmitSlot *__restrict__ slots, uint32_t n_slots, const uint32_t *__restrict__ t_bits,
-																	uint64_t *__restrict__ t_boff)
+__device__ __forceinline__ uint64_t wave_incl_max64(uint64_t v, int lane)
+{
+	for (int o = 1; o < 64; o <<= 1) {
+		const uint64_t t = __shfl_up(v, o, 64);
+		if (lane >= o)
+			v = t > v ? t : v;
+	}
+	return v;
+}
+
+/* one wave per slot: each tile's bit offset in its restart interval -- in its slot, for a slot without one.  A segmented scan: the bits behind an
+ * interval end start at a byte boundary again, so a tile's offset is its offset in the slot less that of the tile its interval began with;
+ * offsets only grow, so that one is the largest among the interval starts up to the tile (a running maximum, carried across the chunks in
+ * `seg`).  Every lane runs every step. */
+__global__ __launch_bounds__(256) void k_emit_scan(const EmitSlot *__restrict__ slots, const EmitTile *__restrict__ tiles, uint32_t n_slots,
+																	const uint32_t *__restrict__ t_bits, uint64_t *__restrict__ t_boff)
 {
 	const int lane = threadIdx.x & 63;
 	const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
 	if (i >= n_slots)
 		return;
 	const EmitSlot s = slots[i];
-	uint64_t base = 0;
+	uint64_t base = 0, seg = 0;
 	for (uint32_t t0 = 0; t0 < s.n_tiles; t0 += 64) {
 		const uint32_t t = t0 + (uint32_t)lane;
 		const uint32_t v = t < s.n_tiles ? t_bits[s.first_tile + t] : 0u;
 		const uint32_t incl = wave_incl_scan(v, lane);
+		const uint64_t excl = base + incl - v;
+		uint64_t from = 0;
+		if (s.ri) { /* the same in every lane of the wave: a slot without an interval skips the tile flags and the second scan */
+			const bool starts = t > 0 && t < s.n_tiles && (tiles[s.first_tile + t - 1].pad & MIJ_TILE_ENDS) != 0;
+			from = wave_incl_max64(starts ? excl : seg, lane);
+		}
 		if (t < s.n_tiles)
-			t_boff[s.first_tile + t] = base + incl - v;
+			t_boff[s.first_tile + t] = excl - from;
+		seg = __shfl(from, 63, 64);
 		base += __shfl(incl, 63, 64);
 	}
 }
@@ -352,7 +395,8 @@ __global__ __launch_bounds__(256) void k_emit_count(const EmitSlot *__restrict__
 }
 
 /* one wave per slot: each tile's offset in the stuffed entropy-coded segment, and the segment's size (~0: refused) */
-__global__ __launch_bounds__(256) void k_emit_stuff(const EmitSlot *__restrict__ slots, uint32_t n_slots, const uint32_t *__restrict__ t_bits,
+__global__ __launch_bounds__(256) void k_emit_stuff(const EmitSlot *__restrict__ slots, const EmitTile *__restrict__ tiles, uint32_t n_slots,
+																	 const uint32_t *__restrict__ t_bits,
 																	 const uint64_t *__restrict__ t_boff, const uint32_t *__restrict__ t_ff, const uint32_t *__restrict__ t_frag,
 																	 uint64_t *__restrict__ t_out, uint64_t *__restrict__ s_ent)
 {
@@ -377,6 +421,10 @@ __global__ __launch_bounds__(256) void k_emit_stuff(const EmitSlot *__restrict__
 					const uint32_t byte = ((t_frag[g - 1] >> 8) << (8 - h)) | (t_frag[g] & 0xFFu);
 					v += byte == 0xFFu;
 				}
+				/* the two marker bytes behind an interval end are added here, in byte space: they never pass through the stuffing.  The interval's
+				 * filled last byte is an ordinary whole byte of its tile and was counted as one (t_ff, or the shared byte above) */
+				if (s.ri && (tiles[g].pad & MIJ_TILE_ENDS))
+					v += 2u;
 			}
 		}
 		const uint32_t incl = wave_incl_scan(v, lane);
@@ -459,7 +507,7 @@ __global__ __launch_bounds__(256) void k_emit_write(const EmitSlot *__restrict__
 	if (tl.first == 0)
 		for (uint32_t i = threadIdx.x; i < s.hlen; i += blockDim.x)
 			out[i] = hdrs[(size_t)s.hdr * MIJ_EMIT_HDR + i];
-	if (tl.first + MIJ_EMIT_TILE >= s.n_du && threadIdx.x == 0) {
+	if (tl.first + emit_tile_units(tl) >= s.n_du && threadIdx.x == 0) {
 		out[r.len - 2] = 0xFF;
 		out[r.len - 1] = 0xD9;
 	}
@@ -492,6 +540,11 @@ __global__ __launch_bounds__(256) void k_emit_write(const EmitSlot *__restrict__
 		if (b == 0xFFu)
 			*o++ = 0;
 	}
+	if ((tl.pad & MIJ_TILE_ENDS) && threadIdx.x == 0) { /* the interval's marker, unstuffed, behind the tile's stuffed bytes */
+		uint8_t *m = out + s.hlen + t_out[blockIdx.x] + part[0] + part[1] + part[2] + part[3];
+		m[0] = 0xFF;
+		m[1] = (uint8_t)(0xD0u + ((tl.pad >> 10) & 7u));
+	}
 }
 
 /* ---- optimised Huffman tables */
@@ -523,11 +576,10 @@ __global__ __launch_bounds__(256) void k_emit_hist(const EmitSlot *__restrict__ 
 	const EmitSlot s = slots[tl.slot];
 	const int16_t *du = reinterpret_cast<const int16_t *>(du_base + s.du_off);
 	const int lane = threadIdx.x & 63;
-	const uint32_t n = min((uint32_t)MIJ_EMIT_TILE, s.n_du - tl.first);
 	for (uint32_t i = threadIdx.x; i < 4 * 256; i += blockDim.x)
 		hist[i] = 0;
 	__syncthreads();
-	emit_unit_loop(s, du, tl.first, n, [&](uint32_t, uint32_t u, UnitIn in) {
+	emit_unit_loop(s, tl, du, [&](uint32_t, uint32_t u, UnitIn in) {
 		LaneCounter c = {hist, nullptr, nullptr};
 		emit_owner(s, in, u, lane, c);
 	});
@@ -666,7 +718,9 @@ __global__ __launch_bounds__(256) void k_emit_build(EmitSlot *__restrict__ slots
 	/* a slot without chroma (dpm == ny) carries the two luma tables only, in the shorter header */
 	const bool grey = slots[slot].dpm == slots[slot].ny;
 	const uint32_t dht_at = grey ? MIJ_EMIT_DHT_AT1 : MIJ_EMIT_DHT_AT, sos_len = grey ? 10u : 14u;
-	const uint32_t hlen = grey ? dht_at + 2u * 17u + nvals[0] + nvals[2] + sos_len : dht_at + 4u * 17u + nvals[0] + nvals[1] + nvals[2] + nvals[3] + sos_len;
+	/* behind the DHT segment: the DRI segment of a slot with a restart interval, then SOS */
+	const uint32_t ri = slots[slot].ri, tail = sos_len + (ri ? 6u : 0u);
+	const uint32_t hlen = grey ? dht_at + 2u * 17u + nvals[0] + nvals[2] + tail : dht_at + 4u * 17u + nvals[0] + nvals[1] + nvals[2] + nvals[3] + tail;
 	const bool ok = !fail && hlen <= MIJ_EMIT_HDR && nvals[t] == nv;
 	const bool all_ok = __syncthreads_and(ok) != 0;
 	const uint32_t tile0 = slots[slot].first_tile, ntile = slots[slot].n_tiles;
@@ -699,9 +753,13 @@ __global__ __launch_bounds__(256) void k_emit_build(EmitSlot *__restrict__ slots
 		}
 		if (t == 3 && (uint32_t)lane < sos_len)
 			h[hlen - sos_len + lane] = grey ? k_emit_sos1[lane] : k_emit_sos[lane];
+		if (t == 2 && ri && lane < 6) {
+			const uint32_t dri = 0xFFu | 0xDDu << 8 | 4u << 24; /* FF DD 00 04 */
+			h[hlen - tail + lane] = (uint8_t)(lane < 4 ? dri >> (8 * lane) : (lane == 4 ? ri >> 8 : ri));
+		}
 		if (threadIdx.x == 0) {
-			h[dht_at - 2] = (uint8_t)((hlen - sos_len - (dht_at - 2)) >> 8);
-			h[dht_at - 1] = (uint8_t)((hlen - sos_len - (dht_at - 2)) & 0xFFu);
+			h[dht_at - 2] = (uint8_t)((hlen - tail - (dht_at - 2)) >> 8);
+			h[dht_at - 1] = (uint8_t)((hlen - tail - (dht_at - 2)) & 0xFFu);
 			slots[slot].hlen = hlen;
 			opt_ok[k] = 1;
 		}

@@ -3178,7 +3178,7 @@ extern "C" int mij_batch_entropy_rounds(const mij_batch *b) { return b && b->es 
 #include "mij_host.h"
 #include "mij_emit_kernels.h"
 #include "mij_transcode_kernels.h"
-static_assert(MIJ_EMIT_HDR == MJW_HEADER_BYTES, "header size");
+static_assert(MIJ_EMIT_HDR == MJW_HEADER_RESTART_BYTES, "header size");
 
 /* where a slot's input comes from: pinned staging, a device tensor, given units, a decode batch's coefficient planes */
 enum { ENC_HOST = 0, ENC_DEVICE = 1, ENC_UNITS = 2, ENC_COEF = 3 };
@@ -3192,6 +3192,7 @@ struct EncSlot {
 	int clone_of, flip;
 	int kind;                   /* ENC_*; a clone copies its root's pixels whatever the root's kind */
 	bool optimize;              /* mij_enc_set_optimize */
+	int restart;                /* mij_enc_set_restart: the restart interval in MCUs, 0: none */
 	mij_in_tensor in;           /* ENC_DEVICE */
 	mij_in_convert cv;          /* ENC_DEVICE with float elements (mij_enc_add_device_float); cv.dtype is MIJ_DT_U8 for every other slot */
 	std::vector<int16_t> units; /* ENC_UNITS */
@@ -3531,6 +3532,7 @@ static int enc_add_common(mij_encoder *e, const mjw_plan &plan, const void *pixe
 	s.clone_of = clone_of;
 	s.kind = kind;
 	s.optimize = false;
+	s.restart = 0;
 	memset(&s.in, 0, sizeof(s.in));
 	memset(&s.cv, 0, sizeof(s.cv));
 	s.cv.dtype = MIJ_DT_U8;
@@ -3663,8 +3665,10 @@ extern "C" int mij_enc_add_clone(mij_encoder *e, int src_slot)
 		return set_err(MIJ_E_ARG, "slot %d holds given data units or coefficient planes, which have no pixels to clone", src_slot);
 	const mjw_plan plan = e->slots[(size_t)root].plan;
 	const int slot = enc_add_common(e, plan, nullptr, e->slots[(size_t)root].flip, root);
-	if (slot >= 0)
+	if (slot >= 0) {
 		e->slots[(size_t)slot].optimize = e->slots[(size_t)src_slot].optimize;
+		e->slots[(size_t)slot].restart = e->slots[(size_t)src_slot].restart;
+	}
 	return slot;
 }
 
@@ -3678,6 +3682,30 @@ extern "C" int mij_enc_set_optimize(mij_encoder *e, int slot, int on)
 		return set_err(MIJ_E_ARG, "slot %d: the symbol counts of %zu data units do not fit 32 bits", slot, mjw_plan_du_count(&e->slots[(size_t)slot].plan));
 	e->slots[(size_t)slot].optimize = on != 0;
 	return MIJ_OK;
+}
+
+extern "C" int mij_enc_set_restart(mij_encoder *e, int slot, int restart_mcus)
+{
+	if (!e || slot < 0 || slot >= (int)e->slots.size())
+		return set_err(MIJ_E_ARG, "bad slot");
+	if (e->uploaded)
+		return set_err(MIJ_E_STATE, "mij_enc_set_restart after mij_enc_upload");
+	if (restart_mcus < 0 || restart_mcus > 65535)
+		return set_err(MIJ_E_ARG, "slot %d: a restart interval of %d MCUs is outside 0..65535", slot, restart_mcus);
+	EncSlot &s = e->slots[(size_t)slot];
+	/* given units were judged unbroken when they were added: with an interval the DC differences are other ones */
+	const char *why = nullptr;
+	if (s.kind == ENC_UNITS && restart_mcus && !mjw_units_codable_restart(&s.plan, s.units.data(), restart_mcus, &why))
+		return set_err(MIJ_E_ARG, "slot %d at a restart interval of %d MCUs: %s", slot, restart_mcus, why ? why : "not codable");
+	s.restart = restart_mcus;
+	return MIJ_OK;
+}
+
+extern "C" int mij_enc_slot_restart(const mij_encoder *e, int slot)
+{
+	if (!e || slot < 0 || slot >= (int)e->slots.size())
+		return set_err(MIJ_E_ARG, "bad slot");
+	return e->slots[(size_t)slot].restart;
 }
 
 extern "C" int mij_enc_slot_optimized(const mij_encoder *e, int slot)
@@ -3808,7 +3836,35 @@ static int enc_gather_float(mij_encoder *e)
 
 /* A slot has a header of its own unless it is a plain clone of a plain root, which shares the root's: k_emit_build writes an optimised
  * slot's DHT segment into its header. */
-static bool enc_own_header(const mij_encoder *e, const EncSlot &s) { return s.clone_of < 0 || s.optimize || e->slots[(size_t)s.clone_of].optimize; }
+static bool enc_own_header(const mij_encoder *e, const EncSlot &s)
+{
+	return s.clone_of < 0 || s.optimize || e->slots[(size_t)s.clone_of].optimize || s.restart != e->slots[(size_t)s.clone_of].restart;
+}
+
+/* The tiles of a slot's nu units: MIJ_EMIT_TILE units each, cut at every end of a restart interval of ri MCUs (dpm units each) so that no tile
+ * straddles one.  f(first unit, EmitTile.pad) per tile, in order; returns their number. */
+template <typename F>
+static size_t enc_slot_tiles(size_t nu, uint32_t dpm, uint32_t ri, F f)
+{
+	const size_t iu = ri ? (size_t)ri * dpm : nu;
+	size_t count = 0;
+	uint32_t k = 0;
+	for (size_t start = 0; start < nu; start += iu, ++k) {
+		const size_t stop = std::min(nu, start + iu);
+		for (size_t u = start; u < stop; u += MIJ_EMIT_TILE, ++count) {
+			const size_t n = std::min((size_t)MIJ_EMIT_TILE, stop - u);
+			f((uint32_t)u, emit_tile_pad((uint32_t)n, u == start, u + n == stop, ri && u + n == stop && stop < nu, k));
+		}
+	}
+	return count;
+}
+static size_t enc_slot_tile_count(const EncSlot &s)
+{
+	const size_t nu = mjw_plan_du_count(&s.plan), iu = s.restart ? (size_t)s.restart * (size_t)s.plan.du_per_mcu : nu;
+	if (!s.restart || iu >= nu)
+		return (nu + MIJ_EMIT_TILE - 1) / MIJ_EMIT_TILE;
+	return nu / iu * ((iu + MIJ_EMIT_TILE - 1) / MIJ_EMIT_TILE) + (nu % iu + MIJ_EMIT_TILE - 1) / MIJ_EMIT_TILE;
+}
 
 /* Emission lists at upload: one EmitSlot per slot, its tiles of MIJ_EMIT_TILE units, its headers (enc_own_header).  Optimised slots also get their tiles in a list of their
  * own, a table entry and counts. */
@@ -3817,7 +3873,7 @@ static int enc_emit_lists(mij_encoder *e)
 	const size_t n = e->slots.size();
 	size_t nt = 0, nh = 0, no = 0, not_ = 0;
 	for (const EncSlot &s : e->slots) {
-		const size_t tiles = (mjw_plan_du_count(&s.plan) + MIJ_EMIT_TILE - 1) / MIJ_EMIT_TILE;
+		const size_t tiles = enc_slot_tile_count(s);
 		nt += tiles;
 		nh += enc_own_header(e, s);
 		no += s.optimize;
@@ -3871,27 +3927,30 @@ static int enc_emit_lists(mij_encoder *e)
 		rc = grow_dev(e->d_sent, e->sent_cap, n);
 	if (rc != MIJ_OK)
 		return rc;
-	std::vector<uint32_t> hdr_of(n), hlen_of(n, (uint32_t)MIJ_EMIT_HDR);
+	std::vector<uint32_t> hdr_of(n), hlen_of(n, (uint32_t)MJW_HEADER_BYTES);
 	uint32_t t = 0, h = 0, k = 0, ot = 0;
 	e->opt_of.assign(n, -1);
 	for (size_t i = 0; i < n; ++i) {
 		const EncSlot &s = e->slots[i];
 		if (enc_own_header(e, s)) {
 			if (s.kind == ENC_COEF) /* shorter for a grey slot */
-				hlen_of[i] = (uint32_t)mjw_theader(&s.tp, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
+				hlen_of[i] = (uint32_t)mjw_theader_restart(&s.tp, s.restart, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
 			else
-				mjw_header(&s.plan, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
+				hlen_of[i] = (uint32_t)mjw_header_restart(&s.plan, s.restart, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
 			hdr_of[i] = h++;
 		} else {
 			hdr_of[i] = hdr_of[(size_t)s.clone_of];
+			hlen_of[i] = hlen_of[(size_t)s.clone_of];
 		}
 		EmitSlot &es = e->h_eslot[i];
 		es.du_off = s.dev.du_off;
 		es.n_du = (uint32_t)mjw_plan_du_count(&s.plan);
 		es.dpm = (uint32_t)s.plan.du_per_mcu;
 		es.first_tile = t;
-		es.n_tiles = (es.n_du + MIJ_EMIT_TILE - 1) / MIJ_EMIT_TILE;
+		es.n_tiles = (uint32_t)enc_slot_tile_count(s);
 		es.hdr = hdr_of[i];
+		es.ri = (uint32_t)s.restart;
+		es.pad = 0;
 		es.tab = 0;
 		es.ny = s.kind == ENC_COEF ? (s.tp.ncomp == 1 ? 1u : (uint32_t)(s.tp.lh * s.tp.lv)) : (s.plan.subsample ? 4u : 1u);
 		es.hlen = hlen_of[i];
@@ -3900,12 +3959,12 @@ static int enc_emit_lists(mij_encoder *e)
 			e->h_optslot[k] = (uint32_t)i;
 			es.tab = ++k;
 		}
-		for (uint32_t u = 0; u < es.n_du; u += MIJ_EMIT_TILE) {
-			const EmitTile tl = {(uint32_t)i, u, 0u, 0u};
+		enc_slot_tiles(es.n_du, es.dpm, es.ri, [&](uint32_t u, uint32_t pad) {
+			const EmitTile tl = {(uint32_t)i, u, 0u, pad};
 			e->h_etile[t++] = tl;
 			if (s.optimize)
 				e->h_otile[ot++] = tl;
-		}
+		});
 	}
 	e->n_etile = nt;
 	e->n_opt = no;
@@ -3933,10 +3992,10 @@ static int enc_emit_launch(mij_encoder *e)
 								 e->d_optok);
 	}
 	hipLaunchKernelGGL(k_emit_len, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_tbits);
-	hipLaunchKernelGGL(k_emit_scan, per_slot, block, 0, e->stream, e->d_eslot, n, e->d_tbits, e->d_tboff);
+	hipLaunchKernelGGL(k_emit_scan, per_slot, block, 0, e->stream, e->d_eslot, e->d_etile, n, e->d_tbits, e->d_tboff);
 	hipLaunchKernelGGL(k_emit_count, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_tbits, e->d_tboff, e->d_tff, e->d_tfrag,
 							 e->has_coef ? e->d_sflag : nullptr);
-	hipLaunchKernelGGL(k_emit_stuff, per_slot, block, 0, e->stream, e->d_eslot, n, e->d_tbits, e->d_tboff, e->d_tff, e->d_tfrag, e->d_tout, e->d_sent);
+	hipLaunchKernelGGL(k_emit_stuff, per_slot, block, 0, e->stream, e->d_eslot, e->d_etile, n, e->d_tbits, e->d_tboff, e->d_tff, e->d_tfrag, e->d_tout, e->d_sent);
 	hipLaunchKernelGGL(k_emit_place, dim3(1), dim3(1024), 0, e->stream, e->d_eslot, n, e->d_sent, (uint64_t)e->arena_cap, e->d_res);
 	hipLaunchKernelGGL(k_emit_write, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_hdr, e->d_tbits, e->d_tboff, e->d_tfrag,
 							 e->d_tout, e->d_res, e->d_arena);
@@ -4402,6 +4461,7 @@ static int enc_coef_convert(mij_encoder *e)
 			if (s.kind != ENC_COEF || s.src != g.b || s.coef_fmt != g.fmt || s.coef.orient != g.orient || g.rq != (s.coef.rq != 0) || g.win != (s.coef.win != 0))
 				continue;
 			e->h_cslot[k] = s.coef;
+			e->h_cslot[k].ri = (uint32_t)s.restart;
 			if (g.rq) {
 				rq_fill(e->h_rqt[q], (s.coef.orient & MIJ_CONV_TR) != 0, s.rq_from[0], s.tp.plan.ytab, s.rq_from[1], s.tp.plan.ctab);
 				e->h_cslot[k].rq = (uint32_t)++q;

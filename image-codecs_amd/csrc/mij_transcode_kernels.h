@@ -45,6 +45,10 @@
  * swap, mirrors and origin: the first unit of the window predicts from 0 whatever lies left of the cut.  The work list of such a slot
  * names only the tiles that hold a block of the rectangle (enc_coef_convert), and no chroma tile for a grey destination.
  * WIN = 0 instances contain none of this.
+ *
+ * Restart intervals (mij_enc_set_restart): the DC difference that is checked is the one that will be coded, so the first unit of each component
+ * in an MCU whose index in the DESTINATION (after orientation, crop and grey) is a multiple of CoefSlot.ri predicts from 0.  ri is run-time and
+ * wave-uniform; ri = 0 skips the test.
  */
 #pragma once
 
@@ -58,7 +62,8 @@ struct CoefSlot {
 	uint32_t d_mcu_x, d_mcu_y, d_lh, d_lv;      /* the destination's (the source's again for orientation 1) */
 	uint32_t ext_x, ext_y;                      /* the source's MCU columns and rows that the trim keeps */
 	uint32_t w_ox[2], w_oy[2], w_ew[2], w_eh[2]; /* a windowed slot (win != 0): the kept rectangle of the source plane in blocks, luma and chroma */
-	uint32_t win, pad;                          /* win: 1 for a slot the WIN = 1 instances convert */
+	uint32_t win, ri;                           /* win: 1 for a slot the WIN = 1 instances convert; ri: the destination's restart interval in MCUs
+	                                               (mij_enc_set_restart), 0: none */
 	uint32_t orient, rq;                        /* MIJ_CONV_NX | MIJ_CONV_NY | MIJ_CONV_TR: which template instance converts the slot; rq: 1 + the
 	                                               index of the slot's RqTable for a requantising slot (the RQ = 1 instances), 0 for a plain one */
 };
@@ -209,6 +214,8 @@ __global__ __launch_bounds__(64) void k_coef_units(const CoefSlot *__restrict__ 
 			px = bx - 1u, py = by;
 		else if (sy > 0)
 			px = mx * dh + dh - 1u, py = by - 1u;
+		else if (s.ri && (my * dmcu_x + mx) % s.ri == 0u) /* the first MCU of a restart interval of the destination: predicted from 0 */
+			has = false;
 		else if (mx > 0)
 			px = mx * dh - 1u, py = my * dv + dv - 1u;
 		else if (my > 0)

@@ -453,11 +453,12 @@ int mjw_units_crop(const mjw_tplan *src, const int16_t *du_src, const int rect[4
 /* one step's units replace the previous step's */
 static int16_t *units_for(const mjw_tplan *t) { return (int16_t *)malloc(mjw_tplan_du_count(t) * 64 * sizeof(int16_t)); }
 
-int mjw_transcode_memory_window_at(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
-                                   const unsigned char *chroma, int coarsen_only, unsigned char **out, size_t *out_len, int *rect_out,
-                                   const char **reason)
+int mjw_transcode_memory_restart_at(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
+                                    const unsigned char *chroma, int coarsen_only, int restart_rows, int restart_mcus, unsigned char **out,
+                                    size_t *out_len, int *rect_out, int *ri_out, const char **reason)
 {
 	mij_image_desc d;
+	int ri = 0;
 	mjw_tplan t, next;
 	const char *why = NULL;
 	uint8_t *region = NULL;
@@ -523,7 +524,10 @@ int mjw_transcode_memory_window_at(const uint8_t *src, int len, unsigned flags, 
 			STEP(1, mjw_units_requant(&t, &next, du, dn));
 	}
 #undef STEP
-	if (!mjw_tunits_codable(&t, du, reason))
+	/* the interval is one of the destination: its MCU rows are the rows after grey, orientation and crop */
+	if (!mjw_restart_interval(&t, restart_rows, restart_mcus, &ri, reason))
+		goto done;
+	if (!mjw_tunits_codable_restart(&t, du, ri, reason))
 		goto done;
 	cap = MJW_STREAM_CAP(mjw_tplan_du_count(&t));
 	buf = (unsigned char *)malloc(cap);
@@ -531,7 +535,7 @@ int mjw_transcode_memory_window_at(const uint8_t *src, int len, unsigned flags, 
 		refuse(reason, "out of memory");
 		goto done;
 	}
-	n = mjw_temit_to_memory(&t, du, flags & MJW_OPTIMIZE_HUFFMAN, buf, cap);
+	n = ri ? mjw_temit_restart_to_memory(&t, du, flags & MJW_OPTIMIZE_HUFFMAN, ri, buf, cap) : mjw_temit_to_memory(&t, du, flags & MJW_OPTIMIZE_HUFFMAN, buf, cap);
 	if (!n) {
 		refuse(reason, "emission failed");
 		goto done;
@@ -546,12 +550,21 @@ int mjw_transcode_memory_window_at(const uint8_t *src, int len, unsigned flags, 
 	}
 	if (ok && rect_out)
 		memcpy(rect_out, rect, sizeof(rect));
+	if (ok && ri_out)
+		*ri_out = ri;
 done:
 	free(region);
 	free(du);
 	free(dn);
 	free(buf);
 	return ok;
+}
+
+int mjw_transcode_memory_window_at(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
+                                   const unsigned char *chroma, int coarsen_only, unsigned char **out, size_t *out_len, int *rect_out,
+                                   const char **reason)
+{
+	return mjw_transcode_memory_restart_at(src, len, flags, o, trim, crop, grey, luma, chroma, coarsen_only, 0, 0, out, out_len, rect_out, NULL, reason);
 }
 
 int mjw_transcode_memory_requant_at(const uint8_t *src, int len, unsigned flags, int o, int trim, const unsigned char *luma,

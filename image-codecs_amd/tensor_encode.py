@@ -62,6 +62,26 @@ def denorm_scale_bias(n, mean=None, std=None):
     return out[0], out[1]
 
 
+def _restart_values(v, n, name):
+    """restart_rows= / restart_mcus= as one int >= 0 per picture (None is 0: none)"""
+    what = name + " must be None, an int >= 0 or one of those per picture (got %r)"
+    if v is None or (isinstance(v, int) and not isinstance(v, bool)):
+        vals = [v] * n
+    else:
+        if isinstance(v, (str, bytes, torch.Tensor)):
+            raise ValueError(what % (v,))
+        try:
+            vals = list(v)
+        except TypeError:
+            raise ValueError(what % (v,)) from None
+        if len(vals) != n:
+            raise ValueError("%s has %d values for %d pictures" % (name, len(vals), n))
+    for x in vals:
+        if not (x is None or (isinstance(x, int) and not isinstance(x, bool) and x >= 0)):
+            raise ValueError(what % (x,))
+    return [0 if x is None else x for x in vals]
+
+
 class TensorEncoder:
     """Encodes uint8 pictures that live on a GPU into JPEG byte streams, each exactly what stbi_write_jpg_to_func writes for that
     picture (encode), and float16 / bfloat16 / float32 pictures as the uint8 pictures they de-normalise to (encode_normalized).
@@ -80,6 +100,7 @@ class TensorEncoder:
         self._cap = (0, 0, 0)
         self._arena = 0
         self.last_host_emitted = 0
+        self.last_restarts = []
 
     @property
     def device(self):
@@ -181,16 +202,21 @@ class TensorEncoder:
             self._enc.reset()
         return self._enc
 
-    def encode(self, images, *, quality=90, layout="CHW", flip_vertically=False, optimize=False):
+    def encode(self, images, *, quality=90, layout="CHW", flip_vertically=False, optimize=False, restart_rows=None, restart_mcus=None):
         """quality: 1..100, or 0 for the default 90, as stbi_write_jpg takes it.  images: a 4-D uint8 tensor on the GPU ([N, C, H, W] for layout "CHW", [N, H, W, C] for "HWC") or a sequence of 3-D
         (2-D: grey) uint8 tensors, whose sizes may differ; C is 1..4 (stbi_write_jpg's comp).  Strided views are accepted (unit
         stride along W for CHW; strides C and 1 along W and C for HWC).  -> one bytes object per picture: what
         stbi_write_jpg_to_func(W, H, C, picture, quality) writes (under stbi_flip_vertically_on_write(1) with flip_vertically).
         optimize (a bool): every stream gets Huffman tables built on the GPU from its own symbol statistics -- the same coefficients in
-        fewer bytes, what mjw_emit_optimized writes for the picture's data units, whatever the arena's size."""
-        return self._encode(images, None, None, quality, layout, flip_vertically, optimize, False)
+        fewer bytes, what mjw_emit_optimized writes for the picture's data units, whatever the arena's size.
+        restart_rows, restart_mcus: None, an int >= 0 or one of those per picture: restart markers after every so many MCU rows, or MCUs
+        (an MCU is 16 x 16 pixels up to quality 90 and 8 x 8 above) -- what mjw_emit_restart writes (include/mij_host.h, RESTART
+        INTERVALS).  None or 0 means none.  ValueError for both given for one picture and for an interval above 65535 MCUs.
+        last_restarts[i] is the interval used, in MCUs."""
+        return self._encode(images, None, None, quality, layout, flip_vertically, optimize, False, restart_rows, restart_mcus)
 
-    def encode_normalized(self, images, *, mean=None, std=None, quality=90, layout="CHW", flip_vertically=False, optimize=False):
+    def encode_normalized(self, images, *, mean=None, std=None, quality=90, layout="CHW", flip_vertically=False, optimize=False,
+                          restart_rows=None, restart_mcus=None):
         """encode() for the tensors a model works on: images as for encode() -- the same shapes, stride rules and layouts -- but float16,
         bfloat16 or float32, one dtype per call.  The pictures are de-normalised on the GPU, inside the kernel that gathers them
         (mij_enc_add_device_float), by the contract of include/mij.h: for element x of channel c
@@ -202,10 +228,10 @@ class TensorEncoder:
         Both None: the pictures hold v / 255, tensor_tables' convention; with the mean / std a TensorDecoder.decode was given, its
         tensors come back as the bytes they were made from, for all three dtypes.  A tensor holding 0..255 values is std=[1/255]*C.
         ValueError, before any device is touched, for uint8 or any other non-float dtype, mixed dtypes, a wrong number of mean / std
-        values, a std of 0, a value that is not finite, and everything encode() refuses."""
-        return self._encode(images, mean, std, quality, layout, flip_vertically, optimize, True)
+        values, a std of 0, a value that is not finite, and everything encode() refuses.  restart_rows, restart_mcus: as for encode()."""
+        return self._encode(images, mean, std, quality, layout, flip_vertically, optimize, True, restart_rows, restart_mcus)
 
-    def _encode(self, images, mean, std, quality, layout, flip_vertically, optimize, floats):
+    def _encode(self, images, mean, std, quality, layout, flip_vertically, optimize, floats, restart_rows=None, restart_mcus=None):
         if not isinstance(optimize, bool):
             raise ValueError("optimize must be a bool, got %r" % (optimize,))
         if isinstance(quality, bool) or not isinstance(quality, int) or not 0 <= quality <= 100:
@@ -220,7 +246,9 @@ class TensorEncoder:
                 scale, bias = denorm_scale_bias(c, mean, std)
                 by_c[c] = InConvert(_FLOAT_DT[views[0][0].dtype] if views else MIJ_DT_F32, scale, bias)
             convs = [by_c[v[3]] for v in views]
+        rrows, rmcus = _restart_values(restart_rows, len(views), "restart_rows"), _restart_values(restart_mcus, len(views), "restart_mcus")
         self._placed(views)
+        self.last_restarts = restarts = []
         if not views:
             return []
         flip = bool(flip_vertically)
@@ -230,6 +258,13 @@ class TensorEncoder:
             p = _plan(w, h, c, quality)
             pad_w = _align(w, 16 if p.subsample else 8)
             sizes.append((_align(pad_w * h * 3, 256), _align(p.mcu_x * p.mcu_y * p.du_per_mcu * 128, 256), w * h))
+            k = len(restarts)
+            if rrows[k] and rmcus[k]:
+                raise ValueError("picture %d: restart_rows and restart_mcus are two ways to say the same thing: give one" % k)
+            ri = rrows[k] * p.mcu_x if rrows[k] else rmcus[k]
+            if ri > 65535:
+                raise ValueError("picture %d: a restart interval of %d MCUs does not fit the DRI segment (65535 at most)" % (k, ri))
+            restarts.append(ri)
         _one_hip_runtime()
         torch.cuda.current_stream(self.device).synchronize()
         out, host, i = [], 0, 0
@@ -238,14 +273,14 @@ class TensorEncoder:
             while j < len(views) and j - i < MAX_SLOTS and (j == i or pix + sizes[j][0] <= MAX_PIXEL_BYTES):
                 pix += sizes[j][0]
                 j += 1
-            streams, h = self._encode_chunk(views[i:j], sizes[i:j], quality, lay, flip, optimize, convs[i:j] if floats else None)
+            streams, h = self._encode_chunk(views[i:j], sizes[i:j], quality, lay, flip, optimize, convs[i:j] if floats else None, restarts[i:j])
             out.extend(streams)
             host += h
             i = j
         self.last_host_emitted = host
         return out
 
-    def _encode_chunk(self, views, sizes, quality, lay, flip, optimize, convs=None):
+    def _encode_chunk(self, views, sizes, quality, lay, flip, optimize, convs=None, restarts=None):
         if not self._arena:  # a first guess, about 0.75 bytes per pixel; misses grow it
             self._arena = _align(sum(1024 + (px * 3) // 4 for (_, _, px) in sizes), 1 << 20)
         enc = self._encoder_for(len(views), sum(s[0] for s in sizes), sum(s[1] for s in sizes))
@@ -254,6 +289,8 @@ class TensorEncoder:
             slot = enc.add_device(it, quality, flip) if convs is None else enc.add_device_float(it, convs[k], quality, flip)
             if optimize:
                 enc.set_optimize(slot)
+            if restarts and restarts[k]:
+                enc.set_restart(slot, restarts[k])
         enc.upload()
         enc.launch()
         enc.fetch_streams()
@@ -262,7 +299,7 @@ class TensorEncoder:
             data, n = enc.stream(slot)
             need += n
             if data is None:  # did not fit: its units are still on the device, the host Huffman stage finishes it
-                data = emit_jpeg(enc.plan(slot), enc.fetch(slot), optimize)
+                data = emit_jpeg(enc.plan(slot), enc.fetch(slot), optimize, restart_mcus=enc.slot_restart(slot))
                 host += 1
             streams.append(data)
         if host:

@@ -6,7 +6,7 @@ cross PCIe on the way back.  No pixel kernel is launched.
 
 This module needs no torch."""
 from .binding import Batch, Context, Encoder, HostDecoder, MijError, _qtable_pair, copy_markers as _copy_markers, emit_transcoded, \
-    exif_orientation, exif_set_orientation, quality_tables, transcode_plan, transcode_plan_cropped, transcode_plan_grey, \
+    exif_orientation, exif_set_orientation, quality_tables, restart_interval, transcode_plan, transcode_plan_cropped, transcode_plan_grey, \
     transcode_plan_oriented
 
 # one launch takes at most this many pictures / bytes of coefficient arena; larger calls are cut into chunks
@@ -117,6 +117,26 @@ def _greys(v, n):
     return vals
 
 
+def _intervals(v, n, name):
+    """transcode's restart_rows= / restart_mcus= as one int >= 0 per source (None is 0: none)"""
+    what = name + " must be None, an int >= 0 or one of those per source (got %r)"
+    if v is None or _is_int(v):
+        vals = [v] * n
+    else:
+        if isinstance(v, (str, bytes)):
+            raise ValueError(what % (v,))
+        try:
+            vals = list(v)
+        except TypeError:
+            raise ValueError(what % (v,)) from None
+        if len(vals) != n:
+            raise ValueError("%s has %d values for %d sources" % (name, len(vals), n))
+    for x in vals:
+        if not (x is None or (_is_int(x) and x >= 0)):
+            raise ValueError(what % (x,))
+    return [0 if x is None else x for x in vals]
+
+
 def _destination(desc, o, trim, crop, grey):
     """-> (data-unit elements, pixels) of the picture a source becomes, from its header alone; None where a step refuses (mij_enc_add_coef
     says why later) and the source's own size has to do"""
@@ -135,8 +155,8 @@ class Transcoder:
 
     Owns a Context, a Batch and an Encoder with its emission arena, grown as needed and reused across calls.  Synchronous.  Sources that
     are transcodable: grey, and YCbCr (JFIF or Adobe transform 1) as 4:4:4, 4:2:2, 4:4:0 or 4:2:0, baseline or progressive, with or without
-    restart intervals, whose quantisation tables hold 8-bit entries and are the same for Cb and Cr.  The output is always a baseline stream
-    without restart intervals (include/mij_host.h, mjw_tplan, has the whole contract).  Slots whose streams do not fit the arena are
+    restart intervals, whose quantisation tables hold 8-bit entries and are the same for Cb and Cr.  The output is always a baseline stream,
+    without restart intervals unless they are asked for (include/mij_host.h, mjw_tplan, has the whole contract).  Slots whose streams do not fit the arena are
     finished on the host from their units (last_host_emitted counts them) and the arena grows for the next call."""
 
     def __init__(self, device=None):
@@ -155,6 +175,7 @@ class Transcoder:
         self.last_requantized = []
         self.last_crops = []
         self.last_greyed = []
+        self.last_restarts = []
         self.last_timing = {}
 
     @property
@@ -217,7 +238,7 @@ class Transcoder:
         return self._enc
 
     def transcode(self, datas, *, optimize=True, copy_markers="all", only_if_smaller=False, gpu_entropy=None, threads=16, orientation=None,
-                  edge="perfect", quality=None, qtables=None, coarsen_only=True, crop=None, grey=False):
+                  edge="perfect", quality=None, qtables=None, coarsen_only=True, crop=None, grey=False, restart_rows=None, restart_mcus=None):
         """datas: a sequence of JPEG files as bytes.  -> a list with, per source, the new stream (bytes) or None; last_reasons[i] is None
         or the reason source i was refused or could not be decoded.
         optimize: Huffman tables built from each picture's own statistics (mjw_temit_optimized's stream); False: the Annex-K tables.
@@ -249,6 +270,11 @@ class Transcoder:
         alone, with its reason in last_reasons[i].  The steps run as grey -> orient -> crop -> requantise (include/mij_host.h,
         mjw_tplan_cropped); where crop or grey changed the picture the result is returned whatever only_if_smaller says.  EXIF pixel
         dimensions and thumbnails of copied markers are not fixed up.
+        restart_rows, restart_mcus: None, an int >= 0 or one of those per source: restart markers after every so many MCU rows, or MCUs,
+        of the destination -- its geometry after grey -> orient -> crop (jpegtran -restart N / -restart NB; include/mij_host.h, RESTART
+        INTERVALS).  None or 0 means none; giving both for the same source is a ValueError.  An interval that resolves above 65535 MCUs
+        refuses that picture alone, with its reason in last_reasons[i].  last_restarts[i] is the interval used, in MCUs.  A source's own
+        DRI is never copied (copy_markers copies APPn and COM only), and only_if_smaller compares the finished stream as it is.
         ValueError, before a device is touched, for arguments that are not of these kinds."""
         if not isinstance(optimize, bool) or not isinstance(only_if_smaller, bool):
             raise ValueError("optimize and only_if_smaller must be bools")
@@ -273,6 +299,11 @@ class Transcoder:
         targets = _targets(quality, qtables, len(datas))
         crops = _crops(crop, len(datas))
         greys = _greys(grey, len(datas))
+        rrows, rmcus = _intervals(restart_rows, len(datas), "restart_rows"), _intervals(restart_mcus, len(datas), "restart_mcus")
+        for i, (r, m) in enumerate(zip(rrows, rmcus)):
+            if r and m:
+                raise ValueError("source %d: restart_rows and restart_mcus are two ways to say the same thing: give one" % i)
+        self.last_restarts = restarts = [0] * len(datas)
         self.last_requantized = requantized = [False] * len(datas)
         self.last_crops = kept = [None] * len(datas)
         self.last_greyed = greyed = [False] * len(datas)
@@ -309,7 +340,7 @@ class Transcoder:
                 coef += todo[j][1]
                 j += 1
             self._chunk(datas, todo[k:j], out, reasons, optimize, gpu_entropy, threads, orients, edge == "trim", targets, coarsen_only,
-                        requantized, crops, greys, kept, greyed, windowed)
+                        requantized, crops, greys, kept, greyed, windowed, rrows, rmcus, restarts)
             k = j
         for i, d in enumerate(datas):
             if out[i] is None:
@@ -327,7 +358,7 @@ class Transcoder:
         return out
 
     def _chunk(self, datas, items, out, reasons, optimize, gpu_entropy, threads, orients, trim, targets, coarsen_only, requantized, crops,
-               greys, kept, greyed, windowed):
+               greys, kept, greyed, windowed, rrows, rmcus, restarts):
         n = len(items)
         srcs = [datas[it[0]] for it in items]
         stream = 0
@@ -360,6 +391,14 @@ class Transcoder:
             requantized[it[0]] = enc.slot_requantized(es[it[0]])
             if optimize:
                 enc.set_optimize(es[it[0]])
+            if rrows[it[0]] or rmcus[it[0]]:  # resolved on the destination's plan; a refused one costs its slot, which is never fetched
+                ri, bad = restart_interval(enc.tplan(es[it[0]]), rrows[it[0]], rmcus[it[0]])
+                if ri is None:
+                    reasons[it[0]] = "restart interval: " + bad
+                    del es[it[0]]
+                    continue
+                enc.set_restart(es[it[0]], ri)
+                restarts[it[0]] = ri
         if not es:
             b.wait()
             return
@@ -377,7 +416,8 @@ class Transcoder:
                 if enc.slot_status(slot) == "uncodable":
                     reasons[i] = "not codable: an AC coefficient outside -1023..1023 or a DC difference outside -2047..2047"
                     continue
-                data = emit_transcoded(enc.tplan(slot), enc.fetch(slot), optimize)  # its units are on the device: the host finishes it
+                # its units are on the device: the host finishes it, at the same interval
+                data = emit_transcoded(enc.tplan(slot), enc.fetch(slot), optimize, restart_mcus=restarts[i])
                 host += 1
             need += ln
             out[i] = data

@@ -675,6 +675,22 @@ int mij_enc_set_optimize(mij_encoder *e, int slot, int on);
 int mij_enc_slot_optimized(const mij_encoder *e, int slot);
 
 /*
+ * Restart intervals: a slot's stream with a DRI segment and an RSTk marker after every restart_mcus MCUs (0..65535; 0: none, the
+ * default) -- the bytes mjw_emit_restart / mjw_temit_restart (mij_host.h, RESTART INTERVALS) write for the slot's units at that
+ * interval, plain or optimised.  With an emission arena the same launches write it: the slot's tile list is cut at the interval ends
+ * (mij_emit_kernels.h), so a small interval means many small tiles.  A slot whose stream is finished on the host (no arena, or no room
+ * in it) is finished with those host calls at mij_enc_slot_restart's interval: the same bytes.
+ *
+ * mij_enc_set_restart: for a slot of any kind, after it is added and before mij_enc_upload; MIJ_E_STATE after the upload, MIJ_E_ARG for
+ * a bad slot, an interval outside 0..65535 and, for a slot of given units (mij_enc_add_units, which judged them unbroken), units whose DC
+ * differences against the restarted predictors leave -2047..2047.  A coefficient slot's codability is judged against the restarted
+ * predictors by the conversion kernel.  A clone inherits the interval of the slot it is made from; mij_enc_reset forgets all requests.
+ * mij_enc_slot_restart: the slot's interval, or a negative code for a bad slot.
+ */
+int mij_enc_set_restart(mij_encoder *e, int slot, int restart_mcus);
+int mij_enc_slot_restart(const mij_encoder *e, int slot);
+
+/*
  * Lossless transcode: an encoder slot whose data units are the QUANTISED coefficients of a decode batch's slot, taken from the batch's
  * coefficient planes in device memory -- a new slot kind beside given units.  The contract (which sources are transcodable, the unit
  * order, the stream) is written in mij_host.h (mjw_tplan); the slot's stream is what mjw_temit / mjw_temit_optimized write for

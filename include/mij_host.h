@@ -149,8 +149,11 @@ int mij_write_jpg_to_func(mjw_write_func *func, void *context, int x, int y, int
  * return every out[i] is NULL again and nothing is left for the caller to free. */
 int mij_write_jpg_batch(const void *const *pixels, const int *x, const int *y, const int *comp, int n, int quality, int threads,
                         unsigned char **out, size_t *out_len);
-/* A capacity that holds the stream of `units` data units whatever they contain: a coefficient takes at most 27 bits (a 16-bit code and
- * 11 value bits) and every output byte may be a 0xFF that is stuffed, so under 7 bytes each; headers and EOI fit the 2048.  (Two bytes
+/* A capacity that holds the stream of `units` data units whatever they contain, with or without restart intervals.  Per unit: a DC symbol of at
+ * most 11 + 11 bits and 63 AC symbols of at most 16 + 10, 1660 bits.  The worst interval is one grey unit (Ri = 1, one unit per MCU): its 1660
+ * bits and the 7 fill bits are 1667, so 208 whole bytes (the 3 bits left over are dropped); every one of them may be a 0xFF that takes a stuffed
+ * zero, 416 bytes, and two marker bytes follow: 418 <= 64 * 7 = 448.  Longer intervals and the unbroken scan pay the fill byte and the marker
+ * less often, so 448 bytes per unit bound them too; SOI .. SOS with a DRI segment (MJW_HEADER_RESTART_BYTES) and EOI fit the 2048.  (Two bytes
  * per coefficient are NOT enough: a codable unit can take 1667 bits before stuffing.) */
 #define MJW_STREAM_CAP(units) ((size_t)2048 + (size_t)(units) * 64 * 7)
 /* mjw_emit into memory: bytes written, 0 when `cap` is too small or an argument is bad (MJW_STREAM_CAP(mjw_plan_du_count(p)) always fits) */
@@ -201,7 +204,7 @@ int mij_write_jpg_batch_ex(const void *const *pixels, const int *x, const int *y
  * Blocks a non-interleaved scan never coded are what the planes hold (zeros) and are emitted like any other.
  *
  * Stream: SOI, the writer's JFIF APP0, DQT with the SOURCE's tables in zigzag order (luma as id 0, chroma as id 1), SOF0 with the source's
- * size and sampling, DHT, SOS and the entropy-coded segment exactly as mjw_emit / mjw_emit_optimized code units; no DRI.  For 4:4:4 and 4:2:0
+ * size and sampling, DHT, SOS and the entropy-coded segment exactly as mjw_emit / mjw_emit_optimized code units; no DRI unless asked (RESTART INTERVALS, below).  For 4:4:4 and 4:2:0
  * the header is mjw_header's (mjw_header_optimized's) byte for byte given those tables, for 4:2:2 and 4:4:0 only the luma sampling byte
  * differs; a grey stream has a one-component SOF0 and SOS, one DQT table and only the luma DC and AC tables in its DHT.  At most
  * MJW_HEADER_BYTES.
@@ -378,6 +381,57 @@ int mjw_transcode_memory_window_at(const uint8_t *src, int len, unsigned flags, 
 int mjh_transcode_memory_window(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
                                 const unsigned char *chroma, int coarsen_only, unsigned char **out, size_t *out_len, int *rect_out,
                                 const char **reason);
+
+/*
+ * RESTART INTERVALS (jpegtran -restart N / -restart NB): every stream above is one unbroken entropy-coded segment unless an interval Ri is
+ * asked for, 0..65535 MCUs; Ri = 0 means none and gives the calls above, byte for byte.
+ *
+ * DRI.  For Ri > 0 the segment FF DD 00 04 Ri_hi Ri_lo stands directly in front of SOS, behind DHT (where libjpeg puts it); nothing else of the
+ * header changes, so a header is at most MJW_HEADER_RESTART_BYTES.
+ * INTERVAL END.  After every Ri MCUs that are not the last MCUs of the scan the interval is filled exactly as the scan's end is: seven 1-bits
+ * are appended and what remains below a byte is dropped; a completed 0xFF byte -- the filled one included -- is followed by a stuffed 0x00; then
+ * comes the marker FF D0+(k mod 8), unstuffed, for interval k = 0, 1, ...  No marker follows the final interval, also when the MCU count is a
+ * multiple of Ri.  Ri >= the MCU count gives the entropy bytes of Ri = 0 behind a header with a DRI segment.
+ * PREDICTORS.  The DC prediction of every component restarts from 0 at each interval's first MCU, and what follows the predictors follows:
+ * the histogram of the optimised tables counts the DC categories that are coded, and codability judges a DC difference against the restarted
+ * predictor -- DC +1500 then -1500 in one component is uncodable in one segment and codable at Ri = 1; a unit run that is codable unbroken
+ * can be uncodable with restarts (a DC beyond +-2047 reached in small steps, then predicted from 0).
+ *
+ *   mjw_restart_interval   Ri of a plan from an interval in MCU rows (rows x plan.mcu_x) or in MCUs; 0 with *reason (a static string) for
+ *                          both given, a negative value, or a result above 65535.  (0, 0) is Ri = 0.
+ *   mjw_[t]header[_optimized]_restart   the headers with the DRI segment; 0 for ri outside 0..65535
+ *   mjw_[t]histogram_restart            mjw_histogram's counts with the restarted predictors, of a plan's or a transcode plan's units
+ *   mjw_units_codable_restart, mjw_tunits_codable_restart   mjw_tunits_codable's ranges with the restarted predictors
+ *   mjw_[t]emit_restart[_to_memory]     the stream; flags 0 or MJW_OPTIMIZE_HUFFMAN.  mjw_temit_restart returns 0 for units that are not
+ *                          codable at this ri; MJW_STREAM_CAP holds any of these streams.
+ *   mjw_transcode_memory_restart_at     mjw_transcode_memory_window_at with an interval in destination MCU rows or MCUs, resolved on the
+ *                          destination plan (after grey, orientation and crop); *ri_out (may be NULL) gets the Ri used
+ *   mjh_transcode_memory_restart        mjh_transcode_memory_window's arguments plus Ri in MCUs; _by: rows or MCUs, and *ri_out.  A source's
+ *                          own DRI is never copied: MJW_COPY_MARKERS copies APPn and COM only.
+ */
+#define MJW_HEADER_RESTART_BYTES (MJW_HEADER_BYTES + 6)
+int mjw_restart_interval(const mjw_tplan *t, int rows, int mcus, int *ri, const char **reason);
+size_t mjw_header_restart(const mjw_plan *p, int ri, unsigned char *out);
+size_t mjw_header_optimized_restart(const mjw_plan *p, const uint8_t bits[4][16], const uint8_t vals[4][256], int ri, unsigned char *out);
+size_t mjw_theader_restart(const mjw_tplan *t, int ri, unsigned char *out);
+size_t mjw_theader_optimized_restart(const mjw_tplan *t, const uint8_t bits[4][16], const uint8_t vals[4][256], int ri, unsigned char *out);
+int mjw_histogram_restart(const mjw_plan *p, const int16_t *du, int ri, uint32_t freq[4][256]);
+int mjw_thistogram_restart(const mjw_tplan *t, const int16_t *du, int ri, uint32_t freq[4][256]);
+int mjw_units_codable_restart(const mjw_plan *p, const int16_t *du, int ri, const char **reason);
+int mjw_tunits_codable_restart(const mjw_tplan *t, const int16_t *du, int ri, const char **reason);
+int mjw_emit_restart(const mjw_plan *p, const int16_t *du, unsigned flags, int ri, mjw_write_func *func, void *context);
+int mjw_temit_restart(const mjw_tplan *t, const int16_t *du, unsigned flags, int ri, mjw_write_func *func, void *context);
+size_t mjw_emit_restart_to_memory(const mjw_plan *p, const int16_t *du, unsigned flags, int ri, unsigned char *out, size_t cap);
+size_t mjw_temit_restart_to_memory(const mjw_tplan *t, const int16_t *du, unsigned flags, int ri, unsigned char *out, size_t cap);
+int mjw_transcode_memory_restart_at(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
+                                    const unsigned char *chroma, int coarsen_only, int restart_rows, int restart_mcus, unsigned char **out,
+                                    size_t *out_len, int *rect_out, int *ri_out, const char **reason);
+int mjh_transcode_memory_restart(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
+                                 const unsigned char *chroma, int coarsen_only, unsigned char **out, size_t *out_len, int *rect_out, int ri,
+                                 const char **reason);
+int mjh_transcode_memory_restart_by(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
+                                    const unsigned char *chroma, int coarsen_only, int restart_rows, int restart_mcus, unsigned char **out,
+                                    size_t *out_len, int *rect_out, int *ri_out, const char **reason);
 
 /* The tables of stbi__ldr_to_hdr(common.c:391-424) for mij_batch_set_out_f32: lut[256*k + v] for channel k < n_out.  Colour
  * channels (all of them for odd n_out, all but the last for even n_out) get (float)(pow(v / 255.0f, gamma) * scale), the
