@@ -1233,15 +1233,33 @@ def _restart_mcus(v):
     return int(v)
 
 
-def emit_jpeg(plan, du, optimize=False, restart_mcus=None):
+def _progressive_flag(v, restart=False):
+    """the progressive request as a bool; ValueError for a non-bool and for the request together with a restart interval"""
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError("progressive is a bool (got %r)" % (v,))
+    if v and restart:
+        raise ValueError("restart intervals are not combined with progressive output")
+    return bool(v)
+
+
+def emit_jpeg(plan, du, optimize=False, restart_mcus=None, progressive=False):
     """mjw_emit: headers + Huffman stage over given data units -> bytes.  optimize: mjw_emit_optimized, the same stream with Huffman
     tables built from the units' own symbol statistics.  restart_mcus: mjw_emit_restart, a restart interval of that many MCUs (None or
-    0: none, the calls above); None for an interval outside 0..65535."""
+    0: none, the calls above); None for an interval outside 0..65535.  progressive: mjw_emit_progressive (a WritePlan) or
+    mjw_temit_progressive (a TranscodePlan), the multi-scan stream (include/mij_host.h, PROGRESSIVE STREAMS); its tables are always the
+    optimal ones, and it takes no restart interval (ValueError)."""
     L = lib()
     ri = _restart_mcus(restart_mcus)
     chunks = []
     cb = _WRITE_CB(lambda _c, data, size: chunks.append(C.string_at(data, size)))
     d = np.ascontiguousarray(du, dtype=np.int16)
+    if _progressive_flag(progressive, ri):
+        if d.size != plan.du_elems():
+            raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, plan.du_elems()))
+        t = isinstance(plan, TranscodePlan)
+        fn = L.mjw_temit_progressive if t else L.mjw_emit_progressive
+        fn.argtypes = [C.POINTER(TranscodePlan if t else WritePlan), C.c_void_p, _WRITE_CB, C.c_void_p]
+        return b"".join(chunks) if fn(C.byref(plan), d.ctypes.data_as(C.c_void_p), cb, None) else None
     if ri:
         L.mjw_emit_restart.argtypes = [C.POINTER(WritePlan), C.c_void_p, C.c_uint, C.c_int, _WRITE_CB, C.c_void_p]
         ok = L.mjw_emit_restart(C.byref(plan), d.ctypes.data_as(C.c_void_p), MJW_OPTIMIZE_HUFFMAN if optimize else 0, ri, cb, None)
@@ -1333,10 +1351,29 @@ def units_codable(tplan, du, restart_mcus=None):
     return bool(ok), (None if ok else why.value.decode())
 
 
-def emit_transcoded(tplan, du, optimize=False, restart_mcus=None):
-    """mjw_temit / mjw_temit_optimized over given units -> bytes, None when the units are not codable.  restart_mcus: mjw_temit_restart."""
+class ProgressiveStats(C.Structure):
+    """mjw_progressive_stats (include/mij_host.h)."""
+    _fields_ = [("forced_run_flushes", C.c_uint32), ("forced_bit_flushes", C.c_uint32), ("longest_run", C.c_uint32), ("most_pending_bits", C.c_uint32)]
+
+
+def progressive_stats(tplan, du):
+    """mjw_tprogressive_stats: what the progressive writer meets in these units -> ProgressiveStats, None when refused"""
+    L = lib()
+    d = np.ascontiguousarray(du, np.int16)
+    if d.size != tplan.du_elems():
+        raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, tplan.du_elems()))
+    L.mjw_tprogressive_stats.argtypes = [C.POINTER(TranscodePlan), C.c_void_p, C.POINTER(ProgressiveStats)]
+    st = ProgressiveStats()
+    return st if L.mjw_tprogressive_stats(C.byref(tplan), d.ctypes.data_as(C.c_void_p), C.byref(st)) else None
+
+
+def emit_transcoded(tplan, du, optimize=False, restart_mcus=None, progressive=False):
+    """mjw_temit / mjw_temit_optimized over given units -> bytes, None when the units are not codable.  restart_mcus: mjw_temit_restart.
+    progressive: mjw_temit_progressive (no restart interval with it: ValueError)."""
     L = lib()
     ri = _restart_mcus(restart_mcus)
+    if _progressive_flag(progressive, ri):
+        return emit_jpeg(tplan, du, progressive=True)
     d = np.ascontiguousarray(du, np.int16)
     if d.size != tplan.du_elems():
         raise ValueError("%d data-unit elements for a picture that has %d" % (d.size, tplan.du_elems()))
@@ -1454,19 +1491,29 @@ def units_requant(src, dst, du):
 
 
 def transcode_memory(data, optimize=False, copy_markers=False, orientation=None, trim=False, tables=None, coarsen_only=True, crop=None,
-                     grey=False, restart_rows=None, restart_mcus=None):
+                     grey=False, restart_rows=None, restart_mcus=None, progressive=False):
     """mjh_transcode_memory, the lossless transcode on the host alone -> (bytes, None) or (None, reason).  With an orientation
     (1..8, or "exif" for the file's own tag) it is mjh_transcode_memory_oriented; trim chooses its edge mode.  With tables = (luma,
     chroma) it is mjh_transcode_memory_requant: the coefficients requantised after the orientation.  With crop = (x0, y0, w, h) in the
     displayed frame and / or grey=True it is mjh_transcode_memory_window: grey -> orient -> crop -> requantise.  With restart_rows or
     restart_mcus (an interval in MCU rows or MCUs of the destination; both given, negative or above 65535 MCUs: refused with a reason) it
-    is mjh_transcode_memory_restart_by."""
+    is mjh_transcode_memory_restart_by.  With progressive=True it is mjh_transcode_memory_progressive: the same chain, written as a
+    progressive stream; a restart interval with it is a ValueError."""
     L = lib()
     data = bytes(data)
     out, n, why = C.c_void_p(), C.c_size_t(), C.c_char_p()
     flags = (MJW_OPTIMIZE_HUFFMAN if optimize else 0) | (MJW_COPY_MARKERS if copy_markers else 0)
     rows, mcus = (min(max(_restart_mcus(v), -1), 1 << 30) for v in (restart_rows, restart_mcus))
-    if rows or mcus:
+    if _progressive_flag(progressive, rows or mcus):
+        luma, chroma = (None, None) if tables is None else _qtable_pair(tables)
+        win = None if crop is None else (C.c_int * 4)(*[int(v) for v in crop])
+        L.mjh_transcode_memory_progressive.argtypes = [C.c_char_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_char_p,
+                                                       C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                       C.POINTER(C.c_int), C.POINTER(C.c_char_p)]
+        o = 1 if orientation is None else 0 if orientation == "exif" else int(orientation)
+        ok = L.mjh_transcode_memory_progressive(data, len(data), flags, o, int(bool(trim)), win, int(bool(grey)), luma, chroma,
+                                                int(bool(coarsen_only)), 1, C.byref(out), C.byref(n), None, C.byref(why))
+    elif rows or mcus:
         luma, chroma = (None, None) if tables is None else _qtable_pair(tables)
         win = None if crop is None else (C.c_int * 4)(*[int(v) for v in crop])
         L.mjh_transcode_memory_restart_by.argtypes = [C.c_char_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_char_p,
@@ -1850,10 +1897,11 @@ class Encoder:
         return t
 
     def slot_status(self, slot):
-        """mij_enc_slot_status, after fetch_streams -> "ok", "no room" (finish it on the host from its units) or "uncodable" """
+        """mij_enc_slot_status, after fetch_streams -> "ok", "no room" (finish it on the host from its units), "uncodable" or "host flush"
+        (a progressive slot with a forced EOB-run flush or a table that cannot be built: the host finishes it too)"""
         L = lib()
         L.mij_enc_slot_status.argtypes = [C.c_void_p, C.c_int]
-        return ("ok", "no room", "uncodable")[_check(L.mij_enc_slot_status(self._h, int(slot)), "mij_enc_slot_status")]
+        return ("ok", "no room", "uncodable", "host flush")[_check(L.mij_enc_slot_status(self._h, int(slot)), "mij_enc_slot_status")]
 
     def coef_ms(self):
         """ms the conversion kernels (planes -> units) of the last upload took, None when there were none"""
@@ -1874,6 +1922,19 @@ class Encoder:
         L = lib()
         L.mij_enc_set_restart.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _check(L.mij_enc_set_restart(self._h, int(slot), _restart_mcus(restart_mcus)), "mij_enc_set_restart")
+
+    def set_progressive(self, slot, on=True):
+        """mij_enc_set_progressive: the slot's stream is written as a progressive stream (include/mij_host.h, PROGRESSIVE STREAMS); before
+        upload.  MijError for a slot with a restart interval."""
+        L = lib()
+        L.mij_enc_set_progressive.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        _check(L.mij_enc_set_progressive(self._h, int(slot), int(bool(on))), "mij_enc_set_progressive")
+
+    def slot_progressive(self, slot):
+        """mij_enc_slot_progressive: whether progressive output was asked for the slot"""
+        L = lib()
+        L.mij_enc_slot_progressive.argtypes = [C.c_void_p, C.c_int]
+        return bool(_check(L.mij_enc_slot_progressive(self._h, int(slot)), "mij_enc_slot_progressive"))
 
     def slot_restart(self, slot):
         """mij_enc_slot_restart: the slot's restart interval in MCUs, 0 when it has none"""

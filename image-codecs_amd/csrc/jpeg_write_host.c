@@ -750,17 +750,14 @@ int mjw_emit_optimized(const mjw_plan *p, const int16_t *du, mjw_write_func *fun
 static int tplan_ny(const mjw_tplan *t) { return t->ncomp == 1 ? 1 : t->lh * t->lv; }
 size_t mjw_tplan_du_count(const mjw_tplan *t) { return t ? mjw_plan_du_count(&t->plan) : 0; }
 
-/* SOI .. SOS with the four tables given as BITS (16 counts) and HUFFVAL, indexed luma DC, chroma DC, luma AC, chroma AC; a grey picture
- * carries one quantisation table, one component and the two luma tables */
-static size_t theader_tables(const mjw_tplan *t, const unsigned char *const bits[4], const unsigned char *const vals[4], unsigned char *out)
+/* SOI, APP0, DQT and the frame header under marker `sof` (0xC0 baseline, 0xC2 progressive); a grey picture carries one quantisation table
+ * and one component */
+static size_t theader_frame(const mjw_tplan *t, int sof, unsigned char *out)
 {
 	static const unsigned char soi_app0[] = {0xFF, 0xD8, 0xFF, 0xE0, 0, 0x10, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
-	static const unsigned char ids[4] = {0x00, 0x10, 0x01, 0x11};
-	static const int order[4] = {0, 2, 1, 3};
-	const int grey = t->ncomp == 1, ntab = grey ? 2 : 4;
+	const int grey = t->ncomp == 1;
 	const mjw_plan *p = &t->plan;
-	unsigned char *o = out, *dht_len;
-	int k, i, n;
+	unsigned char *o = out;
 #define PUT(src, n) (memcpy(o, (src), (n)), o += (n))
 	PUT(soi_app0, sizeof(soi_app0));
 	*o++ = 0xFF, *o++ = 0xDB, *o++ = 0, *o++ = (unsigned char)(grey ? 0x43 : 0x84), *o++ = 0;
@@ -769,7 +766,7 @@ static size_t theader_tables(const mjw_tplan *t, const unsigned char *const bits
 		*o++ = 1;
 		PUT(p->ctab, 64);
 	}
-	*o++ = 0xFF, *o++ = 0xC0, *o++ = 0, *o++ = (unsigned char)(grey ? 0x0B : 0x11), *o++ = 8;
+	*o++ = 0xFF, *o++ = (unsigned char)sof, *o++ = 0, *o++ = (unsigned char)(grey ? 0x0B : 0x11), *o++ = 8;
 	*o++ = (unsigned char)(p->height >> 8), *o++ = (unsigned char)(p->height & 0xff);
 	*o++ = (unsigned char)(p->width >> 8), *o++ = (unsigned char)(p->width & 0xff);
 	*o++ = (unsigned char)t->ncomp;
@@ -778,6 +775,20 @@ static size_t theader_tables(const mjw_tplan *t, const unsigned char *const bits
 		*o++ = 2, *o++ = 0x11, *o++ = 1;
 		*o++ = 3, *o++ = 0x11, *o++ = 1;
 	}
+#undef PUT
+	return (size_t)(o - out);
+}
+
+/* SOI .. SOS with the four tables given as BITS (16 counts) and HUFFVAL, indexed luma DC, chroma DC, luma AC, chroma AC; a grey picture
+ * carries only the two luma tables */
+static size_t theader_tables(const mjw_tplan *t, const unsigned char *const bits[4], const unsigned char *const vals[4], unsigned char *out)
+{
+	static const unsigned char ids[4] = {0x00, 0x10, 0x01, 0x11};
+	static const int order[4] = {0, 2, 1, 3};
+	const int grey = t->ncomp == 1, ntab = grey ? 2 : 4;
+	unsigned char *o = out + theader_frame(t, 0xC0, out), *dht_len;
+	int k, i, n;
+#define PUT(src, n) (memcpy(o, (src), (n)), o += (n))
 	*o++ = 0xFF, *o++ = 0xC4;
 	dht_len = o;
 	o += 2;
@@ -1100,6 +1111,320 @@ size_t mjw_temit_restart_to_memory(const mjw_tplan *t, const int16_t *du, unsign
 {
 	mem_sink m = {out, cap, 0, 0};
 	if (!out || !mjw_temit_restart(t, du, flags, ri, mem_sink_write, &m) || m.overflow)
+		return 0;
+	return m.len;
+}
+
+/* ---- progressive streams (include/mij_host.h, PROGRESSIVE STREAMS): the units coded scan after scan in libjpeg's jpeg_simple_progression
+ * script, each scan under the optimal tables of its own symbol counts.  Every scan is walked twice: once counting, once writing. */
+
+typedef struct {
+	unsigned char ncomp, comp[3], ss, se, ah, al; /* comp: 0 luma, 1 Cb, 2 Cr */
+} pg_scan;
+static const pg_scan k_pg_colour[MJW_PROGRESSIVE_SCANS_COLOUR] = {
+	{3, {0, 1, 2}, 0, 0, 0, 1}, {1, {0, 0, 0}, 1, 5, 0, 2},  {1, {2, 0, 0}, 1, 63, 0, 1}, {1, {1, 0, 0}, 1, 63, 0, 1}, {1, {0, 0, 0}, 6, 63, 0, 2},
+	{1, {0, 0, 0}, 1, 63, 2, 1}, {3, {0, 1, 2}, 0, 0, 1, 0}, {1, {2, 0, 0}, 1, 63, 1, 0}, {1, {1, 0, 0}, 1, 63, 1, 0}, {1, {0, 0, 0}, 1, 63, 1, 0}};
+static const pg_scan k_pg_grey[MJW_PROGRESSIVE_SCANS_GREY] = {{1, {0, 0, 0}, 0, 0, 0, 1}, {1, {0, 0, 0}, 1, 5, 0, 2},  {1, {0, 0, 0}, 6, 63, 0, 2},
+																				  {1, {0, 0, 0}, 1, 63, 2, 1}, {1, {0, 0, 0}, 0, 0, 1, 0}, {1, {0, 0, 0}, 1, 63, 1, 0}};
+
+typedef struct {
+	jw_sink *s;          /* NULL while the scan's symbols are only counted */
+	uint32_t *freq;      /* the table that counts / codes the next symbol */
+	const enc_table *tb;
+	unsigned eobrun, be; /* blocks of the pending end-of-band run; correction bits buffered behind it */
+	unsigned char corr[MJW_PROGRESSIVE_MAX_CORR_BITS];
+	mjw_progressive_stats *st;
+} pg_state;
+
+static inline void pg_symbol(pg_state *g, int sym)
+{
+	if (g->s)
+		put_bits(g->s, g->tb->code[sym], g->tb->len[sym]);
+	else
+		++g->freq[sym];
+}
+static inline void pg_bits(pg_state *g, unsigned v, int n)
+{
+	if (g->s && n)
+		put_bits(g->s, v & ((1u << n) - 1u), n);
+}
+static void pg_buffered(pg_state *g, const unsigned char *b, unsigned n)
+{
+	unsigned i;
+	if (g->s)
+		for (i = 0; i < n; ++i)
+			put_bits(g->s, b[i], 1);
+}
+/* the pending run leaves: EOBn, the run's low n bits, then the correction bits that waited for it (jcphuff.c, emit_eobrun) */
+static void pg_eobrun(pg_state *g)
+{
+	if (g->eobrun) {
+		const int n = 31 - __builtin_clz(g->eobrun);
+		if (g->st) {
+			if (g->eobrun > g->st->longest_run)
+				g->st->longest_run = g->eobrun;
+			if (g->be > g->st->most_pending_bits)
+				g->st->most_pending_bits = g->be;
+		}
+		pg_symbol(g, n << 4);
+		pg_bits(g, g->eobrun, n);
+		g->eobrun = 0;
+		pg_buffered(g, g->corr, g->be);
+		g->be = 0;
+	}
+}
+
+/* AC first scan of one block (encode_mcu_AC_first): magnitudes shifted towards zero */
+static void pg_ac_first(pg_state *g, const int16_t *blk, int ss, int se, int al)
+{
+	int k, r = 0;
+	for (k = ss; k <= se; ++k) {
+		const int v = blk[k];
+		const unsigned a = (unsigned)(v < 0 ? -v : v) >> al;
+		int n;
+		if (!a) {
+			++r;
+			continue;
+		}
+		pg_eobrun(g);
+		for (; r > 15; r -= 16)
+			pg_symbol(g, 0xF0);
+		n = 32 - __builtin_clz(a);
+		pg_symbol(g, (r << 4) + n);
+		pg_bits(g, v < 0 ? ~a : a, n);
+		r = 0;
+	}
+	if (r > 0) {
+		if (++g->eobrun == 0x7FFF) {
+			if (g->st && !g->s)
+				++g->st->forced_run_flushes;
+			pg_eobrun(g);
+		}
+	}
+}
+
+/* AC refinement scan of one block (encode_mcu_AC_refine) */
+static void pg_ac_refine(pg_state *g, const int16_t *blk, int ss, int se, int al)
+{
+	unsigned char absv[64], *br_buf = g->corr + g->be;
+	unsigned br = 0;
+	int k, r = 0, eob = 0;
+	for (k = ss; k <= se; ++k) {
+		const unsigned a = (unsigned)(blk[k] < 0 ? -blk[k] : blk[k]) >> al;
+		absv[k] = (unsigned char)(a > 2 ? 2 | (a & 1) : a); /* all that is asked of it: zero, one, larger, and its low bit */
+		if (a == 1)
+			eob = k; /* the last newly non-zero coefficient */
+	}
+	for (k = ss; k <= se; ++k) {
+		const unsigned a = absv[k];
+		if (!a) {
+			++r;
+			continue;
+		}
+		while (r > 15 && k <= eob) { /* a ZRL is only worth writing in front of a newly non-zero coefficient */
+			pg_eobrun(g);
+			pg_symbol(g, 0xF0);
+			r -= 16;
+			pg_buffered(g, br_buf, br); /* the correction bits the sixteen zeros skipped over */
+			br_buf = g->corr;
+			br = 0;
+		}
+		if (a > 1) { /* already non-zero: one correction bit, behind the next symbol */
+			br_buf[br++] = (unsigned char)(a & 1);
+			continue;
+		}
+		pg_eobrun(g);
+		pg_symbol(g, (r << 4) + 1);
+		pg_bits(g, blk[k] < 0 ? 0 : 1, 1);
+		pg_buffered(g, br_buf, br);
+		br_buf = g->corr;
+		br = 0;
+		r = 0;
+	}
+	if (r > 0 || br > 0) { /* the block's trailing correction bits join the run's */
+		++g->eobrun;
+		g->be += br;
+		if (g->eobrun == 0x7FFF || g->be > MJW_PROGRESSIVE_MAX_CORR_BITS - 64 + 1) {
+			if (g->st && !g->s)
+				++*(g->eobrun == 0x7FFF ? &g->st->forced_run_flushes : &g->st->forced_bit_flushes);
+			pg_eobrun(g);
+		}
+	}
+}
+
+/* one scan over the units: DC scans MCU after MCU with every unit of the MCU, AC scans over the component's own ceil(w / 8) x ceil(h / 8)
+ * blocks in raster order.  freq / tb: the scan's table 0 and, in the colour DC scan, the chroma table 1. */
+static void pg_run_scan(pg_state *g, const mjw_tplan *t, const pg_scan *sc, const int16_t *du, uint32_t freq[2][256], const enc_table tb[2])
+{
+	const int ny = tplan_ny(t), dpm = t->plan.du_per_mcu;
+	g->eobrun = g->be = 0;
+	if (sc->ss == 0) {
+		const size_t nm = (size_t)t->plan.mcu_x * (size_t)t->plan.mcu_y;
+		int pred[3] = {0, 0, 0}, p;
+		size_t m;
+		for (m = 0; m < nm; ++m)
+			for (p = 0; p < dpm; ++p, du += 64) {
+				const int c = p < ny ? 0 : p - ny + 1;
+				if (sc->ah) {
+					pg_bits(g, (unsigned)(du[0] >> sc->al) & 1u, 1);
+				} else {
+					const int v = du[0] >> sc->al, diff = v - pred[c]; /* the shift is arithmetic: -1 >> 1 is -1 */
+					unsigned bits = 0;
+					int nbits = 0;
+					pred[c] = v;
+					if (diff)
+						magnitude_bits(diff, &bits, &nbits);
+					g->freq = freq[c ? 1 : 0];
+					g->tb = &tb[c ? 1 : 0];
+					pg_symbol(g, nbits);
+					pg_bits(g, bits, nbits);
+				}
+			}
+	} else {
+		const int c = sc->comp[0], h = c ? 1 : t->lh, v = c ? 1 : t->lv, off = c ? ny + c - 1 : 0;
+		const int bw = c || t->ncomp == 1 ? t->plan.mcu_x : (t->plan.width + 7) / 8, bh = c || t->ncomp == 1 ? t->plan.mcu_y : (t->plan.height + 7) / 8;
+		const int hh = t->ncomp == 1 ? 1 : h, vv = t->ncomp == 1 ? 1 : v;
+		int bx, by;
+		g->freq = freq[0];
+		g->tb = &tb[0];
+		for (by = 0; by < bh; ++by)
+			for (bx = 0; bx < bw; ++bx) {
+				const int16_t *blk =
+					du + 64 * (((size_t)(by / vv) * (size_t)t->plan.mcu_x + (size_t)(bx / hh)) * (size_t)dpm + (size_t)(off + (c ? 0 : (by % vv) * hh + bx % hh)));
+				if (sc->ah)
+					pg_ac_refine(g, blk, sc->ss, sc->se, sc->al);
+				else
+					pg_ac_first(g, blk, sc->ss, sc->se, sc->al);
+			}
+		pg_eobrun(g);
+	}
+}
+
+static void pg_put_dht(jw_sink *s, int id, const uint8_t bits[16], const uint8_t *vals, int n)
+{
+	const unsigned char head[5] = {0xFF, 0xC4, (unsigned char)((19 + n) >> 8), (unsigned char)((19 + n) & 0xff), (unsigned char)id};
+	sink_bytes(s, head, 5);
+	sink_bytes(s, bits, 16);
+	sink_bytes(s, vals, n);
+}
+
+static int plan_shape_ok(const mjw_tplan *t)
+{
+	return t && (t->ncomp == 1 || t->ncomp == 3) && t->plan.mcu_x > 0 && t->plan.mcu_y > 0 && t->plan.width > 0 && t->plan.height > 0 &&
+			 (t->ncomp == 1 ? t->plan.du_per_mcu == 1 : (t->lh >= 1 && t->lh <= 2 && t->lv >= 1 && t->lv <= 2 && t->plan.du_per_mcu == t->lh * t->lv + 2)) &&
+			 mjw_tplan_du_count(t) <= (size_t)(UINT32_MAX / 64);
+}
+
+static int emit_progressive(const mjw_tplan *t, const int16_t *du, mjw_write_func *func, void *context, mjw_progressive_stats *st)
+{
+	const pg_scan *script = t->ncomp == 1 ? k_pg_grey : k_pg_colour;
+	const int nscan = t->ncomp == 1 ? MJW_PROGRESSIVE_SCANS_GREY : MJW_PROGRESSIVE_SCANS_COLOUR;
+	unsigned char hdr[MJW_HEADER_BYTES];
+	jw_sink *s = NULL;
+	pg_state *g = (pg_state *)calloc(1, sizeof(*g));
+	int i, k, ok = 0;
+	if (!g)
+		return 0;
+	if (st)
+		memset(st, 0, sizeof(*st));
+	g->st = st;
+	if (func) {
+		s = (jw_sink *)calloc(1, sizeof(*s));
+		if (!s)
+			goto done;
+		s->func = func;
+		s->context = context;
+		sink_bytes(s, hdr, (int)theader_frame(t, 0xC2, hdr));
+	}
+	for (i = 0; i < nscan; ++i) {
+		const pg_scan *sc = &script[i];
+		const int ntab = sc->ss == 0 ? (sc->ah ? 0 : (t->ncomp == 3 ? 2 : 1)) : 1;
+		uint32_t freq[2][256];
+		uint8_t bits[2][16], vals[2][256];
+		unsigned char b17[17];
+		enc_table tb[2];
+		int n[2] = {0, 0};
+		memset(freq, 0, sizeof(freq));
+		g->s = NULL;
+		pg_run_scan(g, t, sc, du, freq, tb);
+		for (k = 0; k < ntab; ++k) {
+			if (!mjw_optimal_table(freq[k], bits[k], vals[k], &n[k]))
+				goto done; /* a code longer than 32 bits before limiting: no plain table knows the EOBn symbols */
+			b17[0] = 0;
+			memcpy(b17 + 1, bits[k], 16);
+			make_enc_table(&tb[k], b17, vals[k]);
+		}
+		if (!s)
+			continue;
+		/* the scan's tables, each in a DHT segment of its own; AC tables: luma id 0, chroma id 1 */
+		for (k = 0; k < ntab; ++k)
+			pg_put_dht(s, sc->ss == 0 ? k : 0x10 | (sc->comp[0] ? 1 : 0), bits[k], vals[k], n[k]);
+		sink_byte(s, 0xFF), sink_byte(s, 0xDA), sink_byte(s, 0), sink_byte(s, (unsigned char)(6 + 2 * sc->ncomp)), sink_byte(s, sc->ncomp);
+		for (k = 0; k < sc->ncomp; ++k) {
+			const int c = sc->comp[k], tbl = c ? 1 : 0;
+			sink_byte(s, (unsigned char)(c + 1));
+			sink_byte(s, (unsigned char)(sc->ss ? tbl : (sc->ah ? 0 : tbl << 4))); /* Td only in the first DC scan, Ta only in AC scans */
+		}
+		sink_byte(s, sc->ss), sink_byte(s, sc->se), sink_byte(s, (unsigned char)(sc->ah << 4 | sc->al));
+		s->acc = 0;
+		s->nacc = 0;
+		g->s = s;
+		pg_run_scan(g, t, sc, du, freq, tb);
+		put_bits(s, 0x7F, 7); /* every scan ends as the baseline scan does */
+		put_bits_finish(s);
+	}
+	if (s) {
+		sink_byte(s, 0xFF);
+		sink_byte(s, 0xD9);
+		sink_flush(s);
+	}
+	ok = 1;
+done:
+	free(s);
+	free(g);
+	return ok;
+}
+
+size_t mjw_tframe_progressive(const mjw_tplan *t, unsigned char *out) { return plan_shape_ok(t) && out ? theader_frame(t, 0xC2, out) : 0; }
+
+static void tplan_of_plan(mjw_tplan *t, const mjw_plan *p)
+{
+	t->plan = *p;
+	t->ncomp = 3;
+	t->lh = t->lv = p->subsample ? 2 : 1;
+}
+
+int mjw_temit_progressive(const mjw_tplan *t, const int16_t *du, mjw_write_func *func, void *context)
+{
+	if (!plan_shape_ok(t) || !du || !func || !mjw_tunits_codable(t, du, NULL))
+		return 0;
+	return emit_progressive(t, du, func, context, NULL);
+}
+int mjw_emit_progressive(const mjw_plan *p, const int16_t *du, mjw_write_func *func, void *context)
+{
+	mjw_tplan t;
+	if (!p)
+		return 0;
+	tplan_of_plan(&t, p);
+	return mjw_temit_progressive(&t, du, func, context);
+}
+int mjw_tprogressive_stats(const mjw_tplan *t, const int16_t *du, mjw_progressive_stats *st)
+{
+	if (!plan_shape_ok(t) || !du || !st || !mjw_tunits_codable(t, du, NULL))
+		return 0;
+	return emit_progressive(t, du, NULL, NULL, st);
+}
+size_t mjw_temit_progressive_to_memory(const mjw_tplan *t, const int16_t *du, unsigned char *out, size_t cap)
+{
+	mem_sink m = {out, cap, 0, 0};
+	if (!out || !mjw_temit_progressive(t, du, mem_sink_write, &m) || m.overflow)
+		return 0;
+	return m.len;
+}
+size_t mjw_emit_progressive_to_memory(const mjw_plan *p, const int16_t *du, unsigned char *out, size_t cap)
+{
+	mem_sink m = {out, cap, 0, 0};
+	if (!out || !mjw_emit_progressive(p, du, mem_sink_write, &m) || m.overflow)
 		return 0;
 	return m.len;
 }

@@ -37,6 +37,14 @@
  *                  shortening keeps table 0 (the plain tables) and the plain header
  * The tile kernels read the tables their EmitTile.tab names -- in the tile's own entry, so that the copy of the tables into LDS waits
  * for that entry alone and not for the slot's as well -- and the header length EmitSlot.hlen.
+ *
+ * Progressive output (mij_enc_set_progressive; the contract is include/mij_host.h, PROGRESSIVE STREAMS): mij_progressive_kernels.h.  A scan is
+ * a segment as a restart interval is, so the six launches write such a slot too: the tile kernels branch once per tile on EmitSlot.prog
+ * (prog_tile_setup, prog_blocks, prog_pack_tile in place of emit_units / emit_pack_tile), k_emit_scan restarts the offsets behind every scan,
+ * k_emit_stuff adds the next scan's header where it adds a marker, and -- a progressive tile can hold less than a byte, even nothing -- also
+ * carries each tile's partial byte across such tiles (ProgArgs.ctail), which k_emit_write completes the next byte from.  Four launches in
+ * front (k_prog_flags, k_prog_runs, k_prog_hist, k_prog_build), none without a progressive slot.  A slot without the request takes the
+ * branches it took before.
  */
 #pragma once
 
@@ -57,7 +65,7 @@ struct EmitSlot {
 	uint32_t first_tile, n_tiles;
 	uint32_t hdr, tab; /* header of the slot: hdrs + hdr * MIJ_EMIT_HDR; tab > 0: optimised, its tables are entry tab, its counts tab - 1 */
 	uint32_t hlen, ny; /* the header's length: what the upload wrote, or what k_emit_build wrote; luma units per MCU (1, 2 or 4): unit p of an MCU is luma when p < ny */
-	uint32_t ri, pad;  /* the restart interval in MCUs (mij_enc_set_restart), 0: none */
+	uint32_t ri, prog; /* the restart interval in MCUs (mij_enc_set_restart), 0: none; prog > 0: a progressive slot (mij_enc_set_progressive), ProgSlot prog - 1 */
 };
 
 struct EmitTile {
@@ -69,6 +77,8 @@ struct EmitTile {
  * MIJ_TILE_STARTS when the tile's first MCU is the first of an interval or of the slot (its units predict from 0); MIJ_TILE_FILLS when its last
  * unit is the last of an interval or of the slot (the 7 fill bits follow it).  A slot without an interval has STARTS on its first tile, FILLS on
  * its last and never ENDS.  The kernels take what depends on the interval from these flags: no division by it anywhere. */
+/* A progressive slot's tiles (mij_progressive_kernels.h) also carry their scan in bits 16-19; a scan is a segment as an interval is: ENDS on the
+ * last tile of a scan that another follows, whose header then stands where the marker would. */
 #define MIJ_TILE_ENDS 0x200u
 #define MIJ_TILE_STARTS 0x2000u
 #define MIJ_TILE_FILLS 0x4000u
@@ -259,6 +269,18 @@ __device__ __forceinline__ void lds_put(uint32_t *buf, uint32_t pos, uint32_t co
 }
 __device__ __forceinline__ uint32_t lds_byte(const uint32_t *buf, uint32_t j) { return (buf[j >> 2] >> (24 - 8 * (j & 3u))) & 0xFFu; }
 
+#include "mij_progressive_kernels.h"
+
+/* what the tile kernels need of a launch's progressive slots: all NULL without one */
+struct ProgArgs {
+	const ProgSlot *slots;
+	const uint8_t *fl;      /* k_prog_flags' block bytes */
+	const ProgAfter *after; /* k_prog_runs' per-tile results */
+	const uint8_t *hdr;     /* scan headers behind the first: entry (prog - 1) * MIJ_PROG_SCANS + scan, MIJ_PROG_HDR bytes each */
+	const uint32_t *hlen;   /* their lengths */
+	uint32_t *ctail;        /* per tile: the partial byte behind it, bits of earlier tiles included (k_emit_stuff) */
+};
+
 /* Packs tile tl's bits into buf from bit h on (buf zeroed here; nwords of it are used).  uoff: MIJ_EMIT_TILE + 1 words of LDS. */
 __device__ void emit_pack_tile(const EmitTables *__restrict__ T, const EmitSlot &s, const EmitTile &tl, const int16_t *__restrict__ du, uint32_t h,
 										 uint32_t nwords, uint32_t *buf, uint32_t *uoff)
@@ -294,17 +316,25 @@ __device__ void emit_pack_tile(const EmitTables *__restrict__ T, const EmitSlot 
 }
 
 __global__ __launch_bounds__(256) void k_emit_len(const EmitSlot *__restrict__ slots, const EmitTile *__restrict__ tiles,
-																  const EmitTables *__restrict__ T, const uint8_t *__restrict__ du_base, uint32_t *__restrict__ t_bits)
+																  const EmitTables *__restrict__ T, const uint8_t *__restrict__ du_base, uint32_t *__restrict__ t_bits, ProgArgs pa)
 {
 	__shared__ uint32_t part[4];
 	__shared__ EmitTables tab;
+	__shared__ ProgLds pl;
 	const EmitTile tl = tiles[blockIdx.x];
 	const EmitSlot s = slots[tl.slot];
 	const int16_t *du = reinterpret_cast<const int16_t *>(du_base + s.du_off);
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	emit_tables_to_lds(T + tl.tab, &tab);
 	uint32_t acc = 0;
-	emit_units(&tab, s, tl, du, [&](uint32_t, const LaneBits &L) { acc += wave_sum((uint32_t)L.total()); });
+	if (s.prog) {
+		const ProgSlot &ps = pa.slots[s.prog - 1u];
+		const ProgScanDef sc = k_prog_script[ps.grey][prog_tile_scan(tl)];
+		prog_tile_setup(ps, s, tl, blockIdx.x, sc, pa.fl, pa.after, nullptr, &pl);
+		prog_blocks<false>(&tab, nullptr, s, tl, sc, du, &pl, [](uint32_t, uint32_t, uint32_t, int) {}, [&](uint32_t, uint32_t bits) { acc += bits; });
+	} else {
+		emit_units(&tab, s, tl, du, [&](uint32_t, const LaneBits &L) { acc += wave_sum((uint32_t)L.total()); });
+	}
 	if (lane == 0)
 		part[wave] = acc;
 	__syncthreads();
@@ -341,7 +371,7 @@ __global__ __launch_bounds__(256) void k_emit_scan(const EmitSlot *__restrict__ 
 		const uint32_t incl = wave_incl_scan(v, lane);
 		const uint64_t excl = base + incl - v;
 		uint64_t from = 0;
-		if (s.ri) { /* the same in every lane of the wave: a slot without an interval skips the tile flags and the second scan */
+		if (s.ri | s.prog) { /* the same in every lane of the wave: a slot without an interval or scans skips the tile flags and the second scan */
 			const bool starts = t > 0 && t < s.n_tiles && (tiles[s.first_tile + t - 1].pad & MIJ_TILE_ENDS) != 0;
 			from = wave_incl_max64(starts ? excl : seg, lane);
 		}
@@ -356,12 +386,13 @@ __global__ __launch_bounds__(256) void k_emit_scan(const EmitSlot *__restrict__ 
 __global__ __launch_bounds__(256) void k_emit_count(const EmitSlot *__restrict__ slots, const EmitTile *__restrict__ tiles,
 																	 const EmitTables *__restrict__ T, const uint8_t *__restrict__ du_base, const uint32_t *__restrict__ t_bits,
 																	 const uint64_t *__restrict__ t_boff, uint32_t *__restrict__ t_ff, uint32_t *__restrict__ t_frag,
-																	 const uint32_t *__restrict__ s_flag)
+																	 const uint32_t *__restrict__ s_flag, const uint32_t *__restrict__ p_flag, ProgArgs pa)
 {
 	__shared__ uint32_t buf[MIJ_EMIT_LDS_WORDS];
 	__shared__ uint32_t uoff[MIJ_EMIT_TILE + 1];
 	__shared__ uint32_t part[4];
 	__shared__ EmitTables tab;
+	__shared__ ProgLds pl;
 	const EmitTile tl = tiles[blockIdx.x];
 	const EmitSlot s = slots[tl.slot];
 	const uint64_t b0 = t_boff[blockIdx.x], b1 = b0 + t_bits[blockIdx.x];
@@ -369,7 +400,8 @@ __global__ __launch_bounds__(256) void k_emit_count(const EmitSlot *__restrict__
 	const uint32_t nwords = (uint32_t)((h + (b1 - b0) + 31) / 32);
 	/* units outside the writer's ranges: the slot is refused (k_emit_stuff) before anything is packed -- a coefficient slot the conversion
 	 * kernel flagged (s_flag, NULL when the launch has no such slot), or a tile longer than the ranges allow */
-	if ((s_flag && s_flag[tl.slot]) || nwords > MIJ_EMIT_LDS_WORDS - 1) {
+	/* a progressive slot with a forced flush or without a table (p_flag, NULL without a progressive slot) goes the same way */
+	if ((s_flag && s_flag[tl.slot]) || (p_flag && p_flag[tl.slot]) || nwords > MIJ_EMIT_LDS_WORDS - 1) {
 		if (threadIdx.x == 0) {
 			t_ff[blockIdx.x] = ~0u;
 			t_frag[blockIdx.x] = 0;
@@ -377,7 +409,14 @@ __global__ __launch_bounds__(256) void k_emit_count(const EmitSlot *__restrict__
 		return;
 	}
 	emit_tables_to_lds(T + tl.tab, &tab);
-	emit_pack_tile(&tab, s, tl, reinterpret_cast<const int16_t *>(du_base + s.du_off), h, nwords, buf, uoff);
+	if (s.prog) {
+		const ProgSlot &ps = pa.slots[s.prog - 1u];
+		const ProgScanDef sc = k_prog_script[ps.grey][prog_tile_scan(tl)];
+		prog_tile_setup(ps, s, tl, blockIdx.x, sc, pa.fl, pa.after, nullptr, &pl);
+		prog_pack_tile(&tab, s, tl, sc, reinterpret_cast<const int16_t *>(du_base + s.du_off), h, nwords, buf, uoff, &pl);
+	} else {
+		emit_pack_tile(&tab, s, tl, reinterpret_cast<const int16_t *>(du_base + s.du_off), h, nwords, buf, uoff);
+	}
 	uint32_t c = 0;
 	for (uint32_t j = (h ? 1u : 0u) + threadIdx.x; j < n_own; j += blockDim.x)
 		c += lds_byte(buf, j) == 0xFFu;
@@ -398,7 +437,7 @@ __global__ __launch_bounds__(256) void k_emit_count(const EmitSlot *__restrict__
 __global__ __launch_bounds__(256) void k_emit_stuff(const EmitSlot *__restrict__ slots, const EmitTile *__restrict__ tiles, uint32_t n_slots,
 																	 const uint32_t *__restrict__ t_bits,
 																	 const uint64_t *__restrict__ t_boff, const uint32_t *__restrict__ t_ff, const uint32_t *__restrict__ t_frag,
-																	 uint64_t *__restrict__ t_out, uint64_t *__restrict__ s_ent)
+																	 uint64_t *__restrict__ t_out, uint64_t *__restrict__ s_ent, ProgArgs pa)
 {
 	const int lane = threadIdx.x & 63;
 	const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -407,9 +446,40 @@ __global__ __launch_bounds__(256) void k_emit_stuff(const EmitSlot *__restrict__
 	const EmitSlot s = slots[i];
 	uint64_t base = 0;
 	bool bad = false;
+	uint32_t c_len = 0, c_val = 0; /* progressive: the partial byte the chunk before leaves */
 	for (uint32_t t0 = 0; t0 < s.n_tiles; t0 += 64) {
 		const uint32_t t = t0 + (uint32_t)lane, g = s.first_tile + t;
-		uint32_t v = 0;
+		uint32_t v = 0, prev_tail = 0;
+		if (s.prog) {
+			/* A progressive tile can hold less than a byte, even nothing (blocks inside an EOB run), so a byte can gather bits of many tiles.
+			 * The partial byte behind each tile, as a segmented scan: a tile that completes a byte, or starts a scan, starts afresh with its
+			 * own tail; any other appends its few bits to what came before.  Every lane runs every step. */
+			uint32_t rs = 1, ln = 0, vl = 0;
+			if (t < s.n_tiles && t_ff[g] != ~0u) {
+				const uint64_t b0 = t_boff[g], b1 = b0 + t_bits[g];
+				rs = (b1 >> 3) != (b0 >> 3) || (tiles[g].pad & MIJ_TILE_STARTS) ? 1u : 0u;
+				ln = rs ? (uint32_t)(b1 & 7u) : t_bits[g];
+				vl = t_frag[g] >> 8;
+			}
+			for (int o = 1; o < 64; o <<= 1) {
+				const uint32_t xs = __shfl_up(rs, o, 64), xl = __shfl_up(ln, o, 64), xv = __shfl_up(vl, o, 64);
+				if (lane >= o && !rs) {
+					vl |= xv << ln;
+					ln += xl;
+					rs = xs;
+				}
+			}
+			if (!rs) {
+				vl |= c_val << ln;
+				ln += c_len;
+			}
+			const uint32_t up = __shfl_up(vl, 1, 64);
+			prev_tail = lane ? up : c_val;
+			c_len = __shfl(ln, 63, 64);
+			c_val = __shfl(vl, 63, 64);
+			if (t < s.n_tiles)
+				pa.ctail[g] = vl & 0xFFu;
+		}
 		if (t < s.n_tiles) {
 			const uint64_t b0 = t_boff[g], b1 = b0 + t_bits[g];
 			const uint32_t h = (uint32_t)(b0 & 7u), ff = t_ff[g];
@@ -418,13 +488,16 @@ __global__ __launch_bounds__(256) void k_emit_stuff(const EmitSlot *__restrict__
 			} else {
 				v = (uint32_t)((b1 >> 3) - (b0 >> 3)) + ff;
 				if (h && t > 0) { /* the byte shared with the previous tile */
-					const uint32_t byte = ((t_frag[g - 1] >> 8) << (8 - h)) | (t_frag[g] & 0xFFu);
-					v += byte == 0xFFu;
+					const uint32_t byte = ((s.prog ? prev_tail : t_frag[g - 1] >> 8) << (8 - h)) | (t_frag[g] & 0xFFu);
+					v += byte == 0xFFu && (b1 >> 3) != (b0 >> 3);
 				}
 				/* the two marker bytes behind an interval end are added here, in byte space: they never pass through the stuffing.  The interval's
 				 * filled last byte is an ordinary whole byte of its tile and was counted as one (t_ff, or the shared byte above) */
 				if (s.ri && (tiles[g].pad & MIJ_TILE_ENDS))
 					v += 2u;
+				/* behind a scan's last tile: the header of the next scan */
+				if (s.prog && (tiles[g].pad & MIJ_TILE_ENDS))
+					v += pa.hlen[(s.prog - 1u) * MIJ_PROG_SCANS + prog_tile_scan(tiles[g]) + 1u];
 			}
 		}
 		const uint32_t incl = wave_incl_scan(v, lane);
@@ -492,22 +565,24 @@ __global__ __launch_bounds__(1024) void k_emit_place(const EmitSlot *__restrict_
 __global__ __launch_bounds__(256) void k_emit_write(const EmitSlot *__restrict__ slots, const EmitTile *__restrict__ tiles,
 																	 const EmitTables *__restrict__ T, const uint8_t *__restrict__ du_base, const uint8_t *__restrict__ hdrs,
 																	 const uint32_t *__restrict__ t_bits, const uint64_t *__restrict__ t_boff, const uint32_t *__restrict__ t_frag,
-																	 const uint64_t *__restrict__ t_out, const EmitResult *__restrict__ res, uint8_t *__restrict__ arena)
+																	 const uint64_t *__restrict__ t_out, const EmitResult *__restrict__ res, uint8_t *__restrict__ arena, ProgArgs pa)
 {
 	__shared__ uint32_t buf[MIJ_EMIT_LDS_WORDS];
 	__shared__ uint32_t uoff[MIJ_EMIT_TILE + 1];
 	__shared__ uint32_t part[4];
 	__shared__ EmitTables tab;
+	__shared__ ProgLds pl;
 	const EmitTile tl = tiles[blockIdx.x];
 	const EmitResult r = res[tl.slot];
 	if (r.off == ~0ull)
 		return;
 	const EmitSlot s = slots[tl.slot];
 	uint8_t *out = arena + r.off;
-	if (tl.first == 0)
+	if (tl.first == 0 && prog_tile_scan(tl) == 0) /* a progressive slot's later scans start at block 0 again */
 		for (uint32_t i = threadIdx.x; i < s.hlen; i += blockDim.x)
 			out[i] = hdrs[(size_t)s.hdr * MIJ_EMIT_HDR + i];
-	if (tl.first + emit_tile_units(tl) >= s.n_du && threadIdx.x == 0) {
+	const bool last_tile = s.prog ? (tl.pad & (MIJ_TILE_FILLS | MIJ_TILE_ENDS)) == MIJ_TILE_FILLS : tl.first + emit_tile_units(tl) >= s.n_du;
+	if (last_tile && threadIdx.x == 0) {
 		out[r.len - 2] = 0xFF;
 		out[r.len - 1] = 0xD9;
 	}
@@ -515,9 +590,16 @@ __global__ __launch_bounds__(256) void k_emit_write(const EmitSlot *__restrict__
 	const uint32_t h = (uint32_t)(b0 & 7u), n_own = (uint32_t)((b1 >> 3) - (b0 >> 3));
 	const uint32_t nwords = (uint32_t)((h + (b1 - b0) + 31) / 32);
 	emit_tables_to_lds(T + tl.tab, &tab);
-	emit_pack_tile(&tab, s, tl, reinterpret_cast<const int16_t *>(du_base + s.du_off), h, nwords, buf, uoff);
+	if (s.prog) {
+		const ProgSlot &ps = pa.slots[s.prog - 1u];
+		const ProgScanDef sc = k_prog_script[ps.grey][prog_tile_scan(tl)];
+		prog_tile_setup(ps, s, tl, blockIdx.x, sc, pa.fl, pa.after, nullptr, &pl);
+		prog_pack_tile(&tab, s, tl, sc, reinterpret_cast<const int16_t *>(du_base + s.du_off), h, nwords, buf, uoff, &pl);
+	} else {
+		emit_pack_tile(&tab, s, tl, reinterpret_cast<const int16_t *>(du_base + s.du_off), h, nwords, buf, uoff);
+	}
 	if (h && threadIdx.x == 0) /* the previous tile's tail completes the first byte */
-		buf[0] |= (t_frag[blockIdx.x - 1] >> 8) << (32 - h);
+		buf[0] |= (s.prog ? pa.ctail[blockIdx.x - 1] : t_frag[blockIdx.x - 1] >> 8) << (32 - h);
 	__syncthreads();
 	/* each thread a contiguous run of the tile's bytes; a block scan of the stuffed sizes places the runs */
 	const uint32_t per = (n_own + blockDim.x - 1) / blockDim.x;
@@ -540,7 +622,12 @@ __global__ __launch_bounds__(256) void k_emit_write(const EmitSlot *__restrict__
 		if (b == 0xFFu)
 			*o++ = 0;
 	}
-	if ((tl.pad & MIJ_TILE_ENDS) && threadIdx.x == 0) { /* the interval's marker, unstuffed, behind the tile's stuffed bytes */
+	if ((tl.pad & MIJ_TILE_ENDS) && s.prog) { /* the next scan's header behind the scan's stuffed bytes */
+		const uint32_t q = (s.prog - 1u) * MIJ_PROG_SCANS + prog_tile_scan(tl) + 1u;
+		uint8_t *m = out + s.hlen + t_out[blockIdx.x] + part[0] + part[1] + part[2] + part[3];
+		for (uint32_t i = threadIdx.x; i < pa.hlen[q]; i += blockDim.x)
+			m[i] = pa.hdr[(size_t)q * MIJ_PROG_HDR + i];
+	} else if ((tl.pad & MIJ_TILE_ENDS) && threadIdx.x == 0) { /* the interval's marker, unstuffed, behind the tile's stuffed bytes */
 		uint8_t *m = out + s.hlen + t_out[blockIdx.x] + part[0] + part[1] + part[2] + part[3];
 		m[0] = 0xFF;
 		m[1] = (uint8_t)(0xD0u + ((tl.pad >> 10) & 7u));
@@ -605,26 +692,19 @@ __device__ __forceinline__ uint64_t wave_min64(uint64_t v)
 	return v;
 }
 
-/* One workgroup per optimised slot k (slot opt_slots[k], counts freq[k], tables tabs[k + 1]), wave t builds table t by ITU-T T.81 K.2 as
- * libjpeg's jpeg_gen_optimal_table does (mjw_optimal_table, csrc/jpeg_write_host.c, is the same procedure on the host).  Lane l holds
+/* Wave t of a workgroup of four builds table t from its 256 counts f by ITU-T T.81 K.2 as libjpeg's jpeg_gen_optimal_table does
+ * (mjw_optimal_table, csrc/jpeg_write_host.c, is the same procedure on the host); k_emit_build and k_prog_build share it.  Lane l holds
  * the entries l, l + 64, l + 128, l + 192 and, lane 0, the pseudo-symbol 256 in registers.  A merge is two wave-wide argmins over
  * (count, largest index first) and one pass that gives every leaf of the two trees one more bit and the first tree's name -- the
  * leaves libjpeg reaches through its `others` chains.  Counts are uint32: a table holds at most 64 symbols per unit and
- * mij_enc_set_optimize refuses slots of more than 2^32 / 64 units, so no sum wraps.  Integer arithmetic only. */
-__global__ __launch_bounds__(256) void k_emit_build(EmitSlot *__restrict__ slots, EmitTile *__restrict__ tiles, const uint32_t *__restrict__ opt_slots,
-																	 const uint32_t *__restrict__ freq, EmitTables *__restrict__ tabs, uint8_t *__restrict__ hdrs,
-																	 uint32_t *__restrict__ opt_ok)
+ * mij_enc_set_optimize / mij_enc_set_progressive refuse slots of more than 2^32 / 64 units, so no sum wraps.  Integer arithmetic only.
+ * Out: bits[t][l] the number of codes of length l after K.3, first_code / first_pos Annex C's first code and first HUFFVAL position of each
+ * length, nvals[t] the number of codes; pos[q] the HUFFVAL position of symbol lane + 64 * q (-1: no code), nv their number; *fail_p is
+ * raised for a code above 32 bits before the shortening.  bits[t][0..33] and *fail_p are zero on entry, behind a barrier. */
+__device__ __forceinline__ void emit_k2(const uint32_t *__restrict__ f, int lane, int t, uint32_t (*bits)[34], uint32_t (*first_code)[17],
+													 uint32_t (*first_pos)[17], uint32_t *nvals, uint32_t *fail_p, int pos[4], uint32_t &nv)
 {
-	__shared__ uint32_t bits[4][34], first_code[4][17], first_pos[4][17], nvals[4];
-	__shared__ uint32_t fail;
-	const int lane = threadIdx.x & 63, t = threadIdx.x >> 6;
-	const uint32_t k = blockIdx.x, slot = opt_slots[k];
-	if (threadIdx.x == 0)
-		fail = 0;
-	if (lane < 34)
-		bits[t][lane] = 0;
-	__syncthreads();
-	const uint32_t *f = freq + (size_t)k * (4 * 256) + t * 256;
+	uint32_t &fail = *fail_p;
 	uint32_t fr[5];
 	int cs[5], grp[5];
 #pragma unroll
@@ -677,8 +757,8 @@ __global__ __launch_bounds__(256) void k_emit_build(EmitSlot *__restrict__ slots
 	}
 	if (__ballot(deep) != 0 && lane == 0)
 		atomicOr(&fail, 1u);
-	int pos[4] = {-1, -1, -1, -1};
-	uint32_t nv = 0;
+	pos[0] = pos[1] = pos[2] = pos[3] = -1;
+	nv = 0;
 	for (int l = 1; l <= 32; ++l)
 #pragma unroll
 		for (int q = 0; q < 4; ++q) {
@@ -715,6 +795,26 @@ __global__ __launch_bounds__(256) void k_emit_build(EmitSlot *__restrict__ slots
 		nvals[t] = p;
 	}
 	__syncthreads();
+}
+
+/* One workgroup per optimised slot k (slot opt_slots[k], counts freq[k], tables tabs[k + 1]): the four tables by emit_k2, the slot's EmitTables
+ * entry, its DHT segment and header length */
+__global__ __launch_bounds__(256) void k_emit_build(EmitSlot *__restrict__ slots, EmitTile *__restrict__ tiles, const uint32_t *__restrict__ opt_slots,
+																	 const uint32_t *__restrict__ freq, EmitTables *__restrict__ tabs, uint8_t *__restrict__ hdrs,
+																	 uint32_t *__restrict__ opt_ok)
+{
+	__shared__ uint32_t bits[4][34], first_code[4][17], first_pos[4][17], nvals[4];
+	__shared__ uint32_t fail;
+	const int lane = threadIdx.x & 63, t = threadIdx.x >> 6;
+	const uint32_t k = blockIdx.x, slot = opt_slots[k];
+	if (threadIdx.x == 0)
+		fail = 0;
+	if (lane < 34)
+		bits[t][lane] = 0;
+	__syncthreads();
+	int pos[4];
+	uint32_t nv;
+	emit_k2(freq + (size_t)k * (4 * 256) + t * 256, lane, t, bits, first_code, first_pos, nvals, &fail, pos, nv);
 	/* a slot without chroma (dpm == ny) carries the two luma tables only, in the shorter header */
 	const bool grey = slots[slot].dpm == slots[slot].ny;
 	const uint32_t dht_at = grey ? MIJ_EMIT_DHT_AT1 : MIJ_EMIT_DHT_AT, sos_len = grey ? 10u : 14u;
@@ -765,6 +865,90 @@ __global__ __launch_bounds__(256) void k_emit_build(EmitSlot *__restrict__ slots
 		}
 	} else if (threadIdx.x == 0) { /* the plain tables and the plain header, which the upload left in place */
 		opt_ok[k] = 0; /* hlen is still the plain header's, as the upload wrote it */
+	}
+}
+
+/* One workgroup per (progressive slot, scan): the scan's tables by emit_k2 from the counts k_prog_hist left -- DC tables 0 and 1 in the first
+ * DC scan, the AC table in wave 2 of an AC scan, none in the DC refinement -- into EmitTables entry tab0 + scan, which the scan's tiles are
+ * pointed at; the scan's header: a DHT segment per table, then SOS.  The first scan's goes behind the frame header of the slot's header
+ * (EmitSlot.hlen grows by it), the others into phdr for k_emit_write to place between the scans.  A table K.2 refuses raises p_flag. */
+__global__ __launch_bounds__(256) void k_prog_build(EmitSlot *__restrict__ slots, EmitTile *__restrict__ tiles, const ProgSlot *__restrict__ pslots,
+																	 const uint32_t *__restrict__ freq, EmitTables *__restrict__ tabs, uint8_t *__restrict__ hdrs,
+																	 uint8_t *__restrict__ phdr, uint32_t *__restrict__ phlen, uint32_t *__restrict__ p_flag)
+{
+	__shared__ uint32_t bits[4][34], first_code[4][17], first_pos[4][17], nvals[4];
+	__shared__ uint32_t fail;
+	const int lane = threadIdx.x & 63, t = threadIdx.x >> 6;
+	const uint32_t q = blockIdx.x, scan = q % MIJ_PROG_SCANS;
+	const ProgSlot &ps = pslots[q / MIJ_PROG_SCANS];
+	if (scan >= ps.nscan)
+		return;
+	const ProgScanDef sc = k_prog_script[ps.grey][scan];
+	if (threadIdx.x == 0)
+		fail = 0;
+	if (lane < 34)
+		bits[t][lane] = 0;
+	__syncthreads();
+	int pos[4];
+	uint32_t nv;
+	emit_k2(freq + (size_t)q * (4 * 256) + t * 256, lane, t, bits, first_code, first_pos, nvals, &fail, pos, nv);
+	const bool dc = sc.ss == 0, grey = ps.grey != 0;
+	const bool used = dc ? !sc.ah && (t == 0 || (t == 1 && !grey)) : t == 2;
+	const bool all_ok = __syncthreads_and(!fail && nvals[t] == nv) != 0;
+	const uint32_t dht = dc ? (sc.ah ? 0u : 21u + nvals[0] + (grey ? 0u : 21u + nvals[1])) : 21u + nvals[2];
+	const uint32_t sos_len = 8u + 2u * sc.ncomp, hl = dht + sos_len;
+	uint8_t *h = scan == 0 ? hdrs + (size_t)slots[ps.slot].hdr * MIJ_EMIT_HDR + ps.frame_len : phdr + (size_t)q * MIJ_PROG_HDR;
+	for (uint32_t i = ps.tile0[scan] + threadIdx.x; i < ps.tile0[scan + 1]; i += blockDim.x)
+		tiles[i].tab = ps.tab0 + scan;
+	if (threadIdx.x == 0) {
+		phlen[q] = hl;
+		if (scan == 0)
+			slots[ps.slot].hlen = ps.frame_len + hl;
+		if (!all_ok)
+			p_flag[ps.slot] = 1u;
+	}
+	if (!all_ok)
+		return;
+	EmitTables *T = tabs + ps.tab0 + scan;
+	uint8_t *seg = h + (dc && t == 1 ? 21u + nvals[0] : 0u);
+	if (used) {
+		const uint32_t head = 0xFFu | 0xC4u << 8 | ((19u + nv) >> 8) << 16 | ((19u + nv) & 0xFFu) << 24; /* FF C4, the segment's length */
+		if (lane < 4)
+			seg[lane] = (uint8_t)(head >> (8 * lane));
+		if (lane == 4)
+			seg[4] = (uint8_t)(dc ? t : 0x10 | (sc.comp ? 1 : 0));
+		if (lane < 16)
+			seg[5 + lane] = (uint8_t)bits[t][lane + 1];
+	}
+#pragma unroll
+	for (int qq = 0; qq < 4; ++qq) {
+		uint32_t code = 0, len = 0;
+		if (pos[qq] >= 0) {
+			for (int l = 1; l <= 16; ++l)
+				if ((uint32_t)pos[qq] >= first_pos[t][l] && (uint32_t)pos[qq] < first_pos[t][l] + bits[t][l]) {
+					len = (uint32_t)l;
+					code = first_code[t][l] + (uint32_t)pos[qq] - first_pos[t][l];
+				}
+			if (used)
+				seg[21 + pos[qq]] = (uint8_t)(lane + 64 * qq);
+		}
+		T->code[t][lane + 64 * qq] = (uint16_t)code;
+		T->len[t][lane + 64 * qq] = (uint8_t)len;
+	}
+	if (t == 3 && (uint32_t)lane < sos_len) { /* FF DA, length, components with their table byte, Ss, Se, Ah Al */
+		const uint32_t nc = sc.ncomp, i = (uint32_t)lane;
+		uint32_t b;
+		if (i < 5)
+			b = i == 0 ? 0xFFu : (i == 1 ? 0xDAu : (i == 2 ? 0u : (i == 3 ? 6u + 2u * nc : nc)));
+		else if (i < 5 + 2 * nc) {
+			const uint32_t c = dc ? (i - 5) >> 1 : sc.comp;
+			/* Td only in the first DC scan, Ta only in AC scans */
+			b = (i - 5) & 1u ? (dc ? (sc.ah || c == 0 ? 0u : 0x10u) : (c ? 1u : 0u)) : c + 1u;
+		} else {
+			const uint32_t k = i - 5 - 2 * nc;
+			b = k == 0 ? sc.ss : (k == 1 ? sc.se : (uint32_t)sc.ah << 4 | sc.al);
+		}
+		h[dht + i] = (uint8_t)b;
 	}
 }
 

@@ -3193,6 +3193,7 @@ struct EncSlot {
 	int kind;                   /* ENC_*; a clone copies its root's pixels whatever the root's kind */
 	bool optimize;              /* mij_enc_set_optimize */
 	int restart;                /* mij_enc_set_restart: the restart interval in MCUs, 0: none */
+	bool progressive;           /* mij_enc_set_progressive */
 	mij_in_tensor in;           /* ENC_DEVICE */
 	mij_in_convert cv;          /* ENC_DEVICE with float elements (mij_enc_add_device_float); cv.dtype is MIJ_DT_U8 for every other slot */
 	std::vector<int16_t> units; /* ENC_UNITS */
@@ -3276,6 +3277,21 @@ struct mij_encoder {
 	std::vector<uint32_t> sflag; /* after mij_enc_fetch_streams */
 	hipEvent_t ev_conv0, ev_conv1; /* around the conversion kernels of the last upload (mij_enc_coef_ms) */
 	bool conv_timed;
+	/* progressive slots (mij_enc_set_progressive; mij_progressive_kernels.h): their records, the numbers of their tiles in the tile list, the
+	 * block bytes of their AC scans, per-tile summaries and run results, per-scan counts, scan headers and their lengths, and the per-slot flag
+	 * of the slots the host finishes (a forced flush, a table that cannot be built) */
+	ProgSlot *h_pslot, *d_pslot;
+	size_t pslot_cap, n_prog;
+	uint32_t *h_ptile, *d_ptile;
+	size_t ptile_cap, n_ptile;
+	uint8_t *d_pfl, *d_phdr;
+	size_t pfl_cap, phdr_cap;
+	ProgTileSum *d_tsum;
+	ProgAfter *d_tafter;
+	size_t tsum_cap, tafter_cap;
+	uint32_t *d_pfreq, *d_phlen, *d_pflag, *d_ctail;
+	size_t pfreq_cap, phlen_cap, pflag_cap, ctail_cap;
+	std::vector<uint32_t> pflag; /* after mij_enc_fetch_streams */
 	std::vector<int> opt_of;      /* slot -> k, or -1 */
 	std::vector<uint32_t> opt_ok; /* after mij_enc_fetch_streams */
 };
@@ -3327,6 +3343,20 @@ static void enc_free_emit(mij_encoder *e)
 	free_dev(e->d_tout);
 	free_dev(e->d_sent);
 	e->tmeta_cap = e->sent_cap = 0;
+	free_host(e->h_pslot);
+	free_dev(e->d_pslot);
+	free_host(e->h_ptile);
+	free_dev(e->d_ptile);
+	free_dev(e->d_pfl);
+	free_dev(e->d_phdr);
+	free_dev(e->d_tsum);
+	free_dev(e->d_tafter);
+	free_dev(e->d_pfreq);
+	free_dev(e->d_phlen);
+	free_dev(e->d_pflag);
+	free_dev(e->d_ctail);
+	e->pslot_cap = e->n_prog = e->ptile_cap = e->n_ptile = e->pfl_cap = e->phdr_cap = e->tsum_cap = e->tafter_cap = 0;
+	e->pfreq_cap = e->phlen_cap = e->pflag_cap = e->ctail_cap = 0;
 	e->emit_queued = e->streams_fetched = false;
 }
 
@@ -3532,6 +3562,7 @@ static int enc_add_common(mij_encoder *e, const mjw_plan &plan, const void *pixe
 	s.clone_of = clone_of;
 	s.kind = kind;
 	s.optimize = false;
+	s.progressive = false;
 	s.restart = 0;
 	memset(&s.in, 0, sizeof(s.in));
 	memset(&s.cv, 0, sizeof(s.cv));
@@ -3668,6 +3699,7 @@ extern "C" int mij_enc_add_clone(mij_encoder *e, int src_slot)
 	if (slot >= 0) {
 		e->slots[(size_t)slot].optimize = e->slots[(size_t)src_slot].optimize;
 		e->slots[(size_t)slot].restart = e->slots[(size_t)src_slot].restart;
+		e->slots[(size_t)slot].progressive = e->slots[(size_t)src_slot].progressive;
 	}
 	return slot;
 }
@@ -3693,12 +3725,36 @@ extern "C" int mij_enc_set_restart(mij_encoder *e, int slot, int restart_mcus)
 	if (restart_mcus < 0 || restart_mcus > 65535)
 		return set_err(MIJ_E_ARG, "slot %d: a restart interval of %d MCUs is outside 0..65535", slot, restart_mcus);
 	EncSlot &s = e->slots[(size_t)slot];
+	if (restart_mcus && s.progressive)
+		return set_err(MIJ_E_ARG, "slot %d is progressive: restart intervals are not combined with progressive output", slot);
 	/* given units were judged unbroken when they were added: with an interval the DC differences are other ones */
 	const char *why = nullptr;
 	if (s.kind == ENC_UNITS && restart_mcus && !mjw_units_codable_restart(&s.plan, s.units.data(), restart_mcus, &why))
 		return set_err(MIJ_E_ARG, "slot %d at a restart interval of %d MCUs: %s", slot, restart_mcus, why ? why : "not codable");
 	s.restart = restart_mcus;
 	return MIJ_OK;
+}
+
+extern "C" int mij_enc_set_progressive(mij_encoder *e, int slot, int on)
+{
+	if (!e || slot < 0 || slot >= (int)e->slots.size())
+		return set_err(MIJ_E_ARG, "bad slot");
+	if (e->uploaded)
+		return set_err(MIJ_E_STATE, "mij_enc_set_progressive after mij_enc_upload");
+	EncSlot &s = e->slots[(size_t)slot];
+	if (on && s.restart)
+		return set_err(MIJ_E_ARG, "slot %d has a restart interval: restart intervals are not combined with progressive output", slot);
+	if (on && mjw_plan_du_count(&s.plan) > (size_t)(UINT32_MAX / 64))
+		return set_err(MIJ_E_ARG, "slot %d: the symbol counts of %zu data units do not fit 32 bits", slot, mjw_plan_du_count(&s.plan));
+	s.progressive = on != 0;
+	return MIJ_OK;
+}
+
+extern "C" int mij_enc_slot_progressive(const mij_encoder *e, int slot)
+{
+	if (!e || slot < 0 || slot >= (int)e->slots.size())
+		return set_err(MIJ_E_ARG, "bad slot");
+	return e->slots[(size_t)slot].progressive ? 1 : 0;
 }
 
 extern "C" int mij_enc_slot_restart(const mij_encoder *e, int slot)
@@ -3838,7 +3894,44 @@ static int enc_gather_float(mij_encoder *e)
  * slot's DHT segment into its header. */
 static bool enc_own_header(const mij_encoder *e, const EncSlot &s)
 {
-	return s.clone_of < 0 || s.optimize || e->slots[(size_t)s.clone_of].optimize || s.restart != e->slots[(size_t)s.clone_of].restart;
+	return s.clone_of < 0 || s.optimize || e->slots[(size_t)s.clone_of].optimize || s.restart != e->slots[(size_t)s.clone_of].restart || s.progressive ||
+			 e->slots[(size_t)s.clone_of].progressive;
+}
+
+/* A progressive slot's geometry as its scans see it (include/mij_host.h, PROGRESSIVE STREAMS): the transcode plan of a coefficient slot, the
+ * writer's 4:2:0 / 4:4:4 plan of any other */
+static mjw_tplan enc_prog_tplan(const EncSlot &s)
+{
+	if (s.kind == ENC_COEF)
+		return s.tp;
+	mjw_tplan t;
+	t.plan = s.plan;
+	t.ncomp = 3;
+	t.lh = t.lv = s.plan.subsample ? 2 : 1;
+	return t;
+}
+/* the units (a DC scan) or blocks (an AC scan: the component's own grid, without MCU padding) scan `sc` visits, and the grid's columns */
+static size_t enc_prog_scan_blocks(const mjw_tplan &t, const ProgScanDef &sc, uint32_t *bw)
+{
+	const bool own_grid = sc.comp == 0 && t.ncomp == 3; /* luma of a colour picture; chroma and grey have the MCU grid */
+	const size_t w = own_grid ? ((size_t)t.plan.width + 7) / 8 : (size_t)t.plan.mcu_x, h = own_grid ? ((size_t)t.plan.height + 7) / 8 : (size_t)t.plan.mcu_y;
+	*bw = (uint32_t)w;
+	return sc.ss == 0 ? mjw_plan_du_count(&t.plan) : w * h;
+}
+static size_t enc_prog_tile_count(const EncSlot &s, size_t *flag_bytes)
+{
+	const mjw_tplan t = enc_prog_tplan(s);
+	const int grey = t.ncomp == 1, nscan = grey ? MJW_PROGRESSIVE_SCANS_GREY : MJW_PROGRESSIVE_SCANS_COLOUR;
+	size_t tiles = 0, fb = 0;
+	for (int k = 0; k < nscan; ++k) {
+		uint32_t bw;
+		const size_t nb = enc_prog_scan_blocks(t, k_prog_script_host[grey][k], &bw);
+		tiles += (nb + MIJ_EMIT_TILE - 1) / MIJ_EMIT_TILE;
+		fb += k_prog_script_host[grey][k].ss ? nb : 0;
+	}
+	if (flag_bytes)
+		*flag_bytes = fb;
+	return tiles;
 }
 
 /* The tiles of a slot's nu units: MIJ_EMIT_TILE units each, cut at every end of a restart interval of ri MCUs (dpm units each) so that no tile
@@ -3860,6 +3953,8 @@ static size_t enc_slot_tiles(size_t nu, uint32_t dpm, uint32_t ri, F f)
 }
 static size_t enc_slot_tile_count(const EncSlot &s)
 {
+	if (s.progressive)
+		return enc_prog_tile_count(s, nullptr);
 	const size_t nu = mjw_plan_du_count(&s.plan), iu = s.restart ? (size_t)s.restart * (size_t)s.plan.du_per_mcu : nu;
 	if (!s.restart || iu >= nu)
 		return (nu + MIJ_EMIT_TILE - 1) / MIJ_EMIT_TILE;
@@ -3871,18 +3966,29 @@ static size_t enc_slot_tile_count(const EncSlot &s)
 static int enc_emit_lists(mij_encoder *e)
 {
 	const size_t n = e->slots.size();
-	size_t nt = 0, nh = 0, no = 0, not_ = 0;
+	size_t nt = 0, nh = 0, no = 0, not_ = 0, np = 0, npt = 0, nfl = 0;
 	for (const EncSlot &s : e->slots) {
 		const size_t tiles = enc_slot_tile_count(s);
 		nt += tiles;
 		nh += enc_own_header(e, s);
+		if (s.progressive) { /* progressive implies its own per-scan tables: the slot is not in the optimised list */
+			size_t fb = 0;
+			(void)enc_prog_tile_count(s, &fb);
+			++np;
+			npt += tiles;
+			nfl += fb;
+			continue;
+		}
 		no += s.optimize;
 		not_ += s.optimize ? tiles : 0;
 	}
+	const size_t ntab = no + 1 + np * MIJ_PROG_SCANS;
 	if (nt > UINT32_MAX)
 		return set_err(MIJ_E_ARG, "too many data units to emit in one launch");
 	if (n > e->eslot_cap || nt > e->etile_cap || nh * MIJ_EMIT_HDR > e->hdr_cap || n + 1 > e->res_cap || nt > e->tmeta_cap || n > e->sent_cap ||
-		 not_ > e->otile_cap || no > e->optslot_cap || no * 1024 > e->freq_cap || no > e->optok_cap || no + 1 > e->tabs_cap)
+		 not_ > e->otile_cap || no > e->optslot_cap || no * 1024 > e->freq_cap || no > e->optok_cap || ntab > e->tabs_cap || np > e->pslot_cap ||
+		 npt > e->ptile_cap || nfl + 1 > e->pfl_cap ||
+		 (np && (nt > e->tsum_cap || nt > e->ctail_cap || n > e->pflag_cap || np * MIJ_PROG_SCANS * 1024 > e->pfreq_cap || np * MIJ_PROG_SCANS * MIJ_PROG_HDR > e->phdr_cap)))
 		HIP_TRY(hipStreamSynchronize(e->stream)); /* the buffers may still be in use by an earlier launch */
 	int rc = grow_pair(e->h_eslot, e->d_eslot, e->eslot_cap, n);
 	if (rc == MIJ_OK && no) {
@@ -3893,11 +3999,32 @@ static int enc_emit_lists(mij_encoder *e)
 			rc = grow_dev(e->d_freq, e->freq_cap, no * 1024);
 		if (rc == MIJ_OK)
 			rc = grow_dev(e->d_optok, e->optok_cap, no);
-		if (rc == MIJ_OK && no + 1 > e->tabs_cap) {
-			rc = grow_dev(e->d_tabs, e->tabs_cap, no + 1);
-			if (rc == MIJ_OK)
-				HIP_TRY(hipMemcpy(e->d_tabs, &e->h_tabs0, sizeof(EmitTables), hipMemcpyHostToDevice));
-		}
+	}
+	if (rc == MIJ_OK && ntab > e->tabs_cap) {
+		rc = grow_dev(e->d_tabs, e->tabs_cap, ntab);
+		if (rc == MIJ_OK)
+			HIP_TRY(hipMemcpy(e->d_tabs, &e->h_tabs0, sizeof(EmitTables), hipMemcpyHostToDevice));
+	}
+	if (rc == MIJ_OK && np) {
+		rc = grow_pair(e->h_pslot, e->d_pslot, e->pslot_cap, np);
+		if (rc == MIJ_OK)
+			rc = grow_pair(e->h_ptile, e->d_ptile, e->ptile_cap, npt);
+		if (rc == MIJ_OK)
+			rc = grow_dev(e->d_pfl, e->pfl_cap, nfl + 1);
+		if (rc == MIJ_OK)
+			rc = grow_dev(e->d_phdr, e->phdr_cap, np * MIJ_PROG_SCANS * MIJ_PROG_HDR);
+		if (rc == MIJ_OK)
+			rc = grow_dev(e->d_tsum, e->tsum_cap, nt);
+		if (rc == MIJ_OK)
+			rc = grow_dev(e->d_tafter, e->tafter_cap, nt);
+		if (rc == MIJ_OK)
+			rc = grow_dev(e->d_pfreq, e->pfreq_cap, np * MIJ_PROG_SCANS * 1024);
+		if (rc == MIJ_OK)
+			rc = grow_dev(e->d_phlen, e->phlen_cap, np * MIJ_PROG_SCANS);
+		if (rc == MIJ_OK)
+			rc = grow_dev(e->d_pflag, e->pflag_cap, n);
+		if (rc == MIJ_OK)
+			rc = grow_dev(e->d_ctail, e->ctail_cap, nt);
 	}
 	if (rc == MIJ_OK)
 		rc = grow_pair(e->h_etile, e->d_etile, e->etile_cap, nt);
@@ -3928,12 +4055,16 @@ static int enc_emit_lists(mij_encoder *e)
 	if (rc != MIJ_OK)
 		return rc;
 	std::vector<uint32_t> hdr_of(n), hlen_of(n, (uint32_t)MJW_HEADER_BYTES);
-	uint32_t t = 0, h = 0, k = 0, ot = 0;
+	uint32_t t = 0, h = 0, k = 0, ot = 0, pk = 0, pt = 0;
+	uint64_t fl_off = 0;
 	e->opt_of.assign(n, -1);
 	for (size_t i = 0; i < n; ++i) {
 		const EncSlot &s = e->slots[i];
 		if (enc_own_header(e, s)) {
-			if (s.kind == ENC_COEF) /* shorter for a grey slot */
+			if (s.progressive) { /* SOI .. SOF2; k_prog_build appends the first scan's tables and SOS */
+				const mjw_tplan tp = enc_prog_tplan(s);
+				hlen_of[i] = (uint32_t)mjw_tframe_progressive(&tp, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
+			} else if (s.kind == ENC_COEF) /* shorter for a grey slot */
 				hlen_of[i] = (uint32_t)mjw_theader_restart(&s.tp, s.restart, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
 			else
 				hlen_of[i] = (uint32_t)mjw_header_restart(&s.plan, s.restart, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
@@ -3950,10 +4081,41 @@ static int enc_emit_lists(mij_encoder *e)
 		es.n_tiles = (uint32_t)enc_slot_tile_count(s);
 		es.hdr = hdr_of[i];
 		es.ri = (uint32_t)s.restart;
-		es.pad = 0;
+		es.prog = 0;
 		es.tab = 0;
 		es.ny = s.kind == ENC_COEF ? (s.tp.ncomp == 1 ? 1u : (uint32_t)(s.tp.lh * s.tp.lv)) : (s.plan.subsample ? 4u : 1u);
 		es.hlen = hlen_of[i];
+		if (s.progressive) { /* its tiles name (scan, first block, count); a scan is a segment as a restart interval is */
+			const mjw_tplan tp = enc_prog_tplan(s);
+			ProgSlot &ps = e->h_pslot[pk];
+			memset(&ps, 0, sizeof(ps));
+			ps.slot = (uint32_t)i;
+			ps.grey = tp.ncomp == 1;
+			ps.nscan = ps.grey ? MJW_PROGRESSIVE_SCANS_GREY : MJW_PROGRESSIVE_SCANS_COLOUR;
+			ps.lh = ps.grey ? 1u : (uint32_t)tp.lh;
+			ps.lv = ps.grey ? 1u : (uint32_t)tp.lv;
+			ps.mcu_x = (uint32_t)tp.plan.mcu_x;
+			ps.frame_len = hlen_of[i];
+			ps.tab0 = (uint32_t)(no + 1 + (size_t)pk * MIJ_PROG_SCANS);
+			es.prog = ++pk;
+			for (uint32_t sc = 0; sc < ps.nscan; ++sc) {
+				const ProgScanDef &def = k_prog_script_host[ps.grey][sc];
+				const size_t nb = enc_prog_scan_blocks(tp, def, &ps.bw[sc]);
+				ps.tile0[sc] = t;
+				ps.flag_off[sc] = fl_off;
+				fl_off += def.ss ? nb : 0;
+				for (size_t b = 0; b < nb; b += MIJ_EMIT_TILE) {
+					const size_t cnt = std::min((size_t)MIJ_EMIT_TILE, nb - b);
+					const bool last = b + cnt == nb;
+					const EmitTile tl = {(uint32_t)i, (uint32_t)b, 0u, emit_tile_pad((uint32_t)cnt, b == 0, last, last && sc + 1 < ps.nscan, 0u) | sc << 16};
+					e->h_ptile[pt++] = t;
+					e->h_etile[t++] = tl;
+				}
+			}
+			for (uint32_t sc = ps.nscan; sc <= MIJ_PROG_SCANS; ++sc)
+				ps.tile0[sc] = t;
+			continue;
+		}
 		if (s.optimize) {
 			e->opt_of[i] = (int)k;
 			e->h_optslot[k] = (uint32_t)i;
@@ -3969,6 +4131,12 @@ static int enc_emit_lists(mij_encoder *e)
 	e->n_etile = nt;
 	e->n_opt = no;
 	e->n_otile = not_;
+	e->n_prog = np;
+	e->n_ptile = npt;
+	if (np) {
+		HIP_TRY(hipMemcpyAsync(e->d_pslot, e->h_pslot, sizeof(ProgSlot) * np, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->d_ptile, e->h_ptile, sizeof(uint32_t) * npt, hipMemcpyHostToDevice, e->stream));
+	}
 	if (no) {
 		HIP_TRY(hipMemcpyAsync(e->d_otile, e->h_otile, sizeof(EmitTile) * not_, hipMemcpyHostToDevice, e->stream));
 		HIP_TRY(hipMemcpyAsync(e->d_optslot, e->h_optslot, sizeof(uint32_t) * no, hipMemcpyHostToDevice, e->stream));
@@ -3991,14 +4159,35 @@ static int enc_emit_launch(mij_encoder *e)
 		hipLaunchKernelGGL(k_emit_build, dim3((unsigned)e->n_opt), block, 0, e->stream, e->d_eslot, e->d_etile, e->d_optslot, e->d_freq, e->d_tabs, e->d_hdr,
 								 e->d_optok);
 	}
-	hipLaunchKernelGGL(k_emit_len, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_tbits);
+	ProgArgs pa = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+	if (e->n_prog) { /* block flags, run lengths, per-scan counts, per-scan tables and headers: four launches whatever the slots and scans */
+		const size_t nq = e->n_prog * MIJ_PROG_SCANS;
+		HIP_TRY(hipMemsetAsync(e->d_pfreq, 0, sizeof(uint32_t) * 1024 * nq, e->stream));
+		HIP_TRY(hipMemsetAsync(e->d_phlen, 0, sizeof(uint32_t) * nq, e->stream));
+		HIP_TRY(hipMemsetAsync(e->d_pflag, 0, sizeof(uint32_t) * n, e->stream));
+		hipLaunchKernelGGL(k_prog_flags, dim3((unsigned)e->n_ptile), block, 0, e->stream, e->d_eslot, e->d_etile, e->d_ptile, e->d_pslot, du, e->d_pfl, e->d_tsum);
+		hipLaunchKernelGGL(k_prog_runs, dim3((unsigned)((e->n_prog + 3) / 4)), block, 0, e->stream, e->d_eslot, e->d_etile, e->d_pslot, (uint32_t)e->n_prog,
+								 e->d_tsum, e->d_tafter);
+		hipLaunchKernelGGL(k_prog_hist, dim3((unsigned)e->n_ptile), block, 0, e->stream, e->d_eslot, e->d_etile, e->d_ptile, e->d_pslot, du, e->d_pfl, e->d_tafter,
+								 e->d_pfreq, e->d_pflag);
+		hipLaunchKernelGGL(k_prog_build, dim3((unsigned)nq), block, 0, e->stream, e->d_eslot, e->d_etile, e->d_pslot, e->d_pfreq, e->d_tabs, e->d_hdr, e->d_phdr,
+								 e->d_phlen, e->d_pflag);
+		pa.slots = e->d_pslot;
+		pa.fl = e->d_pfl;
+		pa.after = e->d_tafter;
+		pa.hdr = e->d_phdr;
+		pa.hlen = e->d_phlen;
+		pa.ctail = e->d_ctail;
+	}
+	hipLaunchKernelGGL(k_emit_len, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_tbits, pa);
 	hipLaunchKernelGGL(k_emit_scan, per_slot, block, 0, e->stream, e->d_eslot, e->d_etile, n, e->d_tbits, e->d_tboff);
 	hipLaunchKernelGGL(k_emit_count, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_tbits, e->d_tboff, e->d_tff, e->d_tfrag,
-							 e->has_coef ? e->d_sflag : nullptr);
-	hipLaunchKernelGGL(k_emit_stuff, per_slot, block, 0, e->stream, e->d_eslot, e->d_etile, n, e->d_tbits, e->d_tboff, e->d_tff, e->d_tfrag, e->d_tout, e->d_sent);
+							 e->has_coef ? e->d_sflag : nullptr, e->n_prog ? e->d_pflag : nullptr, pa);
+	hipLaunchKernelGGL(k_emit_stuff, per_slot, block, 0, e->stream, e->d_eslot, e->d_etile, n, e->d_tbits, e->d_tboff, e->d_tff, e->d_tfrag, e->d_tout, e->d_sent,
+							 pa);
 	hipLaunchKernelGGL(k_emit_place, dim3(1), dim3(1024), 0, e->stream, e->d_eslot, n, e->d_sent, (uint64_t)e->arena_cap, e->d_res);
 	hipLaunchKernelGGL(k_emit_write, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_hdr, e->d_tbits, e->d_tboff, e->d_tfrag,
-							 e->d_tout, e->d_res, e->d_arena);
+							 e->d_tout, e->d_res, e->d_arena, pa);
 	HIP_TRY(hipGetLastError());
 	e->emit_queued = true;
 	return MIJ_OK;
@@ -4058,6 +4247,9 @@ extern "C" int mij_enc_fetch_streams(mij_encoder *e)
 	e->sflag.assign(n, 0u);
 	if (e->has_coef)
 		HIP_TRY(hipMemcpy(e->sflag.data(), e->d_sflag, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+	e->pflag.assign(n, 0u);
+	if (e->n_prog)
+		HIP_TRY(hipMemcpy(e->pflag.data(), e->d_pflag, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
 	e->opt_ok.assign(e->n_opt, 0u);
 	if (e->n_opt)
 		HIP_TRY(hipMemcpy(e->opt_ok.data(), e->d_optok, sizeof(uint32_t) * e->n_opt, hipMemcpyDeviceToHost));
@@ -4341,6 +4533,10 @@ extern "C" int mij_enc_slot_status(const mij_encoder *e, int slot)
 	if ((size_t)slot < e->sflag.size() && e->sflag[(size_t)slot]) {
 		set_err(MIJ_E_ARG, "slot %d: not codable: an AC coefficient outside -1023..1023 or a DC difference outside -2047..2047", slot);
 		return MIJ_ENC_SLOT_UNCODABLE;
+	}
+	if ((size_t)slot < e->pflag.size() && e->pflag[(size_t)slot]) {
+		set_err(MIJ_E_ARG, "slot %d: progressive with a forced EOB-run flush or a table that cannot be built: finish it on the host from its units", slot);
+		return MIJ_ENC_SLOT_HOST_FLUSH;
 	}
 	if (e->h_res[slot].off == ~0ull) {
 		set_err(MIJ_E_NOMEM, "slot %d did not fit in the emission arena (needs %llu bytes)", slot, (unsigned long long)e->h_res[slot].len);

@@ -453,9 +453,10 @@ int mjw_units_crop(const mjw_tplan *src, const int16_t *du_src, const int rect[4
 /* one step's units replace the previous step's */
 static int16_t *units_for(const mjw_tplan *t) { return (int16_t *)malloc(mjw_tplan_du_count(t) * 64 * sizeof(int16_t)); }
 
-int mjw_transcode_memory_restart_at(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
-                                    const unsigned char *chroma, int coarsen_only, int restart_rows, int restart_mcus, unsigned char **out,
-                                    size_t *out_len, int *rect_out, int *ri_out, const char **reason)
+/* the whole chain; progressive 1 ends it in mjw_temit_progressive (include/mij_host.h, PROGRESSIVE STREAMS), which takes no interval */
+static int transcode_memory_at(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
+                               const unsigned char *chroma, int coarsen_only, int restart_rows, int restart_mcus, int progressive, unsigned char **out,
+                               size_t *out_len, int *rect_out, int *ri_out, const char **reason)
 {
 	mij_image_desc d;
 	int ri = 0;
@@ -474,6 +475,10 @@ int mjw_transcode_memory_restart_at(const uint8_t *src, int len, unsigned flags,
 		return refuse(reason, "bad argument");
 	if (flags & ~(MJW_OPTIMIZE_HUFFMAN | MJW_COPY_MARKERS))
 		return refuse(reason, "unknown flag");
+	if (progressive != 0 && progressive != 1)
+		return refuse(reason, "progressive is 0 or 1");
+	if (progressive && (restart_rows || restart_mcus))
+		return refuse(reason, "restart intervals are not combined with progressive output");
 	if (!mjh_probe_memory(src, len, 0, &d, &why))
 		return refuse(reason, why ? why : "decode failed");
 	rbytes = mij_image_region_bytes(&d);
@@ -529,13 +534,13 @@ int mjw_transcode_memory_restart_at(const uint8_t *src, int len, unsigned flags,
 		goto done;
 	if (!mjw_tunits_codable_restart(&t, du, ri, reason))
 		goto done;
-	cap = MJW_STREAM_CAP(mjw_tplan_du_count(&t));
+	cap = progressive ? MJW_PROGRESSIVE_STREAM_CAP(mjw_tplan_du_count(&t)) : MJW_STREAM_CAP(mjw_tplan_du_count(&t));
 	buf = (unsigned char *)malloc(cap);
 	if (!buf) {
 		refuse(reason, "out of memory");
 		goto done;
 	}
-	n = ri ? mjw_temit_restart_to_memory(&t, du, flags & MJW_OPTIMIZE_HUFFMAN, ri, buf, cap) : mjw_temit_to_memory(&t, du, flags & MJW_OPTIMIZE_HUFFMAN, buf, cap);
+	n = progressive ? mjw_temit_progressive_to_memory(&t, du, buf, cap) : ri ? mjw_temit_restart_to_memory(&t, du, flags & MJW_OPTIMIZE_HUFFMAN, ri, buf, cap) : mjw_temit_to_memory(&t, du, flags & MJW_OPTIMIZE_HUFFMAN, buf, cap);
 	if (!n) {
 		refuse(reason, "emission failed");
 		goto done;
@@ -558,6 +563,21 @@ done:
 	free(dn);
 	free(buf);
 	return ok;
+}
+
+int mjw_transcode_memory_restart_at(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
+                                    const unsigned char *chroma, int coarsen_only, int restart_rows, int restart_mcus, unsigned char **out,
+                                    size_t *out_len, int *rect_out, int *ri_out, const char **reason)
+{
+	return transcode_memory_at(src, len, flags, o, trim, crop, grey, luma, chroma, coarsen_only, restart_rows, restart_mcus, 0, out, out_len, rect_out,
+										ri_out, reason);
+}
+
+int mjw_transcode_memory_progressive_at(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
+                                        const unsigned char *chroma, int coarsen_only, int progressive, unsigned char **out, size_t *out_len,
+                                        int *rect_out, const char **reason)
+{
+	return transcode_memory_at(src, len, flags, o, trim, crop, grey, luma, chroma, coarsen_only, 0, 0, progressive, out, out_len, rect_out, NULL, reason);
 }
 
 int mjw_transcode_memory_window_at(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,

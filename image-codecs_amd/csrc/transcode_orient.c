@@ -8,9 +8,9 @@
 
 #include "mij_host.h"
 
-int mjh_transcode_memory_restart_by(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
-                                    const unsigned char *chroma, int coarsen_only, int restart_rows, int restart_mcus, unsigned char **out,
-                                    size_t *out_len, int *rect_out, int *ri_out, const char **reason)
+static int transcode_memory(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
+                            const unsigned char *chroma, int coarsen_only, int restart_rows, int restart_mcus, int progressive, unsigned char **out,
+                            size_t *out_len, int *rect_out, int *ri_out, const char **reason)
 {
 	if (o < 0 || o > 8) {
 		if (out)
@@ -23,13 +23,30 @@ int mjh_transcode_memory_restart_by(const uint8_t *src, int len, unsigned flags,
 	}
 	if (o == 0)
 		o = mjh_exif_orientation(src, len);
-	if (!mjw_transcode_memory_restart_at(src, len, flags, o, trim, crop, grey, luma, chroma, coarsen_only, restart_rows, restart_mcus, out, out_len,
-													  rect_out, ri_out, reason))
+	if (!(progressive ? mjw_transcode_memory_progressive_at(src, len, flags, o, trim, crop, grey, luma, chroma, coarsen_only, progressive, out, out_len,
+																			  rect_out, reason)
+							: mjw_transcode_memory_restart_at(src, len, flags, o, trim, crop, grey, luma, chroma, coarsen_only, restart_rows, restart_mcus, out,
+																		 out_len, rect_out, ri_out, reason)))
 		return 0;
 	/* the picture is upright now: a copied tag that still said otherwise would turn it a second time */
 	if ((flags & MJW_COPY_MARKERS) && o != 1)
 		(void)mjh_exif_set_orientation(*out, *out_len > (size_t)INT_MAX ? INT_MAX : (int)*out_len, 1);
 	return 1;
+}
+
+int mjh_transcode_memory_restart_by(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
+                                    const unsigned char *chroma, int coarsen_only, int restart_rows, int restart_mcus, unsigned char **out,
+                                    size_t *out_len, int *rect_out, int *ri_out, const char **reason)
+{
+	return transcode_memory(src, len, flags, o, trim, crop, grey, luma, chroma, coarsen_only, restart_rows, restart_mcus, 0, out, out_len, rect_out, ri_out,
+									reason);
+}
+
+int mjh_transcode_memory_progressive(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
+                                     const unsigned char *chroma, int coarsen_only, int progressive, unsigned char **out, size_t *out_len,
+                                     int *rect_out, const char **reason)
+{
+	return transcode_memory(src, len, flags, o, trim, crop, grey, luma, chroma, coarsen_only, 0, 0, progressive, out, out_len, rect_out, NULL, reason);
 }
 
 int mjh_transcode_memory_restart(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,

@@ -202,7 +202,8 @@ class TensorEncoder:
             self._enc.reset()
         return self._enc
 
-    def encode(self, images, *, quality=90, layout="CHW", flip_vertically=False, optimize=False, restart_rows=None, restart_mcus=None):
+    def encode(self, images, *, quality=90, layout="CHW", flip_vertically=False, optimize=False, restart_rows=None, restart_mcus=None,
+               progressive=False):
         """quality: 1..100, or 0 for the default 90, as stbi_write_jpg takes it.  images: a 4-D uint8 tensor on the GPU ([N, C, H, W] for layout "CHW", [N, H, W, C] for "HWC") or a sequence of 3-D
         (2-D: grey) uint8 tensors, whose sizes may differ; C is 1..4 (stbi_write_jpg's comp).  Strided views are accepted (unit
         stride along W for CHW; strides C and 1 along W and C for HWC).  -> one bytes object per picture: what
@@ -212,11 +213,14 @@ class TensorEncoder:
         restart_rows, restart_mcus: None, an int >= 0 or one of those per picture: restart markers after every so many MCU rows, or MCUs
         (an MCU is 16 x 16 pixels up to quality 90 and 8 x 8 above) -- what mjw_emit_restart writes (include/mij_host.h, RESTART
         INTERVALS).  None or 0 means none.  ValueError for both given for one picture and for an interval above 65535 MCUs.
-        last_restarts[i] is the interval used, in MCUs."""
-        return self._encode(images, None, None, quality, layout, flip_vertically, optimize, False, restart_rows, restart_mcus)
+        last_restarts[i] is the interval used, in MCUs.
+        progressive (a bool): every stream is written as a progressive one -- what mjw_emit_progressive writes for the picture's data
+        units (include/mij_host.h, PROGRESSIVE STREAMS), under per-scan optimal tables whatever optimize says.  ValueError together with
+        a restart interval."""
+        return self._encode(images, None, None, quality, layout, flip_vertically, optimize, False, restart_rows, restart_mcus, progressive)
 
     def encode_normalized(self, images, *, mean=None, std=None, quality=90, layout="CHW", flip_vertically=False, optimize=False,
-                          restart_rows=None, restart_mcus=None):
+                          restart_rows=None, restart_mcus=None, progressive=False):
         """encode() for the tensors a model works on: images as for encode() -- the same shapes, stride rules and layouts -- but float16,
         bfloat16 or float32, one dtype per call.  The pictures are de-normalised on the GPU, inside the kernel that gathers them
         (mij_enc_add_device_float), by the contract of include/mij.h: for element x of channel c
@@ -228,12 +232,16 @@ class TensorEncoder:
         Both None: the pictures hold v / 255, tensor_tables' convention; with the mean / std a TensorDecoder.decode was given, its
         tensors come back as the bytes they were made from, for all three dtypes.  A tensor holding 0..255 values is std=[1/255]*C.
         ValueError, before any device is touched, for uint8 or any other non-float dtype, mixed dtypes, a wrong number of mean / std
-        values, a std of 0, a value that is not finite, and everything encode() refuses.  restart_rows, restart_mcus: as for encode()."""
-        return self._encode(images, mean, std, quality, layout, flip_vertically, optimize, True, restart_rows, restart_mcus)
+        values, a std of 0, a value that is not finite, and everything encode() refuses.  restart_rows, restart_mcus, progressive: as for
+        encode()."""
+        return self._encode(images, mean, std, quality, layout, flip_vertically, optimize, True, restart_rows, restart_mcus, progressive)
 
-    def _encode(self, images, mean, std, quality, layout, flip_vertically, optimize, floats, restart_rows=None, restart_mcus=None):
+    def _encode(self, images, mean, std, quality, layout, flip_vertically, optimize, floats, restart_rows=None, restart_mcus=None,
+                progressive=False):
         if not isinstance(optimize, bool):
             raise ValueError("optimize must be a bool, got %r" % (optimize,))
+        if not isinstance(progressive, bool):
+            raise ValueError("progressive must be a bool, got %r" % (progressive,))
         if isinstance(quality, bool) or not isinstance(quality, int) or not 0 <= quality <= 100:
             raise ValueError("quality must be an int in 0..100 (0: stbi_write_jpg's default, 90), got %r" % (quality,))
         views = self._views(images, layout, floats)
@@ -247,6 +255,8 @@ class TensorEncoder:
                 by_c[c] = InConvert(_FLOAT_DT[views[0][0].dtype] if views else MIJ_DT_F32, scale, bias)
             convs = [by_c[v[3]] for v in views]
         rrows, rmcus = _restart_values(restart_rows, len(views), "restart_rows"), _restart_values(restart_mcus, len(views), "restart_mcus")
+        if progressive and (any(rrows) or any(rmcus)):
+            raise ValueError("restart intervals are not combined with progressive output")
         self._placed(views)
         self.last_restarts = restarts = []
         if not views:
@@ -273,36 +283,43 @@ class TensorEncoder:
             while j < len(views) and j - i < MAX_SLOTS and (j == i or pix + sizes[j][0] <= MAX_PIXEL_BYTES):
                 pix += sizes[j][0]
                 j += 1
-            streams, h = self._encode_chunk(views[i:j], sizes[i:j], quality, lay, flip, optimize, convs[i:j] if floats else None, restarts[i:j])
+            streams, h = self._encode_chunk(views[i:j], sizes[i:j], quality, lay, flip, optimize, convs[i:j] if floats else None, restarts[i:j],
+                                            progressive)
             out.extend(streams)
             host += h
             i = j
         self.last_host_emitted = host
         return out
 
-    def _encode_chunk(self, views, sizes, quality, lay, flip, optimize, convs=None, restarts=None):
+    def _encode_chunk(self, views, sizes, quality, lay, flip, optimize, convs=None, restarts=None, progressive=False):
         if not self._arena:  # a first guess, about 0.75 bytes per pixel; misses grow it
             self._arena = _align(sum(1024 + (px * 3) // 4 for (_, _, px) in sizes), 1 << 20)
         enc = self._encoder_for(len(views), sum(s[0] for s in sizes), sum(s[1] for s in sizes))
         for k, (t, w, h, c, rp, pp) in enumerate(views):
             it = InTensor(t.data_ptr(), lay, w, h, c, rp, pp)
             slot = enc.add_device(it, quality, flip) if convs is None else enc.add_device_float(it, convs[k], quality, flip)
-            if optimize:
+            if progressive:
+                enc.set_progressive(slot)
+            elif optimize:
                 enc.set_optimize(slot)
             if restarts and restarts[k]:
                 enc.set_restart(slot, restarts[k])
         enc.upload()
         enc.launch()
         enc.fetch_streams()
-        streams, need, host = [], 0, 0
+        streams, need, host, grow = [], 0, 0, 0
         for slot in range(len(views)):
             data, n = enc.stream(slot)
-            need += n
             if data is None:  # did not fit: its units are still on the device, the host Huffman stage finishes it
-                data = emit_jpeg(enc.plan(slot), enc.fetch(slot), optimize, restart_mcus=enc.slot_restart(slot))
+                data = emit_jpeg(enc.plan(slot), enc.fetch(slot), optimize, restart_mcus=enc.slot_restart(slot), progressive=progressive)
                 host += 1
+                if enc.slot_status(slot) == "host flush":  # a progressive slot with a forced flush: the device reported no length
+                    n = len(data)
+                else:
+                    grow += 1
+            need += n
             streams.append(data)
-        if host:
+        if grow:
             self._arena = _align(need + need // 8, 1 << 20)
             enc.stream_reserve(self._arena)
         return streams, host

@@ -117,6 +117,23 @@ def _greys(v, n):
     return vals
 
 
+def _progressives(v, n):
+    """transcode's progressive= as one bool per source"""
+    vals = [v] * n if isinstance(v, bool) else None
+    if vals is None:
+        if isinstance(v, (str, bytes)):
+            raise ValueError("progressive must be a bool or one per source (got %r)" % (v,))
+        try:
+            vals = list(v)
+        except TypeError:
+            raise ValueError("progressive must be a bool or one per source (got %r)" % (v,)) from None
+        if len(vals) != n:
+            raise ValueError("progressive has %d values for %d sources" % (len(vals), n))
+    if not all(isinstance(p, bool) for p in vals):
+        raise ValueError("progressive must be a bool or one per source (got %r)" % (v,))
+    return vals
+
+
 def _intervals(v, n, name):
     """transcode's restart_rows= / restart_mcus= as one int >= 0 per source (None is 0: none)"""
     what = name + " must be None, an int >= 0 or one of those per source (got %r)"
@@ -155,9 +172,11 @@ class Transcoder:
 
     Owns a Context, a Batch and an Encoder with its emission arena, grown as needed and reused across calls.  Synchronous.  Sources that
     are transcodable: grey, and YCbCr (JFIF or Adobe transform 1) as 4:4:4, 4:2:2, 4:4:0 or 4:2:0, baseline or progressive, with or without
-    restart intervals, whose quantisation tables hold 8-bit entries and are the same for Cb and Cr.  The output is always a baseline stream,
-    without restart intervals unless they are asked for (include/mij_host.h, mjw_tplan, has the whole contract).  Slots whose streams do not fit the arena are
-    finished on the host from their units (last_host_emitted counts them) and the arena grows for the next call."""
+    restart intervals, whose quantisation tables hold 8-bit entries and are the same for Cb and Cr.  The output is a baseline stream
+    without restart intervals unless they are asked for, or a progressive stream with progressive=True (include/mij_host.h, mjw_tplan
+    and PROGRESSIVE STREAMS, has the whole contract).  Slots whose streams do not fit the arena are finished on the host from their units
+    and the arena grows for the next call; so are progressive slots in which libjpeg would flush an end-of-band run early
+    (last_host_emitted counts both)."""
 
     def __init__(self, device=None):
         if device is not None and (isinstance(device, bool) or not isinstance(device, int) or device < 0):
@@ -176,6 +195,7 @@ class Transcoder:
         self.last_crops = []
         self.last_greyed = []
         self.last_restarts = []
+        self.last_progressive = []
         self.last_timing = {}
 
     @property
@@ -238,7 +258,8 @@ class Transcoder:
         return self._enc
 
     def transcode(self, datas, *, optimize=True, copy_markers="all", only_if_smaller=False, gpu_entropy=None, threads=16, orientation=None,
-                  edge="perfect", quality=None, qtables=None, coarsen_only=True, crop=None, grey=False, restart_rows=None, restart_mcus=None):
+                  edge="perfect", quality=None, qtables=None, coarsen_only=True, crop=None, grey=False, restart_rows=None, restart_mcus=None,
+                  progressive=False):
         """datas: a sequence of JPEG files as bytes.  -> a list with, per source, the new stream (bytes) or None; last_reasons[i] is None
         or the reason source i was refused or could not be decoded.
         optimize: Huffman tables built from each picture's own statistics (mjw_temit_optimized's stream); False: the Annex-K tables.
@@ -275,6 +296,10 @@ class Transcoder:
         INTERVALS).  None or 0 means none; giving both for the same source is a ValueError.  An interval that resolves above 65535 MCUs
         refuses that picture alone, with its reason in last_reasons[i].  last_restarts[i] is the interval used, in MCUs.  A source's own
         DRI is never copied (copy_markers copies APPn and COM only), and only_if_smaller compares the finished stream as it is.
+        progressive: a bool, or one per source: the stream is written as a progressive one (jpegtran -progressive; include/mij_host.h,
+        PROGRESSIVE STREAMS): the same coefficients in libjpeg's ten scans (six for grey), each under the optimal tables of its own
+        symbols, whatever optimize says.  It composes with every step above; last_progressive[i] says which outputs are progressive
+        (False where only_if_smaller kept the source).  Together with a restart interval for the same source it is a ValueError.
         ValueError, before a device is touched, for arguments that are not of these kinds."""
         if not isinstance(optimize, bool) or not isinstance(only_if_smaller, bool):
             raise ValueError("optimize and only_if_smaller must be bools")
@@ -303,6 +328,11 @@ class Transcoder:
         for i, (r, m) in enumerate(zip(rrows, rmcus)):
             if r and m:
                 raise ValueError("source %d: restart_rows and restart_mcus are two ways to say the same thing: give one" % i)
+        progs = _progressives(progressive, len(datas))
+        for i, p in enumerate(progs):
+            if p and (rrows[i] or rmcus[i]):
+                raise ValueError("source %d: restart intervals are not combined with progressive output" % i)
+        self.last_progressive = written = [False] * len(datas)
         self.last_restarts = restarts = [0] * len(datas)
         self.last_requantized = requantized = [False] * len(datas)
         self.last_crops = kept = [None] * len(datas)
@@ -340,7 +370,7 @@ class Transcoder:
                 coef += todo[j][1]
                 j += 1
             self._chunk(datas, todo[k:j], out, reasons, optimize, gpu_entropy, threads, orients, edge == "trim", targets, coarsen_only,
-                        requantized, crops, greys, kept, greyed, windowed, rrows, rmcus, restarts)
+                        requantized, crops, greys, kept, greyed, windowed, rrows, rmcus, restarts, progs)
             k = j
         for i, d in enumerate(datas):
             if out[i] is None:
@@ -352,13 +382,15 @@ class Transcoder:
                     continue
                 if orients[i] != 1:  # the picture is upright now: the copied tag must not turn it again
                     out[i], _ = exif_set_orientation(out[i], 1)
+            written[i] = progs[i]
             if only_if_smaller and orients[i] == 1 and not windowed[i] and len(out[i]) >= len(d):
                 out[i] = d
+                written[i] = False
         self.last_reasons = reasons
         return out
 
     def _chunk(self, datas, items, out, reasons, optimize, gpu_entropy, threads, orients, trim, targets, coarsen_only, requantized, crops,
-               greys, kept, greyed, windowed, rrows, rmcus, restarts):
+               greys, kept, greyed, windowed, rrows, rmcus, restarts, progs):
         n = len(items)
         srcs = [datas[it[0]] for it in items]
         stream = 0
@@ -389,7 +421,9 @@ class Transcoder:
             greyed[it[0]] = enc.slot_greyed(es[it[0]])
             windowed[it[0]] = enc.slot_windowed(es[it[0]])
             requantized[it[0]] = enc.slot_requantized(es[it[0]])
-            if optimize:
+            if progs[it[0]]:  # implies the optimal tables, per scan
+                enc.set_progressive(es[it[0]])
+            elif optimize:
                 enc.set_optimize(es[it[0]])
             if rrows[it[0]] or rmcus[it[0]]:  # resolved on the destination's plan; a refused one costs its slot, which is never fetched
                 ri, bad = restart_interval(enc.tplan(es[it[0]]), rrows[it[0]], rmcus[it[0]])
@@ -409,19 +443,24 @@ class Transcoder:
         enc.fetch_streams()
         self.last_timing["convert_ms"] += enc.coef_ms() or 0.0
         self.last_timing["emit_ms"] += enc.timer_ms()
-        need, host = 0, 0
+        need, host, grow = 0, 0, 0
         for i, slot in es.items():
             data, ln = enc.stream(slot)
             if data is None:
-                if enc.slot_status(slot) == "uncodable":
+                status = enc.slot_status(slot)
+                if status == "uncodable":
                     reasons[i] = "not codable: an AC coefficient outside -1023..1023 or a DC difference outside -2047..2047"
                     continue
-                # its units are on the device: the host finishes it, at the same interval
-                data = emit_transcoded(enc.tplan(slot), enc.fetch(slot), optimize, restart_mcus=restarts[i])
+                # its units are on the device: the host finishes it, at the same interval or as the same progressive stream
+                data = emit_transcoded(enc.tplan(slot), enc.fetch(slot), optimize, restart_mcus=restarts[i], progressive=progs[i])
                 host += 1
+                if status == "host flush":  # a forced flush, not a lack of room: the device reported no length
+                    ln = len(data)
+                else:
+                    grow += 1
             need += ln
             out[i] = data
         self.last_host_emitted += host
-        if host:
+        if grow:
             self._arena = _align(need + need // 8, 1 << 20)
             enc.stream_reserve(self._arena)

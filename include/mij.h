@@ -691,6 +691,29 @@ int mij_enc_set_restart(mij_encoder *e, int slot, int restart_mcus);
 int mij_enc_slot_restart(const mij_encoder *e, int slot);
 
 /*
+ * Progressive output (jpegtran -progressive): a slot's stream written as the multi-scan SOF2 stream of include/mij_host.h, PROGRESSIVE
+ * STREAMS -- libjpeg's jpeg_simple_progression script, every scan under the optimal tables of its own symbols, libjpeg's bytes for the
+ * slot's units.  With an emission arena the GPU writes it (mij_progressive_kernels.h): four launches in front of the emission's six over the
+ * progressive tiles only, their number independent of the slots and the scans, and none without a progressive slot; a slot without the
+ * request runs the code it ran before and gives the same bytes.  The request implies optimised tables (mij_enc_set_optimize adds nothing to
+ * it, and mij_enc_slot_optimized reports 0: the tables are per scan).
+ *
+ * FORCED FLUSHES.  libjpeg flushes an end-of-band run early when it reaches 32767 blocks or when more than 937 correction bits are
+ * pending.  Both are sequential decisions and do not run on the GPU: a slot in which one occurs, and a slot with a scan whose table K.2
+ * cannot build (there are no plain tables with EOBn codes to fall back to), is reported as MIJ_ENC_SLOT_HOST_FLUSH by mij_enc_slot_status
+ * (mij_enc_stream: NULL, length 0): finish it on the host from its units with mjw_emit_progressive / mjw_temit_progressive, which also
+ * finish a progressive slot that had no room or no arena.  The bytes are the contract's either way.
+ *
+ * mij_enc_set_progressive: for a slot of any kind, after it is added and before mij_enc_upload; MIJ_E_STATE after the upload; MIJ_E_ARG
+ * for a bad slot, for a slot with a restart interval (mij_enc_set_restart in turn refuses an interval on a progressive slot: libjpeg
+ * re-emits DRI per scan, which is out of scope) and for one whose unit count times 64 does not fit 32 bits.  A clone inherits the request;
+ * mij_enc_reset forgets all requests.
+ * mij_enc_slot_progressive: 1 or 0, or a negative code for a bad slot.
+ */
+int mij_enc_set_progressive(mij_encoder *e, int slot, int on);
+int mij_enc_slot_progressive(const mij_encoder *e, int slot);
+
+/*
  * Lossless transcode: an encoder slot whose data units are the QUANTISED coefficients of a decode batch's slot, taken from the batch's
  * coefficient planes in device memory -- a new slot kind beside given units.  The contract (which sources are transcodable, the unit
  * order, the stream) is written in mij_host.h (mjw_tplan); the slot's stream is what mjw_temit / mjw_temit_optimized write for
@@ -710,8 +733,8 @@ int mij_enc_slot_restart(const mij_encoder *e, int slot);
  * must not be reset, uploaded again, walked again or destroyed until then.
  *
  * mij_enc_slot_status: after mij_enc_fetch_streams (MIJ_E_STATE before), for a slot of any kind: MIJ_ENC_SLOT_OK, MIJ_ENC_SLOT_NO_ROOM
- * (it did not fit the arena: finish it on the host from its units) or MIJ_ENC_SLOT_UNCODABLE (never for slots that are not coefficient
- * slots); mij_last_error says the same in words.
+ * (it did not fit the arena: finish it on the host from its units), MIJ_ENC_SLOT_UNCODABLE (never for slots that are not coefficient
+ * slots) or MIJ_ENC_SLOT_HOST_FLUSH (a progressive slot the host finishes: mij_enc_set_progressive); mij_last_error says the same in words.
  * mij_enc_coef_ms: measurement: milliseconds the conversion kernels of the last mij_enc_upload took, -1 when there were none.
  *
  * mij_enc_add_coef_oriented: the same slot with one of the eight EXIF orientations applied to the coefficients on the way (lossless
@@ -744,7 +767,7 @@ int mij_enc_slot_restart(const mij_encoder *e, int slot);
  * changed the picture), 0 for a plain one; MIJ_E_ARG for any other slot.
  * mij_enc_coef_tiles: the number of plane tiles the last mij_enc_upload queued for conversion, over all its coefficient slots.
  */
-enum { MIJ_ENC_SLOT_OK = 0, MIJ_ENC_SLOT_NO_ROOM = 1, MIJ_ENC_SLOT_UNCODABLE = 2 };
+enum { MIJ_ENC_SLOT_OK = 0, MIJ_ENC_SLOT_NO_ROOM = 1, MIJ_ENC_SLOT_UNCODABLE = 2, MIJ_ENC_SLOT_HOST_FLUSH = 3 };
 int mij_enc_add_coef(mij_encoder *e, mij_batch *b, int slot);
 int mij_enc_add_coef_oriented(mij_encoder *e, mij_batch *b, int slot, int orientation, int trim);
 int mij_enc_add_coef_requant(mij_encoder *e, mij_batch *b, int slot, int orientation, int trim, const unsigned char *luma,

@@ -433,6 +433,90 @@ int mjh_transcode_memory_restart_by(const uint8_t *src, int len, unsigned flags,
                                     const unsigned char *chroma, int coarsen_only, int restart_rows, int restart_mcus, unsigned char **out,
                                     size_t *out_len, int *rect_out, int *ri_out, const char **reason);
 
+/*
+ * PROGRESSIVE STREAMS (jpegtran -progressive): the same units, so the same coefficients to the bit, written as a multi-scan SOF2 stream whose
+ * bytes are libjpeg's for those coefficients.  Restart intervals are not combined with it (libjpeg re-emits DRI per scan with a per-scan
+ * interval): these calls take none.  Arbitrary scan scripts are not taken either.
+ *
+ * STREAM.  SOI, APP0 and DQT exactly as the plan's baseline stream has them; the frame header of that stream under marker FF C2; then the
+ * scans of libjpeg's jpeg_simple_progression; EOI.  Every scan is: one DHT segment (FF C4, one table) per table the scan uses, SOS, its
+ * entropy-coded segment, filled at its end as the baseline scan is (seven 1-bits, what remains below a byte dropped, 0xFF stuffed).
+ * Notation `components: Ss-Se Ah Al`; components are 1 luma, 2 Cb, 3 Cr:
+ *   three components, MJW_PROGRESSIVE_SCANS_COLOUR = 10 scans
+ *      1,2,3: 0-0 0 1   interleaved, DC tables 0, 1, 1 (two DHT segments: id 0, then id 1)
+ *      1: 1-5 0 2       3: 1-63 0 1      2: 1-63 0 1      1: 6-63 0 2      1: 1-63 2 1
+ *      1,2,3: 0-0 1 0   no table
+ *      3: 1-63 1 0      2: 1-63 1 0      1: 1-63 1 0      (Cr before Cb in both chroma pairs)
+ *   grey, MJW_PROGRESSIVE_SCANS_GREY = 6 scans:   0-0 0 1,  1-5 0 2,  6-63 0 2,  1-63 2 1,  0-0 1 0,  1-63 1 0
+ * Every AC scan carries one DHT segment of class 1: id 0 for luma, id 1 for chroma.  In SOS a component's table byte names its DC table only
+ * in the first DC scan and its AC table only in AC scans; the rest is 0.
+ * TABLES.  Each table is mjw_optimal_table of the counts of the symbols that scan codes with it (Cb and Cr add into DC table 1), the pending
+ * run's EOBn at the scan's end included.  There is no plain-table fallback: no Annex-K table has EOBn codes, so where mjw_optimal_table
+ * refuses (a code longer than 32 bits before limiting) the call returns 0.
+ *
+ * SEMANTICS, libjpeg's jcphuff.c.  Unit coefficient k is zigzag k, so a band Ss..Se is unit[Ss..Se].
+ *   DC, first scan      v = unit[0] >> Al, the ARITHMETIC shift (-1 >> 1 = -1); the difference against the previous v of the component in MCU
+ *                       order (from 0) is coded as the baseline DC is: category symbol, then the category's bits.
+ *   DC, refinement      one bit per unit: bit Al of unit[0] (of its two's complement), no symbol.
+ *   DC scans            are interleaved: every unit of every MCU, padding units included, in the writer's unit order.
+ *   AC scans            take one component and visit its ceil(w_i / 8) x ceil(h_i / 8) blocks in raster order -- w_i, h_i the component's own
+ *                       size: the picture's for luma, ceil(W / lh) x ceil(H / lv) for chroma.  MCU padding blocks are not coded there.
+ *   AC, first scan      a = |c| >> Al, shifted TOWARDS ZERO.  a == 0 counts into the zero run r.  Otherwise: the pending EOB run is flushed,
+ *                       one 0xF0 per sixteen of r, then symbol (r << 4) + category(a) and category(a) bits: a, or ~a for c < 0.  A block whose
+ *                       band ends in zeros (r > 0) adds one to EOBRUN.
+ *   EOB RUNS            EOBRUN is folded across the blocks of the scan.  A flush writes symbol n << 4, n = floor(log2(EOBRUN)), then the low n
+ *                       bits of EOBRUN, then the correction bits buffered behind the run.  It is flushed in front of the next coded symbol,
+ *                       at the scan's end, and at once when it reaches 0x7FFF.
+ *   AC, refinement      a = |c| >> Al.  a == 0: r grows.  a > 1 (already non-zero): its correction bit a & 1 is BUFFERED.  a == 1 (newly
+ *                       non-zero): EOB run flushed, symbol (r << 4) + 1, one sign bit (1 for c > 0), then the buffered correction bits, r = 0.
+ *                       While r > 15 and a newly non-zero coefficient still follows in the band: EOB run flushed, 0xF0, the buffered
+ *                       correction bits, r -= 16 -- so correction bits stand behind the symbol that covers them: behind the first ZRL of a
+ *                       run, otherwise behind symbol and sign.  A block that ends with r > 0 or with correction bits buffered adds one to
+ *                       EOBRUN, and its trailing correction bits join the run's buffer.  The run is flushed at once when it reaches 0x7FFF
+ *                       or when more than MJW_PROGRESSIVE_MAX_CORR_BITS - 64 + 1 = 937 correction bits are pending.
+ *
+ * CAPACITY.  MJW_PROGRESSIVE_STREAM_CAP(units) holds any such stream.  Per unit, every code at most 16 bits: the DC scans take at most
+ * 16 + 11 and 1 bits.  A first AC scan takes at most 16 + 10 bits per coefficient position (a ZRL's 16 bits cover sixteen positions) and an
+ * EOBn of at most 16 + 14; a refinement scan at most 16 + 1 per position and the same EOBn.  A luma unit lies in two first scans that share its
+ * 63 positions and in two refinement scans: 28 + 63 * 26 + 2 * 30 + 2 * (63 * 17 + 30) = 3928 bits; a chroma unit in one of each: fewer.
+ * 3928 bits are 491 bytes, every one of which may be a 0xFF that takes a stuffed zero: 982 <= 1024.  Outside the units: SOI .. SOF2 at most
+ * 173 bytes, EOI 2, and per scan at most two DHT segments of 5 + 16 + 256 bytes, an SOS of 14 and a fill byte that may be stuffed:
+ * 10 * (2 * 277 + 14 + 2) = 5700.  So 6144 + 1024 per unit.
+ *
+ *   mjw_[t]emit_progressive[_to_memory]   the stream of a plan's (transcode plan's) units; 0 on bad arguments, for units outside
+ *                          mjw_tunits_codable's ranges (judged as for the baseline stream; the shifted DC differences are no larger), where
+ *                          a table cannot be built, or when cap is too small
+ *   mjw_tprogressive_stats what the writer met on the way, without writing: how often a run was flushed for its length or for its pending bits,
+ *                          the longest run and the most correction bits a flush carried.  GPU emission (mij_enc_set_progressive, mij.h) hands
+ *                          slots with a forced flush to this writer; the tests hold their inputs against these counters.
+ *   mjw_transcode_memory_progressive_at   mjw_transcode_memory_window_at with the request: progressive 0 is that call byte for byte, 1 emits
+ *                          the destination's units (after grey, orientation, crop and requantisation) with mjw_temit_progressive;
+ *                          MJW_OPTIMIZE_HUFFMAN is implied, MJW_COPY_MARKERS works as before.  Any other value is refused.
+ *   mjh_transcode_memory_progressive      the same with o = 0 meaning the file's own tag
+ */
+#define MJW_PROGRESSIVE_SCANS_COLOUR 10
+#define MJW_PROGRESSIVE_SCANS_GREY 6
+#define MJW_PROGRESSIVE_MAX_CORR_BITS 1000
+#define MJW_PROGRESSIVE_STREAM_CAP(units) ((size_t)6144 + (size_t)(units) * 1024)
+typedef struct {
+	uint32_t forced_run_flushes; /* runs flushed because they reached 0x7FFF blocks */
+	uint32_t forced_bit_flushes; /* runs flushed because more than 937 correction bits were pending */
+	uint32_t longest_run;        /* blocks */
+	uint32_t most_pending_bits;  /* correction bits one flush carried */
+} mjw_progressive_stats;
+int mjw_emit_progressive(const mjw_plan *p, const int16_t *du, mjw_write_func *func, void *context);
+int mjw_temit_progressive(const mjw_tplan *t, const int16_t *du, mjw_write_func *func, void *context);
+size_t mjw_emit_progressive_to_memory(const mjw_plan *p, const int16_t *du, unsigned char *out, size_t cap);
+size_t mjw_temit_progressive_to_memory(const mjw_tplan *t, const int16_t *du, unsigned char *out, size_t cap);
+int mjw_tprogressive_stats(const mjw_tplan *t, const int16_t *du, mjw_progressive_stats *st);
+size_t mjw_tframe_progressive(const mjw_tplan *t, unsigned char *out); /* SOI .. SOF2 of the stream, at most 173 bytes; 0 for a bad plan */
+int mjw_transcode_memory_progressive_at(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
+                                        const unsigned char *chroma, int coarsen_only, int progressive, unsigned char **out, size_t *out_len,
+                                        int *rect_out, const char **reason);
+int mjh_transcode_memory_progressive(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
+                                     const unsigned char *chroma, int coarsen_only, int progressive, unsigned char **out, size_t *out_len,
+                                     int *rect_out, const char **reason);
+
 /* The tables of stbi__ldr_to_hdr(common.c:391-424) for mij_batch_set_out_f32: lut[256*k + v] for channel k < n_out.  Colour
  * channels (all of them for odd n_out, all but the last for even n_out) get (float)(pow(v / 255.0f, gamma) * scale), the
  * alpha channel of n_out 2 and 4 gets v / 255.0f -- the reference's expressions, evaluated with libm's pow. */
