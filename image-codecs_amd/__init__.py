@@ -59,6 +59,12 @@ from .binding import (  # noqa: F401
     transcode_plan_cropped,
     units_crop,
     quality_tables,
+    SAMPLINGS,
+    sampling_factors,
+    sampling_name,
+    sampled_plan,
+    host_transform_sampled,
+    write_jpg_sampled_to_memory,
     requant_magic,
     transcode_plan_requant,
     units_requant,

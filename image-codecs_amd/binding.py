@@ -1452,6 +1452,96 @@ def quality_tables(quality):
     return luma, chroma
 
 
+SAMPLINGS = {"444": (3, 1, 1), "422": (3, 2, 1), "440": (3, 1, 2), "420": (3, 2, 2), "grey": (1, 1, 1)}
+
+
+def sampling_factors(sampling):
+    """a sampling name -> (ncomp, lh, lv) (include/mij_host.h, SAMPLED ENCODING); None -> (0, 0, 0), the writer's own choice;
+    ValueError for any other value"""
+    if sampling is None:
+        return (0, 0, 0)
+    if not isinstance(sampling, str) or sampling not in SAMPLINGS:
+        raise ValueError("sampling must be None or one of %s (got %r)" % (", ".join(repr(k) for k in SAMPLINGS), sampling))
+    return SAMPLINGS[sampling]
+
+
+def sampling_name(tplan):
+    """the name of a TranscodePlan's sampling"""
+    key = (1, 1, 1) if tplan.ncomp == 1 else (tplan.ncomp, tplan.lh, tplan.lv)
+    return {v: k for k, v in SAMPLINGS.items()}[key]
+
+
+class EncOpts(C.Structure):
+    """mij_enc_opts (include/mij.h)."""
+    _fields_ = [("ncomp", C.c_int), ("lh", C.c_int), ("lv", C.c_int), ("luma", C.c_char_p), ("chroma", C.c_char_p)]
+
+
+def enc_opts(sampling=None, qtables=None):
+    """-> an EncOpts, or None when neither is given (the plain calls).  ValueError for an unknown name or bad tables."""
+    ncomp, lh, lv = sampling_factors(sampling)
+    luma, chroma = (None, None) if qtables is None else _qtable_pair(qtables)
+    if not ncomp and luma is None:
+        return None
+    return EncOpts(ncomp, lh, lv, luma, chroma)
+
+
+def sampled_plan(width, height, comp, quality=90, sampling=None, qtables=None):
+    """mjw_splan_init -> TranscodePlan; None where the writer refuses the picture"""
+    L = lib()
+    o = enc_opts(sampling, qtables) or EncOpts()
+    t = TranscodePlan()
+    L.mjw_splan_init.argtypes = [C.POINTER(TranscodePlan), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p]
+    if not L.mjw_splan_init(C.byref(t), int(width), int(height), int(comp), int(quality), o.ncomp, o.lh, o.lv, o.luma, o.chroma):
+        return None
+    return t
+
+
+def _hwc_u8(pixels):
+    a = np.ascontiguousarray(pixels, dtype=np.uint8)
+    return a[:, :, None] if a.ndim == 2 else a
+
+
+def host_transform_sampled(pixels, quality=90, sampling=None, qtables=None, flip=False):
+    """mjw_splan_init + mjw_stransform_host: the units of a sampled slot computed on the HOST -> (TranscodePlan, int16 [n_du, 64]); the
+    CPU twin of Encoder.add(..., sampling=, qtables=)."""
+    a = _hwc_u8(pixels)
+    h, w, comp = a.shape
+    t = sampled_plan(w, h, comp, quality, sampling, qtables)
+    if t is None:
+        return None, None
+    L = lib()
+    L.mjw_stransform_host.argtypes = [C.POINTER(TranscodePlan), C.c_void_p, C.c_int, C.c_void_p]
+    du = np.empty(t.du_elems(), dtype=np.int16)
+    L.mjw_stransform_host(C.byref(t), a.ctypes.data_as(C.c_void_p), int(bool(flip)), du.ctypes.data_as(C.c_void_p))
+    return t, du.reshape(-1, 64)
+
+
+def write_jpg_sampled_to_memory(pixels, quality=90, sampling=None, qtables=None, flip=False, optimize=False, restart_rows=None, restart_mcus=None,
+                                progressive=False):
+    """mjh_write_jpg_sampled_to_memory: the host writer with a sampling ("444", "422", "440", "420", "grey"; None: the writer's own) and
+    / or (luma, chroma) tables -> bytes, None where it refuses.  restart_rows counts MCU rows of the sampling's own MCU size."""
+    a = _hwc_u8(pixels)
+    h, w, comp = a.shape
+    o = enc_opts(sampling, qtables) or EncOpts()
+    rows, mcus = _restart_mcus(restart_rows), _restart_mcus(restart_mcus)
+    if rows and mcus:
+        raise ValueError("restart_rows and restart_mcus are two ways to say the same thing: give one")
+    if rows:
+        t = sampled_plan(w, h, comp, quality, sampling, qtables)
+        if t is None:
+            return None
+        mcus = rows * t.plan.mcu_x
+    prog = _progressive_flag(progressive, mcus)
+    L = lib()
+    L.mjh_write_jpg_sampled_to_memory.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
+                                                  C.c_int, C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    out, n = C.c_void_p(), C.c_size_t()
+    if not L.mjh_write_jpg_sampled_to_memory(a.ctypes.data_as(C.c_void_p), w, h, comp, int(quality), o.ncomp, o.lh, o.lv, o.luma, o.chroma,
+                                             int(bool(flip)), MJW_OPTIMIZE_HUFFMAN if optimize else 0, mcus, int(prog), C.byref(out), C.byref(n)):
+        return None
+    return _take_malloced(out, n.value)
+
+
 def requant_magic(b):
     """mjw_requant_magic -> (m, inc): n // b == ((n + inc) * m) >> 32 for every n < 2^24, the division of the conversion kernel"""
     L = lib()
@@ -1765,12 +1855,19 @@ class Encoder:
     def reset(self):
         _check(lib().mij_enc_reset(self._h), "mij_enc_reset")
 
-    def add(self, pixels, quality=90, flip=False):
+    def add(self, pixels, quality=90, flip=False, sampling=None, qtables=None):
+        """mij_enc_add; with sampling ("444", "422", "440", "420", "grey") and / or qtables ((luma, chroma), 64 ints 1..255 each in zigzag
+        order) mij_enc_add_ex: a slot with a sampling or tables of its own (include/mij_host.h, SAMPLED ENCODING)."""
         a = np.ascontiguousarray(pixels, dtype=np.uint8)
         if a.ndim == 2:
             a = a[:, :, None]
         h, w, comp = a.shape
-        return _check(lib().mij_enc_add(self._h, a.ctypes.data_as(C.c_void_p), w, h, comp, int(quality), int(bool(flip))), "mij_enc_add")
+        o = enc_opts(sampling, qtables)
+        if o is None:
+            return _check(lib().mij_enc_add(self._h, a.ctypes.data_as(C.c_void_p), w, h, comp, int(quality), int(bool(flip))), "mij_enc_add")
+        L = lib()
+        L.mij_enc_add_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncOpts)]
+        return _check(L.mij_enc_add_ex(self._h, a.ctypes.data_as(C.c_void_p), w, h, comp, int(quality), int(bool(flip)), C.byref(o)), "mij_enc_add_ex")
 
     def add_clone(self, src):
         return _check(lib().mij_enc_add_clone(self._h, int(src)), "mij_enc_add_clone")
@@ -1801,16 +1898,27 @@ class Encoder:
         _check(lib().mij_enc_fetch(self._h, int(slot), du.ctypes.data_as(C.c_void_p), C.c_size_t(du.size)), "mij_enc_fetch")
         return du.reshape(-1, 64)
 
-    def add_device(self, t, quality=90, flip=False):
-        """mij_enc_add_device: a slot whose uint8 pixels lie in device memory, described by an InTensor."""
+    def add_device(self, t, quality=90, flip=False, sampling=None, qtables=None):
+        """mij_enc_add_device: a slot whose uint8 pixels lie in device memory, described by an InTensor.  sampling, qtables: as for add
+        (mij_enc_add_device_ex)."""
         L = lib()
+        o = enc_opts(sampling, qtables)
+        if o is not None:
+            L.mij_enc_add_device_ex.argtypes = [C.c_void_p, C.POINTER(InTensor), C.c_int, C.c_int, C.POINTER(EncOpts)]
+            return _check(L.mij_enc_add_device_ex(self._h, C.byref(t), int(quality), int(bool(flip)), C.byref(o)), "mij_enc_add_device_ex")
         L.mij_enc_add_device.argtypes = [C.c_void_p, C.POINTER(InTensor), C.c_int, C.c_int]
         return _check(L.mij_enc_add_device(self._h, C.byref(t), int(quality), int(bool(flip))), "mij_enc_add_device")
 
-    def add_device_float(self, t, convert, quality=90, flip=False):
+    def add_device_float(self, t, convert, quality=90, flip=False, sampling=None, qtables=None):
         """mij_enc_add_device_float: a slot whose float16 / bfloat16 / float32 elements lie in device memory, described by an InTensor
-        (pitches in elements), de-normalised on the GPU by the contract of include/mij.h with the InConvert's scale and bias."""
+        (pitches in elements), de-normalised on the GPU by the contract of include/mij.h with the InConvert's scale and bias.  sampling,
+        qtables: as for add (mij_enc_add_device_float_ex)."""
         L = lib()
+        o = enc_opts(sampling, qtables)
+        if o is not None:
+            L.mij_enc_add_device_float_ex.argtypes = [C.c_void_p, C.POINTER(InTensor), C.POINTER(InConvert), C.c_int, C.c_int, C.POINTER(EncOpts)]
+            return _check(L.mij_enc_add_device_float_ex(self._h, C.byref(t), C.byref(convert), int(quality), int(bool(flip)), C.byref(o)),
+                          "mij_enc_add_device_float_ex")
         L.mij_enc_add_device_float.argtypes = [C.c_void_p, C.POINTER(InTensor), C.POINTER(InConvert), C.c_int, C.c_int]
         return _check(L.mij_enc_add_device_float(self._h, C.byref(t), C.byref(convert), int(quality), int(bool(flip))), "mij_enc_add_device_float")
 
@@ -1889,7 +1997,7 @@ class Encoder:
         return bool(_check(L.mij_enc_slot_requantized(self._h, int(slot)), "mij_enc_slot_requantized"))
 
     def tplan(self, slot):
-        """mij_enc_tplan: the TranscodePlan of a slot made by add_coef"""
+        """mij_enc_tplan: the TranscodePlan of a slot made by add_coef, or by add / add_device / add_device_float with a sampling or tables"""
         L = lib()
         L.mij_enc_tplan.argtypes = [C.c_void_p, C.c_int, C.POINTER(TranscodePlan)]
         t = TranscodePlan()

@@ -1429,6 +1429,140 @@ size_t mjw_emit_progressive_to_memory(const mjw_plan *p, const int16_t *du, unsi
 	return m.len;
 }
 
+/* ---- sampled encoding (include/mij_host.h, SAMPLED ENCODING): the writer's transform over the five MCU shapes, under the tables of a
+ * quality or given ones */
+
+int mjw_splan_init(mjw_tplan *t, int width, int height, int comp, int quality, int ncomp, int lh, int lv, const unsigned char *luma,
+                   const unsigned char *chroma)
+{
+	static const float aasf[8] = {1.0f * 2.828427125f,         1.387039845f * 2.828427125f, 1.306562965f * 2.828427125f, 1.175875602f * 2.828427125f,
+											1.0f * 2.828427125f,         0.785694958f * 2.828427125f, 0.541196100f * 2.828427125f, 0.275899379f * 2.828427125f};
+	mjw_plan *p;
+	int row, col, k;
+	if (!t || !mjw_plan_init(&t->plan, width, height, comp, quality) || !luma != !chroma)
+		return 0;
+	p = &t->plan;
+	if (!ncomp) /* the writer's own choice for the quality */
+		ncomp = 3, lh = lv = p->subsample ? 2 : 1;
+	if (ncomp == 1 ? (lh != 1 || lv != 1) : (ncomp != 3 || lh < 1 || lh > 2 || lv < 1 || lv > 2))
+		return 0;
+	if (luma) {
+		for (k = 0; k < 64; ++k)
+			if (!luma[k] || !chroma[k])
+				return 0;
+		memcpy(p->ytab, luma, 64);
+		memcpy(p->ctab, chroma, 64);
+		for (row = 0, k = 0; row < 8; ++row)
+			for (col = 0; col < 8; ++col, ++k) {
+				p->fdtbl_y[k] = 1 / (p->ytab[k_zigzag_of[k]] * aasf[row] * aasf[col]);
+				p->fdtbl_c[k] = 1 / (p->ctab[k_zigzag_of[k]] * aasf[row] * aasf[col]);
+			}
+	}
+	t->ncomp = ncomp;
+	t->lh = lh;
+	t->lv = lv;
+	p->subsample = ncomp == 3 && lh == 2 && lv == 2;
+	p->mcu_x = (width + 8 * lh - 1) / (8 * lh);
+	p->mcu_y = (height + 8 * lv - 1) / (8 * lv);
+	p->du_per_mcu = ncomp == 1 ? 1 : lh * lv + 2;
+	return 1;
+}
+
+void mjw_stransform_host(const mjw_tplan *t, const void *data, int flip, int16_t *du)
+{
+	const mjw_plan *p = &t->plan;
+	const int width = p->width, height = p->height, comp = p->comp;
+	const int og = comp > 2 ? 1 : 0, ob = comp > 2 ? 2 : 0;
+	const unsigned char *px = (const unsigned char *)data;
+	const int mw = 8 * t->lh, mh = 8 * t->lv, npx = mw * mh;
+	int x, y, row, col, pos, i;
+	float Y[128], U[128], V[128], R[128], G[128], B[128], su[64], sv[64];
+	if (t->ncomp == 3 && t->lh == t->lv) { /* 4:2:0 and 4:4:4: the writer's own two shapes */
+		mjw_transform_host(p, data, flip, du);
+		return;
+	}
+	for (y = 0; y < height; y += mh)
+		for (x = 0; x < width; x += mw) {
+			for (row = y, pos = 0; row < y + mh; ++row) {
+				int crow = row < height ? row : height - 1; /* replicate the last row / column */
+				int base = (flip ? (height - 1 - crow) : crow) * width * comp;
+				for (col = x; col < x + mw; ++col, ++pos) {
+					int q = base + (col < width ? col : width - 1) * comp;
+					R[pos] = px[q], G[pos] = px[q + og], B[pos] = px[q + ob];
+				}
+			}
+			/* mjw_transform_host's expressions and association */
+			for (pos = 0; pos < npx; pos += 4) {
+				const __m128 r = _mm_loadu_ps(R + pos), g = _mm_loadu_ps(G + pos), b = _mm_loadu_ps(B + pos);
+				_mm_storeu_ps(Y + pos, _mm_sub_ps(_mm_add_ps(_mm_add_ps(_mm_mul_ps(_mm_set1_ps(+0.29900f), r), _mm_mul_ps(_mm_set1_ps(0.58700f), g)),
+																			  _mm_mul_ps(_mm_set1_ps(0.11400f), b)), _mm_set1_ps(128.0f)));
+				if (t->ncomp == 1)
+					continue;
+				_mm_storeu_ps(U + pos, _mm_add_ps(_mm_sub_ps(_mm_mul_ps(_mm_set1_ps(-0.16874f), r), _mm_mul_ps(_mm_set1_ps(0.33126f), g)),
+															 _mm_mul_ps(_mm_set1_ps(0.50000f), b)));
+				_mm_storeu_ps(V + pos, _mm_sub_ps(_mm_sub_ps(_mm_mul_ps(_mm_set1_ps(+0.50000f), r), _mm_mul_ps(_mm_set1_ps(0.41869f), g)),
+															 _mm_mul_ps(_mm_set1_ps(0.08131f), b)));
+			}
+			if (t->ncomp == 1) {
+				transform_du(Y, 8, p->fdtbl_y, du);
+				du += 64;
+				continue;
+			}
+			if (t->lh == 2) { /* 4:2:2: 16 x 8 pixels, the mean of (left, right) */
+				transform_du(Y + 0, 16, p->fdtbl_y, du);
+				transform_du(Y + 8, 16, p->fdtbl_y, du + 64);
+				for (i = 0; i < 64; ++i) {
+					const int j = (i >> 3) * 16 + (i & 7) * 2;
+					su[i] = (U[j] + U[j + 1]) * 0.5f;
+					sv[i] = (V[j] + V[j + 1]) * 0.5f;
+				}
+			} else { /* 4:4:0: 8 x 16 pixels, the mean of (top, bottom) */
+				transform_du(Y + 0, 8, p->fdtbl_y, du);
+				transform_du(Y + 64, 8, p->fdtbl_y, du + 64);
+				for (i = 0; i < 64; ++i) {
+					const int j = (i >> 3) * 16 + (i & 7);
+					su[i] = (U[j] + U[j + 8]) * 0.5f;
+					sv[i] = (V[j] + V[j + 8]) * 0.5f;
+				}
+			}
+			transform_du(su, 8, p->fdtbl_c, du + 128);
+			transform_du(sv, 8, p->fdtbl_c, du + 192);
+			du += 256;
+		}
+}
+
+int mjh_write_jpg_sampled_to_memory(const void *pixels, int width, int height, int comp, int quality, int ncomp, int lh, int lv,
+                                    const unsigned char *luma, const unsigned char *chroma, int flip, unsigned flags, int restart_mcus,
+                                    int progressive, unsigned char **out, size_t *out_len)
+{
+	mjw_tplan t;
+	int16_t *du;
+	unsigned char *buf;
+	size_t nu, cap, n;
+	if (!pixels || !out || !out_len || (flags & ~MJW_OPTIMIZE_HUFFMAN) || !ri_ok(restart_mcus) || (progressive && restart_mcus) ||
+		 !mjw_splan_init(&t, width, height, comp, quality, ncomp, lh, lv, luma, chroma))
+		return 0;
+	nu = mjw_tplan_du_count(&t);
+	cap = progressive ? MJW_PROGRESSIVE_STREAM_CAP(nu) : MJW_STREAM_CAP(nu);
+	du = (int16_t *)malloc(nu * 64 * sizeof(int16_t));
+	buf = (unsigned char *)malloc(cap);
+	if (!du || !buf) {
+		free(du);
+		free(buf);
+		return 0;
+	}
+	mjw_stransform_host(&t, pixels, flip, du);
+	n = progressive ? mjw_temit_progressive_to_memory(&t, du, buf, cap) : mjw_temit_restart_to_memory(&t, du, flags, restart_mcus, buf, cap);
+	free(du);
+	if (!n) {
+		free(buf);
+		return 0;
+	}
+	*out = buf;
+	*out_len = n;
+	return 1;
+}
+
 int stbi_write_jpg_to_func(stbi_write_func *func, void *context, int x, int y, int comp, const void *data, int quality)
 {
 	mjw_plan plan;

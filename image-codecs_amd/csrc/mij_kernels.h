@@ -3130,6 +3130,269 @@ __global__ __launch_bounds__(192) void k_encode444(const EncImage *__restrict__ 
 	}
 }
 
+/* ------------------------------------------------------------------ sampled encoders: 4:2:2, 4:4:0 and grey (include/mij_host.h, SAMPLED ENCODING)
+ *
+ * The strip design of k_encode420 / k_encode444 for the three other MCU shapes a pixel slot can ask for (mij_enc_add_ex): one workgroup
+ * owns a strip of consecutive MCUs (MCU index order, so a strip may run over the end of an MCU row), reads its staged packed-RGB rows
+ * from HBM once with coalesced 8- or 16-byte loads into LDS, converts each byte once per component that needs it, stages the finished
+ * units in LDS (enc_du_chunk's swizzle) over the dead pixel rows and writes the strip's contiguous cnt * du_per_mcu * 128 bytes with
+ * coalesced 16-byte stores.  Rows are staged as whole MCU columns (enc_padded_width), so there is no column clamp; rows past the picture
+ * repeat the last one (EncPix::row_base).  64-bit slot offsets, 32-bit offsets inside a slot.
+ *   k_encode422    32 MCUs of 16 x 8: 8 rows x 1536 B.  Wave 0: lane = (MCU, left | right luma block), Y straight into the row-pair form,
+ *                  the horizontal (left + right) * 0.5f means of Cb and Cr as (row 2k, row 2k+1) pairs into a float stage.  Wave 1: lane =
+ *                  (MCU, Cb | Cr), its unit read back from the stage.  Algorithmic bytes 3 + 4 per pixel.
+ *   k_encode440    64 MCUs of 8 x 16: 16 rows x 1536 B.  Waves 0 / 1: lane = MCU, the top / bottom luma block; the vertical mean is
+ *                  (W.x + W.y) * 0.5f of the (top, bottom) pairs the conversion builds anyway, two of them making one row pair of the
+ *                  chroma unit.  Waves 2 / 3: lane = MCU, Cb / Cr from the stage.  3 + 4 bytes per pixel.
+ *   k_encode_grey  256 MCUs of 8 x 8: 8 rows x 6144 B, four waves, lane = MCU, Y only.  3 + 2 bytes per pixel.
+ * The float stage (256 B per chroma unit, 16-byte chunks swizzled with the unit index) lies behind the pixel rows / staged units.
+ */
+#define MIJ_ENC422_STRIP 32
+#define MIJ_ENC422_PIXROW (MIJ_ENC422_STRIP * 48)
+#define MIJ_ENC422_LDS_A (MIJ_ENC422_STRIP * 4 * MIJ_ENC_DUPITCH) /* staged units; the pixel rows (8 x 1536 B) lie inside */
+#define MIJ_ENC422_LDS (MIJ_ENC422_LDS_A + MIJ_ENC422_STRIP * 2 * MIJ_ENC_CPITCH)
+#define MIJ_ENC440_STRIP 64
+#define MIJ_ENC440_PIXROW (MIJ_ENC440_STRIP * 24)
+#define MIJ_ENC440_LDS_A (MIJ_ENC440_STRIP * 4 * MIJ_ENC_DUPITCH) /* staged units; the pixel rows (16 x 1536 B) lie inside */
+#define MIJ_ENC440_LDS (MIJ_ENC440_LDS_A + MIJ_ENC440_STRIP * 2 * MIJ_ENC_CPITCH)
+#define MIJ_ENCGREY_STRIP 256
+#define MIJ_ENCGREY_PIXROW (MIJ_ENCGREY_STRIP * 24)
+#define MIJ_ENCGREY_LDS (8 * MIJ_ENCGREY_PIXROW) /* the pixel rows; the staged units (256 x 128 B) lie inside */
+
+/* 16-byte chunk h16 = 4 * (row pair) + (column pair) of chroma unit u's 64 floats in the stage at `base`: four floats = two columns x
+ * (row 2k, row 2k + 1) */
+__device__ __forceinline__ int enc_stage_chunk(int base, int u, int h16) { return base + u * MIJ_ENC_CPITCH + ((h16 ^ (u & 15)) << 4); }
+
+/* a chroma unit's row-pair form back from the stage */
+__device__ __forceinline__ void enc_stage_read(const uint8_t *lds, int base, int u, f2 (&V)[4][8])
+{
+#pragma unroll
+	for (int k = 0; k < 4; ++k)
+#pragma unroll
+		for (int h = 0; h < 4; ++h) {
+			const float4 f = *reinterpret_cast<const float4 *>(lds + enc_stage_chunk(base, u, 4 * k + h));
+			V[k][2 * h] = (f2){f.x, f.y};
+			V[k][2 * h + 1] = (f2){f.z, f.w};
+		}
+}
+
+/* The strip's pixel rows into LDS: ROWS rows of STRIP MCUs of MB bytes each, in chunks of sizeof(T) bytes, chunk c of a row by thread
+ * c % NT.  MCUs past the last one read any valid pixels (their units are dropped). */
+template <typename T, int MB, int ROWS, int STRIP, int NT>
+__device__ __forceinline__ void enc_strip_load(const EncPix &P, const EncImage &im, uint32_t m0, uint32_t nmcu, uint8_t *spx, int tid)
+{
+	constexpr int CB = (int)sizeof(T), PER = MB / CB, NCH = STRIP * PER;
+#pragma unroll
+	for (int c0 = 0; c0 < NCH; c0 += NT) {
+		const uint32_t c = (uint32_t)(c0 + tid);
+		if (NCH % NT != 0 && c >= (uint32_t)NCH)
+			break;
+		const uint32_t j = c / (uint32_t)PER, part = c - (uint32_t)PER * j;
+		const uint32_t m = min(m0 + j, nmcu - 1u);
+		const uint32_t my = m / (uint32_t)im.mcu_x, mx = m - my * (uint32_t)im.mcu_x;
+		const uint32_t cbase = mx * (uint32_t)MB + part * (uint32_t)CB;
+		T v[ROWS];
+#pragma unroll
+		for (int i = 0; i < ROWS; ++i)
+			v[i] = *reinterpret_cast<const T *>(P.px + P.row_base((int)((uint32_t)ROWS * my) + i) + cbase);
+#pragma unroll
+		for (int i = 0; i < ROWS; ++i)
+			*reinterpret_cast<T *>(spx + i * (STRIP * MB) + (int)c * CB) = v[i];
+		enc_row_fence();
+	}
+}
+
+/* the strip's cnt * DPM staged units out: contiguous bytes, coalesced 16-byte stores */
+template <int DPM, int NT>
+__device__ __forceinline__ void enc_strip_store(const EncImage &im, uint32_t m0, uint32_t cnt, const uint8_t *sdu, int16_t *du, int tid)
+{
+	uint8_t *out = reinterpret_cast<uint8_t *>(du) + im.du_off + (size_t)m0 * (size_t)(DPM * 128);
+	const int nchunk = (int)cnt * DPM * 8;
+	for (int g = tid; g < nchunk; g += NT) {
+		const uint4 t = *reinterpret_cast<const uint4 *>(sdu + enc_du_chunk(g >> 3, g & 7));
+		__builtin_nontemporal_store((u4v){t.x, t.y, t.z, t.w}, reinterpret_cast<u4v *>(out + (size_t)g * 16u));
+	}
+}
+
+/* rows (2k, 2k + 1) of a lane's eight 24-byte pixel rows (pitch PIXROW) as dwords */
+template <int PIXROW>
+__device__ __forceinline__ void enc_row_pair(const uint8_t *src, int k, uint32_t (&t)[6], uint32_t (&b)[6])
+{
+	const uint2 *tp = reinterpret_cast<const uint2 *>(src + (2 * k) * PIXROW);
+	const uint2 *bp = reinterpret_cast<const uint2 *>(src + (2 * k + 1) * PIXROW);
+	const uint2 t0 = tp[0], t1 = tp[1], t2 = tp[2], b0 = bp[0], b1 = bp[1], b2 = bp[2];
+	t[0] = t0.x, t[1] = t0.y, t[2] = t1.x, t[3] = t1.y, t[4] = t2.x, t[5] = t2.y;
+	b[0] = b0.x, b[1] = b0.y, b[2] = b1.x, b[3] = b1.y, b[4] = b2.x, b[5] = b2.y;
+}
+
+__global__ __launch_bounds__(128) void k_encode422(const EncImage *__restrict__ imgs, const WorkIdct *__restrict__ work, const uint8_t *__restrict__ pix,
+																	int16_t *__restrict__ du)
+{
+	extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+	uint8_t *const spx = lds; /* pixel rows, later the staged data units */
+	uint8_t *const sdu = lds;
+	const WorkIdct wk = work[blockIdx.x];
+	const EncImage &im = imgs[wk.img];
+	const int tid = threadIdx.x;
+	const uint32_t nmcu = (uint32_t)(im.mcu_x * im.mcu_y);
+	const uint32_t m0 = wk.first;
+	const uint32_t cnt = min((uint32_t)MIJ_ENC422_STRIP, nmcu - m0);
+	EncPix P;
+	enc_setup(im, pix, P);
+	enc_strip_load<uint4, 48, 8, MIJ_ENC422_STRIP, 128>(P, im, m0, nmcu, spx, tid);
+	__syncthreads();
+
+	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+	f2 V[4][8];
+	if (wave == 0) {
+		const int j = lane >> 1, bx = lane & 1;
+		const uint8_t *src = spx + lane * 24;
+#pragma unroll
+		for (int k = 0; k < 4; ++k) {
+			uint32_t t[6], b[6];
+			enc_row_pair<MIJ_ENC422_PIXROW>(src, k, t, b);
+			f2 Wu[8], Wv[8];
+#define MIJ_ENC_PX(XI)                                                                                                      \
+	{                                                                                                                       \
+		const f2 r = enc_byte2<3 * (XI) + 0>(t, b), g = enc_byte2<3 * (XI) + 1>(t, b), bl = enc_byte2<3 * (XI) + 2>(t, b);      \
+		V[k][XI] = enc_component2<0>(r, g, bl);                                                                               \
+		Wu[XI] = enc_component2<1>(r, g, bl);                                                                                 \
+		Wv[XI] = enc_component2<2>(r, g, bl);                                                                                 \
+	}
+			MIJ_ENC_PX(0) MIJ_ENC_PX(1) MIJ_ENC_PX(2) MIJ_ENC_PX(3) MIJ_ENC_PX(4) MIJ_ENC_PX(5) MIJ_ENC_PX(6) MIJ_ENC_PX(7)
+#undef MIJ_ENC_PX
+			/* chroma columns 4 * bx .. 4 * bx + 3 of row pair k: (left + right) * 0.5f on both rows at once */
+			f2 Mu[4], Mv[4];
+#pragma unroll
+			for (int jj = 0; jj < 4; ++jj) {
+				Mu[jj] = (Wu[2 * jj] + Wu[2 * jj + 1]) * 0.5f;
+				Mv[jj] = (Wv[2 * jj] + Wv[2 * jj + 1]) * 0.5f;
+			}
+			const int h0 = 4 * k + 2 * bx;
+			*reinterpret_cast<float4 *>(lds + enc_stage_chunk(MIJ_ENC422_LDS_A, 2 * j, h0)) = make_float4(Mu[0].x, Mu[0].y, Mu[1].x, Mu[1].y);
+			*reinterpret_cast<float4 *>(lds + enc_stage_chunk(MIJ_ENC422_LDS_A, 2 * j, h0 + 1)) = make_float4(Mu[2].x, Mu[2].y, Mu[3].x, Mu[3].y);
+			*reinterpret_cast<float4 *>(lds + enc_stage_chunk(MIJ_ENC422_LDS_A, 2 * j + 1, h0)) = make_float4(Mv[0].x, Mv[0].y, Mv[1].x, Mv[1].y);
+			*reinterpret_cast<float4 *>(lds + enc_stage_chunk(MIJ_ENC422_LDS_A, 2 * j + 1, h0 + 1)) = make_float4(Mv[2].x, Mv[2].y, Mv[3].x, Mv[3].y);
+			enc_row_fence();
+		}
+	}
+	__syncthreads(); /* pixel rows dead, chroma means staged */
+
+	if (wave == 1)
+		enc_stage_read(lds, MIJ_ENC422_LDS_A, lane, V);
+	{
+		/* one instance of the transform for both waves, its quantiser table behind one wave-uniform pointer (see k_encode420) */
+		const float *fd = wave == 1 ? im.fc : im.fy;
+		const int u = (lane >> 1) * 4 + 2 * wave + (lane & 1);
+		fdct_quant_store<0>(V, fd, reinterpret_cast<int16_t *>(sdu + u * MIJ_ENC_DUPITCH), u & 7);
+	}
+	__syncthreads();
+	enc_strip_store<4, 128>(im, m0, cnt, sdu, du, tid);
+}
+
+__global__ __launch_bounds__(256) void k_encode440(const EncImage *__restrict__ imgs, const WorkIdct *__restrict__ work, const uint8_t *__restrict__ pix,
+																	int16_t *__restrict__ du)
+{
+	extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+	uint8_t *const spx = lds; /* pixel rows, later the staged data units */
+	uint8_t *const sdu = lds;
+	const WorkIdct wk = work[blockIdx.x];
+	const EncImage &im = imgs[wk.img];
+	const int tid = threadIdx.x;
+	const uint32_t nmcu = (uint32_t)(im.mcu_x * im.mcu_y);
+	const uint32_t m0 = wk.first;
+	const uint32_t cnt = min((uint32_t)MIJ_ENC440_STRIP, nmcu - m0);
+	EncPix P;
+	enc_setup(im, pix, P);
+	enc_strip_load<uint2, 24, 16, MIJ_ENC440_STRIP, 256>(P, im, m0, nmcu, spx, tid);
+	__syncthreads();
+
+	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+	f2 V[4][8];
+	if (wave < 2) {
+		const uint8_t *src = spx + (8 * wave) * MIJ_ENC440_PIXROW + lane * 24;
+#pragma unroll
+		for (int kc = 0; kc < 2; ++kc) {
+			f2 Mu[8], Mv[8]; /* chroma rows (2 * wave + kc) * 2, + 1 of column x as one pair */
+#pragma unroll
+			for (int k2 = 0; k2 < 2; ++k2) {
+				const int k = 2 * kc + k2;
+				uint32_t t[6], b[6];
+				enc_row_pair<MIJ_ENC440_PIXROW>(src, k, t, b);
+#define MIJ_ENC_PX(XI)                                                                                                      \
+	{                                                                                                                       \
+		const f2 r = enc_byte2<3 * (XI) + 0>(t, b), g = enc_byte2<3 * (XI) + 1>(t, b), bl = enc_byte2<3 * (XI) + 2>(t, b);      \
+		V[k][XI] = enc_component2<0>(r, g, bl);                                                                               \
+		const f2 wu = enc_component2<1>(r, g, bl), wv = enc_component2<2>(r, g, bl);                                          \
+		const float mu = (wu.x + wu.y) * 0.5f, mv = (wv.x + wv.y) * 0.5f;                                                     \
+		if (k2 == 0)                                                                                                          \
+			Mu[XI].x = mu, Mv[XI].x = mv;                                                                                       \
+		else                                                                                                                  \
+			Mu[XI].y = mu, Mv[XI].y = mv;                                                                                       \
+	}
+				MIJ_ENC_PX(0) MIJ_ENC_PX(1) MIJ_ENC_PX(2) MIJ_ENC_PX(3) MIJ_ENC_PX(4) MIJ_ENC_PX(5) MIJ_ENC_PX(6) MIJ_ENC_PX(7)
+#undef MIJ_ENC_PX
+				enc_row_fence();
+			}
+			const int h0 = 4 * (2 * wave + kc);
+#pragma unroll
+			for (int h = 0; h < 4; ++h) {
+				*reinterpret_cast<float4 *>(lds + enc_stage_chunk(MIJ_ENC440_LDS_A, 2 * lane, h0 + h)) =
+					make_float4(Mu[2 * h].x, Mu[2 * h].y, Mu[2 * h + 1].x, Mu[2 * h + 1].y);
+				*reinterpret_cast<float4 *>(lds + enc_stage_chunk(MIJ_ENC440_LDS_A, 2 * lane + 1, h0 + h)) =
+					make_float4(Mv[2 * h].x, Mv[2 * h].y, Mv[2 * h + 1].x, Mv[2 * h + 1].y);
+			}
+		}
+	}
+	__syncthreads(); /* pixel rows dead, chroma means staged */
+
+	if (wave >= 2)
+		enc_stage_read(lds, MIJ_ENC440_LDS_A, 2 * lane + (wave - 2), V);
+	{
+		const float *fd = wave >= 2 ? im.fc : im.fy;
+		const int u = lane * 4 + wave;
+		fdct_quant_store<0>(V, fd, reinterpret_cast<int16_t *>(sdu + u * MIJ_ENC_DUPITCH), u & 7);
+	}
+	__syncthreads();
+	enc_strip_store<4, 256>(im, m0, cnt, sdu, du, tid);
+}
+
+__global__ __launch_bounds__(256) void k_encode_grey(const EncImage *__restrict__ imgs, const WorkIdct *__restrict__ work, const uint8_t *__restrict__ pix,
+																	  int16_t *__restrict__ du)
+{
+	extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+	uint8_t *const spx = lds; /* pixel rows, later the staged data units */
+	uint8_t *const sdu = lds;
+	const WorkIdct wk = work[blockIdx.x];
+	const EncImage &im = imgs[wk.img];
+	const int tid = threadIdx.x;
+	const uint32_t nmcu = (uint32_t)(im.mcu_x * im.mcu_y);
+	const uint32_t m0 = wk.first;
+	const uint32_t cnt = min((uint32_t)MIJ_ENCGREY_STRIP, nmcu - m0);
+	EncPix P;
+	enc_setup(im, pix, P);
+	enc_strip_load<uint2, 24, 8, MIJ_ENCGREY_STRIP, 256>(P, im, m0, nmcu, spx, tid);
+	__syncthreads();
+
+	f2 V[4][8];
+	{
+		const uint8_t *src = spx + tid * 24;
+#pragma unroll
+		for (int k = 0; k < 4; ++k) {
+			uint32_t t[6], b[6];
+			enc_row_pair<MIJ_ENCGREY_PIXROW>(src, k, t, b);
+#define MIJ_ENC_PX(XI) V[k][XI] = enc_component2<0>(enc_byte2<3 * (XI) + 0>(t, b), enc_byte2<3 * (XI) + 1>(t, b), enc_byte2<3 * (XI) + 2>(t, b));
+			MIJ_ENC_PX(0) MIJ_ENC_PX(1) MIJ_ENC_PX(2) MIJ_ENC_PX(3) MIJ_ENC_PX(4) MIJ_ENC_PX(5) MIJ_ENC_PX(6) MIJ_ENC_PX(7)
+#undef MIJ_ENC_PX
+			enc_row_fence();
+		}
+	}
+	__syncthreads(); /* pixel rows dead */
+	fdct_quant_store<0>(V, im.fy, reinterpret_cast<int16_t *>(sdu + tid * MIJ_ENC_DUPITCH), tid & 7);
+	__syncthreads();
+	enc_strip_store<1, 256>(im, m0, cnt, sdu, du, tid);
+}
+
 /* ------------------------------------------------------------------ float output (mij_batch_set_out_f32, stbi_loadf*)
  *
  * k_out_f32 turns a slot's decoded bytes into floats through one 256-entry table per channel: byte i of the slot uses the

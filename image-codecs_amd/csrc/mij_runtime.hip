@@ -3204,6 +3204,7 @@ struct EncSlot {
 	int coef_fmt;
 	int rect[4];                  /* the kept rectangle in the displayed frame (mij_enc_slot_rect) */
 	bool greyed;                  /* Cb and Cr of a colour source were dropped */
+	bool sampled;                 /* a pixel slot made with a sampling or tables of its own (mij_enc_add_ex and its kin): tp is its plan */
 	unsigned char rq_from[2][64]; /* a requantising slot (coef.rq != 0): the tables tp's replaced, luma and chroma, zigzag order */
 };
 
@@ -3222,7 +3223,8 @@ struct mij_encoder {
 	EncImage *h_imgs, *d_imgs;
 	WorkIdct *h_work, *d_work;
 	size_t work_cap;
-	size_t n_work[6], first_work[6]; /* [sub*2 + kind]: kind 0 luma units, 1 chroma units; [4]: fused 4:2:0 strips; [5]: fused 4:4:4 strips */
+	size_t n_work[9], first_work[9]; /* [sub*2 + kind]: kind 0 luma units, 1 chroma units; [4]: fused 4:2:0 strips; [5]: fused 4:4:4 strips;
+	                                    [6], [7], [8]: 4:2:2, 4:4:0 and grey strips (sampled slots) */
 	std::vector<EncSlot> slots;
 	bool uploaded, launched, force_generic;
 	/* device-pixel slots: the gather kernel's slots and work (rows of MIJ_GATHER_ROWS) */
@@ -3516,9 +3518,9 @@ extern "C" int mij_enc_reset(mij_encoder *e)
  * r = g = b = grey, an RGBA picture loses its alpha.  The device therefore only ever sees three channels, the same float expressions run on the
  * same values, and the strip kernels (k_encode420 / k_encode444: 16-byte or 8-byte row chunks, no column clamp) take every width and every
  * `comp`, not only RGB at multiples of 16 / 8 (the per-unit kernels remain as their test twins, mij_enc_force_generic). */
-static int enc_padded_width(int width, int subsample)
+static int enc_padded_width(int width, int lh)
 {
-	const int unit = subsample ? 16 : 8;
+	const int unit = 8 * lh; /* the MCU width of the slot's sampling */
 	return (width + unit - 1) / unit * unit;
 }
 static void enc_stage_rows(uint8_t *dst, const uint8_t *src, int width, int height, int comp, int pad_w)
@@ -3544,16 +3546,35 @@ static void enc_stage_rows(uint8_t *dst, const uint8_t *src, int width, int heig
 			memcpy(d + (size_t)x * 3, d + (size_t)(width - 1) * 3, 3);
 	}
 }
-extern "C" size_t mij_enc_pixel_bytes(int width, int height, int comp, int quality)
+/* the plan of a pixel slot under its options (NULL or all zero: as the writer itself chooses) */
+static int enc_opts_plan(mjw_tplan *t, int width, int height, int comp, int quality, const mij_enc_opts *o)
 {
-	mjw_plan plan;
-	if (!mjw_plan_init(&plan, width, height, comp, quality))
+	return mjw_splan_init(t, width, height, comp, quality, o ? o->ncomp : 0, o ? o->lh : 0, o ? o->lv : 0, o ? o->luma : nullptr, o ? o->chroma : nullptr);
+}
+static bool enc_opts_given(const mij_enc_opts *o) { return o && (o->ncomp || o->lh || o->lv || o->luma || o->chroma); }
+
+extern "C" size_t mij_enc_pixel_bytes_ex(int width, int height, int comp, int quality, const mij_enc_opts *opts)
+{
+	mjw_tplan t;
+	if (!enc_opts_plan(&t, width, height, comp, quality, opts))
 		return 0;
-	return align_up((size_t)enc_padded_width(width, plan.subsample) * height * 3, 256);
+	return align_up((size_t)enc_padded_width(width, t.lh) * height * 3, 256);
+}
+extern "C" size_t mij_enc_pixel_bytes(int width, int height, int comp, int quality) { return mij_enc_pixel_bytes_ex(width, height, comp, quality, nullptr); }
+
+/* the transcode-plan view of a writer's plan: 4:2:0 or 4:4:4 */
+static mjw_tplan enc_tplan_of(const mjw_plan &plan)
+{
+	mjw_tplan t;
+	t.plan = plan;
+	t.ncomp = 3;
+	t.lh = t.lv = plan.subsample ? 2 : 1;
+	return t;
 }
 
-static int enc_add_common(mij_encoder *e, const mjw_plan &plan, const void *pixels, int flip, int clone_of, int kind = ENC_HOST)
+static int enc_add_common(mij_encoder *e, const mjw_tplan &tplan, const void *pixels, int flip, int clone_of, int kind = ENC_HOST, bool sampled = false)
 {
+	const mjw_plan &plan = tplan.plan;
 	if ((int)e->slots.size() >= e->max_images)
 		return set_err(MIJ_E_NOMEM, "encoder batch is full (%d images)", e->max_images);
 	EncSlot s;
@@ -3567,10 +3588,13 @@ static int enc_add_common(mij_encoder *e, const mjw_plan &plan, const void *pixe
 	memset(&s.in, 0, sizeof(s.in));
 	memset(&s.cv, 0, sizeof(s.cv));
 	s.cv.dtype = MIJ_DT_U8;
-	s.pad_w = enc_padded_width(plan.width, plan.subsample);
+	s.pad_w = enc_padded_width(plan.width, tplan.ncomp == 1 ? 1 : tplan.lh);
 	s.src = nullptr;
 	s.coef_fmt = 0;
+	s.sampled = sampled;
 	memset(&s.tp, 0, sizeof(s.tp));
+	if (sampled)
+		s.tp = tplan;
 	memset(&s.coef, 0, sizeof(s.coef));
 	memset(s.rq_from, 0, sizeof(s.rq_from));
 	memset(s.rect, 0, sizeof(s.rect));
@@ -3613,24 +3637,33 @@ static int enc_add_common(mij_encoder *e, const mjw_plan &plan, const void *pixe
 	return (int)e->slots.size() - 1;
 }
 
-extern "C" int mij_enc_add(mij_encoder *e, const void *pixels, int width, int height, int comp, int quality, int flip_vertically)
+extern "C" int mij_enc_add_ex(mij_encoder *e, const void *pixels, int width, int height, int comp, int quality, int flip_vertically,
+                              const mij_enc_opts *opts)
 {
 	if (!e || !pixels)
 		return set_err(MIJ_E_ARG, "bad argument");
-	mjw_plan plan;
-	if (!mjw_plan_init(&plan, width, height, comp, quality))
-		return set_err(MIJ_E_ARG, "bad image arguments (%dx%dx%d)", width, height, comp);
-	return enc_add_common(e, plan, pixels, flip_vertically ? 1 : 0, -1);
+	mjw_tplan t;
+	if (!enc_opts_plan(&t, width, height, comp, quality, opts))
+		return set_err(MIJ_E_ARG, "bad image arguments (%dx%dx%d), sampling or tables", width, height, comp);
+	return enc_add_common(e, t, pixels, flip_vertically ? 1 : 0, -1, ENC_HOST, enc_opts_given(opts));
+}
+extern "C" int mij_enc_add(mij_encoder *e, const void *pixels, int width, int height, int comp, int quality, int flip_vertically)
+{
+	return mij_enc_add_ex(e, pixels, width, height, comp, quality, flip_vertically, nullptr);
 }
 
-extern "C" int mij_enc_add_uncopied(mij_encoder *e, int width, int height, int comp, int quality, int flip_vertically)
+extern "C" int mij_enc_add_uncopied_ex(mij_encoder *e, int width, int height, int comp, int quality, int flip_vertically, const mij_enc_opts *opts)
 {
 	if (!e)
 		return set_err(MIJ_E_ARG, "bad argument");
-	mjw_plan plan;
-	if (!mjw_plan_init(&plan, width, height, comp, quality))
-		return set_err(MIJ_E_ARG, "bad image arguments (%dx%dx%d)", width, height, comp);
-	return enc_add_common(e, plan, nullptr, flip_vertically ? 1 : 0, -1);
+	mjw_tplan t;
+	if (!enc_opts_plan(&t, width, height, comp, quality, opts))
+		return set_err(MIJ_E_ARG, "bad image arguments (%dx%dx%d), sampling or tables", width, height, comp);
+	return enc_add_common(e, t, nullptr, flip_vertically ? 1 : 0, -1, ENC_HOST, enc_opts_given(opts));
+}
+extern "C" int mij_enc_add_uncopied(mij_encoder *e, int width, int height, int comp, int quality, int flip_vertically)
+{
+	return mij_enc_add_uncopied_ex(e, width, height, comp, quality, flip_vertically, nullptr);
 }
 
 extern "C" int mij_enc_stage_pixels(mij_encoder *e, int slot, const void *pixels)
@@ -3694,8 +3727,9 @@ extern "C" int mij_enc_add_clone(mij_encoder *e, int src_slot)
 	const int root = e->slots[(size_t)src_slot].clone_of >= 0 ? e->slots[(size_t)src_slot].clone_of : src_slot;
 	if (!enc_has_pixels(e->slots[(size_t)root].kind))
 		return set_err(MIJ_E_ARG, "slot %d holds given data units or coefficient planes, which have no pixels to clone", src_slot);
-	const mjw_plan plan = e->slots[(size_t)root].plan;
-	const int slot = enc_add_common(e, plan, nullptr, e->slots[(size_t)root].flip, root);
+	const bool sampled = e->slots[(size_t)root].sampled;
+	const mjw_tplan plan = sampled ? e->slots[(size_t)root].tp : enc_tplan_of(e->slots[(size_t)root].plan);
+	const int slot = enc_add_common(e, plan, nullptr, e->slots[(size_t)root].flip, root, ENC_HOST, sampled);
 	if (slot >= 0) {
 		e->slots[(size_t)slot].optimize = e->slots[(size_t)src_slot].optimize;
 		e->slots[(size_t)slot].restart = e->slots[(size_t)src_slot].restart;
@@ -3902,13 +3936,9 @@ static bool enc_own_header(const mij_encoder *e, const EncSlot &s)
  * writer's 4:2:0 / 4:4:4 plan of any other */
 static mjw_tplan enc_prog_tplan(const EncSlot &s)
 {
-	if (s.kind == ENC_COEF)
+	if (s.kind == ENC_COEF || s.sampled)
 		return s.tp;
-	mjw_tplan t;
-	t.plan = s.plan;
-	t.ncomp = 3;
-	t.lh = t.lv = s.plan.subsample ? 2 : 1;
-	return t;
+	return enc_tplan_of(s.plan);
 }
 /* the units (a DC scan) or blocks (an AC scan: the component's own grid, without MCU padding) scan `sc` visits, and the grid's columns */
 static size_t enc_prog_scan_blocks(const mjw_tplan &t, const ProgScanDef &sc, uint32_t *bw)
@@ -4064,7 +4094,7 @@ static int enc_emit_lists(mij_encoder *e)
 			if (s.progressive) { /* SOI .. SOF2; k_prog_build appends the first scan's tables and SOS */
 				const mjw_tplan tp = enc_prog_tplan(s);
 				hlen_of[i] = (uint32_t)mjw_tframe_progressive(&tp, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
-			} else if (s.kind == ENC_COEF) /* shorter for a grey slot */
+			} else if (s.kind == ENC_COEF || s.sampled) /* shorter for a grey slot */
 				hlen_of[i] = (uint32_t)mjw_theader_restart(&s.tp, s.restart, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
 			else
 				hlen_of[i] = (uint32_t)mjw_header_restart(&s.plan, s.restart, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
@@ -4083,7 +4113,7 @@ static int enc_emit_lists(mij_encoder *e)
 		es.ri = (uint32_t)s.restart;
 		es.prog = 0;
 		es.tab = 0;
-		es.ny = s.kind == ENC_COEF ? (s.tp.ncomp == 1 ? 1u : (uint32_t)(s.tp.lh * s.tp.lv)) : (s.plan.subsample ? 4u : 1u);
+		es.ny = s.kind == ENC_COEF || s.sampled ? (s.tp.ncomp == 1 ? 1u : (uint32_t)(s.tp.lh * s.tp.lv)) : (s.plan.subsample ? 4u : 1u);
 		es.hlen = hlen_of[i];
 		if (s.progressive) { /* its tiles name (scan, first block, count); a scan is a segment as a restart interval is */
 			const mjw_tplan tp = enc_prog_tplan(s);
@@ -4280,16 +4310,16 @@ extern "C" const unsigned char *mij_enc_stream(const mij_encoder *e, int slot, s
 }
 
 /* mij_enc_add_device (cv NULL: uint8 elements) and mij_enc_add_device_float: the checks they share, extents in bytes of the element */
-static int enc_add_device(mij_encoder *e, const mij_in_tensor *t, const mij_in_convert *cv, int quality, int flip_vertically)
+static int enc_add_device(mij_encoder *e, const mij_in_tensor *t, const mij_in_convert *cv, int quality, int flip_vertically, const mij_enc_opts *opts)
 {
 	if (!e || !t)
 		return set_err(MIJ_E_ARG, "bad argument");
 	const uint64_t es = !cv ? 1u : cv->dtype == MIJ_DT_F32 ? 4u : 2u;
 	if (t->layout != MIJ_LAYOUT_HWC && t->layout != MIJ_LAYOUT_CHW)
 		return set_err(MIJ_E_ARG, "mij_enc_add_device: layout %d unknown", t->layout);
-	mjw_plan plan;
-	if (!mjw_plan_init(&plan, t->width, t->height, t->comp, quality))
-		return set_err(MIJ_E_ARG, "bad image arguments (%dx%dx%d)", t->width, t->height, t->comp);
+	mjw_tplan plan;
+	if (!enc_opts_plan(&plan, t->width, t->height, t->comp, quality, opts))
+		return set_err(MIJ_E_ARG, "bad image arguments (%dx%dx%d)%s", t->width, t->height, t->comp, enc_opts_given(opts) ? ", sampling or tables" : "");
 	const bool chw = t->layout == MIJ_LAYOUT_CHW;
 	const int64_t w = t->width, h = t->height, C = t->comp, rp = t->row_pitch, pp = chw ? t->plane_pitch : 0;
 	const int64_t lim = (int64_t)1 << 40;
@@ -4307,7 +4337,7 @@ static int enc_add_device(mij_encoder *e, const mij_in_tensor *t, const mij_in_c
 	const int rc = device_extent(e->ctx->device, t->src, (last + 1) * es, "src");
 	if (rc != MIJ_OK)
 		return rc;
-	const int slot = enc_add_common(e, plan, nullptr, flip_vertically ? 1 : 0, -1, ENC_DEVICE);
+	const int slot = enc_add_common(e, plan, nullptr, flip_vertically ? 1 : 0, -1, ENC_DEVICE, enc_opts_given(opts));
 	if (slot >= 0) {
 		e->slots[(size_t)slot].in = *t;
 		if (cv)
@@ -4316,12 +4346,21 @@ static int enc_add_device(mij_encoder *e, const mij_in_tensor *t, const mij_in_c
 	return slot;
 }
 
+extern "C" int mij_enc_add_device_ex(mij_encoder *e, const mij_in_tensor *t, int quality, int flip_vertically, const mij_enc_opts *opts)
+{
+	return enc_add_device(e, t, nullptr, quality, flip_vertically, opts);
+}
 extern "C" int mij_enc_add_device(mij_encoder *e, const mij_in_tensor *t, int quality, int flip_vertically)
 {
-	return enc_add_device(e, t, nullptr, quality, flip_vertically);
+	return enc_add_device(e, t, nullptr, quality, flip_vertically, nullptr);
 }
 
 extern "C" int mij_enc_add_device_float(mij_encoder *e, const mij_in_tensor *t, const mij_in_convert *cv, int quality, int flip_vertically)
+{
+	return mij_enc_add_device_float_ex(e, t, cv, quality, flip_vertically, nullptr);
+}
+extern "C" int mij_enc_add_device_float_ex(mij_encoder *e, const mij_in_tensor *t, const mij_in_convert *cv, int quality, int flip_vertically,
+                                           const mij_enc_opts *opts)
 {
 	if (!e || !t || !cv)
 		return set_err(MIJ_E_ARG, "bad argument");
@@ -4331,7 +4370,7 @@ extern "C" int mij_enc_add_device_float(mij_encoder *e, const mij_in_tensor *t, 
 	for (int c = 0; c < t->comp && c < 4; ++c)
 		if (!std::isfinite(cv->scale[c]) || !std::isfinite(cv->bias[c]))
 			return set_err(MIJ_E_ARG, "mij_enc_add_device_float: scale / bias of channel %d is not finite", c);
-	return enc_add_device(e, t, cv, quality, flip_vertically);
+	return enc_add_device(e, t, cv, quality, flip_vertically, opts);
 }
 
 extern "C" int mij_enc_add_units(mij_encoder *e, int width, int height, int comp, int quality, const int16_t *du)
@@ -4361,7 +4400,7 @@ extern "C" int mij_enc_add_units(mij_encoder *e, int width, int height, int comp
 	} catch (const std::bad_alloc &) {
 		return set_err(MIJ_E_NOMEM, "out of host memory");
 	}
-	const int slot = enc_add_common(e, plan, nullptr, 0, -1, ENC_UNITS);
+	const int slot = enc_add_common(e, enc_tplan_of(plan), nullptr, 0, -1, ENC_UNITS);
 	if (slot >= 0)
 		e->slots[(size_t)slot].units.swap(units);
 	return slot;
@@ -4408,7 +4447,7 @@ extern "C" int mij_enc_add_coef_window(mij_encoder *e, mij_batch *b, int slot, i
 	const size_t nu = mjw_tplan_du_count(&tp);
 	if (mjw_tplan_du_count(&sp) > UINT32_MAX / 64)
 		return set_err(MIJ_E_ARG, "not transcodable: too many data units");
-	const int es = enc_add_common(e, tp.plan, nullptr, 0, -1, ENC_COEF);
+	const int es = enc_add_common(e, tp, nullptr, 0, -1, ENC_COEF);
 	if (es < 0)
 		return es;
 	EncSlot &s = e->slots[(size_t)es];
@@ -4511,7 +4550,7 @@ extern "C" int mij_enc_add_coef(mij_encoder *e, mij_batch *b, int slot) { return
 
 extern "C" int mij_enc_tplan(const mij_encoder *e, int slot, mjw_tplan *out)
 {
-	if (!e || slot < 0 || slot >= (int)e->slots.size() || !out || e->slots[(size_t)slot].kind != ENC_COEF)
+	if (!e || slot < 0 || slot >= (int)e->slots.size() || !out || (e->slots[(size_t)slot].kind != ENC_COEF && !e->slots[(size_t)slot].sampled))
 		return set_err(MIJ_E_ARG, "bad slot, or not a coefficient slot");
 	*out = e->slots[(size_t)slot].tp;
 	return MIJ_OK;
@@ -4701,7 +4740,7 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 	const size_t n = e->slots.size();
 	if (!n)
 		return set_err(MIJ_E_STATE, "encoder batch is empty");
-	std::vector<WorkIdct> work[6];
+	std::vector<WorkIdct> work[9];
 	for (size_t i = 0; i < n; ++i) {
 		const EncSlot &s = e->slots[i];
 		const uint32_t nm = (uint32_t)(s.plan.mcu_x * s.plan.mcu_y);
@@ -4710,8 +4749,20 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 		e->h_imgs[i] = s.dev;
 		if (!enc_has_pixels(s.kind)) /* given units, or units made from coefficient planes: nothing to transform */
 			continue;
+		/* a sampling of its own: the strip kernel of its MCU shape, whatever force_generic says; 4:2:0 and 4:4:4 go on below, through the
+		 * kernel instances a default slot takes */
+		if (s.sampled && (s.tp.ncomp == 1 || s.tp.lh != s.tp.lv)) {
+			const int g = s.tp.ncomp == 1 ? 8 : s.tp.lh == 2 ? 6 : 7;
+			const uint32_t strip = g == 8 ? MIJ_ENCGREY_STRIP : g == 6 ? MIJ_ENC422_STRIP : MIJ_ENC440_STRIP;
+			for (uint32_t f = 0; f < nm; f += strip) {
+				WorkIdct w = {(uint32_t)i, 0u, f, 0u};
+				work[g].push_back(w);
+			}
+			continue;
+		}
+		const bool generic = e->force_generic && !s.sampled;
 		/* strips of 32 MCUs through the fused kernel: whole 16-pixel columns, packed RGB, 16-byte aligned rows (every width: enc_padded_width) */
-		if (sub && !e->force_generic) { /* every comp: the staging is packed RGB */
+		if (sub && !generic) { /* every comp: the staging is packed RGB */
 			for (uint32_t f = 0; f < nm; f += MIJ_ENC_STRIP) {
 				WorkIdct w = {(uint32_t)i, 0u, f, 0u};
 				work[4].push_back(w);
@@ -4719,7 +4770,7 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 			continue;
 		}
 		/* 4:4:4 (quality above 90): strips of 64 MCUs through k_encode444: whole 8-pixel columns, packed RGB, 8-byte aligned rows */
-		if (!sub && !e->force_generic) {
+		if (!sub && !generic) {
 			for (uint32_t f = 0; f < nm; f += MIJ_ENC444_STRIP) {
 				WorkIdct w = {(uint32_t)i, 0u, f, 0u};
 				work[5].push_back(w);
@@ -4735,14 +4786,16 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 			work[sub * 2 + 1].push_back(w);
 		}
 	}
-	const size_t total = work[0].size() + work[1].size() + work[2].size() + work[3].size() + work[4].size() + work[5].size();
+	size_t total = 0;
+	for (int g = 0; g < 9; ++g)
+		total += work[g].size();
 	if (total > e->work_cap)
 		HIP_TRY(hipStreamSynchronize(e->stream));
 	int rc = grow_pair(e->h_work, e->d_work, e->work_cap, total);
 	if (rc != MIJ_OK)
 		return rc;
 	size_t pos = 0;
-	for (int g = 0; g < 6; ++g) {
+	for (int g = 0; g < 9; ++g) {
 		e->first_work[g] = pos;
 		e->n_work[g] = work[g].size();
 		if (!work[g].empty())
@@ -4789,12 +4842,18 @@ extern "C" int mij_enc_launch(mij_encoder *e)
 	if (!e->uploaded)
 		return set_err(MIJ_E_STATE, "mij_enc_launch before mij_enc_upload");
 	HIP_TRY(hipSetDevice(e->ctx->device));
-	for (int g = 0; g < 6; ++g) {
+	for (int g = 0; g < 9; ++g) {
 		if (!e->n_work[g])
 			continue;
-		const dim3 grid((unsigned)e->n_work[g]), block(g >= 4 ? 192 : 256);
+		const dim3 grid((unsigned)e->n_work[g]), block(g == 6 ? 128 : g == 4 || g == 5 ? 192 : 256);
 		const WorkIdct *wk = e->d_work + e->first_work[g];
-		if (g == 4)
+		if (g == 6)
+			hipLaunchKernelGGL(k_encode422, grid, block, MIJ_ENC422_LDS, e->stream, e->d_imgs, wk, e->d_pix, e->d_du);
+		else if (g == 7)
+			hipLaunchKernelGGL(k_encode440, grid, block, MIJ_ENC440_LDS, e->stream, e->d_imgs, wk, e->d_pix, e->d_du);
+		else if (g == 8)
+			hipLaunchKernelGGL(k_encode_grey, grid, block, MIJ_ENCGREY_LDS, e->stream, e->d_imgs, wk, e->d_pix, e->d_du);
+		else if (g == 4)
 			hipLaunchKernelGGL(k_encode420, grid, block, MIJ_ENC_LDS, e->stream, e->d_imgs, wk, e->d_pix, e->d_du);
 		else if (g == 5)
 			hipLaunchKernelGGL(k_encode444, grid, block, MIJ_ENC444_LDS, e->stream, e->d_imgs, wk, e->d_pix, e->d_du);

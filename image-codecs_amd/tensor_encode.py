@@ -9,8 +9,8 @@ import math
 
 import torch
 
-from .binding import (Context, Encoder, InConvert, InTensor, WritePlan, emit_jpeg, lib, MIJ_LAYOUT_HWC, MIJ_LAYOUT_CHW, MIJ_DT_F16, MIJ_DT_BF16,
-                      MIJ_DT_F32)
+from .binding import (Context, Encoder, InConvert, InTensor, WritePlan, emit_jpeg, emit_transcoded, lib, sampled_plan, sampling_factors,
+                      sampling_name, _qtable_pair, MIJ_LAYOUT_HWC, MIJ_LAYOUT_CHW, MIJ_DT_F16, MIJ_DT_BF16, MIJ_DT_F32)
 from .tensor_out import _one_hip_runtime
 
 # one launch takes at most this many pictures / bytes of pixel arena; larger calls are cut into chunks
@@ -82,6 +82,24 @@ def _restart_values(v, n, name):
     return [0 if x is None else x for x in vals]
 
 
+def _sampling_values(v, n):
+    """subsampling= as one name or None per picture"""
+    if v is None or isinstance(v, str):
+        vals = [v] * n
+    else:
+        if isinstance(v, (bytes, torch.Tensor)):
+            raise ValueError("subsampling must be None, a sampling name or one of those per picture (got %r)" % (v,))
+        try:
+            vals = list(v)
+        except TypeError:
+            raise ValueError("subsampling must be None, a sampling name or one of those per picture (got %r)" % (v,)) from None
+        if len(vals) != n:
+            raise ValueError("subsampling has %d values for %d pictures" % (len(vals), n))
+    for x in vals:
+        sampling_factors(x)  # ValueError for an unknown name
+    return vals
+
+
 class TensorEncoder:
     """Encodes uint8 pictures that live on a GPU into JPEG byte streams, each exactly what stbi_write_jpg_to_func writes for that
     picture (encode), and float16 / bfloat16 / float32 pictures as the uint8 pictures they de-normalise to (encode_normalized).
@@ -101,6 +119,7 @@ class TensorEncoder:
         self._arena = 0
         self.last_host_emitted = 0
         self.last_restarts = []
+        self.last_subsampling = []
 
     @property
     def device(self):
@@ -203,7 +222,7 @@ class TensorEncoder:
         return self._enc
 
     def encode(self, images, *, quality=90, layout="CHW", flip_vertically=False, optimize=False, restart_rows=None, restart_mcus=None,
-               progressive=False):
+               progressive=False, subsampling=None, qtables=None):
         """quality: 1..100, or 0 for the default 90, as stbi_write_jpg takes it.  images: a 4-D uint8 tensor on the GPU ([N, C, H, W] for layout "CHW", [N, H, W, C] for "HWC") or a sequence of 3-D
         (2-D: grey) uint8 tensors, whose sizes may differ; C is 1..4 (stbi_write_jpg's comp).  Strided views are accepted (unit
         stride along W for CHW; strides C and 1 along W and C for HWC).  -> one bytes object per picture: what
@@ -216,11 +235,20 @@ class TensorEncoder:
         last_restarts[i] is the interval used, in MCUs.
         progressive (a bool): every stream is written as a progressive one -- what mjw_emit_progressive writes for the picture's data
         units (include/mij_host.h, PROGRESSIVE STREAMS), under per-scan optimal tables whatever optimize says.  ValueError together with
-        a restart interval."""
-        return self._encode(images, None, None, quality, layout, flip_vertically, optimize, False, restart_rows, restart_mcus, progressive)
+        a restart interval.
+        subsampling: None, "444", "422", "440", "420" or "grey", or one of those per picture: the chroma subsampling of the stream, or a
+        one-component grey stream (allowed for every C; it codes the luma of the picture) -- what mjh_write_jpg_sampled_to_memory writes
+        (include/mij_host.h, SAMPLED ENCODING).  None leaves the choice to the quality as stbi_write_jpg makes it ("420" up to 90, "444"
+        above), and naming that choice gives the same bytes.  The MCU, and with it a restart interval, is 8 * lh x 8 * lv pixels.
+        last_subsampling[i] is the name each stream used.
+        qtables: None or (luma, chroma), 64 ints 1..255 each in zigzag order (quality_tables' convention) in place of the tables of a
+        quality; the sampling is then "420" unless subsampling says otherwise.  ValueError for an unknown name, for qtables together
+        with a quality other than the default, and for tables that are not 64 values in 1..255."""
+        return self._encode(images, None, None, quality, layout, flip_vertically, optimize, False, restart_rows, restart_mcus, progressive,
+                            subsampling, qtables)
 
     def encode_normalized(self, images, *, mean=None, std=None, quality=90, layout="CHW", flip_vertically=False, optimize=False,
-                          restart_rows=None, restart_mcus=None, progressive=False):
+                          restart_rows=None, restart_mcus=None, progressive=False, subsampling=None, qtables=None):
         """encode() for the tensors a model works on: images as for encode() -- the same shapes, stride rules and layouts -- but float16,
         bfloat16 or float32, one dtype per call.  The pictures are de-normalised on the GPU, inside the kernel that gathers them
         (mij_enc_add_device_float), by the contract of include/mij.h: for element x of channel c
@@ -232,19 +260,26 @@ class TensorEncoder:
         Both None: the pictures hold v / 255, tensor_tables' convention; with the mean / std a TensorDecoder.decode was given, its
         tensors come back as the bytes they were made from, for all three dtypes.  A tensor holding 0..255 values is std=[1/255]*C.
         ValueError, before any device is touched, for uint8 or any other non-float dtype, mixed dtypes, a wrong number of mean / std
-        values, a std of 0, a value that is not finite, and everything encode() refuses.  restart_rows, restart_mcus, progressive: as for
-        encode()."""
-        return self._encode(images, mean, std, quality, layout, flip_vertically, optimize, True, restart_rows, restart_mcus, progressive)
+        values, a std of 0, a value that is not finite, and everything encode() refuses.  restart_rows, restart_mcus, progressive,
+        subsampling, qtables: as for encode()."""
+        return self._encode(images, mean, std, quality, layout, flip_vertically, optimize, True, restart_rows, restart_mcus, progressive,
+                            subsampling, qtables)
 
     def _encode(self, images, mean, std, quality, layout, flip_vertically, optimize, floats, restart_rows=None, restart_mcus=None,
-                progressive=False):
+                progressive=False, subsampling=None, qtables=None):
         if not isinstance(optimize, bool):
             raise ValueError("optimize must be a bool, got %r" % (optimize,))
         if not isinstance(progressive, bool):
             raise ValueError("progressive must be a bool, got %r" % (progressive,))
         if isinstance(quality, bool) or not isinstance(quality, int) or not 0 <= quality <= 100:
             raise ValueError("quality must be an int in 0..100 (0: stbi_write_jpg's default, 90), got %r" % (quality,))
+        if qtables is not None:
+            if quality not in (0, 90):
+                raise ValueError("qtables replace the tables of a quality: give one of the two (quality=%r)" % (quality,))
+            qtables = _qtable_pair(qtables)
+            qtables = (list(qtables[0]), list(qtables[1]))
         views = self._views(images, layout, floats)
+        samplings = _sampling_values(subsampling, len(views))
         convs = None
         if floats:  # one InConvert per channel count among the pictures; mean / std are checked even for an empty call
             mean, std = _numbers(mean, "mean"), _numbers(std, "std")
@@ -259,16 +294,26 @@ class TensorEncoder:
             raise ValueError("restart intervals are not combined with progressive output")
         self._placed(views)
         self.last_restarts = restarts = []
+        self.last_subsampling = used = []
         if not views:
             return []
         flip = bool(flip_vertically)
         lay = MIJ_LAYOUT_CHW if layout == "CHW" else MIJ_LAYOUT_HWC
         sizes = []
         for (_, w, h, c, _, _) in views:
-            p = _plan(w, h, c, quality)
-            pad_w = _align(w, 16 if p.subsample else 8)
-            sizes.append((_align(pad_w * h * 3, 256), _align(p.mcu_x * p.mcu_y * p.du_per_mcu * 128, 256), w * h))
             k = len(restarts)
+            if samplings[k] is None and qtables is None:
+                p = _plan(w, h, c, quality)
+                pad_w = _align(w, 16 if p.subsample else 8)
+                used.append("420" if p.subsample else "444")
+            else:  # the sizes of the slot's own sampling: rows of whole MCU columns, mjw_tplan_du_count units
+                t = sampled_plan(w, h, c, quality, samplings[k], qtables)
+                if t is None:
+                    raise ValueError("picture %dx%d with %d channels is refused by the writer" % (w, h, c))
+                p = t.plan
+                pad_w = _align(w, 8 * t.lh)
+                used.append(sampling_name(t))
+            sizes.append((_align(pad_w * h * 3, 256), _align(p.mcu_x * p.mcu_y * p.du_per_mcu * 128, 256), w * h))
             if rrows[k] and rmcus[k]:
                 raise ValueError("picture %d: restart_rows and restart_mcus are two ways to say the same thing: give one" % k)
             ri = rrows[k] * p.mcu_x if rrows[k] else rmcus[k]
@@ -284,20 +329,22 @@ class TensorEncoder:
                 pix += sizes[j][0]
                 j += 1
             streams, h = self._encode_chunk(views[i:j], sizes[i:j], quality, lay, flip, optimize, convs[i:j] if floats else None, restarts[i:j],
-                                            progressive)
+                                            progressive, samplings[i:j], qtables)
             out.extend(streams)
             host += h
             i = j
         self.last_host_emitted = host
         return out
 
-    def _encode_chunk(self, views, sizes, quality, lay, flip, optimize, convs=None, restarts=None, progressive=False):
+    def _encode_chunk(self, views, sizes, quality, lay, flip, optimize, convs=None, restarts=None, progressive=False, samplings=None, qtables=None):
         if not self._arena:  # a first guess, about 0.75 bytes per pixel; misses grow it
             self._arena = _align(sum(1024 + (px * 3) // 4 for (_, _, px) in sizes), 1 << 20)
         enc = self._encoder_for(len(views), sum(s[0] for s in sizes), sum(s[1] for s in sizes))
         for k, (t, w, h, c, rp, pp) in enumerate(views):
             it = InTensor(t.data_ptr(), lay, w, h, c, rp, pp)
-            slot = enc.add_device(it, quality, flip) if convs is None else enc.add_device_float(it, convs[k], quality, flip)
+            sm = samplings[k] if samplings else None
+            slot = (enc.add_device(it, quality, flip, sm, qtables) if convs is None else
+                    enc.add_device_float(it, convs[k], quality, flip, sm, qtables))
             if progressive:
                 enc.set_progressive(slot)
             elif optimize:
@@ -311,7 +358,10 @@ class TensorEncoder:
         for slot in range(len(views)):
             data, n = enc.stream(slot)
             if data is None:  # did not fit: its units are still on the device, the host Huffman stage finishes it
-                data = emit_jpeg(enc.plan(slot), enc.fetch(slot), optimize, restart_mcus=enc.slot_restart(slot), progressive=progressive)
+                if qtables is not None or (samplings and samplings[slot] is not None):  # a plan of its own (mij_enc_tplan)
+                    data = emit_transcoded(enc.tplan(slot), enc.fetch(slot), optimize, restart_mcus=enc.slot_restart(slot), progressive=progressive)
+                else:
+                    data = emit_jpeg(enc.plan(slot), enc.fetch(slot), optimize, restart_mcus=enc.slot_restart(slot), progressive=progressive)
                 host += 1
                 if enc.slot_status(slot) == "host flush":  # a progressive slot with a forced flush: the device reported no length
                     n = len(data)

@@ -568,7 +568,8 @@ const int16_t *mij_enc_units(const mij_encoder *e, int slot);
 int mij_enc_upload(mij_encoder *e);
 int mij_enc_launch(mij_encoder *e);
 int mij_enc_wait(mij_encoder *e);
-int mij_enc_force_generic(mij_encoder *e, int on); /* tests: per-unit kernels even where the fused 4:2:0 kernel applies; before upload */
+int mij_enc_force_generic(mij_encoder *e, int on); /* tests: per-unit kernels even where the fused 4:2:0 kernel applies; before upload.  Default
+                                                     * slots only: a slot made with mij_enc_opts stays on its strip kernel */
 /* D2H of a slot's data units (mcu_x*mcu_y*du_per_mcu*64 int16) */
 int mij_enc_fetch(mij_encoder *e, int slot, int16_t *dst, size_t dst_elems);
 int mij_enc_timer_begin(mij_encoder *e);
@@ -650,6 +651,31 @@ typedef struct {
 	float scale[4], bias[4];
 } mij_in_convert;
 int mij_enc_add_device_float(mij_encoder *e, const mij_in_tensor *t, const mij_in_convert *cv, int quality, int flip_vertically);
+
+/*
+ * Pixel slots with a chroma subsampling, grey output or quantisation tables of their own (mij_host.h, SAMPLED ENCODING, is the contract;
+ * the units equal mjw_stransform_host's bit for bit).  (ncomp, lh, lv) is one of (3,1,1) 4:4:4, (3,2,1) 4:2:2, (3,1,2) 4:4:0, (3,2,2)
+ * 4:2:0, (1,1,1) grey; ncomp 0 leaves the sampling to the quality as stbi_write_jpg does.  luma and chroma are 64 entries 1..255 each in
+ * zigzag order (read during the call only), both NULL for the tables of the quality.  opts NULL or all zero: the call without _ex,
+ * exactly.  MIJ_E_ARG for any other sampling, one table without the other and a zero entry.
+ * A slot made with options keeps its plan as an mjw_tplan: mij_enc_tplan (mij_host.h) answers for it, its header is mjw_theader's
+ * (one component and the luma tables only for grey), its rows are staged as whole MCU columns of ITS sampling (width rounded up to
+ * 8 * lh: mij_enc_pixel_bytes_ex), its data-unit share is mjw_tplan_du_count, and a restart interval counts MCUs of its own MCU size.
+ * mij_enc_set_optimize, mij_enc_set_restart, mij_enc_set_progressive, mij_enc_add_clone, emission and the fetches work on it unchanged.
+ * 4:2:2, 4:4:0 and grey slots run k_encode422, k_encode440 and k_encode_grey; a 4:2:0 or 4:4:4 slot runs the kernel instance a default
+ * slot of that shape runs, and with the writer's own sampling and no tables its stream is the default slot's byte for byte.
+ * mij_enc_force_generic keeps its meaning for default slots; slots made with options stay on their strip kernels.
+ */
+typedef struct {
+	int ncomp, lh, lv;                  /* 0, 0, 0: as the quality decides */
+	const unsigned char *luma, *chroma; /* NULL, NULL: as the quality decides */
+} mij_enc_opts;
+int mij_enc_add_ex(mij_encoder *e, const void *pixels, int width, int height, int comp, int quality, int flip_vertically, const mij_enc_opts *opts);
+int mij_enc_add_uncopied_ex(mij_encoder *e, int width, int height, int comp, int quality, int flip_vertically, const mij_enc_opts *opts);
+int mij_enc_add_device_ex(mij_encoder *e, const mij_in_tensor *t, int quality, int flip_vertically, const mij_enc_opts *opts);
+int mij_enc_add_device_float_ex(mij_encoder *e, const mij_in_tensor *t, const mij_in_convert *cv, int quality, int flip_vertically,
+                                const mij_enc_opts *opts);
+size_t mij_enc_pixel_bytes_ex(int width, int height, int comp, int quality, const mij_enc_opts *opts);
 
 /* A slot whose quantised data units are given: mjw_plan_du_count * 64 int16 in zigzag order, MCU after MCU (copied).  No transform
  * runs for it; its units are uploaded and emitted.  MIJ_E_ARG when a DC difference (per component, in MCU order, from 0) leaves

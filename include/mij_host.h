@@ -224,7 +224,8 @@ int mij_write_jpg_batch_ex(const void *const *pixels, const int *x, const int *y
  *   mjh_transcode_memory   the whole thing on the host: host walk, units, emit; flags MJW_OPTIMIZE_HUFFMAN and / or MJW_COPY_MARKERS.
  *                          *out is malloc'ed (the caller frees it); 0 with *reason for a picture that is undecodable, not transcodable
  *                          or not codable.
- *   mij_enc_tplan          the plan the GPU encoder holds for a slot made by mij_enc_add_coef (MIJ_E_ARG for any other slot)
+ *   mij_enc_tplan          the plan the GPU encoder holds for a slot made by mij_enc_add_coef, or for a pixel slot made with mij_enc_opts
+ *                          (SAMPLED ENCODING, below); MIJ_E_ARG for any other slot
  */
 typedef struct {
 	mjw_plan plan;
@@ -516,6 +517,46 @@ int mjw_transcode_memory_progressive_at(const uint8_t *src, int len, unsigned fl
 int mjh_transcode_memory_progressive(const uint8_t *src, int len, unsigned flags, int o, int trim, const int *crop, int grey, const unsigned char *luma,
                                      const unsigned char *chroma, int coarsen_only, int progressive, unsigned char **out, size_t *out_len,
                                      int *rect_out, const char **reason);
+
+/*
+ * SAMPLED ENCODING: the pixel encoder with a chosen chroma subsampling, grey output and given quantisation tables (Pillow's, torchvision's
+ * and nvJPEG's subsampling= / qtables=).  On the GPU: mij_enc_add_ex and its kin (mij.h); these calls are the written contract, and the GPU
+ * gives the same data units bit for bit.
+ *
+ * SAMPLING: (ncomp, lh, lv), one of "444" (3,1,1), "422" (3,2,1), "440" (3,1,2), "420" (3,2,2), "grey" (1,1,1).  Chroma is always 1x1, the
+ * MCU is 8*lh x 8*lv pixels, and the picture is extended to whole MCUs by repeating its last column and last row (the reference's edge rule,
+ * codec/jpeg_write.c:294-296).  Unit order is mjw_tplan's (LOSSLESS TRANSCODE, above): the luma blocks of an MCU in raster order, then Cb, then
+ * Cr -- 4:2:2 is Y0 Y1 Cb Cr, 4:4:0 is Ytop Ybottom Cb Cr, grey is one unit per MCU.
+ *
+ * ARITHMETIC: the channel rule (comp 1 and 2: r = g = b = grey; comp 4: alpha dropped), the colour expressions, the AAN fDCT and the quantiser
+ * are mjw_transform_host's, the same float expressions in the same order, no fused multiply-add.  The chroma sample of one subsampled
+ * position, from the converted floats of its pixels:
+ *   4:2:0  (a + b + c + e) * 0.25f   top-left, top-right, bottom-left, bottom-right (codec/jpeg_write.c:317-318)
+ *   4:2:2  (a + b) * 0.5f            left, right
+ *   4:4:0  (t + b) * 0.5f            top, bottom
+ * Grey computes Y only, from the staged r, g, b (equal for comp 1 and 2); it is allowed for every comp.
+ *
+ * TABLES: the pair `quality` gives (mjw_plan_init's), or a given (luma, chroma) pair of 64 entries 1..255 in zigzag order, mjw_quality_tables'
+ * convention; the reciprocal tables are derived from them by mjw_plan_init's expression.  A grey stream carries the luma table only.
+ *
+ * STREAMS: mjw_temit*, mjw_temit_restart* and mjw_temit_progressive* of the plan and its units.  With no sampling and no tables given the
+ * stream is stbi_write_jpg_to_func's byte for byte, and so is one whose sampling is the writer's own choice named explicitly ("420" up to
+ * quality 90, "444" above).
+ *
+ *   mjw_splan_init      the plan: quality as mjw_plan_init takes it (0: 90); ncomp 0: the writer's own sampling for that quality (lh, lv
+ *                       ignored); luma and chroma both NULL: the tables of the quality.  0 on bad arguments: mjw_plan_init's, a sampling
+ *                       that is none of the five, one table without the other, a zero entry.  plan.subsample is 1 for (3,2,2) only,
+ *                       plan.du_per_mcu 1, 3, 4 or 6, plan.comp the pixels' comp.
+ *   mjw_stransform_host the units of the pixels (comp = t->plan.comp bytes each), mjw_tplan_du_count(t) of them
+ *   mjh_write_jpg_sampled_to_memory   plan + transform + emit on the host: flags 0 or MJW_OPTIMIZE_HUFFMAN, restart_mcus 0 (none) .. 65535,
+ *                       progressive 0 or 1 (not with an interval).  *out is malloc'ed (the caller frees it).  0 on bad arguments.
+ */
+int mjw_splan_init(mjw_tplan *t, int width, int height, int comp, int quality, int ncomp, int lh, int lv, const unsigned char *luma,
+                   const unsigned char *chroma);
+void mjw_stransform_host(const mjw_tplan *t, const void *pixels, int flip_vertically, int16_t *du);
+int mjh_write_jpg_sampled_to_memory(const void *pixels, int width, int height, int comp, int quality, int ncomp, int lh, int lv,
+                                    const unsigned char *luma, const unsigned char *chroma, int flip_vertically, unsigned flags, int restart_mcus,
+                                    int progressive, unsigned char **out, size_t *out_len);
 
 /* The tables of stbi__ldr_to_hdr(common.c:391-424) for mij_batch_set_out_f32: lut[256*k + v] for channel k < n_out.  Colour
  * channels (all of them for odd n_out, all but the last for even n_out) get (float)(pow(v / 255.0f, gamma) * scale), the
