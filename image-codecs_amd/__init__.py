@@ -65,6 +65,12 @@ from .binding import (  # noqa: F401
     sampled_plan,
     host_transform_sampled,
     write_jpg_sampled_to_memory,
+    plane_shapes,
+    split_planes,
+    planes_plan,
+    video_range_convert,
+    host_transform_planes,
+    write_jpg_planes_to_memory,
     requant_magic,
     transcode_plan_requant,
     units_requant,

@@ -1542,6 +1542,167 @@ def write_jpg_sampled_to_memory(pixels, quality=90, sampling=None, qtables=None,
     return _take_malloced(out, n.value)
 
 
+class Plane(C.Structure):
+    """mij_plane (include/mij.h): sample (y, x) is the byte at src + y * row_pitch + x * x_pitch."""
+    _fields_ = [("src", C.c_void_p), ("row_pitch", C.c_int64), ("x_pitch", C.c_int64)]
+
+
+class InPlanes(C.Structure):
+    """mij_in_planes (include/mij.h)."""
+    _fields_ = [("planes", Plane * 3), ("width", C.c_int32), ("height", C.c_int32), ("opts", EncOpts), ("convert", C.c_void_p),
+                ("flip_vertically", C.c_int32)]
+
+
+def plane_shapes(width, height, sampling):
+    """the (rows, columns) of the Y, Cb and Cr planes of a width x height picture (include/mij_host.h, PLANE ENCODING); grey: Y only"""
+    ncomp, lh, lv = plane_sampling(sampling)
+    chroma = ((height + lv - 1) // lv, (width + lh - 1) // lh)
+    return [(height, width)] + [chroma] * (ncomp - 1)
+
+
+def plane_sampling(sampling):
+    """sampling_factors for plane encoding, where the sampling is required: ValueError for None too"""
+    if sampling is None:
+        raise ValueError("plane encoding needs its sampling: one of %s" % ", ".join(repr(k) for k in SAMPLINGS))
+    return sampling_factors(sampling)
+
+
+def video_range_convert():
+    """mjw_video_range: the InConvert that takes studio-range samples (Y 16..235, chroma 16..240) to JFIF's full range"""
+    L = lib()
+    L.mjw_video_range.argtypes = [C.POINTER(InConvert)]
+    L.mjw_video_range.restype = None
+    cv = InConvert(MIJ_DT_U8)
+    L.mjw_video_range(C.byref(cv))
+    return cv
+
+
+def _plane_convert(video_range, convert):
+    """-> an InConvert or None: video_range=True is mjw_video_range's, convert a ((scale_y, scale_cb, scale_cr), (bias ...)) pair or an
+    InConvert of the caller's.  ValueError for both given and for values that are not finite."""
+    if video_range and convert is not None:
+        raise ValueError("video_range and convert both say how samples are converted: give one")
+    if video_range:
+        return video_range_convert()
+    if convert is None:
+        return None
+    if not isinstance(convert, InConvert):
+        scale, bias = convert
+        convert = InConvert(MIJ_DT_U8, [float(v) for v in scale], [float(v) for v in bias])
+    if not all(np.isfinite(convert.scale[k]) and np.isfinite(convert.bias[k]) for k in range(3)):
+        raise ValueError("the conversion's scale and bias must be finite")
+    return convert
+
+
+def split_planes(picture, sampling):
+    """a picture of planes -- (Y, Cb, Cr), (Y, CbCr) with CbCr of shape [ch, cw, 2] (NV12), or Y alone for "grey" (bare, or in a sequence
+    of one) -- as the list of its 2-D planes, views of the caller's arrays; ValueError for anything else.  Works on numpy arrays and on
+    tensors alike (only .ndim / .shape and indexing are used)."""
+    ncomp, _, _ = plane_sampling(sampling)
+    parts = [picture] if hasattr(picture, "shape") else list(picture)
+    if len(parts) == 2 and ncomp == 3 and len(parts[1].shape) == 3 and parts[1].shape[2] == 2:
+        parts = [parts[0], parts[1][:, :, 0], parts[1][:, :, 1]]
+    if ncomp == 1 and len(parts) != 1:
+        raise ValueError("a grey picture is its Y plane alone: chroma planes were given")
+    if len(parts) != ncomp:
+        raise ValueError("sampling %r takes (Y, Cb, Cr) or (Y, CbCr[ch, cw, 2]); got %d planes" % (sampling, len(parts)))
+    for k, a in enumerate(parts):
+        if len(a.shape) != 2:
+            raise ValueError("plane %d is %d-D; planes are 2-D" % (k, len(a.shape)))
+    h, w = parts[0].shape
+    for k, (a, want) in enumerate(zip(parts, plane_shapes(w, h, sampling))):
+        if tuple(a.shape) != want:
+            raise ValueError("plane %d is %dx%d (rows x columns); a %dx%d picture at sampling %r needs %dx%d" %
+                             (k, a.shape[0], a.shape[1], h, w, sampling, want[0], want[1]))
+    return parts
+
+
+def _numpy_planes(picture, sampling, positive=False):
+    """-> ([(address, row_pitch, x_pitch)], width, height, keep): the planes of numpy arrays, arbitrary 2-D uint8 views, pitches from
+    their strides.  positive: views with a negative stride are copied first (the GPU encoder's slots take pitches > 0)."""
+    parts = split_planes(picture, sampling)
+    keep, out = [], []
+    for k, a in enumerate(parts):
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
+            raise ValueError("plane %d must be a uint8 numpy array" % k)
+        if 0 in a.shape:
+            raise ValueError("plane %d is empty" % k)
+        if positive and any(st < 0 for st in a.strides):
+            a = np.ascontiguousarray(a)
+        keep.append(a)
+        # a stride of an axis of one element addresses nothing: 0 rows down, 1 sample across
+        out.append((a.ctypes.data, a.strides[0] if a.shape[0] > 1 else 0, (a.strides[1] or 1) if a.shape[1] > 1 else 1))
+    return out, parts[0].shape[1], parts[0].shape[0], keep
+
+
+def in_planes(triples, width, height, sampling, qtables=None, convert=None, flip=False):
+    """-> (InPlanes, keep): the mij_in_planes of (address, row_pitch, x_pitch) triples; keep holds what the struct points into"""
+    ncomp, lh, lv = plane_sampling(sampling)
+    luma, chroma = (None, None) if qtables is None else _qtable_pair(qtables)
+    p = InPlanes()
+    for k, (addr, rp, xp) in enumerate(triples):
+        p.planes[k] = Plane(addr, rp, xp)
+    p.width, p.height = int(width), int(height)
+    p.opts = EncOpts(ncomp, lh, lv, luma, chroma)
+    p.convert = C.cast(C.pointer(convert), C.c_void_p) if convert is not None else None
+    p.flip_vertically = int(bool(flip))
+    return p, (luma, chroma, convert)
+
+
+def planes_plan(width, height, sampling, quality=90, qtables=None):
+    """mjw_pplan_init -> TranscodePlan; None where the writer refuses the size"""
+    ncomp, lh, lv = plane_sampling(sampling)
+    luma, chroma = (None, None) if qtables is None else _qtable_pair(qtables)
+    L = lib()
+    L.mjw_pplan_init.argtypes = [C.POINTER(TranscodePlan), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p]
+    t = TranscodePlan()
+    if not L.mjw_pplan_init(C.byref(t), int(width), int(height), int(quality), ncomp, lh, lv, luma, chroma):
+        return None
+    return t
+
+
+def host_transform_planes(picture, sampling, quality=90, qtables=None, video_range=False, flip=False, convert=None):
+    """mjw_pplan_init + mjw_ptransform_host: the units of a plane slot computed on the HOST -> (TranscodePlan, int16 [n_du, 64]); the CPU
+    twin of Encoder.add_planes.  picture: see split_planes; numpy arrays may be arbitrary 2-D views."""
+    triples, w, h, keep = _numpy_planes(picture, sampling)
+    cv = _plane_convert(video_range, convert)
+    t = planes_plan(w, h, sampling, quality, qtables)
+    if t is None:
+        return None, None
+    L = lib()
+    L.mjw_ptransform_host.argtypes = [C.POINTER(TranscodePlan), C.POINTER(Plane), C.c_void_p, C.c_int, C.c_void_p]
+    pl = (Plane * 3)(*[Plane(*tr) for tr in triples])
+    du = np.empty(t.du_elems(), dtype=np.int16)
+    if not L.mjw_ptransform_host(C.byref(t), pl, C.byref(cv) if cv is not None else None, int(bool(flip)), du.ctypes.data_as(C.c_void_p)):
+        return None, None
+    return t, du.reshape(-1, 64)
+
+
+def write_jpg_planes_to_memory(picture, sampling, quality=90, qtables=None, video_range=False, flip=False, optimize=False, restart_rows=None,
+                               restart_mcus=None, progressive=False, convert=None):
+    """mjh_write_jpg_planes_to_memory: the host writer fed with Y, Cb and Cr planes (include/mij_host.h, PLANE ENCODING) -> bytes, None
+    where it refuses.  restart_rows counts MCU rows of the sampling's own MCU size."""
+    triples, w, h, keep = _numpy_planes(picture, sampling)
+    cv = _plane_convert(video_range, convert)
+    ncomp, lh, lv = plane_sampling(sampling)
+    luma, chroma = (None, None) if qtables is None else _qtable_pair(qtables)
+    rows, mcus = _restart_mcus(restart_rows), _restart_mcus(restart_mcus)
+    if rows and mcus:
+        raise ValueError("restart_rows and restart_mcus are two ways to say the same thing: give one")
+    if rows:
+        mcus = rows * ((w + 8 * lh - 1) // (8 * lh))
+    prog = _progressive_flag(progressive, mcus)
+    L = lib()
+    L.mjh_write_jpg_planes_to_memory.argtypes = [C.POINTER(Plane), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
+                                                 C.c_void_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    pl = (Plane * 3)(*[Plane(*tr) for tr in triples])
+    out, n = C.c_void_p(), C.c_size_t()
+    if not L.mjh_write_jpg_planes_to_memory(pl, w, h, int(quality), ncomp, lh, lv, luma, chroma, C.byref(cv) if cv is not None else None,
+                                            int(bool(flip)), MJW_OPTIMIZE_HUFFMAN if optimize else 0, mcus, int(prog), C.byref(out), C.byref(n)):
+        return None
+    return _take_malloced(out, n.value)
+
+
 def requant_magic(b):
     """mjw_requant_magic -> (m, inc): n // b == ((n + inc) * m) >> 32 for every n < 2^24, the division of the conversion kernel"""
     L = lib()
@@ -1921,6 +2082,37 @@ class Encoder:
                           "mij_enc_add_device_float_ex")
         L.mij_enc_add_device_float.argtypes = [C.c_void_p, C.POINTER(InTensor), C.POINTER(InConvert), C.c_int, C.c_int]
         return _check(L.mij_enc_add_device_float(self._h, C.byref(t), C.byref(convert), int(quality), int(bool(flip))), "mij_enc_add_device_float")
+
+    def add_planes(self, picture, sampling, quality=90, qtables=None, video_range=False, flip=False, convert=None):
+        """mij_enc_add_planes: a slot fed with Y, Cb and Cr planes in host memory (include/mij_host.h, PLANE ENCODING).  picture: (Y, Cb,
+        Cr), (Y, CbCr[ch, cw, 2]) or Y alone for "grey"; numpy arrays may be arbitrary 2-D uint8 views, pitches come from their strides."""
+        triples, w, h, keep = _numpy_planes(picture, sampling, positive=True)
+        p, keep2 = in_planes(triples, w, h, sampling, qtables, _plane_convert(video_range, convert), flip)
+        L = lib()
+        L.mij_enc_add_planes.argtypes = [C.c_void_p, C.POINTER(InPlanes), C.c_int]
+        return _check(L.mij_enc_add_planes(self._h, C.byref(p), int(quality)), "mij_enc_add_planes")
+
+    def add_device_planes(self, triples, width, height, sampling, quality=90, qtables=None, video_range=False, flip=False, convert=None):
+        """mij_enc_add_device_planes: the same slot with its planes in caller-owned device memory; triples: one (device address, row_pitch,
+        x_pitch) in bytes per plane -- Y, Cb, Cr, or Y alone for "grey"."""
+        ncomp = plane_sampling(sampling)[0]
+        triples = list(triples)
+        if len(triples) != ncomp:
+            raise ValueError("sampling %r takes %d plane%s, got %d" % (sampling, ncomp, "" if ncomp == 1 else "s", len(triples)))
+        p, keep = in_planes(triples, width, height, sampling, qtables, _plane_convert(video_range, convert), flip)
+        L = lib()
+        L.mij_enc_add_device_planes.argtypes = [C.c_void_p, C.POINTER(InPlanes), C.c_int]
+        return _check(L.mij_enc_add_device_planes(self._h, C.byref(p), int(quality)), "mij_enc_add_device_planes")
+
+    @staticmethod
+    def plane_bytes(width, height, sampling):
+        """mij_enc_plane_bytes: what a plane slot takes in the pixel arenas"""
+        ncomp, lh, lv = plane_sampling(sampling)
+        L = lib()
+        L.mij_enc_plane_bytes.argtypes = [C.c_int, C.c_int, C.POINTER(EncOpts)]
+        L.mij_enc_plane_bytes.restype = C.c_size_t
+        o = EncOpts(ncomp, lh, lv, None, None)
+        return L.mij_enc_plane_bytes(int(width), int(height), C.byref(o))
 
     def add_units(self, width, height, comp, quality, du):
         """mij_enc_add_units: a slot whose quantised data units (int16 [n_du, 64], zigzag order) are given."""

@@ -18,6 +18,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <math.h>
 
 #include <stdint.h>
 #include <emmintrin.h>
@@ -1552,6 +1553,119 @@ int mjh_write_jpg_sampled_to_memory(const void *pixels, int width, int height, i
 		return 0;
 	}
 	mjw_stransform_host(&t, pixels, flip, du);
+	n = progressive ? mjw_temit_progressive_to_memory(&t, du, buf, cap) : mjw_temit_restart_to_memory(&t, du, flags, restart_mcus, buf, cap);
+	free(du);
+	if (!n) {
+		free(buf);
+		return 0;
+	}
+	*out = buf;
+	*out_len = n;
+	return 1;
+}
+
+/* ---- plane encoding (include/mij_host.h, PLANE ENCODING): the writer behind its colour stage, fed with Y, Cb and Cr samples as they lie */
+
+void mjw_video_range(mij_in_convert *cv)
+{
+	const double sy = 255.0 / 219.0, sc = 255.0 / 224.0;
+	memset(cv, 0, sizeof(*cv));
+	cv->dtype = MIJ_DT_U8;
+	cv->scale[0] = (float)sy;
+	cv->bias[0] = (float)(-16.0 * sy);
+	cv->scale[1] = cv->scale[2] = (float)sc;
+	cv->bias[1] = cv->bias[2] = (float)(128.0 - 128.0 * sc);
+}
+
+int mjw_pplan_init(mjw_tplan *t, int width, int height, int quality, int ncomp, int lh, int lv, const unsigned char *luma, const unsigned char *chroma)
+{
+	if (ncomp != 1 && ncomp != 3) /* the sampling is required: never the quality's choice */
+		return 0;
+	return mjw_splan_init(t, width, height, ncomp, quality, ncomp, lh, lv, luma, chroma);
+}
+
+/* what mjw_pplan_init made, and planes and a conversion that can be read */
+static int planes_ok(const mjw_tplan *t, const mij_plane *pl, const mij_in_convert *cv)
+{
+	int c;
+	if (!t || !pl || (t->ncomp != 1 && t->ncomp != 3) || t->plan.comp != t->ncomp)
+		return 0;
+	for (c = 0; c < 3; ++c) {
+		if (c < t->ncomp ? (!pl[c].src || !pl[c].x_pitch) : pl[c].src != NULL)
+			return 0;
+		if (cv && c < t->ncomp && !(isfinite(cv->scale[c]) && isfinite(cv->bias[c])))
+			return 0;
+	}
+	return !cv || cv->dtype == MIJ_DT_U8;
+}
+
+/* the contract's u for sample s of component c (mij.h, mij_in_convert): two roundings, no fused multiply-add (-ffp-contract=off) */
+static unsigned char plane_convert(unsigned char s, const mij_in_convert *cv, int c)
+{
+	float t = (float)s * cv->scale[c];
+	t = t + cv->bias[c];
+	t = t > 0.0f ? t : 0.0f; /* fmaxf, fminf and rintf spelled without libm: a NaN fails the comparison and becomes 0 */
+	t = t < 255.0f ? t : 255.0f;
+	return (unsigned char)_mm_cvtss_si32(_mm_set_ss(t)); /* round half to even */
+}
+
+int mjw_ptransform_host(const mjw_tplan *t, const mij_plane *pl, const mij_in_convert *cv, int flip, int16_t *du)
+{
+	const mjw_plan *p;
+	int c, mx, my, sx, sy, row, col, i;
+	float blk[64];
+	unsigned char lut[3][256];
+	if (!planes_ok(t, pl, cv) || !du)
+		return 0;
+	p = &t->plan;
+	for (c = 0; c < t->ncomp; ++c)
+		for (i = 0; i < 256; ++i)
+			lut[c][i] = cv ? plane_convert((unsigned char)i, cv, c) : (unsigned char)i;
+	for (my = 0; my < p->mcu_y; ++my)
+		for (mx = 0; mx < p->mcu_x; ++mx)
+			for (c = 0; c < t->ncomp; ++c) {
+				/* each plane on its own: its size, its blocks per MCU, its last column and row repeated */
+				const int h = c ? 1 : t->lh, v = c ? 1 : t->lv;
+				const int w = c ? (p->width + t->lh - 1) / t->lh : p->width, ht = c ? (p->height + t->lv - 1) / t->lv : p->height;
+				const unsigned char *base = (const unsigned char *)pl[c].src;
+				for (sy = 0; sy < v; ++sy)
+					for (sx = 0; sx < h; ++sx) {
+						for (row = 0; row < 8; ++row) {
+							const int y = (my * v + sy) * 8 + row, cy = y < ht ? y : ht - 1;
+							const unsigned char *line = base + (int64_t)(flip ? ht - 1 - cy : cy) * pl[c].row_pitch;
+							for (col = 0; col < 8; ++col) {
+								const int x = (mx * h + sx) * 8 + col;
+								blk[8 * row + col] = (float)lut[c][line[(int64_t)(x < w ? x : w - 1) * pl[c].x_pitch]] - 128.0f;
+							}
+						}
+						transform_du(blk, 8, c ? p->fdtbl_c : p->fdtbl_y, du);
+						du += 64;
+					}
+			}
+	return 1;
+}
+
+int mjh_write_jpg_planes_to_memory(const mij_plane *planes, int width, int height, int quality, int ncomp, int lh, int lv, const unsigned char *luma,
+                                   const unsigned char *chroma, const mij_in_convert *cv, int flip, unsigned flags, int restart_mcus, int progressive,
+                                   unsigned char **out, size_t *out_len)
+{
+	mjw_tplan t;
+	int16_t *du;
+	unsigned char *buf;
+	size_t nu, cap, n;
+	if (!planes || !out || !out_len || (flags & ~MJW_OPTIMIZE_HUFFMAN) || !ri_ok(restart_mcus) || (progressive && restart_mcus) ||
+		 !mjw_pplan_init(&t, width, height, quality, ncomp, lh, lv, luma, chroma) || !planes_ok(&t, planes, cv))
+		return 0;
+	nu = mjw_tplan_du_count(&t);
+	cap = progressive ? MJW_PROGRESSIVE_STREAM_CAP(nu) : MJW_STREAM_CAP(nu);
+	du = (int16_t *)malloc(nu * 64 * sizeof(int16_t));
+	buf = (unsigned char *)malloc(cap);
+	if (!du || !buf) {
+		free(du);
+		free(buf);
+		return 0;
+	}
+	mjw_ptransform_host(&t, planes, cv, flip, du);
 	n = progressive ? mjw_temit_progressive_to_memory(&t, du, buf, cap) : mjw_temit_restart_to_memory(&t, du, flags, restart_mcus, buf, cap);
 	free(du);
 	if (!n) {

@@ -1127,3 +1127,68 @@ __global__ __launch_bounds__(256) void k_enc_gather_float(const EncGatherF *__re
 		gather_float_rows<D, 4, 3>(G, y0, rows, pix);
 	}
 }
+
+/* ---- plane slots with device planes (mij_enc_add_device_planes; include/mij_host.h, PLANE ENCODING): each plane into the slot's share of
+ * the pixel arena as planar rows padded to whole MCUs of its component -- the edge rule (the plane's own last column and row repeated),
+ * the flip, the de-interleaving of NV12 / NV21 / packed layouts (x_pitch) and the range conversion all happen here, so the strip kernels
+ * meet aligned rows and need no edge code.  k_enc_gather's work list: one workgroup per MIJ_PGATHER_ROWS staged rows of one plane; a
+ * thread makes runs of 8 samples = one aligned 8-byte store.  Where x_pitch is 1 and the run lies inside the plane it is one 8-byte load
+ * when its address is so aligned, two 4-byte loads when it is 4-aligned, and element loads otherwise (the edge run, other pitches). */
+struct EncGatherP {
+	const uint8_t *src[3];
+	int64_t row_pitch[3], x_pitch[3];
+	int32_t w[3], h[3];         /* each plane's own size */
+	int32_t pad_w[3], pad_h[3]; /* its staged size: multiples of 8 */
+	uint64_t dst_off[3];        /* where its staged rows begin in the pixel arena */
+	int32_t flip, convert;
+	float scale[3], bias[3];
+};
+#define MIJ_PGATHER_ROWS 8
+
+__global__ __launch_bounds__(256) void k_enc_gather_planes(const EncGatherP *__restrict__ gs, const WorkIdct *__restrict__ work, uint8_t *__restrict__ pix)
+{
+	const WorkIdct wk = work[blockIdx.x];
+	const EncGatherP &g = gs[wk.img];
+	const int c = (int)wk.comp;
+	const uint8_t *src = g.src[c];
+	const int64_t rp = g.row_pitch[c], xp = g.x_pitch[c];
+	const int w = g.w[c], h = g.h[c];
+	const uint32_t y0 = wk.first, groups = (uint32_t)g.pad_w[c] / 8; /* pad_h is a multiple of MIJ_PGATHER_ROWS */
+	const bool cvt = g.convert != 0;
+	const float scale = g.scale[c], bias = g.bias[c];
+	for (uint32_t idx = threadIdx.x; idx < MIJ_PGATHER_ROWS * groups; idx += blockDim.x) {
+		const uint32_t y = y0 + idx / groups, x0 = (idx % groups) * 8;
+		const int cy = min((int)y, h - 1);
+		const uint8_t *row = src + (int64_t)(g.flip ? h - 1 - cy : cy) * rp;
+		uint32_t lo, hi;
+		const uint8_t *p = row + x0;
+		if (xp == 1 && x0 + 8 <= (uint32_t)w && ((uintptr_t)p & 3) == 0) {
+			if (((uintptr_t)p & 7) == 0) {
+				const gather_u32x2 v = *reinterpret_cast<const gather_u32x2 *>(p);
+				lo = v.x, hi = v.y;
+			} else {
+				lo = *reinterpret_cast<const uint32_t *>(p), hi = *reinterpret_cast<const uint32_t *>(p + 4);
+			}
+		} else {
+			lo = hi = 0;
+#pragma unroll
+			for (int k = 0; k < 8; ++k) {
+				const uint32_t v = row[(int64_t)min((int)x0 + k, w - 1) * xp];
+				if (k < 4)
+					lo |= v << (8 * k);
+				else
+					hi |= v << (8 * (k - 4));
+			}
+		}
+		if (cvt) {
+			uint32_t a = 0, b = 0;
+#pragma unroll
+			for (int k = 0; k < 4; ++k) {
+				a |= gather_denorm((float)((lo >> (8 * k)) & 255u), scale, bias) << (8 * k);
+				b |= gather_denorm((float)((hi >> (8 * k)) & 255u), scale, bias) << (8 * k);
+			}
+			lo = a, hi = b;
+		}
+		*reinterpret_cast<gather_u32x2 *>(pix + g.dst_off[c] + (size_t)y * (size_t)g.pad_w[c] + x0) = (gather_u32x2){lo, hi};
+	}
+}

@@ -3393,6 +3393,88 @@ __global__ __launch_bounds__(256) void k_encode_grey(const EncImage *__restrict_
 	enc_strip_store<1, 256>(im, m0, cnt, sdu, du, tid);
 }
 
+/* ------------------------------------------------------------------ plane encoders (include/mij_host.h, PLANE ENCODING)
+ *
+ * The strip design once more, for slots whose input is Y, Cb and Cr planes (mij_enc_add_planes, mij_enc_add_device_planes).  The gather
+ * (k_enc_gather_planes) or the host staging has laid each plane out as planar rows of whole MCUs of its component -- luma 8 * lh * mcu_x
+ * by 8 * lv * mcu_y, then Cb, then Cr at 8 * mcu_x by 8 * mcu_y each -- edge rule, flip and range conversion applied, so there is no
+ * clamp and no flip here.  One workgroup owns STRIP consecutive MCUs (MCU index order, so a strip may run over the end of an MCU row) and
+ * one lane owns one data unit: NT = STRIP * du_per_mcu threads.  Lanes are ordered so that a wavefront reads whole rows: for each luma
+ * block row sy of the MCU, STRIP * LH lanes in block-column order (64 lanes = 512 contiguous bytes of a staged row), then STRIP lanes of
+ * Cb and STRIP of Cr (256 contiguous bytes each) -- every load instruction of a wavefront fetches whole 128-byte lines, which is what
+ * staging the rows in LDS first would be for, so a lane takes its eight 8-byte rows straight from memory (eight loads in flight per
+ * lane, 4 KiB per wavefront) and LDS holds the finished units only.  A sample is converted by v_cvt_f32_ubyteN, level-shifted by a
+ * packed subtract of 128 -- exact -- and goes through the fDCT and quantiser every encoder kernel shares; the luma / chroma table sits
+ * behind one wave-uniform pointer (STRIP * LH * LV is a multiple of 64, so no wavefront mixes the two).  Units are staged in LDS in
+ * mjw_tplan order (enc_du_chunk's swizzle) and leave as the strip's contiguous cnt * du_per_mcu * 128 bytes with coalesced 16-byte
+ * stores.  Algorithmic bytes: 1 read + 2 written per sample.  LDS: NT * 128 bytes -- 24 KiB ("420": 32 MCUs, 192 threads; "444": 64,
+ * 192) or 32 KiB ("422", "440": 64 MCUs, 256 threads; grey: 256, 256).
+ */
+#define MIJ_ENCP_STRIP(LH, LV, NC) ((NC) == 1 ? 256 : (LH) * (LV) == 4 ? 32 : 64)
+#define MIJ_ENCP_DPM(LH, LV, NC) ((NC) == 1 ? 1 : (LH) * (LV) + 2)
+#define MIJ_ENCP_NT(LH, LV, NC) (MIJ_ENCP_STRIP(LH, LV, NC) * MIJ_ENCP_DPM(LH, LV, NC))
+#define MIJ_ENCP_LDS(LH, LV, NC) (MIJ_ENCP_NT(LH, LV, NC) * MIJ_ENC_DUPITCH)
+
+template <int LH, int LV, int NC>
+__global__ __launch_bounds__(MIJ_ENCP_NT(LH, LV, NC)) void k_encode_planes(const EncImage *__restrict__ imgs, const WorkIdct *__restrict__ work,
+                                                                          const uint8_t *__restrict__ pix, int16_t *__restrict__ du)
+{
+	constexpr int STRIP = MIJ_ENCP_STRIP(LH, LV, NC), DPM = MIJ_ENCP_DPM(LH, LV, NC), NT = MIJ_ENCP_NT(LH, LV, NC);
+	constexpr int NL = STRIP * LH * LV; /* luma lanes */
+	static_assert(NL % 64 == 0 && NT <= 256, "a wavefront is all luma or all chroma");
+	extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+	uint8_t *const sdu = lds; /* the staged data units */
+	const WorkIdct wk = work[blockIdx.x];
+	const EncImage &im = imgs[wk.img];
+	const int tid = threadIdx.x;
+	const uint32_t nmcu = (uint32_t)(im.mcu_x * im.mcu_y);
+	const uint32_t m0 = wk.first;
+	const uint32_t cnt = min((uint32_t)STRIP, nmcu - m0);
+	const bool chroma = NC == 3 && __builtin_amdgcn_readfirstlane(tid >> 6) >= NL / 64;
+
+	/* the lane's unit: MCU j of the strip, unit usub of the MCU; its block in the staged plane */
+	const size_t ybytes = (size_t)im.mcu_x * (8 * LH) * (size_t)im.mcu_y * (8 * LV), cbytes = (size_t)im.mcu_x * 8 * (size_t)im.mcu_y * 8;
+	uint32_t j, usub;
+	size_t off, pitch;
+	if (!chroma) {
+		const uint32_t sy = (uint32_t)tid / (uint32_t)(STRIP * LH), i = (uint32_t)tid % (uint32_t)(STRIP * LH), bx = i % (uint32_t)LH;
+		j = i / (uint32_t)LH;
+		usub = sy * LH + bx;
+		const uint32_t m = min(m0 + j, nmcu - 1u); /* MCUs past the last one read valid samples; their units are dropped */
+		const uint32_t my = m / (uint32_t)im.mcu_x, mx = m - my * (uint32_t)im.mcu_x;
+		pitch = (size_t)im.mcu_x * (8 * LH);
+		off = ((size_t)my * (8 * LV) + sy * 8u) * pitch + ((size_t)mx * LH + bx) * 8u;
+	} else {
+		const uint32_t c = (uint32_t)(tid - NL) / (uint32_t)STRIP;
+		j = (uint32_t)(tid - NL) % (uint32_t)STRIP;
+		usub = LH * LV + c;
+		const uint32_t m = min(m0 + j, nmcu - 1u);
+		const uint32_t my = m / (uint32_t)im.mcu_x, mx = m - my * (uint32_t)im.mcu_x;
+		pitch = (size_t)im.mcu_x * 8;
+		off = ybytes + c * cbytes + (size_t)my * 8u * pitch + (size_t)mx * 8u;
+	}
+	const uint8_t *src = pix + im.pix_off + off;
+	uint2 r[8];
+#pragma unroll
+	for (int y = 0; y < 8; ++y)
+		r[y] = *reinterpret_cast<const uint2 *>(src + (size_t)y * pitch);
+	f2 V[4][8];
+#pragma unroll
+	for (int k = 0; k < 4; ++k) {
+		const uint32_t t[2] = {r[2 * k].x, r[2 * k].y}, b[2] = {r[2 * k + 1].x, r[2 * k + 1].y};
+#define MIJ_ENC_PX(XI) V[k][XI] = enc_byte2<XI>(t, b) - (f2){128.0f, 128.0f};
+		MIJ_ENC_PX(0) MIJ_ENC_PX(1) MIJ_ENC_PX(2) MIJ_ENC_PX(3) MIJ_ENC_PX(4) MIJ_ENC_PX(5) MIJ_ENC_PX(6) MIJ_ENC_PX(7)
+#undef MIJ_ENC_PX
+	}
+	{
+		const float *fd = chroma ? im.fc : im.fy;
+		const int u = (int)(j * DPM + usub);
+		fdct_quant_store<0>(V, fd, reinterpret_cast<int16_t *>(sdu + u * MIJ_ENC_DUPITCH), u & 7);
+	}
+	__syncthreads();
+	enc_strip_store<DPM, NT>(im, m0, cnt, sdu, du, tid);
+}
+
 /* ------------------------------------------------------------------ float output (mij_batch_set_out_f32, stbi_loadf*)
  *
  * k_out_f32 turns a slot's decoded bytes into floats through one 256-entry table per channel: byte i of the slot uses the

@@ -3184,6 +3184,7 @@ static_assert(MIJ_EMIT_HDR == MJW_HEADER_RESTART_BYTES, "header size");
 enum { ENC_HOST = 0, ENC_DEVICE = 1, ENC_UNITS = 2, ENC_COEF = 3 };
 static inline bool enc_has_pixels(int kind) { return kind == ENC_HOST || kind == ENC_DEVICE; }
 
+#define MIJ_ENC_GROUPS 14
 struct EncSlot {
 	mjw_plan plan;
 	EncImage dev;
@@ -3205,6 +3206,9 @@ struct EncSlot {
 	int rect[4];                  /* the kept rectangle in the displayed frame (mij_enc_slot_rect) */
 	bool greyed;                  /* Cb and Cr of a colour source were dropped */
 	bool sampled;                 /* a pixel slot made with a sampling or tables of its own (mij_enc_add_ex and its kin): tp is its plan */
+	bool planes;                  /* a plane slot (mij_enc_add_planes, mij_enc_add_device_planes): sampled too, tp its plan; the staging is planar */
+	mij_plane pl[3];              /* its planes, ENC_DEVICE only */
+	bool pl_convert;              /* cv holds its range conversion (dtype MIJ_DT_U8; entries 0..2: Y, Cb, Cr) */
 	unsigned char rq_from[2][64]; /* a requantising slot (coef.rq != 0): the tables tp's replaced, luma and chroma, zigzag order */
 };
 
@@ -3223,8 +3227,9 @@ struct mij_encoder {
 	EncImage *h_imgs, *d_imgs;
 	WorkIdct *h_work, *d_work;
 	size_t work_cap;
-	size_t n_work[9], first_work[9]; /* [sub*2 + kind]: kind 0 luma units, 1 chroma units; [4]: fused 4:2:0 strips; [5]: fused 4:4:4 strips;
-	                                    [6], [7], [8]: 4:2:2, 4:4:0 and grey strips (sampled slots) */
+	size_t n_work[MIJ_ENC_GROUPS], first_work[MIJ_ENC_GROUPS]; /* [sub*2 + kind]: kind 0 luma units, 1 chroma units; [4]: fused 4:2:0 strips;
+	                                    [5]: fused 4:4:4 strips; [6], [7], [8]: 4:2:2, 4:4:0 and grey strips (sampled slots); [9] .. [13]: the
+	                                    strips of plane slots: 4:4:4, 4:2:2, 4:4:0, 4:2:0, grey */
 	std::vector<EncSlot> slots;
 	bool uploaded, launched, force_generic;
 	/* device-pixel slots: the gather kernel's slots and work (rows of MIJ_GATHER_ROWS) */
@@ -3232,6 +3237,11 @@ struct mij_encoder {
 	size_t gath_cap;
 	WorkIdct *h_gwork, *d_gwork;
 	size_t gwork_cap, n_gwork;
+	/* the same for the device plane slots (k_enc_gather_planes) */
+	EncGatherP *h_pgath, *d_pgath;
+	size_t pgath_cap;
+	WorkIdct *h_pgwork, *d_pgwork;
+	size_t pgwork_cap;
 	/* the same for the float device-pixel slots, grouped by dtype: one launch of k_enc_gather_float each */
 	EncGatherF *h_fgath, *d_fgath;
 	size_t fgath_cap;
@@ -3396,6 +3406,9 @@ extern "C" int mij_enc_create_ex(mij_ctx *ctx, int max_images, size_t stage_byte
 	e->h_fgath = e->d_fgath = nullptr;
 	e->h_fgwork = e->d_fgwork = nullptr;
 	e->fgath_cap = e->fgwork_cap = 0;
+	e->h_pgath = e->d_pgath = nullptr;
+	e->h_pgwork = e->d_pgwork = nullptr;
+	e->pgath_cap = e->pgwork_cap = 0;
 	e->d_arena = e->h_arena = nullptr;
 	e->d_tabs = nullptr;
 	e->h_eslot = e->d_eslot = nullptr;
@@ -3476,6 +3489,10 @@ extern "C" void mij_enc_destroy(mij_encoder *e)
 	free_dev(e->d_fgath);
 	free_host(e->h_fgwork);
 	free_dev(e->d_fgwork);
+	free_host(e->h_pgath);
+	free_dev(e->d_pgath);
+	free_host(e->h_pgwork);
+	free_dev(e->d_pgwork);
 	free_host(e->h_cslot);
 	free_dev(e->d_cslot);
 	free_host(e->h_cwork);
@@ -3562,6 +3579,19 @@ extern "C" size_t mij_enc_pixel_bytes_ex(int width, int height, int comp, int qu
 }
 extern "C" size_t mij_enc_pixel_bytes(int width, int height, int comp, int quality) { return mij_enc_pixel_bytes_ex(width, height, comp, quality, nullptr); }
 
+/* a plane slot's share of the pixel arenas: luma blocks plus two chroma blocks per MCU, 64 samples each */
+static size_t enc_plane_bytes(const mjw_tplan &t)
+{
+	return align_up((size_t)t.plan.mcu_x * (size_t)t.plan.mcu_y * (size_t)t.plan.du_per_mcu * 64, 256);
+}
+extern "C" size_t mij_enc_plane_bytes(int width, int height, const mij_enc_opts *opts)
+{
+	mjw_tplan t;
+	if (!opts || !mjw_pplan_init(&t, width, height, 0, opts->ncomp, opts->lh, opts->lv, nullptr, nullptr))
+		return 0;
+	return enc_plane_bytes(t);
+}
+
 /* the transcode-plan view of a writer's plan: 4:2:0 or 4:4:4 */
 static mjw_tplan enc_tplan_of(const mjw_plan &plan)
 {
@@ -3572,7 +3602,8 @@ static mjw_tplan enc_tplan_of(const mjw_plan &plan)
 	return t;
 }
 
-static int enc_add_common(mij_encoder *e, const mjw_tplan &tplan, const void *pixels, int flip, int clone_of, int kind = ENC_HOST, bool sampled = false)
+static int enc_add_common(mij_encoder *e, const mjw_tplan &tplan, const void *pixels, int flip, int clone_of, int kind = ENC_HOST, bool sampled = false,
+                          bool planes = false)
 {
 	const mjw_plan &plan = tplan.plan;
 	if ((int)e->slots.size() >= e->max_images)
@@ -3592,6 +3623,9 @@ static int enc_add_common(mij_encoder *e, const mjw_tplan &tplan, const void *pi
 	s.src = nullptr;
 	s.coef_fmt = 0;
 	s.sampled = sampled;
+	s.planes = planes;
+	memset(s.pl, 0, sizeof(s.pl));
+	s.pl_convert = false;
 	memset(&s.tp, 0, sizeof(s.tp));
 	if (sampled)
 		s.tp = tplan;
@@ -3600,6 +3634,8 @@ static int enc_add_common(mij_encoder *e, const mjw_tplan &tplan, const void *pi
 	memset(s.rect, 0, sizeof(s.rect));
 	s.greyed = false;
 	s.pix_bytes = !enc_has_pixels(kind) ? 0 : align_up((size_t)s.pad_w * plan.height * 3, 256); /* staged as packed RGB whatever plan.comp is (enc_stage_rows) */
+	if (planes) /* planar, every plane padded to whole MCUs of its component both ways */
+		s.pix_bytes = enc_plane_bytes(tplan);
 	s.du_bytes = align_up(mjw_plan_du_count(&plan) * 128, 256);
 	if (e->pix_used + s.pix_bytes > e->pix_cap)
 		return set_err(MIJ_E_NOMEM, "pixel arena exhausted");
@@ -3625,6 +3661,11 @@ static int enc_add_common(mij_encoder *e, const mjw_tplan &tplan, const void *pi
 	s.dev.mcu_x = plan.mcu_x;
 	s.dev.mcu_y = plan.mcu_y;
 	s.dev.flip = flip;
+	if (planes) { /* k_encode_planes derives the staged geometry from mcu_x and mcu_y */
+		s.dev.height = plan.mcu_y * 8 * tplan.lv;
+		s.dev.comp = 1;
+		s.dev.flip = 0; /* applied on the way into the staging */
+	}
 	s.dev.pix_off = e->pix_used;
 	s.dev.du_off = e->du_used;
 	memcpy(s.dev.fy, plan.fdtbl_y, sizeof(s.dev.fy));
@@ -3668,7 +3709,8 @@ extern "C" int mij_enc_add_uncopied(mij_encoder *e, int width, int height, int c
 
 extern "C" int mij_enc_stage_pixels(mij_encoder *e, int slot, const void *pixels)
 {
-	if (!e || !pixels || slot < 0 || slot >= (int)e->slots.size() || e->slots[(size_t)slot].clone_of >= 0 || e->slots[(size_t)slot].kind != ENC_HOST)
+	if (!e || !pixels || slot < 0 || slot >= (int)e->slots.size() || e->slots[(size_t)slot].clone_of >= 0 || e->slots[(size_t)slot].kind != ENC_HOST ||
+		 e->slots[(size_t)slot].planes)
 		return set_err(MIJ_E_ARG, "bad slot or pixels");
 	const EncSlot &s = e->slots[(size_t)slot];
 	enc_stage_rows(e->stage + s.stage_off, static_cast<const uint8_t *>(pixels), s.plan.width, s.plan.height, s.plan.comp, s.pad_w);
@@ -3729,7 +3771,7 @@ extern "C" int mij_enc_add_clone(mij_encoder *e, int src_slot)
 		return set_err(MIJ_E_ARG, "slot %d holds given data units or coefficient planes, which have no pixels to clone", src_slot);
 	const bool sampled = e->slots[(size_t)root].sampled;
 	const mjw_tplan plan = sampled ? e->slots[(size_t)root].tp : enc_tplan_of(e->slots[(size_t)root].plan);
-	const int slot = enc_add_common(e, plan, nullptr, e->slots[(size_t)root].flip, root, ENC_HOST, sampled);
+	const int slot = enc_add_common(e, plan, nullptr, e->slots[(size_t)root].flip, root, ENC_HOST, sampled, e->slots[(size_t)root].planes);
 	if (slot >= 0) {
 		e->slots[(size_t)slot].optimize = e->slots[(size_t)src_slot].optimize;
 		e->slots[(size_t)slot].restart = e->slots[(size_t)src_slot].restart;
@@ -3814,7 +3856,7 @@ static int enc_gather(mij_encoder *e)
 {
 	size_t ng = 0, nw = 0;
 	for (const EncSlot &s : e->slots)
-		if (s.clone_of < 0 && s.kind == ENC_DEVICE && s.cv.dtype == MIJ_DT_U8) {
+		if (s.clone_of < 0 && s.kind == ENC_DEVICE && s.cv.dtype == MIJ_DT_U8 && !s.planes) {
 			++ng;
 			nw += ((size_t)s.plan.height + MIJ_GATHER_ROWS - 1) / MIJ_GATHER_ROWS;
 		}
@@ -3831,7 +3873,7 @@ static int enc_gather(mij_encoder *e)
 	uint32_t g = 0;
 	size_t w = 0;
 	for (const EncSlot &s : e->slots) {
-		if (s.clone_of >= 0 || s.kind != ENC_DEVICE || s.cv.dtype != MIJ_DT_U8)
+		if (s.clone_of >= 0 || s.kind != ENC_DEVICE || s.cv.dtype != MIJ_DT_U8 || s.planes)
 			continue;
 		EncGather &G = e->h_gath[g];
 		G.src = static_cast<const uint8_t *>(s.in.src);
@@ -3863,7 +3905,7 @@ static int enc_gather_float(mij_encoder *e)
 {
 	size_t ng = 0, nw = 0;
 	for (const EncSlot &s : e->slots)
-		if (s.clone_of < 0 && s.kind == ENC_DEVICE && s.cv.dtype != MIJ_DT_U8) {
+		if (s.clone_of < 0 && s.kind == ENC_DEVICE && s.cv.dtype != MIJ_DT_U8 && !s.planes) {
 			++ng;
 			nw += ((size_t)s.plan.height + MIJ_GATHER_ROWS - 1) / MIJ_GATHER_ROWS;
 		}
@@ -3882,7 +3924,7 @@ static int enc_gather_float(mij_encoder *e)
 	size_t w = 0;
 	for (int k = 0; k < 3; ++k) {
 		for (const EncSlot &s : e->slots) {
-			if (s.clone_of >= 0 || s.kind != ENC_DEVICE || s.cv.dtype != dts[k])
+			if (s.clone_of >= 0 || s.kind != ENC_DEVICE || s.cv.dtype != dts[k] || s.planes)
 				continue;
 			EncGatherF &G = e->h_fgath[g];
 			G.g.src = static_cast<const uint8_t *>(s.in.src);
@@ -3923,6 +3965,153 @@ static int enc_gather_float(mij_encoder *e)
 	}
 	return MIJ_OK;
 }
+
+/* The device plane slots (mij_enc_add_device_planes): their gather list and one launch of k_enc_gather_planes.  Nothing is queued when
+ * there are none. */
+static void enc_plane_geometry(const mjw_tplan &t, int c, int32_t *w, int32_t *h, int32_t *pad_w, int32_t *pad_h)
+{
+	const int lh = c ? 1 : t.lh, lv = c ? 1 : t.lv;
+	*w = c ? (t.plan.width + t.lh - 1) / t.lh : t.plan.width;
+	*h = c ? (t.plan.height + t.lv - 1) / t.lv : t.plan.height;
+	*pad_w = t.plan.mcu_x * 8 * lh;
+	*pad_h = t.plan.mcu_y * 8 * lv;
+}
+
+static int enc_gather_planes(mij_encoder *e)
+{
+	size_t ng = 0, nw = 0;
+	for (const EncSlot &s : e->slots)
+		if (s.clone_of < 0 && s.kind == ENC_DEVICE && s.planes) {
+			++ng;
+			nw += (size_t)s.plan.mcu_y * (size_t)(s.tp.ncomp == 1 ? 1 : s.tp.lv + 2) * (8 / MIJ_PGATHER_ROWS);
+		}
+	if (!ng)
+		return MIJ_OK;
+	if (ng > e->pgath_cap || nw > e->pgwork_cap)
+		HIP_TRY(hipStreamSynchronize(e->stream)); /* an earlier upload's copies may still read the pinned lists */
+	int rc = grow_pair(e->h_pgath, e->d_pgath, e->pgath_cap, ng);
+	if (rc == MIJ_OK)
+		rc = grow_pair(e->h_pgwork, e->d_pgwork, e->pgwork_cap, nw);
+	if (rc != MIJ_OK)
+		return rc;
+	uint32_t g = 0;
+	size_t w = 0;
+	for (const EncSlot &s : e->slots) {
+		if (s.clone_of >= 0 || s.kind != ENC_DEVICE || !s.planes)
+			continue;
+		EncGatherP &G = e->h_pgath[g];
+		memset(&G, 0, sizeof(G));
+		uint64_t off = s.dev.pix_off;
+		for (int c = 0; c < s.tp.ncomp; ++c) {
+			G.src[c] = static_cast<const uint8_t *>(s.pl[c].src);
+			G.row_pitch[c] = s.pl[c].row_pitch;
+			G.x_pitch[c] = s.pl[c].x_pitch;
+			enc_plane_geometry(s.tp, c, &G.w[c], &G.h[c], &G.pad_w[c], &G.pad_h[c]);
+			G.dst_off[c] = off;
+			off += (uint64_t)G.pad_w[c] * (uint64_t)G.pad_h[c];
+			G.scale[c] = s.cv.scale[c];
+			G.bias[c] = s.cv.bias[c];
+			for (uint32_t y = 0; y < (uint32_t)G.pad_h[c]; y += MIJ_PGATHER_ROWS) {
+				const WorkIdct wk = {g, (uint32_t)c, y, 0u};
+				e->h_pgwork[w++] = wk;
+			}
+		}
+		G.flip = s.flip;
+		G.convert = s.pl_convert ? 1 : 0;
+		++g;
+	}
+	HIP_TRY(hipMemcpyAsync(e->d_pgath, e->h_pgath, sizeof(EncGatherP) * ng, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->d_pgwork, e->h_pgwork, sizeof(WorkIdct) * w, hipMemcpyHostToDevice, e->stream));
+	hipLaunchKernelGGL(k_enc_gather_planes, dim3((unsigned)w), dim3(256), 0, e->stream, e->d_pgath, e->d_pgwork, e->d_pix);
+	HIP_TRY(hipGetLastError());
+	return MIJ_OK;
+}
+
+/* a host plane slot's staging: the layout k_enc_gather_planes makes, by the same rules */
+static void enc_stage_planes(uint8_t *dst, const mjw_tplan &t, const mij_plane *pl, const mij_in_convert *cv, int flip)
+{
+	for (int c = 0; c < t.ncomp; ++c) {
+		int32_t w, h, pad_w, pad_h;
+		enc_plane_geometry(t, c, &w, &h, &pad_w, &pad_h);
+		uint8_t lut[256];
+		for (int i = 0; i < 256; ++i) {
+			float v = (float)i;
+			if (cv) {
+				v = v * cv->scale[c];
+				v = v + cv->bias[c];
+				v = rintf(fminf(fmaxf(v, 0.0f), 255.0f));
+			}
+			lut[i] = (uint8_t)v;
+		}
+		const uint8_t *src = static_cast<const uint8_t *>(pl[c].src);
+		for (int y = 0; y < pad_h; ++y) {
+			const int cy = y < h ? y : h - 1;
+			const uint8_t *row = src + (int64_t)(flip ? h - 1 - cy : cy) * pl[c].row_pitch;
+			uint8_t *d = dst + (size_t)y * (size_t)pad_w;
+			for (int x = 0; x < w; ++x)
+				d[x] = lut[row[(int64_t)x * pl[c].x_pitch]];
+			memset(d + w, d[w - 1], (size_t)(pad_w - w));
+		}
+		dst += (size_t)pad_w * (size_t)pad_h;
+	}
+}
+
+static int enc_add_planes(mij_encoder *e, const mij_in_planes *p, int quality, bool device)
+{
+	if (!e || !p)
+		return set_err(MIJ_E_ARG, "bad argument");
+	mjw_tplan t;
+	if (!mjw_pplan_init(&t, p->width, p->height, quality, p->opts.ncomp, p->opts.lh, p->opts.lv, p->opts.luma, p->opts.chroma))
+		return set_err(MIJ_E_ARG, "bad plane arguments (%dx%d): the sampling (%d, %d, %d) is required and one of the five, tables come in pairs of entries 1..255",
+							p->width, p->height, p->opts.ncomp, p->opts.lh, p->opts.lv);
+	const mij_in_convert *cv = p->convert;
+	if (cv && cv->dtype != MIJ_DT_U8)
+		return set_err(MIJ_E_ARG, "planes hold uint8 samples: convert->dtype must be MIJ_DT_U8");
+	const int64_t lim = (int64_t)1 << 40;
+	for (int c = 0; c < 3; ++c) {
+		const mij_plane &q = p->planes[c];
+		if (c >= t.ncomp) {
+			if (q.src)
+				return set_err(MIJ_E_ARG, "a grey slot takes no chroma plane (planes[%d].src is not NULL)", c);
+			continue;
+		}
+		int32_t w, h, pad_w, pad_h;
+		enc_plane_geometry(t, c, &w, &h, &pad_w, &pad_h);
+		if (!q.src)
+			return set_err(MIJ_E_ARG, "planes[%d].src is NULL", c);
+		if (q.x_pitch <= 0 || q.x_pitch > lim || q.row_pitch < 0 || q.row_pitch > lim)
+			return set_err(MIJ_E_ARG, "planes[%d]: pitch out of range (row %lld, x %lld)", c, (long long)q.row_pitch, (long long)q.x_pitch);
+		if (cv && (!std::isfinite(cv->scale[c]) || !std::isfinite(cv->bias[c])))
+			return set_err(MIJ_E_ARG, "scale / bias of component %d is not finite", c);
+		if (!device)
+			continue;
+		const int64_t line = (int64_t)(w - 1) * q.x_pitch + 1;
+		if (h > 1 && q.row_pitch < line)
+			return set_err(MIJ_E_ARG, "planes[%d]: a row pitch of %lld lets its %lld-byte rows overlap", c, (long long)q.row_pitch, (long long)line);
+		char what[16];
+		snprintf(what, sizeof(what), "planes[%d]", c);
+		const int rc = device_extent(e->ctx->device, q.src, (uint64_t)((int64_t)(h - 1) * q.row_pitch + line), what);
+		if (rc != MIJ_OK)
+			return rc;
+	}
+	const int flip = p->flip_vertically ? 1 : 0;
+	const int slot = enc_add_common(e, t, nullptr, flip, -1, device ? ENC_DEVICE : ENC_HOST, true, true);
+	if (slot < 0)
+		return slot;
+	EncSlot &s = e->slots[(size_t)slot];
+	if (device) {
+		memcpy(s.pl, p->planes, sizeof(s.pl));
+		if (cv) {
+			s.cv = *cv;
+			s.pl_convert = true;
+		}
+	} else {
+		enc_stage_planes(e->stage + s.stage_off, t, p->planes, cv, flip);
+	}
+	return slot;
+}
+extern "C" int mij_enc_add_planes(mij_encoder *e, const mij_in_planes *p, int quality) { return enc_add_planes(e, p, quality, false); }
+extern "C" int mij_enc_add_device_planes(mij_encoder *e, const mij_in_planes *p, int quality) { return enc_add_planes(e, p, quality, true); }
 
 /* A slot has a header of its own unless it is a plain clone of a plain root, which shares the root's: k_emit_build writes an optimised
  * slot's DHT segment into its header. */
@@ -4740,7 +4929,7 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 	const size_t n = e->slots.size();
 	if (!n)
 		return set_err(MIJ_E_STATE, "encoder batch is empty");
-	std::vector<WorkIdct> work[9];
+	std::vector<WorkIdct> work[MIJ_ENC_GROUPS];
 	for (size_t i = 0; i < n; ++i) {
 		const EncSlot &s = e->slots[i];
 		const uint32_t nm = (uint32_t)(s.plan.mcu_x * s.plan.mcu_y);
@@ -4749,6 +4938,15 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 		e->h_imgs[i] = s.dev;
 		if (!enc_has_pixels(s.kind)) /* given units, or units made from coefficient planes: nothing to transform */
 			continue;
+		if (s.planes) { /* always its own strip kernel */
+			const int g = s.tp.ncomp == 1 ? 13 : 9 + (s.tp.lh == 2 ? 1 : 0) + (s.tp.lv == 2 ? 2 : 0);
+			const uint32_t strip = (uint32_t)MIJ_ENCP_STRIP(s.tp.lh, s.tp.lv, s.tp.ncomp);
+			for (uint32_t f = 0; f < nm; f += strip) {
+				WorkIdct w = {(uint32_t)i, 0u, f, 0u};
+				work[g].push_back(w);
+			}
+			continue;
+		}
 		/* a sampling of its own: the strip kernel of its MCU shape, whatever force_generic says; 4:2:0 and 4:4:4 go on below, through the
 		 * kernel instances a default slot takes */
 		if (s.sampled && (s.tp.ncomp == 1 || s.tp.lh != s.tp.lv)) {
@@ -4787,7 +4985,7 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 		}
 	}
 	size_t total = 0;
-	for (int g = 0; g < 9; ++g)
+	for (int g = 0; g < MIJ_ENC_GROUPS; ++g)
 		total += work[g].size();
 	if (total > e->work_cap)
 		HIP_TRY(hipStreamSynchronize(e->stream));
@@ -4795,7 +4993,7 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 	if (rc != MIJ_OK)
 		return rc;
 	size_t pos = 0;
-	for (int g = 0; g < 9; ++g) {
+	for (int g = 0; g < MIJ_ENC_GROUPS; ++g) {
 		e->first_work[g] = pos;
 		e->n_work[g] = work[g].size();
 		if (!work[g].empty())
@@ -4815,6 +5013,8 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 	rc = enc_gather(e); /* device-pixel slots, before the clones copy them */
 	if (rc == MIJ_OK)
 		rc = enc_gather_float(e);
+	if (rc == MIJ_OK)
+		rc = enc_gather_planes(e);
 	if (rc == MIJ_OK)
 		rc = enc_coef_convert(e);
 	if (rc != MIJ_OK)
@@ -4842,12 +5042,26 @@ extern "C" int mij_enc_launch(mij_encoder *e)
 	if (!e->uploaded)
 		return set_err(MIJ_E_STATE, "mij_enc_launch before mij_enc_upload");
 	HIP_TRY(hipSetDevice(e->ctx->device));
-	for (int g = 0; g < 9; ++g) {
+	for (int g = 0; g < MIJ_ENC_GROUPS; ++g) {
 		if (!e->n_work[g])
 			continue;
 		const dim3 grid((unsigned)e->n_work[g]), block(g == 6 ? 128 : g == 4 || g == 5 ? 192 : 256);
 		const WorkIdct *wk = e->d_work + e->first_work[g];
-		if (g == 6)
+#define MIJ_ENCP_LAUNCH(LH, LV, NC)                                                                                                      \
+	hipLaunchKernelGGL((k_encode_planes<LH, LV, NC>), grid, dim3(MIJ_ENCP_NT(LH, LV, NC)), MIJ_ENCP_LDS(LH, LV, NC), e->stream, e->d_imgs, wk, \
+							 e->d_pix, e->d_du)
+		if (g == 9)
+			MIJ_ENCP_LAUNCH(1, 1, 3);
+		else if (g == 10)
+			MIJ_ENCP_LAUNCH(2, 1, 3);
+		else if (g == 11)
+			MIJ_ENCP_LAUNCH(1, 2, 3);
+		else if (g == 12)
+			MIJ_ENCP_LAUNCH(2, 2, 3);
+		else if (g == 13)
+			MIJ_ENCP_LAUNCH(1, 1, 1);
+#undef MIJ_ENCP_LAUNCH
+		else if (g == 6)
 			hipLaunchKernelGGL(k_encode422, grid, block, MIJ_ENC422_LDS, e->stream, e->d_imgs, wk, e->d_pix, e->d_du);
 		else if (g == 7)
 			hipLaunchKernelGGL(k_encode440, grid, block, MIJ_ENC440_LDS, e->stream, e->d_imgs, wk, e->d_pix, e->d_du);

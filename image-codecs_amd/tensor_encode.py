@@ -10,7 +10,7 @@ import math
 import torch
 
 from .binding import (Context, Encoder, InConvert, InTensor, WritePlan, emit_jpeg, emit_transcoded, lib, sampled_plan, sampling_factors,
-                      sampling_name, _qtable_pair, MIJ_LAYOUT_HWC, MIJ_LAYOUT_CHW, MIJ_DT_F16, MIJ_DT_BF16, MIJ_DT_F32)
+                      sampling_name, _qtable_pair, plane_sampling, planes_plan, split_planes, video_range_convert, MIJ_LAYOUT_HWC, MIJ_LAYOUT_CHW, MIJ_DT_F16, MIJ_DT_BF16, MIJ_DT_F32)
 from .tensor_out import _one_hip_runtime
 
 # one launch takes at most this many pictures / bytes of pixel arena; larger calls are cut into chunks
@@ -265,6 +265,129 @@ class TensorEncoder:
         return self._encode(images, mean, std, quality, layout, flip_vertically, optimize, True, restart_rows, restart_mcus, progressive,
                             subsampling, qtables)
 
+    def encode_ycbcr(self, pictures, *, subsampling="420", video_range=False, quality=90, qtables=None, flip_vertically=False, optimize=False,
+                     restart_rows=None, restart_mcus=None, progressive=False):
+        """JPEG streams from Y, Cb and Cr PLANES as a video decoder, a camera pipeline or a model holds them: no conversion to RGB and
+        back, no second chroma filter -- the samples reach the stream as they lie (include/mij_host.h, PLANE ENCODING) -> one bytes
+        object per picture: what mjh_write_jpg_planes_to_memory writes for those planes.
+        pictures: a sequence whose entries are (Y, Cb, Cr), three 2-D uint8 tensors on the GPU with any strides (I420, 4:2:2, 4:4:4);
+        (Y, CbCr) with CbCr of shape [ch, cw, 2] (NV12; for NV21 pass CbCr.flip(-1) or the two strided slices); or Y alone with
+        subsampling="grey".  Or one [N, 3, H, W] tensor with subsampling="444".  Y is H x W, Cb and Cr are ceil(H / lv) x ceil(W / lh).
+        subsampling: "444", "422", "440", "420" or "grey", one value or one per picture.  It is required knowledge, never guessed from
+        the shapes.
+        video_range: the planes hold studio-range samples (Y 16..235, chroma 16..240) and are expanded to JFIF's full range on the GPU,
+        inside the kernel that gathers them (mjw_video_range's constants, mij_in_convert's arithmetic).  Only the range is converted: the
+        colour matrix (BT.601 against BT.709) is not touched.
+        quality, qtables, flip_vertically, optimize, restart_rows, restart_mcus, progressive: as for encode(); the MCU, and with it a
+        restart interval, is 8 * lh x 8 * lv pixels.  last_subsampling and last_restarts report as they do for encode().
+        ValueError for plane shapes that do not match, a dtype other than uint8, a tensor that is not on a GPU, an unknown sampling and a
+        restart interval together with progressive."""
+        if not isinstance(optimize, bool):
+            raise ValueError("optimize must be a bool, got %r" % (optimize,))
+        if not isinstance(progressive, bool):
+            raise ValueError("progressive must be a bool, got %r" % (progressive,))
+        if not isinstance(video_range, bool):
+            raise ValueError("video_range must be a bool, got %r" % (video_range,))
+        if isinstance(quality, bool) or not isinstance(quality, int) or not 0 <= quality <= 100:
+            raise ValueError("quality must be an int in 0..100 (0: stbi_write_jpg's default, 90), got %r" % (quality,))
+        if qtables is not None:
+            if quality not in (0, 90):
+                raise ValueError("qtables replace the tables of a quality: give one of the two (quality=%r)" % (quality,))
+            qtables = _qtable_pair(qtables)
+            qtables = (list(qtables[0]), list(qtables[1]))
+        if isinstance(pictures, torch.Tensor):
+            if pictures.dim() != 4 or pictures.shape[1] != 3:
+                raise ValueError("a tensor of pictures is [N, 3, H, W] (with subsampling='444'), got %s" % (tuple(pictures.shape),))
+            pictures = [tuple(p.unbind(0)) for p in pictures.unbind(0)]
+        else:
+            pictures = list(pictures)
+        if subsampling is None:
+            plane_sampling(None)  # ValueError: the sampling is required
+        samplings = _sampling_values(subsampling, len(pictures))
+        for sm in samplings:
+            plane_sampling(sm)
+        pics = []
+        for i, (pic, sm) in enumerate(zip(pictures, samplings)):
+            for t in ([pic] if isinstance(pic, torch.Tensor) else list(pic)):
+                if not isinstance(t, torch.Tensor):
+                    raise ValueError("picture %d: a plane is not a tensor" % i)
+                if t.dtype != torch.uint8:
+                    raise ValueError("picture %d: a plane is %s; planes hold uint8 samples" % (i, t.dtype))
+            try:
+                planes = split_planes(pic, sm)
+            except ValueError as e:
+                raise ValueError("picture %d: %s" % (i, e)) from None
+            pics.append(planes)
+        rrows, rmcus = _restart_values(restart_rows, len(pics), "restart_rows"), _restart_values(restart_mcus, len(pics), "restart_mcus")
+        if progressive and (any(rrows) or any(rmcus)):
+            raise ValueError("restart intervals are not combined with progressive output")
+        for i, planes in enumerate(pics):
+            for t in planes:
+                if t.device.type != "cuda":
+                    raise ValueError("picture %d: a plane is on %s, not on a GPU" % (i, t.device))
+                if t.device != planes[0].device:
+                    raise ValueError("picture %d: its planes are on different devices" % i)
+                if any(st == 0 and n > 1 for st, n in zip(t.stride(), t.shape)):
+                    raise ValueError("picture %d: a plane has a stride of 0 (an expanded tensor); planes are addressed by pitches > 0" % i)
+            h, w = planes[0].shape
+            if not (1 <= w <= 65535 and 1 <= h <= 65535):
+                raise ValueError("picture size %dx%d outside 1..65535" % (w, h))
+        self.last_restarts = restarts = []
+        self.last_subsampling = used = []
+        if not pics:
+            return []
+        sizes, plans = [], {}
+        for k, planes in enumerate(pics):
+            h, w = planes[0].shape
+            t = plans.get((w, h, samplings[k]))
+            if t is None:
+                t = plans[(w, h, samplings[k])] = planes_plan(w, h, samplings[k], quality, qtables)
+            if t is None:
+                raise ValueError("picture %dx%d is refused by the writer" % (w, h))
+            p = t.plan
+            used.append(sampling_name(t))
+            units = p.mcu_x * p.mcu_y * p.du_per_mcu
+            sizes.append((_align(units * 64, 256), _align(units * 128, 256), w * h))
+            if rrows[k] and rmcus[k]:
+                raise ValueError("picture %d: restart_rows and restart_mcus are two ways to say the same thing: give one" % k)
+            ri = rrows[k] * p.mcu_x if rrows[k] else rmcus[k]
+            if ri > 65535:
+                raise ValueError("picture %d: a restart interval of %d MCUs does not fit the DRI segment (65535 at most)" % (k, ri))
+            restarts.append(ri)
+        if pics[0][0].device.index is not None and self._dev.index is not None and pics[0][0].device != self._dev:
+            raise ValueError("the planes are on %s, the encoder on %s" % (pics[0][0].device, self._dev))
+        _one_hip_runtime()
+        torch.cuda.current_stream(self.device).synchronize()
+        cv = video_range_convert() if video_range else None
+        flip = bool(flip_vertically)
+        out, host, i = [], 0, 0
+        while i < len(pics):
+            j, pix = i, 0
+            while j < len(pics) and j - i < MAX_SLOTS and (j == i or pix + sizes[j][0] <= MAX_PIXEL_BYTES):
+                pix += sizes[j][0]
+                j += 1
+            if not self._arena:  # a first guess, about 0.75 bytes per pixel; misses grow it
+                self._arena = _align(sum(1024 + (px * 3) // 4 for (_, _, px) in sizes[i:j]), 1 << 20)
+            enc = self._encoder_for(j - i, sum(s[0] for s in sizes[i:j]), sum(s[1] for s in sizes[i:j]))
+            for k in range(i, j):
+                planes = pics[k]
+                h, w = planes[0].shape
+                # a stride of an axis of one element addresses nothing: 0 rows down, 1 sample across
+                triples = [(t.data_ptr(), t.stride(0) if t.shape[0] > 1 else 0, t.stride(1) if t.shape[1] > 1 else 1) for t in planes]
+                slot = enc.add_device_planes(triples, w, h, samplings[k], quality, qtables, flip=flip, convert=cv)
+                if progressive:
+                    enc.set_progressive(slot)
+                elif optimize:
+                    enc.set_optimize(slot)
+                if restarts[k]:
+                    enc.set_restart(slot, restarts[k])
+            streams, hst = self._run(enc, [True] * (j - i), optimize, progressive)
+            out.extend(streams)
+            host += hst
+            i = j
+        self.last_host_emitted = host
+        return out
+
     def _encode(self, images, mean, std, quality, layout, flip_vertically, optimize, floats, restart_rows=None, restart_mcus=None,
                 progressive=False, subsampling=None, qtables=None):
         if not isinstance(optimize, bool):
@@ -351,14 +474,19 @@ class TensorEncoder:
                 enc.set_optimize(slot)
             if restarts and restarts[k]:
                 enc.set_restart(slot, restarts[k])
+        own = [qtables is not None or bool(samplings and samplings[slot] is not None) for slot in range(len(views))]
+        return self._run(enc, own, optimize, progressive)
+
+    def _run(self, enc, own, optimize, progressive):
+        """upload, launch and bring back the streams of the encoder's slots; own[slot]: the slot has a plan of its own (mij_enc_tplan)"""
         enc.upload()
         enc.launch()
         enc.fetch_streams()
         streams, need, host, grow = [], 0, 0, 0
-        for slot in range(len(views)):
+        for slot in range(len(own)):
             data, n = enc.stream(slot)
             if data is None:  # did not fit: its units are still on the device, the host Huffman stage finishes it
-                if qtables is not None or (samplings and samplings[slot] is not None):  # a plan of its own (mij_enc_tplan)
+                if own[slot]:
                     data = emit_transcoded(enc.tplan(slot), enc.fetch(slot), optimize, restart_mcus=enc.slot_restart(slot), progressive=progressive)
                 else:
                     data = emit_jpeg(enc.plan(slot), enc.fetch(slot), optimize, restart_mcus=enc.slot_restart(slot), progressive=progressive)

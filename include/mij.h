@@ -677,6 +677,41 @@ int mij_enc_add_device_float_ex(mij_encoder *e, const mij_in_tensor *t, const mi
                                 const mij_enc_opts *opts);
 size_t mij_enc_pixel_bytes_ex(int width, int height, int comp, int quality, const mij_enc_opts *opts);
 
+/*
+ * Slots whose input is Y, Cb and Cr PLANES (mij_host.h, PLANE ENCODING, is the contract; the units equal mjw_ptransform_host's bit for
+ * bit): frames of a video decoder (NV12, I420), 4:2:2 camera frames, the planes a model works in.  No colour conversion and no chroma
+ * filter runs: the samples reach the stream as they lie.  Sample (y, x) of plane c is the byte at planes[c].src + y * row_pitch +
+ * x * x_pitch; planes[0] is Y (height x width), planes[1] and [2] are Cb and Cr (ceil(height / lv) x ceil(width / lh)), both with
+ * src NULL for grey.  opts.ncomp, lh, lv are REQUIRED (one of the five samplings of mij_enc_opts; never 0), its tables optional.
+ * convert NULL: full-range samples; else dtype MIJ_DT_U8 and scale / bias [0] for Y, [1] for Cb, [2] for Cr (mjw_video_range fills it
+ * for studio-range frames).
+ * mij_enc_add_planes: host pointers, read during the call and staged in pinned memory.  mij_enc_add_device_planes: caller-owned device
+ * memory; every check of mij_enc_add_device applies to each plane (device memory of this device, the read extent inside one
+ * allocation, rows that do not overlap: row_pitch >= (w - 1) * x_pitch + 1 where the plane has more than one row), and its ORDERING rule.
+ * At mij_enc_upload k_enc_gather_planes brings the planes of device slots into the slot's share of the pixel arena as planar rows padded
+ * to whole MCUs of each component (mij_enc_plane_bytes), edge rule, flip, de-interleaving and range conversion applied; host slots are
+ * staged in that layout by the call.  k_encode_planes<LH, LV> then makes the units; mij_enc_force_generic does not apply.  MIJ_E_ARG for:
+ * a missing sampling, a chroma plane given for grey or missing otherwise, a zero or negative pitch, sizes mjw_plan_init refuses, a scale
+ * or bias that is not finite.  Everything behind the units works unchanged: mij_enc_set_optimize, mij_enc_set_restart (in the slot's own
+ * MCUs), mij_enc_set_progressive, mij_enc_add_clone, emission, the fetches, mij_enc_tplan.  Plane slots and pixel slots may share an
+ * upload; an upload without a plane slot queues exactly what it queued before.
+ */
+typedef struct {
+	const void *src;
+	int64_t row_pitch, x_pitch; /* bytes */
+} mij_plane;
+typedef struct {
+	mij_plane planes[3]; /* Y, Cb, Cr */
+	int32_t width, height;
+	mij_enc_opts opts;             /* sampling required */
+	const mij_in_convert *convert; /* NULL: none */
+	int32_t flip_vertically;
+} mij_in_planes;
+int mij_enc_add_planes(mij_encoder *e, const mij_in_planes *p, int quality);
+int mij_enc_add_device_planes(mij_encoder *e, const mij_in_planes *p, int quality);
+/* bytes a plane slot takes in the pixel arenas: (lh * lv + 2) * 64 * mcu_x * mcu_y (64 * mcu_x * mcu_y for grey), rounded up to 256 */
+size_t mij_enc_plane_bytes(int width, int height, const mij_enc_opts *opts);
+
 /* A slot whose quantised data units are given: mjw_plan_du_count * 64 int16 in zigzag order, MCU after MCU (copied).  No transform
  * runs for it; its units are uploaded and emitted.  MIJ_E_ARG when a DC difference (per component, in MCU order, from 0) leaves
  * -2047..2047 or an AC value leaves -1023..1023: those fall outside the writer's tables.  mij_enc_add_clone refuses such a slot. */

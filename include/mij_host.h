@@ -558,6 +558,52 @@ int mjh_write_jpg_sampled_to_memory(const void *pixels, int width, int height, i
                                     const unsigned char *luma, const unsigned char *chroma, int flip_vertically, unsigned flags, int restart_mcus,
                                     int progressive, unsigned char **out, size_t *out_len);
 
+/*
+ * PLANE ENCODING: the writer fed with Y, Cb and Cr samples as a producer holds them (I420, NV12 / NV21, 4:2:2, 4:4:4, packed YCbCr, grey) --
+ * nvJPEG's nvjpegEncodeYUV, Pillow's "YCbCr" mode.  A JPEG's components are Y, Cb and Cr at their sampling factors, so this is SAMPLED
+ * ENCODING with its first stage left out: no colour expression and no chroma mean; whatever subsampling the producer did is kept to the
+ * sample.  On the GPU: mij_enc_add_planes and mij_enc_add_device_planes (mij.h); these calls are the written contract, and the GPU gives the
+ * same data units bit for bit.
+ *
+ * PLAN: mjw_splan_init's plan for (ncomp, lh, lv), one of the five of SAMPLED ENCODING.  The sampling is REQUIRED: it is never derived from
+ * the quality and never guessed from plane shapes (a picture one pixel wide makes "444" and "422" indistinguishable).  plan.comp is 3, or 1
+ * for grey.  Tables as SAMPLED ENCODING has them.
+ *
+ * PLANES: Y is height x width; Cb and Cr are ceil(height / lv) x ceil(width / lh) each; grey has no Cb or Cr (their src must be NULL).
+ * Sample (y, x) of a plane is the byte at src + y * row_pitch + x * x_pitch (mij_plane, mij.h; pitches in bytes), so NV12 (x_pitch 2 on one
+ * interleaved plane: Cb at base, Cr at base + 1), NV21 (the same, swapped) and packed HWC YCbCr (x_pitch 3) are views, not formats.
+ *
+ * EDGE RULE: each plane is extended ON ITS OWN to whole blocks of its component -- 8 * mcu_x * lh luma columns and 8 * mcu_x chroma
+ * columns, 8 * mcu_y * lv luma rows and 8 * mcu_y chroma rows -- by repeating that plane's last column and last row.  flip_vertically
+ * reverses the rows of every plane.
+ *
+ * ARITHMETIC: the value that enters the fDCT for sample s is (float)s - 128.0f, which is exact; from there on mjw_transform_host's AAN
+ * fDCT and quantiser, the same functions.  Unit order is mjw_tplan's.
+ *
+ * VIDEO RANGE (optional per call): with a conversion cv (mij_in_convert, mij.h; dtype MIJ_DT_U8; entry 0 for Y, 1 for Cb, 2 for Cr) a
+ * sample first becomes u by mij_in_convert's contract applied to x = (float)s:
+ *     t = fl32( fl32(x * scale[c]) + bias[c] )        two roundings, no fused multiply-add
+ *     u = (uint8) rintf( fminf( fmaxf(t, 0.0f), 255.0f ) )
+ * and u is what is level-shifted.  mjw_video_range fills cv for studio-range frames (Y 16..235, chroma 16..240) into JFIF's full range:
+ * scale_y = float32(255/219), bias_y = float32(-16*255/219), scale_c = float32(255/224), bias_c = float32(128 - 128*255/224), each computed
+ * in double and rounded once: 16 -> 0, 235 -> 255, chroma 128 -> 128, chroma 240 -> 255, values outside clamp.  Only the range is
+ * converted: the colour MATRIX (BT.601 against BT.709) is not touched -- a decoder of the stream applies JFIF's BT.601 matrix.
+ *
+ *   mjw_pplan_init       mjw_splan_init with comp = ncomp and the sampling required: 0 also for ncomp 0
+ *   mjw_ptransform_host  the units of the planes, mjw_tplan_du_count(t) of them; cv may be NULL.  0 on bad arguments: a plan that is not
+ *                        mjw_pplan_init's, a missing plane, a chroma plane given for grey, a zero x_pitch, a scale or bias that is not finite
+ *   mjh_write_jpg_planes_to_memory   plan + transform + mjw_temit* on the host; flags, restart_mcus and progressive as
+ *                        mjh_write_jpg_sampled_to_memory takes them.  *out is malloc'ed (the caller frees it).  0 on bad arguments.
+ * Out of scope: decoding to planes, 4:1:1 and other factors, samples wider than 8 bits, conversion between colour matrices.
+ */
+void mjw_video_range(mij_in_convert *cv);
+int mjw_pplan_init(mjw_tplan *t, int width, int height, int quality, int ncomp, int lh, int lv, const unsigned char *luma,
+                   const unsigned char *chroma);
+int mjw_ptransform_host(const mjw_tplan *t, const mij_plane *planes, const mij_in_convert *cv, int flip_vertically, int16_t *du);
+int mjh_write_jpg_planes_to_memory(const mij_plane *planes, int width, int height, int quality, int ncomp, int lh, int lv,
+                                   const unsigned char *luma, const unsigned char *chroma, const mij_in_convert *cv, int flip_vertically,
+                                   unsigned flags, int restart_mcus, int progressive, unsigned char **out, size_t *out_len);
+
 /* The tables of stbi__ldr_to_hdr(common.c:391-424) for mij_batch_set_out_f32: lut[256*k + v] for channel k < n_out.  Colour
  * channels (all of them for odd n_out, all but the last for even n_out) get (float)(pow(v / 255.0f, gamma) * scale), the
  * alpha channel of n_out 2 and 4 gets v / 255.0f -- the reference's expressions, evaluated with libm's pow. */
