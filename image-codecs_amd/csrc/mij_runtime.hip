@@ -3181,131 +3181,62 @@ extern "C" int mij_batch_entropy_rounds(const mij_batch *b) { return b && b->es 
 static_assert(MIJ_EMIT_HDR == MJW_HEADER_RESTART_BYTES, "header size");
 
 /* where a slot's input comes from: pinned staging, a device tensor, given units, a decode batch's coefficient planes */
-enum { ENC_HOST = 0, ENC_DEVICE = 1, ENC_UNITS = 2, ENC_COEF = 3 };
-static inline bool enc_has_pixels(int kind) { return kind == ENC_HOST || kind == ENC_DEVICE; }
+enum EncKind { ENC_HOST = 0, ENC_DEVICE = 1, ENC_UNITS = 2, ENC_COEF = 3 };
+static inline bool enc_has_pixels(EncKind kind) { return kind == ENC_HOST || kind == ENC_DEVICE; }
 
-#define MIJ_ENC_GROUPS 14
+/* The transform kernels, in launch order: the per-unit luma / chroma pairs of 4:4:4 and 4:2:0 (the strip kernels' test twins,
+ * mij_enc_force_generic), the strip kernels of pixel slots, the strip kernels of plane slots.  Every one takes (slots, work, pixel arena,
+ * unit arena).  A work item is `strip` consecutive MCUs of one slot; of the per-unit pairs, 256 units of one kind. */
+enum EncGroup { EG_NONE = -1, EG_Y444 = 0, EG_C444, EG_Y420, EG_C420, EG_420, EG_444, EG_422, EG_440, EG_GREY, EG_P444, EG_P422, EG_P440, EG_P420, EG_PGREY, EG_GROUPS };
+struct EncFamily {
+	void (*k)(const EncImage *, const WorkIdct *, const uint8_t *, int16_t *);
+	unsigned threads; /* workgroup size */
+	size_t lds;       /* dynamic LDS bytes */
+	uint32_t strip;
+};
+#define MIJ_ENCP(LH, LV, NC) {k_encode_planes<LH, LV, NC>, MIJ_ENCP_NT(LH, LV, NC), MIJ_ENCP_LDS(LH, LV, NC), MIJ_ENCP_STRIP(LH, LV, NC)}
+static const EncFamily enc_families[EG_GROUPS] = {
+	/* EG_Y444 */ {k_encode_y<0>, 256, 0, 256},
+	/* EG_C444 */ {k_encode_c<0>, 256, 0, 256},
+	/* EG_Y420 */ {k_encode_y<1>, 256, 0, 256},
+	/* EG_C420 */ {k_encode_c<1>, 256, 0, 256},
+	/* EG_420 */ {k_encode420, 192, MIJ_ENC_LDS, MIJ_ENC_STRIP},
+	/* EG_444 */ {k_encode444, 192, MIJ_ENC444_LDS, MIJ_ENC444_STRIP},
+	/* EG_422 */ {k_encode422, 128, MIJ_ENC422_LDS, MIJ_ENC422_STRIP},
+	/* EG_440 */ {k_encode440, 256, MIJ_ENC440_LDS, MIJ_ENC440_STRIP},
+	/* EG_GREY */ {k_encode_grey, 256, MIJ_ENCGREY_LDS, MIJ_ENCGREY_STRIP},
+	/* EG_P444 */ MIJ_ENCP(1, 1, 3),
+	/* EG_P422 */ MIJ_ENCP(2, 1, 3),
+	/* EG_P440 */ MIJ_ENCP(1, 2, 3),
+	/* EG_P420 */ MIJ_ENCP(2, 2, 3),
+	/* EG_PGREY */ MIJ_ENCP(1, 1, 1),
+};
+#undef MIJ_ENCP
+
 struct EncSlot {
-	mjw_plan plan;
+	mjw_tplan tp; /* the slot's plan, whatever its kind: a pixel slot without options has the writer's 4:2:0 or 4:4:4 */
 	EncImage dev;
 	size_t stage_off, pix_bytes, du_bytes;
 	int pad_w; /* pixels per staged row: the width rounded up to whole MCU columns (enc_padded_width); staged rows are packed RGB */
 	int clone_of, flip;
-	int kind;                   /* ENC_*; a clone copies its root's pixels whatever the root's kind */
+	EncKind kind;               /* a clone copies its root's pixels whatever the root's kind */
 	bool optimize;              /* mij_enc_set_optimize */
 	int restart;                /* mij_enc_set_restart: the restart interval in MCUs, 0: none */
 	bool progressive;           /* mij_enc_set_progressive */
 	mij_in_tensor in;           /* ENC_DEVICE */
 	mij_in_convert cv;          /* ENC_DEVICE with float elements (mij_enc_add_device_float); cv.dtype is MIJ_DT_U8 for every other slot */
 	std::vector<int16_t> units; /* ENC_UNITS */
-	/* ENC_COEF (mij_enc_add_coef): the transcode plan (tp.plan == plan), the batch, and where the slot's planes lay when it was added */
-	mjw_tplan tp;
+	/* ENC_COEF (mij_enc_add_coef): the batch, and where the slot's planes lay when it was added */
 	mij_batch *src;
 	CoefSlot coef;
 	int coef_fmt;
 	int rect[4];                  /* the kept rectangle in the displayed frame (mij_enc_slot_rect) */
 	bool greyed;                  /* Cb and Cr of a colour source were dropped */
-	bool sampled;                 /* a pixel slot made with a sampling or tables of its own (mij_enc_add_ex and its kin): tp is its plan */
-	bool planes;                  /* a plane slot (mij_enc_add_planes, mij_enc_add_device_planes): sampled too, tp its plan; the staging is planar */
+	bool sampled;                 /* a pixel slot made with a sampling or tables of its own (mij_enc_add_ex and its kin): mij_enc_tplan answers */
+	bool planes;                  /* a plane slot (mij_enc_add_planes, mij_enc_add_device_planes): sampled too; the staging is planar */
 	mij_plane pl[3];              /* its planes, ENC_DEVICE only */
 	bool pl_convert;              /* cv holds its range conversion (dtype MIJ_DT_U8; entries 0..2: Y, Cb, Cr) */
 	unsigned char rq_from[2][64]; /* a requantising slot (coef.rq != 0): the tables tp's replaced, luma and chroma, zigzag order */
-};
-
-struct mij_encoder {
-	mij_ctx *ctx;
-	hipStream_t stream;
-	hipEvent_t ev_begin, ev_end;
-	int max_images;
-	uint8_t *stage;   /* pinned pixels */
-	size_t stage_cap, stage_used;
-	uint8_t *d_pix;
-	size_t pix_cap, pix_used;
-	int16_t *d_du;
-	size_t du_cap, du_used; /* bytes */
-	int16_t *h_du;   /* pinned mirror for fetch */
-	EncImage *h_imgs, *d_imgs;
-	WorkIdct *h_work, *d_work;
-	size_t work_cap;
-	size_t n_work[MIJ_ENC_GROUPS], first_work[MIJ_ENC_GROUPS]; /* [sub*2 + kind]: kind 0 luma units, 1 chroma units; [4]: fused 4:2:0 strips;
-	                                    [5]: fused 4:4:4 strips; [6], [7], [8]: 4:2:2, 4:4:0 and grey strips (sampled slots); [9] .. [13]: the
-	                                    strips of plane slots: 4:4:4, 4:2:2, 4:4:0, 4:2:0, grey */
-	std::vector<EncSlot> slots;
-	bool uploaded, launched, force_generic;
-	/* device-pixel slots: the gather kernel's slots and work (rows of MIJ_GATHER_ROWS) */
-	EncGather *h_gath, *d_gath;
-	size_t gath_cap;
-	WorkIdct *h_gwork, *d_gwork;
-	size_t gwork_cap, n_gwork;
-	/* the same for the device plane slots (k_enc_gather_planes) */
-	EncGatherP *h_pgath, *d_pgath;
-	size_t pgath_cap;
-	WorkIdct *h_pgwork, *d_pgwork;
-	size_t pgwork_cap;
-	/* the same for the float device-pixel slots, grouped by dtype: one launch of k_enc_gather_float each */
-	EncGatherF *h_fgath, *d_fgath;
-	size_t fgath_cap;
-	WorkIdct *h_fgwork, *d_fgwork;
-	size_t fgwork_cap;
-	/* GPU emission (mij_enc_stream_reserve): the stream arena and its pinned mirror, the code tables, per-slot and per-tile lists */
-	uint8_t *d_arena, *h_arena;
-	size_t arena_cap;
-	EmitTables *d_tabs;
-	EmitSlot *h_eslot, *d_eslot;
-	size_t eslot_cap;
-	EmitTile *h_etile, *d_etile;
-	size_t etile_cap, n_etile;
-	uint8_t *h_hdr, *d_hdr;
-	size_t hdr_cap;
-	EmitResult *h_res, *d_res;
-	size_t res_cap;
-	uint32_t *d_tbits, *d_tff, *d_tfrag;
-	uint64_t *d_tboff, *d_tout, *d_sent;
-	size_t tmeta_cap, sent_cap;
-	bool emit_queued, streams_fetched;
-	/* optimised Huffman tables (mij_enc_set_optimize): d_tabs holds tabs_cap entries, entry 0 the plain tables (h_tabs0) and entry k + 1 those of
-	 * the k-th optimised slot; its tiles, its slot number, its counts and whether it kept its own tables */
-	EmitTables h_tabs0;
-	size_t tabs_cap;
-	EmitTile *h_otile, *d_otile;
-	size_t otile_cap, n_otile;
-	uint32_t *h_optslot, *d_optslot;
-	size_t optslot_cap, n_opt;
-	uint32_t *d_freq, *d_optok;
-	size_t freq_cap, optok_cap;
-	/* coefficient slots (mij_enc_add_coef): the conversion kernel's slots and work (plane tiles), the event that orders it behind the
-	 * batch's stream, and the per-slot flags it raises for uncodable values (d_sflag: one per slot, read by k_emit_count) */
-	CoefSlot *h_cslot, *d_cslot;
-	size_t cslot_cap;
-	WorkIdct *h_cwork, *d_cwork;
-	size_t cwork_cap;
-	RqTable *h_rqt, *d_rqt; /* one per requantising slot of the upload (CoefSlot::rq - 1) */
-	size_t rqt_cap;
-	uint32_t *d_sflag;
-	size_t sflag_cap;
-	hipEvent_t ev_coef;
-	bool has_coef; /* the last upload had a coefficient slot */
-	uint32_t coef_tiles; /* plane tiles its conversion queued (mij_enc_coef_tiles) */
-	std::vector<uint32_t> sflag; /* after mij_enc_fetch_streams */
-	hipEvent_t ev_conv0, ev_conv1; /* around the conversion kernels of the last upload (mij_enc_coef_ms) */
-	bool conv_timed;
-	/* progressive slots (mij_enc_set_progressive; mij_progressive_kernels.h): their records, the numbers of their tiles in the tile list, the
-	 * block bytes of their AC scans, per-tile summaries and run results, per-scan counts, scan headers and their lengths, and the per-slot flag
-	 * of the slots the host finishes (a forced flush, a table that cannot be built) */
-	ProgSlot *h_pslot, *d_pslot;
-	size_t pslot_cap, n_prog;
-	uint32_t *h_ptile, *d_ptile;
-	size_t ptile_cap, n_ptile;
-	uint8_t *d_pfl, *d_phdr;
-	size_t pfl_cap, phdr_cap;
-	ProgTileSum *d_tsum;
-	ProgAfter *d_tafter;
-	size_t tsum_cap, tafter_cap;
-	uint32_t *d_pfreq, *d_phlen, *d_pflag, *d_ctail;
-	size_t pfreq_cap, phlen_cap, pflag_cap, ctail_cap;
-	std::vector<uint32_t> pflag; /* after mij_enc_fetch_streams */
-	std::vector<int> opt_of;      /* slot -> k, or -1 */
-	std::vector<uint32_t> opt_ok; /* after mij_enc_fetch_streams */
 };
 
 template <typename T>
@@ -3321,54 +3252,151 @@ static int grow_dev(T *&d, size_t &cap, size_t need)
 	return MIJ_OK;
 }
 
+/* A list or an arena the encoder owns: `cap` elements in pinned memory, in device memory or (a list the host fills and a kernel reads) in
+ * both.  alloc is for the arenas, whose size the caller chose; grow for the lists, by the rule of grow_pair, and only through EncGrow. */
+enum { ENC_PINNED = 1, ENC_ON_DEVICE = 2 };
+template <typename T, int SIDES = ENC_PINNED | ENC_ON_DEVICE>
+struct EncBuf {
+	T *h = nullptr, *d = nullptr;
+	size_t cap = 0;
+	EncBuf() = default;
+	EncBuf &operator=(EncBuf &&o) /* o, a temporary, releases what this held */
+	{
+		std::swap(h, o.h), std::swap(d, o.d), std::swap(cap, o.cap);
+		return *this;
+	}
+	~EncBuf() { release(); }
+	void release()
+	{
+		free_host(h);
+		free_dev(d);
+		cap = 0;
+	}
+	hipError_t alloc(size_t n) /* exactly n elements; an empty arena still has an address */
+	{
+		release();
+		hipError_t r = hipSuccess;
+		if (SIDES & ENC_PINNED)
+			r = hipHostMalloc(reinterpret_cast<void **>(&h), sizeof(T) * (n ? n : 16), hipHostMallocDefault);
+		if (r == hipSuccess && (SIDES & ENC_ON_DEVICE))
+			r = hipMalloc(reinterpret_cast<void **>(&d), sizeof(T) * (n ? n : 16));
+		if (r == hipSuccess)
+			cap = n;
+		return r;
+	}
+	int grow(size_t need)
+	{
+		static_assert(SIDES & ENC_ON_DEVICE, "only the lists grow");
+		if constexpr ((SIDES & ENC_PINNED) != 0)
+			return grow_pair(h, d, cap, need);
+		else
+			return grow_dev(d, cap, need);
+	}
+};
+
+/* Grows the lists of one upload step.  Copies and launches queued earlier may still read a list, so the first one that has to be
+ * reallocated waits for the stream: one wait however many grow, none when none does.  rc is the first failure. */
+struct EncGrow {
+	hipStream_t stream;
+	bool waited = false;
+	int rc = MIJ_OK;
+	explicit EncGrow(hipStream_t st) : stream(st) {}
+	template <typename T, int SIDES>
+	bool operator()(EncBuf<T, SIDES> &b, size_t need) /* true: b was reallocated */
+	{
+		if (rc != MIJ_OK || need <= b.cap)
+			return false;
+		if (!waited) {
+			const hipError_t r = hipStreamSynchronize(stream);
+			if (r != hipSuccess) {
+				rc = set_err(MIJ_E_HIP, "hipStreamSynchronize(e->stream) failed: %s", hipGetErrorString(r));
+				return false;
+			}
+			waited = true;
+		}
+		rc = b.grow(need);
+		return rc == MIJ_OK;
+	}
+};
+
+/* GPU emission (mij_enc_stream_reserve): everything enc_free_emit gives back */
+struct EncEmit {
+	EncBuf<uint8_t> arena; /* the streams, and the pinned mirror mij_enc_stream points into; bytes */
+	/* the code tables: entry 0 the plain ones (h_tabs0), entry k + 1 those of the k-th optimised slot, then MIJ_PROG_SCANS per progressive slot */
+	EncBuf<EmitTables, ENC_ON_DEVICE> tabs;
+	EmitTables h_tabs0;
+	/* per-slot and per-tile lists, the headers (MIJ_EMIT_HDR bytes each), the results */
+	EncBuf<EmitSlot> eslot;
+	EncBuf<EmitTile> etile;
+	EncBuf<uint8_t> hdr;
+	EncBuf<EmitResult> res;
+	EncBuf<uint32_t, ENC_ON_DEVICE> tbits, tff, tfrag;
+	EncBuf<uint64_t, ENC_ON_DEVICE> tboff, tout, sent;
+	size_t n_etile = 0;
+	/* optimised Huffman tables (mij_enc_set_optimize): the optimised slots' tiles, their slot numbers, their counts and whether each kept
+	 * its own tables */
+	EncBuf<EmitTile> otile;
+	EncBuf<uint32_t> optslot;
+	EncBuf<uint32_t, ENC_ON_DEVICE> freq, optok;
+	size_t n_otile = 0, n_opt = 0;
+	/* progressive slots (mij_enc_set_progressive; mij_progressive_kernels.h): their records, the numbers of their tiles in the tile list, the
+	 * block bytes of their AC scans, scan headers and their lengths, per-tile summaries and run results, per-scan counts, and the per-slot
+	 * flag of the slots the host finishes (a forced flush, a table that cannot be built) */
+	EncBuf<ProgSlot> pslot;
+	EncBuf<uint32_t> ptile;
+	EncBuf<uint8_t, ENC_ON_DEVICE> pfl, phdr;
+	EncBuf<ProgTileSum, ENC_ON_DEVICE> tsum;
+	EncBuf<ProgAfter, ENC_ON_DEVICE> tafter;
+	EncBuf<uint32_t, ENC_ON_DEVICE> pfreq, phlen, pflag, ctail;
+	size_t n_prog = 0, n_ptile = 0;
+};
+
+struct mij_encoder {
+	mij_ctx *ctx = nullptr;
+	hipStream_t stream = nullptr;
+	hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+	int max_images = 0;
+	/* the arenas, sized at creation, in bytes: pinned pixels, device pixels, the data units and their pinned mirror (made at the first
+	 * mij_enc_fetch_all) */
+	EncBuf<uint8_t, ENC_PINNED> stage;
+	EncBuf<uint8_t, ENC_ON_DEVICE> pix;
+	EncBuf<uint8_t, ENC_ON_DEVICE> du;
+	EncBuf<uint8_t, ENC_PINNED> du_host;
+	size_t stage_used = 0, pix_used = 0, du_used = 0;
+	EncBuf<EncImage> imgs; /* max_images of them */
+	EncBuf<WorkIdct> work;  /* the transform kernels' work items, group after group */
+	size_t n_work[EG_GROUPS] = {}, first_work[EG_GROUPS] = {};
+	std::vector<EncSlot> slots;
+	bool uploaded = false, launched = false, force_generic = false;
+	/* device-pixel slots: the gather kernels' slots and work (rows of MIJ_GATHER_ROWS) for uint8 tensors, float tensors (grouped by dtype:
+	 * one launch of k_enc_gather_float each) and planes (k_enc_gather_planes) */
+	EncBuf<EncGather> gath;
+	EncBuf<EncGatherF> fgath;
+	EncBuf<EncGatherP> pgath;
+	EncBuf<WorkIdct> gwork, fgwork, pgwork;
+	EncEmit em;
+	bool emit_queued = false, streams_fetched = false;
+	std::vector<int> opt_of;      /* slot -> k, or -1 */
+	std::vector<uint32_t> opt_ok; /* after mij_enc_fetch_streams */
+	std::vector<uint32_t> pflag;  /* after mij_enc_fetch_streams */
+	/* coefficient slots (mij_enc_add_coef): the conversion kernel's slots and work (plane tiles), one table per requantising slot of the
+	 * upload (CoefSlot::rq - 1), the event that orders it behind the batch's stream, and the per-slot flags it raises for uncodable
+	 * values (sflag_dev: one per slot, read by k_emit_count) */
+	EncBuf<CoefSlot> cslot;
+	EncBuf<WorkIdct> cwork;
+	EncBuf<RqTable> rqt;
+	EncBuf<uint32_t, ENC_ON_DEVICE> sflag_dev;
+	hipEvent_t ev_coef = nullptr;
+	bool has_coef = false;       /* the last upload had a coefficient slot */
+	uint32_t coef_tiles = 0;     /* plane tiles its conversion queued (mij_enc_coef_tiles) */
+	std::vector<uint32_t> sflag; /* after mij_enc_fetch_streams */
+	hipEvent_t ev_conv0 = nullptr, ev_conv1 = nullptr; /* around the conversion kernels of the last upload (mij_enc_coef_ms) */
+	bool conv_timed = false;
+};
+
 static void enc_free_emit(mij_encoder *e)
 {
-	free_dev(e->d_arena);
-	free_host(e->h_arena);
-	free_dev(e->d_tabs);
-	e->arena_cap = e->tabs_cap = 0;
-	free_host(e->h_otile);
-	free_dev(e->d_otile);
-	e->otile_cap = e->n_otile = 0;
-	free_host(e->h_optslot);
-	free_dev(e->d_optslot);
-	e->optslot_cap = e->n_opt = 0;
-	free_dev(e->d_freq);
-	free_dev(e->d_optok);
-	e->freq_cap = e->optok_cap = 0;
-	free_host(e->h_eslot);
-	free_dev(e->d_eslot);
-	e->eslot_cap = 0;
-	free_host(e->h_etile);
-	free_dev(e->d_etile);
-	e->etile_cap = e->n_etile = 0;
-	free_host(e->h_hdr);
-	free_dev(e->d_hdr);
-	e->hdr_cap = 0;
-	free_host(e->h_res);
-	free_dev(e->d_res);
-	e->res_cap = 0;
-	free_dev(e->d_tbits);
-	free_dev(e->d_tff);
-	free_dev(e->d_tfrag);
-	free_dev(e->d_tboff);
-	free_dev(e->d_tout);
-	free_dev(e->d_sent);
-	e->tmeta_cap = e->sent_cap = 0;
-	free_host(e->h_pslot);
-	free_dev(e->d_pslot);
-	free_host(e->h_ptile);
-	free_dev(e->d_ptile);
-	free_dev(e->d_pfl);
-	free_dev(e->d_phdr);
-	free_dev(e->d_tsum);
-	free_dev(e->d_tafter);
-	free_dev(e->d_pfreq);
-	free_dev(e->d_phlen);
-	free_dev(e->d_pflag);
-	free_dev(e->d_ctail);
-	e->pslot_cap = e->n_prog = e->ptile_cap = e->n_ptile = e->pfl_cap = e->phdr_cap = e->tsum_cap = e->tafter_cap = 0;
-	e->pfreq_cap = e->phlen_cap = e->pflag_cap = e->ctail_cap = 0;
+	e->em = EncEmit();
 	e->emit_queued = e->streams_fetched = false;
 }
 
@@ -3388,66 +3416,20 @@ extern "C" int mij_enc_create_ex(mij_ctx *ctx, int max_images, size_t stage_byte
 		return set_err(MIJ_E_NOMEM, "out of host memory");
 	e->ctx = ctx;
 	e->max_images = max_images;
-	e->stage = nullptr;
-	e->d_pix = nullptr;
-	e->d_du = nullptr;
-	e->h_du = nullptr;
-	e->h_imgs = e->d_imgs = nullptr;
-	e->h_work = e->d_work = nullptr;
-	e->work_cap = 0;
-	e->stage_cap = stage_bytes;
-	e->pix_cap = pixel_bytes;
-	e->du_cap = du_bytes;
-	e->stage_used = e->pix_used = e->du_used = 0;
-	e->uploaded = e->launched = false;
-	e->h_gath = e->d_gath = nullptr;
-	e->h_gwork = e->d_gwork = nullptr;
-	e->gath_cap = e->gwork_cap = e->n_gwork = 0;
-	e->h_fgath = e->d_fgath = nullptr;
-	e->h_fgwork = e->d_fgwork = nullptr;
-	e->fgath_cap = e->fgwork_cap = 0;
-	e->h_pgath = e->d_pgath = nullptr;
-	e->h_pgwork = e->d_pgwork = nullptr;
-	e->pgath_cap = e->pgwork_cap = 0;
-	e->d_arena = e->h_arena = nullptr;
-	e->d_tabs = nullptr;
-	e->h_eslot = e->d_eslot = nullptr;
-	e->h_etile = e->d_etile = nullptr;
-	e->h_hdr = e->d_hdr = nullptr;
-	e->h_res = e->d_res = nullptr;
-	e->d_tbits = e->d_tff = e->d_tfrag = nullptr;
-	e->d_tboff = e->d_tout = e->d_sent = nullptr;
-	e->h_otile = e->d_otile = nullptr;
-	e->h_optslot = e->d_optslot = nullptr;
-	e->d_freq = e->d_optok = nullptr;
-	e->h_cslot = e->d_cslot = nullptr;
-	e->h_cwork = e->d_cwork = nullptr;
-	e->h_rqt = e->d_rqt = nullptr;
-	e->rqt_cap = 0;
-	e->d_sflag = nullptr;
-	e->cslot_cap = e->cwork_cap = e->sflag_cap = 0;
-	e->ev_coef = e->ev_conv0 = e->ev_conv1 = nullptr;
-	e->has_coef = e->conv_timed = false;
-	e->coef_tiles = 0;
-	enc_free_emit(e);
 	e->force_generic = getenv("MIJ_ENC_GENERIC") != nullptr;
-	e->stream = nullptr;
-	e->ev_begin = e->ev_end = nullptr;
 	hipError_t r = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
 	if (r == hipSuccess)
 		r = hipEventCreate(&e->ev_begin);
 	if (r == hipSuccess)
 		r = hipEventCreate(&e->ev_end);
 	if (r == hipSuccess)
-		r = hipHostMalloc(reinterpret_cast<void **>(&e->stage), stage_bytes ? stage_bytes : 16, hipHostMallocDefault);
+		r = e->stage.alloc(stage_bytes);
 	if (r == hipSuccess)
-		r = hipMalloc(reinterpret_cast<void **>(&e->d_pix), pixel_bytes ? pixel_bytes : 16);
+		r = e->pix.alloc(pixel_bytes);
 	if (r == hipSuccess)
-		r = hipMalloc(reinterpret_cast<void **>(&e->d_du), du_bytes ? du_bytes : 16);
+		r = e->du.alloc(du_bytes);
 	if (r == hipSuccess)
-		r = hipHostMalloc(reinterpret_cast<void **>(&e->h_imgs), sizeof(EncImage) * (size_t)max_images, hipHostMallocDefault);
-	if (r == hipSuccess)
-		r = hipMalloc(reinterpret_cast<void **>(&e->d_imgs), sizeof(EncImage) * (size_t)max_images);
+		r = e->imgs.alloc((size_t)max_images);
 	if (r != hipSuccess) {
 		int code = (r == hipErrorOutOfMemory) ? MIJ_E_NOMEM : MIJ_E_HIP;
 		set_err(code, "mij_enc_create: %s", hipGetErrorString(r));
@@ -3465,55 +3447,14 @@ extern "C" void mij_enc_destroy(mij_encoder *e)
 	(void)hipSetDevice(e->ctx->device);
 	if (e->stream)
 		(void)hipStreamSynchronize(e->stream);
-	if (e->stage)
-		(void)hipHostFree(e->stage);
-	if (e->d_pix)
-		(void)hipFree(e->d_pix);
-	if (e->d_du)
-		(void)hipFree(e->d_du);
-	if (e->h_du)
-		(void)hipHostFree(e->h_du);
-	if (e->h_imgs)
-		(void)hipHostFree(e->h_imgs);
-	if (e->d_imgs)
-		(void)hipFree(e->d_imgs);
-	if (e->h_work)
-		(void)hipHostFree(e->h_work);
-	if (e->d_work)
-		(void)hipFree(e->d_work);
-	free_host(e->h_gath);
-	free_dev(e->d_gath);
-	free_host(e->h_gwork);
-	free_dev(e->d_gwork);
-	free_host(e->h_fgath);
-	free_dev(e->d_fgath);
-	free_host(e->h_fgwork);
-	free_dev(e->d_fgwork);
-	free_host(e->h_pgath);
-	free_dev(e->d_pgath);
-	free_host(e->h_pgwork);
-	free_dev(e->d_pgwork);
-	free_host(e->h_cslot);
-	free_dev(e->d_cslot);
-	free_host(e->h_cwork);
-	free_dev(e->d_cwork);
-	free_host(e->h_rqt);
-	free_dev(e->d_rqt);
-	free_dev(e->d_sflag);
-	if (e->ev_coef)
-		(void)hipEventDestroy(e->ev_coef);
-	if (e->ev_conv0)
-		(void)hipEventDestroy(e->ev_conv0);
-	if (e->ev_conv1)
-		(void)hipEventDestroy(e->ev_conv1);
-	enc_free_emit(e);
-	if (e->ev_begin)
-		(void)hipEventDestroy(e->ev_begin);
-	if (e->ev_end)
-		(void)hipEventDestroy(e->ev_end);
-	if (e->stream)
-		(void)hipStreamDestroy(e->stream);
-	delete e;
+	const hipStream_t stream = e->stream;
+	const hipEvent_t events[] = {e->ev_coef, e->ev_conv0, e->ev_conv1, e->ev_begin, e->ev_end};
+	delete e; /* its buffers release themselves, before the events and the stream go */
+	for (hipEvent_t ev : events)
+		if (ev)
+			(void)hipEventDestroy(ev);
+	if (stream)
+		(void)hipStreamDestroy(stream);
 }
 
 extern "C" int mij_enc_reset(mij_encoder *e)
@@ -3592,24 +3533,14 @@ extern "C" size_t mij_enc_plane_bytes(int width, int height, const mij_enc_opts 
 	return enc_plane_bytes(t);
 }
 
-/* the transcode-plan view of a writer's plan: 4:2:0 or 4:4:4 */
-static mjw_tplan enc_tplan_of(const mjw_plan &plan)
-{
-	mjw_tplan t;
-	t.plan = plan;
-	t.ncomp = 3;
-	t.lh = t.lv = plan.subsample ? 2 : 1;
-	return t;
-}
-
-static int enc_add_common(mij_encoder *e, const mjw_tplan &tplan, const void *pixels, int flip, int clone_of, int kind = ENC_HOST, bool sampled = false,
+static int enc_add_common(mij_encoder *e, const mjw_tplan &tplan, const void *pixels, int flip, int clone_of, EncKind kind = ENC_HOST, bool sampled = false,
                           bool planes = false)
 {
 	const mjw_plan &plan = tplan.plan;
 	if ((int)e->slots.size() >= e->max_images)
 		return set_err(MIJ_E_NOMEM, "encoder batch is full (%d images)", e->max_images);
 	EncSlot s;
-	s.plan = plan;
+	s.tp = tplan;
 	s.flip = flip;
 	s.clone_of = clone_of;
 	s.kind = kind;
@@ -3626,9 +3557,6 @@ static int enc_add_common(mij_encoder *e, const mjw_tplan &tplan, const void *pi
 	s.planes = planes;
 	memset(s.pl, 0, sizeof(s.pl));
 	s.pl_convert = false;
-	memset(&s.tp, 0, sizeof(s.tp));
-	if (sampled)
-		s.tp = tplan;
 	memset(&s.coef, 0, sizeof(s.coef));
 	memset(s.rq_from, 0, sizeof(s.rq_from));
 	memset(s.rect, 0, sizeof(s.rect));
@@ -3637,18 +3565,18 @@ static int enc_add_common(mij_encoder *e, const mjw_tplan &tplan, const void *pi
 	if (planes) /* planar, every plane padded to whole MCUs of its component both ways */
 		s.pix_bytes = enc_plane_bytes(tplan);
 	s.du_bytes = align_up(mjw_plan_du_count(&plan) * 128, 256);
-	if (e->pix_used + s.pix_bytes > e->pix_cap)
+	if (e->pix_used + s.pix_bytes > e->pix.cap)
 		return set_err(MIJ_E_NOMEM, "pixel arena exhausted");
-	if (e->du_used + s.du_bytes > e->du_cap)
+	if (e->du_used + s.du_bytes > e->du.cap)
 		return set_err(MIJ_E_NOMEM, "data-unit arena exhausted");
 	if (clone_of < 0 && kind != ENC_HOST) {
 		s.stage_off = 0; /* no pinned staging: the gather kernel or the units' own copy fills the device side */
 	} else if (clone_of < 0) {
-		if (e->stage_used + s.pix_bytes > e->stage_cap)
+		if (e->stage_used + s.pix_bytes > e->stage.cap)
 			return set_err(MIJ_E_NOMEM, "pixel staging exhausted");
 		s.stage_off = e->stage_used;
 		if (pixels) /* mij_enc_add_uncopied: the caller stages the pixels itself (mij_enc_stage_pixels, several threads at once) */
-			enc_stage_rows(e->stage + s.stage_off, static_cast<const uint8_t *>(pixels), plan.width, plan.height, plan.comp, s.pad_w);
+			enc_stage_rows(e->stage.h + s.stage_off, static_cast<const uint8_t *>(pixels), plan.width, plan.height, plan.comp, s.pad_w);
 		e->stage_used += s.pix_bytes;
 	} else {
 		s.stage_off = e->slots[(size_t)clone_of].stage_off;
@@ -3713,7 +3641,7 @@ extern "C" int mij_enc_stage_pixels(mij_encoder *e, int slot, const void *pixels
 		 e->slots[(size_t)slot].planes)
 		return set_err(MIJ_E_ARG, "bad slot or pixels");
 	const EncSlot &s = e->slots[(size_t)slot];
-	enc_stage_rows(e->stage + s.stage_off, static_cast<const uint8_t *>(pixels), s.plan.width, s.plan.height, s.plan.comp, s.pad_w);
+	enc_stage_rows(e->stage.h + s.stage_off, static_cast<const uint8_t *>(pixels), s.tp.plan.width, s.tp.plan.height, s.tp.plan.comp, s.pad_w);
 	return MIJ_OK;
 }
 
@@ -3721,7 +3649,7 @@ extern "C" void *mij_enc_staging(mij_encoder *e, int slot)
 {
 	if (!e || slot < 0 || slot >= (int)e->slots.size() || e->slots[(size_t)slot].clone_of >= 0 || e->slots[(size_t)slot].kind != ENC_HOST)
 		return nullptr;
-	return e->stage + e->slots[(size_t)slot].stage_off;
+	return e->stage.h + e->slots[(size_t)slot].stage_off;
 }
 
 /* every slot's data units into the encoder's pinned mirror in one copy; mij_enc_units(slot) then points at a slot's units */
@@ -3732,10 +3660,10 @@ extern "C" int mij_enc_fetch_all(mij_encoder *e)
 	if (!e->launched)
 		return set_err(MIJ_E_STATE, "mij_enc_fetch_all before launch");
 	HIP_TRY(hipSetDevice(e->ctx->device));
-	if (!e->h_du)
-		HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_du), e->du_cap, hipHostMallocDefault));
+	if (!e->du_host.h)
+		HIP_TRY(e->du_host.alloc(e->du.cap));
 	if (e->du_used)
-		HIP_TRY(hipMemcpyAsync(e->h_du, e->d_du, e->du_used, hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->du_host.h, e->du.d, e->du_used, hipMemcpyDeviceToHost, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	return MIJ_OK;
 }
@@ -3748,226 +3676,217 @@ extern "C" int mij_enc_fetch_all_async(mij_encoder *e)
 	if (!e->launched)
 		return set_err(MIJ_E_STATE, "mij_enc_fetch_all_async before launch");
 	HIP_TRY(hipSetDevice(e->ctx->device));
-	if (!e->h_du)
-		HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_du), e->du_cap, hipHostMallocDefault));
+	if (!e->du_host.h)
+		HIP_TRY(e->du_host.alloc(e->du.cap));
 	if (e->du_used)
-		HIP_TRY(hipMemcpyAsync(e->h_du, e->d_du, e->du_used, hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->du_host.h, e->du.d, e->du_used, hipMemcpyDeviceToHost, e->stream));
 	return MIJ_OK;
 }
 
 extern "C" const int16_t *mij_enc_units(const mij_encoder *e, int slot)
 {
-	if (!e || !e->h_du || slot < 0 || slot >= (int)e->slots.size())
+	if (!e || !e->du_host.h || slot < 0 || slot >= (int)e->slots.size())
 		return nullptr;
-	return reinterpret_cast<const int16_t *>(reinterpret_cast<const uint8_t *>(e->h_du) + e->slots[(size_t)slot].dev.du_off);
+	return reinterpret_cast<const int16_t *>(e->du_host.h + e->slots[(size_t)slot].dev.du_off);
+}
+
+/* the slot, or NULL with MIJ_E_ARG and `what` as the error */
+static const EncSlot *enc_slot(const mij_encoder *e, int slot, const char *what = "bad slot")
+{
+	if (!e || slot < 0 || slot >= (int)e->slots.size()) {
+		set_err(MIJ_E_ARG, "%s", what);
+		return nullptr;
+	}
+	return &e->slots[(size_t)slot];
+}
+static EncSlot *enc_slot(mij_encoder *e, int slot, const char *what = "bad slot")
+{
+	return const_cast<EncSlot *>(enc_slot(static_cast<const mij_encoder *>(e), slot, what));
 }
 
 extern "C" int mij_enc_add_clone(mij_encoder *e, int src_slot)
 {
-	if (!e || src_slot < 0 || src_slot >= (int)e->slots.size())
-		return set_err(MIJ_E_ARG, "bad source slot");
-	const int root = e->slots[(size_t)src_slot].clone_of >= 0 ? e->slots[(size_t)src_slot].clone_of : src_slot;
-	if (!enc_has_pixels(e->slots[(size_t)root].kind))
+	const EncSlot *src = enc_slot(e, src_slot, "bad source slot");
+	if (!src)
+		return MIJ_E_ARG;
+	const int root = src->clone_of >= 0 ? src->clone_of : src_slot;
+	const EncSlot &r = e->slots[(size_t)root];
+	if (!enc_has_pixels(r.kind))
 		return set_err(MIJ_E_ARG, "slot %d holds given data units or coefficient planes, which have no pixels to clone", src_slot);
-	const bool sampled = e->slots[(size_t)root].sampled;
-	const mjw_tplan plan = sampled ? e->slots[(size_t)root].tp : enc_tplan_of(e->slots[(size_t)root].plan);
-	const int slot = enc_add_common(e, plan, nullptr, e->slots[(size_t)root].flip, root, ENC_HOST, sampled, e->slots[(size_t)root].planes);
+	const bool optimize = src->optimize, progressive = src->progressive; /* src and r do not outlive the push */
+	const int restart = src->restart;
+	const int slot = enc_add_common(e, mjw_tplan(r.tp), nullptr, r.flip, root, ENC_HOST, r.sampled, r.planes);
 	if (slot >= 0) {
-		e->slots[(size_t)slot].optimize = e->slots[(size_t)src_slot].optimize;
-		e->slots[(size_t)slot].restart = e->slots[(size_t)src_slot].restart;
-		e->slots[(size_t)slot].progressive = e->slots[(size_t)src_slot].progressive;
+		e->slots[(size_t)slot].optimize = optimize;
+		e->slots[(size_t)slot].restart = restart;
+		e->slots[(size_t)slot].progressive = progressive;
 	}
 	return slot;
 }
 
 extern "C" int mij_enc_set_optimize(mij_encoder *e, int slot, int on)
 {
-	if (!e || slot < 0 || slot >= (int)e->slots.size())
-		return set_err(MIJ_E_ARG, "bad slot");
+	EncSlot *s = enc_slot(e, slot);
+	if (!s)
+		return MIJ_E_ARG;
 	if (e->uploaded)
 		return set_err(MIJ_E_STATE, "mij_enc_set_optimize after mij_enc_upload");
-	if (on && mjw_plan_du_count(&e->slots[(size_t)slot].plan) > (size_t)(UINT32_MAX / 64))
-		return set_err(MIJ_E_ARG, "slot %d: the symbol counts of %zu data units do not fit 32 bits", slot, mjw_plan_du_count(&e->slots[(size_t)slot].plan));
-	e->slots[(size_t)slot].optimize = on != 0;
+	if (on && mjw_plan_du_count(&s->tp.plan) > (size_t)(UINT32_MAX / 64))
+		return set_err(MIJ_E_ARG, "slot %d: the symbol counts of %zu data units do not fit 32 bits", slot, mjw_plan_du_count(&s->tp.plan));
+	s->optimize = on != 0;
 	return MIJ_OK;
 }
 
 extern "C" int mij_enc_set_restart(mij_encoder *e, int slot, int restart_mcus)
 {
-	if (!e || slot < 0 || slot >= (int)e->slots.size())
-		return set_err(MIJ_E_ARG, "bad slot");
+	EncSlot *s = enc_slot(e, slot);
+	if (!s)
+		return MIJ_E_ARG;
 	if (e->uploaded)
 		return set_err(MIJ_E_STATE, "mij_enc_set_restart after mij_enc_upload");
 	if (restart_mcus < 0 || restart_mcus > 65535)
 		return set_err(MIJ_E_ARG, "slot %d: a restart interval of %d MCUs is outside 0..65535", slot, restart_mcus);
-	EncSlot &s = e->slots[(size_t)slot];
-	if (restart_mcus && s.progressive)
+	if (restart_mcus && s->progressive)
 		return set_err(MIJ_E_ARG, "slot %d is progressive: restart intervals are not combined with progressive output", slot);
 	/* given units were judged unbroken when they were added: with an interval the DC differences are other ones */
 	const char *why = nullptr;
-	if (s.kind == ENC_UNITS && restart_mcus && !mjw_units_codable_restart(&s.plan, s.units.data(), restart_mcus, &why))
+	if (s->kind == ENC_UNITS && restart_mcus && !mjw_units_codable_restart(&s->tp.plan, s->units.data(), restart_mcus, &why))
 		return set_err(MIJ_E_ARG, "slot %d at a restart interval of %d MCUs: %s", slot, restart_mcus, why ? why : "not codable");
-	s.restart = restart_mcus;
+	s->restart = restart_mcus;
 	return MIJ_OK;
 }
 
 extern "C" int mij_enc_set_progressive(mij_encoder *e, int slot, int on)
 {
-	if (!e || slot < 0 || slot >= (int)e->slots.size())
-		return set_err(MIJ_E_ARG, "bad slot");
+	EncSlot *s = enc_slot(e, slot);
+	if (!s)
+		return MIJ_E_ARG;
 	if (e->uploaded)
 		return set_err(MIJ_E_STATE, "mij_enc_set_progressive after mij_enc_upload");
-	EncSlot &s = e->slots[(size_t)slot];
-	if (on && s.restart)
+	if (on && s->restart)
 		return set_err(MIJ_E_ARG, "slot %d has a restart interval: restart intervals are not combined with progressive output", slot);
-	if (on && mjw_plan_du_count(&s.plan) > (size_t)(UINT32_MAX / 64))
-		return set_err(MIJ_E_ARG, "slot %d: the symbol counts of %zu data units do not fit 32 bits", slot, mjw_plan_du_count(&s.plan));
-	s.progressive = on != 0;
+	if (on && mjw_plan_du_count(&s->tp.plan) > (size_t)(UINT32_MAX / 64))
+		return set_err(MIJ_E_ARG, "slot %d: the symbol counts of %zu data units do not fit 32 bits", slot, mjw_plan_du_count(&s->tp.plan));
+	s->progressive = on != 0;
 	return MIJ_OK;
 }
 
 extern "C" int mij_enc_slot_progressive(const mij_encoder *e, int slot)
 {
-	if (!e || slot < 0 || slot >= (int)e->slots.size())
-		return set_err(MIJ_E_ARG, "bad slot");
-	return e->slots[(size_t)slot].progressive ? 1 : 0;
+	const EncSlot *s = enc_slot(e, slot);
+	return s ? (s->progressive ? 1 : 0) : MIJ_E_ARG;
 }
 
 extern "C" int mij_enc_slot_restart(const mij_encoder *e, int slot)
 {
-	if (!e || slot < 0 || slot >= (int)e->slots.size())
-		return set_err(MIJ_E_ARG, "bad slot");
-	return e->slots[(size_t)slot].restart;
+	const EncSlot *s = enc_slot(e, slot);
+	return s ? s->restart : MIJ_E_ARG;
 }
 
 extern "C" int mij_enc_slot_optimized(const mij_encoder *e, int slot)
 {
-	if (!e || slot < 0 || slot >= (int)e->slots.size())
-		return set_err(MIJ_E_ARG, "bad slot");
+	if (!enc_slot(e, slot))
+		return MIJ_E_ARG;
 	if (!e->streams_fetched)
 		return set_err(MIJ_E_STATE, "mij_enc_slot_optimized before mij_enc_fetch_streams");
 	const int k = e->opt_of[(size_t)slot];
 	return k >= 0 && e->opt_ok[(size_t)k] ? 1 : 0;
 }
 
-/* The gather kernel of the device-pixel slots (their padded packed-RGB rows from the caller's tensor), queued at upload in place of
- * the host-to-device copy.  Nothing is queued when there are none. */
-static int enc_gather(mij_encoder *e)
+/* One gather pass, queued at upload in place of a host-to-device copy.  The device slots that takes(slot, k) names get a record each in
+ * `list` (fill) and their work items in `work` (items(slot, push) calls push(component, first row) for each, in order), class k = 0 ..
+ * CLASSES - 1 after class; launch(k, work, grid) then runs once per class that has work.  Nothing is queued when there are no such slots. */
+template <int CLASSES, typename G, typename Takes, typename Items, typename Fill, typename Launch>
+static int enc_gather_pass(mij_encoder *e, EncBuf<G> &list, EncBuf<WorkIdct> &work, Takes takes, Items items, Fill fill, Launch launch)
 {
+	const auto gathered = [&](const EncSlot &s, int k) { return s.clone_of < 0 && s.kind == ENC_DEVICE && takes(s, k); };
 	size_t ng = 0, nw = 0;
-	for (const EncSlot &s : e->slots)
-		if (s.clone_of < 0 && s.kind == ENC_DEVICE && s.cv.dtype == MIJ_DT_U8 && !s.planes) {
-			++ng;
-			nw += ((size_t)s.plan.height + MIJ_GATHER_ROWS - 1) / MIJ_GATHER_ROWS;
-		}
-	e->n_gwork = nw;
-	if (!ng)
-		return MIJ_OK;
-	if (ng > e->gath_cap || nw > e->gwork_cap)
-		HIP_TRY(hipStreamSynchronize(e->stream)); /* an earlier upload's copies may still read the pinned lists */
-	int rc = grow_pair(e->h_gath, e->d_gath, e->gath_cap, ng);
-	if (rc == MIJ_OK)
-		rc = grow_pair(e->h_gwork, e->d_gwork, e->gwork_cap, nw);
-	if (rc != MIJ_OK)
-		return rc;
-	uint32_t g = 0;
-	size_t w = 0;
-	for (const EncSlot &s : e->slots) {
-		if (s.clone_of >= 0 || s.kind != ENC_DEVICE || s.cv.dtype != MIJ_DT_U8 || s.planes)
-			continue;
-		EncGather &G = e->h_gath[g];
-		G.src = static_cast<const uint8_t *>(s.in.src);
-		G.row_pitch = s.in.row_pitch;
-		G.plane_pitch = s.in.plane_pitch;
-		G.layout = s.in.layout;
-		G.width = s.plan.width;
-		G.height = s.plan.height;
-		G.comp = s.plan.comp;
-		G.pad_w = s.pad_w;
-		G.pad = 0;
-		G.pix_off = s.dev.pix_off;
-		for (uint32_t y = 0; y < (uint32_t)s.plan.height; y += MIJ_GATHER_ROWS) {
-			const WorkIdct wk = {g, 0u, y, 0u};
-			e->h_gwork[w++] = wk;
-		}
-		++g;
-	}
-	HIP_TRY(hipMemcpyAsync(e->d_gath, e->h_gath, sizeof(EncGather) * ng, hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipMemcpyAsync(e->d_gwork, e->h_gwork, sizeof(WorkIdct) * nw, hipMemcpyHostToDevice, e->stream));
-	hipLaunchKernelGGL(k_enc_gather, dim3((unsigned)nw), dim3(256), 0, e->stream, e->d_gath, e->d_gwork, e->d_pix);
-	HIP_TRY(hipGetLastError());
-	return MIJ_OK;
-}
-
-/* The float device-pixel slots (mij_enc_add_device_float): their gather lists, grouped by dtype, and one launch of k_enc_gather_float
- * per dtype that has slots.  Nothing is queued when there are none. */
-static int enc_gather_float(mij_encoder *e)
-{
-	size_t ng = 0, nw = 0;
-	for (const EncSlot &s : e->slots)
-		if (s.clone_of < 0 && s.kind == ENC_DEVICE && s.cv.dtype != MIJ_DT_U8 && !s.planes) {
-			++ng;
-			nw += ((size_t)s.plan.height + MIJ_GATHER_ROWS - 1) / MIJ_GATHER_ROWS;
-		}
-	if (!ng)
-		return MIJ_OK;
-	if (ng > e->fgath_cap || nw > e->fgwork_cap)
-		HIP_TRY(hipStreamSynchronize(e->stream)); /* an earlier upload's copies may still read the pinned lists */
-	int rc = grow_pair(e->h_fgath, e->d_fgath, e->fgath_cap, ng);
-	if (rc == MIJ_OK)
-		rc = grow_pair(e->h_fgwork, e->d_fgwork, e->fgwork_cap, nw);
-	if (rc != MIJ_OK)
-		return rc;
-	static const int32_t dts[3] = {MIJ_DT_F16, MIJ_DT_BF16, MIJ_DT_F32};
-	size_t first[4] = {0, 0, 0, 0};
-	uint32_t g = 0;
-	size_t w = 0;
-	for (int k = 0; k < 3; ++k) {
-		for (const EncSlot &s : e->slots) {
-			if (s.clone_of >= 0 || s.kind != ENC_DEVICE || s.cv.dtype != dts[k] || s.planes)
-				continue;
-			EncGatherF &G = e->h_fgath[g];
-			G.g.src = static_cast<const uint8_t *>(s.in.src);
-			G.g.row_pitch = s.in.row_pitch;
-			G.g.plane_pitch = s.in.plane_pitch;
-			G.g.layout = s.in.layout;
-			G.g.width = s.plan.width;
-			G.g.height = s.plan.height;
-			G.g.comp = s.plan.comp;
-			G.g.pad_w = s.pad_w;
-			G.g.pad = 0;
-			G.g.pix_off = s.dev.pix_off;
-			memcpy(G.scale, s.cv.scale, sizeof(G.scale));
-			memcpy(G.bias, s.cv.bias, sizeof(G.bias));
-			for (uint32_t y = 0; y < (uint32_t)s.plan.height; y += MIJ_GATHER_ROWS) {
-				const WorkIdct wk = {g, 0u, y, 0u};
-				e->h_fgwork[w++] = wk;
+	for (int k = 0; k < CLASSES; ++k)
+		for (const EncSlot &s : e->slots)
+			if (gathered(s, k)) {
+				++ng;
+				items(s, [&](uint32_t, uint32_t) { ++nw; });
 			}
+	if (!ng)
+		return MIJ_OK;
+	EncGrow grow(e->stream);
+	grow(list, ng);
+	grow(work, nw);
+	if (grow.rc != MIJ_OK)
+		return grow.rc;
+	size_t first[CLASSES + 1] = {0};
+	uint32_t g = 0;
+	size_t w = 0;
+	for (int k = 0; k < CLASSES; ++k) {
+		for (const EncSlot &s : e->slots) {
+			if (!gathered(s, k))
+				continue;
+			fill(list.h[g], s);
+			items(s, [&](uint32_t c, uint32_t y) { work.h[w++] = WorkIdct{g, c, y, 0u}; });
 			++g;
 		}
 		first[k + 1] = w;
 	}
-	HIP_TRY(hipMemcpyAsync(e->d_fgath, e->h_fgath, sizeof(EncGatherF) * ng, hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipMemcpyAsync(e->d_fgwork, e->h_fgwork, sizeof(WorkIdct) * nw, hipMemcpyHostToDevice, e->stream));
-	for (int k = 0; k < 3; ++k) {
-		const size_t n = first[k + 1] - first[k];
-		if (!n)
+	HIP_TRY(hipMemcpyAsync(list.d, list.h, sizeof(G) * ng, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(work.d, work.h, sizeof(WorkIdct) * nw, hipMemcpyHostToDevice, e->stream));
+	for (int k = 0; k < CLASSES; ++k) {
+		if (first[k + 1] == first[k])
 			continue;
-		const dim3 grid((unsigned)n), block(256);
-		const WorkIdct *wk = e->d_fgwork + first[k];
-		if (dts[k] == MIJ_DT_F16)
-			hipLaunchKernelGGL(k_enc_gather_float<GatherF16>, grid, block, 0, e->stream, e->d_fgath, wk, e->d_pix);
-		else if (dts[k] == MIJ_DT_BF16)
-			hipLaunchKernelGGL(k_enc_gather_float<GatherBF16>, grid, block, 0, e->stream, e->d_fgath, wk, e->d_pix);
-		else
-			hipLaunchKernelGGL(k_enc_gather_float<GatherF32>, grid, block, 0, e->stream, e->d_fgath, wk, e->d_pix);
+		launch(k, work.d + first[k], dim3((unsigned)(first[k + 1] - first[k])));
 		HIP_TRY(hipGetLastError());
 	}
 	return MIJ_OK;
 }
 
-/* The device plane slots (mij_enc_add_device_planes): their gather list and one launch of k_enc_gather_planes.  Nothing is queued when
- * there are none. */
+/* a device tensor's record and its work items: the padded packed-RGB rows, MIJ_GATHER_ROWS at a time */
+static void enc_gather_fill(EncGather &G, const EncSlot &s)
+{
+	G.src = static_cast<const uint8_t *>(s.in.src);
+	G.row_pitch = s.in.row_pitch;
+	G.plane_pitch = s.in.plane_pitch;
+	G.layout = s.in.layout;
+	G.width = s.tp.plan.width;
+	G.height = s.tp.plan.height;
+	G.comp = s.tp.plan.comp;
+	G.pad_w = s.pad_w;
+	G.pad = 0;
+	G.pix_off = s.dev.pix_off;
+}
+template <typename Push>
+static void enc_gather_rows(const EncSlot &s, Push push)
+{
+	for (uint32_t y = 0; y < (uint32_t)s.tp.plan.height; y += MIJ_GATHER_ROWS)
+		push(0u, y);
+}
+
+/* the uint8 device-pixel slots (mij_enc_add_device): k_enc_gather */
+static int enc_gather(mij_encoder *e)
+{
+	return enc_gather_pass<1>(
+		e, e->gath, e->gwork, [](const EncSlot &s, int) { return s.cv.dtype == MIJ_DT_U8 && !s.planes; },
+		[](const EncSlot &s, auto push) { enc_gather_rows(s, push); }, enc_gather_fill,
+		[e](int, const WorkIdct *wk, dim3 grid) { hipLaunchKernelGGL(k_enc_gather, grid, dim3(256), 0, e->stream, e->gath.d, wk, e->pix.d); });
+}
+
+/* the float ones (mij_enc_add_device_float), grouped by dtype: one launch of k_enc_gather_float per dtype that has slots */
+static int enc_gather_float(mij_encoder *e)
+{
+	static const int32_t dts[3] = {MIJ_DT_F16, MIJ_DT_BF16, MIJ_DT_F32};
+	return enc_gather_pass<3>(
+		e, e->fgath, e->fgwork, [](const EncSlot &s, int k) { return s.cv.dtype == dts[k] && !s.planes; },
+		[](const EncSlot &s, auto push) { enc_gather_rows(s, push); },
+		[](EncGatherF &G, const EncSlot &s) {
+			enc_gather_fill(G.g, s);
+			memcpy(G.scale, s.cv.scale, sizeof(G.scale));
+			memcpy(G.bias, s.cv.bias, sizeof(G.bias));
+		},
+		[e](int k, const WorkIdct *wk, dim3 grid) {
+			const auto kernel = dts[k] == MIJ_DT_F16 ? k_enc_gather_float<GatherF16> : dts[k] == MIJ_DT_BF16 ? k_enc_gather_float<GatherBF16> : k_enc_gather_float<GatherF32>;
+			hipLaunchKernelGGL(kernel, grid, dim3(256), 0, e->stream, e->fgath.d, wk, e->pix.d);
+		});
+}
+
+/* the device plane slots (mij_enc_add_device_planes): k_enc_gather_planes, rows of MIJ_PGATHER_ROWS of each padded plane */
 static void enc_plane_geometry(const mjw_tplan &t, int c, int32_t *w, int32_t *h, int32_t *pad_w, int32_t *pad_h)
 {
 	const int lh = c ? 1 : t.lh, lv = c ? 1 : t.lv;
@@ -3979,52 +3898,33 @@ static void enc_plane_geometry(const mjw_tplan &t, int c, int32_t *w, int32_t *h
 
 static int enc_gather_planes(mij_encoder *e)
 {
-	size_t ng = 0, nw = 0;
-	for (const EncSlot &s : e->slots)
-		if (s.clone_of < 0 && s.kind == ENC_DEVICE && s.planes) {
-			++ng;
-			nw += (size_t)s.plan.mcu_y * (size_t)(s.tp.ncomp == 1 ? 1 : s.tp.lv + 2) * (8 / MIJ_PGATHER_ROWS);
-		}
-	if (!ng)
-		return MIJ_OK;
-	if (ng > e->pgath_cap || nw > e->pgwork_cap)
-		HIP_TRY(hipStreamSynchronize(e->stream)); /* an earlier upload's copies may still read the pinned lists */
-	int rc = grow_pair(e->h_pgath, e->d_pgath, e->pgath_cap, ng);
-	if (rc == MIJ_OK)
-		rc = grow_pair(e->h_pgwork, e->d_pgwork, e->pgwork_cap, nw);
-	if (rc != MIJ_OK)
-		return rc;
-	uint32_t g = 0;
-	size_t w = 0;
-	for (const EncSlot &s : e->slots) {
-		if (s.clone_of >= 0 || s.kind != ENC_DEVICE || !s.planes)
-			continue;
-		EncGatherP &G = e->h_pgath[g];
-		memset(&G, 0, sizeof(G));
-		uint64_t off = s.dev.pix_off;
-		for (int c = 0; c < s.tp.ncomp; ++c) {
-			G.src[c] = static_cast<const uint8_t *>(s.pl[c].src);
-			G.row_pitch[c] = s.pl[c].row_pitch;
-			G.x_pitch[c] = s.pl[c].x_pitch;
-			enc_plane_geometry(s.tp, c, &G.w[c], &G.h[c], &G.pad_w[c], &G.pad_h[c]);
-			G.dst_off[c] = off;
-			off += (uint64_t)G.pad_w[c] * (uint64_t)G.pad_h[c];
-			G.scale[c] = s.cv.scale[c];
-			G.bias[c] = s.cv.bias[c];
-			for (uint32_t y = 0; y < (uint32_t)G.pad_h[c]; y += MIJ_PGATHER_ROWS) {
-				const WorkIdct wk = {g, (uint32_t)c, y, 0u};
-				e->h_pgwork[w++] = wk;
+	return enc_gather_pass<1>(
+		e, e->pgath, e->pgwork, [](const EncSlot &s, int) { return s.planes; },
+		[](const EncSlot &s, auto push) {
+			for (int c = 0; c < s.tp.ncomp; ++c) {
+				int32_t w, h, pad_w, pad_h;
+				enc_plane_geometry(s.tp, c, &w, &h, &pad_w, &pad_h);
+				for (uint32_t y = 0; y < (uint32_t)pad_h; y += MIJ_PGATHER_ROWS)
+					push((uint32_t)c, y);
 			}
-		}
-		G.flip = s.flip;
-		G.convert = s.pl_convert ? 1 : 0;
-		++g;
-	}
-	HIP_TRY(hipMemcpyAsync(e->d_pgath, e->h_pgath, sizeof(EncGatherP) * ng, hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipMemcpyAsync(e->d_pgwork, e->h_pgwork, sizeof(WorkIdct) * w, hipMemcpyHostToDevice, e->stream));
-	hipLaunchKernelGGL(k_enc_gather_planes, dim3((unsigned)w), dim3(256), 0, e->stream, e->d_pgath, e->d_pgwork, e->d_pix);
-	HIP_TRY(hipGetLastError());
-	return MIJ_OK;
+		},
+		[](EncGatherP &G, const EncSlot &s) {
+			memset(&G, 0, sizeof(G));
+			uint64_t off = s.dev.pix_off;
+			for (int c = 0; c < s.tp.ncomp; ++c) {
+				G.src[c] = static_cast<const uint8_t *>(s.pl[c].src);
+				G.row_pitch[c] = s.pl[c].row_pitch;
+				G.x_pitch[c] = s.pl[c].x_pitch;
+				enc_plane_geometry(s.tp, c, &G.w[c], &G.h[c], &G.pad_w[c], &G.pad_h[c]);
+				G.dst_off[c] = off;
+				off += (uint64_t)G.pad_w[c] * (uint64_t)G.pad_h[c];
+				G.scale[c] = s.cv.scale[c];
+				G.bias[c] = s.cv.bias[c];
+			}
+			G.flip = s.flip;
+			G.convert = s.pl_convert ? 1 : 0;
+		},
+		[e](int, const WorkIdct *wk, dim3 grid) { hipLaunchKernelGGL(k_enc_gather_planes, grid, dim3(256), 0, e->stream, e->pgath.d, wk, e->pix.d); });
 }
 
 /* a host plane slot's staging: the layout k_enc_gather_planes makes, by the same rules */
@@ -4106,7 +4006,7 @@ static int enc_add_planes(mij_encoder *e, const mij_in_planes *p, int quality, b
 			s.pl_convert = true;
 		}
 	} else {
-		enc_stage_planes(e->stage + s.stage_off, t, p->planes, cv, flip);
+		enc_stage_planes(e->stage.h + s.stage_off, t, p->planes, cv, flip);
 	}
 	return slot;
 }
@@ -4121,15 +4021,8 @@ static bool enc_own_header(const mij_encoder *e, const EncSlot &s)
 			 e->slots[(size_t)s.clone_of].progressive;
 }
 
-/* A progressive slot's geometry as its scans see it (include/mij_host.h, PROGRESSIVE STREAMS): the transcode plan of a coefficient slot, the
- * writer's 4:2:0 / 4:4:4 plan of any other */
-static mjw_tplan enc_prog_tplan(const EncSlot &s)
-{
-	if (s.kind == ENC_COEF || s.sampled)
-		return s.tp;
-	return enc_tplan_of(s.plan);
-}
-/* the units (a DC scan) or blocks (an AC scan: the component's own grid, without MCU padding) scan `sc` visits, and the grid's columns */
+/* A progressive slot's geometry as its scans see it (include/mij_host.h, PROGRESSIVE STREAMS):
+ * the units (a DC scan) or blocks (an AC scan: the component's own grid, without MCU padding) scan `sc` visits, and the grid's columns */
 static size_t enc_prog_scan_blocks(const mjw_tplan &t, const ProgScanDef &sc, uint32_t *bw)
 {
 	const bool own_grid = sc.comp == 0 && t.ncomp == 3; /* luma of a colour picture; chroma and grey have the MCU grid */
@@ -4139,7 +4032,7 @@ static size_t enc_prog_scan_blocks(const mjw_tplan &t, const ProgScanDef &sc, ui
 }
 static size_t enc_prog_tile_count(const EncSlot &s, size_t *flag_bytes)
 {
-	const mjw_tplan t = enc_prog_tplan(s);
+	const mjw_tplan &t = s.tp;
 	const int grey = t.ncomp == 1, nscan = grey ? MJW_PROGRESSIVE_SCANS_GREY : MJW_PROGRESSIVE_SCANS_COLOUR;
 	size_t tiles = 0, fb = 0;
 	for (int k = 0; k < nscan; ++k) {
@@ -4174,7 +4067,7 @@ static size_t enc_slot_tile_count(const EncSlot &s)
 {
 	if (s.progressive)
 		return enc_prog_tile_count(s, nullptr);
-	const size_t nu = mjw_plan_du_count(&s.plan), iu = s.restart ? (size_t)s.restart * (size_t)s.plan.du_per_mcu : nu;
+	const size_t nu = mjw_plan_du_count(&s.tp.plan), iu = s.restart ? (size_t)s.restart * (size_t)s.tp.plan.du_per_mcu : nu;
 	if (!s.restart || iu >= nu)
 		return (nu + MIJ_EMIT_TILE - 1) / MIJ_EMIT_TILE;
 	return nu / iu * ((iu + MIJ_EMIT_TILE - 1) / MIJ_EMIT_TILE) + (nu % iu + MIJ_EMIT_TILE - 1) / MIJ_EMIT_TILE;
@@ -4201,78 +4094,43 @@ static int enc_emit_lists(mij_encoder *e)
 		no += s.optimize;
 		not_ += s.optimize ? tiles : 0;
 	}
-	const size_t ntab = no + 1 + np * MIJ_PROG_SCANS;
+	const size_t ntab = no + 1 + np * MIJ_PROG_SCANS, nq = np * MIJ_PROG_SCANS;
 	if (nt > UINT32_MAX)
 		return set_err(MIJ_E_ARG, "too many data units to emit in one launch");
-	if (n > e->eslot_cap || nt > e->etile_cap || nh * MIJ_EMIT_HDR > e->hdr_cap || n + 1 > e->res_cap || nt > e->tmeta_cap || n > e->sent_cap ||
-		 not_ > e->otile_cap || no > e->optslot_cap || no * 1024 > e->freq_cap || no > e->optok_cap || ntab > e->tabs_cap || np > e->pslot_cap ||
-		 npt > e->ptile_cap || nfl + 1 > e->pfl_cap ||
-		 (np && (nt > e->tsum_cap || nt > e->ctail_cap || n > e->pflag_cap || np * MIJ_PROG_SCANS * 1024 > e->pfreq_cap || np * MIJ_PROG_SCANS * MIJ_PROG_HDR > e->phdr_cap)))
-		HIP_TRY(hipStreamSynchronize(e->stream)); /* the buffers may still be in use by an earlier launch */
-	int rc = grow_pair(e->h_eslot, e->d_eslot, e->eslot_cap, n);
-	if (rc == MIJ_OK && no) {
-		rc = grow_pair(e->h_otile, e->d_otile, e->otile_cap, not_);
-		if (rc == MIJ_OK)
-			rc = grow_pair(e->h_optslot, e->d_optslot, e->optslot_cap, no);
-		if (rc == MIJ_OK)
-			rc = grow_dev(e->d_freq, e->freq_cap, no * 1024);
-		if (rc == MIJ_OK)
-			rc = grow_dev(e->d_optok, e->optok_cap, no);
+	EncEmit &m = e->em;
+	EncGrow grow(e->stream); /* the buffers may still be in use by an earlier launch */
+	grow(m.eslot, n);
+	if (no) {
+		grow(m.otile, not_);
+		grow(m.optslot, no);
+		grow(m.freq, no * 1024);
+		grow(m.optok, no);
 	}
-	if (rc == MIJ_OK && ntab > e->tabs_cap) {
-		rc = grow_dev(e->d_tabs, e->tabs_cap, ntab);
-		if (rc == MIJ_OK)
-			HIP_TRY(hipMemcpy(e->d_tabs, &e->h_tabs0, sizeof(EmitTables), hipMemcpyHostToDevice));
+	if (grow(m.tabs, ntab)) /* entry 0 again */
+		HIP_TRY(hipMemcpy(m.tabs.d, &m.h_tabs0, sizeof(EmitTables), hipMemcpyHostToDevice));
+	if (np) {
+		grow(m.pslot, np);
+		grow(m.ptile, npt);
+		grow(m.pfl, nfl + 1);
+		grow(m.phdr, nq * MIJ_PROG_HDR);
+		grow(m.tsum, nt);
+		grow(m.tafter, nt);
+		grow(m.pfreq, nq * 1024);
+		grow(m.phlen, nq);
+		grow(m.pflag, n);
+		grow(m.ctail, nt);
 	}
-	if (rc == MIJ_OK && np) {
-		rc = grow_pair(e->h_pslot, e->d_pslot, e->pslot_cap, np);
-		if (rc == MIJ_OK)
-			rc = grow_pair(e->h_ptile, e->d_ptile, e->ptile_cap, npt);
-		if (rc == MIJ_OK)
-			rc = grow_dev(e->d_pfl, e->pfl_cap, nfl + 1);
-		if (rc == MIJ_OK)
-			rc = grow_dev(e->d_phdr, e->phdr_cap, np * MIJ_PROG_SCANS * MIJ_PROG_HDR);
-		if (rc == MIJ_OK)
-			rc = grow_dev(e->d_tsum, e->tsum_cap, nt);
-		if (rc == MIJ_OK)
-			rc = grow_dev(e->d_tafter, e->tafter_cap, nt);
-		if (rc == MIJ_OK)
-			rc = grow_dev(e->d_pfreq, e->pfreq_cap, np * MIJ_PROG_SCANS * 1024);
-		if (rc == MIJ_OK)
-			rc = grow_dev(e->d_phlen, e->phlen_cap, np * MIJ_PROG_SCANS);
-		if (rc == MIJ_OK)
-			rc = grow_dev(e->d_pflag, e->pflag_cap, n);
-		if (rc == MIJ_OK)
-			rc = grow_dev(e->d_ctail, e->ctail_cap, nt);
-	}
-	if (rc == MIJ_OK)
-		rc = grow_pair(e->h_etile, e->d_etile, e->etile_cap, nt);
-	if (rc == MIJ_OK)
-		rc = grow_pair(e->h_hdr, e->d_hdr, e->hdr_cap, nh * MIJ_EMIT_HDR);
-	if (rc == MIJ_OK)
-		rc = grow_pair(e->h_res, e->d_res, e->res_cap, n + 1);
-	if (rc == MIJ_OK && nt > e->tmeta_cap) {
-		size_t c = e->tmeta_cap;
-		rc = grow_dev(e->d_tbits, c, nt);
-		c = e->tmeta_cap;
-		if (rc == MIJ_OK)
-			rc = grow_dev(e->d_tff, c, nt);
-		c = e->tmeta_cap;
-		if (rc == MIJ_OK)
-			rc = grow_dev(e->d_tfrag, c, nt);
-		c = e->tmeta_cap;
-		if (rc == MIJ_OK)
-			rc = grow_dev(e->d_tboff, c, nt);
-		c = e->tmeta_cap;
-		if (rc == MIJ_OK)
-			rc = grow_dev(e->d_tout, c, nt);
-		if (rc == MIJ_OK)
-			e->tmeta_cap = c;
-	}
-	if (rc == MIJ_OK)
-		rc = grow_dev(e->d_sent, e->sent_cap, n);
-	if (rc != MIJ_OK)
-		return rc;
+	grow(m.etile, nt);
+	grow(m.hdr, nh * MIJ_EMIT_HDR);
+	grow(m.res, n + 1);
+	grow(m.tbits, nt);
+	grow(m.tff, nt);
+	grow(m.tfrag, nt);
+	grow(m.tboff, nt);
+	grow(m.tout, nt);
+	grow(m.sent, n);
+	if (grow.rc != MIJ_OK)
+		return grow.rc;
 	std::vector<uint32_t> hdr_of(n), hlen_of(n, (uint32_t)MJW_HEADER_BYTES);
 	uint32_t t = 0, h = 0, k = 0, ot = 0, pk = 0, pt = 0;
 	uint64_t fl_off = 0;
@@ -4280,33 +4138,31 @@ static int enc_emit_lists(mij_encoder *e)
 	for (size_t i = 0; i < n; ++i) {
 		const EncSlot &s = e->slots[i];
 		if (enc_own_header(e, s)) {
-			if (s.progressive) { /* SOI .. SOF2; k_prog_build appends the first scan's tables and SOS */
-				const mjw_tplan tp = enc_prog_tplan(s);
-				hlen_of[i] = (uint32_t)mjw_tframe_progressive(&tp, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
-			} else if (s.kind == ENC_COEF || s.sampled) /* shorter for a grey slot */
-				hlen_of[i] = (uint32_t)mjw_theader_restart(&s.tp, s.restart, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
-			else
-				hlen_of[i] = (uint32_t)mjw_header_restart(&s.plan, s.restart, e->h_hdr + (size_t)h * MIJ_EMIT_HDR);
+			uint8_t *hdr = m.hdr.h + (size_t)h * MIJ_EMIT_HDR;
+			if (s.progressive) /* SOI .. SOF2; k_prog_build appends the first scan's tables and SOS */
+				hlen_of[i] = (uint32_t)mjw_tframe_progressive(&s.tp, hdr);
+			else /* shorter for a grey slot; for the writer's own 4:2:0 and 4:4:4 what mjw_header_restart writes */
+				hlen_of[i] = (uint32_t)mjw_theader_restart(&s.tp, s.restart, hdr);
 			hdr_of[i] = h++;
 		} else {
 			hdr_of[i] = hdr_of[(size_t)s.clone_of];
 			hlen_of[i] = hlen_of[(size_t)s.clone_of];
 		}
-		EmitSlot &es = e->h_eslot[i];
+		EmitSlot &es = m.eslot.h[i];
 		es.du_off = s.dev.du_off;
-		es.n_du = (uint32_t)mjw_plan_du_count(&s.plan);
-		es.dpm = (uint32_t)s.plan.du_per_mcu;
+		es.n_du = (uint32_t)mjw_plan_du_count(&s.tp.plan);
+		es.dpm = (uint32_t)s.tp.plan.du_per_mcu;
 		es.first_tile = t;
 		es.n_tiles = (uint32_t)enc_slot_tile_count(s);
 		es.hdr = hdr_of[i];
 		es.ri = (uint32_t)s.restart;
 		es.prog = 0;
 		es.tab = 0;
-		es.ny = s.kind == ENC_COEF || s.sampled ? (s.tp.ncomp == 1 ? 1u : (uint32_t)(s.tp.lh * s.tp.lv)) : (s.plan.subsample ? 4u : 1u);
+		es.ny = s.tp.ncomp == 1 ? 1u : (uint32_t)(s.tp.lh * s.tp.lv);
 		es.hlen = hlen_of[i];
 		if (s.progressive) { /* its tiles name (scan, first block, count); a scan is a segment as a restart interval is */
-			const mjw_tplan tp = enc_prog_tplan(s);
-			ProgSlot &ps = e->h_pslot[pk];
+			const mjw_tplan &tp = s.tp;
+			ProgSlot &ps = m.pslot.h[pk];
 			memset(&ps, 0, sizeof(ps));
 			ps.slot = (uint32_t)i;
 			ps.grey = tp.ncomp == 1;
@@ -4327,8 +4183,8 @@ static int enc_emit_lists(mij_encoder *e)
 					const size_t cnt = std::min((size_t)MIJ_EMIT_TILE, nb - b);
 					const bool last = b + cnt == nb;
 					const EmitTile tl = {(uint32_t)i, (uint32_t)b, 0u, emit_tile_pad((uint32_t)cnt, b == 0, last, last && sc + 1 < ps.nscan, 0u) | sc << 16};
-					e->h_ptile[pt++] = t;
-					e->h_etile[t++] = tl;
+					m.ptile.h[pt++] = t;
+					m.etile.h[t++] = tl;
 				}
 			}
 			for (uint32_t sc = ps.nscan; sc <= MIJ_PROG_SCANS; ++sc)
@@ -4337,76 +4193,77 @@ static int enc_emit_lists(mij_encoder *e)
 		}
 		if (s.optimize) {
 			e->opt_of[i] = (int)k;
-			e->h_optslot[k] = (uint32_t)i;
+			m.optslot.h[k] = (uint32_t)i;
 			es.tab = ++k;
 		}
 		enc_slot_tiles(es.n_du, es.dpm, es.ri, [&](uint32_t u, uint32_t pad) {
 			const EmitTile tl = {(uint32_t)i, u, 0u, pad};
-			e->h_etile[t++] = tl;
+			m.etile.h[t++] = tl;
 			if (s.optimize)
-				e->h_otile[ot++] = tl;
+				m.otile.h[ot++] = tl;
 		});
 	}
-	e->n_etile = nt;
-	e->n_opt = no;
-	e->n_otile = not_;
-	e->n_prog = np;
-	e->n_ptile = npt;
+	m.n_etile = nt;
+	m.n_opt = no;
+	m.n_otile = not_;
+	m.n_prog = np;
+	m.n_ptile = npt;
 	if (np) {
-		HIP_TRY(hipMemcpyAsync(e->d_pslot, e->h_pslot, sizeof(ProgSlot) * np, hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipMemcpyAsync(e->d_ptile, e->h_ptile, sizeof(uint32_t) * npt, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(m.pslot.d, m.pslot.h, sizeof(ProgSlot) * np, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(m.ptile.d, m.ptile.h, sizeof(uint32_t) * npt, hipMemcpyHostToDevice, e->stream));
 	}
 	if (no) {
-		HIP_TRY(hipMemcpyAsync(e->d_otile, e->h_otile, sizeof(EmitTile) * not_, hipMemcpyHostToDevice, e->stream));
-		HIP_TRY(hipMemcpyAsync(e->d_optslot, e->h_optslot, sizeof(uint32_t) * no, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(m.otile.d, m.otile.h, sizeof(EmitTile) * not_, hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipMemcpyAsync(m.optslot.d, m.optslot.h, sizeof(uint32_t) * no, hipMemcpyHostToDevice, e->stream));
 	}
-	HIP_TRY(hipMemcpyAsync(e->d_eslot, e->h_eslot, sizeof(EmitSlot) * n, hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipMemcpyAsync(e->d_etile, e->h_etile, sizeof(EmitTile) * nt, hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipMemcpyAsync(e->d_hdr, e->h_hdr, (size_t)nh * MIJ_EMIT_HDR, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(m.eslot.d, m.eslot.h, sizeof(EmitSlot) * n, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(m.etile.d, m.etile.h, sizeof(EmitTile) * nt, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(m.hdr.d, m.hdr.h, (size_t)nh * MIJ_EMIT_HDR, hipMemcpyHostToDevice, e->stream));
 	return MIJ_OK;
 }
 
 /* The six emission launches behind the transform (mij_emit_kernels.h); with optimised slots, their counts and tables first. */
 static int enc_emit_launch(mij_encoder *e)
 {
+	const EncEmit &m = e->em;
 	const uint32_t n = (uint32_t)e->slots.size();
-	const dim3 tiles((unsigned)e->n_etile), per_slot((n + 3) / 4), block(256);
-	const uint8_t *du = reinterpret_cast<const uint8_t *>(e->d_du);
-	if (e->n_opt) {
-		HIP_TRY(hipMemsetAsync(e->d_freq, 0, sizeof(uint32_t) * 1024 * e->n_opt, e->stream));
-		hipLaunchKernelGGL(k_emit_hist, dim3((unsigned)e->n_otile), block, 0, e->stream, e->d_eslot, e->d_otile, du, e->d_freq);
-		hipLaunchKernelGGL(k_emit_build, dim3((unsigned)e->n_opt), block, 0, e->stream, e->d_eslot, e->d_etile, e->d_optslot, e->d_freq, e->d_tabs, e->d_hdr,
-								 e->d_optok);
+	const dim3 tiles((unsigned)m.n_etile), per_slot((n + 3) / 4), block(256);
+	const uint8_t *du = e->du.d;
+	if (m.n_opt) {
+		HIP_TRY(hipMemsetAsync(m.freq.d, 0, sizeof(uint32_t) * 1024 * m.n_opt, e->stream));
+		hipLaunchKernelGGL(k_emit_hist, dim3((unsigned)m.n_otile), block, 0, e->stream, m.eslot.d, m.otile.d, du, m.freq.d);
+		hipLaunchKernelGGL(k_emit_build, dim3((unsigned)m.n_opt), block, 0, e->stream, m.eslot.d, m.etile.d, m.optslot.d, m.freq.d, m.tabs.d, m.hdr.d,
+								 m.optok.d);
 	}
 	ProgArgs pa = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-	if (e->n_prog) { /* block flags, run lengths, per-scan counts, per-scan tables and headers: four launches whatever the slots and scans */
-		const size_t nq = e->n_prog * MIJ_PROG_SCANS;
-		HIP_TRY(hipMemsetAsync(e->d_pfreq, 0, sizeof(uint32_t) * 1024 * nq, e->stream));
-		HIP_TRY(hipMemsetAsync(e->d_phlen, 0, sizeof(uint32_t) * nq, e->stream));
-		HIP_TRY(hipMemsetAsync(e->d_pflag, 0, sizeof(uint32_t) * n, e->stream));
-		hipLaunchKernelGGL(k_prog_flags, dim3((unsigned)e->n_ptile), block, 0, e->stream, e->d_eslot, e->d_etile, e->d_ptile, e->d_pslot, du, e->d_pfl, e->d_tsum);
-		hipLaunchKernelGGL(k_prog_runs, dim3((unsigned)((e->n_prog + 3) / 4)), block, 0, e->stream, e->d_eslot, e->d_etile, e->d_pslot, (uint32_t)e->n_prog,
-								 e->d_tsum, e->d_tafter);
-		hipLaunchKernelGGL(k_prog_hist, dim3((unsigned)e->n_ptile), block, 0, e->stream, e->d_eslot, e->d_etile, e->d_ptile, e->d_pslot, du, e->d_pfl, e->d_tafter,
-								 e->d_pfreq, e->d_pflag);
-		hipLaunchKernelGGL(k_prog_build, dim3((unsigned)nq), block, 0, e->stream, e->d_eslot, e->d_etile, e->d_pslot, e->d_pfreq, e->d_tabs, e->d_hdr, e->d_phdr,
-								 e->d_phlen, e->d_pflag);
-		pa.slots = e->d_pslot;
-		pa.fl = e->d_pfl;
-		pa.after = e->d_tafter;
-		pa.hdr = e->d_phdr;
-		pa.hlen = e->d_phlen;
-		pa.ctail = e->d_ctail;
+	if (m.n_prog) { /* block flags, run lengths, per-scan counts, per-scan tables and headers: four launches whatever the slots and scans */
+		const size_t nq = m.n_prog * MIJ_PROG_SCANS;
+		HIP_TRY(hipMemsetAsync(m.pfreq.d, 0, sizeof(uint32_t) * 1024 * nq, e->stream));
+		HIP_TRY(hipMemsetAsync(m.phlen.d, 0, sizeof(uint32_t) * nq, e->stream));
+		HIP_TRY(hipMemsetAsync(m.pflag.d, 0, sizeof(uint32_t) * n, e->stream));
+		hipLaunchKernelGGL(k_prog_flags, dim3((unsigned)m.n_ptile), block, 0, e->stream, m.eslot.d, m.etile.d, m.ptile.d, m.pslot.d, du, m.pfl.d, m.tsum.d);
+		hipLaunchKernelGGL(k_prog_runs, dim3((unsigned)((m.n_prog + 3) / 4)), block, 0, e->stream, m.eslot.d, m.etile.d, m.pslot.d, (uint32_t)m.n_prog,
+								 m.tsum.d, m.tafter.d);
+		hipLaunchKernelGGL(k_prog_hist, dim3((unsigned)m.n_ptile), block, 0, e->stream, m.eslot.d, m.etile.d, m.ptile.d, m.pslot.d, du, m.pfl.d, m.tafter.d,
+								 m.pfreq.d, m.pflag.d);
+		hipLaunchKernelGGL(k_prog_build, dim3((unsigned)nq), block, 0, e->stream, m.eslot.d, m.etile.d, m.pslot.d, m.pfreq.d, m.tabs.d, m.hdr.d, m.phdr.d,
+								 m.phlen.d, m.pflag.d);
+		pa.slots = m.pslot.d;
+		pa.fl = m.pfl.d;
+		pa.after = m.tafter.d;
+		pa.hdr = m.phdr.d;
+		pa.hlen = m.phlen.d;
+		pa.ctail = m.ctail.d;
 	}
-	hipLaunchKernelGGL(k_emit_len, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_tbits, pa);
-	hipLaunchKernelGGL(k_emit_scan, per_slot, block, 0, e->stream, e->d_eslot, e->d_etile, n, e->d_tbits, e->d_tboff);
-	hipLaunchKernelGGL(k_emit_count, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_tbits, e->d_tboff, e->d_tff, e->d_tfrag,
-							 e->has_coef ? e->d_sflag : nullptr, e->n_prog ? e->d_pflag : nullptr, pa);
-	hipLaunchKernelGGL(k_emit_stuff, per_slot, block, 0, e->stream, e->d_eslot, e->d_etile, n, e->d_tbits, e->d_tboff, e->d_tff, e->d_tfrag, e->d_tout, e->d_sent,
+	hipLaunchKernelGGL(k_emit_len, tiles, block, 0, e->stream, m.eslot.d, m.etile.d, m.tabs.d, du, m.tbits.d, pa);
+	hipLaunchKernelGGL(k_emit_scan, per_slot, block, 0, e->stream, m.eslot.d, m.etile.d, n, m.tbits.d, m.tboff.d);
+	hipLaunchKernelGGL(k_emit_count, tiles, block, 0, e->stream, m.eslot.d, m.etile.d, m.tabs.d, du, m.tbits.d, m.tboff.d, m.tff.d, m.tfrag.d,
+							 e->has_coef ? e->sflag_dev.d : nullptr, m.n_prog ? m.pflag.d : nullptr, pa);
+	hipLaunchKernelGGL(k_emit_stuff, per_slot, block, 0, e->stream, m.eslot.d, m.etile.d, n, m.tbits.d, m.tboff.d, m.tff.d, m.tfrag.d, m.tout.d, m.sent.d,
 							 pa);
-	hipLaunchKernelGGL(k_emit_place, dim3(1), dim3(1024), 0, e->stream, e->d_eslot, n, e->d_sent, (uint64_t)e->arena_cap, e->d_res);
-	hipLaunchKernelGGL(k_emit_write, tiles, block, 0, e->stream, e->d_eslot, e->d_etile, e->d_tabs, du, e->d_hdr, e->d_tbits, e->d_tboff, e->d_tfrag,
-							 e->d_tout, e->d_res, e->d_arena, pa);
+	hipLaunchKernelGGL(k_emit_place, dim3(1), dim3(1024), 0, e->stream, m.eslot.d, n, m.sent.d, (uint64_t)m.arena.cap, m.res.d);
+	hipLaunchKernelGGL(k_emit_write, tiles, block, 0, e->stream, m.eslot.d, m.etile.d, m.tabs.d, du, m.hdr.d, m.tbits.d, m.tboff.d, m.tfrag.d,
+							 m.tout.d, m.res.d, m.arena.d, pa);
 	HIP_TRY(hipGetLastError());
 	e->emit_queued = true;
 	return MIJ_OK;
@@ -4425,22 +4282,18 @@ extern "C" int mij_enc_stream_reserve(mij_encoder *e, size_t bytes)
 	uint16_t code[4][256];
 	uint8_t len[4][256];
 	mjw_huff_tables(code, len);
-	EmitTables &tabs = e->h_tabs0;
+	EmitTables &tabs = e->em.h_tabs0;
 	memcpy(tabs.code, code, sizeof(code));
 	memcpy(tabs.len, len, sizeof(len));
-	hipError_t r = hipMalloc(reinterpret_cast<void **>(&e->d_arena), bytes);
+	hipError_t r = e->em.arena.alloc(bytes);
 	if (r == hipSuccess)
-		r = hipHostMalloc(reinterpret_cast<void **>(&e->h_arena), bytes, hipHostMallocDefault);
+		r = e->em.tabs.alloc(1);
 	if (r == hipSuccess)
-		r = hipMalloc(reinterpret_cast<void **>(&e->d_tabs), sizeof(EmitTables));
-	if (r == hipSuccess)
-		r = hipMemcpy(e->d_tabs, &tabs, sizeof(tabs), hipMemcpyHostToDevice);
+		r = hipMemcpy(e->em.tabs.d, &tabs, sizeof(tabs), hipMemcpyHostToDevice);
 	if (r != hipSuccess) {
 		enc_free_emit(e);
 		return set_err(r == hipErrorOutOfMemory ? MIJ_E_NOMEM : MIJ_E_HIP, "mij_enc_stream_reserve(%zu): %s", bytes, hipGetErrorString(r));
 	}
-	e->arena_cap = bytes;
-	e->tabs_cap = 1;
 	return MIJ_OK;
 }
 
@@ -4448,54 +4301,52 @@ extern "C" int mij_enc_fetch_streams(mij_encoder *e)
 {
 	if (!e)
 		return set_err(MIJ_E_ARG, "encoder is NULL");
-	if (!e->d_arena)
+	if (!e->em.arena.d)
 		return set_err(MIJ_E_STATE, "mij_enc_fetch_streams without an emission arena (mij_enc_stream_reserve)");
 	if (!e->launched || !e->emit_queued)
 		return set_err(MIJ_E_STATE, "mij_enc_fetch_streams before mij_enc_launch");
 	HIP_TRY(hipSetDevice(e->ctx->device));
 	const size_t n = e->slots.size();
-	HIP_TRY(hipMemcpyAsync(e->h_res, e->d_res, sizeof(EmitResult) * (n + 1), hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->em.res.h, e->em.res.d, sizeof(EmitResult) * (n + 1), hipMemcpyDeviceToHost, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
-	const size_t used = (size_t)e->h_res[n].off;
-	if (used > e->arena_cap)
-		return set_err(MIJ_E_HIP, "emission reported %zu bytes for a %zu-byte arena", used, e->arena_cap);
+	const size_t used = (size_t)e->em.res.h[n].off;
+	if (used > e->em.arena.cap)
+		return set_err(MIJ_E_HIP, "emission reported %zu bytes for a %zu-byte arena", used, e->em.arena.cap);
 	if (used) {
-		HIP_TRY(hipMemcpyAsync(e->h_arena, e->d_arena, used, hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->em.arena.h, e->em.arena.d, used, hipMemcpyDeviceToHost, e->stream));
 		HIP_TRY(hipStreamSynchronize(e->stream));
 	}
 	e->sflag.assign(n, 0u);
 	if (e->has_coef)
-		HIP_TRY(hipMemcpy(e->sflag.data(), e->d_sflag, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(e->sflag.data(), e->sflag_dev.d, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
 	e->pflag.assign(n, 0u);
-	if (e->n_prog)
-		HIP_TRY(hipMemcpy(e->pflag.data(), e->d_pflag, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-	e->opt_ok.assign(e->n_opt, 0u);
-	if (e->n_opt)
-		HIP_TRY(hipMemcpy(e->opt_ok.data(), e->d_optok, sizeof(uint32_t) * e->n_opt, hipMemcpyDeviceToHost));
+	if (e->em.n_prog)
+		HIP_TRY(hipMemcpy(e->pflag.data(), e->em.pflag.d, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+	e->opt_ok.assign(e->em.n_opt, 0u);
+	if (e->em.n_opt)
+		HIP_TRY(hipMemcpy(e->opt_ok.data(), e->em.optok.d, sizeof(uint32_t) * e->em.n_opt, hipMemcpyDeviceToHost));
 	e->streams_fetched = true;
-	return (int)e->h_res[n].len;
+	return (int)e->em.res.h[n].len;
 }
 
 extern "C" const unsigned char *mij_enc_stream(const mij_encoder *e, int slot, size_t *len)
 {
 	if (len)
 		*len = 0;
-	if (!e || slot < 0 || slot >= (int)e->slots.size()) {
-		set_err(MIJ_E_ARG, "bad slot");
+	if (!enc_slot(e, slot))
 		return nullptr;
-	}
 	if (!e->streams_fetched) {
 		set_err(MIJ_E_STATE, "mij_enc_stream before mij_enc_fetch_streams");
 		return nullptr;
 	}
-	const EmitResult &r = e->h_res[slot];
+	const EmitResult &r = e->em.res.h[slot];
 	if (len)
 		*len = (size_t)r.len;
 	if (r.off == ~0ull) {
 		set_err(MIJ_E_NOMEM, "slot %d did not fit in the emission arena (needs %llu bytes)", slot, (unsigned long long)r.len);
 		return nullptr;
 	}
-	return e->h_arena + r.off;
+	return e->em.arena.h + r.off;
 }
 
 /* mij_enc_add_device (cv NULL: uint8 elements) and mij_enc_add_device_float: the checks they share, extents in bytes of the element */
@@ -4566,11 +4417,11 @@ extern "C" int mij_enc_add_units(mij_encoder *e, int width, int height, int comp
 {
 	if (!e || !du)
 		return set_err(MIJ_E_ARG, "bad argument");
-	mjw_plan plan;
-	if (!mjw_plan_init(&plan, width, height, comp, quality))
+	mjw_tplan t;
+	if (!enc_opts_plan(&t, width, height, comp, quality, nullptr))
 		return set_err(MIJ_E_ARG, "bad image arguments (%dx%dx%d)", width, height, comp);
-	const size_t nu = mjw_plan_du_count(&plan);
-	const int dpm = plan.du_per_mcu;
+	const size_t nu = mjw_plan_du_count(&t.plan);
+	const int dpm = t.plan.du_per_mcu;
 	int pred[3] = {0, 0, 0};
 	for (size_t u = 0; u < nu; ++u) {
 		const int p = (int)(u % (size_t)dpm), c = dpm == 6 ? (p < 4 ? 0 : p - 3) : p;
@@ -4589,7 +4440,7 @@ extern "C" int mij_enc_add_units(mij_encoder *e, int width, int height, int comp
 	} catch (const std::bad_alloc &) {
 		return set_err(MIJ_E_NOMEM, "out of host memory");
 	}
-	const int slot = enc_add_common(e, enc_tplan_of(plan), nullptr, 0, -1, ENC_UNITS);
+	const int slot = enc_add_common(e, t, nullptr, 0, -1, ENC_UNITS);
 	if (slot >= 0)
 		e->slots[(size_t)slot].units.swap(units);
 	return slot;
@@ -4640,7 +4491,6 @@ extern "C" int mij_enc_add_coef_window(mij_encoder *e, mij_batch *b, int slot, i
 	if (es < 0)
 		return es;
 	EncSlot &s = e->slots[(size_t)es];
-	s.tp = tp;
 	s.src = b;
 	s.coef_fmt = bs.coef_bytes_fmt ? 1 : 0;
 	memcpy(s.rect, rect, sizeof(rect));
@@ -4700,26 +4550,36 @@ extern "C" int mij_enc_add_coef_requant(mij_encoder *e, mij_batch *b, int slot, 
 	return mij_enc_add_coef_window(e, b, slot, orientation, trim, nullptr, 0, luma, chroma, coarsen_only, nullptr);
 }
 
+/* the slot if it is a coefficient slot, or NULL with the error set */
+static const EncSlot *enc_coef_slot(const mij_encoder *e, int slot)
+{
+	const EncSlot *s = enc_slot(e, slot, "bad slot, or not a coefficient slot");
+	if (s && s->kind != ENC_COEF) {
+		set_err(MIJ_E_ARG, "bad slot, or not a coefficient slot");
+		return nullptr;
+	}
+	return s;
+}
+
 extern "C" int mij_enc_slot_rect(const mij_encoder *e, int slot, int rect[4])
 {
-	if (!e || slot < 0 || slot >= (int)e->slots.size() || !rect || e->slots[(size_t)slot].kind != ENC_COEF)
+	const EncSlot *s = rect ? enc_coef_slot(e, slot) : nullptr;
+	if (!s)
 		return set_err(MIJ_E_ARG, "bad slot, or not a coefficient slot");
-	memcpy(rect, e->slots[(size_t)slot].rect, sizeof(e->slots[(size_t)slot].rect));
+	memcpy(rect, s->rect, sizeof(s->rect));
 	return MIJ_OK;
 }
 
 extern "C" int mij_enc_slot_greyed(const mij_encoder *e, int slot)
 {
-	if (!e || slot < 0 || slot >= (int)e->slots.size() || e->slots[(size_t)slot].kind != ENC_COEF)
-		return set_err(MIJ_E_ARG, "bad slot, or not a coefficient slot");
-	return e->slots[(size_t)slot].greyed ? 1 : 0;
+	const EncSlot *s = enc_coef_slot(e, slot);
+	return s ? (s->greyed ? 1 : 0) : MIJ_E_ARG;
 }
 
 extern "C" int mij_enc_slot_windowed(const mij_encoder *e, int slot)
 {
-	if (!e || slot < 0 || slot >= (int)e->slots.size() || e->slots[(size_t)slot].kind != ENC_COEF)
-		return set_err(MIJ_E_ARG, "bad slot, or not a coefficient slot");
-	return e->slots[(size_t)slot].coef.win ? 1 : 0;
+	const EncSlot *s = enc_coef_slot(e, slot);
+	return s ? (s->coef.win ? 1 : 0) : MIJ_E_ARG;
 }
 
 extern "C" int mij_enc_coef_tiles(const mij_encoder *e, uint32_t *tiles)
@@ -4739,23 +4599,23 @@ extern "C" int mij_enc_add_coef(mij_encoder *e, mij_batch *b, int slot) { return
 
 extern "C" int mij_enc_tplan(const mij_encoder *e, int slot, mjw_tplan *out)
 {
-	if (!e || slot < 0 || slot >= (int)e->slots.size() || !out || (e->slots[(size_t)slot].kind != ENC_COEF && !e->slots[(size_t)slot].sampled))
+	const EncSlot *s = out ? enc_slot(e, slot, "bad slot, or not a coefficient slot") : nullptr;
+	if (!s || (s->kind != ENC_COEF && !s->sampled)) /* every slot has a plan; the slots of mij_enc_plan keep that accessor */
 		return set_err(MIJ_E_ARG, "bad slot, or not a coefficient slot");
-	*out = e->slots[(size_t)slot].tp;
+	*out = s->tp;
 	return MIJ_OK;
 }
 
 extern "C" int mij_enc_slot_requantized(const mij_encoder *e, int slot)
 {
-	if (!e || slot < 0 || slot >= (int)e->slots.size() || e->slots[(size_t)slot].kind != ENC_COEF)
-		return set_err(MIJ_E_ARG, "bad slot, or not a coefficient slot");
-	return e->slots[(size_t)slot].coef.rq ? 1 : 0;
+	const EncSlot *s = enc_coef_slot(e, slot);
+	return s ? (s->coef.rq ? 1 : 0) : MIJ_E_ARG;
 }
 
 extern "C" int mij_enc_slot_status(const mij_encoder *e, int slot)
 {
-	if (!e || slot < 0 || slot >= (int)e->slots.size())
-		return set_err(MIJ_E_ARG, "bad slot");
+	if (!enc_slot(e, slot))
+		return MIJ_E_ARG;
 	if (!e->streams_fetched)
 		return set_err(MIJ_E_STATE, "mij_enc_slot_status before mij_enc_fetch_streams");
 	if ((size_t)slot < e->sflag.size() && e->sflag[(size_t)slot]) {
@@ -4766,8 +4626,8 @@ extern "C" int mij_enc_slot_status(const mij_encoder *e, int slot)
 		set_err(MIJ_E_ARG, "slot %d: progressive with a forced EOB-run flush or a table that cannot be built: finish it on the host from its units", slot);
 		return MIJ_ENC_SLOT_HOST_FLUSH;
 	}
-	if (e->h_res[slot].off == ~0ull) {
-		set_err(MIJ_E_NOMEM, "slot %d did not fit in the emission arena (needs %llu bytes)", slot, (unsigned long long)e->h_res[slot].len);
+	if (e->em.res.h[slot].off == ~0ull) {
+		set_err(MIJ_E_NOMEM, "slot %d did not fit in the emission arena (needs %llu bytes)", slot, (unsigned long long)e->em.res.h[slot].len);
 		return MIJ_ENC_SLOT_NO_ROOM;
 	}
 	return MIJ_ENC_SLOT_OK;
@@ -4841,17 +4701,13 @@ static int enc_coef_convert(mij_encoder *e)
 		return MIJ_OK;
 	if (nw > UINT32_MAX)
 		return set_err(MIJ_E_ARG, "too many plane tiles to convert in one launch");
-	if (nc > e->cslot_cap || nw > e->cwork_cap || n > e->sflag_cap || nq > e->rqt_cap)
-		HIP_TRY(hipStreamSynchronize(e->stream));
-	int rc = grow_pair(e->h_cslot, e->d_cslot, e->cslot_cap, nc);
-	if (rc == MIJ_OK)
-		rc = grow_pair(e->h_rqt, e->d_rqt, e->rqt_cap, nq);
-	if (rc == MIJ_OK)
-		rc = grow_pair(e->h_cwork, e->d_cwork, e->cwork_cap, nw);
-	if (rc == MIJ_OK)
-		rc = grow_dev(e->d_sflag, e->sflag_cap, n);
-	if (rc != MIJ_OK)
-		return rc;
+	EncGrow grow(e->stream);
+	grow(e->cslot, nc);
+	grow(e->rqt, nq);
+	grow(e->cwork, nw);
+	grow(e->sflag_dev, n);
+	if (grow.rc != MIJ_OK)
+		return grow.rc;
 	if (!e->ev_coef) {
 		HIP_TRY(hipEventCreateWithFlags(&e->ev_coef, hipEventDisableTiming));
 		HIP_TRY(hipEventCreate(&e->ev_conv0));
@@ -4884,23 +4740,23 @@ static int enc_coef_convert(mij_encoder *e)
 		for (const EncSlot &s : e->slots) {
 			if (s.kind != ENC_COEF || s.src != g.b || s.coef_fmt != g.fmt || s.coef.orient != g.orient || g.rq != (s.coef.rq != 0) || g.win != (s.coef.win != 0))
 				continue;
-			e->h_cslot[k] = s.coef;
-			e->h_cslot[k].ri = (uint32_t)s.restart;
+			e->cslot.h[k] = s.coef;
+			e->cslot.h[k].ri = (uint32_t)s.restart;
 			if (g.rq) {
-				rq_fill(e->h_rqt[q], (s.coef.orient & MIJ_CONV_TR) != 0, s.rq_from[0], s.tp.plan.ytab, s.rq_from[1], s.tp.plan.ctab);
-				e->h_cslot[k].rq = (uint32_t)++q;
+				rq_fill(e->rqt.h[q], (s.coef.orient & MIJ_CONV_TR) != 0, s.rq_from[0], s.tp.plan.ytab, s.rq_from[1], s.tp.plan.ctab);
+				e->cslot.h[k].rq = (uint32_t)++q;
 			}
 			for (uint32_t c = 0; c < s.coef.ncomp; ++c)
-				coef_slot_tiles(s.coef, c, [&](uint32_t t) { e->h_cwork[w++] = WorkIdct{(uint32_t)k, c, t, 0u}; });
+				coef_slot_tiles(s.coef, c, [&](uint32_t t) { e->cwork.h[w++] = WorkIdct{(uint32_t)k, c, t, 0u}; });
 			++k;
 		}
 		g.count = w - g.first;
 	}
-	HIP_TRY(hipMemcpyAsync(e->d_cslot, e->h_cslot, sizeof(CoefSlot) * nc, hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipMemcpyAsync(e->d_cwork, e->h_cwork, sizeof(WorkIdct) * nw, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->cslot.d, e->cslot.h, sizeof(CoefSlot) * nc, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->cwork.d, e->cwork.h, sizeof(WorkIdct) * nw, hipMemcpyHostToDevice, e->stream));
 	if (nq)
-		HIP_TRY(hipMemcpyAsync(e->d_rqt, e->h_rqt, sizeof(RqTable) * nq, hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipMemsetAsync(e->d_sflag, 0, sizeof(uint32_t) * n, e->stream));
+		HIP_TRY(hipMemcpyAsync(e->rqt.d, e->rqt.h, sizeof(RqTable) * nq, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemsetAsync(e->sflag_dev.d, 0, sizeof(uint32_t) * n, e->stream));
 	for (mij_batch *b : batches) { /* whatever the batch's stream still does to the planes comes first */
 		HIP_TRY(hipEventRecord(e->ev_coef, b->stream));
 		HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_coef, 0));
@@ -4910,15 +4766,35 @@ static int enc_coef_convert(mij_encoder *e)
 		if (!g.count)
 			continue;
 		const dim3 grid((unsigned)g.count), block(64);
-		uint8_t *du = reinterpret_cast<uint8_t *>(e->d_du);
-		hipLaunchKernelGGL((g.win ? k_coef_units_win_of : k_coef_units_of)[g.rq ? 1 : 0][g.fmt ? 1 : 0][g.orient & 7u], grid, block, 0, e->stream, e->d_cslot, e->d_cwork + g.first, g.b->d_coef, du,
-								 e->d_sflag, static_cast<const RqTable *>(e->d_rqt));
+		uint8_t *du = e->du.d;
+		hipLaunchKernelGGL((g.win ? k_coef_units_win_of : k_coef_units_of)[g.rq ? 1 : 0][g.fmt ? 1 : 0][g.orient & 7u], grid, block, 0, e->stream, e->cslot.d, e->cwork.d + g.first, g.b->d_coef, du,
+								 e->sflag_dev.d, static_cast<const RqTable *>(e->rqt.d));
 		HIP_TRY(hipGetLastError());
 	}
 	HIP_TRY(hipEventRecord(e->ev_conv1, e->stream));
 	e->coef_tiles = (uint32_t)nw;
 	e->conv_timed = true;
 	return MIJ_OK;
+}
+
+/* The transform group of a slot; EG_NONE for given units and for units made from coefficient planes, which have nothing to transform.  A
+ * plane slot always takes its own strip kernel.  A pixel slot takes the strip kernel of its MCU shape (a sampled 4:2:0 or 4:4:4 the
+ * instance a default slot takes), or under force_generic, which a sampled slot ignores, the per-unit luma kernel of its sampling: the
+ * chroma one is the next group. */
+static EncGroup enc_classify(const mij_encoder *e, const EncSlot &s)
+{
+	const mjw_tplan &t = s.tp;
+	if (!enc_has_pixels(s.kind))
+		return EG_NONE;
+	if (s.planes)
+		return t.ncomp == 1 ? EG_PGREY : t.lh == 2 ? (t.lv == 2 ? EG_P420 : EG_P422) : (t.lv == 2 ? EG_P440 : EG_P444);
+	if (t.ncomp == 1)
+		return EG_GREY;
+	if (t.lh != t.lv)
+		return t.lh == 2 ? EG_422 : EG_440;
+	if (e->force_generic && !s.sampled)
+		return t.lh == 2 ? EG_Y420 : EG_Y444;
+	return t.lh == 2 ? EG_420 : EG_444;
 }
 
 extern "C" int mij_enc_upload(mij_encoder *e)
@@ -4929,88 +4805,46 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 	const size_t n = e->slots.size();
 	if (!n)
 		return set_err(MIJ_E_STATE, "encoder batch is empty");
-	std::vector<WorkIdct> work[MIJ_ENC_GROUPS];
+	std::vector<WorkIdct> work[EG_GROUPS];
 	for (size_t i = 0; i < n; ++i) {
 		const EncSlot &s = e->slots[i];
-		const uint32_t nm = (uint32_t)(s.plan.mcu_x * s.plan.mcu_y);
-		const int sub = s.plan.subsample ? 1 : 0;
-		const uint32_t ny = nm * (sub ? 4u : 1u), nc = nm * 2u;
-		e->h_imgs[i] = s.dev;
-		if (!enc_has_pixels(s.kind)) /* given units, or units made from coefficient planes: nothing to transform */
+		e->imgs.h[i] = s.dev;
+		const EncGroup g = enc_classify(e, s);
+		if (g == EG_NONE)
 			continue;
-		if (s.planes) { /* always its own strip kernel */
-			const int g = s.tp.ncomp == 1 ? 13 : 9 + (s.tp.lh == 2 ? 1 : 0) + (s.tp.lv == 2 ? 2 : 0);
-			const uint32_t strip = (uint32_t)MIJ_ENCP_STRIP(s.tp.lh, s.tp.lv, s.tp.ncomp);
-			for (uint32_t f = 0; f < nm; f += strip) {
-				WorkIdct w = {(uint32_t)i, 0u, f, 0u};
-				work[g].push_back(w);
-			}
-			continue;
-		}
-		/* a sampling of its own: the strip kernel of its MCU shape, whatever force_generic says; 4:2:0 and 4:4:4 go on below, through the
-		 * kernel instances a default slot takes */
-		if (s.sampled && (s.tp.ncomp == 1 || s.tp.lh != s.tp.lv)) {
-			const int g = s.tp.ncomp == 1 ? 8 : s.tp.lh == 2 ? 6 : 7;
-			const uint32_t strip = g == 8 ? MIJ_ENCGREY_STRIP : g == 6 ? MIJ_ENC422_STRIP : MIJ_ENC440_STRIP;
-			for (uint32_t f = 0; f < nm; f += strip) {
-				WorkIdct w = {(uint32_t)i, 0u, f, 0u};
-				work[g].push_back(w);
-			}
-			continue;
-		}
-		const bool generic = e->force_generic && !s.sampled;
-		/* strips of 32 MCUs through the fused kernel: whole 16-pixel columns, packed RGB, 16-byte aligned rows (every width: enc_padded_width) */
-		if (sub && !generic) { /* every comp: the staging is packed RGB */
-			for (uint32_t f = 0; f < nm; f += MIJ_ENC_STRIP) {
-				WorkIdct w = {(uint32_t)i, 0u, f, 0u};
-				work[4].push_back(w);
-			}
-			continue;
-		}
-		/* 4:4:4 (quality above 90): strips of 64 MCUs through k_encode444: whole 8-pixel columns, packed RGB, 8-byte aligned rows */
-		if (!sub && !generic) {
-			for (uint32_t f = 0; f < nm; f += MIJ_ENC444_STRIP) {
-				WorkIdct w = {(uint32_t)i, 0u, f, 0u};
-				work[5].push_back(w);
-			}
-			continue;
-		}
-		for (uint32_t f = 0; f < ny; f += 256) {
-			WorkIdct w = {(uint32_t)i, 0u, f, 0u};
-			work[sub * 2 + 0].push_back(w);
-		}
-		for (uint32_t f = 0; f < nc; f += 256) {
-			WorkIdct w = {(uint32_t)i, 1u, f, 0u};
-			work[sub * 2 + 1].push_back(w);
-		}
+		/* a strip kernel's items count MCUs; the per-unit pair's count the luma units, and in the next group the two chroma units per MCU */
+		const bool pair = g <= EG_C420;
+		const uint32_t nm = (uint32_t)(s.tp.plan.mcu_x * s.tp.plan.mcu_y);
+		const uint32_t count[2] = {pair ? nm * (g == EG_Y420 ? 4u : 1u) : nm, nm * 2u};
+		for (uint32_t k = 0; k < (pair ? 2u : 1u); ++k)
+			for (uint32_t f = 0; f < count[k]; f += enc_families[g + k].strip)
+				work[g + k].push_back(WorkIdct{(uint32_t)i, k, f, 0u});
 	}
 	size_t total = 0;
-	for (int g = 0; g < MIJ_ENC_GROUPS; ++g)
+	for (int g = 0; g < EG_GROUPS; ++g)
 		total += work[g].size();
-	if (total > e->work_cap)
-		HIP_TRY(hipStreamSynchronize(e->stream));
-	int rc = grow_pair(e->h_work, e->d_work, e->work_cap, total);
-	if (rc != MIJ_OK)
-		return rc;
+	EncGrow grow(e->stream);
+	grow(e->work, total);
+	if (grow.rc != MIJ_OK)
+		return grow.rc;
 	size_t pos = 0;
-	for (int g = 0; g < MIJ_ENC_GROUPS; ++g) {
+	for (int g = 0; g < EG_GROUPS; ++g) {
 		e->first_work[g] = pos;
 		e->n_work[g] = work[g].size();
 		if (!work[g].empty())
-			memcpy(e->h_work + pos, work[g].data(), work[g].size() * sizeof(WorkIdct));
+			memcpy(e->work.h + pos, work[g].data(), work[g].size() * sizeof(WorkIdct));
 		pos += work[g].size();
 	}
-	HIP_TRY(hipMemcpyAsync(e->d_imgs, e->h_imgs, sizeof(EncImage) * n, hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipMemcpyAsync(e->d_work, e->h_work, sizeof(WorkIdct) * total, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->imgs.d, e->imgs.h, sizeof(EncImage) * n, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->work.d, e->work.h, sizeof(WorkIdct) * total, hipMemcpyHostToDevice, e->stream));
 	for (size_t i = 0; i < n; ++i) {
 		const EncSlot &s = e->slots[i];
 		if (s.clone_of < 0 && s.kind == ENC_HOST)
-			HIP_TRY(hipMemcpyAsync(e->d_pix + s.dev.pix_off, e->stage + s.stage_off, s.pix_bytes, hipMemcpyHostToDevice, e->stream));
+			HIP_TRY(hipMemcpyAsync(e->pix.d + s.dev.pix_off, e->stage.h + s.stage_off, s.pix_bytes, hipMemcpyHostToDevice, e->stream));
 		else if (s.kind == ENC_UNITS)
-			HIP_TRY(hipMemcpyAsync(reinterpret_cast<uint8_t *>(e->d_du) + s.dev.du_off, s.units.data(), s.units.size() * sizeof(int16_t),
-										  hipMemcpyHostToDevice, e->stream));
+			HIP_TRY(hipMemcpyAsync(e->du.d + s.dev.du_off, s.units.data(), s.units.size() * sizeof(int16_t), hipMemcpyHostToDevice, e->stream));
 	}
-	rc = enc_gather(e); /* device-pixel slots, before the clones copy them */
+	int rc = enc_gather(e); /* device-pixel slots, before the clones copy them */
 	if (rc == MIJ_OK)
 		rc = enc_gather_float(e);
 	if (rc == MIJ_OK)
@@ -5022,9 +4856,9 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 	for (size_t i = 0; i < n; ++i) {
 		const EncSlot &s = e->slots[i];
 		if (s.clone_of >= 0)
-			HIP_TRY(hipMemcpyAsync(e->d_pix + s.dev.pix_off, e->d_pix + e->slots[(size_t)s.clone_of].dev.pix_off, s.pix_bytes, hipMemcpyDeviceToDevice, e->stream));
+			HIP_TRY(hipMemcpyAsync(e->pix.d + s.dev.pix_off, e->pix.d + e->slots[(size_t)s.clone_of].dev.pix_off, s.pix_bytes, hipMemcpyDeviceToDevice, e->stream));
 	}
-	if (e->d_arena) {
+	if (e->em.arena.d) {
 		rc = enc_emit_lists(e);
 		if (rc != MIJ_OK)
 			return rc;
@@ -5042,46 +4876,15 @@ extern "C" int mij_enc_launch(mij_encoder *e)
 	if (!e->uploaded)
 		return set_err(MIJ_E_STATE, "mij_enc_launch before mij_enc_upload");
 	HIP_TRY(hipSetDevice(e->ctx->device));
-	for (int g = 0; g < MIJ_ENC_GROUPS; ++g) {
+	for (int g = 0; g < EG_GROUPS; ++g) {
 		if (!e->n_work[g])
 			continue;
-		const dim3 grid((unsigned)e->n_work[g]), block(g == 6 ? 128 : g == 4 || g == 5 ? 192 : 256);
-		const WorkIdct *wk = e->d_work + e->first_work[g];
-#define MIJ_ENCP_LAUNCH(LH, LV, NC)                                                                                                      \
-	hipLaunchKernelGGL((k_encode_planes<LH, LV, NC>), grid, dim3(MIJ_ENCP_NT(LH, LV, NC)), MIJ_ENCP_LDS(LH, LV, NC), e->stream, e->d_imgs, wk, \
-							 e->d_pix, e->d_du)
-		if (g == 9)
-			MIJ_ENCP_LAUNCH(1, 1, 3);
-		else if (g == 10)
-			MIJ_ENCP_LAUNCH(2, 1, 3);
-		else if (g == 11)
-			MIJ_ENCP_LAUNCH(1, 2, 3);
-		else if (g == 12)
-			MIJ_ENCP_LAUNCH(2, 2, 3);
-		else if (g == 13)
-			MIJ_ENCP_LAUNCH(1, 1, 1);
-#undef MIJ_ENCP_LAUNCH
-		else if (g == 6)
-			hipLaunchKernelGGL(k_encode422, grid, block, MIJ_ENC422_LDS, e->stream, e->d_imgs, wk, e->d_pix, e->d_du);
-		else if (g == 7)
-			hipLaunchKernelGGL(k_encode440, grid, block, MIJ_ENC440_LDS, e->stream, e->d_imgs, wk, e->d_pix, e->d_du);
-		else if (g == 8)
-			hipLaunchKernelGGL(k_encode_grey, grid, block, MIJ_ENCGREY_LDS, e->stream, e->d_imgs, wk, e->d_pix, e->d_du);
-		else if (g == 4)
-			hipLaunchKernelGGL(k_encode420, grid, block, MIJ_ENC_LDS, e->stream, e->d_imgs, wk, e->d_pix, e->d_du);
-		else if (g == 5)
-			hipLaunchKernelGGL(k_encode444, grid, block, MIJ_ENC444_LDS, e->stream, e->d_imgs, wk, e->d_pix, e->d_du);
-		else if (g == 0)
-			hipLaunchKernelGGL((k_encode_y<0>), grid, block, 0, e->stream, e->d_imgs, wk, e->d_pix, e->d_du);
-		else if (g == 1)
-			hipLaunchKernelGGL((k_encode_c<0>), grid, block, 0, e->stream, e->d_imgs, wk, e->d_pix, e->d_du);
-		else if (g == 2)
-			hipLaunchKernelGGL((k_encode_y<1>), grid, block, 0, e->stream, e->d_imgs, wk, e->d_pix, e->d_du);
-		else
-			hipLaunchKernelGGL((k_encode_c<1>), grid, block, 0, e->stream, e->d_imgs, wk, e->d_pix, e->d_du);
+		const EncFamily &f = enc_families[g];
+		hipLaunchKernelGGL(f.k, dim3((unsigned)e->n_work[g]), dim3(f.threads), f.lds, e->stream, e->imgs.d, e->work.d + e->first_work[g], e->pix.d,
+								 reinterpret_cast<int16_t *>(e->du.d));
 		HIP_TRY(hipGetLastError());
 	}
-	if (e->d_arena) {
+	if (e->em.arena.d) {
 		const int rc = enc_emit_launch(e);
 		if (rc != MIJ_OK)
 			return rc;
@@ -5116,18 +4919,18 @@ extern "C" int mij_enc_fetch(mij_encoder *e, int slot, int16_t *dst, size_t dst_
 	if (!e->launched)
 		return set_err(MIJ_E_STATE, "mij_enc_fetch before launch");
 	const EncSlot &s = e->slots[(size_t)slot];
-	const size_t elems = mjw_plan_du_count(&s.plan) * 64;
+	const size_t elems = mjw_plan_du_count(&s.tp.plan) * 64;
 	if (dst_elems < elems)
 		return set_err(MIJ_E_ARG, "destination too small");
 	HIP_TRY(hipSetDevice(e->ctx->device));
-	return d2h_bounced(e->ctx, e->stream, dst, reinterpret_cast<const uint8_t *>(e->d_du) + s.dev.du_off, elems * 2);
+	return d2h_bounced(e->ctx, e->stream, dst, e->du.d + s.dev.du_off, elems * 2);
 }
 
 extern "C" int mij_enc_plan(const mij_encoder *e, int slot, mjw_plan *out)
 {
 	if (!e || slot < 0 || slot >= (int)e->slots.size() || !out)
 		return set_err(MIJ_E_ARG, "bad slot");
-	*out = e->slots[(size_t)slot].plan;
+	*out = e->slots[(size_t)slot].tp.plan;
 	return MIJ_OK;
 }
 

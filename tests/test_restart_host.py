@@ -233,3 +233,32 @@ def test_edges(ica):
 def _region(ica, data):
     desc, region = ica.binding.host_decode_staged(data, 0, False)[:2]
     return desc, region, False
+
+
+def test_the_transcode_header_of_a_default_plan_is_the_writers(ica):
+    """the GPU encoder keeps one mjw_tplan per slot and writes every baseline header with mjw_theader_restart: for the writer's own
+    4:2:0 / 4:4:4 plan (three components, lh = lv = subsample ? 2 : 1) that is mjw_header_restart byte for byte, over every comp,
+    both samplings, tiny and padded sizes and the ends of the interval's range"""
+    ica.lib()
+    B, L = ica.binding, C.CDLL(ica.binding.LIB_PATH)  # a handle of its own: the prototypes set here stay off the one the other tests share
+    L.mjw_plan_init.argtypes = [C.POINTER(B.WritePlan), C.c_int, C.c_int, C.c_int, C.c_int]
+    L.mjw_header_restart.restype = L.mjw_theader_restart.restype = C.c_size_t
+    L.mjw_header_restart.argtypes = [C.POINTER(B.WritePlan), C.c_int, C.c_char_p]
+    L.mjw_theader_restart.argtypes = [C.POINTER(B.TranscodePlan), C.c_int, C.c_char_p]
+    widths = (1, 7, 8, 16, 17, 200)
+    cap = 607 + 6  # MJW_HEADER_RESTART_BYTES
+    cases = 0
+    for comp in (1, 2, 3, 4):
+        for q in (1, 50, 90, 91, 100):
+            for w, h in zip(widths, widths[::-1]):
+                plan = B.WritePlan()
+                assert L.mjw_plan_init(C.byref(plan), w, h, comp, q)
+                t = B.TranscodePlan(copy.deepcopy(plan), 3, 2 if plan.subsample else 1, 2 if plan.subsample else 1)
+                assert plan.subsample == (q <= 90)
+                for ri in (0, 1, 5, 65535):
+                    a, b = C.create_string_buffer(b"\xaa" * (cap + 8), cap + 8), C.create_string_buffer(b"\x55" * (cap + 8), cap + 8)
+                    na, nb = L.mjw_header_restart(C.byref(plan), ri, a), L.mjw_theader_restart(C.byref(t), ri, b)
+                    assert 0 < na == nb <= cap and a.raw[:na] == b.raw[:nb], (comp, q, w, h, ri)
+                    assert a.raw[na:] == b"\xaa" * (cap + 8 - na) and b.raw[nb:] == b"\x55" * (cap + 8 - nb)
+                    cases += 1
+    assert cases == 480
