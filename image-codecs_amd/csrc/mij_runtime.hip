@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -20,6 +21,7 @@
 #include "mij_host.h"
 #include "mij_kernels.h"
 #include "mij_scaled_kernels.h"
+#include "mij_entropy_kernels.h"
 
 using namespace mij;
 
@@ -324,15 +326,149 @@ static inline int out_w(const Slot &s) { return mij_scaled_dim(s.desc.width, s.s
 static inline int out_h(const Slot &s) { return mij_scaled_dim(s.desc.height, s.scale); }
 static inline size_t out_px_bytes(const Slot &s) { return (size_t)s.desc.n_out * (size_t)out_w(s) * (size_t)out_h(s); }
 
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+/* one free per device / pinned pointer, which is left null */
+template <typename T> static void free_dev(T *&p) { if (p) (void)hipFree(p); p = nullptr; }
+template <typename T> static void free_host(T *&p) { if (p) (void)hipHostFree(p); p = nullptr; }
+
+/* A list or an arena a batch or an encoder owns: `cap` elements in pinned memory, in device memory or (a list the host fills and a kernel
+ * reads) in both.  alloc is for what has its size when it is made: the arenas, whose size the caller chose, and the per-slot tables.  The
+ * lists are reallocated through Grow and nowhere else. */
+enum { BUF_PINNED = 1, BUF_ON_DEVICE = 2 };
+template <typename T, int SIDES = BUF_PINNED | BUF_ON_DEVICE>
+struct Buf {
+	T *h = nullptr, *d = nullptr;
+	size_t cap = 0;
+	Buf() = default;
+	Buf &operator=(Buf &&o) /* o, a temporary, releases what this held */
+	{
+		std::swap(h, o.h), std::swap(d, o.d), std::swap(cap, o.cap);
+		return *this;
+	}
+	~Buf() { release(); }
+	void release()
+	{
+		free_host(h);
+		free_dev(d);
+		cap = 0;
+	}
+	hipError_t alloc(size_t n) /* exactly n elements, the pinned side first; an empty arena still has an address; cap stays 0 on failure */
+	{
+		release();
+		hipError_t r = hipSuccess;
+		if (SIDES & BUF_PINNED)
+			r = hipHostMalloc(reinterpret_cast<void **>(&h), sizeof(T) * (n ? n : 16), hipHostMallocDefault);
+		if (r == hipSuccess && (SIDES & BUF_ON_DEVICE))
+			r = hipMalloc(reinterpret_cast<void **>(&d), sizeof(T) * (n ? n : 16));
+		if (r == hipSuccess)
+			cap = n;
+		return r;
+	}
+};
+
+/* Grows the lists of one upload step.  Copies and launches queued earlier may still read a list, so the first one that has to be
+ * reallocated waits for the stream: one wait however many grow, none when none does.  A list grows to need + need / 2 + 64 elements;
+ * exact() is for the scratch planes, which take what the upload needs and no more.  rc is the first failure, hip what the allocation
+ * behind it answered. */
+struct Grow {
+	hipStream_t stream;
+	bool waited = false;
+	int rc = MIJ_OK;
+	hipError_t hip = hipSuccess;
+	explicit Grow(hipStream_t st) : stream(st) {}
+	template <typename T, int SIDES>
+	bool operator()(Buf<T, SIDES> &b, size_t need) /* true: b was reallocated */
+	{
+		return to(b, need, need + need / 2 + 64);
+	}
+	template <typename T, int SIDES>
+	bool exact(Buf<T, SIDES> &b, size_t need)
+	{
+		return to(b, need, need);
+	}
+
+private:
+	template <typename T, int SIDES>
+	bool to(Buf<T, SIDES> &b, size_t need, size_t ncap)
+	{
+		static_assert(SIDES & BUF_ON_DEVICE, "only what a kernel reads grows");
+		if (rc != MIJ_OK || need <= b.cap)
+			return false;
+		if (!waited) {
+			const hipError_t r = hipStreamSynchronize(stream);
+			if (r != hipSuccess) {
+				rc = set_err(MIJ_E_HIP, "hipStreamSynchronize before growing a list failed: %s", hipGetErrorString(r));
+				return false;
+			}
+			waited = true;
+		}
+		hip = b.alloc(ncap);
+		if (hip != hipSuccess)
+			rc = set_err(MIJ_E_HIP, "growing a list to %zu elements failed: %s", ncap, hipGetErrorString(hip));
+		return rc == MIJ_OK;
+	}
+};
+
 struct Work4 { /* WorkBand and WorkIdct are both four u32 */
 	uint32_t a, b, c, d;
 };
 
 /* an output pass's plan -- descriptors, tables and work list -- in one pinned buffer and its device copy */
 struct PlanBuf {
-	uint8_t *h = nullptr, *d = nullptr;
-	size_t cap = 0;
+	Buf<uint8_t> buf;
 	size_t items = 0, lut_at = 0, work_at = 0; /* work items of the last upload; byte offsets of the tables and the work list */
+};
+
+/* GPU entropy stage (mij_batch_entropy_*; see mij_entropy_kernels.h for the algorithm).  The arena holds everything the kernels touch
+ * besides the coefficient planes: the unstuffed streams, per-scan descriptors and Huffman tables, three state words and a counter per
+ * subsequence, a DC difference and an L1 accumulator per block, and five verdict words per scan.  Made by mij_batch_entropy_reserve. */
+static const int ES_MAX_ROUNDS = 96;
+enum EsVerdict { EV_ANOMALY = 0, EV_CHANGED, EV_TOTAL, EV_L1MAX, EV_PFINAL, EV_ROWS }; /* the rows of the verdict table, scan_cap words each */
+struct EsArena {
+	Buf<uint8_t> stream; /* h: the pinned region the host stage writes the unstuffed streams into; cap bytes */
+	Buf<DevScan> scans;  /* scan_cap */
+	Buf<DevHuff> huff;   /* eight per table set */
+	Buf<EsWork> work;
+	Buf<WorkIdct> pack; /* k_es_pack: (slot, component, first block) per 256 blocks of every compact-plane slot */
+	Buf<uint64_t, BUF_ON_DEVICE> start, end[2]; /* end[0]: the cold pass's end states, end[1]: the current ones (first round on) */
+	Buf<uint4, BUF_ON_DEVICE> uni;  /* k_es_tables: one EsUni per table set */
+	Buf<uint4, BUF_ON_DEVICE> wtab; /* ... and one EsW (the record-form write pass's tables) */
+	Buf<uint32_t> tabscan;          /* table set -> a scan that uses it */
+	Buf<uint32_t, BUF_ON_DEVICE> qidx[2];   /* the queues of k_es_syncq, alternating by round: subsequence ... */
+	Buf<uint64_t, BUF_ON_DEVICE> qstate[2]; /* ... and the start state it has to run from; a scan's entries start at its sub_off */
+	Buf<uint32_t, BUF_ON_DEVICE> cnt, base;
+	size_t sub_cap = 0;    /* subsequences: start, end, the queues, cnt and base */
+	uint32_t sub_bits = 0; /* bits per subsequence of this arena's scans */
+	int rounds0 = 0;       /* synchronisation rounds queued before the first look at the verdicts */
+	Buf<uint64_t, BUF_ON_DEVICE> meta; /* per block: L1 of its AC coefficients | DC difference << 32 */
+	/* compact planes, the write pass's intermediate form: the zigzag image, 64 bytes per block, or with use_records the record form
+	 * (k_es_writer / k_es_pack2), rec_region64 eight-byte words per subsequence.  Only one of the two is allocated. */
+	Buf<uint8_t, BUF_ON_DEVICE> zz;
+	Buf<uint64_t, BUF_ON_DEVICE> rec;
+	uint32_t rec_region64 = 0;
+	size_t rec_words = 0;
+	bool use_records = false;
+	size_t blk_cap = 0;
+	Buf<uint32_t, BUF_ON_DEVICE> verdict; /* [EV_ROWS][scan_cap] */
+	Buf<uint32_t, BUF_PINNED> verdict_host;
+	Buf<uint32_t, BUF_ON_DEVICE> rounds_changed; /* [ES_MAX_ROUNDS]: k_es_tails' scratch */
+	Buf<uint32_t, BUF_ON_DEVICE> changed; /* [ES_MAX_ROUNDS][scan_cap]: subsequences moved per scan, one slice per synchronisation round -- cleared once
+	                                       * per launch instead of once per round (a one-picture batch queues 24 rounds: 24 fewer commands per stbi_load call) */
+	std::vector<int> scan_slot; /* scan index -> batch slot */
+	size_t sub_used = 0, blk_used = 0, work_used = 0, pack_used = 0, scan_cap = 0, n_tabs = 0;
+	int last_rounds = 0;
+	bool in_flight = false;
+
+	uint32_t *d_row(EsVerdict v) { return verdict.d + (size_t)v * scan_cap; }
+	const uint32_t *h_row(EsVerdict v) const { return verdict_host.h + (size_t)v * scan_cap; }
+	uint32_t *h_row(EsVerdict v) { return verdict_host.h + (size_t)v * scan_cap; }
+	void reset() /* mij_batch_reset: no scans, nothing in flight */
+	{
+		scan_slot.clear();
+		sub_used = blk_used = work_used = pack_used = n_tabs = 0;
+		in_flight = false;
+	}
 };
 
 struct mij_batch {
@@ -342,23 +478,18 @@ struct mij_batch {
 	hipEvent_t ev_pack0 = nullptr, ev_pack1 = nullptr; /* around k_pack_c8 in the last upload (mij_batch_pack_ms); created on first use */
 	bool pack_timed = false;
 	int max_images = 0;
-	/* arenas */
-	uint8_t *stage = nullptr;
-	size_t stage_cap = 0, stage_used = 0;
-	uint8_t *d_coef = nullptr;
-	size_t coef_cap = 0, coef_used = 0;
-	uint8_t *d_out = nullptr;
-	size_t out_cap = 0, out_used = 0;
-	uint8_t *d_planes = nullptr;
-	size_t planes_cap = 0;
-	uint8_t *d_up16 = nullptr; /* upload scratch: int16 planes on their way into compact planes (k_pack_c8), stage_cap bytes */
-	uint32_t *d_l1max = nullptr, *h_l1max = nullptr; /* per slot: largest per-block L1 the pack kernel saw (MIJ_FLAG_L1_ON_DEVICE); max_images entries, created on first use */
-	/* descriptors + work lists (pinned host mirror + device copy) */
-	DevImage *h_imgs = nullptr, *d_imgs = nullptr;
-	Work4 *h_work = nullptr, *d_work = nullptr;
-	size_t work_cap = 0;
-	DevRoi *h_roi = nullptr, *d_roi = nullptr; /* per slot, for the windowed kernels: created by the first upload that plans one */
-	size_t roi_cap = 0;
+	/* the arenas, in bytes: pinned staging, coefficient planes, pixels, the two-pass path's scratch sample planes (as large as the largest
+	 * upload needed), and the upload scratch: int16 planes on their way into compact planes (k_pack_c8), as large as the staging arena,
+	 * made by the first upload that packs */
+	Buf<uint8_t, BUF_PINNED> stage;
+	Buf<uint8_t, BUF_ON_DEVICE> coef, out, planes, up16;
+	size_t stage_used = 0, coef_used = 0, out_used = 0;
+	/* per slot, max_images entries: the descriptors; the largest per-block L1 the pack kernel saw (MIJ_FLAG_L1_ON_DEVICE) and the windows
+	 * of the windowed kernels, both made by the first upload that needs them */
+	Buf<DevImage> imgs;
+	Buf<uint32_t> l1max;
+	Buf<DevRoi> roi;
+	Buf<Work4> work; /* the work lists: the pack list, then one range per launch */
 	std::vector<Slot> slots;
 	/* launch plan built by upload: one per non-empty (family, variant) work list */
 	struct Launch {
@@ -371,11 +502,11 @@ struct mij_batch {
 	int force_generic = 0; /* 0: fused kernels where they apply; 1: two-pass path for every image; 2: and its run-time-general pass 2 */
 	int coef_fmt = 1;  /* format new coefficient planes get in HBM: 1 compact (default), 0 int16 (MIJ_COEF_FORMAT=int16, mij_batch_set_coef_format) */
 	int band_rows = 0; /* MCU rows per fused workgroup; 0 = automatic */
-	struct EsArena *es = nullptr; /* GPU entropy stage, allocated by mij_batch_entropy_reserve */
+	std::unique_ptr<EsArena> es; /* GPU entropy stage, made by mij_batch_entropy_reserve */
 	/* float output (mij_batch_set_out_f32): the arena, one request per slot that asked (its place in the arena and its tables), and what
 	 * upload made of them for k_out_f32 -- descriptors, tables and (slot, chunk) work list */
-	uint8_t *d_f32 = nullptr;
-	size_t f32_cap = 0, f32_used = 0;
+	Buf<uint8_t, BUF_ON_DEVICE> f32;
+	size_t f32_used = 0;
 	struct F32Req {
 		int slot;
 		size_t off;
@@ -411,13 +542,19 @@ struct mij_batch {
 	PlanBuf tentplan, rsztplan;
 };
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-static void es_free_fwd(struct EsArena *e);
-static void es_reset_fwd(struct EsArena *e);
-
-/* one free per device / pinned pointer, which is left null */
-template <typename T> static void free_dev(T *&p) { if (p) (void)hipFree(p); p = nullptr; }
-template <typename T> static void free_host(T *&p) { if (p) (void)hipHostFree(p); p = nullptr; }
+/* the slot, or null with MIJ_E_ARG and `what` as the error text */
+static const Slot *batch_slot(const mij_batch *b, int slot, const char *what = "bad slot")
+{
+	if (!b || slot < 0 || slot >= (int)b->slots.size()) {
+		set_err(MIJ_E_ARG, "%s", what);
+		return nullptr;
+	}
+	return &b->slots[(size_t)slot];
+}
+static Slot *batch_slot(mij_batch *b, int slot, const char *what = "bad slot")
+{
+	return const_cast<Slot *>(batch_slot(static_cast<const mij_batch *>(b), slot, what));
+}
 
 static inline size_t comp_tiles(const mij_comp_desc &cp) { return ((size_t)(cp.bw * cp.bh) + 63) >> 6; }
 
@@ -444,9 +581,6 @@ extern "C" int mij_batch_create(mij_ctx *ctx, int max_images, size_t stage_bytes
 		return set_err(MIJ_E_NOMEM, "out of host memory");
 	b->ctx = ctx;
 	b->max_images = max_images;
-	b->stage_cap = stage_bytes;
-	b->coef_cap = coef_bytes;
-	b->out_cap = out_bytes;
 	const char *fmt = getenv("MIJ_COEF_FORMAT");
 	b->coef_fmt = (fmt && (!strcmp(fmt, "int16") || !strcmp(fmt, "0"))) ? 0 : 1;
 	const char *env = getenv("MIJ_BAND_ROWS");
@@ -459,15 +593,13 @@ extern "C" int mij_batch_create(mij_ctx *ctx, int max_images, size_t stage_bytes
 	if (e == hipSuccess)
 		e = hipEventCreate(&b->ev_end);
 	if (e == hipSuccess && stage_bytes)
-		e = hipHostMalloc(reinterpret_cast<void **>(&b->stage), stage_bytes, hipHostMallocDefault);
+		e = b->stage.alloc(stage_bytes);
 	if (e == hipSuccess && coef_bytes)
-		e = hipMalloc(reinterpret_cast<void **>(&b->d_coef), coef_bytes);
+		e = b->coef.alloc(coef_bytes);
 	if (e == hipSuccess && out_bytes)
-		e = hipMalloc(reinterpret_cast<void **>(&b->d_out), out_bytes);
+		e = b->out.alloc(out_bytes);
 	if (e == hipSuccess)
-		e = hipHostMalloc(reinterpret_cast<void **>(&b->h_imgs), sizeof(DevImage) * (size_t)max_images, hipHostMallocDefault);
-	if (e == hipSuccess)
-		e = hipMalloc(reinterpret_cast<void **>(&b->d_imgs), sizeof(DevImage) * (size_t)max_images);
+		e = b->imgs.alloc((size_t)max_images);
 	if (e != hipSuccess) {
 		int code = (e == hipErrorOutOfMemory) ? MIJ_E_NOMEM : MIJ_E_HIP;
 		set_err(code, "mij_batch_create: %s", hipGetErrorString(e));
@@ -486,32 +618,14 @@ extern "C" void mij_batch_destroy(mij_batch *b)
 	(void)hipSetDevice(b->ctx->device);
 	if (b->stream)
 		(void)hipStreamSynchronize(b->stream);
-	free_host(b->stage);
-	free_dev(b->d_coef);
-	free_dev(b->d_out);
-	free_dev(b->d_planes);
-	free_host(b->h_imgs);
-	free_dev(b->d_imgs);
-	free_host(b->h_work);
-	free_dev(b->d_work);
-	free_host(b->h_roi);
-	free_dev(b->d_roi);
-	free_dev(b->d_up16);
-	free_dev(b->d_l1max);
-	free_host(b->h_l1max);
-	if (b->es)
-		es_free_fwd(b->es);
-	free_dev(b->d_f32);
-	for (PlanBuf *p : {&b->f32plan, &b->tenplan, &b->rszplan, &b->tentplan, &b->rsztplan}) {
-		free_host(p->h);
-		free_dev(p->d);
-	}
-	for (hipEvent_t ev : {b->ev_begin, b->ev_end, b->ev_pack0, b->ev_pack1})
+	const hipStream_t stream = b->stream;
+	const hipEvent_t events[] = {b->ev_begin, b->ev_end, b->ev_pack0, b->ev_pack1};
+	delete b; /* its buffers and its entropy arena release themselves, before the events and the stream go */
+	for (hipEvent_t ev : events)
 		if (ev)
 			(void)hipEventDestroy(ev);
-	if (b->stream)
-		(void)hipStreamDestroy(b->stream);
-	delete b;
+	if (stream)
+		(void)hipStreamDestroy(stream);
 }
 
 extern "C" int mij_batch_reset(mij_batch *b)
@@ -529,7 +643,8 @@ extern "C" int mij_batch_reset(mij_batch *b)
 	b->ten_req.clear();
 	b->rsz_coef.clear();
 	b->f32plan.items = b->tenplan.items = b->rszplan.items = b->tentplan.items = b->rsztplan.items = 0;
-	es_reset_fwd(b->es);
+	if (b->es)
+		b->es->reset();
 	return MIJ_OK;
 }
 
@@ -649,9 +764,9 @@ static int add_common(mij_batch *b, const mij_image_desc *d, int clone_of, bool 
 	if ((int)b->slots.size() >= b->max_images)
 		return set_err(MIJ_E_NOMEM, "batch is full (%d images)", b->max_images);
 	const size_t cbytes = mij_image_coef_bytes(d), obytes = mij_image_out_bytes(d);
-	if (b->coef_used + cbytes > b->coef_cap)
+	if (b->coef_used + cbytes > b->coef.cap)
 		return set_err(MIJ_E_NOMEM, "coefficient arena exhausted");
-	if (b->out_used + obytes > b->out_cap)
+	if (b->out_used + obytes > b->out.cap)
 		return set_err(MIJ_E_NOMEM, "output arena exhausted");
 	Slot s;
 	s.desc = *d;
@@ -667,14 +782,14 @@ static int add_common(mij_batch *b, const mij_image_desc *d, int clone_of, bool 
 	s.roi_on = s.roi_auto = s.reg = false;
 	s.work_items = 0;
 	if (clone_of < 0) {
-		if (b->stage_used + cbytes > b->stage_cap) {
+		if (b->stage_used + cbytes > b->stage.cap) {
 			if (!lazy_stage)
 				return set_err(MIJ_E_NOMEM, "staging arena exhausted");
 			s.stage_off = MIJ_NO_STAGE;
 		} else {
 			s.stage_off = b->stage_used;
 			if (!lazy_stage && clear)
-				memset(b->stage + s.stage_off, 0, cbytes);
+				memset(b->stage.h + s.stage_off, 0, cbytes);
 			b->stage_used += cbytes;
 		}
 	} else {
@@ -712,8 +827,8 @@ extern "C" int mij_batch_add_uncleared(mij_batch *b, const mij_image_desc *d)
 
 extern "C" int mij_batch_add_clone(mij_batch *b, int src_slot)
 {
-	if (!b || src_slot < 0 || src_slot >= (int)b->slots.size())
-		return set_err(MIJ_E_ARG, "bad source slot");
+	if (!batch_slot(b, src_slot, "bad source slot"))
+		return MIJ_E_ARG;
 	int root = b->slots[(size_t)src_slot].clone_of >= 0 ? b->slots[(size_t)src_slot].clone_of : src_slot;
 	mij_image_desc d = b->slots[(size_t)root].desc;
 	return add_common(b, &d, root);
@@ -721,49 +836,45 @@ extern "C" int mij_batch_add_clone(mij_batch *b, int src_slot)
 
 extern "C" int16_t *mij_batch_coef(mij_batch *b, int slot, int comp)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size()) {
-		set_err(MIJ_E_ARG, "bad slot");
+	if (!batch_slot(b, slot))
 		return nullptr;
-	}
 	const Slot &s = b->slots[(size_t)slot];
-	if (comp < 0 || comp >= s.desc.ncomp || s.clone_of >= 0 || !b->stage || s.stage_off == MIJ_NO_STAGE) {
+	if (comp < 0 || comp >= s.desc.ncomp || s.clone_of >= 0 || !b->stage.h || s.stage_off == MIJ_NO_STAGE) {
 		set_err(MIJ_E_ARG, "bad component, or slot has no staging of its own");
 		return nullptr;
 	}
 	size_t off = s.stage_off;
 	for (int c = 0; c < comp; ++c)
 		off += mij_plane_elems((uint32_t)(s.desc.comp[c].bw * s.desc.comp[c].bh)) * sizeof(int16_t);
-	return reinterpret_cast<int16_t *>(b->stage + off);
+	return reinterpret_cast<int16_t *>(b->stage.h + off);
 }
 
 extern "C" uint8_t *mij_batch_stage_region(mij_batch *b, int slot, size_t *bytes)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size()) {
-		set_err(MIJ_E_ARG, "bad slot");
+	if (!batch_slot(b, slot))
 		return nullptr;
-	}
 	const Slot &s = b->slots[(size_t)slot];
-	if (s.clone_of >= 0 || !b->stage || s.stage_off == MIJ_NO_STAGE) {
+	if (s.clone_of >= 0 || !b->stage.h || s.stage_off == MIJ_NO_STAGE) {
 		set_err(MIJ_E_ARG, "slot has no staging of its own");
 		return nullptr;
 	}
 	if (bytes)
 		*bytes = s.coef_bytes;
-	return b->stage + s.stage_off;
+	return b->stage.h + s.stage_off;
 }
 
 extern "C" int mij_batch_coef_format(const mij_batch *b) { return b ? b->coef_fmt : MIJ_COEF_COMPACT; }
 extern "C" uint32_t mij_batch_slot_flags(const mij_batch *b, int slot)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size())
+	if (!batch_slot(b, slot))
 		return 0;
 	return b->slots[(size_t)slot].desc.flags;
 }
 
 extern "C" int mij_batch_set_flags(mij_batch *b, int slot, uint32_t flags)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size())
-		return set_err(MIJ_E_ARG, "bad slot");
+	if (!batch_slot(b, slot))
+		return MIJ_E_ARG;
 	b->slots[(size_t)slot].desc.flags = flags;
 	b->slots[(size_t)slot].dev.flags = (int32_t)flags | (b->slots[(size_t)slot].coef_bytes_fmt ? MIJ_DEV_COEF_BYTES : 0);
 	b->uploaded = b->launched = false;
@@ -789,8 +900,8 @@ static int scaled_layout(const mij_image_desc &d)
 
 extern "C" int mij_batch_set_scale(mij_batch *b, int slot, int denom)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size())
-		return set_err(MIJ_E_ARG, "mij_batch_set_scale: bad slot");
+	if (!batch_slot(b, slot, "mij_batch_set_scale: bad slot"))
+		return MIJ_E_ARG;
 	if (b->uploaded)
 		return set_err(MIJ_E_STATE, "mij_batch_set_scale after mij_batch_upload");
 	Slot &s = b->slots[(size_t)slot];
@@ -811,8 +922,8 @@ extern "C" int mij_batch_set_scale(mij_batch *b, int slot, int denom)
 
 extern "C" int mij_batch_slot_out_size(const mij_batch *b, int slot, int *w, int *h)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size())
-		return set_err(MIJ_E_ARG, "mij_batch_slot_out_size: bad slot");
+	if (!batch_slot(b, slot, "mij_batch_slot_out_size: bad slot"))
+		return MIJ_E_ARG;
 	const Slot &s = b->slots[(size_t)slot];
 	if (w)
 		*w = out_w(s);
@@ -827,8 +938,8 @@ static bool rect_inside(const int r[4], int W, int H) { return r[0] >= 0 && r[1]
 
 extern "C" int mij_batch_set_roi(mij_batch *b, int slot, int x0, int y0, int w, int h)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size())
-		return set_err(MIJ_E_ARG, "mij_batch_set_roi: bad slot");
+	if (!batch_slot(b, slot, "mij_batch_set_roi: bad slot"))
+		return MIJ_E_ARG;
 	if (b->uploaded)
 		return set_err(MIJ_E_STATE, "mij_batch_set_roi after mij_batch_upload");
 	Slot &s = b->slots[(size_t)slot];
@@ -850,8 +961,8 @@ extern "C" int mij_batch_set_roi(mij_batch *b, int slot, int x0, int y0, int w, 
 
 extern "C" int mij_batch_set_roi_auto(mij_batch *b, int slot, int on)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size())
-		return set_err(MIJ_E_ARG, "mij_batch_set_roi_auto: bad slot");
+	if (!batch_slot(b, slot, "mij_batch_set_roi_auto: bad slot"))
+		return MIJ_E_ARG;
 	if (b->uploaded)
 		return set_err(MIJ_E_STATE, "mij_batch_set_roi_auto after mij_batch_upload");
 	Slot &s = b->slots[(size_t)slot];
@@ -865,7 +976,7 @@ extern "C" int mij_batch_set_roi_auto(mij_batch *b, int slot, int on)
 
 extern "C" int mij_batch_slot_roi_rect(const mij_batch *b, int slot, int rect[4])
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size() || !rect)
+	if (!rect || !batch_slot(b, slot))
 		return set_err(MIJ_E_ARG, "mij_batch_slot_roi_rect: bad slot or destination");
 	if (!b->uploaded)
 		return set_err(MIJ_E_STATE, "mij_batch_slot_roi_rect before mij_batch_upload");
@@ -882,8 +993,8 @@ extern "C" int mij_batch_slot_roi_rect(const mij_batch *b, int slot, int rect[4]
 
 extern "C" int mij_batch_slot_work_items(const mij_batch *b, int slot)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size())
-		return set_err(MIJ_E_ARG, "mij_batch_slot_work_items: bad slot");
+	if (!batch_slot(b, slot, "mij_batch_slot_work_items: bad slot"))
+		return MIJ_E_ARG;
 	if (!b->uploaded)
 		return set_err(MIJ_E_STATE, "mij_batch_slot_work_items before mij_batch_upload");
 	return b->slots[(size_t)slot].work_items;
@@ -891,8 +1002,8 @@ extern "C" int mij_batch_slot_work_items(const mij_batch *b, int slot)
 
 extern "C" int mij_batch_slot_kernel(const mij_batch *b, int slot, int *kind, int *variant, int *segments)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size())
-		return set_err(MIJ_E_ARG, "mij_batch_slot_kernel: bad slot");
+	if (!batch_slot(b, slot, "mij_batch_slot_kernel: bad slot"))
+		return MIJ_E_ARG;
 	if (!b->uploaded)
 		return set_err(MIJ_E_STATE, "mij_batch_slot_kernel before mij_batch_upload");
 	const Choice &c = b->slots[(size_t)slot].choice;
@@ -908,8 +1019,8 @@ extern "C" int mij_batch_slot_kernel(const mij_batch *b, int slot, int *kind, in
 /* tests: 1 when the launch that decodes the slot runs the pipelined twin of its kernel (band_prefetch on its list's LDS), 0 when the plain one */
 extern "C" int mij_batch_slot_pipelined(const mij_batch *b, int slot)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size())
-		return set_err(MIJ_E_ARG, "mij_batch_slot_pipelined: bad slot");
+	if (!batch_slot(b, slot, "mij_batch_slot_pipelined: bad slot"))
+		return MIJ_E_ARG;
 	if (!b->uploaded)
 		return set_err(MIJ_E_STATE, "mij_batch_slot_pipelined before mij_batch_upload");
 	const Choice &c = b->slots[(size_t)slot].choice;
@@ -922,8 +1033,8 @@ extern "C" int mij_batch_slot_pipelined(const mij_batch *b, int slot)
 /* tests: 1 when that launch runs the twin whose phase B marches down its lanes' own strips (band_march), 0 otherwise */
 extern "C" int mij_batch_slot_marched(const mij_batch *b, int slot)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size())
-		return set_err(MIJ_E_ARG, "mij_batch_slot_marched: bad slot");
+	if (!batch_slot(b, slot, "mij_batch_slot_marched: bad slot"))
+		return MIJ_E_ARG;
 	if (!b->uploaded)
 		return set_err(MIJ_E_STATE, "mij_batch_slot_marched before mij_batch_upload");
 	const Choice &c = b->slots[(size_t)slot].choice;
@@ -935,8 +1046,8 @@ extern "C" int mij_batch_slot_marched(const mij_batch *b, int slot)
 
 extern "C" int mij_batch_set_color(mij_batch *b, int slot, int color)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size())
-		return set_err(MIJ_E_ARG, "bad slot");
+	if (!batch_slot(b, slot))
+		return MIJ_E_ARG;
 	Slot &s = b->slots[(size_t)slot];
 	mij_image_desc d = s.desc;
 	d.color = color;
@@ -953,7 +1064,7 @@ extern "C" int mij_batch_set_color(mij_batch *b, int slot, int color)
 
 extern "C" int mij_batch_set_dequant(mij_batch *b, int slot, const mij_image_desc *from)
 {
-	if (!b || !from || slot < 0 || slot >= (int)b->slots.size())
+	if (!from || !batch_slot(b, slot))
 		return set_err(MIJ_E_ARG, "mij_batch_set_dequant: bad slot or descriptor");
 	Slot &s = b->slots[(size_t)slot];
 	if (from->ncomp != s.desc.ncomp)
@@ -978,7 +1089,7 @@ extern "C" int mij_batch_set_dequant(mij_batch *b, int slot, const mij_image_des
 extern "C" int mij_batch_image_count(const mij_batch *b) { return b ? (int)b->slots.size() : 0; }
 extern "C" int mij_batch_slot_path(const mij_batch *b, int slot)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size())
+	if (!batch_slot(b, slot))
 		return 0;
 	return b->slots[(size_t)slot].choice.path;
 }
@@ -1159,33 +1270,17 @@ static hipError_t copy_table_to_host(void *dst_pinned, const void *src_dev, size
 	return hipGetLastError();
 }
 
-template <typename T>
-static int grow_pair(T *&h, T *&d, size_t &cap, size_t need)
-{
-	if (need <= cap)
-		return MIJ_OK;
-	size_t ncap = need + need / 2 + 64;
-	free_host(h);
-	free_dev(d);
-	cap = 0;
-	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h), sizeof(T) * ncap, hipHostMallocDefault));
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof(T) * ncap));
-	cap = ncap;
-	return MIJ_OK;
-}
-
-/* Puts an output pass's plan of `need` bytes on the device: grows the buffer pair (waiting for the stream first, whose launches may
+/* Puts an output pass's plan of `need` bytes on the device: grows the buffer (Grow waits for the stream first, whose launches may
  * still read the old one), lets fill write the pinned side, copies it up on the batch stream, and records the items and offsets. */
 template <typename Fill>
 static int plan_put(mij_batch *b, PlanBuf &p, size_t need, size_t items, size_t lut_at, size_t work_at, Fill fill)
 {
-	if (need > p.cap)
-		HIP_TRY(hipStreamSynchronize(b->stream));
-	int rc = grow_pair(p.h, p.d, p.cap, align_up(need, 4));
-	if (rc != MIJ_OK)
-		return rc;
-	fill(p.h);
-	HIP_TRY(copy_table(p.d, p.h, align_up(need, 4), b->stream));
+	Grow grow(b->stream);
+	grow(p.buf, align_up(need, 4));
+	if (grow.rc != MIJ_OK)
+		return grow.rc;
+	fill(p.buf.h);
+	HIP_TRY(copy_table(p.buf.d, p.buf.h, align_up(need, 4), b->stream));
 	p.items = items;
 	p.lut_at = lut_at;
 	p.work_at = work_at;
@@ -1405,8 +1500,8 @@ static int plane_formats(mij_batch *b)
 		if (host_staged(s) && s.coef_bytes_fmt && !(s.desc.flags & MIJ_FLAG_STAGED_COMPACT))
 			need_pack = true;
 	}
-	if (need_pack && !b->d_up16) {
-		hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_up16), b->stage_cap ? b->stage_cap : 16);
+	if (need_pack && !b->up16.d) {
+		hipError_t e = b->up16.alloc(b->stage.cap);
 		if (e != hipSuccess)
 			return set_err(e == hipErrorOutOfMemory ? MIJ_E_NOMEM : MIJ_E_HIP, "upload scratch: %s", hipGetErrorString(e));
 	}
@@ -1425,42 +1520,39 @@ static int l1_prepack(mij_batch *b)
 			push_tiles(pre, (uint32_t)i, b->slots[i].desc);
 	if (pre.empty())
 		return MIJ_OK;
-	if (!b->d_l1max) {
-		HIP_TRY(hipMalloc(reinterpret_cast<void **>(&b->d_l1max), sizeof(uint32_t) * (size_t)b->max_images));
-		HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&b->h_l1max), sizeof(uint32_t) * (size_t)b->max_images, hipHostMallocDefault));
-	}
-	if (pre.size() > b->work_cap)
-		HIP_TRY(hipStreamSynchronize(b->stream));
-	int rc = grow_pair(b->h_work, b->d_work, b->work_cap, pre.size());
-	if (rc != MIJ_OK)
-		return rc;
-	memcpy(b->h_work, pre.data(), pre.size() * sizeof(Work4));
+	if (!b->l1max.cap) /* a failure leaves cap 0: the next upload tries again */
+		HIP_TRY(b->l1max.alloc((size_t)b->max_images));
+	Grow grow(b->stream);
+	grow(b->work, pre.size());
+	if (grow.rc != MIJ_OK)
+		return grow.rc;
+	memcpy(b->work.h, pre.data(), pre.size() * sizeof(Work4));
 	for (size_t i = 0; i < n; ++i) {
 		Slot &s = b->slots[i];
 		s.dev.src16_off = s.stage_off == MIJ_NO_STAGE ? 0 : s.stage_off;
-		b->h_imgs[i] = s.dev;
+		b->imgs.h[i] = s.dev;
 		if (host_staged(s) && (s.desc.flags & MIJ_FLAG_L1_ON_DEVICE))
-			b->h_imgs[i].flags |= MIJ_DEV_L1_MAX;
+			b->imgs.h[i].flags |= MIJ_DEV_L1_MAX;
 	}
-	HIP_TRY(copy_table(b->d_imgs, b->h_imgs, sizeof(DevImage) * n, b->stream));
-	HIP_TRY(copy_table(b->d_work, b->h_work, sizeof(Work4) * pre.size(), b->stream));
-	HIP_TRY(hipMemsetAsync(b->d_l1max, 0, sizeof(uint32_t) * n, b->stream));
+	HIP_TRY(copy_table(b->imgs.d, b->imgs.h, sizeof(DevImage) * n, b->stream));
+	HIP_TRY(copy_table(b->work.d, b->work.h, sizeof(Work4) * pre.size(), b->stream));
+	HIP_TRY(hipMemsetAsync(b->l1max.d, 0, sizeof(uint32_t) * n, b->stream));
 	for (const Slot &s : b->slots)
 		if (l1_on_device(s)) {
 			size_t bytes16 = 0;
 			for (int c = 0; c < s.desc.ncomp; ++c)
 				bytes16 += comp_tiles(s.desc.comp[c]) << 13;
-			HIP_TRY(hipMemcpyAsync(b->d_up16 + s.stage_off, b->stage + s.stage_off, bytes16, hipMemcpyHostToDevice, b->stream));
+			HIP_TRY(hipMemcpyAsync(b->up16.d + s.stage_off, b->stage.h + s.stage_off, bytes16, hipMemcpyHostToDevice, b->stream));
 		}
-	hipLaunchKernelGGL(k_pack_c8, dim3((unsigned)pre.size()), dim3(256), 0, b->stream, b->d_imgs, reinterpret_cast<const WorkIdct *>(b->d_work), b->d_up16, b->d_coef, b->d_l1max);
+	hipLaunchKernelGGL(k_pack_c8, dim3((unsigned)pre.size()), dim3(256), 0, b->stream, b->imgs.d, reinterpret_cast<const WorkIdct *>(b->work.d), b->up16.d, b->coef.d, b->l1max.d);
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(copy_table_to_host(b->h_l1max, b->d_l1max, sizeof(uint32_t) * n, b->stream));
+	HIP_TRY(copy_table_to_host(b->l1max.h, b->l1max.d, sizeof(uint32_t) * n, b->stream));
 	HIP_TRY(hipStreamSynchronize(b->stream));
 	for (size_t i = 0; i < n; ++i) {
 		Slot &s = b->slots[i];
 		if (l1_on_device(s)) {
 			s.desc.flags &= ~(uint32_t)MIJ_FLAG_L1_ON_DEVICE;
-			if (b->h_l1max[i] > (uint32_t)MIJ_BLOCK_L1_LIMIT)
+			if (b->l1max.h[i] > (uint32_t)MIJ_BLOCK_L1_LIMIT)
 				s.desc.flags |= MIJ_FLAG_WIDE_IDCT;
 			s.dev.flags = (int32_t)s.desc.flags | MIJ_DEV_COEF_BYTES;
 			s.dev_coef = 1;
@@ -1740,16 +1832,11 @@ static void plan_decode(mij_batch *b, Plan &p)
 /* scratch planes for the two-pass path */
 static int scratch_planes(mij_batch *b, size_t need)
 {
-	if (need <= b->planes_cap)
-		return MIJ_OK;
-	HIP_TRY(hipStreamSynchronize(b->stream));
-	free_dev(b->d_planes);
-	b->planes_cap = 0;
-	hipError_t e = hipMalloc(reinterpret_cast<void **>(&b->d_planes), need);
-	if (e != hipSuccess)
-		return set_err(e == hipErrorOutOfMemory ? MIJ_E_NOMEM : MIJ_E_HIP, "scratch planes: %s", hipGetErrorString(e));
-	b->planes_cap = need;
-	return MIJ_OK;
+	Grow grow(b->stream);
+	grow.exact(b->planes, need);
+	if (grow.hip != hipSuccess)
+		return set_err(grow.hip == hipErrorOutOfMemory ? MIJ_E_NOMEM : MIJ_E_HIP, "scratch planes: %s", hipGetErrorString(grow.hip));
+	return grow.rc;
 }
 
 /* Whether a launch takes k_fused420m where it would take k_fused420p: every picture of its list has rows of whole dwords (RGBA, or a width
@@ -1778,40 +1865,39 @@ static int lay_out_work(mij_batch *b, const Plan &p)
 	for (const auto &family : p.lists)
 		for (const std::vector<Work4> &L : family)
 			total += L.size();
-	if (total > b->work_cap)
-		HIP_TRY(hipStreamSynchronize(b->stream));
-	int rc = grow_pair(b->h_work, b->d_work, b->work_cap, total);
-	if (rc != MIJ_OK)
-		return rc;
+	Grow grow(b->stream);
+	grow(b->work, total);
+	if (grow.rc != MIJ_OK)
+		return grow.rc;
 	b->launches.clear();
 	if (!p.pack.empty())
-		memcpy(b->h_work, p.pack.data(), p.pack.size() * sizeof(Work4));
+		memcpy(b->work.h, p.pack.data(), p.pack.size() * sizeof(Work4));
 	size_t pos = p.pack.size();
 	for (int k = 0; k < MK_KINDS; ++k)
 		for (int v = 0; v < MK_VARIANTS; ++v) {
 			const std::vector<Work4> &L = p.lists[k][v];
 			if (L.empty())
 				continue;
-			memcpy(b->h_work + pos, L.data(), L.size() * sizeof(Work4));
+			memcpy(b->work.h + pos, L.data(), L.size() * sizeof(Work4));
 			b->launches.push_back(mij_batch::Launch{k, v, pos, L.size(), p.lds[k][v], band_march(b, k, v, p.lds[k][v], L)});
 			pos += L.size();
 		}
 	const size_t n = b->slots.size();
 	for (size_t i = 0; i < n; ++i)
-		b->h_imgs[i] = b->slots[i].dev;
-	HIP_TRY(copy_table(b->d_imgs, b->h_imgs, sizeof(DevImage) * n, b->stream));
+		b->imgs.h[i] = b->slots[i].dev;
+	HIP_TRY(copy_table(b->imgs.d, b->imgs.h, sizeof(DevImage) * n, b->stream));
 	bool windowed = false;
 	for (const mij_batch::Launch &l : b->launches)
 		windowed = windowed || families[l.kind].roi;
 	if (windowed) { /* the windows of the slots the windowed kernels decode; the others' entries are never read */
-		if (!b->h_roi && (rc = grow_pair(b->h_roi, b->d_roi, b->roi_cap, (size_t)b->max_images)) != MIJ_OK)
-			return rc;
+		if (!b->roi.cap)
+			HIP_TRY(b->roi.alloc((size_t)b->max_images));
 		for (size_t i = 0; i < n; ++i)
-			b->h_roi[i] = b->slots[i].reg ? b->slots[i].win : DevRoi{0u, 0u, 0u, 0u};
-		HIP_TRY(copy_table(b->d_roi, b->h_roi, sizeof(DevRoi) * n, b->stream));
+			b->roi.h[i] = b->slots[i].reg ? b->slots[i].win : DevRoi{0u, 0u, 0u, 0u};
+		HIP_TRY(copy_table(b->roi.d, b->roi.h, sizeof(DevRoi) * n, b->stream));
 	}
 	if (total)
-		HIP_TRY(copy_table(b->d_work, b->h_work, sizeof(Work4) * total, b->stream));
+		HIP_TRY(copy_table(b->work.d, b->work.h, sizeof(Work4) * total, b->stream));
 	return MIJ_OK;
 }
 
@@ -1838,12 +1924,12 @@ static int copy_coefficients(mij_batch *b)
 					bytes += b->slots[j].coef_bytes;
 					++j;
 				}
-				HIP_TRY(hipMemcpyAsync(b->d_coef + sc.coef_base, b->stage + sc.stage_off, bytes, hipMemcpyHostToDevice, b->stream));
+				HIP_TRY(hipMemcpyAsync(b->coef.d + sc.coef_base, b->stage.h + sc.stage_off, bytes, hipMemcpyHostToDevice, b->stream));
 				i = j;
 				continue;
 			}
 			const size_t main_bytes = mij_compact_main_bytes(&sc.desc);
-			HIP_TRY(hipMemcpyAsync(b->d_coef + sc.coef_base, b->stage + sc.stage_off, (sc.desc.flags & MIJ_FLAG_HAS_ESCAPES) ? sc.coef_bytes : main_bytes, hipMemcpyHostToDevice, b->stream));
+			HIP_TRY(hipMemcpyAsync(b->coef.d + sc.coef_base, b->stage.h + sc.stage_off, (sc.desc.flags & MIJ_FLAG_HAS_ESCAPES) ? sc.coef_bytes : main_bytes, hipMemcpyHostToDevice, b->stream));
 			++i;
 			continue;
 		}
@@ -1855,7 +1941,7 @@ static int copy_coefficients(mij_batch *b)
 			bytes += b->slots[j].coef_bytes;
 			++j;
 		}
-		HIP_TRY(hipMemcpyAsync(fmt ? b->d_up16 + s0 : b->d_coef + c0, b->stage + s0, bytes, hipMemcpyHostToDevice, b->stream));
+		HIP_TRY(hipMemcpyAsync(fmt ? b->up16.d + s0 : b->coef.d + c0, b->stage.h + s0, bytes, hipMemcpyHostToDevice, b->stream));
 		i = j;
 	}
 	return MIJ_OK;
@@ -1872,7 +1958,7 @@ static int launch_pack(mij_batch *b, size_t items)
 		HIP_TRY(hipEventCreate(&b->ev_pack1));
 	}
 	HIP_TRY(hipEventRecord(b->ev_pack0, b->stream));
-	hipLaunchKernelGGL(k_pack_c8, dim3((unsigned)items), dim3(256), 0, b->stream, b->d_imgs, reinterpret_cast<const WorkIdct *>(b->d_work), b->d_up16, b->d_coef, b->d_l1max);
+	hipLaunchKernelGGL(k_pack_c8, dim3((unsigned)items), dim3(256), 0, b->stream, b->imgs.d, reinterpret_cast<const WorkIdct *>(b->work.d), b->up16.d, b->coef.d, b->l1max.d);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(b->ev_pack1, b->stream));
 	b->pack_timed = true;
@@ -1884,7 +1970,7 @@ static int copy_clones(mij_batch *b)
 {
 	for (const Slot &s : b->slots)
 		if (s.clone_of >= 0)
-			HIP_TRY(hipMemcpyAsync(b->d_coef + s.coef_base, b->d_coef + b->slots[(size_t)s.clone_of].coef_base, s.coef_bytes, hipMemcpyDeviceToDevice, b->stream));
+			HIP_TRY(hipMemcpyAsync(b->coef.d + s.coef_base, b->coef.d + b->slots[(size_t)s.clone_of].coef_base, s.coef_bytes, hipMemcpyDeviceToDevice, b->stream));
 	return MIJ_OK;
 }
 
@@ -1923,8 +2009,8 @@ static int launch_out_pass(mij_batch *b, const PlanBuf &p, void (*kernel)(const 
 {
 	if (!p.items)
 		return MIJ_OK;
-	hipLaunchKernelGGL(kernel, dim3((unsigned)p.items), dim3(256), 0, b->stream, reinterpret_cast<const Dev *>(p.d), reinterpret_cast<const Work *>(p.d + p.work_at),
-							 reinterpret_cast<const Lut *>(p.d + p.lut_at), tail...);
+	hipLaunchKernelGGL(kernel, dim3((unsigned)p.items), dim3(256), 0, b->stream, reinterpret_cast<const Dev *>(p.buf.d), reinterpret_cast<const Work *>(p.buf.d + p.work_at),
+							 reinterpret_cast<const Lut *>(p.buf.d + p.lut_at), tail...);
 	HIP_TRY(hipGetLastError());
 	return MIJ_OK;
 }
@@ -1938,10 +2024,10 @@ extern "C" int mij_batch_launch(mij_batch *b)
 	HIP_TRY(hipSetDevice(b->ctx->device));
 	for (const auto &L : b->launches) { /* in family order: pass 2 of the two-pass family runs behind every pass-1 launch */
 		const Family &f = families[L.kind];
-		const Work4 *wk = b->d_work + L.first;
-		const uint8_t *in = f.io == PLANES_OUT ? b->d_planes : b->d_coef;
-		uint8_t *out = f.io == COEF_PLANES ? b->d_planes : b->d_out;
-		void *args4[] = {&b->d_imgs, &wk, &in, &out}, *args5[] = {&b->d_imgs, &wk, &in, &out, &b->d_roi}; /* the windowed forms take the table of windows */
+		const Work4 *wk = b->work.d + L.first;
+		const uint8_t *in = f.io == PLANES_OUT ? b->planes.d : b->coef.d;
+		uint8_t *out = f.io == COEF_PLANES ? b->planes.d : b->out.d;
+		void *args4[] = {&b->imgs.d, &wk, &in, &out}, *args5[] = {&b->imgs.d, &wk, &in, &out, &b->roi.d}; /* the windowed forms take the table of windows */
 		const void *k = L.marched ? k420_march[L.var] : (band_prefetch(L.kind, L.var, L.lds, (size_t)b->ctx->max_dyn_lds) ? k420_prefetch[L.var] : f.k[L.var]);
 		(void)hipLaunchKernel(k, dim3((unsigned)L.count), dim3(f.threads), f.roi ? args5 : args4, L.lds, b->stream);
 		HIP_TRY(hipGetLastError());
@@ -1949,10 +2035,10 @@ extern "C" int mij_batch_launch(mij_batch *b)
 	/* the output passes, behind every decode family (both front ends end here): float output, tensor output into the callers' memory,
 	 * resized tensor output, then the transposed (oriented 5..8) forms of the last two */
 	int rc;
-	if ((rc = launch_out_pass(b, b->f32plan, k_out_f32, b->d_out, b->d_f32)) != MIJ_OK || (rc = launch_out_pass(b, b->tenplan, k_out_tensor, b->d_out)) != MIJ_OK ||
-		 (rc = launch_out_pass(b, b->rszplan, k_out_resize, b->rszplan.d, b->d_out)) != MIJ_OK ||
-		 (rc = launch_out_pass(b, b->tentplan, k_out_tensor_t, b->d_out)) != MIJ_OK ||
-		 (rc = launch_out_pass(b, b->rsztplan, k_out_resize_t, b->rsztplan.d, b->d_out)) != MIJ_OK)
+	if ((rc = launch_out_pass(b, b->f32plan, k_out_f32, b->out.d, b->f32.d)) != MIJ_OK || (rc = launch_out_pass(b, b->tenplan, k_out_tensor, b->out.d)) != MIJ_OK ||
+		 (rc = launch_out_pass(b, b->rszplan, k_out_resize, b->rszplan.buf.d, b->out.d)) != MIJ_OK ||
+		 (rc = launch_out_pass(b, b->tentplan, k_out_tensor_t, b->out.d)) != MIJ_OK ||
+		 (rc = launch_out_pass(b, b->rsztplan, k_out_resize_t, b->rsztplan.buf.d, b->out.d)) != MIJ_OK)
 		return rc;
 	b->launched = true;
 	return MIJ_OK;
@@ -1977,7 +2063,7 @@ extern "C" int mij_batch_wait(mij_batch *b)
 
 extern "C" int mij_batch_fetch(mij_batch *b, int slot, uint8_t *dst, size_t dst_bytes)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size() || !dst)
+	if (!dst || !batch_slot(b, slot))
 		return set_err(MIJ_E_ARG, "bad slot or destination");
 	if (!b->launched)
 		return set_err(MIJ_E_STATE, "mij_batch_fetch before launch");
@@ -1988,7 +2074,7 @@ extern "C" int mij_batch_fetch(mij_batch *b, int slot, uint8_t *dst, size_t dst_
 	if (dst_bytes < bytes)
 		return set_err(MIJ_E_ARG, "destination too small (%zu < %zu)", dst_bytes, bytes);
 	HIP_TRY(hipSetDevice(b->ctx->device));
-	return d2h_bounced(b->ctx, b->stream, dst, b->d_out + s.dev.out_off, bytes);
+	return d2h_bounced(b->ctx, b->stream, dst, b->out.d + s.dev.out_off, bytes);
 }
 
 extern "C" int mij_batch_fetch_all_async(mij_batch *b, uint8_t *dst, size_t dst_bytes)
@@ -2001,13 +2087,13 @@ extern "C" int mij_batch_fetch_all_async(mij_batch *b, uint8_t *dst, size_t dst_
 		return set_err(MIJ_E_ARG, "destination too small (%zu < %zu)", dst_bytes, b->out_used);
 	HIP_TRY(hipSetDevice(b->ctx->device));
 	if (b->out_used)
-		HIP_TRY(hipMemcpyAsync(dst, b->d_out, b->out_used, hipMemcpyDeviceToHost, b->stream));
+		HIP_TRY(hipMemcpyAsync(dst, b->out.d, b->out_used, hipMemcpyDeviceToHost, b->stream));
 	return MIJ_OK;
 }
 
 extern "C" size_t mij_batch_out_offset(const mij_batch *b, int slot)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size())
+	if (!batch_slot(b, slot))
 		return (size_t)-1;
 	return (size_t)b->slots[(size_t)slot].dev.out_off;
 }
@@ -2033,9 +2119,9 @@ extern "C" void mij_host_free(void *p)
 
 extern "C" void *mij_batch_device_out(mij_batch *b, int slot)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size())
+	if (!batch_slot(b, slot))
 		return nullptr;
-	return b->d_out + b->slots[(size_t)slot].dev.out_off;
+	return b->out.d + b->slots[(size_t)slot].dev.out_off;
 }
 
 /* ------------------------------------------------------------------ float output */
@@ -2046,7 +2132,7 @@ extern "C" int mij_batch_out_f32_reserve(mij_batch *b, size_t bytes)
 {
 	if (!b || !bytes)
 		return set_err(MIJ_E_ARG, "mij_batch_out_f32_reserve: bad argument");
-	if (bytes <= b->f32_cap)
+	if (bytes <= b->f32.cap)
 		return MIJ_OK;
 	if (!b->f32_req.empty())
 		return set_err(MIJ_E_STATE, "mij_batch_out_f32_reserve: slots hold float requests (reset the batch first)");
@@ -2054,27 +2140,24 @@ extern "C" int mij_batch_out_f32_reserve(mij_batch *b, size_t bytes)
 	HIP_TRY(hipStreamSynchronize(b->stream));
 	/* the new arena first, so that a failure leaves the old one in place; only when memory is short does the old one go first */
 	const size_t cap = align_up(bytes, 256);
-	uint8_t *p = nullptr;
-	hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), cap);
-	if (e == hipErrorOutOfMemory && b->d_f32) {
+	Buf<uint8_t, BUF_ON_DEVICE> arena;
+	hipError_t e = arena.alloc(cap);
+	if (e == hipErrorOutOfMemory && b->f32.d) {
 		(void)hipGetLastError();
-		free_dev(b->d_f32);
-		b->f32_cap = 0;
-		e = hipMalloc(reinterpret_cast<void **>(&p), cap);
+		b->f32.release();
+		e = arena.alloc(cap);
 	}
 	if (e != hipSuccess) {
 		(void)hipGetLastError();
 		return set_err(e == hipErrorOutOfMemory ? MIJ_E_NOMEM : MIJ_E_HIP, "mij_batch_out_f32_reserve: %s", hipGetErrorString(e));
 	}
-	free_dev(b->d_f32);
-	b->d_f32 = p;
-	b->f32_cap = cap;
+	b->f32 = std::move(arena); /* arena takes the old one and releases it */
 	return MIJ_OK;
 }
 
 extern "C" int mij_batch_set_out_f32(mij_batch *b, int slot, const float *lut)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size() || !lut)
+	if (!lut || !batch_slot(b, slot))
 		return set_err(MIJ_E_ARG, "mij_batch_set_out_f32: bad slot or table");
 	if (b->uploaded)
 		return set_err(MIJ_E_STATE, "mij_batch_set_out_f32 after mij_batch_upload");
@@ -2087,8 +2170,8 @@ extern "C" int mij_batch_set_out_f32(mij_batch *b, int slot, const float *lut)
 		return set_err(MIJ_E_ARG, "mij_batch_set_out_f32: slot %d decodes a region only; float output of a region is not supported", slot);
 	if (s.f32 < 0) {
 		const size_t need = mij_image_out_f32_bytes(&s.desc);
-		if (!b->d_f32 || b->f32_used + need > b->f32_cap)
-			return set_err(MIJ_E_ARG, "float arena too small (%zu of %zu bytes used, %zu needed; mij_batch_out_f32_reserve)", b->f32_used, b->f32_cap, need);
+		if (!b->f32.d || b->f32_used + need > b->f32.cap)
+			return set_err(MIJ_E_ARG, "float arena too small (%zu of %zu bytes used, %zu needed; mij_batch_out_f32_reserve)", b->f32_used, b->f32.cap, need);
 		mij_batch::F32Req q;
 		q.slot = slot;
 		q.off = b->f32_used;
@@ -2104,7 +2187,7 @@ extern "C" int mij_batch_set_out_f32(mij_batch *b, int slot, const float *lut)
 
 extern "C" int mij_batch_fetch_f32(mij_batch *b, int slot, float *dst, size_t dst_elems)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size() || !dst)
+	if (!dst || !batch_slot(b, slot))
 		return set_err(MIJ_E_ARG, "bad slot or destination");
 	const Slot &s = b->slots[(size_t)slot];
 	if (s.f32 < 0)
@@ -2117,14 +2200,15 @@ extern "C" int mij_batch_fetch_f32(mij_batch *b, int slot, float *dst, size_t ds
 	if (dst_elems < elems)
 		return set_err(MIJ_E_ARG, "destination too small (%zu < %zu floats)", dst_elems, elems);
 	HIP_TRY(hipSetDevice(b->ctx->device));
-	return d2h_bounced(b->ctx, b->stream, dst, b->d_f32 + b->f32_req[(size_t)s.f32].off, elems * sizeof(float));
+	return d2h_bounced(b->ctx, b->stream, dst, b->f32.d + b->f32_req[(size_t)s.f32].off, elems * sizeof(float));
 }
 
 extern "C" void *mij_batch_device_out_f32(mij_batch *b, int slot)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size() || b->slots[(size_t)slot].f32 < 0)
+	const Slot *s = batch_slot(b, slot);
+	if (!s || s->f32 < 0)
 		return nullptr;
-	return b->d_f32 + b->f32_req[(size_t)b->slots[(size_t)slot].f32].off;
+	return b->f32.d + b->f32_req[(size_t)s->f32].off;
 }
 
 /* ------------------------------------------------------------------ tensor output */
@@ -2221,7 +2305,7 @@ static const uint8_t orient_tr[9] = {0, 0, 0, 0, 0, 1, 1, 1, 1}, orient_mx[9] = 
 
 static int set_out_tensor(mij_batch *b, int slot, const mij_out_tensor *t, const mij_out_resize *rz, int32_t orient, const void *table)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size() || !t)
+	if (!t || !batch_slot(b, slot))
 		return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor: bad slot or request");
 	if (b->uploaded)
 		return set_err(MIJ_E_STATE, "mij_batch_set_out_tensor after mij_batch_upload");
@@ -2368,7 +2452,7 @@ extern "C" int mij_batch_pack_ms(mij_batch *b, float *ms)
 
 extern "C" int mij_batch_hash_out(mij_batch *b, int slot, uint64_t *hash)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size() || !hash)
+	if (!hash || !batch_slot(b, slot))
 		return set_err(MIJ_E_ARG, "bad argument");
 	const Slot &s = b->slots[(size_t)slot];
 	if (wants_region(s))
@@ -2414,141 +2498,40 @@ extern "C" int mij_batch_diff_slots(mij_batch *b, const int *sa, const int *sb, 
 	if (!b->launched)
 		return set_err(MIJ_E_STATE, "mij_batch_diff_slots before launch");
 	HIP_TRY(hipSetDevice(b->ctx->device));
-	unsigned long long *d_cnt = nullptr, h_cnt = 0;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_cnt), sizeof(unsigned long long)));
-	hipError_t e = hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), b->stream);
+	Buf<unsigned long long, BUF_ON_DEVICE> cnt; /* freed on every way out (hipFree waits for the kernels queued so far) */
+	unsigned long long h_cnt = 0;
+	HIP_TRY(cnt.alloc(1));
+	hipError_t e = hipMemsetAsync(cnt.d, 0, sizeof(unsigned long long), b->stream);
 	for (int i = 0; i < n && e == hipSuccess; ++i) {
-		if (sa[i] < 0 || sb[i] < 0 || sa[i] >= (int)b->slots.size() || sb[i] >= (int)b->slots.size()) {
-			(void)hipFree(d_cnt);
+		if (!batch_slot(b, sa[i]) || !batch_slot(b, sb[i]))
 			return set_err(MIJ_E_ARG, "bad slot pair %d", i);
-		}
 		const Slot &x = b->slots[(size_t)sa[i]], &y = b->slots[(size_t)sb[i]];
-		if (wants_region(x) || wants_region(y)) {
-			(void)hipFree(d_cnt);
+		if (wants_region(x) || wants_region(y))
 			return set_err(MIJ_E_STATE, "mij_batch_diff_slots: slot pair %d: a slot that decodes a region only cannot be compared", i);
-		}
 		/* a reduced picture leaves the rest of its region unwritten: its last, partial word is compared byte by byte */
 		const bool exact = x.scale > 1 || y.scale > 1;
 		const size_t px = out_px_bytes(x), bytes = exact ? px & ~(size_t)15 : align_up(px, 16);
-		if (exact ? px != out_px_bytes(y) : bytes != align_up(out_px_bytes(y), 16)) {
-			(void)hipFree(d_cnt);
+		if (exact ? px != out_px_bytes(y) : bytes != align_up(out_px_bytes(y), 16))
 			return set_err(MIJ_E_ARG, "slot pair %d: different sizes", i);
-		}
 		if (exact && px > bytes)
-			hipLaunchKernelGGL(k_count_diff_tail, dim3(1), dim3(64), 0, b->stream, b->d_out + x.dev.out_off + bytes, b->d_out + y.dev.out_off + bytes, (uint32_t)(px - bytes), d_cnt);
+			hipLaunchKernelGGL(k_count_diff_tail, dim3(1), dim3(64), 0, b->stream, b->out.d + x.dev.out_off + bytes, b->out.d + y.dev.out_off + bytes, (uint32_t)(px - bytes), cnt.d);
 		/* outputs are 256-byte aligned and padded in the arena, so whole 16-byte words may be compared */
-		hipLaunchKernelGGL(k_count_diff, dim3(1024), dim3(256), 0, b->stream, reinterpret_cast<const uint4 *>(b->d_out + x.dev.out_off),
-								 reinterpret_cast<const uint4 *>(b->d_out + y.dev.out_off), (uint32_t)(bytes / 16), d_cnt);
+		hipLaunchKernelGGL(k_count_diff, dim3(1024), dim3(256), 0, b->stream, reinterpret_cast<const uint4 *>(b->out.d + x.dev.out_off),
+								 reinterpret_cast<const uint4 *>(b->out.d + y.dev.out_off), (uint32_t)(bytes / 16), cnt.d);
 		e = hipGetLastError();
 	}
-	int rc_copy = MIJ_OK;
-	if (e == hipSuccess)
-		rc_copy = d2h_bounced(b->ctx, b->stream, &h_cnt, d_cnt, sizeof(h_cnt));
-	else
+	if (e != hipSuccess) {
 		(void)hipStreamSynchronize(b->stream);
-	(void)hipFree(d_cnt);
-	if (e != hipSuccess)
 		return set_err(MIJ_E_HIP, "mij_batch_diff_slots: %s", hipGetErrorString(e));
-	if (rc_copy != MIJ_OK)
-		return rc_copy;
+	}
+	const int rc = d2h_bounced(b->ctx, b->stream, &h_cnt, cnt.d, sizeof(h_cnt));
+	if (rc != MIJ_OK)
+		return rc;
 	*ndiff = (uint64_t)h_cnt;
 	return MIJ_OK;
 }
 
-/* ------------------------------------------------------------------ GPU entropy stage (mij_batch_entropy_*)
- *
- * See mij_entropy_kernels.h for the algorithm.  The arena holds everything the five kernels touch besides the
- * coefficient planes: the unstuffed streams, per-scan descriptors and Huffman tables, three state words and a
- * counter per subsequence, a DC difference and an L1 accumulator per block, and four verdict words per scan.
- */
-#include "mij_entropy_kernels.h"
-
-struct EsArena {
-	uint8_t *stage, *d_stream; /* pinned / device, stream_cap bytes */
-	size_t stream_cap;
-	DevScan *h_scans, *d_scans;
-	DevHuff *h_huff, *d_huff;
-	EsWork *h_work, *d_work;
-	size_t work_cap;
-	WorkIdct *h_pack, *d_pack; /* k_es_pack: (slot, component, first block) per 256 blocks of every compact-plane slot */
-	size_t pack_cap, pack_used;
-	uint64_t *d_start, *d_end[2]; /* d_end[0]: the cold pass's end states, d_end[1]: the current ones (first round on) */
-	uint4 *d_uni;          /* k_es_tables: one EsUni per table set */
-	uint4 *d_wtab;         /* ... and one EsW (the record-form write pass's tables) */
-	uint32_t *h_tabscan, *d_tabscan; /* table set -> a scan that uses it */
-	uint32_t *d_qidx[2];  /* the queues of k_es_syncq, alternating by round: subsequence ... */
-	uint64_t *d_qstate[2]; /* ... and the start state it has to run from; a scan's entries start at its sub_off */
-	uint32_t *d_cnt, *d_base;
-	size_t sub_cap;
-	uint32_t sub_bits; /* bits per subsequence of this arena's scans */
-	int rounds0;       /* synchronisation rounds queued before the first look at the verdicts */
-	uint64_t *d_meta; /* per block: L1 of its AC coefficients | DC difference << 32 */
-	uint8_t *d_zz; /* compact planes: the write pass's intermediate image, 64 bytes per block in zigzag order */
-	uint64_t *d_rec;  /* compact planes, record form (k_es_writer / k_es_pack2): rec_region64 eight-byte words per subsequence */
-	uint32_t rec_region64;
-	size_t rec_words;
-	bool use_records;
-	size_t blk_cap;
-	uint32_t *d_verdict, *h_verdict; /* [5][scan_cap]: anomaly, changed, total, l1max, final bit position */
-	uint32_t *d_rounds_changed, *h_rounds_changed; /* [MAX_ROUNDS] sum over scans, for tuning */
-	uint32_t *d_changed; /* [ES_MAX_ROUNDS][scan_cap]: subsequences moved per scan, one slice per synchronisation round -- cleared once per
-	                      * launch instead of once per round (a one-picture batch queues 24 rounds: 24 fewer commands per stbi_load call) */
-	std::vector<int> scan_slot; /* scan index -> batch slot */
-	size_t sub_used, blk_used, work_used, scan_cap, n_tabs;
-	int last_rounds, cur;
-	bool in_flight;
-};
-
-static const int ES_MAX_ROUNDS = 96;
-
-static void es_free(EsArena *e)
-{
-	if (!e)
-		return;
-	if (e->stage) (void)hipHostFree(e->stage);
-	if (e->d_stream) (void)hipFree(e->d_stream);
-	if (e->h_scans) (void)hipHostFree(e->h_scans);
-	if (e->d_scans) (void)hipFree(e->d_scans);
-	if (e->h_huff) (void)hipHostFree(e->h_huff);
-	if (e->d_huff) (void)hipFree(e->d_huff);
-	if (e->h_work) (void)hipHostFree(e->h_work);
-	if (e->d_work) (void)hipFree(e->d_work);
-	if (e->h_pack) (void)hipHostFree(e->h_pack);
-	if (e->d_pack) (void)hipFree(e->d_pack);
-	if (e->d_start) (void)hipFree(e->d_start);
-	if (e->d_end[0]) (void)hipFree(e->d_end[0]);
-	if (e->d_end[1]) (void)hipFree(e->d_end[1]);
-	if (e->d_uni) (void)hipFree(e->d_uni);
-	if (e->d_wtab) (void)hipFree(e->d_wtab);
-	if (e->h_tabscan) (void)hipHostFree(e->h_tabscan);
-	if (e->d_tabscan) (void)hipFree(e->d_tabscan);
-	for (int q = 0; q < 2; ++q) {
-		if (e->d_qidx[q]) (void)hipFree(e->d_qidx[q]);
-		if (e->d_qstate[q]) (void)hipFree(e->d_qstate[q]);
-	}
-	if (e->d_cnt) (void)hipFree(e->d_cnt);
-	if (e->d_base) (void)hipFree(e->d_base);
-	if (e->d_meta) (void)hipFree(e->d_meta);
-	if (e->d_zz) (void)hipFree(e->d_zz);
-	if (e->d_rec) (void)hipFree(e->d_rec);
-	if (e->d_verdict) (void)hipFree(e->d_verdict);
-	if (e->h_verdict) (void)hipHostFree(e->h_verdict);
-	if (e->d_rounds_changed) (void)hipFree(e->d_rounds_changed);
-	if (e->d_changed) (void)hipFree(e->d_changed);
-	if (e->h_rounds_changed) (void)hipHostFree(e->h_rounds_changed);
-	delete e;
-}
-
-static void es_free_fwd(EsArena *e) { es_free(e); }
-static void es_reset_fwd(EsArena *e)
-{
-	if (!e)
-		return;
-	e->scan_slot.clear();
-	e->sub_used = e->blk_used = e->work_used = e->n_tabs = 0;
-	e->pack_used = 0;
-	e->in_flight = false;
-}
+/* ------------------------------------------------------------------ GPU entropy stage (mij_batch_entropy_*): EsArena, above */
 
 extern "C" int mij_batch_entropy_reserve(mij_batch *b, size_t stream_bytes)
 {
@@ -2557,12 +2540,11 @@ extern "C" int mij_batch_entropy_reserve(mij_batch *b, size_t stream_bytes)
 	if (b->es)
 		return set_err(MIJ_E_STATE, "the entropy arena exists already");
 	HIP_TRY(hipSetDevice(b->ctx->device));
-	EsArena *e = new (std::nothrow) EsArena();
+	std::unique_ptr<EsArena> e(new (std::nothrow) EsArena());
 	if (!e)
 		return set_err(MIJ_E_NOMEM, "out of host memory");
-	memset(static_cast<void *>(e), 0, offsetof(EsArena, scan_slot));
 	const size_t n = (size_t)b->max_images;
-	e->stream_cap = align_up(stream_bytes + 64 * n, 256);
+	const size_t stream_cap = align_up(stream_bytes + 64 * n, 256);
 	e->scan_cap = 16 * n + 1024; /* restart intervals are walked one DevScan each */
 	/* one picture per batch: short subsequences (latency), see MIJ_ES_BITS_SINGLE; MIJ_ES_BITS_OVERRIDE for experiments */
 	e->sub_bits = n == 1 ? MIJ_ES_BITS_SINGLE : MIJ_ES_BITS;
@@ -2574,53 +2556,49 @@ extern "C" int mij_batch_entropy_reserve(mij_batch *b, size_t stream_bytes)
 	/* shorter subsequences settle in more rounds; a round in which nothing moves costs a launch (~8 us), a look at the verdicts
 	 * a wait: measured on one-picture batches, 1024 bits with 24 rounds queued up front is the quickest (profiles/r02v_single_call.json) */
 	e->rounds0 = e->sub_bits >= 4096u ? 4 : (e->sub_bits >= 2048u ? 12 : (e->sub_bits >= 1024u ? 24 : 32));
-	e->sub_cap = e->stream_cap * 8 / e->sub_bits + 2 * e->scan_cap;
-	e->blk_cap = b->coef_cap / 128 + n;
-	e->work_cap = e->sub_cap / MIJ_ES_WG + 2 * e->scan_cap;
-	e->pack_cap = e->blk_cap / 256 + 8 * n;
-	hipError_t r = hipHostMalloc(reinterpret_cast<void **>(&e->stage), e->stream_cap, hipHostMallocDefault);
-	if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_stream), e->stream_cap);
-	if (r == hipSuccess) r = hipHostMalloc(reinterpret_cast<void **>(&e->h_scans), sizeof(DevScan) * e->scan_cap, hipHostMallocDefault);
-	if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_scans), sizeof(DevScan) * e->scan_cap);
-	if (r == hipSuccess) r = hipHostMalloc(reinterpret_cast<void **>(&e->h_huff), sizeof(DevHuff) * 8 * n, hipHostMallocDefault);
-	if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_huff), sizeof(DevHuff) * 8 * n);
-	if (r == hipSuccess) r = hipHostMalloc(reinterpret_cast<void **>(&e->h_work), sizeof(EsWork) * e->work_cap, hipHostMallocDefault);
-	if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_work), sizeof(EsWork) * e->work_cap);
-	if (r == hipSuccess) r = hipHostMalloc(reinterpret_cast<void **>(&e->h_pack), sizeof(WorkIdct) * e->pack_cap, hipHostMallocDefault);
-	if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_pack), sizeof(WorkIdct) * e->pack_cap);
-	if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_start), sizeof(uint64_t) * e->sub_cap);
-	if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_end[0]), sizeof(uint64_t) * e->sub_cap);
-	if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_end[1]), sizeof(uint64_t) * e->sub_cap);
-	if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_uni), sizeof(EsUni) * n);
-	if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_wtab), sizeof(EsW) * n);
-	if (r == hipSuccess) r = hipHostMalloc(reinterpret_cast<void **>(&e->h_tabscan), sizeof(uint32_t) * n, hipHostMallocDefault);
-	if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_tabscan), sizeof(uint32_t) * n);
-	for (int q = 0; q < 2; ++q) {
-		if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_qidx[q]), sizeof(uint32_t) * e->sub_cap);
-		if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_qstate[q]), sizeof(uint64_t) * e->sub_cap);
-	}
-	if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_cnt), sizeof(uint32_t) * e->sub_cap);
-	if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_base), sizeof(uint32_t) * e->sub_cap);
-	if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_meta), sizeof(uint64_t) * e->blk_cap);
+	e->sub_cap = stream_cap * 8 / e->sub_bits + 2 * e->scan_cap;
+	e->blk_cap = b->coef.cap / 128 + n;
+	const size_t work_cap = e->sub_cap / MIJ_ES_WG + 2 * e->scan_cap, pack_cap = e->blk_cap / 256 + 8 * n;
 	/* the write pass's intermediate form for compact planes: the record stream (mij_entropy_kernels.h) when its arena's record indices fit
 	 * 32 bits (8 GiB: streams of about 1 GiB per batch) and MIJ_ES_RECORDS / the environment allow it, else the zigzag image */
 	e->rec_region64 = (e->sub_bits + MIJ_ES_REC_SLACK) / 8u;
 	e->rec_words = (e->sub_cap + 1) * (size_t)e->rec_region64;
 	e->use_records = MIJ_ES_RECORDS && e->rec_words < ((size_t)1 << 30) && !(getenv("MIJ_ES_RECORDS") && getenv("MIJ_ES_RECORDS")[0] == '0');
-	if (e->use_records) {
-		if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_rec), sizeof(uint64_t) * e->rec_words);
-	} else if (r == hipSuccess)
-		r = hipMalloc(reinterpret_cast<void **>(&e->d_zz), 64 * e->blk_cap);
-	if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_verdict), sizeof(uint32_t) * 5 * e->scan_cap);
-	if (r == hipSuccess) r = hipHostMalloc(reinterpret_cast<void **>(&e->h_verdict), sizeof(uint32_t) * 5 * e->scan_cap, hipHostMallocDefault);
-	if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_rounds_changed), sizeof(uint32_t) * ES_MAX_ROUNDS);
-	if (r == hipSuccess) r = hipMalloc(reinterpret_cast<void **>(&e->d_changed), sizeof(uint32_t) * ES_MAX_ROUNDS * e->scan_cap);
-	if (r == hipSuccess) r = hipHostMalloc(reinterpret_cast<void **>(&e->h_rounds_changed), sizeof(uint32_t) * ES_MAX_ROUNDS, hipHostMallocDefault);
-	if (r != hipSuccess) {
-		es_free(e);
-		return set_err(r == hipErrorOutOfMemory ? MIJ_E_NOMEM : MIJ_E_HIP, "mij_batch_entropy_reserve: %s", hipGetErrorString(r));
+	static_assert(sizeof(EsUni) % sizeof(uint4) == 0 && sizeof(EsW) % sizeof(uint4) == 0, "the table sets are read as uint4");
+	hipError_t r = hipSuccess;
+	auto get = [&r](auto &buf, size_t count) { /* in this order: the allocator sees the same sequence from every arena */
+		if (r == hipSuccess)
+			r = buf.alloc(count);
+	};
+	get(e->stream, stream_cap);
+	get(e->scans, e->scan_cap);
+	get(e->huff, 8 * n);
+	get(e->work, work_cap);
+	get(e->pack, pack_cap);
+	get(e->start, e->sub_cap);
+	get(e->end[0], e->sub_cap);
+	get(e->end[1], e->sub_cap);
+	get(e->uni, n * (sizeof(EsUni) / sizeof(uint4)));
+	get(e->wtab, n * (sizeof(EsW) / sizeof(uint4)));
+	get(e->tabscan, n);
+	for (int q = 0; q < 2; ++q) {
+		get(e->qidx[q], e->sub_cap);
+		get(e->qstate[q], e->sub_cap);
 	}
-	b->es = e;
+	get(e->cnt, e->sub_cap);
+	get(e->base, e->sub_cap);
+	get(e->meta, e->blk_cap);
+	if (e->use_records)
+		get(e->rec, e->rec_words);
+	else
+		get(e->zz, 64 * e->blk_cap);
+	get(e->verdict, EV_ROWS * e->scan_cap);
+	get(e->verdict_host, EV_ROWS * e->scan_cap);
+	get(e->rounds_changed, (size_t)ES_MAX_ROUNDS);
+	get(e->changed, ES_MAX_ROUNDS * e->scan_cap);
+	if (r != hipSuccess) /* e goes, and what it got with it; b->es stays null */
+		return set_err(r == hipErrorOutOfMemory ? MIJ_E_NOMEM : MIJ_E_HIP, "mij_batch_entropy_reserve: %s", hipGetErrorString(r));
+	b->es = std::move(e);
 	return MIJ_OK;
 }
 
@@ -2629,16 +2607,16 @@ extern "C" uint8_t *mij_batch_entropy_stage(mij_batch *b, size_t *capacity)
 	if (!b || !b->es)
 		return nullptr;
 	if (capacity)
-		*capacity = b->es->stream_cap;
-	return b->es->stage;
+		*capacity = b->es->stream.cap;
+	return b->es->stream.h;
 }
 
 extern "C" int mij_batch_add_stream(mij_batch *b, const mjg_scan *scan, uint8_t *stream, size_t stream_len)
 {
 	if (!b || !b->es || !scan || !stream)
 		return set_err(MIJ_E_ARG, "mij_batch_add_stream: bad argument (entropy arena reserved?)");
-	EsArena *e = b->es;
-	if (stream < e->stage || stream + stream_len + 32 > e->stage + e->stream_cap || ((size_t)(stream - e->stage) & 3u))
+	EsArena *e = b->es.get();
+	if (stream < e->stream.h || stream + stream_len + 32 > e->stream.h + e->stream.cap || ((size_t)(stream - e->stream.h) & 3u))
 		return set_err(MIJ_E_ARG, "the stream must lie 4-byte aligned inside the pinned entropy region with 32 spare bytes behind it");
 	if (scan->blocks_per_mcu < 1 || scan->blocks_per_mcu > 10 || scan->nblocks == 0 || stream_len >= (1u << 28))
 		return set_err(MIJ_E_ARG, "bad scan description");
@@ -2672,7 +2650,7 @@ extern "C" int mij_batch_add_stream(mij_batch *b, const mjg_scan *scan, uint8_t 
 	size_t need_pack = 0;
 	for (int c = 0; c < scan->desc.ncomp; ++c)
 		need_pack += (comp_tiles(scan->desc.comp[c]) * 64 + 255) / 256;
-	if (b->coef_fmt && b->es->pack_used + need_pack > b->es->pack_cap)
+	if (b->coef_fmt && b->es->pack_used + need_pack > b->es->pack.cap)
 		return set_err(MIJ_E_NOMEM, "entropy arena exhausted");
 	/* one DevScan per restart interval (one for the whole stream without restart markers) */
 	const uint32_t nseg = scan->n_seg ? scan->n_seg : 1u;
@@ -2691,7 +2669,7 @@ extern "C" int mij_batch_add_stream(mij_batch *b, const mjg_scan *scan, uint8_t 
 	}
 	if (scan->n_seg && ((uint64_t)scan->restart_mcus * (nseg - 1) >= nmcu || (uint64_t)scan->restart_mcus * nseg < nmcu))
 		return set_err(MIJ_E_ARG, "segment count does not match the restart interval");
-	if (e->sub_used + need_sub > e->sub_cap || e->blk_used + scan->nblocks > e->blk_cap || e->work_used + need_work > e->work_cap ||
+	if (e->sub_used + need_sub > e->sub_cap || e->blk_used + scan->nblocks > e->blk_cap || e->work_used + need_work > e->work.cap ||
 		 e->scan_slot.size() + nseg > e->scan_cap || e->n_tabs + 1 > (size_t)b->max_images)
 		return set_err(MIJ_E_NOMEM, "entropy arena exhausted");
 	const int slot = add_common(b, &scan->desc, -1, true);
@@ -2709,7 +2687,7 @@ extern "C" int mij_batch_add_stream(mij_batch *b, const mjg_scan *scan, uint8_t 
 		for (int c = 0; c < scan->desc.ncomp; ++c)
 			for (uint32_t f = 0, nb = (uint32_t)comp_tiles(scan->desc.comp[c]) * 64u; f < nb; f += 256) {
 				WorkIdct w = {(uint32_t)slot, (uint32_t)c, f, 0u};
-				e->h_pack[e->pack_used++] = w;
+				e->pack.h[e->pack_used++] = w;
 			}
 	s.dev.es_blk_off = (uint32_t)e->blk_used;
 	s.dev.es_bpm = (uint8_t)scan->blocks_per_mcu;
@@ -2719,17 +2697,17 @@ extern "C" int mij_batch_add_stream(mij_batch *b, const mjg_scan *scan, uint8_t 
 	}
 	static_assert(sizeof(DevHuff) == sizeof(mjg_huff), "mjg_huff and DevHuff must match");
 	const size_t tab = e->n_tabs++;
-	memcpy(&e->h_huff[8 * tab], scan->huff, sizeof(mjg_huff) * 8);
-	e->h_tabscan[tab] = (uint32_t)e->scan_slot.size(); /* the first of this picture's scans */
+	memcpy(&e->huff.h[8 * tab], scan->huff, sizeof(mjg_huff) * 8);
+	e->tabscan.h[tab] = (uint32_t)e->scan_slot.size(); /* the first of this picture's scans */
 	uint32_t first_mcu = 0;
 	for (uint32_t g = 0; g < nseg; ++g) {
 		const size_t k = e->scan_slot.size();
 		const size_t off = table[2 * g], len = table[2 * g + 1];
 		const uint32_t seg_mcus = scan->n_seg ? (g + 1 < nseg ? scan->restart_mcus : nmcu - first_mcu) : nmcu;
 		const size_t ns = (len * 8 + e->sub_bits - 1) / e->sub_bits;
-		DevScan &d = e->h_scans[k];
+		DevScan &d = e->scans.h[k];
 		memset(&d, 0, sizeof(d));
-		d.stream_off = (uint64_t)(stream - e->stage) + off;
+		d.stream_off = (uint64_t)(stream - e->stream.h) + off;
 		d.nbits = (uint32_t)(len * 8);
 		d.nsub = (uint32_t)(ns ? ns : 1);
 		d.sub_off = (uint32_t)e->sub_used;
@@ -2751,7 +2729,7 @@ extern "C" int mij_batch_add_stream(mij_batch *b, const mjg_scan *scan, uint8_t 
 		memcpy(d.qz, scan->qz, sizeof(d.qz));
 		for (uint32_t f = 0; f < d.nsub; f += MIJ_ES_WG) {
 			EsWork w = {(uint32_t)k, f};
-			e->h_work[e->work_used++] = w;
+			e->work.h[e->work_used++] = w;
 		}
 		e->sub_used += d.nsub;
 		e->blk_used += d.nblocks;
@@ -2764,14 +2742,14 @@ extern "C" int mij_batch_add_stream(mij_batch *b, const mjg_scan *scan, uint8_t 
 /* everything after the synchronisation rounds: offsets, write, tails, DC, verdict D2H (asynchronous) */
 static int es_enqueue_tail(mij_batch *b)
 {
-	EsArena *e = b->es;
+	EsArena *e = b->es.get();
 	hipStream_t st = b->stream;
 	const size_t ns = e->scan_slot.size();
 	/* the counters of the last round queued so far (slice 0 is clear when there was none) */
-	uint32_t *v_anom = e->d_verdict, *v_changed = e->d_changed + (size_t)(e->last_rounds > 0 ? e->last_rounds - 1 : 0) * e->scan_cap, *v_total = e->d_verdict + 2 * e->scan_cap,
-				*v_l1 = e->d_verdict + 3 * e->scan_cap, *v_pfinal = e->d_verdict + 4 * e->scan_cap;
+	uint32_t *v_anom = e->d_row(EV_ANOMALY), *v_changed = e->changed.d + (size_t)(e->last_rounds > 0 ? e->last_rounds - 1 : 0) * e->scan_cap, *v_total = e->d_row(EV_TOTAL),
+				*v_l1 = e->d_row(EV_L1MAX), *v_pfinal = e->d_row(EV_PFINAL);
 	const dim3 gw((unsigned)e->work_used), gs((unsigned)ns), blk(256), wblk(MIJ_ES_WG);
-	hipLaunchKernelGGL(k_es_offsets, gs, blk, 0, st, e->d_scans, e->d_cnt, e->d_base, v_total);
+	hipLaunchKernelGGL(k_es_offsets, gs, blk, 0, st, e->scans.d, e->cnt.d, e->base.d, v_total);
 	HIP_TRY(hipGetLastError());
 	{
 		/* compact planes: the write pass fills a cleared intermediate image (k_es_pack then writes every byte of the
@@ -2779,9 +2757,9 @@ static int es_enqueue_tail(mij_batch *b)
 		 * no clearing).  int16 planes: the write pass only stores non-zero coefficients, so the planes of those images
 		 * are cleared (neighbours in the arena as one range). */
 		if (e->pack_used && !e->use_records)
-			HIP_TRY(hipMemsetAsync(e->d_zz, 0, 64 * e->blk_used, st));
+			HIP_TRY(hipMemsetAsync(e->zz.d, 0, 64 * e->blk_used, st));
 		if (e->pack_used && e->use_records) /* record form: "no subsequence began this block" until the write pass says where its records start */
-			HIP_TRY(hipMemsetAsync(e->d_meta, 0xff, sizeof(uint64_t) * e->blk_used, st));
+			HIP_TRY(hipMemsetAsync(e->meta.d, 0xff, sizeof(uint64_t) * e->blk_used, st));
 		size_t lo = 0, hi = 0;
 		for (const Slot &sl : b->slots) {
 			if (!sl.dev_coef || sl.clone_of >= 0 || sl.coef_bytes_fmt)
@@ -2792,68 +2770,66 @@ static int es_enqueue_tail(mij_batch *b)
 				continue;
 			}
 			if (hi > lo)
-				HIP_TRY(hipMemsetAsync(b->d_coef + lo, 0, hi - lo, st));
+				HIP_TRY(hipMemsetAsync(b->coef.d + lo, 0, hi - lo, st));
 			lo = a;
 			hi = z;
 		}
 		if (hi > lo)
-			HIP_TRY(hipMemsetAsync(b->d_coef + lo, 0, hi - lo, st));
+			HIP_TRY(hipMemsetAsync(b->coef.d + lo, 0, hi - lo, st));
 		/* one launch per plane format in use (the other kind's workgroups leave at once) */
 		bool any_fmt[2] = {false, false};
 		for (size_t k = 0; k < ns; ++k)
-			any_fmt[e->h_scans[k].fmt ? 1 : 0] = true;
+			any_fmt[e->scans.h[k].fmt ? 1 : 0] = true;
 		if (any_fmt[1] && e->use_records)
-			hipLaunchKernelGGL(k_es_writer, gw, wblk, 0, st, e->d_scans, e->d_work, e->d_huff, e->d_stream, e->d_start, e->d_base, e->d_meta, v_anom, v_pfinal, e->d_rec,
-									 e->rec_region64, e->d_wtab);
+			hipLaunchKernelGGL(k_es_writer, gw, wblk, 0, st, e->scans.d, e->work.d, e->huff.d, e->stream.d, e->start.d, e->base.d, e->meta.d, v_anom, v_pfinal, e->rec.d,
+									 e->rec_region64, e->wtab.d);
 		else if (any_fmt[1])
-			hipLaunchKernelGGL(k_es_write<true>, gw, wblk, 0, st, e->d_scans, e->d_work, e->d_huff, e->d_stream, b->d_imgs, e->d_start, e->d_base,
-									 reinterpret_cast<int16_t *>(b->d_coef), e->d_meta, v_anom, v_pfinal, e->d_zz);
+			hipLaunchKernelGGL(k_es_write<true>, gw, wblk, 0, st, e->scans.d, e->work.d, e->huff.d, e->stream.d, b->imgs.d, e->start.d, e->base.d,
+									 reinterpret_cast<int16_t *>(b->coef.d), e->meta.d, v_anom, v_pfinal, e->zz.d);
 		if (any_fmt[0])
-			hipLaunchKernelGGL(k_es_write<false>, gw, wblk, 0, st, e->d_scans, e->d_work, e->d_huff, e->d_stream, b->d_imgs, e->d_start, e->d_base,
-									 reinterpret_cast<int16_t *>(b->d_coef), e->d_meta, v_anom, v_pfinal, e->d_zz);
+			hipLaunchKernelGGL(k_es_write<false>, gw, wblk, 0, st, e->scans.d, e->work.d, e->huff.d, e->stream.d, b->imgs.d, e->start.d, e->base.d,
+									 reinterpret_cast<int16_t *>(b->coef.d), e->meta.d, v_anom, v_pfinal, e->zz.d);
 		HIP_TRY(hipGetLastError());
 		if (any_fmt[1] && !e->use_records)
-			hipLaunchKernelGGL(k_es_tails<true>, gw, wblk, 0, st, e->d_scans, e->d_work, e->d_huff, e->d_stream, b->d_imgs, e->d_start, e->d_base,
-									 reinterpret_cast<int16_t *>(b->d_coef), e->d_meta, e->d_rounds_changed, e->d_zz);
+			hipLaunchKernelGGL(k_es_tails<true>, gw, wblk, 0, st, e->scans.d, e->work.d, e->huff.d, e->stream.d, b->imgs.d, e->start.d, e->base.d,
+									 reinterpret_cast<int16_t *>(b->coef.d), e->meta.d, e->rounds_changed.d, e->zz.d);
 		if (any_fmt[0])
-			hipLaunchKernelGGL(k_es_tails<false>, gw, wblk, 0, st, e->d_scans, e->d_work, e->d_huff, e->d_stream, b->d_imgs, e->d_start, e->d_base,
-									 reinterpret_cast<int16_t *>(b->d_coef), e->d_meta, e->d_rounds_changed, e->d_zz);
+			hipLaunchKernelGGL(k_es_tails<false>, gw, wblk, 0, st, e->scans.d, e->work.d, e->huff.d, e->stream.d, b->imgs.d, e->start.d, e->base.d,
+									 reinterpret_cast<int16_t *>(b->coef.d), e->meta.d, e->rounds_changed.d, e->zz.d);
 	}
 	HIP_TRY(hipGetLastError());
 	if (e->pack_used) {
 		if (e->use_records)
-			hipLaunchKernelGGL(k_es_pack2, dim3((unsigned)e->pack_used), blk, 0, st, b->d_imgs, e->d_pack, e->d_rec, (uint32_t)e->rec_words, b->d_coef, e->d_meta);
+			hipLaunchKernelGGL(k_es_pack2, dim3((unsigned)e->pack_used), blk, 0, st, b->imgs.d, e->pack.d, e->rec.d, (uint32_t)e->rec_words, b->coef.d, e->meta.d);
 		else
-			hipLaunchKernelGGL(k_es_pack, dim3((unsigned)e->pack_used), blk, 0, st, b->d_imgs, e->d_pack, e->d_zz, b->d_coef, e->d_meta);
+			hipLaunchKernelGGL(k_es_pack, dim3((unsigned)e->pack_used), blk, 0, st, b->imgs.d, e->pack.d, e->zz.d, b->coef.d, e->meta.d);
 		HIP_TRY(hipGetLastError());
 	}
-	hipLaunchKernelGGL(k_es_dc, gs, blk, 0, st, e->d_scans, b->d_imgs, v_total, v_changed, reinterpret_cast<int16_t *>(b->d_coef), e->d_meta,
-							 v_anom, v_l1, v_pfinal, e->d_stream);
+	hipLaunchKernelGGL(k_es_dc, gs, blk, 0, st, e->scans.d, b->imgs.d, v_total, v_changed, reinterpret_cast<int16_t *>(b->coef.d), e->meta.d,
+							 v_anom, v_l1, v_pfinal, e->stream.d);
 	HIP_TRY(hipGetLastError());
 	/* only the words of this batch's scans: five short runs */
-	for (int v = 0; v < 5; ++v)
-		HIP_TRY(copy_table_to_host(e->h_verdict + (size_t)v * e->scan_cap, v == 1 ? v_changed : e->d_verdict + (size_t)v * e->scan_cap, sizeof(uint32_t) * ns, st));
+	for (int v = 0; v < EV_ROWS; ++v)
+		HIP_TRY(copy_table_to_host(e->h_row((EsVerdict)v), v == EV_CHANGED ? v_changed : e->d_row((EsVerdict)v), sizeof(uint32_t) * ns, st));
 	return MIJ_OK;
 }
 
 static int es_enqueue_round(mij_batch *b)
 {
-	EsArena *e = b->es;
+	EsArena *e = b->es.get();
 	hipStream_t st = b->stream;
-	const size_t ns = e->scan_slot.size();
 	if (e->last_rounds >= ES_MAX_ROUNDS)
 		return set_err(MIJ_E_STATE, "too many synchronisation rounds");
-	uint32_t *v_changed = e->d_changed + (size_t)e->last_rounds * e->scan_cap; /* this round's slice, cleared by the launch */
+	uint32_t *v_changed = e->changed.d + (size_t)e->last_rounds * e->scan_cap; /* this round's slice, cleared by the launch */
 	const dim3 gw((unsigned)e->work_used), blk(MIJ_ES_WG);
-	(void)ns;
 	/* v_changed: what this round leaves for the next one (0 everywhere: the chains have settled) */
 	const int r = e->last_rounds;
 	if (r == 0)
-		hipLaunchKernelGGL(k_es_sync, gw, blk, 0, st, e->d_scans, e->d_work, e->d_huff, e->d_stream, e->d_start, e->d_end[0], e->d_end[1], e->d_cnt, v_changed, e->d_qidx[0],
-								 e->d_qstate[0], e->d_uni);
+		hipLaunchKernelGGL(k_es_sync, gw, blk, 0, st, e->scans.d, e->work.d, e->huff.d, e->stream.d, e->start.d, e->end[0].d, e->end[1].d, e->cnt.d, v_changed, e->qidx[0].d,
+								 e->qstate[0].d, e->uni.d);
 	else
-		hipLaunchKernelGGL(k_es_syncq, gw, blk, 0, st, e->d_scans, e->d_work, e->d_huff, e->d_stream, e->d_start, e->d_end[1], e->d_cnt, v_changed - e->scan_cap,
-								 e->d_qidx[(r - 1) & 1], e->d_qstate[(r - 1) & 1], v_changed, e->d_qidx[r & 1], e->d_qstate[r & 1], e->d_uni);
+		hipLaunchKernelGGL(k_es_syncq, gw, blk, 0, st, e->scans.d, e->work.d, e->huff.d, e->stream.d, e->start.d, e->end[1].d, e->cnt.d, v_changed - e->scan_cap,
+								 e->qidx[(r - 1) & 1].d, e->qstate[(r - 1) & 1].d, v_changed, e->qidx[r & 1].d, e->qstate[r & 1].d, e->uni.d);
 	HIP_TRY(hipGetLastError());
 	++e->last_rounds;
 	return MIJ_OK;
@@ -2865,7 +2841,7 @@ extern "C" int mij_batch_entropy_launch(mij_batch *b)
 {
 	if (!b || !b->es)
 		return set_err(MIJ_E_ARG, "mij_batch_entropy_launch: bad argument");
-	EsArena *e = b->es;
+	EsArena *e = b->es.get();
 	const size_t ns = e->scan_slot.size();
 	e->in_flight = false;
 	if (!ns)
@@ -2874,17 +2850,17 @@ extern "C" int mij_batch_entropy_launch(mij_batch *b)
 	hipStream_t st = b->stream;
 	const size_t n = b->slots.size();
 	for (size_t i = 0; i < n; ++i)
-		b->h_imgs[i] = b->slots[i].dev;
-	HIP_TRY(copy_table(b->d_imgs, b->h_imgs, sizeof(DevImage) * n, st));
-	HIP_TRY(copy_table(e->d_scans, e->h_scans, sizeof(DevScan) * ns, st));
-	HIP_TRY(copy_table(e->d_huff, e->h_huff, sizeof(DevHuff) * 8 * e->n_tabs, st));
-	HIP_TRY(copy_table(e->d_tabscan, e->h_tabscan, sizeof(uint32_t) * e->n_tabs, st));
-	HIP_TRY(copy_table(e->d_work, e->h_work, sizeof(EsWork) * e->work_used, st));
-	HIP_TRY(copy_table(e->d_pack, e->h_pack, sizeof(WorkIdct) * e->pack_used, st));
+		b->imgs.h[i] = b->slots[i].dev;
+	HIP_TRY(copy_table(b->imgs.d, b->imgs.h, sizeof(DevImage) * n, st));
+	HIP_TRY(copy_table(e->scans.d, e->scans.h, sizeof(DevScan) * ns, st));
+	HIP_TRY(copy_table(e->huff.d, e->huff.h, sizeof(DevHuff) * 8 * e->n_tabs, st));
+	HIP_TRY(copy_table(e->tabscan.d, e->tabscan.h, sizeof(uint32_t) * e->n_tabs, st));
+	HIP_TRY(copy_table(e->work.d, e->work.h, sizeof(EsWork) * e->work_used, st));
+	HIP_TRY(copy_table(e->pack.d, e->pack.h, sizeof(WorkIdct) * e->pack_used, st));
 	/* streams: one copy from the first to the last byte in use */
 	size_t lo = (size_t)-1, hi = 0;
 	for (size_t k = 0; k < ns; ++k) {
-		const DevScan &d = e->h_scans[k];
+		const DevScan &d = e->scans.h[k];
 		lo = d.stream_off < lo ? (size_t)d.stream_off : lo;
 		const size_t end = (size_t)d.stream_off + d.nbits / 8 + 32;
 		hi = end > hi ? end : hi;
@@ -2892,17 +2868,16 @@ extern "C" int mij_batch_entropy_launch(mij_batch *b)
 	/* The copy engine, not the copy kernel: measured both ways with four walks in flight (profiles/r02n): through
 	 * k_copy_words16 the call never blocks but the 58 MB cross PCIe under a kernel that holds workgroup slots (78 Gpix/s end
 	 * to end); hipMemcpyAsync blocks the host for ~7 ms one call in three or four and still comes out ahead (100 Gpix/s). */
-	HIP_TRY(hipMemcpyAsync(e->d_stream + lo, e->stage + lo, hi - lo, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(e->stream.d + lo, e->stream.h + lo, hi - lo, hipMemcpyHostToDevice, st));
 	/* the write pass stores every block of the MCU grid whole and its L1 word with it, so neither the
 	 * coefficient planes nor the accumulators need clearing; the verdicts do */
-	HIP_TRY(hipMemsetAsync(e->d_verdict, 0, sizeof(uint32_t) * 5 * e->scan_cap, st));
-	HIP_TRY(hipMemsetAsync(e->d_changed, 0, sizeof(uint32_t) * ES_MAX_ROUNDS * e->scan_cap, st));
+	HIP_TRY(hipMemsetAsync(e->verdict.d, 0, sizeof(uint32_t) * EV_ROWS * e->scan_cap, st));
+	HIP_TRY(hipMemsetAsync(e->changed.d, 0, sizeof(uint32_t) * ES_MAX_ROUNDS * e->scan_cap, st));
 	const dim3 gw((unsigned)e->work_used), blk(MIJ_ES_WG);
-	hipLaunchKernelGGL(k_es_tables, dim3((unsigned)e->n_tabs), dim3(256), 0, st, e->d_scans, e->d_tabscan, e->d_huff, e->d_uni, e->d_wtab);
+	hipLaunchKernelGGL(k_es_tables, dim3((unsigned)e->n_tabs), dim3(256), 0, st, e->scans.d, e->tabscan.d, e->huff.d, e->uni.d, e->wtab.d);
 	HIP_TRY(hipGetLastError());
-	hipLaunchKernelGGL(k_es_cold, gw, blk, 0, st, e->d_scans, e->d_work, e->d_huff, e->d_stream, e->d_start, e->d_end[0], e->d_cnt, e->d_uni);
+	hipLaunchKernelGGL(k_es_cold, gw, blk, 0, st, e->scans.d, e->work.d, e->huff.d, e->stream.d, e->start.d, e->end[0].d, e->cnt.d, e->uni.d);
 	HIP_TRY(hipGetLastError());
-	e->cur = 0;
 	e->last_rounds = 0;
 	int rounds = e->rounds0; /* 4096-bit subsequences: ordinary pictures settle in two or three of four; finish() adds rounds for those that have not */
 	if (const char *env = getenv("MIJ_ES_ROUNDS"))
@@ -2925,7 +2900,7 @@ extern "C" int mij_batch_entropy_finish(mij_batch *b, int *fallback, int cap, in
 {
 	if (!b || !b->es || !n_fallback)
 		return set_err(MIJ_E_ARG, "mij_batch_entropy_finish: bad argument");
-	EsArena *e = b->es;
+	EsArena *e = b->es.get();
 	*n_fallback = 0;
 	const size_t ns = e->scan_slot.size();
 	if (!ns || !e->in_flight)
@@ -2936,7 +2911,7 @@ extern "C" int mij_batch_entropy_finish(mij_batch *b, int *fallback, int cap, in
 	HIP_TRY(hipStreamSynchronize(st));
 	bool unsettled = false;
 	for (size_t k = 0; k < ns; ++k)
-		unsettled |= (e->h_verdict[k] & 8u) != 0;
+		unsettled |= (e->h_row(EV_ANOMALY)[k] & 8u) != 0;
 	if (unsettled) {
 		while (e->last_rounds < ES_MAX_ROUNDS) {
 			int rc = MIJ_OK;
@@ -2944,17 +2919,17 @@ extern "C" int mij_batch_entropy_finish(mij_batch *b, int *fallback, int cap, in
 				rc = es_enqueue_round(b);
 			if (rc != MIJ_OK)
 				return rc;
-			HIP_TRY(hipMemcpyAsync(e->h_verdict + e->scan_cap, e->d_changed + (size_t)(e->last_rounds - 1) * e->scan_cap, sizeof(uint32_t) * ns, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipMemcpyAsync(e->h_row(EV_CHANGED), e->changed.d + (size_t)(e->last_rounds - 1) * e->scan_cap, sizeof(uint32_t) * ns, hipMemcpyDeviceToHost, st));
 			HIP_TRY(hipStreamSynchronize(st));
 			uint32_t any = 0;
 			for (size_t k = 0; k < ns; ++k)
-				any |= e->h_verdict[e->scan_cap + k];
+				any |= e->h_row(EV_CHANGED)[k];
 			if (!any)
 				break;
 		}
 		/* the passes behind the rounds again, on clean verdicts (the last round's counters stay) */
-		HIP_TRY(hipMemsetAsync(e->d_verdict, 0, sizeof(uint32_t) * e->scan_cap, st));
-		HIP_TRY(hipMemsetAsync(e->d_verdict + 2 * e->scan_cap, 0, sizeof(uint32_t) * 3 * e->scan_cap, st));
+		HIP_TRY(hipMemsetAsync(e->d_row(EV_ANOMALY), 0, sizeof(uint32_t) * e->scan_cap, st));
+		HIP_TRY(hipMemsetAsync(e->d_row(EV_TOTAL), 0, sizeof(uint32_t) * (EV_ROWS - EV_TOTAL) * e->scan_cap, st));
 		int rc = es_enqueue_tail(b);
 		if (rc != MIJ_OK)
 			return rc;
@@ -2962,16 +2937,15 @@ extern "C" int mij_batch_entropy_finish(mij_batch *b, int *fallback, int cap, in
 	}
 	if (getenv("MIJ_ES_DEBUG"))
 		for (size_t k = 0; k < ns; ++k)
-			fprintf(stderr, "es scan %zu slot %d: anomaly %u changed %u blocks %u/%u l1max %u nsub %u rounds %d\n", k, e->scan_slot[k], e->h_verdict[k],
-					  e->h_verdict[e->scan_cap + k], e->h_verdict[2 * e->scan_cap + k], e->h_scans[k].nblocks,
-					  e->h_verdict[3 * e->scan_cap + k], e->h_scans[k].nsub, e->last_rounds);
+			fprintf(stderr, "es scan %zu slot %d: anomaly %u changed %u blocks %u/%u l1max %u nsub %u rounds %d\n", k, e->scan_slot[k], e->h_row(EV_ANOMALY)[k],
+					  e->h_row(EV_CHANGED)[k], e->h_row(EV_TOTAL)[k], e->scans.h[k].nblocks, e->h_row(EV_L1MAX)[k], e->scans.h[k].nsub, e->last_rounds);
 	/* a slot's restart intervals are consecutive scans: any verdict bit in one of them hands the image back */
 	for (size_t k = 0; k < ns;) {
 		const int slot = e->scan_slot[k];
 		uint32_t bad = 0, l1max = 0;
 		for (; k < ns && e->scan_slot[k] == slot; ++k) {
-			bad |= e->h_verdict[k];
-			const uint32_t v = e->h_verdict[3 * e->scan_cap + k];
+			bad |= e->h_row(EV_ANOMALY)[k];
+			const uint32_t v = e->h_row(EV_L1MAX)[k];
 			l1max = v > l1max ? v : l1max;
 		}
 		Slot &s = b->slots[(size_t)slot];
@@ -3000,16 +2974,16 @@ extern "C" int mij_batch_entropy_run(mij_batch *b, int *fallback, int cap, int *
 
 extern "C" int mij_batch_entropy_anomaly(mij_batch *b, int slot)
 {
-	if (!b || !b->es || slot < 0 || slot >= (int)b->slots.size())
+	if (!batch_slot(b, slot) || !b->es)
 		return set_err(MIJ_E_ARG, "mij_batch_entropy_anomaly: bad argument");
-	const EsArena *e = b->es;
+	const EsArena *e = b->es.get();
 	if (e->in_flight)
 		return set_err(MIJ_E_ARG, "mij_batch_entropy_anomaly: the walk has not been finished");
 	uint32_t bad = 0;
 	bool found = false;
 	for (size_t k = 0; k < e->scan_slot.size(); ++k)
 		if (e->scan_slot[k] == slot) {
-			bad |= e->h_verdict[k];
+			bad |= e->h_row(EV_ANOMALY)[k];
 			found = true;
 		}
 	if (!found)
@@ -3019,8 +2993,8 @@ extern "C" int mij_batch_entropy_anomaly(mij_batch *b, int slot)
 
 extern "C" int mij_batch_fallback_prepare(mij_batch *b, int slot)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size())
-		return set_err(MIJ_E_ARG, "bad slot");
+	if (!batch_slot(b, slot))
+		return MIJ_E_ARG;
 	Slot &s = b->slots[(size_t)slot];
 	if (!s.dev_coef)
 		return MIJ_OK;
@@ -3030,14 +3004,14 @@ extern "C" int mij_batch_fallback_prepare(mij_batch *b, int slot)
 	s.coef_bytes_fmt = 0; /* staged as int16 by the host walk; upload decides the format in HBM */
 	layout_coef(s);
 	s.desc.flags &= ~(uint32_t)MIJ_FLAG_WIDE_IDCT;
-	memset(b->stage + s.stage_off, 0, s.coef_bytes);
+	memset(b->stage.h + s.stage_off, 0, s.coef_bytes);
 	b->uploaded = b->launched = false;
 	return MIJ_OK;
 }
 
 extern "C" int mij_batch_fetch_coef(mij_batch *b, int slot, int16_t *dst, size_t dst_elems)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size() || !dst)
+	if (!dst || !batch_slot(b, slot))
 		return set_err(MIJ_E_ARG, "bad slot or destination");
 	const Slot &s = b->slots[(size_t)slot];
 	size_t elems = 0;
@@ -3047,12 +3021,12 @@ extern "C" int mij_batch_fetch_coef(mij_batch *b, int slot, int16_t *dst, size_t
 		return set_err(MIJ_E_ARG, "destination too small");
 	HIP_TRY(hipSetDevice(b->ctx->device));
 	if (!s.coef_bytes_fmt) {
-		return d2h_bounced(b->ctx, b->stream, dst, b->d_coef + s.coef_base, elems * sizeof(int16_t));
+		return d2h_bounced(b->ctx, b->stream, dst, b->coef.d + s.coef_base, elems * sizeof(int16_t));
 	}
 	/* compact planes: bring the region over and expand it on the host into the int16 tile layout */
 	std::vector<uint8_t> raw(s.coef_bytes);
 	{
-		const int rc = d2h_bounced(b->ctx, b->stream, raw.data(), b->d_coef + s.coef_base, s.coef_bytes);
+		const int rc = d2h_bounced(b->ctx, b->stream, raw.data(), b->coef.d + s.coef_base, s.coef_bytes);
 		if (rc != MIJ_OK)
 			return rc;
 	}
@@ -3093,8 +3067,8 @@ extern "C" int mij_batch_set_coef_format(mij_batch *b, int fmt)
 
 extern "C" int mij_batch_slot_escapes(mij_batch *b, int slot)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size())
-		return set_err(MIJ_E_ARG, "bad slot");
+	if (!batch_slot(b, slot))
+		return MIJ_E_ARG;
 	const Slot &s = b->slots[(size_t)slot];
 	if (!s.coef_bytes_fmt)
 		return 0;
@@ -3104,7 +3078,7 @@ extern "C" int mij_batch_slot_escapes(mij_batch *b, int slot)
 		const size_t nt = comp_tiles(s.desc.comp[c]);
 		std::vector<uint8_t> lo(nt << 12);
 		{
-			const int rc = d2h_bounced(b->ctx, b->stream, lo.data(), b->d_coef + s.dev.comp[c].coef_off, nt << 12);
+			const int rc = d2h_bounced(b->ctx, b->stream, lo.data(), b->coef.d + s.dev.comp[c].coef_off, nt << 12);
 			if (rc != MIJ_OK)
 				return rc;
 		}
@@ -3129,11 +3103,11 @@ extern "C" int mij_batch_count_idct_classes(mij_batch *b, int on)
 	const size_t n = b->slots.size();
 	for (size_t i = 0; i < n; ++i) {
 		if (on)
-			b->h_imgs[i].flags |= MIJ_DEV_COUNT_CLASSES;
+			b->imgs.h[i].flags |= MIJ_DEV_COUNT_CLASSES;
 		else
-			b->h_imgs[i].flags &= ~(int32_t)MIJ_DEV_COUNT_CLASSES;
+			b->imgs.h[i].flags &= ~(int32_t)MIJ_DEV_COUNT_CLASSES;
 	}
-	HIP_TRY(copy_table(b->d_imgs, b->h_imgs, sizeof(DevImage) * n, b->stream));
+	HIP_TRY(copy_table(b->imgs.d, b->imgs.h, sizeof(DevImage) * n, b->stream));
 	if (on) {
 		void *sym = nullptr;
 		HIP_TRY(hipGetSymbolAddress(&sym, HIP_SYMBOL(g_idct_class)));
@@ -3161,7 +3135,7 @@ extern "C" int mij_batch_idct_class_counts(mij_batch *b, uint64_t out[4])
 
 extern "C" int mij_batch_slot_coef_bytes(const mij_batch *b, int slot)
 {
-	if (!b || slot < 0 || slot >= (int)b->slots.size())
+	if (!batch_slot(b, slot))
 		return 0;
 	return b->slots[(size_t)slot].coef_bytes_fmt;
 }
@@ -3239,115 +3213,35 @@ struct EncSlot {
 	unsigned char rq_from[2][64]; /* a requantising slot (coef.rq != 0): the tables tp's replaced, luma and chroma, zigzag order */
 };
 
-template <typename T>
-static int grow_dev(T *&d, size_t &cap, size_t need)
-{
-	if (need <= cap)
-		return MIJ_OK;
-	const size_t ncap = need + need / 2 + 64;
-	free_dev(d);
-	cap = 0;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof(T) * ncap));
-	cap = ncap;
-	return MIJ_OK;
-}
-
-/* A list or an arena the encoder owns: `cap` elements in pinned memory, in device memory or (a list the host fills and a kernel reads) in
- * both.  alloc is for the arenas, whose size the caller chose; grow for the lists, by the rule of grow_pair, and only through EncGrow. */
-enum { ENC_PINNED = 1, ENC_ON_DEVICE = 2 };
-template <typename T, int SIDES = ENC_PINNED | ENC_ON_DEVICE>
-struct EncBuf {
-	T *h = nullptr, *d = nullptr;
-	size_t cap = 0;
-	EncBuf() = default;
-	EncBuf &operator=(EncBuf &&o) /* o, a temporary, releases what this held */
-	{
-		std::swap(h, o.h), std::swap(d, o.d), std::swap(cap, o.cap);
-		return *this;
-	}
-	~EncBuf() { release(); }
-	void release()
-	{
-		free_host(h);
-		free_dev(d);
-		cap = 0;
-	}
-	hipError_t alloc(size_t n) /* exactly n elements; an empty arena still has an address */
-	{
-		release();
-		hipError_t r = hipSuccess;
-		if (SIDES & ENC_PINNED)
-			r = hipHostMalloc(reinterpret_cast<void **>(&h), sizeof(T) * (n ? n : 16), hipHostMallocDefault);
-		if (r == hipSuccess && (SIDES & ENC_ON_DEVICE))
-			r = hipMalloc(reinterpret_cast<void **>(&d), sizeof(T) * (n ? n : 16));
-		if (r == hipSuccess)
-			cap = n;
-		return r;
-	}
-	int grow(size_t need)
-	{
-		static_assert(SIDES & ENC_ON_DEVICE, "only the lists grow");
-		if constexpr ((SIDES & ENC_PINNED) != 0)
-			return grow_pair(h, d, cap, need);
-		else
-			return grow_dev(d, cap, need);
-	}
-};
-
-/* Grows the lists of one upload step.  Copies and launches queued earlier may still read a list, so the first one that has to be
- * reallocated waits for the stream: one wait however many grow, none when none does.  rc is the first failure. */
-struct EncGrow {
-	hipStream_t stream;
-	bool waited = false;
-	int rc = MIJ_OK;
-	explicit EncGrow(hipStream_t st) : stream(st) {}
-	template <typename T, int SIDES>
-	bool operator()(EncBuf<T, SIDES> &b, size_t need) /* true: b was reallocated */
-	{
-		if (rc != MIJ_OK || need <= b.cap)
-			return false;
-		if (!waited) {
-			const hipError_t r = hipStreamSynchronize(stream);
-			if (r != hipSuccess) {
-				rc = set_err(MIJ_E_HIP, "hipStreamSynchronize(e->stream) failed: %s", hipGetErrorString(r));
-				return false;
-			}
-			waited = true;
-		}
-		rc = b.grow(need);
-		return rc == MIJ_OK;
-	}
-};
-
 /* GPU emission (mij_enc_stream_reserve): everything enc_free_emit gives back */
 struct EncEmit {
-	EncBuf<uint8_t> arena; /* the streams, and the pinned mirror mij_enc_stream points into; bytes */
+	Buf<uint8_t> arena; /* the streams, and the pinned mirror mij_enc_stream points into; bytes */
 	/* the code tables: entry 0 the plain ones (h_tabs0), entry k + 1 those of the k-th optimised slot, then MIJ_PROG_SCANS per progressive slot */
-	EncBuf<EmitTables, ENC_ON_DEVICE> tabs;
+	Buf<EmitTables, BUF_ON_DEVICE> tabs;
 	EmitTables h_tabs0;
 	/* per-slot and per-tile lists, the headers (MIJ_EMIT_HDR bytes each), the results */
-	EncBuf<EmitSlot> eslot;
-	EncBuf<EmitTile> etile;
-	EncBuf<uint8_t> hdr;
-	EncBuf<EmitResult> res;
-	EncBuf<uint32_t, ENC_ON_DEVICE> tbits, tff, tfrag;
-	EncBuf<uint64_t, ENC_ON_DEVICE> tboff, tout, sent;
+	Buf<EmitSlot> eslot;
+	Buf<EmitTile> etile;
+	Buf<uint8_t> hdr;
+	Buf<EmitResult> res;
+	Buf<uint32_t, BUF_ON_DEVICE> tbits, tff, tfrag;
+	Buf<uint64_t, BUF_ON_DEVICE> tboff, tout, sent;
 	size_t n_etile = 0;
 	/* optimised Huffman tables (mij_enc_set_optimize): the optimised slots' tiles, their slot numbers, their counts and whether each kept
 	 * its own tables */
-	EncBuf<EmitTile> otile;
-	EncBuf<uint32_t> optslot;
-	EncBuf<uint32_t, ENC_ON_DEVICE> freq, optok;
+	Buf<EmitTile> otile;
+	Buf<uint32_t> optslot;
+	Buf<uint32_t, BUF_ON_DEVICE> freq, optok;
 	size_t n_otile = 0, n_opt = 0;
 	/* progressive slots (mij_enc_set_progressive; mij_progressive_kernels.h): their records, the numbers of their tiles in the tile list, the
 	 * block bytes of their AC scans, scan headers and their lengths, per-tile summaries and run results, per-scan counts, and the per-slot
 	 * flag of the slots the host finishes (a forced flush, a table that cannot be built) */
-	EncBuf<ProgSlot> pslot;
-	EncBuf<uint32_t> ptile;
-	EncBuf<uint8_t, ENC_ON_DEVICE> pfl, phdr;
-	EncBuf<ProgTileSum, ENC_ON_DEVICE> tsum;
-	EncBuf<ProgAfter, ENC_ON_DEVICE> tafter;
-	EncBuf<uint32_t, ENC_ON_DEVICE> pfreq, phlen, pflag, ctail;
+	Buf<ProgSlot> pslot;
+	Buf<uint32_t> ptile;
+	Buf<uint8_t, BUF_ON_DEVICE> pfl, phdr;
+	Buf<ProgTileSum, BUF_ON_DEVICE> tsum;
+	Buf<ProgAfter, BUF_ON_DEVICE> tafter;
+	Buf<uint32_t, BUF_ON_DEVICE> pfreq, phlen, pflag, ctail;
 	size_t n_prog = 0, n_ptile = 0;
 };
 
@@ -3358,22 +3252,22 @@ struct mij_encoder {
 	int max_images = 0;
 	/* the arenas, sized at creation, in bytes: pinned pixels, device pixels, the data units and their pinned mirror (made at the first
 	 * mij_enc_fetch_all) */
-	EncBuf<uint8_t, ENC_PINNED> stage;
-	EncBuf<uint8_t, ENC_ON_DEVICE> pix;
-	EncBuf<uint8_t, ENC_ON_DEVICE> du;
-	EncBuf<uint8_t, ENC_PINNED> du_host;
+	Buf<uint8_t, BUF_PINNED> stage;
+	Buf<uint8_t, BUF_ON_DEVICE> pix;
+	Buf<uint8_t, BUF_ON_DEVICE> du;
+	Buf<uint8_t, BUF_PINNED> du_host;
 	size_t stage_used = 0, pix_used = 0, du_used = 0;
-	EncBuf<EncImage> imgs; /* max_images of them */
-	EncBuf<WorkIdct> work;  /* the transform kernels' work items, group after group */
+	Buf<EncImage> imgs; /* max_images of them */
+	Buf<WorkIdct> work;  /* the transform kernels' work items, group after group */
 	size_t n_work[EG_GROUPS] = {}, first_work[EG_GROUPS] = {};
 	std::vector<EncSlot> slots;
 	bool uploaded = false, launched = false, force_generic = false;
 	/* device-pixel slots: the gather kernels' slots and work (rows of MIJ_GATHER_ROWS) for uint8 tensors, float tensors (grouped by dtype:
 	 * one launch of k_enc_gather_float each) and planes (k_enc_gather_planes) */
-	EncBuf<EncGather> gath;
-	EncBuf<EncGatherF> fgath;
-	EncBuf<EncGatherP> pgath;
-	EncBuf<WorkIdct> gwork, fgwork, pgwork;
+	Buf<EncGather> gath;
+	Buf<EncGatherF> fgath;
+	Buf<EncGatherP> pgath;
+	Buf<WorkIdct> gwork, fgwork, pgwork;
 	EncEmit em;
 	bool emit_queued = false, streams_fetched = false;
 	std::vector<int> opt_of;      /* slot -> k, or -1 */
@@ -3382,10 +3276,10 @@ struct mij_encoder {
 	/* coefficient slots (mij_enc_add_coef): the conversion kernel's slots and work (plane tiles), one table per requantising slot of the
 	 * upload (CoefSlot::rq - 1), the event that orders it behind the batch's stream, and the per-slot flags it raises for uncodable
 	 * values (sflag_dev: one per slot, read by k_emit_count) */
-	EncBuf<CoefSlot> cslot;
-	EncBuf<WorkIdct> cwork;
-	EncBuf<RqTable> rqt;
-	EncBuf<uint32_t, ENC_ON_DEVICE> sflag_dev;
+	Buf<CoefSlot> cslot;
+	Buf<WorkIdct> cwork;
+	Buf<RqTable> rqt;
+	Buf<uint32_t, BUF_ON_DEVICE> sflag_dev;
 	hipEvent_t ev_coef = nullptr;
 	bool has_coef = false;       /* the last upload had a coefficient slot */
 	uint32_t coef_tiles = 0;     /* plane tiles its conversion queued (mij_enc_coef_tiles) */
@@ -3797,7 +3691,7 @@ extern "C" int mij_enc_slot_optimized(const mij_encoder *e, int slot)
  * `list` (fill) and their work items in `work` (items(slot, push) calls push(component, first row) for each, in order), class k = 0 ..
  * CLASSES - 1 after class; launch(k, work, grid) then runs once per class that has work.  Nothing is queued when there are no such slots. */
 template <int CLASSES, typename G, typename Takes, typename Items, typename Fill, typename Launch>
-static int enc_gather_pass(mij_encoder *e, EncBuf<G> &list, EncBuf<WorkIdct> &work, Takes takes, Items items, Fill fill, Launch launch)
+static int enc_gather_pass(mij_encoder *e, Buf<G> &list, Buf<WorkIdct> &work, Takes takes, Items items, Fill fill, Launch launch)
 {
 	const auto gathered = [&](const EncSlot &s, int k) { return s.clone_of < 0 && s.kind == ENC_DEVICE && takes(s, k); };
 	size_t ng = 0, nw = 0;
@@ -3809,7 +3703,7 @@ static int enc_gather_pass(mij_encoder *e, EncBuf<G> &list, EncBuf<WorkIdct> &wo
 			}
 	if (!ng)
 		return MIJ_OK;
-	EncGrow grow(e->stream);
+	Grow grow(e->stream);
 	grow(list, ng);
 	grow(work, nw);
 	if (grow.rc != MIJ_OK)
@@ -4098,7 +3992,7 @@ static int enc_emit_lists(mij_encoder *e)
 	if (nt > UINT32_MAX)
 		return set_err(MIJ_E_ARG, "too many data units to emit in one launch");
 	EncEmit &m = e->em;
-	EncGrow grow(e->stream); /* the buffers may still be in use by an earlier launch */
+	Grow grow(e->stream); /* the buffers may still be in use by an earlier launch */
 	grow(m.eslot, n);
 	if (no) {
 		grow(m.otile, not_);
@@ -4701,7 +4595,7 @@ static int enc_coef_convert(mij_encoder *e)
 		return MIJ_OK;
 	if (nw > UINT32_MAX)
 		return set_err(MIJ_E_ARG, "too many plane tiles to convert in one launch");
-	EncGrow grow(e->stream);
+	Grow grow(e->stream);
 	grow(e->cslot, nc);
 	grow(e->rqt, nq);
 	grow(e->cwork, nw);
@@ -4767,7 +4661,7 @@ static int enc_coef_convert(mij_encoder *e)
 			continue;
 		const dim3 grid((unsigned)g.count), block(64);
 		uint8_t *du = e->du.d;
-		hipLaunchKernelGGL((g.win ? k_coef_units_win_of : k_coef_units_of)[g.rq ? 1 : 0][g.fmt ? 1 : 0][g.orient & 7u], grid, block, 0, e->stream, e->cslot.d, e->cwork.d + g.first, g.b->d_coef, du,
+		hipLaunchKernelGGL((g.win ? k_coef_units_win_of : k_coef_units_of)[g.rq ? 1 : 0][g.fmt ? 1 : 0][g.orient & 7u], grid, block, 0, e->stream, e->cslot.d, e->cwork.d + g.first, g.b->coef.d, du,
 								 e->sflag_dev.d, static_cast<const RqTable *>(e->rqt.d));
 		HIP_TRY(hipGetLastError());
 	}
@@ -4823,7 +4717,7 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 	size_t total = 0;
 	for (int g = 0; g < EG_GROUPS; ++g)
 		total += work[g].size();
-	EncGrow grow(e->stream);
+	Grow grow(e->stream);
 	grow(e->work, total);
 	if (grow.rc != MIJ_OK)
 		return grow.rc;
