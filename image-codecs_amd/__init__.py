@@ -21,6 +21,8 @@ from .binding import (  # noqa: F401
     Batch,
     OutTensor,
     OutResize,
+    OutPlane,
+    OutPlanes,
     FILTERS,
     MIJ_FILTER_BOX,
     MIJ_FILTER_BILINEAR,
@@ -113,7 +115,7 @@ from .binding import (  # noqa: F401
 )
 from .synth import synth_rgb, synth_jpeg, synth_rgb_edges  # noqa: F401
 
-_TENSOR_OUT = ("TensorDecoder", "tensor_tables")
+_TENSOR_OUT = ("TensorDecoder", "tensor_tables", "ycbcr_subsampling")
 _TENSOR_ENCODE = ("TensorEncoder",)
 _TRANSCODE = ("Transcoder",)
 

@@ -476,6 +476,12 @@ class HostDecoder:
         return d
 
     @staticmethod
+    def plane_shapes(desc):
+        """-> [(ph, pw), ...]: the shape of every stored component's plane (include/mij.h, PLANE OUTPUT): ceil(W * h_c / h_max) columns
+        and ceil(H * v_c / v_max) rows, which are the descriptor's comp[c].x / .y.  Host only."""
+        return [(int(desc.comp[c].y), int(desc.comp[c].x)) for c in range(desc.ncomp)]
+
+    @staticmethod
     def decode(data, req_comp=0, out=None):
         """-> (desc, arena int16[coef_elems]) ; `out` may be a preallocated int16 array (e.g. a view of pinned staging)."""
         d = HostDecoder.probe(data, req_comp)
@@ -647,7 +653,18 @@ KERNEL_KINDS = (
     "MK_RS_FAST+RS_GEN4", "MK_420", "MK_422", "MK_444", "MK_GREY", "MK_440", "MK_420W", "MK_440W", "MK_420X", "MK_420S", "MK_420T", "MK_422W",
     "MK_422X", "MK_422S", "MK_422T", "MK_1X1C", "MK_420C", "MK_440C", "MK_SCALED+SC_Y", "MK_SCALED+SC_444", "MK_SCALED+SC_420",
     "MK_SCALED+SC_422", "MK_444R", "MK_GREYR", "MK_1X1CR", "MK_SCALEDR+SC_Y", "MK_SCALEDR+SC_444", "MK_SCALEDR+SC_420", "MK_SCALEDR+SC_422",
+    "MK_PLANES_OUT",
 )
+
+
+class OutPlane(C.Structure):
+    """mij_out_plane (include/mij.h)."""
+    _fields_ = [("dst", C.c_void_p), ("row_pitch", C.c_int64), ("x_pitch", C.c_int64)]
+
+
+class OutPlanes(C.Structure):
+    """mij_out_planes (include/mij.h)."""
+    _fields_ = [("planes", OutPlane * 4), ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class Batch:
@@ -1085,6 +1102,33 @@ class Batch:
         L = lib()
         L.mij_batch_set_out_tensor_resized.argtypes = [C.c_void_p, C.c_int, C.POINTER(OutTensor), C.POINTER(OutResize), C.c_void_p]
         _check(L.mij_batch_set_out_tensor_resized(self._h, int(slot), C.byref(t), C.byref(r), tp), "mij_batch_set_out_tensor_resized")
+
+    # ---- plane output (mij_batch_set_out_planes): k_planes_out writes the stored components' samples into device memory the caller owns
+    def set_out_planes(self, slot, planes, window=None, reserved=(0, 0)):
+        """planes: up to four entries in the frame header's component order, each None (not wanted) or (raw device address, row pitch,
+        x pitch) in bytes; window: None (the whole picture) or (x0, y0, w, h) in picture coordinates, on the grid of every wanted
+        component.  No upsampling and no colour conversion: the samples as the file stores them (include/mij.h, PLANE OUTPUT)."""
+        planes = list(planes)
+        if len(planes) > 4:
+            raise ValueError("at most four planes (got %d)" % len(planes))
+        req = OutPlanes()
+        for c, pl in enumerate(planes):
+            if pl is not None:
+                req.planes[c] = OutPlane(C.c_void_p(int(pl[0])), int(pl[1]), int(pl[2]))
+        if window is not None:
+            req.x0, req.y0, req.w, req.h = (int(v) for v in window)
+        req.reserved[0], req.reserved[1] = int(reserved[0]), int(reserved[1])
+        L = lib()
+        L.mij_batch_set_out_planes.argtypes = [C.c_void_p, C.c_int, C.POINTER(OutPlanes)]
+        _check(L.mij_batch_set_out_planes(self._h, int(slot), C.byref(req)), "mij_batch_set_out_planes")
+
+    def plane_rect(self, slot, comp):
+        """(x0, y0, w, h) of the window of component `comp` in its own samples, as the slot's plane request has it (mij_batch_slot_plane_rect)"""
+        L = lib()
+        L.mij_batch_slot_plane_rect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int * 4)]
+        r = (C.c_int * 4)()
+        _check(L.mij_batch_slot_plane_rect(self._h, int(slot), int(comp), C.byref(r)), "mij_batch_slot_plane_rect")
+        return tuple(r)
 
     def fetch_all_async(self, dst_ptr, dst_bytes):
         """mij_batch_fetch_all_async into a (pinned) host buffer; wait() completes it."""

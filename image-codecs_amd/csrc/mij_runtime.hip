@@ -22,6 +22,7 @@
 #include "mij_kernels.h"
 #include "mij_scaled_kernels.h"
 #include "mij_entropy_kernels.h"
+#include "mij_planes_out_kernels.h"
 
 using namespace mij;
 
@@ -59,11 +60,12 @@ extern "C" int mij_device_count(void)
 /* ------------------------------------------------------------------ decode kernel families */
 
 /* kernel families of a launch plan, in launch order.  MK_RS_FAST + RS_*: pass 2 compiled per resampler (k_resample_fast) */
-enum { MK_PLANES = 0, MK_RESAMPLE, MK_RS_FAST, MK_420 = MK_RS_FAST + RS_KINDS, MK_422, MK_444, MK_GREY, MK_440, MK_420W, MK_440W /* k_fused420w / k_fused440w: 512 threads, wide pictures */, MK_420X /* 1024 threads: one workgroup per CU */, MK_420S, MK_420T /* 128 / 64 threads: narrow pictures */, MK_422W, MK_422X, MK_422S, MK_422T /* k_fused422 with 512 / 1024 / 128 / 64 threads */, MK_1X1C /* k_fused1x1c: RGB-tagged / CMYK / YCCK at 1x1 */, MK_420C, MK_440C /* column segments: a row of MCUs beyond a CU's LDS */, MK_SCALED /* + SC_*: reduced-size decode, k_scaled per layout */, MK_444R = MK_SCALED + SC_LAYOUTS, MK_GREYR, MK_1X1CR /* windowed forms of k_fused444 / k_fused_grey / k_fused1x1c: slots with a region (mij_batch_set_roi) */, MK_SCALEDR /* + SC_*: k_scaled on a window */, MK_KINDS = MK_SCALEDR + SC_LAYOUTS };
+enum { MK_PLANES = 0, MK_RESAMPLE, MK_RS_FAST, MK_420 = MK_RS_FAST + RS_KINDS, MK_422, MK_444, MK_GREY, MK_440, MK_420W, MK_440W /* k_fused420w / k_fused440w: 512 threads, wide pictures */, MK_420X /* 1024 threads: one workgroup per CU */, MK_420S, MK_420T /* 128 / 64 threads: narrow pictures */, MK_422W, MK_422X, MK_422S, MK_422T /* k_fused422 with 512 / 1024 / 128 / 64 threads */, MK_1X1C /* k_fused1x1c: RGB-tagged / CMYK / YCCK at 1x1 */, MK_420C, MK_440C /* column segments: a row of MCUs beyond a CU's LDS */, MK_SCALED /* + SC_*: reduced-size decode, k_scaled per layout */, MK_444R = MK_SCALED + SC_LAYOUTS, MK_GREYR, MK_1X1CR /* windowed forms of k_fused444 / k_fused_grey / k_fused1x1c: slots with a region (mij_batch_set_roi) */, MK_SCALEDR /* + SC_*: k_scaled on a window */, MK_PLANES_OUT = MK_SCALEDR + SC_LAYOUTS /* k_planes_out: slots with a plane request (mij_batch_set_out_planes) */, MK_KINDS };
 
 /* A family's kernels per variant = 4 * (n_out == 4) + 2 * wide IDCT + compact planes (k_resample_fast: 4 * (n_out == 4) + 2 * YCbCr
  * colour; k_scaled: 2 * (log2 of the scale - 1) + compact planes).  Every decode kernel takes (const DevImage *, const Work *, const uint8_t *in, uint8_t *out); io says which arenas in and
- * out are.  roi: a windowed form, which takes the batch's DevRoi table as a fifth argument. */
+ * out are.  roi: a windowed form, which takes the batch's DevRoi table as a fifth argument; planes: k_planes_out, which takes the table of plane
+ * requests there and writes the callers' memory, not the output arena. */
 enum { MK_VARIANTS = 8 };
 enum Arena { COEF_OUT, COEF_PLANES, PLANES_OUT };
 struct Family {
@@ -71,13 +73,17 @@ struct Family {
 	Arena io;
 	bool band; /* a band kernel: dynamic LDS up to the whole CU's */
 	const void *k[MK_VARIANTS];
-	bool roi;
+	bool roi, planes;
 };
 #define MIJ_K(...) reinterpret_cast<const void *>(&__VA_ARGS__)
 #define MIJ_NWB(K)                                                                                                                  \
 	{ MIJ_K(K<3, false, false>), MIJ_K(K<3, false, true>), MIJ_K(K<3, true, false>), MIJ_K(K<3, true, true>),                      \
 	  MIJ_K(K<4, false, false>), MIJ_K(K<4, false, true>), MIJ_K(K<4, true, false>), MIJ_K(K<4, true, true>) }
 #define MIJ_WB(K) { MIJ_K(K<false, false>), MIJ_K(K<false, true>), MIJ_K(K<true, false>), MIJ_K(K<true, true>) }
+/* k_planes_out: 4 * (the slot's request has a paired form) + 2 * wide IDCT + compact planes */
+#define MIJ_WBP(K)                                                                                                                  \
+	{ MIJ_K(K<false, false, false>), MIJ_K(K<false, true, false>), MIJ_K(K<true, false, false>), MIJ_K(K<true, true, false>),       \
+	  MIJ_K(K<false, false, true>), MIJ_K(K<false, true, true>), MIJ_K(K<true, false, true>), MIJ_K(K<true, true, true>) }
 /* the windowed forms: the same kernels with the DevRoi table as fifth parameter */
 #define MIJ_R const DevRoi *
 #define MIJ_NWBR(K)                                                                                                                 \
@@ -128,6 +134,7 @@ static const Family families[MK_KINDS] = {
 	{256, COEF_OUT, false, MIJ_SCR(SC_444), true},
 	{256, COEF_OUT, false, MIJ_SCR(SC_420), true},
 	{256, COEF_OUT, false, MIJ_SCR(SC_422), true},
+	/* MK_PLANES_OUT */ {256, COEF_OUT, false, MIJ_WBP(k_planes_out), false, true},
 };
 /* MK_420's pipelined twins (k_fused420p), by variant: compact planes without the wide IDCT only.  Not a family: a launch of MK_420 takes the twin of
  * its variant where band_prefetch says so, and everything that names a picture's kernel (kind, variant, segments) stays what it was. */
@@ -147,6 +154,7 @@ static const void *const k420_march[MK_VARIANTS] = {nullptr, MIJ_K(k_fused420m<3
 #undef MIJ_R
 #undef MIJ_SC
 #undef MIJ_RSF
+#undef MIJ_WBP
 #undef MIJ_WB
 #undef MIJ_NWB
 #undef MIJ_K
@@ -288,7 +296,7 @@ extern "C" int mij_ctx_info(const mij_ctx *ctx, char *arch, size_t arch_len, int
 /* ------------------------------------------------------------------ batch */
 
 /* the kernel family the last upload chose for a slot (mij_batch_slot_path) */
-enum SlotPath { PATH_NONE = 0, PATH_420, PATH_TWO_PASS, PATH_444, PATH_422, PATH_GREY, PATH_440, PATH_1X1C, PATH_SCALED };
+enum SlotPath { PATH_NONE = 0, PATH_420, PATH_TWO_PASS, PATH_444, PATH_422, PATH_GREY, PATH_440, PATH_1X1C, PATH_SCALED, PATH_PLANES_OUT };
 
 /* what classify chose for a slot: the path, the family (MK_*) and variant whose work list takes its items (two-pass: pass 2's),
  * column segments per band, and the LDS of a whole row of MCUs (the band kernels) */
@@ -310,6 +318,7 @@ struct Slot {
 	Choice choice;     /* of the last upload; path 0 none, 1 fused 4:2:0, 2 two-pass, 3 fused 4:4:4, 4 fused 4:2:2, 5 fused grey, 6 fused 4:4:0, 7 fused 1x1 colour, 8 reduced-size */
 	int f32;           /* float output: index of the slot's request (mij_batch::f32_req), -1 none */
 	int ten;           /* tensor output: index of the slot's request (mij_batch::ten_req), -1 none */
+	int pln;           /* plane output: index of the slot's request (mij_batch::pln_req), -1 none */
 	int scale;         /* reduced-size decode (mij_batch_set_scale): 1, 2, 4 or 8; the stored picture is out_w(s) x out_h(s) */
 	/* region of interest: what was asked for (mij_batch_set_roi: roi_on and roi[] = x0, y0, w, h in stored pixels; mij_batch_set_roi_auto), and
 	 * what the last upload made of it -- the region in force (reg, reg_px: none for two-pass slots and for windows that need every MCU), the
@@ -537,6 +546,14 @@ struct mij_batch {
 	/* resized tensor output (mij_batch_set_out_tensor_resized): coefficients per (in, out, filter), kept until reset (std::map: the
 	 * requests point at them), and k_out_resize's plan -- descriptors, tables, coefficients and work list -- in a buffer pair of its own */
 	std::map<uint64_t, RszCoef> rsz_coef;
+	/* plane output (mij_batch_set_out_planes): one validated request per slot that asked, as k_planes_out reads it (a component that is
+	 * not wanted has dst 0), and the per-slot table the kernel takes, max_images entries, made by the first upload that needs it */
+	struct PlnReq {
+		int slot;
+		DevPlanes dev;
+	};
+	std::vector<PlnReq> pln_req;
+	Buf<DevPlanes> pln;
 	PlanBuf rszplan;
 	/* oriented tensor output with orientations 5..8 (mij_batch_set_out_tensor_oriented): k_out_tensor_t's and k_out_resize_t's plans */
 	PlanBuf tentplan, rsztplan;
@@ -641,6 +658,7 @@ extern "C" int mij_batch_reset(mij_batch *b)
 	b->f32_req.clear();
 	b->f32_used = 0;
 	b->ten_req.clear();
+	b->pln_req.clear();
 	b->rsz_coef.clear();
 	b->f32plan.items = b->tenplan.items = b->rszplan.items = b->tentplan.items = b->rsztplan.items = 0;
 	if (b->es)
@@ -778,6 +796,7 @@ static int add_common(mij_batch *b, const mij_image_desc *d, int clone_of, bool 
 	s.choice = Choice();
 	s.f32 = -1;
 	s.ten = -1;
+	s.pln = -1;
 	s.scale = 1;
 	s.roi_on = s.roi_auto = s.reg = false;
 	s.work_items = 0;
@@ -914,6 +933,8 @@ extern "C" int mij_batch_set_scale(mij_batch *b, int slot, int denom)
 										  "%d components, colour mode %d, luma %dx%d of %dx%d)", slot, s.desc.ncomp, s.desc.color, s.desc.comp[0].h, s.desc.comp[0].v, s.desc.h_max, s.desc.v_max);
 	if (denom > 1 && s.f32 >= 0)
 		return set_err(MIJ_E_ARG, "mij_batch_set_scale: slot %d has a float output request; float output of reduced pictures is not supported", slot);
+	if (denom > 1 && s.pln >= 0)
+		return set_err(MIJ_E_STATE, "mij_batch_set_scale: slot %d has a plane request; planes are not decoded at reduced size", slot);
 	if (denom != s.scale && s.ten >= 0)
 		return set_err(MIJ_E_STATE, "mij_batch_set_scale: slot %d already has a tensor request for its %dx%d picture; set the scale first", slot, out_w(s), out_h(s));
 	s.scale = denom;
@@ -949,6 +970,8 @@ extern "C" int mij_batch_set_roi(mij_batch *b, int slot, int x0, int y0, int w, 
 		s.roi_on = false;
 		return MIJ_OK;
 	}
+	if (s.pln >= 0)
+		return set_err(MIJ_E_STATE, "mij_batch_set_roi: slot %d has a plane request, which carries its own window", slot);
 	const int r[4] = {x0, y0, w, h};
 	if (!rect_inside(r, out_w(s), out_h(s)))
 		return set_err(MIJ_E_ARG, "mij_batch_set_roi: region %d,%d %dx%d is empty or outside the %dx%d stored picture of slot %d", x0, y0, w, h, out_w(s), out_h(s), slot);
@@ -968,6 +991,8 @@ extern "C" int mij_batch_set_roi_auto(mij_batch *b, int slot, int on)
 	Slot &s = b->slots[(size_t)slot];
 	if (s.desc.flags & MIJ_FLAG_SKIP)
 		return set_err(MIJ_E_STATE, "slot %d was rejected by the host stage", slot);
+	if (on && s.pln >= 0)
+		return set_err(MIJ_E_STATE, "mij_batch_set_roi_auto: slot %d has a plane request, which carries its own window", slot);
 	if (on && s.f32 >= 0)
 		return set_err(MIJ_E_ARG, "mij_batch_set_roi_auto: slot %d has a float output request; float output of a region is not supported", slot);
 	s.roi_auto = on != 0;
@@ -1179,6 +1204,8 @@ static Choice classify(const mij_batch *b, const Slot &s)
 	const int o4 = d.n_out == 4 ? 4 : 0, var = o4 | ((d.flags & MIJ_FLAG_WIDE_IDCT) ? 2 : 0) | (s.coef_bytes_fmt ? 1 : 0);
 	if (d.flags & MIJ_FLAG_SKIP) /* rejected by the host stage after it got a slot */
 		return Choice();
+	if (s.pln >= 0) /* plane output: no pixel kernel, whatever the layout and whatever force_generic says */
+		return Choice{PATH_PLANES_OUT, MK_PLANES_OUT, (var & 3) | (b->pln_req[(size_t)s.pln].dev.c[1].form == PLN_PAIRED ? 4 : 0)};
 	if (s.scale > 1) /* reduced-size decode: one family per layout, whatever force_generic says (the two-pass path has no such form) */
 		return Choice{PATH_SCALED, MK_SCALED + scaled_layout(d), (s.scale == 2 ? 0 : (s.scale == 4 ? 2 : 4)) | (s.coef_bytes_fmt ? 1 : 0)};
 	if (!b->force_generic) {
@@ -1743,6 +1770,19 @@ static void apply_region(Slot &s)
 	}
 }
 
+/* (slot, component, first unit) per 256 blocks of the window of every component a plane request wants.  Component 2 of a pair
+ * (PLN_PAIRED) queues nothing: the lanes of component 1's items transform both. */
+static void push_planes(std::vector<Work4> &L, uint32_t i, const DevPlanes &r)
+{
+	for (uint32_t c = 0; c < 4; ++c) {
+		const DevPlane &p = r.c[c];
+		if (!p.dst || (p.form == PLN_PAIRED && c == 2))
+			continue;
+		for (uint32_t f = 0, n = p.blk.w * p.blk.h; f < n; f += 256)
+			L.push_back(Work4{i, c, f, 0u});
+	}
+}
+
 /* (slot, component, first block) per 256 blocks of one component */
 static void push_blocks(std::vector<Work4> &L, uint32_t i, const mij_image_desc &d, int comp)
 {
@@ -1798,6 +1838,9 @@ static void plan_decode(mij_batch *b, Plan &p)
 				push_window(L, (uint32_t)i, s.win);
 			else
 				push_blocks(L, (uint32_t)i, d, 0);
+			break;
+		case PATH_PLANES_OUT: /* (slot, component, first block of its window) per 256 blocks of every wanted component; a pair counts once */
+			push_planes(L, (uint32_t)i, b->pln_req[(size_t)s.pln].dev);
 			break;
 		case PATH_SCALED: { /* 256 MCUs a workgroup; the luma-only form: 256 luma blocks */
 			if (s.reg) {
@@ -1895,6 +1938,16 @@ static int lay_out_work(mij_batch *b, const Plan &p)
 		for (size_t i = 0; i < n; ++i)
 			b->roi.h[i] = b->slots[i].reg ? b->slots[i].win : DevRoi{0u, 0u, 0u, 0u};
 		HIP_TRY(copy_table(b->roi.d, b->roi.h, sizeof(DevRoi) * n, b->stream));
+	}
+	bool planes = false;
+	for (const mij_batch::Launch &l : b->launches)
+		planes = planes || families[l.kind].planes;
+	if (planes) { /* the requests of the slots k_planes_out decodes; the others' entries are never read */
+		if (!b->pln.cap)
+			HIP_TRY(b->pln.alloc((size_t)b->max_images));
+		for (const mij_batch::PlnReq &q : b->pln_req)
+			b->pln.h[(size_t)q.slot] = q.dev;
+		HIP_TRY(copy_table(b->pln.d, b->pln.h, sizeof(DevPlanes) * n, b->stream));
 	}
 	if (total)
 		HIP_TRY(copy_table(b->work.d, b->work.h, sizeof(Work4) * total, b->stream));
@@ -2027,9 +2080,10 @@ extern "C" int mij_batch_launch(mij_batch *b)
 		const Work4 *wk = b->work.d + L.first;
 		const uint8_t *in = f.io == PLANES_OUT ? b->planes.d : b->coef.d;
 		uint8_t *out = f.io == COEF_PLANES ? b->planes.d : b->out.d;
-		void *args4[] = {&b->imgs.d, &wk, &in, &out}, *args5[] = {&b->imgs.d, &wk, &in, &out, &b->roi.d}; /* the windowed forms take the table of windows */
+		/* the windowed forms take the table of windows, k_planes_out the table of plane requests */
+		void *args4[] = {&b->imgs.d, &wk, &in, &out}, *args5[] = {&b->imgs.d, &wk, &in, &out, f.planes ? (void *)&b->pln.d : (void *)&b->roi.d};
 		const void *k = L.marched ? k420_march[L.var] : (band_prefetch(L.kind, L.var, L.lds, (size_t)b->ctx->max_dyn_lds) ? k420_prefetch[L.var] : f.k[L.var]);
-		(void)hipLaunchKernel(k, dim3((unsigned)L.count), dim3(f.threads), f.roi ? args5 : args4, L.lds, b->stream);
+		(void)hipLaunchKernel(k, dim3((unsigned)L.count), dim3(f.threads), (f.roi || f.planes) ? args5 : args4, L.lds, b->stream);
 		HIP_TRY(hipGetLastError());
 	}
 	/* the output passes, behind every decode family (both front ends end here): float output, tensor output into the callers' memory,
@@ -2070,6 +2124,8 @@ extern "C" int mij_batch_fetch(mij_batch *b, int slot, uint8_t *dst, size_t dst_
 	const Slot &s = b->slots[(size_t)slot];
 	if (s.desc.flags & MIJ_FLAG_SKIP)
 		return set_err(MIJ_E_STATE, "slot %d was rejected by the host stage", slot);
+	if (s.pln >= 0)
+		return set_err(MIJ_E_STATE, "mij_batch_fetch: slot %d has a plane request: it decodes no pixels", slot);
 	const size_t bytes = out_px_bytes(s);
 	if (dst_bytes < bytes)
 		return set_err(MIJ_E_ARG, "destination too small (%zu < %zu)", dst_bytes, bytes);
@@ -2164,6 +2220,8 @@ extern "C" int mij_batch_set_out_f32(mij_batch *b, int slot, const float *lut)
 	Slot &s = b->slots[(size_t)slot];
 	if (s.desc.flags & MIJ_FLAG_SKIP)
 		return set_err(MIJ_E_STATE, "slot %d was rejected by the host stage", slot);
+	if (s.pln >= 0)
+		return set_err(MIJ_E_STATE, "mij_batch_set_out_f32: slot %d has a plane request: it decodes no pixels", slot);
 	if (s.scale > 1)
 		return set_err(MIJ_E_ARG, "mij_batch_set_out_f32: slot %d is decoded at 1/%d size; float output of reduced pictures is not supported", slot, s.scale);
 	if (wants_region(s))
@@ -2312,6 +2370,8 @@ static int set_out_tensor(mij_batch *b, int slot, const mij_out_tensor *t, const
 	Slot &s = b->slots[(size_t)slot];
 	if (s.desc.flags & MIJ_FLAG_SKIP)
 		return set_err(MIJ_E_STATE, "slot %d was rejected by the host stage", slot);
+	if (s.pln >= 0)
+		return set_err(MIJ_E_STATE, "mij_batch_set_out_tensor: slot %d has a plane request: it decodes no pixels", slot);
 	if (t->dtype < MIJ_DT_U8 || t->dtype > MIJ_DT_F32 || (t->layout != MIJ_LAYOUT_HWC && t->layout != MIJ_LAYOUT_CHW))
 		return set_err(MIJ_E_ARG, "mij_batch_set_out_tensor: dtype %d / layout %d unknown", t->dtype, t->layout);
 	if (!table && t->dtype != MIJ_DT_U8)
@@ -2409,6 +2469,117 @@ extern "C" int mij_batch_set_out_tensor_oriented(mij_batch *b, int slot, const m
 	return set_out_tensor(b, slot, t, r, orientation, table);
 }
 
+/* ------------------------------------------------------------------ plane output (include/mij.h, PLANE OUTPUT) */
+
+static inline uint32_t low_bit(uint64_t v, uint32_t cap)
+{
+	uint32_t a = 1;
+	while (a < cap && !(v & a))
+		a <<= 1;
+	return a;
+}
+
+extern "C" int mij_batch_set_out_planes(mij_batch *b, int slot, const mij_out_planes *p)
+{
+	if (!p || !batch_slot(b, slot))
+		return set_err(MIJ_E_ARG, "mij_batch_set_out_planes: bad slot or request");
+	if (b->uploaded)
+		return set_err(MIJ_E_STATE, "mij_batch_set_out_planes after mij_batch_upload");
+	Slot &s = b->slots[(size_t)slot];
+	const mij_image_desc &d = s.desc;
+	if (d.flags & MIJ_FLAG_SKIP)
+		return set_err(MIJ_E_STATE, "slot %d was rejected by the host stage", slot);
+	if (s.f32 >= 0 || s.ten >= 0)
+		return set_err(MIJ_E_STATE, "mij_batch_set_out_planes: slot %d already has a %s request; a slot holds one kind", slot, s.f32 >= 0 ? "float" : "tensor");
+	if (s.scale > 1 || wants_region(s))
+		return set_err(MIJ_E_STATE, "mij_batch_set_out_planes: slot %d has a %s; planes are decoded at full size through the request's own window", slot,
+							s.scale > 1 ? "scale" : "region");
+	if (p->reserved[0] || p->reserved[1])
+		return set_err(MIJ_E_ARG, "mij_batch_set_out_planes: reserved is not 0");
+	int64_t x0 = p->x0, y0 = p->y0, w = p->w, h = p->h;
+	if (!x0 && !y0 && !w && !h)
+		w = d.width, h = d.height;
+	if (w < 1 || h < 1 || x0 < 0 || y0 < 0 || x0 + w > d.width || y0 + h > d.height)
+		return set_err(MIJ_E_ARG, "mij_batch_set_out_planes: window %d,%d %dx%d is empty or outside the %dx%d picture of slot %d", p->x0, p->y0, p->w, p->h, d.width,
+							d.height, slot);
+	mij_batch::PlnReq q;
+	q.slot = slot;
+	memset(&q.dev, 0, sizeof(q.dev));
+	int wanted = 0;
+	const int64_t lim = (int64_t)1 << 40; /* keeps the extent below in range */
+	for (int c = 0; c < 4; ++c) {
+		const mij_out_plane &pl = p->planes[c];
+		if (!pl.dst)
+			continue;
+		if (c >= d.ncomp)
+			return set_err(MIJ_E_ARG, "mij_batch_set_out_planes: a plane for component %d, slot %d has %d", c, slot, d.ncomp);
+		const mij_comp_desc &cp = d.comp[c];
+		if ((x0 * cp.h) % d.h_max || (y0 * cp.v) % d.v_max)
+			return set_err(MIJ_E_ARG, "mij_batch_set_out_planes: window origin %d,%d is off the grid of component %d (%dx%d of %dx%d)", p->x0, p->y0, c, cp.h, cp.v,
+								d.h_max, d.v_max);
+		const int64_t sx0 = x0 * cp.h / d.h_max, sy0 = y0 * cp.v / d.v_max;
+		const int64_t sx1 = std::min<int64_t>(((x0 + w) * cp.h + d.h_max - 1) / d.h_max, cp.x), sy1 = std::min<int64_t>(((y0 + h) * cp.v + d.v_max - 1) / d.v_max, cp.y);
+		if (sx1 <= sx0 || sy1 <= sy0)
+			return set_err(MIJ_E_ARG, "mij_batch_set_out_planes: the window holds no sample of component %d", c);
+		const int64_t wc = sx1 - sx0, hc = sy1 - sy0, rp = pl.row_pitch, xp = pl.x_pitch;
+		if (rp < 1 || xp < 1 || rp > lim || xp > lim)
+			return set_err(MIJ_E_ARG, "mij_batch_set_out_planes: component %d: pitches %lld, %lld are not positive (or beyond 2^40)", c, (long long)rp, (long long)xp);
+		if (hc > 1 && rp < (wc - 1) * xp + 1)
+			return set_err(MIJ_E_ARG, "mij_batch_set_out_planes: component %d: row pitch %lld lets its rows of %lld samples %lld bytes apart overlap", c, (long long)rp,
+								(long long)wc, (long long)xp);
+		const uint64_t extent = (uint64_t)((hc - 1) * rp + (wc - 1) * xp + 1);
+		const int rc = device_extent(b->ctx->device, pl.dst, extent, "plane dst");
+		if (rc != MIJ_OK)
+			return rc;
+		DevPlane &v = q.dev.c[c];
+		v.dst = (uint64_t)(uintptr_t)pl.dst;
+		v.row_pitch = rp;
+		v.x_pitch = xp;
+		v.sx0 = (uint32_t)sx0, v.sy0 = (uint32_t)sy0, v.sx1 = (uint32_t)sx1, v.sy1 = (uint32_t)sy1;
+		v.blk = DevRoi{(uint32_t)(sx0 >> 3), (uint32_t)(sy0 >> 3), (uint32_t)(((sx1 + 7) >> 3) - (sx0 >> 3)), (uint32_t)(((sy1 + 7) >> 3) - (sy0 >> 3))};
+		/* fast form: every block's row starts 8-byte aligned (dst + (8 by - sy0) * rp + 8 bx - sx0) */
+		v.form = (xp == 1 && !((v.dst - (uint64_t)sx0) & 7u) && !(rp & 7)) ? PLN_FAST : PLN_GENERAL;
+		++wanted;
+	}
+	if (!wanted)
+		return set_err(MIJ_E_ARG, "mij_batch_set_out_planes: no component is wanted");
+	/* paired form (NV12 / NV21): components 1 and 2 of one geometry and rectangle, two bytes a sample, one byte apart, on an even base */
+	DevPlane &u = q.dev.c[1], &v = q.dev.c[2];
+	if (u.dst && v.dst && u.x_pitch == 2 && v.x_pitch == 2 && u.row_pitch == v.row_pitch && d.comp[1].bw == d.comp[2].bw && d.comp[1].bh == d.comp[2].bh &&
+		 u.sx0 == v.sx0 && u.sy0 == v.sy0 && u.sx1 == v.sx1 && u.sy1 == v.sy1 && (u.dst + 1 == v.dst || v.dst + 1 == u.dst)) {
+		const uint64_t base = std::min(u.dst, v.dst);
+		const uint32_t align = low_bit((base - 2u * (uint64_t)u.sx0) | (uint64_t)u.row_pitch, 16u);
+		if (align >= 2u) {
+			const uint32_t first = u.dst < v.dst ? 1u : 2u;
+			u.form = v.form = PLN_PAIRED;
+			u.dst = v.dst = base;
+			u.first = v.first = first;
+			u.align = v.align = align;
+		}
+	}
+	if (s.pln < 0) {
+		b->pln_req.push_back(q);
+		s.pln = (int)b->pln_req.size() - 1;
+	} else {
+		b->pln_req[(size_t)s.pln] = q;
+	}
+	return MIJ_OK;
+}
+
+extern "C" int mij_batch_slot_plane_rect(const mij_batch *b, int slot, int comp, int rect[4])
+{
+	if (!rect || !batch_slot(b, slot) || comp < 0 || comp > 3)
+		return set_err(MIJ_E_ARG, "mij_batch_slot_plane_rect: bad slot, component or destination");
+	const Slot &s = b->slots[(size_t)slot];
+	if (s.pln < 0)
+		return set_err(MIJ_E_STATE, "mij_batch_slot_plane_rect: slot %d has no plane request", slot);
+	const DevPlane &v = b->pln_req[(size_t)s.pln].dev.c[comp];
+	if (!v.dst)
+		return set_err(MIJ_E_ARG, "mij_batch_slot_plane_rect: component %d of slot %d is not wanted", comp, slot);
+	rect[0] = (int)v.sx0, rect[1] = (int)v.sy0, rect[2] = (int)(v.sx1 - v.sx0), rect[3] = (int)(v.sy1 - v.sy0);
+	return MIJ_OK;
+}
+
 extern "C" int mij_batch_timer_begin(mij_batch *b)
 {
 	if (!b)
@@ -2455,6 +2626,8 @@ extern "C" int mij_batch_hash_out(mij_batch *b, int slot, uint64_t *hash)
 	if (!hash || !batch_slot(b, slot))
 		return set_err(MIJ_E_ARG, "bad argument");
 	const Slot &s = b->slots[(size_t)slot];
+	if (s.pln >= 0)
+		return set_err(MIJ_E_STATE, "mij_batch_hash_out: slot %d has a plane request: it decodes no pixels", slot);
 	if (wants_region(s))
 		return set_err(MIJ_E_STATE, "mij_batch_hash_out: slot %d decodes a region only; the rest of its picture is unspecified", slot);
 	const size_t bytes = out_px_bytes(s);
@@ -2506,6 +2679,8 @@ extern "C" int mij_batch_diff_slots(mij_batch *b, const int *sa, const int *sb, 
 		if (!batch_slot(b, sa[i]) || !batch_slot(b, sb[i]))
 			return set_err(MIJ_E_ARG, "bad slot pair %d", i);
 		const Slot &x = b->slots[(size_t)sa[i]], &y = b->slots[(size_t)sb[i]];
+		if (x.pln >= 0 || y.pln >= 0)
+			return set_err(MIJ_E_STATE, "mij_batch_diff_slots: slot pair %d: a slot with a plane request decodes no pixels", i);
 		if (wants_region(x) || wants_region(y))
 			return set_err(MIJ_E_STATE, "mij_batch_diff_slots: slot pair %d: a slot that decodes a region only cannot be compared", i);
 		/* a reduced picture leaves the rest of its region unwritten: its last, partial word is compared byte by byte */

@@ -111,6 +111,42 @@ def auto_reduce(w, h, out_w, out_h):
     return 1
 
 
+_SUBSAMPLINGS = {(1, 1): "444", (2, 1): "422", (1, 2): "440", (2, 2): "420"}
+YCBCR_FORMATS = ("planar", "nv12", "nv21")
+
+
+def ycbcr_subsampling(d):
+    """A descriptor's sampling as TensorEncoder.encode_ycbcr names it -- "444", "422", "440", "420" or "grey" -- where the file is one of
+    those five (chroma at 1 x 1 under the luma factors); "h{H}v{V}" of the luma factors for anything else (4:1:1: "h4v1")."""
+    if d.ncomp == 1:
+        return "grey"
+    lh, lv = d.comp[0].h, d.comp[0].v
+    plain = (lh, lv) == (d.h_max, d.v_max) and all((d.comp[c].h, d.comp[c].v) == (1, 1) for c in range(1, d.ncomp))
+    return _SUBSAMPLINGS[(lh, lv)] if plain and (lh, lv) in _SUBSAMPLINGS else "h%dv%d" % (lh, lv)
+
+
+def plane_windows(d, win, comps):
+    """(x0, y0, w, h) of the picture window `win` in the samples of each component of comps (include/mij.h, PLANE OUTPUT); ValueError for
+    a window off the grid of one of them"""
+    x0, y0, w, h = win
+    out = []
+    for c in comps:
+        ch, cv = d.comp[c].h, d.comp[c].v
+        if (x0 * ch) % d.h_max or (y0 * cv) % d.v_max:
+            raise ValueError("crop %s starts off the sample grid of component %d (x0 a multiple of %d / %d, y0 of %d / %d)" % (win, c, d.h_max, ch, d.v_max, cv))
+        sx0, sy0 = x0 * ch // d.h_max, y0 * cv // d.v_max
+        out.append((sx0, sy0, -(-(x0 + w) * ch // d.h_max) - sx0, -(-(y0 + h) * cv // d.v_max) - sy0))
+    return out
+
+
+def _pitches(t, what):
+    """(row pitch, sample pitch) in bytes of a 2-D uint8 tensor; the stride of an axis of one element addresses nothing"""
+    rp, xp = t.stride(0), t.stride(1)
+    if (t.shape[0] > 1 and rp < 1) or (t.shape[1] > 1 and xp < 1):
+        raise ValueError("%s has strides %s: planes need positive strides" % (what, tuple(t.stride())))
+    return (rp if rp >= 1 else 1), (xp if xp >= 1 else 1)
+
+
 def _one_hip_runtime():
     """torch and the library must share one HIP runtime, or torch's allocations are unknown to the library (which then refuses them).
     They do when torch is imported before the library is first loaded; loaded the other way round, torch brings its own copy."""
@@ -133,6 +169,7 @@ class TensorDecoder:
         self._ctx = None
         self._batch = None
         self._cap = (0, 0, 0)
+        self.last_subsampling = []  # of the last decode_ycbcr: one name per picture, None for a rejected one
 
     @property
     def device(self):
@@ -321,3 +358,136 @@ class TensorDecoder:
                 if r is not None:
                     out[i].zero_()
         return out, reasons
+
+    def decode_ycbcr(self, datas, *, format="planar", luma_only=False, crops=None, out=None, threads=16):
+        """-> (pictures, reasons): the Y, Cb and Cr samples of each JPEG as the file stores them, at their own resolutions -- no chroma
+        upsampling, no colour conversion, no RGB in between (include/mij.h, PLANE OUTPUT; k_planes_out).  pictures[i] is what
+        TensorEncoder.encode_ycbcr takes, uint8 tensors on this device:
+            format "planar"  (Y, Cb, Cr), three 2-D tensors (I420 for a 4:2:0 file)
+            format "nv12"    (Y, CbCr) with CbCr of shape [ch, cw, 2], Cb and Cr interleaved in memory
+            format "nv21"    (Y, Cb, Cr) where Cb and Cr are the two strided slices [:, :, 1] and [:, :, 0] of one [ch, cw, 2] buffer, which
+                             is NV21 in memory (torch has no view that reverses an axis)
+        and Y alone for a grey file or with luma_only=True, which transforms no chroma block at all.  A rejected picture is None with
+        its reason in reasons[i].  Pictures may differ in size and sampling; Y is H x W, Cb and Cr are ceil(H * v_c / v_max) x
+        ceil(W * h_c / h_max).  last_subsampling[i] names the file's sampling as encode_ycbcr names it ("444", "422", "440", "420",
+        "grey"; "h{H}v{V}" of the luma factors for other files, None for a rejected picture), so that
+        enc.encode_ycbcr(pictures, subsampling=dec.last_subsampling) takes the result as it is.
+        crops: None, or one (x0, y0, w, h) in picture coordinates or None per picture; every wanted component then receives the samples
+        its part of the window holds (Batch.plane_rect).  x0 and y0 lie on the grid of every wanted component (4:2:0: even); an
+        off-grid window is a ValueError.  out: None, or one entry per picture in the shapes above (None for pictures to allocate), with
+        any positive strides; a picture written into out[i] is out[i].  Planes allocated here are slices of one tensor per plane and
+        group of equally shaped pictures (three allocations for a batch of equal 4:2:0 pictures), so a kept picture keeps its group's
+        memory alive; .clone() what outlives the batch.
+        Served here: grey and YCbCr files.  RGB-tagged, CMYK, YCCK and other four-component files are rejected per picture with a
+        reason (mij_batch_set_out_planes serves them: their planes are their stored components)."""
+        datas = list(datas)
+        n = len(datas)
+        if format not in YCBCR_FORMATS:
+            raise ValueError("format must be one of %s (got %r)" % (", ".join(YCBCR_FORMATS), format))
+        if not isinstance(luma_only, bool):
+            raise ValueError("luma_only must be a bool (got %r)" % (luma_only,))
+        if crops is not None:
+            crops = list(crops)
+            if len(crops) != n:
+                raise ValueError("crops has %d windows for %d pictures" % (len(crops), n))
+            crops = [None if c is None else tuple(int(v) for v in c) for c in crops]
+            if any(c is not None and len(c) != 4 for c in crops):
+                raise ValueError("a crop is (x0, y0, w, h)")
+        if out is not None:
+            out = list(out)
+            if len(out) != n:
+                raise ValueError("out has %d entries for %d pictures" % (len(out), n))
+        # headers only: geometry, shapes and arena needs, before any device call
+        descs, reasons = [], [None] * n
+        for i, data in enumerate(datas):
+            try:
+                d = HostDecoder.probe(data, 0)
+            except MijError as e:
+                d, reasons[i] = None, str(e)
+            if d is not None and not ((d.ncomp == 1 and d.color == 0) or (d.ncomp == 3 and d.color == 1)):
+                reasons[i] = "not a grey or YCbCr file (%d components, colour mode %d): its planes are served by mij_batch_set_out_planes only" % (d.ncomp, d.color)
+                d = None
+            descs.append(d)
+        plans = [None] * n  # per picture: (components, their windows, picture window or None)
+        for i, d in enumerate(descs):
+            if d is None:
+                continue
+            comps = [0] if (luma_only or d.ncomp == 1) else [0, 1, 2]
+            win = (0, 0, d.width, d.height) if crops is None or crops[i] is None else crops[i]
+            if win[2] < 1 or win[3] < 1 or win[0] < 0 or win[1] < 0 or win[0] + win[2] > d.width or win[1] + win[3] > d.height:
+                raise ValueError("crop %s of picture %d outside its %dx%d picture" % (win, i, d.width, d.height))
+            rects = plane_windows(d, win, comps)
+            if len(comps) == 3 and format != "planar" and rects[1] != rects[2]:
+                reasons[i], descs[i] = "Cb and Cr differ in sampling: no %s" % format, None
+                continue
+            plans[i] = (comps, rects, None if crops is None or crops[i] is None else win)
+        pictures, views = [None] * n, [None] * n
+        for i, plan in enumerate(plans):  # the caller's tensors first: every ValueError comes before the first allocation on the device
+            if plan is None or out is None or out[i] is None:
+                continue
+            comps, rects, _ = plan
+            shapes = [(r[3], r[2]) for r in rects]
+            given = out[i]
+            parts = [given] if isinstance(given, torch.Tensor) else list(given)
+            if len(parts) == 2 and len(comps) == 3 and isinstance(parts[1], torch.Tensor) and parts[1].dim() == 3 and parts[1].shape[2] == 2:
+                parts = [parts[0], parts[1][:, :, 0], parts[1][:, :, 1]]
+            if len(parts) != len(comps):
+                raise ValueError("out[%d] has %d planes, %d expected" % (i, len(parts), len(comps)))
+            for k, (t, s) in enumerate(zip(parts, shapes)):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or tuple(t.shape) != s:
+                    raise ValueError("out[%d] plane %d is %s, uint8 %s expected" % (i, k, "%s %s" % (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t), s))
+                _pitches(t, "plane %d of out[%d]" % (k, i))
+                if t.device.type != "cuda" or (self._dev.index is not None and t.device != self._dev):
+                    raise ValueError("out[%d] plane %d is on %s, the decoder on %s" % (i, k, t.device, self._dev))
+            pictures[i], views[i] = given, parts
+        # the pictures to allocate, by shape: one tensor per plane and group of equal pictures, whose slices the pictures are (a batch
+        # of 256 equal pictures is three allocations, not 768)
+        groups = {}
+        for i, plan in enumerate(plans):
+            if plan is not None and views[i] is None:
+                groups.setdefault(tuple((r[3], r[2]) for r in plan[1]), []).append(i)
+        for shapes, members in groups.items():
+            g = len(members)
+            ys = torch.empty((g,) + shapes[0], dtype=torch.uint8, device=self.device).unbind(0)
+            if len(shapes) == 1:
+                for k, i in enumerate(members):
+                    pictures[i], views[i] = ys[k], [ys[k]]
+            elif format == "planar":
+                cbs, crs = (torch.empty((g,) + s, dtype=torch.uint8, device=self.device).unbind(0) for s in shapes[1:])
+                for k, i in enumerate(members):
+                    pictures[i] = (ys[k], cbs[k], crs[k])
+                    views[i] = list(pictures[i])
+            else:
+                pairs = torch.empty((g,) + shapes[1] + (2,), dtype=torch.uint8, device=self.device)
+                lo, hi = pairs[..., 0].unbind(0), pairs[..., 1].unbind(0)
+                for k, (i, pair) in enumerate(zip(members, pairs.unbind(0))):
+                    if format == "nv12":
+                        pictures[i], views[i] = (ys[k], pair), [ys[k], lo[k], hi[k]]
+                    else:
+                        pictures[i] = (ys[k], hi[k], lo[k])
+                        views[i] = list(pictures[i])
+        triples = [None if v is None else [(t,) + _pitches(t, "plane %d of picture %d" % (k, i)) for k, t in enumerate(v)] for i, v in enumerate(views)]
+        self.last_subsampling = [None if d is None else ycbcr_subsampling(d) for d in descs]
+        ok = [d for d in descs if d is not None]
+        if not ok:
+            return pictures, reasons
+        _one_hip_runtime()
+        b = self._batch_for(n, sum(Batch.coef_bytes(d) for d in ok), sum(Batch.out_bytes(d) for d in ok))
+        good = [i for i, d in enumerate(descs) if d is not None]
+        _, slots, why = b.decode_jpegs([datas[i] for i in good], 0, threads=int(threads))
+        asked = 0
+        for k, (i, sl) in enumerate(zip(good, slots)):
+            if sl < 0:
+                reasons[i], pictures[i], self.last_subsampling[i] = why[k] or "rejected", None, None
+                continue
+            b.descs[sl] = descs[i]
+            try:
+                b.set_out_planes(sl, [(t.data_ptr(), rp, xp) for t, rp, xp in triples[i]], plans[i][2])
+                asked += 1
+            except MijError as e:  # a marker behind the header changed what the file is
+                reasons[i], pictures[i], self.last_subsampling[i] = str(e), None, None
+        if asked:
+            torch.cuda.current_stream(self.device).synchronize()
+            b.submit()
+            b.wait()
+        return pictures, reasons

@@ -268,7 +268,7 @@ int mij_batch_hash_out(mij_batch *b, int slot, uint64_t *hash);
 int mij_batch_diff_slots(mij_batch *b, const int *sa, const int *sb, int n, uint64_t *ndiff);
 
 /* which kernel family the last upload chose for a slot: 0 none (skipped), 1 fused 4:2:0, 2 generic two-pass,
- * 3 fused 4:4:4, 4 fused 4:2:2, 5 fused grey, 6 fused 4:4:0, 7 fused 1x1 RGB-tagged / CMYK / YCCK, 8 reduced-size decode */
+ * 3 fused 4:4:4, 4 fused 4:2:2, 5 fused grey, 6 fused 4:4:0, 7 fused 1x1 RGB-tagged / CMYK / YCCK, 8 reduced-size decode, 9 plane output */
 int mij_batch_slot_path(const mij_batch *b, int slot);
 /* parity tests compare the kernel families: on = 1 sends every image of the batch down the two-pass path (IDCT to sample
  * planes, then resampling + colour; its pass 2 compiled per resampler where the layout allows), on = 2 also insists on
@@ -528,6 +528,54 @@ int mij_batch_set_out_tensor_resized(mij_batch *b, int slot, const mij_out_tenso
  * 5..8 run passes of their own (k_out_tensor_t, k_out_resize_t), launched only when such a request exists.
  */
 int mij_batch_set_out_tensor_oriented(mij_batch *b, int slot, const mij_out_tensor *t, const mij_out_resize *r, int32_t orientation, const void *table);
+
+/*
+ * PLANE OUTPUT (the mirror image of mij_enc_add_device_planes): a slot may ask, before upload, for the samples of its stored
+ * COMPONENTS -- the Y, Cb and Cr planes of a YCbCr file as they are coded, at their own resolutions -- in device memory the caller owns.
+ * THE CONTRACT, for a picture of W x H whose component c has sampling factors (h_c, v_c) under (h_max, v_max):
+ *   - plane c is pw_c x ph_c samples, pw_c = ceil(W * h_c / h_max), ph_c = ceil(H * v_c / v_max): mij_comp_desc.x / .y, the reference's
+ *     img_comp[c].x / .y (4:2:0: ceil(W / 2) x ceil(H / 2) chroma, the shapes mij_enc_add_device_planes takes);
+ *   - sample (x, y) of plane c is byte (x & 7, y & 7) of the reference's IDCT (codec/jpeg.c:615-679, the clamp included) of the
+ *     de-quantised block (x >> 3, y >> 3) of that component;
+ *   - nothing else is applied: no upsampling, no colour conversion, no CMYK inversion; the planes of an RGB-tagged, CMYK or YCCK file
+ *     are its stored components, in the frame header's order.  Every file the decoder accepts is eligible, whatever its factors
+ *     (4:1:1 included), baseline or progressive;
+ *   - samples of padding blocks, and of columns or rows beyond pw_c x ph_c, do not exist and are never written.
+ * Addressing: sample (y, x) of a component's window goes to dst + y * row_pitch + x * x_pitch (bytes; the convention of mij_plane).
+ * NV12 is planes[1] = {p, pitch, 2}, planes[2] = {p + 1, pitch, 2}; NV21 swaps the two; packed YCbCr has x_pitch 3.  dst NULL: the
+ * component is not wanted, and none of its blocks is transformed (luma only: a third of the blocks of a 4:4:4 file).
+ * Window (x0, y0, w, h) in picture coordinates, all 0 for the whole picture: x0 * h_c must be a multiple of h_max and y0 * v_c of v_max
+ * for every wanted component (x0 a multiple of h_max / h_c: 2 for 4:2:0 chroma); component c then receives
+ *     [x0 * h_c / h_max, ceil((x0 + w) * h_c / h_max)) x [y0 * v_c / v_max, ceil((y0 + h) * v_c / v_max))
+ * of its plane, which mij_batch_slot_plane_rect reports (x0, y0, w, h in the component's own samples; any time after the request).
+ *
+ * Rules, checked on the host: before mij_batch_upload (else MIJ_E_STATE); MIJ_E_STATE for a skipped slot; asking again replaces the
+ * request, mij_batch_reset forgets it, a refused request keeps the earlier one.  MIJ_E_ARG for: a window that is empty, leaves the
+ * picture or is off the grid above; no wanted component; a plane given for a component the file lacks; a pitch below 1; rows of one
+ * plane that overlap (row_pitch < (w_c - 1) * x_pitch + 1 where the window has more than one row); dst that is not device memory of the
+ * batch's device; a written extent [dst, last sample] not inside the one allocation hipMemGetAddressRange reports for dst; a non-zero
+ * reserved.  Planes may interleave with each other (that is NV12); the library does not look for planes that overwrite each other.
+ * A slot holds either a plane request or a float / tensor request: the second kind asked for is refused with MIJ_E_STATE.  With a
+ * plane request mij_batch_set_scale above 1, mij_batch_set_roi (other than taking a region back) and mij_batch_set_roi_auto are refused
+ * with MIJ_E_STATE, and a slot that has a scale or a region refuses the plane request likewise.
+ *
+ * A slot with a plane request launches no pixel kernel: k_planes_out (mij_planes_out_kernels.h; mij_batch_slot_path 9) writes the
+ * planes and nothing else.  Its share of the output arena is not written; mij_batch_fetch, mij_batch_fetch_f32, mij_batch_hash_out and
+ * mij_batch_diff_slots on it return MIJ_E_STATE; mij_batch_fetch_coef works; mij_batch_slot_work_items counts one item per 256 blocks
+ * of each wanted component's window (components 1 and 2 of an NV12 / NV21 request count once: one lane transforms both).  A batch
+ * without plane requests plans, uploads and launches exactly what it does without this section.  ORDERING as for tensor output.
+ */
+typedef struct {
+	void *dst;                  /* NULL: this component is not wanted */
+	int64_t row_pitch, x_pitch; /* bytes */
+} mij_out_plane;
+typedef struct {
+	mij_out_plane planes[4]; /* in the frame header's component order */
+	int32_t x0, y0, w, h;    /* window in picture coordinates; all 0: the whole picture */
+	int32_t reserved[2];     /* 0 */
+} mij_out_planes;
+int mij_batch_set_out_planes(mij_batch *b, int slot, const mij_out_planes *p);
+int mij_batch_slot_plane_rect(const mij_batch *b, int slot, int comp, int rect[4]);
 
 /*
  * Encoder half (BASELINE config 5): the JPEG writer's colour transform, edge replication, 2x2
