@@ -38,6 +38,8 @@ from .binding import (  # noqa: F401
     MIJ_DT_F32,
     MIJ_LAYOUT_HWC,
     MIJ_LAYOUT_CHW,
+    MIJ_ARITH_STB,
+    MIJ_ARITH_LIBJPEG,
     Context,
     Encoder,
     InTensor,

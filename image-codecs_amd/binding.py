@@ -573,6 +573,7 @@ def _check(rc, what):
 
 MIJ_DT_U8, MIJ_DT_F16, MIJ_DT_BF16, MIJ_DT_F32 = 0, 1, 2, 3
 MIJ_LAYOUT_HWC, MIJ_LAYOUT_CHW = 0, 1
+MIJ_ARITH_STB, MIJ_ARITH_LIBJPEG = 0, 1  # mij_batch_set_arith
 _DTYPES = {"u8": MIJ_DT_U8, "f16": MIJ_DT_F16, "bf16": MIJ_DT_BF16, "f32": MIJ_DT_F32}
 _LAYOUTS = {"HWC": MIJ_LAYOUT_HWC, "CHW": MIJ_LAYOUT_CHW}
 
@@ -653,7 +654,7 @@ KERNEL_KINDS = (
     "MK_RS_FAST+RS_GEN4", "MK_420", "MK_422", "MK_444", "MK_GREY", "MK_440", "MK_420W", "MK_440W", "MK_420X", "MK_420S", "MK_420T", "MK_422W",
     "MK_422X", "MK_422S", "MK_422T", "MK_1X1C", "MK_420C", "MK_440C", "MK_SCALED+SC_Y", "MK_SCALED+SC_444", "MK_SCALED+SC_420",
     "MK_SCALED+SC_422", "MK_444R", "MK_GREYR", "MK_1X1CR", "MK_SCALEDR+SC_Y", "MK_SCALEDR+SC_444", "MK_SCALEDR+SC_420", "MK_SCALEDR+SC_422",
-    "MK_PLANES_OUT",
+    "MK_PLANES_OUT", "MK_LJ_IDCT", "MK_LJ_COLOR+LJ_11", "MK_LJ_COLOR+LJ_21", "MK_LJ_COLOR+LJ_12", "MK_LJ_COLOR+LJ_22",
 )
 
 
@@ -981,6 +982,13 @@ class Batch:
         L = lib()
         L.mij_batch_set_scale.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _check(L.mij_batch_set_scale(self._h, int(slot), int(denom)), "mij_batch_set_scale")
+
+    def set_arith(self, slot, arith):
+        """mij_batch_set_arith: ARITH_LIBJPEG decodes the slot with libjpeg's arithmetic (ISLOW inverse DCT, fancy upsampling, jdcolor
+        tables: Pillow's pixels byte for byte), ARITH_STB (the default) with the reference's; before upload."""
+        L = lib()
+        L.mij_batch_set_arith.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        _check(L.mij_batch_set_arith(self._h, int(slot), int(arith)), "mij_batch_set_arith")
 
     def set_roi(self, slot, x0, y0, w, h):
         """mij_batch_set_roi: only the MCUs that the rectangle (x0, y0, w, h) of the slot's stored picture needs are decoded; the pixels

@@ -23,6 +23,7 @@
 #include "mij_scaled_kernels.h"
 #include "mij_entropy_kernels.h"
 #include "mij_planes_out_kernels.h"
+#include "mij_libjpeg_kernels.h"
 
 using namespace mij;
 
@@ -60,7 +61,9 @@ extern "C" int mij_device_count(void)
 /* ------------------------------------------------------------------ decode kernel families */
 
 /* kernel families of a launch plan, in launch order.  MK_RS_FAST + RS_*: pass 2 compiled per resampler (k_resample_fast) */
-enum { MK_PLANES = 0, MK_RESAMPLE, MK_RS_FAST, MK_420 = MK_RS_FAST + RS_KINDS, MK_422, MK_444, MK_GREY, MK_440, MK_420W, MK_440W /* k_fused420w / k_fused440w: 512 threads, wide pictures */, MK_420X /* 1024 threads: one workgroup per CU */, MK_420S, MK_420T /* 128 / 64 threads: narrow pictures */, MK_422W, MK_422X, MK_422S, MK_422T /* k_fused422 with 512 / 1024 / 128 / 64 threads */, MK_1X1C /* k_fused1x1c: RGB-tagged / CMYK / YCCK at 1x1 */, MK_420C, MK_440C /* column segments: a row of MCUs beyond a CU's LDS */, MK_SCALED /* + SC_*: reduced-size decode, k_scaled per layout */, MK_444R = MK_SCALED + SC_LAYOUTS, MK_GREYR, MK_1X1CR /* windowed forms of k_fused444 / k_fused_grey / k_fused1x1c: slots with a region (mij_batch_set_roi) */, MK_SCALEDR /* + SC_*: k_scaled on a window */, MK_PLANES_OUT = MK_SCALEDR + SC_LAYOUTS /* k_planes_out: slots with a plane request (mij_batch_set_out_planes) */, MK_KINDS };
+enum { MK_PLANES = 0, MK_RESAMPLE, MK_RS_FAST, MK_420 = MK_RS_FAST + RS_KINDS, MK_422, MK_444, MK_GREY, MK_440, MK_420W, MK_440W /* k_fused420w / k_fused440w: 512 threads, wide pictures */, MK_420X /* 1024 threads: one workgroup per CU */, MK_420S, MK_420T /* 128 / 64 threads: narrow pictures */, MK_422W, MK_422X, MK_422S, MK_422T /* k_fused422 with 512 / 1024 / 128 / 64 threads */, MK_1X1C /* k_fused1x1c: RGB-tagged / CMYK / YCCK at 1x1 */, MK_420C, MK_440C /* column segments: a row of MCUs beyond a CU's LDS */, MK_SCALED /* + SC_*: reduced-size decode, k_scaled per layout */, MK_444R = MK_SCALED + SC_LAYOUTS, MK_GREYR, MK_1X1CR /* windowed forms of k_fused444 / k_fused_grey / k_fused1x1c: slots with a region (mij_batch_set_roi) */, MK_SCALEDR /* + SC_*: k_scaled on a window */, MK_PLANES_OUT = MK_SCALEDR + SC_LAYOUTS /* k_planes_out: slots with a plane request (mij_batch_set_out_planes) */, MK_LJ_IDCT /* libjpeg arithmetic (mij_batch_set_arith): k_lj_idct, pass 1 */, MK_LJ_COLOR /* + LJ_*: k_lj_color per chroma subsampling, pass 2 */, MK_KINDS = MK_LJ_COLOR + 4 };
+/* the chroma subsamplings of k_lj_color; LJ_11 also takes one-component files and luma-only outputs */
+enum { LJ_11 = 0, LJ_21, LJ_12, LJ_22 };
 
 /* A family's kernels per variant = 4 * (n_out == 4) + 2 * wide IDCT + compact planes (k_resample_fast: 4 * (n_out == 4) + 2 * YCbCr
  * colour; k_scaled: 2 * (log2 of the scale - 1) + compact planes).  Every decode kernel takes (const DevImage *, const Work *, const uint8_t *in, uint8_t *out); io says which arenas in and
@@ -135,6 +138,12 @@ static const Family families[MK_KINDS] = {
 	{256, COEF_OUT, false, MIJ_SCR(SC_420), true},
 	{256, COEF_OUT, false, MIJ_SCR(SC_422), true},
 	/* MK_PLANES_OUT */ {256, COEF_OUT, false, MIJ_WBP(k_planes_out), false, true},
+	/* MK_LJ_IDCT: variant = compact planes */ {256, COEF_PLANES, false, {MIJ_K(k_lj_idct<false>), MIJ_K(k_lj_idct<true>)}},
+	/* MK_LJ_COLOR + LJ_11, LJ_21, LJ_12, LJ_22: variant = n_out - 1 */
+	{256, PLANES_OUT, false, {MIJ_K(k_lj_color<1, 1, 1>), MIJ_K(k_lj_color<1, 1, 2>), MIJ_K(k_lj_color<1, 1, 3>), MIJ_K(k_lj_color<1, 1, 4>)}},
+	{256, PLANES_OUT, false, {nullptr, nullptr, MIJ_K(k_lj_color<2, 1, 3>), MIJ_K(k_lj_color<2, 1, 4>)}},
+	{256, PLANES_OUT, false, {nullptr, nullptr, MIJ_K(k_lj_color<1, 2, 3>), MIJ_K(k_lj_color<1, 2, 4>)}},
+	{256, PLANES_OUT, false, {nullptr, nullptr, MIJ_K(k_lj_color<2, 2, 3>), MIJ_K(k_lj_color<2, 2, 4>)}},
 };
 /* MK_420's pipelined twins (k_fused420p), by variant: compact planes without the wide IDCT only.  Not a family: a launch of MK_420 takes the twin of
  * its variant where band_prefetch says so, and everything that names a picture's kernel (kind, variant, segments) stays what it was. */
@@ -296,7 +305,7 @@ extern "C" int mij_ctx_info(const mij_ctx *ctx, char *arch, size_t arch_len, int
 /* ------------------------------------------------------------------ batch */
 
 /* the kernel family the last upload chose for a slot (mij_batch_slot_path) */
-enum SlotPath { PATH_NONE = 0, PATH_420, PATH_TWO_PASS, PATH_444, PATH_422, PATH_GREY, PATH_440, PATH_1X1C, PATH_SCALED, PATH_PLANES_OUT };
+enum SlotPath { PATH_NONE = 0, PATH_420, PATH_TWO_PASS, PATH_444, PATH_422, PATH_GREY, PATH_440, PATH_1X1C, PATH_SCALED, PATH_PLANES_OUT, PATH_LIBJPEG };
 
 /* what classify chose for a slot: the path, the family (MK_*) and variant whose work list takes its items (two-pass: pass 2's),
  * column segments per band, and the LDS of a whole row of MCUs (the band kernels) */
@@ -320,6 +329,7 @@ struct Slot {
 	int ten;           /* tensor output: index of the slot's request (mij_batch::ten_req), -1 none */
 	int pln;           /* plane output: index of the slot's request (mij_batch::pln_req), -1 none */
 	int scale;         /* reduced-size decode (mij_batch_set_scale): 1, 2, 4 or 8; the stored picture is out_w(s) x out_h(s) */
+	int arith;         /* MIJ_ARITH_STB, or MIJ_ARITH_LIBJPEG (mij_batch_set_arith): the slot takes k_lj_idct and k_lj_color */
 	/* region of interest: what was asked for (mij_batch_set_roi: roi_on and roi[] = x0, y0, w, h in stored pixels; mij_batch_set_roi_auto), and
 	 * what the last upload made of it -- the region in force (reg, reg_px: none for two-pass slots and for windows that need every MCU), the
 	 * decoded rectangle (rect) and the rectangle of lane units the windowed kernels count through (win) */
@@ -798,6 +808,7 @@ static int add_common(mij_batch *b, const mij_image_desc *d, int clone_of, bool 
 	s.ten = -1;
 	s.pln = -1;
 	s.scale = 1;
+	s.arith = MIJ_ARITH_STB;
 	s.roi_on = s.roi_auto = s.reg = false;
 	s.work_items = 0;
 	if (clone_of < 0) {
@@ -931,6 +942,8 @@ extern "C" int mij_batch_set_scale(mij_batch *b, int slot, int denom)
 	if (denom > 1 && scaled_layout(s.desc) < 0)
 		return set_err(MIJ_E_ARG, "mij_batch_set_scale: slot %d cannot be decoded at reduced size (grey, or YCbCr 4:4:4 / 4:2:0 / 4:2:2 only; "
 										  "%d components, colour mode %d, luma %dx%d of %dx%d)", slot, s.desc.ncomp, s.desc.color, s.desc.comp[0].h, s.desc.comp[0].v, s.desc.h_max, s.desc.v_max);
+	if (denom > 1 && s.arith == MIJ_ARITH_LIBJPEG)
+		return set_err(MIJ_E_ARG, "mij_batch_set_scale: slot %d is decoded with libjpeg's arithmetic, which has no reduced-size form", slot);
 	if (denom > 1 && s.f32 >= 0)
 		return set_err(MIJ_E_ARG, "mij_batch_set_scale: slot %d has a float output request; float output of reduced pictures is not supported", slot);
 	if (denom > 1 && s.pln >= 0)
@@ -938,6 +951,50 @@ extern "C" int mij_batch_set_scale(mij_batch *b, int slot, int denom)
 	if (denom != s.scale && s.ten >= 0)
 		return set_err(MIJ_E_STATE, "mij_batch_set_scale: slot %d already has a tensor request for its %dx%d picture; set the scale first", slot, out_w(s), out_h(s));
 	s.scale = denom;
+	return MIJ_OK;
+}
+
+/* Which k_lj_color form (LJ_*) decodes a picture with libjpeg's arithmetic, or -1: one component; or three-component YCbCr whose luma has
+ * the picture's resolution and whose chroma planes share 4:4:4, 4:2:2, 4:4:0 or 4:2:0 subsampling (fewer than three channels: the luma alone) */
+static int lj_layout(const mij_image_desc &d)
+{
+	if (d.n_out < 1 || d.n_out > 4)
+		return -1;
+	if (d.ncomp == 1 && d.color == MIJ_COLOR_GREY)
+		return LJ_11;
+	if (d.ncomp != 3 || (d.color != MIJ_COLOR_YCBCR && !(d.color == MIJ_COLOR_GREY && d.n_out < 3)))
+		return -1;
+	if (d.comp[0].h != d.h_max || d.comp[0].v != d.v_max || d.comp[1].h != d.comp[2].h || d.comp[1].v != d.comp[2].v)
+		return -1;
+	if (d.h_max % d.comp[1].h || d.v_max % d.comp[1].v)
+		return -1;
+	const int hs = d.h_max / d.comp[1].h, vs = d.v_max / d.comp[1].v;
+	if (hs < 1 || hs > 2 || vs < 1 || vs > 2)
+		return -1;
+	return d.n_out < 3 ? LJ_11 : (hs == 2 ? (vs == 2 ? LJ_22 : LJ_21) : (vs == 2 ? LJ_12 : LJ_11));
+}
+
+extern "C" int mij_batch_set_arith(mij_batch *b, int slot, int arith)
+{
+	if (!batch_slot(b, slot, "mij_batch_set_arith: bad slot"))
+		return MIJ_E_ARG;
+	if (b->uploaded)
+		return set_err(MIJ_E_STATE, "mij_batch_set_arith after mij_batch_upload");
+	Slot &s = b->slots[(size_t)slot];
+	if (s.desc.flags & MIJ_FLAG_SKIP)
+		return set_err(MIJ_E_STATE, "slot %d was rejected by the host stage", slot);
+	if (arith != MIJ_ARITH_STB && arith != MIJ_ARITH_LIBJPEG)
+		return set_err(MIJ_E_ARG, "mij_batch_set_arith: arithmetic %d is neither MIJ_ARITH_STB nor MIJ_ARITH_LIBJPEG", arith);
+	if (arith == MIJ_ARITH_LIBJPEG) {
+		if (lj_layout(s.desc) < 0)
+			return set_err(MIJ_E_ARG, "mij_batch_set_arith: slot %d cannot be decoded with libjpeg's arithmetic (grey, or YCbCr 4:4:4 / 4:2:2 / 4:4:0 / 4:2:0 only; "
+											  "%d components, colour mode %d, luma %dx%d of %dx%d)", slot, s.desc.ncomp, s.desc.color, s.desc.comp[0].h, s.desc.comp[0].v, s.desc.h_max, s.desc.v_max);
+		if (s.scale > 1)
+			return set_err(MIJ_E_ARG, "mij_batch_set_arith: slot %d is decoded at 1/%d size; libjpeg's reduced transforms are not implemented", slot, s.scale);
+		if (s.pln >= 0)
+			return set_err(MIJ_E_STATE, "mij_batch_set_arith: slot %d has a plane request, whose samples are the reference's", slot);
+	}
+	s.arith = arith;
 	return MIJ_OK;
 }
 
@@ -1081,6 +1138,8 @@ extern "C" int mij_batch_set_color(mij_batch *b, int slot, int color)
 		return rc;
 	if (s.scale > 1 && scaled_layout(d) < 0)
 		return set_err(MIJ_E_ARG, "mij_batch_set_color: slot %d is decoded at 1/%d size, which colour mode %d does not support", slot, s.scale, color);
+	if (s.arith == MIJ_ARITH_LIBJPEG && lj_layout(d) < 0)
+		return set_err(MIJ_E_ARG, "mij_batch_set_color: slot %d is decoded with libjpeg's arithmetic, which colour mode %d does not support", slot, color);
 	s.desc.color = color;
 	s.dev.color = color;
 	b->uploaded = b->launched = false;
@@ -1206,6 +1265,8 @@ static Choice classify(const mij_batch *b, const Slot &s)
 		return Choice();
 	if (s.pln >= 0) /* plane output: no pixel kernel, whatever the layout and whatever force_generic says */
 		return Choice{PATH_PLANES_OUT, MK_PLANES_OUT, (var & 3) | (b->pln_req[(size_t)s.pln].dev.c[1].form == PLN_PAIRED ? 4 : 0)};
+	if (s.arith == MIJ_ARITH_LIBJPEG) /* its own two passes, whatever force_generic says; the variant is pass 2's: n_out - 1 */
+		return Choice{PATH_LIBJPEG, MK_LJ_COLOR + lj_layout(d), d.n_out - 1};
 	if (s.scale > 1) /* reduced-size decode: one family per layout, whatever force_generic says (the two-pass path has no such form) */
 		return Choice{PATH_SCALED, MK_SCALED + scaled_layout(d), (s.scale == 2 ? 0 : (s.scale == 4 ? 2 : 4)) | (s.coef_bytes_fmt ? 1 : 0)};
 	if (!b->force_generic) {
@@ -1852,6 +1913,19 @@ static void plan_decode(mij_batch *b, Plan &p)
 				L.push_back(Work4{(uint32_t)i, 0u, f, 0u});
 			break;
 		}
+		case PATH_LIBJPEG: { /* pass 2's items of MIJ_LJ_ITEM_W x MIJ_LJ_ITEM_H pixels in L, pass 1's blocks in the MK_LJ_IDCT list */
+			for (uint32_t ty = 0; ty * MIJ_LJ_ITEM_H < (uint32_t)d.height; ++ty)
+				for (uint32_t tx = 0; tx * MIJ_LJ_ITEM_W < (uint32_t)d.width; ++tx)
+					L.push_back(Work4{(uint32_t)i, tx, ty, 0u});
+			const int ncomp = c.kind == MK_LJ_COLOR + LJ_11 && (d.ncomp == 1 || d.n_out < 3) ? 1 : d.ncomp; /* luma alone: no chroma block is transformed */
+			for (int comp = 0; comp < ncomp; ++comp)
+				push_blocks(p.lists[MK_LJ_IDCT][s.coef_bytes_fmt ? 1 : 0], (uint32_t)i, d, comp);
+			for (int comp = 0; comp < ncomp; ++comp) { /* its sample planes in the scratch arena, as the two-pass slots' */
+				s.dev.comp[comp].plane_off = p.planes_need;
+				p.planes_need += align_up((size_t)d.comp[comp].bw * 8 * d.comp[comp].bh * 8, 256);
+			}
+			break;
+		}
 		default: { /* PATH_TWO_PASS: pass 2's rows in L, pass 1's blocks in the MK_PLANES list */
 			/* the vs == 2 forms of k_resample_fast take item r as output rows r-1 .. r+2 (row pairs around a chroma row) */
 			const uint32_t r_end = (uint32_t)d.height + ((c.kind == MK_RS_FAST + RS_V2 || c.kind == MK_RS_FAST + RS_HV2) ? 2u : 0u);
@@ -2037,6 +2111,9 @@ extern "C" int mij_batch_upload(mij_batch *b)
 	for (size_t i = 0; i < b->slots.size(); ++i) /* flags and colour may have changed since mij_batch_set_scale */
 		if (b->slots[i].scale > 1 && !(b->slots[i].desc.flags & MIJ_FLAG_SKIP) && scaled_layout(b->slots[i].desc) < 0)
 			return set_err(MIJ_E_ARG, "mij_batch_upload: slot %zu cannot be decoded at 1/%d size", i, b->slots[i].scale);
+	for (size_t i = 0; i < b->slots.size(); ++i) /* ... and since mij_batch_set_arith */
+		if (b->slots[i].arith == MIJ_ARITH_LIBJPEG && !(b->slots[i].desc.flags & MIJ_FLAG_SKIP) && lj_layout(b->slots[i].desc) < 0)
+			return set_err(MIJ_E_ARG, "mij_batch_upload: slot %zu cannot be decoded with libjpeg's arithmetic", i);
 	Plan p;
 	int rc;
 	if ((rc = resolve_regions(b)) != MIJ_OK)
@@ -2494,6 +2571,8 @@ extern "C" int mij_batch_set_out_planes(mij_batch *b, int slot, const mij_out_pl
 	if (s.scale > 1 || wants_region(s))
 		return set_err(MIJ_E_STATE, "mij_batch_set_out_planes: slot %d has a %s; planes are decoded at full size through the request's own window", slot,
 							s.scale > 1 ? "scale" : "region");
+	if (s.arith == MIJ_ARITH_LIBJPEG)
+		return set_err(MIJ_E_STATE, "mij_batch_set_out_planes: slot %d is decoded with libjpeg's arithmetic; plane output has the reference's samples only", slot);
 	if (p->reserved[0] || p->reserved[1])
 		return set_err(MIJ_E_ARG, "mij_batch_set_out_planes: reserved is not 0");
 	int64_t x0 = p->x0, y0 = p->y0, w = p->w, h = p->h;

@@ -5,7 +5,7 @@ Importing this module imports torch; ``import image_codecs_amd`` alone does not 
 from here on first use)."""
 import torch
 
-from .binding import FILTERS, Batch, Context, HostDecoder, MijError, exif_orientation, MIJ_DT_U8, MIJ_DT_F16, MIJ_DT_BF16, MIJ_DT_F32, MIJ_LAYOUT_HWC, MIJ_LAYOUT_CHW
+from .binding import FILTERS, Batch, Context, HostDecoder, MijError, exif_orientation, MIJ_DT_U8, MIJ_DT_F16, MIJ_DT_BF16, MIJ_DT_F32, MIJ_LAYOUT_HWC, MIJ_LAYOUT_CHW, MIJ_ARITH_LIBJPEG
 
 _DT = {torch.uint8: MIJ_DT_U8, torch.float16: MIJ_DT_F16, torch.bfloat16: MIJ_DT_BF16, torch.float32: MIJ_DT_F32}
 _BITS = {torch.uint8: torch.uint8, torch.float16: torch.int16, torch.bfloat16: torch.int16, torch.float32: torch.int32}
@@ -103,6 +103,23 @@ def reducible(d):
     return (d.h_max, d.v_max) in ((1, 1), (2, 2), (2, 1))
 
 
+ARITHMETICS = ("stb", "libjpeg")
+
+
+def libjpeg_decodable(d):
+    """Whether mij_batch_set_arith takes a picture with descriptor d for libjpeg's arithmetic (include/mij.h, LIBJPEG ARITHMETIC): one
+    component, or three-component YCbCr whose luma has the picture's resolution with 4:4:4, 4:2:2, 4:4:0 or 4:2:0 chroma."""
+    if d.ncomp == 1 and d.color == 0:
+        return True
+    if d.ncomp != 3 or d.color not in (0, 1) or (d.color == 0 and d.n_out >= 3):
+        return False
+    if (d.comp[0].h, d.comp[0].v) != (d.h_max, d.v_max) or (d.comp[1].h, d.comp[1].v) != (d.comp[2].h, d.comp[2].v):
+        return False
+    if d.h_max % d.comp[1].h or d.v_max % d.comp[1].v:
+        return False
+    return (d.h_max // d.comp[1].h, d.v_max // d.comp[1].v) in _SUBSAMPLINGS
+
+
 def auto_reduce(w, h, out_w, out_h):
     """The largest denominator at which a w x h picture, reduced, is still at least out_w x out_h: never upsample from a reduced picture"""
     for s in (8, 4, 2):
@@ -170,6 +187,7 @@ class TensorDecoder:
         self._batch = None
         self._cap = (0, 0, 0)
         self.last_subsampling = []  # of the last decode_ycbcr: one name per picture, None for a rejected one
+        self.last_arithmetic = []  # of the last decode: "stb" or "libjpeg" per picture, None for a rejected one
 
     @property
     def device(self):
@@ -202,7 +220,7 @@ class TensorDecoder:
         return self._batch
 
     def decode(self, datas, *, req_comp=3, crops=None, flip_x=None, flip_y=None, layout="CHW", dtype=torch.float16, mean=None, std=None,
-               out=None, threads=16, size=None, filter="bilinear", orientation=None, reduce=None, roi=False):
+               out=None, threads=16, size=None, filter="bilinear", orientation=None, reduce=None, roi=False, arithmetic="stb"):
         """-> (tensor, reasons).  crops: None (the whole picture; every picture the same size) or one (x0, y0, w, h) per picture, all of
         the same w and h.  size: None, or (out_h, out_w): each window is resized to it with filter (box, bilinear, hamming, bicubic or
         lanczos; the exact integer contract of mij_batch_set_out_tensor_resized, Pillow's for one channel, crop first), and windows and
@@ -218,7 +236,16 @@ class TensorDecoder:
         RGB-tagged, CMYK) is rejected with its reason when s > 1.  "auto" (needs size= and crops=None) takes per picture the largest s at
         which the displayed reduced picture is still at least out_w x out_h -- it never upsamples from a reduced picture -- and 1 for
         layouts without a reduced decode.  roi: False, or True: with crops, every picture decodes only the MCUs its window reads
-        (mij_batch_set_roi_auto; the tensor is the same, bit for bit); with crops=None it changes nothing."""
+        (mij_batch_set_roi_auto; the tensor is the same, bit for bit); with crops=None it changes nothing.  arithmetic: "stb" (the
+        reference's pixels) or "libjpeg": every picture is decoded with libjpeg's arithmetic (mij_batch_set_arith: ISLOW inverse DCT,
+        fancy upsampling, the jdcolor tables), so the pixels under crops, size, orientation and the tables are the ones
+        PIL.Image.open(...).convert("RGB") and torchvision.io.decode_jpeg give, byte for byte; it takes no reduce other than None or 1
+        (ValueError), and a picture whose layout it does not serve (4:1:1, RGB-tagged, CMYK) is rejected with its reason.
+        last_arithmetic[i] names what picture i used (None for a rejected one)."""
+        if arithmetic not in ARITHMETICS:
+            raise ValueError("arithmetic must be one of %s (got %r)" % (", ".join(ARITHMETICS), arithmetic))
+        if arithmetic == "libjpeg" and not (reduce is None or (isinstance(reduce, int) and not isinstance(reduce, bool) and reduce == 1)):
+            raise ValueError("arithmetic='libjpeg' has no reduced-size decode: reduce must be None or 1 (got %r)" % (reduce,))
         if not isinstance(roi, bool):
             raise ValueError("roi must be False or True (got %r)" % (roi,))
         datas = list(datas)
@@ -264,6 +291,9 @@ class TensorDecoder:
         for i, d in enumerate(descs):
             if d is not None and scales[i] > 1 and not reducible(d):
                 refused[i] = "no reduced-size decode for this layout (%d components, colour mode %d, luma %dx%d of %dx%d)" % (
+                    d.ncomp, d.color, d.comp[0].h, d.comp[0].v, d.h_max, d.v_max)
+            elif d is not None and arithmetic == "libjpeg" and not libjpeg_decodable(d):
+                refused[i] = "no decode with libjpeg's arithmetic for this layout (%d components, colour mode %d, luma %dx%d of %dx%d)" % (
                     d.ncomp, d.color, d.comp[0].h, d.comp[0].v, d.h_max, d.v_max)
         dsz = [None if z is None or i in refused else (-(-z[0] // scales[i]), -(-z[1] // scales[i])) for i, z in enumerate(dsz)]
         chans = {d.n_out for d in ok}
@@ -316,6 +346,7 @@ class TensorDecoder:
             row_pitch, plane_pitch = st[1], 0
         if not ok_strides:
             raise ValueError("out strides %s: %s needs unit-stride channels / pixels" % (st, layout))
+        self.last_arithmetic = [None] * n
         if n == 0:
             return out, reasons
         _one_hip_runtime()
@@ -340,6 +371,13 @@ class TensorDecoder:
                 except MijError as e:  # a marker behind the header changed the colour branch
                     reasons[i] = str(e)
                     continue
+            if arithmetic == "libjpeg":
+                try:
+                    b.set_arith(sl, MIJ_ARITH_LIBJPEG)
+                except MijError as e:  # a marker behind the header changed the colour branch
+                    reasons[i] = str(e)
+                    continue
+            self.last_arithmetic[i] = arithmetic
             x0, y0 = wins[i][0], wins[i][1]
             lay = MIJ_LAYOUT_CHW if layout == "CHW" else MIJ_LAYOUT_HWC
             if size is None:

@@ -268,7 +268,8 @@ int mij_batch_hash_out(mij_batch *b, int slot, uint64_t *hash);
 int mij_batch_diff_slots(mij_batch *b, const int *sa, const int *sb, int n, uint64_t *ndiff);
 
 /* which kernel family the last upload chose for a slot: 0 none (skipped), 1 fused 4:2:0, 2 generic two-pass,
- * 3 fused 4:4:4, 4 fused 4:2:2, 5 fused grey, 6 fused 4:4:0, 7 fused 1x1 RGB-tagged / CMYK / YCCK, 8 reduced-size decode, 9 plane output */
+ * 3 fused 4:4:4, 4 fused 4:2:2, 5 fused grey, 6 fused 4:4:0, 7 fused 1x1 RGB-tagged / CMYK / YCCK, 8 reduced-size decode, 9 plane output,
+ * 10 libjpeg arithmetic (mij_batch_set_arith) */
 int mij_batch_slot_path(const mij_batch *b, int slot);
 /* parity tests compare the kernel families: on = 1 sends every image of the batch down the two-pass path (IDCT to sample
  * planes, then resampling + colour; its pass 2 compiled per resampler where the layout allows), on = 2 also insists on
@@ -302,6 +303,61 @@ static inline int mij_scaled_dim(int v, int denom) { return (v + denom - 1) / de
 int mij_batch_set_scale(mij_batch *b, int slot, int denom);
 /* the stored picture's size: the descriptor's, or the reduced one */
 int mij_batch_slot_out_size(const mij_batch *b, int slot, int *w, int *h);
+
+/*
+ * LIBJPEG ARITHMETIC: a slot may ask, before upload, to be decoded with the arithmetic of libjpeg's default decode (libjpeg-turbo as
+ * Pillow, torchvision and OpenCV use it: ISLOW inverse DCT, fancy upsampling, the jdcolor tables) instead of the reference's, so that its
+ * pixels are those libraries' pixels byte for byte.  Nothing changes without the request: the stbi_* names and every other path keep the
+ * reference's bytes, and a batch without a request plans and launches exactly what it does without this section.
+ * THE CONTRACT (tests/libjpeg_model.py restates it in numpy).  Input: the slot's quantised coefficients c[u][v] and tables q[u][v] in
+ * natural order.  All arithmetic is 32-bit two's-complement and wrapping; shifts are arithmetic.
+ *   De-quantise: d = c * q, the 32-bit product (not the reference's (short)).
+ *   Inverse DCT (jidctint.c: CONST_BITS 13, PASS1_BITS 2): the 1-D transform below on the eight columns with descale (x + 1024) >> 11
+ *   into a 32-bit workspace, then on the eight workspace rows with descale (x + 131072) >> 18; sample = clamp(result + 128, 0, 255).
+ *       z1 = (s2 + s6) * 4433;  t2 = z1 - s6 * 15137;  t3 = z1 + s2 * 6270
+ *       t0 = (s0 + s4) << 13;   t1 = (s0 - s4) << 13
+ *       e0 = t0 + t3; e3 = t0 - t3; e1 = t1 + t2; e2 = t1 - t2
+ *       a = s7; b = s5; c = s3; d = s1
+ *       z1 = a + d; z2 = b + c; z3 = a + c; z4 = b + d; z5 = (z3 + z4) * 9633
+ *       a *= 2446; b *= 16819; c *= 25172; d *= 12299
+ *       z1 *= -7373; z2 *= -20995; z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5
+ *       a += z1 + z3; b += z2 + z4; c += z2 + z3; d += z1 + z4
+ *       out = (e0 + d, e1 + c, e2 + b, e3 + a, e3 - a, e2 - b, e1 - c, e0 - d)
+ *   libjpeg's zero-column and zero-row shortcuts give the same values.  The clamp is libjpeg-turbo's SIMD behaviour; libjpeg's C code
+ *   wraps through a 1024-entry table beyond +-512 instead.  The two agree on every stream an encoder wrote.
+ *   Planes: component c is ph_c x pw_c = ceil(H * v_c / v_max) x ceil(W * h_c / h_max) samples (mij_comp_desc.y / .x); samples of the
+ *   padding blocks beyond that are never used as neighbours.
+ *   Upsampling (jdsample.c, fancy); p is a chroma plane, row and column indices are clamped to [0, ph_c - 1] and [0, pw_c - 1]:
+ *       4:2:2 (h2v1), per row:     out[2i] = (3 p[i] + p[i-1] + 1) >> 2,  out[2i+1] = (3 p[i] + p[i+1] + 2) >> 2
+ *                                  (so out[0] = p[0] and out[2 pw_c - 1] = p[pw_c - 1])
+ *       4:4:0 (h1v2), per column:  out[2j] = (3 p[j] + p[j-1] + 1) >> 2,  out[2j+1] = (3 p[j] + p[j+1] + 2) >> 2
+ *       4:2:0 (h2v2):              s[2j] = 3 p[j] + p[j-1], s[2j+1] = 3 p[j] + p[j+1] down the columns, unshifted; then per row
+ *                                  out[2i] = (3 s[i] + s[i-1] + 8) >> 4,  out[2i+1] = (3 s[i] + s[i+1] + 7) >> 4
+ *                                  (so out[0] = (4 s[0] + 8) >> 4 and out[2 pw_c - 1] = (4 s[pw_c - 1] + 7) >> 4)
+ *   libjpeg's small-width rule: when pw_c <= 2, 4:2:2 and 4:2:0 are not filtered at all: every chroma sample is replicated 2 x 1 or
+ *   2 x 2.  4:4:0 has no such rule.  The result is cut to W x H.
+ *   Colour (jdcolor.c, SCALEBITS 16), with cb -= 128 and cr -= 128:
+ *       R = clamp(Y + ((91881 cr + 32768) >> 16))
+ *       G = clamp(Y + ((-22554 cb - 46802 cr + 32768) >> 16))
+ *       B = clamp(Y + ((116130 cb + 32768) >> 16))
+ *   Output channels: n_out 3: R, G, B; 4: R, G, B, 255; 1: Y alone (libjpeg's JCS_GRAYSCALE, Pillow's draft("L")); 2: Y, 255; a
+ *   one-component file: its samples, replicated for n_out >= 3.
+ * Served: one component, and three-component YCbCr (MIJ_COLOR_YCBCR; n_out < 3: its luma) whose luma has the picture's resolution with
+ * 4:4:4, 4:2:2, 4:4:0 or 4:2:0 chroma; baseline or progressive; either coefficient-plane format; either front end.  Refused, not
+ * approximated (MIJ_E_ARG): 4:1:1 and other sampling factors, RGB-tagged, CMYK and YCCK files, and a slot with mij_batch_set_scale above 1,
+ * in either order of the two calls (libjpeg's reduced transforms are another contract).  Not promised: parity for truncated progressive
+ * files, where libjpeg smooths blocks whose scans are missing.
+ * mij_batch_set_arith: before mij_batch_upload (else MIJ_E_STATE); MIJ_E_STATE for a skipped slot; asking again replaces the request,
+ * mij_batch_reset forgets it, clones start at MIJ_ARITH_STB.  A slot with a plane request refuses it, and such a slot refuses a plane
+ * request (MIJ_E_STATE): plane output has the reference's samples.  mij_batch_slot_path reports 10; mij_batch_slot_work_items and
+ * mij_batch_slot_kernel answer as for a two-pass slot (pass 2's items; *kind the family of k_lj_color by chroma subsampling, *variant
+ * n_out - 1).  The stored picture lies where the slot's picture always lies, with the same pitch: mij_batch_fetch, mij_batch_device_out,
+ * mij_batch_hash_out, mij_batch_diff_slots, the float request and the three tensor requests (windows, resize, orientations) see it
+ * unchanged.  A region (mij_batch_set_roi) is accepted and the picture is decoded whole, as for two-pass layouts.  The kernels are
+ * k_lj_idct and k_lj_color (mij_libjpeg_kernels.h); the sample planes between them live in the scratch arena of the two-pass path.
+ */
+enum { MIJ_ARITH_STB = 0, MIJ_ARITH_LIBJPEG = 1 };
+int mij_batch_set_arith(mij_batch *b, int slot, int arith);
 
 /*
  * Region of interest: a slot may carry, before upload, a rectangle (x0, y0, w, h) in pixels of its STORED picture -- the reduced one when
