@@ -69,6 +69,14 @@ from .binding import (  # noqa: F401
     sampled_plan,
     host_transform_sampled,
     write_jpg_sampled_to_memory,
+    ARITHMETICS,
+    ENC_GROUPS,
+    libjpeg_plan,
+    host_transform_libjpeg,
+    host_transform_libjpeg_planes,
+    libjpeg_quantise_all,
+    libjpeg_reframe,
+    write_jpg_libjpeg_to_memory,
     plane_shapes,
     split_planes,
     planes_plan,

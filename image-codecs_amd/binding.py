@@ -1594,6 +1594,86 @@ def write_jpg_sampled_to_memory(pixels, quality=90, sampling=None, qtables=None,
     return _take_malloced(out, n.value)
 
 
+ARITHMETICS = {"stb": MIJ_ARITH_STB, "libjpeg": MIJ_ARITH_LIBJPEG}  # mij_enc_set_arith
+ENC_GROUPS = 22  # MIJ_ENC_GROUPS
+
+
+def libjpeg_plan(width, height, comp, quality=90, sampling=None, qtables=None):
+    """mjw_lj_plan_init -> TranscodePlan (include/mij_host.h, LIBJPEG ENCODING); None for what it refuses ("440", comp 2 and 4).  No
+    sampling: "420"."""
+    L = lib()
+    o = enc_opts(sampling, qtables) or EncOpts()
+    t = TranscodePlan()
+    L.mjw_lj_plan_init.argtypes = [C.POINTER(TranscodePlan), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p]
+    if not L.mjw_lj_plan_init(C.byref(t), int(width), int(height), int(comp), int(quality), o.ncomp, o.lh, o.lv, o.luma, o.chroma):
+        return None
+    return t
+
+
+def host_transform_libjpeg(pixels, quality=90, sampling=None, qtables=None, flip=False):
+    """mjw_lj_plan_init + mjw_lj_transform_host: the units of a libjpeg slot computed on the HOST -> (TranscodePlan, int16 [n_du, 64]);
+    (None, None) for what is refused"""
+    a = _hwc_u8(pixels)
+    h, w, comp = a.shape
+    t = libjpeg_plan(w, h, comp, quality, sampling, qtables)
+    if t is None:
+        return None, None
+    L = lib()
+    L.mjw_lj_transform_host.argtypes = [C.POINTER(TranscodePlan), C.c_void_p, C.c_int, C.c_void_p]
+    du = np.empty(t.du_elems(), dtype=np.int16)
+    if not L.mjw_lj_transform_host(C.byref(t), a.ctypes.data_as(C.c_void_p), int(bool(flip)), du.ctypes.data_as(C.c_void_p)):
+        return None, None
+    return t, du.reshape(-1, 64)
+
+
+def libjpeg_quantise_all(q):
+    """mjw_lj_quantise(x, q) for x = -32768 .. 32768 -> int32 [65537]: the multiply-high quantiser of LIBJPEG ENCODING"""
+    L = lib()
+    L.mjw_lj_quantise_all.argtypes = [C.c_int, C.c_void_p]
+    L.mjw_lj_quantise_all.restype = None
+    out = np.empty(65537, np.int32)
+    L.mjw_lj_quantise_all(int(q), out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def libjpeg_reframe(stream):
+    """mjw_lj_reframe: a stream of this library's writer in libjpeg's framing (a DQT and a DHT segment per table) -> bytes; None for a
+    malformed header"""
+    L = lib()
+    L.mjw_lj_reframe.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p]
+    L.mjw_lj_reframe.restype = C.c_size_t
+    data = bytes(stream)
+    out = C.create_string_buffer(len(data) + 64)
+    n = L.mjw_lj_reframe(data, len(data), out)
+    return out.raw[:n] if n else None
+
+
+def write_jpg_libjpeg_to_memory(pixels, quality=90, sampling=None, qtables=None, flip=False, optimize=False, restart_rows=None, restart_mcus=None,
+                                progressive=False):
+    """mjh_write_jpg_libjpeg_to_memory: the host twin of arithmetic="libjpeg" -- what Pillow's save(..., quality=, subsampling=) writes for
+    these pixels, byte for byte -> bytes, None where it refuses ("440", 2 or 4 channels).  sampling None: "420"."""
+    a = _hwc_u8(pixels)
+    h, w, comp = a.shape
+    o = enc_opts(sampling, qtables) or EncOpts()
+    rows, mcus = _restart_mcus(restart_rows), _restart_mcus(restart_mcus)
+    if rows and mcus:
+        raise ValueError("restart_rows and restart_mcus are two ways to say the same thing: give one")
+    if rows:
+        t = libjpeg_plan(w, h, comp, quality, sampling, qtables)
+        if t is None:
+            return None
+        mcus = rows * t.plan.mcu_x
+    prog = _progressive_flag(progressive, mcus)
+    L = lib()
+    L.mjh_write_jpg_libjpeg_to_memory.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
+                                                  C.c_int, C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    out, n = C.c_void_p(), C.c_size_t()
+    if not L.mjh_write_jpg_libjpeg_to_memory(a.ctypes.data_as(C.c_void_p), w, h, comp, int(quality), o.ncomp, o.lh, o.lv, o.luma, o.chroma,
+                                             int(bool(flip)), MJW_OPTIMIZE_HUFFMAN if optimize else 0, mcus, int(prog), C.byref(out), C.byref(n)):
+        return None
+    return _take_malloced(out, n.value)
+
+
 class Plane(C.Structure):
     """mij_plane (include/mij.h): sample (y, x) is the byte at src + y * row_pitch + x * x_pitch."""
     _fields_ = [("src", C.c_void_p), ("row_pitch", C.c_int64), ("x_pitch", C.c_int64)]
@@ -1726,6 +1806,23 @@ def host_transform_planes(picture, sampling, quality=90, qtables=None, video_ran
     pl = (Plane * 3)(*[Plane(*tr) for tr in triples])
     du = np.empty(t.du_elems(), dtype=np.int16)
     if not L.mjw_ptransform_host(C.byref(t), pl, C.byref(cv) if cv is not None else None, int(bool(flip)), du.ctypes.data_as(C.c_void_p)):
+        return None, None
+    return t, du.reshape(-1, 64)
+
+
+def host_transform_libjpeg_planes(picture, sampling, quality=90, qtables=None, video_range=False, flip=False, convert=None):
+    """mjw_pplan_init + mjw_lj_ptransform_host: host_transform_planes with libjpeg's forward DCT, quantiser and dummy blocks (include/mij_host.h,
+    LIBJPEG ENCODING); (None, None) for what is refused ("440")"""
+    triples, w, h, keep = _numpy_planes(picture, sampling)
+    cv = _plane_convert(video_range, convert)
+    t = planes_plan(w, h, sampling, quality, qtables)
+    if t is None:
+        return None, None
+    L = lib()
+    L.mjw_lj_ptransform_host.argtypes = [C.POINTER(TranscodePlan), C.POINTER(Plane), C.c_void_p, C.c_int, C.c_void_p]
+    pl = (Plane * 3)(*[Plane(*tr) for tr in triples])
+    du = np.empty(t.du_elems(), dtype=np.int16)
+    if not L.mjw_lj_ptransform_host(C.byref(t), pl, C.byref(cv) if cv is not None else None, int(bool(flip)), du.ctypes.data_as(C.c_void_p)):
         return None, None
     return t, du.reshape(-1, 64)
 
@@ -2281,6 +2378,26 @@ class Encoder:
         L = lib()
         L.mij_enc_set_progressive.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _check(L.mij_enc_set_progressive(self._h, int(slot), int(bool(on))), "mij_enc_set_progressive")
+
+    def set_arith(self, slot, arith=MIJ_ARITH_LIBJPEG):
+        """mij_enc_set_arith: MIJ_ARITH_LIBJPEG (or "libjpeg") gives the slot libjpeg's arithmetic and header (include/mij_host.h, LIBJPEG
+        ENCODING: Pillow's file byte for byte), MIJ_ARITH_STB (or "stb", the default) the reference's; before upload.  MijError for slots of
+        units or coefficients, "440" and pictures of 2 or 4 channels."""
+        L = lib()
+        L.mij_enc_set_arith.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        _check(L.mij_enc_set_arith(self._h, int(slot), int(ARITHMETICS.get(arith, arith))), "mij_enc_set_arith")
+
+    def slot_arith(self, slot):
+        """mij_enc_slot_arith: MIJ_ARITH_STB or MIJ_ARITH_LIBJPEG"""
+        L = lib()
+        L.mij_enc_slot_arith.argtypes = [C.c_void_p, C.c_int]
+        return _check(L.mij_enc_slot_arith(self._h, int(slot)), "mij_enc_slot_arith")
+
+    def group_work(self):
+        """mij_enc_group_work of every group: the work items the last upload queued per transform kernel of the kernel table"""
+        L = lib()
+        L.mij_enc_group_work.argtypes = [C.c_void_p, C.c_int]
+        return [_check(L.mij_enc_group_work(self._h, g), "mij_enc_group_work") for g in range(ENC_GROUPS)]
 
     def slot_progressive(self, slot):
         """mij_enc_slot_progressive: whether progressive output was asked for the slot"""

@@ -1677,6 +1677,313 @@ int mjh_write_jpg_planes_to_memory(const mij_plane *planes, int width, int heigh
 	return 1;
 }
 
+/* ---- libjpeg encoding (include/mij_host.h, LIBJPEG ENCODING): libjpeg's default compression in integers, and its framing of the header */
+
+int mjw_lj_plan_init(mjw_tplan *t, int width, int height, int comp, int quality, int ncomp, int lh, int lv, const unsigned char *luma,
+                     const unsigned char *chroma)
+{
+	if (comp != 1 && comp != 3) /* libjpeg takes no grey + alpha and no RGBA rows */
+		return 0;
+	if (!ncomp) /* libjpeg's default sampling, whatever the quality */
+		ncomp = 3, lh = lv = 2;
+	if (ncomp == 3 && lh == 1 && lv == 2) /* "440": Pillow cannot write it, so nothing judges it */
+		return 0;
+	return mjw_splan_init(t, width, height, comp, quality, ncomp, lh, lv, luma, chroma);
+}
+
+uint32_t mjw_lj_quant_magic(int q) { return q < 1 || q > 255 ? 0u : (uint32_t)(((uint64_t)1 << 32) / (uint32_t)(8 * q)) + 1u; }
+
+int mjw_lj_quantise(int x, int q)
+{
+	const uint32_t a = (uint32_t)(x < 0 ? -x : x) + 4u * (uint32_t)q;
+	const int y = (int)(((uint64_t)a * mjw_lj_quant_magic(q)) >> 32); /* a div 8q, exact for a < 2^17 */
+	return x < 0 ? -y : y;
+}
+
+void mjw_lj_quantise_all(int q, int32_t *out)
+{
+	int x;
+	for (x = -32768; x <= 32768; ++x)
+		out[x + 32768] = mjw_lj_quantise(x, q);
+}
+
+void mjw_lj_ycc(int r, int g, int b, unsigned char ycc[3])
+{
+	ycc[0] = (unsigned char)((19595 * r + 38470 * g + 7471 * b + 32768) >> 16);
+	ycc[1] = (unsigned char)((-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16);
+	ycc[2] = (unsigned char)((32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16);
+}
+
+#define LJ_D(x, n) (((x) + (1 << ((n) - 1))) >> (n))
+/* jfdctint.c's pass over d[0], d[s], .. d[7s] in place: the first pass (rows) scales up by 4, the second (columns) descales */
+static void lj_fdct8(int32_t *d, int s, int first)
+{
+	const int n = first ? 11 : 15;
+	int32_t t0 = d[0] + d[7 * s], t7 = d[0] - d[7 * s], t1 = d[s] + d[6 * s], t6 = d[s] - d[6 * s];
+	int32_t t2 = d[2 * s] + d[5 * s], t5 = d[2 * s] - d[5 * s], t3 = d[3 * s] + d[4 * s], t4 = d[3 * s] - d[4 * s];
+	const int32_t t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+	int32_t z1, z2, z3, z4, z5;
+	d[0] = first ? (t10 + t11) * 4 : LJ_D(t10 + t11, 2);
+	d[4 * s] = first ? (t10 - t11) * 4 : LJ_D(t10 - t11, 2);
+	z1 = (t12 + t13) * 4433;
+	d[2 * s] = LJ_D(z1 + t13 * 6270, n);
+	d[6 * s] = LJ_D(z1 - t12 * 15137, n);
+	z1 = t4 + t7, z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+	z5 = (z3 + z4) * 9633;
+	t4 *= 2446, t5 *= 16819, t6 *= 25172, t7 *= 12299;
+	z1 *= -7373, z2 *= -20995;
+	z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5;
+	d[7 * s] = LJ_D(t4 + z1 + z3, n);
+	d[5 * s] = LJ_D(t5 + z2 + z4, n);
+	d[3 * s] = LJ_D(t6 + z2 + z3, n);
+	d[s] = LJ_D(t7 + z1 + z4, n);
+}
+
+/* one block of samples (pitch bytes between rows) -> its unit under table tab (zigzag order) */
+static void lj_block(const unsigned char *src, size_t pitch, const unsigned char *tab, int16_t *du)
+{
+	int32_t d[64];
+	int i;
+	for (i = 0; i < 64; ++i)
+		d[i] = (int32_t)src[(size_t)(i >> 3) * pitch + (size_t)(i & 7)] - 128;
+	for (i = 0; i < 8; ++i)
+		lj_fdct8(d + 8 * i, 1, 1);
+	for (i = 0; i < 8; ++i)
+		lj_fdct8(d + i, 8, 0);
+	for (i = 0; i < 64; ++i) {
+		const int z = k_zigzag_of[i];
+		du[z] = (int16_t)mjw_lj_quantise(d[i], tab[z]);
+	}
+}
+
+size_t mjw_lj_staged_bytes(const mjw_tplan *t)
+{
+	return t ? (size_t)t->plan.mcu_x * (size_t)t->plan.mcu_y * (size_t)t->plan.du_per_mcu * 64 : 0;
+}
+
+/* pass 2: the staged planes (Y of 8 lh mcu_x x 8 lv mcu_y samples, then Cb, then Cr of 8 mcu_x x 8 mcu_y) -> the units, dummy blocks by rule */
+int mjw_lj_units_from_staged(const mjw_tplan *t, const unsigned char *staged, int16_t *du)
+{
+	const mjw_plan *p;
+	int lh, lv, rw, rh, mx, my, sx, sy, c;
+	size_t ypitch, cpitch, ybytes, cbytes;
+	if (!t || !staged || !du || (t->ncomp != 1 && t->ncomp != 3))
+		return 0;
+	p = &t->plan;
+	lh = t->ncomp == 1 ? 1 : t->lh, lv = t->ncomp == 1 ? 1 : t->lv;
+	rw = (p->width + 7) / 8, rh = (p->height + 7) / 8;
+	ypitch = (size_t)p->mcu_x * 8 * (size_t)lh, cpitch = (size_t)p->mcu_x * 8;
+	ybytes = ypitch * (size_t)p->mcu_y * 8 * (size_t)lv, cbytes = cpitch * (size_t)p->mcu_y * 8;
+	for (my = 0; my < p->mcu_y; ++my)
+		for (mx = 0; mx < p->mcu_x; ++mx) {
+			int16_t *const mcu = du;
+			for (sy = 0; sy < lv; ++sy)
+				for (sx = 0; sx < lh; ++sx, du += 64) {
+					const int bx = mx * lh + sx, by = my * lv + sy;
+					if (bx < rw && by < rh) {
+						lj_block(staged + ((size_t)by * 8) * ypitch + (size_t)bx * 8, ypitch, p->ytab, du);
+						continue;
+					}
+					/* a dummy block: no AC, the DC of the block before it -- its left neighbour in a real block row, the last block
+					 * of the MCU's previous block row anywhere in a row below the picture */
+					memset(du, 0, 64 * sizeof(int16_t));
+					du[0] = by < rh ? du[-64] : mcu[((sy - 1) * lh + lh - 1) * 64];
+				}
+			for (c = 1; c < t->ncomp; ++c, du += 64)
+				lj_block(staged + ybytes + (size_t)(c - 1) * cbytes + ((size_t)my * 8) * cpitch + (size_t)mx * 8, cpitch, p->ctab, du);
+		}
+	return 1;
+}
+
+/* pass 1: pixels -> the staged planes: the colour conversion, the column and row rules, the chroma filter */
+int mjw_lj_stage_host(const mjw_tplan *t, const void *data, int flip, unsigned char *staged)
+{
+	const mjw_plan *p;
+	const unsigned char *px = (const unsigned char *)data;
+	int lh, lv, W, H, CW, CH, x, y, c, comp, rows, width, height;
+	unsigned char *Y, *full;
+	if (!t || !data || !staged || (t->ncomp != 1 && t->ncomp != 3) || (t->plan.comp != 1 && t->plan.comp != 3))
+		return 0;
+	p = &t->plan;
+	comp = p->comp, width = p->width, height = p->height;
+	lh = t->ncomp == 1 ? 1 : t->lh, lv = t->ncomp == 1 ? 1 : t->lv;
+	W = p->mcu_x * 8 * lh, H = p->mcu_y * 8 * lv, CW = p->mcu_x * 8, CH = p->mcu_y * 8;
+	rows = (height + lv - 1) / lv * lv; /* the pixel rows a chroma filter reads */
+	Y = staged;
+	full = (unsigned char *)malloc((size_t)W * (size_t)rows * 2); /* Cb and Cr at full size, columns extended */
+	if (!full)
+		return 0;
+	for (y = 0; y < H; ++y) {
+		const int cy = y < height ? y : height - 1;
+		const unsigned char *line = px + (size_t)(flip ? height - 1 - cy : cy) * (size_t)width * (size_t)comp;
+		for (x = 0; x < W; ++x) {
+			const unsigned char *q = line + (size_t)(x < width ? x : width - 1) * (size_t)comp;
+			unsigned char ycc[3];
+			mjw_lj_ycc(q[0], q[comp > 2 ? 1 : 0], q[comp > 2 ? 2 : 0], ycc);
+			Y[(size_t)y * W + x] = ycc[0];
+			if (y < rows) {
+				full[(size_t)y * W + x] = ycc[1];
+				full[(size_t)(rows + y) * W + x] = ycc[2];
+			}
+		}
+	}
+	for (c = 0; c < t->ncomp - 1; ++c) {
+		const unsigned char *src = full + (size_t)c * (size_t)rows * W;
+		unsigned char *dst = staged + (size_t)W * H + (size_t)c * (size_t)CW * CH;
+		const int srows = rows / lv;
+		for (y = 0; y < CH; ++y) {
+			const unsigned char *a = src + (size_t)(y < srows ? y : srows - 1) * lv * W, *b = a + W; /* the last SAMPLE row repeated */
+			for (x = 0; x < CW; ++x)
+				dst[(size_t)y * CW + x] = lh == 1   ? a[x]
+				                          : lv == 1 ? (unsigned char)((a[2 * x] + a[2 * x + 1] + (x & 1)) >> 1)
+				                                    : (unsigned char)((a[2 * x] + a[2 * x + 1] + b[2 * x] + b[2 * x + 1] + 1 + (x & 1)) >> 2);
+		}
+	}
+	free(full);
+	return 1;
+}
+
+int mjw_lj_transform_host(const mjw_tplan *t, const void *pixels, int flip, int16_t *du)
+{
+	unsigned char *staged = t ? (unsigned char *)malloc(mjw_lj_staged_bytes(t)) : NULL;
+	const int ok = staged && mjw_lj_stage_host(t, pixels, flip, staged) && mjw_lj_units_from_staged(t, staged, du);
+	free(staged);
+	return ok;
+}
+
+/* mjw_ptransform_host's staging (each plane extended on its own by its last column and row), then pass 2 */
+int mjw_lj_ptransform_host(const mjw_tplan *t, const mij_plane *pl, const mij_in_convert *cv, int flip, int16_t *du)
+{
+	unsigned char *staged, *dst;
+	unsigned char lut[256];
+	int c, x, y, i, ok;
+	if (!planes_ok(t, pl, cv) || !du || (t->ncomp == 3 && t->lh == 1 && t->lv == 2))
+		return 0;
+	staged = dst = (unsigned char *)malloc(mjw_lj_staged_bytes(t));
+	if (!staged)
+		return 0;
+	for (c = 0; c < t->ncomp; ++c) {
+		const int h = c ? 1 : t->lh, v = c ? 1 : t->lv;
+		const int w = c ? (t->plan.width + t->lh - 1) / t->lh : t->plan.width, ht = c ? (t->plan.height + t->lv - 1) / t->lv : t->plan.height;
+		const int pw = t->plan.mcu_x * 8 * h, ph = t->plan.mcu_y * 8 * v;
+		for (i = 0; i < 256; ++i)
+			lut[i] = cv ? plane_convert((unsigned char)i, cv, c) : (unsigned char)i;
+		for (y = 0; y < ph; ++y) {
+			const int cy = y < ht ? y : ht - 1;
+			const unsigned char *line = (const unsigned char *)pl[c].src + (int64_t)(flip ? ht - 1 - cy : cy) * pl[c].row_pitch;
+			for (x = 0; x < pw; ++x)
+				dst[(size_t)y * pw + x] = lut[line[(int64_t)(x < w ? x : w - 1) * pl[c].x_pitch]];
+		}
+		dst += (size_t)pw * ph;
+	}
+	ok = mjw_lj_units_from_staged(t, staged, du);
+	free(staged);
+	return ok;
+}
+
+/* `len` bytes that start with SOI and run at least to the first SOS marker, in libjpeg's framing: every DQT and DHT segment before that
+ * SOS split into one segment per table; everything else, and everything from SOS on, as it is.  Returns the new length (at most
+ * len + 4 per table), 0 for a malformed segment. */
+size_t mjw_lj_reframe(const unsigned char *in, size_t len, unsigned char *out)
+{
+	size_t i = 2, o = 2;
+	if (!in || !out || len < 4 || in[0] != 0xFF || in[1] != 0xD8)
+		return 0;
+	out[0] = 0xFF, out[1] = 0xD8;
+	while (i + 4 <= len && in[i] == 0xFF && in[i + 1] != 0xDA) {
+		const int marker = in[i + 1];
+		const size_t seg = (size_t)in[i + 2] << 8 | in[i + 3], end = i + 2 + seg;
+		if (seg < 2 || end > len)
+			return 0;
+		if (marker != 0xDB && marker != 0xC4) {
+			memcpy(out + o, in + i, 2 + seg);
+			o += 2 + seg;
+			i = end;
+			continue;
+		}
+		for (i += 4; i < end;) {
+			size_t n = 65; /* DQT: Pq / Tq and 64 bytes (eight-bit tables only) */
+			int k;
+			if (marker == 0xC4) {
+				if (i + 17 > end)
+					return 0;
+				for (k = 0, n = 17; k < 16; ++k)
+					n += in[i + 1 + k];
+			} else if (in[i] >> 4) {
+				return 0;
+			}
+			if (i + n > end)
+				return 0;
+			out[o++] = 0xFF, out[o++] = (unsigned char)marker, out[o++] = (unsigned char)((n + 2) >> 8), out[o++] = (unsigned char)((n + 2) & 0xff);
+			memcpy(out + o, in + i, n);
+			o += n;
+			i += n;
+		}
+	}
+	if (i + 2 > len || in[i] != 0xFF || in[i + 1] != 0xDA)
+		return 0;
+	memcpy(out + o, in + i, len - i);
+	return o + (len - i);
+}
+
+size_t mjw_lj_theader_restart(const mjw_tplan *t, int ri, unsigned char *out)
+{
+	unsigned char hdr[MJW_HEADER_RESTART_BYTES];
+	const size_t n = t && out ? mjw_theader_restart(t, ri, hdr) : 0;
+	return n ? mjw_lj_reframe(hdr, n, out) : 0;
+}
+
+size_t mjw_lj_theader_optimized_restart(const mjw_tplan *t, const uint8_t bits[4][16], const uint8_t vals[4][256], int ri, unsigned char *out)
+{
+	unsigned char hdr[MJW_HEADER_RESTART_BYTES];
+	const size_t n = t && out ? mjw_theader_optimized_restart(t, bits, vals, ri, hdr) : 0;
+	return n ? mjw_lj_reframe(hdr, n, out) : 0;
+}
+
+/* SOI .. SOF2: the progressive frame header with a DQT segment per table (there is no SOS to stop at: the same walk to the end) */
+size_t mjw_lj_tframe_progressive(const mjw_tplan *t, unsigned char *out)
+{
+	unsigned char hdr[MJW_HEADER_RESTART_BYTES + 2];
+	size_t n = t && out ? mjw_tframe_progressive(t, hdr) : 0;
+	if (!n)
+		return 0;
+	hdr[n] = 0xFF, hdr[n + 1] = 0xDA;
+	n = mjw_lj_reframe(hdr, n + 2, out);
+	return n ? n - 2 : 0;
+}
+
+int mjh_write_jpg_libjpeg_to_memory(const void *pixels, int width, int height, int comp, int quality, int ncomp, int lh, int lv,
+                                    const unsigned char *luma, const unsigned char *chroma, int flip, unsigned flags, int restart_mcus,
+                                    int progressive, unsigned char **out, size_t *out_len)
+{
+	mjw_tplan t;
+	int16_t *du;
+	unsigned char *buf, *res;
+	size_t nu, cap, n;
+	if (!pixels || !out || !out_len || (flags & ~MJW_OPTIMIZE_HUFFMAN) || !ri_ok(restart_mcus) || (progressive && restart_mcus) ||
+		 !mjw_lj_plan_init(&t, width, height, comp, quality, ncomp, lh, lv, luma, chroma))
+		return 0;
+	nu = mjw_tplan_du_count(&t);
+	cap = progressive ? MJW_PROGRESSIVE_STREAM_CAP(nu) : MJW_STREAM_CAP(nu);
+	du = (int16_t *)malloc(nu * 64 * sizeof(int16_t));
+	buf = (unsigned char *)malloc(cap);
+	res = (unsigned char *)malloc(cap + MJW_LJ_HEADER_EXTRA);
+	n = 0;
+	if (du && buf && res && mjw_lj_transform_host(&t, pixels, flip, du)) {
+		n = progressive ? mjw_temit_progressive_to_memory(&t, du, buf, cap) : mjw_temit_restart_to_memory(&t, du, flags, restart_mcus, buf, cap);
+		n = n ? mjw_lj_reframe(buf, n, res) : 0;
+	}
+	free(du);
+	free(buf);
+	if (!n) {
+		free(res);
+		return 0;
+	}
+	*out = res;
+	*out_len = n;
+	return 1;
+}
+
 int stbi_write_jpg_to_func(stbi_write_func *func, void *context, int x, int y, int comp, const void *data, int quality)
 {
 	mjw_plan plan;

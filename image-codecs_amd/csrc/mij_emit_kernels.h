@@ -49,7 +49,7 @@
 #pragma once
 
 #define MIJ_EMIT_TILE 128
-#define MIJ_EMIT_HDR 613 /* MJW_HEADER_RESTART_BYTES: the stride of the header list, and the longest header */
+#define MIJ_EMIT_HDR 629 /* MJW_LJ_HEADER_BYTES: the stride of the header list, and the longest header */
 /* most bits a unit within the writer's ranges takes: chroma DC 11 + 11, 63 AC symbols of 16 + 10, the 7 fill bits */
 #define MIJ_EMIT_MAX_DU_BITS (22 + 63 * 26 + 7)
 #define MIJ_EMIT_LDS_WORDS ((MIJ_EMIT_TILE * MIJ_EMIT_MAX_DU_BITS + 7 + 31) / 32 + 1)
@@ -66,6 +66,7 @@ struct EmitSlot {
 	uint32_t hdr, tab; /* header of the slot: hdrs + hdr * MIJ_EMIT_HDR; tab > 0: optimised, its tables are entry tab, its counts tab - 1 */
 	uint32_t hlen, ny; /* the header's length: what the upload wrote, or what k_emit_build wrote; luma units per MCU (1, 2 or 4): unit p of an MCU is luma when p < ny */
 	uint32_t ri, prog; /* the restart interval in MCUs (mij_enc_set_restart), 0: none; prog > 0: a progressive slot (mij_enc_set_progressive), ProgSlot prog - 1 */
+	uint32_t lj, pad;  /* lj: the header is in libjpeg's framing (mij_enc_set_arith; mij_host.h, LIBJPEG ENCODING): a DQT and a DHT segment per table */
 };
 
 struct EmitTile {
@@ -817,10 +818,12 @@ __global__ __launch_bounds__(256) void k_emit_build(EmitSlot *__restrict__ slots
 	emit_k2(freq + (size_t)k * (4 * 256) + t * 256, lane, t, bits, first_code, first_pos, nvals, &fail, pos, nv);
 	/* a slot without chroma (dpm == ny) carries the two luma tables only, in the shorter header */
 	const bool grey = slots[slot].dpm == slots[slot].ny;
-	const uint32_t dht_at = grey ? MIJ_EMIT_DHT_AT1 : MIJ_EMIT_DHT_AT, sos_len = grey ? 10u : 14u;
+	/* libjpeg's framing: a second DQT segment in front (4 bytes more), and every table in a DHT segment of its own (4 bytes more each) */
+	const uint32_t lj = slots[slot].lj ? 4u : 0u;
+	const uint32_t dht_at = (grey ? MIJ_EMIT_DHT_AT1 : MIJ_EMIT_DHT_AT + lj), sos_len = grey ? 10u : 14u;
 	/* behind the DHT segment: the DRI segment of a slot with a restart interval, then SOS */
 	const uint32_t ri = slots[slot].ri, tail = sos_len + (ri ? 6u : 0u);
-	const uint32_t hlen = grey ? dht_at + 2u * 17u + nvals[0] + nvals[2] + tail : dht_at + 4u * 17u + nvals[0] + nvals[1] + nvals[2] + nvals[3] + tail;
+	const uint32_t hlen = grey ? dht_at + 2u * 17u + lj + nvals[0] + nvals[2] + tail : dht_at + 4u * 17u + 3u * lj + nvals[0] + nvals[1] + nvals[2] + nvals[3] + tail;
 	const bool ok = !fail && hlen <= MIJ_EMIT_HDR && nvals[t] == nv;
 	const bool all_ok = __syncthreads_and(ok) != 0;
 	const uint32_t tile0 = slots[slot].first_tile, ntile = slots[slot].n_tiles;
@@ -828,12 +831,16 @@ __global__ __launch_bounds__(256) void k_emit_build(EmitSlot *__restrict__ slots
 		tiles[tile0 + i].tab = all_ok ? k + 1 : 0u;
 	if (all_ok) {
 		/* the DHT segment holds the tables in mjw_header's order: luma DC, luma AC, chroma DC, chroma AC */
-		const uint32_t before = t == 0 ? 0u : (t == 2 ? 17u + nvals[0] : (t == 1 ? 34u + nvals[0] + nvals[2] : 51u + nvals[0] + nvals[2] + nvals[1]));
+		const uint32_t before = t == 0 ? 0u : (t == 2 ? 17u + lj + nvals[0] : (t == 1 ? 34u + 2u * lj + nvals[0] + nvals[2] : 51u + 3u * lj + nvals[0] + nvals[2] + nvals[1]));
 		uint8_t *h = hdrs + (size_t)slots[slot].hdr * MIJ_EMIT_HDR, *seg = h + dht_at + before;
 		EmitTables *T = tabs + k + 1;
 		const bool in_dht = !grey || t == 0 || t == 2; /* the code tables are written for all four: a grey slot never looks its chroma tables up */
 		if (lane == 0 && in_dht)
 			seg[0] = (uint8_t)(t == 0 ? 0x00 : (t == 2 ? 0x10 : (t == 1 ? 0x01 : 0x11)));
+		if (lane < 4 && in_dht && lj) { /* the table's own FF C4 and length */
+			const uint32_t head = 0xFFu | 0xC4u << 8 | ((19u + nvals[t]) >> 8) << 16 | ((19u + nvals[t]) & 0xFFu) << 24;
+			seg[lane - 4] = (uint8_t)(head >> (8 * lane));
+		}
 		if (lane < 16 && in_dht)
 			seg[1 + lane] = (uint8_t)bits[t][lane + 1];
 #pragma unroll
@@ -858,8 +865,10 @@ __global__ __launch_bounds__(256) void k_emit_build(EmitSlot *__restrict__ slots
 			h[hlen - tail + lane] = (uint8_t)(lane < 4 ? dri >> (8 * lane) : (lane == 4 ? ri >> 8 : ri));
 		}
 		if (threadIdx.x == 0) {
-			h[dht_at - 2] = (uint8_t)((hlen - tail - (dht_at - 2)) >> 8);
-			h[dht_at - 1] = (uint8_t)((hlen - tail - (dht_at - 2)) & 0xFFu);
+			if (!lj) {
+				h[dht_at - 2] = (uint8_t)((hlen - tail - (dht_at - 2)) >> 8);
+				h[dht_at - 1] = (uint8_t)((hlen - tail - (dht_at - 2)) & 0xFFu);
+			}
 			slots[slot].hlen = hlen;
 			opt_ok[k] = 1;
 		}

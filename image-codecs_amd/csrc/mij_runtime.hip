@@ -3406,7 +3406,8 @@ extern "C" int mij_batch_entropy_rounds(const mij_batch *b) { return b && b->es 
 #include "mij_host.h"
 #include "mij_emit_kernels.h"
 #include "mij_transcode_kernels.h"
-static_assert(MIJ_EMIT_HDR == MJW_HEADER_RESTART_BYTES, "header size");
+#include "mij_libjpeg_enc_kernels.h"
+static_assert(MIJ_EMIT_HDR == MJW_LJ_HEADER_BYTES, "header size");
 
 /* where a slot's input comes from: pinned staging, a device tensor, given units, a decode batch's coefficient planes */
 enum EncKind { ENC_HOST = 0, ENC_DEVICE = 1, ENC_UNITS = 2, ENC_COEF = 3 };
@@ -3415,31 +3416,53 @@ static inline bool enc_has_pixels(EncKind kind) { return kind == ENC_HOST || kin
 /* The transform kernels, in launch order: the per-unit luma / chroma pairs of 4:4:4 and 4:2:0 (the strip kernels' test twins,
  * mij_enc_force_generic), the strip kernels of pixel slots, the strip kernels of plane slots.  Every one takes (slots, work, pixel arena,
  * unit arena).  A work item is `strip` consecutive MCUs of one slot; of the per-unit pairs, 256 units of one kind. */
-enum EncGroup { EG_NONE = -1, EG_Y444 = 0, EG_C444, EG_Y420, EG_C420, EG_420, EG_444, EG_422, EG_440, EG_GREY, EG_P444, EG_P422, EG_P440, EG_P420, EG_PGREY, EG_GROUPS };
+enum EncGroup {
+	EG_NONE = -1, EG_Y444 = 0, EG_C444, EG_Y420, EG_C420, EG_420, EG_444, EG_422, EG_440, EG_GREY, EG_P444, EG_P422, EG_P440, EG_P420, EG_PGREY,
+	/* libjpeg slots (mij_enc_set_arith; mij_libjpeg_enc_kernels.h): pass 1 of the pixel slots, then pass 2 of pixel and plane slots alike */
+	EG_LJC444, EG_LJC422, EG_LJC420, EG_LJCGREY, EG_LJ444, EG_LJ422, EG_LJ420, EG_LJGREY,
+	EG_GROUPS
+};
+static_assert(EG_GROUPS == MIJ_ENC_GROUPS, "mij.h names the groups");
+#define EG_LJ_PASS1(g) ((EncGroup)((g) - (EG_LJ444 - EG_LJC444))) /* the colour pass in front of transform group g */
+typedef void (*enc_lj_fn)(const EncImage *, const WorkIdct *, const uint8_t *, int16_t *, const LjEncSlot *, uint8_t *);
 struct EncFamily {
 	void (*k)(const EncImage *, const WorkIdct *, const uint8_t *, int16_t *);
 	unsigned threads; /* workgroup size */
 	size_t lds;       /* dynamic LDS bytes */
 	uint32_t strip;
+	enc_lj_fn klj; /* a libjpeg family's kernel instead of k: it also takes the slots' LjEncSlot list and the plane scratch */
 };
-#define MIJ_ENCP(LH, LV, NC) {k_encode_planes<LH, LV, NC>, MIJ_ENCP_NT(LH, LV, NC), MIJ_ENCP_LDS(LH, LV, NC), MIJ_ENCP_STRIP(LH, LV, NC)}
+#define MIJ_ENCP(LH, LV, NC) {k_encode_planes<LH, LV, NC>, MIJ_ENCP_NT(LH, LV, NC), MIJ_ENCP_LDS(LH, LV, NC), MIJ_ENCP_STRIP(LH, LV, NC), nullptr}
+/* pass 1: an item is one row of cells (8 mcu_y of them); pass 2: k_encode_planes' strips */
+#define MIJ_LJC(LH, LV, NC) {nullptr, 256, 0, 1, k_lj_enc_color<LH, LV, NC>}
+#define MIJ_LJP(LH, LV, NC) {nullptr, MIJ_ENCP_NT(LH, LV, NC), MIJ_ENCP_LDS(LH, LV, NC), MIJ_ENCP_STRIP(LH, LV, NC), k_lj_encode_planes<LH, LV, NC>}
 static const EncFamily enc_families[EG_GROUPS] = {
-	/* EG_Y444 */ {k_encode_y<0>, 256, 0, 256},
-	/* EG_C444 */ {k_encode_c<0>, 256, 0, 256},
-	/* EG_Y420 */ {k_encode_y<1>, 256, 0, 256},
-	/* EG_C420 */ {k_encode_c<1>, 256, 0, 256},
-	/* EG_420 */ {k_encode420, 192, MIJ_ENC_LDS, MIJ_ENC_STRIP},
-	/* EG_444 */ {k_encode444, 192, MIJ_ENC444_LDS, MIJ_ENC444_STRIP},
-	/* EG_422 */ {k_encode422, 128, MIJ_ENC422_LDS, MIJ_ENC422_STRIP},
-	/* EG_440 */ {k_encode440, 256, MIJ_ENC440_LDS, MIJ_ENC440_STRIP},
-	/* EG_GREY */ {k_encode_grey, 256, MIJ_ENCGREY_LDS, MIJ_ENCGREY_STRIP},
+	/* EG_Y444 */ {k_encode_y<0>, 256, 0, 256, nullptr},
+	/* EG_C444 */ {k_encode_c<0>, 256, 0, 256, nullptr},
+	/* EG_Y420 */ {k_encode_y<1>, 256, 0, 256, nullptr},
+	/* EG_C420 */ {k_encode_c<1>, 256, 0, 256, nullptr},
+	/* EG_420 */ {k_encode420, 192, MIJ_ENC_LDS, MIJ_ENC_STRIP, nullptr},
+	/* EG_444 */ {k_encode444, 192, MIJ_ENC444_LDS, MIJ_ENC444_STRIP, nullptr},
+	/* EG_422 */ {k_encode422, 128, MIJ_ENC422_LDS, MIJ_ENC422_STRIP, nullptr},
+	/* EG_440 */ {k_encode440, 256, MIJ_ENC440_LDS, MIJ_ENC440_STRIP, nullptr},
+	/* EG_GREY */ {k_encode_grey, 256, MIJ_ENCGREY_LDS, MIJ_ENCGREY_STRIP, nullptr},
 	/* EG_P444 */ MIJ_ENCP(1, 1, 3),
 	/* EG_P422 */ MIJ_ENCP(2, 1, 3),
 	/* EG_P440 */ MIJ_ENCP(1, 2, 3),
 	/* EG_P420 */ MIJ_ENCP(2, 2, 3),
 	/* EG_PGREY */ MIJ_ENCP(1, 1, 1),
+	/* EG_LJC444 */ MIJ_LJC(1, 1, 3),
+	/* EG_LJC422 */ MIJ_LJC(2, 1, 3),
+	/* EG_LJC420 */ MIJ_LJC(2, 2, 3),
+	/* EG_LJCGREY */ MIJ_LJC(1, 1, 1),
+	/* EG_LJ444 */ MIJ_LJP(1, 1, 3),
+	/* EG_LJ422 */ MIJ_LJP(2, 1, 3),
+	/* EG_LJ420 */ MIJ_LJP(2, 2, 3),
+	/* EG_LJGREY */ MIJ_LJP(1, 1, 1),
 };
 #undef MIJ_ENCP
+#undef MIJ_LJC
+#undef MIJ_LJP
 
 struct EncSlot {
 	mjw_tplan tp; /* the slot's plan, whatever its kind: a pixel slot without options has the writer's 4:2:0 or 4:4:4 */
@@ -3451,6 +3474,7 @@ struct EncSlot {
 	bool optimize;              /* mij_enc_set_optimize */
 	int restart;                /* mij_enc_set_restart: the restart interval in MCUs, 0: none */
 	bool progressive;           /* mij_enc_set_progressive */
+	int arith;                  /* mij_enc_set_arith: MIJ_ARITH_STB, or MIJ_ARITH_LIBJPEG (include/mij_host.h, LIBJPEG ENCODING) */
 	mij_in_tensor in;           /* ENC_DEVICE */
 	mij_in_convert cv;          /* ENC_DEVICE with float elements (mij_enc_add_device_float); cv.dtype is MIJ_DT_U8 for every other slot */
 	std::vector<int16_t> units; /* ENC_UNITS */
@@ -3522,6 +3546,9 @@ struct mij_encoder {
 	Buf<EncGatherF> fgath;
 	Buf<EncGatherP> pgath;
 	Buf<WorkIdct> gwork, fgwork, pgwork;
+	/* libjpeg slots (mij_enc_set_arith): one LjEncSlot per slot and the planes pass 1 leaves for pass 2, both grown at upload */
+	Buf<LjEncSlot> lj;
+	Buf<uint8_t, BUF_ON_DEVICE> lj_planes;
 	EncEmit em;
 	bool emit_queued = false, streams_fetched = false;
 	std::vector<int> opt_of;      /* slot -> k, or -1 */
@@ -3695,6 +3722,7 @@ static int enc_add_common(mij_encoder *e, const mjw_tplan &tplan, const void *pi
 	s.optimize = false;
 	s.progressive = false;
 	s.restart = 0;
+	s.arith = MIJ_ARITH_STB;
 	memset(&s.in, 0, sizeof(s.in));
 	memset(&s.cv, 0, sizeof(s.cv));
 	s.cv.dtype = MIJ_DT_U8;
@@ -3862,14 +3890,56 @@ extern "C" int mij_enc_add_clone(mij_encoder *e, int src_slot)
 	if (!enc_has_pixels(r.kind))
 		return set_err(MIJ_E_ARG, "slot %d holds given data units or coefficient planes, which have no pixels to clone", src_slot);
 	const bool optimize = src->optimize, progressive = src->progressive; /* src and r do not outlive the push */
-	const int restart = src->restart;
+	const int restart = src->restart, arith = src->arith;
 	const int slot = enc_add_common(e, mjw_tplan(r.tp), nullptr, r.flip, root, ENC_HOST, r.sampled, r.planes);
 	if (slot >= 0) {
 		e->slots[(size_t)slot].optimize = optimize;
 		e->slots[(size_t)slot].restart = restart;
 		e->slots[(size_t)slot].progressive = progressive;
+		e->slots[(size_t)slot].arith = arith;
 	}
 	return slot;
+}
+
+/* natural index (8 * row + column) -> zigzag position, the order quantisation tables are kept in */
+static const uint8_t enc_zigzag_of[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30, 41, 43, 9,  11, 18, 24, 31, 40, 44, 53,
+														10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
+
+/* include/mij.h: libjpeg's arithmetic and header for a pixel or plane slot (include/mij_host.h, LIBJPEG ENCODING) */
+extern "C" int mij_enc_set_arith(mij_encoder *e, int slot, int arith)
+{
+	EncSlot *s = enc_slot(e, slot);
+	if (!s)
+		return MIJ_E_ARG;
+	if (arith != MIJ_ARITH_STB && arith != MIJ_ARITH_LIBJPEG)
+		return set_err(MIJ_E_ARG, "mij_enc_set_arith: arithmetic %d is neither MIJ_ARITH_STB nor MIJ_ARITH_LIBJPEG", arith);
+	if (e->uploaded)
+		return set_err(MIJ_E_STATE, "mij_enc_set_arith after mij_enc_upload");
+	if (arith == MIJ_ARITH_LIBJPEG) {
+		if (!enc_has_pixels(s->kind))
+			return set_err(MIJ_E_ARG, "slot %d holds given data units or coefficient planes: there is nothing to transform", slot);
+		if (s->tp.ncomp == 3 && s->tp.lh == 1 && s->tp.lv == 2)
+			return set_err(MIJ_E_ARG, "slot %d is 4:4:0, which libjpeg's arithmetic does not serve (no writer to judge it)", slot);
+		if (s->tp.plan.comp != 1 && s->tp.plan.comp != 3)
+			return set_err(MIJ_E_ARG, "slot %d has %d channels: libjpeg's arithmetic serves 1 and 3", slot, s->tp.plan.comp);
+	}
+	s->arith = arith;
+	return MIJ_OK;
+}
+
+extern "C" int mij_enc_group_work(const mij_encoder *e, int group)
+{
+	if (!e || group < 0 || group >= EG_GROUPS)
+		return set_err(MIJ_E_ARG, "bad encoder or group");
+	if (!e->uploaded)
+		return set_err(MIJ_E_STATE, "mij_enc_group_work before mij_enc_upload");
+	return (int)e->n_work[group];
+}
+
+extern "C" int mij_enc_slot_arith(const mij_encoder *e, int slot)
+{
+	const EncSlot *s = enc_slot(e, slot);
+	return s ? s->arith : MIJ_E_ARG;
 }
 
 extern "C" int mij_enc_set_optimize(mij_encoder *e, int slot, int on)
@@ -4166,7 +4236,7 @@ extern "C" int mij_enc_add_device_planes(mij_encoder *e, const mij_in_planes *p,
 static bool enc_own_header(const mij_encoder *e, const EncSlot &s)
 {
 	return s.clone_of < 0 || s.optimize || e->slots[(size_t)s.clone_of].optimize || s.restart != e->slots[(size_t)s.clone_of].restart || s.progressive ||
-			 e->slots[(size_t)s.clone_of].progressive;
+			 e->slots[(size_t)s.clone_of].progressive || s.arith != e->slots[(size_t)s.clone_of].arith;
 }
 
 /* A progressive slot's geometry as its scans see it (include/mij_host.h, PROGRESSIVE STREAMS):
@@ -4287,10 +4357,11 @@ static int enc_emit_lists(mij_encoder *e)
 		const EncSlot &s = e->slots[i];
 		if (enc_own_header(e, s)) {
 			uint8_t *hdr = m.hdr.h + (size_t)h * MIJ_EMIT_HDR;
+			const bool lj = s.arith == MIJ_ARITH_LIBJPEG; /* libjpeg's framing: a DQT and a DHT segment per table */
 			if (s.progressive) /* SOI .. SOF2; k_prog_build appends the first scan's tables and SOS */
-				hlen_of[i] = (uint32_t)mjw_tframe_progressive(&s.tp, hdr);
+				hlen_of[i] = (uint32_t)(lj ? mjw_lj_tframe_progressive(&s.tp, hdr) : mjw_tframe_progressive(&s.tp, hdr));
 			else /* shorter for a grey slot; for the writer's own 4:2:0 and 4:4:4 what mjw_header_restart writes */
-				hlen_of[i] = (uint32_t)mjw_theader_restart(&s.tp, s.restart, hdr);
+				hlen_of[i] = (uint32_t)(lj ? mjw_lj_theader_restart(&s.tp, s.restart, hdr) : mjw_theader_restart(&s.tp, s.restart, hdr));
 			hdr_of[i] = h++;
 		} else {
 			hdr_of[i] = hdr_of[(size_t)s.clone_of];
@@ -4305,6 +4376,8 @@ static int enc_emit_lists(mij_encoder *e)
 		es.hdr = hdr_of[i];
 		es.ri = (uint32_t)s.restart;
 		es.prog = 0;
+		es.lj = s.arith == MIJ_ARITH_LIBJPEG;
+		es.pad = 0;
 		es.tab = 0;
 		es.ny = s.tp.ncomp == 1 ? 1u : (uint32_t)(s.tp.lh * s.tp.lv);
 		es.hlen = hlen_of[i];
@@ -4934,6 +5007,8 @@ static EncGroup enc_classify(const mij_encoder *e, const EncSlot &s)
 	const mjw_tplan &t = s.tp;
 	if (!enc_has_pixels(s.kind))
 		return EG_NONE;
+	if (s.arith == MIJ_ARITH_LIBJPEG) /* pass 2's group; a pixel slot also takes EG_LJ_PASS1 of it */
+		return t.ncomp == 1 ? EG_LJGREY : t.lh == 1 ? EG_LJ444 : t.lv == 1 ? EG_LJ422 : EG_LJ420;
 	if (s.planes)
 		return t.ncomp == 1 ? EG_PGREY : t.lh == 2 ? (t.lv == 2 ? EG_P420 : EG_P422) : (t.lv == 2 ? EG_P440 : EG_P444);
 	if (t.ncomp == 1)
@@ -4954,12 +5029,45 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 	if (!n)
 		return set_err(MIJ_E_STATE, "encoder batch is empty");
 	std::vector<WorkIdct> work[EG_GROUPS];
+	size_t lj_bytes = 0, n_lj = 0;
+	for (const EncSlot &s : e->slots)
+		n_lj += s.arith == MIJ_ARITH_LIBJPEG;
+	if (n_lj) { /* one record per slot; the planes of the pixel slots among them one behind the other */
+		Grow grow(e->stream);
+		grow(e->lj, n);
+		if (grow.rc != MIJ_OK)
+			return grow.rc;
+		memset(e->lj.h, 0, sizeof(LjEncSlot) * n);
+	}
 	for (size_t i = 0; i < n; ++i) {
 		const EncSlot &s = e->slots[i];
 		e->imgs.h[i] = s.dev;
 		const EncGroup g = enc_classify(e, s);
 		if (g == EG_NONE)
 			continue;
+		if (s.arith == MIJ_ARITH_LIBJPEG) {
+			const mjw_tplan &t = s.tp;
+			LjEncSlot &L = e->lj.h[i];
+			L.from_pix = s.planes;
+			L.off = lj_bytes;
+			L.rw = (uint32_t)(t.plan.width + 7) / 8u;
+			L.rh = (uint32_t)(t.plan.height + 7) / 8u;
+			L.srows = (uint32_t)(t.plan.height + (t.ncomp == 1 ? 1 : t.lv) - 1) / (uint32_t)(t.ncomp == 1 ? 1 : t.lv);
+			for (int k = 0; k < 64; ++k) { /* natural order from the tables' zigzag order */
+				const int z = enc_zigzag_of[k];
+				L.m[0][k] = mjw_lj_quant_magic(t.plan.ytab[z]), L.h[0][k] = 4u * t.plan.ytab[z];
+				L.m[1][k] = mjw_lj_quant_magic(t.plan.ctab[z]), L.h[1][k] = 4u * t.plan.ctab[z];
+			}
+			const uint32_t nm = (uint32_t)(t.plan.mcu_x * t.plan.mcu_y);
+			if (!s.planes) {
+				lj_bytes += enc_plane_bytes(t);
+				for (uint32_t cy = 0; cy < (uint32_t)t.plan.mcu_y * 8u; ++cy)
+					work[EG_LJ_PASS1(g)].push_back(WorkIdct{(uint32_t)i, 0u, cy, 0u});
+			}
+			for (uint32_t f = 0; f < nm; f += enc_families[g].strip)
+				work[g].push_back(WorkIdct{(uint32_t)i, 0u, f, 0u});
+			continue;
+		}
 		/* a strip kernel's items count MCUs; the per-unit pair's count the luma units, and in the next group the two chroma units per MCU */
 		const bool pair = g <= EG_C420;
 		const uint32_t nm = (uint32_t)(s.tp.plan.mcu_x * s.tp.plan.mcu_y);
@@ -4973,8 +5081,12 @@ extern "C" int mij_enc_upload(mij_encoder *e)
 		total += work[g].size();
 	Grow grow(e->stream);
 	grow(e->work, total);
+	if (lj_bytes)
+		grow(e->lj_planes, lj_bytes);
 	if (grow.rc != MIJ_OK)
 		return grow.rc;
+	if (n_lj)
+		HIP_TRY(hipMemcpyAsync(e->lj.d, e->lj.h, sizeof(LjEncSlot) * n, hipMemcpyHostToDevice, e->stream));
 	size_t pos = 0;
 	for (int g = 0; g < EG_GROUPS; ++g) {
 		e->first_work[g] = pos;
@@ -5028,8 +5140,12 @@ extern "C" int mij_enc_launch(mij_encoder *e)
 		if (!e->n_work[g])
 			continue;
 		const EncFamily &f = enc_families[g];
-		hipLaunchKernelGGL(f.k, dim3((unsigned)e->n_work[g]), dim3(f.threads), f.lds, e->stream, e->imgs.d, e->work.d + e->first_work[g], e->pix.d,
-								 reinterpret_cast<int16_t *>(e->du.d));
+		if (f.klj)
+			hipLaunchKernelGGL(f.klj, dim3((unsigned)e->n_work[g]), dim3(f.threads), f.lds, e->stream, e->imgs.d, e->work.d + e->first_work[g], e->pix.d,
+									 reinterpret_cast<int16_t *>(e->du.d), static_cast<const LjEncSlot *>(e->lj.d), e->lj_planes.d);
+		else
+			hipLaunchKernelGGL(f.k, dim3((unsigned)e->n_work[g]), dim3(f.threads), f.lds, e->stream, e->imgs.d, e->work.d + e->first_work[g], e->pix.d,
+									 reinterpret_cast<int16_t *>(e->du.d));
 		HIP_TRY(hipGetLastError());
 	}
 	if (e->em.arena.d) {

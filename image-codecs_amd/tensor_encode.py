@@ -10,7 +10,8 @@ import math
 import torch
 
 from .binding import (Context, Encoder, InConvert, InTensor, WritePlan, emit_jpeg, emit_transcoded, lib, sampled_plan, sampling_factors,
-                      sampling_name, _qtable_pair, plane_sampling, planes_plan, split_planes, video_range_convert, MIJ_LAYOUT_HWC, MIJ_LAYOUT_CHW, MIJ_DT_F16, MIJ_DT_BF16, MIJ_DT_F32)
+                      sampling_name, _qtable_pair, plane_sampling, planes_plan, split_planes, video_range_convert, MIJ_LAYOUT_HWC, MIJ_LAYOUT_CHW, MIJ_DT_F16, MIJ_DT_BF16, MIJ_DT_F32,
+                      MIJ_ARITH_LIBJPEG, ARITHMETICS, libjpeg_reframe)
 from .tensor_out import _one_hip_runtime
 
 # one launch takes at most this many pictures / bytes of pixel arena; larger calls are cut into chunks
@@ -100,6 +101,26 @@ def _sampling_values(v, n):
     return vals
 
 
+def _arith_values(v, n):
+    """arithmetic= as one of "stb" / "libjpeg" per picture"""
+    what = "arithmetic must be 'stb', 'libjpeg' or one of those per picture (got %r)"
+    if isinstance(v, str):
+        vals = [v] * n
+    else:
+        if v is None or isinstance(v, (bytes, torch.Tensor)):
+            raise ValueError(what % (v,))
+        try:
+            vals = list(v)
+        except TypeError:
+            raise ValueError(what % (v,)) from None
+        if len(vals) != n:
+            raise ValueError("arithmetic has %d values for %d pictures" % (len(vals), n))
+    for x in vals:
+        if not isinstance(x, str) or x not in ARITHMETICS:
+            raise ValueError(what % (x,))
+    return vals
+
+
 class TensorEncoder:
     """Encodes uint8 pictures that live on a GPU into JPEG byte streams, each exactly what stbi_write_jpg_to_func writes for that
     picture (encode), and float16 / bfloat16 / float32 pictures as the uint8 pictures they de-normalise to (encode_normalized).
@@ -120,6 +141,7 @@ class TensorEncoder:
         self.last_host_emitted = 0
         self.last_restarts = []
         self.last_subsampling = []
+        self.last_arithmetic = []
 
     @property
     def device(self):
@@ -222,7 +244,7 @@ class TensorEncoder:
         return self._enc
 
     def encode(self, images, *, quality=90, layout="CHW", flip_vertically=False, optimize=False, restart_rows=None, restart_mcus=None,
-               progressive=False, subsampling=None, qtables=None):
+               progressive=False, subsampling=None, qtables=None, arithmetic="stb"):
         """quality: 1..100, or 0 for the default 90, as stbi_write_jpg takes it.  images: a 4-D uint8 tensor on the GPU ([N, C, H, W] for layout "CHW", [N, H, W, C] for "HWC") or a sequence of 3-D
         (2-D: grey) uint8 tensors, whose sizes may differ; C is 1..4 (stbi_write_jpg's comp).  Strided views are accepted (unit
         stride along W for CHW; strides C and 1 along W and C for HWC).  -> one bytes object per picture: what
@@ -243,12 +265,18 @@ class TensorEncoder:
         last_subsampling[i] is the name each stream used.
         qtables: None or (luma, chroma), 64 ints 1..255 each in zigzag order (quality_tables' convention) in place of the tables of a
         quality; the sampling is then "420" unless subsampling says otherwise.  ValueError for an unknown name, for qtables together
-        with a quality other than the default, and for tables that are not 64 values in 1..255."""
+        with a quality other than the default, and for tables that are not 64 values in 1..255.
+        arithmetic: "stb" (the default) or "libjpeg", or one of those per picture.  "libjpeg" writes what PIL.Image.save(..., quality=,
+        subsampling=), torchvision.io.encode_jpeg and cv2.imencode (libjpeg-turbo) write for the picture, byte for byte -- libjpeg's integer
+        colour conversion, chroma filter, forward DCT and quantiser and its framing of the header (include/mij_host.h, LIBJPEG ENCODING);
+        optimize, progressive and restart intervals are libjpeg's optimize=, progressive= and restart markers.  Its default subsampling is
+        "420" whatever the quality, as libjpeg's is.  It takes C = 1 or 3 and no "440": ValueError otherwise, and for any other value.
+        last_arithmetic[i] is what each picture got."""
         return self._encode(images, None, None, quality, layout, flip_vertically, optimize, False, restart_rows, restart_mcus, progressive,
-                            subsampling, qtables)
+                            subsampling, qtables, arithmetic)
 
     def encode_normalized(self, images, *, mean=None, std=None, quality=90, layout="CHW", flip_vertically=False, optimize=False,
-                          restart_rows=None, restart_mcus=None, progressive=False, subsampling=None, qtables=None):
+                          restart_rows=None, restart_mcus=None, progressive=False, subsampling=None, qtables=None, arithmetic="stb"):
         """encode() for the tensors a model works on: images as for encode() -- the same shapes, stride rules and layouts -- but float16,
         bfloat16 or float32, one dtype per call.  The pictures are de-normalised on the GPU, inside the kernel that gathers them
         (mij_enc_add_device_float), by the contract of include/mij.h: for element x of channel c
@@ -261,12 +289,12 @@ class TensorEncoder:
         tensors come back as the bytes they were made from, for all three dtypes.  A tensor holding 0..255 values is std=[1/255]*C.
         ValueError, before any device is touched, for uint8 or any other non-float dtype, mixed dtypes, a wrong number of mean / std
         values, a std of 0, a value that is not finite, and everything encode() refuses.  restart_rows, restart_mcus, progressive,
-        subsampling, qtables: as for encode()."""
+        subsampling, qtables, arithmetic: as for encode()."""
         return self._encode(images, mean, std, quality, layout, flip_vertically, optimize, True, restart_rows, restart_mcus, progressive,
-                            subsampling, qtables)
+                            subsampling, qtables, arithmetic)
 
     def encode_ycbcr(self, pictures, *, subsampling="420", video_range=False, quality=90, qtables=None, flip_vertically=False, optimize=False,
-                     restart_rows=None, restart_mcus=None, progressive=False):
+                     restart_rows=None, restart_mcus=None, progressive=False, arithmetic="stb"):
         """JPEG streams from Y, Cb and Cr PLANES as a video decoder, a camera pipeline or a model holds them: no conversion to RGB and
         back, no second chroma filter -- the samples reach the stream as they lie (include/mij_host.h, PLANE ENCODING) -> one bytes
         object per picture: what mjh_write_jpg_planes_to_memory writes for those planes.
@@ -280,6 +308,8 @@ class TensorEncoder:
         colour matrix (BT.601 against BT.709) is not touched.
         quality, qtables, flip_vertically, optimize, restart_rows, restart_mcus, progressive: as for encode(); the MCU, and with it a
         restart interval, is 8 * lh x 8 * lv pixels.  last_subsampling and last_restarts report as they do for encode().
+        arithmetic: as for encode(): "libjpeg" gives the planes libjpeg's forward DCT, quantiser, dummy blocks and header -- what Pillow
+        writes for a "YCbCr"-mode or "L" picture of those samples; no "440".
         ValueError for plane shapes that do not match, a dtype other than uint8, a tensor that is not on a GPU, an unknown sampling and a
         restart interval together with progressive."""
         if not isinstance(optimize, bool):
@@ -306,6 +336,10 @@ class TensorEncoder:
         samplings = _sampling_values(subsampling, len(pictures))
         for sm in samplings:
             plane_sampling(sm)
+        ariths = _arith_values(arithmetic, len(pictures))
+        for sm, ar in zip(samplings, ariths):
+            if ar == "libjpeg" and sm == "440":
+                raise ValueError("arithmetic 'libjpeg' does not serve subsampling '440'")
         pics = []
         for i, (pic, sm) in enumerate(zip(pictures, samplings)):
             for t in ([pic] if isinstance(pic, torch.Tensor) else list(pic)):
@@ -334,6 +368,7 @@ class TensorEncoder:
                 raise ValueError("picture size %dx%d outside 1..65535" % (w, h))
         self.last_restarts = restarts = []
         self.last_subsampling = used = []
+        self.last_arithmetic = list(ariths)
         if not pics:
             return []
         sizes, plans = [], {}
@@ -375,13 +410,15 @@ class TensorEncoder:
                 # a stride of an axis of one element addresses nothing: 0 rows down, 1 sample across
                 triples = [(t.data_ptr(), t.stride(0) if t.shape[0] > 1 else 0, t.stride(1) if t.shape[1] > 1 else 1) for t in planes]
                 slot = enc.add_device_planes(triples, w, h, samplings[k], quality, qtables, flip=flip, convert=cv)
+                if ariths[k] == "libjpeg":
+                    enc.set_arith(slot, MIJ_ARITH_LIBJPEG)
                 if progressive:
                     enc.set_progressive(slot)
                 elif optimize:
                     enc.set_optimize(slot)
                 if restarts[k]:
                     enc.set_restart(slot, restarts[k])
-            streams, hst = self._run(enc, [True] * (j - i), optimize, progressive)
+            streams, hst = self._run(enc, [True] * (j - i), optimize, progressive, [a == "libjpeg" for a in ariths[i:j]])
             out.extend(streams)
             host += hst
             i = j
@@ -389,7 +426,7 @@ class TensorEncoder:
         return out
 
     def _encode(self, images, mean, std, quality, layout, flip_vertically, optimize, floats, restart_rows=None, restart_mcus=None,
-                progressive=False, subsampling=None, qtables=None):
+                progressive=False, subsampling=None, qtables=None, arithmetic="stb"):
         if not isinstance(optimize, bool):
             raise ValueError("optimize must be a bool, got %r" % (optimize,))
         if not isinstance(progressive, bool):
@@ -403,6 +440,16 @@ class TensorEncoder:
             qtables = (list(qtables[0]), list(qtables[1]))
         views = self._views(images, layout, floats)
         samplings = _sampling_values(subsampling, len(views))
+        ariths = _arith_values(arithmetic, len(views))
+        for k, (v, ar) in enumerate(zip(views, ariths)):
+            if ar != "libjpeg":
+                continue
+            if samplings[k] is None:  # libjpeg's default, not the writer's quality-dependent choice
+                samplings[k] = "420"
+            if samplings[k] == "440":
+                raise ValueError("picture %d: arithmetic 'libjpeg' does not serve subsampling '440'" % k)
+            if v[3] not in (1, 3):
+                raise ValueError("picture %d has %d channels; arithmetic 'libjpeg' takes 1 or 3" % (k, v[3]))
         convs = None
         if floats:  # one InConvert per channel count among the pictures; mean / std are checked even for an empty call
             mean, std = _numbers(mean, "mean"), _numbers(std, "std")
@@ -418,6 +465,7 @@ class TensorEncoder:
         self._placed(views)
         self.last_restarts = restarts = []
         self.last_subsampling = used = []
+        self.last_arithmetic = list(ariths)
         if not views:
             return []
         flip = bool(flip_vertically)
@@ -452,14 +500,15 @@ class TensorEncoder:
                 pix += sizes[j][0]
                 j += 1
             streams, h = self._encode_chunk(views[i:j], sizes[i:j], quality, lay, flip, optimize, convs[i:j] if floats else None, restarts[i:j],
-                                            progressive, samplings[i:j], qtables)
+                                            progressive, samplings[i:j], qtables, ariths[i:j])
             out.extend(streams)
             host += h
             i = j
         self.last_host_emitted = host
         return out
 
-    def _encode_chunk(self, views, sizes, quality, lay, flip, optimize, convs=None, restarts=None, progressive=False, samplings=None, qtables=None):
+    def _encode_chunk(self, views, sizes, quality, lay, flip, optimize, convs=None, restarts=None, progressive=False, samplings=None, qtables=None,
+                      ariths=None):
         if not self._arena:  # a first guess, about 0.75 bytes per pixel; misses grow it
             self._arena = _align(sum(1024 + (px * 3) // 4 for (_, _, px) in sizes), 1 << 20)
         enc = self._encoder_for(len(views), sum(s[0] for s in sizes), sum(s[1] for s in sizes))
@@ -468,6 +517,8 @@ class TensorEncoder:
             sm = samplings[k] if samplings else None
             slot = (enc.add_device(it, quality, flip, sm, qtables) if convs is None else
                     enc.add_device_float(it, convs[k], quality, flip, sm, qtables))
+            if ariths and ariths[k] == "libjpeg":
+                enc.set_arith(slot, MIJ_ARITH_LIBJPEG)
             if progressive:
                 enc.set_progressive(slot)
             elif optimize:
@@ -475,10 +526,11 @@ class TensorEncoder:
             if restarts and restarts[k]:
                 enc.set_restart(slot, restarts[k])
         own = [qtables is not None or bool(samplings and samplings[slot] is not None) for slot in range(len(views))]
-        return self._run(enc, own, optimize, progressive)
+        return self._run(enc, own, optimize, progressive, [a == "libjpeg" for a in ariths] if ariths else None)
 
-    def _run(self, enc, own, optimize, progressive):
-        """upload, launch and bring back the streams of the encoder's slots; own[slot]: the slot has a plan of its own (mij_enc_tplan)"""
+    def _run(self, enc, own, optimize, progressive, lj=None):
+        """upload, launch and bring back the streams of the encoder's slots; own[slot]: the slot has a plan of its own (mij_enc_tplan);
+        lj[slot]: it is a libjpeg slot, whose host-finished stream takes libjpeg's framing"""
         enc.upload()
         enc.launch()
         enc.fetch_streams()
@@ -490,6 +542,8 @@ class TensorEncoder:
                     data = emit_transcoded(enc.tplan(slot), enc.fetch(slot), optimize, restart_mcus=enc.slot_restart(slot), progressive=progressive)
                 else:
                     data = emit_jpeg(enc.plan(slot), enc.fetch(slot), optimize, restart_mcus=enc.slot_restart(slot), progressive=progressive)
+                if lj and lj[slot]:
+                    data = libjpeg_reframe(data)
                 host += 1
                 if enc.slot_status(slot) == "host flush":  # a progressive slot with a forced flush: the device reported no length
                     n = len(data)

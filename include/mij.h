@@ -879,6 +879,33 @@ int mij_enc_set_progressive(mij_encoder *e, int slot, int on);
 int mij_enc_slot_progressive(const mij_encoder *e, int slot);
 
 /*
+ * libjpeg's arithmetic for a slot: mij_batch_set_arith's counterpart on the writing side.  With MIJ_ARITH_LIBJPEG the slot's data units and
+ * header are those of the section LIBJPEG ENCODING of mij_host.h -- jccolor's constants, jcsample's chroma filter with its edge rules, the
+ * ISLOW forward DCT, libjpeg's quantiser and dummy-block DCs, a DQT and a DHT segment per table -- so that its stream is what Pillow,
+ * torchvision and OpenCV (libjpeg-turbo) write for those pixels, byte for byte.  MIJ_ARITH_STB (the default) is the reference's writer.
+ *
+ * For pixel slots (host, device, device-float) and plane slots.  A pixel slot runs two kernels (mij_libjpeg_enc_kernels.h):
+ * k_lj_enc_color<LH, LV, NC> turns its staged rows into whole-MCU planes of Y, Cb and Cr in a plane scratch the encoder owns and grows at
+ * upload; k_lj_encode_planes<LH, LV, NC> makes the units.  A plane slot runs the second alone on its staged planes.  The slot keeps the
+ * sampling it was added with -- a slot added without options has the writer's own choice for its quality, not libjpeg's "420" default;
+ * name the sampling to be sure.  Optimised tables, restart intervals, progressive output, clones (which inherit the request), emission and
+ * the fetches work unchanged; mij_enc_force_generic does not apply.  An encoder without a request queues exactly what it queued before.
+ *
+ * mij_enc_set_arith: after the slot is added and before mij_enc_upload: MIJ_E_STATE after the upload.  MIJ_E_ARG for a bad slot or
+ * value and, with MIJ_ARITH_LIBJPEG, for a slot of given units or coefficient planes (nothing is transformed), a "440" slot (nothing
+ * judges it) and pictures of 2 or 4 channels.  Asking again replaces the request; mij_enc_reset forgets all requests.
+ * mij_enc_slot_arith: the slot's arithmetic, or a negative code for a bad slot.
+ */
+int mij_enc_set_arith(mij_encoder *e, int slot, int arith);
+int mij_enc_slot_arith(const mij_encoder *e, int slot);
+/* Measurement and tests: the work items the last mij_enc_upload queued for transform kernel `group` of the encoder's kernel table, in
+ * launch order: 0..3 the per-unit pairs (4:4:4 luma, chroma; 4:2:0 luma, chroma), 4..8 the strip kernels of pixel slots (420, 444, 422,
+ * 440, grey), 9..13 those of plane slots (444, 422, 440, 420, grey), 14..17 k_lj_enc_color (444, 422, 420, grey) and 18..21
+ * k_lj_encode_planes (the same).  A group without items is not launched.  MIJ_E_ARG beyond MIJ_ENC_GROUPS, MIJ_E_STATE before upload. */
+#define MIJ_ENC_GROUPS 22
+int mij_enc_group_work(const mij_encoder *e, int group);
+
+/*
  * Lossless transcode: an encoder slot whose data units are the QUANTISED coefficients of a decode batch's slot, taken from the batch's
  * coefficient planes in device memory -- a new slot kind beside given units.  The contract (which sources are transcodable, the unit
  * order, the stream) is written in mij_host.h (mjw_tplan); the slot's stream is what mjw_temit / mjw_temit_optimized write for

@@ -604,6 +604,96 @@ int mjh_write_jpg_planes_to_memory(const mij_plane *planes, int width, int heigh
                                    const unsigned char *luma, const unsigned char *chroma, const mij_in_convert *cv, int flip_vertically,
                                    unsigned flags, int restart_mcus, int progressive, unsigned char **out, size_t *out_len);
 
+/*
+ * LIBJPEG ENCODING: the pixel and plane encoders with libjpeg's default compression arithmetic and libjpeg's framing of the header, so that
+ * the file is what PIL.Image.save, torchvision.io.encode_jpeg and cv2.imencode (libjpeg-turbo) write, byte for byte.  On the GPU:
+ * mij_enc_set_arith(e, slot, MIJ_ARITH_LIBJPEG) (mij.h); these calls are the written contract, tests/libjpeg_enc_model.py restates it in
+ * numpy, and Pillow's files (tests/golden/libjpeg_pillow_enc.npz) are the judge: where a formula here and Pillow disagree, Pillow wins and
+ * this text is corrected.  All arithmetic is integer (nothing leaves 32 bits) and every shift is arithmetic.  Only the pixel side and the
+ * header differ from SAMPLED ENCODING: the emission behind the data units (plain, optimised, restart intervals, progressive) is the same.
+ *
+ * SERVED: uint8 pictures of 3 components (RGB) as "444" (3,1,1), "422" (3,2,1) or "420" (3,2,2), and pictures of 1 or 3 components as
+ * "grey" (1,1,1).  REFUSED, never approximated: "440" (Pillow cannot write it: nothing judges it) and comp 2 and 4.  With no sampling given
+ * (ncomp 0) the sampling is "420", libjpeg's default, whatever the quality.
+ *
+ * COLOUR (jccolor, 16 fraction bits; comp 1: r = g = b, which gives Y = the sample):
+ *   Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *   Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *   Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16
+ *
+ * EDGES.  The MCU is 8 lh x 8 lv pixels.  Columns: every component plane of pixels is extended by its last column to whole MCUs before
+ * any chroma filter.  Luma rows: extended by the last pixel row.  Chroma rows -- NOT the rule of SAMPLED ENCODING -- : the pixel rows are
+ * extended by the last row to a multiple of lv, filtered, and then the last SAMPLE row is repeated down to 8 mcu_y rows.  An 8 x 8 or
+ * 160 x 120 4:2:0 picture therefore has below the picture a chroma row equal to the mean of its last two pixel rows, not the last row alone.
+ *
+ * CHROMA FILTER (jcsample), x the OUTPUT column:
+ *   4:2:2  (a + b + (x & 1)) >> 1                left, right
+ *   4:2:0  (a + b + c + d + 1 + (x & 1)) >> 2    the bias alternates 1, 2, 1, 2 along a row and starts at 1 in every row
+ *
+ * FORWARD DCT (jfdctint, ISLOW) on sample - 128, rows first, then columns; D(x, n) = (x + (1 << (n - 1))) >> n:
+ *   t0=d0+d7 t7=d0-d7 t1=d1+d6 t6=d1-d6 t2=d2+d5 t5=d2-d5 t3=d3+d4 t4=d3-d4
+ *   t10=t0+t3 t13=t0-t3 t11=t1+t2 t12=t1-t2
+ *   rows:    o0=(t10+t11)<<2   o4=(t10-t11)<<2   n=11
+ *   columns: o0=D(t10+t11,2)   o4=D(t10-t11,2)   n=15
+ *   z1=(t12+t13)*4433   o2=D(z1+t13*6270,n)   o6=D(z1-t12*15137,n)
+ *   z1=t4+t7 z2=t5+t6 z3=t4+t6 z4=t5+t7 z5=(z3+z4)*9633
+ *   t4*=2446 t5*=16819 t6*=25172 t7*=12299 z1*=-7373 z2*=-20995 z3=z3*-16069+z5 z4=z4*-3196+z5
+ *   o7=D(t4+z1+z3,n) o5=D(t5+z2+z4,n) o3=D(t6+z2+z3,n) o1=D(t7+z1+z4,n)
+ * The result is the DCT scaled by 8; |o| <= 32768.
+ *
+ * QUANTISER, q the table entry: y = sign(x) * ((|x| + 4q) div 8q).  The division is one multiply-high: with m = floor(2^32 / 8q) + 1
+ * (mjw_lj_quant_magic), (a * m) >> 32 == a div 8q for every a = |x| + 4q with |x| <= 32768 and q = 1..255 -- walked exhaustively by
+ * tests/test_encode_libjpeg_host.py.
+ *
+ * DUMMY BLOCKS.  A luma block of an MCU that lies wholly outside the ceil(W/8) x ceil(H/8) blocks of the picture is not transformed: its AC
+ * terms are 0 and its DC is the QUANTISED DC of the block before it -- in a real block row the block to its left; in a block row below the
+ * picture, for every block of that row, the last block of the MCU's previous block row (which may itself be a right-edge dummy).  Chroma,
+ * "444" and grey have no dummy blocks.
+ *
+ * TABLES: as SAMPLED ENCODING (the quality mapping is libjpeg's own, forced to 1..255), or a given pair.
+ *
+ * STREAM: SOI; APP0 JFIF 1.01, units 0, density 1 x 1, no thumbnail; one DQT segment PER TABLE (table 0 always, table 1 for three
+ * components); SOF0 or SOF2 with component ids 1, 2, 3 and tables 0, 1, 1; one DHT segment PER TABLE in the order DC0, AC0, DC1, AC1
+ * (grey: DC0, AC0); DRI, if any, directly before SOS; SOS, data, EOI.  That is mjw_theader*'s header with its DQT and its DHT segment split
+ * (mjw_lj_reframe): 4 bytes more per table after the first, at most MJW_LJ_HEADER_BYTES.  A progressive stream's scans already carry one
+ * DHT segment per table; only the DQT segment in front of SOF2 changes.
+ *
+ * PLANES (mjw_lj_ptransform_host): PLANE ENCODING's staging -- each plane extended on its own by its last column and row, no filter -- then
+ * the forward DCT, quantiser and dummy blocks above.
+ *
+ *   mjw_lj_plan_init       mjw_splan_init under the rules of SERVED; 0 for what is refused
+ *   mjw_lj_stage_host      pass 1: the pixels as planes of whole MCUs -- Y (8 lh mcu_x x 8 lv mcu_y), then Cb, then Cr (8 mcu_x x 8 mcu_y
+ *                          each), mjw_lj_staged_bytes(t) bytes: colour, edges and the chroma filter
+ *   mjw_lj_units_from_staged   pass 2: those planes -> the units in mjw_tplan order, dummy blocks included
+ *   mjw_lj_transform_host  both; 0 on bad arguments or when memory runs out
+ *   mjw_lj_theader_restart, mjw_lj_theader_optimized_restart, mjw_lj_tframe_progressive   the siblings of mjw_theader_restart,
+ *                          mjw_theader_optimized_restart and mjw_tframe_progressive in libjpeg's framing
+ *   mjh_write_jpg_libjpeg_to_memory   plan + transform + mjw_temit* + framing on the host; arguments as mjh_write_jpg_sampled_to_memory.
+ *                          *out is malloc'ed (the caller frees it).  0 on bad arguments and for what is refused.
+ * Out of scope: 4:4:0 and 4:1:1, alpha inputs, dpi / ICC / EXIF segments, input smoothing, the fast and float DCTs, trellis or mozjpeg
+ * tables, arithmetic coding.
+ */
+#define MJW_LJ_HEADER_EXTRA 16 /* three more DHT segments and one more DQT segment */
+#define MJW_LJ_HEADER_BYTES (MJW_HEADER_RESTART_BYTES + MJW_LJ_HEADER_EXTRA)
+int mjw_lj_plan_init(mjw_tplan *t, int width, int height, int comp, int quality, int ncomp, int lh, int lv, const unsigned char *luma,
+                     const unsigned char *chroma);
+uint32_t mjw_lj_quant_magic(int q);
+int mjw_lj_quantise(int x, int q);
+void mjw_lj_quantise_all(int q, int32_t *out); /* out[x + 32768] = mjw_lj_quantise(x, q) for x = -32768 .. 32768 */
+void mjw_lj_ycc(int r, int g, int b, unsigned char ycc[3]);
+size_t mjw_lj_staged_bytes(const mjw_tplan *t);
+int mjw_lj_stage_host(const mjw_tplan *t, const void *pixels, int flip_vertically, unsigned char *staged);
+int mjw_lj_units_from_staged(const mjw_tplan *t, const unsigned char *staged, int16_t *du);
+int mjw_lj_transform_host(const mjw_tplan *t, const void *pixels, int flip_vertically, int16_t *du);
+int mjw_lj_ptransform_host(const mjw_tplan *t, const mij_plane *planes, const mij_in_convert *cv, int flip_vertically, int16_t *du);
+size_t mjw_lj_reframe(const unsigned char *in, size_t len, unsigned char *out);
+size_t mjw_lj_theader_restart(const mjw_tplan *t, int ri, unsigned char *out);
+size_t mjw_lj_theader_optimized_restart(const mjw_tplan *t, const uint8_t bits[4][16], const uint8_t vals[4][256], int ri, unsigned char *out);
+size_t mjw_lj_tframe_progressive(const mjw_tplan *t, unsigned char *out);
+int mjh_write_jpg_libjpeg_to_memory(const void *pixels, int width, int height, int comp, int quality, int ncomp, int lh, int lv,
+                                    const unsigned char *luma, const unsigned char *chroma, int flip_vertically, unsigned flags, int restart_mcus,
+                                    int progressive, unsigned char **out, size_t *out_len);
+
 /* The tables of stbi__ldr_to_hdr(common.c:391-424) for mij_batch_set_out_f32: lut[256*k + v] for channel k < n_out.  Colour
  * channels (all of them for odd n_out, all but the last for even n_out) get (float)(pow(v / 255.0f, gamma) * scale), the
  * alpha channel of n_out 2 and 4 gets v / 255.0f -- the reference's expressions, evaluated with libm's pow. */
