@@ -118,6 +118,7 @@ from .binding import (  # noqa: F401
     stbi_write_jpg_to_memory,
     detile_coefficients,
     host_decode_staged,
+    host_decode_rows,
     compact_offsets,
     expand_compact_region,
     decode_jpegs_multi,

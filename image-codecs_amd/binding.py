@@ -512,6 +512,25 @@ def host_decode_staged(data, req_comp=0, want_compact=True):
     return d2, region
 
 
+def host_decode_rows(data, req_comp=0, want_compact=True):
+    """mjh_decode_memory_rows (no GPU): host_decode_staged plus the walk's row-extent table -> (desc, region bytes, classes), classes one
+    uint8 per block row, component after component (mij.h, "row-extent table": 0 DC only, 1 inside the 2x2, 2 inside the 4x4, 3 anything
+    or unknown)."""
+    d = HostDecoder.probe(data, req_comp)
+    L = lib()
+    L.mjh_decode_memory_rows.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(ImageDesc), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
+                                         C.POINTER(C.c_char_p)]
+    tiles = [((d.comp[c].bw * d.comp[c].bh) + 63) // 64 for c in range(d.ncomp)]
+    region = np.full(sum(tiles) * (4096 + 128 + 4096), 0xA5, dtype=np.uint8)
+    rows = np.full(sum(d.comp[c].bh for c in range(d.ncomp)), 0xA5, dtype=np.uint8)
+    why = C.c_char_p()
+    d2 = ImageDesc()
+    if not L.mjh_decode_memory_rows(bytes(data), len(data), int(req_comp), C.byref(d2), region.ctypes.data_as(C.c_void_p), C.c_size_t(region.size),
+                                    int(bool(want_compact)), rows.ctypes.data_as(C.c_void_p), C.c_size_t(rows.size), C.byref(why)):
+        raise MijError(why.value.decode() if why.value else "decode failed")
+    return d2, region, rows
+
+
 def compact_offsets(desc):
     """mij_compact_offsets: per component (lo, dc, hi) byte offsets inside an image's region, and the main part's size"""
     tiles = [((desc.comp[c].bw * desc.comp[c].bh) + 63) // 64 for c in range(desc.ncomp)]
@@ -808,6 +827,26 @@ class Batch:
         L.mij_batch_slot_marched.argtypes = [C.c_void_p, C.c_int]
         return bool(_check(L.mij_batch_slot_marched(self._h, int(slot)), "mij_batch_slot_marched"))
 
+    def slot_row_classes(self, slot):
+        """tests: the slot's row-extent table as the next upload sends it (mij_batch_slot_row_classes): one uint8 per block row, component
+        after component; all 3 unless the library's own host walk staged the slot (a clone reads its source's)"""
+        L = lib()
+        L.mij_batch_slot_row_classes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        n = _check(L.mij_batch_slot_row_classes(self._h, int(slot), None, 0), "mij_batch_slot_row_classes")
+        out = np.empty(n, dtype=np.uint8)
+        _check(L.mij_batch_slot_row_classes(self._h, int(slot), out.ctypes.data_as(C.c_void_p), C.c_size_t(n)), "mij_batch_slot_row_classes")
+        return out
+
+    def slot_row_classes_device(self, slot):
+        """tests: the packed table the band kernels read, copied back from the device (mij_batch_fetch_row_classes_packed): one uint8 per
+        MCU row, two bits a component"""
+        L = lib()
+        L.mij_batch_fetch_row_classes_packed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        n = _check(L.mij_batch_fetch_row_classes_packed(self._h, int(slot), None, 0), "mij_batch_fetch_row_classes_packed")
+        out = np.empty(n, dtype=np.uint8)
+        _check(L.mij_batch_fetch_row_classes_packed(self._h, int(slot), out.ctypes.data_as(C.c_void_p), C.c_size_t(n)), "mij_batch_fetch_row_classes_packed")
+        return out
+
     def slot_coef_bytes(self, slot):
         """1 when the slot's coefficients sit in HBM as compact planes (the default), 0 for the int16 tile layout."""
         return lib().mij_batch_slot_coef_bytes(self._h, int(slot))
@@ -866,8 +905,8 @@ class Batch:
 
     def add_jpeg(self, data, req_comp=0, stage=None):
         """Host stage of one image straight into a new slot's pinned staging; returns the slot.  stage None: what the batch front ends do
-        (mjh_decode_memory_fmt: a baseline file is staged as COMPACT planes by the walk itself when the batch's format is compact, no
-        pack pass on the device); "int16": int16 tile-layout staging whatever the file (mjh_decode_memory; compact batches then pack
+        (mjh_decode_memory_rows: a baseline file is staged as COMPACT planes by the walk itself when the batch's format is compact, no
+        pack pass on the device, and the slot takes the walk's row-extent table); "int16": int16 tile-layout staging whatever the file (mjh_decode_memory; compact batches then pack
         it on the device with k_pack_c8 -- the pipeline of rounds 1 and 2, kept for progressive files)."""
         d = HostDecoder.probe(data, req_comp)
         slot = self.add(d)
@@ -878,14 +917,27 @@ class Batch:
             L.mij_batch_stage_region.restype = C.c_void_p
             L.mij_batch_stage_region.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]
             L.mij_batch_coef_format.argtypes = [C.c_void_p]
-            L.mjh_decode_memory_fmt.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(ImageDesc), C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_char_p)]
+            rows_fn = hasattr(L, "mjh_decode_memory_rows")  # an A/B library from before the table (MIJ_LIB) stages without one
+            if rows_fn:
+                L.mjh_decode_memory_rows.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(ImageDesc), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
+                                                     C.POINTER(C.c_char_p)]
+                L.mij_batch_set_row_classes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+            else:
+                L.mjh_decode_memory_fmt.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(ImageDesc), C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_char_p)]
             nb = C.c_size_t()
             region = L.mij_batch_stage_region(self._h, int(slot), C.byref(nb))
             if not region:
                 raise MijError("mij_batch_stage_region: " + L.mij_last_error().decode())
             d2, why = ImageDesc(), C.c_char_p()
-            if not L.mjh_decode_memory_fmt(bytes(data), len(data), int(req_comp), C.byref(d2), region, nb, int(L.mij_batch_coef_format(self._h) == 1), C.byref(why)):
-                raise MijError("mjh_decode_memory_fmt: %s" % (why.value.decode() if why.value else "failed"))
+            # the walk's row-extent table goes in with the planes it describes, as in the batch front ends (mij.h, "row-extent table")
+            rows = np.empty(sum(d.comp[c].bh for c in range(d.ncomp)), dtype=np.uint8)
+            compact = int(L.mij_batch_coef_format(self._h) == 1)
+            if not (L.mjh_decode_memory_rows(bytes(data), len(data), int(req_comp), C.byref(d2), region, nb, compact, rows.ctypes.data_as(C.c_void_p),
+                                             C.c_size_t(rows.size), C.byref(why)) if rows_fn else
+                    L.mjh_decode_memory_fmt(bytes(data), len(data), int(req_comp), C.byref(d2), region, nb, compact, C.byref(why))):
+                raise MijError("mjh_decode_memory_fmt: %s" % (why.value.decode() if why.value else "failed"))  # either entry point: the text callers match
+            if rows_fn:
+                _check(L.mij_batch_set_row_classes(self._h, int(slot), rows.ctypes.data_as(C.c_void_p), C.c_size_t(rows.size)), "mij_batch_set_row_classes")
         if d2.flags:
             _check(L.mij_batch_set_flags(self._h, slot, d2.flags), "mij_batch_set_flags")
             d.flags = d2.flags

@@ -15,6 +15,7 @@
 #include "jpeg_entropy.h"
 #include "mij.h"
 #include "mij_host.h"
+#include "mij_internal.h"
 
 typedef struct {
 	mij_batch *b;
@@ -45,10 +46,21 @@ static void sync_tables(mij_batch *b, int slot, const mij_image_desc *now, const
 		mij_batch_set_dequant(b, slot, now);
 }
 
+/* the row-extent table of a slot whose staging the host walk has just written (mij_internal.h) */
+static void stage_row_classes(mij_batch *b, int slot, const mij_image_desc *d, const uint8_t *rows)
+{
+	size_t n = 0;
+	int c;
+	for (c = 0; c < d->ncomp; ++c)
+		n += (size_t)d->comp[c].bh;
+	mij_batch_set_row_classes(b, slot, rows, n);
+}
+
 static void *worker(void *arg)
 {
 	pool_t *p = (pool_t *)arg;
 	int good = 0;
+	uint8_t rows[MJH_ROW_CLASSES_MAX];
 	for (;;) {
 		int i, slot;
 		const char *why = NULL;
@@ -67,7 +79,8 @@ static void *worker(void *arg)
 			 * batch was asked for int16 planes; progressive files stay int16 (mjh_decode_memory_fmt) */
 			size_t bytes = 0;
 			uint8_t *region = mij_batch_stage_region(p->b, slot, &bytes);
-			if (region && mjh_decode_memory_fmt(p->bufs[i], p->lens[i], p->req_comp, &d, region, bytes, mij_batch_coef_format(p->b) == MIJ_COEF_COMPACT, &why)) {
+			if (region && mjh_decode_memory_rows(p->bufs[i], p->lens[i], p->req_comp, &d, region, bytes, mij_batch_coef_format(p->b) == MIJ_COEF_COMPACT, rows, sizeof(rows), &why)) {
+				stage_row_classes(p->b, slot, &d, rows);
 				if (d.flags)
 					mij_batch_set_flags(p->b, slot, d.flags);
 				if (d.color != p->descs[i].color) /* a JFIF / Adobe marker behind SOF changed the colour branch */
@@ -549,6 +562,7 @@ static void *multi_worker(void *arg)
 	multi_t *m = (multi_t *)arg;
 	pool_t *p = &m->p;
 	int good = 0;
+	uint8_t rows[MJH_ROW_CLASSES_MAX];
 	for (;;) {
 		int i, slot, k, last;
 		const char *why = NULL;
@@ -565,7 +579,8 @@ static void *multi_worker(void *arg)
 			size_t bytes = 0;
 			uint8_t *region = mij_batch_stage_region(b, slot, &bytes);
 			d = p->descs[i];
-			if (region && mjh_decode_memory_fmt(p->bufs[i], p->lens[i], p->req_comp, &d, region, bytes, mij_batch_coef_format(b) == MIJ_COEF_COMPACT, &why)) {
+			if (region && mjh_decode_memory_rows(p->bufs[i], p->lens[i], p->req_comp, &d, region, bytes, mij_batch_coef_format(b) == MIJ_COEF_COMPACT, rows, sizeof(rows), &why)) {
+				stage_row_classes(b, slot, &d, rows);
 				if (d.flags)
 					mij_batch_set_flags(b, slot, d.flags);
 				if (d.color != p->descs[i].color)

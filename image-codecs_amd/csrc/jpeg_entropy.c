@@ -160,6 +160,9 @@ static const uint8_t k_dezigzag[64 + 15] = {
 static uint16_t k_tile_off[64 + 15];
 static uint8_t k_pos_of_zig[64 + 15]; /* zigzag index -> in-block position P = 8*column + slot (the escape bytes' order) */
 static uint8_t k_zig_of_pos[64]; /* in-tile position P = 8*chunk + slot -> zigzag index */
+/* zigzag index -> what a non-zero coefficient there rules out for its block (the extent classes of mij.h, "row-extent table"):
+ * 1 not DC only, 2 not inside the top-left 2 x 2, 4 not inside the 4 x 4 */
+static uint8_t k_ext_of_zig[64 + 15];
 static int k_tile_off_ready;
 static int k_have_pdep; /* the CPU has BMI2 pdep and popcnt at full speed: the refinement scans take their correction bits a run at a time */
 static void init_zig_masks(void);
@@ -174,6 +177,7 @@ static void init_tile_off(void)
 		int P = 8 * (nat & 7) + mij_rowslot[nat >> 3];
 		k_tile_off[k] = (uint16_t)(((P >> 3) << 9) + (P & 7));
 		k_pos_of_zig[k] = (uint8_t)P;
+		k_ext_of_zig[k] = (uint8_t)((k ? 1 : 0) | (((nat >> 3) > 1 || (nat & 7) > 1) ? 2 : 0) | (((nat >> 3) > 3 || (nat & 7) > 3) ? 4 : 0));
 		if (k < 64)
 			k_zig_of_pos[P] = (uint8_t)k;
 	}
@@ -563,11 +567,12 @@ static int decode_block(mjh_decoder *d, int16_t *blk, const mjh_huff *hdc, const
  * and -- only for a block that holds a coefficient outside -128..127 -- 64 escape bytes h with coefficient == sext8(low) + 256 * h.
  * The fast-AC table only holds values inside a byte (build_fast_ac), so only the slow path can escape.  Same symbols, same order,
  * same failure points as decode_block: the planes k_pack_c8 would make from decode_block's output, byte for byte (tests).
+ * *rowext, the extent of the block's row so far (k_ext_of_zig), takes every position the block writes and 4 for an escaped block.
  */
-static int decode_block_c8(mjh_decoder *d, mjh_comp *cp, int L, const mjh_huff *hdc, const mjh_huff *hac, const int16_t *fac, const uint16_t *qz)
+static int decode_block_c8(mjh_decoder *d, mjh_comp *cp, int L, const mjh_huff *hdc, const mjh_huff *hac, const int16_t *fac, const uint16_t *qz, uint8_t *rowext)
 {
 	uint8_t *blk = cp->lo8 + block_base(L), *esc = NULL;
-	int diff, dc, k, t;
+	int diff, dc, k, t, ext = 0;
 	int32_t l1;
 	bitreg b = reg_load(d);
 
@@ -603,6 +608,7 @@ static int decode_block_c8(mjh_decoder *d, mjh_comp *cp, int L, const mjh_huff *
 			b.buf <<= s;
 			b.bits -= s;
 			blk[k_tile_off[k]] = (uint8_t)(r >> 8);
+			ext |= k_ext_of_zig[k];
 			if (esc) /* a spill position written twice: what was there may have had a high byte */
 				esc[k_pos_of_zig[k]] = 0;
 			l1 += iabs16((r >> 8) * qz[k]);
@@ -624,6 +630,7 @@ static int decode_block_c8(mjh_decoder *d, mjh_comp *cp, int L, const mjh_huff *
 				k += r;
 				v = extend_receive_r(d, s, &b);
 				blk[k_tile_off[k]] = (uint8_t)v;
+				ext |= k_ext_of_zig[k];
 				if (esc || v != (int8_t)v) {
 					if (!esc) {
 						esc = cp->hi8 + ((size_t)L << 6);
@@ -639,6 +646,7 @@ static int decode_block_c8(mjh_decoder *d, mjh_comp *cp, int L, const mjh_huff *
 		}
 	} while (k < 64);
 	reg_store(d, &b);
+	*rowext |= (uint8_t)(esc ? 4 : ext);
 	if (l1 > d->max_block_l1)
 		d->max_block_l1 = l1;
 	return 1;
@@ -1127,7 +1135,7 @@ static int parse_entropy_coded_data(mjh_decoder *d)
 			const int16_t *fac = d->fast_ac[cp->ha];
 			for (j = 0; j < h; ++j)
 				for (i = 0; i < w; ++i) {
-					if (!(d->compact ? decode_block_c8(d, cp, i + j * cp->bw, hdc, hac, fac, qz[0]) : decode_block(d, cp->plane + block_base(i + j * cp->bw), hdc, hac, fac, cp, qz[0])))
+					if (!(d->compact ? decode_block_c8(d, cp, i + j * cp->bw, hdc, hac, fac, qz[0], d->row_ext[d->order[0]] + j) : decode_block(d, cp->plane + block_base(i + j * cp->bw), hdc, hac, fac, cp, qz[0])))
 						return 0;
 					if (restart_check(d)) {
 						cp->touched = 1;
@@ -1147,7 +1155,7 @@ static int parse_entropy_coded_data(mjh_decoder *d)
 						for (y = 0; y < cp->v; ++y)
 							for (x = 0; x < cp->h; ++x) {
 								int L = (i * cp->h + x) + (j * cp->v + y) * cp->bw;
-								if (!(d->compact ? decode_block_c8(d, cp, L, hdc, hac, fac, qz[ci]) : decode_block(d, cp->plane + block_base(L), hdc, hac, fac, cp, qz[ci])))
+								if (!(d->compact ? decode_block_c8(d, cp, L, hdc, hac, fac, qz[ci], d->row_ext[d->order[ci]] + (j * cp->v + y)) : decode_block(d, cp->plane + block_base(L), hdc, hac, fac, cp, qz[ci])))
 									return 0;
 							}
 					}
@@ -1687,6 +1695,7 @@ int mjh_attach_staging(mjh_decoder *d, const mij_image_desc *desc, uint8_t *regi
 	int i;
 	init_tile_off();
 	d->any_escape = 0;
+	memset(d->row_ext, 0, sizeof(d->row_ext));
 	d->defer_l1 = (want_compact && d->progressive) ? 1 : 0; /* the planes will be packed on the device: k_pack_c8 takes the L1 bound there */
 	if (want_compact && !d->progressive) {
 		for (i = 0; i < desc->ncomp; ++i) {
@@ -1721,7 +1730,25 @@ uint32_t mjh_stage_flags(const mjh_decoder *d)
 			 ((d->progressive && d->defer_l1) ? MIJ_FLAG_L1_ON_DEVICE : 0u);
 }
 
+void mjh_row_classes(const mjh_decoder *d, const mij_image_desc *desc, uint8_t *out)
+{
+	/* the walk saw every block of every row it lowers: rows no scan reached hold the zeros the staging was cleared to */
+	const int known = d->compact && !d->progressive && !mjh_needs_wide_idct(d);
+	int i, r;
+	for (i = 0; i < desc->ncomp; ++i)
+		for (r = 0; r < desc->comp[i].bh; ++r) {
+			const int e = r < MJH_ROWS_MAX ? d->row_ext[i][r] : 4;
+			*out++ = (uint8_t)((!known || (e & 4)) ? 3 : ((e & 2) ? 2 : (e & 1)));
+		}
+}
+
 int mjh_decode_memory_fmt(const uint8_t *buf, int len, int req_comp, mij_image_desc *desc, uint8_t *region, size_t region_bytes, int want_compact, const char **reason)
+{
+	return mjh_decode_memory_rows(buf, len, req_comp, desc, region, region_bytes, want_compact, NULL, 0, reason);
+}
+
+int mjh_decode_memory_rows(const uint8_t *buf, int len, int req_comp, mij_image_desc *desc, uint8_t *region, size_t region_bytes, int want_compact, uint8_t *row_classes,
+									size_t row_classes_bytes, const char **reason)
 {
 	const char *why = NULL;
 	mjh_reader r;
@@ -1745,6 +1772,17 @@ int mjh_decode_memory_fmt(const uint8_t *buf, int len, int req_comp, mij_image_d
 		desc->flags |= mjh_stage_flags(d);
 		desc->color = mjh_color_mode(d, desc->n_out); /* JFIF / Adobe markers behind SOF count too (codec/jpeg.c:2244) */
 		mjh_final_dequant(d, desc);                   /* ... and so do DQT segments */
+		if (row_classes) {
+			size_t rows = 0;
+			int i;
+			for (i = 0; i < desc->ncomp; ++i)
+				rows += (size_t)desc->comp[i].bh;
+			if (rows > row_classes_bytes) {
+				why = "outofmem";
+				goto done;
+			}
+			mjh_row_classes(d, desc, row_classes);
+		}
 		ok = 1;
 	}
 done:

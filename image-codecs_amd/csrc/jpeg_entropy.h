@@ -44,6 +44,7 @@ long mjh_reader_unread(const mjh_reader *r);
 
 /* ---- decoder state ---- */
 #define MJH_FAST_BITS 9
+#define MJH_ROWS_MAX 8200 /* block rows of a component: at most 65535 / 8 rounded up to whole MCUs of up to four */
 
 typedef struct {
 	uint8_t fast[1 << MJH_FAST_BITS]; /* symbol index for codes <= 9 bits, 255 = take the slow path */
@@ -100,6 +101,9 @@ typedef struct {
 	 * read, so no pack pass and half the bytes over PCIe; progressive scans read-modify-write int16 planes and never set this.
 	 * any_escape: some block holds a coefficient beyond a byte (its escape bytes are in use: MIJ_FLAG_HAS_ESCAPES) */
 	int compact, any_escape;
+	/* compact baseline walks: per component and block row, what the row's blocks hold beyond the extent classes (jpeg_entropy.c,
+	 * k_ext_of_zig; 4 as well for an escaped block) -- the row-extent table of mij.h before it is read out (mjh_row_classes) */
+	uint8_t row_ext[4][MJH_ROWS_MAX];
 	/* 1: a progressive file staged for a batch that packs on the device: the per-block L1 bound is taken there (MIJ_FLAG_L1_ON_DEVICE), not in a pass over the planes here */
 	int defer_l1;
 	/* largest per-block sum of |de-quantised coefficient| seen (baseline), for MIJ_FLAG_WIDE_IDCT */
@@ -140,6 +144,9 @@ int mjh_needs_wide_idct(const mjh_decoder *d);
 int mjh_attach_staging(mjh_decoder *d, const mij_image_desc *desc, uint8_t *region, int want_compact);
 /* MIJ_FLAG_* the finished walk raises: WIDE_IDCT, and STAGED_COMPACT / HAS_ESCAPES for compact staging */
 uint32_t mjh_stage_flags(const mjh_decoder *d);
+/* The finished walk's row-extent table (mij.h, "row-extent table") into out, desc->comp[c].bh bytes for each component in turn: the
+ * classes a baseline walk into compact planes saw, 3 throughout for anything else and for a stream that needs MIJ_FLAG_WIDE_IDCT */
+void mjh_row_classes(const mjh_decoder *d, const mij_image_desc *desc, uint8_t *out);
 
 /* the one-call memory forms and the batch front end are declared in include/mij_host.h */
 

@@ -59,6 +59,9 @@ struct DevImage {
 	uint64_t src16_off; /* k_pack_c8 only: byte offset of the image's int16 tile-layout planes (back to back) in the upload scratch */
 	uint32_t es_blk_off; /* GPU entropy stage: index of the image's first block in the per-block arrays (scan order) */
 	uint8_t es_bpm, es_j0[4], es_pad[3]; /* blocks per MCU; first block-in-MCU of every component */
+	uint32_t rc_off; /* band kernels: byte offset (a multiple of 8) of the image's packed row-extent table in the coefficient arena, whose head
+	                    the batch keeps for these tables: one byte per MCU row, two bits a component (fused_band, "Row classes"); in what was
+	                    padding, so nothing else moves */
 	uint64_t plane_bytes_total;
 	DevComp comp[4];
 	uint32_t dq[4][32]; /* per component: quantisation table as u16 pairs in in-block position order P */
@@ -494,7 +497,9 @@ __device__ __forceinline__ void load_block_fmt(const CoefView &cv, uint32_t L, c
  * throughout.  Measured and dropped (round 3, tools/ab3.sh, three builds interleaved on one device): the class carried in a 32-bit
  * DC word per block, read one wave-task ahead so that only the chunks the class needs are fetched at all (0 / 2 / 4 / 8 of eight) --
  * 10 % fewer bytes read, and slower: 2.04 against 2.01-2.02 ms on the headline batch, 2.32 against 2.28 ms on the harsh one.  The
- * kernel is bound by instruction issue, not by bytes, and the dependent load costs more than the classification it saves.
+ * kernel is bound by instruction issue, not by bytes, and the dependent load costs more than the classification it saves.  Round 6 took the
+ * idea up in another form, without the dependent vector load and without touching the planes: the extent class of a whole block ROW, kept
+ * beside the planes and fetched with scalar loads rows ahead (fused_band, "Row classes"; load_raw_b8's cap).
  * MIJ_DEV_COUNT_CLASSES in DevImage.flags: lane 0 of every wavefront adds one to g_idct_class[class] (measurement only). */
 #define MIJ_DEV_COUNT_CLASSES 0x200
 __device__ unsigned long long g_idct_class[4];
@@ -616,24 +621,66 @@ struct RawB8 {
 	uint2 h[8];
 	uint16_t dc; /* 16 bits as loaded: widened where it is read, not where a loop carries it */
 };
-__device__ __forceinline__ void load_raw_b8(const CoefView &cv, uint32_t L, RawB8 &r)
+/* CAP: cap (wave-uniform) is the extent class of the block's whole row from the row-extent table (3: unknown).  Only the chunks a block
+ * of that class can hold anything in are fetched -- columns 0-1 for 1, 0-3 for 2, none for 0, whose flags byte is then not read either
+ * (a class below 3 says that no block of the row escaped) -- and the others stay what they were: nobody may read them. */
+template <bool CAP = false>
+__device__ __forceinline__ void load_raw_b8(const CoefView &cv, uint32_t L, RawB8 &r, [[maybe_unused]] int cap = 3)
 {
 	const uint8_t *base = cv.plane + ((size_t)(L >> 6) << 12) + ((size_t)(L & 63u) << 3);
-#pragma unroll
-	for (int k = 0; k < 8; ++k) {
+	if constexpr (CAP) {
 		typedef uint32_t u2v __attribute__((ext_vector_type(2)));
-		const u2v v = __builtin_nontemporal_load(reinterpret_cast<const u2v *>(base + (k << 9)));
-		r.h[k] = make_uint2(v.x, v.y);
+#define MIJ_CHUNK(k)                                                                                          \
+	{                                                                                                          \
+		const u2v v = __builtin_nontemporal_load(reinterpret_cast<const u2v *>(base + ((k) << 9)));            \
+		r.h[k] = make_uint2(v.x, v.y);                                                                          \
+	}
+		if (cap != 0) {
+			MIJ_CHUNK(0) MIJ_CHUNK(1)
+			if (cap >= 2) {
+				MIJ_CHUNK(2) MIJ_CHUNK(3)
+				if (cap >= 3) {
+					MIJ_CHUNK(4) MIJ_CHUNK(5) MIJ_CHUNK(6) MIJ_CHUNK(7)
+				}
+			}
+		}
+#undef MIJ_CHUNK
+	} else {
+#pragma unroll
+		for (int k = 0; k < 8; ++k) {
+			typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+			const u2v v = __builtin_nontemporal_load(reinterpret_cast<const u2v *>(base + (k << 9)));
+			r.h[k] = make_uint2(v.x, v.y);
+		}
 	}
 	r.dc = *reinterpret_cast<const uint16_t *>(cv.dc + 2u * (size_t)L);
 }
-/* classify the wavefront's loaded blocks and run the cheapest transform that covers them (not WIDE); returns the class */
-__device__ __forceinline__ int idct_raw_b8(const IdctK &K, const CoefView &cv, uint32_t L, const uint32_t *__restrict__ dq, const RawB8 &raw, uint2 (&rows)[8])
+/* block_class_b8 for a row whose class is at most cap < 3: the tests that can still fail, on the chunks that were loaded */
+__device__ __forceinline__ int block_class_b8_low(const uint2 (&h)[8], int cap)
+{
+	if (cap == 0)
+		return 0;
+	if (cap == 2) {
+		const uint32_t x01 = h[0].x | h[1].x, y01 = h[0].y | h[1].y, x23 = h[2].x | h[3].x, y23 = h[2].y | h[3].y;
+		const uint32_t bad2 = or3(x23 | y23, x01 & 0x00ff0000u, y01 & 0x0000ff00u);
+		if (__builtin_amdgcn_ballot_w64(bad2 != 0u) != 0ull)
+			return 2;
+	}
+	const uint32_t bad1 = or3(h[1].x, h[1].y, h[0].y & 0xffu);
+	return __builtin_amdgcn_ballot_w64(bad1 != 0u) != 0ull ? 1 : 0;
+}
+/* classify the wavefront's loaded blocks and run the cheapest transform that covers them (not WIDE); returns the class.  The class
+ * found is at most cap, so the transform reads no chunk that was not loaded. */
+template <bool CAP = false>
+__device__ __forceinline__ int idct_raw_b8(const IdctK &K, const CoefView &cv, uint32_t L, const uint32_t *__restrict__ dq, const RawB8 &raw, uint2 (&rows)[8], [[maybe_unused]] int cap = 3)
 {
 	const uint2 (&h)[8] = raw.h;
 	const uint32_t dc = raw.dc;
 	uint4 c[8];
 	int cls;
+		if constexpr (CAP)
+			cls = cap >= 3 ? block_class_b8(h) : block_class_b8_low(h, cap); /* cap: what load_raw_b8 was given */
+		else
 		cls = block_class_b8(h);
 		if (cls == 3) {
 			dequant_block_b8(cv, L, dq, h, dc, c);
@@ -676,9 +723,10 @@ __device__ __forceinline__ int idct_raw_b8(const IdctK &K, const CoefView &cv, u
 }
 
 /* One block per lane from either plane format through the cheapest transform that covers the wavefront's blocks.
- * Returns the class taken (wave-uniform).  count != 0 (wave-uniform): measurement, see MIJ_DEV_COUNT_CLASSES. */
-template <bool WIDE, bool B8>
-__device__ __forceinline__ int load_idct_block(const IdctK &K, const CoefView &cv, uint32_t L, const uint32_t *__restrict__ dq, uint2 (&rows)[8], int count)
+ * Returns the class taken (wave-uniform).  count != 0 (wave-uniform): measurement, see MIJ_DEV_COUNT_CLASSES.  cap: the row's class
+ * (load_raw_b8; compact planes that are not WIDE only). */
+template <bool WIDE, bool B8, bool CAP = false>
+__device__ __forceinline__ int load_idct_block(const IdctK &K, const CoefView &cv, uint32_t L, const uint32_t *__restrict__ dq, uint2 (&rows)[8], int count, [[maybe_unused]] int cap = 3)
 {
 	uint4 c[8];
 	int cls = 3;
@@ -687,8 +735,8 @@ __device__ __forceinline__ int load_idct_block(const IdctK &K, const CoefView &c
 		idct_block<WIDE, B8>(K, c, dq, rows);
 	} else if constexpr (B8) {
 		RawB8 raw;
-		load_raw_b8(cv, L, raw);
-		cls = idct_raw_b8(K, cv, L, dq, raw, rows);
+		load_raw_b8<CAP>(cv, L, raw, cap);
+		cls = idct_raw_b8<CAP>(K, cv, L, dq, raw, rows, cap);
 	} else {
 		load_block(cv.plane, L, c);
 		cls = block_class_i16(c);
@@ -1365,6 +1413,22 @@ __device__ __forceinline__ BandTask band_task(int m, int ww, int lane0, int nYw,
  * strip sits at compile-time constants from the first (+512 bytes in a chroma row, +1024 in a luma row).  The aligned and edge-fixed
  * vector of the upper chroma row and the luma dword of the row above an MCU row are carried in registers from the row pair before: a row
  * pair loads the lower chroma row only, and the save buffers and their copy loop are not used (but for the halo row of the prologue). */
+/* Row classes (compact planes that are not WIDE; A/B knob: -DMIJ_ROW_CLASSES=0 never reads the table).  coef + im.rc_off is the picture's
+ * row-extent table as the upload packs it for these kernels: one byte per MCU row, two bits a component -- the largest extent class of
+ * the row's blocks (luma: of block rows 2m and 2m+1), 3 where nobody knows (mij.h, "row-extent table").  A task's row is known from m
+ * and its component alone, so its class is wave-uniform and comes through scalar loads, two MCU rows ahead: rc_cur is MCU row m's byte,
+ * rc_nxt row m+1's -- the row whose first coefficient loads the last tasks of row m issue -- and row m+2's is taken at the top of row m
+ * from a window of eight rows' bytes, which is loaded once per eight rows (the scalar registers of these kernels are spilled to lanes,
+ * and a spill waits for its load).  The class decides how many chunks a task fetches (load_raw_b8) and caps the class test; no vector
+ * load waits for a loaded class.  The halo rows' classes are fetched in the prologue. */
+#ifndef MIJ_ROW_CLASSES
+#define MIJ_ROW_CLASSES 1
+#endif
+__device__ __forceinline__ uint32_t row_class_at(const uint8_t *__restrict__ tab, uint32_t idx)
+{
+	return (*reinterpret_cast<const uint32_t *>(tab + (idx & ~3u)) >> ((idx & 3u) * 8u)) & 0x3fu;
+}
+
 template <int NOUT, bool WIDE, bool B8, bool H2, int NT, bool SEG = false, bool PF = false, bool MARCH = false>
 __device__ __forceinline__ void fused_band(const DevImage *__restrict__ imgs, const WorkBand *__restrict__ work, const uint8_t *__restrict__ coef,
 														 uint8_t *__restrict__ outbase)
@@ -1414,6 +1478,19 @@ __device__ __forceinline__ void fused_band(const DevImage *__restrict__ imgs, co
 	KC.init();
 	const int count_classes = im.flags & MIJ_DEV_COUNT_CLASSES;
 
+	/* ---- row classes of MCU row mr (clamped to the picture: the rows asked for ahead of the band's last), packed two bits a component */
+	constexpr bool RC = MIJ_ROW_CLASSES && B8 && !WIDE;
+	[[maybe_unused]] auto rc_fetch = [&](int mr) -> uint32_t { return row_class_at(coef + im.rc_off, (uint32_t)min(max(mr, 0), im.mcu_y - 1)); };
+	[[maybe_unused]] uint64_t rc_win = 0; /* the bytes of the eight MCU rows around row m+2 */
+	[[maybe_unused]] auto rc_cap = [](uint32_t rc, int comp) -> int { return (int)((rc >> (2 * comp)) & 3u); };
+	[[maybe_unused]] uint32_t rc_top = 0x3fu, rc_bot = 0x3fu, rc_cur = 0x3fu, rc_nxt = 0x3fu; /* the halo rows above and below the band; rows m and m+1 */
+	if constexpr (RC) {
+		rc_top = rc_fetch((int)wk.m0 - 1);
+		rc_bot = rc_fetch((int)wk.m1);
+		rc_cur = rc_fetch((int)wk.m0);
+		rc_nxt = rc_fetch((int)wk.m0 + 1);
+	}
+
 	/* ---- chroma-only IDCT of block row mc, keeping sample row 7 (keep != 0) or 0 in dstCb/dstCr (halo rows) */
 	auto chroma_halo = [&](int mc, int keep, uint8_t *dstCb, uint8_t *dstCr) {
 		for (int ww = wave; ww < 2 * nCw; ww += NT / 64) {
@@ -1421,6 +1498,9 @@ __device__ __forceinline__ void fused_band(const DevImage *__restrict__ imgs, co
 			const int bx = (comp == 1 ? ww : ww - nCw) * 64 + lane;
 			if (bx < bwC) {
 				uint2 rows[8];
+				if constexpr (RC)
+					load_idct_block<WIDE, B8, true>(KI, comp == 1 ? cvCb : cvCr, (uint32_t)(mc * gbwC + bx0C + bx), im.dq[comp], rows, 0, rc_cap(keep ? rc_top : rc_bot, comp));
+				else
 				load_idct_block<WIDE, B8>(KI, comp == 1 ? cvCb : cvCr, (uint32_t)(mc * gbwC + bx0C + bx), im.dq[comp], rows, 0);
 				*reinterpret_cast<uint2 *>((comp == 1 ? dstCb : dstCr) + 8 * bx) = keep ? rows[7] : rows[0];
 			}
@@ -1640,8 +1720,10 @@ __device__ __forceinline__ void fused_band(const DevImage *__restrict__ imgs, co
 	 * NEXT task.  A task begins with the one wait for them and their copy into cur, issues the loads of the task behind it into nxt, and only
 	 * then classifies and transforms cur: nine loads are in flight under every transform.  The task behind a row's last task is the wave's
 	 * first task of the next MCU row, whose loads so have the barrier and the whole of phase B to arrive; behind the band's last task every
-	 * lane re-reads that task's first block (one cache line per load), which nobody uses.  So every task issues exactly nine loads -- none is
-	 * predicated, per lane or per wave, and no path reaches a wait with another number in flight.  A lane beyond the row's blocks reads the
+	 * lane re-reads that task's first block (one cache line per load), which nobody uses.  So every task issues its loads -- nine where the
+	 * row's class is 3 or unknown, and five, three or the DC word alone where the row-extent table says 2, 1 or 0 ("Row classes" above) --
+	 * under wave-uniform branches only: none is predicated per lane, and whatever their number the next task's one vmcnt(0) waits for all
+	 * of them, so no path reaches a wait with another task's loads in flight.  A lane beyond the row's blocks reads the
 	 * row's last block and only its LDS writes are dropped; the copies vote in the class ballot like the block they copy, so classes and
 	 * class counts are those of the plain loop.  (Two register sets taken in turn would save the copy, sixteen v_mov per task, but want a
 	 * second instance of the transforms: the compiler folds a set picked by a wave-uniform flag back into one set and a swap.) */
@@ -1659,11 +1741,21 @@ __device__ __forceinline__ void fused_band(const DevImage *__restrict__ imgs, co
 	if constexpr (PIPE) {
 		if (wave < ntask && m0 < m1) {
 			const BandTask t = task_of(m0, wave, lane);
+			if constexpr (RC)
+				load_raw_b8<true>(task_view(t.comp), t.L, nxt, rc_cap(rc_cur, t.comp));
+			else
 			load_raw_b8(task_view(t.comp), t.L, nxt);
 		}
 	}
 
 	for (int m = m0; m < m1; ++m) {
+		[[maybe_unused]] uint32_t rc_far = 0x3fu; /* row m+2's: asked for now, wanted when the next row begins */
+		if constexpr (RC) {
+			const uint32_t mf = (uint32_t)min(m + 2, im.mcu_y - 1);
+			if (m == m0 || (mf & 7u) == 0u)
+				rc_win = *reinterpret_cast<const uint64_t *>(coef + im.rc_off + (mf & ~7u));
+			rc_far = (uint32_t)(rc_win >> ((mf & 7u) * 8u)) & 0x3fu;
+		}
 		__syncthreads(); /* previous phase B (and the prologue) done with the planes / save buffers */
 		/* ---- phase A: IDCT of MCU row m, one block per lane, component uniform per wave; one call site for the three components
 		 * (the sparse-class transforms of load_idct_block are instantiated once per kernel) */
@@ -1680,9 +1772,16 @@ __device__ __forceinline__ void fused_band(const DevImage *__restrict__ imgs, co
 									 "+v"(nxt.h[4].x), "+v"(nxt.h[4].y), "+v"(nxt.h[5].x), "+v"(nxt.h[5].y), "+v"(nxt.h[6].x), "+v"(nxt.h[6].y), "+v"(nxt.h[7].x), "+v"(nxt.h[7].y),
 									 "+v"(nxt.dc));
 				const RawB8 cur = nxt;
+				if constexpr (RC)
+					load_raw_b8<true>(ncv, nt.L, nxt, rc_cap(nm == m ? rc_cur : rc_nxt, nt.comp));
+				else
 				load_raw_b8(ncv, nt.L, nxt);
 				uint2 rows[8];
-				const int cls = idct_raw_b8(KI, cv, t.L, im.dq[comp], cur, rows);
+				int cls;
+				if constexpr (RC)
+					cls = idct_raw_b8<true>(KI, cv, t.L, im.dq[comp], cur, rows, rc_cap(rc_cur, comp));
+				else
+				cls = idct_raw_b8(KI, cv, t.L, im.dq[comp], cur, rows);
 				if (count_classes && lane == 0)
 					atomicAdd(&g_idct_class[cls], 1ull);
 				if (i < nblk) {
@@ -1704,12 +1803,19 @@ __device__ __forceinline__ void fused_band(const DevImage *__restrict__ imgs, co
 				const int by = (comp == 0 && i >= bwY) ? 1 : 0, bx = i - by * bwY;
 				const int pitch = comp == 0 ? YP : CP;
 				const uint32_t L = SEG ? (uint32_t)(comp == 0 ? (2 * m + by) * gbwY + bx0Y + bx : m * gbwC + bx0C + bx) : (uint32_t)((comp == 0 ? 2 * m * bwY : m * bwC) + i);
+				if constexpr (RC)
+					load_idct_block<WIDE, B8, true>(KI, comp == 0 ? cvY : (comp == 1 ? cvCb : cvCr), L, im.dq[comp], rows, count_classes, rc_cap(rc_cur, comp));
+				else
 				load_idct_block<WIDE, B8>(KI, comp == 0 ? cvY : (comp == 1 ? cvCb : cvCr), L, im.dq[comp], rows, count_classes);
 				uint8_t *dst = (comp == 0 ? sY : (comp == 1 ? sCb : sCr)) + (8 * by) * pitch + 8 * bx;
 #pragma unroll
 				for (int r = 0; r < 8; ++r)
 					*reinterpret_cast<uint2 *>(dst + r * pitch) = rows[r];
 			}
+		}
+		if constexpr (RC) {
+			rc_cur = rc_nxt;
+			rc_nxt = rc_far;
 		}
 		__syncthreads();
 

@@ -19,6 +19,7 @@
 
 #include "mij.h"
 #include "mij_host.h"
+#include "mij_internal.h"
 #include "mij_kernels.h"
 #include "mij_scaled_kernels.h"
 #include "mij_entropy_kernels.h"
@@ -337,7 +338,17 @@ struct Slot {
 	int roi[4], reg_px[4], rect[4];
 	DevRoi win;
 	int work_items; /* of the last upload, on the slot's own family list (mij_batch_slot_work_items) */
+	/* the row-extent table (mij.h): a byte per block row, component after component; all 3 until a producer that saw every block of the
+	 * slot's rows hands its own in (mij_batch_set_row_classes), and 3 again whenever the staging is handed out.  Clones: their source's, at upload */
+	std::vector<uint8_t> rowcls;
 };
+static inline size_t row_class_count(const mij_image_desc &d)
+{
+	size_t n = 0;
+	for (int c = 0; c < d.ncomp; ++c)
+		n += (size_t)d.comp[c].bh;
+	return n;
+}
 static inline bool wants_region(const Slot &s) { return s.roi_on || s.roi_auto; }
 
 /* the stored picture of a slot: what every consumer of its pixels sees */
@@ -506,6 +517,12 @@ struct mij_batch {
 	/* per slot, max_images entries: the descriptors; the largest per-block L1 the pack kernel saw (MIJ_FLAG_L1_ON_DEVICE) and the windows
 	 * of the windowed kernels, both made by the first upload that needs them */
 	Buf<DevImage> imgs;
+	/* the slots' row-extent tables as the band kernels read them (DevImage.rc_off): laid out by every upload in pinned memory, as much as it
+	 * needs, and copied to the head of the coefficient arena -- rc_room bytes in front of the first slot's planes, room for a byte per
+	 * block row of whatever fits the arena (a block row is at least one block, 130 bytes of its tile; the kernels' form is a byte per MCU
+	 * row) and eight bytes of slack per slot */
+	Buf<uint8_t, BUF_PINNED> rowcls;
+	size_t rc_room = 0;
 	Buf<uint32_t> l1max;
 	Buf<DevRoi> roi;
 	Buf<Work4> work; /* the work lists: the pack list, then one range per launch */
@@ -622,7 +639,8 @@ extern "C" int mij_batch_create(mij_ctx *ctx, int max_images, size_t stage_bytes
 	if (e == hipSuccess && stage_bytes)
 		e = b->stage.alloc(stage_bytes);
 	if (e == hipSuccess && coef_bytes)
-		e = b->coef.alloc(coef_bytes);
+		e = b->coef.alloc(coef_bytes + (b->rc_room = align_up(coef_bytes / 130 + 8 * (size_t)max_images + 16, 4096)));
+	b->coef_used = b->rc_room;
 	if (e == hipSuccess && out_bytes)
 		e = b->out.alloc(out_bytes);
 	if (e == hipSuccess)
@@ -662,7 +680,8 @@ extern "C" int mij_batch_reset(mij_batch *b)
 	HIP_TRY(hipSetDevice(b->ctx->device));
 	HIP_TRY(hipStreamSynchronize(b->stream));
 	b->slots.clear();
-	b->stage_used = b->coef_used = b->out_used = 0;
+	b->stage_used = b->out_used = 0;
+	b->coef_used = b->rc_room;
 	b->uploaded = b->launched = false;
 	b->launches.clear();
 	b->f32_req.clear();
@@ -811,6 +830,7 @@ static int add_common(mij_batch *b, const mij_image_desc *d, int clone_of, bool 
 	s.arith = MIJ_ARITH_STB;
 	s.roi_on = s.roi_auto = s.reg = false;
 	s.work_items = 0;
+	s.rowcls.assign(row_class_count(*d), (uint8_t)3);
 	if (clone_of < 0) {
 		if (b->stage_used + cbytes > b->stage.cap) {
 			if (!lazy_stage)
@@ -868,11 +888,12 @@ extern "C" int16_t *mij_batch_coef(mij_batch *b, int slot, int comp)
 {
 	if (!batch_slot(b, slot))
 		return nullptr;
-	const Slot &s = b->slots[(size_t)slot];
+	Slot &s = b->slots[(size_t)slot];
 	if (comp < 0 || comp >= s.desc.ncomp || s.clone_of >= 0 || !b->stage.h || s.stage_off == MIJ_NO_STAGE) {
 		set_err(MIJ_E_ARG, "bad component, or slot has no staging of its own");
 		return nullptr;
 	}
+	std::fill(s.rowcls.begin(), s.rowcls.end(), (uint8_t)3); /* whoever asks for the staging is about to write it */
 	size_t off = s.stage_off;
 	for (int c = 0; c < comp; ++c)
 		off += mij_plane_elems((uint32_t)(s.desc.comp[c].bw * s.desc.comp[c].bh)) * sizeof(int16_t);
@@ -883,14 +904,56 @@ extern "C" uint8_t *mij_batch_stage_region(mij_batch *b, int slot, size_t *bytes
 {
 	if (!batch_slot(b, slot))
 		return nullptr;
-	const Slot &s = b->slots[(size_t)slot];
+	Slot &s = b->slots[(size_t)slot];
 	if (s.clone_of >= 0 || !b->stage.h || s.stage_off == MIJ_NO_STAGE) {
 		set_err(MIJ_E_ARG, "slot has no staging of its own");
 		return nullptr;
 	}
 	if (bytes)
 		*bytes = s.coef_bytes;
+	std::fill(s.rowcls.begin(), s.rowcls.end(), (uint8_t)3); /* whoever asks for the staging is about to write it */
 	return b->stage.h + s.stage_off;
+}
+
+extern "C" int mij_batch_set_row_classes(mij_batch *b, int slot, const uint8_t *classes, size_t n)
+{
+	Slot *s = batch_slot(b, slot);
+	if (!s)
+		return MIJ_E_ARG;
+	if (!classes || n != s->rowcls.size() || s->clone_of >= 0)
+		return set_err(MIJ_E_ARG, "mij_batch_set_row_classes: slot %d has %zu block rows of its own staging", slot, s->clone_of >= 0 ? (size_t)0 : s->rowcls.size());
+	for (size_t i = 0; i < n; ++i)
+		s->rowcls[i] = classes[i] < 3 ? classes[i] : (uint8_t)3;
+	b->uploaded = b->launched = false;
+	return MIJ_OK;
+}
+
+extern "C" int mij_batch_fetch_row_classes_packed(mij_batch *b, int slot, uint8_t *dst, size_t cap)
+{
+	const Slot *s = batch_slot(b, slot);
+	if (!s)
+		return MIJ_E_ARG;
+	if (!b->uploaded)
+		return set_err(MIJ_E_STATE, "mij_batch_fetch_row_classes_packed before mij_batch_upload");
+	const size_t n = (size_t)s->desc.mcu_y;
+	if (dst && cap >= n) {
+		HIP_TRY(hipSetDevice(b->ctx->device));
+		const int rc = d2h_bounced(b->ctx, b->stream, dst, b->coef.d + s->dev.rc_off, n);
+		if (rc != MIJ_OK)
+			return rc;
+	}
+	return (int)n;
+}
+
+extern "C" int mij_batch_slot_row_classes(const mij_batch *b, int slot, uint8_t *dst, size_t cap)
+{
+	const Slot *s = batch_slot(b, slot);
+	if (!s)
+		return MIJ_E_ARG;
+	const Slot &src = s->clone_of >= 0 ? b->slots[(size_t)s->clone_of] : *s; /* what the next upload gives a clone */
+	if (dst && cap >= src.rowcls.size())
+		memcpy(dst, src.rowcls.data(), src.rowcls.size());
+	return (int)src.rowcls.size();
 }
 
 extern "C" int mij_batch_coef_format(const mij_batch *b) { return b ? b->coef_fmt : MIJ_COEF_COMPACT; }
@@ -2000,6 +2063,35 @@ static int lay_out_work(mij_batch *b, const Plan &p)
 			pos += L.size();
 		}
 	const size_t n = b->slots.size();
+	/* the row-extent tables as the band kernels read them: a byte per MCU row, two bits a component (the largest class of the component's
+	 * block rows in that MCU row), each slot's at a multiple of eight bytes with eight bytes of room behind the last (the kernels read
+	 * the aligned dword or two around a byte): a clone's is its source's, a rejected slot's is never read */
+	size_t rc_bytes = 0;
+	for (size_t i = 0; i < n; ++i) {
+		b->slots[i].dev.rc_off = (uint32_t)rc_bytes;
+		rc_bytes += align_up((size_t)b->slots[i].desc.mcu_y, 8);
+	}
+	rc_bytes += 8;
+	if (rc_bytes > b->rc_room || rc_bytes > 0xffffffffull) /* cannot happen: see rc_room */
+		return set_err(MIJ_E_NOMEM, "row-extent tables beyond their room in the coefficient arena");
+	if (rc_bytes > b->rowcls.cap) {
+		HIP_TRY(hipStreamSynchronize(b->stream)); /* an earlier upload's copy may still read the old one */
+		HIP_TRY(b->rowcls.alloc(rc_bytes + rc_bytes / 2 + 64));
+	}
+	memset(b->rowcls.h, 0xff, rc_bytes);
+	for (size_t i = 0; i < n; ++i) {
+		const Slot &s = b->slots[i], &src = s.clone_of >= 0 ? b->slots[(size_t)s.clone_of] : s;
+		uint8_t *row = b->rowcls.h + s.dev.rc_off;
+		size_t at = 0;
+		for (int c = 0; c < s.desc.ncomp && at + (size_t)s.desc.comp[c].bh <= src.rowcls.size(); at += (size_t)s.desc.comp[c].bh, ++c)
+			for (int m = 0; m < s.desc.mcu_y; ++m) {
+				uint8_t cls = 0;
+				for (int v = 0; v < s.desc.comp[c].v; ++v)
+					cls = std::max(cls, src.rowcls[at + (size_t)(m * s.desc.comp[c].v + v)]);
+				row[m] = (uint8_t)((row[m] & ~(3u << (2 * c))) | ((unsigned)(cls & 3u) << (2 * c)));
+			}
+	}
+	HIP_TRY(copy_table(b->coef.d, b->rowcls.h, rc_bytes, b->stream));
 	for (size_t i = 0; i < n; ++i)
 		b->imgs.h[i] = b->slots[i].dev;
 	HIP_TRY(copy_table(b->imgs.d, b->imgs.h, sizeof(DevImage) * n, b->stream));

@@ -456,6 +456,24 @@ int mij_batch_slot_pipelined(const mij_batch *b, int slot);
 /* tests: 1 when that launch runs k_fused420m, the pipelined twin whose phase B marches down its lanes' own strips: a pipelined list of which every
  * picture has rows of whole dwords (four channels, or a width that is a multiple of four) of at most 2048 pixels; 0 otherwise */
 int mij_batch_slot_marched(const mij_batch *b, int slot);
+/*
+ * Row-extent table: library-internal state of a slot, beside its coefficient planes and not part of their format.  One byte per block
+ * row, component after component (comp[c].bh bytes each): the largest extent class over the row's blocks -- 0 DC only, 1 non-zero
+ * coefficients inside the top-left 2 x 2, 2 inside the 4 x 4, 3 anything, an escaped block, a stream that needs MIJ_FLAG_WIDE_IDCT, or
+ * simply unknown.  Every slot starts as all 3, handing out its staging (mij_batch_stage_region, mij_batch_coef) makes it all 3 again,
+ * and only a producer inside the library that saw every block of the slot's rows lowers entries, after it has written the staging
+ * (csrc/mij_internal.h; not part of this interface): the host walk of the batch front ends (mjh_decode_batch*) does for baseline files.
+ * mij_batch_upload sends the table with the slot and gives a clone its source's; the 4:2:0 / 4:4:0 band kernels fetch only the
+ * coefficient chunks a row of that class can hold anything in (mij_kernels.h, "Row classes").  A table that claims less than the
+ * planes hold changes pixels: staging written from outside keeps all 3.
+ * tests: mij_batch_slot_row_classes copies the table the next upload sends (a clone's: its source's) into dst when cap allows and
+ * returns its length.
+ */
+int mij_batch_slot_row_classes(const mij_batch *b, int slot, uint8_t *dst, size_t cap);
+/* tests: the table as the last upload put it on the device for the band kernels, copied back from there: one byte per MCU row, bits 2c and
+ * 2c+1 the largest class of component c's block rows in that MCU row (bits of components the picture does not have read 3); returns
+ * mcu_y.  MIJ_E_STATE before upload. */
+int mij_batch_fetch_row_classes_packed(mij_batch *b, int slot, uint8_t *dst, size_t cap);
 /* The format new coefficient planes of this batch get in HBM: MIJ_COEF_COMPACT (default; environment
  * MIJ_COEF_FORMAT=int16 flips the default) or MIJ_COEF_INT16.  Applies to slots added or uploaded afterwards. */
 int mij_batch_set_coef_format(mij_batch *b, int fmt);

@@ -43,6 +43,15 @@ int mjh_decode_memory(const uint8_t *buf, int len, int req_comp, mij_image_desc 
  * as mjh_decode_memory.  The reference's block decoder being restated either way: codec/jpeg.c:308-370.
  */
 int mjh_decode_memory_fmt(const uint8_t *buf, int len, int req_comp, mij_image_desc *desc, uint8_t *region, size_t region_bytes, int want_compact, const char **reason);
+/*
+ * The same, and the picture's row-extent table (mij.h, "row-extent table") into row_classes: one byte per block row, component
+ * after component, row_classes_bytes >= the sum of desc->comp[c].bh (MJH_ROW_CLASSES_MAX always suffices).  A baseline file walked into
+ * compact planes gets the classes the walk saw -- folded into its block loop from the positions it writes -- unless the stream needs
+ * MIJ_FLAG_WIDE_IDCT; everything else (progressive files, int16 staging) gets 3 throughout.  row_classes may be NULL.
+ */
+#define MJH_ROW_CLASSES_MAX (4 * 8200)
+int mjh_decode_memory_rows(const uint8_t *buf, int len, int req_comp, mij_image_desc *desc, uint8_t *region, size_t region_bytes, int want_compact, uint8_t *row_classes,
+									size_t row_classes_bytes, const char **reason);
 
 /* Header parse + extraction of the entropy segment for the GPU entropy stage (mij.h: mjg_scan,
  * mij_batch_add_stream).  Returns 1: *scan filled, the segment without its 0xFF00 stuffing written to stream
